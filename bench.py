@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- megapixels/s of the full film pipeline (neg + print + grain + halation + MTF).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg4_100mp|cfg3_45mp|cfg2_24mp|cfg5_batch]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg4_100mp|cfg3_45mp|cfg2_24mp|cfg5_batch] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 (`--gpus N` > 1 without a launcher: bench.py starts its N ranks itself, as a child process running torch.distributed.run.)
 
@@ -40,6 +40,8 @@ if ROOT not in sys.path:
 FP64_PEAK_TFLOPS = 78.6   # MI355X fp64 vector peak (FMA = 2 flop): 256 CU x 4 SIMD x 16 lanes x 2 x 2.4 GHz
 HBM_PEAK_GBPS = 8000.0    # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured with a float4 copy)
 GRAIN_SEED = 20260630
+DUMP_BYTES = 64 << 20     # --dump-outputs: at most this many bytes of .npy files in all
+DUMP_SEED = 20261015      # --dump-outputs: the rows sampled from a frame larger than DUMP_BYTES
 BASELINE_METRIC = "megapixels/sec full film pipeline (neg+print+grain+halation+MTF), 100MP frame"
 METRICS = {
     "cfg4_100mp": BASELINE_METRIC,
@@ -126,6 +128,32 @@ def self_launch(n: int) -> int:
     return subprocess.run(cmd).returncode
 
 
+def dump_outputs(path: str, out, H: int, r0: int, rank: int, world: int, batch: bool) -> None:
+    """--dump-outputs: what the last timed step handed its caller -- this rank's (rows, W, 3) output frame (cfg5_batch: the last
+    frame of the step), as float32 -- written to `path`.  A frame larger than DUMP_BYTES is sampled by whole rows drawn with a
+    fixed seed (the first and last row included): the same rows on every run with the same arguments.
+    output_rows.npy holds those rows, output_rows_index.npy their row numbers in the frame (float64).  N > 1: every rank writes
+    its own two files with a _rank<r> suffix; row-sharded, the sample is drawn over the whole frame's rows and each rank
+    keeps the ones it rendered; frame-per-GPU, every rank samples its own frame from a 1/N share of the bytes."""
+    import numpy as np
+    import torch
+
+    W = out.shape[1]
+    budget = DUMP_BYTES // (world if batch else 1) - 4096  # (4096: the two .npy headers, generously)
+    n = min(H, budget // (W * 3 * 4 + 8))  # a row of float32 output + its float64 row number
+    if n >= H:
+        rows = np.arange(H)
+    else:
+        drawn = np.random.default_rng(DUMP_SEED).choice(np.arange(1, H - 1), n - 2, replace=False)
+        rows = np.sort(np.concatenate(([0, H - 1], drawn)))
+    mine = rows[(rows >= r0) & (rows < r0 + out.shape[0])]
+    sample = out.index_select(0, torch.as_tensor(mine - r0, device=out.device)).float().cpu().numpy()
+    suffix = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, f"output_rows{suffix}.npy"), sample)
+    np.save(os.path.join(path, f"output_rows_index{suffix}.npy"), mine.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -167,7 +195,12 @@ def main():
     ap.add_argument("--parse-only", action="store_true",
                     help="print the parsed arguments as JSON and exit without touching torch or the GPU (tests/test_bench_host.py checks "
                          "the command lines of tools/first_multi_gpu.sh with it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one handed its caller to DIR as float32 .npy files: a fixed, "
+                         "seeded sample of the output frame's rows (at most 64 MB in all) and their row numbers (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.parse_only:
         print(json.dumps(vars(args)))
         return
@@ -319,6 +352,8 @@ def main():
     # which scratch element the halation's passes of the LAST TIMED frame took (r2f_render chooses on the device, frame by frame);
     # asked now, before the eager breakdown steps overwrite the frame block
     scratch_choice = proc.ctx.frame_exposure_range() if effects else None
+    if args.dump_outputs:  # before anything below renders into `out` again
+        dump_outputs(args.dump_outputs, out, H, r0, rank, world, batch)
     if use_dist:
         t = torch.tensor([dt], dtype=torch.float64, device=frame.device if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

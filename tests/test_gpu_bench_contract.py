@@ -52,3 +52,41 @@ def test_default_bench_line_carries_the_contract_fields():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["unit"] == "MP/s" and c["cores"] >= 1 and c["value"] > 0 and isinstance(c["sample"], str)
     assert d["value"] / c["value"] > 100  # a reported ratio, not the target -- but the GPU path must not be the CPU path
+
+
+def test_dump_outputs_hold_the_last_timed_step_and_repeat(tmp_path):
+    """--dump-outputs: rows of what the LAST timed step handed its caller, float32, within 64 MB, the same from run to run with the
+    same arguments.  cfg3_45mp draws a new grain seed every frame, so the rows are checked against the frame rendered here with
+    that step's seed (2 warm-up frames -- the graph is captured on the second -- then 2 timed ones: GRAIN_SEED + 4)."""
+    import numpy as np
+    import torch
+
+    from raw2film_amd import HipProcessor, filmstock
+    from raw2film_amd.synthetic import CONFIGS, synthetic_frame_device
+
+    args = ["--config", "cfg3_45mp", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-breakdown", "--no-pcie", "--no-alone"]
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert res.returncode == 0, res.stderr[-2000:]
+        assert sum(f.stat().st_size for f in d.glob("*.npy")) <= 64 << 20
+        dumps.append({f.stem: np.load(f) for f in d.glob("*.npy")})
+    assert sorted(dumps[0]) == sorted(dumps[1]) == ["output_rows", "output_rows_index"]
+    for k in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k])
+    W, H = CONFIGS["cfg3_45mp"]
+    rows, idx = dumps[0]["output_rows"], dumps[0]["output_rows_index"].astype(np.int64)
+    assert rows.dtype == np.float32 and rows.shape == (len(idx), W, 3) and idx[0] == 0 and idx[-1] == H - 1 and len(idx) < H
+
+    stocks = filmstock.builtin_stocks()
+    neg, prt = stocks["Kodak Portra 400"], stocks["Kodak 2383"]
+    settings = dict(print_film=prt, frame_width=36, frame_height=24, exp_kelvin=6000, color_masking=1.0, halation=True, halation_size=1.0,
+                    halation_green_factor=0.3, halation_intensity=1.0, sharpness=True, sharpening_strength=0.0, grain=2)  # bench.py's
+    frame = synthetic_frame_device(H, W, seed=1234, device="cuda:0")
+    proc = HipProcessor(device=0)
+    want = proc.process_array(frame, neg, 6, 0.4, colorspace="linear-rec709", seed=20260630 + 4, return_float=True, output="device",
+                              **settings)
+    np.testing.assert_array_equal(rows, want[torch.as_tensor(idx, device=want.device)].cpu().numpy())
+    proc.close()

@@ -2,8 +2,9 @@
     python tools/range_probe.py
 """
 import os, sys, torch, numpy as np
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
-sys.path.insert(0, os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "tests"))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from raw2film_amd import HipProcessor, filmstock, stencils
 from raw2film_amd.hip_processor import REC709_TO_XYZ
 W, H = 12288, 8192
