@@ -18,18 +18,56 @@ rendering something else.
 
 from __future__ import annotations
 
+import inspect
 import math
 import random
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 from . import _lib, filmstock, geometry, stencils
 from .context import LOG_EPS, LUT3D_SCALE, HipContext
+from .results import ResultBuffers
 
 REC709_TO_XYZ = np.array(  # data.py:128-135
     [[0.4124564, 0.3575761, 0.1804375], [0.2126729, 0.7151522, 0.0721750], [0.0193339, 0.1191920, 0.9503041]],
     dtype=np.float32,
 )
+
+
+def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canvas_mode="No"):
+    """Why a phase-1 payload cannot stream through the pipeline in row bands, or None (its render's stages have the last word:
+    plan_bands).  `shape`, `dtype`: of its frame as a tensor (_payload_tensor: "torch.float32", or "torch.int16" for uint16)."""
+    is_u16 = dtype == "torch.int16"  # LibRaw's 16-bit output: converted band by band on the device (raw_conversion.py:50-52)
+    if (payload.get("warp") or payload.get("resize_to") or payload.get("upscale_to") or payload.get("chroma_nr")
+            or payload.get("canvas_resolution") or canvas_mode != "No" or on_device or len(shape) != 3
+            or int(shape[2]) not in (3, 4) or math.prod(shape) < (1 << 24) or dtype not in ("torch.float32", "torch.int16")
+            or (payload.get("u16_factor") is None) == is_u16):  # (a uint16 frame comes with its exposure factor, a float one without)
+        return ("a device pre-path, a canvas, or a frame below 16.7 M samples: " + ", ".join(
+            f"{k} = {payload.get(k)!r}" for k in ("warp", "resize_to", "upscale_to", "chroma_nr", "canvas_resolution", "u16_factor",
+                                                  "clip_on_device")) + f", frame {tuple(shape)} {dtype}")
+    fr = payload.get("final_resolution") if final_scaling == "cpu" else None  # (cpu_processor.py:411-412: the final scaling)
+    if fr is not None and (int(fr[0]), int(fr[1])) != (int(shape[0]), int(shape[1])):
+        return f"the finished frame is scaled to {fr}"
+    return None
+
+
+def plan_bands(H, flags, ha, ma, bands, taper):
+    """(row bounds, None) of the bands a frame of H rows streams in, or (None, why it cannot).  `flags`: prepare()'s; `ha`, `ma`:
+    (rows above, rows below) the halation / MTF stencils read, (0, 0) for a stage that does not run."""
+    if flags & _lib.F_BURN:
+        return None, "highlight burn (a function of the whole grained frame)"
+    floor_rows = max(2 * max(ha + ma) + 2, 64)  # a band holds its neighbours' halo (and is worth a launch)
+    n = min(int(bands), max(H // 512, 2))
+    while n > 1 and H // n < floor_rows:
+        n -= 1
+    if n < 2:
+        return None, f"{n} band(s) of {H} rows above the stencils' reach {ha} + {ma}"
+    bounds = [H * i // n for i in range(n + 1)]
+    # the last bands are the ones nothing hides (their stencil stages, tail and download run behind the last byte of the upload):
+    # the final `taper` of them are halved while they stay above the stencils' reach (100 MP: 23.26 -> 22.73 ms with 2)
+    cut = [(bounds[i] + bounds[i + 1]) // 2 for i in range(max(n - int(taper), 0), n) if bounds[i + 1] - bounds[i] >= 2 * floor_rows]
+    return sorted(set(bounds + cut)), None
 
 
 class PendingFrame:
@@ -70,6 +108,7 @@ class HipProcessor:
         self.lenses = lenses
         self.payload_alpha = bool(payload_alpha)
         self.result_buffers = int(result_buffers)  # 0: process() returns a fresh array; n: views of n pinned buffers in turn (_download)
+        self._results = ResultBuffers(lambda shape: torch.empty(shape, dtype=torch.uint8, pin_memory=True))
         # process(host array, cache=False) with pinned result buffers streams a large frame through the pipeline in row bands while it
         # is still arriving (_process_streamed): at most this many, of at least 512 rows each (100 MP: 16 bands of 512 rows = 23.3 ms
         # against 24.7 with 8, 27.2 with 4, 24.9 with 24 -- tools/stream_bands_probe.py); 0: upload, render, download one after the other
@@ -92,10 +131,7 @@ class HipProcessor:
         self.last_output = None  # device uint8 (H, W, 3) of the last process()/process_preloaded(): histogram source
 
     def close(self):
-        pool = getattr(self, "_copy_pool", None)
-        if pool is not None:
-            pool.shutdown(wait=True)
-            self._copy_pool = None
+        self._results.close()
         self._stream_bufs = None
         self._texture = None  # the frame kept on the device for re-renders
         self._texture_src = None
@@ -366,6 +402,11 @@ class HipProcessor:
         dtype, address and a checksum of up to 32 evenly spaced rows -- an edit confined to other rows is NOT seen: pass
         cache=False after a partial in-place edit, or `src_version`, any hashable token of the caller's that changes whenever
         the buffer's content does and then replaces the checksum)."""
+        settings = dict(locals())  # every keyword of the signature (the unknown ones in `_` aside), named nowhere else
+        for k in ("self", "src", "negative_film", "grain_size", "grain_sigma", "dst_texture", "histogram_texture", "_"):
+            del settings[k]
+        # load_image_texture's share; prepare() and the render take what they need of all of them and swallow the rest
+        load = {k: settings[k] for k in _LOAD_KEYWORDS}
         if dst_texture is not None:
             self._check_texture(dst_texture, "dst_texture")
         if histogram_texture is not None:
@@ -381,46 +422,18 @@ class HipProcessor:
         elif (not cache and self.stream_bands > 1 and dst_texture is None and isinstance(src, np.ndarray) and src.size >= (1 << 24)
               and not rotation and not chroma_nr and canvas_mode == "No" and not highlight_burn):
             # a large host frame that is uploaded for this one render: streamed through the pipeline in row bands while it arrives
-            res = self._process_streamed(
-                src, negative_film, grain_size, grain_sigma,
-                load=dict(cam=cam, lens=lens, lens_correction=lens_correction, frame_width=frame_width, frame_height=frame_height,
-                          rotation=rotation, zoom=zoom, rotate_times=rotate_times, flip=flip, resolution=resolution, half_size=half_size,
-                          cache=cache, chroma_nr=chroma_nr, max_scale=max_scale, canvas_mode=canvas_mode, canvas_scale=canvas_scale,
-                          canvas_ratio=canvas_ratio, exposure=exposure, metadata=metadata),
-                print_film=print_film, exp_comp=exp_comp, red_light=red_light, green_light=green_light, blue_light=blue_light,
-                projector_kelvin=projector_kelvin, shadow_comp=shadow_comp, sat_adjust=sat_adjust, gamma_func=gamma_func,
-                exp_kelvin=exp_kelvin, tint=tint, inversion_gamma=inversion_gamma, idealized_curve=idealized_curve, inversion=inversion,
-                push_pull=push_pull, white_balance=white_balance, white_clip=white_clip, icc_transform=icc_transform,
-                frame_width=frame_width, frame_height=frame_height, halation_intensity=halation_intensity, halation=halation,
-                halation_size=halation_size, halation_green_factor=halation_green_factor, sharpness=sharpness,
-                sharpening_strength=sharpening_strength, sharpening_sigma=sharpening_sigma, grain=grain, highlight_burn=highlight_burn,
-                burn_scale=burn_scale, color_masking=color_masking, seed=seed)
+            res = self._process_streamed(src, negative_film, grain_size, grain_sigma, load, settings)
             if res is not None:
                 return res
         # GpuProcessor.load_image_texture (gpu_processor.py:655-719): the pre-processed frame stays on the device while the
         # load parameters do not change -- a re-render with other film settings neither prepares nor uploads it again
-        self.load_image_texture(
-            src, cam, lens, lens_correction, frame_width, frame_height, rotation, zoom, rotate_times, flip, resolution,
-            half_size, cache, chroma_nr, max_scale, canvas_mode, canvas_scale, canvas_ratio, exposure=exposure, metadata=metadata,
-            src_version=src_version,
-        )
+        self.load_image_texture(src, **load)
         image, layout, payload = self._texture
         if prof:
             self._torch.cuda.synchronize(self.device)
             t_loaded = time.perf_counter()
-        out_u8 = self._render_prepared(
-            image, layout, payload, negative_film, grain_size, grain_sigma, dst_texture, histogram_texture, "cpu",
-            print_film=print_film, exp_comp=exp_comp,
-            red_light=red_light, green_light=green_light, blue_light=blue_light, projector_kelvin=projector_kelvin,
-            shadow_comp=shadow_comp, sat_adjust=sat_adjust, gamma_func=gamma_func, exp_kelvin=exp_kelvin, tint=tint,
-            inversion_gamma=inversion_gamma, idealized_curve=idealized_curve, inversion=inversion, push_pull=push_pull,
-            white_balance=white_balance, white_clip=white_clip, icc_transform=icc_transform, frame_width=frame_width,
-            frame_height=frame_height, halation_intensity=halation_intensity, halation=halation,
-            halation_size=halation_size, halation_green_factor=halation_green_factor, sharpness=sharpness,
-            sharpening_strength=sharpening_strength, sharpening_sigma=sharpening_sigma, grain=grain,
-            highlight_burn=highlight_burn, burn_scale=burn_scale, color_masking=color_masking, seed=seed,
-            canvas_mode=canvas_mode, canvas_scale=canvas_scale, canvas_ratio=canvas_ratio,
-        )
+        out_u8 = self._render_prepared(image, layout, payload, negative_film, grain_size, grain_sigma, dst_texture, histogram_texture,
+                                       "cpu", **settings)
         if prof:
             self._torch.cuda.synchronize(self.device)
             t_rendered = time.perf_counter()
@@ -526,22 +539,20 @@ class HipProcessor:
             # upload -- the frame goes up in row chunks on a copy stream and every chunk is clamped on the launch stream while the
             # next one travels, so that of its 2.4 GB pass (0.5 ms at 100 MP) only the last chunk's share is left behind the copy
             torch = self._torch
-            if getattr(self, "_up_stream", None) is None:
-                self._up_stream = torch.cuda.Stream(device=self.device)
-                self._down_stream = torch.cuda.Stream(device=self.device)
+            up, _ = self._copy_streams()
             compute = torch.cuda.current_stream(self.device)
             image = torch.empty(host.shape, dtype=host.dtype, device=self.device)
-            self._up_stream.wait_stream(compute)  # (the block may have been another frame's a moment ago)
+            up.wait_stream(compute)  # (the block may have been another frame's a moment ago)
             rows = int(host.shape[0])
             step = -(-rows // 8)
             for a0 in range(0, rows, step):
                 a1 = min(a0 + step, rows)
-                with torch.cuda.stream(self._up_stream):
+                with torch.cuda.stream(up):
                     image[a0:a1].copy_(host[a0:a1], non_blocking=True)
-                    arrived = self._up_stream.record_event()
+                    arrived = up.record_event()
                 compute.wait_event(arrived)
                 image[a0:a1].clamp_(0.0, 65504.0)
-            image.record_stream(self._up_stream)
+            image.record_stream(up)
             cpu_payload = dict(cpu_payload, clip_on_device=False)
         else:
             image = host.to(self.device, non_blocking=True)  # HOST -> DEVICE, the reference's write_texture
@@ -577,7 +588,7 @@ class HipProcessor:
                                        histogram_texture, final_scaling, **settings)
         return None if out_u8 is None else self._download(out_u8)  # DEVICE -> HOST, the reference's read_texture/map_sync
 
-    def _process_streamed(self, src, negative_film, grain_size, grain_sigma, *, load, **settings):
+    def _process_streamed(self, src, negative_film, grain_size, grain_sigma, load, settings):
         """process() of a large host frame that is uploaded for this one render (cache=False: the GUI's export calls,
         gui.py:2374,2458,2479): the frame goes through the pipeline in `stream_bands` row bands WHILE IT ARRIVES -- band k is clamped and taken through S0 + S1
         as soon as it is on the device, the halation of band k - 1 follows (its stencil reads the first rows of band k), then the
@@ -592,11 +603,7 @@ class HipProcessor:
         Returns None when the frame does not qualify (the caller then takes the one-after-the-other path): a device pre-path
         (rotation, chroma NR, scaling), a canvas, a highlight burn (a function of the whole grained frame), a small frame.
         The two-phase API's device phase (process_preloaded, submit_preloaded: batch export) streams its payload the same way."""
-        payload = self.extract_image_data_cpu(
-            src, load["cam"], load["lens"], load["lens_correction"], load["frame_width"], load["frame_height"], load["rotation"],
-            load["zoom"], load["rotate_times"], load["flip"], load["resolution"], load["half_size"], load["cache"], load["chroma_nr"],
-            load["max_scale"], load["canvas_mode"], load["canvas_scale"], load["canvas_ratio"], exposure=load["exposure"],
-            metadata=load["metadata"], _internal=True)
+        payload = self.extract_image_data_cpu(src, **load, _internal=True)
         res = self._stream_payload(payload, negative_film, grain_size, grain_sigma, "cpu", **settings)
         # (should the frame not qualify, load_image_texture takes the payload from here)
         self._stash_payload = payload if res is None else None
@@ -606,276 +613,151 @@ class HipProcessor:
         """A phase-1 payload (extract_image_data_cpu) through the pipeline in row bands while it arrives: see _process_streamed.
         Returns the uint8 frame, or None (with `stream_rejected` saying why) when the payload does not qualify."""
         host = self._payload_tensor(payload)
-        torch = self._torch
-        is_u16 = host.dtype == torch.int16  # LibRaw's 16-bit output: converted band by band on the device (raw_conversion.py:50-52)
-        if (payload.get("warp") or payload.get("resize_to") or payload.get("upscale_to") or payload.get("chroma_nr")
-                or payload.get("canvas_resolution") or settings.get("canvas_mode", "No") != "No" or host.is_cuda or host.dim() != 3
-                or int(host.shape[2]) not in (3, 4) or host.numel() < (1 << 24)
-                or (host.dtype not in (torch.float32, torch.int16))
-                or (payload.get("u16_factor") is None if is_u16 else payload.get("u16_factor") is not None)):
-            self.stream_rejected = ("a device pre-path, a canvas, or a frame below 16.7 M samples: " + ", ".join(
-                f"{k} = {payload.get(k)!r}" for k in ("warp", "resize_to", "upscale_to", "chroma_nr", "canvas_resolution", "u16_factor",
-                                                      "clip_on_device")) + f", frame {tuple(host.shape)} {host.dtype}")
+        self.stream_rejected = stream_rejection(payload, tuple(host.shape), str(host.dtype), host.is_cuda, final_scaling,
+                                                settings.get("canvas_mode", "No"))
+        if self.stream_rejected is not None:
             return None
         H, W = int(host.shape[0]), int(host.shape[1])
-        fr = payload.get("final_resolution") if final_scaling == "cpu" else None  # (cpu_processor.py:411-412: the final scaling)
-        if fr is not None and (int(fr[0]), int(fr[1])) != (H, W):
-            self.stream_rejected = f"the finished frame is scaled to {fr}"
-            return None
-        ctx = self.ctx
         params = self.prepare(negative_film, grain_size, grain_sigma, (W, H), **settings)
-        flags = int(params.flags)
-        hal, mtf, grain = bool(flags & _lib.F_HALATION), bool(flags & _lib.F_MTF), bool(flags & _lib.F_GRAIN)
-        if flags & _lib.F_BURN:
-            self.stream_rejected = "highlight burn (a function of the whole grained frame)"
-            return None
+        hal, mtf = bool(params.flags & _lib.F_HALATION), bool(params.flags & _lib.F_MTF)
         ha = self._halation_reach if hal else (0, 0)
         ma = self._mtf_reach if mtf else (0, 0)
-        n = min(int(self.stream_bands), max(H // 512, 2))
-        while n > 1 and H // n < max(2 * max(ha + ma) + 2, 64):  # a band holds its neighbours' halo (and is worth a launch)
-            n -= 1
-        if n < 2:
-            self.stream_rejected = f"{n} band(s) of {H} rows above the stencils' reach {ha} + {ma}"
+        bounds, self.stream_rejected = plan_bands(H, int(params.flags), ha, ma, self.stream_bands, self.stream_taper)
+        if bounds is None:
             return None
-        self.stream_rejected = None
-        bounds = [H * i // n for i in range(n + 1)]
-        # the last bands are the ones nothing hides (their stencil stages, tail and download run behind the last byte of the upload):
-        # the final `stream_taper` of them are halved while they stay above the stencils' reach (100 MP: 23.26 -> 22.73 ms with 2)
-        floor_rows = max(2 * max(ha + ma) + 2, 64)
-        cut = [(bounds[i] + bounds[i + 1]) // 2 for i in range(max(n - int(self.stream_taper), 0), n)
-               if bounds[i + 1] - bounds[i] >= 2 * floor_rows]
-        bounds = sorted(set(bounds + cut))
-        n = len(bounds) - 1
-        bufs = getattr(self, "_stream_bufs", None)
-        chans = 3 if is_u16 else int(host.shape[2])  # (a payload with upstream's constant alpha plane, gpu_processor.py:765: 4)
-        if bufs is None or bufs["shape"] != (H, W, chans) or bufs["mtf"] != mtf:
-            def planes():
-                return torch.empty((3, H, W), dtype=torch.float32, device=self.device)
+        bufs = self._stream_buffers(host, mtf)
+        p = _lib.Params.from_buffer_copy(params)
+        p.flags |= _lib.F_FRAME_RESIDENT  # the seed is written once, here; the stage calls read it from the frame block
+        self.ctx.write_frame_params(p)     # (and the exposure-range record starts empty)
+        sink = self._results.sink((H, W, 3), self.result_buffers, lease=self._lease_result)
+        try:
+            self._run_bands(host, payload, p, bounds, bufs, ha, ma, sink)
+        except BaseException:
+            # a stage call refused (or the caller interrupted): let the queued work drain, hand a lent buffer back, pass it on
+            self._torch.cuda.synchronize(self.device)
+            sink.abandon()
+            raise
+        # (the frame kept on the device for re-renders -- a preview's, typically -- is left alone: an export in between does not cost
+        # the preview its cached frame, which the one-after-the-other path has to overwrite because it works in it)
+        self.last_output = bufs["u8"]
+        return sink.finish()
 
+    def _stream_buffers(self, host, mtf):
+        """The device buffers a streamed frame works in (kept for the next frame of the same kind): `host` is its payload tensor."""
+        torch = self._torch
+        H, W = int(host.shape[0]), int(host.shape[1])
+        chans = 3 if host.dtype == torch.int16 else int(host.shape[2])  # (a payload with upstream's alpha plane, gpu_processor.py:765: 4)
+        bufs = getattr(self, "_stream_bufs", None)
+        if bufs is None or bufs["shape"] != (H, W, chans) or bufs["mtf"] != mtf:
             bufs = self._stream_bufs = {"shape": (H, W, chans), "mtf": mtf,
                                         "image": torch.empty((H, W, chans), dtype=torch.float32, device=self.device),
-                                        "E": planes(), "D": planes(), "D2": planes() if mtf else None,
                                         "u8": torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)}
-        image, E, D, D2, out_u8 = bufs["image"], bufs["E"], bufs["D"], bufs["D2"], bufs["u8"]
-        if is_u16 and (bufs.get("u16") is None or tuple(bufs["u16"].shape) != tuple(host.shape)):
+            for k in ("E", "D", "D2") if mtf else ("E", "D"):
+                bufs[k] = torch.empty((3, H, W), dtype=torch.float32, device=self.device)
+        if host.dtype == torch.int16 and (bufs.get("u16") is None or tuple(bufs["u16"].shape) != tuple(host.shape)):
             bufs["u16"] = torch.empty(tuple(host.shape), dtype=torch.int16, device=self.device)
-        raw16 = bufs.get("u16") if is_u16 else None
-        nres = self.result_buffers
-        fresh, copies = None, []
-        if nres > 0:  # the caller takes views of pinned buffers in turn (_download)
-            ring = getattr(self, "_result_ring", None)
-            if ring is None or ring[0].shape != out_u8.shape or len(ring) != nres:
-                ring = self._result_ring = [torch.empty(out_u8.shape, dtype=torch.uint8, pin_memory=True) for _ in range(nres)]
-                self._result_turn = 0
-            result = ring[self._result_turn % nres]
-            self._result_turn += 1
-        elif (leased := self._lease_result(tuple(out_u8.shape))) is not None:
-            # upstream's ownership semantics -- an array of the caller's own per call -- without a fresh allocation: the array is a
-            # view of one of up to three pinned buffers this object lends out, and the buffer comes back when the caller's last
-            # reference to the array (or to any view of it) is gone.  A caller that drops a result before asking for the next but
-            # one -- an export loop, a preview widget -- never meets a fresh page
-            result = leased
-        else:
-            # ... and for a caller that holds on to more results than that: a FRESH array.  Its pages are touched for the first time by whoever writes them
-            # (~30 ms for 0.3 GB) -- here by four helper threads that fault them in while the first bands are still on their way up,
-            # then copy each band out of a pinned staging buffer as soon as it is back, instead of by one pageable download behind
-            # the render
-            stage = bufs.get("stage")
-            if stage is None:
-                stage = bufs["stage"] = torch.empty(out_u8.shape, dtype=torch.uint8, pin_memory=True)
-            result = stage
-            fresh = np.empty((H, W, 3), dtype=np.uint8)
-            if getattr(self, "_copy_pool", None) is None:
-                from concurrent.futures import ThreadPoolExecutor
+        return bufs
 
-                self._copy_pool = ThreadPoolExecutor(max_workers=4, thread_name_prefix="r2f-result")
-            stage_np = stage.numpy()
-            flat = fresh.reshape(-1)
-
-            def touch(i0, i1):
-                flat[i0:i1:4096] = 0  # one byte per page (NumPy releases the GIL for the strided fill)
-
-            q = -(-flat.size // 4)
-            copies += [self._copy_pool.submit(touch, i, min(i + q, flat.size)) for i in range(0, flat.size, q)]
-
-            def copy_out(back, y0, y1):
-                back.synchronize()  # (releases the GIL)
-                np.copyto(fresh[y0:y1], stage_np[y0:y1])
-        if getattr(self, "_up_stream", None) is None:
-            self._up_stream = torch.cuda.Stream(device=self.device)
-            self._down_stream = torch.cuda.Stream(device=self.device)
-        up, down, compute = self._up_stream, self._down_stream, torch.cuda.current_stream(self.device)
-        p = _lib.Params.from_buffer_copy(params)
-        p.flags |= _lib.F_FRAME_RESIDENT  # the seed is written once, below; the stage calls read it from the frame block
-        ctx.write_frame_params(p)          # (and the exposure-range record starts empty)
-        up.wait_stream(compute)            # (the buffers may still be read by the previous frame's launches)
-        down.wait_stream(compute)
+    def _run_bands(self, host, payload, p, bounds, bufs, ha, ma, sink):
+        """_stream_payload's band loop (see _process_streamed): every stage runs a band as soon as the rows it reads exist (a stencil
+        stage reads into the band after its own), and the tail's rows go back into `sink`."""
+        torch, ctx = self._torch, self.ctx
+        H, n = int(host.shape[0]), len(bounds) - 1
+        hal, mtf, grain = (bool(p.flags & f) for f in (_lib.F_HALATION, _lib.F_MTF, _lib.F_GRAIN))
         pointwise = not (hal or mtf or grain)
-        state = {"front": 0, "dens": 0, "mtf": 0, "tail": 0, "ident": 0}
-        cur = D2 if mtf else D
+        is_u16 = host.dtype == torch.int16
+        image, E, D, out_u8 = bufs["image"], bufs["E"], bufs["D"], bufs["u8"]
+        landing = bufs["u16"] if is_u16 else image
+        up, down = self._copy_streams()
+        compute = torch.cuda.current_stream(self.device)
+        up.wait_stream(compute)  # (the buffers may still be read by the previous frame's launches)
+        down.wait_stream(compute)
 
-        def band(b):
-            return bounds[b], bounds[b + 1]
+        def send_up(k):
+            with torch.cuda.stream(up):
+                landing[bounds[k]:bounds[k + 1]].copy_(host[bounds[k]:bounds[k + 1]], non_blocking=True)
+                return up.record_event()
 
         def send_back(b):
-            y0, y1 = band(b)
+            y0, y1 = bounds[b], bounds[b + 1]
             done = compute.record_event()
             with torch.cuda.stream(down):
                 down.wait_event(done)
-                result[y0:y1].copy_(out_u8[y0:y1], non_blocking=True)
-                if fresh is not None:
-                    copies.append(self._copy_pool.submit(copy_out, down.record_event(), y0, y1))
-
-        def advance():
-            # every stage runs a band as soon as the rows it reads exist: a stencil stage reads into the band after its own
-            while True:
-                moved = False
-                if hal and state["dens"] < n and state["front"] > min(state["dens"] + 1, n - 1):
-                    y0, y1 = band(state["dens"])
-                    lo, hi = max(y0 - ha[0], 0), min(y1 + ha[1], H)
-                    ctx.stage_halation(E[:, lo:hi], D, p, src_gy0=lo, dst_gy0=0, y0=y0, y1=y1, H_global=H,
-                                       identity_done=state["ident"], range_valid=True)
-                    state["dens"] += 1
-                    moved = True
-                if not hal:
-                    state["dens"] = state["front"]
-                if mtf and state["mtf"] < n and state["dens"] > min(state["mtf"] + 1, n - 1):
-                    y0, y1 = band(state["mtf"])
-                    lo, hi = max(y0 - ma[0], 0), min(y1 + ma[1], H)
-                    ctx.stage_mtf(D[:, lo:hi], D2, p, src_gy0=lo, dst_gy0=0, y0=y0, y1=y1, H_global=H)
-                    state["mtf"] += 1
-                    moved = True
-                ready = state["mtf"] if mtf else state["dens"]
-                if not pointwise and state["tail"] < ready:
-                    y0, y1 = band(state["tail"])
-                    ctx.stage_tail(cur, p, src_gy0=0, out_u8=out_u8, out_gy0=0, y0=y0, y1=y1, H_global=H)
-                    send_back(state["tail"])
-                    state["tail"] += 1
-                    moved = True
-                if not moved:
-                    return
-
-        landing = raw16 if is_u16 else image
-
-        def send_up(k):
-            a0, a1 = band(k)
-            with torch.cuda.stream(up):
-                landing[a0:a1].copy_(host[a0:a1], non_blocking=True)
-                return up.record_event()
+                sink.target[y0:y1].copy_(out_u8[y0:y1], non_blocking=True)
+                sink.band_back(down.record_event() if sink.per_band else down, y0, y1)
 
         # A copy out of ordinary (pageable) host memory -- any NumPy array that was not made from pinned memory -- returns only when
         # its bytes have left the host: issued from this thread, every band's copy would hold back the launches of the band before
         # it (measured: 35.5 ms against 32.7 one after the other).  So such a source is sent up by a helper thread of its own, band
-        # by band, and this thread launches a band when its arrival event comes through the queue.
-        arrivals, uploader = None, None
-        if not host.is_pinned():
-            import queue
-            import threading
-
-            arrivals = queue.Queue()
-
-            def upload_all():
-                try:
-                    with torch.cuda.device(self.device):
-                        for k in range(n):
-                            arrivals.put(send_up(k))
-                except BaseException as e:  # noqa: BLE001 -- handed to the thread that waits for the bands
-                    arrivals.put(e)
-
-            uploader = threading.Thread(target=upload_all, name="r2f-upload", daemon=True)
-            uploader.start()
+        # by band, and this thread launches a band when its arrival event is there.
+        uploader = None if host.is_pinned() else ThreadPoolExecutor(max_workers=1, thread_name_prefix="r2f-upload",
+                                                                     initializer=torch.cuda.set_device, initargs=(self.device,))
+        arrivals = None if uploader is None else [uploader.submit(send_up, k) for k in range(n)]
+        dens = sharp = tail = ident = 0  # bands through the halation, the MTF, the tail; the last front call's identity flag
         try:
             for k in range(n):
-                a0, a1 = band(k)
-                arrived = send_up(k) if arrivals is None else arrivals.get()
-                if isinstance(arrived, BaseException):
-                    raise arrived
-                compute.wait_event(arrived)
+                a0, a1 = bounds[k], bounds[k + 1]
+                compute.wait_event(send_up(k) if arrivals is None else arrivals[k].result())
                 rows = image[a0:a1]
                 if is_u16:
-                    ctx.decode_u16(raw16[a0:a1], payload["u16_factor"], out=rows)
+                    ctx.decode_u16(landing[a0:a1], payload["u16_factor"], out=rows)
                 elif payload.get("clip_on_device"):
                     rows.clamp_(0.0, 65504.0)  # np.clip(image, 0, 65504) of gpu_processor.py:275, band by band
                 if pointwise:  # LUTs only: one fused pass per band, straight to uint8
                     ctx.stage_front(rows, p, 2, in_gy0=a0, out_u8=out_u8, out_gy0=0, y0=a0, y1=a1, H_global=H)
                     send_back(k)
-                elif hal:
-                    state["ident"] = ctx.stage_front_split(rows, p, E, D, in_gy0=a0, y0=a0, y1=a1, H_global=H, track_range=True)
+                    continue
+                if hal:
+                    ident = ctx.stage_front_split(rows, p, E, D, in_gy0=a0, y0=a0, y1=a1, H_global=H, track_range=True)
                 else:
                     ctx.stage_front(rows, p, 1, in_gy0=a0, dst=D, dst_gy0=0, y0=a0, y1=a1, H_global=H)
-                state["front"] = k + 1
-                advance()
-        except BaseException:
-            # a stage call refused (or the caller interrupted): let the queued work drain, hand a lent buffer back, pass it on
+                moved = True
+                while moved:
+                    moved = False
+                    if not hal:
+                        dens = k + 1
+                    elif dens < n and k + 1 > min(dens + 1, n - 1):
+                        y0, y1 = bounds[dens], bounds[dens + 1]
+                        lo, hi = max(y0 - ha[0], 0), min(y1 + ha[1], H)
+                        ctx.stage_halation(E[:, lo:hi], D, p, src_gy0=lo, dst_gy0=0, y0=y0, y1=y1, H_global=H, identity_done=ident,
+                                           range_valid=True)
+                        dens, moved = dens + 1, True
+                    if mtf and sharp < n and dens > min(sharp + 1, n - 1):
+                        y0, y1 = bounds[sharp], bounds[sharp + 1]
+                        lo, hi = max(y0 - ma[0], 0), min(y1 + ma[1], H)
+                        ctx.stage_mtf(D[:, lo:hi], bufs["D2"], p, src_gy0=lo, dst_gy0=0, y0=y0, y1=y1, H_global=H)
+                        sharp, moved = sharp + 1, True
+                    if tail < (sharp if mtf else dens):
+                        y0, y1 = bounds[tail], bounds[tail + 1]
+                        ctx.stage_tail(bufs["D2"] if mtf else D, p, src_gy0=0, out_u8=out_u8, out_gy0=0, y0=y0, y1=y1, H_global=H)
+                        send_back(tail)
+                        tail, moved = tail + 1, True
+        finally:
             if uploader is not None:
-                uploader.join()
-            torch.cuda.synchronize(self.device)
-            for c in copies:
-                c.cancel()
-            if nres <= 0 and fresh is None:
-                self._lease_pool.append(result)
-            raise
-        if uploader is not None:
-            uploader.join()
-        down.synchronize()
-        for c in copies:
-            c.result()
-        # (the frame kept on the device for re-renders -- a preview's, typically -- is left alone: an export in between does not cost
-        # the preview its cached frame, which the one-after-the-other path has to overwrite because it works in it)
-        self.last_output = out_u8
-        if fresh is not None:
-            return fresh
-        arr = result.numpy()
-        if nres <= 0:  # a lent buffer: back into the pool when the caller lets go of the array
-            import weakref
-
-            weakref.finalize(arr, self._lease_pool.append, result)
-        return arr
+                uploader.shutdown(cancel_futures=True)
 
     def _lease_result(self, shape):
-        """A pinned uint8 buffer of `shape` to lend to the caller of process() as its result (see _process_streamed), or None when
-        three are out already."""
-        pool = self.__dict__.setdefault("_lease_pool", [])
-        for i, t in enumerate(pool):
-            if tuple(t.shape) == shape:
-                return pool.pop(i)
-        del pool[:]  # (buffers of another frame size: let them go)
-        if self.__dict__.get("_lease_shape") != shape:
-            self._lease_shape, self._lease_count = shape, 0
-        if self._lease_count >= 3:
-            return None
-        self._lease_count += 1
-        return self._torch.empty(shape, dtype=self._torch.uint8, pin_memory=True)
+        """A pinned buffer of `shape` to lend out as a result, or None when three are out (every lease goes through here)."""
+        return self._results.lease(shape)
+
+    def _copy_streams(self):
+        """(host-to-device, device-to-host) copy streams of this processor, made on first use."""
+        if getattr(self, "_up_stream", None) is None:
+            self._up_stream = self._torch.cuda.Stream(device=self.device)
+            self._down_stream = self._torch.cuda.Stream(device=self.device)
+        return self._up_stream, self._down_stream
 
     def _download(self, out_u8):
-        """The uint8 result as a NumPy array.  Default: an array of the caller's own per call, like upstream.  With result_buffers = n > 0 the
-        frame lands in one of n pinned host buffers taken in turn (a 24 MP frame then takes 1.5 instead of 6 ms to come down)
-        and the returned array is a VIEW of it: valid until n more frames of the same size have been returned."""
-        n = getattr(self, "result_buffers", 0)
-        torch = self._torch
-        if n <= 0:
-            # the caller's own array, like upstream's -- for a frame of a megapixel and more a view of a pinned buffer this object
-            # lends out (up to three; see _process_streamed) instead of a freshly allocated pageable array: the download runs at
-            # the link's rate and no page is touched for the first time (24 MP: 2.7 instead of 7.8 ms)
-            leased = self._lease_result(tuple(out_u8.shape)) if out_u8.numel() >= (3 << 20) else None
-            if leased is None:
-                return out_u8.cpu().numpy()
-            import weakref
-
-            leased.copy_(out_u8, non_blocking=True)
-            torch.cuda.current_stream(self.device).synchronize()
-            arr = leased.numpy()
-            weakref.finalize(arr, self._lease_pool.append, leased)
-            return arr
-        ring = getattr(self, "_result_ring", None)
-        if ring is None or ring[0].shape != out_u8.shape or len(ring) != n:
-            ring = self._result_ring = [torch.empty(out_u8.shape, dtype=torch.uint8, pin_memory=True) for _ in range(n)]
-            self._result_turn = 0
-        host = ring[self._result_turn % n]
-        self._result_turn += 1
-        host.copy_(out_u8, non_blocking=True)
-        torch.cuda.current_stream(self.device).synchronize()
-        return host.numpy()
+        """The uint8 result as a NumPy array (results.py): with result_buffers = n > 0 a view of one of n pinned buffers (24 MP: 1.5
+        instead of 6 ms to come down); else the caller's own array, from 3 M samples up a lent pinned buffer (2.7 instead of 7.8 ms)."""
+        sink = None
+        if self.result_buffers > 0 or out_u8.numel() >= (3 << 20):
+            sink = self._results.sink(tuple(out_u8.shape), self.result_buffers, staged=False, lease=self._lease_result)
+        if sink is None:
+            return out_u8.cpu().numpy()
+        sink.target.copy_(out_u8, non_blocking=True)
+        sink.band_back(self._torch.cuda.current_stream(self.device), 0, int(out_u8.shape[0]))
+        return sink.finish()
 
     def _payload_tensor(self, cpu_payload):
         """The payload's frame as a torch tensor: float32, or the 16 bits of a uint16 frame (as int16: same bytes)."""
@@ -903,28 +785,26 @@ class HipProcessor:
             res = self._stream_payload(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, **settings)
             if res is not None:
                 return PendingFrame.finished(res)
-        if getattr(self, "_up_stream", None) is None:
-            self._up_stream = torch.cuda.Stream(device=self.device)
-            self._down_stream = torch.cuda.Stream(device=self.device)
+        up, down = self._copy_streams()
         image = self._payload_tensor(cpu_payload)
         # (A pageable source -- an ordinary NumPy array -- makes the "asynchronous" copy below a synchronous one: this thread waits
         # for the frame's bytes to leave the host.  That is fine: the frame before is already queued on the device and its render
         # and download run meanwhile.  Pinning the array first, which this method did until round 6, is a fresh pinned allocation
         # and a single-threaded host copy per frame: 64 instead of 6.3 ms per 24 MP frame, tools/batch_pageable_probe.py.)
         compute = torch.cuda.current_stream(self.device)
-        with torch.cuda.stream(self._up_stream):
+        with torch.cuda.stream(up):
             dev = image.to(self.device, non_blocking=True)
-            uploaded = self._up_stream.record_event()
+            uploaded = up.record_event()
         compute.wait_event(uploaded)
         dev.record_stream(compute)
         out_u8 = self._render_preloaded(dev, cpu_payload, negative_film, grain_size, grain_sigma, None, None, final_scaling, **settings)
         rendered = compute.record_event()
-        with torch.cuda.stream(self._down_stream):
-            self._down_stream.wait_event(rendered)
+        with torch.cuda.stream(down):
+            down.wait_event(rendered)
             host = torch.empty(out_u8.shape, dtype=torch.uint8, pin_memory=True)
             host.copy_(out_u8, non_blocking=True)
-            out_u8.record_stream(self._down_stream)
-            done = self._down_stream.record_event()
+            out_u8.record_stream(down)
+            done = down.record_event()
         return PendingFrame(host, done)
 
     def _render_preloaded(self, image, cpu_payload, negative_film, grain_size, grain_sigma, dst_texture, histogram_texture,
@@ -1099,3 +979,6 @@ class HipProcessor:
         _, H, W = self.ctx.layout_of(image, layout)
         params = self.prepare(negative_film, grain_size, grain_sigma, (W, H), **settings)
         return self.ctx.render(image, params, out_f32=out_f32, out_u8=out_u8, want_f32=want_f32, want_u8=want_u8, layout=layout)
+
+
+_LOAD_KEYWORDS = tuple(inspect.signature(HipProcessor.load_image_texture).parameters)[2:]  # (self, src, then these)

@@ -69,6 +69,23 @@ def test_process_keeps_the_reference_keyword_surface():
     assert any(p.kind is inspect.Parameter.VAR_KEYWORD for p in sig.parameters.values())  # **_ swallows GUI extras
 
 
+def test_process_hands_its_keywords_to_the_load_and_the_render(proc):
+    seen = {}
+    proc._texture = ("image", None, {})
+    proc.load_image_texture = lambda src, **kw: seen.update(load=kw)
+    proc._render_prepared = lambda *a, **kw: seen.update(render=kw)  # (None: nothing to download)
+    assert proc.process("frame.npy", "film", 6, 0.4, frame_width=40, canvas_mode="Proportional", zoom=1.5, exp_comp=0.5, seed=3,
+                        src_version=7, extra=1) is None
+    assert list(seen["load"]) == list(inspect.signature(HipProcessor.load_image_texture).parameters)[2:]
+    assert (seen["load"]["frame_width"], seen["load"]["canvas_mode"], seen["load"]["zoom"], seen["load"]["src_version"]) == (
+        40, "Proportional", 1.5, 7)
+    render = seen["render"]
+    assert (render["frame_width"], render["canvas_mode"], render["exp_comp"], render["seed"]) == (40, "Proportional", 0.5, 3)
+    assert "extra" not in render  # (unknown keywords are swallowed by process(), not handed on)
+    shared = set(inspect.signature(HipProcessor.prepare).parameters) & set(inspect.signature(HipProcessor.process).parameters)
+    assert shared - {"self", "negative_film", "grain_size", "grain_sigma", "_"} <= set(render)
+
+
 def test_stage_gating_and_upload_caching(proc):
     stocks = filmstock.builtin_stocks()
     neg, prt = stocks["Kodak Portra 400"], stocks["Kodak 2383"]
