@@ -413,6 +413,22 @@ R2F_API int r2f_plan_stencil(const float* host_khwc, int kh, int kw, int kc, int
 /* Tile order of a gx x gy grid of stencil workgroups (a permutation of 0 .. gx gy - 1; band = 0: automatic band width). */
 R2F_API int r2f_plan_tile_order(int gx, int gy, int band, int* order);
 
+/* --- JPEG export: gui.py:2338-2341 `Image.fromarray(image).save(path, "JPEG", quality=quality)` on the device.  The file is byte for
+ * byte the one Pillow writes with its defaults (libjpeg-turbo baseline: JFIF 1.01 APP0, two 8-bit DQT, SOF0 4:2:0, the four
+ * Annex K Huffman tables, one interleaved scan without restart markers, EOI).  quality: 0 .. 100 like the reference's slider
+ * (0 writes what 1 writes).  H and W: 1 .. 65535. */
+/* Worst-case file size of an H x W frame at any quality (0 for sizes JPEG cannot hold).  No GPU, no context. */
+R2F_API uint64_t r2f_jpeg_bound_bytes(int H, int W);
+/* The file's header, SOI up to and including SOS, into buf (cap >= 623); *len = its length.  No GPU, no context. */
+R2F_API int r2f_jpeg_header(int quality, int H, int W, uint8_t* buf, size_t cap, size_t* len);
+/* Encode a uint8 (H, W, 3) RGB device image whose rows are row_stride bytes apart into the device buffer `out` (out_cap >=
+ * r2f_jpeg_bound_bytes(H, W)); the file's length lands in the device word *out_len (8-byte aligned).  Asynchronous on `stream`:
+ * nothing is read back.  The scratch (about 3 bytes per pixel of coefficients plus the packed scan) belongs to the context and
+ * only grows, so frames of alternating sizes neither re-allocate nor synchronise.  *out_len = 0 would mean an internal bound was
+ * broken (nothing was written past it). */
+R2F_API int r2f_jpeg_encode(r2f_ctx* ctx, const uint8_t* image, int H, int W, int64_t row_stride, int quality, uint8_t* out,
+                            uint64_t out_cap, uint64_t* out_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

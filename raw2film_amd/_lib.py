@@ -168,6 +168,12 @@ _SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     ),
+    "r2f_jpeg_bound_bytes": (C.c_uint64, [C.c_int, C.c_int]),
+    "r2f_jpeg_header": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
+    "r2f_jpeg_encode": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p],
+    ),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -610,6 +610,28 @@ class HipContext:
                                                counts.data_ptr(), self._stream()))
         return counts
 
+    def jpeg_bound_bytes(self, H: int, W: int) -> int:
+        """Largest JPEG file r2f_jpeg_encode can write for an H x W frame."""
+        return int(self._lib.r2f_jpeg_bound_bytes(int(H), int(W)))
+
+    def jpeg_encode(self, image_u8, quality: int):
+        """Baseline JPEG of a uint8 (H, W, 3) device image (rows may be strided; pixels packed) -> (uint8 device buffer of
+        jpeg_bound_bytes, int64 device tensor of 1 holding the file's length).  Asynchronous on the current stream."""
+        torch = self._torch
+        if not (isinstance(image_u8, torch.Tensor) and image_u8.is_cuda and image_u8.dtype == torch.uint8 and image_u8.dim() == 3
+                and image_u8.shape[2] == 3 and image_u8.stride(2) == 1 and image_u8.stride(1) == 3):
+            raise ValueError("jpeg_encode needs a uint8 (H, W, 3) CUDA tensor with packed pixels (row stride free)")
+        self._same_device(image_u8, "image")
+        H, W = int(image_u8.shape[0]), int(image_u8.shape[1])
+        bound = self.jpeg_bound_bytes(H, W)
+        if bound == 0:
+            raise ValueError(f"jpeg_encode: a JPEG holds 1 .. 65535 pixels per side, got {H} x {W}")
+        out = torch.empty(bound, dtype=torch.uint8, device=self.device)
+        length = torch.empty(1, dtype=torch.int64, device=self.device)
+        self._check(self._lib.r2f_jpeg_encode(self._h, image_u8.data_ptr(), H, W, int(image_u8.stride(0)), int(quality), out.data_ptr(),
+                                              bound, length.data_ptr(), self._stream()))
+        return out, length
+
     def stage_noise(self, params, y0, y1, W, want_hash=True, want_noise=True):
         torch = self._torch
         rows = y1 - y0

@@ -12,6 +12,7 @@
 
 #include "../../include/r2f.h"
 #include "r2f_launch.h"
+#include "r2f_jpeg.h"
 #include "r2f_plan.h"
 
 using namespace r2f;
@@ -192,6 +193,9 @@ struct r2f_ctx {
     hipStream_t cap_stream = nullptr;
     int opt_render_graph = 1;
     uint64_t stat_replays = 0, stat_captures = 0, stat_eager = 0, stat_dropped = 0;
+    // r2f_jpeg_encode's scratch (r2f_jpeg_plan.h Scratch): grows to the largest frame encoded so far and stays, so that frames of
+    // alternating sizes neither re-allocate nor synchronise (no captured graph reads it: growing it leaves `generation` alone)
+    DeviceBuf jpeg_scratch;
 };
 
 namespace {
@@ -928,6 +932,7 @@ void r2f_destroy(r2f_ctx* ctx) {
     ctx->frame_buf.release();
     ctx->range_tiles.release();
     ctx->dyn_flags.release();
+    ctx->jpeg_scratch.release();
     ctx->lut2d_buf.release();
     ctx->lut3d_buf.release();
     ctx->curve_buf.release();
@@ -1823,6 +1828,36 @@ int r2f_stage_noise(r2f_ctx* ctx, const r2f_params* p, uint32_t* hash_planes, fl
         if (rc) return rc;
     }
     R2F_HIP(ctx, launch_noise(a, static_cast<hipStream_t>(stream)));
+    return R2F_OK;
+}
+
+int r2f_jpeg_encode(r2f_ctx* ctx, const uint8_t* image, int H, int W, int64_t row_stride, int quality, uint8_t* out,
+                    uint64_t out_cap, uint64_t* out_len, void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    if (!image || !out || !out_len) return fail(ctx, R2F_EINVAL, "jpeg: null image, output or length pointer");
+    if (H < 1 || W < 1 || H > jpeg::kMaxDim || W > jpeg::kMaxDim)
+        return fail(ctx, R2F_EINVAL, "jpeg: a %d x %d frame (JPEG holds 1 .. %d pixels per side)", H, W, jpeg::kMaxDim);
+    if (quality < 0 || quality > 100) return fail(ctx, R2F_EINVAL, "jpeg: quality %d is not in 0 .. 100", quality);
+    if (row_stride < 3LL * W) return fail(ctx, R2F_EINVAL, "jpeg: row stride %lld < 3 W = %lld", (long long)row_stride, 3LL * W);
+    if ((uintptr_t)out_len % 8) return fail(ctx, R2F_EINVAL, "jpeg: out_len must be 8-byte aligned");
+    const uint64_t bound = jpeg::bound_bytes(H, W);
+    if (out_cap < bound)
+        return fail(ctx, R2F_EINVAL, "jpeg: output capacity %llu < bound %llu", (unsigned long long)out_cap, (unsigned long long)bound);
+    const jpeg::Scratch L = jpeg::scratch_layout(H, W);
+    if (ctx->jpeg_scratch.bytes < L.total) {
+        R2F_HIP(ctx, hipDeviceSynchronize());  // (an earlier encode may still be working in the old buffer)
+        ctx->jpeg_scratch.release();
+        R2F_HIP(ctx, hipMalloc(&ctx->jpeg_scratch.p, L.total));
+        ctx->jpeg_scratch.bytes = L.total;
+    }
+    JpegEncodeArgs a;
+    a.image = image, a.row_stride = row_stride, a.H = H, a.W = W, a.scratch = ctx->jpeg_scratch.p;
+    jpeg::make_tables(quality, &a.tables);
+    uint8_t hdr[jpeg::kHeaderBytes];
+    if (jpeg::header(quality, H, W, hdr, sizeof hdr) != jpeg::kHeaderBytes) return fail(ctx, R2F_EINVAL, "jpeg: header");
+    a.header = hdr, a.out = out, a.out_len = reinterpret_cast<unsigned long long*>(out_len);
+    R2F_HIP(ctx, launch_jpeg_encode(a, static_cast<hipStream_t>(stream)));
     return R2F_OK;
 }
 

@@ -1,0 +1,24 @@
+// r2f_jpeg.h -- the launcher of the JPEG encoder (r2f_jpeg.hip), called by r2f_jpeg_encode in r2f_api.hip.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "r2f_jpeg_plan.h"
+
+namespace r2f {
+// r2f_jpeg.hip: the whole encoder on `s` (tables, header and scratch laid out by r2f_jpeg_plan.cpp)
+struct JpegEncodeArgs {
+    const uint8_t* image;  // uint8 (H, W, 3), rows row_stride bytes apart
+    long long row_stride;
+    int H, W;
+    void* scratch;  // jpeg::scratch_layout(H, W).total bytes
+    jpeg::Tables tables;
+    const uint8_t* header;  // jpeg::kHeaderBytes (host memory: copied into a launch argument)
+    uint8_t* out;           // >= jpeg::bound_bytes(H, W)
+    unsigned long long* out_len;
+};
+hipError_t launch_jpeg_encode(const JpegEncodeArgs& a, hipStream_t s);
+
+}  // namespace r2f

@@ -1,0 +1,478 @@
+// r2f_jpeg.hip -- baseline JPEG encoder for gfx950: a uint8 (H, W, 3) device frame -> the bytes Pillow's default JPEG save writes
+// (libjpeg-turbo; host side, tables and header: r2f_jpeg_plan.cpp).  Everything is asynchronous on the caller's stream:
+//   1. transform   one wave per 16 x 16 MCU: RGB -> YCbCr (jccolor.c), h2v2 downsampling (jcsample.c), edge replication, ISLOW
+//                  DCT (jfdctint.c), quantisation (jcdctmgr.c), dummy blocks (jccoefct.c); coefficients stored in zigzag order, and
+//                  the MCU's bits counted except for the DC differences that need the MCU before it
+//   2. dc_bits     those three DC differences (one predictor per component runs across the whole frame: no restart intervals)
+//   3. scan        exclusive scan of the bits per MCU, 64-bit (a worst-case 100 MP frame exceeds 2^32 bits)
+//   4. zero, pack  the words the scan will occupy are cleared; one wave per MCU assembles its bits in LDS and stores them, with an
+//                  atomic OR only for the first and last word, which it may share with its neighbours
+//   5. stuffing    0xFF bytes counted per 4 KB chunk, scanned, and the bytes scattered with a 0x00 behind every 0xFF; the last byte
+//                  is padded with 1-bits first (jchuff.c flush_bits); header, EOI and the file's length are written last
+#include "r2f_launch.h"
+#include "r2f_jpeg.h"
+
+#include <algorithm>
+
+namespace r2f {
+
+namespace {
+
+using u64 = unsigned long long;
+using jpeg::Tables;
+
+constexpr int kWaves = 4;          // MCUs per workgroup of the transform and pack kernels (one per wave)
+constexpr int kPackWords = 320;    // LDS words per wave in pack: an MCU spans at most (31 + 6 * 1660 + 31) / 32 = 313
+
+__constant__ uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                    41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                    30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+struct EncodeArgs {
+    const uint8_t* img;
+    long long stride;  // bytes between rows
+    int H, W;
+    int mx_n;          // MCUs per row
+    long long n_mcus;
+    const Tables* tables;
+    int16_t* coefs;    // [n_mcus][6][64]
+    u64* offsets;      // [n_mcus + 1]
+    uint32_t* words;
+    u64* chunks;       // [n_chunks + 1]
+    long long n_chunks;
+    u64 bound_bits;
+    uint8_t* out;
+    u64* out_len;
+};
+
+struct HeaderBytes {
+    uint8_t b[jpeg::kHeaderBytes];
+};
+
+__device__ inline int magnitude_bits(int v) {
+    v = v < 0 ? -v : v;
+    return v ? 32 - __clz(v) : 0;
+}
+
+__device__ inline u64 shfl_up_u64(u64 v, int d) {
+    const int lo = __shfl_up((int)(uint32_t)v, d, 64), hi = __shfl_up((int)(uint32_t)(v >> 32), d, 64);
+    return ((u64)(uint32_t)hi << 32) | (uint32_t)lo;
+}
+
+// Inclusive scan over the 64 lanes of a wave.
+template <typename T>
+__device__ inline T wave_inclusive(T x, int lane) {
+    for (int d = 1; d < 64; d <<= 1) {
+        T t;
+        if constexpr (sizeof(T) == 8)
+            t = (T)shfl_up_u64((u64)x, d);
+        else
+            t = (T)__shfl_up((int)x, d, 64);
+        if (lane >= d) x += t;
+    }
+    return x;
+}
+
+// --------------------------------------------------------------------------------------------------------------- 1. transform
+// One pass of jfdctint.c jpeg_fdct_islow over 8 samples (first = the row pass, outputs scaled by 2^PASS1_BITS).
+__device__ inline void fdct8(int d[8], bool first) {
+    constexpr int CB = 13, P1 = 2;
+    const int t0 = d[0] + d[7], t7 = d[0] - d[7], t1 = d[1] + d[6], t6 = d[1] - d[6];
+    const int t2 = d[2] + d[5], t5 = d[2] - d[5], t3 = d[3] + d[4], t4 = d[3] - d[4];
+    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    const int sh = first ? CB - P1 : CB + P1;
+    auto desc = [](int x, int n) { return (x + (1 << (n - 1))) >> n; };
+    if (first) {
+        d[0] = (t10 + t11) * (1 << P1);
+        d[4] = (t10 - t11) * (1 << P1);
+    } else {
+        d[0] = desc(t10 + t11, P1);
+        d[4] = desc(t10 - t11, P1);
+    }
+    int z1 = (t12 + t13) * 4433;
+    d[2] = desc(z1 + t13 * 6270, sh);
+    d[6] = desc(z1 - t12 * 15137, sh);
+    z1 = t4 + t7;
+    int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+    const int z5 = (z3 + z4) * 9633;
+    const int a4 = t4 * 2446, a5 = t5 * 16819, a6 = t6 * 25172, a7 = t7 * 12299;
+    z1 *= -7373, z2 *= -20995;
+    z3 = z3 * -16069 + z5;
+    z4 = z4 * -3196 + z5;
+    d[7] = desc(a4 + z1 + z3, sh);
+    d[5] = desc(a5 + z2 + z4, sh);
+    d[3] = desc(a6 + z2 + z3, sh);
+    d[1] = desc(a7 + z1 + z4, sh);
+}
+
+__device__ inline int quantize(int x, int div) {  // jcdctmgr.c: |x| / div rounded half up, sign kept
+    const int q = ((x < 0 ? -x : x) + (div >> 1)) / div;
+    return x < 0 ? -q : q;
+}
+
+__device__ inline int sym_len(uint32_t e) { return (int)(e & 0xFF); }
+
+// Bits lane `lane` (= zigzag position) contributes to its block: the DC difference on lane 0, a non-zero AC coefficient with the
+// ZRLs and the code in front of it, the EOB on the lane of the last non-zero coefficient.  `nz` = ballot of the non-zero AC lanes.
+__device__ inline int lane_bits(const uint32_t* dc, const uint32_t* ac, int v, int dc_diff, u64 nz, int lane) {
+    const u64 mask = nz | 1ull;
+    const int last = 63 - __clzll(mask);
+    int bits = 0;
+    if (lane == 0) {
+        const int n = min(magnitude_bits(dc_diff), 11);
+        bits += sym_len(dc[n]) + n;
+    } else if (v != 0) {
+        const int prev = 63 - __clzll(mask & ((1ull << lane) - 1));
+        const int run = lane - prev - 1, n = min(magnitude_bits(v), 10);
+        bits += (run >> 4) * sym_len(ac[0xF0]) + sym_len(ac[((run & 15) << 4) | n]) + n;
+    }
+    if (lane == last && last < 63) bits += sym_len(ac[0x00]);
+    return bits;
+}
+
+__global__ __launch_bounds__(256) void jpeg_transform_kernel(EncodeArgs a) {
+    __shared__ int blk[kWaves][6][64];  // Y0 Y1 Y2 Y3 Cb Cr of each wave's MCU
+    __shared__ uint32_t s_dc[2][16], s_ac[2][256];
+    __shared__ uint16_t s_q[2][64];
+    for (int i = threadIdx.x; i < 2 * 256; i += blockDim.x) (&s_ac[0][0])[i] = (&a.tables->ac[0][0])[i];
+    if (threadIdx.x < 32) (&s_dc[0][0])[threadIdx.x] = (&a.tables->dc[0][0])[threadIdx.x];
+    if (threadIdx.x < 128) (&s_q[0][0])[threadIdx.x] = (&a.tables->qdiv[0][0])[threadIdx.x];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long m = (long long)blockIdx.x * kWaves + w;
+    const bool live = m < a.n_mcus;
+    const int my = (int)(m / a.mx_n), mx = (int)(m % a.mx_n);
+    int(*B)[64] = blk[w];
+    const int H = a.H, W = a.W;
+    const int ywb = (W + 7) / 8, yhb = (H + 7) / 8, hc = (H + 1) / 2;
+    const bool right_dummy = 2 * mx + 1 >= ywb, bottom_dummy = 2 * my + 1 >= yhb;
+    if (live) {
+        const int cy = lane >> 3, cx = lane & 7;
+        auto rgb = [&](int y, int x, int& r, int& g, int& b) {
+            const uint8_t* p = a.img + (long long)y * a.stride + (long long)x * 3;
+            r = p[0], g = p[1], b = p[2];
+        };
+        // luminance of the lane's 2 x 2 quad: rows and columns past the frame repeat its last ones (expand_right_edge,
+        // expand_bottom_edge); the blocks entirely past them are dummies, fixed below
+        for (int dy = 0; dy < 2; ++dy)
+            for (int dx = 0; dx < 2; ++dx) {
+                const int ly = 2 * cy + dy, lx = 2 * cx + dx;
+                int r, g, b;
+                rgb(min(my * 16 + ly, H - 1), min(mx * 16 + lx, W - 1), r, g, b);
+                B[(ly >> 3) * 2 + (lx >> 3)][(ly & 7) * 8 + (lx & 7)] = ((19595 * r + 38470 * g + 7471 * b + 32768) >> 16) - 128;
+            }
+        // chroma sample (gy, gx): the frame's rows padded to an even count, then chroma rows past the last one repeat it
+        const int gy = min(my * 8 + cy, hc - 1), gx = mx * 8 + cx;
+        int cb = 0, cr = 0;
+        for (int dy = 0; dy < 2; ++dy)
+            for (int dx = 0; dx < 2; ++dx) {
+                int r, g, b;
+                rgb(min(2 * gy + dy, H - 1), min(2 * gx + dx, W - 1), r, g, b);
+                cb += (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
+                cr += (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+            }
+        const int bias = (gx & 1) ? 2 : 1;  // h2v2_downsample: 1, 2, 1, 2 ... along the row
+        B[4][lane] = ((cb + bias) >> 2) - 128;
+        B[5][lane] = ((cr + bias) >> 2) - 128;
+    }
+    __syncthreads();
+    if (live && lane < 48) {  // rows: lane = block * 8 + row
+        int* row = &B[lane >> 3][(lane & 7) * 8];
+        int d[8];
+        for (int i = 0; i < 8; ++i) d[i] = row[i];
+        fdct8(d, true);
+        for (int i = 0; i < 8; ++i) row[i] = d[i];
+    }
+    __syncthreads();
+    if (live && lane < 48) {  // columns, then quantisation
+        const int k = lane >> 3, c = lane & 7;
+        const uint16_t* q = s_q[k < 4 ? 0 : 1];
+        int d[8];
+        for (int i = 0; i < 8; ++i) d[i] = B[k][i * 8 + c];
+        fdct8(d, false);
+        for (int i = 0; i < 8; ++i) B[k][i * 8 + c] = quantize(d[i], q[i * 8 + c]);
+    }
+    __syncthreads();
+    // jccoefct.c compress_data: a dummy block past the right edge copies the DC of the block to its left, a row of dummy blocks
+    // past the bottom the DC of the block before that row (Y1); all of their AC coefficients are zero
+    if (live && right_dummy) B[1][lane] = lane ? 0 : B[0][0];
+    __syncthreads();
+    if (live && (bottom_dummy || right_dummy)) {
+        const int dc = bottom_dummy ? B[1][0] : B[2][0];
+        if (bottom_dummy) B[2][lane] = lane ? 0 : dc;
+        B[3][lane] = lane ? 0 : dc;
+    }
+    __syncthreads();
+    if (!live) return;
+    int bits = 0;
+    int16_t* out = a.coefs + m * 384;
+    for (int k = 0; k < 6; ++k) {
+        const int t = k < 4 ? 0 : 1;
+        const int v = B[k][kZigzag[lane]];
+        out[k * 64 + lane] = (int16_t)v;
+        const u64 nz = __ballot(lane > 0 && v != 0);
+        // (the first block of each component takes its DC difference from the MCU before: dc_bits adds that)
+        const int dd = (k >= 1 && k <= 3) ? v - B[k - 1][0] : 0;
+        int lb = lane_bits(s_dc[t], s_ac[t], v, dd, nz, lane);
+        if (lane == 0 && !(k >= 1 && k <= 3)) lb -= sym_len(s_dc[t][0]);
+        bits += lb;
+    }
+    for (int d = 32; d >= 1; d >>= 1) bits += __shfl_xor(bits, d, 64);
+    if (lane == 0) a.offsets[m] = (u64)bits;
+}
+
+// --------------------------------------------------------------------------------------------------------------- 2. DC bits
+__device__ inline int dc_bits(const Tables* t, int c, int diff) {
+    const int n = min(magnitude_bits(diff), 11);
+    return sym_len(t->dc[c][n]) + n;
+}
+
+__global__ __launch_bounds__(256) void jpeg_dc_bits_kernel(EncodeArgs a) {
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= a.n_mcus) return;
+    const int16_t* c = a.coefs + m * 384;
+    const int16_t* p = m ? c - 384 : nullptr;
+    a.offsets[m] += (u64)(dc_bits(a.tables, 0, c[0] - (p ? p[3 * 64] : 0)) + dc_bits(a.tables, 1, c[4 * 64] - (p ? p[4 * 64] : 0)) +
+                          dc_bits(a.tables, 1, c[5 * 64] - (p ? p[5 * 64] : 0)));
+}
+
+// --------------------------------------------------------------------------------------------------------------- 3. scan
+// Exclusive scan, in place, of each kScanBlock elements of data[0, n); sums[block] = the block's total.  A single block also writes
+// the total to data[n].
+__global__ __launch_bounds__(256) void scan_block_kernel(u64* data, long long n, u64* sums) {
+    __shared__ u64 wave_tot[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long long base = (long long)blockIdx.x * jpeg::kScanBlock + threadIdx.x * 4;
+    u64 v[4], s = 0;
+    for (int j = 0; j < 4; ++j) {
+        v[j] = base + j < n ? data[base + j] : 0;
+        s += v[j];
+    }
+    const u64 inc = wave_inclusive<u64>(s, lane);
+    if (lane == 63) wave_tot[w] = inc;
+    __syncthreads();
+    u64 run = inc - s;
+    for (int i = 0; i < w; ++i) run += wave_tot[i];
+    for (int j = 0; j < 4; ++j) {
+        if (base + j < n) data[base + j] = run;
+        run += v[j];
+    }
+    if (threadIdx.x == 255) {
+        if (sums) sums[blockIdx.x] = run;
+        if (gridDim.x == 1) data[n] = run;
+    }
+}
+
+// data[block * kScanBlock + i] += sums[block] (sums scanned already, sums[gridDim.x] = the total, which goes to data[n]).
+__global__ __launch_bounds__(256) void scan_add_kernel(u64* data, long long n, const u64* sums) {
+    const long long base = (long long)blockIdx.x * jpeg::kScanBlock;
+    const u64 add = sums[blockIdx.x];
+    for (int j = threadIdx.x; j < jpeg::kScanBlock; j += blockDim.x)
+        if (base + j < n) data[base + j] += add;
+    if (blockIdx.x == 0 && threadIdx.x == 0) data[n] = sums[gridDim.x];
+}
+
+void scan_u64(u64* data, long long n, u64* partial, hipStream_t s) {
+    const long long nb = (n + jpeg::kScanBlock - 1) / jpeg::kScanBlock;
+    if (nb <= 1) {
+        launch_k(scan_block_kernel, dim3(1), dim3(256), 0, s, data, n, (u64*)nullptr);
+        return;
+    }
+    launch_k(scan_block_kernel, dim3((unsigned)nb), dim3(256), 0, s, data, n, partial);
+    scan_u64(partial, nb, partial + nb + 1, s);
+    launch_k(scan_add_kernel, dim3((unsigned)nb), dim3(256), 0, s, data, n, (const u64*)partial);
+}
+
+// --------------------------------------------------------------------------------------------------------------- 4. pack
+// Words [0, ceil(total / 32)) of the packed scan cleared (what pack ORs into must start at zero).
+__global__ __launch_bounds__(256) void jpeg_zero_kernel(EncodeArgs a) {
+    const u64 total = a.offsets[a.n_mcus];
+    if (total > a.bound_bits) return;
+    const u64 nw = (total + 31) / 32;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (u64)gridDim.x * blockDim.x) a.words[i] = 0;
+}
+
+// The low `len` (1..32) bits of `v` at bit position `pos` of a wave's LDS words, big-endian (a code and its value bits go in one
+// call: the value must be masked to its own width first, or a negative one's sign bits would land on the code).
+__device__ inline void put_bits(uint32_t* lds, int pos, uint32_t v, int len) {
+    const u64 x = ((u64)(v & (uint32_t)((1ull << len) - 1)) << (64 - len)) >> (pos & 31);
+    atomicOr(&lds[pos >> 5], (uint32_t)(x >> 32));
+    if ((uint32_t)x) atomicOr(&lds[(pos >> 5) + 1], (uint32_t)x);
+}
+
+__global__ __launch_bounds__(256) void jpeg_pack_kernel(EncodeArgs a) {
+    __shared__ uint32_t s_words[kWaves][kPackWords];
+    __shared__ uint32_t s_dc[2][16], s_ac[2][256];
+    for (int i = threadIdx.x; i < 2 * 256; i += blockDim.x) (&s_ac[0][0])[i] = (&a.tables->ac[0][0])[i];
+    if (threadIdx.x < 32) (&s_dc[0][0])[threadIdx.x] = (&a.tables->dc[0][0])[threadIdx.x];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long m = (long long)blockIdx.x * kWaves + w;
+    uint32_t* lds = s_words[w];
+    for (int i = lane; i < kPackWords; i += 64) lds[i] = 0;
+    __syncthreads();
+    const bool live = m < a.n_mcus && a.offsets[a.n_mcus] <= a.bound_bits;
+    const u64 start = live ? a.offsets[m] : 0, end = live ? a.offsets[m + 1] : 0;
+    const int nw = live ? (int)(((start & 31) + (end - start) + 31) >> 5) : 0;
+    if (live && nw <= kPackWords) {
+        const int16_t* c = a.coefs + m * 384;
+        const int16_t* p = m ? c - 384 : nullptr;
+        int pos = (int)(start & 31);  // bit position in the wave's words
+        for (int k = 0; k < 6; ++k) {
+            const int t = k < 4 ? 0 : 1;
+            const uint32_t* dc = s_dc[t];
+            const uint32_t* ac = s_ac[t];
+            const int v = c[k * 64 + lane];
+            const int pred = k >= 1 && k <= 3 ? c[(k - 1) * 64] : (p ? p[(k == 0 ? 3 : k) * 64] : 0);
+            const u64 nz = __ballot(lane > 0 && v != 0);
+            const int len = lane_bits(dc, ac, v, v - pred, nz, lane);
+            const int inc = wave_inclusive<int>(len, lane);
+            int at = pos + inc - len;
+            if (lane == 0) {  // DC: size category, then the difference's low bits (negative: minus one, jchuff.c)
+                const int diff = v - pred, n = min(magnitude_bits(diff), 11);
+                const uint32_t e = dc[n];
+                const int cl = sym_len(e);
+                put_bits(lds, at, ((e >> 8) << n) | ((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << n) - 1)), cl + n);
+                at += cl + n;
+            } else if (v != 0) {
+                const u64 mask = nz | 1ull;
+                const int prev = 63 - __clzll(mask & ((1ull << lane) - 1));
+                int run = lane - prev - 1;
+                const int n = min(magnitude_bits(v), 10);
+                for (; run > 15; run -= 16) {
+                    put_bits(lds, at, ac[0xF0] >> 8, sym_len(ac[0xF0]));
+                    at += sym_len(ac[0xF0]);
+                }
+                const uint32_t e = ac[(run << 4) | n];
+                put_bits(lds, at, ((e >> 8) << n) | ((uint32_t)(v < 0 ? v - 1 : v) & ((1u << n) - 1)), sym_len(e) + n);
+                at += sym_len(e) + n;
+            }
+            const int last = 63 - __clzll(nz | 1ull);
+            if (lane == last && last < 63) put_bits(lds, at, ac[0x00] >> 8, sym_len(ac[0x00]));
+            pos += __shfl(inc, 63, 64);
+        }
+    }
+    __syncthreads();
+    if (!live || nw > kPackWords) return;
+    // words wholly inside this MCU's bits are its own; the first and the last may hold a neighbour's bits too
+    const u64 w0 = start >> 5;
+    for (int i = lane; i < nw; i += 64) {
+        const bool shared = (i == 0 && (start & 31)) || (i == nw - 1 && (end & 31));
+        if (shared)
+            atomicOr(&a.words[w0 + i], lds[i]);
+        else
+            a.words[w0 + i] = lds[i];
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------------- 5. stuffing
+// Byte i of the packed scan, the last one padded with 1-bits (flush_bits).
+__device__ inline uint32_t scan_byte(const uint32_t* words, u64 i, u64 total_bits) {
+    uint32_t b = (words[i >> 2] >> (24 - 8 * (i & 3))) & 0xFF;
+    if (i == (total_bits - 1) / 8 && (total_bits & 7)) b |= 0xFFu >> (total_bits & 7);
+    return b;
+}
+
+// 0xFF bytes of each kStuffChunk bytes of the scan (one chunk per workgroup, 16 bytes per thread); chunks past the scan count 0.
+__global__ __launch_bounds__(256) void jpeg_ff_count_kernel(EncodeArgs a) {
+    __shared__ int wave_tot[4];
+    const u64 total = a.offsets[a.n_mcus];
+    const u64 nbytes = total <= a.bound_bits ? (total + 7) / 8 : 0;
+    const u64 b0 = (u64)blockIdx.x * jpeg::kStuffChunk + threadIdx.x * 16;
+    int cnt = 0;
+    for (int j = 0; j < 16; ++j)
+        if (b0 + j < nbytes) cnt += scan_byte(a.words, b0 + j, total) == 0xFF;
+    for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+    if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) a.chunks[blockIdx.x] = (u64)(wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3]);
+}
+
+// Every scan byte to its place behind the header, a 0x00 behind each 0xFF.
+__global__ __launch_bounds__(256) void jpeg_scatter_kernel(EncodeArgs a) {
+    __shared__ int wave_tot[4];
+    const u64 total = a.offsets[a.n_mcus];
+    const u64 nbytes = total <= a.bound_bits ? (total + 7) / 8 : 0;
+    const u64 b0 = (u64)blockIdx.x * jpeg::kStuffChunk + threadIdx.x * 16;
+    if ((u64)blockIdx.x * jpeg::kStuffChunk >= nbytes) return;  // (the whole workgroup: no barrier is skipped by part of it)
+    uint32_t bytes[16];
+    int cnt = 0;
+    for (int j = 0; j < 16; ++j) {
+        bytes[j] = b0 + j < nbytes ? scan_byte(a.words, b0 + j, total) : 0;
+        cnt += b0 + j < nbytes && bytes[j] == 0xFF;
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int inc = wave_inclusive<int>(cnt, lane);
+    if (lane == 63) wave_tot[w] = inc;
+    __syncthreads();
+    u64 ff = a.chunks[blockIdx.x] + (u64)(inc - cnt);
+    for (int i = 0; i < w; ++i) ff += (u64)wave_tot[i];
+    uint8_t* out = a.out + jpeg::kHeaderBytes;
+    for (int j = 0; j < 16; ++j) {
+        if (b0 + j >= nbytes) break;
+        const u64 o = b0 + j + ff;
+        out[o] = (uint8_t)bytes[j];
+        if (bytes[j] == 0xFF) {
+            out[o + 1] = 0;
+            ++ff;
+        }
+    }
+}
+
+// Header, EOI and the file's length (0 if the scan broke its bound, which the passes above then did not write past).
+__global__ __launch_bounds__(256) void jpeg_finish_kernel(EncodeArgs a, HeaderBytes h) {
+    const u64 total = a.offsets[a.n_mcus];
+    if (total > a.bound_bits) {
+        if (threadIdx.x == 0) *a.out_len = 0;
+        return;
+    }
+    for (int i = threadIdx.x; i < jpeg::kHeaderBytes; i += blockDim.x) a.out[i] = h.b[i];
+    if (threadIdx.x == 0) {
+        const u64 end = jpeg::kHeaderBytes + (total + 7) / 8 + a.chunks[a.n_chunks];
+        a.out[end] = 0xFF;
+        a.out[end + 1] = 0xD9;
+        *a.out_len = end + 2;
+    }
+}
+
+__global__ void jpeg_tables_kernel(Tables t, Tables* dst) {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(&t);
+    uint32_t* d = reinterpret_cast<uint32_t*>(dst);
+    for (int i = threadIdx.x; i < (int)(sizeof(Tables) / 4); i += blockDim.x) d[i] = src[i];
+}
+
+}  // namespace
+
+hipError_t launch_jpeg_encode(const JpegEncodeArgs& e, hipStream_t s) {
+    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W);
+    uint8_t* base = static_cast<uint8_t*>(e.scratch);
+    EncodeArgs a;
+    a.img = e.image, a.stride = e.row_stride, a.H = e.H, a.W = e.W;
+    a.mx_n = (e.W + 15) / 16;
+    a.n_mcus = (long long)L.n_mcus;
+    a.tables = reinterpret_cast<const Tables*>(base + L.tables);
+    a.coefs = reinterpret_cast<int16_t*>(base + L.coefs);
+    a.offsets = reinterpret_cast<u64*>(base + L.offsets);
+    a.words = reinterpret_cast<uint32_t*>(base + L.words);
+    a.chunks = reinterpret_cast<u64*>(base + L.chunks);
+    a.n_chunks = (long long)L.stuff_chunks;
+    a.bound_bits = jpeg::scan_bound_bits(e.H, e.W);
+    a.out = e.out, a.out_len = e.out_len;
+    u64* partial = reinterpret_cast<u64*>(base + L.partial);
+    HeaderBytes h;
+    for (int i = 0; i < jpeg::kHeaderBytes; ++i) h.b[i] = e.header[i];
+
+    const unsigned mcu_groups = (unsigned)((L.n_mcus + kWaves - 1) / kWaves);
+    launch_k(jpeg_tables_kernel, dim3(1), dim3(256), 0, s, e.tables, reinterpret_cast<Tables*>(base + L.tables));
+    launch_k(jpeg_transform_kernel, dim3(mcu_groups), dim3(256), 0, s, a);
+    launch_k(jpeg_dc_bits_kernel, dim3((unsigned)((L.n_mcus + 255) / 256)), dim3(256), 0, s, a);
+    scan_u64(a.offsets, a.n_mcus, partial, s);
+    const u64 max_words = (a.bound_bits + 31) / 32;
+    launch_k(jpeg_zero_kernel, dim3((unsigned)std::min<u64>((max_words + 255) / 256, 4096)), dim3(256), 0, s, a);
+    launch_k(jpeg_pack_kernel, dim3(mcu_groups), dim3(256), 0, s, a);
+    launch_k(jpeg_ff_count_kernel, dim3((unsigned)L.stuff_chunks), dim3(256), 0, s, a);
+    scan_u64(a.chunks, a.n_chunks, partial, s);
+    launch_k(jpeg_scatter_kernel, dim3((unsigned)L.stuff_chunks), dim3(256), 0, s, a);
+    launch_k(jpeg_finish_kernel, dim3(1), dim3(256), 0, s, a, h);
+    return take_launch_status();
+}
+
+}  // namespace r2f

@@ -1,0 +1,173 @@
+// r2f_jpeg_plan.cpp -- host side of the JPEG encoder (see r2f_jpeg_plan.h).  No HIP in this file: it is compiled by hipcc into the
+// library and by g++ -fsanitize=address,undefined into the harness of tests/test_jpeg_host.py.
+#include "r2f_jpeg_plan.h"
+
+#include "../../include/r2f.h"
+
+#include <algorithm>
+#include <cstring>
+
+namespace r2f {
+namespace jpeg {
+
+namespace {
+
+// Annex K.1, natural order (libjpeg jcparam.c std_luminance_quant_tbl / std_chrominance_quant_tbl)
+const uint8_t kStdQuant[2][64] = {
+    {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100,
+     103, 99},
+    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+
+// zigzag position -> natural index
+const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// Annex K.3 tables: code counts per length 1..16, then the symbols
+struct HuffSpec {
+    uint8_t counts[16];
+    const uint8_t* symbols;
+    int n;
+};
+const uint8_t kDcSymbols[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t kAcLumaSymbols[162] = {
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+    0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
+    0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+    0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
+    0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+    0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+    0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
+    0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+const uint8_t kAcChromaSymbols[162] = {
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
+    0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
+    0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
+    0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
+    0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+    0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+    0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
+    0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+// in DHT order: DC luma (class 0, id 0), AC luma (1, 0), DC chroma (0, 1), AC chroma (1, 1) -- jcmarker.c write_scan_header
+const HuffSpec kHuff[4] = {
+    {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, kDcSymbols, 12},
+    {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d}, kAcLumaSymbols, 162},
+    {{0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, kDcSymbols, 12},
+    {{0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}, kAcChromaSymbols, 162},
+};
+const uint8_t kHuffId[4] = {0x00, 0x10, 0x01, 0x11};
+
+// Canonical codes of a table (jchuff.c jpeg_make_c_derived_tbl): out[symbol] = (code << 8) | length.
+void derive(const HuffSpec& h, uint32_t* out, int n_out) {
+    std::fill(out, out + n_out, 0u);
+    uint32_t code = 0;
+    int k = 0;
+    for (int len = 1; len <= 16; ++len) {
+        for (int i = 0; i < h.counts[len - 1]; ++i, ++k, ++code)
+            if (h.symbols[k] < n_out) out[h.symbols[k]] = (code << 8) | (uint32_t)len;
+        code <<= 1;
+    }
+}
+
+struct Writer {
+    uint8_t* p;
+    size_t n = 0;
+    void u8(int v) { p[n++] = (uint8_t)v; }
+    void u16(int v) { u8(v >> 8), u8(v & 0xFF); }
+    void marker(int m, int payload) { u8(0xFF), u8(m), u16(payload + 2); }
+};
+
+}  // namespace
+
+void quant_tables(int quality, uint8_t out[2][64]) {
+    const int q = std::min(std::max(quality, 1), 100);  // jpeg_quality_scaling
+    const long scale = q < 50 ? 5000 / q : 200 - 2 * q;
+    for (int t = 0; t < 2; ++t)
+        for (int i = 0; i < 64; ++i)  // jpeg_add_quant_table(..., force_baseline = TRUE)
+            out[t][i] = (uint8_t)std::min(std::max((kStdQuant[t][i] * scale + 50) / 100, 1L), 255L);
+}
+
+void make_tables(int quality, Tables* t) {
+    std::memset(t, 0, sizeof *t);
+    uint8_t q[2][64];
+    quant_tables(quality, q);
+    for (int c = 0; c < 2; ++c) {
+        derive(kHuff[2 * c], t->dc[c], 16);
+        derive(kHuff[2 * c + 1], t->ac[c], 256);
+        for (int i = 0; i < 64; ++i) t->qdiv[c][i] = (uint16_t)(q[c][i] * 8);
+    }
+}
+
+int header(int quality, int H, int W, uint8_t* buf, size_t cap) {
+    if (!buf || cap < (size_t)kHeaderBytes || quality < 0 || quality > 100 || H < 1 || W < 1 || H > kMaxDim || W > kMaxDim) return -1;
+    uint8_t q[2][64];
+    quant_tables(quality, q);
+    Writer w{buf};
+    w.u8(0xFF), w.u8(0xD8);  // SOI
+    w.marker(0xE0, 14);      // JFIF 1.01, no units, density 1:1, no thumbnail
+    for (int c : {0x4A, 0x46, 0x49, 0x46, 0, 1, 1, 0, 0, 1, 0, 1, 0, 0}) w.u8(c);  // "JFIF\0" ...
+    for (int t = 0; t < 2; ++t) {  // one DQT per table, 8-bit entries in zigzag order
+        w.marker(0xDB, 65);
+        w.u8(t);
+        for (int i = 0; i < 64; ++i) w.u8(q[t][kZigzag[i]]);
+    }
+    w.marker(0xC0, 15);  // SOF0: 8 bits, 3 components, Y 2x2 (table 0), Cb and Cr 1x1 (table 1)
+    w.u8(8), w.u16(H), w.u16(W), w.u8(3);
+    for (int c : {1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1}) w.u8(c);
+    for (int t = 0; t < 4; ++t) {
+        w.marker(0xC4, 17 + kHuff[t].n);
+        w.u8(kHuffId[t]);
+        for (int i = 0; i < 16; ++i) w.u8(kHuff[t].counts[i]);
+        for (int i = 0; i < kHuff[t].n; ++i) w.u8(kHuff[t].symbols[i]);
+    }
+    w.marker(0xDA, 10);  // SOS: 3 components (DC / AC tables 0/0, 1/1, 1/1), Ss 0, Se 63, Ah Al 0
+    for (int c : {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0}) w.u8(c);
+    return (int)w.n;
+}
+
+uint64_t scan_partials(uint64_t n) {
+    if (n <= (uint64_t)kScanBlock) return 0;
+    const uint64_t nb = (n + kScanBlock - 1) / kScanBlock;
+    return nb + 1 + scan_partials(nb);
+}
+
+Scratch scratch_layout(int H, int W) {
+    Scratch s{};
+    s.n_mcus = mcus(H, W);
+    const uint64_t scan_bytes = (scan_bound_bits(H, W) + 7) / 8;
+    s.stuff_chunks = (scan_bytes + kStuffChunk - 1) / kStuffChunk;
+    s.scan_words = s.stuff_chunks * (kStuffChunk / 4);  // (the 0xFF passes read whole chunks)
+    s.partial_elems = std::max(scan_partials(s.n_mcus), scan_partials(s.stuff_chunks));
+    auto align = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    size_t at = 0;
+    s.coefs = at, at = align(at + s.n_mcus * 6 * 64 * sizeof(int16_t));
+    s.offsets = at, at = align(at + (s.n_mcus + 1) * sizeof(uint64_t));
+    s.words = at, at = align(at + s.scan_words * sizeof(uint32_t));
+    s.chunks = at, at = align(at + (s.stuff_chunks + 1) * sizeof(uint64_t));
+    s.partial = at, at = align(at + s.partial_elems * sizeof(uint64_t));
+    s.tables = at, at = align(at + sizeof(Tables));
+    s.total = at;
+    return s;
+}
+
+}  // namespace jpeg
+}  // namespace r2f
+
+extern "C" {
+
+int r2f_jpeg_header(int quality, int H, int W, uint8_t* buf, size_t cap, size_t* len) {
+    if (!len) return R2F_EINVAL;
+    const int n = r2f::jpeg::header(quality, H, W, buf, cap);
+    if (n < 0) return R2F_EINVAL;
+    *len = (size_t)n;
+    return R2F_OK;
+}
+
+uint64_t r2f_jpeg_bound_bytes(int H, int W) {
+    if (H < 1 || W < 1 || H > r2f::jpeg::kMaxDim || W > r2f::jpeg::kMaxDim) return 0;
+    return r2f::jpeg::bound_bytes(H, W);
+}
+
+}  // extern "C"

@@ -133,6 +133,7 @@ class HipProcessor:
     def close(self):
         self._results.close()
         self._stream_bufs = None
+        self._jpeg_host = None
         self._texture = None  # the frame kept on the device for re-renders
         self._texture_src = None
         self.image_param_dict = None
@@ -533,6 +534,16 @@ class HipProcessor:
     def prepare_gpu_textures(self, cpu_payload):
         """PHASE 2's stateful half (gpu_processor.py:785-790): upload the payload's frame and run the device pre-path on it
         (uint16 conversion, free rotation, chroma NR, preview scaling); the result is the frame the pipeline reads."""
+        image, layout = self._upload_payload(cpu_payload)
+        # (what is kept next to the device frame is the payload's geometry, not its host frame: the processor must not keep a
+        # 1.2 GB decode buffer alive)
+        self._texture = (image, layout, {k: v for k, v in cpu_payload.items() if k != "image_array"})
+        self.image_param_dict = None  # (a payload from outside: no load parameters to compare the next process() with)
+        self._texture_src = None
+
+    def _upload_payload(self, cpu_payload):
+        """Upload the payload's frame and run the device pre-path on it -> (frame, layout); keeps nothing (prepare_gpu_textures
+        keeps the result as the processor's device frame, the JPEG exports do not)."""
         host = self._payload_tensor(cpu_payload)
         if cpu_payload.get("clip_on_device") and not host.is_cuda and host.dim() == 3 and host.numel() >= (1 << 24):
             # A large float frame of this object's own making (process(host array)): the clamp of gpu_processor.py:275 rides on the
@@ -556,12 +567,7 @@ class HipProcessor:
             cpu_payload = dict(cpu_payload, clip_on_device=False)
         else:
             image = host.to(self.device, non_blocking=True)  # HOST -> DEVICE, the reference's write_texture
-        image, layout = self._prepare_device_frame(image, cpu_payload)
-        # (what is kept next to the device frame is the payload's geometry, not its host frame: the processor must not keep a
-        # 1.2 GB decode buffer alive)
-        self._texture = (image, layout, {k: v for k, v in cpu_payload.items() if k != "image_array"})
-        self.image_param_dict = None  # (a payload from outside: no load parameters to compare the next process() with)
-        self._texture_src = None
+        return self._prepare_device_frame(image, cpu_payload)
 
     def _check_texture(self, t, what):
         import torch
@@ -587,6 +593,75 @@ class HipProcessor:
         out_u8 = self._render_prepared(image, layout, cpu_payload, negative_film, grain_size, grain_sigma, dst_texture,
                                        histogram_texture, final_scaling, **settings)
         return None if out_u8 is None else self._download(out_u8)  # DEVICE -> HOST, the reference's read_texture/map_sync
+
+    # ------------------------------------------------------------------ JPEG export (gui.py:2338-2341)
+    def encode_jpeg(self, image, quality=100) -> bytes:
+        """`Image.fromarray(image).save(f, "JPEG", quality=quality)` on the device: the same bytes Pillow writes with its defaults
+        (JFIF, 4:2:0, standard Huffman tables, no EXIF / ICC).  image: uint8 (H, W, 3), a NumPy array or a torch tensor (a CUDA
+        tensor may be a row-strided view); quality: an int 0 .. 100 like the reference's slider (gui.py:2532-2588)."""
+        q = _jpeg_quality(quality)
+        torch = self._torch
+        if isinstance(image, np.ndarray):
+            _check_jpeg_image(image.dtype == np.uint8, image.shape, image.dtype)
+            image = torch.from_numpy(np.ascontiguousarray(image)).to(self.device)
+        elif isinstance(image, torch.Tensor):
+            _check_jpeg_image(image.dtype == torch.uint8, tuple(image.shape), image.dtype)
+            if not image.is_cuda:
+                image = image.to(self.device)
+        else:
+            raise ValueError(f"encode_jpeg: expected a uint8 (H, W, 3) NumPy array or torch tensor, got {type(image).__name__}")
+        return self._encode_device(image, q)
+
+    def process_jpeg(self, src, negative_film, grain_size, grain_sigma, quality=100, **settings) -> bytes:
+        """The export of one frame (gui.py:2338-2341): process()'s render with the same keywords -- the pixels process() returns
+        for them -- encoded on the device as encode_jpeg does; only the file comes back to the host.  Write it with
+        `open(path, "wb").write(...)`.  The frame a preview keeps on the device (cache=True) is left alone: the next preview
+        re-render uploads nothing.  The export always extracts and uploads its frame afresh -- also with cache=True when the
+        preview holds the same frame -- and renders it in one piece: it does not take the row-band streaming that
+        process(cache=False) takes for a large host frame (whose FFT windows are anchored per band), so its pixels are those of
+        process()'s one-piece render."""
+        q = _jpeg_quality(quality)
+        for k in ("dst_texture", "histogram_texture"):
+            if settings.pop(k, None) is not None:
+                raise ValueError(f"process_jpeg writes a file: {k} is not taken (use process() for the preview)")
+        # process()'s keywords with process()'s defaults (the unknown ones swallowed like there)
+        bound = inspect.signature(HipProcessor.process).bind(self, src, negative_film, grain_size, grain_sigma, **settings)
+        bound.apply_defaults()
+        settings = {k: v for k, v in bound.arguments.items()
+                    if k not in ("self", "src", "negative_film", "grain_size", "grain_sigma", "dst_texture", "histogram_texture", "_")}
+        payload = self.extract_image_data_cpu(src, **{k: settings[k] for k in _LOAD_KEYWORDS}, _internal=True)
+        image, layout = self._upload_payload(payload)
+        out_u8 = self._render_prepared(image, layout, payload, negative_film, grain_size, grain_sigma, None, None, "cpu", **settings)
+        return self._encode_device(out_u8, q)
+
+    def process_preloaded_jpeg(self, cpu_payload, negative_film, grain_size, grain_sigma, quality=100, final_scaling="gpu",
+                               **settings) -> bytes:
+        """The batch export on the two-phase API: process_preloaded's render of a phase-1 payload, encoded on the device like
+        process_jpeg.  The processor's device frame (prepare_gpu_textures') is left alone."""
+        q = _jpeg_quality(quality)
+        for k in ("dst_texture", "histogram_texture"):
+            if settings.pop(k, None) is not None:
+                raise ValueError(f"process_preloaded_jpeg writes a file: {k} is not taken")
+        image, layout = self._upload_payload(cpu_payload)
+        out_u8 = self._render_prepared(image, layout, cpu_payload, negative_film, grain_size, grain_sigma, None, None, final_scaling,
+                                       **settings)
+        return self._encode_device(out_u8, q)
+
+    def _encode_device(self, image_u8, quality):
+        """A uint8 (H, W, 3) device frame -> the JPEG file's bytes.  The encoder runs on the current stream; reading its 8-byte
+        length back is the one synchronisation, then only the file crosses PCIe, into a pinned buffer this processor keeps (grown
+        to the largest file so far; a pageable download of a 47 MB file cost up to 34 ms) and from there into the bytes object."""
+        if image_u8.stride(2) != 1 or image_u8.stride(1) != 3 or image_u8.stride(0) < 3 * image_u8.shape[1]:
+            image_u8 = image_u8.contiguous()  # (a row-strided view is encoded in place)
+        out, length = self.ctx.jpeg_encode(image_u8, quality)
+        n = int(length.item())
+        if n <= 0:
+            raise RuntimeError("r2f_jpeg_encode reported an empty file")
+        host = getattr(self, "_jpeg_host", None)
+        if host is None or host.numel() < n:
+            host = self._jpeg_host = self._torch.empty(max(n, 1 << 20), dtype=self._torch.uint8, pin_memory=True)
+        host[:n].copy_(out[:n])  # (synchronous: the bytes are there when it returns)
+        return host[:n].numpy().tobytes()
 
     def _process_streamed(self, src, negative_film, grain_size, grain_sigma, load, settings):
         """process() of a large host frame that is uploaded for this one render (cache=False: the GUI's export calls,
@@ -982,3 +1057,21 @@ class HipProcessor:
 
 
 _LOAD_KEYWORDS = tuple(inspect.signature(HipProcessor.load_image_texture).parameters)[2:]  # (self, src, then these)
+
+
+def _jpeg_quality(quality) -> int:
+    """The reference's quality slider: an int 0 .. 100 (0 writes what 1 writes, as in Pillow)."""
+    if isinstance(quality, (bool, np.bool_)) or not isinstance(quality, (int, np.integer)):
+        raise ValueError(f"JPEG quality must be an int in 0 .. 100, got {quality!r}")
+    if not 0 <= int(quality) <= 100:
+        raise ValueError(f"JPEG quality must be in 0 .. 100, got {int(quality)}")
+    return int(quality)
+
+
+def _check_jpeg_image(is_uint8, shape, dtype):
+    if not is_uint8:
+        raise ValueError(f"encode_jpeg: the image must be uint8, got {dtype}")
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"encode_jpeg: the image must be (H, W, 3) RGB, got shape {tuple(shape)}")
+    if not (1 <= shape[0] <= 65535 and 1 <= shape[1] <= 65535):
+        raise ValueError(f"encode_jpeg: a JPEG holds 1 .. 65535 pixels per side, got {shape[0]} x {shape[1]}")
