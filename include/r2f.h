@@ -428,6 +428,18 @@ R2F_API int r2f_jpeg_header(int quality, int H, int W, uint8_t* buf, size_t cap,
  * broken (nothing was written past it). */
 R2F_API int r2f_jpeg_encode(r2f_ctx* ctx, const uint8_t* image, int H, int W, int64_t row_stride, int quality, uint8_t* out,
                             uint64_t out_cap, uint64_t* out_len, void* stream);
+/* Row-wise encode: the same file, written while the frame's rows are still being made.  Begin opens the encode of an H x W frame
+ * into `out` (out_cap >= r2f_jpeg_bound_bytes(H, W)) and writes its header; *out_len (device word, 8-byte aligned) then counts the
+ * leading bytes of the file that are final -- the header and every stuffed scan byte no later rows can change -- and after the call
+ * that completes the frame it is the file's length.  0 means an internal bound was broken.  The state between calls lives in the
+ * context's encoder scratch and a small device carry; nothing is read back, everything is asynchronous on `stream`.  A one-shot
+ * encode or a new begin ends an open row-wise encode. */
+R2F_API int r2f_jpeg_rows_begin(r2f_ctx* ctx, int H, int W, int quality, uint8_t* out, uint64_t out_cap, uint64_t* out_len,
+                                void* stream);
+/* Encode the rows [y0, y1) of the frame whose row 0 is at `image` (uint8 RGB, rows row_stride bytes apart; only these rows are
+ * read).  y0 must be the previous call's y1 (0 at first); y1 must lie past y0 and be a multiple of 16, or H, which completes the
+ * file (padding bits, EOI) and ends the encode.  Anything else, or no open encode: R2F_EINVAL (the open encode stays as it was). */
+R2F_API int r2f_jpeg_rows(r2f_ctx* ctx, const uint8_t* image, int64_t row_stride, int y0, int y1, void* stream);
 
 #ifdef __cplusplus
 }

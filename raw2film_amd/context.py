@@ -632,6 +632,12 @@ class HipContext:
                                               bound, length.data_ptr(), self._stream()))
         return out, length
 
+    def jpeg_rows(self, H: int, W: int, quality: int):
+        """Open a row-wise JPEG encode of an H x W frame (r2f_jpeg_rows_begin) on the current stream -> a JpegRows: feed it the
+        frame's rows in order with .rows(image_u8, y0, y1); .out holds the file, .length the count of its leading bytes that are
+        final.  A one-shot jpeg_encode or another jpeg_rows on this context ends it."""
+        return JpegRows(self, H, W, quality)
+
     def stage_noise(self, params, y0, y1, W, want_hash=True, want_noise=True):
         torch = self._torch
         rows = y1 - y0
@@ -643,3 +649,35 @@ class HipContext:
         )
         self._check(rc)
         return h, n
+
+
+class JpegRows:
+    """A row-wise JPEG encode on a HipContext (HipContext.jpeg_rows).  `out`: uint8 device buffer of jpeg_bound_bytes(H, W) holding
+    the file; `length`: int64 device tensor of 1, the number of leading bytes of `out` that are final -- the header and every
+    stuffed scan byte no later rows can change -- and, once the last rows are in (`done`), the file's length.  Everything runs
+    asynchronously on the stream that is current at each call."""
+
+    def __init__(self, ctx, H, W, quality):
+        torch = ctx._torch
+        H, W = int(H), int(W)
+        bound = ctx.jpeg_bound_bytes(H, W)
+        if bound == 0:
+            raise ValueError(f"jpeg_rows: a JPEG holds 1 .. 65535 pixels per side, got {H} x {W}")
+        self._ctx, self.H, self.W, self.quality = ctx, H, W, int(quality)
+        self.out = torch.empty(bound, dtype=torch.uint8, device=ctx.device)
+        self.length = torch.empty(1, dtype=torch.int64, device=ctx.device)
+        ctx._check(ctx._lib.r2f_jpeg_rows_begin(ctx._h, H, W, self.quality, self.out.data_ptr(), bound, self.length.data_ptr(),
+                                                ctx._stream()))
+        self.next_row, self.done = 0, False
+
+    def rows(self, image_u8, y0: int, y1: int):
+        """Encode rows [y0, y1) of `image_u8`, the whole uint8 (H, W, 3) device frame (rows may be strided, pixels packed; only
+        these rows are read).  y0: where the call before ended (0 at first); y1: a multiple of 16 past y0, or H (the last call)."""
+        torch, ctx = self._ctx._torch, self._ctx
+        if not (isinstance(image_u8, torch.Tensor) and image_u8.is_cuda and image_u8.dtype == torch.uint8 and image_u8.dim() == 3
+                and tuple(image_u8.shape) == (self.H, self.W, 3) and image_u8.stride(2) == 1 and image_u8.stride(1) == 3):
+            raise ValueError(f"jpeg_rows.rows needs the uint8 ({self.H}, {self.W}, 3) CUDA frame with packed pixels (row stride free)")
+        ctx._same_device(image_u8, "image")
+        # (the library refuses rows out of order or misaligned, and rows of an encode that has ended: R2F_EINVAL)
+        ctx._check(ctx._lib.r2f_jpeg_rows(ctx._h, image_u8.data_ptr(), int(image_u8.stride(0)), int(y0), int(y1), ctx._stream()))
+        self.next_row, self.done = int(y1), int(y1) == self.H

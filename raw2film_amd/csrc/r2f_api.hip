@@ -196,6 +196,15 @@ struct r2f_ctx {
     // r2f_jpeg_encode's scratch (r2f_jpeg_plan.h Scratch): grows to the largest frame encoded so far and stays, so that frames of
     // alternating sizes neither re-allocate nor synchronise (no captured graph reads it: growing it leaves `generation` alone)
     DeviceBuf jpeg_scratch;
+    // the open row-wise encode (r2f_jpeg_rows_begin): its frame, the next row it takes and where its file goes; the carry (bits
+    // and 0xFF bytes so far) stays on the device.  A one-shot encode, a new begin or the frame's last rows end it.
+    struct JpegRows {
+        bool open = false;
+        int H = 0, W = 0, next_y = 0;
+        uint8_t* out = nullptr;
+        uint64_t* out_len = nullptr;
+    } jpeg_rows;
+    DeviceBuf jpeg_carry;
 };
 
 namespace {
@@ -933,6 +942,7 @@ void r2f_destroy(r2f_ctx* ctx) {
     ctx->range_tiles.release();
     ctx->dyn_flags.release();
     ctx->jpeg_scratch.release();
+    ctx->jpeg_carry.release();
     ctx->lut2d_buf.release();
     ctx->lut3d_buf.release();
     ctx->curve_buf.release();
@@ -1831,15 +1841,17 @@ int r2f_stage_noise(r2f_ctx* ctx, const r2f_params* p, uint32_t* hash_planes, fl
     return R2F_OK;
 }
 
-int r2f_jpeg_encode(r2f_ctx* ctx, const uint8_t* image, int H, int W, int64_t row_stride, int quality, uint8_t* out,
-                    uint64_t out_cap, uint64_t* out_len, void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (!image || !out || !out_len) return fail(ctx, R2F_EINVAL, "jpeg: null image, output or length pointer");
+namespace {
+
+// What r2f_jpeg_encode and r2f_jpeg_rows_begin check of a frame and its output; then the scratch grown to the frame.
+// (row_stride < 0: no image yet)
+int jpeg_prepare(r2f_ctx* ctx, int H, int W, int64_t row_stride, int quality, uint8_t* out, uint64_t out_cap, uint64_t* out_len) {
+    if (!out || !out_len) return fail(ctx, R2F_EINVAL, "jpeg: null output or length pointer");
     if (H < 1 || W < 1 || H > jpeg::kMaxDim || W > jpeg::kMaxDim)
         return fail(ctx, R2F_EINVAL, "jpeg: a %d x %d frame (JPEG holds 1 .. %d pixels per side)", H, W, jpeg::kMaxDim);
     if (quality < 0 || quality > 100) return fail(ctx, R2F_EINVAL, "jpeg: quality %d is not in 0 .. 100", quality);
-    if (row_stride < 3LL * W) return fail(ctx, R2F_EINVAL, "jpeg: row stride %lld < 3 W = %lld", (long long)row_stride, 3LL * W);
+    if (row_stride >= 0 && row_stride < 3LL * W)
+        return fail(ctx, R2F_EINVAL, "jpeg: row stride %lld < 3 W = %lld", (long long)row_stride, 3LL * W);
     if ((uintptr_t)out_len % 8) return fail(ctx, R2F_EINVAL, "jpeg: out_len must be 8-byte aligned");
     const uint64_t bound = jpeg::bound_bytes(H, W);
     if (out_cap < bound)
@@ -1851,6 +1863,19 @@ int r2f_jpeg_encode(r2f_ctx* ctx, const uint8_t* image, int H, int W, int64_t ro
         R2F_HIP(ctx, hipMalloc(&ctx->jpeg_scratch.p, L.total));
         ctx->jpeg_scratch.bytes = L.total;
     }
+    return R2F_OK;
+}
+
+}  // namespace
+
+int r2f_jpeg_encode(r2f_ctx* ctx, const uint8_t* image, int H, int W, int64_t row_stride, int quality, uint8_t* out,
+                    uint64_t out_cap, uint64_t* out_len, void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    ctx->jpeg_rows.open = false;  // (this encode works in the scratch an open row-wise one keeps its frame's state in)
+    if (!image || !out || !out_len) return fail(ctx, R2F_EINVAL, "jpeg: null image, output or length pointer");
+    int rc = jpeg_prepare(ctx, H, W, row_stride < 0 ? 0 : row_stride, quality, out, out_cap, out_len);
+    if (rc) return rc;
     JpegEncodeArgs a;
     a.image = image, a.row_stride = row_stride, a.H = H, a.W = W, a.scratch = ctx->jpeg_scratch.p;
     jpeg::make_tables(quality, &a.tables);
@@ -1858,6 +1883,53 @@ int r2f_jpeg_encode(r2f_ctx* ctx, const uint8_t* image, int H, int W, int64_t ro
     if (jpeg::header(quality, H, W, hdr, sizeof hdr) != jpeg::kHeaderBytes) return fail(ctx, R2F_EINVAL, "jpeg: header");
     a.header = hdr, a.out = out, a.out_len = reinterpret_cast<unsigned long long*>(out_len);
     R2F_HIP(ctx, launch_jpeg_encode(a, static_cast<hipStream_t>(stream)));
+    return R2F_OK;
+}
+
+int r2f_jpeg_rows_begin(r2f_ctx* ctx, int H, int W, int quality, uint8_t* out, uint64_t out_cap, uint64_t* out_len, void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    ctx->jpeg_rows.open = false;
+    int rc = jpeg_prepare(ctx, H, W, -1, quality, out, out_cap, out_len);
+    if (rc) return rc;
+    if (!ctx->jpeg_carry.p) {
+        R2F_HIP(ctx, hipMalloc(&ctx->jpeg_carry.p, 64));
+        ctx->jpeg_carry.bytes = 64;
+    }
+    JpegEncodeArgs a;
+    a.image = nullptr, a.row_stride = 0, a.H = H, a.W = W, a.scratch = ctx->jpeg_scratch.p, a.carry = ctx->jpeg_carry.p;
+    jpeg::make_tables(quality, &a.tables);
+    uint8_t hdr[jpeg::kHeaderBytes];
+    if (jpeg::header(quality, H, W, hdr, sizeof hdr) != jpeg::kHeaderBytes) return fail(ctx, R2F_EINVAL, "jpeg: header");
+    a.header = hdr, a.out = out, a.out_len = reinterpret_cast<unsigned long long*>(out_len);
+    R2F_HIP(ctx, launch_jpeg_rows_begin(a, static_cast<hipStream_t>(stream)));
+    ctx->jpeg_rows.open = true;
+    ctx->jpeg_rows.H = H, ctx->jpeg_rows.W = W, ctx->jpeg_rows.next_y = 0;
+    ctx->jpeg_rows.out = out, ctx->jpeg_rows.out_len = out_len;
+    return R2F_OK;
+}
+
+int r2f_jpeg_rows(r2f_ctx* ctx, const uint8_t* image, int64_t row_stride, int y0, int y1, void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    auto& r = ctx->jpeg_rows;
+    if (!r.open) return fail(ctx, R2F_EINVAL, "jpeg rows: no row-wise encode is open (r2f_jpeg_rows_begin; a one-shot encode, a new "
+                                              "begin or the frame's last rows end one)");
+    if (!image) return fail(ctx, R2F_EINVAL, "jpeg rows: null image pointer");
+    if (row_stride < 3LL * r.W)
+        return fail(ctx, R2F_EINVAL, "jpeg rows: row stride %lld < 3 W = %lld", (long long)row_stride, 3LL * r.W);
+    if (y0 != r.next_y) return fail(ctx, R2F_EINVAL, "jpeg rows: rows from %d, but the encode is at row %d", y0, r.next_y);
+    jpeg::RowsGrid g;
+    if (!jpeg::rows_grid(r.H, r.W, y0, y1, &g))
+        return fail(ctx, R2F_EINVAL, "jpeg rows: rows [%d, %d) of %d: the end must lie past the start and be a multiple of 16 or %d",
+                    y0, y1, r.H, r.H);
+    JpegEncodeArgs a;
+    a.image = image, a.row_stride = row_stride, a.H = r.H, a.W = r.W, a.scratch = ctx->jpeg_scratch.p, a.carry = ctx->jpeg_carry.p;
+    a.header = nullptr, a.out = r.out, a.out_len = reinterpret_cast<unsigned long long*>(r.out_len);
+    const bool last = y1 == r.H;
+    R2F_HIP(ctx, launch_jpeg_rows(a, g, last, static_cast<hipStream_t>(stream)));
+    r.next_y = y1;
+    r.open = !last;
     return R2F_OK;
 }
 

@@ -18,7 +18,12 @@ struct JpegEncodeArgs {
     const uint8_t* header;  // jpeg::kHeaderBytes (host memory: copied into a launch argument)
     uint8_t* out;           // >= jpeg::bound_bytes(H, W)
     unsigned long long* out_len;
+    void* carry = nullptr;  // row-wise: 2 device words, the scan's bits and 0xFF bytes so far
 };
 hipError_t launch_jpeg_encode(const JpegEncodeArgs& a, hipStream_t s);
+// Row-wise: begin copies the tables into the scratch and writes the header, an empty carry and *out_len; each rows launch encodes
+// the MCUs of grid `g` against the carry (`last`: they end the frame) and leaves in *out_len the bytes of the file that are final.
+hipError_t launch_jpeg_rows_begin(const JpegEncodeArgs& a, hipStream_t s);
+hipError_t launch_jpeg_rows(const JpegEncodeArgs& a, const jpeg::RowsGrid& g, bool last, hipStream_t s);
 
 }  // namespace r2f

@@ -9,6 +9,12 @@
 //                  atomic OR only for the first and last word, which it may share with its neighbours
 //   5. stuffing    0xFF bytes counted per 4 KB chunk, scanned, and the bytes scattered with a 0x00 behind every 0xFF; the last byte
 //                  is padded with 1-bits first (jchuff.c flush_bits); header, EOI and the file's length are written last
+// Row-wise (r2f_jpeg_rows_begin / r2f_jpeg_rows): the same passes over the MCU rows of one call, [m0, m1).  The coefficients of
+// the whole frame stay in the scratch, so the first MCU's DC prediction reads the last MCU of the call before; the bit scan starts
+// at the carried bit count, the words cleared start at the first one not yet touched (the last one of the call before is shared),
+// and the stuffing passes take the bytes that became complete, [floor(before / 8), floor(after / 8)) -- the partial last byte
+// waits for the next call, the last call pads it -- with the 0xFF count scanned from the carried one.  *out_len then counts the
+// leading bytes of the file that are final.
 #include "r2f_launch.h"
 #include "r2f_jpeg.h"
 
@@ -34,6 +40,8 @@ struct EncodeArgs {
     int H, W;
     int mx_n;          // MCUs per row
     long long n_mcus;
+    long long m0, m1;  // the MCUs this launch encodes (one-shot: 0, n_mcus)
+    int last;          // the scan ends with this launch: its bytes run to the padded last one
     const Tables* tables;
     int16_t* coefs;    // [n_mcus][6][64]
     u64* offsets;      // [n_mcus + 1]
@@ -138,8 +146,8 @@ __global__ __launch_bounds__(256) void jpeg_transform_kernel(EncodeArgs a) {
     if (threadIdx.x < 32) (&s_dc[0][0])[threadIdx.x] = (&a.tables->dc[0][0])[threadIdx.x];
     if (threadIdx.x < 128) (&s_q[0][0])[threadIdx.x] = (&a.tables->qdiv[0][0])[threadIdx.x];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long m = (long long)blockIdx.x * kWaves + w;
-    const bool live = m < a.n_mcus;
+    const long long m = a.m0 + (long long)blockIdx.x * kWaves + w;
+    const bool live = m < a.m1;
     const int my = (int)(m / a.mx_n), mx = (int)(m % a.mx_n);
     int(*B)[64] = blk[w];
     const int H = a.H, W = a.W;
@@ -227,8 +235,8 @@ __device__ inline int dc_bits(const Tables* t, int c, int diff) {
 }
 
 __global__ __launch_bounds__(256) void jpeg_dc_bits_kernel(EncodeArgs a) {
-    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= a.n_mcus) return;
+    const long long m = a.m0 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= a.m1) return;
     const int16_t* c = a.coefs + m * 384;
     const int16_t* p = m ? c - 384 : nullptr;
     a.offsets[m] += (u64)(dc_bits(a.tables, 0, c[0] - (p ? p[3 * 64] : 0)) + dc_bits(a.tables, 1, c[4 * 64] - (p ? p[4 * 64] : 0)) +
@@ -237,8 +245,8 @@ __global__ __launch_bounds__(256) void jpeg_dc_bits_kernel(EncodeArgs a) {
 
 // --------------------------------------------------------------------------------------------------------------- 3. scan
 // Exclusive scan, in place, of each kScanBlock elements of data[0, n); sums[block] = the block's total.  A single block also writes
-// the total to data[n].
-__global__ __launch_bounds__(256) void scan_block_kernel(u64* data, long long n, u64* sums) {
+// the total to data[n], and starts from *start if there is one.
+__global__ __launch_bounds__(256) void scan_block_kernel(u64* data, long long n, u64* sums, const u64* start) {
     __shared__ u64 wave_tot[4];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const long long base = (long long)blockIdx.x * jpeg::kScanBlock + threadIdx.x * 4;
@@ -250,7 +258,7 @@ __global__ __launch_bounds__(256) void scan_block_kernel(u64* data, long long n,
     const u64 inc = wave_inclusive<u64>(s, lane);
     if (lane == 63) wave_tot[w] = inc;
     __syncthreads();
-    u64 run = inc - s;
+    u64 run = inc - s + (start ? *start : 0);
     for (int i = 0; i < w; ++i) run += wave_tot[i];
     for (int j = 0; j < 4; ++j) {
         if (base + j < n) data[base + j] = run;
@@ -271,24 +279,26 @@ __global__ __launch_bounds__(256) void scan_add_kernel(u64* data, long long n, c
     if (blockIdx.x == 0 && threadIdx.x == 0) data[n] = sums[gridDim.x];
 }
 
-void scan_u64(u64* data, long long n, u64* partial, hipStream_t s) {
+// (base: a device word added to every element and the total, or nullptr)
+void scan_u64(u64* data, long long n, u64* partial, hipStream_t s, const u64* base = nullptr) {
     const long long nb = (n + jpeg::kScanBlock - 1) / jpeg::kScanBlock;
     if (nb <= 1) {
-        launch_k(scan_block_kernel, dim3(1), dim3(256), 0, s, data, n, (u64*)nullptr);
+        launch_k(scan_block_kernel, dim3(1), dim3(256), 0, s, data, n, (u64*)nullptr, base);
         return;
     }
-    launch_k(scan_block_kernel, dim3((unsigned)nb), dim3(256), 0, s, data, n, partial);
-    scan_u64(partial, nb, partial + nb + 1, s);
+    launch_k(scan_block_kernel, dim3((unsigned)nb), dim3(256), 0, s, data, n, partial, (const u64*)nullptr);
+    scan_u64(partial, nb, partial + nb + 1, s, base);
     launch_k(scan_add_kernel, dim3((unsigned)nb), dim3(256), 0, s, data, n, (const u64*)partial);
 }
 
 // --------------------------------------------------------------------------------------------------------------- 4. pack
-// Words [0, ceil(total / 32)) of the packed scan cleared (what pack ORs into must start at zero).
+// Words [ceil(begin / 32), ceil(end / 32)) of the packed scan cleared (what pack ORs into must start at zero; the word holding bit
+// `begin`, if it is not the first of its word, holds the bits of the launch before).
 __global__ __launch_bounds__(256) void jpeg_zero_kernel(EncodeArgs a) {
-    const u64 total = a.offsets[a.n_mcus];
+    const u64 begin = a.offsets[a.m0], total = a.offsets[a.m1];
     if (total > a.bound_bits) return;
-    const u64 nw = (total + 31) / 32;
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (u64)gridDim.x * blockDim.x) a.words[i] = 0;
+    const u64 w0 = (begin + 31) / 32, nw = (total + 31) / 32;
+    for (u64 i = w0 + (u64)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (u64)gridDim.x * blockDim.x) a.words[i] = 0;
 }
 
 // The low `len` (1..32) bits of `v` at bit position `pos` of a wave's LDS words, big-endian (a code and its value bits go in one
@@ -305,11 +315,11 @@ __global__ __launch_bounds__(256) void jpeg_pack_kernel(EncodeArgs a) {
     for (int i = threadIdx.x; i < 2 * 256; i += blockDim.x) (&s_ac[0][0])[i] = (&a.tables->ac[0][0])[i];
     if (threadIdx.x < 32) (&s_dc[0][0])[threadIdx.x] = (&a.tables->dc[0][0])[threadIdx.x];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long m = (long long)blockIdx.x * kWaves + w;
+    const long long m = a.m0 + (long long)blockIdx.x * kWaves + w;
     uint32_t* lds = s_words[w];
     for (int i = lane; i < kPackWords; i += 64) lds[i] = 0;
     __syncthreads();
-    const bool live = m < a.n_mcus && a.offsets[a.n_mcus] <= a.bound_bits;
+    const bool live = m < a.m1 && a.offsets[a.m1] <= a.bound_bits;
     const u64 start = live ? a.offsets[m] : 0, end = live ? a.offsets[m + 1] : 0;
     const int nw = live ? (int)(((start & 31) + (end - start) + 31) >> 5) : 0;
     if (live && nw <= kPackWords) {
@@ -371,33 +381,41 @@ __device__ inline uint32_t scan_byte(const uint32_t* words, u64 i, u64 total_bit
     return b;
 }
 
-// 0xFF bytes of each kStuffChunk bytes of the scan (one chunk per workgroup, 16 bytes per thread); chunks past the scan count 0.
+// The scan bytes [lo, hi) this launch stuffs: every one up to the padded last (last launch), else the complete ones, from the
+// partial byte the launch before left (none if the scan broke its bound).
+__device__ inline void stuff_range(const EncodeArgs& a, u64& lo, u64& hi, u64& total) {
+    total = a.offsets[a.m1];
+    lo = a.offsets[a.m0] / 8;
+    hi = total > a.bound_bits ? lo : a.last ? (total + 7) / 8 : total / 8;
+}
+
+// 0xFF bytes of each kStuffChunk bytes of the range (one chunk per workgroup, 16 bytes per thread); chunks past it count 0.
 __global__ __launch_bounds__(256) void jpeg_ff_count_kernel(EncodeArgs a) {
     __shared__ int wave_tot[4];
-    const u64 total = a.offsets[a.n_mcus];
-    const u64 nbytes = total <= a.bound_bits ? (total + 7) / 8 : 0;
-    const u64 b0 = (u64)blockIdx.x * jpeg::kStuffChunk + threadIdx.x * 16;
+    u64 lo, hi, total;
+    stuff_range(a, lo, hi, total);
+    const u64 b0 = lo + (u64)blockIdx.x * jpeg::kStuffChunk + threadIdx.x * 16;
     int cnt = 0;
     for (int j = 0; j < 16; ++j)
-        if (b0 + j < nbytes) cnt += scan_byte(a.words, b0 + j, total) == 0xFF;
+        if (b0 + j < hi) cnt += scan_byte(a.words, b0 + j, total) == 0xFF;
     for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
     if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = cnt;
     __syncthreads();
     if (threadIdx.x == 0) a.chunks[blockIdx.x] = (u64)(wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3]);
 }
 
-// Every scan byte to its place behind the header, a 0x00 behind each 0xFF.
+// Every byte of the range to its place behind the header, a 0x00 behind each 0xFF (chunks[] scanned from the 0xFF bytes before).
 __global__ __launch_bounds__(256) void jpeg_scatter_kernel(EncodeArgs a) {
     __shared__ int wave_tot[4];
-    const u64 total = a.offsets[a.n_mcus];
-    const u64 nbytes = total <= a.bound_bits ? (total + 7) / 8 : 0;
-    const u64 b0 = (u64)blockIdx.x * jpeg::kStuffChunk + threadIdx.x * 16;
-    if ((u64)blockIdx.x * jpeg::kStuffChunk >= nbytes) return;  // (the whole workgroup: no barrier is skipped by part of it)
+    u64 lo, hi, total;
+    stuff_range(a, lo, hi, total);
+    const u64 b0 = lo + (u64)blockIdx.x * jpeg::kStuffChunk + threadIdx.x * 16;
+    if (lo + (u64)blockIdx.x * jpeg::kStuffChunk >= hi) return;  // (the whole workgroup: no barrier is skipped by part of it)
     uint32_t bytes[16];
     int cnt = 0;
     for (int j = 0; j < 16; ++j) {
-        bytes[j] = b0 + j < nbytes ? scan_byte(a.words, b0 + j, total) : 0;
-        cnt += b0 + j < nbytes && bytes[j] == 0xFF;
+        bytes[j] = b0 + j < hi ? scan_byte(a.words, b0 + j, total) : 0;
+        cnt += b0 + j < hi && bytes[j] == 0xFF;
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int inc = wave_inclusive<int>(cnt, lane);
@@ -407,7 +425,7 @@ __global__ __launch_bounds__(256) void jpeg_scatter_kernel(EncodeArgs a) {
     for (int i = 0; i < w; ++i) ff += (u64)wave_tot[i];
     uint8_t* out = a.out + jpeg::kHeaderBytes;
     for (int j = 0; j < 16; ++j) {
-        if (b0 + j >= nbytes) break;
+        if (b0 + j >= hi) break;
         const u64 o = b0 + j + ff;
         out[o] = (uint8_t)bytes[j];
         if (bytes[j] == 0xFF) {
@@ -419,7 +437,7 @@ __global__ __launch_bounds__(256) void jpeg_scatter_kernel(EncodeArgs a) {
 
 // Header, EOI and the file's length (0 if the scan broke its bound, which the passes above then did not write past).
 __global__ __launch_bounds__(256) void jpeg_finish_kernel(EncodeArgs a, HeaderBytes h) {
-    const u64 total = a.offsets[a.n_mcus];
+    const u64 total = a.offsets[a.m1];
     if (total > a.bound_bits) {
         if (threadIdx.x == 0) *a.out_len = 0;
         return;
@@ -433,21 +451,49 @@ __global__ __launch_bounds__(256) void jpeg_finish_kernel(EncodeArgs a, HeaderBy
     }
 }
 
+// Row-wise: the header, an empty carry ({bits, 0xFF bytes} so far) and *out_len = the header's length.
+__global__ __launch_bounds__(256) void jpeg_rows_begin_kernel(HeaderBytes h, uint8_t* out, u64* out_len, u64* carry) {
+    for (int i = threadIdx.x; i < jpeg::kHeaderBytes; i += blockDim.x) out[i] = h.b[i];
+    if (threadIdx.x == 0) {
+        carry[0] = carry[1] = 0;
+        *out_len = jpeg::kHeaderBytes;
+    }
+}
+
+// Row-wise: the carry for the next launch and the final bytes so far (the last launch adds EOI).  A broken bound leaves
+// *out_len = 0 and a carried bit count past the bound, so that every later launch of the encode writes nothing either.
+__global__ void jpeg_rows_finish_kernel(EncodeArgs a, long long n_chunks, u64* carry) {
+    const u64 total = a.offsets[a.m1];
+    if (total > a.bound_bits) {
+        carry[0] = a.bound_bits + 1;
+        *a.out_len = 0;
+        return;
+    }
+    const u64 ff = a.chunks[n_chunks];
+    u64 end = jpeg::kHeaderBytes + (a.last ? (total + 7) / 8 : total / 8) + ff;
+    if (a.last) {
+        a.out[end] = 0xFF;
+        a.out[end + 1] = 0xD9;
+        end += 2;
+    }
+    carry[0] = total;
+    carry[1] = ff;
+    *a.out_len = end;
+}
+
 __global__ void jpeg_tables_kernel(Tables t, Tables* dst) {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(&t);
     uint32_t* d = reinterpret_cast<uint32_t*>(dst);
     for (int i = threadIdx.x; i < (int)(sizeof(Tables) / 4); i += blockDim.x) d[i] = src[i];
 }
 
-}  // namespace
-
-hipError_t launch_jpeg_encode(const JpegEncodeArgs& e, hipStream_t s) {
-    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W);
+EncodeArgs encode_args(const JpegEncodeArgs& e, const jpeg::Scratch& L) {
     uint8_t* base = static_cast<uint8_t*>(e.scratch);
     EncodeArgs a;
     a.img = e.image, a.stride = e.row_stride, a.H = e.H, a.W = e.W;
     a.mx_n = (e.W + 15) / 16;
     a.n_mcus = (long long)L.n_mcus;
+    a.m0 = 0, a.m1 = a.n_mcus, a.last = 1;
     a.tables = reinterpret_cast<const Tables*>(base + L.tables);
     a.coefs = reinterpret_cast<int16_t*>(base + L.coefs);
     a.offsets = reinterpret_cast<u64*>(base + L.offsets);
@@ -456,12 +502,25 @@ hipError_t launch_jpeg_encode(const JpegEncodeArgs& e, hipStream_t s) {
     a.n_chunks = (long long)L.stuff_chunks;
     a.bound_bits = jpeg::scan_bound_bits(e.H, e.W);
     a.out = e.out, a.out_len = e.out_len;
-    u64* partial = reinterpret_cast<u64*>(base + L.partial);
+    return a;
+}
+
+HeaderBytes header_bytes(const uint8_t* header) {
     HeaderBytes h;
-    for (int i = 0; i < jpeg::kHeaderBytes; ++i) h.b[i] = e.header[i];
+    for (int i = 0; i < jpeg::kHeaderBytes; ++i) h.b[i] = header[i];
+    return h;
+}
+
+}  // namespace
+
+hipError_t launch_jpeg_encode(const JpegEncodeArgs& e, hipStream_t s) {
+    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W);
+    const EncodeArgs a = encode_args(e, L);
+    u64* partial = reinterpret_cast<u64*>(static_cast<uint8_t*>(e.scratch) + L.partial);
+    const HeaderBytes h = header_bytes(e.header);
 
     const unsigned mcu_groups = (unsigned)((L.n_mcus + kWaves - 1) / kWaves);
-    launch_k(jpeg_tables_kernel, dim3(1), dim3(256), 0, s, e.tables, reinterpret_cast<Tables*>(base + L.tables));
+    launch_k(jpeg_tables_kernel, dim3(1), dim3(256), 0, s, e.tables, const_cast<Tables*>(a.tables));
     launch_k(jpeg_transform_kernel, dim3(mcu_groups), dim3(256), 0, s, a);
     launch_k(jpeg_dc_bits_kernel, dim3((unsigned)((L.n_mcus + 255) / 256)), dim3(256), 0, s, a);
     scan_u64(a.offsets, a.n_mcus, partial, s);
@@ -472,6 +531,37 @@ hipError_t launch_jpeg_encode(const JpegEncodeArgs& e, hipStream_t s) {
     scan_u64(a.chunks, a.n_chunks, partial, s);
     launch_k(jpeg_scatter_kernel, dim3((unsigned)L.stuff_chunks), dim3(256), 0, s, a);
     launch_k(jpeg_finish_kernel, dim3(1), dim3(256), 0, s, a, h);
+    return take_launch_status();
+}
+
+hipError_t launch_jpeg_rows_begin(const JpegEncodeArgs& e, hipStream_t s) {
+    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W);
+    Tables* tables = reinterpret_cast<Tables*>(static_cast<uint8_t*>(e.scratch) + L.tables);
+    launch_k(jpeg_tables_kernel, dim3(1), dim3(256), 0, s, e.tables, tables);
+    launch_k(jpeg_rows_begin_kernel, dim3(1), dim3(256), 0, s, header_bytes(e.header), e.out, e.out_len,
+             static_cast<u64*>(e.carry));
+    return take_launch_status();
+}
+
+hipError_t launch_jpeg_rows(const JpegEncodeArgs& e, const jpeg::RowsGrid& g, bool last, hipStream_t s) {
+    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W);
+    EncodeArgs a = encode_args(e, L);
+    a.m0 = (long long)g.m0, a.m1 = (long long)g.m1, a.last = last ? 1 : 0;
+    a.n_chunks = (long long)g.stuff_chunks;
+    u64* partial = reinterpret_cast<u64*>(static_cast<uint8_t*>(e.scratch) + L.partial);
+    u64* carry = static_cast<u64*>(e.carry);
+
+    const long long n = a.m1 - a.m0;
+    const unsigned mcu_groups = (unsigned)((n + kWaves - 1) / kWaves);
+    launch_k(jpeg_transform_kernel, dim3(mcu_groups), dim3(256), 0, s, a);
+    launch_k(jpeg_dc_bits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    scan_u64(a.offsets + a.m0, n, partial, s, carry);  // offsets[m0] = the bits before, offsets[m1] = the bits after
+    launch_k(jpeg_zero_kernel, dim3((unsigned)std::min<u64>((g.zero_words + 255) / 256, 4096)), dim3(256), 0, s, a);
+    launch_k(jpeg_pack_kernel, dim3(mcu_groups), dim3(256), 0, s, a);
+    launch_k(jpeg_ff_count_kernel, dim3((unsigned)g.stuff_chunks), dim3(256), 0, s, a);
+    scan_u64(a.chunks, a.n_chunks, partial, s, carry + 1);
+    launch_k(jpeg_scatter_kernel, dim3((unsigned)g.stuff_chunks), dim3(256), 0, s, a);
+    launch_k(jpeg_rows_finish_kernel, dim3(1), dim3(64), 0, s, a, a.n_chunks, carry);
     return take_launch_status();
 }
 

@@ -152,6 +152,19 @@ Scratch scratch_layout(int H, int W) {
     return s;
 }
 
+bool rows_grid(int H, int W, int y0, int y1, RowsGrid* g) {
+    *g = RowsGrid{};
+    if (H < 1 || W < 1 || H > kMaxDim || W > kMaxDim || y0 < 0 || y0 % 16 || y1 <= y0 || y1 > H || (y1 % 16 && y1 != H)) return false;
+    const uint64_t mx = (uint64_t)((W + 15) / 16);
+    g->m0 = (uint64_t)(y0 / 16) * mx;
+    g->m1 = (uint64_t)((y1 + 15) / 16) * mx;
+    const uint64_t bits = (g->m1 - g->m0) * 6 * kBlockBoundBits;
+    const uint64_t bytes = (bits + 7) / 8 + 1;  // [floor(before / 8), ceil(after / 8)): the carried partial byte, then the new ones
+    g->stuff_chunks = std::min((bytes + kStuffChunk - 1) / kStuffChunk, scratch_layout(H, W).stuff_chunks);
+    g->zero_words = (bits + 31) / 32;  // [ceil(before / 32), ceil(after / 32))
+    return true;
+}
+
 }  // namespace jpeg
 }  // namespace r2f
 

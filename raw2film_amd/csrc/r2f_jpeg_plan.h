@@ -54,5 +54,16 @@ Scratch scratch_layout(int H, int W);
 // Workgroup sums the scan of n elements needs (recursively, every level).
 uint64_t scan_partials(uint64_t n);
 
+// One call of a row-wise encode (r2f_jpeg_rows): the MCUs of rows [y0, y1) of an H x W frame and the launch grids of its passes,
+// fixed without the bit counts.  A call's scan bits are at most (m1 - m0) * 6 * kBlockBoundBits; the words it clears start at the
+// first one the call before did not touch, and its stuffing passes cover the bytes that become complete, the partial byte carried
+// in included: stuff_chunks chunks (never more than the frame's, which hold every byte of its scan), zero_words words.
+struct RowsGrid {
+    uint64_t m0, m1;  // MCUs [m0, m1): whole MCU rows, row-major
+    uint64_t stuff_chunks, zero_words;
+};
+// y0 a multiple of 16, y0 < y1 <= H, y1 a multiple of 16 or H; returns false (grid zeroed) otherwise.
+bool rows_grid(int H, int W, int y0, int y1, RowsGrid* g);
+
 }  // namespace jpeg
 }  // namespace r2f

@@ -27,6 +27,7 @@ import numpy as np
 
 from . import _lib, filmstock, geometry, stencils
 from .context import LOG_EPS, LUT3D_SCALE, HipContext
+from .jpeg_stream import JpegBandSink, JpegStaging, deliver
 from .results import ResultBuffers
 
 REC709_TO_XYZ = np.array(  # data.py:128-135
@@ -49,6 +50,21 @@ def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canv
     fr = payload.get("final_resolution") if final_scaling == "cpu" else None  # (cpu_processor.py:411-412: the final scaling)
     if fr is not None and (int(fr[0]), int(fr[1])) != (int(shape[0]), int(shape[1])):
         return f"the finished frame is scaled to {fr}"
+    return None
+
+
+def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="No", highlight_burn=0.0):
+    """Why process(src, cache=False) renders a frame in one piece before it extracts its payload (stream_rejection and plan_bands
+    come after that), or None."""
+    if stream_bands <= 1:
+        return f"stream_bands = {stream_bands}"
+    if not isinstance(src, np.ndarray):
+        return f"the source is a {type(src).__name__}, not a host array"
+    if src.size < (1 << 24):
+        return f"a frame of {src.size} samples, below 16.7 M"
+    if rotation or chroma_nr or canvas_mode != "No" or highlight_burn:
+        return (f"a device pre-path, a canvas or a highlight burn: rotation = {rotation!r}, chroma_nr = {chroma_nr!r}, "
+                f"canvas_mode = {canvas_mode!r}, highlight_burn = {highlight_burn!r}")
     return None
 
 
@@ -134,6 +150,9 @@ class HipProcessor:
         self._results.close()
         self._stream_bufs = None
         self._jpeg_host = None
+        if getattr(self, "_jpeg_staging", None) is not None:
+            self._jpeg_staging.close()
+            self._jpeg_staging = None
         self._texture = None  # the frame kept on the device for re-renders
         self._texture_src = None
         self.image_param_dict = None
@@ -420,8 +439,8 @@ class HipProcessor:
 
             self._torch.cuda.synchronize(self.device)
             t_start = time.perf_counter()
-        elif (not cache and self.stream_bands > 1 and dst_texture is None and isinstance(src, np.ndarray) and src.size >= (1 << 24)
-              and not rotation and not chroma_nr and canvas_mode == "No" and not highlight_burn):
+        elif (not cache and dst_texture is None
+              and host_stream_gate(src, self.stream_bands, rotation, chroma_nr, canvas_mode, highlight_burn) is None):
             # a large host frame that is uploaded for this one render: streamed through the pipeline in row bands while it arrives
             res = self._process_streamed(src, negative_film, grain_size, grain_sigma, load, settings)
             if res is not None:
@@ -612,14 +631,18 @@ class HipProcessor:
             raise ValueError(f"encode_jpeg: expected a uint8 (H, W, 3) NumPy array or torch tensor, got {type(image).__name__}")
         return self._encode_device(image, q)
 
-    def process_jpeg(self, src, negative_film, grain_size, grain_sigma, quality=100, **settings) -> bytes:
+    def process_jpeg(self, src, negative_film, grain_size, grain_sigma, quality=100, stream=False, file=None, **settings):
         """The export of one frame (gui.py:2338-2341): process()'s render with the same keywords -- the pixels process() returns
-        for them -- encoded on the device as encode_jpeg does; only the file comes back to the host.  Write it with
-        `open(path, "wb").write(...)`.  The frame a preview keeps on the device (cache=True) is left alone: the next preview
-        re-render uploads nothing.  The export always extracts and uploads its frame afresh -- also with cache=True when the
-        preview holds the same frame -- and renders it in one piece: it does not take the row-band streaming that
-        process(cache=False) takes for a large host frame (whose FFT windows are anchored per band), so its pixels are those of
-        process()'s one-piece render."""
+        for them -- encoded on the device as encode_jpeg does; only the file comes back to the host.  The frame a preview keeps on
+        the device (cache=True) is left alone: the next preview re-render uploads nothing.  The export always extracts and uploads
+        its frame afresh -- also with cache=True when the preview holds the same frame.
+        stream=False: the frame is rendered in one piece, then encoded -- its pixels are those of process()'s one-piece render.
+        stream=True: the file is Pillow's of process(src, cache=False, ...)'s pixels.  A large host frame that process(cache=False)
+        streams (see _process_streamed) goes through the same row bands and stage calls, and each band's finished MCU rows are
+        encoded behind its tail: the file's final bytes go down (and into `file`) while later bands are still arriving.  A frame
+        that does not stream takes the one-piece path, and `stream_rejected` says why.
+        file: a path or a binary file object the bytes are written into (as they arrive, when streaming); the call then returns
+        their count.  Without it the call returns the bytes."""
         q = _jpeg_quality(quality)
         for k in ("dst_texture", "histogram_texture"):
             if settings.pop(k, None) is not None:
@@ -629,23 +652,40 @@ class HipProcessor:
         bound.apply_defaults()
         settings = {k: v for k, v in bound.arguments.items()
                     if k not in ("self", "src", "negative_film", "grain_size", "grain_sigma", "dst_texture", "histogram_texture", "_")}
-        payload = self.extract_image_data_cpu(src, **{k: settings[k] for k in _LOAD_KEYWORDS}, _internal=True)
+        load = {k: settings[k] for k in _LOAD_KEYWORDS}
+        if stream:  # process(cache=False)'s gates, in its order: the early ones, then the payload's (_stream_payload's)
+            self.stream_rejected = ("profile_stages is on" if getattr(self, "profile_stages", False) else
+                                    host_stream_gate(src, self.stream_bands, settings["rotation"], settings["chroma_nr"],
+                                                     settings["canvas_mode"], settings["highlight_burn"]))
+        payload = self.extract_image_data_cpu(src, **load, _internal=True)
+        if stream and self.stream_rejected is None:
+            res = self._stream_jpeg(payload, negative_film, grain_size, grain_sigma, "cpu", q, file, settings)
+            if res is not None:
+                return res
         image, layout = self._upload_payload(payload)
         out_u8 = self._render_prepared(image, layout, payload, negative_film, grain_size, grain_sigma, None, None, "cpu", **settings)
-        return self._encode_device(out_u8, q)
+        return deliver(self._encode_device(out_u8, q), file)
 
     def process_preloaded_jpeg(self, cpu_payload, negative_film, grain_size, grain_sigma, quality=100, final_scaling="gpu",
-                               **settings) -> bytes:
+                               stream=False, file=None, **settings):
         """The batch export on the two-phase API: process_preloaded's render of a phase-1 payload, encoded on the device like
-        process_jpeg.  The processor's device frame (prepare_gpu_textures') is left alone."""
+        process_jpeg.  The processor's device frame (prepare_gpu_textures') is left alone.  stream=True: the file is Pillow's of
+        process_preloaded(cpu_payload, final_scaling=..., ...)'s pixels, and a payload process_preloaded streams in row bands is
+        encoded band by band as in process_jpeg (else `stream_rejected` says why not).  file: see process_jpeg."""
         q = _jpeg_quality(quality)
         for k in ("dst_texture", "histogram_texture"):
             if settings.pop(k, None) is not None:
                 raise ValueError(f"process_preloaded_jpeg writes a file: {k} is not taken")
+        if stream:
+            self.stream_rejected = None if self.stream_bands > 1 else f"stream_bands = {self.stream_bands}"
+            if self.stream_rejected is None:
+                res = self._stream_jpeg(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, q, file, settings)
+                if res is not None:
+                    return res
         image, layout = self._upload_payload(cpu_payload)
         out_u8 = self._render_prepared(image, layout, cpu_payload, negative_film, grain_size, grain_sigma, None, None, final_scaling,
                                        **settings)
-        return self._encode_device(out_u8, q)
+        return deliver(self._encode_device(out_u8, q), file)
 
     def _encode_device(self, image_u8, quality):
         """A uint8 (H, W, 3) device frame -> the JPEG file's bytes.  The encoder runs on the current stream; reading its 8-byte
@@ -687,6 +727,27 @@ class HipProcessor:
     def _stream_payload(self, payload, negative_film, grain_size, grain_sigma, final_scaling="cpu", **settings):
         """A phase-1 payload (extract_image_data_cpu) through the pipeline in row bands while it arrives: see _process_streamed.
         Returns the uint8 frame, or None (with `stream_rejected` saying why) when the payload does not qualify."""
+        plan = self._stream_plan(payload, negative_film, grain_size, grain_sigma, final_scaling, settings)
+        if plan is None:
+            return None
+        host, p, bounds, bufs, ha, ma = plan
+        H, W = int(host.shape[0]), int(host.shape[1])
+        sink = self._results.sink((H, W, 3), self.result_buffers, lease=self._lease_result)
+        try:
+            self._run_bands(host, payload, p, bounds, bufs, ha, ma, sink)
+        except BaseException:
+            # a stage call refused (or the caller interrupted): let the queued work drain, hand a lent buffer back, pass it on
+            self._torch.cuda.synchronize(self.device)
+            sink.abandon()
+            raise
+        # (the frame kept on the device for re-renders -- a preview's, typically -- is left alone: an export in between does not cost
+        # the preview its cached frame, which the one-after-the-other path has to overwrite because it works in it)
+        self.last_output = bufs["u8"]
+        return sink.finish()
+
+    def _stream_plan(self, payload, negative_film, grain_size, grain_sigma, final_scaling, settings):
+        """Qualify a payload for the row-band path and set its frame up: (host tensor, frame params, band bounds, device buffers,
+        halation reach, MTF reach), or None with `stream_rejected` saying why it does not stream."""
         host = self._payload_tensor(payload)
         self.stream_rejected = stream_rejection(payload, tuple(host.shape), str(host.dtype), host.is_cuda, final_scaling,
                                                 settings.get("canvas_mode", "No"))
@@ -704,18 +765,32 @@ class HipProcessor:
         p = _lib.Params.from_buffer_copy(params)
         p.flags |= _lib.F_FRAME_RESIDENT  # the seed is written once, here; the stage calls read it from the frame block
         self.ctx.write_frame_params(p)     # (and the exposure-range record starts empty)
-        sink = self._results.sink((H, W, 3), self.result_buffers, lease=self._lease_result)
+        return host, p, bounds, bufs, ha, ma
+
+    def _stream_jpeg(self, payload, negative_film, grain_size, grain_sigma, final_scaling, quality, file, settings):
+        """_stream_payload with a JPEG sink: the same bands and stage calls, no pixels downloaded; each band's finished MCU rows
+        are encoded behind its tail and the file's final bytes go down while later bands arrive (jpeg_stream.py).  Returns the
+        file's bytes (file=None) or their count, or None (with `stream_rejected` saying why) when the payload does not qualify."""
+        plan = self._stream_plan(payload, negative_film, grain_size, grain_sigma, final_scaling, settings)
+        if plan is None:
+            return None
+        host, p, bounds, bufs, ha, ma = plan
+        staging = getattr(self, "_jpeg_staging", None)
+        if staging is None:
+            staging = self._jpeg_staging = JpegStaging(self._torch, self.device)
+        _, down = self._copy_streams()
+        sink = JpegBandSink(staging, self.ctx, bufs["u8"], quality, bounds, down, file)
         try:
-            self._run_bands(host, payload, p, bounds, bufs, ha, ma, sink)
+            self._run_bands(host, payload, p, bounds, bufs, ha, ma, None, band_done=sink.band)
+            res = sink.finish()
         except BaseException:
-            # a stage call refused (or the caller interrupted): let the queued work drain, hand a lent buffer back, pass it on
+            # a stage call refused, a write raised (or the caller interrupted): let the queued work drain, stop the copies and the
+            # writes, pass it on (the next export begins a new row-wise encode)
             self._torch.cuda.synchronize(self.device)
             sink.abandon()
             raise
-        # (the frame kept on the device for re-renders -- a preview's, typically -- is left alone: an export in between does not cost
-        # the preview its cached frame, which the one-after-the-other path has to overwrite because it works in it)
         self.last_output = bufs["u8"]
-        return sink.finish()
+        return res
 
     def _stream_buffers(self, host, mtf):
         """The device buffers a streamed frame works in (kept for the next frame of the same kind): `host` is its payload tensor."""
@@ -733,9 +808,10 @@ class HipProcessor:
             bufs["u16"] = torch.empty(tuple(host.shape), dtype=torch.int16, device=self.device)
         return bufs
 
-    def _run_bands(self, host, payload, p, bounds, bufs, ha, ma, sink):
+    def _run_bands(self, host, payload, p, bounds, bufs, ha, ma, sink, band_done=None):
         """_stream_payload's band loop (see _process_streamed): every stage runs a band as soon as the rows it reads exist (a stencil
-        stage reads into the band after its own), and the tail's rows go back into `sink`."""
+        stage reads into the band after its own), and the tail's rows go back into `sink` -- or, with `band_done`, band_done(b) is
+        called instead once band b's tail is queued (on the launching stream; the JPEG export's sink)."""
         torch, ctx = self._torch, self.ctx
         H, n = int(host.shape[0]), len(bounds) - 1
         hal, mtf, grain = (bool(p.flags & f) for f in (_lib.F_HALATION, _lib.F_MTF, _lib.F_GRAIN))
@@ -754,6 +830,9 @@ class HipProcessor:
                 return up.record_event()
 
         def send_back(b):
+            if band_done is not None:
+                band_done(b)
+                return
             y0, y1 = bounds[b], bounds[b + 1]
             done = compute.record_event()
             with torch.cuda.stream(down):
