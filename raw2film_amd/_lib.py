@@ -57,6 +57,10 @@ class Blit(C.Structure):  # r2f_blit: the uniform block of shaders/copy_to_int.w
     ]
 
 
+class JpegOpts(C.Structure):  # r2f_jpeg_opts (sampling: 0 4:4:4, 1 4:2:2, 2 4:2:0)
+    _fields_ = [("quality", C.c_int32), ("sampling", C.c_int32), ("optimize", C.c_int32), ("reserved", C.c_int32)]
+
+
 _P = C.POINTER
 _fp = C.c_void_p  # float* (host numpy or device) passed as an address
 _SIGNATURES = {
@@ -179,6 +183,17 @@ _SIGNATURES = {
         [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p],
     ),
     "r2f_jpeg_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "r2f_jpeg_bound_bytes_ex": (C.c_uint64, [C.c_int, C.c_int, C.c_int]),
+    "r2f_jpeg_header_ex": (C.c_int, [_P(JpegOpts), C.c_int, C.c_int, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
+    "r2f_jpeg_optimal_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_int)]),
+    "r2f_jpeg_encode_ex": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _P(JpegOpts), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p],
+    ),
+    "r2f_jpeg_rows_begin_ex": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.c_int, _P(JpegOpts), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p],
+    ),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -610,33 +610,43 @@ class HipContext:
                                                counts.data_ptr(), self._stream()))
         return counts
 
-    def jpeg_bound_bytes(self, H: int, W: int) -> int:
-        """Largest JPEG file r2f_jpeg_encode can write for an H x W frame."""
-        return int(self._lib.r2f_jpeg_bound_bytes(int(H), int(W)))
+    def jpeg_bound_bytes(self, H: int, W: int, subsampling: int = 2) -> int:
+        """Largest JPEG file r2f_jpeg_encode(_ex) can write for an H x W frame (subsampling: 0 4:4:4, 1 4:2:2, 2 4:2:0)."""
+        if int(subsampling) == 2:
+            return int(self._lib.r2f_jpeg_bound_bytes(int(H), int(W)))
+        return int(self._lib.r2f_jpeg_bound_bytes_ex(int(H), int(W), int(subsampling)))
 
-    def jpeg_encode(self, image_u8, quality: int):
+    def jpeg_encode(self, image_u8, quality: int, subsampling: int = 2, optimize: bool = False):
         """Baseline JPEG of a uint8 (H, W, 3) device image (rows may be strided; pixels packed) -> (uint8 device buffer of
-        jpeg_bound_bytes, int64 device tensor of 1 holding the file's length).  Asynchronous on the current stream."""
+        jpeg_bound_bytes, int64 device tensor of 1 holding the file's length).  Asynchronous on the current stream, except with
+        optimize, whose call waits once for the frame's symbol counts (r2f_jpeg_encode_ex).  subsampling: 0 4:4:4, 1 4:2:2,
+        2 4:2:0."""
         torch = self._torch
         if not (isinstance(image_u8, torch.Tensor) and image_u8.is_cuda and image_u8.dtype == torch.uint8 and image_u8.dim() == 3
                 and image_u8.shape[2] == 3 and image_u8.stride(2) == 1 and image_u8.stride(1) == 3):
             raise ValueError("jpeg_encode needs a uint8 (H, W, 3) CUDA tensor with packed pixels (row stride free)")
         self._same_device(image_u8, "image")
         H, W = int(image_u8.shape[0]), int(image_u8.shape[1])
-        bound = self.jpeg_bound_bytes(H, W)
+        bound = self.jpeg_bound_bytes(H, W, subsampling)
         if bound == 0:
-            raise ValueError(f"jpeg_encode: a JPEG holds 1 .. 65535 pixels per side, got {H} x {W}")
+            raise ValueError(f"jpeg_encode: a JPEG holds 1 .. 65535 pixels per side, got {H} x {W} (subsampling {subsampling})")
         out = torch.empty(bound, dtype=torch.uint8, device=self.device)
         length = torch.empty(1, dtype=torch.int64, device=self.device)
-        self._check(self._lib.r2f_jpeg_encode(self._h, image_u8.data_ptr(), H, W, int(image_u8.stride(0)), int(quality), out.data_ptr(),
-                                              bound, length.data_ptr(), self._stream()))
+        if int(subsampling) == 2 and not optimize:
+            self._check(self._lib.r2f_jpeg_encode(self._h, image_u8.data_ptr(), H, W, int(image_u8.stride(0)), int(quality),
+                                                  out.data_ptr(), bound, length.data_ptr(), self._stream()))
+        else:
+            opts = _lib.JpegOpts(int(quality), int(subsampling), 1 if optimize else 0, 0)
+            self._check(self._lib.r2f_jpeg_encode_ex(self._h, image_u8.data_ptr(), H, W, int(image_u8.stride(0)), C.byref(opts),
+                                                     out.data_ptr(), bound, length.data_ptr(), self._stream()))
         return out, length
 
-    def jpeg_rows(self, H: int, W: int, quality: int):
+    def jpeg_rows(self, H: int, W: int, quality: int, subsampling: int = 2):
         """Open a row-wise JPEG encode of an H x W frame (r2f_jpeg_rows_begin) on the current stream -> a JpegRows: feed it the
         frame's rows in order with .rows(image_u8, y0, y1); .out holds the file, .length the count of its leading bytes that are
-        final.  A one-shot jpeg_encode or another jpeg_rows on this context ends it."""
-        return JpegRows(self, H, W, quality)
+        final.  A one-shot jpeg_encode or another jpeg_rows on this context ends it.  subsampling: 0 4:4:4, 1 4:2:2 (8-row
+        MCUs), 2 4:2:0 (16-row MCUs)."""
+        return JpegRows(self, H, W, quality, subsampling)
 
     def stage_noise(self, params, y0, y1, W, want_hash=True, want_noise=True):
         torch = self._torch
@@ -657,22 +667,28 @@ class JpegRows:
     stuffed scan byte no later rows can change -- and, once the last rows are in (`done`), the file's length.  Everything runs
     asynchronously on the stream that is current at each call."""
 
-    def __init__(self, ctx, H, W, quality):
+    def __init__(self, ctx, H, W, quality, subsampling=2):
         torch = ctx._torch
         H, W = int(H), int(W)
-        bound = ctx.jpeg_bound_bytes(H, W)
+        bound = ctx.jpeg_bound_bytes(H, W, subsampling)
         if bound == 0:
-            raise ValueError(f"jpeg_rows: a JPEG holds 1 .. 65535 pixels per side, got {H} x {W}")
-        self._ctx, self.H, self.W, self.quality = ctx, H, W, int(quality)
+            raise ValueError(f"jpeg_rows: a JPEG holds 1 .. 65535 pixels per side, got {H} x {W} (subsampling {subsampling})")
+        self._ctx, self.H, self.W, self.quality, self.subsampling = ctx, H, W, int(quality), int(subsampling)
         self.out = torch.empty(bound, dtype=torch.uint8, device=ctx.device)
         self.length = torch.empty(1, dtype=torch.int64, device=ctx.device)
-        ctx._check(ctx._lib.r2f_jpeg_rows_begin(ctx._h, H, W, self.quality, self.out.data_ptr(), bound, self.length.data_ptr(),
-                                                ctx._stream()))
+        if self.subsampling == 2:
+            ctx._check(ctx._lib.r2f_jpeg_rows_begin(ctx._h, H, W, self.quality, self.out.data_ptr(), bound, self.length.data_ptr(),
+                                                    ctx._stream()))
+        else:
+            opts = _lib.JpegOpts(self.quality, self.subsampling, 0, 0)
+            ctx._check(ctx._lib.r2f_jpeg_rows_begin_ex(ctx._h, H, W, C.byref(opts), self.out.data_ptr(), bound,
+                                                       self.length.data_ptr(), ctx._stream()))
         self.next_row, self.done = 0, False
 
     def rows(self, image_u8, y0: int, y1: int):
         """Encode rows [y0, y1) of `image_u8`, the whole uint8 (H, W, 3) device frame (rows may be strided, pixels packed; only
-        these rows are read).  y0: where the call before ended (0 at first); y1: a multiple of 16 past y0, or H (the last call)."""
+        these rows are read).  y0: where the call before ended (0 at first); y1: a multiple of the MCU height (16, or 8 for 4:2:2
+        and 4:4:4) past y0, or H (the last call)."""
         torch, ctx = self._ctx._torch, self._ctx
         if not (isinstance(image_u8, torch.Tensor) and image_u8.is_cuda and image_u8.dtype == torch.uint8 and image_u8.dim() == 3
                 and tuple(image_u8.shape) == (self.H, self.W, 3) and image_u8.stride(2) == 1 and image_u8.stride(1) == 3):

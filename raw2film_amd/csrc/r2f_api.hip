@@ -201,10 +201,12 @@ struct r2f_ctx {
     struct JpegRows {
         bool open = false;
         int H = 0, W = 0, next_y = 0;
+        int sampling = 2, header_len = 0;
         uint8_t* out = nullptr;
         uint64_t* out_len = nullptr;
     } jpeg_rows;
     DeviceBuf jpeg_carry;
+    DeviceBuf jpeg_freq;  // r2f_jpeg_encode_ex with optimize: the frame's symbol counts, uint64 [4][256]
 };
 
 namespace {
@@ -943,6 +945,7 @@ void r2f_destroy(r2f_ctx* ctx) {
     ctx->dyn_flags.release();
     ctx->jpeg_scratch.release();
     ctx->jpeg_carry.release();
+    ctx->jpeg_freq.release();
     ctx->lut2d_buf.release();
     ctx->lut3d_buf.release();
     ctx->curve_buf.release();
@@ -1843,20 +1846,25 @@ int r2f_stage_noise(r2f_ctx* ctx, const r2f_params* p, uint32_t* hash_planes, fl
 
 namespace {
 
-// What r2f_jpeg_encode and r2f_jpeg_rows_begin check of a frame and its output; then the scratch grown to the frame.
+// What r2f_jpeg_encode_ex and r2f_jpeg_rows_begin_ex check of a frame and its output; then the scratch grown to the frame.
 // (row_stride < 0: no image yet)
-int jpeg_prepare(r2f_ctx* ctx, int H, int W, int64_t row_stride, int quality, uint8_t* out, uint64_t out_cap, uint64_t* out_len) {
-    if (!out || !out_len) return fail(ctx, R2F_EINVAL, "jpeg: null output or length pointer");
+int jpeg_prepare(r2f_ctx* ctx, int H, int W, int64_t row_stride, const r2f_jpeg_opts* o, uint8_t* out, uint64_t out_cap,
+                 uint64_t* out_len) {
+    if (!out || !out_len || !o) return fail(ctx, R2F_EINVAL, "jpeg: null output, length or options pointer");
     if (H < 1 || W < 1 || H > jpeg::kMaxDim || W > jpeg::kMaxDim)
         return fail(ctx, R2F_EINVAL, "jpeg: a %d x %d frame (JPEG holds 1 .. %d pixels per side)", H, W, jpeg::kMaxDim);
-    if (quality < 0 || quality > 100) return fail(ctx, R2F_EINVAL, "jpeg: quality %d is not in 0 .. 100", quality);
+    if (o->quality < 0 || o->quality > 100) return fail(ctx, R2F_EINVAL, "jpeg: quality %d is not in 0 .. 100", o->quality);
+    if (!jpeg::valid_sampling(o->sampling))
+        return fail(ctx, R2F_EINVAL, "jpeg: sampling %d is not 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0)", o->sampling);
+    if (o->optimize != 0 && o->optimize != 1) return fail(ctx, R2F_EINVAL, "jpeg: optimize %d is not 0 or 1", o->optimize);
+    if (o->reserved) return fail(ctx, R2F_EINVAL, "jpeg: reserved option %d is not 0", o->reserved);
     if (row_stride >= 0 && row_stride < 3LL * W)
         return fail(ctx, R2F_EINVAL, "jpeg: row stride %lld < 3 W = %lld", (long long)row_stride, 3LL * W);
     if ((uintptr_t)out_len % 8) return fail(ctx, R2F_EINVAL, "jpeg: out_len must be 8-byte aligned");
-    const uint64_t bound = jpeg::bound_bytes(H, W);
+    const uint64_t bound = jpeg::bound_bytes(H, W, o->sampling);
     if (out_cap < bound)
         return fail(ctx, R2F_EINVAL, "jpeg: output capacity %llu < bound %llu", (unsigned long long)out_cap, (unsigned long long)bound);
-    const jpeg::Scratch L = jpeg::scratch_layout(H, W);
+    const jpeg::Scratch L = jpeg::scratch_layout(H, W, o->sampling);
     if (ctx->jpeg_scratch.bytes < L.total) {
         R2F_HIP(ctx, hipDeviceSynchronize());  // (an earlier encode may still be working in the old buffer)
         ctx->jpeg_scratch.release();
@@ -1866,47 +1874,99 @@ int jpeg_prepare(r2f_ctx* ctx, int H, int W, int64_t row_stride, int quality, ui
     return R2F_OK;
 }
 
+// The standard tables and header of an encode.
+int jpeg_std_setup(r2f_ctx* ctx, const r2f_jpeg_opts* o, int H, int W, JpegEncodeArgs* a, uint8_t* hdr, size_t cap) {
+    jpeg::Huffman h;
+    jpeg::std_huffman(&h);
+    jpeg::make_tables(o->quality, h, &a->tables);
+    const int n = jpeg::header(o->quality, o->sampling, h, H, W, hdr, cap);
+    if (n < 0) return fail(ctx, R2F_EINVAL, "jpeg: header");
+    a->header = hdr, a->header_len = n, a->sampling = o->sampling;
+    return R2F_OK;
+}
+
 }  // namespace
 
-int r2f_jpeg_encode(r2f_ctx* ctx, const uint8_t* image, int H, int W, int64_t row_stride, int quality, uint8_t* out,
-                    uint64_t out_cap, uint64_t* out_len, void* stream) {
+int r2f_jpeg_encode_ex(r2f_ctx* ctx, const uint8_t* image, int H, int W, int64_t row_stride, const r2f_jpeg_opts* opts, uint8_t* out,
+                       uint64_t out_cap, uint64_t* out_len, void* stream) {
     if (!ctx) return R2F_EINVAL;
     R2F_GUARD(ctx);
     ctx->jpeg_rows.open = false;  // (this encode works in the scratch an open row-wise one keeps its frame's state in)
     if (!image || !out || !out_len) return fail(ctx, R2F_EINVAL, "jpeg: null image, output or length pointer");
-    int rc = jpeg_prepare(ctx, H, W, row_stride < 0 ? 0 : row_stride, quality, out, out_cap, out_len);
+    int rc = jpeg_prepare(ctx, H, W, row_stride < 0 ? 0 : row_stride, opts, out, out_cap, out_len);
     if (rc) return rc;
+    const hipStream_t s = static_cast<hipStream_t>(stream);
     JpegEncodeArgs a;
     a.image = image, a.row_stride = row_stride, a.H = H, a.W = W, a.scratch = ctx->jpeg_scratch.p;
-    jpeg::make_tables(quality, &a.tables);
+    a.out = out, a.out_len = reinterpret_cast<unsigned long long*>(out_len);
     uint8_t hdr[jpeg::kHeaderBytes];
-    if (jpeg::header(quality, H, W, hdr, sizeof hdr) != jpeg::kHeaderBytes) return fail(ctx, R2F_EINVAL, "jpeg: header");
-    a.header = hdr, a.out = out, a.out_len = reinterpret_cast<unsigned long long*>(out_len);
-    R2F_HIP(ctx, launch_jpeg_encode(a, static_cast<hipStream_t>(stream)));
+    if ((rc = jpeg_std_setup(ctx, opts, H, W, &a, hdr, sizeof hdr))) return rc;
+    if (opts->optimize) {
+        // the frame's symbol counts (the one synchronisation), then its tables and header (libjpeg's optimize_coding)
+        if (!ctx->jpeg_freq.p) {
+            R2F_HIP(ctx, hipMalloc(&ctx->jpeg_freq.p, 4 * 256 * sizeof(uint64_t)));
+            ctx->jpeg_freq.bytes = 4 * 256 * sizeof(uint64_t);
+        }
+        unsigned long long* freq_dev = static_cast<unsigned long long*>(ctx->jpeg_freq.p);
+        R2F_HIP(ctx, launch_jpeg_stats(a, freq_dev, s));
+        uint64_t freq[4][256];
+        R2F_HIP(ctx, hipMemcpyAsync(freq, freq_dev, sizeof freq, hipMemcpyDeviceToHost, s));
+        R2F_HIP(ctx, hipStreamSynchronize(s));
+        jpeg::Huffman h{};
+        for (int t = 0; t < 4; ++t) {
+            uint8_t bits[17];
+            const int n = jpeg::optimal_table(freq[t], bits, h.huffval[t]);
+            if (n < 0) return fail(ctx, R2F_ETOOLARGE, "jpeg: the symbol counts of table %d pass libjpeg's 10^9 sentinel", t);
+            if (n < 1 || n > (t % 2 ? 162 : 12)) return fail(ctx, R2F_EHIP, "jpeg: optimized table %d has %d symbols", t, n);
+            for (int i = 0; i < 16; ++i) h.bits[t][i] = bits[i + 1];
+            h.n[t] = n;
+        }
+        if (jpeg::scan_bits(freq, h) > jpeg::scan_bound_bits(H, W, opts->sampling))
+            return fail(ctx, R2F_ETOOLARGE, "jpeg: the optimized scan exceeds the bound");
+        jpeg::make_tables(opts->quality, h, &a.tables);
+        const int n = jpeg::header(opts->quality, opts->sampling, h, H, W, hdr, sizeof hdr);
+        if (n < 0) return fail(ctx, R2F_EINVAL, "jpeg: header");
+        a.header_len = n, a.recount = true;
+    }
+    R2F_HIP(ctx, launch_jpeg_encode(a, s));
     return R2F_OK;
 }
 
-int r2f_jpeg_rows_begin(r2f_ctx* ctx, int H, int W, int quality, uint8_t* out, uint64_t out_cap, uint64_t* out_len, void* stream) {
+int r2f_jpeg_encode(r2f_ctx* ctx, const uint8_t* image, int H, int W, int64_t row_stride, int quality, uint8_t* out,
+                    uint64_t out_cap, uint64_t* out_len, void* stream) {
+    const r2f_jpeg_opts o{quality, 2, 0, 0};
+    return r2f_jpeg_encode_ex(ctx, image, H, W, row_stride, &o, out, out_cap, out_len, stream);
+}
+
+int r2f_jpeg_rows_begin_ex(r2f_ctx* ctx, int H, int W, const r2f_jpeg_opts* opts, uint8_t* out, uint64_t out_cap, uint64_t* out_len,
+                           void* stream) {
     if (!ctx) return R2F_EINVAL;
     R2F_GUARD(ctx);
     ctx->jpeg_rows.open = false;
-    int rc = jpeg_prepare(ctx, H, W, -1, quality, out, out_cap, out_len);
+    int rc = jpeg_prepare(ctx, H, W, -1, opts, out, out_cap, out_len);
     if (rc) return rc;
+    if (opts->optimize)
+        return fail(ctx, R2F_EINVAL, "jpeg rows: optimize needs the whole frame's statistics before the first scan byte");
     if (!ctx->jpeg_carry.p) {
         R2F_HIP(ctx, hipMalloc(&ctx->jpeg_carry.p, 64));
         ctx->jpeg_carry.bytes = 64;
     }
     JpegEncodeArgs a;
     a.image = nullptr, a.row_stride = 0, a.H = H, a.W = W, a.scratch = ctx->jpeg_scratch.p, a.carry = ctx->jpeg_carry.p;
-    jpeg::make_tables(quality, &a.tables);
     uint8_t hdr[jpeg::kHeaderBytes];
-    if (jpeg::header(quality, H, W, hdr, sizeof hdr) != jpeg::kHeaderBytes) return fail(ctx, R2F_EINVAL, "jpeg: header");
-    a.header = hdr, a.out = out, a.out_len = reinterpret_cast<unsigned long long*>(out_len);
+    if ((rc = jpeg_std_setup(ctx, opts, H, W, &a, hdr, sizeof hdr))) return rc;
+    a.out = out, a.out_len = reinterpret_cast<unsigned long long*>(out_len);
     R2F_HIP(ctx, launch_jpeg_rows_begin(a, static_cast<hipStream_t>(stream)));
     ctx->jpeg_rows.open = true;
     ctx->jpeg_rows.H = H, ctx->jpeg_rows.W = W, ctx->jpeg_rows.next_y = 0;
+    ctx->jpeg_rows.sampling = opts->sampling, ctx->jpeg_rows.header_len = a.header_len;
     ctx->jpeg_rows.out = out, ctx->jpeg_rows.out_len = out_len;
     return R2F_OK;
+}
+
+int r2f_jpeg_rows_begin(r2f_ctx* ctx, int H, int W, int quality, uint8_t* out, uint64_t out_cap, uint64_t* out_len, void* stream) {
+    const r2f_jpeg_opts o{quality, 2, 0, 0};
+    return r2f_jpeg_rows_begin_ex(ctx, H, W, &o, out, out_cap, out_len, stream);
 }
 
 int r2f_jpeg_rows(r2f_ctx* ctx, const uint8_t* image, int64_t row_stride, int y0, int y1, void* stream) {
@@ -1920,11 +1980,12 @@ int r2f_jpeg_rows(r2f_ctx* ctx, const uint8_t* image, int64_t row_stride, int y0
         return fail(ctx, R2F_EINVAL, "jpeg rows: row stride %lld < 3 W = %lld", (long long)row_stride, 3LL * r.W);
     if (y0 != r.next_y) return fail(ctx, R2F_EINVAL, "jpeg rows: rows from %d, but the encode is at row %d", y0, r.next_y);
     jpeg::RowsGrid g;
-    if (!jpeg::rows_grid(r.H, r.W, y0, y1, &g))
-        return fail(ctx, R2F_EINVAL, "jpeg rows: rows [%d, %d) of %d: the end must lie past the start and be a multiple of 16 or %d",
-                    y0, y1, r.H, r.H);
+    if (!jpeg::rows_grid(r.H, r.W, r.sampling, y0, y1, &g))
+        return fail(ctx, R2F_EINVAL, "jpeg rows: rows [%d, %d) of %d: the end must lie past the start and be a multiple of %d or %d",
+                    y0, y1, r.H, jpeg::layout(r.sampling).mh, r.H);
     JpegEncodeArgs a;
     a.image = image, a.row_stride = row_stride, a.H = r.H, a.W = r.W, a.scratch = ctx->jpeg_scratch.p, a.carry = ctx->jpeg_carry.p;
+    a.sampling = r.sampling, a.header_len = r.header_len;
     a.header = nullptr, a.out = r.out, a.out_len = reinterpret_cast<unsigned long long*>(r.out_len);
     const bool last = y1 == r.H;
     R2F_HIP(ctx, launch_jpeg_rows(a, g, last, static_cast<hipStream_t>(stream)));

@@ -9,6 +9,13 @@
 //                  atomic OR only for the first and last word, which it may share with its neighbours
 //   5. stuffing    0xFF bytes counted per 4 KB chunk, scanned, and the bytes scattered with a 0x00 behind every 0xFF; the last byte
 //                  is padded with 1-bits first (jchuff.c flush_bits); header, EOI and the file's length are written last
+// Samplings (r2f_jpeg_encode_ex): the MCU kernels are templated on it -- 4:2:0 as above; 4:2:2 (h2v1) 16 x 8 MCUs of Y0 Y1 Cb Cr,
+// chroma pairs averaged with bias 0, 1, 0, 1 (jcsample.c h2v1_downsample), a dummy Y1 when the luma blocks per row are odd;
+// 4:4:4 (h1v1) 8 x 8 MCUs of Y Cb Cr at full size, no dummies.  The DC predictors run across the whole frame in each.
+// optimize (one-shot only): transform stores the coefficients; a stats kernel counts their symbols as libjpeg's gather pass does
+// (jchuff.c htest_one_block) into per-workgroup LDS histograms, added into 4 x 256 global counts; the host reads the counts back,
+// builds the tables (jpeg_gen_optimal_table, r2f_jpeg_plan.cpp) and the header, and a bits kernel recounts each MCU's bits with
+// those tables before the scan, pack and stuffing passes run as above.  The header's length is a launch argument.
 // Row-wise (r2f_jpeg_rows_begin / r2f_jpeg_rows): the same passes over the MCU rows of one call, [m0, m1).  The coefficients of
 // the whole frame stay in the scratch, so the first MCU's DC prediction reads the last MCU of the call before; the bit scan starts
 // at the carried bit count, the words cleared start at the first one not yet touched (the last one of the call before is shared),
@@ -29,6 +36,13 @@ using jpeg::Tables;
 
 constexpr int kWaves = 4;          // MCUs per workgroup of the transform and pack kernels (one per wave)
 constexpr int kPackWords = 320;    // LDS words per wave in pack: an MCU spans at most (31 + 6 * 1660 + 31) / 32 = 313
+constexpr int kStatsGroups = 1024; // workgroups of the stats kernel (each walks MCUs, then adds its histograms: <= 1024 atomics)
+
+// An MCU's shape per sampling (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0): pixels, luminance blocks, all blocks (Y.. Cb Cr)
+template <int S> struct Mcu;
+template <> struct Mcu<0> { static constexpr int MW = 8, MH = 8, NY = 1, NB = 3; };
+template <> struct Mcu<1> { static constexpr int MW = 16, MH = 8, NY = 2, NB = 4; };
+template <> struct Mcu<2> { static constexpr int MW = 16, MH = 16, NY = 4, NB = 6; };
 
 __constant__ uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                                     41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
@@ -43,7 +57,7 @@ struct EncodeArgs {
     long long m0, m1;  // the MCUs this launch encodes (one-shot: 0, n_mcus)
     int last;          // the scan ends with this launch: its bytes run to the padded last one
     const Tables* tables;
-    int16_t* coefs;    // [n_mcus][6][64]
+    int16_t* coefs;    // [n_mcus][blocks per MCU][64]
     u64* offsets;      // [n_mcus + 1]
     uint32_t* words;
     u64* chunks;       // [n_chunks + 1]
@@ -51,6 +65,7 @@ struct EncodeArgs {
     u64 bound_bits;
     uint8_t* out;
     u64* out_len;
+    int hdr_len;       // the header's bytes (the scan starts there)
 };
 
 struct HeaderBytes {
@@ -138,8 +153,10 @@ __device__ inline int lane_bits(const uint32_t* dc, const uint32_t* ac, int v, i
     return bits;
 }
 
+template <int S>
 __global__ __launch_bounds__(256) void jpeg_transform_kernel(EncodeArgs a) {
-    __shared__ int blk[kWaves][6][64];  // Y0 Y1 Y2 Y3 Cb Cr of each wave's MCU
+    using L = Mcu<S>;
+    __shared__ int blk[kWaves][L::NB][64];  // Y0 Y1 Y2 Y3 Cb Cr of each wave's MCU (4:2:2: Y0 Y1 Cb Cr, 4:4:4: Y Cb Cr)
     __shared__ uint32_t s_dc[2][16], s_ac[2][256];
     __shared__ uint16_t s_q[2][64];
     for (int i = threadIdx.x; i < 2 * 256; i += blockDim.x) (&s_ac[0][0])[i] = (&a.tables->ac[0][0])[i];
@@ -152,8 +169,35 @@ __global__ __launch_bounds__(256) void jpeg_transform_kernel(EncodeArgs a) {
     int(*B)[64] = blk[w];
     const int H = a.H, W = a.W;
     const int ywb = (W + 7) / 8, yhb = (H + 7) / 8, hc = (H + 1) / 2;
-    const bool right_dummy = 2 * mx + 1 >= ywb, bottom_dummy = 2 * my + 1 >= yhb;
-    if (live) {
+    const bool right_dummy = S != 0 && 2 * mx + 1 >= ywb, bottom_dummy = S == 2 && 2 * my + 1 >= yhb;
+    (void)hc;
+    if constexpr (S == 0) {
+        if (live) {  // one pixel per lane, edges replicated (no downsampling, no dummies)
+            const int cy = lane >> 3, cx = lane & 7;
+            const uint8_t* p = a.img + (long long)min(my * 8 + cy, H - 1) * a.stride + (long long)min(mx * 8 + cx, W - 1) * 3;
+            const int r = p[0], g = p[1], b = p[2];
+            B[0][lane] = ((19595 * r + 38470 * g + 7471 * b + 32768) >> 16) - 128;
+            B[1][lane] = ((-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16) - 128;
+            B[2][lane] = ((32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16) - 128;
+        }
+    } else if constexpr (S == 1) {
+        if (live) {  // the lane's horizontal pair: two luminance samples and one chroma sample (rows past the frame repeat its last)
+            const int cy = lane >> 3, cx = lane & 7;
+            const int y = min(my * 8 + cy, H - 1), gx = mx * 8 + cx;
+            int cb = 0, cr = 0;
+            for (int dx = 0; dx < 2; ++dx) {
+                const int lx = 2 * cx + dx;
+                const uint8_t* p = a.img + (long long)y * a.stride + (long long)min(mx * 16 + lx, W - 1) * 3;
+                const int r = p[0], g = p[1], b = p[2];
+                B[lx >> 3][cy * 8 + (lx & 7)] = ((19595 * r + 38470 * g + 7471 * b + 32768) >> 16) - 128;
+                cb += (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
+                cr += (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+            }
+            const int bias = gx & 1;  // h2v1_downsample: 0, 1, 0, 1 ... along the row
+            B[2][lane] = ((cb + bias) >> 1) - 128;
+            B[3][lane] = ((cr + bias) >> 1) - 128;
+        }
+    } else if (live) {
         const int cy = lane >> 3, cx = lane & 7;
         auto rgb = [&](int y, int x, int& r, int& g, int& b) {
             const uint8_t* p = a.img + (long long)y * a.stride + (long long)x * 3;
@@ -183,7 +227,7 @@ __global__ __launch_bounds__(256) void jpeg_transform_kernel(EncodeArgs a) {
         B[5][lane] = ((cr + bias) >> 2) - 128;
     }
     __syncthreads();
-    if (live && lane < 48) {  // rows: lane = block * 8 + row
+    if (live && lane < L::NB * 8) {  // rows: lane = block * 8 + row
         int* row = &B[lane >> 3][(lane & 7) * 8];
         int d[8];
         for (int i = 0; i < 8; ++i) d[i] = row[i];
@@ -191,9 +235,9 @@ __global__ __launch_bounds__(256) void jpeg_transform_kernel(EncodeArgs a) {
         for (int i = 0; i < 8; ++i) row[i] = d[i];
     }
     __syncthreads();
-    if (live && lane < 48) {  // columns, then quantisation
+    if (live && lane < L::NB * 8) {  // columns, then quantisation
         const int k = lane >> 3, c = lane & 7;
-        const uint16_t* q = s_q[k < 4 ? 0 : 1];
+        const uint16_t* q = s_q[k < L::NY ? 0 : 1];
         int d[8];
         for (int i = 0; i < 8; ++i) d[i] = B[k][i * 8 + c];
         fdct8(d, false);
@@ -204,24 +248,26 @@ __global__ __launch_bounds__(256) void jpeg_transform_kernel(EncodeArgs a) {
     // past the bottom the DC of the block before that row (Y1); all of their AC coefficients are zero
     if (live && right_dummy) B[1][lane] = lane ? 0 : B[0][0];
     __syncthreads();
-    if (live && (bottom_dummy || right_dummy)) {
-        const int dc = bottom_dummy ? B[1][0] : B[2][0];
-        if (bottom_dummy) B[2][lane] = lane ? 0 : dc;
-        B[3][lane] = lane ? 0 : dc;
+    if constexpr (S == 2) {
+        if (live && (bottom_dummy || right_dummy)) {
+            const int dc = bottom_dummy ? B[1][0] : B[2][0];
+            if (bottom_dummy) B[2][lane] = lane ? 0 : dc;
+            B[3][lane] = lane ? 0 : dc;
+        }
+        __syncthreads();
     }
-    __syncthreads();
     if (!live) return;
     int bits = 0;
-    int16_t* out = a.coefs + m * 384;
-    for (int k = 0; k < 6; ++k) {
-        const int t = k < 4 ? 0 : 1;
+    int16_t* out = a.coefs + m * (L::NB * 64);
+    for (int k = 0; k < L::NB; ++k) {
+        const int t = k < L::NY ? 0 : 1;
         const int v = B[k][kZigzag[lane]];
         out[k * 64 + lane] = (int16_t)v;
         const u64 nz = __ballot(lane > 0 && v != 0);
         // (the first block of each component takes its DC difference from the MCU before: dc_bits adds that)
-        const int dd = (k >= 1 && k <= 3) ? v - B[k - 1][0] : 0;
+        const int dd = (k >= 1 && k < L::NY) ? v - B[k - 1][0] : 0;
         int lb = lane_bits(s_dc[t], s_ac[t], v, dd, nz, lane);
-        if (lane == 0 && !(k >= 1 && k <= 3)) lb -= sym_len(s_dc[t][0]);
+        if (lane == 0 && !(k >= 1 && k < L::NY)) lb -= sym_len(s_dc[t][0]);
         bits += lb;
     }
     for (int d = 32; d >= 1; d >>= 1) bits += __shfl_xor(bits, d, 64);
@@ -234,13 +280,86 @@ __device__ inline int dc_bits(const Tables* t, int c, int diff) {
     return sym_len(t->dc[c][n]) + n;
 }
 
+template <int S>
 __global__ __launch_bounds__(256) void jpeg_dc_bits_kernel(EncodeArgs a) {
+    constexpr int NY = Mcu<S>::NY, NB = Mcu<S>::NB;
     const long long m = a.m0 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= a.m1) return;
-    const int16_t* c = a.coefs + m * 384;
-    const int16_t* p = m ? c - 384 : nullptr;
-    a.offsets[m] += (u64)(dc_bits(a.tables, 0, c[0] - (p ? p[3 * 64] : 0)) + dc_bits(a.tables, 1, c[4 * 64] - (p ? p[4 * 64] : 0)) +
-                          dc_bits(a.tables, 1, c[5 * 64] - (p ? p[5 * 64] : 0)));
+    const int16_t* c = a.coefs + m * (NB * 64);
+    const int16_t* p = m ? c - NB * 64 : nullptr;
+    a.offsets[m] += (u64)(dc_bits(a.tables, 0, c[0] - (p ? p[(NY - 1) * 64] : 0)) +
+                          dc_bits(a.tables, 1, c[NY * 64] - (p ? p[NY * 64] : 0)) +
+                          dc_bits(a.tables, 1, c[(NY + 1) * 64] - (p ? p[(NY + 1) * 64] : 0)));
+}
+
+// The DC prediction of block k of an MCU (c) after the MCU p (nullptr: the first MCU): the block before of the same component.
+template <int S>
+__device__ inline int dc_pred(const int16_t* c, const int16_t* p, int k) {
+    constexpr int NY = Mcu<S>::NY;
+    return k >= 1 && k < NY ? c[(k - 1) * 64] : (p ? p[(k == 0 ? NY - 1 : k) * 64] : 0);
+}
+
+// ------------------------------------------------------------------------------------------------------ optimize: stats, bits
+// libjpeg's gather pass (jchuff.c htest_one_block) over the stored coefficients: per block the DC difference's category, a ZRL
+// per 16 zeros before a non-zero coefficient, (run << 4) | size, and the EOB when the last non-zero coefficient is before 63.
+// freq[DC0, AC0, DC1, AC1][256] (zeroed before): luminance into tables 0, Cb and Cr into tables 1.  Each workgroup walks MCUs
+// into LDS histograms, then adds its non-zero bins with one 64-bit atomic each (integer sums: the result is deterministic).
+template <int S>
+__global__ __launch_bounds__(256) void jpeg_stats_kernel(EncodeArgs a, u64* freq) {
+    using L = Mcu<S>;
+    __shared__ uint32_t h[4][256];
+    for (int i = threadIdx.x; i < 4 * 256; i += blockDim.x) (&h[0][0])[i] = 0;
+    __syncthreads();
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (long long m = a.m0 + (long long)blockIdx.x * kWaves + w; m < a.m1; m += (long long)gridDim.x * kWaves) {
+        const int16_t* c = a.coefs + m * (L::NB * 64);
+        const int16_t* p = m ? c - L::NB * 64 : nullptr;
+        for (int k = 0; k < L::NB; ++k) {
+            const int t = k < L::NY ? 0 : 1;
+            const int v = c[k * 64 + lane];
+            const u64 nz = __ballot(lane > 0 && v != 0);
+            const u64 mask = nz | 1ull;
+            if (lane == 0) {
+                atomicAdd(&h[2 * t][min(magnitude_bits(v - dc_pred<S>(c, p, k)), 11)], 1u);
+            } else if (v != 0) {
+                const int prev = 63 - __clzll(mask & ((1ull << lane) - 1));
+                const int run = lane - prev - 1;
+                if (run >> 4) atomicAdd(&h[2 * t + 1][0xF0], (uint32_t)(run >> 4));
+                atomicAdd(&h[2 * t + 1][((run & 15) << 4) | min(magnitude_bits(v), 10)], 1u);
+            }
+            const int last = 63 - __clzll(mask);
+            if (lane == last && last < 63) atomicAdd(&h[2 * t + 1][0x00], 1u);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 4 * 256; i += blockDim.x) {
+        const uint32_t n = (&h[0][0])[i];
+        if (n) atomicAdd((unsigned long long*)&freq[i], (unsigned long long)n);
+    }
+}
+
+// Each MCU's bits with the tables in the scratch (the optimized ones), its DC differences included: offsets[m].
+template <int S>
+__global__ __launch_bounds__(256) void jpeg_bits_kernel(EncodeArgs a) {
+    using L = Mcu<S>;
+    __shared__ uint32_t s_dc[2][16], s_ac[2][256];
+    for (int i = threadIdx.x; i < 2 * 256; i += blockDim.x) (&s_ac[0][0])[i] = (&a.tables->ac[0][0])[i];
+    if (threadIdx.x < 32) (&s_dc[0][0])[threadIdx.x] = (&a.tables->dc[0][0])[threadIdx.x];
+    __syncthreads();
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long m = a.m0 + (long long)blockIdx.x * kWaves + w;
+    if (m >= a.m1) return;
+    const int16_t* c = a.coefs + m * (L::NB * 64);
+    const int16_t* p = m ? c - L::NB * 64 : nullptr;
+    int bits = 0;
+    for (int k = 0; k < L::NB; ++k) {
+        const int t = k < L::NY ? 0 : 1;
+        const int v = c[k * 64 + lane];
+        const u64 nz = __ballot(lane > 0 && v != 0);
+        bits += lane_bits(s_dc[t], s_ac[t], v, v - dc_pred<S>(c, p, k), nz, lane);
+    }
+    for (int d = 32; d >= 1; d >>= 1) bits += __shfl_xor(bits, d, 64);
+    if (lane == 0) a.offsets[m] = (u64)bits;
 }
 
 // --------------------------------------------------------------------------------------------------------------- 3. scan
@@ -309,7 +428,9 @@ __device__ inline void put_bits(uint32_t* lds, int pos, uint32_t v, int len) {
     if ((uint32_t)x) atomicOr(&lds[(pos >> 5) + 1], (uint32_t)x);
 }
 
+template <int S>
 __global__ __launch_bounds__(256) void jpeg_pack_kernel(EncodeArgs a) {
+    using L = Mcu<S>;
     __shared__ uint32_t s_words[kWaves][kPackWords];
     __shared__ uint32_t s_dc[2][16], s_ac[2][256];
     for (int i = threadIdx.x; i < 2 * 256; i += blockDim.x) (&s_ac[0][0])[i] = (&a.tables->ac[0][0])[i];
@@ -323,15 +444,15 @@ __global__ __launch_bounds__(256) void jpeg_pack_kernel(EncodeArgs a) {
     const u64 start = live ? a.offsets[m] : 0, end = live ? a.offsets[m + 1] : 0;
     const int nw = live ? (int)(((start & 31) + (end - start) + 31) >> 5) : 0;
     if (live && nw <= kPackWords) {
-        const int16_t* c = a.coefs + m * 384;
-        const int16_t* p = m ? c - 384 : nullptr;
+        const int16_t* c = a.coefs + m * (L::NB * 64);
+        const int16_t* p = m ? c - L::NB * 64 : nullptr;
         int pos = (int)(start & 31);  // bit position in the wave's words
-        for (int k = 0; k < 6; ++k) {
-            const int t = k < 4 ? 0 : 1;
+        for (int k = 0; k < L::NB; ++k) {
+            const int t = k < L::NY ? 0 : 1;
             const uint32_t* dc = s_dc[t];
             const uint32_t* ac = s_ac[t];
             const int v = c[k * 64 + lane];
-            const int pred = k >= 1 && k <= 3 ? c[(k - 1) * 64] : (p ? p[(k == 0 ? 3 : k) * 64] : 0);
+            const int pred = dc_pred<S>(c, p, k);
             const u64 nz = __ballot(lane > 0 && v != 0);
             const int len = lane_bits(dc, ac, v, v - pred, nz, lane);
             const int inc = wave_inclusive<int>(len, lane);
@@ -423,7 +544,7 @@ __global__ __launch_bounds__(256) void jpeg_scatter_kernel(EncodeArgs a) {
     __syncthreads();
     u64 ff = a.chunks[blockIdx.x] + (u64)(inc - cnt);
     for (int i = 0; i < w; ++i) ff += (u64)wave_tot[i];
-    uint8_t* out = a.out + jpeg::kHeaderBytes;
+    uint8_t* out = a.out + a.hdr_len;
     for (int j = 0; j < 16; ++j) {
         if (b0 + j >= hi) break;
         const u64 o = b0 + j + ff;
@@ -442,9 +563,9 @@ __global__ __launch_bounds__(256) void jpeg_finish_kernel(EncodeArgs a, HeaderBy
         if (threadIdx.x == 0) *a.out_len = 0;
         return;
     }
-    for (int i = threadIdx.x; i < jpeg::kHeaderBytes; i += blockDim.x) a.out[i] = h.b[i];
+    for (int i = threadIdx.x; i < a.hdr_len; i += blockDim.x) a.out[i] = h.b[i];
     if (threadIdx.x == 0) {
-        const u64 end = jpeg::kHeaderBytes + (total + 7) / 8 + a.chunks[a.n_chunks];
+        const u64 end = (u64)a.hdr_len + (total + 7) / 8 + a.chunks[a.n_chunks];
         a.out[end] = 0xFF;
         a.out[end + 1] = 0xD9;
         *a.out_len = end + 2;
@@ -452,11 +573,11 @@ __global__ __launch_bounds__(256) void jpeg_finish_kernel(EncodeArgs a, HeaderBy
 }
 
 // Row-wise: the header, an empty carry ({bits, 0xFF bytes} so far) and *out_len = the header's length.
-__global__ __launch_bounds__(256) void jpeg_rows_begin_kernel(HeaderBytes h, uint8_t* out, u64* out_len, u64* carry) {
-    for (int i = threadIdx.x; i < jpeg::kHeaderBytes; i += blockDim.x) out[i] = h.b[i];
+__global__ __launch_bounds__(256) void jpeg_rows_begin_kernel(HeaderBytes h, int hdr_len, uint8_t* out, u64* out_len, u64* carry) {
+    for (int i = threadIdx.x; i < hdr_len; i += blockDim.x) out[i] = h.b[i];
     if (threadIdx.x == 0) {
         carry[0] = carry[1] = 0;
-        *out_len = jpeg::kHeaderBytes;
+        *out_len = (u64)hdr_len;
     }
 }
 
@@ -470,7 +591,7 @@ __global__ void jpeg_rows_finish_kernel(EncodeArgs a, long long n_chunks, u64* c
         return;
     }
     const u64 ff = a.chunks[n_chunks];
-    u64 end = jpeg::kHeaderBytes + (a.last ? (total + 7) / 8 : total / 8) + ff;
+    u64 end = (u64)a.hdr_len + (a.last ? (total + 7) / 8 : total / 8) + ff;
     if (a.last) {
         a.out[end] = 0xFF;
         a.out[end + 1] = 0xD9;
@@ -491,7 +612,8 @@ EncodeArgs encode_args(const JpegEncodeArgs& e, const jpeg::Scratch& L) {
     uint8_t* base = static_cast<uint8_t*>(e.scratch);
     EncodeArgs a;
     a.img = e.image, a.stride = e.row_stride, a.H = e.H, a.W = e.W;
-    a.mx_n = (e.W + 15) / 16;
+    const int mw = jpeg::layout(e.sampling).mw;
+    a.mx_n = (e.W + mw - 1) / mw;
     a.n_mcus = (long long)L.n_mcus;
     a.m0 = 0, a.m1 = a.n_mcus, a.last = 1;
     a.tables = reinterpret_cast<const Tables*>(base + L.tables);
@@ -500,33 +622,71 @@ EncodeArgs encode_args(const JpegEncodeArgs& e, const jpeg::Scratch& L) {
     a.words = reinterpret_cast<uint32_t*>(base + L.words);
     a.chunks = reinterpret_cast<u64*>(base + L.chunks);
     a.n_chunks = (long long)L.stuff_chunks;
-    a.bound_bits = jpeg::scan_bound_bits(e.H, e.W);
+    a.bound_bits = jpeg::scan_bound_bits(e.H, e.W, e.sampling);
     a.out = e.out, a.out_len = e.out_len;
+    a.hdr_len = e.header_len;
     return a;
 }
 
-HeaderBytes header_bytes(const uint8_t* header) {
-    HeaderBytes h;
-    for (int i = 0; i < jpeg::kHeaderBytes; ++i) h.b[i] = header[i];
+HeaderBytes header_bytes(const uint8_t* header, int len) {
+    HeaderBytes h{};
+    for (int i = 0; i < len; ++i) h.b[i] = header[i];
     return h;
+}
+
+// The MCU kernels of a sampling.
+struct McuKernels {
+    void (*transform)(EncodeArgs);
+    void (*dc_bits)(EncodeArgs);
+    void (*pack)(EncodeArgs);
+    void (*stats)(EncodeArgs, u64*);
+    void (*bits)(EncodeArgs);
+};
+template <int S>
+McuKernels mcu_kernels_of() {
+    return {jpeg_transform_kernel<S>, jpeg_dc_bits_kernel<S>, jpeg_pack_kernel<S>, jpeg_stats_kernel<S>, jpeg_bits_kernel<S>};
+}
+McuKernels mcu_kernels(int sampling) {
+    return sampling == 0 ? mcu_kernels_of<0>() : sampling == 1 ? mcu_kernels_of<1>() : mcu_kernels_of<2>();
 }
 
 }  // namespace
 
+hipError_t launch_jpeg_stats(const JpegEncodeArgs& e, unsigned long long* freq, hipStream_t s) {
+    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W, e.sampling);
+    const EncodeArgs a = encode_args(e, L);
+    const McuKernels K = mcu_kernels(e.sampling);
+    const unsigned mcu_groups = (unsigned)((L.n_mcus + kWaves - 1) / kWaves);
+    launch_k(jpeg_tables_kernel, dim3(1), dim3(256), 0, s, e.tables, const_cast<Tables*>(a.tables));
+    launch_k(K.transform, dim3(mcu_groups), dim3(256), 0, s, a);
+    hipError_t err = hipMemsetAsync(freq, 0, 4 * 256 * sizeof(u64), s);
+    if (err != hipSuccess) {
+        (void)take_launch_status();
+        return err;
+    }
+    launch_k(K.stats, dim3(std::min<unsigned>(mcu_groups, kStatsGroups)), dim3(256), 0, s, a, reinterpret_cast<u64*>(freq));
+    return take_launch_status();
+}
+
 hipError_t launch_jpeg_encode(const JpegEncodeArgs& e, hipStream_t s) {
-    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W);
+    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W, e.sampling);
     const EncodeArgs a = encode_args(e, L);
     u64* partial = reinterpret_cast<u64*>(static_cast<uint8_t*>(e.scratch) + L.partial);
-    const HeaderBytes h = header_bytes(e.header);
+    const HeaderBytes h = header_bytes(e.header, e.header_len);
+    const McuKernels K = mcu_kernels(e.sampling);
 
     const unsigned mcu_groups = (unsigned)((L.n_mcus + kWaves - 1) / kWaves);
     launch_k(jpeg_tables_kernel, dim3(1), dim3(256), 0, s, e.tables, const_cast<Tables*>(a.tables));
-    launch_k(jpeg_transform_kernel, dim3(mcu_groups), dim3(256), 0, s, a);
-    launch_k(jpeg_dc_bits_kernel, dim3((unsigned)((L.n_mcus + 255) / 256)), dim3(256), 0, s, a);
+    if (e.recount) {  // (optimize: the coefficients are in the scratch, launch_jpeg_stats made them)
+        launch_k(K.bits, dim3(mcu_groups), dim3(256), 0, s, a);
+    } else {
+        launch_k(K.transform, dim3(mcu_groups), dim3(256), 0, s, a);
+        launch_k(K.dc_bits, dim3((unsigned)((L.n_mcus + 255) / 256)), dim3(256), 0, s, a);
+    }
     scan_u64(a.offsets, a.n_mcus, partial, s);
     const u64 max_words = (a.bound_bits + 31) / 32;
     launch_k(jpeg_zero_kernel, dim3((unsigned)std::min<u64>((max_words + 255) / 256, 4096)), dim3(256), 0, s, a);
-    launch_k(jpeg_pack_kernel, dim3(mcu_groups), dim3(256), 0, s, a);
+    launch_k(K.pack, dim3(mcu_groups), dim3(256), 0, s, a);
     launch_k(jpeg_ff_count_kernel, dim3((unsigned)L.stuff_chunks), dim3(256), 0, s, a);
     scan_u64(a.chunks, a.n_chunks, partial, s);
     launch_k(jpeg_scatter_kernel, dim3((unsigned)L.stuff_chunks), dim3(256), 0, s, a);
@@ -535,17 +695,18 @@ hipError_t launch_jpeg_encode(const JpegEncodeArgs& e, hipStream_t s) {
 }
 
 hipError_t launch_jpeg_rows_begin(const JpegEncodeArgs& e, hipStream_t s) {
-    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W);
+    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W, e.sampling);
     Tables* tables = reinterpret_cast<Tables*>(static_cast<uint8_t*>(e.scratch) + L.tables);
     launch_k(jpeg_tables_kernel, dim3(1), dim3(256), 0, s, e.tables, tables);
-    launch_k(jpeg_rows_begin_kernel, dim3(1), dim3(256), 0, s, header_bytes(e.header), e.out, e.out_len,
+    launch_k(jpeg_rows_begin_kernel, dim3(1), dim3(256), 0, s, header_bytes(e.header, e.header_len), e.header_len, e.out, e.out_len,
              static_cast<u64*>(e.carry));
     return take_launch_status();
 }
 
 hipError_t launch_jpeg_rows(const JpegEncodeArgs& e, const jpeg::RowsGrid& g, bool last, hipStream_t s) {
-    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W);
+    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W, e.sampling);
     EncodeArgs a = encode_args(e, L);
+    const McuKernels K = mcu_kernels(e.sampling);
     a.m0 = (long long)g.m0, a.m1 = (long long)g.m1, a.last = last ? 1 : 0;
     a.n_chunks = (long long)g.stuff_chunks;
     u64* partial = reinterpret_cast<u64*>(static_cast<uint8_t*>(e.scratch) + L.partial);
@@ -553,11 +714,11 @@ hipError_t launch_jpeg_rows(const JpegEncodeArgs& e, const jpeg::RowsGrid& g, bo
 
     const long long n = a.m1 - a.m0;
     const unsigned mcu_groups = (unsigned)((n + kWaves - 1) / kWaves);
-    launch_k(jpeg_transform_kernel, dim3(mcu_groups), dim3(256), 0, s, a);
-    launch_k(jpeg_dc_bits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    launch_k(K.transform, dim3(mcu_groups), dim3(256), 0, s, a);
+    launch_k(K.dc_bits, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
     scan_u64(a.offsets + a.m0, n, partial, s, carry);  // offsets[m0] = the bits before, offsets[m1] = the bits after
     launch_k(jpeg_zero_kernel, dim3((unsigned)std::min<u64>((g.zero_words + 255) / 256, 4096)), dim3(256), 0, s, a);
-    launch_k(jpeg_pack_kernel, dim3(mcu_groups), dim3(256), 0, s, a);
+    launch_k(K.pack, dim3(mcu_groups), dim3(256), 0, s, a);
     launch_k(jpeg_ff_count_kernel, dim3((unsigned)g.stuff_chunks), dim3(256), 0, s, a);
     scan_u64(a.chunks, a.n_chunks, partial, s, carry + 1);
     launch_k(jpeg_scatter_kernel, dim3((unsigned)g.stuff_chunks), dim3(256), 0, s, a);

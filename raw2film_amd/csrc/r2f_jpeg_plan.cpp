@@ -60,12 +60,12 @@ const HuffSpec kHuff[4] = {
 const uint8_t kHuffId[4] = {0x00, 0x10, 0x01, 0x11};
 
 // Canonical codes of a table (jchuff.c jpeg_make_c_derived_tbl): out[symbol] = (code << 8) | length.
-void derive(const HuffSpec& h, uint32_t* out, int n_out) {
+void derive(const HuffSpec& h, const uint8_t* counts, uint32_t* out, int n_out) {
     std::fill(out, out + n_out, 0u);
     uint32_t code = 0;
     int k = 0;
     for (int len = 1; len <= 16; ++len) {
-        for (int i = 0; i < h.counts[len - 1]; ++i, ++k, ++code)
+        for (int i = 0; i < counts[len - 1] && k < h.n; ++i, ++k, ++code)
             if (h.symbols[k] < n_out) out[h.symbols[k]] = (code << 8) | (uint32_t)len;
         code <<= 1;
     }
@@ -89,19 +89,104 @@ void quant_tables(int quality, uint8_t out[2][64]) {
             out[t][i] = (uint8_t)std::min(std::max((kStdQuant[t][i] * scale + 50) / 100, 1L), 255L);
 }
 
-void make_tables(int quality, Tables* t) {
+void std_huffman(Huffman* h) {
+    std::memset(h, 0, sizeof *h);
+    for (int t = 0; t < 4; ++t) {
+        std::memcpy(h->bits[t], kHuff[t].counts, 16);
+        std::memcpy(h->huffval[t], kHuff[t].symbols, (size_t)kHuff[t].n);
+        h->n[t] = kHuff[t].n;
+    }
+}
+
+int optimal_table(const uint64_t freq_in[256], uint8_t bits_out[17], uint8_t huffval[256], bool* adjusted) {
+    constexpr int kMaxClen = 32;
+    uint64_t freq[257];
+    int bits[kMaxClen + 1] = {}, codesize[257] = {}, others[257];
+    for (int i = 0; i < 256; ++i) freq[i] = freq_in[i];
+    freq[256] = 1;  // the reserved symbol: no real symbol gets the all-ones code
+    for (int i = 0; i < 257; ++i) others[i] = -1;
+    for (;;) {
+        int c1 = -1, c2 = -1;
+        uint64_t v = 1000000000ULL;
+        for (int i = 0; i <= 256; ++i)  // the smallest non-zero count, ties to the larger symbol
+            if (freq[i] && freq[i] <= v) v = freq[i], c1 = i;
+        v = 1000000000ULL;
+        for (int i = 0; i <= 256; ++i)
+            if (freq[i] && freq[i] <= v && i != c1) v = freq[i], c2 = i;
+        if (c2 < 0) break;
+        freq[c1] += freq[c2];
+        freq[c2] = 0;
+        ++codesize[c1];
+        while (others[c1] >= 0) ++codesize[c1 = others[c1]];
+        others[c1] = c2;
+        ++codesize[c2];
+        while (others[c2] >= 0) ++codesize[c2 = others[c2]];
+    }
+    for (int i = 0; i <= 256; ++i)
+        if (codesize[i]) {
+            if (codesize[i] > kMaxClen) return -1;  // (libjpeg: JERR_HUFF_CLEN_OVERFLOW; 257 symbols cannot get there)
+            ++bits[codesize[i]];
+        }
+    if (adjusted) *adjusted = false;
+    int i = kMaxClen;
+    for (; i > 16; --i)
+        while (bits[i] > 0) {  // Annex K.3: fold a pair of the longest codes into the next length that is in use
+            int j = i - 2;
+            while (bits[j] == 0) --j;
+            bits[i] -= 2, ++bits[i - 1], bits[j + 1] += 2, --bits[j];
+            if (adjusted) *adjusted = true;
+        }
+    while (i > 0 && bits[i] == 0) --i;
+    if (i == 0) return -1;  // (only the reserved symbol: every count was zero)
+    --bits[i];
+    int n = 0;
+    bits_out[0] = 0;
+    for (int k = 1; k <= 16; ++k) bits_out[k] = (uint8_t)bits[k], n += bits[k];
+    // Counts past the sentinel stop the merging early and leave symbols without a code or lengths no prefix code can have; libjpeg
+    // then fails (jpeg_make_c_derived_tbl: JERR_BAD_HUFF_TABLE, or a missing code when the symbol is encoded).  Only frames with
+    // more than 10^9 symbols of one table can get there.
+    uint64_t code = 0;
+    for (int k = 1; k <= 16; ++k) {
+        code += bits[k];
+        if (code > (1ULL << k) - (k == 16 ? 1 : 0)) return -1;
+        code <<= 1;
+    }
+    for (int j = 0; j < 256; ++j)
+        if (freq_in[j] && !codesize[j]) return -1;
+    int p = 0;
+    for (int len = 1; len <= kMaxClen; ++len)
+        for (int j = 0; j <= 255; ++j)
+            if (codesize[j] == len) huffval[p++] = (uint8_t)j;
+    return n;
+}
+
+void make_tables(int quality, const Huffman& h, Tables* t) {
     std::memset(t, 0, sizeof *t);
     uint8_t q[2][64];
     quant_tables(quality, q);
     for (int c = 0; c < 2; ++c) {
-        derive(kHuff[2 * c], t->dc[c], 16);
-        derive(kHuff[2 * c + 1], t->ac[c], 256);
+        derive(HuffSpec{{}, h.huffval[2 * c], h.n[2 * c]}, h.bits[2 * c], t->dc[c], 16);
+        derive(HuffSpec{{}, h.huffval[2 * c + 1], h.n[2 * c + 1]}, h.bits[2 * c + 1], t->ac[c], 256);
         for (int i = 0; i < 64; ++i) t->qdiv[c][i] = (uint16_t)(q[c][i] * 8);
     }
 }
 
-int header(int quality, int H, int W, uint8_t* buf, size_t cap) {
-    if (!buf || cap < (size_t)kHeaderBytes || quality < 0 || quality > 100 || H < 1 || W < 1 || H > kMaxDim || W > kMaxDim) return -1;
+void make_tables(int quality, Tables* t) {
+    Huffman h;
+    std_huffman(&h);
+    make_tables(quality, h, t);
+}
+
+int header(int quality, int sampling, const Huffman& h, int H, int W, uint8_t* buf, size_t cap) {
+    if (!buf || !valid_sampling(sampling) || quality < 0 || quality > 100 || H < 1 || W < 1 || H > kMaxDim || W > kMaxDim) return -1;
+    int len = 275;  // everything but the DHT symbols
+    for (int t = 0; t < 4; ++t) {
+        int n = 0;
+        for (int i = 0; i < 16; ++i) n += h.bits[t][i];
+        if (n != h.n[t] || n < 1 || n > (t % 2 ? 162 : 12)) return -1;
+        len += n;
+    }
+    if (cap < (size_t)len) return -1;
     uint8_t q[2][64];
     quant_tables(quality, q);
     Writer w{buf};
@@ -113,18 +198,39 @@ int header(int quality, int H, int W, uint8_t* buf, size_t cap) {
         w.u8(t);
         for (int i = 0; i < 64; ++i) w.u8(q[t][kZigzag[i]]);
     }
-    w.marker(0xC0, 15);  // SOF0: 8 bits, 3 components, Y 2x2 (table 0), Cb and Cr 1x1 (table 1)
+    w.marker(0xC0, 15);  // SOF0: 8 bits, 3 components, Y 1x1 / 2x1 / 2x2 (table 0), Cb and Cr 1x1 (table 1)
     w.u8(8), w.u16(H), w.u16(W), w.u8(3);
-    for (int c : {1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1}) w.u8(c);
+    for (int c : {1, layout(sampling).y_factor, 0, 2, 0x11, 1, 3, 0x11, 1}) w.u8(c);
     for (int t = 0; t < 4; ++t) {
-        w.marker(0xC4, 17 + kHuff[t].n);
+        w.marker(0xC4, 17 + h.n[t]);
         w.u8(kHuffId[t]);
-        for (int i = 0; i < 16; ++i) w.u8(kHuff[t].counts[i]);
-        for (int i = 0; i < kHuff[t].n; ++i) w.u8(kHuff[t].symbols[i]);
+        for (int i = 0; i < 16; ++i) w.u8(h.bits[t][i]);
+        for (int i = 0; i < h.n[t]; ++i) w.u8(h.huffval[t][i]);
     }
     w.marker(0xDA, 10);  // SOS: 3 components (DC / AC tables 0/0, 1/1, 1/1), Ss 0, Se 63, Ah Al 0
     for (int c : {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0}) w.u8(c);
     return (int)w.n;
+}
+
+int header(int quality, int H, int W, uint8_t* buf, size_t cap) {
+    if (cap < (size_t)kHeaderBytes) return -1;
+    Huffman h;
+    std_huffman(&h);
+    return header(quality, 2, h, H, W, buf, cap);
+}
+
+uint64_t scan_bits(const uint64_t freq[4][256], const Huffman& h) {
+    uint64_t total = 0;
+    for (int t = 0; t < 4; ++t) {
+        uint32_t codes[256];
+        derive(HuffSpec{{}, h.huffval[t], h.n[t]}, h.bits[t], codes, 256);
+        for (int s = 0; s < 256; ++s) {
+            if (!freq[t][s]) continue;
+            if (!codes[s]) return UINT64_MAX;
+            total += freq[t][s] * (uint64_t)((codes[s] & 0xFF) + (t % 2 ? (s & 15) : s));
+        }
+    }
+    return total;
 }
 
 uint64_t scan_partials(uint64_t n) {
@@ -133,16 +239,18 @@ uint64_t scan_partials(uint64_t n) {
     return nb + 1 + scan_partials(nb);
 }
 
-Scratch scratch_layout(int H, int W) {
+Scratch scratch_layout(int H, int W) { return scratch_layout(H, W, 2); }
+
+Scratch scratch_layout(int H, int W, int sampling) {
     Scratch s{};
-    s.n_mcus = mcus(H, W);
-    const uint64_t scan_bytes = (scan_bound_bits(H, W) + 7) / 8;
+    s.n_mcus = mcus(H, W, sampling);
+    const uint64_t scan_bytes = (scan_bound_bits(H, W, sampling) + 7) / 8;
     s.stuff_chunks = (scan_bytes + kStuffChunk - 1) / kStuffChunk;
     s.scan_words = s.stuff_chunks * (kStuffChunk / 4);  // (the 0xFF passes read whole chunks)
     s.partial_elems = std::max(scan_partials(s.n_mcus), scan_partials(s.stuff_chunks));
     auto align = [](size_t v) { return (v + 15) & ~(size_t)15; };
     size_t at = 0;
-    s.coefs = at, at = align(at + s.n_mcus * 6 * 64 * sizeof(int16_t));
+    s.coefs = at, at = align(at + s.n_mcus * layout(sampling).nb * 64 * sizeof(int16_t));
     s.offsets = at, at = align(at + (s.n_mcus + 1) * sizeof(uint64_t));
     s.words = at, at = align(at + s.scan_words * sizeof(uint32_t));
     s.chunks = at, at = align(at + (s.stuff_chunks + 1) * sizeof(uint64_t));
@@ -152,15 +260,20 @@ Scratch scratch_layout(int H, int W) {
     return s;
 }
 
-bool rows_grid(int H, int W, int y0, int y1, RowsGrid* g) {
+bool rows_grid(int H, int W, int y0, int y1, RowsGrid* g) { return rows_grid(H, W, 2, y0, y1, g); }
+
+bool rows_grid(int H, int W, int sampling, int y0, int y1, RowsGrid* g) {
     *g = RowsGrid{};
-    if (H < 1 || W < 1 || H > kMaxDim || W > kMaxDim || y0 < 0 || y0 % 16 || y1 <= y0 || y1 > H || (y1 % 16 && y1 != H)) return false;
-    const uint64_t mx = (uint64_t)((W + 15) / 16);
-    g->m0 = (uint64_t)(y0 / 16) * mx;
-    g->m1 = (uint64_t)((y1 + 15) / 16) * mx;
-    const uint64_t bits = (g->m1 - g->m0) * 6 * kBlockBoundBits;
+    if (!valid_sampling(sampling)) return false;
+    const Layout l = layout(sampling);
+    if (H < 1 || W < 1 || H > kMaxDim || W > kMaxDim || y0 < 0 || y0 % l.mh || y1 <= y0 || y1 > H || (y1 % l.mh && y1 != H))
+        return false;
+    const uint64_t mx = (uint64_t)((W + l.mw - 1) / l.mw);
+    g->m0 = (uint64_t)(y0 / l.mh) * mx;
+    g->m1 = (uint64_t)((y1 + l.mh - 1) / l.mh) * mx;
+    const uint64_t bits = (g->m1 - g->m0) * l.nb * kBlockBoundBits;
     const uint64_t bytes = (bits + 7) / 8 + 1;  // [floor(before / 8), ceil(after / 8)): the carried partial byte, then the new ones
-    g->stuff_chunks = std::min((bytes + kStuffChunk - 1) / kStuffChunk, scratch_layout(H, W).stuff_chunks);
+    g->stuff_chunks = std::min((bytes + kStuffChunk - 1) / kStuffChunk, scratch_layout(H, W, sampling).stuff_chunks);
     g->zero_words = (bits + 31) / 32;  // [ceil(before / 32), ceil(after / 32))
     return true;
 }
@@ -181,6 +294,29 @@ int r2f_jpeg_header(int quality, int H, int W, uint8_t* buf, size_t cap, size_t*
 uint64_t r2f_jpeg_bound_bytes(int H, int W) {
     if (H < 1 || W < 1 || H > r2f::jpeg::kMaxDim || W > r2f::jpeg::kMaxDim) return 0;
     return r2f::jpeg::bound_bytes(H, W);
+}
+
+uint64_t r2f_jpeg_bound_bytes_ex(int H, int W, int sampling) {
+    if (H < 1 || W < 1 || H > r2f::jpeg::kMaxDim || W > r2f::jpeg::kMaxDim || !r2f::jpeg::valid_sampling(sampling)) return 0;
+    return r2f::jpeg::bound_bytes(H, W, sampling);
+}
+
+int r2f_jpeg_header_ex(const r2f_jpeg_opts* o, int H, int W, uint8_t* buf, size_t cap, size_t* len) {
+    if (!o || !len || o->optimize) return R2F_EINVAL;  // (an optimized header needs the frame's statistics: r2f_jpeg_encode_ex)
+    r2f::jpeg::Huffman h;
+    r2f::jpeg::std_huffman(&h);
+    const int n = r2f::jpeg::header(o->quality, o->sampling, h, H, W, buf, cap);
+    if (n < 0) return R2F_EINVAL;
+    *len = (size_t)n;
+    return R2F_OK;
+}
+
+int r2f_jpeg_optimal_table(const uint64_t freq[256], uint8_t bits[17], uint8_t huffval[256], int* n) {
+    if (!freq || !bits || !huffval || !n) return R2F_EINVAL;
+    const int k = r2f::jpeg::optimal_table(freq, bits, huffval);
+    if (k < 0) return R2F_EINVAL;
+    *n = k;
+    return R2F_OK;
 }
 
 }  // extern "C"

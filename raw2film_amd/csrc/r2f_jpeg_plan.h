@@ -39,6 +39,48 @@ inline uint64_t scan_bound_bits(int H, int W) { return mcus(H, W) * 6 * kBlockBo
 // Largest file for H x W at any quality: header, every scan byte stuffed, EOI.
 inline uint64_t bound_bytes(int H, int W) { return kHeaderBytes + 2 * ((scan_bound_bits(H, W) + 7) / 8) + 2; }
 
+// ---- Pillow's subsampling and optimize options.  sampling: 0 = 4:4:4 (h1v1), 1 = 4:2:2 (h2v1), 2 = 4:2:0 (h2v2, the default);
+// every overload below returns the function above's result for sampling 2.
+struct Layout {
+    int mw, mh;    // MCU width and height in pixels
+    int ny, nb;    // luminance blocks and all blocks per MCU (Y.. Cb Cr)
+    int y_factor;  // SOF0 sampling byte of Y
+};
+inline bool valid_sampling(int s) { return s >= 0 && s <= 2; }
+inline Layout layout(int sampling) {
+    return sampling == 0 ? Layout{8, 8, 1, 3, 0x11} : sampling == 1 ? Layout{16, 8, 2, 4, 0x21} : Layout{16, 16, 4, 6, 0x22};
+}
+inline uint64_t mcus(int H, int W, int sampling) {
+    const Layout l = layout(sampling);
+    return (uint64_t)((H + l.mh - 1) / l.mh) * (uint64_t)((W + l.mw - 1) / l.mw);
+}
+inline uint64_t scan_bound_bits(int H, int W, int sampling) { return mcus(H, W, sampling) * layout(sampling).nb * kBlockBoundBits; }
+inline uint64_t bound_bytes(int H, int W, int sampling) { return kHeaderBytes + 2 * ((scan_bound_bits(H, W, sampling) + 7) / 8) + 2; }
+
+// Huffman tables as DHT holds them, in DHT order DC0, AC0, DC1, AC1: code counts per length 1..16, then n symbols.
+struct Huffman {
+    uint8_t bits[4][16];
+    uint8_t huffval[4][256];
+    int n[4];
+};
+// Annex K.3's tables (what make_tables and header above use).
+void std_huffman(Huffman* h);
+// jchuff.c jpeg_gen_optimal_table, step for step: the reserved symbol 256 with count 1, the merge of the two smallest non-zero
+// counts (ties to the larger symbol, counts above the 1000000000 sentinel never taken), the codesize / others chains, Annex K.3's
+// folding of lengths over 16, the reserved code taken from the longest length, huffval sorted by code length, then symbol.
+// bits[0] = 0, bits[1..16]; returns the symbol count, or -1 when every count is zero or the result is no table libjpeg would take
+// (a counted symbol left without a code, or more codes than lengths allow: counts past the sentinel).  *adjusted (optional):
+// lengths were folded.
+int optimal_table(const uint64_t freq[256], uint8_t bits[17], uint8_t huffval[256], bool* adjusted = nullptr);
+// The device tables of a quality with the given Huffman tables.
+void make_tables(int quality, const Huffman& h, Tables* t);
+// The header with the sampling's SOF0 and DHT from `h`; returns its length (<= kHeaderBytes: an optimized table holds at most
+// 12 DC or 162 AC symbols), or -1 for bad arguments or a cap below the length.
+int header(int quality, int sampling, const Huffman& h, int H, int W, uint8_t* buf, size_t cap);
+// The scan's exact bit count (before padding) for symbol counts freq[DC0, AC0, DC1, AC1][256] coded with `h`; UINT64_MAX when a
+// counted symbol has no code.
+uint64_t scan_bits(const uint64_t freq[4][256], const Huffman& h);
+
 // Byte offsets of the encoder's device scratch (all 16-byte aligned), sized for an H x W frame.
 struct Scratch {
     size_t coefs;    // int16 [mcus][6][64], zigzag order
@@ -51,6 +93,7 @@ struct Scratch {
     uint64_t n_mcus, scan_words, stuff_chunks, partial_elems;
 };
 Scratch scratch_layout(int H, int W);
+Scratch scratch_layout(int H, int W, int sampling);  // (coefs: int16 [mcus][nb][64])
 // Workgroup sums the scan of n elements needs (recursively, every level).
 uint64_t scan_partials(uint64_t n);
 
@@ -64,6 +107,8 @@ struct RowsGrid {
 };
 // y0 a multiple of 16, y0 < y1 <= H, y1 a multiple of 16 or H; returns false (grid zeroed) otherwise.
 bool rows_grid(int H, int W, int y0, int y1, RowsGrid* g);
+// The same for a sampling: y0 a multiple of the MCU height (16 or 8), y1 one too or H.
+bool rows_grid(int H, int W, int sampling, int y0, int y1, RowsGrid* g);
 
 }  // namespace jpeg
 }  // namespace r2f

@@ -21,13 +21,14 @@ from __future__ import annotations
 import inspect
 import math
 import random
+import sys
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 from . import _lib, filmstock, geometry, stencils
 from .context import LOG_EPS, LUT3D_SCALE, HipContext
-from .jpeg_stream import JpegBandSink, JpegStaging, deliver
+from .jpeg_stream import JpegBandSink, JpegStaging, app1_segment, deliver
 from .results import ResultBuffers
 
 REC709_TO_XYZ = np.array(  # data.py:128-135
@@ -614,11 +615,15 @@ class HipProcessor:
         return None if out_u8 is None else self._download(out_u8)  # DEVICE -> HOST, the reference's read_texture/map_sync
 
     # ------------------------------------------------------------------ JPEG export (gui.py:2338-2341)
-    def encode_jpeg(self, image, quality=100) -> bytes:
-        """`Image.fromarray(image).save(f, "JPEG", quality=quality)` on the device: the same bytes Pillow writes with its defaults
-        (JFIF, 4:2:0, standard Huffman tables, no EXIF / ICC).  image: uint8 (H, W, 3), a NumPy array or a torch tensor (a CUDA
-        tensor may be a row-strided view); quality: an int 0 .. 100 like the reference's slider (gui.py:2532-2588)."""
+    def encode_jpeg(self, image, quality=100, *, subsampling=-1, optimize=False, exif=b"") -> bytes:
+        """`Image.fromarray(image).save(f, "JPEG", quality=quality, subsampling=subsampling, optimize=optimize, exif=exif)` on the
+        device: the same bytes Pillow writes (JFIF, standard or optimized Huffman tables, no ICC).  image: uint8 (H, W, 3), a NumPy
+        array or a torch tensor (a CUDA tensor may be a row-strided view); quality: an int 0 .. 100 like the reference's slider
+        (gui.py:2532-2588).  subsampling: -1 (libjpeg's default, 4:2:0), 0 / "4:4:4", 1 / "4:2:2", 2 / "4:2:0".  optimize: truthy
+        for per-image Huffman tables (the call then waits once for the frame's symbol counts).  exif: bytes or a PIL.Image.Exif,
+        written as an APP1 segment after the JFIF one (empty: none)."""
         q = _jpeg_quality(quality)
+        opts = _jpeg_options(subsampling, optimize, exif)
         torch = self._torch
         if isinstance(image, np.ndarray):
             _check_jpeg_image(image.dtype == np.uint8, image.shape, image.dtype)
@@ -629,9 +634,10 @@ class HipProcessor:
                 image = image.to(self.device)
         else:
             raise ValueError(f"encode_jpeg: expected a uint8 (H, W, 3) NumPy array or torch tensor, got {type(image).__name__}")
-        return self._encode_device(image, q)
+        return self._encode_device(image, q, *opts)
 
-    def process_jpeg(self, src, negative_film, grain_size, grain_sigma, quality=100, stream=False, file=None, **settings):
+    def process_jpeg(self, src, negative_film, grain_size, grain_sigma, quality=100, stream=False, file=None, *, subsampling=-1,
+                     optimize=False, exif=b"", **settings):
         """The export of one frame (gui.py:2338-2341): process()'s render with the same keywords -- the pixels process() returns
         for them -- encoded on the device as encode_jpeg does; only the file comes back to the host.  The frame a preview keeps on
         the device (cache=True) is left alone: the next preview re-render uploads nothing.  The export always extracts and uploads
@@ -642,8 +648,11 @@ class HipProcessor:
         encoded behind its tail: the file's final bytes go down (and into `file`) while later bands are still arriving.  A frame
         that does not stream takes the one-piece path, and `stream_rejected` says why.
         file: a path or a binary file object the bytes are written into (as they arrive, when streaming); the call then returns
-        their count.  Without it the call returns the bytes."""
+        their count.  Without it the call returns the bytes.
+        subsampling, optimize, exif: Pillow's, as in encode_jpeg.  optimize=True needs the whole frame's symbol counts before the
+        first scan byte: with stream=True it takes the one-piece path, and `stream_rejected` says so."""
         q = _jpeg_quality(quality)
+        opts = _jpeg_options(subsampling, optimize, exif)
         for k in ("dst_texture", "histogram_texture"):
             if settings.pop(k, None) is not None:
                 raise ValueError(f"process_jpeg writes a file: {k} is not taken (use process() for the preview)")
@@ -654,46 +663,51 @@ class HipProcessor:
                     if k not in ("self", "src", "negative_film", "grain_size", "grain_sigma", "dst_texture", "histogram_texture", "_")}
         load = {k: settings[k] for k in _LOAD_KEYWORDS}
         if stream:  # process(cache=False)'s gates, in its order: the early ones, then the payload's (_stream_payload's)
-            self.stream_rejected = ("profile_stages is on" if getattr(self, "profile_stages", False) else
+            self.stream_rejected = (_OPTIMIZE_REJECTED if opts[1] else
+                                    "profile_stages is on" if getattr(self, "profile_stages", False) else
                                     host_stream_gate(src, self.stream_bands, settings["rotation"], settings["chroma_nr"],
                                                      settings["canvas_mode"], settings["highlight_burn"]))
         payload = self.extract_image_data_cpu(src, **load, _internal=True)
         if stream and self.stream_rejected is None:
-            res = self._stream_jpeg(payload, negative_film, grain_size, grain_sigma, "cpu", q, file, settings)
+            res = self._stream_jpeg(payload, negative_film, grain_size, grain_sigma, "cpu", q, file, settings, opts)
             if res is not None:
                 return res
         image, layout = self._upload_payload(payload)
         out_u8 = self._render_prepared(image, layout, payload, negative_film, grain_size, grain_sigma, None, None, "cpu", **settings)
-        return deliver(self._encode_device(out_u8, q), file)
+        return deliver(self._encode_device(out_u8, q, *opts), file)
 
     def process_preloaded_jpeg(self, cpu_payload, negative_film, grain_size, grain_sigma, quality=100, final_scaling="gpu",
-                               stream=False, file=None, **settings):
+                               stream=False, file=None, *, subsampling=-1, optimize=False, exif=b"", **settings):
         """The batch export on the two-phase API: process_preloaded's render of a phase-1 payload, encoded on the device like
         process_jpeg.  The processor's device frame (prepare_gpu_textures') is left alone.  stream=True: the file is Pillow's of
         process_preloaded(cpu_payload, final_scaling=..., ...)'s pixels, and a payload process_preloaded streams in row bands is
-        encoded band by band as in process_jpeg (else `stream_rejected` says why not).  file: see process_jpeg."""
+        encoded band by band as in process_jpeg (else `stream_rejected` says why not).  file, subsampling, optimize, exif: see
+        process_jpeg."""
         q = _jpeg_quality(quality)
+        opts = _jpeg_options(subsampling, optimize, exif)
         for k in ("dst_texture", "histogram_texture"):
             if settings.pop(k, None) is not None:
                 raise ValueError(f"process_preloaded_jpeg writes a file: {k} is not taken")
         if stream:
-            self.stream_rejected = None if self.stream_bands > 1 else f"stream_bands = {self.stream_bands}"
+            self.stream_rejected = (_OPTIMIZE_REJECTED if opts[1] else
+                                    None if self.stream_bands > 1 else f"stream_bands = {self.stream_bands}")
             if self.stream_rejected is None:
-                res = self._stream_jpeg(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, q, file, settings)
+                res = self._stream_jpeg(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, q, file, settings, opts)
                 if res is not None:
                     return res
         image, layout = self._upload_payload(cpu_payload)
         out_u8 = self._render_prepared(image, layout, cpu_payload, negative_film, grain_size, grain_sigma, None, None, final_scaling,
                                        **settings)
-        return deliver(self._encode_device(out_u8, q), file)
+        return deliver(self._encode_device(out_u8, q, *opts), file)
 
-    def _encode_device(self, image_u8, quality):
+    def _encode_device(self, image_u8, quality, subsampling=2, optimize=False, exif=b""):
         """A uint8 (H, W, 3) device frame -> the JPEG file's bytes.  The encoder runs on the current stream; reading its 8-byte
-        length back is the one synchronisation, then only the file crosses PCIe, into a pinned buffer this processor keeps (grown
-        to the largest file so far; a pageable download of a 47 MB file cost up to 34 ms) and from there into the bytes object."""
+        length back is the one synchronisation (optimize adds one for the symbol counts), then only the file crosses PCIe, into a
+        pinned buffer this processor keeps (grown to the largest file so far; a pageable download of a 47 MB file cost up to 34 ms)
+        and from there into the bytes object -- with the EXIF APP1 spliced in on the way, in the same single copy."""
         if image_u8.stride(2) != 1 or image_u8.stride(1) != 3 or image_u8.stride(0) < 3 * image_u8.shape[1]:
             image_u8 = image_u8.contiguous()  # (a row-strided view is encoded in place)
-        out, length = self.ctx.jpeg_encode(image_u8, quality)
+        out, length = self.ctx.jpeg_encode(image_u8, quality, subsampling, optimize)
         n = int(length.item())
         if n <= 0:
             raise RuntimeError("r2f_jpeg_encode reported an empty file")
@@ -701,6 +715,9 @@ class HipProcessor:
         if host is None or host.numel() < n:
             host = self._jpeg_host = self._torch.empty(max(n, 1 << 20), dtype=self._torch.uint8, pin_memory=True)
         host[:n].copy_(out[:n])  # (synchronous: the bytes are there when it returns)
+        if exif:
+            data = host[:n].numpy().data
+            return b"".join((data[:20], app1_segment(exif), data[20:]))
         return host[:n].numpy().tobytes()
 
     def _process_streamed(self, src, negative_film, grain_size, grain_sigma, load, settings):
@@ -767,7 +784,7 @@ class HipProcessor:
         self.ctx.write_frame_params(p)     # (and the exposure-range record starts empty)
         return host, p, bounds, bufs, ha, ma
 
-    def _stream_jpeg(self, payload, negative_film, grain_size, grain_sigma, final_scaling, quality, file, settings):
+    def _stream_jpeg(self, payload, negative_film, grain_size, grain_sigma, final_scaling, quality, file, settings, opts=(2, False, b"")):
         """_stream_payload with a JPEG sink: the same bands and stage calls, no pixels downloaded; each band's finished MCU rows
         are encoded behind its tail and the file's final bytes go down while later bands arrive (jpeg_stream.py).  Returns the
         file's bytes (file=None) or their count, or None (with `stream_rejected` saying why) when the payload does not qualify."""
@@ -779,7 +796,8 @@ class HipProcessor:
         if staging is None:
             staging = self._jpeg_staging = JpegStaging(self._torch, self.device)
         _, down = self._copy_streams()
-        sink = JpegBandSink(staging, self.ctx, bufs["u8"], quality, bounds, down, file)
+        subsampling, _, exif = opts  # (optimize never streams)
+        sink = JpegBandSink(staging, self.ctx, bufs["u8"], quality, bounds, down, file, subsampling, exif)
         try:
             self._run_bands(host, payload, p, bounds, bufs, ha, ma, None, band_done=sink.band)
             res = sink.finish()
@@ -1145,6 +1163,42 @@ def _jpeg_quality(quality) -> int:
     if not 0 <= int(quality) <= 100:
         raise ValueError(f"JPEG quality must be in 0 .. 100, got {int(quality)}")
     return int(quality)
+
+
+_SUBSAMPLINGS = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}
+_EXIF_MAX = 65533  # a marker segment's payload (Pillow's MAX_BYTES_IN_MARKER)
+_OPTIMIZE_REJECTED = "optimize=True: its Huffman tables need the whole frame's statistics before the first scan byte"
+
+
+def _jpeg_subsampling(subsampling) -> int:
+    """Pillow's subsampling option -> 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0): -1 (libjpeg's default, 4:2:0), 0 / "4:4:4",
+    1 / "4:2:2", 2 / "4:2:0".  "keep" (it needs a JPEG source), "4:1:1" (which Pillow maps with a warning) and anything else raise
+    ValueError."""
+    if isinstance(subsampling, str):
+        if subsampling in _SUBSAMPLINGS:
+            return _SUBSAMPLINGS[subsampling]
+    elif not isinstance(subsampling, (bool, np.bool_)) and isinstance(subsampling, (int, np.integer)) and -1 <= int(subsampling) <= 2:
+        return 2 if int(subsampling) == -1 else int(subsampling)
+    raise ValueError(f"JPEG subsampling must be -1, 0 / '4:4:4', 1 / '4:2:2' or 2 / '4:2:0', got {subsampling!r}")
+
+
+def _jpeg_exif(exif) -> bytes:
+    """Pillow's exif option -> the APP1 payload: bytes-like, or a PIL.Image.Exif (its .tobytes()); b"" for none."""
+    if isinstance(exif, (bytes, bytearray, memoryview)):
+        data = bytes(exif)
+    else:
+        Exif = getattr(sys.modules.get("PIL.Image"), "Exif", None)  # (an Exif instance means Pillow is imported already)
+        if Exif is None or not isinstance(exif, Exif):
+            raise ValueError(f"JPEG exif must be bytes or a PIL.Image.Exif, got {type(exif).__name__}")
+        data = exif.tobytes()
+    if len(data) > _EXIF_MAX:
+        raise ValueError(f"EXIF data is too long: {len(data)} bytes (a JPEG marker holds at most {_EXIF_MAX})")
+    return data
+
+
+def _jpeg_options(subsampling, optimize, exif):
+    """(sampling 0 / 1 / 2, optimize, exif bytes) of an export's options, checked before any work starts."""
+    return _jpeg_subsampling(subsampling), bool(optimize), _jpeg_exif(exif)
 
 
 def _check_jpeg_image(is_uint8, shape, dtype):

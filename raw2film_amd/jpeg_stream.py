@@ -19,13 +19,14 @@ CHUNK = 8 << 20  # bytes per slot of the pinned ring (a 101 MP file of ~130 MB a
 SLOTS = 4
 
 
-def jpeg_row_steps(bounds, H):
+def jpeg_row_steps(bounds, H, mcu_height=16):
     """Per band of `bounds` (plan_bands': 0 = bounds[0] < ... < bounds[-1] = H): the rows (y0, y1) the encoder takes once that
-    band's tail is done, or None.  Rows [0, bounds[b + 1]) exist then; the encoder takes them up to the last multiple of 16 (an MCU
-    row reads 16 rows), the last band up to H.  The steps partition [0, H) in order."""
+    band's tail is done, or None.  Rows [0, bounds[b + 1]) exist then; the encoder takes them up to the last multiple of the MCU
+    height (an MCU row reads 16 rows in 4:2:0, 8 in 4:2:2 and 4:4:4), the last band up to H.  The steps partition [0, H) in
+    order."""
     steps, done = [], 0
     for b in range(len(bounds) - 1):
-        y1 = H if bounds[b + 1] >= H else bounds[b + 1] // 16 * 16
+        y1 = H if bounds[b + 1] >= H else bounds[b + 1] // mcu_height * mcu_height
         steps.append((done, y1) if y1 > done else None)
         done = max(done, y1)
     return steps
@@ -59,6 +60,12 @@ class JpegStaging:
         self.ring = self.ring_np = self.lens = None
 
 
+def app1_segment(exif: bytes) -> bytes:
+    """The APP1 segment Pillow writes for `exif` (b"" for none): FF E1, the length + 2 (big-endian), the bytes.  It goes right after
+    the file's first 20 bytes (SOI + APP0)."""
+    return b"\xff\xe1" + (len(exif) + 2).to_bytes(2, "big") + exif if exif else b""
+
+
 def open_output(file):
     """(binary file object, whether this call opened it) for a path or a file object; (BytesIO, False) for None."""
     if file is None:
@@ -72,13 +79,16 @@ def open_output(file):
 
 class JpegBandSink:
     """One streamed export: band(b) after band b's tail (on the launching thread), then finish() -> the file's bytes (file=None)
-    or its length, or abandon() on an error with the device drained."""
+    or its length, or abandon() on an error with the device drained.  subsampling: 0 4:4:4, 1 4:2:2, 2 4:2:0; exif: the bytes of
+    an APP1 segment the writer puts after the file's first 20 bytes (b"": none)."""
 
-    def __init__(self, staging, ctx, image_u8, quality, bounds, down, file=None):
+    def __init__(self, staging, ctx, image_u8, quality, bounds, down, file=None, subsampling=2, exif=b""):
         torch = ctx._torch
         H, W = int(image_u8.shape[0]), int(image_u8.shape[1])
         self._torch, self._st, self._image, self._down = torch, staging, image_u8, down
-        self.steps = jpeg_row_steps(bounds, H)
+        self.steps = jpeg_row_steps(bounds, H, 16 if subsampling == 2 else 8)
+        self._app1 = app1_segment(exif)  # (written by the first write: every first chunk holds the whole header)
+        self._app1_pending = bool(self._app1)
         self._lens = staging.lengths(len(self.steps))
         self._lens_np = self._lens.numpy()
         self._file, self._own = open_output(file)
@@ -89,7 +99,7 @@ class JpegBandSink:
         self._compute = torch.cuda.current_stream(ctx.device)
         self._snap = torch.empty(len(self.steps), dtype=torch.int64, device=ctx.device)  # the word after each band's encode
         try:
-            self.enc = ctx.jpeg_rows(H, W, quality)  # (header and carry written on the launching stream)
+            self.enc = ctx.jpeg_rows(H, W, quality, subsampling)  # (header and carry written on the launching stream)
         except BaseException:
             self._close_file()
             raise
@@ -127,7 +137,13 @@ class JpegBandSink:
         try:
             copied.synchronize()
             if not self._failed:
-                self._file.write(memoryview(self._st.ring_np[slot, :m]))
+                chunk = memoryview(self._st.ring_np[slot, :m])
+                if self._app1_pending:
+                    self._file.write(chunk[:20])
+                    self._file.write(self._app1)
+                    chunk = chunk[20:]
+                    self._app1_pending = False
+                self._file.write(chunk)
         except BaseException:
             self._failed = True
             raise
@@ -141,7 +157,7 @@ class JpegBandSink:
             w.result()
         if not self.enc.done:
             raise RuntimeError("the streamed export ended before the frame's last rows")
-        n = self._sent
+        n = self._sent + len(self._app1)
         out = self._file.getvalue() if self._return_bytes else n
         self._close_file()
         return out
