@@ -445,14 +445,21 @@ R2F_API int r2f_jpeg_rows(r2f_ctx* ctx, const uint8_t* image, int64_t row_stride
 /* --- JPEG export with Pillow's options: save(..., quality=q, subsampling=s, optimize=o).  The entry points above are the
  * sampling = 2, optimize = 0 cases of these.  sampling: 0 = 4:4:4 (8 x 8 MCUs), 1 = 4:2:2 (16 x 8), 2 = 4:2:0 (16 x 16).
  * optimize: per-image Huffman tables (libjpeg's optimize_coding), generated from the frame's symbol counts.  EXIF (an APP1
- * segment after SOI + APP0) is the caller's to splice into the file: it needs no device work.  reserved: 0. */
+ * segment after SOI + APP0) is the caller's to splice into the file: it needs no device work.  progressive: 0, or 1 for
+ * save(..., progressive=True): SOF2 and libjpeg's ten-scan jpeg_simple_progression, every scan with its own optimized tables
+ * (libjpeg forces optimize_coding there, so `optimize` makes no difference); one-shot only (r2f_jpeg_encode_ex). */
 typedef struct r2f_jpeg_opts {
-    int32_t quality, sampling, optimize, reserved;
+    int32_t quality, sampling, optimize, progressive;
 } r2f_jpeg_opts;
 /* Worst-case file size of an H x W frame in `sampling` at any quality and either table choice (0 for sizes JPEG cannot hold or a
  * bad sampling).  Per pixel: about 9.7 bytes for 4:2:0, 13.0 for 4:2:2, 19.5 for 4:4:4.  No GPU, no context. */
 R2F_API uint64_t r2f_jpeg_bound_bytes_ex(int H, int W, int sampling);
-/* The header (SOI .. SOS) with the standard tables; R2F_EINVAL for optimize (its tables come from the frame).  No GPU. */
+/* Worst-case file size for any options, progressive included (0 for bad options or sizes).  A progressive file's bound is
+ * larger than a baseline one's: a coefficient can cost a symbol, its value bits and correction bits in several scans (about
+ * 12.1 bytes per pixel for 4:2:0, 16.1 for 4:2:2, 24.1 for 4:4:4).  No GPU, no context. */
+R2F_API uint64_t r2f_jpeg_bound_bytes_opts(const r2f_jpeg_opts* opts, int H, int W);
+/* The header (SOI .. SOS) with the standard tables; R2F_EINVAL for optimize and progressive (their tables come from the
+ * frame).  No GPU. */
 R2F_API int r2f_jpeg_header_ex(const r2f_jpeg_opts* opts, int H, int W, uint8_t* buf, size_t cap, size_t* len);
 /* jpeg_gen_optimal_table of libjpeg: symbol counts -> bits[0] = 0, bits[1..16] codes per length, huffval[*n] the symbols by
  * code length, then symbol.  R2F_EINVAL when every count is zero, or when counts past libjpeg's 10^9 sentinel leave a table
@@ -463,11 +470,15 @@ R2F_API int r2f_jpeg_optimal_table(const uint64_t freq[256], uint8_t bits[17], u
  * 8 KB of counts are read back, the tables and header are built on the host, and the rest of the encode is queued on `stream`.
  * The context's scratch grows with the sampling: about 3, 4 and 6 bytes per pixel of coefficients plus the packed scan.
  * R2F_ETOOLARGE (optimize only): the optimized scan would exceed the bound, or the frame's symbol counts pass libjpeg's 10^9
- * sentinel (r2f_jpeg_optimal_table); nothing is written. */
+ * sentinel (r2f_jpeg_optimal_table); nothing is written.
+ * progressive: out_cap >= r2f_jpeg_bound_bytes_opts(opts, H, W).  The call blocks for the ten scans' symbol counts (40 KB read
+ * back), builds every scan's tables and headers on the host, queues the packing of the scans one after the other and waits for
+ * the file's length.  R2F_ETOOLARGE when the counts pass libjpeg's 10^9 sentinel, or -- which the bound rules out -- the exact
+ * file would exceed out_cap: *out_len is then 0 and `out` holds no file. */
 R2F_API int r2f_jpeg_encode_ex(r2f_ctx* ctx, const uint8_t* image, int H, int W, int64_t row_stride, const r2f_jpeg_opts* opts,
                                uint8_t* out, uint64_t out_cap, uint64_t* out_len, void* stream);
 /* r2f_jpeg_rows_begin with options (out_cap >= r2f_jpeg_bound_bytes_ex(H, W, sampling)); R2F_EINVAL for optimize, whose tables
- * need the whole frame before the first scan byte. */
+ * need the whole frame before the first scan byte, and for progressive, whose every scan spans the whole frame. */
 R2F_API int r2f_jpeg_rows_begin_ex(r2f_ctx* ctx, int H, int W, const r2f_jpeg_opts* opts, uint8_t* out, uint64_t out_cap,
                                    uint64_t* out_len, void* stream);
 

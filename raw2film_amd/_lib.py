@@ -57,8 +57,8 @@ class Blit(C.Structure):  # r2f_blit: the uniform block of shaders/copy_to_int.w
     ]
 
 
-class JpegOpts(C.Structure):  # r2f_jpeg_opts (sampling: 0 4:4:4, 1 4:2:2, 2 4:2:0)
-    _fields_ = [("quality", C.c_int32), ("sampling", C.c_int32), ("optimize", C.c_int32), ("reserved", C.c_int32)]
+class JpegOpts(C.Structure):  # r2f_jpeg_opts (sampling: 0 4:4:4, 1 4:2:2, 2 4:2:0; progressive: 0 or 1)
+    _fields_ = [("quality", C.c_int32), ("sampling", C.c_int32), ("optimize", C.c_int32), ("progressive", C.c_int32)]
 
 
 _P = C.POINTER
@@ -185,6 +185,7 @@ _SIGNATURES = {
     "r2f_jpeg_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "r2f_jpeg_bound_bytes_ex": (C.c_uint64, [C.c_int, C.c_int, C.c_int]),
     "r2f_jpeg_header_ex": (C.c_int, [_P(JpegOpts), C.c_int, C.c_int, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
+    "r2f_jpeg_bound_bytes_opts": (C.c_uint64, [_P(JpegOpts), C.c_int, C.c_int]),
     "r2f_jpeg_optimal_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_int)]),
     "r2f_jpeg_encode_ex": (
         C.c_int,

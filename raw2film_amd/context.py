@@ -616,27 +616,35 @@ class HipContext:
             return int(self._lib.r2f_jpeg_bound_bytes(int(H), int(W)))
         return int(self._lib.r2f_jpeg_bound_bytes_ex(int(H), int(W), int(subsampling)))
 
-    def jpeg_encode(self, image_u8, quality: int, subsampling: int = 2, optimize: bool = False):
+    def jpeg_bound_bytes_opts(self, H: int, W: int, quality: int, subsampling: int = 2, optimize: bool = False,
+                              progressive: bool = False) -> int:
+        """Largest JPEG file r2f_jpeg_encode_ex can write for an H x W frame with these options (r2f_jpeg_bound_bytes_opts)."""
+        opts = _lib.JpegOpts(int(quality), int(subsampling), 1 if optimize else 0, 1 if progressive else 0)
+        return int(self._lib.r2f_jpeg_bound_bytes_opts(C.byref(opts), int(H), int(W)))
+
+    def jpeg_encode(self, image_u8, quality: int, subsampling: int = 2, optimize: bool = False, progressive: bool = False):
         """Baseline JPEG of a uint8 (H, W, 3) device image (rows may be strided; pixels packed) -> (uint8 device buffer of
         jpeg_bound_bytes, int64 device tensor of 1 holding the file's length).  Asynchronous on the current stream, except with
-        optimize, whose call waits once for the frame's symbol counts (r2f_jpeg_encode_ex).  subsampling: 0 4:4:4, 1 4:2:2,
-        2 4:2:0."""
+        optimize, whose call waits once for the frame's symbol counts (r2f_jpeg_encode_ex), and progressive, whose call waits for
+        the ten scans' counts and then for the file's length (the buffer is then the progressive bound).  subsampling: 0 4:4:4,
+        1 4:2:2, 2 4:2:0."""
         torch = self._torch
         if not (isinstance(image_u8, torch.Tensor) and image_u8.is_cuda and image_u8.dtype == torch.uint8 and image_u8.dim() == 3
                 and image_u8.shape[2] == 3 and image_u8.stride(2) == 1 and image_u8.stride(1) == 3):
             raise ValueError("jpeg_encode needs a uint8 (H, W, 3) CUDA tensor with packed pixels (row stride free)")
         self._same_device(image_u8, "image")
         H, W = int(image_u8.shape[0]), int(image_u8.shape[1])
-        bound = self.jpeg_bound_bytes(H, W, subsampling)
+        bound = (self.jpeg_bound_bytes_opts(H, W, quality, subsampling, optimize, True) if progressive else
+                 self.jpeg_bound_bytes(H, W, subsampling))
         if bound == 0:
             raise ValueError(f"jpeg_encode: a JPEG holds 1 .. 65535 pixels per side, got {H} x {W} (subsampling {subsampling})")
         out = torch.empty(bound, dtype=torch.uint8, device=self.device)
         length = torch.empty(1, dtype=torch.int64, device=self.device)
-        if int(subsampling) == 2 and not optimize:
+        if int(subsampling) == 2 and not optimize and not progressive:
             self._check(self._lib.r2f_jpeg_encode(self._h, image_u8.data_ptr(), H, W, int(image_u8.stride(0)), int(quality),
                                                   out.data_ptr(), bound, length.data_ptr(), self._stream()))
         else:
-            opts = _lib.JpegOpts(int(quality), int(subsampling), 1 if optimize else 0, 0)
+            opts = _lib.JpegOpts(int(quality), int(subsampling), 1 if optimize else 0, 1 if progressive else 0)
             self._check(self._lib.r2f_jpeg_encode_ex(self._h, image_u8.data_ptr(), H, W, int(image_u8.stride(0)), C.byref(opts),
                                                      out.data_ptr(), bound, length.data_ptr(), self._stream()))
         return out, length

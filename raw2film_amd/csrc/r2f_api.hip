@@ -1857,19 +1857,20 @@ int jpeg_prepare(r2f_ctx* ctx, int H, int W, int64_t row_stride, const r2f_jpeg_
     if (!jpeg::valid_sampling(o->sampling))
         return fail(ctx, R2F_EINVAL, "jpeg: sampling %d is not 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0)", o->sampling);
     if (o->optimize != 0 && o->optimize != 1) return fail(ctx, R2F_EINVAL, "jpeg: optimize %d is not 0 or 1", o->optimize);
-    if (o->reserved) return fail(ctx, R2F_EINVAL, "jpeg: reserved option %d is not 0", o->reserved);
+    if (o->progressive != 0 && o->progressive != 1)
+        return fail(ctx, R2F_EINVAL, "jpeg: progressive %d is not 0 or 1", o->progressive);
     if (row_stride >= 0 && row_stride < 3LL * W)
         return fail(ctx, R2F_EINVAL, "jpeg: row stride %lld < 3 W = %lld", (long long)row_stride, 3LL * W);
     if ((uintptr_t)out_len % 8) return fail(ctx, R2F_EINVAL, "jpeg: out_len must be 8-byte aligned");
-    const uint64_t bound = jpeg::bound_bytes(H, W, o->sampling);
+    const uint64_t bound = o->progressive ? jpeg::prog_bound_bytes(H, W, o->sampling) : jpeg::bound_bytes(H, W, o->sampling);
     if (out_cap < bound)
         return fail(ctx, R2F_EINVAL, "jpeg: output capacity %llu < bound %llu", (unsigned long long)out_cap, (unsigned long long)bound);
-    const jpeg::Scratch L = jpeg::scratch_layout(H, W, o->sampling);
-    if (ctx->jpeg_scratch.bytes < L.total) {
+    const size_t total = o->progressive ? jpeg::prog_scratch_layout(H, W, o->sampling).total : jpeg::scratch_layout(H, W, o->sampling).total;
+    if (ctx->jpeg_scratch.bytes < total) {
         R2F_HIP(ctx, hipDeviceSynchronize());  // (an earlier encode may still be working in the old buffer)
         ctx->jpeg_scratch.release();
-        R2F_HIP(ctx, hipMalloc(&ctx->jpeg_scratch.p, L.total));
-        ctx->jpeg_scratch.bytes = L.total;
+        R2F_HIP(ctx, hipMalloc(&ctx->jpeg_scratch.p, total));
+        ctx->jpeg_scratch.bytes = total;
     }
     return R2F_OK;
 }
@@ -1882,6 +1883,67 @@ int jpeg_std_setup(r2f_ctx* ctx, const r2f_jpeg_opts* o, int H, int W, JpegEncod
     const int n = jpeg::header(o->quality, o->sampling, h, H, W, hdr, cap);
     if (n < 0) return fail(ctx, R2F_EINVAL, "jpeg: header");
     a->header = hdr, a->header_len = n, a->sampling = o->sampling;
+    return R2F_OK;
+}
+
+// progressive=True: the ten scans' symbol counts (the first synchronisation), every scan's tables and header on the host, the
+// packing queued, and the file's length read back (the second).
+int jpeg_encode_progressive(r2f_ctx* ctx, const r2f_jpeg_opts* o, JpegEncodeArgs& a, uint64_t out_cap, hipStream_t s) {
+    const int H = a.H, W = a.W;
+    R2F_HIP(ctx, launch_jpeg_prog_stats(a, s));
+    const jpeg::ProgScratch P = jpeg::prog_scratch_layout(H, W, o->sampling);
+    std::vector<uint64_t> freq(jpeg::kProgFreqWords);
+    R2F_HIP(ctx, hipMemcpyAsync(freq.data(), static_cast<uint8_t*>(a.scratch) + P.freq, jpeg::kProgScans * 513 * sizeof(uint64_t),
+                                hipMemcpyDeviceToHost, s));
+    R2F_HIP(ctx, hipStreamSynchronize(s));
+    uint8_t frame[jpeg::kProgFrameHeaderBytes];
+    if (jpeg::prog_frame_header(o->quality, o->sampling, H, W, frame, sizeof frame) != jpeg::kProgFrameHeaderBytes)
+        return fail(ctx, R2F_EINVAL, "jpeg: progressive frame header");
+    std::vector<ProgScanPlan> plans(jpeg::kProgScans);
+    uint64_t file = jpeg::kProgFrameHeaderBytes + 2;
+    const uint64_t scan_bound = jpeg::prog_scratch_layout(H, W, o->sampling).scan_words * 32ull;
+    for (int scan = 0; scan < jpeg::kProgScans; ++scan) {
+        const jpeg::ProgScan& sc = jpeg::prog_scan(scan);
+        const uint64_t(*f)[256] = reinterpret_cast<const uint64_t(*)[256]>(freq.data() + (size_t)scan * 512);
+        jpeg::ProgTables t{};
+        for (int k = 0; k < jpeg::prog_slots(sc); ++k) {
+            uint8_t bits[17];
+            const int n = jpeg::optimal_table(f[k], bits, t.huffval[k]);
+            if (n < 0) return fail(ctx, R2F_ETOOLARGE, "jpeg: the symbol counts of scan %d pass libjpeg's 10^9 sentinel", scan);
+            if (n > (sc.Ss ? jpeg::kProgAcSymbols : 12)) return fail(ctx, R2F_EHIP, "jpeg: scan %d's table has %d symbols", scan, n);
+            for (int i = 0; i < 16; ++i) t.bits[k][i] = bits[i + 1];
+            t.n[k] = n;
+        }
+        ProgScanPlan& pl = plans[scan];
+        std::memset(&pl, 0, sizeof pl);
+        // (a table slot's codes: the same canonical derivation the baseline tables take)
+        jpeg::Huffman h{};
+        for (int k = 0; k < jpeg::prog_slots(sc); ++k) {
+            std::memcpy(h.bits[1], t.bits[k], 16), std::memcpy(h.huffval[1], t.huffval[k], 256), h.n[1] = t.n[k];
+            std::memcpy(h.bits[0], t.bits[k], 16), std::memcpy(h.huffval[0], t.huffval[k], 256), h.n[0] = t.n[k];
+            jpeg::Tables dt;
+            jpeg::make_tables(o->quality, h, &dt);
+            for (int v = 0; v < 256; ++v) pl.codes[k][v] = sc.Ss ? dt.ac[0][v] : (v < 16 ? dt.dc[0][v] : 0);
+        }
+        pl.header_len = jpeg::prog_scan_header(scan, t, pl.header, sizeof pl.header);
+        if (pl.header_len < 0) return fail(ctx, R2F_EHIP, "jpeg: scan %d's header", scan);
+        const uint64_t n_blocks = jpeg::prog_geom(H, W, o->sampling, scan).n;
+        const uint64_t extra = sc.Ss == 0 ? (sc.Ah ? n_blocks : 0) : freq[(size_t)jpeg::kProgScans * 512 + scan];
+        const uint64_t bits = jpeg::prog_scan_bits(scan, f, t, extra);
+        if (bits > scan_bound || bits > n_blocks * jpeg::kProgScanBlockBits)
+            return fail(ctx, R2F_EHIP, "jpeg: scan %d's %llu bits pass its bound", scan, (unsigned long long)bits);
+        file += (uint64_t)pl.header_len + (bits + 7) / 8;
+    }
+    if (file > out_cap)  // (before stuffing: too large already, nothing is written)
+        return fail(ctx, R2F_ETOOLARGE, "jpeg: the progressive file takes at least %llu bytes, out_cap is %llu",
+                    (unsigned long long)file, (unsigned long long)out_cap);
+    R2F_HIP(ctx, launch_jpeg_prog_pack(a, frame, plans.data(), out_cap, s));
+    uint64_t len = 0;
+    R2F_HIP(ctx, hipMemcpyAsync(&len, a.out_len, sizeof len, hipMemcpyDeviceToHost, s));
+    R2F_HIP(ctx, hipStreamSynchronize(s));
+    if (len == 0)
+        return fail(ctx, R2F_ETOOLARGE, "jpeg: the progressive file with its stuffed bytes exceeds out_cap %llu",
+                    (unsigned long long)out_cap);
     return R2F_OK;
 }
 
@@ -1901,6 +1963,7 @@ int r2f_jpeg_encode_ex(r2f_ctx* ctx, const uint8_t* image, int H, int W, int64_t
     a.out = out, a.out_len = reinterpret_cast<unsigned long long*>(out_len);
     uint8_t hdr[jpeg::kHeaderBytes];
     if ((rc = jpeg_std_setup(ctx, opts, H, W, &a, hdr, sizeof hdr))) return rc;
+    if (opts->progressive) return jpeg_encode_progressive(ctx, opts, a, out_cap, s);
     if (opts->optimize) {
         // the frame's symbol counts (the one synchronisation), then its tables and header (libjpeg's optimize_coding)
         if (!ctx->jpeg_freq.p) {
@@ -1943,6 +2006,7 @@ int r2f_jpeg_rows_begin_ex(r2f_ctx* ctx, int H, int W, const r2f_jpeg_opts* opts
     if (!ctx) return R2F_EINVAL;
     R2F_GUARD(ctx);
     ctx->jpeg_rows.open = false;
+    if (opts && opts->progressive) return fail(ctx, R2F_EINVAL, "jpeg rows: every progressive scan spans the whole frame");
     int rc = jpeg_prepare(ctx, H, W, -1, opts, out, out_cap, out_len);
     if (rc) return rc;
     if (opts->optimize)

@@ -31,5 +31,22 @@ hipError_t launch_jpeg_stats(const JpegEncodeArgs& a, unsigned long long* freq, 
 // the MCUs of grid `g` against the carry (`last`: they end the frame) and leaves in *out_len the bytes of the file that are final.
 hipError_t launch_jpeg_rows_begin(const JpegEncodeArgs& a, hipStream_t s);
 hipError_t launch_jpeg_rows(const JpegEncodeArgs& a, const jpeg::RowsGrid& g, bool last, hipStream_t s);
+// The tables copied into the scratch and the transform pass alone: the frame's coefficients in the scratch (progressive).
+hipError_t launch_jpeg_transform(const JpegEncodeArgs& a, hipStream_t s);
+// The exclusive 64-bit scan of r2f_jpeg.hip: data[0, n) in place, the total to data[n]; partial: jpeg::scan_partials(n) words.
+void jpeg_scan_u64(unsigned long long* data, long long n, unsigned long long* partial, hipStream_t s);
+
+// r2f_jpeg_prog.hip: progressive=True.  prog_stats: the transform, then per scan the blocks' symbols and the EOB runs resolved,
+// into the scratch's counts (jpeg::ProgScratch::freq); the host reads them back and builds every scan's tables and header.
+// prog_pack: the frame header, then per scan its bits, packing, stuffing and header into `out` (at most out_cap bytes), and the
+// file's length (0 when it does not fit) into *out_len.
+struct ProgScanPlan {
+    uint32_t codes[2][256];  // (code << 8) | length per symbol of the scan's table slots
+    uint8_t header[jpeg::kProgScanHeaderMax];
+    int header_len;
+};
+hipError_t launch_jpeg_prog_stats(const JpegEncodeArgs& a, hipStream_t s);
+hipError_t launch_jpeg_prog_pack(const JpegEncodeArgs& a, const uint8_t* frame_header, const ProgScanPlan* plans, uint64_t out_cap,
+                                 hipStream_t s);
 
 }  // namespace r2f

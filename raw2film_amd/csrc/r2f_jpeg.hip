@@ -668,6 +668,16 @@ hipError_t launch_jpeg_stats(const JpegEncodeArgs& e, unsigned long long* freq, 
     return take_launch_status();
 }
 
+hipError_t launch_jpeg_transform(const JpegEncodeArgs& e, hipStream_t s) {
+    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W, e.sampling);
+    const EncodeArgs a = encode_args(e, L);
+    launch_k(jpeg_tables_kernel, dim3(1), dim3(256), 0, s, e.tables, const_cast<Tables*>(a.tables));
+    launch_k(mcu_kernels(e.sampling).transform, dim3((unsigned)((L.n_mcus + kWaves - 1) / kWaves)), dim3(256), 0, s, a);
+    return take_launch_status();
+}
+
+void jpeg_scan_u64(unsigned long long* data, long long n, unsigned long long* partial, hipStream_t s) { scan_u64(data, n, partial, s); }
+
 hipError_t launch_jpeg_encode(const JpegEncodeArgs& e, hipStream_t s) {
     const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W, e.sampling);
     const EncodeArgs a = encode_args(e, L);

@@ -278,6 +278,133 @@ bool rows_grid(int H, int W, int sampling, int y0, int y1, RowsGrid* g) {
     return true;
 }
 
+
+// ---- progressive
+namespace {
+const ProgScan kProgScript[kProgScans] = {
+    {3, 0, 0, 0, 0, 1}, {1, 0, 1, 5, 0, 2},  {1, 2, 1, 63, 0, 1}, {1, 1, 1, 63, 0, 1}, {1, 0, 6, 63, 0, 2},
+    {1, 0, 1, 63, 2, 1}, {3, 0, 0, 0, 1, 0}, {1, 2, 1, 63, 1, 0}, {1, 1, 1, 63, 1, 0}, {1, 0, 1, 63, 1, 0},
+};
+}  // namespace
+
+const ProgScan& prog_scan(int i) { return kProgScript[i]; }
+
+ProgGeom prog_geom(int H, int W, int sampling, int scan) {
+    const Layout l = layout(sampling);
+    const ProgScan& s = kProgScript[scan];
+    const int mx = (W + l.mw - 1) / l.mw, my = (H + l.mh - 1) / l.mh;
+    if (s.Ss == 0) return ProgGeom{mcus(H, W, sampling) * (uint64_t)l.nb, l.nb, 0};
+    const int bw = s.comp ? mx : (W + 7) / 8, bh = s.comp ? my : (H + 7) / 8;
+    return ProgGeom{(uint64_t)bw * (uint64_t)bh, bw, bh};
+}
+
+int prog_frame_header(int quality, int sampling, int H, int W, uint8_t* buf, size_t cap) {
+    if (!buf || !valid_sampling(sampling) || quality < 0 || quality > 100 || H < 1 || W < 1 || H > kMaxDim || W > kMaxDim ||
+        cap < (size_t)kProgFrameHeaderBytes)
+        return -1;
+    uint8_t q[2][64];
+    quant_tables(quality, q);
+    Writer w{buf};
+    w.u8(0xFF), w.u8(0xD8);
+    w.marker(0xE0, 14);
+    for (int c : {0x4A, 0x46, 0x49, 0x46, 0, 1, 1, 0, 0, 1, 0, 1, 0, 0}) w.u8(c);
+    for (int t = 0; t < 2; ++t) {
+        w.marker(0xDB, 65);
+        w.u8(t);
+        for (int i = 0; i < 64; ++i) w.u8(q[t][kZigzag[i]]);
+    }
+    w.marker(0xC2, 15);  // SOF2: as SOF0
+    w.u8(8), w.u16(H), w.u16(W), w.u8(3);
+    for (int c : {1, layout(sampling).y_factor, 0, 2, 0x11, 1, 3, 0x11, 1}) w.u8(c);
+    return (int)w.n;
+}
+
+int prog_scan_header(int scan, const ProgTables& t, uint8_t* buf, size_t cap) {
+    if (!buf || scan < 0 || scan >= kProgScans) return -1;
+    const ProgScan& s = kProgScript[scan];
+    const int slots = prog_slots(s);
+    size_t len = 2 + 2 + 1 + 2 * (size_t)s.ncomp + 3;
+    for (int k = 0; k < slots; ++k) {
+        int n = 0;
+        for (int i = 0; i < 16; ++i) n += t.bits[k][i];
+        if (n != t.n[k] || n < 1 || n > (s.Ss ? kProgAcSymbols : 12)) return -1;
+        len += 2 + 2 + 1 + 16 + (size_t)n;
+    }
+    if (cap < len) return -1;
+    Writer w{buf};
+    for (int k = 0; k < slots; ++k) {  // jcmarker.c emit_dht: DC0 then DC1 (once for Cb and Cr), or the AC scan's one table
+        w.marker(0xC4, 17 + t.n[k]);
+        w.u8(s.Ss ? 0x10 | (s.comp ? 1 : 0) : k);
+        for (int i = 0; i < 16; ++i) w.u8(t.bits[k][i]);
+        for (int i = 0; i < t.n[k]; ++i) w.u8(t.huffval[k][i]);
+    }
+    w.marker(0xDA, 2 * s.ncomp + 4);
+    w.u8(s.ncomp);
+    for (int c = 0; c < s.ncomp; ++c) {
+        const int comp = s.ncomp == 3 ? c : s.comp;
+        const int td = s.Ss == 0 && s.Ah == 0 ? (comp ? 1 : 0) : 0, ta = s.Se ? (comp ? 1 : 0) : 0;
+        w.u8(comp + 1), w.u8((td << 4) | ta);
+    }
+    w.u8(s.Ss), w.u8(s.Se), w.u8((s.Ah << 4) | s.Al);
+    return (int)w.n;
+}
+
+uint64_t prog_scan_bits(int scan, const uint64_t freq[2][256], const ProgTables& t, uint64_t extra) {
+    const ProgScan& s = kProgScript[scan];
+    uint64_t total = extra;
+    for (int k = 0; k < prog_slots(s); ++k) {
+        uint32_t codes[256];
+        derive(HuffSpec{{}, t.huffval[k], t.n[k]}, t.bits[k], codes, 256);
+        for (int v = 0; v < 256; ++v) {
+            if (!freq[k][v]) continue;
+            if (!codes[v]) return UINT64_MAX;
+            // DC: the category's bits; AC: the size's bits, an EOB run's extra bits (ZRL: none)
+            const int raw = s.Ss == 0 ? v : (v & 15) ? (v & 15) : (v == 0xF0 ? 0 : v >> 4);
+            total += freq[k][v] * (uint64_t)((codes[v] & 0xFF) + raw);
+        }
+    }
+    return total;
+}
+
+int prog_levels(uint64_t n, bool refine) {
+    const uint64_t links = n / (refine ? 15 : kProgEobrunMax) + 2;
+    int l = 1;
+    while ((1ull << l) <= links) ++l;
+    return l;
+}
+
+ProgScratch prog_scratch_layout(int H, int W, int sampling) {
+    ProgScratch p{};
+    const Scratch b = scratch_layout(H, W, sampling);
+    for (int i = 0; i < kProgScans; ++i) {
+        const ProgGeom g = prog_geom(H, W, sampling, i);
+        p.n_max = std::max(p.n_max, g.n);
+        if (kProgScript[i].Ss) p.run_at[i] = p.run_elems, p.run_elems += g.n;
+    }
+    p.levels = prog_levels(p.n_max, true);
+    const uint64_t n1 = p.n_max + 1;
+    const uint64_t scan_bytes = (p.n_max * kProgScanBlockBits + 7) / 8;
+    p.stuff_chunks = (scan_bytes + kStuffChunk - 1) / kStuffChunk;
+    p.scan_words = p.stuff_chunks * (kStuffChunk / 4);
+    p.partial_elems = std::max(scan_partials(p.n_max), scan_partials(p.stuff_chunks));
+    auto align = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    size_t at = b.total;
+    p.coefs = b.coefs, p.tables = b.tables;
+    p.runs = at, at = align(at + p.run_elems * sizeof(uint32_t));
+    p.ecount = at, at = align(at + n1 * sizeof(uint64_t));
+    p.bcount = at, at = align(at + n1 * sizeof(uint64_t));
+    p.ccount = at, at = align(at + n1 * sizeof(uint64_t));
+    p.jump = at, at = align(at + (size_t)p.levels * n1 * sizeof(uint32_t));
+    p.mark = at, at = align(at + n1 * sizeof(uint32_t));
+    p.offsets = at, at = align(at + n1 * sizeof(uint64_t));
+    p.words = at, at = align(at + p.scan_words * sizeof(uint32_t));
+    p.chunks = at, at = align(at + (p.stuff_chunks + 1) * sizeof(uint64_t));
+    p.partial = at, at = align(at + p.partial_elems * sizeof(uint64_t));
+    p.freq = at, at = align(at + kProgFreqWords * sizeof(uint64_t));
+    p.total = at;
+    return p;
+}
+
 }  // namespace jpeg
 }  // namespace r2f
 
@@ -302,13 +429,20 @@ uint64_t r2f_jpeg_bound_bytes_ex(int H, int W, int sampling) {
 }
 
 int r2f_jpeg_header_ex(const r2f_jpeg_opts* o, int H, int W, uint8_t* buf, size_t cap, size_t* len) {
-    if (!o || !len || o->optimize) return R2F_EINVAL;  // (an optimized header needs the frame's statistics: r2f_jpeg_encode_ex)
+    if (!o || !len || o->optimize || o->progressive) return R2F_EINVAL;  // (an optimized header needs the frame's statistics: r2f_jpeg_encode_ex)
     r2f::jpeg::Huffman h;
     r2f::jpeg::std_huffman(&h);
     const int n = r2f::jpeg::header(o->quality, o->sampling, h, H, W, buf, cap);
     if (n < 0) return R2F_EINVAL;
     *len = (size_t)n;
     return R2F_OK;
+}
+
+uint64_t r2f_jpeg_bound_bytes_opts(const r2f_jpeg_opts* o, int H, int W) {
+    if (!o || (o->progressive != 0 && o->progressive != 1)) return 0;
+    if (!o->progressive) return r2f_jpeg_bound_bytes_ex(H, W, o->sampling);
+    if (H < 1 || W < 1 || H > r2f::jpeg::kMaxDim || W > r2f::jpeg::kMaxDim || !r2f::jpeg::valid_sampling(o->sampling)) return 0;
+    return r2f::jpeg::prog_bound_bytes(H, W, o->sampling);
 }
 
 int r2f_jpeg_optimal_table(const uint64_t freq[256], uint8_t bits[17], uint8_t huffval[256], int* n) {

@@ -110,5 +110,80 @@ bool rows_grid(int H, int W, int y0, int y1, RowsGrid* g);
 // The same for a sampling: y0 a multiple of the MCU height (16 or 8), y1 one too or H.
 bool rows_grid(int H, int W, int sampling, int y0, int y1, RowsGrid* g);
 
+// ---- Pillow's progressive=True (libjpeg-turbo jcphuff.c over jpeg_simple_progression's ten scans; optimize_coding forced, so
+// every scan but the DC refinement carries its own optimized tables).  The DC scans walk the MCU grid's blocks, dummies included;
+// each AC scan walks its one component's ceil(comp_w / 8) x ceil(comp_h / 8) blocks row-major, dummies left out.
+constexpr int kProgScans = 10;
+constexpr int kProgEobrunMax = 0x7FFF;      // jcphuff.c: an EOB run is flushed when it reaches this many blocks
+constexpr int kProgMaxBE = 1000 - 64 + 1;   // ... or when its buffered correction bits pass MAX_CORR_BITS - DCTSIZE2 + 1
+// Most bits one block can add to all ten scans together: DC 16 + 11 and 1; per AC position the code and value bits of the scan
+// that first makes it non-zero (16 + 10) and one correction bit per later refinement (Y 2, chroma 1); per AC scan at most three
+// ZRLs (16 bits each) and one EOB run symbol with its extra bits (16 + 14).  Y: 28 + 63 * 28 + 9 * 16 + 4 * 30 = 2056;
+// chroma: 28 + 63 * 27 + 6 * 16 + 2 * 30 = 1885.
+constexpr int kProgBlockBoundBits = 2056;
+// Most bits one block can take in one scan (its own symbols, a run's EOB symbol and its correction bits): 63 * (16 + 10 + 1) +
+// 3 * 16 + 30 (the DC scans: 27 and 1).
+constexpr int kProgScanBlockBits = 63 * 27 + 3 * 16 + 30;
+constexpr int kProgFrameHeaderBytes = 177;  // SOI, APP0, 2 DQT, SOF2
+// AC symbols of a progressive scan: run / size 160, ZRL, EOB0 .. EOB14 (176 at most, the baseline's 162 less EOB plus 15 runs)
+constexpr int kProgAcSymbols = 176;
+constexpr int kProgScanHeaderMax = 2 + 2 + 1 + 16 + kProgAcSymbols + 10;  // the largest scan header: an AC DHT and its SOS (DC: <= 80)
+struct ProgScan {
+    int ncomp, comp;  // components in the scan: 3 (Y Cb Cr, the DC scans) or 1 (`comp`: 0 Y, 1 Cb, 2 Cr)
+    int Ss, Se, Ah, Al;
+};
+const ProgScan& prog_scan(int i);
+// Table slots of a scan: 2 for the DC first scan (DC0 of Y, DC1 of Cb and Cr), 0 for the DC refinement, 1 for an AC scan.
+inline int prog_slots(const ProgScan& s) { return s.Ss == 0 ? (s.Ah == 0 ? 2 : 0) : 1; }
+// The blocks a scan walks, and their grid for an AC scan (bw x bh; the DC scans: mcus x blocks per MCU, bw = blocks per MCU).
+struct ProgGeom {
+    uint64_t n;
+    int bw, bh;
+};
+ProgGeom prog_geom(int H, int W, int sampling, int scan);
+// Worst-case bits of the whole entropy-coded data, and the file: headers, every scan byte stuffed, the padding bytes, EOI.
+inline uint64_t prog_bound_bits(int H, int W, int sampling) { return mcus(H, W, sampling) * layout(sampling).nb * kProgBlockBoundBits; }
+inline uint64_t prog_bound_bytes(int H, int W, int sampling) {
+    return kProgFrameHeaderBytes + 2 * (uint64_t)kProgScans * (kProgScanHeaderMax + 1) + 2 * ((prog_bound_bits(H, W, sampling) + 7) / 8) + 2;
+}
+// One scan's optimized tables: bits[slot][16] (lengths 1..16) and huffval[slot][n[slot]].
+struct ProgTables {
+    uint8_t bits[2][16];
+    uint8_t huffval[2][256];
+    int n[2];
+};
+// SOI .. SOF2; returns its length (kProgFrameHeaderBytes) or -1 for bad arguments or a cap below it.
+int prog_frame_header(int quality, int sampling, int H, int W, uint8_t* buf, size_t cap);
+// The scan's DHT segments (none for the DC refinement) and SOS; returns the length or -1.
+int prog_scan_header(int scan, const ProgTables& t, uint8_t* buf, size_t cap);
+// The scan's exact bits before padding: freq[slot][256] coded with `t`, plus the raw bits no symbol implies (`extra`: the
+// correction bits of a refinement, the one bit per block of the DC refinement).  UINT64_MAX when a counted symbol has no code.
+uint64_t prog_scan_bits(int scan, const uint64_t freq[2][256], const ProgTables& t, uint64_t extra);
+// Pointer-doubling levels the run resolution of an n-block scan needs: consecutive flushes of one stretch lie at least 15 blocks
+// apart in a refinement scan (a flush needs 938 correction bits, at most 63 per block) and 0x7FFF apart in a first scan, so a
+// chain has at most n / 15 + 2 (n / 0x7FFF + 2) links; 2^levels exceeds that.
+int prog_levels(uint64_t n, bool refine);
+
+// Byte offsets of the progressive encoder's device scratch (16-byte aligned): the baseline scratch (whose coefficients, tables
+// and transform pass it shares), then the per-scan state.
+struct ProgScratch {
+    size_t coefs, tables;  // as Scratch
+    size_t runs;           // uint32 per block of each AC scan: the EOB run a block starts (0: none), scans back to back
+    size_t ecount, bcount, ccount;  // uint64 [n_max + 1]: joining blocks, correction bits, coded blocks -> exclusive prefix sums
+    size_t jump;           // uint32 [levels][n_max + 1]: the run chain's pointer-doubling levels
+    size_t mark;           // uint32 [n_max + 1]: run starts
+    size_t offsets;        // uint64 [n_max + 1]: bits per block, then their exclusive scan
+    size_t words;          // uint32 [scan_words]: one packed scan
+    size_t chunks;         // uint64 [stuff_chunks + 1]
+    size_t partial;        // uint64 [partial_elems]
+    size_t freq;           // uint64 [kProgScans][2][256] symbol counts, then [kProgScans] extra bits, then 2 words: file position, overflow
+    size_t total;
+    uint64_t n_max, run_elems, scan_words, stuff_chunks, partial_elems;
+    uint64_t run_at[kProgScans];  // element offset of each AC scan's runs
+    int levels;
+};
+ProgScratch prog_scratch_layout(int H, int W, int sampling);
+constexpr size_t kProgFreqWords = (size_t)kProgScans * 2 * 256 + kProgScans + 2;
+
 }  // namespace jpeg
 }  // namespace r2f

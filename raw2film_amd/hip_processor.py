@@ -615,15 +615,17 @@ class HipProcessor:
         return None if out_u8 is None else self._download(out_u8)  # DEVICE -> HOST, the reference's read_texture/map_sync
 
     # ------------------------------------------------------------------ JPEG export (gui.py:2338-2341)
-    def encode_jpeg(self, image, quality=100, *, subsampling=-1, optimize=False, exif=b"") -> bytes:
+    def encode_jpeg(self, image, quality=100, *, subsampling=-1, optimize=False, exif=b"", progressive=False) -> bytes:
         """`Image.fromarray(image).save(f, "JPEG", quality=quality, subsampling=subsampling, optimize=optimize, exif=exif)` on the
         device: the same bytes Pillow writes (JFIF, standard or optimized Huffman tables, no ICC).  image: uint8 (H, W, 3), a NumPy
         array or a torch tensor (a CUDA tensor may be a row-strided view); quality: an int 0 .. 100 like the reference's slider
         (gui.py:2532-2588).  subsampling: -1 (libjpeg's default, 4:2:0), 0 / "4:4:4", 1 / "4:2:2", 2 / "4:2:0".  optimize: truthy
         for per-image Huffman tables (the call then waits once for the frame's symbol counts).  exif: bytes or a PIL.Image.Exif,
-        written as an APP1 segment after the JFIF one (empty: none)."""
+        written as an APP1 segment after the JFIF one (empty: none).  progressive: True for Pillow's progressive=True (SOF2, libjpeg's
+        ten scans, each with its own optimized tables, so optimize makes no difference); False, 0 or 1 -- anything else raises."""
         q = _jpeg_quality(quality)
         opts = _jpeg_options(subsampling, optimize, exif)
+        prog = _jpeg_progressive(progressive)
         torch = self._torch
         if isinstance(image, np.ndarray):
             _check_jpeg_image(image.dtype == np.uint8, image.shape, image.dtype)
@@ -634,10 +636,10 @@ class HipProcessor:
                 image = image.to(self.device)
         else:
             raise ValueError(f"encode_jpeg: expected a uint8 (H, W, 3) NumPy array or torch tensor, got {type(image).__name__}")
-        return self._encode_device(image, q, *opts)
+        return self._encode_device(image, q, *opts, progressive=prog)
 
     def process_jpeg(self, src, negative_film, grain_size, grain_sigma, quality=100, stream=False, file=None, *, subsampling=-1,
-                     optimize=False, exif=b"", **settings):
+                     optimize=False, exif=b"", progressive=False, **settings):
         """The export of one frame (gui.py:2338-2341): process()'s render with the same keywords -- the pixels process() returns
         for them -- encoded on the device as encode_jpeg does; only the file comes back to the host.  The frame a preview keeps on
         the device (cache=True) is left alone: the next preview re-render uploads nothing.  The export always extracts and uploads
@@ -650,9 +652,11 @@ class HipProcessor:
         file: a path or a binary file object the bytes are written into (as they arrive, when streaming); the call then returns
         their count.  Without it the call returns the bytes.
         subsampling, optimize, exif: Pillow's, as in encode_jpeg.  optimize=True needs the whole frame's symbol counts before the
-        first scan byte: with stream=True it takes the one-piece path, and `stream_rejected` says so."""
+        first scan byte: with stream=True it takes the one-piece path, and `stream_rejected` says so.  progressive (as in
+        encode_jpeg) needs the whole frame for every scan: the same."""
         q = _jpeg_quality(quality)
         opts = _jpeg_options(subsampling, optimize, exif)
+        prog = _jpeg_progressive(progressive)
         for k in ("dst_texture", "histogram_texture"):
             if settings.pop(k, None) is not None:
                 raise ValueError(f"process_jpeg writes a file: {k} is not taken (use process() for the preview)")
@@ -663,7 +667,7 @@ class HipProcessor:
                     if k not in ("self", "src", "negative_film", "grain_size", "grain_sigma", "dst_texture", "histogram_texture", "_")}
         load = {k: settings[k] for k in _LOAD_KEYWORDS}
         if stream:  # process(cache=False)'s gates, in its order: the early ones, then the payload's (_stream_payload's)
-            self.stream_rejected = (_OPTIMIZE_REJECTED if opts[1] else
+            self.stream_rejected = (_PROGRESSIVE_REJECTED if prog else _OPTIMIZE_REJECTED if opts[1] else
                                     "profile_stages is on" if getattr(self, "profile_stages", False) else
                                     host_stream_gate(src, self.stream_bands, settings["rotation"], settings["chroma_nr"],
                                                      settings["canvas_mode"], settings["highlight_burn"]))
@@ -674,22 +678,24 @@ class HipProcessor:
                 return res
         image, layout = self._upload_payload(payload)
         out_u8 = self._render_prepared(image, layout, payload, negative_film, grain_size, grain_sigma, None, None, "cpu", **settings)
-        return deliver(self._encode_device(out_u8, q, *opts), file)
+        return deliver(self._encode_device(out_u8, q, *opts, progressive=prog), file)
 
     def process_preloaded_jpeg(self, cpu_payload, negative_film, grain_size, grain_sigma, quality=100, final_scaling="gpu",
-                               stream=False, file=None, *, subsampling=-1, optimize=False, exif=b"", **settings):
+                               stream=False, file=None, *, subsampling=-1, optimize=False, exif=b"", progressive=False,
+                               **settings):
         """The batch export on the two-phase API: process_preloaded's render of a phase-1 payload, encoded on the device like
         process_jpeg.  The processor's device frame (prepare_gpu_textures') is left alone.  stream=True: the file is Pillow's of
         process_preloaded(cpu_payload, final_scaling=..., ...)'s pixels, and a payload process_preloaded streams in row bands is
-        encoded band by band as in process_jpeg (else `stream_rejected` says why not).  file, subsampling, optimize, exif: see
-        process_jpeg."""
+        encoded band by band as in process_jpeg (else `stream_rejected` says why not).  file, subsampling, optimize, exif,
+        progressive: see process_jpeg."""
         q = _jpeg_quality(quality)
         opts = _jpeg_options(subsampling, optimize, exif)
+        prog = _jpeg_progressive(progressive)
         for k in ("dst_texture", "histogram_texture"):
             if settings.pop(k, None) is not None:
                 raise ValueError(f"process_preloaded_jpeg writes a file: {k} is not taken")
         if stream:
-            self.stream_rejected = (_OPTIMIZE_REJECTED if opts[1] else
+            self.stream_rejected = (_PROGRESSIVE_REJECTED if prog else _OPTIMIZE_REJECTED if opts[1] else
                                     None if self.stream_bands > 1 else f"stream_bands = {self.stream_bands}")
             if self.stream_rejected is None:
                 res = self._stream_jpeg(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, q, file, settings, opts)
@@ -698,16 +704,16 @@ class HipProcessor:
         image, layout = self._upload_payload(cpu_payload)
         out_u8 = self._render_prepared(image, layout, cpu_payload, negative_film, grain_size, grain_sigma, None, None, final_scaling,
                                        **settings)
-        return deliver(self._encode_device(out_u8, q, *opts), file)
+        return deliver(self._encode_device(out_u8, q, *opts, progressive=prog), file)
 
-    def _encode_device(self, image_u8, quality, subsampling=2, optimize=False, exif=b""):
+    def _encode_device(self, image_u8, quality, subsampling=2, optimize=False, exif=b"", progressive=False):
         """A uint8 (H, W, 3) device frame -> the JPEG file's bytes.  The encoder runs on the current stream; reading its 8-byte
-        length back is the one synchronisation (optimize adds one for the symbol counts), then only the file crosses PCIe, into a
+        length back is the one synchronisation (optimize and progressive add one for the symbol counts), then only the file crosses PCIe, into a
         pinned buffer this processor keeps (grown to the largest file so far; a pageable download of a 47 MB file cost up to 34 ms)
         and from there into the bytes object -- with the EXIF APP1 spliced in on the way, in the same single copy."""
         if image_u8.stride(2) != 1 or image_u8.stride(1) != 3 or image_u8.stride(0) < 3 * image_u8.shape[1]:
             image_u8 = image_u8.contiguous()  # (a row-strided view is encoded in place)
-        out, length = self.ctx.jpeg_encode(image_u8, quality, subsampling, optimize)
+        out, length = self.ctx.jpeg_encode(image_u8, quality, subsampling, optimize, progressive)
         n = int(length.item())
         if n <= 0:
             raise RuntimeError("r2f_jpeg_encode reported an empty file")
@@ -1168,6 +1174,7 @@ def _jpeg_quality(quality) -> int:
 _SUBSAMPLINGS = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}
 _EXIF_MAX = 65533  # a marker segment's payload (Pillow's MAX_BYTES_IN_MARKER)
 _OPTIMIZE_REJECTED = "optimize=True: its Huffman tables need the whole frame's statistics before the first scan byte"
+_PROGRESSIVE_REJECTED = "progressive=True: every one of its scans spans the whole frame"
 
 
 def _jpeg_subsampling(subsampling) -> int:
@@ -1199,6 +1206,15 @@ def _jpeg_exif(exif) -> bytes:
 def _jpeg_options(subsampling, optimize, exif):
     """(sampling 0 / 1 / 2, optimize, exif bytes) of an export's options, checked before any work starts."""
     return _jpeg_subsampling(subsampling), bool(optimize), _jpeg_exif(exif)
+
+
+def _jpeg_progressive(progressive) -> bool:
+    """Pillow's progressive option: True / False, or 0 / 1 (NumPy's included); anything else raises ValueError."""
+    if isinstance(progressive, (bool, np.bool_)):
+        return bool(progressive)
+    if isinstance(progressive, (int, np.integer)) and int(progressive) in (0, 1):
+        return bool(int(progressive))
+    raise ValueError(f"JPEG progressive must be True / False (or 0 / 1), got {progressive!r}")
 
 
 def _check_jpeg_image(is_uint8, shape, dtype):
