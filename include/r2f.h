@@ -71,8 +71,10 @@ enum {
                                      samples this call writes for the halation's FFT channels into the context's exposure-range record
                                      -- a grid of 64 x 256-pixel tiles over the GLOBAL frame, reset by r2f_write_frame_params -- which is
                                      what r2f_render's front kernel does for a whole frame.  A call whose kernel cannot record (the
-                                     generic pointwise kernel) leaves its tiles "unknown": the windows that touch them keep complex128,
-                                     nothing goes wrong silently */
+                                     generic pointwise kernel: an input view that is not 16-byte aligned, destination planes that do
+                                     not allow float4 stores, option front_fast = 0) marks the frame's record unusable: if any
+                                     tracked call of the frame could not record, every window of the frame's halation call keeps
+                                     complex128 (its rows may share a 64-row tile with rows another call recorded) */
     R2F_F_RANGE_VALID = 1u << 9    /* r2f_stage_halation: the caller has kept the record for the rows the `exposure` buffer holds for the
                                      FFT channels (own rows by R2F_F_TRACK_RANGE front calls, rows received from neighbours by
                                      r2f_stage_exposure_range): the passes may then choose the 12-byte scratch element on the device,

@@ -253,7 +253,8 @@ __device__ __forceinline__ void curve_eval_near_lds(const float4* cells, const D
 
 // ---------------------------------------------------------------------------- the exposure-range record, per tile
 // The frame-level range fields above decide nothing any more (the measurement harness derives the frame's extremes from the tiles,
-// r2f_frame_exposure_range; e_max = +inf remains the "a front kernel could not record" mark): the halation's FFT passes choose
+// r2f_frame_exposure_range; e_max = +inf remains the "a front kernel could not record" mark, which keeps every window pair of the
+// frame's halation call on complex128, fft_decide_kernel): the halation's FFT passes choose
 // their scratch element PER WINDOW PAIR from the range of the samples that pair's two windows hold -- the error of the 12-byte
 // element scales with the energy of the window a pixel shares, not of the frame (r2f_api.hip, dyn_rule) -- and a window's range
 // comes from a grid of tiles over the GLOBAL frame: tile (gy / 64, x / 256) holds {min, max |.|} of the exposure samples recorded

@@ -318,7 +318,9 @@ __device__ __forceinline__ char* simg(double2* s1, long long pair, long long n) 
 //   stencil makes from the rows within its reach): rows that feed only discarded outputs cannot reach a kept one, and the rows
 //   within the reach of a kept output are reflected into the frame rows of the window (a window keeps an output only if it holds the
 //   reach above it).  tests/test_gpu_fft.py holds both edge cases.
-// A tile nobody recorded (reset values) means "unknown": complex128.
+// A tile nobody recorded (reset values) means "unknown": complex128.  So does the whole call once a front call of the frame was
+// asked to record and could not (the mark: e_max = +inf, frame_params_kernel mode 3): the rows it wrote may share a 64-row tile
+// with rows another call recorded, and that tile would read as known without them.
 #ifndef R2F_DECIDE_OWN_COLUMNS_ONLY
 #define R2F_DECIDE_OWN_COLUMNS_ONLY 0
 #endif
@@ -332,7 +334,7 @@ __global__ __launch_bounds__(256) void fft_decide_kernel(const FftConvArgs a, co
     const int pc = blockIdx.x * 256 + threadIdx.x;
     if (pc >= a.ppc) return;
     int lo = (int)kFrameMinReset, hi = 0;
-    bool known = rec.tiles != nullptr;
+    bool known = rec.tiles != nullptr && !(rec.blk && rec.blk->e_max == 0x7f800000u);
     for (int half = 0; half < 2 && known; ++half) {
         int wy, wx;
         if (!window_of(a, 2 * pc + half, wy, wx)) continue;

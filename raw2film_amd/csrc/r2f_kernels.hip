@@ -1323,7 +1323,8 @@ hipError_t launch_noise(const NoiseArgs& a, hipStream_t s) {
 // mode 0: only the seed (a stage entry's own write in the middle of a frame keeps the exposure range the front kernel recorded);
 // 1: the whole block (seed + range reset: the start of a frame); 2: only the range reset (a caller that keeps the seed resident);
 // 3: the range is made unusable (max = +inf) -- a front kernel that was asked to record the range of what it writes and cannot (its
-// rows' TILES simply stay unwritten, which the per-window choice reads as "unknown": complex128).
+// rows' TILES stay unwritten, but they may share a tile with rows another call recorded: fft_decide_kernel reads the mark and keeps
+// every pair of the call on complex128).
 // Modes 1 and 2 also reset the record's tile grid ({+inf, 0} = unknown), one thread per tile.
 __global__ __launch_bounds__(256) void frame_params_kernel(FrameParams* dst, const FrameParams v, const int mode, int2* tiles, const int n_tiles) {
     const int i = blockIdx.x * 256 + threadIdx.x;

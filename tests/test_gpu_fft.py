@@ -596,6 +596,125 @@ def test_the_per_window_choice_counts_what_the_reflection_brings_into_an_edge_wi
     assert info["packed_pairs"] == (1 if edge == "right" else 3), info
 
 
+@pytest.mark.parametrize("route", ["misaligned_view", "front_fast_0"])
+@pytest.mark.parametrize("frame", ["bright_band_in_shadow", "shadow_band_in_bright"])
+def test_a_front_call_that_cannot_record_keeps_every_pair_of_its_frame_on_complex128(ctx, frame, route):
+    """The R2F_F_TRACK_RANGE front calls of one frame may mix kernels: a call whose input view is not 16-byte aligned (a C-ABI
+    caller's buffer), or that runs with front_fast 0, takes the generic kernel, which cannot record -- it leaves the mark (e_max =
+    +inf) and no tiles.  Here it writes rows [100, 120), and the tracked calls either side of it write the other rows of range-tile
+    row 1 (rows 64 .. 127): that tile reads as KNOWN while it holds none of the band's samples.  The decide kernel used to let the
+    pairs whose windows hold the band take the 12-byte element on the tracked rows' range alone; it now reads the mark, and every pair
+    of the call keeps complex128, whichever of the three calls it is (first, between, last).  The next frame's reset clears the mark.
+    Frames: deep shadow (1e-3 .. 2e-3) with a bright (4 000 .. 8 000) band over one tile column of rows 100 .. 119, and the reverse.
+    (The band spans one tile column, not the whole row: the element's rounding of a window row spreads along the row, so the shadows
+    of the same rows beyond the stencil's reach of the band show it, while across the rows it stays within the reach, where the band's
+    own light outweighs it.  In the reverse frame no output is dark enough to show it -- the shadow band lies within the reach of the
+    bright field around it, and the forced element stays within the promise -- so there the host model's verdict carries the test.)"""
+    import os
+    import sys
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import scratch_choice_model as scm
+
+    neg, _, _ = stocks()
+    rng = np.random.default_rng(16)
+    H, W = 600, 1100
+    k = ok.compute_halation_kernel(341.33, halation_green_factor=0.3)
+    lut2d = neg.get_input_lut(6000, 0.0, 0.0)
+    ctx.set_lut2d(lut2d)
+    ctx.set_curve1d(neg.get_density_curve(0.0, 1.0))
+    ctx.set_kernel(0, k)
+    ctx.set_option("stencil_fft_window_rows", 256)
+    ctx.set_option("stencil_fft_window", 512)
+    params = ctx.make_params(halation=True)  # (no matrix: the input is XYZ)
+    # a neutral input whose exposure in the FFT channels (the 2-D LUT's output, proportional to X + Y + Z) lies in the ranges above
+    white = np.array([0.9505, 1.0, 1.089], dtype=np.float32)
+    gain = float(np.mean(st.apply_2d_lut(white[None, None, :], lut2d)[0, 0, :2]))
+
+    def level(lo, hi, shape):
+        return (rng.uniform(lo, hi, shape)[..., None] / gain * white).astype(np.float32)
+
+    dark, bright = (1e-3, 2e-3), (4000.0, 8000.0)
+    field, band = (dark, bright) if frame == "bright_band_in_shadow" else (bright, dark)
+    img = level(*field, (H, W))
+    img[100:120, :256] = level(*band, (20, 256))
+    src = torch.from_numpy(img).cuda()
+    E = torch.empty((3, H, W), dtype=torch.float32, device="cuda")
+    keep = []  # (the misaligned copies stay alive until the halation has run)
+
+    def front(y0, y1, records):
+        rows = src[y0:y1]
+        if not records and route == "misaligned_view":  # a buffer 4 bytes off 16-byte alignment: the generic kernel
+            big = torch.empty((y1 - y0) * W * 3 + 1, dtype=torch.float32, device="cuda")
+            rows = big[1:].view(y1 - y0, W, 3)
+            rows.copy_(src[y0:y1])
+            assert rows.data_ptr() % 16 == 4
+            keep.append(big)
+        if not records and route == "front_fast_0":
+            ctx.set_option("front_fast", 0)
+        try:
+            ctx.stage_front(rows, params, 0, in_gy0=y0, dst=E, y0=y0, y1=y1, H_global=H, track_range=True)
+        finally:
+            ctx.set_option("front_fast", 1)
+
+    def halation(range_valid=False, forced=0):
+        ctx.set_option("stencil_fft_scratch96", forced)
+        d = torch.empty((3, H, W), dtype=torch.float32, device="cuda")
+        ctx.stage_halation(E, d, params, y0=0, y1=H, H_global=H, range_valid=range_valid)
+        ctx.set_option("stencil_fft_scratch96", 0)
+        return d
+
+    geo = scm.geometry(k, (0, 1))
+    vy, vx = 256 - geo[0] + 1, (512 - geo[1] + 1) & ~3
+    gx = (W + vx - 1) // vx
+    ntiles = gx * ((H + vy - 1) // vy)
+
+    def kept(pc):  # the outputs the two windows of pair pc keep
+        return [(slice(t // gx * vy, t // gx * vy + vy), slice(t % gx * vx, t % gx * vx + vx)) for t in (2 * pc, 2 * pc + 1) if t < ntiles]
+
+    def worst(a, b, where=(slice(None), slice(None))):  # beyond the ulp two fp32 roundings may differ by
+        a, b = a[(slice(0, 2),) + where], b[(slice(0, 2),) + where]
+        return float((np.abs(a - b) - np.abs(b) * 2.0 ** -23).max())
+
+    def against_own_samples(info, flags):
+        m = scm.model(E.cpu().numpy(), geo, 0, H, H, W, 0, H, info["bound"], info["floor"], (0, 1))
+        assert info["armed"] and len(flags) == len(m) == info["pairs"] > 0, info
+        return m, [(pc, m[pc]) for pc in range(len(m)) if flags[pc] and not m[pc][0]]
+
+    orders = {"first": [(100, 120, False), (0, 100, True), (120, H, True)],
+              "between": [(0, 100, True), (100, 120, False), (120, H, True)],
+              "last": [(0, 100, True), (120, H, True), (100, 120, False)]}
+    for order, calls in orders.items():
+        ctx.write_frame_params(params)
+        for y0, y1, records in calls:
+            front(y0, y1, records)
+        chosen = halation(range_valid=True)
+        info, flags = ctx.frame_exposure_range(), ctx.frame_scratch_flags()
+        keep.clear()
+        m, bad = against_own_samples(info, flags)
+        rejected = [pc for pc in range(len(m)) if not m[pc][0]]
+        assert rejected, (order, m)                        # the band's pairs must keep complex128 on their own samples ...
+        assert not bad, (order, bad)                       # ... no flag says otherwise ...
+        assert info["packed_pairs"] == 0 and np.isinf(info["max_abs"]), (order, info)  # ... nor any other: the mark counts
+        D = {"chosen": chosen, "c128": halation(), "forced": halation(forced=1)}
+        D = {name: d.cpu().numpy().astype(np.float64) for name, d in D.items()}
+        bite = max(worst(D["forced"], D["c128"], region) for pc in rejected for region in kept(pc))
+        print(f"{frame} {route} untracked call {order}: pairs {info['pairs']}, rejected by the model {rejected}; "
+              f"forced element on them {bite:.2e}, chosen {worst(D['chosen'], D['c128']):.2e}")
+        if frame == "bright_band_in_shadow":
+            assert bite > 2 * 3.6e-7, (order, bite)        # the element on those pairs WOULD break the promise
+        assert worst(D["chosen"], D["c128"]) <= 3.6e-7, (order, worst(D["chosen"], D["c128"]))  # the promise, everywhere
+    # the mark does not outlive its frame: the next one, every row recorded, takes the element again where its samples allow
+    ctx.write_frame_params(params)
+    for y0, y1 in ((0, 100), (100, 120), (120, H)):
+        front(y0, y1, True)
+    halation(range_valid=True)
+    info, flags = ctx.frame_exposure_range(), ctx.frame_scratch_flags()
+    m, bad = against_own_samples(info, flags)
+    assert not bad, bad
+    assert np.isfinite(info["max_abs"]) and 0 < info["packed_pairs"] < info["pairs"], info
+
+
 def test_no_window_pair_takes_the_twelve_byte_element_against_its_own_samples(ctx):
     """The soundness of the per-window-pair choice without any numerics (tools/scratch_choice_model.py): the flags the device left
     (r2f_frame_scratch_flags) against a host model that gathers, from the exposure planes themselves, the samples whose rounding can
@@ -616,6 +735,25 @@ def test_no_window_pair_takes_the_twelve_byte_element_against_its_own_samples(ct
     assert tot[0] > 300 and tot[1] > 30          # the cases do exercise the choice ...
     assert tot[1] <= tot[2]                       # ... a superset decides, so it never allows more than the exact range would ...
     assert tot[1] >= 0.5 * tot[2], tot            # ... and the 64 x 256 tiles do not cost most of what it allows
+
+
+def test_no_window_pair_takes_the_twelve_byte_element_when_several_producers_keep_its_record(ctx):
+    """The soak above with the record of a call kept by SEVERAL producers (tools/scratch_choice_model.py --producers mixed): the rows
+    of the call's source buffer cut into 1-4 segments at random rows (not at tile boundaries), each recorded by the fast front kernel,
+    by the range kernel, or by a front call that cannot record (a misaligned input view or front_fast 0: the generic kernel), for whole
+    frames and row shards.  A flagged pair must satisfy the rule on its own samples, as before; a call with a segment that could not
+    record must take the element on no pair, and the mark (e_max = +inf) must say so exactly then."""
+    import os
+    import sys
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import scratch_choice_model as scm
+
+    tot, bad = scm.soak(ctx, torch, budget=60, seed=20261016, producers="mixed")
+    print(f"mixed producers against the host model: {tot[0]} pairs, {tot[1]} took the element, {tot[2]} allowed by their own samples")
+    assert not bad, bad[:5]
+    # (with no violation, every pair that took the element did so in a call whose segments all recorded)
+    assert tot[0] > 250 and 20 < tot[1] <= tot[2], tot
 
 
 def test_a_nan_sample_keeps_its_windows_on_complex128():

@@ -15,10 +15,16 @@ kernel or by the front kernel, and whole frames through r2f_render itself (eager
 costs).  Numerics play no part: this is the soundness of the decision, which no parity soak sees (the right-edge hole of round 6 -- a
 window that reflects in columns its tiles did not cover -- passed 2 700 fuzz cases; this tool finds it in 5 of 1 500 random calls:
 profiles/r06_scratch_choice_model.txt).
-    python tools/scratch_choice_model.py [--budget 300] [--seed 1] [--verbose] [--lib tools/_var/lib_owncols.so]
+--producers mixed: the record of one call is kept by SEVERAL producers instead of one -- the source buffer's rows cut into 1-4 segments
+anywhere (not at tile boundaries), each recorded by the fast front kernel (R2F_F_TRACK_RANGE), by the range kernel, or by a front call
+asked to record that cannot (an input view 4 bytes off 16-byte alignment, or front_fast 0: the generic kernel).  A tile may then hold
+rows of a segment that recorded and of one that did not; the mark the latter leaves must keep every pair of the call on complex128.
+On top of the model's check, such a call must take the element on no pair, and the mark must be there exactly when a segment could
+not record.
+    python tools/scratch_choice_model.py [--budget 300] [--seed 1] [--producers single|mixed] [--verbose] [--lib tools/_var/lib_owncols.so]
 (--lib: another build of the library, e.g. `python tools/build_variant.py owncols=-DR2F_DECIDE_OWN_COLUMNS_ONLY=1`, the decide kernel
 as it was before the reflected columns counted: the tool must FAIL on it.)
-tests/test_gpu_fft.py runs the same function on a fixed, smaller budget."""
+tests/test_gpu_fft.py runs the same function on a fixed, smaller budget, with either kind of producers."""
 import argparse
 import os
 import sys
@@ -103,8 +109,9 @@ def random_frame(rng, H, W, hostile):
     return np.ascontiguousarray(img, dtype=np.float32)
 
 
-def run_case(ctx, torch, rng, params, kernel, hostile, front=None, log=None):
-    """One random case; returns (pairs, packed, allowed_by_model, violations)."""
+def run_case(ctx, torch, rng, params, kernel, hostile, front=None, log=None, producers="single"):
+    """One random case; returns (pairs, packed, allowed_by_model, violations).  producers: "single" (one producer records the call's
+    rows: the range kernel, the fast front kernel or r2f_render) or "mixed" (run_mixed_case; needs `front`)."""
     fft_channels = (0, 1)  # (the stand-in halation stencil leaves blue to a single tap)
     geo = geometry(kernel, fft_channels)
     bh, bw, ay, ax = geo
@@ -125,6 +132,8 @@ def run_case(ctx, torch, rng, params, kernel, hostile, front=None, log=None):
         buf1 = max(buf1, min(ay - y0 + 1, H))
     if y1 + below > H:
         buf0 = min(buf0, max(2 * (H - 1) - (y1 - 1 + below), 0))
+    if producers == "mixed":
+        return run_mixed_case(ctx, torch, rng, params, geo, fft_channels, img, H, W, y0, y1, buf0, buf1, front, log)
     use_front = front is not None and bool(rng.integers(0, 3) == 0)
     use_render = front is not None and not shard and not use_front and bool(rng.integers(0, 3) == 0)
     ctx.write_frame_params(params)
@@ -178,6 +187,64 @@ def run_case(ctx, torch, rng, params, kernel, hostile, front=None, log=None):
     return len(m), int(flags.sum()), sum(a for a, _, _ in m), [(H, W, y0, y1, buf0, buf1, pc, v) for pc, v in bad]
 
 
+def run_mixed_case(ctx, torch, rng, params, geo, fft_channels, img, H, W, y0, y1, buf0, buf1, front, log=None):
+    """run_case with producers="mixed": the rows [buf0, buf1) of the call's source buffer cut into 1-4 segments at random rows, each
+    recorded by the fast front kernel, the range kernel or a front call that cannot record."""
+    src = torch.from_numpy(img).cuda()
+    Efull = torch.empty((3, H, W), dtype=torch.float32, device="cuda")
+    ctx.stage_front(src, front, 0, dst=Efull)  # every row's exposure (what the range segments record; rows outside the buffer)
+    cuts = sorted({int(c) for c in rng.integers(buf0 + 1, buf1, int(rng.integers(0, 4)))}) if buf1 - buf0 > 1 else []
+    bounds = [buf0] + cuts + [buf1]
+    segments = []
+    for a, b in zip(bounds[:-1], bounds[1:]):
+        how = ("front", "range", "cannot")[int(rng.integers(0, 3))]
+        if how == "cannot":
+            how = ("misaligned", "front_fast_0")[int(rng.integers(0, 2))]
+        segments.append((a, b, how))
+    ctx.write_frame_params(params)
+    keep = []  # (the misaligned copies stay alive until the call has read them)
+    for a, b, how in segments:
+        if how == "range":
+            ctx.stage_exposure_range(Efull, y0=a, y1=b)
+            continue
+        rows = src[a:b]
+        if how == "misaligned":
+            n = (b - a) * W * 3
+            big = torch.empty(n + 1, dtype=torch.float32, device="cuda")
+            rows = big[1:].view(b - a, W, 3)
+            rows.copy_(src[a:b])
+            keep.append(big)
+        if how == "front_fast_0":
+            ctx.set_option("front_fast", 0)
+        try:
+            ctx.stage_front(rows, front, 0, in_gy0=a, dst=Efull, y0=a, y1=b, H_global=H, track_range=True)
+        finally:
+            if how == "front_fast_0":
+                ctx.set_option("front_fast", 1)
+    # (a frame whose width is not a multiple of 4 has no 16-byte aligned rows: no front call of it can record)
+    unrecorded = any(how in ("misaligned", "front_fast_0") or (how == "front" and W % 4) for _, _, how in segments)
+    D = torch.empty((3, y1 - y0, W), dtype=torch.float32, device="cuda")
+    ctx.stage_halation(Efull[:, buf0:buf1], D, params, src_gy0=buf0, dst_gy0=y0, y0=y0, y1=y1, H_global=H, range_valid=True)
+    info = ctx.frame_exposure_range()
+    flags = ctx.frame_scratch_flags()
+    del keep
+    if not info["armed"]:
+        return 0, 0, 0, []
+    m = model(Efull.cpu().numpy(), geo, y0, y1, H, W, buf0, buf1, info["bound"], info["floor"], fft_channels)
+    assert len(m) == len(flags), (len(m), len(flags), H, W, y0, y1)
+    case = (H, W, y0, y1, buf0, buf1)
+    bad = [case + (pc, m[pc]) for pc in range(len(m)) if flags[pc] and not m[pc][0]]
+    if unrecorded and flags.any():
+        bad.append(case + ("a segment could not record, yet pairs took the element", int(flags.sum()), segments))
+    if unrecorded != bool(np.isinf(info["max_abs"])):
+        bad.append(case + ("the could-not-record mark disagrees with the segments", info["max_abs"], segments))
+    if log:
+        log(f"H {H:4d} W {W:4d} rows [{y0}, {y1}) buffer [{buf0}, {buf1}) segments {[(a, b, how) for a, b, how in segments]}: "
+            f"pairs {len(m)} packed {int(flags.sum())} allowed by their own samples {sum(a for a, _, _ in m)}"
+            f"{'  VIOLATIONS ' + str(bad) if bad else ''}")
+    return len(m), int(flags.sum()), sum(a for a, _, _ in m), bad
+
+
 def setup(ctx):
     """The halation stencil of the 100 MP pitch (87 x 87 taps, an 85 x 85 box), the stand-in stock's tables, 256 x 512 windows."""
     from helpers import SEED, oracle_inputs, stocks
@@ -191,7 +258,7 @@ def setup(ctx):
     return ctx.make_params(halation=True), front, np.asarray(p.halation_kernel)
 
 
-def soak(ctx, torch, budget, seed, log=None):
+def soak(ctx, torch, budget, seed, log=None, producers="single"):
     import hostile
 
     params, front, kernel = setup(ctx)
@@ -199,7 +266,7 @@ def soak(ctx, torch, budget, seed, log=None):
     tot = np.zeros(3, dtype=np.int64)
     bad = []
     for _ in range(budget):
-        n, packed, allowed, v = run_case(ctx, torch, rng, params, kernel, hostile, front=front, log=log)
+        n, packed, allowed, v = run_case(ctx, torch, rng, params, kernel, hostile, front=front, log=log, producers=producers)
         tot += (n, packed, allowed)
         bad += v
     return tot, bad
@@ -211,15 +278,20 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--lib", default=None)
+    ap.add_argument("--producers", choices=("single", "mixed"), default="single",
+                    help="single: one producer records a call's rows; mixed: 1-4 row segments, each recorded by its own producer")
     args = ap.parse_args()
     import torch
 
     from raw2film_amd.context import HipContext
 
     ctx = HipContext(0, lib_path=args.lib)
-    tot, bad = soak(ctx, torch, args.budget, args.seed, log=print if args.verbose else None)
-    print(f"# tools/scratch_choice_model.py --budget {args.budget} --seed {args.seed}{' --lib ' + args.lib if args.lib else ''}: {tot[0]} window pairs in {args.budget} random calls "
-          f"(whole frames and row shards; record by the range kernel, the front kernel, r2f_render)")
+    tot, bad = soak(ctx, torch, args.budget, args.seed, log=print if args.verbose else None, producers=args.producers)
+    mixed = args.producers == "mixed"
+    print(f"# tools/scratch_choice_model.py --budget {args.budget} --seed {args.seed}{' --producers mixed' if mixed else ''}"
+          f"{' --lib ' + args.lib if args.lib else ''}: {tot[0]} window pairs in {args.budget} random calls "
+          f"(whole frames and row shards; record by "
+          f"{'segments of the fast front kernel, the range kernel and front calls that cannot record' if mixed else 'the range kernel, the front kernel, r2f_render'})")
     print(f"#   took the 12-byte element: {tot[1]}   allowed by their own samples (exact per-pair range): {tot[2]}   "
           f"-> the 64 x 256 tiles cost {tot[2] - tot[1]} pairs ({100.0 * (tot[2] - tot[1]) / max(tot[2], 1):.1f} % of the allowed ones)")
     print(f"#   pairs that took the element AGAINST their own samples: {len(bad)}")
