@@ -131,7 +131,8 @@ R2F_API int r2f_set_kernel(r2f_ctx* ctx, int which, const float* host_khwc, int 
 /* --- whole-frame render: CpuProcessor.process hot loop cpu_processor.py:363-407,
  *     GpuProcessor._execute_gpu_pipeline gpu_processor.py:1756-1877 ---
  * in: device image (in_layout), H x W.  out_f32_hwc / out_u8_hwc: device (H, W, 3), either may be NULL.
- * workspace: device scratch of at least r2f_workspace_bytes(...) bytes (caller-owned): the plane sets between the stages.
+ * workspace: device scratch of at least r2f_workspace_bytes(...) bytes (caller-owned, 16-byte aligned): the plane sets between the
+ * stages; nothing past workspace_bytes is touched.
  * Stencils of >= 400 taps run as fp64 overlap-save FFTs (like cv.filter2D's own DFT branch above 11 x 11 taps, which the
  * reference's CPU path takes for both of them); their pass scratch (1 MiB per window pair in flight, 192 by default) and
  * the kernels' spectra (1 MiB per stencil channel) belong to the context, allocated on first use.
@@ -203,6 +204,8 @@ R2F_API int r2f_write_frame_params(r2f_ctx* ctx, const r2f_params* p, void* stre
  * destination plane that shares bytes with a source plane is refused with R2F_EINVAL (tiles and FFT batches read halo rows
  * that others would already have overwritten).  r2f_stage_grain is pointwise on the density and may run exactly in place
  * (same base, stride and first row); any other overlap is refused.
+ * A call writes rows [y0, y1) of its destination -- every sample of them -- and nothing else: not the destination's other rows, not
+ * the pad between its planes, not a byte in front of or behind it, and nothing of its source (tests/test_gpu_write_bounds.py).
  * Every entry point binds the context's device for the duration of the call and restores the caller's current device on
  * return, so several contexts (one per GPU) can be driven from one thread. --- */
 
@@ -322,7 +325,7 @@ R2F_API int r2f_decode_u16(r2f_ctx* ctx, const uint16_t* src_hwc, int H, int W, 
 /* The GPU processor's preview blit, shaders/copy_to_int.wgsl as bound by gpu_processor.py:1416-1539: the display-referred float
  * frame (H, W, 3) sampled bilinearly (clamp to edge) into an RGBA8 destination (dst_h, dst_w, 4): inside the scaled image the
  * sample (alpha 255), elsewhere inside the canvas bounds the canvas colour, transparent outside.  The transform is the shader's
- * uniform block (raw2film_amd.geometry.blit_transform computes it like _bind_copy_to_dst). */
+ * uniform block (raw2film_amd.geometry.blit_transform computes it like _bind_copy_to_dst).  dst_rgba: 4-byte aligned. */
 typedef struct r2f_blit {
     float scale_x, scale_y;    /* 1 / rendered size of the image inside the destination, in destination pixels */
     float offset_x, offset_y;  /* its top-left corner */
@@ -335,7 +338,8 @@ R2F_API int r2f_blit_rgba8(r2f_ctx* ctx, const float* src_f32_hwc, int H, int W,
 /* shaders/histogram.wgsl pass2_process + pass3_render and shaders/scale_texture.wgsl (gpu_processor.py:1245-1285, 1883-1889) on
  * the counts of r2f_histogram_u8: log1p of the normalised counts, 3-bin smoothing, bar heights, the (height, 256, 4) RGBA bar
  * image coloured by mix_table_rgba (HOST, 8 x 4 bytes, index is_r * 4 + is_g * 2 + is_b) and, when target_rgba is given, its
- * nearest-neighbour copy into a (target_h, target_w, 4) widget texture.  counts / image / target are device pointers. */
+ * nearest-neighbour copy into a (target_h, target_w, 4) widget texture.  counts / image / target are device pointers; image and
+ * target 4-byte aligned. */
 R2F_API int r2f_histogram_render(r2f_ctx* ctx, const uint32_t* counts, const uint8_t* mix_table_rgba, int height, uint8_t* image_rgba,
                          uint8_t* target_rgba, int target_h, int target_w, void* stream);
 
