@@ -388,7 +388,7 @@ R2F_API uint64_t r2f_generation(const r2f_ctx* ctx);
  *                                 allows it (above); stencil_fft_scratch96 (mask per stencil) forces it for all
  *   stencil_fft_mixed_sign     1: channels with taps of both signs take the float64 FFT form whatever their size
  * (older ones: stencil_fft, stencil_fft_window[_rows|_max], stencil_fft_batch, stencil_fft_streams, stencil_fft_scratch32,
- *  stencil_fft_min_taps, stencil_fft_epilogue_lds, render_graph, front_fast, ... -- see r2f_set_option in r2f_api.hip) */
+ *  stencil_fft_min_taps, stencil_fft_epilogue_lds, render_graph, front_fast, ... -- the table in r2f_plan.cpp, defaults in r2f_plan.h) */
 R2F_API int r2f_set_option(r2f_ctx* ctx, const char* name, int value);
 
 /* --- plan-only entry points: the host-side planners of this library (raw2film_amd/csrc/r2f_plan.cpp), callable without a GPU and

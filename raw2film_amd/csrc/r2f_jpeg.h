@@ -1,4 +1,4 @@
-// r2f_jpeg.h -- the launcher of the JPEG encoder (r2f_jpeg.hip), called by r2f_jpeg_encode in r2f_api.hip.
+// r2f_jpeg.h -- the launcher of the JPEG encoder (r2f_jpeg.hip), called by r2f_jpeg_encode in r2f_jpeg_api.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -492,6 +492,88 @@ size_t workspace_floats(unsigned flags, int burn_cell, int H, int W) {
     return (size_t)sets * plane_set_floats(H, W) + burn_floats;
 }
 
+bool centrally_symmetric(const Taps& t, const int* chans, int nch, const int box[4]) {
+    const int bh = box[1] - box[0] + 1, bw = box[3] - box[2] + 1;
+    if (!(bh & 1) || !(bw & 1) || t.kh / 2 - box[0] != bh / 2 || t.kw / 2 - box[2] != bw / 2) return false;
+    for (int i = 0; i < nch; ++i)
+        for (int y = 0; y < bh; ++y)
+            for (int x = 0; x < bw; ++x) {
+                const float u = t.at(box[0] + y, box[2] + x, chans[i]), v = t.at(box[1] - y, box[3] - x, chans[i]);
+                if (memcmp(&u, &v, sizeof u)) return false;
+            }
+    return true;
+}
+
+std::vector<float> fft_kernel_image(const Taps& t, int c, const int box[4], int ny, int nx, bool wrap) {
+    const int bh = box[1] - box[0] + 1, bw = box[3] - box[2] + 1;
+    const int ay = t.kh / 2 - box[0], ax = t.kw / 2 - box[2];  // anchor (kh/2, kw/2): cv.filter2D's default
+    std::vector<float> img((size_t)ny * nx, 0.f);
+    for (int y = 0; y < bh; ++y)
+        for (int x = 0; x < bw; ++x) {
+            const int py = wrap ? (y - ay + ny) % ny : y, px = wrap ? (x - ax + nx) % nx : x;
+            img[(size_t)py * nx + px] = t.at(box[0] + y, box[2] + x, c);
+        }
+    return img;
+}
+
+// ------------------------------------------------------------------------------------------------ options
+namespace {
+using K = OptionKind;
+constexpr int kMax = 0x7fffffff;
+const OptionRow kOptions[] = {
+    {"stencil_variant", &Options::variant, K::Range, -1, kNumStencilVariants - 1, {}, "stencil_variant out of range"},
+    {"render_graph", &Options::render_graph, K::Switch, 0, 0, {}, nullptr},
+    {"stencil_lds_kb", &Options::lds_kb, K::Range, 8, 160, {}, "stencil_lds_kb must be in [8, 160]"},
+    {"stencil_sym", &Options::sym, K::Switch, 0, 0, {}, nullptr},
+    {"stencil_ablate", &Options::ablate, K::Raw, 0, 0, {}, nullptr},
+    {"kernel_timing", &Options::timing, K::Mask, 7, 0, {}, nullptr},  // bit per pass: 1 rows forward, 2 columns, 4 rows inverse
+    {"stencil_fft", &Options::fft, K::Switch, 0, 0, {}, nullptr},
+    {"stencil_fft_window", &Options::fft_window, K::OneOf, 4, 0, {0, 256, 512, 1024}, "stencil_fft_window must be 0, 256, 512 or 1024"},
+    {"stencil_fft_window_max", &Options::fft_window_max, K::OneOf, 3, 0, {256, 512, 1024}, "stencil_fft_window_max must be 256, 512 or 1024"},
+    {"stencil_fft_even_batches", &Options::fft_even, K::Switch, 0, 0, {}, nullptr},
+    {"stencil_fixed", &Options::stencil_fixed, K::Switch, 0, 0, {}, nullptr},
+    {"grain_fixed", &Options::grain_fixed, K::Switch, 0, 0, {}, nullptr},
+    {"front_fast", &Options::front_fast, K::Switch, 0, 0, {}, nullptr},
+    {"grain_separable", &Options::grain_sep, K::Switch, 0, 0, {}, nullptr},
+    {"front_blocks_per_cu", &Options::front_blocks, K::Range, 1, 64, {}, "front_blocks_per_cu must be in [1, 64]"},
+    {"stencil_fft_window_rows", &Options::fft_window_rows, K::OneOf, 3, 0, {0, 256, 512}, "stencil_fft_window_rows must be 0, 256 or 512"},
+    {"stencil_fft_min_taps", &Options::fft_min_taps, K::Raw, 0, 0, {}, nullptr},
+    {"stencil_fft_streams", &Options::fft_streams, K::Range, 1, 4, {}, "stencil_fft_streams must be in [1, 4]"},
+    {"stencil_fft_cols_walk", &Options::fft_cols_walk, K::Switch, 0, 0, {}, nullptr},
+    {"stencil_fft_mixed_sign", &Options::fft_mixed_sign, K::Switch, 0, 0, {}, nullptr},
+    {"stencil_fft_real_spectrum", &Options::fft_real, K::Switch, 0, 0, {}, nullptr},
+    {"stencil_fft_epilogue_lds", &Options::fft_epi_lds, K::Switch, 0, 0, {}, nullptr},
+    {"stencil_fft_scratch96_auto", &Options::fft_s96_auto, K::Switch, 0, 0, {}, nullptr},
+    {"stencil_fft_scratch96", &Options::fft_s96, K::Range, 0, 7, {}, "stencil_fft_scratch96 is a mask over the three stencils (0..7)"},
+    {"stencil_fft_scratch32", &Options::fft_s32, K::Range, 0, 7, {}, "stencil_fft_scratch32 is a mask over the three stencils (0..7)"},
+    {"stencil_fft_batch", &Options::fft_batch, K::Range, 1, kMax, {}, "stencil_fft_batch must be >= 1"},
+    {"xcd_band", &Options::xcd_band, K::Range, 0, kMax, {}, "xcd_band must be >= 0"},  // (r2f_set_option also forgets the tile orders)
+    {"xcd_remap", &Options::xcd_remap, K::Range, 0, 2, {}, "xcd_remap must be 0, 1 or 2"},
+};
+}  // namespace
+
+const OptionRow* find_option(const char* name) {
+    for (const OptionRow& row : kOptions)
+        if (!strcmp(name, row.name)) return &row;
+    return nullptr;
+}
+
+bool store_option(Options* o, const OptionRow& row, int value) {
+    switch (row.kind) {
+        case K::Switch: value = value ? 1 : 0; break;
+        case K::Mask: value &= row.a; break;
+        case K::Raw: break;
+        case K::Range:
+            if (value < row.a || value > row.b) return false;
+            break;
+        case K::OneOf:
+            if (std::find(row.v, row.v + row.a, value) == row.v + row.a) return false;
+            break;
+    }
+    o->*row.field = value;
+    return true;
+}
+
 }  // namespace plan
 }  // namespace r2f
 

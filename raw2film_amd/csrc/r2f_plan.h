@@ -1,5 +1,5 @@
-// r2f_plan.h -- the host-side planners of libr2f_hip.so, free of HIP: everything r2f_api.hip decides on the CPU before it uploads
-// a table or launches a kernel (tap boxes and their device entry lists, FFT window shapes and batch sizes, tile orders,
+// r2f_plan.h -- the host-side planners of libr2f_hip.so, free of HIP: everything the host units (r2f_api.hip, r2f_stencil.hip)
+// decide on the CPU before they upload a table or launch a kernel (the option table, tap boxes and their device entry lists, FFT window shapes and batch sizes, tile orders,
 // LANCZOS4 / Gaussian tables, curve cells, workspace sizes).  Plain C++ so that the same translation unit also builds with
 // `g++ -fsanitize=address,undefined` into the fuzz harness of tests/test_plan_sanitizers.py (GPU-side sanitizers are not available on
 // this pool; this is the part of the library that can run under one).  Nothing here touches the device.
@@ -77,6 +77,77 @@ struct FftBatches {
 };
 // Tiling of output rows [y0, y1) x W columns into window pairs and their batches; elem_bytes: 16 (complex128), 8 or 12.
 FftBatches fft_batches(const FftOptions& o, int ny, int nx, int bh, int bw, int W, int y0, int y1, int nch, int elem_bytes);
+
+// Is every channel of `chans` centrally symmetric bit for bit (k[i][j] == k[bh-1-i][bw-1-j]) inside `box`, an odd x odd box whose
+// centre is the anchor (kh / 2, kw / 2)?  Such a box, laid out with its anchor on the window origin, has a real spectrum.
+bool centrally_symmetric(const Taps& t, const int* chans, int nch, const int box[4]);
+// The zero-padded ny x nx kernel image of channel c's `box`: in the window's top left corner (outputs from row / column 0 on), or,
+// wrap = true (a real spectrum), wrapped around the window with the anchor on the origin.
+std::vector<float> fft_kernel_image(const Taps& t, int c, const int box[4], int ny, int nx, bool wrap);
+
+// ------------------------------------------------------------------------------------------------ options
+// The integer options of r2f_set_option with their defaults.  (Bits `which` of the masks: R2F_KERNEL_HALATION / _MTF / _GRAIN.)
+struct Options {
+    int fft_window = 0;      // window columns: 0 = the cheapest of 256 / 512 / 1024 per stencil and frame, or one of them forced
+    int fft_window_max = 512;  // widest window the automatic choice may take (1024 columns: 9 % fewer window elements for the
+                               // 87-tap disc, but the passes run 10-25 % slower per element)
+    int fft_window_rows = 0;  // window rows, likewise
+    // optional per-launch timing of the FFT passes with events on the launch stream (bench.py's roofline): class 0 / 1 / 2 =
+    // pass 1 / 2 / 3; algorithmic bytes are summed alongside
+    int timing = 0;
+    int fft = 1;             // 1: stencil channels with a large enough kernel take the FFT form
+    int fft_min_taps = 400;  // ... "large enough": cropped box of at least this many taps (and at most 200 x 200);
+                             // measured crossover with the direct form: 17 x 17 ties, 23 x 23 is 1.5x faster by FFT
+    int fft_streams = 2;     // internal streams taking alternate batches (r2f_ctx::Fft)
+    int fft_even = 1;        // batches sized so that every internal stream gets the same number of launch triples
+    int fft_batch = 192;     // window pairs per launch triple: 192 MB of scratch stay inside the 256 MB Infinity Cache
+    // bit `which`: that stencil's FFT scratch images hold complex64 instead of complex128 elements (r2f_fft.hip, sld / sst).
+    // Default: the MTF only -- it acts on density, whose values are bounded, so two fp32 roundings of the spectrum cost ~1e-7
+    // absolute; the halation acts on linear exposure, where the same roundings are relative to the brightest pixel of the window.
+    int fft_s32 = 1 << 1;
+    int fft_s96 = 0;  // bit `which`: 12-byte scratch elements (doubles rounded to 48 bits, 2^-37) whatever the frame holds -- A/B
+    // 1: the halation's FFT passes choose between complex128 and the 12-byte element ON THE DEVICE, per frame and per WINDOW PAIR,
+    // from the range of the exposure samples the pair's windows hold (the record's tiles, filled by the front kernel): the 12-byte
+    // element costs a shadow at most 1.46e-11 x (max |x| / shadow) of itself (two roundings at 2^-37; kDynCoefficient adds a
+    // factor 1.5) -- which the density curve turns into 0.434 x slope x that; the bound keeps it under three fp32 ulps of a density
+    // in [1, 2), what the MTF's complex64 scratch is allowed, and window pairs with a wider range keep complex128 (the stand-in Portra
+    // curve: max / shadow <= 6.2e4; the headline's noise frame spans 1.4e5 as a whole, ~2e4 per window: 99 % of its pairs qualify).
+    int fft_s96_auto = 1;
+    int fft_epi_lds = 1;  // pass 3's epilogue gathers its curve cells from LDS (0: from global memory; A/B)
+    // 1: a centrally symmetric tap box (k[i][j] == k[bh-1-i][bw-1-j] bit for bit, anchor at its centre -- every halation disc and
+    // |ifft2| MTF kernel the reference builds, effects.py:200-217, :123-143) is laid out with its anchor on the window origin, so its
+    // spectrum is real: pass 2 reads 8 instead of 16 bytes of it per element (FftConvArgs::kreal).  0: complex spectra for all (A/B).
+    int fft_real = 1;
+    int fft_mixed_sign = 1;  // channels with taps of both signs take the float64 FFT form on complex128 scratch whatever their size
+    int fft_cols_walk = 1;  // pass 2 of real-spectrum launches as a resident grid walking the launch's pairs (0: one workgroup per pair; A/B)
+    int xcd_band = 0;  // tile columns per band of the xcd_remap = 2 order; 0 = auto
+    int variant = -1;  // -1 auto
+    int xcd_remap = 2;  // 0 = launch order, 1 = one contiguous row-major run of tiles per XCD, 2 = that run walked in column bands
+    int ablate = 0;
+    int sym = 1;      // use the mirror-symmetric entry form when a channel's taps allow it
+    int grain_fixed = 1;  // 0: always the generic entry list (A/B)
+    int grain_sep = 1;    // 0: never take the separable form (A/B)
+    int stencil_fixed = 1;
+    int front_fast = 1;    // the fused LUT-only pass may take the specialised kernel (r2f_front.hip); 0 = always the generic one (A/B)
+    int front_blocks = 6;  // front kernel with the curve in LDS: workgroups per CU in its grid (3 are resident at 48 KB each)
+    int lds_kb = 80;  // LDS budget per stencil workgroup; 80 KB -> two workgroups per CU
+    int render_graph = 1;
+};
+// One row per option name: how a value is checked and stored, and what r2f_last_error says when it is refused.
+//   Switch: stored as value ? 1 : 0.   Range: a <= value <= b.   OneOf: value among v[0 .. n).   Raw: stored unchecked.
+//   Mask: stored as value & a, nothing refused.
+enum class OptionKind { Switch, Range, OneOf, Raw, Mask };
+struct OptionRow {
+    const char* name;
+    int Options::*field;
+    OptionKind kind;
+    int a, b;  // Range: bounds; Mask: a; OneOf: a = n
+    int v[4];
+    const char* error;
+};
+constexpr int kNumStencilVariants = 3;  // = r2f_launch.h's (restated for the range of stencil_variant)
+const OptionRow* find_option(const char* name);  // nullptr: unknown
+bool store_option(Options* o, const OptionRow& row, int value);  // false: refused (row.error), *o untouched
 
 // ------------------------------------------------------------------------------------------------ tables
 // Tile order of a gx x gy grid of stencil workgroups: entry i = tile index of linear workgroup id i (XCD-contiguous runs walked

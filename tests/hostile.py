@@ -121,7 +121,7 @@ def roughen(rng, p, n2: int, m1: int, n3: int, rough2: float = 0.2, rough3: floa
 
 
 # ---------------------------------------------------------------------------------------------- 12-byte scratch element
-# Frames for the search behind the guard of the halation's 12-byte FFT scratch element (r2f_api.hip dyn_rule).
+# Frames for the search behind the guard of the halation's 12-byte FFT scratch element (r2f_stencil.hip dyn_rule).
 # The element rounds every scratch value to 2^-37 of itself, so what it costs a pixel scales with the energy of the WINDOW the
 # pixel shares, while the guard sees max |x| and min x of the frame: the worst frames put as much bright, spectrally rich signal as
 # possible into a window and a shadow further than the stencil's reach (43 px at the 100 MP pitch) from all of it.

@@ -224,10 +224,75 @@ static void fuzz_tables() {
     }
 }
 
+// The two host decisions of the FFT form's kernel spectrum (run_stencil_fft): a real spectrum needs every channel centrally
+// symmetric bit for bit about an anchor at the centre of an odd x odd box, and the wrapped kernel image is the corner one rolled
+// by (-ay, -ax).  Fixed cases, every run.
+static void check_fft_kernel_forms() {
+    const int chans[2] = {0, 1};
+    auto disc = [](int kh, int kw, int cy, int cx, int r) {  // (kh, kw, 3): channels 0 and 1 a disc around (cy, cx), channel 2 its centre tap
+        std::vector<float> k((size_t)kh * kw * 3, 0.f);
+        for (int i = 0; i < kh; ++i)
+            for (int j = 0; j < kw; ++j) {
+                const int d2 = (i - cy) * (i - cy) + (j - cx) * (j - cx);
+                if (d2 <= r * r) k[((size_t)i * kw + j) * 3] = 1.f / (1.f + d2), k[((size_t)i * kw + j) * 3 + 1] = 0.3f / (2.f + d2);
+            }
+        k[((size_t)cy * kw + cx) * 3 + 2] = 1.f;
+        return k;
+    };
+    auto rolled = [&](const Taps& t, int c, const int box[4]) {  // wrapped image == corner image rolled by (-ay, -ax)
+        const int ny = 16, nx = 32, ay = t.kh / 2 - box[0], ax = t.kw / 2 - box[2];
+        const std::vector<float> u = fft_kernel_image(t, c, box, ny, nx, false), w = fft_kernel_image(t, c, box, ny, nx, true);
+        CHECK(u.size() == (size_t)ny * nx && w.size() == u.size(), "image size");
+        for (int y = 0; y < ny; ++y)
+            for (int x = 0; x < nx; ++x)
+                CHECK(!memcmp(&w[(size_t)((y - ay + ny) % ny) * nx + (x - ax + nx) % nx], &u[(size_t)y * nx + x], sizeof(float)), "roll at %d %d", y, x);
+        for (int y = 0; y < ny; ++y)  // the corner image: the box, then zeros
+            for (int x = 0; x < nx; ++x) {
+                const bool in = y <= box[1] - box[0] && x <= box[3] - box[2];
+                const float want = in ? t.at(box[0] + y, box[2] + x, c) : 0.f;
+                CHECK(!memcmp(&u[(size_t)y * nx + x], &want, sizeof want), "corner image at %d %d", y, x);
+            }
+    };
+    int box[4];
+    {  // a symmetric disc around the anchor: real
+        std::vector<float> k = disc(13, 13, 6, 6, 4);
+        Taps t{k.data(), 13, 13, 3};
+        tap_box(t, 0, box);
+        CHECK(box[0] == 2 && box[1] == 10 && box[2] == 2 && box[3] == 10, "disc box");
+        CHECK(centrally_symmetric(t, chans, 2, box), "symmetric disc");
+        rolled(t, 0, box), rolled(t, 1, box);
+        // ... the same disc with the last mantissa bit of one tap of channel 1 flipped: not real, for the group
+        uint32_t bits;
+        float& tap = k[((size_t)4 * 13 + 7) * 3 + 1];
+        memcpy(&bits, &tap, 4), bits ^= 1u, memcpy(&tap, &bits, 4);
+        CHECK(!centrally_symmetric(t, chans, 2, box), "one mantissa bit");
+        CHECK(centrally_symmetric(t, chans, 1, box), "channel 0 alone is untouched");
+    }
+    {  // an even-sized box
+        std::vector<float> k((size_t)12 * 12, 0.f);
+        for (int i = 4; i < 8; ++i)
+            for (int j = 4; j < 8; ++j) k[(size_t)i * 12 + j] = 0.0625f;
+        Taps t{k.data(), 12, 12, 1};
+        tap_box(t, 0, box);
+        CHECK(box[1] - box[0] + 1 == 4 && box[3] - box[2] + 1 == 4, "even box");
+        CHECK(!centrally_symmetric(t, chans, 1, box), "even-sized box");
+        rolled(t, 0, box);
+    }
+    {  // a disc that is symmetric in itself, one row below the anchor
+        std::vector<float> k = disc(13, 13, 7, 6, 4);
+        Taps t{k.data(), 13, 13, 3};
+        tap_box(t, 0, box);
+        CHECK(box[0] == 3 && box[1] == 11 && 13 / 2 - box[0] != (box[1] - box[0] + 1) / 2, "off-centre box");
+        CHECK(!centrally_symmetric(t, chans, 2, box), "off-centre anchor");
+        rolled(t, 0, box);
+    }
+}
+
 int main(int argc, char** argv) {
     const uint64_t seed = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1;
     const int cases = argc > 2 ? atoi(argv[2]) : 2000;
     g_state = seed * 0x9E3779B97F4A7C15ULL + 1;
+    check_fft_kernel_forms();
     for (int i = 0; i < cases; ++i) {
         fuzz_fft();
         if (i % 4 == 0) fuzz_stencil();

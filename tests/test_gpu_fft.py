@@ -435,7 +435,7 @@ def test_the_halation_scratch_element_is_chosen_per_frame_on_the_device():
 
 
 def test_the_guard_of_the_twelve_byte_element_stands_on_a_search(ctx):
-    """VERDICT r5, next 4 / ADVICE r5: the constant in r2f_render's rule (r2f_api.hip dyn_rule: what the 12-byte element costs a
+    """VERDICT r5, next 4 / ADVICE r5: the constant in r2f_render's rule (r2f_stencil.hip dyn_rule: what the 12-byte element costs a
     shadow, as a multiple of max / shadow) used to be the maximum of 16 hand-made probes with no margin.  Here a fixed budget of
     random frames -- dark holes in a bright field, blocks, stripes, checkers, gradients, half-bright frames, isolated speculars x
     five bright-region statistics (tests/hostile.py scratch96_frame; tools/scratch96_search.py runs the same search with a larger

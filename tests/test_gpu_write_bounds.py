@@ -54,7 +54,7 @@ class Geo(namedtuple("Geo", "W rows misalign pad")):
     rows_alloc = property(lambda s: s.rows + ABOVE + BELOW)
     a = property(lambda s: ABOVE)                          # the shard's rows in the destination's own numbering: [a, b)
     b = property(lambda s: ABOVE + s.rows)
-    planes_vec = property(lambda s: s.W % 4 == 0 and s.misalign == 0 and s.pad % 4 == 0)  # planes_vec_ok of r2f_api.hip
+    planes_vec = property(lambda s: s.W % 4 == 0 and s.misalign == 0 and s.pad % 4 == 0)  # planes_vec_ok of r2f_ctx.h
     hwc_vec = property(lambda s: s.W % 4 == 0 and s.misalign == 0)
 
     def __str__(self):

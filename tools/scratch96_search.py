@@ -3,7 +3,7 @@ families in tests/hostile.py (dark holes in a bright field, blocks, stripes, che
 speculars) x bright-region statistics x max / min ratios of 2e5 .. 3e6 (the coefficient does not depend on the ratio -- the error is
 linear in hi -- and below 1e5 the fp32 rounding of the two results, 1.2e-7, hides it), 256 x 512 windows forced like cfg 4's.  Per frame:
     coefficient = max |E_12byte - E_complex128| / max(|E_complex128|, lo) / (hi / lo)
-over the FFT channels of the halation stencil -- the constant the guard of r2f_render is built on (r2f_api.hip dyn_rule).
+over the FFT channels of the halation stencil -- the constant the guard of r2f_render is built on (r2f_stencil.hip dyn_rule).
     python tools/scratch96_search.py [--budget 400] [--seed 1] [--shape 600x1100]
 Prints the worst frames and the per-family maxima; tests/test_gpu_fft.py runs the same function on a fixed, smaller budget."""
 import argparse

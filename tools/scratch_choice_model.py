@@ -1,6 +1,6 @@
 """The per-window-pair choice of the halation's FFT scratch element against a HOST MODEL of what each pair's windows hold.
 
-The guard (r2f_api.hip dyn_rule, r2f_fft.hip fft_decide_kernel): a pair may take the 12-byte element when
+The guard (r2f_stencil.hip dyn_rule, r2f_fft.hip fft_decide_kernel): a pair may take the 12-byte element when
     max |x| <= bound * max(min x, floor)
 over the exposure samples whose rounding can reach an output the pair keeps.  The device decides from a grid of 64 x 256-pixel tiles
 (a superset of those samples); this tool reads the flags back (r2f_frame_scratch_flags) and checks the one thing that must hold whatever
