@@ -322,6 +322,30 @@ R2F_API int r2f_resize_area_u8(r2f_ctx* ctx, const uint8_t* src_hwc, int H, int 
 R2F_API int r2f_decode_u16(r2f_ctx* ctx, const uint16_t* src_hwc, int H, int W, int channels, float divisor, float factor, float* dst_f32_hwc3,
                    void* stream);
 
+/* The auto exposure of the uint16 hand-off measured on the device: calc_exposure (color_processing.py:71-99) on the uploaded
+ * frame, so that no host pass over the frame precedes the render and the device never waits for the host to learn the factor.
+ * With u over frame[::2, ::2, 1] of the WHOLE decoded frame: g = (float)u / 65535 (one correctly rounded fp32 division, widened to
+ * double), m = mean(pow(g, 1 / root)), stops = log2(ref_exposure / pow(m, root)), factor = the float32 of 2 ** stops -- upstream's
+ * formula in fp64.  Upstream evaluates it in float32 (raw2film_amd.decode.auto_exposure does so bit for bit) and lands 2e-8 ..
+ * 5e-5 stops away, so the two factors usually differ in the last bits: this is an opt-in mode, not a replacement.
+ *   r2f_exposure_rows    the fp64 sums of the sampled rows (global row index even) of [y0, y1) into a per-row array the context
+ *                        owns (grown when a taller frame arrives; r2f_generation stays).  src_rows: uint16 rows [src_gy0, src_gy0 +
+ *                        src_nrows) of the (H, W, channels) frame on the device, channels 3 or 4.  One fixed-shape reduction per row:
+ *                        a row's sum depends only on its bytes, W, channels and root, so the result is the same bits whether the
+ *                        frame comes in one call, in bands of any size and order, or twice.  No floating-point atomics.
+ *   r2f_exposure_finish  one workgroup adds the ceil(H / 2) row sums in a fixed order and writes stops and factor into the
+ *                        context's device-side record (every sampled row of the frame must have been summed on `stream` before).
+ *   r2f_decode_u16_auto  r2f_decode_u16 with the factor read from the record -- the same floats for the same factor -- and a
+ *                        pitched source: W pixels of each of H rows that lie src_pitch pixels apart (a crop of the uploaded
+ *                        frame is a pointer offset plus the pitch).  dst: float32 (H, W, 3), contiguous.
+ *   r2f_exposure_result  waits for the last r2f_exposure_finish (not for what was queued behind it) and returns its record. */
+R2F_API int r2f_exposure_rows(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int H, int W, int channels, int y0, int y1,
+                      double root, void* stream);
+R2F_API int r2f_exposure_finish(r2f_ctx* ctx, int H, int W, double root, double ref_exposure, void* stream);
+R2F_API int r2f_decode_u16_auto(r2f_ctx* ctx, const uint16_t* src_hwc, int H, int W, int channels, int64_t src_pitch, float divisor,
+                        float* dst_f32_hwc3, void* stream);
+R2F_API int r2f_exposure_result(r2f_ctx* ctx, double* stops, float* factor);
+
 /* The GPU processor's preview blit, shaders/copy_to_int.wgsl as bound by gpu_processor.py:1416-1539: the display-referred float
  * frame (H, W, 3) sampled bilinearly (clamp to edge) into an RGBA8 destination (dst_h, dst_w, 4): inside the scaled image the
  * sample (alpha 255), elsewhere inside the canvas bounds the canvas colour, transparent outside.  The transform is the shader's

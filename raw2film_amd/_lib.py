@@ -157,6 +157,16 @@ _SIGNATURES = {
     "r2f_lanczos4_table_f32": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "r2f_resize_area_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "r2f_decode_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "r2f_exposure_rows": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p],
+    ),
+    "r2f_exposure_finish": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
+    "r2f_decode_u16_auto": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p],
+    ),
+    "r2f_exposure_result": (C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_float)]),
     "r2f_blit_rgba8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, _P(Blit), C.c_void_p]),
     "r2f_plan_fft": (C.c_int, [C.c_int] * 11 + [_P(FftPlan)]),
     "r2f_plan_stencil": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

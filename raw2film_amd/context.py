@@ -521,6 +521,63 @@ class HipContext:
                                              out.data_ptr(), self._stream()))
         return out
 
+    def _check_u16(self, t, what):
+        torch = self._torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in (torch.uint16, torch.int16) and t.is_contiguous()
+                and t.dim() == 3 and t.shape[2] in (3, 4) and t.shape[0] > 0 and t.shape[1] > 0):
+            raise ValueError(f"{what} needs a contiguous, non-empty uint16 (rows, W, 3 or 4) CUDA tensor")
+        self._same_device(t, what)
+
+    def exposure_rows(self, rows_u16, root: float, *, H=None, gy0: int = 0, y0=None, y1=None):
+        """The auto exposure's row statistic (r2f_exposure_rows; calc_exposure, color_processing.py:71-99): the fp64 sums of
+        pow(green / 65535, 1 / root) over the sampled rows (global index even) of [y0, y1) into the context's per-row array.
+        rows_u16: the uint16 rows [gy0, gy0 + rows) of a frame of H rows (default: the whole frame).  A row's sum depends on
+        nothing but its bytes, W, channels and root, so bands of any size, in any order, give the frame's statistic bit for bit."""
+        self._check_u16(rows_u16, "exposure_rows")
+        rows, W, ch = (int(v) for v in rows_u16.shape)
+        gy0 = int(gy0)
+        H = gy0 + rows if H is None else int(H)
+        y0 = gy0 if y0 is None else int(y0)
+        y1 = gy0 + rows if y1 is None else int(y1)
+        if not (0 <= gy0 <= y0 <= y1 <= gy0 + rows <= H):
+            raise ValueError(f"exposure_rows: rows [{y0}, {y1}) of a buffer holding [{gy0}, {gy0 + rows}) of a frame of {H} rows")
+        self._check(self._lib.r2f_exposure_rows(self._h, rows_u16.data_ptr(), gy0, rows, H, W, ch, y0, y1, float(root), self._stream()))
+
+    def exposure_finish(self, H: int, W: int, root: float, ref_exposure: float = 0.18):
+        """r2f_exposure_finish: the row sums of an H x W frame (every sampled row summed on this stream before) -> stops and the
+        float32 factor in the context's device-side record, which decode_u16_auto reads.  Nothing comes back to the host here."""
+        self._check(self._lib.r2f_exposure_finish(self._h, int(H), int(W), float(root), float(ref_exposure), self._stream()))
+
+    def exposure_result(self):
+        """(stops, float32 factor) of the last exposure_finish (r2f_exposure_result): waits for that kernel, not for what was
+        queued behind it."""
+        stops, factor = C.c_double(), C.c_float()
+        self._check(self._lib.r2f_exposure_result(self._h, C.byref(stops), C.byref(factor)))
+        return float(stops.value), np.float32(factor.value)
+
+    def decode_u16_auto(self, frame_u16, window=None, divisor: float = 65535.0, out=None):
+        """decode_u16 with the factor read from the context's exposure record (r2f_decode_u16_auto) -- the same floats as
+        decode_u16 gives for that factor.  window = (row0, col0, rows, cols) of `frame_u16` to decode (default: all of it): a
+        crop costs a pointer offset and a pitch, not a copy.  -> float32 (rows, cols, 3), into `out` when given."""
+        torch = self._torch
+        self._check_u16(frame_u16, "decode_u16_auto")
+        rows, W, ch = (int(v) for v in frame_u16.shape)
+        r0, c0, nr, nc = (0, 0, rows, W) if window is None else (int(v) for v in window)
+        if not (0 <= r0 and 0 <= c0 and nr > 0 and nc > 0 and r0 + nr <= rows and c0 + nc <= W):
+            raise ValueError(f"decode_u16_auto: window {(r0, c0, nr, nc)} is not inside the {rows} x {W} frame")
+        shape = (nr, nc, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                  and tuple(out.shape) == shape):
+            raise ValueError(f"decode_u16_auto: out must be a contiguous float32 CUDA tensor of shape {shape}")
+        else:
+            self._same_device(out, "out")
+        src = frame_u16.data_ptr() + 2 * ch * (r0 * W + c0)
+        self._check(self._lib.r2f_decode_u16_auto(self._h, src, nr, nc, ch, W, float(np.float32(divisor)), out.data_ptr(),
+                                                  self._stream()))
+        return out
+
     def blit_rgba8(self, image_f32, dst_rgba, transform: dict):
         """shaders/copy_to_int.wgsl: the float (H, W, 3) frame letterboxed into the uint8 (h, w, 4) destination tensor.
         `transform`: the dict of geometry.blit_transform (the shader's uniform block)."""

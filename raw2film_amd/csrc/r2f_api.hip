@@ -131,6 +131,12 @@ r2f_ctx::~r2f_ctx() {
         }
 }
 
+r2f_ctx::Exposure::~Exposure() {
+    if (stream) (void)hipStreamDestroy(stream);
+    if (done) (void)hipEventDestroy(done);
+    if (host) (void)hipHostFree(host);
+}
+
 // =============================================================================== C ABI
 extern "C" {
 
@@ -148,7 +154,8 @@ int r2f_create(int device, r2f_ctx** out) {
         return R2F_EHIP;
     r2f_ctx* ctx = new r2f_ctx();
     ctx->device = device;
-    if (ctx->frame_buf.reserve(ctx, sizeof(FrameParams), Grow::Quiet) != R2F_OK || hipMemset(ctx->frame_buf.p, 0, sizeof(FrameParams)) != hipSuccess) {
+    if (ctx->frame_buf.reserve(ctx, sizeof(FrameParams), Grow::Quiet) != R2F_OK || hipMemset(ctx->frame_buf.p, 0, sizeof(FrameParams)) != hipSuccess ||
+        ctx->exposure.rec.reserve(ctx, sizeof(ExposureRecord), Grow::Quiet) != R2F_OK) {
         delete ctx;  // (frees the block if it was the hipMemset that failed)
         return R2F_EHIP;
     }
@@ -802,6 +809,73 @@ int r2f_decode_u16(r2f_ctx* ctx, const uint16_t* src_hwc, int H, int W, int chan
     if (!src_hwc || !dst_f32_hwc3 || H <= 0 || W <= 0 || (channels != 3 && channels != 4) || !(divisor > 0.f))
         return fail(ctx, R2F_EINVAL, "decode_u16: a non-empty 3- or 4-channel frame and a positive divisor are required");
     R2F_HIP(ctx, launch_decode_u16(src_hwc, (long long)H * W, channels, divisor, factor, dst_f32_hwc3, static_cast<hipStream_t>(stream)));
+    return R2F_OK;
+}
+
+// ------------------------------------------------------------------------------- auto exposure on the device
+static bool exposure_root_ok(double root) { return root >= 1.0 && root <= 1.0e6; }  // (calc_exposure's is sqrt(...) + 1; NaN fails)
+
+int r2f_exposure_rows(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int H, int W, int channels, int y0, int y1,
+                      double root, void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    if (!src_rows || H <= 0 || W <= 0 || (channels != 3 && channels != 4) || !exposure_root_ok(root))
+        return fail(ctx, R2F_EINVAL, "exposure_rows: a non-empty 3- or 4-channel frame and a root in [1, 1e6] are required");
+    if (y0 < 0 || y1 > H || y0 > y1 || src_gy0 < 0 || src_nrows < 0 || y0 < src_gy0 || (long long)y1 > (long long)src_gy0 + src_nrows)
+        return fail(ctx, R2F_EINVAL, "exposure_rows: rows [%d, %d) not inside the frame's [0, %d) and the buffer's [%d, %lld)", y0, y1, H,
+                    src_gy0, (long long)src_gy0 + src_nrows);
+    const int n_rows = (H + 1) / 2;
+    if (n_rows > ctx->exposure.rows_cap) {  // a taller frame: the sums of a shorter one are not kept (its finish has been queued)
+        int rc = ctx->exposure.sums.reserve(ctx, (size_t)n_rows * sizeof(double), Grow::Sync);
+        if (rc) return rc;
+        ctx->exposure.rows_cap = n_rows;
+    }
+    R2F_HIP(ctx, launch_exposure_rows(src_rows, src_gy0, W, channels, y0, y1, root, static_cast<double*>(ctx->exposure.sums.p),
+                                      static_cast<hipStream_t>(stream)));
+    return R2F_OK;
+}
+
+int r2f_exposure_finish(r2f_ctx* ctx, int H, int W, double root, double ref_exposure, void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    if (H <= 0 || W <= 0 || !exposure_root_ok(root) || !(ref_exposure > 0.0))
+        return fail(ctx, R2F_EINVAL, "exposure_finish: a non-empty frame, a root in [1, 1e6] and a positive reference are required");
+    auto& ex = ctx->exposure;
+    if ((H + 1) / 2 > ex.rows_cap) return fail(ctx, R2F_EINVAL, "exposure_finish: no row sums of a frame of %d rows (r2f_exposure_rows)", H);
+    // (each under its own check: one that failed is tried again by the next call, and nothing is used before it exists)
+    if (!ex.stream) R2F_HIP(ctx, hipStreamCreateWithFlags(&ex.stream, hipStreamNonBlocking));
+    if (!ex.done) R2F_HIP(ctx, hipEventCreateWithFlags(&ex.done, hipEventDisableTiming));
+    if (!ex.host) R2F_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ex.host), sizeof(ExposureRecord), hipHostMallocDefault));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    R2F_HIP(ctx, launch_exposure_finish(static_cast<const double*>(ex.sums.p), H, W, root, ref_exposure,
+                                        static_cast<ExposureRecord*>(ex.rec.p), s));
+    R2F_HIP(ctx, hipEventRecord(ex.done, s));
+    R2F_HIP(ctx, hipStreamWaitEvent(ex.stream, ex.done, 0));
+    R2F_HIP(ctx, hipMemcpyAsync(ex.host, ex.rec.p, sizeof(ExposureRecord), hipMemcpyDeviceToHost, ex.stream));
+    ex.measured = true;
+    return R2F_OK;
+}
+
+int r2f_decode_u16_auto(r2f_ctx* ctx, const uint16_t* src_hwc, int H, int W, int channels, int64_t src_pitch, float divisor,
+                        float* dst_f32_hwc3, void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    if (!src_hwc || !dst_f32_hwc3 || H <= 0 || W <= 0 || (channels != 3 && channels != 4) || !(divisor > 0.f) || src_pitch < W)
+        return fail(ctx, R2F_EINVAL, "decode_u16_auto: a non-empty 3- or 4-channel frame, a pitch of at least W pixels and a positive "
+                                     "divisor are required");
+    if (!ctx->exposure.measured) return fail(ctx, R2F_EINVAL, "decode_u16_auto: no exposure has been measured (r2f_exposure_finish)");
+    R2F_HIP(ctx, launch_decode_u16_auto(src_hwc, H, W, channels, src_pitch, divisor, static_cast<const ExposureRecord*>(ctx->exposure.rec.p),
+                                        dst_f32_hwc3, static_cast<hipStream_t>(stream)));
+    return R2F_OK;
+}
+
+int r2f_exposure_result(r2f_ctx* ctx, double* stops, float* factor) {
+    if (!ctx || !stops || !factor) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    if (!ctx->exposure.measured) return fail(ctx, R2F_EINVAL, "exposure_result: no exposure has been measured (r2f_exposure_finish)");
+    R2F_HIP(ctx, hipStreamSynchronize(ctx->exposure.stream));  // (behind the last finish kernel, not behind what was queued after it)
+    *stops = ctx->exposure.host->stops;
+    *factor = ctx->exposure.host->factor;
     return R2F_OK;
 }
 

@@ -181,6 +181,19 @@ struct r2f_ctx {
     r2f::DeviceBuf range_tiles, dyn_flags;
     int tiles_tyn = 0, tiles_txn = 0;
     int dyn_flags_ppc = 0;  // pairs per channel of the last call that chose per pair (r2f_frame_scratch_choice)
+    // The auto exposure measured on the device (r2f_exposure_rows / _finish): the fp64 sums of the sampled rows, sized by capacity
+    // (ceil(H / 2) doubles of the tallest frame so far; no captured graph reads it: growing it leaves `generation` alone), and the
+    // record {stops, factor} r2f_decode_u16_auto reads.  A copy of the record follows every finish into pinned host memory on a
+    // stream of the context's own, so that r2f_exposure_result waits for the finish kernel and not for the render queued behind it.
+    struct Exposure {
+        r2f::DeviceBuf sums, rec;
+        int rows_cap = 0;  // sampled rows `sums` holds
+        r2f::ExposureRecord* host = nullptr;
+        hipStream_t stream = nullptr;
+        hipEvent_t done = nullptr;
+        bool measured = false;  // a finish has been queued: the record holds (or will hold) a frame's values
+        ~Exposure();
+    } exposure;
     r2f::RenderGraphCache graphs;  // (retired and reaped by r2f_destroy ahead of the buffers its graphs point into)
     struct Jpeg {
         // r2f_jpeg_encode's scratch (r2f_jpeg_plan.h Scratch): grows to the largest frame encoded so far and stays, so that frames of

@@ -295,6 +295,17 @@ hipError_t launch_burn_sums(const BurnSumsArgs& a, hipStream_t s);
 hipError_t launch_resize_area_u8(const uint8_t* src, int H, int W, uint8_t* dst, int out_h, int out_w, hipStream_t s);
 hipError_t launch_stream_copy(const void* src, void* dst, long long bytes, hipStream_t s);
 hipError_t launch_decode_u16(const uint16_t* src, long long n, int ch, float divisor, float factor, float* dst, hipStream_t s);
+// The auto-exposure record of the context (exposure_finish_kernel writes it, decode_u16_auto_kernel reads the factor): 16 bytes.
+struct ExposureRecord {
+    double stops;
+    float factor;
+    unsigned pad;
+};
+// the fp64 sums of the sampled (even) rows of [y0, y1) -> sums[y / 2]; src: row src_gy0 of the (H, W, ch) uint16 frame
+hipError_t launch_exposure_rows(const uint16_t* src, int src_gy0, int W, int ch, int y0, int y1, double root, double* sums, hipStream_t s);
+hipError_t launch_exposure_finish(const double* sums, int H, int W, double root, double ref, ExposureRecord* rec, hipStream_t s);
+hipError_t launch_decode_u16_auto(const uint16_t* src, int H, int W, int ch, long long src_pitch, float divisor, const ExposureRecord* rec,
+                                  float* dst, hipStream_t s);
 hipError_t launch_lanczos4_f32(const void* in, int in_layout, int H, int W, const DevPlanes& dst, int out_h, int out_w, const int* xofs,
                                const float* xcoef, const int* yofs, const float* ycoef, hipStream_t s);
 hipError_t launch_blit_rgba8(const float* src, int H, int W, uint8_t* dst, int dst_h, int dst_w, const ::r2f_blit& t, hipStream_t s);

@@ -313,6 +313,135 @@ __global__ __launch_bounds__(256) void decode_u16_kernel(const DecodeU16Args a) 
         for (int c = 0; c < 3; ++c) a.dst[p * 3 + c] = fminf((float)a.src[p * a.ch + c] / a.divisor * a.factor, 65504.0f);
 }
 
+// ---------------------------------------------------------------------------------------------------- auto exposure
+// calc_exposure (color_processing.py:71-99) measured on the uploaded uint16 frame: over u = frame[::2, ::2, 1],
+//   g = (float)u / 65535 (the fp32 division of raw_conversion.py:50), widened to double; m = mean(pow(g, 1 / root));
+//   stops = log2(ref / pow(m, root)); factor = (float)(2 ** stops)
+// -- upstream's formula in fp64 (upstream's own float32 evaluation is 2e-8 .. 5e-5 stops away from it).
+//
+// exposure_rows_kernel: one workgroup per sampled row (global row index even) -> that row's fp64 sum in sums[y / 2].  The shape of
+// the sum is a function of W alone: the row is cut into chunks of 8 pixels (4 samples, 48 bytes of a 3-channel row), lane t adds
+// the chunks t, t + 256, ... sample by sample into one accumulator, and the 256 accumulators meet in a fixed LDS tree.  Whether a
+// chunk comes in as three 16-byte loads (3 channels, row base 16-byte aligned) or sample by sample changes no operand, so a
+// row's sum depends only on its bytes, W, channels and root: the same bits however the rows are delivered.  No atomics.
+struct ExposureRowsArgs {
+    const uint16_t* src;  // row src_gy0 of the (H, W, ch) frame
+    int src_gy0;
+    int W, ch;
+    int y_first, n_rows;  // first sampled row (even) and the number of sampled rows of this call
+    double inv_root;
+    double* sums;  // [ceil(H / 2)]
+};
+
+__device__ __forceinline__ double exposure_term(unsigned u, double inv_root) {
+    const float g = (float)u / 65535.0f;  // correctly rounded, like NumPy's and decode_u16_kernel's
+    return pow((double)g, inv_root);
+}
+
+// The sum of 256 lane accumulators in a fixed order (s = 128, 64, ... 1: red[i] += red[i + s]); every lane gets it.
+__device__ __forceinline__ double block_sum_256(double mine, double* red) {
+    const int i = threadIdx.x;
+    red[i] = mine;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (i < s) red[i] = red[i] + red[i + s];
+        __syncthreads();
+    }
+    const double total = red[0];
+    __syncthreads();
+    return total;
+}
+
+__global__ __launch_bounds__(256) void exposure_rows_kernel(const ExposureRowsArgs a) {
+    __shared__ double red[256];
+    if ((int)blockIdx.x >= a.n_rows) return;
+    const int y = a.y_first + 2 * (int)blockIdx.x;
+    const uint16_t* row = a.src + (long long)(y - a.src_gy0) * a.W * a.ch;
+    const bool vec = a.ch == 3 && (reinterpret_cast<uintptr_t>(row) & 15u) == 0;  // (uniform over the workgroup)
+    const int chunks = (a.W + 7) / 8;
+    double acc = 0.0;
+    for (int c = threadIdx.x; c < chunks; c += 256) {
+        const int x0 = 8 * c;
+        if (vec && x0 + 8 <= a.W) {
+            const uint4* s4 = reinterpret_cast<const uint4*>(row + (long long)x0 * 3);  // 24 samples; the greens are 1, 7, 13, 19
+            const uint4 w0 = s4[0], w1 = s4[1], w2 = s4[2];
+            acc = acc + exposure_term(w0.x >> 16, a.inv_root);
+            acc = acc + exposure_term(w0.w >> 16, a.inv_root);
+            acc = acc + exposure_term(w1.z >> 16, a.inv_root);
+            acc = acc + exposure_term(w2.y >> 16, a.inv_root);
+        } else {
+            for (int x = x0; x < min(x0 + 8, a.W); x += 2)
+                acc = acc + exposure_term(row[(long long)x * a.ch + 1], a.inv_root);
+        }
+    }
+    const double total = block_sum_256(acc, red);
+    if (threadIdx.x == 0) a.sums[y >> 1] = total;
+}
+
+// exposure_finish_kernel: ONE workgroup adds the ceil(H / 2) row sums (lane t takes t, t + 256, ... in order, then the same LDS
+// tree) and writes stops and factor into the context's record.
+struct ExposureFinishArgs {
+    const double* sums;
+    int n_rows;        // ceil(H / 2)
+    double n_samples;  // ceil(H / 2) * ceil(W / 2)
+    double root, ref;
+    ExposureRecord* rec;
+};
+
+__global__ __launch_bounds__(256) void exposure_finish_kernel(const ExposureFinishArgs a) {
+    __shared__ double red[256];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < a.n_rows; i += 256) acc = acc + a.sums[i];
+    const double total = block_sum_256(acc, red);
+    if (threadIdx.x != 0) return;
+    const double m = total / a.n_samples;
+    const double stops = log2(a.ref / pow(m, a.root));  // (an all-zero sample set: 0.18 / 0 = +inf stops, like the host's)
+    a.rec->stops = stops;
+    a.rec->factor = (float)exp2(stops);
+    a.rec->pad = 0u;
+}
+
+// decode_u16_kernel with the factor read from the record and a pitched source: W pixels of each of H rows that lie src_pitch
+// pixels apart (a crop of the uploaded frame is a pointer offset plus the pitch).  The same expression, contraction off: the same
+// floats for the same factor.  One lane = 4 pixels of one row.
+struct DecodeU16AutoArgs {
+    const uint16_t* src;
+    float* dst;
+    long long W, src_pitch;  // pixels
+    int H, ch;
+    unsigned quad_blocks;    // workgroups per row
+    float divisor;
+    const ExposureRecord* rec;
+    int vec;  // 1: ch == 3, every source row starts 8-byte and every destination row 16-byte aligned -> 8-byte loads, 16-byte stores
+};
+
+__global__ __launch_bounds__(256) void decode_u16_auto_kernel(const DecodeU16AutoArgs a) {
+    const long long y = blockIdx.x / a.quad_blocks;
+    const long long p0 = ((long long)(blockIdx.x % a.quad_blocks) * 256 + threadIdx.x) * 4;
+    if (y >= a.H || p0 >= a.W) return;
+    const float factor = a.rec->factor;
+    const uint16_t* src = a.src + y * a.src_pitch * a.ch;
+    float* dst = a.dst + y * a.W * 3;
+    if (a.vec && p0 + 4 <= a.W) {
+        const uint2* s2 = reinterpret_cast<const uint2*>(src + p0 * 3);
+        const uint2 w0 = s2[0], w1 = s2[1], w2 = s2[2];
+        const unsigned w[6] = {w0.x, w0.y, w1.x, w1.y, w2.x, w2.y};
+        float f[12];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            f[2 * i] = fminf((float)(w[i] & 0xffffu) / a.divisor * factor, 65504.0f);
+            f[2 * i + 1] = fminf((float)(w[i] >> 16) / a.divisor * factor, 65504.0f);
+        }
+        float4* d4 = reinterpret_cast<float4*>(dst + p0 * 3);
+        d4[0] = make_float4(f[0], f[1], f[2], f[3]);
+        d4[1] = make_float4(f[4], f[5], f[6], f[7]);
+        d4[2] = make_float4(f[8], f[9], f[10], f[11]);
+        return;
+    }
+    for (long long p = p0; p < min(p0 + 4, a.W); ++p)
+        for (int c = 0; c < 3; ++c) dst[p * 3 + c] = fminf((float)src[p * a.ch + c] / a.divisor * factor, 65504.0f);
+}
+
 // Measurement aid (bench.py's `copy_ceiling`): a float4 streaming copy, 2 x `bytes` of HBM traffic -- what this chip moves when a
 // kernel does nothing but load and store coalesced 16-byte lanes.  One float4 per lane, non-temporal both ways, one workgroup per
 // 4 KB: the fastest of the shapes in tools/ubench/copy_rate.hip on MI355X (6.57 TB/s; plain loads / stores 6.23, four float4 per
@@ -337,6 +466,33 @@ hipError_t launch_decode_u16(const uint16_t* src, long long n, int ch, float div
                     (ch == 3 && (reinterpret_cast<uintptr_t>(src) & 15u) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) ? 1 : 0};
     const long long quads = (n + 3) / 4;
     launch_k(decode_u16_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, a);
+    return take_launch_status();
+}
+
+hipError_t launch_exposure_rows(const uint16_t* src, int src_gy0, int W, int ch, int y0, int y1, double root, double* sums, hipStream_t s) {
+    const int y_first = y0 + (y0 & 1), n_rows = (y1 - y_first + 1) / 2;  // the even rows of [y0, y1)
+    if (n_rows <= 0) return hipSuccess;
+    ExposureRowsArgs a{src, src_gy0, W, ch, y_first, n_rows, 1.0 / root, sums};
+    launch_k(exposure_rows_kernel, dim3((unsigned)n_rows), dim3(256), 0, s, a);
+    return take_launch_status();
+}
+
+hipError_t launch_exposure_finish(const double* sums, int H, int W, double root, double ref, ExposureRecord* rec, hipStream_t s) {
+    const int n_rows = (H + 1) / 2;
+    ExposureFinishArgs a{sums, n_rows, (double)n_rows * (double)((W + 1) / 2), root, ref, rec};
+    launch_k(exposure_finish_kernel, dim3(1), dim3(256), 0, s, a);
+    return take_launch_status();
+}
+
+hipError_t launch_decode_u16_auto(const uint16_t* src, int H, int W, int ch, long long src_pitch, float divisor, const ExposureRecord* rec,
+                                  float* dst, hipStream_t s) {
+    DecodeU16AutoArgs a{src, dst, W, src_pitch, H, ch, 0u, divisor, rec, 0};
+    if (src_pitch == W) a.W = a.src_pitch = (long long)H * W, a.H = 1;  // contiguous rows: one long row, like decode_u16_kernel
+    const bool rows_ok = a.H == 1 || (a.W % 4 == 0 && a.src_pitch % 4 == 0);
+    a.vec = (ch == 3 && rows_ok && (reinterpret_cast<uintptr_t>(src) & 7u) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) ? 1 : 0;
+    const long long quads = (a.W + 3) / 4;
+    a.quad_blocks = (unsigned)((quads + 255) / 256);
+    launch_k(decode_u16_auto_kernel, dim3((unsigned)((long long)a.quad_blocks * a.H)), dim3(256), 0, s, a);
     return take_launch_status();
 }
 

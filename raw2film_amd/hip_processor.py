@@ -87,6 +87,19 @@ def plan_bands(H, flags, ha, ma, bands, taper):
     return sorted(set(bounds + cut)), None
 
 
+DEVICE_EXPOSURE = "device"  # exposure="device": the auto exposure of a uint16 frame is measured on the device; also the marker a
+                            # payload carries in place of its float `u16_factor`
+
+
+def exposure_on_device(exposure) -> bool:
+    """Is `exposure` the device mode?  None (measured on the host) and a number (stops) are not; any other string raises."""
+    if isinstance(exposure, (str, bytes, bytearray)):
+        if exposure == DEVICE_EXPOSURE:
+            return True
+        raise ValueError(f"exposure must be None (measured on the host), a number of stops or {DEVICE_EXPOSURE!r}, got {exposure!r}")
+    return False
+
+
 class PendingFrame:
     """A frame submitted with HipProcessor.submit_preloaded: `.result()` waits for its download and returns the uint8 array."""
 
@@ -146,6 +159,14 @@ class HipProcessor:
         self.matrix_key = None
         self.uploads = 0  # number of table uploads, for the caching tests
         self.last_output = None  # device uint8 (H, W, 3) of the last process()/process_preloaded(): histogram source
+        # stops the device measured for the last exposure="device" frame this processor uploaded (calc_exposure's, in fp64); frames of
+        # the other modes leave it alone
+        self._last_auto_exposure = None
+        self._auto_exposure_pending = False  # the device-side record holds stops that have not been read back yet
+        self._defer_exposure_read = False  # submit_preloaded's frame in flight: read them when asked, not when the frame is queued
+        # why the uint16 frame the last process / process_preloaded / submit_preloaded / *_jpeg call uploaded was measured on the host
+        # although it asked for exposure="device"; None for every other call (one that re-rendered a cached frame included)
+        self.exposure_rejected = None
 
     def close(self):
         self._results.close()
@@ -289,7 +310,13 @@ class HipProcessor:
                                cache=True, chroma_nr=0, max_scale=400.0, canvas_mode="No", canvas_scale=1.0,
                                canvas_ratio=1.0, exposure=None, metadata=None, **kwargs):
         """PHASE 1 of the two-phase batch API (gpu_processor.py:715-783): pure host work, touches
-        no instance state.  Returns the same payload dict; `image_array` is (H, W, 4) float32 ((H, W, 3) with payload_alpha=False)."""
+        no instance state.  Returns the same payload dict; `image_array` is (H, W, 4) float32 ((H, W, 3) with payload_alpha=False).
+        exposure="device" (a uint16 frame): no pass over the frame here.  `image_array` is then the WHOLE decoded frame -- the caller's
+        array itself when that is contiguous --, `u16_window` the (row0, col0, rows, cols) the aspect and zoom crops keep of it,
+        `exposure_root` calc_exposure's exponent and `u16_factor` the marker "device": phase 2 measures the exposure on the uploaded
+        frame and decodes the window with it.  A frame that is turned or rotated is measured here as with exposure=None, and the
+        payload's `exposure_rejected` says why."""
+        on_device = exposure_on_device(exposure)
         if lens_correction and cam is not None and lens is not None:
             # the reference corrects only when both are given (cpu_processor.py:107-108, effects.py:22-30); lensfun is not
             # part of the accelerated path, and rendering an uncorrected frame in its place would be a silent difference
@@ -299,8 +326,21 @@ class HipProcessor:
         # gpu_processor.py:275 runs on the device after the upload instead of as a 12 B/px pass over host memory
         internal = bool(kwargs.get("_internal"))
         image = self._load_decoded(src, clip=not internal)
-        u16_factor = None
-        if image.dtype == np.uint16:
+        u16_factor = u16_window = exposure_root = exposure_rejected = None
+        if image.dtype == np.uint16 and on_device and (rotation or int(rotate_times) % 4):
+            exposure_rejected = (f"rotation = {rotation!r}, rotate_times = {rotate_times!r}: a turned or rotated frame is measured on "
+                                 "the host")
+            on_device, exposure = False, None
+        if image.dtype == np.uint16 and on_device:
+            from . import decode
+
+            # the statistic is the whole frame's (upstream measures before any crop), so the whole frame goes up; the crops become
+            # a window the device decodes (raw_conversion.crop_rotate_zoom's index arithmetic, raw_conversion.py:56-72)
+            r0, c0, nr, nc = geometry.crop_box(image.shape[0], image.shape[1], 1, frame_width / frame_height, flip)
+            zr0, zc0, znr, znc = geometry.crop_box(nr, nc, zoom, frame_width / frame_height, False)
+            u16_window = (r0 + zr0, c0 + zc0, znr, znc)
+            u16_factor, exposure_root = DEVICE_EXPOSURE, float(decode.exposure_root(metadata))
+        elif image.dtype == np.uint16:
             # raw_to_linear's tail (raw_conversion.py:50-52) moves to the device: the auto exposure is measured here, on the
             # whole decoded frame like upstream (before any crop), unless the caller brings the stops along
             from . import decode
@@ -321,6 +361,8 @@ class HipProcessor:
                 raise ValueError(f"rotation {rotation} / zoom {zoom} leave an empty frame")
             warp = {"m_dst_to_src": m_inv, "window": (wr0 + zr0, wc0 + zc0, znr, znc), "rotate_times": int(rotate_times) % 4}
             h, w = (znc, znr) if warp["rotate_times"] % 2 else (znr, znc)
+        elif u16_window is not None:
+            h, w = u16_window[2:]  # (the frame stays whole: the window is cut on the device)
         else:
             # aspect crop / zoom / quarter turns: index arithmetic of raw_conversion.crop_rotate_zoom (raw_conversion.py:56-72)
             image = geometry.crop_to_frame(image, frame_width, frame_height, zoom, rotate_times, flip)
@@ -357,7 +399,9 @@ class HipProcessor:
             res, _, _ = geometry.canvas_layout((out_h, out_w), canvas_mode, canvas_scale, canvas_ratio)
             canvas_res = (res[1], res[0])
         alpha = getattr(self, "payload_alpha", True) and not internal
-        if u16_factor is not None:
+        if u16_window is not None:
+            image = np.ascontiguousarray(image)  # (the array itself when it is contiguous; a fourth channel is dropped on the device)
+        elif u16_factor is not None:
             image = np.ascontiguousarray(image[..., :3])
         elif image.shape[2] == 3 and alpha:
             image = np.concatenate([image, np.ones_like(image[..., :1])], axis=-1)  # gpu_processor.py:765
@@ -367,7 +411,12 @@ class HipProcessor:
             image = np.ascontiguousarray(image, dtype=np.float32)
         return {
             "image_array": image,
-            "u16_factor": u16_factor,  # float32 exposure factor of a uint16 payload (converted on the device), else None
+            # float32 exposure factor of a uint16 payload (converted on the device), else None; "device": measured there too, on the
+            # whole frame `image_array` then is, of which the pipeline takes `u16_window` (calc_exposure's exponent: `exposure_root`)
+            "u16_factor": u16_factor,
+            "u16_window": u16_window,
+            "exposure_root": exposure_root,
+            "exposure_rejected": exposure_rejected,  # why exposure="device" was measured on the host after all, or None
             "clip_on_device": internal and u16_factor is None,  # the float frame still has to be clamped to [0, 65504]
             "final_resolution": final_resolution,
             "output_resolution": (out_w, out_h),
@@ -417,13 +466,16 @@ class HipProcessor:
         like GpuProcessor.process with a destination (gpu_processor.py:1865-1890): the frame is letterboxed into it on the
         device, `histogram_texture` (same kind of tensor) receives the histogram image, and None is returned.
         A uint16 `src` is LibRaw's 16-bit output before raw_to_linear's last two lines (raw_conversion.py:50-52): those run on
-        the device with the auto exposure measured on the host (`metadata`: the EXIF dict calc_exposure reads) or given in stops
-        (`exposure`).
+        the device with the auto exposure measured on the host (`metadata`: the EXIF dict calc_exposure reads), given in stops
+        (`exposure`), or -- exposure="device" -- measured on the device on the uploaded frame: upstream's formula in fp64, a few
+        1e-5 stops at most from upstream's own float32 evaluation and not bit-equal to it; `last_auto_exposure` then holds the stops.
         An array `src` that is the array of the previous call is taken for the same frame when a fingerprint of it agrees (shape,
         dtype, address and a checksum of up to 32 evenly spaced rows -- an edit confined to other rows is NOT seen: pass
         cache=False after a partial in-place edit, or `src_version`, any hashable token of the caller's that changes whenever
         the buffer's content does and then replaces the checksum)."""
         settings = dict(locals())  # every keyword of the signature (the unknown ones in `_` aside), named nowhere else
+        exposure_on_device(exposure)  # (any string but "device" raises before any work starts)
+        self.exposure_rejected = None
         for k in ("self", "src", "negative_film", "grain_size", "grain_sigma", "dst_texture", "histogram_texture", "_"):
             del settings[k]
         # load_image_texture's share; prepare() and the render take what they need of all of them and swallow the rest
@@ -604,6 +656,7 @@ class HipProcessor:
         final_scaling: "gpu" -- like GpuProcessor, the canvas keeps its size and only a `max_scale` render is scaled back up;
         "cpu" -- like CpuProcessor.process (cpu_processor.py:411-412), the finished frame, canvas included, is scaled to the
         requested resolution (INTER_AREA down, LANCZOS4 up).  dst_texture / histogram_texture: see process()."""
+        self.exposure_rejected = None
         if dst_texture is None and histogram_texture is None and self.stream_bands > 1:
             res = self._stream_payload(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, **settings)
             if res is not None:  # a large frame without a device pre-path: through the pipeline in row bands while it arrives
@@ -657,6 +710,8 @@ class HipProcessor:
         q = _jpeg_quality(quality)
         opts = _jpeg_options(subsampling, optimize, exif)
         prog = _jpeg_progressive(progressive)
+        exposure_on_device(settings.get("exposure"))
+        self.exposure_rejected = None
         for k in ("dst_texture", "histogram_texture"):
             if settings.pop(k, None) is not None:
                 raise ValueError(f"process_jpeg writes a file: {k} is not taken (use process() for the preview)")
@@ -691,6 +746,7 @@ class HipProcessor:
         q = _jpeg_quality(quality)
         opts = _jpeg_options(subsampling, optimize, exif)
         prog = _jpeg_progressive(progressive)
+        self.exposure_rejected = None
         for k in ("dst_texture", "histogram_texture"):
             if settings.pop(k, None) is not None:
                 raise ValueError(f"process_preloaded_jpeg writes a file: {k} is not taken")
@@ -754,10 +810,11 @@ class HipProcessor:
         if plan is None:
             return None
         host, p, bounds, bufs, ha, ma = plan
-        H, W = int(host.shape[0]), int(host.shape[1])
+        H, W = bufs["shape"][:2]
         sink = self._results.sink((H, W, 3), self.result_buffers, lease=self._lease_result)
         try:
             self._run_bands(host, payload, p, bounds, bufs, ha, ma, sink)
+            self._collect_auto_exposure()
         except BaseException:
             # a stage call refused (or the caller interrupted): let the queued work drain, hand a lent buffer back, pass it on
             self._torch.cuda.synchronize(self.device)
@@ -772,11 +829,15 @@ class HipProcessor:
         """Qualify a payload for the row-band path and set its frame up: (host tensor, frame params, band bounds, device buffers,
         halation reach, MTF reach), or None with `stream_rejected` saying why it does not stream."""
         host = self._payload_tensor(payload)
-        self.stream_rejected = stream_rejection(payload, tuple(host.shape), str(host.dtype), host.is_cuda, final_scaling,
+        shape = tuple(host.shape)
+        if payload.get("u16_window") is not None and len(shape) == 3:  # (the pipeline's frame is the window of the uploaded one)
+            shape = tuple(int(v) for v in payload["u16_window"][2:]) + shape[2:]
+        self.stream_rejected = stream_rejection(payload, shape, str(host.dtype), host.is_cuda, final_scaling,
                                                 settings.get("canvas_mode", "No"))
         if self.stream_rejected is not None:
             return None
-        H, W = int(host.shape[0]), int(host.shape[1])
+        self.exposure_rejected = payload.get("exposure_rejected")
+        H, W = int(shape[0]), int(shape[1])
         params = self.prepare(negative_film, grain_size, grain_sigma, (W, H), **settings)
         hal, mtf = bool(params.flags & _lib.F_HALATION), bool(params.flags & _lib.F_MTF)
         ha = self._halation_reach if hal else (0, 0)
@@ -784,7 +845,7 @@ class HipProcessor:
         bounds, self.stream_rejected = plan_bands(H, int(params.flags), ha, ma, self.stream_bands, self.stream_taper)
         if bounds is None:
             return None
-        bufs = self._stream_buffers(host, mtf)
+        bufs = self._stream_buffers(host, mtf, H, W)
         p = _lib.Params.from_buffer_copy(params)
         p.flags |= _lib.F_FRAME_RESIDENT  # the seed is written once, here; the stage calls read it from the frame block
         self.ctx.write_frame_params(p)     # (and the exposure-range record starts empty)
@@ -806,6 +867,7 @@ class HipProcessor:
         sink = JpegBandSink(staging, self.ctx, bufs["u8"], quality, bounds, down, file, subsampling, exif)
         try:
             self._run_bands(host, payload, p, bounds, bufs, ha, ma, None, band_done=sink.band)
+            self._collect_auto_exposure()
             res = sink.finish()
         except BaseException:
             # a stage call refused, a write raised (or the caller interrupted): let the queued work drain, stop the copies and the
@@ -816,10 +878,10 @@ class HipProcessor:
         self.last_output = bufs["u8"]
         return res
 
-    def _stream_buffers(self, host, mtf):
-        """The device buffers a streamed frame works in (kept for the next frame of the same kind): `host` is its payload tensor."""
+    def _stream_buffers(self, host, mtf, H, W):
+        """The device buffers a streamed H x W frame works in (kept for the next frame of the same kind): `host` is its payload tensor
+        (the frame itself, or the whole uint16 frame the pipeline takes a window of)."""
         torch = self._torch
-        H, W = int(host.shape[0]), int(host.shape[1])
         chans = 3 if host.dtype == torch.int16 else int(host.shape[2])  # (a payload with upstream's alpha plane, gpu_processor.py:765: 4)
         bufs = getattr(self, "_stream_bufs", None)
         if bufs is None or bufs["shape"] != (H, W, chans) or bufs["mtf"] != mtf:
@@ -837,12 +899,17 @@ class HipProcessor:
         stage reads into the band after its own), and the tail's rows go back into `sink` -- or, with `band_done`, band_done(b) is
         called instead once band b's tail is queued (on the launching stream; the JPEG export's sink)."""
         torch, ctx = self._torch, self.ctx
-        H, n = int(host.shape[0]), len(bounds) - 1
+        H, n = int(bounds[-1]), len(bounds) - 1
         hal, mtf, grain = (bool(p.flags & f) for f in (_lib.F_HALATION, _lib.F_MTF, _lib.F_GRAIN))
         pointwise = not (hal or mtf or grain)
         is_u16 = host.dtype == torch.int16
         image, E, D, out_u8 = bufs["image"], bufs["E"], bufs["D"], bufs["u8"]
         landing = bufs["u16"] if is_u16 else image
+        # exposure="device": the whole uint16 frame goes up (the statistic is the whole frame's), the bands are rows of its window --
+        # band k travels as the frame rows `ub[k]:ub[k + 1]`, the first and the last taking the rows above and below the window along
+        auto = is_u16 and payload.get("u16_factor") == DEVICE_EXPOSURE
+        r0, c0, _, nc = payload["u16_window"] if auto else (0, 0, 0, 0)
+        ub = [0] + [b + r0 for b in bounds[1:-1]] + [int(host.shape[0])] if auto else bounds
         up, down = self._copy_streams()
         compute = torch.cuda.current_stream(self.device)
         up.wait_stream(compute)  # (the buffers may still be read by the previous frame's launches)
@@ -850,7 +917,7 @@ class HipProcessor:
 
         def send_up(k):
             with torch.cuda.stream(up):
-                landing[bounds[k]:bounds[k + 1]].copy_(host[bounds[k]:bounds[k + 1]], non_blocking=True)
+                landing[ub[k]:ub[k + 1]].copy_(host[ub[k]:ub[k + 1]], non_blocking=True)
                 return up.record_event()
 
         def send_back(b):
@@ -873,11 +940,23 @@ class HipProcessor:
         arrivals = None if uploader is None else [uploader.submit(send_up, k) for k in range(n)]
         dens = sharp = tail = ident = 0  # bands through the halation, the MTF, the tail; the last front call's identity flag
         try:
+            if auto:
+                # every band's row statistic behind its arrival, then the finish: the factor is in the device-side record before the
+                # first decode reads it, and the host never learns it in between (the render starts behind the upload in this mode)
+                Hf, Wf, root = int(host.shape[0]), int(host.shape[1]), payload["exposure_root"]
+                for k in range(n):
+                    compute.wait_event(send_up(k) if arrivals is None else arrivals[k].result())
+                    ctx.exposure_rows(landing[ub[k]:ub[k + 1]], root, H=Hf, gy0=ub[k])
+                ctx.exposure_finish(Hf, Wf, root)
+                self._auto_exposure_pending = True
             for k in range(n):
                 a0, a1 = bounds[k], bounds[k + 1]
-                compute.wait_event(send_up(k) if arrivals is None else arrivals[k].result())
+                if not auto:
+                    compute.wait_event(send_up(k) if arrivals is None else arrivals[k].result())
                 rows = image[a0:a1]
-                if is_u16:
+                if auto:
+                    ctx.decode_u16_auto(landing[r0 + a0:r0 + a1], (0, c0, a1 - a0, nc), out=rows)
+                elif is_u16:
                     ctx.decode_u16(landing[a0:a1], payload["u16_factor"], out=rows)
                 elif payload.get("clip_on_device"):
                     rows.clamp_(0.0, 65504.0)  # np.clip(image, 0, 65504) of gpu_processor.py:275, band by band
@@ -954,6 +1033,7 @@ class HipProcessor:
         directions with the render (raw2film_amd.sharding.BatchSharder.run(..., collect=...) does exactly that) -- what the
         reference's queue.write_texture / read_texture pair serialises."""
         torch = self._torch
+        self.exposure_rejected = None
         src = cpu_payload.get("image_array")
         if self.stream_bands > 1 and not (isinstance(src, torch.Tensor) and (src.is_cuda or src.is_pinned())):
             # a large frame in ordinary (pageable) host memory: its copy blocks this thread, so nothing of the next frame's host work
@@ -975,7 +1055,13 @@ class HipProcessor:
             uploaded = up.record_event()
         compute.wait_event(uploaded)
         dev.record_stream(compute)
-        out_u8 = self._render_preloaded(dev, cpu_payload, negative_film, grain_size, grain_sigma, None, None, final_scaling, **settings)
+        # (a frame in flight: the stops of exposure="device" are read back when `last_auto_exposure` is asked for, not here -- the read
+        # waits for this frame's upload and statistic, the time in which the caller prepares the next frame)
+        self._defer_exposure_read = True
+        try:
+            out_u8 = self._render_preloaded(dev, cpu_payload, negative_film, grain_size, grain_sigma, None, None, final_scaling, **settings)
+        finally:
+            self._defer_exposure_read = False
         rendered = compute.record_event()
         with torch.cuda.stream(down):
             down.wait_event(rendered)
@@ -998,7 +1084,17 @@ class HipProcessor:
         if image.dtype in (torch.int16, torch.uint16):  # a decoded 16-bit frame: raw_conversion.py:50-52 on the device
             if cpu_payload.get("u16_factor") is None:
                 raise ValueError("a uint16 payload needs its exposure factor (`u16_factor`, extract_image_data_cpu sets it)")
-            image = self.ctx.decode_u16(image.contiguous(), cpu_payload["u16_factor"])
+            self.exposure_rejected = cpu_payload.get("exposure_rejected")
+            if cpu_payload["u16_factor"] == DEVICE_EXPOSURE:
+                # statistic, finish, decode from the record: queued one behind the other, no host synchronisation in between
+                image = image.contiguous()
+                root = cpu_payload["exposure_root"]
+                self.ctx.exposure_rows(image, root)
+                self.ctx.exposure_finish(int(image.shape[0]), int(image.shape[1]), root)
+                self._auto_exposure_pending = True
+                image = self.ctx.decode_u16_auto(image, cpu_payload["u16_window"])
+            else:
+                image = self.ctx.decode_u16(image.contiguous(), cpu_payload["u16_factor"])
         elif cpu_payload.get("clip_on_device"):
             image = image.clamp_(0.0, 65504.0)  # np.clip(image, 0, 65504) of gpu_processor.py:275, on the uploaded copy
         layout = None  # the payload is (H, W, C) like the reference's; the device pre-path hands on (3, H, W) planes
@@ -1032,6 +1128,7 @@ class HipProcessor:
         torch = self._torch  # noqa: F841
         out_f32, out_u8 = self._execute_pipeline(image, negative_film, grain_size, grain_sigma, want_f32=dst_texture is not None,
                                                  want_u8=True, layout=layout, **settings)
+        self._collect_auto_exposure()
         if dst_texture is not None:
             # GpuProcessor's destination branch (gpu_processor.py:1865-1890): letterbox the float frame into the widget's
             # texture with copy_to_int.wgsl's transform, draw the histogram into its own texture, return nothing
@@ -1064,6 +1161,27 @@ class HipProcessor:
                 out_u8 = self.ctx.resize_area_u8(out_u8.contiguous(), *size)
         self.last_output = out_u8
         return out_u8
+
+    def _collect_auto_exposure(self, now=False):
+        """exposure="device": once the frame is queued, the stops the device measured come back into `last_auto_exposure` (the wait
+        is for the finish kernel behind the upload, not for the render).  submit_preloaded's frame in flight leaves the read to the
+        first look at `last_auto_exposure` (now=True)."""
+        if self._auto_exposure_pending and (now or not self._defer_exposure_read):
+            self._auto_exposure_pending = False
+            self._last_auto_exposure = self.ctx.exposure_result()[0]
+
+    @property
+    def last_auto_exposure(self):
+        """Stops the device measured for the last exposure="device" frame, else what was stored last.  After submit_preloaded
+        the first read synchronises with the device: it may block until the frame in flight has been uploaded and measured
+        (not until it is rendered).  After process / process_preloaded the value is already on the host and the read is free."""
+        self._collect_auto_exposure(now=True)
+        return self._last_auto_exposure
+
+    @last_auto_exposure.setter
+    def last_auto_exposure(self, stops):
+        self._auto_exposure_pending = False
+        self._last_auto_exposure = stops
 
     def generate_histogram(self, image=None, mix_table=None, height=100):
         """utils.generate_histogram (utils.py:145-223) of `image` (uint8 (H, W, 3), NumPy or device) -- or, with no image,
