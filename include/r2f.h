@@ -162,6 +162,12 @@ R2F_API int r2f_set_kernel(r2f_ctx* ctx, int which, const float* host_khwc, int 
 R2F_API size_t r2f_workspace_bytes(const r2f_params* p, int H, int W);
 R2F_API int r2f_render(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, float* out_f32_hwc,
                uint8_t* out_u8_hwc, int H, int W, void* workspace, size_t workspace_bytes, void* stream);
+/* r2f_render with a 16-bit result: out_u16_hwc, device (H, W, 3) uint16, 2-byte aligned, = clip(x * 65535.0f, 0, 65535) truncated in
+ * fp32 -- cpu_processor.py:407's `(image * 255).astype(uint8)` with 2 ** 16 - 1 -- of the very float out_f32_hwc receives (which may
+ * be NULL).  Shares r2f_render's graph cache: which output a frame writes is part of its key, so r2f_render and r2f_render16 may
+ * alternate on the same input and workspace. */
+R2F_API int r2f_render16(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, float* out_f32_hwc, uint16_t* out_u16_hwc,
+                 int H, int W, void* workspace, size_t workspace_bytes, void* stream);
 /* Counters of r2f_render since r2f_create: out[0] frames replayed from a graph, out[1] graphs captured, out[2] frames launched
  * kernel by kernel, out[3] graphs dropped (context changes, evictions, failed captures). */
 R2F_API int r2f_render_stats(const r2f_ctx* ctx, uint64_t* out4);
@@ -214,6 +220,10 @@ R2F_API int r2f_write_frame_params(r2f_ctx* ctx, const r2f_params* p, void* stre
 R2F_API int r2f_stage_front(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, int in_gy0, int in_rows,
                     int upto, const r2f_planes* dst, float* out_f32_hwc, uint8_t* out_u8_hwc, int out_gy0, int y0,
                     int y1, int W, int H_global, void* stream);
+/* r2f_stage_front(upto = OUTPUT) with the 16-bit output of r2f_render16 (rows indexed from out_gy0; either output may be NULL).
+ * It runs the generic pointwise kernel: the LDS-staged front kernel of the 8-bit and float outputs has no uint16 store. */
+R2F_API int r2f_stage_front16(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, int in_gy0, int in_rows, float* out_f32_hwc,
+                      uint16_t* out_u16_hwc, int out_gy0, int y0, int y1, int W, int H_global, void* stream);
 /* r2f_stage_front(upto = EXPOSURE) for a frame that goes on to r2f_stage_halation, split by what the halation does to each
  * channel: a channel with a real stencil gets its exposure written to `exposure`; a channel whose halation stencil is ONE tap
  * at the anchor (f_c = 0: the blue layer of a colour stock) needs no neighbours, so its tap weight, S3 and S4 are applied here
@@ -250,6 +260,16 @@ R2F_API int r2f_stage_grain_field(r2f_ctx* ctx, const r2f_params* p, const r2f_p
                           void* stream);
 R2F_API int r2f_stage_tail_field(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const r2f_planes* field, float* out_f32,
                          uint8_t* out_u8, int out_gy0, int y0, int y1, int W, int H_global, void* stream);
+
+/* r2f_stage_tail / r2f_stage_tail_field with a third output form beside float and uint8: out_u16_hwc, uint16 (rows, W, 3) indexed
+ * from out_gy0 like the others, 2-byte aligned (a row is 6 W bytes: with an odd W no row but the first starts on more than that).
+ * S9 with 16 bits: clip(x * 65535.0f, 0, 65535) truncated, cpu_processor.py:407's rule with 2 ** 16 - 1, from the same float
+ * out_f32_hwc receives.  Any of the three may be NULL, not all of them; out_f32_hwc and out_u8_hwc receive exactly what
+ * r2f_stage_tail writes. */
+R2F_API int r2f_stage_tail16(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const float* burn_map, float* out_f32_hwc,
+                     uint8_t* out_u8_hwc, uint16_t* out_u16_hwc, int out_gy0, int y0, int y1, int W, int H_global, void* stream);
+R2F_API int r2f_stage_tail_field16(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const r2f_planes* field, float* out_f32,
+                           uint8_t* out_u8, uint16_t* out_u16, int out_gy0, int y0, int y1, int W, int H_global, void* stream);
 
 /* S6 grain + clip alone, density planes -> density planes (the first half of the tail when S7 is on: the burn map
  * is a function of the WHOLE grained frame, so the frame has to exist before any pixel can be finished). */
@@ -312,6 +332,16 @@ R2F_API int r2f_histogram_u8(r2f_ctx* ctx, const uint8_t* image_hwc, int H, int 
  * INTER_AREA) when the rendered (and canvas-framed) frame is larger than the requested resolution.  src / dst: uint8
  * (H, W, 3) / (out_h, out_w, 3) on the device, out_h <= H, out_w <= W. */
 R2F_API int r2f_resize_area_u8(r2f_ctx* ctx, const uint8_t* src_hwc, int H, int W, uint8_t* dst_hwc, int out_h, int out_w, void* stream);
+
+/* The two post-path resamplers on a 16-bit result (r2f_render16): utils.resolution_scaling (utils.py:226-244) as
+ * cpu_processor.py:411-412 applies it, on uint16 (H, W, 3) device frames, 2-byte aligned.
+ *   r2f_resize_lanczos4_u16  cv.resize(uint16, INTER_LANCZOS4): OpenCV's float-weight path (the tables of r2f_lanczos4_table_f32),
+ *                            the horizontal pass then the vertical one in float, saturate_cast<ushort> (round half to even, clamp
+ *                            to [0, 65535]) at the end.
+ *   r2f_resize_area_u16      cv.resize(uint16, INTER_AREA), out_h <= H, out_w <= W: exact 2 x 2 as (a + b + c + d + 2) >> 2, every
+ *                            other ratio as the float area sum with the same rounding and clamp. */
+R2F_API int r2f_resize_lanczos4_u16(r2f_ctx* ctx, const uint16_t* src_hwc, int H, int W, uint16_t* dst_hwc, int out_h, int out_w, void* stream);
+R2F_API int r2f_resize_area_u16(r2f_ctx* ctx, const uint16_t* src_hwc, int H, int W, uint16_t* dst_hwc, int out_h, int out_w, void* stream);
 
 /* The hand-off from RAW decoding: the last two lines of raw_to_linear (raw_conversion.py:50-52) applied to LibRaw's 16-bit
  * output on the device, so that a decoded frame crosses PCIe as uint16 (6 bytes per pixel) instead of float32 (12 or 16):
@@ -511,6 +541,22 @@ R2F_API int r2f_jpeg_encode_ex(r2f_ctx* ctx, const uint8_t* image, int H, int W,
  * need the whole frame before the first scan byte, and for progressive, whose every scan spans the whole frame. */
 R2F_API int r2f_jpeg_rows_begin_ex(r2f_ctx* ctx, int H, int W, const r2f_jpeg_opts* opts, uint8_t* out, uint64_t out_cap,
                                    uint64_t* out_len, void* stream);
+
+/* --- TIFF export: a 16-bit (or 8-bit) result on disk.  Upstream stops at gui.py:2338-2341's 8-bit JPEG; this is the same hand-off
+ * for a frame of r2f_render16.  The file is baseline TIFF 6.0: little-endian, uncompressed, chunky RGB, BitsPerSample 8,8,8 or
+ * 16,16,16, Orientation 1, one strip per rows_per_strip rows (about 256 KiB each), the ICC profile in tag 34675 when given.
+ * Everything but the pixels is the header this call writes; the strips follow it one behind the other, so row y of the frame is
+ * the row_bytes bytes at header_bytes + y * row_bytes (samples little-endian) and every offset is known before a pixel exists.
+ * buf = NULL: the sizes alone (*len, *plan).  R2F_ETOOLARGE: the file would pass a classic TIFF's 4 GiB (plan->file_bytes says by
+ * how much; nothing is written).  No GPU, no context. */
+typedef struct r2f_tiff_plan {
+    uint64_t header_bytes; /* = *len: where the first strip starts (4-byte aligned) */
+    uint64_t file_bytes;
+    uint64_t row_bytes;    /* W * 3 * bits / 8 */
+    uint32_t rows_per_strip, strips;
+} r2f_tiff_plan;
+R2F_API int r2f_tiff_header(int H, int W, int bits, const uint8_t* icc, size_t icc_len, uint8_t* buf, size_t cap, size_t* len,
+                    r2f_tiff_plan* plan);
 
 #ifdef __cplusplus
 }

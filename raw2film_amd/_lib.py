@@ -61,6 +61,11 @@ class JpegOpts(C.Structure):  # r2f_jpeg_opts (sampling: 0 4:4:4, 1 4:2:2, 2 4:2
     _fields_ = [("quality", C.c_int32), ("sampling", C.c_int32), ("optimize", C.c_int32), ("progressive", C.c_int32)]
 
 
+class TiffPlan(C.Structure):  # r2f_tiff_plan
+    _fields_ = [("header_bytes", C.c_uint64), ("file_bytes", C.c_uint64), ("row_bytes", C.c_uint64), ("rows_per_strip", C.c_uint32),
+                ("strips", C.c_uint32)]
+
+
 _P = C.POINTER
 _fp = C.c_void_p  # float* (host numpy or device) passed as an address
 _SIGNATURES = {
@@ -204,6 +209,31 @@ _SIGNATURES = {
     "r2f_jpeg_rows_begin_ex": (
         C.c_int,
         [C.c_void_p, C.c_int, C.c_int, _P(JpegOpts), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p],
+    ),
+    "r2f_render16": (
+        C.c_int,
+        [C.c_void_p, _P(Params), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
+    "r2f_stage_front16": (
+        C.c_int,
+        [C.c_void_p, _P(Params), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+         C.c_int, C.c_void_p],
+    ),
+    "r2f_stage_tail16": (
+        C.c_int,
+        [C.c_void_p, _P(Params), _P(Planes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+         C.c_int, C.c_void_p],
+    ),
+    "r2f_stage_tail_field16": (
+        C.c_int,
+        [C.c_void_p, _P(Params), _P(Planes), _P(Planes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+         C.c_int, C.c_void_p],
+    ),
+    "r2f_resize_lanczos4_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "r2f_resize_area_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "r2f_tiff_header": (
+        C.c_int,
+        [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, _P(C.c_size_t), _P(TiffPlan)],
     ),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -265,6 +265,86 @@ class HipContext:
         self._check(rc)
         return out_f32, out_u8
 
+    # ------------------------------------------------------------------ 16-bit output (r2f_render16 and the stage calls beside it)
+    def _check_out16(self, t, W, what, **kw):
+        """A 16-bit output tensor: uint16, or int16 holding the same bits (torch's uint16 knows few operations)."""
+        if t is not None and t.dtype not in (self._torch.int16, self._torch.uint16):
+            raise ValueError(f"{what} must be a contiguous 16-bit CUDA tensor of shape (rows, {int(W)}, 3)")
+        self._check_out(t, None if t is None else t.dtype, W, what, **kw)
+
+    def render16(self, image, params, out_f32=None, out_u16=None, want_f32=False, layout=None):
+        """render() with the 16-bit result of r2f_render16: clip(x * 65535, 0, 65535) truncated, from the float out_f32 holds.
+        Returns (out_f32 or None, out_u16): device tensors (H, W, 3); out_u16 is int16 holding the uint16 bits unless one is given."""
+        torch = self._torch
+        self._check_image(image)
+        layout, H, W = self.layout_of(image, layout)
+        if out_f32 is None and want_f32:
+            out_f32 = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
+        if out_u16 is None:
+            out_u16 = torch.empty((H, W, 3), dtype=torch.int16, device=self.device)
+        self._check_out(out_f32, torch.float32, W, "out_f32", rows=H)
+        self._check_out16(out_u16, W, "out_u16", rows=H)
+        nbytes = self.workspace_bytes(params, H, W)
+        ws = self._get_workspace(nbytes)
+        self._check(self._lib.r2f_render16(
+            self._h, C.byref(params), image.data_ptr(), layout, out_f32.data_ptr() if out_f32 is not None else None,
+            out_u16.data_ptr(), H, W, ws.data_ptr() if ws is not None else None, nbytes, self._stream()))
+        return out_f32, out_u16
+
+    def stage_front16(self, image, params, *, in_gy0=0, out_f32=None, out_u16=None, out_gy0=0, y0=None, y1=None, H_global=None,
+                      layout=None):
+        """stage_front(upto = output) with the 16-bit output (r2f_stage_front16)."""
+        self._check_image(image)
+        layout, rows, W = self.layout_of(image, layout)
+        y0 = in_gy0 if y0 is None else y0
+        y1 = in_gy0 + rows if y1 is None else y1
+        H_global = in_gy0 + rows if H_global is None else H_global
+        self._check_out(out_f32, self._torch.float32, W, "out_f32", gy0=out_gy0, y0=y0, y1=y1)
+        self._check_out16(out_u16, W, "out_u16", gy0=out_gy0, y0=y0, y1=y1)
+        self._check(self._lib.r2f_stage_front16(
+            self._h, C.byref(params), image.data_ptr(), layout, in_gy0, rows, out_f32.data_ptr() if out_f32 is not None else None,
+            out_u16.data_ptr() if out_u16 is not None else None, out_gy0, y0, y1, W, H_global, self._stream()))
+
+    def stage_tail16(self, density, params, *, src_gy0=0, out_f32=None, out_u8=None, out_u16=None, out_gy0=0, y0, y1, H_global,
+                     burn_map=None, field=None, field_gy0=0):
+        """stage_tail (or, with `field`, stage_tail_field) with the 16-bit output beside the other two (r2f_stage_tail16,
+        r2f_stage_tail_field16)."""
+        pd = self.planes(density, src_gy0)
+        W = int(density.shape[2])
+        self._check_out(out_f32, self._torch.float32, W, "out_f32", gy0=out_gy0, y0=y0, y1=y1)
+        self._check_out(out_u8, self._torch.uint8, W, "out_u8", gy0=out_gy0, y0=y0, y1=y1)
+        self._check_out16(out_u16, W, "out_u16", gy0=out_gy0, y0=y0, y1=y1)
+        outs = [t.data_ptr() if t is not None else None for t in (out_f32, out_u8, out_u16)]
+        if field is not None:
+            pf = self.planes(field, field_gy0)
+            self._check(self._lib.r2f_stage_tail_field16(self._h, C.byref(params), C.byref(pd), C.byref(pf), *outs, out_gy0, y0, y1, W,
+                                                         H_global, self._stream()))
+            return
+        if burn_map is not None:
+            self._check_lowres(burn_map, params, H_global, W, "burn_map")
+        self._check(self._lib.r2f_stage_tail16(self._h, C.byref(params), C.byref(pd),
+                                               burn_map.data_ptr() if burn_map is not None else None, *outs, out_gy0, y0, y1, W,
+                                               H_global, self._stream()))
+
+    def _resize16(self, fn, what, image_u16, out_h, out_w):
+        torch = self._torch
+        if not (isinstance(image_u16, torch.Tensor) and image_u16.is_cuda and image_u16.dtype in (torch.int16, torch.uint16)
+                and image_u16.is_contiguous() and image_u16.dim() == 3 and image_u16.shape[2] == 3):
+            raise ValueError(f"{what} needs a contiguous 16-bit (H, W, 3) CUDA tensor")
+        self._same_device(image_u16, "image")
+        out = torch.empty((int(out_h), int(out_w), 3), dtype=image_u16.dtype, device=self.device)
+        self._check(fn(self._h, image_u16.data_ptr(), int(image_u16.shape[0]), int(image_u16.shape[1]), out.data_ptr(), int(out_h),
+                       int(out_w), self._stream()))
+        return out
+
+    def resize_lanczos4_u16(self, image_u16, out_h: int, out_w: int):
+        """cv.resize(uint16 (H, W, 3), (out_w, out_h), interpolation=cv.INTER_LANCZOS4) on the device (int16 tensors: same bits)."""
+        return self._resize16(self._lib.r2f_resize_lanczos4_u16, "resize_lanczos4_u16", image_u16, out_h, out_w)
+
+    def resize_area_u16(self, image_u16, out_h: int, out_w: int):
+        """cv.resize(uint16 (H, W, 3), (out_w, out_h), interpolation=cv.INTER_AREA), shrinking, on the device."""
+        return self._resize16(self._lib.r2f_resize_area_u16, "resize_area_u16", image_u16, out_h, out_w)
+
     # ------------------------------------------------------------------ stages (row-shard aware)
     def stage_front(self, image, params, upto, *, in_gy0=0, dst=None, dst_gy0=0, out_f32=None, out_u8=None,
                     out_gy0=0, y0=None, y1=None, H_global=None, layout=None, track_range=False):

@@ -304,7 +304,8 @@ int r2f_stage_front_split(r2f_ctx* ctx, const r2f_params* p, const void* in, int
 // block and *tracked says whether that happened (only the split fast kernel does it).
 int r2f::stage_front_impl(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, int in_gy0, int in_rows, int upto,
                             const r2f_planes* dst, float* out_f32, uint8_t* out_u8, int out_gy0, int y0, int y1, int W,
-                            int H_global, void* stream, const r2f_planes* finish_dst, int* finished_mask, bool* tracked) {
+                            int H_global, void* stream, const r2f_planes* finish_dst, int* finished_mask, bool* tracked,
+                            uint16_t* out_u16) {
     if (tracked) *tracked = false;
     if (!ctx || !p) return R2F_EINVAL;
     R2F_GUARD(ctx);
@@ -342,10 +343,12 @@ int r2f::stage_front_impl(r2f_ctx* ctx, const r2f_params* p, const void* in, int
     if (upto >= R2F_UPTO_DENSITY && !ctx->curve.cells) return fail(ctx, R2F_EINVAL, "density curve not set (r2f_set_curve1d)");
     if (upto == R2F_UPTO_OUTPUT) {
         if (!ctx->lut3d.tex) return fail(ctx, R2F_EINVAL, "output LUT not set (r2f_set_lut3d)");
-        if (!out_f32 && !out_u8) return fail(ctx, R2F_EINVAL, "front: no output buffer");
+        if (!out_f32 && !out_u8 && !out_u16) return fail(ctx, R2F_EINVAL, "front: no output buffer");
         if (y0 < out_gy0) return fail(ctx, R2F_EINVAL, "front: y0 above the output buffer");
+        if (reinterpret_cast<uintptr_t>(out_u16) & 1u) return fail(ctx, R2F_EINVAL, "front: the uint16 output must be 2-byte aligned");
         a.out_f32 = out_f32;
         a.out_u8 = out_u8;
+        a.out_u16 = out_u16;
         a.out_gy0 = out_gy0;
         vec = vec && (!out_f32 || aligned16(out_f32)) && (!out_u8 || (reinterpret_cast<uintptr_t>(out_u8) & 3u) == 0);
     } else if (upto == R2F_UPTO_EXPOSURE || upto == R2F_UPTO_DENSITY) {
@@ -517,7 +520,7 @@ static int ensure_grain_fixed(r2f_ctx* ctx) {
 
 static int run_tail(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const r2f_planes* planes_out,
                     const float* burn_map, float* out_f32, uint8_t* out_u8, int out_gy0, int y0, int y1, int W, int H_global,
-                    void* stream, const r2f_planes* gfield = nullptr) {
+                    void* stream, const r2f_planes* gfield = nullptr, uint16_t* out_u16 = nullptr) {
     if (y1 <= y0) return R2F_OK;
     const bool field_only = density == nullptr && planes_out != nullptr;
     if (field_only) {
@@ -526,7 +529,8 @@ static int run_tail(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density
     }
     const bool to_planes = planes_out != nullptr;
     if (W <= 0 || y0 < 0 || y1 > H_global || (!to_planes && y0 < out_gy0)) return fail(ctx, R2F_EINVAL, "tail: bad geometry");
-    if (!to_planes && !out_f32 && !out_u8) return fail(ctx, R2F_EINVAL, "tail: no output buffer");
+    if (!to_planes && !out_f32 && !out_u8 && !out_u16) return fail(ctx, R2F_EINVAL, "tail: no output buffer");
+    if (reinterpret_cast<uintptr_t>(out_u16) & 1u) return fail(ctx, R2F_EINVAL, "tail: the uint16 output must be 2-byte aligned");
     if (!to_planes && !ctx->lut3d.tex) return fail(ctx, R2F_EINVAL, "output LUT not set (r2f_set_lut3d)");
     int rc = field_only ? R2F_OK : check_rows(ctx, "tail src", density, y0, y1);
     if (rc) return rc;
@@ -535,6 +539,7 @@ static int run_tail(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density
     a.src = to_dev(density);
     a.out_f32 = out_f32;
     a.out_u8 = out_u8;
+    a.out_u16 = out_u16;
     a.out_gy0 = out_gy0;
     a.y0 = y0;
     a.y1 = y1;
@@ -625,6 +630,36 @@ int r2f_stage_tail(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density,
     if (!ctx || !p) return R2F_EINVAL;
     R2F_GUARD(ctx);
     return run_tail(ctx, p, density, nullptr, burn_map, out_f32, out_u8, out_gy0, y0, y1, W, H_global, stream);
+}
+
+}  // extern "C"
+
+int r2f::stage_tail_impl(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const float* burn_map, float* out_f32,
+                         uint8_t* out_u8, uint16_t* out_u16, int out_gy0, int y0, int y1, int W, int H_global, void* stream) {
+    if (!ctx || !p) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    return run_tail(ctx, p, density, nullptr, burn_map, out_f32, out_u8, out_gy0, y0, y1, W, H_global, stream, nullptr, out_u16);
+}
+
+extern "C" {
+
+int r2f_stage_tail16(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const float* burn_map, float* out_f32,
+                     uint8_t* out_u8, uint16_t* out_u16, int out_gy0, int y0, int y1, int W, int H_global, void* stream) {
+    return stage_tail_impl(ctx, p, density, burn_map, out_f32, out_u8, out_u16, out_gy0, y0, y1, W, H_global, stream);
+}
+
+int r2f_stage_tail_field16(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const r2f_planes* field, float* out_f32,
+                           uint8_t* out_u8, uint16_t* out_u16, int out_gy0, int y0, int y1, int W, int H_global, void* stream) {
+    if (!ctx || !p) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    if (!field) return fail(ctx, R2F_EINVAL, "tail: null grain field");
+    return run_tail(ctx, p, density, nullptr, nullptr, out_f32, out_u8, out_gy0, y0, y1, W, H_global, stream, field, out_u16);
+}
+
+int r2f_stage_front16(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, int in_gy0, int in_rows, float* out_f32,
+                      uint16_t* out_u16, int out_gy0, int y0, int y1, int W, int H_global, void* stream) {
+    return stage_front_impl(ctx, p, in, in_layout, in_gy0, in_rows, R2F_UPTO_OUTPUT, nullptr, out_f32, nullptr, out_gy0, y0, y1, W,
+                            H_global, stream, nullptr, nullptr, nullptr, out_u16);
 }
 
 int r2f_stage_grain_field(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* field, int y0, int y1, int W, int H_global,
@@ -790,6 +825,45 @@ int r2f_resize_lanczos4_u8(r2f_ctx* ctx, const uint8_t* src_hwc, int H, int W, u
     a.xcoef = reinterpret_cast<const short*>(base + coef_off);
     a.ycoef = a.xcoef + 8 * (size_t)out_w;
     R2F_HIP(ctx, launch_lanczos4_u8(a, static_cast<hipStream_t>(stream)));
+    return R2F_OK;
+}
+
+int r2f_resize_lanczos4_u16(r2f_ctx* ctx, const uint16_t* src_hwc, int H, int W, uint16_t* dst_hwc, int out_h, int out_w, void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    if (!src_hwc || !dst_hwc || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0)
+        return fail(ctx, R2F_EINVAL, "resize_lanczos4_u16: bad arguments");
+    if ((reinterpret_cast<uintptr_t>(src_hwc) | reinterpret_cast<uintptr_t>(dst_hwc)) & 1u)
+        return fail(ctx, R2F_EINVAL, "resize_lanczos4_u16: source and destination must be 2-byte aligned");
+    const size_t n_ofs = (size_t)out_w + out_h, n_coef = 8 * n_ofs;
+    const size_t coef_off = (n_ofs * sizeof(int) + 15) / 16 * 16;
+    const int key[4] = {H, W, out_h, out_w};
+    if (memcmp(key, ctx->lanczos_u16_key, sizeof key) != 0 || !ctx->lanczos_u16_buf.p) {
+        std::vector<unsigned char> host(coef_off + n_coef * sizeof(float));
+        int* ofs = reinterpret_cast<int*>(host.data());
+        float* coef = reinterpret_cast<float*>(host.data() + coef_off);
+        r2f_lanczos4_table_f32(W, out_w, ofs, coef);
+        r2f_lanczos4_table_f32(H, out_h, ofs + out_w, coef + 8 * (size_t)out_w);
+        int rc = upload(ctx, ctx->lanczos_u16_buf, host.data(), host.size());
+        if (rc) return rc;
+        memcpy(ctx->lanczos_u16_key, key, sizeof key);
+    }
+    const unsigned char* base = static_cast<const unsigned char*>(ctx->lanczos_u16_buf.p);
+    const int* xofs = reinterpret_cast<const int*>(base);
+    const float* xcoef = reinterpret_cast<const float*>(base + coef_off);
+    R2F_HIP(ctx, launch_lanczos4_u16(src_hwc, H, W, dst_hwc, out_h, out_w, xofs, xcoef, xofs + out_w, xcoef + 8 * (size_t)out_w,
+                                     static_cast<hipStream_t>(stream)));
+    return R2F_OK;
+}
+
+int r2f_resize_area_u16(r2f_ctx* ctx, const uint16_t* src_hwc, int H, int W, uint16_t* dst_hwc, int out_h, int out_w, void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    if (!src_hwc || !dst_hwc || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0 || out_h > H || out_w > W)
+        return fail(ctx, R2F_EINVAL, "resize_area_u16: the target must be a non-empty frame no larger than the source");
+    if ((reinterpret_cast<uintptr_t>(src_hwc) | reinterpret_cast<uintptr_t>(dst_hwc)) & 1u)
+        return fail(ctx, R2F_EINVAL, "resize_area_u16: source and destination must be 2-byte aligned");
+    R2F_HIP(ctx, launch_resize_area_u16(src_hwc, H, W, dst_hwc, out_h, out_w, static_cast<hipStream_t>(stream)));
     return R2F_OK;
 }
 

@@ -71,6 +71,7 @@ struct RenderGraph {
     int in_layout = 0;
     float* out_f32 = nullptr;
     uint8_t* out_u8 = nullptr;
+    uint16_t* out_u16 = nullptr;  // r2f_render16's frames: which output a frame writes is part of its key
     int H = 0, W = 0;
     void* workspace = nullptr;
     r2f_params p{};  // seed zeroed
@@ -164,6 +165,8 @@ struct r2f_ctx {
     r2f::DeviceBuf lanczos_buf;  // [xofs | yofs | xcoef | ycoef] of the last LANCZOS4 geometry
     r2f::DeviceBuf lanczos_f32_buf;  // the same for the float32 up-scale before the path
     int lanczos_key[4] = {0, 0, 0, 0};
+    r2f::DeviceBuf lanczos_u16_buf;  // the float tables of the last uint16 LANCZOS4 geometry (r2f_resize_lanczos4_u16)
+    int lanczos_u16_key[4] = {0, 0, 0, 0};
     // the grain stencil as weight pairs for grain_stencil_fixed (small square symmetric kernels), built on first use
     r2f::DeviceBuf grain_fixed_w;
     bool grain_fixed_valid = false;
@@ -274,7 +277,11 @@ int write_frame_params(r2f_ctx* ctx, const r2f_params* p, hipStream_t s, int mod
 // r2f_stage_front / r2f_stage_front_split; tracked: r2f_render's front call asks whether the exposure range was recorded
 int stage_front_impl(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, int in_gy0, int in_rows, int upto,
                      const r2f_planes* dst, float* out_f32, uint8_t* out_u8, int out_gy0, int y0, int y1, int W, int H_global,
-                     void* stream, const r2f_planes* finish_dst, int* finished_mask, bool* tracked = nullptr);
+                     void* stream, const r2f_planes* finish_dst, int* finished_mask, bool* tracked = nullptr,
+                     uint16_t* out_u16 = nullptr);
+// r2f_stage_tail / r2f_stage_tail16 (out_u16: the 16-bit output, r2f_graph.hip's render16 calls it too)
+int stage_tail_impl(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const float* burn_map, float* out_f32, uint8_t* out_u8,
+                    uint16_t* out_u16, int out_gy0, int y0, int y1, int W, int H_global, void* stream);
 
 // r2f_stencil.hip
 constexpr int kFixedMaxR = 11;  // largest unrolled direct form (23 x 23)

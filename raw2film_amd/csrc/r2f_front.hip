@@ -369,6 +369,7 @@ size_t fast_lds_bytes(const FrontArgs& a) {
 
 // Is the pointwise pass of `a` in the fast kernels' domain?
 bool front_fast_eligible(const FrontArgs& a) {
+    if (a.out_u16) return false;  // (the 16-bit output is the generic kernel's)
     if (!a.vec || a.lut2d.n < 2 || (long long)a.W * 16 >= (1ll << 31) || fast_lds_bytes(a) > 144 * 1024) return false;
     if ((a.upto >= R2F_UPTO_DENSITY || a.finish_mask) && !(a.curve.near && a.curve.m >= 2)) return false;
     if (a.upto == R2F_UPTO_OUTPUT && !(a.lut3d_mode == 0 && a.lut3d.n >= 2 && a.lut3d.n <= 256)) return false;

@@ -37,10 +37,78 @@ __device__ __forceinline__ uint32_t to_u8(float v) {
     return (uint32_t)s;
 }
 
+__device__ __forceinline__ uint32_t to_u16(float v) {
+    // cpu_processor.py:407 with 2 ** 16 - 1 in place of 255: (image * 65535).astype(uint16) -- truncation, from the same float
+    float s = fminf(fmaxf(v * 65535.0f, 0.0f), 65535.0f);
+    return (uint32_t)s;
+}
+
+// Four pixels (twelve samples, 24 bytes) of a uint16 row at `o`.  A pixel is 6 bytes and a row 6 W, so `o` is only 2-byte aligned
+// when W is odd; a lane's segments lie 24 bytes apart, so (address & 7) is the same for every lane of a ROW.  A wave of the
+// pointwise kernels (64 lanes along x) therefore takes ONE of the four shapes below.  A wave of tail_kernel spans four rows (16
+// lanes each): when 6 W is no multiple of 8 (W no multiple of 4) its rows differ in phase and the wave runs through up to four
+// shapes one after the other, each with a quarter of its lanes -- every shape covers the same 24 bytes, so only time is at stake
+// (profiles/r11_output16_probe.txt, W against W - 2).  8-byte stores where the address allows them (the 16-byte phase alternates
+// from lane to lane -- a 16-byte store would split every wave in two), a 4-byte and a 2-byte store at the ends.  Plain vector stores.
+__device__ __forceinline__ void store_u16x12(uint16_t* o, const uint32_t (&h)[12]) {
+    const uint32_t phase = (uint32_t)(reinterpret_cast<uintptr_t>(o) & 7u);
+    if ((phase & 2u) == 0) {
+        uint32_t w[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) w[i] = h[2 * i] | (h[2 * i + 1] << 16);
+        uint32_t* d = reinterpret_cast<uint32_t*>(o);
+        if (phase == 0) {
+            *reinterpret_cast<uint2*>(d) = make_uint2(w[0], w[1]);
+            *reinterpret_cast<uint2*>(d + 2) = make_uint2(w[2], w[3]);
+            *reinterpret_cast<uint2*>(d + 4) = make_uint2(w[4], w[5]);
+        } else {  // 4
+            d[0] = w[0];
+            *reinterpret_cast<uint2*>(d + 1) = make_uint2(w[1], w[2]);
+            *reinterpret_cast<uint2*>(d + 3) = make_uint2(w[3], w[4]);
+            d[5] = w[5];
+        }
+    } else {
+        uint32_t w[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) w[i] = h[2 * i + 1] | (h[2 * i + 2] << 16);
+        o[0] = (uint16_t)h[0];
+        uint32_t* d = reinterpret_cast<uint32_t*>(o + 1);
+        if (phase == 6) {  // o + 1 is 8-byte aligned
+            *reinterpret_cast<uint2*>(d) = make_uint2(w[0], w[1]);
+            *reinterpret_cast<uint2*>(d + 2) = make_uint2(w[2], w[3]);
+            d[4] = w[4];
+        } else {  // 2: o + 1 is 4-byte aligned, o + 3 8-byte
+            d[0] = w[0];
+            *reinterpret_cast<uint2*>(d + 1) = make_uint2(w[1], w[2]);
+            *reinterpret_cast<uint2*>(d + 3) = make_uint2(w[3], w[4]);
+        }
+        o[11] = (uint16_t)h[11];
+    }
+}
+
 // Write `nv` (1..4) consecutive pixels of row `orow` starting at column x, interleaved HWC.
-__device__ __forceinline__ void emit_hwc(float* out_f32, uint8_t* out_u8, long long orow, int x, int W, int nv, bool vec,
-                                         const float (&r)[4], const float (&g)[4], const float (&b)[4]) {
+__device__ __forceinline__ void emit_hwc(float* out_f32, uint8_t* out_u8, uint16_t* out_u16, long long orow, int x, int W, int nv,
+                                         bool vec, const float (&r)[4], const float (&g)[4], const float (&b)[4]) {
     const long long base = (orow * W + x) * 3;
+    if (out_u16) {  // (2-byte aligned is all it asks: the shape is chosen per row segment, whatever `vec` says about the others)
+        uint16_t* o = out_u16 + base;
+        if (nv == 4) {
+            uint32_t h[12];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                h[3 * p + 0] = to_u16(r[p]);
+                h[3 * p + 1] = to_u16(g[p]);
+                h[3 * p + 2] = to_u16(b[p]);
+            }
+            store_u16x12(o, h);
+        } else {  // the last one to three pixels of a row whose width is no multiple of 4
+            for (int p = 0; p < nv; ++p) {
+                o[3 * p + 0] = (uint16_t)to_u16(r[p]);
+                o[3 * p + 1] = (uint16_t)to_u16(g[p]);
+                o[3 * p + 2] = (uint16_t)to_u16(b[p]);
+            }
+        }
+    }
     if (out_f32) {
         float* o = out_f32 + base;
         if (vec && nv == 4) {
@@ -219,7 +287,7 @@ __global__ __launch_bounds__(64 * kFrontBY) void front_kernel(const FrontArgs a)
             if (a.upto == R2F_UPTO_OUTPUT) apply_lut3d(a.lut3d, a.lut3d_scale, a.lut3d_mode, r[q], g[q], b[q]);
         }
         if (a.upto == R2F_UPTO_OUTPUT)
-            emit_hwc(a.out_f32, a.out_u8, gy - a.out_gy0, x, W, nv, vec, r, g, b);
+            emit_hwc(a.out_f32, a.out_u8, a.out_u16, gy - a.out_gy0, x, W, nv, vec, r, g, b);
         else
             store_planes4(a.dst, gy, x, W, nv, vec, r, g, b);
     }
@@ -230,6 +298,7 @@ struct Lut3dArgs {
     DevPlanes src;
     float* out_f32;
     uint8_t* out_u8;
+    uint16_t* out_u16;
     int out_gy0, y0, y1, W;
     DevLut3D lut3d;
     float lut3d_scale;
@@ -286,7 +355,7 @@ __global__ __launch_bounds__(256) void lut3d_kernel(const Lut3dArgs a) {
         }
         apply_lut3d(a.lut3d, a.lut3d_scale, a.lut3d_mode, r[q], g[q], b[q]);
     }
-    emit_hwc(a.out_f32, a.out_u8, gy - a.out_gy0, x, a.W, nv, a.vec != 0, r, g, b);
+    emit_hwc(a.out_f32, a.out_u8, a.out_u16, gy - a.out_gy0, x, a.W, nv, a.vec != 0, r, g, b);
 }
 
 // ------------------------------------------------------------------------------ stencil
@@ -691,7 +760,7 @@ __global__ __launch_bounds__(kTailBX* kTailBY) void tail_kernel(const TailArgs a
         if (a.to_planes)
             store_planes4(a.dst, gy, gx, a.W, nv, vec, r, g, b);
         else
-            emit_hwc(a.out_f32, a.out_u8, gy - a.out_gy0, gx, a.W, nv, vec, r, g, b);
+            emit_hwc(a.out_f32, a.out_u8, a.out_u16, gy - a.out_gy0, gx, a.W, nv, vec, r, g, b);
     }
 }
 
@@ -1217,6 +1286,7 @@ hipError_t launch_tail(const TailArgs& a, hipStream_t s) {
         l.src = a.src;
         l.out_f32 = a.out_f32;
         l.out_u8 = a.out_u8;
+        l.out_u16 = a.out_u16;
         l.out_gy0 = a.out_gy0;
         l.y0 = a.y0;
         l.y1 = a.y1;

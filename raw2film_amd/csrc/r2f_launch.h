@@ -42,6 +42,7 @@ struct FrontArgs {
     DevPlanes dst;
     float* out_f32;
     uint8_t* out_u8;
+    uint16_t* out_u16;  // upto = OUTPUT: the 16-bit form of out_u8 (generic kernel only)
     int out_gy0;
     int y0, y1, W, H_global;
     int use_matrix;
@@ -118,6 +119,7 @@ struct TailArgs {
     DevPlanes src;
     float* out_f32;
     uint8_t* out_u8;
+    uint16_t* out_u16;  // (H, W, 3) uint16: clip(x * 65535, 0, 65535) truncated, from the float out_f32 would hold
     int out_gy0;
     int y0, y1, W, H_global;
     int grain;  // 0/1
@@ -293,6 +295,9 @@ hipError_t launch_histogram_u8(const uint8_t* image, long long n_bytes, uint32_t
 hipError_t launch_burn_sums(const BurnSumsArgs& a, hipStream_t s);
 // r2f_post.hip
 hipError_t launch_resize_area_u8(const uint8_t* src, int H, int W, uint8_t* dst, int out_h, int out_w, hipStream_t s);
+hipError_t launch_resize_area_u16(const uint16_t* src, int H, int W, uint16_t* dst, int out_h, int out_w, hipStream_t s);
+hipError_t launch_lanczos4_u16(const uint16_t* src, int H, int W, uint16_t* dst, int out_h, int out_w, const int* xofs, const float* xcoef,
+                               const int* yofs, const float* ycoef, hipStream_t s);
 hipError_t launch_stream_copy(const void* src, void* dst, long long bytes, hipStream_t s);
 hipError_t launch_decode_u16(const uint16_t* src, long long n, int ch, float divisor, float factor, float* dst, hipStream_t s);
 // The auto-exposure record of the context (exposure_finish_kernel writes it, decode_u16_auto_kernel reads the factor): 16 bytes.

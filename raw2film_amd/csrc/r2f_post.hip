@@ -1,4 +1,5 @@
 // r2f_post.hip -- what sits after the path on the caller's side, kept on the device:
+//   resize_area_u16 / lanczos4_u16: the same two steps on a 16-bit result (output_bits = 16)
 //   resize_area_u8     cpu_processor.py:411-412 -> utils.resolution_scaling -> cv.resize(uint8 canvas, INTER_AREA): the CPU
 //                      processor's final shrink of the rendered (and canvas-framed) uint8 frame to the requested resolution
 //   blit_rgba8         shaders/copy_to_int.wgsl (bound by gpu_processor.py:1416-1539): the display-referred float frame
@@ -55,31 +56,68 @@ __device__ __forceinline__ uint8_t sat_u8(float v) {  // saturate_cast<uchar>(fl
     return (uint8_t)min(max(r, 0), 255);
 }
 
-struct AreaU8Args {
-    const uint8_t* src;
-    uint8_t* dst;
+__device__ __forceinline__ uint16_t sat_u16(float v) {  // saturate_cast<ushort>(float): the same rounding, the wider clamp
+    const int r = __float2int_rn(v);
+    return (uint16_t)min(max(r, 0), 65535);
+}
+template <typename T>
+__device__ __forceinline__ T sat_as(float v) {
+    if constexpr (sizeof(T) == 1)
+        return sat_u8(v);
+    else
+        return sat_u16(v);
+}
+
+// T = uint8_t, or uint16_t for the 16-bit output (cv.resize(uint16, INTER_AREA): the same structure with saturate_cast<ushort>;
+// the block sums of the integer factors are float sums there, as OpenCV's are -- a uint8 block sum is exact either way)
+template <typename T>
+struct AreaArgs {
+    const T* src;
+    T* dst;
     int H, W, out_h, out_w;
 };
 
-__global__ __launch_bounds__(256) void resize_area_u8_kernel(const AreaU8Args a) {
+template <typename T>
+__global__ __launch_bounds__(256) void resize_area_int_kernel(const AreaArgs<T> a) {
 #pragma clang fp contract(off)
     const int dx = blockIdx.x * 64 + threadIdx.x, dy = blockIdx.y * 4 + threadIdx.y;
     if (dx >= a.out_w || dy >= a.out_h) return;
     const double sx = (double)a.W / a.out_w, sy = (double)a.H / a.out_h;
     const int isx = (int)sx, isy = (int)sy;
-    uint8_t* o = a.dst + ((long long)dy * a.out_w + dx) * 3;
+    T* o = a.dst + ((long long)dy * a.out_w + dx) * 3;
     if ((double)isx == sx && (double)isy == sy) {  // resizeAreaFast_
         int sum[3] = {0, 0, 0};
+        if constexpr (sizeof(T) == 2) {
+            if (isx != 2 || isy != 2) {
+                // resizeAreaFast_<ushort, float>: the block's samples in row order, four at a time added as integers and each group
+                // (then each sample that is left) added to a FLOAT sum -- past 256 bright samples that sum rounds, and so must this
+                const int area = isx * isy, area4 = area & ~3;
+                float fsum[3] = {0.f, 0.f, 0.f};
+                int k = 0;
+                for (int y = 0; y < isy; ++y) {
+                    const T* row = a.src + ((long long)(dy * isy + y) * a.W + (long long)dx * isx) * 3;
+                    for (int x = 0; x < isx; ++x) {
+                        for (int c = 0; c < 3; ++c) sum[c] += row[3 * x + c];
+                        ++k;
+                        if (k > area4 || (k & 3) == 0)
+                            for (int c = 0; c < 3; ++c) fsum[c] = fsum[c] + (float)sum[c], sum[c] = 0;
+                    }
+                }
+                const float scale = 1.f / (float)area;
+                for (int c = 0; c < 3; ++c) o[c] = sat_as<T>(fsum[c] * scale);
+                return;
+            }
+        }
         for (int y = 0; y < isy; ++y) {
-            const uint8_t* row = a.src + ((long long)(dy * isy + y) * a.W + (long long)dx * isx) * 3;
+            const T* row = a.src + ((long long)(dy * isy + y) * a.W + (long long)dx * isx) * 3;
             for (int x = 0; x < isx; ++x)
                 for (int c = 0; c < 3; ++c) sum[c] += row[3 * x + c];
         }
         if (isx == 2 && isy == 2) {
-            for (int c = 0; c < 3; ++c) o[c] = (uint8_t)((sum[c] + 2) >> 2);
+            for (int c = 0; c < 3; ++c) o[c] = (T)((sum[c] + 2) >> 2);
         } else {
             const float scale = 1.f / (float)(isx * isy);
-            for (int c = 0; c < 3; ++c) o[c] = sat_u8((float)sum[c] * scale);
+            for (int c = 0; c < 3; ++c) o[c] = sat_as<T>((float)sum[c] * scale);
         }
         return;
     }
@@ -89,7 +127,7 @@ __global__ __launch_bounds__(256) void resize_area_u8_kernel(const AreaU8Args a)
     area_tab(dy, sy, a.H, y0, ny, wfy, wy, wly, hfy, nfy, hly);
     float sum[3] = {0.f, 0.f, 0.f};
     for (int j = 0; j < ny; ++j) {
-        const uint8_t* row = a.src + ((long long)(y0 + j) * a.W + x0) * 3;
+        const T* row = a.src + ((long long)(y0 + j) * a.W + x0) * 3;
         float buf[3] = {0.f, 0.f, 0.f};
         for (int k = 0; k < nx; ++k) {
             const float alpha = area_w(k, hfx, nfx, wfx, wx, wlx);
@@ -104,7 +142,7 @@ __global__ __launch_bounds__(256) void resize_area_u8_kernel(const AreaU8Args a)
             sum[c] = j == 0 ? term : sum[c] + term;
         }
     }
-    for (int c = 0; c < 3; ++c) o[c] = sat_u8(sum[c]);
+    for (int c = 0; c < 3; ++c) o[c] = sat_as<T>(sum[c]);
 }
 
 // ---------------------------------------------------------------------------------------------------- LANCZOS4, float32
@@ -167,6 +205,53 @@ __global__ __launch_bounds__(256) void lanczos4_f32_kernel(const LanczosF32Args 
     p0[0] = acc[0];
     p0[a.dst.plane_stride] = acc[1];
     p0[2 * a.dst.plane_stride] = acc[2];
+}
+
+// ---------------------------------------------------------------------------------------------------- LANCZOS4, uint16
+// cv.resize(uint16 frame, INTER_LANCZOS4): the way back from max_scale for a 16-bit result.  CV_16U takes the float-weight path of
+// the float frame above (the same tables), HResizeLanczos4 then VResizeLanczos4 in float, and ends in saturate_cast<ushort>:
+// round half to even, clamp to [0, 65535].  One lane per output pixel.
+struct LanczosU16Args {
+    const uint16_t* src;  // (H, W, 3)
+    uint16_t* dst;        // (out_h, out_w, 3)
+    int H, W, out_h, out_w;
+    const int* xofs;
+    const float* xcoef;
+    const int* yofs;
+    const float* ycoef;
+};
+
+__global__ __launch_bounds__(256) void lanczos4_u16_kernel(const LanczosU16Args a) {
+#pragma clang fp contract(off)
+    const int dx = blockIdx.x * 64 + threadIdx.x, dy = blockIdx.y * 4 + threadIdx.y;
+    if (dx >= a.out_w || dy >= a.out_h) return;
+    const int sx = a.xofs[dx] - 3, sy = a.yofs[dy] - 3;
+    float wx[8], wy[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) wx[k] = a.xcoef[dx * 8 + k], wy[k] = a.ycoef[dy * 8 + k];
+    float acc[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint16_t* row = a.src + (long long)clampi(sy + k, 0, a.H - 1) * a.W * 3;
+        float h[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint16_t* px = row + (long long)clampi(sx + j, 0, a.W - 1) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float prod = (float)px[c] * wx[j];
+                h[c] = j == 0 ? prod : h[c] + prod;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float prod = h[c] * wy[k];
+            acc[c] = k == 0 ? prod : acc[c] + prod;
+        }
+    }
+    uint16_t* o = a.dst + ((long long)dy * a.out_w + dx) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = sat_u16(acc[c]);
 }
 
 // ---------------------------------------------------------------------------------------------------- preview blit
@@ -497,8 +582,21 @@ hipError_t launch_decode_u16_auto(const uint16_t* src, int H, int W, int ch, lon
 }
 
 hipError_t launch_resize_area_u8(const uint8_t* src, int H, int W, uint8_t* dst, int out_h, int out_w, hipStream_t s) {
-    AreaU8Args a{src, dst, H, W, out_h, out_w};
-    launch_k(resize_area_u8_kernel, dim3((out_w + 63) / 64, (out_h + 3) / 4), dim3(64, 4), 0, s, a);
+    AreaArgs<uint8_t> a{src, dst, H, W, out_h, out_w};
+    launch_k(resize_area_int_kernel<uint8_t>, dim3((out_w + 63) / 64, (out_h + 3) / 4), dim3(64, 4), 0, s, a);
+    return take_launch_status();
+}
+
+hipError_t launch_resize_area_u16(const uint16_t* src, int H, int W, uint16_t* dst, int out_h, int out_w, hipStream_t s) {
+    AreaArgs<uint16_t> a{src, dst, H, W, out_h, out_w};
+    launch_k(resize_area_int_kernel<uint16_t>, dim3((out_w + 63) / 64, (out_h + 3) / 4), dim3(64, 4), 0, s, a);
+    return take_launch_status();
+}
+
+hipError_t launch_lanczos4_u16(const uint16_t* src, int H, int W, uint16_t* dst, int out_h, int out_w, const int* xofs, const float* xcoef,
+                               const int* yofs, const float* ycoef, hipStream_t s) {
+    LanczosU16Args a{src, dst, H, W, out_h, out_w, xofs, xcoef, yofs, ycoef};
+    launch_k(lanczos4_u16_kernel, dim3((out_w + 63) / 64, (out_h + 3) / 4), dim3(64, 4), 0, s, a);
     return take_launch_status();
 }
 

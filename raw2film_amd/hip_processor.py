@@ -28,6 +28,7 @@ import numpy as np
 
 from . import _lib, filmstock, geometry, stencils
 from .context import LOG_EPS, LUT3D_SCALE, HipContext
+from . import tiff
 from .jpeg_stream import JpegBandSink, JpegStaging, app1_segment, deliver
 from .results import ResultBuffers
 
@@ -87,6 +88,21 @@ def plan_bands(H, flags, ha, ma, bands, taper):
     return sorted(set(bounds + cut)), None
 
 
+def check_output_bits(output_bits, dst_texture=None) -> int:
+    """`output_bits` of a render: 8 (upstream's (image * 255).astype(uint8), cpu_processor.py:407) or 16 (the same rule with
+    2 ** 16 - 1); anything else raises before any work starts, and so does 16 with a widget texture, which is RGBA8."""
+    if isinstance(output_bits, (bool, np.bool_)) or not isinstance(output_bits, (int, np.integer)) or int(output_bits) not in (8, 16):
+        raise ValueError(f"output_bits must be 8 or 16, got {output_bits!r}")
+    if int(output_bits) == 16 and dst_texture is not None:
+        raise ValueError("output_bits=16 cannot be combined with dst_texture: the widget texture is RGBA8")
+    return int(output_bits)
+
+
+def _host16(arr):
+    """The host array of a result: the uint16 view of a 16-bit frame (carried as int16, the same bits), else the array itself."""
+    return arr.view(np.uint16) if arr.dtype == np.int16 else arr
+
+
 DEVICE_EXPOSURE = "device"  # exposure="device": the auto exposure of a uint16 frame is measured on the device; also the marker a
                             # payload carries in place of its float `u16_factor`
 
@@ -101,7 +117,8 @@ def exposure_on_device(exposure) -> bool:
 
 
 class PendingFrame:
-    """A frame submitted with HipProcessor.submit_preloaded: `.result()` waits for its download and returns the uint8 array."""
+    """A frame submitted with HipProcessor.submit_preloaded: `.result()` waits for its download and returns the uint8 array (the
+    uint16 one of a frame submitted with output_bits=16)."""
 
     def __init__(self, host, done, array=None):
         self._host, self._done, self._array = host, done, array
@@ -118,7 +135,7 @@ class PendingFrame:
         if self._array is not None:
             return self._array
         self._done.synchronize()
-        return self._host.numpy()
+        return _host16(self._host.numpy())
 
 
 class HipProcessor:
@@ -139,6 +156,8 @@ class HipProcessor:
         self.payload_alpha = bool(payload_alpha)
         self.result_buffers = int(result_buffers)  # 0: process() returns a fresh array; n: views of n pinned buffers in turn (_download)
         self._results = ResultBuffers(lambda shape: torch.empty(shape, dtype=torch.uint8, pin_memory=True))
+        # ... and of the 16-bit results (output_bits=16; int16 holds the bits): a pool of its own, so the pool is keyed by dtype
+        self._results16 = ResultBuffers(lambda shape: torch.empty(shape, dtype=torch.int16, pin_memory=True), np.uint16)
         # process(host array, cache=False) with pinned result buffers streams a large frame through the pipeline in row bands while it
         # is still arriving (_process_streamed): at most this many, of at least 512 rows each (100 MP: 16 bands of 512 rows = 23.3 ms
         # against 24.7 with 8, 27.2 with 4, 24.9 with 24 -- tools/stream_bands_probe.py); 0: upload, render, download one after the other
@@ -170,6 +189,7 @@ class HipProcessor:
 
     def close(self):
         self._results.close()
+        self._results16.close()
         self._stream_bufs = None
         self._jpeg_host = None
         if getattr(self, "_jpeg_staging", None) is not None:
@@ -459,7 +479,7 @@ class HipProcessor:
                 canvas_ratio=1.0, halation_intensity=1.0, halation=True, halation_size=1.0, halation_green_factor=0.4,
                 sharpness=True, sharpening_strength=0.0, sharpening_sigma=1.0, chroma_nr=0, grain=2,
                 highlight_burn=0.0, burn_scale=50.0, half_size=True, cache=True, color_masking=None, max_scale=400.0,
-                seed=None, exposure=None, metadata=None, src_version=None, **_):
+                seed=None, exposure=None, metadata=None, src_version=None, output_bits=8, **_):
         """Load (decoded) frame and render it: np.uint8 (H, W, 3), like cpu_processor.py:414 -- including the CPU processor's
         last step, resolution_scaling of the finished (canvas-framed) frame to the requested resolution (cpu_processor.py:411-412).
         With `dst_texture` (a uint8 (h, w, 4) CUDA tensor standing in for the preview widget's wgpu texture) the call behaves
@@ -472,9 +492,14 @@ class HipProcessor:
         An array `src` that is the array of the previous call is taken for the same frame when a fingerprint of it agrees (shape,
         dtype, address and a checksum of up to 32 evenly spaced rows -- an edit confined to other rows is NOT seen: pass
         cache=False after a partial in-place edit, or `src_version`, any hashable token of the caller's that changes whenever
-        the buffer's content does and then replaces the checksum)."""
+        the buffer's content does and then replaces the checksum).
+        output_bits=16: np.uint16 (H, W, 3) instead -- clip(x * 65535, 0, 65535) truncated, cpu_processor.py:407's rule with
+        2 ** 16 - 1 -- with the whole post-path at 16 bits: the canvas colour c * 257, the LANCZOS4 way back from `max_scale` and
+        the final INTER_AREA as cv.resize applies them to uint16, the result lent from a pinned pool of its own and a large
+        cache=False frame streamed in row bands exactly where an 8-bit one is.  Not with dst_texture (RGBA8)."""
         settings = dict(locals())  # every keyword of the signature (the unknown ones in `_` aside), named nowhere else
         exposure_on_device(exposure)  # (any string but "device" raises before any work starts)
+        settings["output_bits"] = check_output_bits(output_bits, dst_texture)
         self.exposure_rejected = None
         for k in ("self", "src", "negative_film", "grain_size", "grain_sigma", "dst_texture", "histogram_texture", "_"):
             del settings[k]
@@ -655,7 +680,8 @@ class HipProcessor:
 
         final_scaling: "gpu" -- like GpuProcessor, the canvas keeps its size and only a `max_scale` render is scaled back up;
         "cpu" -- like CpuProcessor.process (cpu_processor.py:411-412), the finished frame, canvas included, is scaled to the
-        requested resolution (INTER_AREA down, LANCZOS4 up).  dst_texture / histogram_texture: see process()."""
+        requested resolution (INTER_AREA down, LANCZOS4 up).  dst_texture / histogram_texture, output_bits: see process()."""
+        check_output_bits(settings.get("output_bits", 8), dst_texture)
         self.exposure_rejected = None
         if dst_texture is None and histogram_texture is None and self.stream_bands > 1:
             res = self._stream_payload(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, **settings)
@@ -762,6 +788,90 @@ class HipProcessor:
                                        **settings)
         return deliver(self._encode_device(out_u8, q, *opts, progressive=prog), file)
 
+    # ------------------------------------------------------------------ TIFF export (8 or 16 bits per sample)
+    def process_tiff(self, src, negative_film, grain_size, grain_sigma, file=None, *, output_bits=16, icc_profile=b"", stream=False,
+                     **params):
+        """The export of one frame at full depth: process()'s render with the same keywords -- the pixels
+        process(..., output_bits=output_bits) returns for them -- as a baseline TIFF 6.0 file (tiff.py: little-endian, uncompressed,
+        chunky RGB, 8 or 16 bits per sample, `icc_profile` bytes in tag 34675).  Returns the file's bytes, or with `file` (a path or
+        a binary file object) their count.  Like process_jpeg it takes no textures, extracts and uploads its frame afresh and
+        leaves the frame a preview keeps on the device alone.
+        stream=True: the file is the one-piece file of process(src, cache=False, output_bits=..., ...)'s pixels.  A large host frame
+        that process(cache=False) streams goes through the same row bands: the header (every offset is known in advance) is written
+        first, then each band's finished rows go down and into the file while later bands arrive.  A frame that does not stream
+        is exported in one piece, and `stream_rejected` says why.  A file past a classic TIFF's 4 GiB raises ValueError."""
+        bits = check_output_bits(output_bits)
+        icc = tiff.check_icc(icc_profile)
+        exposure_on_device(params.get("exposure"))
+        self.exposure_rejected = self.stream_rejected = None
+        for k in ("dst_texture", "histogram_texture"):
+            if params.pop(k, None) is not None:
+                raise ValueError(f"process_tiff writes a file: {k} is not taken (use process() for the preview)")
+        bound = inspect.signature(HipProcessor.process).bind(self, src, negative_film, grain_size, grain_sigma, output_bits=bits, **params)
+        bound.apply_defaults()
+        settings = {k: v for k, v in bound.arguments.items()
+                    if k not in ("self", "src", "negative_film", "grain_size", "grain_sigma", "dst_texture", "histogram_texture", "_")}
+        load = {k: settings[k] for k in _LOAD_KEYWORDS}
+        if stream:  # process(cache=False)'s gates, in its order
+            self.stream_rejected = ("profile_stages is on" if getattr(self, "profile_stages", False) else
+                                    host_stream_gate(src, self.stream_bands, settings["rotation"], settings["chroma_nr"],
+                                                     settings["canvas_mode"], settings["highlight_burn"]))
+        payload = self.extract_image_data_cpu(src, **load, _internal=True)
+        if stream and self.stream_rejected is None:
+            res = self._stream_tiff(payload, negative_film, grain_size, grain_sigma, "cpu", icc, file, settings)
+            if res is not None:
+                return res
+        image, layout = self._upload_payload(payload)
+        out = self._render_prepared(image, layout, payload, negative_film, grain_size, grain_sigma, None, None, "cpu", **settings)
+        return tiff.deliver(self._download(out), icc, file)
+
+    def process_preloaded_tiff(self, cpu_payload, negative_film, grain_size, grain_sigma, file=None, final_scaling="gpu", *,
+                               output_bits=16, icc_profile=b"", stream=False, **settings):
+        """The batch export on the two-phase API: process_preloaded's render of a phase-1 payload as a TIFF file like
+        process_tiff's.  The processor's device frame is left alone.  stream=True: a payload process_preloaded streams in row bands
+        is written band by band (else `stream_rejected` says why not)."""
+        settings["output_bits"] = check_output_bits(output_bits)
+        icc = tiff.check_icc(icc_profile)
+        self.exposure_rejected = self.stream_rejected = None
+        for k in ("dst_texture", "histogram_texture"):
+            if settings.pop(k, None) is not None:
+                raise ValueError(f"process_preloaded_tiff writes a file: {k} is not taken")
+        if stream:
+            self.stream_rejected = None if self.stream_bands > 1 else f"stream_bands = {self.stream_bands}"
+            if self.stream_rejected is None:
+                res = self._stream_tiff(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, icc, file, settings)
+                if res is not None:
+                    return res
+        image, layout = self._upload_payload(cpu_payload)
+        out = self._render_prepared(image, layout, cpu_payload, negative_film, grain_size, grain_sigma, None, None, final_scaling,
+                                    **settings)
+        return tiff.deliver(self._download(out), icc, file)
+
+    def _stream_tiff(self, payload, negative_film, grain_size, grain_sigma, final_scaling, icc, file, settings):
+        """_stream_payload with a TIFF sink: the same bands and stage calls; the header first, then every band's rows into the file
+        behind their download (tiff.TiffBandSink).  Returns the file's bytes (file=None) or their count, or None (with
+        `stream_rejected` saying why) when the payload does not qualify."""
+        plan = self._stream_plan(payload, negative_film, grain_size, grain_sigma, final_scaling, settings)
+        if plan is None:
+            return None
+        host, p, bounds, bufs, ha, ma = plan
+        H, W = bufs["shape"][:2]
+        bits = settings.get("output_bits", 8)
+        head, tplan = tiff.header(H, W, bits, icc)  # (refuses a file past 4 GiB before any band runs)
+        pool = self._results16 if bits == 16 else self._results
+        target, give_back = pool.borrow((H, W, 3), lease=self._lease_result16 if bits == 16 else self._lease_result)
+        sink = tiff.TiffBandSink(target, head, tplan, file, give_back)
+        try:
+            self._run_bands(host, payload, p, bounds, bufs, ha, ma, sink, bits=bits)
+            self._collect_auto_exposure()
+            res = sink.finish()
+        except BaseException:
+            self._torch.cuda.synchronize(self.device)
+            sink.abandon()
+            raise
+        self.last_output = bufs["u16out" if bits == 16 else "u8"]
+        return res
+
     def _encode_device(self, image_u8, quality, subsampling=2, optimize=False, exif=b"", progressive=False):
         """A uint8 (H, W, 3) device frame -> the JPEG file's bytes.  The encoder runs on the current stream; reading its 8-byte
         length back is the one synchronisation (optimize and progressive add one for the symbol counts), then only the file crosses PCIe, into a
@@ -811,9 +921,13 @@ class HipProcessor:
             return None
         host, p, bounds, bufs, ha, ma = plan
         H, W = bufs["shape"][:2]
-        sink = self._results.sink((H, W, 3), self.result_buffers, lease=self._lease_result)
+        bits = settings.get("output_bits", 8)
+        if bits == 16:
+            sink = self._results16.sink((H, W, 3), self.result_buffers, lease=self._lease_result16)
+        else:
+            sink = self._results.sink((H, W, 3), self.result_buffers, lease=self._lease_result)
         try:
-            self._run_bands(host, payload, p, bounds, bufs, ha, ma, sink)
+            self._run_bands(host, payload, p, bounds, bufs, ha, ma, sink, bits=bits)
             self._collect_auto_exposure()
         except BaseException:
             # a stage call refused (or the caller interrupted): let the queued work drain, hand a lent buffer back, pass it on
@@ -822,8 +936,8 @@ class HipProcessor:
             raise
         # (the frame kept on the device for re-renders -- a preview's, typically -- is left alone: an export in between does not cost
         # the preview its cached frame, which the one-after-the-other path has to overwrite because it works in it)
-        self.last_output = bufs["u8"]
-        return sink.finish()
+        self.last_output = bufs["u16out" if bits == 16 else "u8"]
+        return _host16(sink.finish())
 
     def _stream_plan(self, payload, negative_film, grain_size, grain_sigma, final_scaling, settings):
         """Qualify a payload for the row-band path and set its frame up: (host tensor, frame params, band bounds, device buffers,
@@ -845,7 +959,7 @@ class HipProcessor:
         bounds, self.stream_rejected = plan_bands(H, int(params.flags), ha, ma, self.stream_bands, self.stream_taper)
         if bounds is None:
             return None
-        bufs = self._stream_buffers(host, mtf, H, W)
+        bufs = self._stream_buffers(host, mtf, H, W, settings.get("output_bits", 8))
         p = _lib.Params.from_buffer_copy(params)
         p.flags |= _lib.F_FRAME_RESIDENT  # the seed is written once, here; the stage calls read it from the frame block
         self.ctx.write_frame_params(p)     # (and the exposure-range record starts empty)
@@ -878,7 +992,7 @@ class HipProcessor:
         self.last_output = bufs["u8"]
         return res
 
-    def _stream_buffers(self, host, mtf, H, W):
+    def _stream_buffers(self, host, mtf, H, W, bits=8):
         """The device buffers a streamed H x W frame works in (kept for the next frame of the same kind): `host` is its payload tensor
         (the frame itself, or the whole uint16 frame the pipeline takes a window of)."""
         torch = self._torch
@@ -886,15 +1000,19 @@ class HipProcessor:
         bufs = getattr(self, "_stream_bufs", None)
         if bufs is None or bufs["shape"] != (H, W, chans) or bufs["mtf"] != mtf:
             bufs = self._stream_bufs = {"shape": (H, W, chans), "mtf": mtf,
-                                        "image": torch.empty((H, W, chans), dtype=torch.float32, device=self.device),
-                                        "u8": torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)}
+                                        "image": torch.empty((H, W, chans), dtype=torch.float32, device=self.device)}
             for k in ("E", "D", "D2") if mtf else ("E", "D"):
                 bufs[k] = torch.empty((3, H, W), dtype=torch.float32, device=self.device)
         if host.dtype == torch.int16 and (bufs.get("u16") is None or tuple(bufs["u16"].shape) != tuple(host.shape)):
             bufs["u16"] = torch.empty(tuple(host.shape), dtype=torch.int16, device=self.device)
+        # the result at the width this frame asks for, made when a frame first asks for it (int16 holds the bits of a 16-bit one)
+        if bits == 16 and bufs.get("u16out") is None:
+            bufs["u16out"] = torch.empty((H, W, 3), dtype=torch.int16, device=self.device)
+        if bits == 8 and bufs.get("u8") is None:
+            bufs["u8"] = torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)
         return bufs
 
-    def _run_bands(self, host, payload, p, bounds, bufs, ha, ma, sink, band_done=None):
+    def _run_bands(self, host, payload, p, bounds, bufs, ha, ma, sink, band_done=None, bits=8):
         """_stream_payload's band loop (see _process_streamed): every stage runs a band as soon as the rows it reads exist (a stencil
         stage reads into the band after its own), and the tail's rows go back into `sink` -- or, with `band_done`, band_done(b) is
         called instead once band b's tail is queued (on the launching stream; the JPEG export's sink)."""
@@ -903,7 +1021,7 @@ class HipProcessor:
         hal, mtf, grain = (bool(p.flags & f) for f in (_lib.F_HALATION, _lib.F_MTF, _lib.F_GRAIN))
         pointwise = not (hal or mtf or grain)
         is_u16 = host.dtype == torch.int16
-        image, E, D, out_u8 = bufs["image"], bufs["E"], bufs["D"], bufs["u8"]
+        image, E, D, out_u8 = bufs["image"], bufs["E"], bufs["D"], bufs["u16out" if bits == 16 else "u8"]  # (the result, either width)
         landing = bufs["u16"] if is_u16 else image
         # exposure="device": the whole uint16 frame goes up (the statistic is the whole frame's), the bands are rows of its window --
         # band k travels as the frame rows `ub[k]:ub[k + 1]`, the first and the last taking the rows above and below the window along
@@ -960,6 +1078,10 @@ class HipProcessor:
                     ctx.decode_u16(landing[a0:a1], payload["u16_factor"], out=rows)
                 elif payload.get("clip_on_device"):
                     rows.clamp_(0.0, 65504.0)  # np.clip(image, 0, 65504) of gpu_processor.py:275, band by band
+                if pointwise and bits == 16:
+                    ctx.stage_front16(rows, p, in_gy0=a0, out_u16=out_u8, out_gy0=0, y0=a0, y1=a1, H_global=H)
+                    send_back(k)
+                    continue
                 if pointwise:  # LUTs only: one fused pass per band, straight to uint8
                     ctx.stage_front(rows, p, 2, in_gy0=a0, out_u8=out_u8, out_gy0=0, y0=a0, y1=a1, H_global=H)
                     send_back(k)
@@ -986,7 +1108,10 @@ class HipProcessor:
                         sharp, moved = sharp + 1, True
                     if tail < (sharp if mtf else dens):
                         y0, y1 = bounds[tail], bounds[tail + 1]
-                        ctx.stage_tail(bufs["D2"] if mtf else D, p, src_gy0=0, out_u8=out_u8, out_gy0=0, y0=y0, y1=y1, H_global=H)
+                        if bits == 16:
+                            ctx.stage_tail16(bufs["D2"] if mtf else D, p, src_gy0=0, out_u16=out_u8, out_gy0=0, y0=y0, y1=y1, H_global=H)
+                        else:
+                            ctx.stage_tail(bufs["D2"] if mtf else D, p, src_gy0=0, out_u8=out_u8, out_gy0=0, y0=y0, y1=y1, H_global=H)
                         send_back(tail)
                         tail, moved = tail + 1, True
         finally:
@@ -996,6 +1121,10 @@ class HipProcessor:
     def _lease_result(self, shape):
         """A pinned buffer of `shape` to lend out as a result, or None when three are out (every lease goes through here)."""
         return self._results.lease(shape)
+
+    def _lease_result16(self, shape):
+        """_lease_result for a 16-bit result: the pool is keyed by dtype as well as shape."""
+        return self._results16.lease(shape)
 
     def _copy_streams(self):
         """(host-to-device, device-to-host) copy streams of this processor, made on first use."""
@@ -1008,13 +1137,15 @@ class HipProcessor:
         """The uint8 result as a NumPy array (results.py): with result_buffers = n > 0 a view of one of n pinned buffers (24 MP: 1.5
         instead of 6 ms to come down); else the caller's own array, from 3 M samples up a lent pinned buffer (2.7 instead of 7.8 ms)."""
         sink = None
+        wide = out_u8.dtype == self._torch.int16  # a 16-bit result: the same ways back, from the pool of its own dtype
         if self.result_buffers > 0 or out_u8.numel() >= (3 << 20):
-            sink = self._results.sink(tuple(out_u8.shape), self.result_buffers, staged=False, lease=self._lease_result)
+            sink = (self._results16 if wide else self._results).sink(tuple(out_u8.shape), self.result_buffers, staged=False,
+                                                                      lease=self._lease_result16 if wide else self._lease_result)
         if sink is None:
-            return out_u8.cpu().numpy()
+            return _host16(out_u8.cpu().numpy())
         sink.target.copy_(out_u8, non_blocking=True)
         sink.band_back(self._torch.cuda.current_stream(self.device), 0, int(out_u8.shape[0]))
-        return sink.finish()
+        return _host16(sink.finish())
 
     def _payload_tensor(self, cpu_payload):
         """The payload's frame as a torch tensor: float32, or the 16 bits of a uint16 frame (as int16: same bytes)."""
@@ -1032,6 +1163,7 @@ class HipProcessor:
         process_preloaded's return value.  Keeping one frame pending while the next one is submitted overlaps both PCIe
         directions with the render (raw2film_amd.sharding.BatchSharder.run(..., collect=...) does exactly that) -- what the
         reference's queue.write_texture / read_texture pair serialises."""
+        check_output_bits(settings.get("output_bits", 8))
         torch = self._torch
         self.exposure_rejected = None
         src = cpu_payload.get("image_array")
@@ -1065,7 +1197,7 @@ class HipProcessor:
         rendered = compute.record_event()
         with torch.cuda.stream(down):
             down.wait_event(rendered)
-            host = torch.empty(out_u8.shape, dtype=torch.uint8, pin_memory=True)
+            host = torch.empty(out_u8.shape, dtype=out_u8.dtype, pin_memory=True)
             host.copy_(out_u8, non_blocking=True)
             out_u8.record_stream(down)
             done = down.record_event()
@@ -1126,6 +1258,8 @@ class HipProcessor:
                 raise ValueError("histogram_texture needs dst_texture (gpu_processor.py:1883: the histogram is only drawn on the "
                                  "destination-texture branch)")
         torch = self._torch  # noqa: F841
+        if check_output_bits(settings.get("output_bits", 8), dst_texture) == 16:
+            return self._render_prepared16(image, layout, cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, **settings)
         out_f32, out_u8 = self._execute_pipeline(image, negative_film, grain_size, grain_sigma, want_f32=dst_texture is not None,
                                                  want_u8=True, layout=layout, **settings)
         self._collect_auto_exposure()
@@ -1162,6 +1296,34 @@ class HipProcessor:
         self.last_output = out_u8
         return out_u8
 
+    def _render_prepared16(self, image, layout, cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, **settings):
+        """_render_prepared's bitmap branch at 16 bits: r2f_render16, then the same post-path on the uint16 frame (an int16 tensor
+        holds its bits) -- the canvas colour c * 257 (255 -> 65535), cv.resize(uint16, ...) for the two scalings."""
+        torch = self._torch
+        _, out = self._execute_pipeline(image, negative_film, grain_size, grain_sigma, want_f32=False, want_u8=False, layout=layout,
+                                        **settings)
+        self._collect_auto_exposure()
+        mode = settings.get("canvas_mode", "No")
+        if mode != "No":  # effects.add_canvas (effects.py:336-357) on the 16-bit frame: a paste, no arithmetic
+            shape, color, (oy, ox) = geometry.canvas_layout(out.shape, mode, settings.get("canvas_scale", 1.0),
+                                                            settings.get("canvas_ratio", 1.0))
+            if oy < 0 or ox < 0:
+                raise ValueError("canvas smaller than the frame (canvas_scale < 1)")
+            canvas = torch.empty((shape[0], shape[1], 3), dtype=torch.int16, device=out.device)
+            canvas[...] = torch.from_numpy((np.asarray(color, dtype=np.uint16) * np.uint16(257)).view(np.int16)).to(out.device)
+            canvas[oy:oy + int(out.shape[0]), ox:ox + int(out.shape[1])] = out
+            out = canvas
+        target = cpu_payload.get("final_resolution") if final_scaling == "cpu" else cpu_payload.get("upscale_to")
+        if target:  # cpu_processor.py:411-412 -> utils.resolution_scaling (utils.py:226-244) on the uint16 frame
+            f = min(target[0] / out.shape[0], target[1] / out.shape[1])
+            size = (round(out.shape[0] * f), round(out.shape[1] * f))
+            if f > 1:
+                out = self.ctx.resize_lanczos4_u16(out.contiguous(), *size)
+            elif f < 1 and final_scaling == "cpu":
+                out = self.ctx.resize_area_u16(out.contiguous(), *size)
+        self.last_output = out
+        return out
+
     def _collect_auto_exposure(self, now=False):
         """exposure="device": once the frame is queued, the stops the device measured come back into `last_auto_exposure` (the wait
         is for the finish kernel behind the upload, not for the render).  submit_preloaded's frame in flight leaves the read to the
@@ -1193,18 +1355,25 @@ class HipProcessor:
             image = self.last_output
             if image is None:
                 raise ValueError("generate_histogram(): no frame has been rendered yet")
+            if image.dtype == self._torch.int16:
+                # a 16-bit render: v // 257 is the bin of the 8-bit render of the same float (both truncate), counted on the device
+                image = torch_div257(self._torch, image)
         return histogram.generate_histogram(image, histogram.MIX_TABLE if mix_table is None else mix_table, height,
                                             ctx=self.ctx)
 
     def process_array(self, image, negative_film, grain_size=6, grain_sigma=0.4, *, colorspace="XYZ", seed=None,
-                      return_float=False, output="host", out=None, **settings):
+                      return_float=False, output="host", out=None, output_bits=8, **settings):
         """Render a decoded frame given as an array / CUDA tensor (synthetic benchmark frames).
 
         colorspace: "XYZ" (S0 skipped) or "linear-rec709" (S0 = data.py:128-135).
         return_float: float32 display-referred (H, W, 3) instead of uint8.  output: "host" | "device".
         out: a device tensor (H, W, 3) of the result's dtype to render into (a stream of frames then keeps its buffers, and
         r2f_render its captured graph).
+        output_bits=16: the uint16 result of r2f_render16 (clip(x * 65535, 0, 65535) truncated) instead of uint8; with
+        output="device" the device tensor (torch.uint16).  Not together with return_float.
         """
+        if check_output_bits(output_bits) == 16 and return_float:
+            raise ValueError("output_bits=16 and return_float=True name two different results")
         torch = self._torch
         if colorspace not in ("XYZ", "linear-rec709"):
             raise ValueError("colorspace must be 'XYZ' or 'linear-rec709'")
@@ -1213,15 +1382,20 @@ class HipProcessor:
         image = image.to(self.device).contiguous()
         if out is not None:
             _, H, W = self.ctx.layout_of(image, settings.get("layout"))
-            want = torch.float32 if return_float else torch.uint8
+            want = torch.float32 if return_float else torch.uint8 if output_bits == 8 else torch.uint16
+            if output_bits == 16 and isinstance(out, torch.Tensor) and out.dtype == torch.int16:
+                want = torch.int16  # (the same bits)
             if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == want and tuple(out.shape) == (H, W, 3) and out.is_contiguous()):
                 raise ValueError(f"out must be a contiguous {want} CUDA tensor of shape {(H, W, 3)}")
         f32, u8 = self._execute_pipeline(
             image, negative_film, grain_size, grain_sigma, want_f32=return_float, want_u8=not return_float,
             matrix=REC709_TO_XYZ if colorspace == "linear-rec709" else None, seed=seed,
-            out_f32=out if return_float else None, out_u8=None if return_float else out, **settings,
+            out_f32=out if return_float else None, out_u8=None if return_float else out, output_bits=output_bits, **settings,
         )
         out = f32 if return_float else u8
+        if output_bits == 16:
+            out = out.view(torch.uint16)
+            return out if output == "device" else out.view(torch.int16).cpu().numpy().view(np.uint16)
         return out if output == "device" else out.cpu().numpy()
 
     # ------------------------------------------------------------------ device pipeline
@@ -1274,7 +1448,15 @@ class HipProcessor:
         single command encoder and submit (gpu_processor.py:1760, 1877); the per-render seed travels in a device-side block."""
         _, H, W = self.ctx.layout_of(image, layout)
         params = self.prepare(negative_film, grain_size, grain_sigma, (W, H), **settings)
+        if settings.get("output_bits", 8) == 16:  # -> (out_f32 or None, the 16-bit frame); out_u8 names the caller's 16-bit buffer
+            return self.ctx.render16(image, params, out_f32=out_f32, out_u16=out_u8, want_f32=want_f32, layout=layout)
         return self.ctx.render(image, params, out_f32=out_f32, out_u8=out_u8, want_f32=want_f32, want_u8=want_u8, layout=layout)
+
+
+def torch_div257(torch, image16):
+    """uint8 v // 257 of a 16-bit device frame (int16 or uint16 holding uint16 bits): the 8-bit render's value of every sample."""
+    v = image16.view(torch.int16).to(torch.int32) & 0xFFFF
+    return torch.div(v, 257, rounding_mode="floor").to(torch.uint8).contiguous()
 
 
 _LOAD_KEYWORDS = tuple(inspect.signature(HipProcessor.load_image_texture).parameters)[2:]  # (self, src, then these)

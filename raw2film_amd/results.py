@@ -33,7 +33,8 @@ class ResultSink:
         self.per_band = fresh is not None  # (the fresh array is filled band by band as the bands land)
         self._done, self._copies, self._touched = None, [], []
         if fresh is not None:
-            self._staged, flat = np.asarray(target), fresh.reshape(-1)
+            # (bytes: a page is touched once whatever the sample width; a 16-bit frame is staged as int16 holding the same bits)
+            self._staged, flat = np.asarray(target).view(fresh.dtype), fresh.reshape(-1).view(np.uint8)
             self._part = -(-flat.size // TOUCH_PARTS)
             self._touched = [pool.submit(touch, flat, i, min(i + self._part, flat.size)) for i in range(0, flat.size, self._part)]
 
@@ -44,7 +45,7 @@ class ResultSink:
 
     def _copy_out(self, done, y0, y1):
         done.synchronize()  # (releases the GIL)
-        row = self._fresh[0].size
+        row = self._fresh[0].nbytes
         # a late touch must not zero a page this copy has filled: wait for the parts that hold these rows (queued before any copy,
         # the touches are running or done by now)
         for t in self._touched[y0 * row // self._part:(y1 * row - 1) // self._part + 1]:
@@ -70,10 +71,13 @@ class ResultSink:
 
 
 class ResultBuffers:
-    """The host buffers of one processor's results; `alloc(shape)` makes a pinned uint8 buffer."""
+    """The host buffers of one processor's results of one sample type; `alloc(shape)` makes a pinned buffer of it (uint8, or the 16
+    bits of a uint16 result) and `dtype` is what a fresh array is made of.  A processor keeps one of these per dtype: a lent 8-bit
+    buffer never comes back as a 16-bit result, nor the other way round."""
 
-    def __init__(self, alloc):
+    def __init__(self, alloc, dtype=np.uint8):
         self._alloc = alloc
+        self._dtype = dtype
         self._ring, self._turn = [], 0
         self._lease_shape, self._free, self._made = None, [], 0
         self._stage, self._pool = None, None
@@ -109,7 +113,18 @@ class ResultBuffers:
             self._stage = self._alloc(shape)
         if self._pool is None:
             self._pool = ThreadPoolExecutor(max_workers=TOUCH_PARTS, thread_name_prefix="r2f-result")
-        return ResultSink(self._stage, fresh=np.empty(shape, np.uint8), pool=self._pool)
+        return ResultSink(self._stage, fresh=np.empty(shape, self._dtype), pool=self._pool)
+
+    def borrow(self, shape, lease=None):
+        """(buffer, give_back) for a caller that fills a whole frame and is done with it before it returns (the TIFF export writes it
+        to the file): a lent buffer and how it goes back into the pool, or -- when LEASES of them are out -- the pool's staging buffer,
+        which sink() keeps for the same case, and None."""
+        leased = (lease or self.lease)(shape)
+        if leased is not None:
+            return leased, self._free.append
+        if self._stage is None or tuple(self._stage.shape) != shape:
+            self._stage = self._alloc(shape)
+        return self._stage, None
 
     def close(self):
         if self._pool is not None:
