@@ -243,114 +243,94 @@ class HipContext:
             self._workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return self._workspace
 
-    def render(self, image, params, out_f32=None, out_u8=None, want_f32=True, want_u8=False, layout=None):
-        """Full pipeline on one frame: S0..S8 (+S9).  Returns (out_f32, out_u8) device tensors (H, W, 3)."""
-        torch = self._torch
-        self._check_image(image)
-        layout, H, W = self.layout_of(image, layout)
-        if out_f32 is None and want_f32:
-            out_f32 = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
-        if out_u8 is None and want_u8:
-            out_u8 = torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)
-        self._check_out(out_f32, torch.float32, W, "out_f32", rows=H)
-        self._check_out(out_u8, torch.uint8, W, "out_u8", rows=H)
-        nbytes = self.workspace_bytes(params, H, W)
-        ws = self._get_workspace(nbytes)
-        rc = self._lib.r2f_render(
-            self._h, C.byref(params), image.data_ptr(), layout,
-            out_f32.data_ptr() if out_f32 is not None else None,
-            out_u8.data_ptr() if out_u8 is not None else None,
-            H, W, ws.data_ptr() if ws is not None else None, nbytes, self._stream(),
-        )
-        self._check(rc)
-        return out_f32, out_u8
+    def _check_outs(self, W, out_f32=None, out_u8=None, out_u16=None, **kw):
+        """The output tensors of a call, each checked like _check_out, -> their pointers (None for one that is not asked for)."""
+        self._check_out(out_f32, self._torch.float32, W, "out_f32", **kw)
+        self._check_out(out_u8, self._torch.uint8, W, "out_u8", **kw)
+        self._check_out16(out_u16, W, "out_u16", **kw)
+        return [t.data_ptr() if t is not None else None for t in (out_f32, out_u8, out_u16)]
 
-    # ------------------------------------------------------------------ 16-bit output (r2f_render16 and the stage calls beside it)
     def _check_out16(self, t, W, what, **kw):
         """A 16-bit output tensor: uint16, or int16 holding the same bits (torch's uint16 knows few operations)."""
         if t is not None and t.dtype not in (self._torch.int16, self._torch.uint16):
             raise ValueError(f"{what} must be a contiguous 16-bit CUDA tensor of shape (rows, {int(W)}, 3)")
         self._check_out(t, None if t is None else t.dtype, W, what, **kw)
 
-    def render16(self, image, params, out_f32=None, out_u16=None, want_f32=False, layout=None):
-        """render() with the 16-bit result of r2f_render16: clip(x * 65535, 0, 65535) truncated, from the float out_f32 holds.
-        Returns (out_f32 or None, out_u16): device tensors (H, W, 3); out_u16 is int16 holding the uint16 bits unless one is given."""
+    def _render(self, wide, image, params, out_f32, out, want_f32, want_out, layout):
+        """render / render16: r2f_render with the uint8 result, or (`wide`) r2f_render16 with the 16-bit one."""
         torch = self._torch
         self._check_image(image)
         layout, H, W = self.layout_of(image, layout)
         if out_f32 is None and want_f32:
             out_f32 = torch.empty((H, W, 3), dtype=torch.float32, device=self.device)
-        if out_u16 is None:
-            out_u16 = torch.empty((H, W, 3), dtype=torch.int16, device=self.device)
-        self._check_out(out_f32, torch.float32, W, "out_f32", rows=H)
-        self._check_out16(out_u16, W, "out_u16", rows=H)
+        if out is None and want_out:
+            out = torch.empty((H, W, 3), dtype=torch.int16 if wide else torch.uint8, device=self.device)
+        if wide:
+            fn, (p32, _, p_out) = self._lib.r2f_render16, self._check_outs(W, out_f32, out_u16=out, rows=H)
+        else:
+            fn, (p32, p_out, _) = self._lib.r2f_render, self._check_outs(W, out_f32, out_u8=out, rows=H)
         nbytes = self.workspace_bytes(params, H, W)
         ws = self._get_workspace(nbytes)
-        self._check(self._lib.r2f_render16(
-            self._h, C.byref(params), image.data_ptr(), layout, out_f32.data_ptr() if out_f32 is not None else None,
-            out_u16.data_ptr(), H, W, ws.data_ptr() if ws is not None else None, nbytes, self._stream()))
-        return out_f32, out_u16
+        self._check(fn(self._h, C.byref(params), image.data_ptr(), layout, p32, p_out, H, W,
+                       ws.data_ptr() if ws is not None else None, nbytes, self._stream()))
+        return out_f32, out
+
+    def render(self, image, params, out_f32=None, out_u8=None, want_f32=True, want_u8=False, layout=None):
+        """Full pipeline on one frame: S0..S8 (+S9).  Returns (out_f32, out_u8) device tensors (H, W, 3)."""
+        return self._render(False, image, params, out_f32, out_u8, want_f32, want_u8, layout)
+
+    # ------------------------------------------------------------------ 16-bit output (r2f_render16 and the stage calls beside it)
+    def render16(self, image, params, out_f32=None, out_u16=None, want_f32=False, layout=None):
+        """render() with the 16-bit result of r2f_render16: clip(x * 65535, 0, 65535) truncated, from the float out_f32 holds.
+        Returns (out_f32 or None, out_u16): device tensors (H, W, 3); out_u16 is int16 holding the uint16 bits unless one is given."""
+        return self._render(True, image, params, out_f32, out_u16, want_f32, True, layout)
 
     def stage_front16(self, image, params, *, in_gy0=0, out_f32=None, out_u16=None, out_gy0=0, y0=None, y1=None, H_global=None,
                       layout=None):
         """stage_front(upto = output) with the 16-bit output (r2f_stage_front16)."""
-        self._check_image(image)
-        layout, rows, W = self.layout_of(image, layout)
-        y0 = in_gy0 if y0 is None else y0
-        y1 = in_gy0 + rows if y1 is None else y1
-        H_global = in_gy0 + rows if H_global is None else H_global
-        self._check_out(out_f32, self._torch.float32, W, "out_f32", gy0=out_gy0, y0=y0, y1=y1)
-        self._check_out16(out_u16, W, "out_u16", gy0=out_gy0, y0=y0, y1=y1)
-        self._check(self._lib.r2f_stage_front16(
-            self._h, C.byref(params), image.data_ptr(), layout, in_gy0, rows, out_f32.data_ptr() if out_f32 is not None else None,
-            out_u16.data_ptr() if out_u16 is not None else None, out_gy0, y0, y1, W, H_global, self._stream()))
+        self._stage_front(image, params, None, in_gy0, None, 0, (out_f32, None, out_u16), out_gy0, y0, y1, H_global, layout)
 
     def stage_tail16(self, density, params, *, src_gy0=0, out_f32=None, out_u8=None, out_u16=None, out_gy0=0, y0, y1, H_global,
                      burn_map=None, field=None, field_gy0=0):
         """stage_tail (or, with `field`, stage_tail_field) with the 16-bit output beside the other two (r2f_stage_tail16,
         r2f_stage_tail_field16)."""
-        pd = self.planes(density, src_gy0)
-        W = int(density.shape[2])
-        self._check_out(out_f32, self._torch.float32, W, "out_f32", gy0=out_gy0, y0=y0, y1=y1)
-        self._check_out(out_u8, self._torch.uint8, W, "out_u8", gy0=out_gy0, y0=y0, y1=y1)
-        self._check_out16(out_u16, W, "out_u16", gy0=out_gy0, y0=y0, y1=y1)
-        outs = [t.data_ptr() if t is not None else None for t in (out_f32, out_u8, out_u16)]
-        if field is not None:
-            pf = self.planes(field, field_gy0)
-            self._check(self._lib.r2f_stage_tail_field16(self._h, C.byref(params), C.byref(pd), C.byref(pf), *outs, out_gy0, y0, y1, W,
-                                                         H_global, self._stream()))
-            return
-        if burn_map is not None:
-            self._check_lowres(burn_map, params, H_global, W, "burn_map")
-        self._check(self._lib.r2f_stage_tail16(self._h, C.byref(params), C.byref(pd),
-                                               burn_map.data_ptr() if burn_map is not None else None, *outs, out_gy0, y0, y1, W,
-                                               H_global, self._stream()))
+        self._stage_tail(True, density, params, src_gy0, (out_f32, out_u8, out_u16), out_gy0, y0, y1, H_global, burn_map, field,
+                         field_gy0)
 
-    def _resize16(self, fn, what, image_u16, out_h, out_w):
+    def _resize_hwc3(self, fn, what, wide, image, out_h, out_w):
+        """The four resamplers of a finished (H, W, 3) frame: uint8, or (`wide`) 16-bit -> a new frame of the same dtype."""
         torch = self._torch
-        if not (isinstance(image_u16, torch.Tensor) and image_u16.is_cuda and image_u16.dtype in (torch.int16, torch.uint16)
-                and image_u16.is_contiguous() and image_u16.dim() == 3 and image_u16.shape[2] == 3):
-            raise ValueError(f"{what} needs a contiguous 16-bit (H, W, 3) CUDA tensor")
-        self._same_device(image_u16, "image")
-        out = torch.empty((int(out_h), int(out_w), 3), dtype=image_u16.dtype, device=self.device)
-        self._check(fn(self._h, image_u16.data_ptr(), int(image_u16.shape[0]), int(image_u16.shape[1]), out.data_ptr(), int(out_h),
-                       int(out_w), self._stream()))
+        dtypes = (torch.int16, torch.uint16) if wide else (torch.uint8,)
+        if not (isinstance(image, torch.Tensor) and image.is_cuda and image.dtype in dtypes and image.is_contiguous()
+                and image.dim() == 3 and image.shape[2] == 3):
+            raise ValueError(f"{what} needs a contiguous {'16-bit' if wide else 'uint8'} (H, W, 3) CUDA tensor")
+        self._same_device(image, "image")
+        out = torch.empty((int(out_h), int(out_w), 3), dtype=image.dtype, device=self.device)
+        self._check(fn(self._h, image.data_ptr(), int(image.shape[0]), int(image.shape[1]), out.data_ptr(), int(out_h), int(out_w),
+                       self._stream()))
         return out
 
     def resize_lanczos4_u16(self, image_u16, out_h: int, out_w: int):
         """cv.resize(uint16 (H, W, 3), (out_w, out_h), interpolation=cv.INTER_LANCZOS4) on the device (int16 tensors: same bits)."""
-        return self._resize16(self._lib.r2f_resize_lanczos4_u16, "resize_lanczos4_u16", image_u16, out_h, out_w)
+        return self._resize_hwc3(self._lib.r2f_resize_lanczos4_u16, "resize_lanczos4_u16", True, image_u16, out_h, out_w)
 
     def resize_area_u16(self, image_u16, out_h: int, out_w: int):
         """cv.resize(uint16 (H, W, 3), (out_w, out_h), interpolation=cv.INTER_AREA), shrinking, on the device."""
-        return self._resize16(self._lib.r2f_resize_area_u16, "resize_area_u16", image_u16, out_h, out_w)
+        return self._resize_hwc3(self._lib.r2f_resize_area_u16, "resize_area_u16", True, image_u16, out_h, out_w)
+
+    def resize_lanczos4_u8(self, image_u8, out_h: int, out_w: int):
+        """cv.resize(uint8 (H, W, 3), (out_w, out_h), interpolation=cv.INTER_LANCZOS4) on the device."""
+        return self._resize_hwc3(self._lib.r2f_resize_lanczos4_u8, "resize_lanczos4_u8", False, image_u8, out_h, out_w)
+
+    def resize_area_u8(self, image_u8, out_h: int, out_w: int):
+        """cv.resize(uint8 (H, W, 3), (out_w, out_h), interpolation=cv.INTER_AREA), shrinking, on the device (utils.py:226-236 as
+        the CPU processor applies it to the finished frame, cpu_processor.py:411-412)."""
+        return self._resize_hwc3(self._lib.r2f_resize_area_u8, "resize_area_u8", False, image_u8, out_h, out_w)
 
     # ------------------------------------------------------------------ stages (row-shard aware)
-    def stage_front(self, image, params, upto, *, in_gy0=0, dst=None, dst_gy0=0, out_f32=None, out_u8=None,
-                    out_gy0=0, y0=None, y1=None, H_global=None, layout=None, track_range=False):
-        """track_range (upto = exposure): the kernel merges the range of the exposure samples it writes for the halation's FFT
-        channels into the context's exposure-range record, a grid of 64 x 256-pixel tiles (R2F_F_TRACK_RANGE), like r2f_render's
-        front kernel does for a whole frame."""
+    def _stage_front(self, image, params, upto, in_gy0, dst, dst_gy0, outs, out_gy0, y0, y1, H_global, layout, track_range=False):
+        """stage_front (r2f_stage_front: up to stage `upto`, into the planes `dst` or the outputs) and, with upto=None, stage_front16
+        (r2f_stage_front16: the output stage with the 16-bit result); `outs`: (out_f32, out_u8, out_u16)."""
         self._check_image(image)
         if track_range:
             params = _lib.Params.from_buffer_copy(params)
@@ -360,16 +340,21 @@ class HipContext:
         y1 = in_gy0 + rows if y1 is None else y1
         H_global = in_gy0 + rows if H_global is None else H_global
         pl = self.planes(dst, dst_gy0) if dst is not None else None
-        self._check_out(out_f32, self._torch.float32, W, "out_f32", gy0=out_gy0, y0=y0, y1=y1)
-        self._check_out(out_u8, self._torch.uint8, W, "out_u8", gy0=out_gy0, y0=y0, y1=y1)
-        rc = self._lib.r2f_stage_front(
-            self._h, C.byref(params), image.data_ptr(), layout, in_gy0, rows, int(upto),
-            C.byref(pl) if pl is not None else None,
-            out_f32.data_ptr() if out_f32 is not None else None,
-            out_u8.data_ptr() if out_u8 is not None else None,
-            out_gy0, y0, y1, W, H_global, self._stream(),
-        )
-        self._check(rc)
+        p32, p8, p16 = self._check_outs(W, *outs, gy0=out_gy0, y0=y0, y1=y1)
+        head = (self._h, C.byref(params), image.data_ptr(), layout, in_gy0, rows)
+        rows_of = (out_gy0, y0, y1, W, H_global, self._stream())
+        if upto is None:
+            self._check(self._lib.r2f_stage_front16(*head, p32, p16, *rows_of))
+        else:
+            self._check(self._lib.r2f_stage_front(*head, int(upto), C.byref(pl) if pl is not None else None, p32, p8, *rows_of))
+
+    def stage_front(self, image, params, upto, *, in_gy0=0, dst=None, dst_gy0=0, out_f32=None, out_u8=None,
+                    out_gy0=0, y0=None, y1=None, H_global=None, layout=None, track_range=False):
+        """track_range (upto = exposure): the kernel merges the range of the exposure samples it writes for the halation's FFT
+        channels into the context's exposure-range record, a grid of 64 x 256-pixel tiles (R2F_F_TRACK_RANGE), like r2f_render's
+        front kernel does for a whole frame."""
+        self._stage_front(image, params, upto, in_gy0, dst, dst_gy0, (out_f32, out_u8, None), out_gy0, y0, y1, H_global, layout,
+                          track_range)
 
     def stage_front_split(self, image, params, exposure, density, *, in_gy0=0, exposure_gy0=0, density_gy0=0, y0=None, y1=None,
                           H_global=None, layout=None, track_range=False) -> int:
@@ -423,21 +408,28 @@ class HipContext:
     def stage_stencil(self, which, src, dst, *, src_gy0=0, dst_gy0=0, y0, y1, H_global):
         self._stencil_call(self._lib.r2f_stage_stencil, int(which), src, src_gy0, dst, dst_gy0, y0, y1, H_global)
 
-    def stage_tail(self, density, params, *, src_gy0=0, out_f32=None, out_u8=None, out_gy0=0, y0, y1, H_global,
-                   burn_map=None):
+    def _stage_tail(self, wide, density, params, src_gy0, outs, out_gy0, y0, y1, H_global, burn_map=None, field=None, field_gy0=0):
+        """The four tail entry points: r2f_stage_tail, or with a grain `field` r2f_stage_tail_field, each with (`wide`) its ...16
+        twin that takes the 16-bit output beside the other two; `outs`: (out_f32, out_u8, out_u16)."""
         pd = self.planes(density, src_gy0)
         W = int(density.shape[2])
-        self._check_out(out_f32, self._torch.float32, W, "out_f32", gy0=out_gy0, y0=y0, y1=y1)
-        self._check_out(out_u8, self._torch.uint8, W, "out_u8", gy0=out_gy0, y0=y0, y1=y1)
-        if burn_map is not None:
-            self._check_lowres(burn_map, params, H_global, W, "burn_map")
-        rc = self._lib.r2f_stage_tail(
-            self._h, C.byref(params), C.byref(pd), burn_map.data_ptr() if burn_map is not None else None,
-            out_f32.data_ptr() if out_f32 is not None else None,
-            out_u8.data_ptr() if out_u8 is not None else None,
-            out_gy0, y0, y1, W, H_global, self._stream(),
-        )
-        self._check(rc)
+        ptrs = self._check_outs(W, *outs, gy0=out_gy0, y0=y0, y1=y1)
+        if not wide:
+            ptrs = ptrs[:2]  # (r2f_stage_tail and r2f_stage_tail_field take out_f32 and out_u8 only)
+        if field is not None:
+            pf = self.planes(field, field_gy0)
+            fn = self._lib.r2f_stage_tail_field16 if wide else self._lib.r2f_stage_tail_field
+            second = C.byref(pf)
+        else:
+            if burn_map is not None:
+                self._check_lowres(burn_map, params, H_global, W, "burn_map")
+            fn = self._lib.r2f_stage_tail16 if wide else self._lib.r2f_stage_tail
+            second = burn_map.data_ptr() if burn_map is not None else None
+        self._check(fn(self._h, C.byref(params), C.byref(pd), second, *ptrs, out_gy0, y0, y1, W, H_global, self._stream()))
+
+    def stage_tail(self, density, params, *, src_gy0=0, out_f32=None, out_u8=None, out_gy0=0, y0, y1, H_global,
+                   burn_map=None):
+        self._stage_tail(False, density, params, src_gy0, (out_f32, out_u8, None), out_gy0, y0, y1, H_global, burn_map)
 
     def stage_grain_field(self, field, params, *, dst_gy0=0, y0, y1, H_global):
         """The grain field K_g * N for rows [y0, y1) -> (3, rows, W) planes; no image involved."""
@@ -448,13 +440,7 @@ class HipContext:
     def stage_tail_field(self, density, field, params, *, src_gy0=0, field_gy0=0, out_f32=None, out_u8=None, out_gy0=0, y0, y1,
                          H_global):
         """stage_tail with a grain field made by stage_grain_field instead of generating it in the same kernel."""
-        pd, pf = self.planes(density, src_gy0), self.planes(field, field_gy0)
-        self._check_out(out_f32, self._torch.float32, int(density.shape[2]), "out_f32", gy0=out_gy0, y0=y0, y1=y1)
-        self._check_out(out_u8, self._torch.uint8, int(density.shape[2]), "out_u8", gy0=out_gy0, y0=y0, y1=y1)
-        self._check(self._lib.r2f_stage_tail_field(
-            self._h, C.byref(params), C.byref(pd), C.byref(pf),
-            out_f32.data_ptr() if out_f32 is not None else None, out_u8.data_ptr() if out_u8 is not None else None,
-            out_gy0, y0, y1, int(density.shape[2]), H_global, self._stream()))
+        self._stage_tail(False, density, params, src_gy0, (out_f32, out_u8, None), out_gy0, y0, y1, H_global, None, field, field_gy0)
 
     def stage_grain(self, density_in, density_out, params, *, src_gy0=0, dst_gy0=0, y0, y1, H_global):
         """S6 + clip alone (planes -> planes): first half of the tail when S7 is on."""
@@ -553,31 +539,6 @@ class HipContext:
         pd = self.planes(out, 0)
         self._check(self._lib.r2f_warp_affine(self._h, image.data_ptr(), layout, H, W, m.ctypes.data, C.byref(pd), nr, nc, r0, c0,
                                               self._stream()))
-        return out
-
-    def resize_lanczos4_u8(self, image_u8, out_h: int, out_w: int):
-        """cv.resize(uint8 (H, W, 3), (out_w, out_h), interpolation=cv.INTER_LANCZOS4) on the device."""
-        torch = self._torch
-        if not (image_u8.is_cuda and image_u8.dtype == torch.uint8 and image_u8.is_contiguous() and image_u8.dim() == 3
-                and image_u8.shape[2] == 3):
-            raise ValueError("resize_lanczos4_u8 needs a contiguous uint8 (H, W, 3) CUDA tensor")
-        self._same_device(image_u8, "image")
-        out = torch.empty((int(out_h), int(out_w), 3), dtype=torch.uint8, device=self.device)
-        self._check(self._lib.r2f_resize_lanczos4_u8(self._h, image_u8.data_ptr(), int(image_u8.shape[0]), int(image_u8.shape[1]),
-                                                     out.data_ptr(), int(out_h), int(out_w), self._stream()))
-        return out
-
-    def resize_area_u8(self, image_u8, out_h: int, out_w: int):
-        """cv.resize(uint8 (H, W, 3), (out_w, out_h), interpolation=cv.INTER_AREA), shrinking, on the device (utils.py:226-236 as
-        the CPU processor applies it to the finished frame, cpu_processor.py:411-412)."""
-        torch = self._torch
-        if not (image_u8.is_cuda and image_u8.dtype == torch.uint8 and image_u8.is_contiguous() and image_u8.dim() == 3
-                and image_u8.shape[2] == 3):
-            raise ValueError("resize_area_u8 needs a contiguous uint8 (H, W, 3) CUDA tensor")
-        self._same_device(image_u8, "image")
-        out = torch.empty((int(out_h), int(out_w), 3), dtype=torch.uint8, device=self.device)
-        self._check(self._lib.r2f_resize_area_u8(self._h, image_u8.data_ptr(), int(image_u8.shape[0]), int(image_u8.shape[1]),
-                                                 out.data_ptr(), int(out_h), int(out_w), self._stream()))
         return out
 
     def decode_u16(self, image_u16, factor: float, divisor: float = 65535.0, out=None):

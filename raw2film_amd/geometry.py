@@ -106,8 +106,9 @@ def canvas_layout(shape, canvas_mode: str, canvas_scale: float = 1.0, canvas_rat
 
 
 def add_canvas(image, canvas_mode: str, canvas_scale: float = 1.0, canvas_ratio: float = 1.0):
-    """effects.add_canvas (effects.py:336-357) for a uint8 (H, W, 3) NumPy array or torch tensor (any device):
-    the frame pasted at `offset` onto a canvas of the mode's colour."""
+    """effects.add_canvas (effects.py:336-357) for an (H, W, 3) NumPy array or torch tensor (any device) of 8- or 16-bit
+    samples: the frame pasted at `offset` onto a canvas of its own dtype in the mode's colour -- c for a uint8 frame, c * 257
+    (255 -> 65535) for a 16-bit one: NumPy uint16, torch uint16 or int16 holding the same bits.  A paste, no arithmetic."""
     if canvas_mode == "No":
         return image
     out, color, (oy, ox) = canvas_layout(image.shape, canvas_mode, canvas_scale, canvas_ratio)
@@ -115,15 +116,20 @@ def add_canvas(image, canvas_mode: str, canvas_scale: float = 1.0, canvas_ratio:
     if oy < 0 or ox < 0:
         raise ValueError("canvas smaller than the frame (canvas_scale < 1)")
     if isinstance(image, np.ndarray):
-        canvas = np.empty((out[0], out[1], 3), dtype=np.uint8)
-        canvas[...] = np.asarray(color, dtype=np.uint8)
+        wide = image.dtype.itemsize == 2
+        canvas = np.empty((out[0], out[1], 3), dtype=image.dtype)
+        canvas[...] = (np.asarray(color, dtype=np.uint16) * np.uint16(257)).view(image.dtype) if wide else np.asarray(color, dtype=np.uint8)
         canvas[oy:oy + h, ox:ox + w] = image
         return canvas
     import torch
 
-    canvas = torch.empty((out[0], out[1], 3), dtype=torch.uint8, device=image.device)
-    canvas[...] = torch.tensor(color, dtype=torch.uint8, device=image.device)
-    canvas[oy:oy + h, ox:ox + w] = image
+    canvas = torch.empty((out[0], out[1], 3), dtype=image.dtype, device=image.device)
+    fill, into = np.asarray(color, dtype=np.uint8), canvas
+    if image.element_size() == 2:  # (written through int16 views: torch's uint16 knows few operations)
+        fill = (np.asarray(color, dtype=np.uint16) * np.uint16(257)).view(np.int16)
+        into, image = canvas.view(torch.int16), image.view(torch.int16)
+    into[...] = torch.from_numpy(fill).to(image.device)
+    into[oy:oy + h, ox:ox + w] = image
     return canvas
 
 

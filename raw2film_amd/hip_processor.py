@@ -23,6 +23,7 @@ import math
 import random
 import sys
 from concurrent.futures import ThreadPoolExecutor
+from typing import Callable, NamedTuple
 
 import numpy as np
 
@@ -98,6 +99,44 @@ def check_output_bits(output_bits, dst_texture=None) -> int:
     return int(output_bits)
 
 
+class OutputDepth(NamedTuple):
+    """What the output side knows of a sample width, 8 or 16 bits (check_output_bits validates the number, HipProcessor keeps one of
+    these per width): the dtypes of a result, the context's entry points that write and resample it -- each pair behind one call
+    shape -- and the pool its host buffers come from.  (The canvas colour's multiplier, 1 or 257, is geometry.add_canvas's, which
+    reads it off the frame's dtype.)"""
+    bits: int
+    torch_dtype: object  # of the device and the pinned buffers (int16 holds the bits of a 16-bit result)
+    numpy_dtype: type  # of the array the caller gets
+    render: Callable  # (image, params, out_f32, out, want_f32, want_out, layout) -> (out_f32, out): r2f_render / r2f_render16
+    front: Callable  # (rows, params, out, **row range): the fused LUTs-only pass of a band, straight to the result
+    tail: Callable  # (density, params, out, **row range)
+    resize_lanczos4: Callable  # (frame, rows, cols): cv.resize(..., INTER_LANCZOS4) / INTER_AREA as applied to this dtype
+    resize_area: Callable
+    pool: ResultBuffers  # a pool per width: a lent 8-bit buffer never comes back as a 16-bit result, nor the other way round
+
+
+def output_depths(torch, ctx) -> dict:
+    """{8: OutputDepth, 16: OutputDepth} of one processor's context."""
+    def depth(bits, torch_dtype, numpy_dtype, *calls):
+        return OutputDepth(bits, torch_dtype, numpy_dtype, *calls,
+                           ResultBuffers(lambda shape: torch.empty(shape, dtype=torch_dtype, pin_memory=True), numpy_dtype))
+
+    return {
+        8: depth(8, torch.uint8, np.uint8,
+                 lambda image, p, out_f32, out, want_f32, want_out, layout: ctx.render(
+                     image, p, out_f32=out_f32, out_u8=out, want_f32=want_f32, want_u8=want_out, layout=layout),
+                 lambda rows, p, out, **kw: ctx.stage_front(rows, p, 2, out_u8=out, **kw),
+                 lambda density, p, out, **kw: ctx.stage_tail(density, p, out_u8=out, **kw),
+                 ctx.resize_lanczos4_u8, ctx.resize_area_u8),
+        16: depth(16, torch.int16, np.uint16,  # (r2f_render16 always writes its 16-bit result: no want_out)
+                  lambda image, p, out_f32, out, want_f32, want_out, layout: ctx.render16(
+                      image, p, out_f32=out_f32, out_u16=out, want_f32=want_f32, layout=layout),
+                  lambda rows, p, out, **kw: ctx.stage_front16(rows, p, out_u16=out, **kw),
+                  lambda density, p, out, **kw: ctx.stage_tail16(density, p, out_u16=out, **kw),
+                  ctx.resize_lanczos4_u16, ctx.resize_area_u16),
+    }
+
+
 def _host16(arr):
     """The host array of a result: the uint16 view of a 16-bit frame (carried as int16, the same bits), else the array itself."""
     return arr.view(np.uint16) if arr.dtype == np.int16 else arr
@@ -155,15 +194,13 @@ class HipProcessor:
         self.lenses = lenses
         self.payload_alpha = bool(payload_alpha)
         self.result_buffers = int(result_buffers)  # 0: process() returns a fresh array; n: views of n pinned buffers in turn (_download)
-        self._results = ResultBuffers(lambda shape: torch.empty(shape, dtype=torch.uint8, pin_memory=True))
-        # ... and of the 16-bit results (output_bits=16; int16 holds the bits): a pool of its own, so the pool is keyed by dtype
-        self._results16 = ResultBuffers(lambda shape: torch.empty(shape, dtype=torch.int16, pin_memory=True), np.uint16)
         # process(host array, cache=False) with pinned result buffers streams a large frame through the pipeline in row bands while it
         # is still arriving (_process_streamed): at most this many, of at least 512 rows each (100 MP: 16 bands of 512 rows = 23.3 ms
         # against 24.7 with 8, 27.2 with 4, 24.9 with 24 -- tools/stream_bands_probe.py); 0: upload, render, download one after the other
         self.stream_bands = 16
         self.stream_taper = 2  # ... and the last two of them are halved (what runs behind the last byte of the upload gets shorter)
         self.ctx = HipContext(device, lib_path=lib_path)
+        self._depths = output_depths(torch, self.ctx)  # output_bits -> what differs between an 8- and a 16-bit result
         self.device = self.ctx.device  # NB: a torch device, not a wgpu device (gui.py:1652 uses bitmap mode)
         # comparison dicts, same role as cpu_processor.py:41-45 / gpu_processor.py
         self.input_param_dict = None
@@ -188,8 +225,8 @@ class HipProcessor:
         self.exposure_rejected = None
 
     def close(self):
-        self._results.close()
-        self._results16.close()
+        for depth in self._depths.values():
+            depth.pool.close()
         self._stream_bufs = None
         self._jpeg_host = None
         if getattr(self, "_jpeg_staging", None) is not None:
@@ -530,12 +567,12 @@ class HipProcessor:
         if prof:
             self._torch.cuda.synchronize(self.device)
             t_loaded = time.perf_counter()
-        out_u8 = self._render_prepared(image, layout, payload, negative_film, grain_size, grain_sigma, dst_texture, histogram_texture,
-                                       "cpu", **settings)
+        out = self._render_prepared(image, layout, payload, negative_film, grain_size, grain_sigma, dst_texture, histogram_texture,
+                                    "cpu", **settings)
         if prof:
             self._torch.cuda.synchronize(self.device)
             t_rendered = time.perf_counter()
-        res = None if out_u8 is None else self._download(out_u8)  # DEVICE -> HOST, the reference's read_texture/map_sync
+        res = None if out is None else self._download(out)  # DEVICE -> HOST, the reference's read_texture/map_sync
         if prof:
             t_end = time.perf_counter()
             self.last_stage_ms = {"load_and_upload": (t_loaded - t_start) * 1e3, "prepare_and_render": (t_rendered - t_loaded) * 1e3,
@@ -689,9 +726,9 @@ class HipProcessor:
                 return res
         self.prepare_gpu_textures(cpu_payload)
         image, layout, _ = self._texture
-        out_u8 = self._render_prepared(image, layout, cpu_payload, negative_film, grain_size, grain_sigma, dst_texture,
-                                       histogram_texture, final_scaling, **settings)
-        return None if out_u8 is None else self._download(out_u8)  # DEVICE -> HOST, the reference's read_texture/map_sync
+        out = self._render_prepared(image, layout, cpu_payload, negative_film, grain_size, grain_sigma, dst_texture,
+                                    histogram_texture, final_scaling, **settings)
+        return None if out is None else self._download(out)  # DEVICE -> HOST, the reference's read_texture/map_sync
 
     # ------------------------------------------------------------------ JPEG export (gui.py:2338-2341)
     def encode_jpeg(self, image, quality=100, *, subsampling=-1, optimize=False, exif=b"", progressive=False) -> bytes:
@@ -738,27 +775,13 @@ class HipProcessor:
         prog = _jpeg_progressive(progressive)
         exposure_on_device(settings.get("exposure"))
         self.exposure_rejected = None
-        for k in ("dst_texture", "histogram_texture"):
-            if settings.pop(k, None) is not None:
-                raise ValueError(f"process_jpeg writes a file: {k} is not taken (use process() for the preview)")
-        # process()'s keywords with process()'s defaults (the unknown ones swallowed like there)
-        bound = inspect.signature(HipProcessor.process).bind(self, src, negative_film, grain_size, grain_sigma, **settings)
-        bound.apply_defaults()
-        settings = {k: v for k, v in bound.arguments.items()
-                    if k not in ("self", "src", "negative_film", "grain_size", "grain_sigma", "dst_texture", "histogram_texture", "_")}
-        load = {k: settings[k] for k in _LOAD_KEYWORDS}
-        if stream:  # process(cache=False)'s gates, in its order: the early ones, then the payload's (_stream_payload's)
-            self.stream_rejected = (_PROGRESSIVE_REJECTED if prog else _OPTIMIZE_REJECTED if opts[1] else
-                                    "profile_stages is on" if getattr(self, "profile_stages", False) else
-                                    host_stream_gate(src, self.stream_bands, settings["rotation"], settings["chroma_nr"],
-                                                     settings["canvas_mode"], settings["highlight_burn"]))
-        payload = self.extract_image_data_cpu(src, **load, _internal=True)
+        settings, _, payload = self._export_frame("process_jpeg", src, negative_film, grain_size, grain_sigma, settings, stream,
+                                                  (_PROGRESSIVE_REJECTED if prog else None, _OPTIMIZE_REJECTED if opts[1] else None))
         if stream and self.stream_rejected is None:
             res = self._stream_jpeg(payload, negative_film, grain_size, grain_sigma, "cpu", q, file, settings, opts)
             if res is not None:
                 return res
-        image, layout = self._upload_payload(payload)
-        out_u8 = self._render_prepared(image, layout, payload, negative_film, grain_size, grain_sigma, None, None, "cpu", **settings)
+        out_u8 = self._render_export(payload, negative_film, grain_size, grain_sigma, "cpu", settings)
         return deliver(self._encode_device(out_u8, q, *opts, progressive=prog), file)
 
     def process_preloaded_jpeg(self, cpu_payload, negative_film, grain_size, grain_sigma, quality=100, final_scaling="gpu",
@@ -773,20 +796,53 @@ class HipProcessor:
         opts = _jpeg_options(subsampling, optimize, exif)
         prog = _jpeg_progressive(progressive)
         self.exposure_rejected = None
+        if self._export_preloaded("process_preloaded_jpeg", settings, stream,
+                                  (_PROGRESSIVE_REJECTED if prog else None, _OPTIMIZE_REJECTED if opts[1] else None)):
+            res = self._stream_jpeg(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, q, file, settings, opts)
+            if res is not None:
+                return res
+        out_u8 = self._render_export(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, settings)
+        return deliver(self._encode_device(out_u8, q, *opts, progressive=prog), file)
+
+    def _export_frame(self, what, src, negative_film, grain_size, grain_sigma, settings, stream, early=()):
+        """The prologue of an export of `src` (process_jpeg, process_tiff; `what` names it in messages): no textures, then
+        process()'s keywords with process()'s defaults (the unknown ones swallowed like there), with stream=True process(cache=False)'s
+        gates in its order into `stream_rejected` -- the export's own `early` reasons (None where one does not apply), the early
+        ones, then the payload's (_stream_plan's) -- and the frame's payload, extracted afresh.  -> (settings, load, payload)."""
+        self._refuse_textures(what, settings, " (use process() for the preview)")
+        bound = inspect.signature(HipProcessor.process).bind(self, src, negative_film, grain_size, grain_sigma, **settings)
+        bound.apply_defaults()
+        settings = {k: v for k, v in bound.arguments.items()
+                    if k not in ("self", "src", "negative_film", "grain_size", "grain_sigma", "dst_texture", "histogram_texture", "_")}
+        load = {k: settings[k] for k in _LOAD_KEYWORDS}
+        if stream:
+            self.stream_rejected = (next((why for why in early if why), None) or
+                                    ("profile_stages is on" if getattr(self, "profile_stages", False) else
+                                     host_stream_gate(src, self.stream_bands, settings["rotation"], settings["chroma_nr"],
+                                                      settings["canvas_mode"], settings["highlight_burn"])))
+        return settings, load, self.extract_image_data_cpu(src, **load, _internal=True)
+
+    def _export_preloaded(self, what, settings, stream, early=()) -> bool:
+        """The prologue of an export of a phase-1 payload: no textures, then with stream=True `stream_rejected` from the export's
+        own `early` reasons and the processor's `stream_bands`.  -> whether to try the row-band path (_stream_plan has the last word)."""
+        self._refuse_textures(what, settings)
+        if stream:
+            self.stream_rejected = (next((why for why in early if why), None) or
+                                    (None if self.stream_bands > 1 else f"stream_bands = {self.stream_bands}"))
+        return bool(stream) and self.stream_rejected is None
+
+    @staticmethod
+    def _refuse_textures(what, settings, hint=""):
         for k in ("dst_texture", "histogram_texture"):
             if settings.pop(k, None) is not None:
-                raise ValueError(f"process_preloaded_jpeg writes a file: {k} is not taken")
-        if stream:
-            self.stream_rejected = (_PROGRESSIVE_REJECTED if prog else _OPTIMIZE_REJECTED if opts[1] else
-                                    None if self.stream_bands > 1 else f"stream_bands = {self.stream_bands}")
-            if self.stream_rejected is None:
-                res = self._stream_jpeg(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, q, file, settings, opts)
-                if res is not None:
-                    return res
-        image, layout = self._upload_payload(cpu_payload)
-        out_u8 = self._render_prepared(image, layout, cpu_payload, negative_film, grain_size, grain_sigma, None, None, final_scaling,
-                                       **settings)
-        return deliver(self._encode_device(out_u8, q, *opts, progressive=prog), file)
+                raise ValueError(f"{what} writes a file: {k} is not taken{hint}")
+
+    def _render_export(self, payload, negative_film, grain_size, grain_sigma, final_scaling, settings):
+        """The one-piece render of an export: its frame is uploaded for this render alone (the processor's device frame, a
+        preview's, is left alone) -> the device result."""
+        image, layout = self._upload_payload(payload)
+        return self._render_prepared(image, layout, payload, negative_film, grain_size, grain_sigma, None, None, final_scaling,
+                                     **settings)
 
     # ------------------------------------------------------------------ TIFF export (8 or 16 bits per sample)
     def process_tiff(self, src, negative_film, grain_size, grain_sigma, file=None, *, output_bits=16, icc_profile=b"", stream=False,
@@ -804,25 +860,13 @@ class HipProcessor:
         icc = tiff.check_icc(icc_profile)
         exposure_on_device(params.get("exposure"))
         self.exposure_rejected = self.stream_rejected = None
-        for k in ("dst_texture", "histogram_texture"):
-            if params.pop(k, None) is not None:
-                raise ValueError(f"process_tiff writes a file: {k} is not taken (use process() for the preview)")
-        bound = inspect.signature(HipProcessor.process).bind(self, src, negative_film, grain_size, grain_sigma, output_bits=bits, **params)
-        bound.apply_defaults()
-        settings = {k: v for k, v in bound.arguments.items()
-                    if k not in ("self", "src", "negative_film", "grain_size", "grain_sigma", "dst_texture", "histogram_texture", "_")}
-        load = {k: settings[k] for k in _LOAD_KEYWORDS}
-        if stream:  # process(cache=False)'s gates, in its order
-            self.stream_rejected = ("profile_stages is on" if getattr(self, "profile_stages", False) else
-                                    host_stream_gate(src, self.stream_bands, settings["rotation"], settings["chroma_nr"],
-                                                     settings["canvas_mode"], settings["highlight_burn"]))
-        payload = self.extract_image_data_cpu(src, **load, _internal=True)
+        settings, _, payload = self._export_frame("process_tiff", src, negative_film, grain_size, grain_sigma,
+                                                  dict(params, output_bits=bits), stream)
         if stream and self.stream_rejected is None:
             res = self._stream_tiff(payload, negative_film, grain_size, grain_sigma, "cpu", icc, file, settings)
             if res is not None:
                 return res
-        image, layout = self._upload_payload(payload)
-        out = self._render_prepared(image, layout, payload, negative_film, grain_size, grain_sigma, None, None, "cpu", **settings)
+        out = self._render_export(payload, negative_film, grain_size, grain_sigma, "cpu", settings)
         return tiff.deliver(self._download(out), icc, file)
 
     def process_preloaded_tiff(self, cpu_payload, negative_film, grain_size, grain_sigma, file=None, final_scaling="gpu", *,
@@ -833,44 +877,24 @@ class HipProcessor:
         settings["output_bits"] = check_output_bits(output_bits)
         icc = tiff.check_icc(icc_profile)
         self.exposure_rejected = self.stream_rejected = None
-        for k in ("dst_texture", "histogram_texture"):
-            if settings.pop(k, None) is not None:
-                raise ValueError(f"process_preloaded_tiff writes a file: {k} is not taken")
-        if stream:
-            self.stream_rejected = None if self.stream_bands > 1 else f"stream_bands = {self.stream_bands}"
-            if self.stream_rejected is None:
-                res = self._stream_tiff(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, icc, file, settings)
-                if res is not None:
-                    return res
-        image, layout = self._upload_payload(cpu_payload)
-        out = self._render_prepared(image, layout, cpu_payload, negative_film, grain_size, grain_sigma, None, None, final_scaling,
-                                    **settings)
+        if self._export_preloaded("process_preloaded_tiff", settings, stream):
+            res = self._stream_tiff(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, icc, file, settings)
+            if res is not None:
+                return res
+        out = self._render_export(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, settings)
         return tiff.deliver(self._download(out), icc, file)
 
     def _stream_tiff(self, payload, negative_film, grain_size, grain_sigma, final_scaling, icc, file, settings):
         """_stream_payload with a TIFF sink: the same bands and stage calls; the header first, then every band's rows into the file
         behind their download (tiff.TiffBandSink).  Returns the file's bytes (file=None) or their count, or None (with
         `stream_rejected` saying why) when the payload does not qualify."""
-        plan = self._stream_plan(payload, negative_film, grain_size, grain_sigma, final_scaling, settings)
-        if plan is None:
-            return None
-        host, p, bounds, bufs, ha, ma = plan
-        H, W = bufs["shape"][:2]
-        bits = settings.get("output_bits", 8)
-        head, tplan = tiff.header(H, W, bits, icc)  # (refuses a file past 4 GiB before any band runs)
-        pool = self._results16 if bits == 16 else self._results
-        target, give_back = pool.borrow((H, W, 3), lease=self._lease_result16 if bits == 16 else self._lease_result)
-        sink = tiff.TiffBandSink(target, head, tplan, file, give_back)
-        try:
-            self._run_bands(host, payload, p, bounds, bufs, ha, ma, sink, bits=bits)
-            self._collect_auto_exposure()
-            res = sink.finish()
-        except BaseException:
-            self._torch.cuda.synchronize(self.device)
-            sink.abandon()
-            raise
-        self.last_output = bufs["u16out" if bits == 16 else "u8"]
-        return res
+        def make_sink(depth, out, bounds):
+            H, W = int(out.shape[0]), int(out.shape[1])
+            head, tplan = tiff.header(H, W, depth.bits, icc)  # (refuses a file past 4 GiB before any band runs)
+            target, give_back = depth.pool.borrow((H, W, 3), lease=self._lease_of(depth))
+            return tiff.TiffBandSink(target, head, tplan, file, give_back), None
+
+        return self._stream(payload, negative_film, grain_size, grain_sigma, final_scaling, settings, make_sink)
 
     def _encode_device(self, image_u8, quality, subsampling=2, optimize=False, exif=b"", progressive=False):
         """A uint8 (H, W, 3) device frame -> the JPEG file's bytes.  The encoder runs on the current stream; reading its 8-byte
@@ -916,28 +940,39 @@ class HipProcessor:
     def _stream_payload(self, payload, negative_film, grain_size, grain_sigma, final_scaling="cpu", **settings):
         """A phase-1 payload (extract_image_data_cpu) through the pipeline in row bands while it arrives: see _process_streamed.
         Returns the uint8 frame, or None (with `stream_rejected` saying why) when the payload does not qualify."""
+        def make_sink(depth, out, bounds):
+            return depth.pool.sink(tuple(out.shape), self.result_buffers, lease=self._lease_of(depth)), None
+
+        res = self._stream(payload, negative_film, grain_size, grain_sigma, final_scaling, settings, make_sink)
+        return None if res is None else _host16(res)
+
+    def _stream(self, payload, negative_film, grain_size, grain_sigma, final_scaling, settings, make_sink):
+        """The streamed render behind _stream_payload, _stream_tiff and _stream_jpeg, which differ in where the finished rows go:
+        plan the bands, make the sink -- make_sink(depth, the frame's result buffer on the device, band bounds) -> (sink, band_done):
+        a ResultSink or one with its interface and None, or a sink that downloads nothing itself and its band_done(b), called once
+        band b's tail is queued --, run the bands, finish.  A finish() that raises is drained and abandoned like a band that does.
+        Returns sink.finish()'s value, or None (with `stream_rejected` saying why) when the payload does not qualify."""
         plan = self._stream_plan(payload, negative_film, grain_size, grain_sigma, final_scaling, settings)
         if plan is None:
             return None
         host, p, bounds, bufs, ha, ma = plan
-        H, W = bufs["shape"][:2]
-        bits = settings.get("output_bits", 8)
-        if bits == 16:
-            sink = self._results16.sink((H, W, 3), self.result_buffers, lease=self._lease_result16)
-        else:
-            sink = self._results.sink((H, W, 3), self.result_buffers, lease=self._lease_result)
+        depth = self._depths[settings.get("output_bits", 8)]
+        out = self._stream_result(bufs, depth)
+        sink, band_done = make_sink(depth, out, bounds)
         try:
-            self._run_bands(host, payload, p, bounds, bufs, ha, ma, sink, bits=bits)
+            self._run_bands(host, payload, p, bounds, bufs, ha, ma, sink, out, depth, band_done)
             self._collect_auto_exposure()
+            res = sink.finish()
         except BaseException:
-            # a stage call refused (or the caller interrupted): let the queued work drain, hand a lent buffer back, pass it on
+            # a stage call refused, a write raised (or the caller interrupted): let the queued work drain, hand a lent buffer back,
+            # stop the copies and the writes, pass it on (the next export begins a new row-wise encode)
             self._torch.cuda.synchronize(self.device)
             sink.abandon()
             raise
         # (the frame kept on the device for re-renders -- a preview's, typically -- is left alone: an export in between does not cost
         # the preview its cached frame, which the one-after-the-other path has to overwrite because it works in it)
-        self.last_output = bufs["u16out" if bits == 16 else "u8"]
-        return _host16(sink.finish())
+        self.last_output = out
+        return res
 
     def _stream_plan(self, payload, negative_film, grain_size, grain_sigma, final_scaling, settings):
         """Qualify a payload for the row-band path and set its frame up: (host tensor, frame params, band bounds, device buffers,
@@ -969,28 +1004,17 @@ class HipProcessor:
         """_stream_payload with a JPEG sink: the same bands and stage calls, no pixels downloaded; each band's finished MCU rows
         are encoded behind its tail and the file's final bytes go down while later bands arrive (jpeg_stream.py).  Returns the
         file's bytes (file=None) or their count, or None (with `stream_rejected` saying why) when the payload does not qualify."""
-        plan = self._stream_plan(payload, negative_film, grain_size, grain_sigma, final_scaling, settings)
-        if plan is None:
-            return None
-        host, p, bounds, bufs, ha, ma = plan
-        staging = getattr(self, "_jpeg_staging", None)
-        if staging is None:
-            staging = self._jpeg_staging = JpegStaging(self._torch, self.device)
-        _, down = self._copy_streams()
-        subsampling, _, exif = opts  # (optimize never streams)
-        sink = JpegBandSink(staging, self.ctx, bufs["u8"], quality, bounds, down, file, subsampling, exif)
-        try:
-            self._run_bands(host, payload, p, bounds, bufs, ha, ma, None, band_done=sink.band)
-            self._collect_auto_exposure()
-            res = sink.finish()
-        except BaseException:
-            # a stage call refused, a write raised (or the caller interrupted): let the queued work drain, stop the copies and the
-            # writes, pass it on (the next export begins a new row-wise encode)
-            self._torch.cuda.synchronize(self.device)
-            sink.abandon()
-            raise
-        self.last_output = bufs["u8"]
-        return res
+        def make_sink(depth, out_u8, bounds):
+            staging = getattr(self, "_jpeg_staging", None)
+            if staging is None:
+                staging = self._jpeg_staging = JpegStaging(self._torch, self.device)
+            _, down = self._copy_streams()
+            subsampling, _, exif = opts  # (optimize never streams)
+            sink = JpegBandSink(staging, self.ctx, out_u8, quality, bounds, down, file, subsampling, exif)
+            return sink, sink.band
+
+        # (a JPEG is 8 bits per sample whatever `output_bits` the caller's settings carry)
+        return self._stream(payload, negative_film, grain_size, grain_sigma, final_scaling, dict(settings, output_bits=8), make_sink)
 
     def _stream_buffers(self, host, mtf, H, W, bits=8):
         """The device buffers a streamed H x W frame works in (kept for the next frame of the same kind): `host` is its payload tensor
@@ -1005,23 +1029,28 @@ class HipProcessor:
                 bufs[k] = torch.empty((3, H, W), dtype=torch.float32, device=self.device)
         if host.dtype == torch.int16 and (bufs.get("u16") is None or tuple(bufs["u16"].shape) != tuple(host.shape)):
             bufs["u16"] = torch.empty(tuple(host.shape), dtype=torch.int16, device=self.device)
-        # the result at the width this frame asks for, made when a frame first asks for it (int16 holds the bits of a 16-bit one)
-        if bits == 16 and bufs.get("u16out") is None:
-            bufs["u16out"] = torch.empty((H, W, 3), dtype=torch.int16, device=self.device)
-        if bits == 8 and bufs.get("u8") is None:
-            bufs["u8"] = torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)
+        self._stream_result(bufs, self._depths[bits])
         return bufs
 
-    def _run_bands(self, host, payload, p, bounds, bufs, ha, ma, sink, band_done=None, bits=8):
-        """_stream_payload's band loop (see _process_streamed): every stage runs a band as soon as the rows it reads exist (a stencil
-        stage reads into the band after its own), and the tail's rows go back into `sink` -- or, with `band_done`, band_done(b) is
-        called instead once band b's tail is queued (on the launching stream; the JPEG export's sink)."""
+    def _stream_result(self, bufs, depth):
+        """The result buffer of a streamed frame at `depth` among its device buffers, made when a frame first asks for that width
+        (int16 holds the bits of a 16-bit one)."""
+        key = ("out", depth.bits)
+        if bufs.get(key) is None:
+            bufs[key] = self._torch.empty(bufs["shape"][:2] + (3,), dtype=depth.torch_dtype, device=self.device)
+        return bufs[key]
+
+    def _run_bands(self, host, payload, p, bounds, bufs, ha, ma, sink, out, depth, band_done=None):
+        """_stream's band loop (see _process_streamed): every stage runs a band as soon as the rows it reads exist (a stencil
+        stage reads into the band after its own), and the tail's rows -- written into `out`, the result at `depth` -- go back into
+        `sink` -- or, with `band_done`, band_done(b) is called instead once band b's tail is queued (on the launching stream; the
+        JPEG export's sink)."""
         torch, ctx = self._torch, self.ctx
         H, n = int(bounds[-1]), len(bounds) - 1
         hal, mtf, grain = (bool(p.flags & f) for f in (_lib.F_HALATION, _lib.F_MTF, _lib.F_GRAIN))
         pointwise = not (hal or mtf or grain)
         is_u16 = host.dtype == torch.int16
-        image, E, D, out_u8 = bufs["image"], bufs["E"], bufs["D"], bufs["u16out" if bits == 16 else "u8"]  # (the result, either width)
+        image, E, D = bufs["image"], bufs["E"], bufs["D"]
         landing = bufs["u16"] if is_u16 else image
         # exposure="device": the whole uint16 frame goes up (the statistic is the whole frame's), the bands are rows of its window --
         # band k travels as the frame rows `ub[k]:ub[k + 1]`, the first and the last taking the rows above and below the window along
@@ -1046,7 +1075,7 @@ class HipProcessor:
             done = compute.record_event()
             with torch.cuda.stream(down):
                 down.wait_event(done)
-                sink.target[y0:y1].copy_(out_u8[y0:y1], non_blocking=True)
+                sink.target[y0:y1].copy_(out[y0:y1], non_blocking=True)
                 sink.band_back(down.record_event() if sink.per_band else down, y0, y1)
 
         # A copy out of ordinary (pageable) host memory -- any NumPy array that was not made from pinned memory -- returns only when
@@ -1078,12 +1107,8 @@ class HipProcessor:
                     ctx.decode_u16(landing[a0:a1], payload["u16_factor"], out=rows)
                 elif payload.get("clip_on_device"):
                     rows.clamp_(0.0, 65504.0)  # np.clip(image, 0, 65504) of gpu_processor.py:275, band by band
-                if pointwise and bits == 16:
-                    ctx.stage_front16(rows, p, in_gy0=a0, out_u16=out_u8, out_gy0=0, y0=a0, y1=a1, H_global=H)
-                    send_back(k)
-                    continue
-                if pointwise:  # LUTs only: one fused pass per band, straight to uint8
-                    ctx.stage_front(rows, p, 2, in_gy0=a0, out_u8=out_u8, out_gy0=0, y0=a0, y1=a1, H_global=H)
+                if pointwise:  # LUTs only: one fused pass per band, straight to the result
+                    depth.front(rows, p, out, in_gy0=a0, out_gy0=0, y0=a0, y1=a1, H_global=H)
                     send_back(k)
                     continue
                 if hal:
@@ -1108,23 +1133,25 @@ class HipProcessor:
                         sharp, moved = sharp + 1, True
                     if tail < (sharp if mtf else dens):
                         y0, y1 = bounds[tail], bounds[tail + 1]
-                        if bits == 16:
-                            ctx.stage_tail16(bufs["D2"] if mtf else D, p, src_gy0=0, out_u16=out_u8, out_gy0=0, y0=y0, y1=y1, H_global=H)
-                        else:
-                            ctx.stage_tail(bufs["D2"] if mtf else D, p, src_gy0=0, out_u8=out_u8, out_gy0=0, y0=y0, y1=y1, H_global=H)
+                        depth.tail(bufs["D2"] if mtf else D, p, out, src_gy0=0, out_gy0=0, y0=y0, y1=y1, H_global=H)
                         send_back(tail)
                         tail, moved = tail + 1, True
         finally:
             if uploader is not None:
                 uploader.shutdown(cancel_futures=True)
 
-    def _lease_result(self, shape):
-        """A pinned buffer of `shape` to lend out as a result, or None when three are out (every lease goes through here)."""
-        return self._results.lease(shape)
+    def _lease_result(self, shape, bits=8):
+        """A pinned buffer of `shape` to lend out as a result of that width, or None when three are out (every lease goes through
+        here; the pools are keyed by width as well as shape)."""
+        return self._depths[bits].pool.lease(shape)
 
-    def _lease_result16(self, shape):
-        """_lease_result for a 16-bit result: the pool is keyed by dtype as well as shape."""
-        return self._results16.lease(shape)
+    def _lease_of(self, depth):
+        """`lease=` of depth.pool's sink() and borrow(): _lease_result, looked up when the lease is made, for that width.  An 8-bit
+        lease is a call with the shape alone, so a replacement of _lease_result that takes nothing else (the lease-counting test's
+        wrapper) serves 8-bit results; one that is to see 16-bit leases too takes (shape, bits=8)."""
+        if depth.bits == 8:
+            return lambda shape: self._lease_result(shape)
+        return lambda shape: self._lease_result(shape, depth.bits)
 
     def _copy_streams(self):
         """(host-to-device, device-to-host) copy streams of this processor, made on first use."""
@@ -1133,18 +1160,18 @@ class HipProcessor:
             self._down_stream = self._torch.cuda.Stream(device=self.device)
         return self._up_stream, self._down_stream
 
-    def _download(self, out_u8):
-        """The uint8 result as a NumPy array (results.py): with result_buffers = n > 0 a view of one of n pinned buffers (24 MP: 1.5
-        instead of 6 ms to come down); else the caller's own array, from 3 M samples up a lent pinned buffer (2.7 instead of 7.8 ms)."""
+    def _download(self, out):
+        """The result, uint8 or 16-bit, as a NumPy array (results.py): with result_buffers = n > 0 a view of one of n pinned buffers
+        (24 MP: 1.5 instead of 6 ms to come down); else the caller's own array, from 3 M samples up a lent pinned buffer (2.7 instead
+        of 7.8 ms)."""
         sink = None
-        wide = out_u8.dtype == self._torch.int16  # a 16-bit result: the same ways back, from the pool of its own dtype
-        if self.result_buffers > 0 or out_u8.numel() >= (3 << 20):
-            sink = (self._results16 if wide else self._results).sink(tuple(out_u8.shape), self.result_buffers, staged=False,
-                                                                      lease=self._lease_result16 if wide else self._lease_result)
+        depth = self._depths[8 * out.element_size()]  # a 16-bit result: the same ways back, from the pool of its own width
+        if self.result_buffers > 0 or out.numel() >= (3 << 20):
+            sink = depth.pool.sink(tuple(out.shape), self.result_buffers, staged=False, lease=self._lease_of(depth))
         if sink is None:
-            return _host16(out_u8.cpu().numpy())
-        sink.target.copy_(out_u8, non_blocking=True)
-        sink.band_back(self._torch.cuda.current_stream(self.device), 0, int(out_u8.shape[0]))
+            return _host16(out.cpu().numpy())
+        sink.target.copy_(out, non_blocking=True)
+        sink.band_back(self._torch.cuda.current_stream(self.device), 0, int(out.shape[0]))
         return _host16(sink.finish())
 
     def _payload_tensor(self, cpu_payload):
@@ -1191,15 +1218,15 @@ class HipProcessor:
         # waits for this frame's upload and statistic, the time in which the caller prepares the next frame)
         self._defer_exposure_read = True
         try:
-            out_u8 = self._render_preloaded(dev, cpu_payload, negative_film, grain_size, grain_sigma, None, None, final_scaling, **settings)
+            out = self._render_preloaded(dev, cpu_payload, negative_film, grain_size, grain_sigma, None, None, final_scaling, **settings)
         finally:
             self._defer_exposure_read = False
         rendered = compute.record_event()
         with torch.cuda.stream(down):
             down.wait_event(rendered)
-            host = torch.empty(out_u8.shape, dtype=out_u8.dtype, pin_memory=True)
-            host.copy_(out_u8, non_blocking=True)
-            out_u8.record_stream(down)
+            host = torch.empty(out.shape, dtype=out.dtype, pin_memory=True)
+            host.copy_(out, non_blocking=True)
+            out.record_stream(down)
             done = down.record_event()
         return PendingFrame(host, done)
 
@@ -1249,7 +1276,9 @@ class HipProcessor:
 
     def _render_prepared(self, image, layout, cpu_payload, negative_film, grain_size, grain_sigma, dst_texture, histogram_texture,
                          final_scaling, **settings):
-        """The pipeline and the post-path on a prepared device frame (which is only read: it can be rendered again)."""
+        """The pipeline and the post-path on a prepared device frame (which is only read: it can be rendered again).  At 16 bits
+        (r2f_render16; an int16 tensor holds the uint16 frame's bits) the post-path is the same on the wider frame: the canvas colour
+        c * 257 (255 -> 65535), cv.resize(uint16, ...) for the two scalings."""
         if dst_texture is not None:
             self._check_texture(dst_texture, "dst_texture")
         if histogram_texture is not None:
@@ -1257,11 +1286,9 @@ class HipProcessor:
             if dst_texture is None:
                 raise ValueError("histogram_texture needs dst_texture (gpu_processor.py:1883: the histogram is only drawn on the "
                                  "destination-texture branch)")
-        torch = self._torch  # noqa: F841
-        if check_output_bits(settings.get("output_bits", 8), dst_texture) == 16:
-            return self._render_prepared16(image, layout, cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, **settings)
-        out_f32, out_u8 = self._execute_pipeline(image, negative_film, grain_size, grain_sigma, want_f32=dst_texture is not None,
-                                                 want_u8=True, layout=layout, **settings)
+        depth = self._depths[check_output_bits(settings.get("output_bits", 8), dst_texture)]
+        out_f32, out = self._execute_pipeline(image, negative_film, grain_size, grain_sigma, want_f32=dst_texture is not None,
+                                              want_out=True, layout=layout, **settings)
         self._collect_auto_exposure()
         if dst_texture is not None:
             # GpuProcessor's destination branch (gpu_processor.py:1865-1890): letterbox the float frame into the widget's
@@ -1276,51 +1303,23 @@ class HipProcessor:
                                         output_resolution=cpu_payload.get("output_resolution"),
                                         canvas_resolution=cpu_payload.get("canvas_resolution"), canvas_color=color)
             self.ctx.blit_rgba8(out_f32, dst_texture, t)
-            self.last_output = out_u8
+            self.last_output = out
             if histogram_texture is not None:
                 from . import histogram
 
-                self.ctx.histogram_render(self.ctx.histogram_counts(out_u8), histogram.MIX_TABLE, 256, target=histogram_texture)
+                self.ctx.histogram_render(self.ctx.histogram_counts(out), histogram.MIX_TABLE, 256, target=histogram_texture)
             return None
         # canvas on the device result (cpu_processor.py:409 / copy_to_int.wgsl): a paste, no arithmetic
-        out_u8 = geometry.add_canvas(out_u8, settings.get("canvas_mode", "No"), settings.get("canvas_scale", 1.0),
-                                     settings.get("canvas_ratio", 1.0))
+        out = geometry.add_canvas(out, settings.get("canvas_mode", "No"), settings.get("canvas_scale", 1.0),
+                                  settings.get("canvas_ratio", 1.0))
         target = cpu_payload.get("final_resolution") if final_scaling == "cpu" else cpu_payload.get("upscale_to")
-        if target:  # cpu_processor.py:411-412 -> utils.resolution_scaling (utils.py:226-244) on the uint8 frame
-            f = min(target[0] / out_u8.shape[0], target[1] / out_u8.shape[1])
-            size = (round(out_u8.shape[0] * f), round(out_u8.shape[1] * f))
-            if f > 1:  # cv.INTER_LANCZOS4
-                out_u8 = self.ctx.resize_lanczos4_u8(out_u8.contiguous(), *size)
-            elif f < 1 and final_scaling == "cpu":  # cv.INTER_AREA: the CPU processor shrinks the canvas-framed frame
-                out_u8 = self.ctx.resize_area_u8(out_u8.contiguous(), *size)
-        self.last_output = out_u8
-        return out_u8
-
-    def _render_prepared16(self, image, layout, cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, **settings):
-        """_render_prepared's bitmap branch at 16 bits: r2f_render16, then the same post-path on the uint16 frame (an int16 tensor
-        holds its bits) -- the canvas colour c * 257 (255 -> 65535), cv.resize(uint16, ...) for the two scalings."""
-        torch = self._torch
-        _, out = self._execute_pipeline(image, negative_film, grain_size, grain_sigma, want_f32=False, want_u8=False, layout=layout,
-                                        **settings)
-        self._collect_auto_exposure()
-        mode = settings.get("canvas_mode", "No")
-        if mode != "No":  # effects.add_canvas (effects.py:336-357) on the 16-bit frame: a paste, no arithmetic
-            shape, color, (oy, ox) = geometry.canvas_layout(out.shape, mode, settings.get("canvas_scale", 1.0),
-                                                            settings.get("canvas_ratio", 1.0))
-            if oy < 0 or ox < 0:
-                raise ValueError("canvas smaller than the frame (canvas_scale < 1)")
-            canvas = torch.empty((shape[0], shape[1], 3), dtype=torch.int16, device=out.device)
-            canvas[...] = torch.from_numpy((np.asarray(color, dtype=np.uint16) * np.uint16(257)).view(np.int16)).to(out.device)
-            canvas[oy:oy + int(out.shape[0]), ox:ox + int(out.shape[1])] = out
-            out = canvas
-        target = cpu_payload.get("final_resolution") if final_scaling == "cpu" else cpu_payload.get("upscale_to")
-        if target:  # cpu_processor.py:411-412 -> utils.resolution_scaling (utils.py:226-244) on the uint16 frame
+        if target:  # cpu_processor.py:411-412 -> utils.resolution_scaling (utils.py:226-244) on the finished frame
             f = min(target[0] / out.shape[0], target[1] / out.shape[1])
             size = (round(out.shape[0] * f), round(out.shape[1] * f))
-            if f > 1:
-                out = self.ctx.resize_lanczos4_u16(out.contiguous(), *size)
-            elif f < 1 and final_scaling == "cpu":
-                out = self.ctx.resize_area_u16(out.contiguous(), *size)
+            if f > 1:  # cv.INTER_LANCZOS4
+                out = depth.resize_lanczos4(out.contiguous(), *size)
+            elif f < 1 and final_scaling == "cpu":  # cv.INTER_AREA: the CPU processor shrinks the canvas-framed frame
+                out = depth.resize_area(out.contiguous(), *size)
         self.last_output = out
         return out
 
@@ -1387,12 +1386,12 @@ class HipProcessor:
                 want = torch.int16  # (the same bits)
             if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == want and tuple(out.shape) == (H, W, 3) and out.is_contiguous()):
                 raise ValueError(f"out must be a contiguous {want} CUDA tensor of shape {(H, W, 3)}")
-        f32, u8 = self._execute_pipeline(
-            image, negative_film, grain_size, grain_sigma, want_f32=return_float, want_u8=not return_float,
+        f32, res = self._execute_pipeline(
+            image, negative_film, grain_size, grain_sigma, want_f32=return_float, want_out=not return_float,
             matrix=REC709_TO_XYZ if colorspace == "linear-rec709" else None, seed=seed,
-            out_f32=out if return_float else None, out_u8=None if return_float else out, output_bits=output_bits, **settings,
+            out_f32=out if return_float else None, out=None if return_float else out, output_bits=output_bits, **settings,
         )
-        out = f32 if return_float else u8
+        out = f32 if return_float else res
         if output_bits == 16:
             out = out.view(torch.uint16)
             return out if output == "device" else out.view(torch.int16).cpu().numpy().view(np.uint16)
@@ -1441,16 +1440,15 @@ class HipProcessor:
                                     grain_mono=grain == 1, seed=seed, lut3d_mode=lut3d_mode,
                                     log_eps=LOG_EPS, lut3d_scale=LUT3D_SCALE, **burn_kw)
 
-    def _execute_pipeline(self, image, negative_film, grain_size, grain_sigma, want_f32=False, want_u8=True, layout=None,
-                          out_f32=None, out_u8=None, **settings):
-        """Tables (re-uploaded only when their parameters changed) + ONE r2f_render: the frame's launches are captured into a
-        HIP graph the second time the same buffers come by and replayed from then on -- the counterpart of the reference's
-        single command encoder and submit (gpu_processor.py:1760, 1877); the per-render seed travels in a device-side block."""
+    def _execute_pipeline(self, image, negative_film, grain_size, grain_sigma, want_f32=False, want_out=True, layout=None,
+                          out_f32=None, out=None, **settings):
+        """Tables (re-uploaded only when their parameters changed) + ONE r2f_render (r2f_render16 with output_bits=16, whose result
+        `out` then names): the frame's launches are captured into a HIP graph the second time the same buffers come by and replayed
+        from then on -- the counterpart of the reference's single command encoder and submit (gpu_processor.py:1760, 1877); the
+        per-render seed travels in a device-side block.  -> (out_f32 or None, the result or None)."""
         _, H, W = self.ctx.layout_of(image, layout)
         params = self.prepare(negative_film, grain_size, grain_sigma, (W, H), **settings)
-        if settings.get("output_bits", 8) == 16:  # -> (out_f32 or None, the 16-bit frame); out_u8 names the caller's 16-bit buffer
-            return self.ctx.render16(image, params, out_f32=out_f32, out_u16=out_u8, want_f32=want_f32, layout=layout)
-        return self.ctx.render(image, params, out_f32=out_f32, out_u8=out_u8, want_f32=want_f32, want_u8=want_u8, layout=layout)
+        return self._depths[settings.get("output_bits", 8)].render(image, params, out_f32, out, want_f32, want_out, layout)
 
 
 def torch_div257(torch, image16):

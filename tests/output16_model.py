@@ -5,6 +5,8 @@ compare with.  This module only CALLS the oracle (oracle/stages.py, oracle/post.
                   returns before its own cast
   lanczos4_u16    cv.resize(uint16, INTER_LANCZOS4): the oracle's float LANCZOS4 restatement, then saturate_cast<ushort>
   area_u16        cv.resize(uint16, INTER_AREA) after oracle/post.py's uint8 structure, with the wider clamp
+  canvas_u16      effects.add_canvas on a uint16 frame: the layout geometry.canvas_layout pins against the reference
+                  (tests/golden/geometry.npz), the colour c * 257 (255 -> 65535), the frame pasted at the layout's offset
   read_tiff       a baseline TIFF reader (struct + numpy): the full-depth array and the tag dictionary
 """
 
@@ -70,6 +72,18 @@ def area_u16(image, out_h: int, out_w: int) -> np.ndarray:
             term = (b * buf[s]).astype(F32)
             total = term if total is None else (total + term).astype(F32)
         out[dy] = sat_u16(total)
+    return out
+
+
+def canvas_u16(image, canvas_mode: str, canvas_scale: float = 1.0, canvas_ratio: float = 1.0) -> np.ndarray:
+    from raw2film_amd import geometry
+
+    image = np.asarray(image, dtype=np.uint16)
+    (rows, cols), color, (oy, ox) = geometry.canvas_layout(image.shape, canvas_mode, canvas_scale, canvas_ratio)
+    out = np.empty((rows, cols, 3), np.uint16)
+    for c in range(3):
+        out[:, :, c] = color[c] * 257
+    out[oy:oy + image.shape[0], ox:ox + image.shape[1]] = image
     return out
 
 

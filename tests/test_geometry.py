@@ -40,6 +40,39 @@ def test_add_canvas_numpy_and_torch_agree():
     assert white.shape == (60, 60, 3) and white[0, 0, 0] == 255
 
 
+def test_add_canvas_pastes_a_16_bit_frame_onto_a_canvas_of_its_own_dtype():
+    """A uint16 NumPy frame and its int16-view torch tensor (the bits a 16-bit render carries on the device): the colour times 257,
+    the frame at the layout's offset (output16_model.canvas_u16); the uint8 result is what it was; too small a canvas still raises."""
+    torch = pytest.importorskip("torch")
+    from output16_model import canvas_u16
+
+    rng = np.random.default_rng(5)
+    img16 = rng.integers(0, 65536, (8, 12, 3), dtype=np.uint16)
+    img16[0, 0] = (0, 32768, 65535)  # (the int16 view of the last two is negative)
+    img8 = rng.integers(0, 256, (8, 12, 3), dtype=np.uint8)
+    for mode, scale, ratio in (("Uniform white", 1.5, 1.0), ("Proportional black", 1.25, 1.0), ("Fixed", 1.3, 2.0)):
+        want = canvas_u16(img16, mode, scale, ratio)
+        assert want.shape[0] > 8 and want.shape[1] > 12  # (the mode pads)
+        got = geometry.add_canvas(img16, mode, scale, ratio)
+        assert got.dtype == np.uint16 and np.array_equal(got, want)
+        t = geometry.add_canvas(torch.from_numpy(img16.view(np.int16)), mode, scale, ratio)
+        assert t.dtype == torch.int16 and np.array_equal(t.numpy().view(np.uint16), want)
+        if hasattr(torch, "uint16"):
+            u = geometry.add_canvas(torch.from_numpy(img16.view(np.int16)).view(torch.uint16), mode, scale, ratio)
+            assert u.dtype == torch.uint16 and np.array_equal(u.view(torch.int16).numpy().view(np.uint16), want)
+        # the uint8 result, written out: the mode's colour everywhere but the frame at the offset
+        (rows, cols), color, (oy, ox) = geometry.canvas_layout(img8.shape, mode, scale, ratio)
+        want8 = np.empty((rows, cols, 3), np.uint8)
+        want8[...] = np.asarray(color, np.uint8)
+        want8[oy:oy + 8, ox:ox + 12] = img8
+        for got8 in (geometry.add_canvas(img8, mode, scale, ratio), geometry.add_canvas(torch.from_numpy(img8), mode, scale, ratio).numpy()):
+            assert got8.dtype == np.uint8 and np.array_equal(got8, want8)
+        assert np.array_equal(want[0, 0], np.asarray(color, np.uint16) * 257)
+    for frame in (img16, torch.from_numpy(img16.view(np.int16)), img8, torch.from_numpy(img8)):
+        with pytest.raises(ValueError, match=r"canvas smaller than the frame \(canvas_scale < 1\)"):
+            geometry.add_canvas(frame, "Uniform white", 0.5)
+
+
 def test_crop_to_frame_quarter_turns():
     img = np.arange(400 * 600 * 3, dtype=np.float32).reshape(400, 600, 3)
     out = geometry.crop_to_frame(img, 36, 24, zoom=1.0, rotate_times=1)
