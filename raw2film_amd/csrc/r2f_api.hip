@@ -47,6 +47,32 @@ int upload(r2f_ctx* ctx, DeviceBuf& buf, const void* host, size_t bytes) {
     return R2F_OK;
 }
 
+static void lanczos4_table(int n, int out_n, int* ofs, short* coef) { r2f_lanczos4_table(n, out_n, ofs, coef); }
+static void lanczos4_table(int n, int out_n, int* ofs, float* coef) { r2f_lanczos4_table_f32(n, out_n, ofs, coef); }
+
+template <typename Coef>
+int LanczosTables::tables(r2f_ctx* ctx, int H, int W, int out_h, int out_w, const int** xofs, const int** yofs, const Coef** xcoef,
+                          const Coef** ycoef) {
+    const size_t n_ofs = (size_t)out_w + out_h, coef_off = (n_ofs * sizeof(int) + 15) / 16 * 16;
+    const int want[4] = {H, W, out_h, out_w};
+    if (memcmp(want, key, sizeof key) != 0 || !buf.p) {
+        std::vector<unsigned char> host(coef_off + 8 * n_ofs * sizeof(Coef));
+        int* ofs = reinterpret_cast<int*>(host.data());
+        Coef* coef = reinterpret_cast<Coef*>(host.data() + coef_off);
+        lanczos4_table(W, out_w, ofs, coef);
+        lanczos4_table(H, out_h, ofs + out_w, coef + 8 * (size_t)out_w);
+        int rc = upload(ctx, buf, host.data(), host.size());  // (waits for renders in flight, like every table upload)
+        if (rc) return rc;
+        memcpy(key, want, sizeof key);
+    }
+    const unsigned char* base = static_cast<const unsigned char*>(buf.p);
+    *xofs = reinterpret_cast<const int*>(base);
+    *yofs = *xofs + out_w;
+    *xcoef = reinterpret_cast<const Coef*>(base + coef_off);
+    *ycoef = *xcoef + 8 * (size_t)out_w;
+    return R2F_OK;
+}
+
 // (4, m) table -> per channel m-1 cells {xp[i], xp[i+1], fp[i], slope[i]} (plan::curve_cells), uploaded.
 static int upload_curve(r2f_ctx* ctx, DeviceBuf& buf, DevCurve& cv, const float* lut, int m) {
     if (!lut || m < 2) return fail(ctx, R2F_EINVAL, "curve: need a (4, m) table with m >= 2");
@@ -285,8 +311,8 @@ int r2f_set_kernel(r2f_ctx* ctx, int which, const float* k, int kh, int kw, int 
 int r2f_stage_front(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, int in_gy0, int in_rows, int upto,
                     const r2f_planes* dst, float* out_f32, uint8_t* out_u8, int out_gy0, int y0, int y1, int W,
                     int H_global, void* stream) {
-    return stage_front_impl(ctx, p, in, in_layout, in_gy0, in_rows, upto, dst, out_f32, out_u8, out_gy0, y0, y1, W, H_global, stream,
-                            nullptr, nullptr);
+    return stage_front_impl(ctx, p, in, in_layout, in_gy0, in_rows, upto, dst, HwcOut{out_f32, out_u8, nullptr, out_gy0}, y0, y1, W,
+                            H_global, stream);
 }
 
 int r2f_stage_front_split(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, int in_gy0, int in_rows,
@@ -294,18 +320,27 @@ int r2f_stage_front_split(r2f_ctx* ctx, const r2f_params* p, const void* in, int
                           int* finished_mask, void* stream) {
     if (!finished_mask) return R2F_EINVAL;
     *finished_mask = 0;
-    return stage_front_impl(ctx, p, in, in_layout, in_gy0, in_rows, R2F_UPTO_EXPOSURE, exposure, nullptr, nullptr, 0, y0, y1, W, H_global,
-                            stream, density, finished_mask);
+    return stage_front_impl(ctx, p, in, in_layout, in_gy0, in_rows, R2F_UPTO_EXPOSURE, exposure, HwcOut{}, y0, y1, W, H_global, stream,
+                            density, finished_mask);
 }
 
 }  // extern "C"
 
+// What an entry point that writes an interleaved output asks of it, in the order the callers have always reported it (the tail
+// folds "y0 above the buffer" into its geometry check, ahead of this).  *vec: may the float4 / packed stores be used?
+static int check_hwc_out(r2f_ctx* ctx, const char* who, const HwcOut& out, int y0, bool* vec) {
+    if (!out.any()) return fail(ctx, R2F_EINVAL, "%s: no output buffer", who);
+    if (y0 < out.gy0) return fail(ctx, R2F_EINVAL, "%s: y0 above the output buffer", who);
+    if (reinterpret_cast<uintptr_t>(out.u16) & 1u) return fail(ctx, R2F_EINVAL, "%s: the uint16 output must be 2-byte aligned", who);
+    *vec = *vec && out.vec_ok();
+    return R2F_OK;
+}
+
 // tracked (whole-frame renders): when given, the fast kernel records the range of the exposure planes it writes in the context's frame
 // block and *tracked says whether that happened (only the split fast kernel does it).
 int r2f::stage_front_impl(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, int in_gy0, int in_rows, int upto,
-                            const r2f_planes* dst, float* out_f32, uint8_t* out_u8, int out_gy0, int y0, int y1, int W,
-                            int H_global, void* stream, const r2f_planes* finish_dst, int* finished_mask, bool* tracked,
-                            uint16_t* out_u16) {
+                            const r2f_planes* dst, const HwcOut& out, int y0, int y1, int W, int H_global, void* stream,
+                            const r2f_planes* finish_dst, int* finished_mask, bool* tracked) {
     if (tracked) *tracked = false;
     if (!ctx || !p) return R2F_EINVAL;
     R2F_GUARD(ctx);
@@ -343,14 +378,9 @@ int r2f::stage_front_impl(r2f_ctx* ctx, const r2f_params* p, const void* in, int
     if (upto >= R2F_UPTO_DENSITY && !ctx->curve.cells) return fail(ctx, R2F_EINVAL, "density curve not set (r2f_set_curve1d)");
     if (upto == R2F_UPTO_OUTPUT) {
         if (!ctx->lut3d.tex) return fail(ctx, R2F_EINVAL, "output LUT not set (r2f_set_lut3d)");
-        if (!out_f32 && !out_u8 && !out_u16) return fail(ctx, R2F_EINVAL, "front: no output buffer");
-        if (y0 < out_gy0) return fail(ctx, R2F_EINVAL, "front: y0 above the output buffer");
-        if (reinterpret_cast<uintptr_t>(out_u16) & 1u) return fail(ctx, R2F_EINVAL, "front: the uint16 output must be 2-byte aligned");
-        a.out_f32 = out_f32;
-        a.out_u8 = out_u8;
-        a.out_u16 = out_u16;
-        a.out_gy0 = out_gy0;
-        vec = vec && (!out_f32 || aligned16(out_f32)) && (!out_u8 || (reinterpret_cast<uintptr_t>(out_u8) & 3u) == 0);
+        int rc = check_hwc_out(ctx, "front", out, y0, &vec);
+        if (rc) return rc;
+        a.out = out;
     } else if (upto == R2F_UPTO_EXPOSURE || upto == R2F_UPTO_DENSITY) {
         int rc = check_rows(ctx, "front dst", dst, y0, y1);
         if (rc) return rc;
@@ -519,8 +549,8 @@ static int ensure_grain_fixed(r2f_ctx* ctx) {
 }
 
 static int run_tail(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const r2f_planes* planes_out,
-                    const float* burn_map, float* out_f32, uint8_t* out_u8, int out_gy0, int y0, int y1, int W, int H_global,
-                    void* stream, const r2f_planes* gfield = nullptr, uint16_t* out_u16 = nullptr) {
+                    const float* burn_map, const HwcOut& out, int y0, int y1, int W, int H_global, void* stream,
+                    const r2f_planes* gfield = nullptr) {
     if (y1 <= y0) return R2F_OK;
     const bool field_only = density == nullptr && planes_out != nullptr;
     if (field_only) {
@@ -528,19 +558,17 @@ static int run_tail(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density
         density = &none;
     }
     const bool to_planes = planes_out != nullptr;
-    if (W <= 0 || y0 < 0 || y1 > H_global || (!to_planes && y0 < out_gy0)) return fail(ctx, R2F_EINVAL, "tail: bad geometry");
-    if (!to_planes && !out_f32 && !out_u8 && !out_u16) return fail(ctx, R2F_EINVAL, "tail: no output buffer");
-    if (reinterpret_cast<uintptr_t>(out_u16) & 1u) return fail(ctx, R2F_EINVAL, "tail: the uint16 output must be 2-byte aligned");
+    if (W <= 0 || y0 < 0 || y1 > H_global || (!to_planes && y0 < out.gy0)) return fail(ctx, R2F_EINVAL, "tail: bad geometry");
+    bool out_vec = true;
+    int rc = to_planes ? R2F_OK : check_hwc_out(ctx, "tail", out, y0, &out_vec);
+    if (rc) return rc;
     if (!to_planes && !ctx->lut3d.tex) return fail(ctx, R2F_EINVAL, "output LUT not set (r2f_set_lut3d)");
-    int rc = field_only ? R2F_OK : check_rows(ctx, "tail src", density, y0, y1);
+    rc = field_only ? R2F_OK : check_rows(ctx, "tail src", density, y0, y1);
     if (rc) return rc;
     TailArgs a;
     memset(&a, 0, sizeof a);
     a.src = to_dev(density);
-    a.out_f32 = out_f32;
-    a.out_u8 = out_u8;
-    a.out_u16 = out_u16;
-    a.out_gy0 = out_gy0;
+    a.out = out;
     a.y0 = y0;
     a.y1 = y1;
     a.W = W;
@@ -576,7 +604,7 @@ static int run_tail(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density
         a.dst = to_dev(planes_out);
         vec = vec && planes_vec_ok(planes_out, W);
     } else {
-        vec = vec && (!out_f32 || aligned16(out_f32)) && (!out_u8 || (reinterpret_cast<uintptr_t>(out_u8) & 3u) == 0);
+        vec = vec && out_vec;
         if (burn_map) {
             if (a.grain || a.has_gfield)
                 return fail(ctx, R2F_EINVAL, "tail with a burn map: apply the grain first (r2f_stage_grain) and clear R2F_F_GRAIN");
@@ -627,25 +655,23 @@ static int run_tail(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density
 
 int r2f_stage_tail(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const float* burn_map, float* out_f32,
                    uint8_t* out_u8, int out_gy0, int y0, int y1, int W, int H_global, void* stream) {
-    if (!ctx || !p) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    return run_tail(ctx, p, density, nullptr, burn_map, out_f32, out_u8, out_gy0, y0, y1, W, H_global, stream);
+    return stage_tail_impl(ctx, p, density, burn_map, HwcOut{out_f32, out_u8, nullptr, out_gy0}, y0, y1, W, H_global, stream);
 }
 
 }  // extern "C"
 
-int r2f::stage_tail_impl(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const float* burn_map, float* out_f32,
-                         uint8_t* out_u8, uint16_t* out_u16, int out_gy0, int y0, int y1, int W, int H_global, void* stream) {
+int r2f::stage_tail_impl(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const float* burn_map, const HwcOut& out, int y0,
+                         int y1, int W, int H_global, void* stream) {
     if (!ctx || !p) return R2F_EINVAL;
     R2F_GUARD(ctx);
-    return run_tail(ctx, p, density, nullptr, burn_map, out_f32, out_u8, out_gy0, y0, y1, W, H_global, stream, nullptr, out_u16);
+    return run_tail(ctx, p, density, nullptr, burn_map, out, y0, y1, W, H_global, stream);
 }
 
 extern "C" {
 
 int r2f_stage_tail16(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const float* burn_map, float* out_f32,
                      uint8_t* out_u8, uint16_t* out_u16, int out_gy0, int y0, int y1, int W, int H_global, void* stream) {
-    return stage_tail_impl(ctx, p, density, burn_map, out_f32, out_u8, out_u16, out_gy0, y0, y1, W, H_global, stream);
+    return stage_tail_impl(ctx, p, density, burn_map, HwcOut{out_f32, out_u8, out_u16, out_gy0}, y0, y1, W, H_global, stream);
 }
 
 int r2f_stage_tail_field16(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const r2f_planes* field, float* out_f32,
@@ -653,13 +679,13 @@ int r2f_stage_tail_field16(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* 
     if (!ctx || !p) return R2F_EINVAL;
     R2F_GUARD(ctx);
     if (!field) return fail(ctx, R2F_EINVAL, "tail: null grain field");
-    return run_tail(ctx, p, density, nullptr, nullptr, out_f32, out_u8, out_gy0, y0, y1, W, H_global, stream, field, out_u16);
+    return run_tail(ctx, p, density, nullptr, nullptr, HwcOut{out_f32, out_u8, out_u16, out_gy0}, y0, y1, W, H_global, stream, field);
 }
 
 int r2f_stage_front16(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, int in_gy0, int in_rows, float* out_f32,
                       uint16_t* out_u16, int out_gy0, int y0, int y1, int W, int H_global, void* stream) {
-    return stage_front_impl(ctx, p, in, in_layout, in_gy0, in_rows, R2F_UPTO_OUTPUT, nullptr, out_f32, nullptr, out_gy0, y0, y1, W,
-                            H_global, stream, nullptr, nullptr, nullptr, out_u16);
+    return stage_front_impl(ctx, p, in, in_layout, in_gy0, in_rows, R2F_UPTO_OUTPUT, nullptr, HwcOut{out_f32, nullptr, out_u16, out_gy0}, y0,
+                            y1, W, H_global, stream);
 }
 
 int r2f_stage_grain_field(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* field, int y0, int y1, int W, int H_global,
@@ -667,7 +693,7 @@ int r2f_stage_grain_field(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* f
     if (!ctx || !p) return R2F_EINVAL;
     R2F_GUARD(ctx);
     if (!field) return fail(ctx, R2F_EINVAL, "grain field: null destination");
-    return run_tail(ctx, p, nullptr, field, nullptr, nullptr, nullptr, 0, y0, y1, W, H_global, stream);
+    return run_tail(ctx, p, nullptr, field, nullptr, HwcOut{}, y0, y1, W, H_global, stream);
 }
 
 int r2f_stage_tail_field(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const r2f_planes* field, float* out_f32,
@@ -675,7 +701,7 @@ int r2f_stage_tail_field(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* de
     if (!ctx || !p) return R2F_EINVAL;
     R2F_GUARD(ctx);
     if (!field) return fail(ctx, R2F_EINVAL, "tail: null grain field");
-    return run_tail(ctx, p, density, nullptr, nullptr, out_f32, out_u8, out_gy0, y0, y1, W, H_global, stream, field);
+    return run_tail(ctx, p, density, nullptr, nullptr, HwcOut{out_f32, out_u8, nullptr, out_gy0}, y0, y1, W, H_global, stream, field);
 }
 
 int r2f_stage_grain(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* din, const r2f_planes* dout, int y0, int y1, int W,
@@ -683,7 +709,7 @@ int r2f_stage_grain(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* din, co
     if (!ctx || !p) return R2F_EINVAL;
     R2F_GUARD(ctx);
     if (!dout) return fail(ctx, R2F_EINVAL, "grain: null destination");
-    return run_tail(ctx, p, din, dout, nullptr, nullptr, nullptr, 0, y0, y1, W, H_global, stream);
+    return run_tail(ctx, p, din, dout, nullptr, HwcOut{}, y0, y1, W, H_global, stream);
 }
 
 int r2f_stage_burn_sums(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, float* cell_sums, int y0, int y1, int W,
@@ -780,19 +806,11 @@ int r2f_resize_lanczos4_f32(r2f_ctx* ctx, const void* in, int in_layout, int H, 
         return fail(ctx, R2F_EINVAL, "resize_lanczos4_f32: bad arguments");
     int rc = check_rows(ctx, "lanczos dst", dst, 0, out_h);
     if (rc) return rc;
-    const size_t n_ofs = (size_t)out_w + out_h, n_coef = 8 * n_ofs;
-    const size_t coef_off = (n_ofs * sizeof(int) + 15) / 16 * 16;
-    std::vector<unsigned char> host(coef_off + n_coef * sizeof(float));
-    int* ofs = reinterpret_cast<int*>(host.data());
-    float* coef = reinterpret_cast<float*>(host.data() + coef_off);
-    r2f_lanczos4_table_f32(W, out_w, ofs, coef);
-    r2f_lanczos4_table_f32(H, out_h, ofs + out_w, coef + 8 * (size_t)out_w);
-    rc = upload(ctx, ctx->lanczos_f32_buf, host.data(), host.size());  // (waits for renders in flight, like every table upload)
+    const int *xofs, *yofs;
+    const float *xcoef, *ycoef;
+    rc = ctx->lanczos_f32.tables(ctx, H, W, out_h, out_w, &xofs, &yofs, &xcoef, &ycoef);
     if (rc) return rc;
-    const unsigned char* base = static_cast<const unsigned char*>(ctx->lanczos_f32_buf.p);
-    const int* xofs = reinterpret_cast<const int*>(base);
-    const float* xcoef = reinterpret_cast<const float*>(base + coef_off);
-    R2F_HIP(ctx, launch_lanczos4_f32(in, in_layout, H, W, to_dev(dst), out_h, out_w, xofs, xcoef, xofs + out_w, xcoef + 8 * (size_t)out_w,
+    R2F_HIP(ctx, launch_lanczos4_f32(in, in_layout, H, W, to_dev(dst), out_h, out_w, xofs, xcoef, yofs, ycoef,
                                      static_cast<hipStream_t>(stream)));
     return R2F_OK;
 }
@@ -802,28 +820,12 @@ int r2f_resize_lanczos4_u8(r2f_ctx* ctx, const uint8_t* src_hwc, int H, int W, u
     R2F_GUARD(ctx);
     if (!src_hwc || !dst_hwc || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0)
         return fail(ctx, R2F_EINVAL, "resize_lanczos4: bad arguments");
-    const size_t n_ofs = (size_t)out_w + out_h, n_coef = 8 * n_ofs;
-    const size_t coef_off = (n_ofs * sizeof(int) + 15) / 16 * 16;
-    const int key[4] = {H, W, out_h, out_w};
-    if (memcmp(key, ctx->lanczos_key, sizeof key) != 0 || !ctx->lanczos_buf.p) {
-        std::vector<unsigned char> host(coef_off + n_coef * sizeof(short));
-        int* ofs = reinterpret_cast<int*>(host.data());
-        short* coef = reinterpret_cast<short*>(host.data() + coef_off);
-        r2f_lanczos4_table(W, out_w, ofs, coef);
-        r2f_lanczos4_table(H, out_h, ofs + out_w, coef + 8 * (size_t)out_w);
-        int rc = upload(ctx, ctx->lanczos_buf, host.data(), host.size());
-        if (rc) return rc;
-        memcpy(ctx->lanczos_key, key, sizeof key);
-    }
     LanczosArgs a;
     a.src = src_hwc;
     a.dst = dst_hwc;
     a.H = H, a.W = W, a.out_h = out_h, a.out_w = out_w;
-    const unsigned char* base = static_cast<const unsigned char*>(ctx->lanczos_buf.p);
-    a.xofs = reinterpret_cast<const int*>(base);
-    a.yofs = a.xofs + out_w;
-    a.xcoef = reinterpret_cast<const short*>(base + coef_off);
-    a.ycoef = a.xcoef + 8 * (size_t)out_w;
+    int rc = ctx->lanczos_u8.tables(ctx, H, W, out_h, out_w, &a.xofs, &a.yofs, &a.xcoef, &a.ycoef);
+    if (rc) return rc;
     R2F_HIP(ctx, launch_lanczos4_u8(a, static_cast<hipStream_t>(stream)));
     return R2F_OK;
 }
@@ -835,24 +837,11 @@ int r2f_resize_lanczos4_u16(r2f_ctx* ctx, const uint16_t* src_hwc, int H, int W,
         return fail(ctx, R2F_EINVAL, "resize_lanczos4_u16: bad arguments");
     if ((reinterpret_cast<uintptr_t>(src_hwc) | reinterpret_cast<uintptr_t>(dst_hwc)) & 1u)
         return fail(ctx, R2F_EINVAL, "resize_lanczos4_u16: source and destination must be 2-byte aligned");
-    const size_t n_ofs = (size_t)out_w + out_h, n_coef = 8 * n_ofs;
-    const size_t coef_off = (n_ofs * sizeof(int) + 15) / 16 * 16;
-    const int key[4] = {H, W, out_h, out_w};
-    if (memcmp(key, ctx->lanczos_u16_key, sizeof key) != 0 || !ctx->lanczos_u16_buf.p) {
-        std::vector<unsigned char> host(coef_off + n_coef * sizeof(float));
-        int* ofs = reinterpret_cast<int*>(host.data());
-        float* coef = reinterpret_cast<float*>(host.data() + coef_off);
-        r2f_lanczos4_table_f32(W, out_w, ofs, coef);
-        r2f_lanczos4_table_f32(H, out_h, ofs + out_w, coef + 8 * (size_t)out_w);
-        int rc = upload(ctx, ctx->lanczos_u16_buf, host.data(), host.size());
-        if (rc) return rc;
-        memcpy(ctx->lanczos_u16_key, key, sizeof key);
-    }
-    const unsigned char* base = static_cast<const unsigned char*>(ctx->lanczos_u16_buf.p);
-    const int* xofs = reinterpret_cast<const int*>(base);
-    const float* xcoef = reinterpret_cast<const float*>(base + coef_off);
-    R2F_HIP(ctx, launch_lanczos4_u16(src_hwc, H, W, dst_hwc, out_h, out_w, xofs, xcoef, xofs + out_w, xcoef + 8 * (size_t)out_w,
-                                     static_cast<hipStream_t>(stream)));
+    const int *xofs, *yofs;
+    const float *xcoef, *ycoef;
+    int rc = ctx->lanczos_u16.tables(ctx, H, W, out_h, out_w, &xofs, &yofs, &xcoef, &ycoef);
+    if (rc) return rc;
+    R2F_HIP(ctx, launch_lanczos4_u16(src_hwc, H, W, dst_hwc, out_h, out_w, xofs, xcoef, yofs, ycoef, static_cast<hipStream_t>(stream)));
     return R2F_OK;
 }
 

@@ -69,9 +69,7 @@ struct StencilSet {
 struct RenderGraph {
     const void* in = nullptr;
     int in_layout = 0;
-    float* out_f32 = nullptr;
-    uint8_t* out_u8 = nullptr;
-    uint16_t* out_u16 = nullptr;  // r2f_render16's frames: which output a frame writes is part of its key
+    HwcOut out{};  // which output a frame writes (r2f_render's u8, r2f_render16's u16) is part of its key
     int H = 0, W = 0;
     void* workspace = nullptr;
     r2f_params p{};  // seed zeroed
@@ -82,6 +80,17 @@ struct RenderGraph {
     bool never = false;  // a capture of this entry failed: kernel by kernel from now on
     bool dyn_armed = false;  // the captured halation launches choose their scratch element on the device
 };
+// The LANCZOS4 tables of one geometry on the device, [xofs | yofs | pad to 16 bytes | xcoef | ycoef], kept until another geometry is
+// asked for.  Coef is short (r2f_lanczos4_table: the uint8 resize) or float (r2f_lanczos4_table_f32: the uint16 and float32 ones).
+struct LanczosTables {
+    DeviceBuf buf;
+    int key[4] = {0, 0, 0, 0};  // H, W, out_h, out_w
+    // Make sure `buf` holds this geometry's tables (a new geometry is an upload: it synchronises and moves `generation`) and hand
+    // out where they are.  Defined in r2f_api.hip, for its three resize entries.
+    template <typename Coef>
+    int tables(r2f_ctx* ctx, int H, int W, int out_h, int out_w, const int** xofs, const int** yofs, const Coef** xcoef, const Coef** ycoef);
+};
+
 struct RenderGraphCache {
     std::vector<RenderGraph> graphs;
     // Executable graphs that left the cache (evicted, or dropped because the generation moved) while a replay of them may still be
@@ -162,11 +171,8 @@ struct r2f_ctx {
     float curve_slope_max = 0.f;  // max |d density / d log10 exposure| over the density curve's cells (host copy, r2f_set_curve1d)
     bool frame_dyn_armed = false;  // the last whole-frame render's halation launches carried the rule (r2f_frame_exposure_range)
     bool capturing = false;        // r2f_render is capturing render_launches: the frame-block write stays outside the graph
-    r2f::DeviceBuf lanczos_buf;  // [xofs | yofs | xcoef | ycoef] of the last LANCZOS4 geometry
-    r2f::DeviceBuf lanczos_f32_buf;  // the same for the float32 up-scale before the path
-    int lanczos_key[4] = {0, 0, 0, 0};
-    r2f::DeviceBuf lanczos_u16_buf;  // the float tables of the last uint16 LANCZOS4 geometry (r2f_resize_lanczos4_u16)
-    int lanczos_u16_key[4] = {0, 0, 0, 0};
+    // one per entry point: the float32 up-scale before the path and the final resize of one process() call differ in geometry
+    r2f::LanczosTables lanczos_u8, lanczos_u16, lanczos_f32;
     // the grain stencil as weight pairs for grain_stencil_fixed (small square symmetric kernels), built on first use
     r2f::DeviceBuf grain_fixed_w;
     bool grain_fixed_valid = false;
@@ -276,12 +282,11 @@ int ensure_range_tiles(r2f_ctx* ctx, int H_global, int W);
 int write_frame_params(r2f_ctx* ctx, const r2f_params* p, hipStream_t s, int mode);
 // r2f_stage_front / r2f_stage_front_split; tracked: r2f_render's front call asks whether the exposure range was recorded
 int stage_front_impl(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, int in_gy0, int in_rows, int upto,
-                     const r2f_planes* dst, float* out_f32, uint8_t* out_u8, int out_gy0, int y0, int y1, int W, int H_global,
-                     void* stream, const r2f_planes* finish_dst, int* finished_mask, bool* tracked = nullptr,
-                     uint16_t* out_u16 = nullptr);
-// r2f_stage_tail / r2f_stage_tail16 (out_u16: the 16-bit output, r2f_graph.hip's render16 calls it too)
-int stage_tail_impl(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const float* burn_map, float* out_f32, uint8_t* out_u8,
-                    uint16_t* out_u16, int out_gy0, int y0, int y1, int W, int H_global, void* stream);
+                     const r2f_planes* dst, const HwcOut& out, int y0, int y1, int W, int H_global, void* stream,
+                     const r2f_planes* finish_dst = nullptr, int* finished_mask = nullptr, bool* tracked = nullptr);
+// r2f_stage_tail / r2f_stage_tail16 (r2f_graph.hip's renders call it too)
+int stage_tail_impl(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density, const float* burn_map, const HwcOut& out, int y0, int y1,
+                    int W, int H_global, void* stream);
 
 // r2f_stencil.hip
 constexpr int kFixedMaxR = 11;  // largest unrolled direct form (23 x 23)

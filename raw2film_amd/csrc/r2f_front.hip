@@ -312,15 +312,15 @@ __global__ __launch_bounds__(64 * BY) void front_fast_kernel(const FrontArgs a) 
                 make_float4(b[0], b[1], b[2], b[3]);
             continue;
         }
-        const long long obase = ((long long)(gy - a.out_gy0) * W + x) * 3;
-        if (a.out_f32) {
-            float4* o4 = reinterpret_cast<float4*>(a.out_f32 + obase);
+        const long long obase = ((long long)(gy - a.out.gy0) * W + x) * 3;
+        if (a.out.f32) {
+            float4* o4 = reinterpret_cast<float4*>(a.out.f32 + obase);
             o4[0] = make_float4(r[0], g[0], b[0], r[1]);
             o4[1] = make_float4(g[1], b[1], r[2], g[2]);
             o4[2] = make_float4(b[2], r[3], g[3], b[3]);
         }
-        if (a.out_u8) {
-            uint32_t* o32 = reinterpret_cast<uint32_t*>(a.out_u8 + obase);
+        if (a.out.u8) {
+            uint32_t* o32 = reinterpret_cast<uint32_t*>(a.out.u8 + obase);
             o32[0] = u8_of(r[0]) | (u8_of(g[0]) << 8) | (u8_of(b[0]) << 16) | (u8_of(r[1]) << 24);
             o32[1] = u8_of(g[1]) | (u8_of(b[1]) << 8) | (u8_of(r[2]) << 16) | (u8_of(g[2]) << 24);
             o32[2] = u8_of(b[2]) | (u8_of(r[3]) << 8) | (u8_of(g[3]) << 16) | (u8_of(b[3]) << 24);
@@ -369,7 +369,7 @@ size_t fast_lds_bytes(const FrontArgs& a) {
 
 // Is the pointwise pass of `a` in the fast kernels' domain?
 bool front_fast_eligible(const FrontArgs& a) {
-    if (a.out_u16) return false;  // (the 16-bit output is the generic kernel's)
+    if (a.out.u16) return false;  // (the 16-bit output is the generic kernel's)
     if (!a.vec || a.lut2d.n < 2 || (long long)a.W * 16 >= (1ll << 31) || fast_lds_bytes(a) > 144 * 1024) return false;
     if ((a.upto >= R2F_UPTO_DENSITY || a.finish_mask) && !(a.curve.near && a.curve.m >= 2)) return false;
     if (a.upto == R2F_UPTO_OUTPUT && !(a.lut3d_mode == 0 && a.lut3d.n >= 2 && a.lut3d.n <= 256)) return false;

@@ -13,7 +13,7 @@ static bool same_structure(const RenderGraph& a, const RenderGraph& b) {
     return a.in_layout == b.in_layout && a.H == b.H && a.W == b.W && !memcmp(&a.p, &b.p, sizeof a.p);
 }
 static bool same_entry(const RenderGraph& a, const RenderGraph& b) {
-    return a.in == b.in && a.out_f32 == b.out_f32 && a.out_u8 == b.out_u8 && a.out_u16 == b.out_u16 && a.workspace == b.workspace && same_structure(a, b);
+    return a.in == b.in && a.out == b.out && a.workspace == b.workspace && same_structure(a, b);
 }
 
 RenderGraphCache::~RenderGraphCache() {
@@ -115,8 +115,8 @@ void RenderGraphCache::reap(bool wait) {
 }  // namespace r2f
 
 // The launches of one frame, in order, on stream `stream` (a capturing stream of the context's own or the caller's).
-static int render_launches(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, float* out_f32, uint8_t* out_u8,
-                           uint16_t* out_u16, int H, int W, void* workspace, void* stream) {
+static int render_launches(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, const HwcOut& out, int H, int W,
+                           void* workspace, void* stream) {
     const bool hal = p->flags & R2F_F_HALATION, mtf = p->flags & R2F_F_MTF, grain = p->flags & R2F_F_GRAIN;
     const bool burn = p->flags & R2F_F_BURN;
     const size_t set_floats = plan::plane_set_floats(H, W);
@@ -136,9 +136,9 @@ static int render_launches(r2f_ctx* ctx, const r2f_params* p, const void* in, in
             if (rc) return rc;
         }
         // ... and also records the range of the exposure planes it writes (every row of them)
-        rc = stage_front_impl(ctx, p, in, in_layout, 0, H, R2F_UPTO_EXPOSURE, &A, nullptr, nullptr, 0, 0, H, W, H, stream, &B, &finished, &tracked);
+        rc = stage_front_impl(ctx, p, in, in_layout, 0, H, R2F_UPTO_EXPOSURE, &A, HwcOut{}, 0, H, W, H, stream, &B, &finished, &tracked);
     } else
-        rc = r2f_stage_front(ctx, p, in, in_layout, 0, H, R2F_UPTO_DENSITY, &A, nullptr, nullptr, 0, 0, H, W, H, stream);
+        rc = stage_front_impl(ctx, p, in, in_layout, 0, H, R2F_UPTO_DENSITY, &A, HwcOut{}, 0, H, W, H, stream);
     if (rc) return rc;
     const r2f_planes* cur = &A;
     const r2f_planes* other = &B;
@@ -154,7 +154,7 @@ static int render_launches(r2f_ctx* ctx, const r2f_params* p, const void* in, in
         if (rc) return rc;
         std::swap(cur, other);
     }
-    if (!burn) return stage_tail_impl(ctx, p, cur, nullptr, out_f32, out_u8, out_u16, 0, 0, H, W, H, stream);
+    if (!burn) return stage_tail_impl(ctx, p, cur, nullptr, out, 0, H, W, H, stream);
     // S7: the burn map depends on the whole grained frame -> grain to planes, reduce, blur, then finish
     int sets_used = (hal || mtf) ? 2 : 1;
     if (grain) {
@@ -174,42 +174,41 @@ static int render_launches(r2f_ctx* ctx, const r2f_params* p, const void* in, in
     if (rc) return rc;
     r2f_params q = *p;
     q.flags &= ~(uint32_t)R2F_F_GRAIN;
-    return stage_tail_impl(ctx, &q, cur, map, out_f32, out_u8, out_u16, 0, 0, H, W, H, stream);
+    return stage_tail_impl(ctx, &q, cur, map, out, 0, H, W, H, stream);
 }
 
-// r2f_render (out_u16 = nullptr) and r2f_render16 (out_u8 = nullptr): one graph cache, the output a frame writes in its key
-static int render_impl(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, float* out_f32, uint8_t* out_u8,
-                       uint16_t* out_u16, bool want16, int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
+// r2f_render (out.u16 = nullptr) and r2f_render16 (out.u8 = nullptr): one graph cache, the output a frame writes in its key
+static int render_impl(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, const HwcOut& out, bool want16, int H, int W,
+                       void* workspace, size_t workspace_bytes, void* stream) {
     if (!ctx || !p) return R2F_EINVAL;
     R2F_GUARD(ctx);
     if (H <= 0 || W <= 0) return fail(ctx, R2F_EINVAL, "render: empty frame");
-    if (want16 && !out_u16) return fail(ctx, R2F_EINVAL, "render16: no uint16 output buffer");
+    if (want16 && !out.u16) return fail(ctx, R2F_EINVAL, "render16: no uint16 output buffer");
     const size_t need = r2f_workspace_bytes(p, H, W);
     if (need > workspace_bytes || (need && !workspace)) return fail(ctx, R2F_EINVAL, "render: workspace too small (%zu needed)", need);
     if (need && !aligned16(workspace)) return fail(ctx, R2F_EINVAL, "render: workspace must be 16-byte aligned");
     const bool hal = p->flags & R2F_F_HALATION, mtf = p->flags & R2F_F_MTF, grain = p->flags & R2F_F_GRAIN;
     const bool burn = p->flags & R2F_F_BURN;
     if (!(hal || mtf || grain || burn))  // config "LUTs only": one fused pointwise pass (one submit as it is)
-        return stage_front_impl(ctx, p, in, in_layout, 0, H, R2F_UPTO_OUTPUT, nullptr, out_f32, out_u8, 0, 0, H, W, H, stream, nullptr,
-                                nullptr, nullptr, out_u16);
+        return stage_front_impl(ctx, p, in, in_layout, 0, H, R2F_UPTO_OUTPUT, nullptr, out, 0, H, W, H, stream);
     hipStream_t s = static_cast<hipStream_t>(stream);
     RenderGraphCache& gc = ctx->graphs;
     // per-launch event timing (bench.py's breakdowns) creates and records events per launch: kernel by kernel only
     if (!ctx->opt.render_graph || ctx->opt.timing) {
         ++gc.eager;
-        return render_launches(ctx, p, in, in_layout, out_f32, out_u8, out_u16, H, W, workspace, stream);
+        return render_launches(ctx, p, in, in_layout, out, H, W, workspace, stream);
     }
     if (!gc.retired.empty()) gc.reap(false);
     gc.follow(ctx->generation);
     RenderGraph key;
-    key.in = in, key.in_layout = in_layout, key.out_f32 = out_f32, key.out_u8 = out_u8, key.out_u16 = out_u16, key.H = H, key.W = W, key.workspace = workspace;
+    key.in = in, key.in_layout = in_layout, key.out = out, key.H = H, key.W = W, key.workspace = workspace;
     key.p = *p;
     key.p.seed = 0;
     key.p.flags &= ~(uint32_t)R2F_F_FRAME_RESIDENT;
     int slot = gc.find(key);
     auto eager = [&]() -> int {
         ++gc.eager;
-        const int rc = render_launches(ctx, p, in, in_layout, out_f32, out_u8, out_u16, H, W, workspace, stream);
+        const int rc = render_launches(ctx, p, in, in_layout, out, H, W, workspace, stream);
         gc.follow(ctx->generation);  // this frame built something (a lazy table, a larger scratch): every captured pointer may dangle
         if (rc == R2F_OK) gc.note_eager(key);
         return rc;
@@ -241,7 +240,7 @@ static int render_impl(r2f_ctx* ctx, const r2f_params* p, const void* in, int in
     int rc = R2F_OK;
     if (e == hipSuccess) {
         ctx->capturing = true;
-        rc = render_launches(ctx, &q, in, in_layout, out_f32, out_u8, out_u16, H, W, workspace, gc.cap_stream);
+        rc = render_launches(ctx, &q, in, in_layout, out, H, W, workspace, gc.cap_stream);
         ctx->capturing = false;
         e = hipStreamEndCapture(gc.cap_stream, &graph);
     }
@@ -273,12 +272,12 @@ extern "C" {
 
 int r2f_render(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, float* out_f32, uint8_t* out_u8, int H,
                int W, void* workspace, size_t workspace_bytes, void* stream) {
-    return render_impl(ctx, p, in, in_layout, out_f32, out_u8, nullptr, false, H, W, workspace, workspace_bytes, stream);
+    return render_impl(ctx, p, in, in_layout, HwcOut{out_f32, out_u8, nullptr, 0}, false, H, W, workspace, workspace_bytes, stream);
 }
 
 int r2f_render16(r2f_ctx* ctx, const r2f_params* p, const void* in, int in_layout, float* out_f32, uint16_t* out_u16, int H, int W,
                  void* workspace, size_t workspace_bytes, void* stream) {
-    return render_impl(ctx, p, in, in_layout, out_f32, nullptr, out_u16, true, H, W, workspace, workspace_bytes, stream);
+    return render_impl(ctx, p, in, in_layout, HwcOut{out_f32, nullptr, out_u16, 0}, true, H, W, workspace, workspace_bytes, stream);
 }
 
 int r2f_render_stats(const r2f_ctx* ctx, uint64_t* out4) {

@@ -86,12 +86,12 @@ __device__ __forceinline__ void store_u16x12(uint16_t* o, const uint32_t (&h)[12
     }
 }
 
-// Write `nv` (1..4) consecutive pixels of row `orow` starting at column x, interleaved HWC.
-__device__ __forceinline__ void emit_hwc(float* out_f32, uint8_t* out_u8, uint16_t* out_u16, long long orow, int x, int W, int nv,
-                                         bool vec, const float (&r)[4], const float (&g)[4], const float (&b)[4]) {
-    const long long base = (orow * W + x) * 3;
-    if (out_u16) {  // (2-byte aligned is all it asks: the shape is chosen per row segment, whatever `vec` says about the others)
-        uint16_t* o = out_u16 + base;
+// Write `nv` (1..4) consecutive pixels of global row `gy` starting at column x, interleaved HWC.
+__device__ __forceinline__ void emit_hwc(const HwcOut& out, int gy, int x, int W, int nv, bool vec, const float (&r)[4],
+                                         const float (&g)[4], const float (&b)[4]) {
+    const long long base = ((long long)(gy - out.gy0) * W + x) * 3;
+    if (out.u16) {  // (2-byte aligned is all it asks: the shape is chosen per row segment, whatever `vec` says about the others)
+        uint16_t* o = out.u16 + base;
         if (nv == 4) {
             uint32_t h[12];
 #pragma unroll
@@ -109,8 +109,8 @@ __device__ __forceinline__ void emit_hwc(float* out_f32, uint8_t* out_u8, uint16
             }
         }
     }
-    if (out_f32) {
-        float* o = out_f32 + base;
+    if (out.f32) {
+        float* o = out.f32 + base;
         if (vec && nv == 4) {
             float4* o4 = reinterpret_cast<float4*>(o);
             o4[0] = make_float4(r[0], g[0], b[0], r[1]);
@@ -124,8 +124,8 @@ __device__ __forceinline__ void emit_hwc(float* out_f32, uint8_t* out_u8, uint16
             }
         }
     }
-    if (out_u8) {
-        uint8_t* o = out_u8 + base;
+    if (out.u8) {
+        uint8_t* o = out.u8 + base;
         if (vec && nv == 4) {
             uint32_t q[12];
 #pragma unroll
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(64 * kFrontBY) void front_kernel(const FrontArgs a)
             if (a.upto == R2F_UPTO_OUTPUT) apply_lut3d(a.lut3d, a.lut3d_scale, a.lut3d_mode, r[q], g[q], b[q]);
         }
         if (a.upto == R2F_UPTO_OUTPUT)
-            emit_hwc(a.out_f32, a.out_u8, a.out_u16, gy - a.out_gy0, x, W, nv, vec, r, g, b);
+            emit_hwc(a.out, gy, x, W, nv, vec, r, g, b);
         else
             store_planes4(a.dst, gy, x, W, nv, vec, r, g, b);
     }
@@ -296,10 +296,8 @@ __global__ __launch_bounds__(64 * kFrontBY) void front_kernel(const FrontArgs a)
 // ------------------------------------------------------------------------------ lut3d
 struct Lut3dArgs {
     DevPlanes src;
-    float* out_f32;
-    uint8_t* out_u8;
-    uint16_t* out_u16;
-    int out_gy0, y0, y1, W;
+    HwcOut out;
+    int y0, y1, W;
     DevLut3D lut3d;
     float lut3d_scale;
     int lut3d_mode;
@@ -355,7 +353,7 @@ __global__ __launch_bounds__(256) void lut3d_kernel(const Lut3dArgs a) {
         }
         apply_lut3d(a.lut3d, a.lut3d_scale, a.lut3d_mode, r[q], g[q], b[q]);
     }
-    emit_hwc(a.out_f32, a.out_u8, a.out_u16, gy - a.out_gy0, x, a.W, nv, a.vec != 0, r, g, b);
+    emit_hwc(a.out, gy, x, a.W, nv, a.vec != 0, r, g, b);
 }
 
 // ------------------------------------------------------------------------------ stencil
@@ -760,7 +758,7 @@ __global__ __launch_bounds__(kTailBX* kTailBY) void tail_kernel(const TailArgs a
         if (a.to_planes)
             store_planes4(a.dst, gy, gx, a.W, nv, vec, r, g, b);
         else
-            emit_hwc(a.out_f32, a.out_u8, a.out_u16, gy - a.out_gy0, gx, a.W, nv, vec, r, g, b);
+            emit_hwc(a.out, gy, gx, a.W, nv, vec, r, g, b);
     }
 }
 
@@ -1284,10 +1282,7 @@ hipError_t launch_tail(const TailArgs& a, hipStream_t s) {
     if (!a.grain) {
         Lut3dArgs l;
         l.src = a.src;
-        l.out_f32 = a.out_f32;
-        l.out_u8 = a.out_u8;
-        l.out_u16 = a.out_u16;
-        l.out_gy0 = a.out_gy0;
+        l.out = a.out;
         l.y0 = a.y0;
         l.y1 = a.y1;
         l.W = a.W;

@@ -34,16 +34,26 @@ inline hipError_t take_launch_status() {
     return e;
 }
 
+// One interleaved (H, W, 3) output: any of the three element types (the uint16 form is clip(x * 65535, 0, 65535) truncated, from the
+// float `f32` would hold), and the global row its row 0 stands for.
+struct HwcOut {
+    float* f32;
+    uint8_t* u8;
+    uint16_t* u16;
+    int gy0;
+    __host__ __device__ bool any() const { return f32 || u8 || u16; }
+    // the float4 / packed-uint32 stores want their bases aligned (u16 chooses its store shape per row segment: no part in this)
+    __host__ __device__ bool vec_ok() const { return !(reinterpret_cast<uintptr_t>(f32) & 15u) && !(reinterpret_cast<uintptr_t>(u8) & 3u); }
+    __host__ __device__ bool operator==(const HwcOut& o) const { return f32 == o.f32 && u8 == o.u8 && u16 == o.u16 && gy0 == o.gy0; }
+};
+
 struct FrontArgs {
     const void* in;
     int in_layout;  // R2F_LAYOUT_*
     int in_gy0, in_rows;
     int upto;  // R2F_UPTO_*
     DevPlanes dst;
-    float* out_f32;
-    uint8_t* out_u8;
-    uint16_t* out_u16;  // upto = OUTPUT: the 16-bit form of out_u8 (generic kernel only)
-    int out_gy0;
+    HwcOut out;  // upto = OUTPUT (u16: generic kernel only)
     int y0, y1, W, H_global;
     int use_matrix;
     Mat3 mat;
@@ -117,10 +127,7 @@ struct BurnMapArgs {
 
 struct TailArgs {
     DevPlanes src;
-    float* out_f32;
-    uint8_t* out_u8;
-    uint16_t* out_u16;  // (H, W, 3) uint16: clip(x * 65535, 0, 65535) truncated, from the float out_f32 would hold
-    int out_gy0;
+    HwcOut out;
     int y0, y1, W, H_global;
     int grain;  // 0/1
     int to_planes;  // 1: stop after grain + clip and write density planes `dst` (S7 needs the whole grained frame);

@@ -247,7 +247,106 @@ def test_odd_addresses_are_refused(ctx, densities):
     assert rc == _lib.EINVAL
 
 
+def test_bad_outputs_are_refused_by_every_entry_that_writes_one(ctx):
+    """No output at all, a row range that starts above the output buffer, an odd uint16 address: every case is refused with its
+    message before anything is launched."""
+    import ctypes as C
+
+    from raw2film_amd import _lib
+
+    H, W = 8, 12
+    params = setup_ctx(ctx, wide_inputs(0))
+    D = torch.zeros((3, H, W), dtype=torch.float32, device="cuda")
+    pd = ctx.planes(D, 0)
+    img = dev(synthetic_frame(H, W, seed=7))
+    f32 = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+    u8 = torch.empty((H, W, 3), dtype=torch.uint8, device="cuda")
+    raw = torch.empty(H * W * 6 + 2, dtype=torch.uint8, device="cuda")
+    lib, h, s = ctx._lib, ctx._h, ctx._stream()
+    # entry -> (call(out_f32, second output, out_gy0, y0), is it a 16-bit entry, what it says about rows above the buffer)
+    entries = {
+        "r2f_stage_tail": (lambda o32, o, gy0, y0: lib.r2f_stage_tail(h, C.byref(params), C.byref(pd), None, o32, o, gy0, y0, H, W, H, s),
+                           False, b"bad geometry"),
+        "r2f_stage_tail16": (lambda o32, o, gy0, y0: lib.r2f_stage_tail16(h, C.byref(params), C.byref(pd), None, o32, None, o, gy0, y0, H, W,
+                                                                          H, s), True, b"bad geometry"),
+        "r2f_stage_front": (lambda o32, o, gy0, y0: lib.r2f_stage_front(h, C.byref(params), img.data_ptr(), 0, 0, H, _lib.UPTO_OUTPUT, None,
+                                                                        o32, o, gy0, y0, H, W, H, s), False, b"y0 above the output buffer"),
+        "r2f_stage_front16": (lambda o32, o, gy0, y0: lib.r2f_stage_front16(h, C.byref(params), img.data_ptr(), 0, 0, H, o32, o, gy0, y0, H,
+                                                                            W, H, s), True, b"y0 above the output buffer"),
+    }
+    for name, (call, wide, above) in entries.items():
+        good = raw.data_ptr() if wide else u8.data_ptr()
+        assert call(None, None, 0, 0) == _lib.EINVAL and b"no output buffer" in lib.r2f_last_error(h), name
+        for o32, o in ((f32.data_ptr(), None), (None, good), (f32.data_ptr(), good)):
+            assert call(o32, o, 3, 2) == _lib.EINVAL and above in lib.r2f_last_error(h), name
+        if wide:
+            for o32 in (None, f32.data_ptr()):
+                assert call(o32, raw.data_ptr() + 1, 0, 0) == _lib.EINVAL and b"2-byte aligned" in lib.r2f_last_error(h), name
+        assert call(f32.data_ptr(), good, 0, 0) == 0, name  # (the same arguments with a good output: accepted)
+    torch.cuda.synchronize()
+
+
+def test_one_tail_call_writes_all_three_outputs(ctx, densities):
+    """f32, u8 and u16 of ONE r2f_stage_tail16 call are what three calls with one output each write, the integer ones are the float
+    one quantised, and the two rows of each buffer above y0 are left alone (out_gy0 = 3, y0 = 5: odd width, 2- and 4-byte edge
+    stores)."""
+    H, W, gy0, y0, y1 = 70, 257, 3, 5, 70
+    params = setup_ctx(ctx, wide_inputs(0))
+    D = to_planes(densities[(H, W)])
+    kinds = (("out_f32", torch.float32), ("out_u8", torch.uint8), ("out_u16", torch.int16))
+    together = {k: Arena.hwc(H - gy0, W, dt, device="cuda") for k, dt in kinds}
+    ctx.stage_tail16(D, params, out_gy0=gy0, y0=y0, y1=y1, H_global=H, **{k: a.view for k, a in together.items()})
+    written = [(None, (y0 - gy0, y1 - gy0))]
+    for k, dt in kinds:
+        alone = Arena.hwc(H - gy0, W, dt, device="cuda")
+        ctx.stage_tail16(D, params, out_gy0=gy0, y0=y0, y1=y1, H_global=H, **{k: alone.view})
+        alone.check(written, expected=alone.view.cpu(), what=f"{k} alone")
+        together[k].check(written, expected=alone.view.cpu(), what=f"{k} beside the other two")  # (rows 3 and 4: the canary)
+        bits = torch.int32 if dt == torch.float32 else dt
+        assert torch.equal(together[k].buf.view(bits), alone.buf.view(bits)), f"{k}: not what the call with only it writes"
+    own = together["out_f32"].view.cpu().numpy()[y0 - gy0:]
+    assert own.min() < 0 and own.max() > 1, "the frame must drive both clamps"
+    assert np.array_equal(u16(together["out_u16"].view)[y0 - gy0:], to_uint16(own))
+    assert np.array_equal(together["out_u8"].view.cpu().numpy()[y0 - gy0:], st.to_uint8(own))
+
+
 # ------------------------------------------------------------------------------- resamplers
+def test_lanczos4_tables_one_cache_per_entry_and_a_key_for_the_f32_one(ctx):
+    """The float32, uint16 and uint8 LANCZOS4 resizes keep one table cache each: none evicts another's, a repeated float32 call at
+    an unchanged geometry uploads nothing (`generation` stays) and a new geometry does.  Every result is compared bit for bit with
+    its entry's model; a stale or shared key shows as a wrong image."""
+    post = __import__("oracle.post", fromlist=["post"])
+    img32 = np.random.default_rng(95).uniform(0, 4, (13, 17, 3)).astype(np.float32)
+    img16 = frame16(11, 9, seed=1)
+    img8 = np.random.default_rng(9).integers(0, 256, (9, 14, 3)).astype(np.uint8)
+    t32, t16, t8 = dev(img32), dev(img16.view(np.int16)), dev(img8)
+
+    def f32(oh, ow):
+        got = ctx.resize_lanczos4_f32(t32, oh, ow).cpu().numpy().transpose(1, 2, 0)
+        np.testing.assert_array_equal(got, post.resize_lanczos4_f32(img32, oh, ow))
+        return got
+
+    def wide():
+        np.testing.assert_array_equal(u16(ctx.resize_lanczos4_u16(t16, 20, 33)), lanczos4_u16(img16, 20, 33))
+
+    def narrow():
+        np.testing.assert_array_equal(ctx.resize_lanczos4_u8(t8, 25, 19).cpu().numpy(), st.resize_lanczos4_u8(img8, 25, 19))
+
+    first = f32(29, 23)  # (i)
+    gen = ctx.generation()
+    again = f32(29, 23)  # (ii)
+    assert ctx.generation() == gen, "a repeated float32 resize at an unchanged geometry uploaded its tables again"
+    assert np.array_equal(first.view(np.int32), again.view(np.int32))
+    wide()  # (iii)
+    narrow()  # (iv)
+    f32(29, 23)  # (v)
+    gen = ctx.generation()
+    f32(31, 40)  # (vi)
+    assert ctx.generation() != gen, "a new geometry must upload its tables"
+    f32(29, 23)  # (vii)
+    wide(), narrow()  # (viii)
+
+
 def frame16(H, W, seed):
     """0, 65535, steps and noise: the LANCZOS4 overshoot saturates at both ends."""
     rng = np.random.default_rng(seed)
