@@ -1,6 +1,7 @@
-// r2f_api.hip -- C ABI (include/r2f.h) over the gfx950 kernels: context, options, table and stencil upload, the stage entry
-// points and the resize / blit / histogram / decode entries.  The stencil dispatch (r2f_stencil.hip), the whole-frame render with
-// its graph cache (r2f_graph.hip) and the JPEG entries (r2f_jpeg_api.hip) are units of their own; r2f_ctx.h is what they share.
+// r2f_api.hip -- C ABI (include/r2f.h) over the gfx950 kernels: context, options, table and stencil upload and the stage entry
+// points of the render path.  The stencil dispatch (r2f_stencil.hip), the whole-frame render with its graph cache (r2f_graph.hip),
+// the JPEG entries (r2f_jpeg_api.hip) and the stages off the path with their entries (r2f_resample.hip, r2f_post.hip) are units of
+// their own; r2f_ctx.h is what they share.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -44,32 +45,6 @@ int upload(r2f_ctx* ctx, DeviceBuf& buf, const void* host, size_t bytes) {
     if (rc) return rc;
     R2F_HIP(ctx, hipMemcpy(buf.p, host, bytes, hipMemcpyHostToDevice));
     ++ctx->generation;
-    return R2F_OK;
-}
-
-static void lanczos4_table(int n, int out_n, int* ofs, short* coef) { r2f_lanczos4_table(n, out_n, ofs, coef); }
-static void lanczos4_table(int n, int out_n, int* ofs, float* coef) { r2f_lanczos4_table_f32(n, out_n, ofs, coef); }
-
-template <typename Coef>
-int LanczosTables::tables(r2f_ctx* ctx, int H, int W, int out_h, int out_w, const int** xofs, const int** yofs, const Coef** xcoef,
-                          const Coef** ycoef) {
-    const size_t n_ofs = (size_t)out_w + out_h, coef_off = (n_ofs * sizeof(int) + 15) / 16 * 16;
-    const int want[4] = {H, W, out_h, out_w};
-    if (memcmp(want, key, sizeof key) != 0 || !buf.p) {
-        std::vector<unsigned char> host(coef_off + 8 * n_ofs * sizeof(Coef));
-        int* ofs = reinterpret_cast<int*>(host.data());
-        Coef* coef = reinterpret_cast<Coef*>(host.data() + coef_off);
-        lanczos4_table(W, out_w, ofs, coef);
-        lanczos4_table(H, out_h, ofs + out_w, coef + 8 * (size_t)out_w);
-        int rc = upload(ctx, buf, host.data(), host.size());  // (waits for renders in flight, like every table upload)
-        if (rc) return rc;
-        memcpy(key, want, sizeof key);
-    }
-    const unsigned char* base = static_cast<const unsigned char*>(buf.p);
-    *xofs = reinterpret_cast<const int*>(base);
-    *yofs = *xofs + out_w;
-    *xcoef = reinterpret_cast<const Coef*>(base + coef_off);
-    *ycoef = *xcoef + 8 * (size_t)out_w;
     return R2F_OK;
 }
 
@@ -755,286 +730,6 @@ int r2f_stage_burn_map(r2f_ctx* ctx, const r2f_params* p, const float* cell_sums
     return R2F_OK;
 }
 
-int r2f_resize_area(r2f_ctx* ctx, const void* in, int in_layout, int H, int W, const r2f_planes* dst, int out_h, int out_w,
-                    void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (!in || in_layout < 0 || in_layout > 2 || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0 || out_h > H || out_w > W)
-        return fail(ctx, R2F_EINVAL, "resize_area: the target must be a non-empty frame no larger than the source");
-    int rc = check_rows(ctx, "resize dst", dst, 0, out_h);
-    if (rc) return rc;
-    ResizeArgs a;
-    a.in = in;
-    a.in_layout = in_layout;
-    a.H = H;
-    a.W = W;
-    a.dst = to_dev(dst);
-    a.out_h = out_h;
-    a.out_w = out_w;
-    R2F_HIP(ctx, launch_resize_area(a, static_cast<hipStream_t>(stream)));
-    return R2F_OK;
-}
-
-int r2f_warp_affine(r2f_ctx* ctx, const void* in, int in_layout, int H, int W, const double* m_dst_to_src, const r2f_planes* dst,
-                    int out_h, int out_w, int oy, int ox, void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (!in || !m_dst_to_src || in_layout < 0 || in_layout > 2 || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0)
-        return fail(ctx, R2F_EINVAL, "warp_affine: bad arguments");
-    int rc = check_rows(ctx, "warp dst", dst, 0, out_h);
-    if (rc) return rc;
-    WarpArgs a;
-    a.in = in;
-    a.in_layout = in_layout;
-    a.H = H;
-    a.W = W;
-    a.dst = to_dev(dst);
-    a.out_h = out_h;
-    a.out_w = out_w;
-    a.oy = oy;
-    a.ox = ox;
-    for (int i = 0; i < 6; ++i) a.m[i] = (float)m_dst_to_src[i];
-    R2F_HIP(ctx, launch_warp_affine(a, static_cast<hipStream_t>(stream)));
-    return R2F_OK;
-}
-
-int r2f_resize_lanczos4_f32(r2f_ctx* ctx, const void* in, int in_layout, int H, int W, const r2f_planes* dst, int out_h, int out_w,
-                            void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (!in || in_layout < 0 || in_layout > 2 || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0)
-        return fail(ctx, R2F_EINVAL, "resize_lanczos4_f32: bad arguments");
-    int rc = check_rows(ctx, "lanczos dst", dst, 0, out_h);
-    if (rc) return rc;
-    const int *xofs, *yofs;
-    const float *xcoef, *ycoef;
-    rc = ctx->lanczos_f32.tables(ctx, H, W, out_h, out_w, &xofs, &yofs, &xcoef, &ycoef);
-    if (rc) return rc;
-    R2F_HIP(ctx, launch_lanczos4_f32(in, in_layout, H, W, to_dev(dst), out_h, out_w, xofs, xcoef, yofs, ycoef,
-                                     static_cast<hipStream_t>(stream)));
-    return R2F_OK;
-}
-
-int r2f_resize_lanczos4_u8(r2f_ctx* ctx, const uint8_t* src_hwc, int H, int W, uint8_t* dst_hwc, int out_h, int out_w, void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (!src_hwc || !dst_hwc || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0)
-        return fail(ctx, R2F_EINVAL, "resize_lanczos4: bad arguments");
-    LanczosArgs a;
-    a.src = src_hwc;
-    a.dst = dst_hwc;
-    a.H = H, a.W = W, a.out_h = out_h, a.out_w = out_w;
-    int rc = ctx->lanczos_u8.tables(ctx, H, W, out_h, out_w, &a.xofs, &a.yofs, &a.xcoef, &a.ycoef);
-    if (rc) return rc;
-    R2F_HIP(ctx, launch_lanczos4_u8(a, static_cast<hipStream_t>(stream)));
-    return R2F_OK;
-}
-
-int r2f_resize_lanczos4_u16(r2f_ctx* ctx, const uint16_t* src_hwc, int H, int W, uint16_t* dst_hwc, int out_h, int out_w, void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (!src_hwc || !dst_hwc || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0)
-        return fail(ctx, R2F_EINVAL, "resize_lanczos4_u16: bad arguments");
-    if ((reinterpret_cast<uintptr_t>(src_hwc) | reinterpret_cast<uintptr_t>(dst_hwc)) & 1u)
-        return fail(ctx, R2F_EINVAL, "resize_lanczos4_u16: source and destination must be 2-byte aligned");
-    const int *xofs, *yofs;
-    const float *xcoef, *ycoef;
-    int rc = ctx->lanczos_u16.tables(ctx, H, W, out_h, out_w, &xofs, &yofs, &xcoef, &ycoef);
-    if (rc) return rc;
-    R2F_HIP(ctx, launch_lanczos4_u16(src_hwc, H, W, dst_hwc, out_h, out_w, xofs, xcoef, yofs, ycoef, static_cast<hipStream_t>(stream)));
-    return R2F_OK;
-}
-
-int r2f_resize_area_u16(r2f_ctx* ctx, const uint16_t* src_hwc, int H, int W, uint16_t* dst_hwc, int out_h, int out_w, void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (!src_hwc || !dst_hwc || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0 || out_h > H || out_w > W)
-        return fail(ctx, R2F_EINVAL, "resize_area_u16: the target must be a non-empty frame no larger than the source");
-    if ((reinterpret_cast<uintptr_t>(src_hwc) | reinterpret_cast<uintptr_t>(dst_hwc)) & 1u)
-        return fail(ctx, R2F_EINVAL, "resize_area_u16: source and destination must be 2-byte aligned");
-    R2F_HIP(ctx, launch_resize_area_u16(src_hwc, H, W, dst_hwc, out_h, out_w, static_cast<hipStream_t>(stream)));
-    return R2F_OK;
-}
-
-int r2f_resize_area_u8(r2f_ctx* ctx, const uint8_t* src_hwc, int H, int W, uint8_t* dst_hwc, int out_h, int out_w, void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (!src_hwc || !dst_hwc || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0 || out_h > H || out_w > W)
-        return fail(ctx, R2F_EINVAL, "resize_area_u8: the target must be a non-empty frame no larger than the source");
-    R2F_HIP(ctx, launch_resize_area_u8(src_hwc, H, W, dst_hwc, out_h, out_w, static_cast<hipStream_t>(stream)));
-    return R2F_OK;
-}
-
-int r2f_decode_u16(r2f_ctx* ctx, const uint16_t* src_hwc, int H, int W, int channels, float divisor, float factor, float* dst_f32_hwc3,
-                   void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (!src_hwc || !dst_f32_hwc3 || H <= 0 || W <= 0 || (channels != 3 && channels != 4) || !(divisor > 0.f))
-        return fail(ctx, R2F_EINVAL, "decode_u16: a non-empty 3- or 4-channel frame and a positive divisor are required");
-    R2F_HIP(ctx, launch_decode_u16(src_hwc, (long long)H * W, channels, divisor, factor, dst_f32_hwc3, static_cast<hipStream_t>(stream)));
-    return R2F_OK;
-}
-
-// ------------------------------------------------------------------------------- auto exposure on the device
-static bool exposure_root_ok(double root) { return root >= 1.0 && root <= 1.0e6; }  // (calc_exposure's is sqrt(...) + 1; NaN fails)
-
-int r2f_exposure_rows(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int H, int W, int channels, int y0, int y1,
-                      double root, void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (!src_rows || H <= 0 || W <= 0 || (channels != 3 && channels != 4) || !exposure_root_ok(root))
-        return fail(ctx, R2F_EINVAL, "exposure_rows: a non-empty 3- or 4-channel frame and a root in [1, 1e6] are required");
-    if (y0 < 0 || y1 > H || y0 > y1 || src_gy0 < 0 || src_nrows < 0 || y0 < src_gy0 || (long long)y1 > (long long)src_gy0 + src_nrows)
-        return fail(ctx, R2F_EINVAL, "exposure_rows: rows [%d, %d) not inside the frame's [0, %d) and the buffer's [%d, %lld)", y0, y1, H,
-                    src_gy0, (long long)src_gy0 + src_nrows);
-    const int n_rows = (H + 1) / 2;
-    if (n_rows > ctx->exposure.rows_cap) {  // a taller frame: the sums of a shorter one are not kept (its finish has been queued)
-        int rc = ctx->exposure.sums.reserve(ctx, (size_t)n_rows * sizeof(double), Grow::Sync);
-        if (rc) return rc;
-        ctx->exposure.rows_cap = n_rows;
-    }
-    R2F_HIP(ctx, launch_exposure_rows(src_rows, src_gy0, W, channels, y0, y1, root, static_cast<double*>(ctx->exposure.sums.p),
-                                      static_cast<hipStream_t>(stream)));
-    return R2F_OK;
-}
-
-int r2f_exposure_finish(r2f_ctx* ctx, int H, int W, double root, double ref_exposure, void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (H <= 0 || W <= 0 || !exposure_root_ok(root) || !(ref_exposure > 0.0))
-        return fail(ctx, R2F_EINVAL, "exposure_finish: a non-empty frame, a root in [1, 1e6] and a positive reference are required");
-    auto& ex = ctx->exposure;
-    if ((H + 1) / 2 > ex.rows_cap) return fail(ctx, R2F_EINVAL, "exposure_finish: no row sums of a frame of %d rows (r2f_exposure_rows)", H);
-    // (each under its own check: one that failed is tried again by the next call, and nothing is used before it exists)
-    if (!ex.stream) R2F_HIP(ctx, hipStreamCreateWithFlags(&ex.stream, hipStreamNonBlocking));
-    if (!ex.done) R2F_HIP(ctx, hipEventCreateWithFlags(&ex.done, hipEventDisableTiming));
-    if (!ex.host) R2F_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ex.host), sizeof(ExposureRecord), hipHostMallocDefault));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    R2F_HIP(ctx, launch_exposure_finish(static_cast<const double*>(ex.sums.p), H, W, root, ref_exposure,
-                                        static_cast<ExposureRecord*>(ex.rec.p), s));
-    R2F_HIP(ctx, hipEventRecord(ex.done, s));
-    R2F_HIP(ctx, hipStreamWaitEvent(ex.stream, ex.done, 0));
-    R2F_HIP(ctx, hipMemcpyAsync(ex.host, ex.rec.p, sizeof(ExposureRecord), hipMemcpyDeviceToHost, ex.stream));
-    ex.measured = true;
-    return R2F_OK;
-}
-
-int r2f_decode_u16_auto(r2f_ctx* ctx, const uint16_t* src_hwc, int H, int W, int channels, int64_t src_pitch, float divisor,
-                        float* dst_f32_hwc3, void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (!src_hwc || !dst_f32_hwc3 || H <= 0 || W <= 0 || (channels != 3 && channels != 4) || !(divisor > 0.f) || src_pitch < W)
-        return fail(ctx, R2F_EINVAL, "decode_u16_auto: a non-empty 3- or 4-channel frame, a pitch of at least W pixels and a positive "
-                                     "divisor are required");
-    if (!ctx->exposure.measured) return fail(ctx, R2F_EINVAL, "decode_u16_auto: no exposure has been measured (r2f_exposure_finish)");
-    R2F_HIP(ctx, launch_decode_u16_auto(src_hwc, H, W, channels, src_pitch, divisor, static_cast<const ExposureRecord*>(ctx->exposure.rec.p),
-                                        dst_f32_hwc3, static_cast<hipStream_t>(stream)));
-    return R2F_OK;
-}
-
-int r2f_exposure_result(r2f_ctx* ctx, double* stops, float* factor) {
-    if (!ctx || !stops || !factor) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (!ctx->exposure.measured) return fail(ctx, R2F_EINVAL, "exposure_result: no exposure has been measured (r2f_exposure_finish)");
-    R2F_HIP(ctx, hipStreamSynchronize(ctx->exposure.stream));  // (behind the last finish kernel, not behind what was queued after it)
-    *stops = ctx->exposure.host->stops;
-    *factor = ctx->exposure.host->factor;
-    return R2F_OK;
-}
-
-int r2f_stream_copy(r2f_ctx* ctx, const void* src, void* dst, size_t bytes, void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (!src || !dst || bytes % 16 != 0 || !aligned16(src) || !aligned16(dst))
-        return fail(ctx, R2F_EINVAL, "stream_copy: 16-byte aligned buffers and a multiple of 16 bytes are required");
-    R2F_HIP(ctx, launch_stream_copy(src, dst, (long long)bytes, static_cast<hipStream_t>(stream)));
-    return R2F_OK;
-}
-
-int r2f_blit_rgba8(r2f_ctx* ctx, const float* src_f32_hwc, int H, int W, uint8_t* dst_rgba, int dst_h, int dst_w, const r2f_blit* t,
-                   void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (!src_f32_hwc || !dst_rgba || !t || H <= 0 || W <= 0 || dst_h <= 0 || dst_w <= 0)
-        return fail(ctx, R2F_EINVAL, "blit: bad arguments");
-    if (reinterpret_cast<uintptr_t>(dst_rgba) & 3u) return fail(ctx, R2F_EINVAL, "blit: the destination must be 4-byte aligned");
-    R2F_HIP(ctx, launch_blit_rgba8(src_f32_hwc, H, W, dst_rgba, dst_h, dst_w, *t, static_cast<hipStream_t>(stream)));
-    return R2F_OK;
-}
-
-int r2f_histogram_render(r2f_ctx* ctx, const uint32_t* counts, const uint8_t* mix_table_rgba, int height, uint8_t* image_rgba,
-                         uint8_t* target_rgba, int target_h, int target_w, void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (!counts || !mix_table_rgba || !image_rgba || height <= 0 || (target_rgba && (target_h <= 0 || target_w <= 0)))
-        return fail(ctx, R2F_EINVAL, "histogram_render: bad arguments");
-    if ((reinterpret_cast<uintptr_t>(image_rgba) & 3u) || (reinterpret_cast<uintptr_t>(target_rgba) & 3u))
-        return fail(ctx, R2F_EINVAL, "histogram_render: images must be 4-byte aligned");
-    R2F_HIP(ctx, launch_histogram_render(counts, mix_table_rgba, height, image_rgba, target_rgba, target_h, target_w,
-                                         static_cast<hipStream_t>(stream)));
-    return R2F_OK;
-}
-
-static int chroma_weights(r2f_ctx* ctx, int size, ChromaArgs& a) {
-    static_assert(kChromaMaxTaps == plan::kChromaMaxTaps, "one tap limit");
-    if (!plan::chroma_weights(size, a.w)) return fail(ctx, R2F_EINVAL, "chroma_nr size must be in [1, %d]", (kChromaMaxTaps - 1) / 2);
-    a.radius = size;
-    return R2F_OK;
-}
-
-int r2f_stage_chroma_nr_h(r2f_ctx* ctx, const void* in, int in_layout, int in_gy0, int in_rows, const r2f_planes* dst, int size,
-                          int y0, int y1, int W, void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (y1 <= y0) return R2F_OK;
-    if (!in || W <= 0 || y0 < in_gy0 || y1 > in_gy0 + in_rows || in_layout < 0 || in_layout > 2)
-        return fail(ctx, R2F_EINVAL, "chroma_nr: bad input geometry");
-    ChromaArgs a;
-    memset(&a, 0, sizeof a);
-    int rc = chroma_weights(ctx, size, a);
-    if (rc) return rc;
-    rc = check_rows(ctx, "chroma_nr dst", dst, y0, y1);
-    if (rc) return rc;
-    a.in = in;
-    a.in_layout = in_layout;
-    a.in_gy0 = in_gy0;
-    a.in_rows = in_rows;
-    a.dst = to_dev(dst);
-    a.y0 = y0;
-    a.y1 = y1;
-    a.W = W;
-    a.H_global = in_gy0 + in_rows;
-    a.vec = planes_vec_ok(dst, W) ? 1 : 0;
-    R2F_HIP(ctx, launch_chroma_h(a, static_cast<hipStream_t>(stream)));
-    return R2F_OK;
-}
-
-int r2f_stage_chroma_nr_v(r2f_ctx* ctx, const r2f_planes* src, const r2f_planes* dst, int size, int y0, int y1, int W,
-                          int H_global, void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (y1 <= y0) return R2F_OK;
-    if (W <= 0 || y0 < 0 || y1 > H_global) return fail(ctx, R2F_EINVAL, "chroma_nr: bad geometry");
-    ChromaArgs a;
-    memset(&a, 0, sizeof a);
-    int rc = chroma_weights(ctx, size, a);
-    if (rc) return rc;
-    rc = check_rows(ctx, "chroma_nr dst", dst, y0, y1);
-    if (rc) return rc;
-    rc = check_rows(ctx, "chroma_nr src", src, std::max(y0 - size, 0), std::min(y1 + size, H_global));
-    if (rc) return rc;
-    if (planes_overlap(src, dst, W)) return fail(ctx, R2F_EINVAL, "chroma_nr: source and destination planes overlap (out of place only)");
-    a.src = to_dev(src);
-    a.dst = to_dev(dst);
-    a.y0 = y0;
-    a.y1 = y1;
-    a.W = W;
-    a.H_global = H_global;
-    a.vec = (planes_vec_ok(src, W) && planes_vec_ok(dst, W)) ? 1 : 0;
-    R2F_HIP(ctx, launch_chroma_v(a, static_cast<hipStream_t>(stream)));
-    return R2F_OK;
-}
-
 int r2f_stage_noise(r2f_ctx* ctx, const r2f_params* p, uint32_t* hash_planes, float* noise_planes, int y0, int y1, int W,
                     void* stream) {
     if (!ctx || !p) return R2F_EINVAL;
@@ -1052,15 +747,6 @@ int r2f_stage_noise(r2f_ctx* ctx, const r2f_params* p, uint32_t* hash_planes, fl
         if (rc) return rc;
     }
     R2F_HIP(ctx, launch_noise(a, static_cast<hipStream_t>(stream)));
-    return R2F_OK;
-}
-
-int r2f_histogram_u8(r2f_ctx* ctx, const uint8_t* image_hwc, int H, int W, uint32_t* counts, void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
-    if (!counts || H < 0 || W < 0 || (!image_hwc && H > 0 && W > 0)) return fail(ctx, R2F_EINVAL, "histogram: bad arguments");
-    if (!aligned16(image_hwc)) return fail(ctx, R2F_EINVAL, "histogram: image must be 16-byte aligned");
-    R2F_HIP(ctx, launch_histogram_u8(image_hwc, (long long)H * W * 3, counts, static_cast<hipStream_t>(stream)));
     return R2F_OK;
 }
 

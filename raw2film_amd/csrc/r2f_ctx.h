@@ -1,4 +1,5 @@
-// r2f_ctx.h -- what the host units of the library share (r2f_api.hip, r2f_stencil.hip, r2f_graph.hip, r2f_jpeg_api.hip): the
+// r2f_ctx.h -- what the host units of the library share (r2f_api.hip, r2f_stencil.hip, r2f_graph.hip, r2f_jpeg_api.hip and the
+// entries of r2f_resample.hip and r2f_post.hip): the
 // context, its owned device buffers, the error and device-binding macros, and the functions one unit calls in another.
 #pragma once
 
@@ -86,9 +87,16 @@ struct LanczosTables {
     DeviceBuf buf;
     int key[4] = {0, 0, 0, 0};  // H, W, out_h, out_w
     // Make sure `buf` holds this geometry's tables (a new geometry is an upload: it synchronises and moves `generation`) and hand
-    // out where they are.  Defined in r2f_api.hip, for its three resize entries.
+    // out where they are.  Defined in r2f_resample.hip, for its three LANCZOS4 entries.
     template <typename Coef>
     int tables(r2f_ctx* ctx, int H, int W, int out_h, int out_w, const int** xofs, const int** yofs, const Coef** xcoef, const Coef** ycoef);
+};
+
+// The auto-exposure record of the context (exposure_finish_kernel writes it, decode_u16_auto_kernel reads the factor): 16 bytes.
+struct ExposureRecord {
+    double stops;
+    float factor;
+    unsigned pad;
 };
 
 struct RenderGraphCache {

@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/r2f.h"
+
 // Wave-uniform read-only tables are addressed through the constant address space so that
 // hipcc emits scalar (s_load) instructions and the values sit in SGPRs.
 #define R2F_CONSTANT __attribute__((address_space(4)))
@@ -140,6 +142,108 @@ __device__ __forceinline__ int reflect101(int i, int n) {
 }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// ---------------------------------------------------------------------------- plane and input accesses
+// Four consecutive pixels of global row `gy` starting at column x, of three planes.
+// NT: non-temporal loads (ld4_stream) -- for planes that are read exactly once and written by another kernel (the tail's densities:
+// 0.95 against 0.99 ms at 100 MP, profiles/r04_tail_overlap_probe.txt; the pointwise kernels' own plane reads lose with them)
+template <bool NT = false>
+__device__ __forceinline__ void load_planes4(const DevPlanes& pl, int gy, int x, int W, int nv, bool vec, float (&r)[4],
+                                             float (&g)[4], float (&b)[4]) {
+    const float* p0 = pl.data + (long long)(gy - pl.gy0) * W + x;
+    const float* p1 = p0 + pl.plane_stride;
+    const float* p2 = p1 + pl.plane_stride;
+    if (vec && nv == 4) {
+        const float4 a = NT ? ld4_stream(p0) : *reinterpret_cast<const float4*>(p0);
+        const float4 c = NT ? ld4_stream(p1) : *reinterpret_cast<const float4*>(p1);
+        const float4 d = NT ? ld4_stream(p2) : *reinterpret_cast<const float4*>(p2);
+        r[0] = a.x; r[1] = a.y; r[2] = a.z; r[3] = a.w;
+        g[0] = c.x; g[1] = c.y; g[2] = c.z; g[3] = c.w;
+        b[0] = d.x; b[1] = d.y; b[2] = d.z; b[3] = d.w;
+    } else {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const bool ok = p < nv;
+            r[p] = ok ? p0[p] : 0.f;
+            g[p] = ok ? p1[p] : 0.f;
+            b[p] = ok ? p2[p] : 0.f;
+        }
+    }
+}
+
+__device__ __forceinline__ void store_planes4(const DevPlanes& pl, int gy, int x, int W, int nv, bool vec,
+                                              const float (&r)[4], const float (&g)[4], const float (&b)[4]) {
+    float* p0 = pl.data + (long long)(gy - pl.gy0) * W + x;
+    float* p1 = p0 + pl.plane_stride;
+    float* p2 = p1 + pl.plane_stride;
+    if (vec && nv == 4) {
+        *reinterpret_cast<float4*>(p0) = make_float4(r[0], r[1], r[2], r[3]);
+        *reinterpret_cast<float4*>(p1) = make_float4(g[0], g[1], g[2], g[3]);
+        *reinterpret_cast<float4*>(p2) = make_float4(b[0], b[1], b[2], b[3]);
+    } else {
+        for (int p = 0; p < nv; ++p) {
+            p0[p] = r[p];
+            p1[p] = g[p];
+            p2[p] = b[p];
+        }
+    }
+}
+
+// One pixel (global row gy, column x) of a caller's float image in any R2F_LAYOUT_*; row in_gy0 is the buffer's first of in_rows.
+__device__ __forceinline__ void load_input1(const void* in_, int layout, int in_gy0, int in_rows, int W, int gy, int x,
+                                            float& X, float& Y, float& Z) {
+    const float* in = static_cast<const float*>(in_);
+    const long long row = gy - in_gy0;
+    if (layout == R2F_LAYOUT_CHW) {
+        const long long plane = (long long)in_rows * W, o = row * W + x;
+        X = in[o];
+        Y = in[plane + o];
+        Z = in[2 * plane + o];
+    } else {
+        const int nc = layout == R2F_LAYOUT_HWC4 ? 4 : 3;
+        const float* p = in + (row * W + x) * nc;
+        X = p[0];
+        Y = p[1];
+        Z = p[2];
+    }
+}
+
+// ---------------------------------------------------------------------------- INTER_AREA cells (S7 burn, float area resize)
+// cv.resize INTER_AREA weight of source sample s for destination sample d (computeResizeAreaTab).
+__device__ __forceinline__ void area_cell(int d, double scale, int ssize, int& s_first, int& s_last, int& s1, int& s2,
+                                          double& w_first, double& w_full, double& w_last) {
+    const double f1 = d * scale, f2 = f1 + scale;
+    const double cell = fmin(scale, (double)ssize - f1);
+    s1 = (int)ceil(f1);
+    s2 = min((int)floor(f2), ssize - 1);
+    s1 = min(s1, s2);
+    w_first = (s1 - f1 > 1e-3) ? (s1 - f1) / cell : 0.0;
+    w_full = 1.0 / cell;
+    w_last = (f2 - s2 > 1e-3) ? fmin(fmin(f2 - s2, 1.0), cell) / cell : 0.0;
+    s_first = max(s1 - 1, 0);
+    s_last = s2;
+}
+
+__device__ __forceinline__ float area_weight(int s, int s1, int s2, double w_first, double w_full, double w_last) {
+    if (s == s1 - 1) return (float)w_first;
+    if (s >= s1 && s < s2) return (float)w_full;
+    if (s == s2) return (float)w_last;
+    return 0.f;
+}
+
+// The sum of 256 lane accumulators in a fixed order (s = 128, 64, ... 1: red[i] += red[i + s]); every lane gets it.
+__device__ __forceinline__ double block_sum_256(double mine, double* red) {
+    const int i = threadIdx.x;
+    red[i] = mine;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (i < s) red[i] = red[i] + red[i + s];
+        __syncthreads();
+    }
+    const double total = red[0];
+    __syncthreads();
+    return total;
+}
 
 // np.interp semantics: linear, clamped to fp[0] / fp[m-1] outside [xp[0], xp[m-1]].  The cell index is
 // guessed from a uniform grid and then walked until the cell's own bounds contain x, so any

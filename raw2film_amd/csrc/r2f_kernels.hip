@@ -1,18 +1,18 @@
-// r2f_kernels.hip -- gfx950 kernels of the film-emulation render path and their launchers.
+// r2f_kernels.hip -- gfx950 kernels of the film-emulation render path and their launchers; nothing here runs off the path (the
+// resamplers are in r2f_resample.hip, the hand-off, chroma NR, blit and histograms in r2f_post.hip).
 //
 // Kernel inventory (pass graph mirrors gpu_processor.py:1763-1862, fused where it is free):
 //   front_kernel      S0 3x3 + S1 2-D LUT [+ S3 log + S4 curve [+ S8 3-D LUT + S9 u8]]        HBM-bound
 //   stencil_kernel    S2 halation (+S3+S4 epilogue) / S5 MTF: LDS-tiled direct stencil         fp32-VALU-bound
+//   single_tap_kernel a stencil channel of one tap (the halation's identity plane)             HBM-bound
 //   tail_kernel       S6 hash noise -> LDS, grain stencil, grain LUT, clip [, S8, S9]          VALU/LDS
 //   lut3d_kernel      [S7 burn subtract +] S8 + S9 from density planes                         HBM-bound
 //   burn_sums/_map    S7: INTER_AREA cell sums of the green density; clip + Gaussian on the map
-//   chroma_h/_v       pre-path chroma NR: xyY + separable Gaussian on the chromaticity planes  HBM-bound
-//   resize_area       pre-path INTER_AREA down-scale to the preview resolution
-//   warp_affine       pre-path free rotation (cv.warpAffine, INTER_LINEAR, zero border)
-//   lanczos4_u8       post-path up-scale of the uint8 result (cv.resize INTER_LANCZOS4): the way back from max_scale
 //   noise_kernel      S6a test entry (hash + Gaussian field)
-//   histogram_u8      caller-side RGB histogram counts of the uint8 output (utils.generate_histogram, histogram.wgsl pass 1)
+//   frame_params / exposure_range   the per-render frame block and the exposure-range record
 #include <algorithm>
+#include <array>
+#include <utility>
 
 #include "r2f_launch.h"
 
@@ -24,7 +24,7 @@
 
 namespace r2f {
 
-const StencilVariant kStencilVariants[kNumStencilVariants] = {
+constexpr StencilVariant kStencilVariants[kNumStencilVariants] = {  // (constexpr here: the generic stencil table below is built from it)
     {0, 32, 16, 4},  // 512 threads, tile 128 x 64, 4x4 outputs per lane
     {1, 16, 8, 4},   // 128 threads, tile 64 x 32: fallback for very wide stencils
     {2, 32, 8, 4},   // 256 threads, tile 128 x 32: never auto-selected first; occupancy experiments (2 waves per SIMD)
@@ -144,50 +144,6 @@ __device__ __forceinline__ void emit_hwc(const HwcOut& out, int gy, int x, int W
                 o[3 * p + 1] = (uint8_t)to_u8(g[p]);
                 o[3 * p + 2] = (uint8_t)to_u8(b[p]);
             }
-        }
-    }
-}
-
-// NT: non-temporal loads (ld4_stream) -- for planes that are read exactly once and written by another kernel (the tail's densities:
-// 0.95 against 0.99 ms at 100 MP, profiles/r04_tail_overlap_probe.txt; the pointwise kernels' own plane reads lose with them)
-template <bool NT = false>
-__device__ __forceinline__ void load_planes4(const DevPlanes& pl, int gy, int x, int W, int nv, bool vec, float (&r)[4],
-                                             float (&g)[4], float (&b)[4]) {
-    const float* p0 = pl.data + (long long)(gy - pl.gy0) * W + x;
-    const float* p1 = p0 + pl.plane_stride;
-    const float* p2 = p1 + pl.plane_stride;
-    if (vec && nv == 4) {
-        const float4 a = NT ? ld4_stream(p0) : *reinterpret_cast<const float4*>(p0);
-        const float4 c = NT ? ld4_stream(p1) : *reinterpret_cast<const float4*>(p1);
-        const float4 d = NT ? ld4_stream(p2) : *reinterpret_cast<const float4*>(p2);
-        r[0] = a.x; r[1] = a.y; r[2] = a.z; r[3] = a.w;
-        g[0] = c.x; g[1] = c.y; g[2] = c.z; g[3] = c.w;
-        b[0] = d.x; b[1] = d.y; b[2] = d.z; b[3] = d.w;
-    } else {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const bool ok = p < nv;
-            r[p] = ok ? p0[p] : 0.f;
-            g[p] = ok ? p1[p] : 0.f;
-            b[p] = ok ? p2[p] : 0.f;
-        }
-    }
-}
-
-__device__ __forceinline__ void store_planes4(const DevPlanes& pl, int gy, int x, int W, int nv, bool vec,
-                                              const float (&r)[4], const float (&g)[4], const float (&b)[4]) {
-    float* p0 = pl.data + (long long)(gy - pl.gy0) * W + x;
-    float* p1 = p0 + pl.plane_stride;
-    float* p2 = p1 + pl.plane_stride;
-    if (vec && nv == 4) {
-        *reinterpret_cast<float4*>(p0) = make_float4(r[0], r[1], r[2], r[3]);
-        *reinterpret_cast<float4*>(p1) = make_float4(g[0], g[1], g[2], g[3]);
-        *reinterpret_cast<float4*>(p2) = make_float4(b[0], b[1], b[2], b[3]);
-    } else {
-        for (int p = 0; p < nv; ++p) {
-            p0[p] = r[p];
-            p1[p] = g[p];
-            p2[p] = b[p];
         }
     }
 }
@@ -763,28 +719,6 @@ __global__ __launch_bounds__(kTailBX* kTailBY) void tail_kernel(const TailArgs a
 }
 
 // ------------------------------------------------------------------------------ S7 highlight burn
-// cv.resize INTER_AREA weight of source sample s for destination sample d (computeResizeAreaTab).
-__device__ __forceinline__ void area_cell(int d, double scale, int ssize, int& s_first, int& s_last, int& s1, int& s2,
-                                          double& w_first, double& w_full, double& w_last) {
-    const double f1 = d * scale, f2 = f1 + scale;
-    const double cell = fmin(scale, (double)ssize - f1);
-    s1 = (int)ceil(f1);
-    s2 = min((int)floor(f2), ssize - 1);
-    s1 = min(s1, s2);
-    w_first = (s1 - f1 > 1e-3) ? (s1 - f1) / cell : 0.0;
-    w_full = 1.0 / cell;
-    w_last = (f2 - s2 > 1e-3) ? fmin(fmin(f2 - s2, 1.0), cell) / cell : 0.0;
-    s_first = max(s1 - 1, 0);
-    s_last = s2;
-}
-
-__device__ __forceinline__ float area_weight(int s, int s1, int s2, double w_first, double w_full, double w_last) {
-    if (s == s1 - 1) return (float)w_first;
-    if (s >= s1 && s < s2) return (float)w_full;
-    if (s == s2) return (float)w_last;
-    return 0.f;
-}
-
 // One workgroup per low-res cell: area-weighted sum of the green density over the cell's source pixels that
 // lie in rows [y0, y1) (a row shard contributes its part; shards' arrays add up to the full-frame value).
 __global__ __launch_bounds__(256) void burn_sums_kernel(const BurnSumsArgs a) {
@@ -811,13 +745,8 @@ __global__ __launch_bounds__(256) void burn_sums_kernel(const BurnSumsArgs a) {
         }
     }
     __shared__ double red[256];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) a.cell_sums[i * a.w_lo + j] = (float)red[0];
+    const double total = block_sum_256(acc, red);
+    if (threadIdx.x == 0) a.cell_sums[i * a.w_lo + j] = (float)total;
 }
 
 // scipy.ndimage "reflect" boundary: d c b a | a b c d | d c b a
@@ -849,223 +778,6 @@ __global__ __launch_bounds__(256) void burn_map_kernel(const BurnMapArgs a) {
     }
 }
 
-// ------------------------------------------------------------------------------ chroma NR (pre-path)
-__device__ __forceinline__ void load_input1(const void* in_, int layout, int in_gy0, int in_rows, int W, int gy, int x,
-                                            float& X, float& Y, float& Z) {
-    const float* in = static_cast<const float*>(in_);
-    const long long row = gy - in_gy0;
-    if (layout == R2F_LAYOUT_CHW) {
-        const long long plane = (long long)in_rows * W, o = row * W + x;
-        X = in[o];
-        Y = in[plane + o];
-        Z = in[2 * plane + o];
-    } else {
-        const int nc = layout == R2F_LAYOUT_HWC4 ? 4 : 3;
-        const float* p = in + (row * W + x) * nc;
-        X = p[0];
-        Y = p[1];
-        Z = p[2];
-    }
-}
-
-// effects.XYZ_to_xyY, effects.py:496-518
-__device__ __forceinline__ void xyz_to_xy(float X, float Y, float Z, float& cx, float& cy) {
-    const float denom = (X + Y) + Z;
-    if (denom > 1e-8f) {
-        cx = X / denom;
-        cy = Y / denom;
-    } else {
-        cx = 0.f;
-        cy = 0.f;
-    }
-}
-
-// Pass 1: one workgroup = one row segment of 1024 pixels.  Chromaticities of the segment plus `radius` clamped
-// neighbours on each side are staged in LDS (the one truly separable blur near this path), then every lane blurs its
-// 4 pixels horizontally.  Output planes: x', y', Y.
-constexpr int kChromaSeg = 1024;
-__global__ __launch_bounds__(256) void chroma_h_kernel(const ChromaArgs a) {
-    __shared__ float sx[kChromaSeg + 2 * 31], sy[kChromaSeg + 2 * 31];
-    const int gy = a.y0 + blockIdx.y;
-    const int seg0 = blockIdx.x * kChromaSeg;
-    const int r = a.radius;
-    const int n = kChromaSeg + 2 * r;
-    float Yown[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int gx = clampi(seg0 - r + i, 0, a.W - 1);  // ix = min(max(x + i, 0), w - 1), effects.py:452
-        float X, Y, Z;
-        load_input1(a.in, a.in_layout, a.in_gy0, a.in_rows, a.W, gy, gx, X, Y, Z);
-        xyz_to_xy(X, Y, Z, sx[i], sy[i]);
-    }
-    __syncthreads();
-    const int x0 = seg0 + 4 * threadIdx.x;
-    if (x0 >= a.W) return;
-    const int nv = min(4, a.W - x0);
-    float bx[4], by[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        float accx = 0.f, accy = 0.f;
-        const int c = 4 * threadIdx.x + p;  // window [c, c + 2r] in LDS
-        for (int t = 0; t <= 2 * r; ++t) {
-            accx = fmaf(sx[c + t], a.w[t], accx);
-            accy = fmaf(sy[c + t], a.w[t], accy);
-        }
-        bx[p] = accx;
-        by[p] = accy;
-        if (p < nv) {
-            float X, Y, Z;
-            load_input1(a.in, a.in_layout, a.in_gy0, a.in_rows, a.W, gy, x0 + p, X, Y, Z);
-            Yown[p] = Y;
-        }
-    }
-    store_planes4(a.dst, gy, x0, a.W, nv, a.vec != 0, bx, by, Yown);
-}
-
-// Pass 2: vertical blur of x', y' (rows clamped to the frame) and effects.xyY_to_XYZ (effects.py:521-544).
-__global__ __launch_bounds__(256) void chroma_v_kernel(const ChromaArgs a) {
-    const int x = (blockIdx.x * 64 + threadIdx.x) * 4;
-    const int gy = a.y0 + blockIdx.y * 4 + threadIdx.y;
-    if (x >= a.W || gy >= a.y1) return;
-    const int nv = min(4, a.W - x);
-    const bool vec = a.vec != 0;
-    const int r = a.radius;
-    float ax[4] = {0.f, 0.f, 0.f, 0.f}, ay[4] = {0.f, 0.f, 0.f, 0.f};
-    float Yc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int t = 0; t <= 2 * r; ++t) {
-        const int sy = clampi(gy - r + t, 0, a.H_global - 1);  // iy = min(max(y + i, 0), h - 1), effects.py:476
-        float px[4], py[4], pY[4];
-        load_planes4(a.src, sy, x, a.W, nv, vec, px, py, pY);
-        const float w = a.w[t];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            ax[p] = fmaf(px[p], w, ax[p]);
-            ay[p] = fmaf(py[p], w, ay[p]);
-            if (t == r) Yc[p] = pY[p];
-        }
-    }
-    float X[4], Z[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        if (ay[p] > 1e-8f) {
-            const float inv = Yc[p] / ay[p];
-            X[p] = ax[p] * inv;
-            Z[p] = ((1.0f - ax[p]) - ay[p]) * inv;
-        } else {
-            X[p] = 0.f;
-            Yc[p] = 0.f;
-            Z[p] = 0.f;
-        }
-    }
-    store_planes4(a.dst, gy, x, a.W, nv, vec, X, Yc, Z);
-}
-
-// ------------------------------------------------------------------------------ area down-scale (pre-path)
-// One lane per destination pixel: weighted mean over its source footprint with the INTER_AREA weights of
-// area_cell() above, all three channels at once.  Pre-path and run once per preview; no tuning beyond coalesced x.
-__global__ __launch_bounds__(256) void resize_area_kernel(const ResizeArgs a) {
-    const int dx = blockIdx.x * 64 + threadIdx.x, dy = blockIdx.y * 4 + threadIdx.y;
-    if (dx >= a.out_w || dy >= a.out_h) return;
-    int ry0, ry1, rs1, rs2, cx0, cx1, cs1, cs2;
-    double wyf, wy, wyl, wxf, wx, wxl;
-    area_cell(dy, (double)a.H / a.out_h, a.H, ry0, ry1, rs1, rs2, wyf, wy, wyl);
-    area_cell(dx, (double)a.W / a.out_w, a.W, cx0, cx1, cs1, cs2, wxf, wx, wxl);
-    float accX = 0.f, accY = 0.f, accZ = 0.f;
-    for (int y = ry0; y <= ry1; ++y) {
-        const float wv = area_weight(y, rs1, rs2, wyf, wy, wyl);
-        if (wv == 0.f) continue;
-        float rX = 0.f, rY = 0.f, rZ = 0.f;
-        for (int x = cx0; x <= cx1; ++x) {
-            const float wh = area_weight(x, cs1, cs2, wxf, wx, wxl);
-            float X, Y, Z;
-            load_input1(a.in, a.in_layout, 0, a.H, a.W, y, x, X, Y, Z);
-            rX = fmaf(wh, X, rX);
-            rY = fmaf(wh, Y, rY);
-            rZ = fmaf(wh, Z, rZ);
-        }
-        accX = fmaf(wv, rX, accX);
-        accY = fmaf(wv, rY, accY);
-        accZ = fmaf(wv, rZ, accZ);
-    }
-    float* p0 = a.dst.data + (long long)(dy - a.dst.gy0) * a.out_w + dx;
-    p0[0] = accX;
-    p0[a.dst.plane_stride] = accY;
-    p0[2 * a.dst.plane_stride] = accZ;
-}
-
-// ------------------------------------------------------------------------------ free rotation (pre-path)
-// effects.rotate (effects.py:46-75): cv.warpAffine(rgb, getRotationMatrix2D(centre, -degrees, 1), same size, INTER_LINEAR)
-// followed by a centred crop; the kernel produces the cropped window only.  One lane per destination pixel, lanes along x.
-// Source coordinates and the two-step lerp are float32, like OpenCV's linear warp kernels (>= 4.11); taps that fall
-// outside the frame read the constant border 0.  HBM/L2-bound gather: neighbouring lanes read neighbouring texels for
-// the small angles a horizon correction uses.
-__global__ __launch_bounds__(256) void warp_affine_kernel(const WarpArgs a) {
-    const int dx = blockIdx.x * 64 + threadIdx.x, dy = blockIdx.y * 4 + threadIdx.y;
-    if (dx >= a.out_w || dy >= a.out_h) return;
-    const float xf = (float)(dx + a.ox), yf = (float)(dy + a.oy);
-    const float sx = __fadd_rn(__fadd_rn(__fmul_rn(xf, a.m[0]), __fmul_rn(yf, a.m[1])), a.m[2]);
-    const float sy = __fadd_rn(__fadd_rn(__fmul_rn(xf, a.m[3]), __fmul_rn(yf, a.m[4])), a.m[5]);
-    const float fx0 = floorf(sx), fy0 = floorf(sy);
-    const float ax = sx - fx0, ay = sy - fy0;
-    float v[3] = {0.f, 0.f, 0.f};
-    // int conversion only for coordinates that can touch the frame (also keeps huge values out of the cast)
-    if (fx0 >= -1.f && fy0 >= -1.f && fx0 < (float)a.W && fy0 < (float)a.H) {
-        const int x0 = (int)fx0, y0 = (int)fy0;
-        float t[2][2][3];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int xx = x0 + i, yy = y0 + j;
-                if (xx >= 0 && xx < a.W && yy >= 0 && yy < a.H)
-                    load_input1(a.in, a.in_layout, 0, a.H, a.W, yy, xx, t[j][i][0], t[j][i][1], t[j][i][2]);
-                else
-                    t[j][i][0] = t[j][i][1] = t[j][i][2] = 0.f;
-            }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float top = __fadd_rn(t[0][0][c], __fmul_rn(ax, __fsub_rn(t[0][1][c], t[0][0][c])));
-            const float bot = __fadd_rn(t[1][0][c], __fmul_rn(ax, __fsub_rn(t[1][1][c], t[1][0][c])));
-            v[c] = __fadd_rn(top, __fmul_rn(ay, __fsub_rn(bot, top)));
-        }
-    }
-    float* p0 = a.dst.data + (long long)(dy - a.dst.gy0) * a.out_w + dx;
-    p0[0] = v[0];
-    p0[a.dst.plane_stride] = v[1];
-    p0[2 * a.dst.plane_stride] = v[2];
-}
-
-// ------------------------------------------------------------------------------ LANCZOS4 up-scale (post-path)
-// utils.resolution_scaling -> cv.resize(uint8, INTER_LANCZOS4) (utils.py:237-242): 8 x 8 taps per output pixel with the
-// 11-bit fixed-point weights OpenCV derives per destination column / row (built on the host, r2f_api.hip), exact int32
-// accumulation, one rounding (+2^21 >> 22), replicated border.  One lane per output pixel, all three channels.
-__global__ __launch_bounds__(256) void lanczos4_u8_kernel(const LanczosArgs a) {
-    const int dx = blockIdx.x * 64 + threadIdx.x, dy = blockIdx.y * 4 + threadIdx.y;
-    if (dx >= a.out_w || dy >= a.out_h) return;
-    const int sx = a.xofs[dx] - 3, sy = a.yofs[dy] - 3;
-    int wx[8], wy[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) wx[k] = a.xcoef[dx * 8 + k], wy[k] = a.ycoef[dy * 8 + k];
-    int acc[3] = {0, 0, 0};
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const uint8_t* row = a.src + (long long)clampi(sy + k, 0, a.H - 1) * a.W * 3;
-        int h[3] = {0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint8_t* p = row + clampi(sx + j, 0, a.W - 1) * 3;
-            h[0] += (int)p[0] * wx[j];
-            h[1] += (int)p[1] * wx[j];
-            h[2] += (int)p[2] * wx[j];
-        }
-        acc[0] += h[0] * wy[k];
-        acc[1] += h[1] * wy[k];
-        acc[2] += h[2] * wy[k];
-    }
-    uint8_t* o = a.dst + ((long long)dy * a.out_w + dx) * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) o[c] = (uint8_t)clampi((acc[c] + (1 << 21)) >> 22, 0, 255);
-}
-
 // ------------------------------------------------------------------------------ noise (test)
 __global__ __launch_bounds__(256) void noise_kernel(const NoiseArgs a) {
     const int x = blockIdx.x * 256 + threadIdx.x;
@@ -1091,51 +803,6 @@ __global__ __launch_bounds__(256) void noise_kernel(const NoiseArgs a) {
     }
 }
 
-// ------------------------------------------------------------------------------ histogram
-// utils.generate_histogram's counting loop (utils.py:160-165) / histogram.wgsl pass1_accumulate on the uint8 (H, W, 3)
-// output: 3 x 256 counts.  HBM-bound (3 B/px); the byte stream is read 16 B per lane, channel = byte index mod 3.  Flat
-// images put most pixels into a few bins, so every group of 8 lanes owns a private copy of the table in LDS (same-address
-// LDS atomics serialise) and the copies are folded into global memory once per workgroup.
-constexpr int kHistCopies = 8, kHistThreads = 256, kHistBytesPerLane = 16, kHistIters = 16;
-
-__global__ __launch_bounds__(kHistThreads) void histogram_u8_kernel(const uint8_t* __restrict__ image, long long n_bytes,
-                                                                    uint32_t* __restrict__ counts) {
-    __shared__ uint32_t h[kHistCopies][768];
-    for (int i = threadIdx.x; i < kHistCopies * 768; i += kHistThreads) (&h[0][0])[i] = 0;
-    __syncthreads();
-    uint32_t* mine = h[threadIdx.x & (kHistCopies - 1)];
-    const long long chunk = (long long)kHistThreads * kHistBytesPerLane;
-    long long base = (long long)blockIdx.x * chunk * kHistIters;
-    for (int it = 0; it < kHistIters; ++it, base += chunk) {
-        const long long o = base + (long long)threadIdx.x * kHistBytesPerLane;
-        if (o >= n_bytes) break;
-        int ch = (int)(o % 3);
-        if (o + kHistBytesPerLane <= n_bytes) {
-            const uint4 v = *reinterpret_cast<const uint4*>(image + o);  // hipMalloc'ed images are 16-byte aligned
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    atomicAdd(&mine[ch * 256 + ((w[k] >> (8 * b)) & 255u)], 1u);
-                    ch = ch == 2 ? 0 : ch + 1;
-                }
-        } else {
-            for (long long i = o; i < n_bytes; ++i) {
-                atomicAdd(&mine[ch * 256 + image[i]], 1u);
-                ch = ch == 2 ? 0 : ch + 1;
-            }
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 768; i += kHistThreads) {
-        uint32_t s = 0;
-#pragma unroll
-        for (int c = 0; c < kHistCopies; ++c) s += h[c][i];
-        if (s) atomicAdd(&counts[i], s);
-    }
-}
-
 // ------------------------------------------------------------------------------ launchers
 size_t stencil_lds_bytes(const StencilVariant& v, const DevStencil* st, int nchan) {
     size_t best = 0;
@@ -1155,62 +822,50 @@ size_t tail_lds_bytes(const DevStencil* gk, int mono, int cells_in_lds, int grai
     return tail_plane_floats(gk, mono) * sizeof(float) + (cells_in_lds ? (size_t)3 * (grain_m - 1) * sizeof(float4) : 0);
 }
 
+// Every instantiation of the two templated kernel families, listed ONCE: init_kernel_attributes raises the dynamic-LDS limit of every
+// entry and the launchers index the same tables, so what can be launched is what had its attribute set.
+using StencilFn = void (*)(StencilArgs);
+using TailFn = void (*)(TailArgs);
+constexpr int kStencilFixedN = 12, kTailFixedN = 10;  // R = 0 (the entry list) and the unrolled forms R = 1 .. 11 / 1 .. 9
+
+template <int EPI, int... R>
+constexpr std::array<StencilFn, sizeof...(R)> stencil_fixed_row(std::integer_sequence<int, R...>) {
+    return {{stencil_kernel<32, 16, 4, EPI, R>...}};
+}
+template <int EPI, int... V>
+constexpr std::array<StencilFn, sizeof...(V)> stencil_generic_row(std::integer_sequence<int, V...>) {
+    return {{stencil_kernel<kStencilVariants[V].BX, kStencilVariants[V].BY, kStencilVariants[V].Q, EPI>...}};
+}
+template <bool SEP, int... R>
+constexpr std::array<TailFn, sizeof...(R)> tail_row(std::integer_sequence<int, R...>) {
+    return {{tail_kernel<R, SEP && (R > 0)>...}};  // (R = 0 has no separable form: the entry list either way)
+}
+template <int N>
+using UpTo = std::make_integer_sequence<int, N>;
+// [EPI][R]: variant 0's tile; R = 0 is its entry-list form
+constexpr std::array<std::array<StencilFn, kStencilFixedN>, 2> kStencilFixed = {
+    {stencil_fixed_row<0>(UpTo<kStencilFixedN>{}), stencil_fixed_row<1>(UpTo<kStencilFixedN>{})}};
+// [EPI][variant]: the entry-list form on every tile of kStencilVariants
+constexpr std::array<std::array<StencilFn, kNumStencilVariants>, 2> kStencilGeneric = {
+    {stencil_generic_row<0>(UpTo<kNumStencilVariants>{}), stencil_generic_row<1>(UpTo<kNumStencilVariants>{})}};
+// [SEP][R]
+constexpr std::array<std::array<TailFn, kTailFixedN>, 2> kTail = {{tail_row<false>(UpTo<kTailFixedN>{}), tail_row<true>(UpTo<kTailFixedN>{})}};
+
 hipError_t init_kernel_attributes() {
-    hipError_t e;
-#define R2F_SET_LDS(k)                                                                                \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            (int)kMaxLds);                                                            \
-    if (e != hipSuccess) return e;
-    R2F_SET_LDS((stencil_kernel<32, 8, 4, 0>))
-    R2F_SET_LDS((stencil_kernel<32, 8, 4, 1>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 0>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 1>))
-    R2F_SET_LDS((stencil_kernel<16, 8, 4, 0>))
-    R2F_SET_LDS((stencil_kernel<16, 8, 4, 1>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 0, 1>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 1, 1>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 0, 2>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 1, 2>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 0, 3>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 1, 3>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 0, 4>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 1, 4>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 0, 5>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 1, 5>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 0, 6>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 1, 6>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 0, 7>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 1, 7>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 0, 8>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 1, 8>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 0, 9>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 1, 9>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 0, 10>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 1, 10>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 0, 11>))
-    R2F_SET_LDS((stencil_kernel<32, 16, 4, 1, 11>))
-    R2F_SET_LDS((tail_kernel<0>))
-    R2F_SET_LDS((tail_kernel<1>))
-    R2F_SET_LDS((tail_kernel<2>))
-    R2F_SET_LDS((tail_kernel<3>))
-    R2F_SET_LDS((tail_kernel<4>))
-    R2F_SET_LDS((tail_kernel<5>))
-    R2F_SET_LDS((tail_kernel<6>))
-    R2F_SET_LDS((tail_kernel<7>))
-    R2F_SET_LDS((tail_kernel<8>))
-    R2F_SET_LDS((tail_kernel<9>))
-    R2F_SET_LDS((tail_kernel<1, true>))
-    R2F_SET_LDS((tail_kernel<2, true>))
-    R2F_SET_LDS((tail_kernel<3, true>))
-    R2F_SET_LDS((tail_kernel<4, true>))
-    R2F_SET_LDS((tail_kernel<5, true>))
-    R2F_SET_LDS((tail_kernel<6, true>))
-    R2F_SET_LDS((tail_kernel<7, true>))
-    R2F_SET_LDS((tail_kernel<8, true>))
-    R2F_SET_LDS((tail_kernel<9, true>))
-    R2F_SET_LDS(front_kernel<true>)
-#undef R2F_SET_LDS
-    return hipSuccess;
+    auto raise = [](const void* k) { return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds); };
+    auto raise_all = [&](const auto& table) {
+        for (const auto& row : table)
+            for (auto k : row) {
+                const hipError_t e = raise(reinterpret_cast<const void*>(k));
+                if (e != hipSuccess) return e;
+            }
+        return hipSuccess;
+    };
+    hipError_t e = raise_all(kStencilFixed);
+    if (e == hipSuccess) e = raise_all(kStencilGeneric);
+    if (e == hipSuccess) e = raise_all(kTail);
+    if (e == hipSuccess) e = raise(reinterpret_cast<const void*>(front_kernel<true>));
+    return e;
 }
 
 hipError_t launch_front(const FrontArgs& a, hipStream_t s) {
@@ -1240,40 +895,10 @@ hipError_t launch_stencil(const StencilArgs& a, int variant, hipStream_t s) {
     const StencilVariant& v = kStencilVariants[variant];
     const size_t lds = stencil_lds_bytes(v, a.st, 3);  // any subset of the channels may be in a.chan
     dim3 block(v.BX * v.BY), grid((a.W + v.TW() - 1) / v.TW(), (a.y1 - a.y0 + v.TH() - 1) / v.TH(), a.nchan);
-    if (variant == 0 && a.fixed_r > 0) {  // small square mirror-symmetric stencils: the unrolled form
-#define R2F_STENCIL_FIXED(R)                                                                        \
-    case R:                                                                                        \
-        if (a.epilogue == 1)                                                                       \
-            launch_k((stencil_kernel<32, 16, 4, 1, R>), grid, block, lds, s, a);         \
-        else                                                                                       \
-            launch_k((stencil_kernel<32, 16, 4, 0, R>), grid, block, lds, s, a);         \
-        return take_launch_status();
-        switch (a.fixed_r) {
-            R2F_STENCIL_FIXED(1)
-            R2F_STENCIL_FIXED(2)
-            R2F_STENCIL_FIXED(3)
-            R2F_STENCIL_FIXED(4)
-            R2F_STENCIL_FIXED(5)
-            R2F_STENCIL_FIXED(6)
-            R2F_STENCIL_FIXED(7)
-            R2F_STENCIL_FIXED(8)
-            R2F_STENCIL_FIXED(9)
-            R2F_STENCIL_FIXED(10)
-            R2F_STENCIL_FIXED(11)
-            default:
-                break;
-        }
-#undef R2F_STENCIL_FIXED
-    }
-    const int key = variant * 2 + (a.epilogue == 1 ? 1 : 0);
-    switch (key) {
-        case 0: launch_k((stencil_kernel<32, 16, 4, 0>), grid, block, lds, s, a); break;
-        case 1: launch_k((stencil_kernel<32, 16, 4, 1>), grid, block, lds, s, a); break;
-        case 2: launch_k((stencil_kernel<16, 8, 4, 0>), grid, block, lds, s, a); break;
-        case 3: launch_k((stencil_kernel<16, 8, 4, 1>), grid, block, lds, s, a); break;
-        case 4: launch_k((stencil_kernel<32, 8, 4, 0>), grid, block, lds, s, a); break;
-        default: launch_k((stencil_kernel<32, 8, 4, 1>), grid, block, lds, s, a); break;
-    }
+    const int epi = a.epilogue == 1 ? 1 : 0;
+    // small square mirror-symmetric stencils: the unrolled form (variant 0's tile only)
+    const bool fixed = variant == 0 && a.fixed_r > 0 && a.fixed_r < kStencilFixedN;
+    launch_k(fixed ? kStencilFixed[epi][a.fixed_r] : kStencilGeneric[epi][variant], grid, block, lds, s, a);
     return take_launch_status();
 }
 
@@ -1294,10 +919,7 @@ hipError_t launch_tail(const TailArgs& a, hipStream_t s) {
         l.gfield = a.gfield;
         l.has_gfield = a.has_gfield;
         l.grain_lut = a.grain_lut;
-        const int quads = (a.W + 3) / 4;
-        dim3 block(64, 4), grid((quads + 63) / 64, (a.y1 - a.y0 + 3) / 4);
-        launch_k(lut3d_kernel, grid, block, 0, s, l);
-        return take_launch_status();
+        return launch_64x4(lut3d_kernel, (a.W + 3) / 4, a.y1 - a.y0, s, l);
     }
     const int TW = 4 * kTailBX, TH = kTailQ * kTailBY;
     dim3 block(kTailBX * kTailBY), grid((a.W + TW - 1) / TW, (a.y1 - a.y0 + TH - 1) / TH);
@@ -1305,28 +927,9 @@ hipError_t launch_tail(const TailArgs& a, hipStream_t s) {
     b.cells_off = (int)tail_plane_floats(a.gk, a.mono);
     b.cells_in_lds = tail_lds_bytes(a.gk, a.mono, 1, a.grain_lut.m) <= 80 * 1024 ? 1 : 0;  // keep two workgroups per CU
     const size_t lds = tail_lds_bytes(a.gk, a.mono, b.cells_in_lds, a.grain_lut.m);
-    switch (a.fixed_r) {  // small square mirror-symmetric stencils take the unrolled form, separable ones two 1-D passes
-#define R2F_TAIL_FIXED(R)                                                        \
-    case R:                                                                     \
-        if (a.sep)                                                              \
-            launch_k((tail_kernel<R, true>), grid, block, lds, s, b); \
-        else                                                                    \
-            launch_k((tail_kernel<R>), grid, block, lds, s, b);       \
-        break;
-        R2F_TAIL_FIXED(1)
-        R2F_TAIL_FIXED(2)
-        R2F_TAIL_FIXED(3)
-        R2F_TAIL_FIXED(4)
-        R2F_TAIL_FIXED(5)
-        R2F_TAIL_FIXED(6)
-        R2F_TAIL_FIXED(7)
-        R2F_TAIL_FIXED(8)
-        R2F_TAIL_FIXED(9)
-#undef R2F_TAIL_FIXED
-        default:
-            launch_k((tail_kernel<0>), grid, block, lds, s, b);
-            break;
-    }
+    // small square mirror-symmetric stencils take the unrolled form, separable ones two 1-D passes
+    const int r = a.fixed_r > 0 && a.fixed_r < kTailFixedN ? a.fixed_r : 0;
+    launch_k(kTail[a.sep ? 1 : 0][r], grid, block, lds, s, b);
     return take_launch_status();
 }
 
@@ -1341,40 +944,9 @@ hipError_t launch_burn_map(const BurnMapArgs& a, hipStream_t s) {
     return take_launch_status();
 }
 
-hipError_t launch_chroma_h(const ChromaArgs& a, hipStream_t s) {
-    if (a.y1 <= a.y0 || a.W <= 0) return hipSuccess;
-    launch_k(chroma_h_kernel, dim3((a.W + kChromaSeg - 1) / kChromaSeg, a.y1 - a.y0), dim3(256), 0, s, a);
-    return take_launch_status();
-}
-
-hipError_t launch_chroma_v(const ChromaArgs& a, hipStream_t s) {
-    if (a.y1 <= a.y0 || a.W <= 0) return hipSuccess;
-    const int quads = (a.W + 3) / 4;
-    launch_k(chroma_v_kernel, dim3((quads + 63) / 64, (a.y1 - a.y0 + 3) / 4), dim3(64, 4), 0, s, a);
-    return take_launch_status();
-}
-
-hipError_t launch_resize_area(const ResizeArgs& a, hipStream_t s) {
-    if (a.out_h <= 0 || a.out_w <= 0) return hipSuccess;
-    launch_k(resize_area_kernel, dim3((a.out_w + 63) / 64, (a.out_h + 3) / 4), dim3(64, 4), 0, s, a);
-    return take_launch_status();
-}
-
-hipError_t launch_warp_affine(const WarpArgs& a, hipStream_t s) {
-    if (a.out_h <= 0 || a.out_w <= 0) return hipSuccess;
-    launch_k(warp_affine_kernel, dim3((a.out_w + 63) / 64, (a.out_h + 3) / 4), dim3(64, 4), 0, s, a);
-    return take_launch_status();
-}
-
 hipError_t launch_single_tap(const TapArgs& a, hipStream_t s) {
     if (a.y1 <= a.y0 || a.W <= 0) return hipSuccess;
     launch_k(single_tap_kernel, dim3((a.W + 1023) / 1024, a.y1 - a.y0), dim3(256), 0, s, a);
-    return take_launch_status();
-}
-
-hipError_t launch_lanczos4_u8(const LanczosArgs& a, hipStream_t s) {
-    if (a.out_h <= 0 || a.out_w <= 0) return hipSuccess;
-    launch_k(lanczos4_u8_kernel, dim3((a.out_w + 63) / 64, (a.out_h + 3) / 4), dim3(64, 4), 0, s, a);
     return take_launch_status();
 }
 
@@ -1463,15 +1035,6 @@ hipError_t launch_exposure_range(const DevPlanes& src, int y0, int y1, int y2, i
     if (rows <= 0 || W <= 0 || !(mask & 7)) return hipSuccess;
     launch_k(exposure_range_kernel, dim3((W + kRangeTileCols - 1) / kRangeTileCols, (rows + kRangeRowsPerBlock - 1) / kRangeRowsPerBlock),
              dim3(64, kRangeRowsPerBlock), 0, s, src, y0, y1, y2, y3, W, mask, rec);
-    return take_launch_status();
-}
-
-hipError_t launch_histogram_u8(const uint8_t* image, long long n_bytes, uint32_t* counts, hipStream_t s) {
-    hipError_t e = hipMemsetAsync(counts, 0, 768 * sizeof(uint32_t), s);
-    if (e != hipSuccess || n_bytes <= 0) return e;
-    const long long per_block = (long long)kHistThreads * kHistBytesPerLane * kHistIters;
-    launch_k(histogram_u8_kernel, dim3((unsigned)((n_bytes + per_block - 1) / per_block)), dim3(kHistThreads), 0, s,
-                       image, n_bytes, counts);
     return take_launch_status();
 }
 

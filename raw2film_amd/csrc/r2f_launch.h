@@ -1,12 +1,11 @@
-// r2f_launch.h -- host-callable launchers implemented in r2f_kernels.hip.
+// r2f_launch.h -- the launch helpers, and the argument structs and host-callable launchers of the render path (r2f_kernels.hip,
+// r2f_front.hip, r2f_fft.hip).  A stage off the path keeps its arguments and its launch next to its kernel.
 #pragma once
 
 #include <cstdint>
 #include <tuple>
 #include <type_traits>
 #include "r2f_device.h"
-
-struct r2f_blit;
 
 namespace r2f {
 
@@ -32,6 +31,12 @@ inline hipError_t take_launch_status() {
     const hipError_t e = tl_launch_error;
     tl_launch_error = hipSuccess;
     return e;
+}
+// One kernel with one lane per item of a w x h grid, lanes along x: workgroups of (64, 4).
+template <typename Args>
+inline hipError_t launch_64x4(void (*kernel)(Args), int w, int h, hipStream_t s, const Args& a) {
+    launch_k(kernel, dim3((w + 63) / 64, (h + 3) / 4), dim3(64, 4), 0, s, a);
+    return take_launch_status();
 }
 
 // One interleaved (H, W, 3) output: any of the three element types (the uint16 form is clip(x * 65535, 0, 65535) truncated, from the
@@ -155,46 +160,6 @@ struct TailArgs {
     float sep_u[3][19], sep_v[3][10];
 };
 
-constexpr int kChromaMaxTaps = 63;
-struct ChromaArgs {
-    const void* in;  // pass 1 input image
-    int in_layout, in_gy0, in_rows;
-    DevPlanes src;  // pass 2 input planes
-    DevPlanes dst;
-    int y0, y1, W, H_global;
-    int radius;  // taps = 2*radius + 1
-    int vec;
-    float w[kChromaMaxTaps];
-};
-
-struct ResizeArgs {
-    const void* in;
-    int in_layout, H, W;
-    DevPlanes dst;
-    int out_h, out_w;
-};
-
-// Pre-path free rotation: dst(y, x) = bilinear sample of `in` at M * (x + ox, y + oy, 1), zero outside (cv.warpAffine,
-// INTER_LINEAR, BORDER_CONSTANT); only the window the rotate() crop keeps is produced.
-struct WarpArgs {
-    const void* in;
-    int in_layout, H, W;
-    DevPlanes dst;
-    int out_h, out_w, oy, ox;
-    float m[6];  // dst -> src, row-major 2 x 3, rounded from double like OpenCV's float kernels
-};
-
-// Post-path up-scale of the uint8 result: cv.resize(..., INTER_LANCZOS4) with host-built fixed-point tables.
-struct LanczosArgs {
-    const uint8_t* src;  // (H, W, 3)
-    uint8_t* dst;        // (out_h, out_w, 3)
-    int H, W, out_h, out_w;
-    const int* xofs;     // out_w: source column of tap 3
-    const short* xcoef;  // out_w x 8
-    const int* yofs;     // out_h
-    const short* ycoef;  // out_h x 8
-};
-
 // A channel whose stencil has a single tap (the halation's identity plane): dst = epilogue(w * src) over rows [y0, y1).
 struct TapArgs {
     DevPlanes src, dst;
@@ -288,8 +253,6 @@ hipError_t init_kernel_attributes();
 hipError_t launch_front(const FrontArgs& a, hipStream_t s);
 hipError_t launch_stencil(const StencilArgs& a, int variant, hipStream_t s);
 hipError_t launch_tail(const TailArgs& a, hipStream_t s);
-hipError_t launch_warp_affine(const WarpArgs& a, hipStream_t s);
-hipError_t launch_lanczos4_u8(const LanczosArgs& a, hipStream_t s);
 hipError_t launch_noise(const NoiseArgs& a, hipStream_t s);
 // the per-render write of the context's FrameParams block (and the reset of the record's tiles) ahead of a frame's launches
 // mode: 0 seed only, 1 seed + range reset, 2 range reset only, 3 range made unusable (frame_params_kernel)
@@ -297,35 +260,7 @@ hipError_t launch_frame_params(const RangeRecord& rec, const FrameParams& v, int
 // the range of rows [y0, y1) and [y2, y3) of the planes in `mask` merged into the record's tiles (r2f_stage_exposure_range)
 hipError_t launch_exposure_range(const DevPlanes& src, int y0, int y1, int y2, int y3, int W, int mask, const RangeRecord& rec, hipStream_t s);
 
-// Caller-side histogram (utils.py:145-165): per-channel counts of an interleaved uint8 image; counts[3][256] is zeroed first.
-hipError_t launch_histogram_u8(const uint8_t* image, long long n_bytes, uint32_t* counts, hipStream_t s);
 hipError_t launch_burn_sums(const BurnSumsArgs& a, hipStream_t s);
-// r2f_post.hip
-hipError_t launch_resize_area_u8(const uint8_t* src, int H, int W, uint8_t* dst, int out_h, int out_w, hipStream_t s);
-hipError_t launch_resize_area_u16(const uint16_t* src, int H, int W, uint16_t* dst, int out_h, int out_w, hipStream_t s);
-hipError_t launch_lanczos4_u16(const uint16_t* src, int H, int W, uint16_t* dst, int out_h, int out_w, const int* xofs, const float* xcoef,
-                               const int* yofs, const float* ycoef, hipStream_t s);
-hipError_t launch_stream_copy(const void* src, void* dst, long long bytes, hipStream_t s);
-hipError_t launch_decode_u16(const uint16_t* src, long long n, int ch, float divisor, float factor, float* dst, hipStream_t s);
-// The auto-exposure record of the context (exposure_finish_kernel writes it, decode_u16_auto_kernel reads the factor): 16 bytes.
-struct ExposureRecord {
-    double stops;
-    float factor;
-    unsigned pad;
-};
-// the fp64 sums of the sampled (even) rows of [y0, y1) -> sums[y / 2]; src: row src_gy0 of the (H, W, ch) uint16 frame
-hipError_t launch_exposure_rows(const uint16_t* src, int src_gy0, int W, int ch, int y0, int y1, double root, double* sums, hipStream_t s);
-hipError_t launch_exposure_finish(const double* sums, int H, int W, double root, double ref, ExposureRecord* rec, hipStream_t s);
-hipError_t launch_decode_u16_auto(const uint16_t* src, int H, int W, int ch, long long src_pitch, float divisor, const ExposureRecord* rec,
-                                  float* dst, hipStream_t s);
-hipError_t launch_lanczos4_f32(const void* in, int in_layout, int H, int W, const DevPlanes& dst, int out_h, int out_w, const int* xofs,
-                               const float* xcoef, const int* yofs, const float* ycoef, hipStream_t s);
-hipError_t launch_blit_rgba8(const float* src, int H, int W, uint8_t* dst, int dst_h, int dst_w, const ::r2f_blit& t, hipStream_t s);
-hipError_t launch_histogram_render(const uint32_t* counts, const uint8_t* mix_rgba, int height, uint8_t* image, uint8_t* target, int th,
-                                   int tw, hipStream_t s);
 hipError_t launch_burn_map(const BurnMapArgs& a, hipStream_t s);
-hipError_t launch_chroma_h(const ChromaArgs& a, hipStream_t s);
-hipError_t launch_chroma_v(const ChromaArgs& a, hipStream_t s);
-hipError_t launch_resize_area(const ResizeArgs& a, hipStream_t s);
 
 }  // namespace r2f

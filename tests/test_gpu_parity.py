@@ -247,13 +247,14 @@ def test_mirror_symmetric_fast_path(ctx):
         ctx.set_option("stencil_fixed", 1)
 
 
-@pytest.mark.parametrize("n", [3, 5, 9, 13, 15, 17, 21, 23, 25])
+@pytest.mark.parametrize("n", [3, 5, 7, 9, 11, 13, 15, 17, 19, 21, 23, 25])
 @pytest.mark.parametrize("epilogue", [0, 1])
 def test_small_square_stencils_unrolled_direct_form(ctx, n, epilogue):
     """Square mirror-symmetric stencils run the direct kernel's fully unrolled form (stencil_fixed) up to the size where the FFT
     form overtakes it: 23 x 23 against complex128 scratch (the halation, epilogue = 1), 19 x 19 against the cheaper complex64
     scratch of the MTF passes (epilogue = 0); beyond that the FFT form.  Against the oracle, against the entry list,
-    per-channel taps, with and without the halation epilogue, on row ranges with halo rows of any origin."""
+    per-channel taps, with and without the halation epilogue, on row ranges with halo rows of any origin.  Every radius 1 .. 11 of
+    both epilogues is launched: 21 x 21 and 23 x 23 without the epilogue only run unrolled with the FFT form off (the last leg)."""
     rng = np.random.default_rng(100 + n)
     H, W = 150, 203
     k = rng.uniform(0.0, 1.0, (n, n, 3)).astype(np.float32)  # (one sign: taps of both signs take the float64 FFT form whatever their size)
@@ -300,6 +301,18 @@ def test_small_square_stencils_unrolled_direct_form(ctx, n, epilogue):
     assert fft_b == ([1, 1, 1] if n >= 21 else [0, 0, 0])  # without the unrolled form the FFT threshold is 400 taps
     assert_close(b, ref, 1e-5, 1e-3, f"{n} x {n} entry list / FFT")
     ctx.set_option("stencil_fixed", 1)
+    if not epilogue and n in (21, 23):
+        # 21 x 21 and 23 x 23 without the epilogue: the unrolled form runs only when the FFT form is off (every instantiation
+        # of the direct kernel is launched by this test)
+        ctx.set_option("stencil_fft", 0)
+        try:
+            last_unrolled = 23
+            c, c_whole, fft_c = run(1)
+        finally:
+            ctx.set_option("stencil_fft", 1)
+        assert fft_c == [0, 0, 0]
+        assert_close(c, ref, 1e-5, 1e-3, f"{n} x {n} unrolled, FFT form off")
+        np.testing.assert_array_equal(c, c_whole)
 
 
 @pytest.mark.parametrize("scale", [14.22, 166.67, 341.33])
@@ -689,7 +702,7 @@ def test_grain_field_split_equals_the_fused_tail_bit_for_bit(ctx):
         assert_close(split.cpu().numpy(), ref, 1e-5, 1e-3, "split tail vs oracle")
 
 
-@pytest.mark.parametrize("n", [3, 5, 7, 9, 11, 13, 15, 19, 21])
+@pytest.mark.parametrize("n", [3, 5, 7, 9, 11, 13, 15, 17, 19, 21])
 @pytest.mark.parametrize("mono, per_channel", [(False, False), (True, False), (False, True)])
 def test_small_square_grain_stencils_unrolled_form_against_the_oracle_and_the_entry_list(ctx, n, mono, per_channel):
     """Square mirror-symmetric grain stencils up to 19 x 19 take the fully unrolled form (stencil_fixed<R, 2>), 21 x 21 and
@@ -729,7 +742,7 @@ def test_small_square_grain_stencils_unrolled_form_against_the_oracle_and_the_en
     assert np.abs(fields[1] - fields[0]).max() <= 1e-6 * np.abs(ref).max()  # two summation orders of the same 2-D sum
 
 
-@pytest.mark.parametrize("n", [3, 5, 9, 13, 19])
+@pytest.mark.parametrize("n", [3, 5, 7, 9, 11, 13, 15, 17, 19])
 @pytest.mark.parametrize("mono, per_channel", [(False, True), (False, False), (True, False), (True, True)])
 def test_separable_grain_stencils_run_as_two_1d_passes(ctx, n, mono, per_channel):
     """A grain stencil that is u v^T to fp32 rounding (any Gaussian-like kernel: the stand-in of filmstock.grain_kernel, per

@@ -10,17 +10,14 @@ import os
 import sys
 
 if "--build" in sys.argv:
-    import subprocess
-
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    from raw2film_amd import build  # the product's sources and flags, plus the switch
+
     os.makedirs(os.path.join(root, "tools", "ablate"), exist_ok=True)
-    src = [os.path.join(root, "raw2film_amd", "csrc", f) for f in ("r2f_kernels.hip", "r2f_fft.hip", "r2f_api.hip", "r2f_stencil.hip", "r2f_graph.hip", "r2f_jpeg_api.hip")]
     for macro, values, stem in (("R2F_EXP", (1, 2, 3, 4), "lib_exp"), ("R2F_TAIL_EXP", (1, 2, 4, 7), "lib_tail")):
         for n in values:
-            out = os.path.join(root, "tools", "ablate", f"{stem}{n}.so")
-            subprocess.run(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared", f"-D{macro}={n}", "-o", out] + src,
-                           check=True)
-            print(out)
+            print(build.build(defines=[f"-D{macro}={n}"], out=os.path.join(root, "tools", "ablate", f"{stem}{n}.so")))
     sys.exit(0)
 
 import torch
