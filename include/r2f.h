@@ -507,25 +507,38 @@ R2F_API int r2f_jpeg_rows(r2f_ctx* ctx, const uint8_t* image, int64_t row_stride
  * optimize: per-image Huffman tables (libjpeg's optimize_coding), generated from the frame's symbol counts.  EXIF (an APP1
  * segment after SOI + APP0) is the caller's to splice into the file: it needs no device work.  progressive: 0, or 1 for
  * save(..., progressive=True): SOF2 and libjpeg's ten-scan jpeg_simple_progression, every scan with its own optimized tables
- * (libjpeg forces optimize_coding there, so `optimize` makes no difference); one-shot only (r2f_jpeg_encode_ex). */
+ * (libjpeg forces optimize_coding there, so `optimize` makes no difference); one-shot only (r2f_jpeg_encode_ex).
+ * restart_interval: 0, or the MCUs per restart interval, 1 .. 65535 -- Pillow's restart_marker_blocks, or restart_marker_rows
+ * times the MCUs per row, clamped to 65535.  The header then carries a DRI segment (FF DD 00 04 hi lo) between the last DHT and
+ * SOS; every interval codes its DC coefficients from predictors of 0 and ends padded with 1-bits to a whole byte, and RSTn
+ * (FF D0 + n, n = the interval's index mod 8, never stuffed) separates it from the next.  Baseline only: with progressive it is
+ * R2F_EINVAL.  x_density, y_density: both > 0 (at most 65535) make APP0 say dots per inch (Pillow's dpi, rounded); otherwise APP0
+ * stays "no units, 1 : 1".  The variable-length segments (EXIF, XMP, ICC, COM) are the caller's to splice in after APP0.
+ * The fields after `progressive` were appended: an initialiser of the first four leaves them 0, which is "none". */
 typedef struct r2f_jpeg_opts {
     int32_t quality, sampling, optimize, progressive;
+    int32_t restart_interval;
+    int32_t x_density, y_density;
 } r2f_jpeg_opts;
 /* Worst-case file size of an H x W frame in `sampling` at any quality and either table choice (0 for sizes JPEG cannot hold or a
  * bad sampling).  Per pixel: about 9.7 bytes for 4:2:0, 13.0 for 4:2:2, 19.5 for 4:4:4.  No GPU, no context. */
 R2F_API uint64_t r2f_jpeg_bound_bytes_ex(int H, int W, int sampling);
 /* Worst-case file size for any options, progressive included (0 for bad options or sizes).  A progressive file's bound is
  * larger than a baseline one's: a coefficient can cost a symbol, its value bits and correction bits in several scans (about
- * 12.1 bytes per pixel for 4:2:0, 16.1 for 4:2:2, 24.1 for 4:4:4).  No GPU, no context. */
+ * 12.1 bytes per pixel for 4:2:0, 16.1 for 4:2:2, 24.1 for 4:4:4).  No GPU, no context.
+ * A restart interval adds the DRI segment's 6 bytes and 4 bytes per interval (ceil(MCUs / restart_interval) of them): the
+ * marker's 2, the byte the interval's padding completes, and the 0x00 stuffed behind that byte when it comes out as 0xFF.  The
+ * scan's own bits are already counted at two bytes per byte. */
 R2F_API uint64_t r2f_jpeg_bound_bytes_opts(const r2f_jpeg_opts* opts, int H, int W);
-/* The header (SOI .. SOS) with the standard tables; R2F_EINVAL for optimize and progressive (their tables come from the
- * frame).  No GPU. */
+/* The header (SOI .. SOS) with the standard tables, APP0's density and the DRI segment of the options (cap >= 629 with a
+ * restart interval); R2F_EINVAL for optimize and progressive (their tables come from the frame).  No GPU. */
 R2F_API int r2f_jpeg_header_ex(const r2f_jpeg_opts* opts, int H, int W, uint8_t* buf, size_t cap, size_t* len);
 /* jpeg_gen_optimal_table of libjpeg: symbol counts -> bits[0] = 0, bits[1..16] codes per length, huffval[*n] the symbols by
  * code length, then symbol.  R2F_EINVAL when every count is zero, or when counts past libjpeg's 10^9 sentinel leave a table
  * libjpeg itself would refuse.  No GPU, no context. */
 R2F_API int r2f_jpeg_optimal_table(const uint64_t freq[256], uint8_t bits[17], uint8_t huffval[256], int* n);
-/* r2f_jpeg_encode with options (out_cap >= r2f_jpeg_bound_bytes_ex(H, W, sampling)).  Without optimize it is asynchronous like
+/* r2f_jpeg_encode with options (out_cap >= r2f_jpeg_bound_bytes_ex(H, W, sampling); with a restart interval
+ * r2f_jpeg_bound_bytes_opts(opts, H, W)).  Without optimize it is asynchronous like
  * r2f_jpeg_encode.  With optimize the call blocks once: the frame's coefficients and symbol counts are made on `stream`, the
  * 8 KB of counts are read back, the tables and header are built on the host, and the rest of the encode is queued on `stream`.
  * The context's scratch grows with the sampling: about 3, 4 and 6 bytes per pixel of coefficients plus the packed scan.
@@ -537,8 +550,9 @@ R2F_API int r2f_jpeg_optimal_table(const uint64_t freq[256], uint8_t bits[17], u
  * file would exceed out_cap: *out_len is then 0 and `out` holds no file. */
 R2F_API int r2f_jpeg_encode_ex(r2f_ctx* ctx, const uint8_t* image, int H, int W, int64_t row_stride, const r2f_jpeg_opts* opts,
                                uint8_t* out, uint64_t out_cap, uint64_t* out_len, void* stream);
-/* r2f_jpeg_rows_begin with options (out_cap >= r2f_jpeg_bound_bytes_ex(H, W, sampling)); R2F_EINVAL for optimize, whose tables
- * need the whole frame before the first scan byte, and for progressive, whose every scan spans the whole frame. */
+/* r2f_jpeg_rows_begin with options (out_cap >= r2f_jpeg_bound_bytes_opts(opts, H, W)); R2F_EINVAL for optimize, whose tables
+ * need the whole frame before the first scan byte, and for progressive, whose every scan spans the whole frame.  A restart
+ * interval may straddle calls: a marker is final, and counted in *out_len, with the call that holds its interval's last MCU. */
 R2F_API int r2f_jpeg_rows_begin_ex(r2f_ctx* ctx, int H, int W, const r2f_jpeg_opts* opts, uint8_t* out, uint64_t out_cap,
                                    uint64_t* out_len, void* stream);
 

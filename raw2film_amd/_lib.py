@@ -57,8 +57,9 @@ class Blit(C.Structure):  # r2f_blit: the uniform block of shaders/copy_to_int.w
     ]
 
 
-class JpegOpts(C.Structure):  # r2f_jpeg_opts (sampling: 0 4:4:4, 1 4:2:2, 2 4:2:0; progressive: 0 or 1)
-    _fields_ = [("quality", C.c_int32), ("sampling", C.c_int32), ("optimize", C.c_int32), ("progressive", C.c_int32)]
+class JpegOpts(C.Structure):  # r2f_jpeg_opts (sampling: 0 4:4:4, 1 4:2:2, 2 4:2:0; progressive: 0 or 1; the rest 0: none)
+    _fields_ = [("quality", C.c_int32), ("sampling", C.c_int32), ("optimize", C.c_int32), ("progressive", C.c_int32),
+                ("restart_interval", C.c_int32), ("x_density", C.c_int32), ("y_density", C.c_int32)]
 
 
 class TiffPlan(C.Structure):  # r2f_tiff_plan

@@ -715,44 +715,48 @@ class HipContext:
         return int(self._lib.r2f_jpeg_bound_bytes_ex(int(H), int(W), int(subsampling)))
 
     def jpeg_bound_bytes_opts(self, H: int, W: int, quality: int, subsampling: int = 2, optimize: bool = False,
-                              progressive: bool = False) -> int:
+                              progressive: bool = False, restart: int = 0) -> int:
         """Largest JPEG file r2f_jpeg_encode_ex can write for an H x W frame with these options (r2f_jpeg_bound_bytes_opts)."""
-        opts = _lib.JpegOpts(int(quality), int(subsampling), 1 if optimize else 0, 1 if progressive else 0)
+        opts = _lib.JpegOpts(int(quality), int(subsampling), 1 if optimize else 0, 1 if progressive else 0, int(restart))
         return int(self._lib.r2f_jpeg_bound_bytes_opts(C.byref(opts), int(H), int(W)))
 
-    def jpeg_encode(self, image_u8, quality: int, subsampling: int = 2, optimize: bool = False, progressive: bool = False):
+    def jpeg_encode(self, image_u8, quality: int, subsampling: int = 2, optimize: bool = False, progressive: bool = False,
+                    restart: int = 0, density=(0, 0)):
         """Baseline JPEG of a uint8 (H, W, 3) device image (rows may be strided; pixels packed) -> (uint8 device buffer of
         jpeg_bound_bytes, int64 device tensor of 1 holding the file's length).  Asynchronous on the current stream, except with
         optimize, whose call waits once for the frame's symbol counts (r2f_jpeg_encode_ex), and progressive, whose call waits for
         the ten scans' counts and then for the file's length (the buffer is then the progressive bound).  subsampling: 0 4:4:4,
-        1 4:2:2, 2 4:2:0."""
+        1 4:2:2, 2 4:2:0.  restart: MCUs per restart interval (0: none; the buffer is then jpeg_bound_bytes_opts); density: APP0's
+        (x, y) dots per inch, (0, 0) for none."""
         torch = self._torch
         if not (isinstance(image_u8, torch.Tensor) and image_u8.is_cuda and image_u8.dtype == torch.uint8 and image_u8.dim() == 3
                 and image_u8.shape[2] == 3 and image_u8.stride(2) == 1 and image_u8.stride(1) == 3):
             raise ValueError("jpeg_encode needs a uint8 (H, W, 3) CUDA tensor with packed pixels (row stride free)")
         self._same_device(image_u8, "image")
         H, W = int(image_u8.shape[0]), int(image_u8.shape[1])
-        bound = (self.jpeg_bound_bytes_opts(H, W, quality, subsampling, optimize, True) if progressive else
-                 self.jpeg_bound_bytes(H, W, subsampling))
+        plain = not restart and not any(density)
+        bound = (self.jpeg_bound_bytes_opts(H, W, quality, subsampling, optimize, bool(progressive), restart)
+                 if progressive or restart else self.jpeg_bound_bytes(H, W, subsampling))
         if bound == 0:
             raise ValueError(f"jpeg_encode: a JPEG holds 1 .. 65535 pixels per side, got {H} x {W} (subsampling {subsampling})")
         out = torch.empty(bound, dtype=torch.uint8, device=self.device)
         length = torch.empty(1, dtype=torch.int64, device=self.device)
-        if int(subsampling) == 2 and not optimize and not progressive:
+        if int(subsampling) == 2 and not optimize and not progressive and plain:
             self._check(self._lib.r2f_jpeg_encode(self._h, image_u8.data_ptr(), H, W, int(image_u8.stride(0)), int(quality),
                                                   out.data_ptr(), bound, length.data_ptr(), self._stream()))
         else:
-            opts = _lib.JpegOpts(int(quality), int(subsampling), 1 if optimize else 0, 1 if progressive else 0)
+            opts = _lib.JpegOpts(int(quality), int(subsampling), 1 if optimize else 0, 1 if progressive else 0, int(restart),
+                                 int(density[0]), int(density[1]))
             self._check(self._lib.r2f_jpeg_encode_ex(self._h, image_u8.data_ptr(), H, W, int(image_u8.stride(0)), C.byref(opts),
                                                      out.data_ptr(), bound, length.data_ptr(), self._stream()))
         return out, length
 
-    def jpeg_rows(self, H: int, W: int, quality: int, subsampling: int = 2):
+    def jpeg_rows(self, H: int, W: int, quality: int, subsampling: int = 2, restart: int = 0, density=(0, 0)):
         """Open a row-wise JPEG encode of an H x W frame (r2f_jpeg_rows_begin) on the current stream -> a JpegRows: feed it the
         frame's rows in order with .rows(image_u8, y0, y1); .out holds the file, .length the count of its leading bytes that are
         final.  A one-shot jpeg_encode or another jpeg_rows on this context ends it.  subsampling: 0 4:4:4, 1 4:2:2 (8-row
-        MCUs), 2 4:2:0 (16-row MCUs)."""
-        return JpegRows(self, H, W, quality, subsampling)
+        MCUs), 2 4:2:0 (16-row MCUs).  restart, density: as in jpeg_encode."""
+        return JpegRows(self, H, W, quality, subsampling, restart, density)
 
     def stage_noise(self, params, y0, y1, W, want_hash=True, want_noise=True):
         torch = self._torch
@@ -773,20 +777,21 @@ class JpegRows:
     stuffed scan byte no later rows can change -- and, once the last rows are in (`done`), the file's length.  Everything runs
     asynchronously on the stream that is current at each call."""
 
-    def __init__(self, ctx, H, W, quality, subsampling=2):
+    def __init__(self, ctx, H, W, quality, subsampling=2, restart=0, density=(0, 0)):
         torch = ctx._torch
         H, W = int(H), int(W)
-        bound = ctx.jpeg_bound_bytes(H, W, subsampling)
+        plain = not restart and not any(density)
+        bound = ctx.jpeg_bound_bytes_opts(H, W, quality, subsampling, restart=restart) if restart else ctx.jpeg_bound_bytes(H, W, subsampling)
         if bound == 0:
             raise ValueError(f"jpeg_rows: a JPEG holds 1 .. 65535 pixels per side, got {H} x {W} (subsampling {subsampling})")
         self._ctx, self.H, self.W, self.quality, self.subsampling = ctx, H, W, int(quality), int(subsampling)
         self.out = torch.empty(bound, dtype=torch.uint8, device=ctx.device)
         self.length = torch.empty(1, dtype=torch.int64, device=ctx.device)
-        if self.subsampling == 2:
+        if self.subsampling == 2 and plain:
             ctx._check(ctx._lib.r2f_jpeg_rows_begin(ctx._h, H, W, self.quality, self.out.data_ptr(), bound, self.length.data_ptr(),
                                                     ctx._stream()))
         else:
-            opts = _lib.JpegOpts(self.quality, self.subsampling, 0, 0)
+            opts = _lib.JpegOpts(self.quality, self.subsampling, 0, 0, int(restart), int(density[0]), int(density[1]))
             ctx._check(ctx._lib.r2f_jpeg_rows_begin_ex(ctx._h, H, W, C.byref(opts), self.out.data_ptr(), bound,
                                                        self.length.data_ptr(), ctx._stream()))
         self.next_row, self.done = 0, False

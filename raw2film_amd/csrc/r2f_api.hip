@@ -141,7 +141,7 @@ r2f_ctx::Exposure::~Exposure() {
 // =============================================================================== C ABI
 extern "C" {
 
-const char* r2f_version(void) { return "r2f-hip 0.6 gfx950 abi6"; }
+const char* r2f_version(void) { return "r2f-hip 0.6 gfx950 abi7"; }
 
 int r2f_create(int device, r2f_ctx** out) {
     if (!out) return R2F_EINVAL;

@@ -221,7 +221,7 @@ struct r2f_ctx {
         struct Rows {
             bool open = false;
             int H = 0, W = 0, next_y = 0;
-            int sampling = 2, header_len = 0;
+            int sampling = 2, header_len = 0, restart = 0;
             uint8_t* out = nullptr;
             uint64_t* out_len = nullptr;
         } rows;

@@ -15,12 +15,13 @@ struct JpegEncodeArgs {
     int H, W;
     void* scratch;  // jpeg::scratch_layout(H, W, sampling).total bytes
     jpeg::Tables tables;
-    const uint8_t* header;  // header_len <= jpeg::kHeaderBytes bytes (host memory: copied into a launch argument)
-    uint8_t* out;           // >= jpeg::bound_bytes(H, W, sampling)
+    const uint8_t* header;  // header_len <= jpeg::kHeaderBytes + jpeg::kDriBytes bytes (host memory: copied into a launch argument)
+    uint8_t* out;           // >= jpeg::bound_bytes(H, W, sampling, restart)
     unsigned long long* out_len;
     void* carry = nullptr;  // row-wise: 2 device words, the scan's bits and 0xFF bytes so far
     int sampling = 2;       // 0 4:4:4, 1 4:2:2, 2 4:2:0
     int header_len = jpeg::kHeaderBytes;
+    int restart = 0;        // MCUs per restart interval (0: none); the scratch is then jpeg::scratch_layout(H, W, sampling, restart)
     bool recount = false;   // encode: the coefficients are in the scratch already (launch_jpeg_stats); count bits with `tables`
 };
 hipError_t launch_jpeg_encode(const JpegEncodeArgs& a, hipStream_t s);

@@ -3,7 +3,7 @@
 //   1. transform   one wave per 16 x 16 MCU: RGB -> YCbCr (jccolor.c), h2v2 downsampling (jcsample.c), edge replication, ISLOW
 //                  DCT (jfdctint.c), quantisation (jcdctmgr.c), dummy blocks (jccoefct.c); coefficients stored in zigzag order, and
 //                  the MCU's bits counted except for the DC differences that need the MCU before it
-//   2. dc_bits     those three DC differences (one predictor per component runs across the whole frame: no restart intervals)
+//   2. dc_bits     those three DC differences (one predictor per component runs across the whole frame, or its restart interval)
 //   3. scan        exclusive scan of the bits per MCU, 64-bit (a worst-case 100 MP frame exceeds 2^32 bits)
 //   4. zero, pack  the words the scan will occupy are cleared; one wave per MCU assembles its bits in LDS and stores them, with an
 //                  atomic OR only for the first and last word, which it may share with its neighbours
@@ -22,6 +22,13 @@
 // and the stuffing passes take the bytes that became complete, [floor(before / 8), floor(after / 8)) -- the partial last byte
 // waits for the next call, the last call pads it -- with the 0xFF count scanned from the carried one.  *out_len then counts the
 // leading bytes of the file that are final.
+// Restart intervals (EncodeArgs::restart MCUs each; 0 takes exactly the passes above): an MCU whose index is a multiple of the
+// interval predicts its DC coefficients from 0 (dc_bits, stats, bits, pack).  The scan's positions are no plain prefix sum any
+// more -- every interval starts on a byte boundary, 16 bits behind the padded end of the one before -- so after the plain scan
+// three small kernels lay the intervals out (restart_* below): each interval's length with its padding and marker, the same
+// 64-bit scan over the intervals, and the shift of every MCU's offset to its interval's place.  offsets[m] is then the MCU's
+// bit position in a scan that holds the padding and the markers: pack, which ends an interval, writes both behind its MCU's
+// bits, and the stuffing passes tell a marker's 0xFF from a data byte by looking its position up in offsets[].
 #include "r2f_launch.h"
 #include "r2f_jpeg.h"
 
@@ -35,7 +42,8 @@ using u64 = unsigned long long;
 using jpeg::Tables;
 
 constexpr int kWaves = 4;          // MCUs per workgroup of the transform and pack kernels (one per wave)
-constexpr int kPackWords = 320;    // LDS words per wave in pack: an MCU spans at most (31 + 6 * 1660 + 31) / 32 = 313
+constexpr int kPackWords = 320;    // LDS words per wave in pack: an MCU spans at most (31 + 6 * 1660 + 31) / 32 = 313 (314 with the
+                                   // 23 bits of padding and marker that end a restart interval)
 constexpr int kStatsGroups = 1024; // workgroups of the stats kernel (each walks MCUs, then adds its histograms: <= 1024 atomics)
 
 // An MCU's shape per sampling (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0): pixels, luminance blocks, all blocks (Y.. Cb Cr)
@@ -66,11 +74,23 @@ struct EncodeArgs {
     uint8_t* out;
     u64* out_len;
     int hdr_len;       // the header's bytes (the scan starts there)
+    int restart;       // MCUs per restart interval (0: none)
+    u64* intervals;    // restart: [intervals of the launch + 1]
 };
 
 struct HeaderBytes {
-    uint8_t b[jpeg::kHeaderBytes];
+    uint8_t b[jpeg::kHeaderBytes + jpeg::kDriBytes];
 };
+
+// The MCU before m for the DC prediction of m's coefficients `c`: none for the frame's first MCU and for the first of a restart
+// interval.
+__device__ inline const int16_t* prev_mcu(const EncodeArgs& a, long long m, const int16_t* c, int mcu_coefs) {
+    return m && !(a.restart && (uint32_t)m % (uint32_t)a.restart == 0) ? c - mcu_coefs : nullptr;  // (MCU indices fit 32 bits)
+}
+// MCU m ends a restart interval (the frame's last MCU ends the last one).
+__device__ inline bool ends_interval(const EncodeArgs& a, long long m) {
+    return (uint32_t)(m + 1) % (uint32_t)a.restart == 0 || m + 1 == a.n_mcus;
+}
 
 __device__ inline int magnitude_bits(int v) {
     v = v < 0 ? -v : v;
@@ -286,7 +306,7 @@ __global__ __launch_bounds__(256) void jpeg_dc_bits_kernel(EncodeArgs a) {
     const long long m = a.m0 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= a.m1) return;
     const int16_t* c = a.coefs + m * (NB * 64);
-    const int16_t* p = m ? c - NB * 64 : nullptr;
+    const int16_t* p = prev_mcu(a, m, c, NB * 64);
     a.offsets[m] += (u64)(dc_bits(a.tables, 0, c[0] - (p ? p[(NY - 1) * 64] : 0)) +
                           dc_bits(a.tables, 1, c[NY * 64] - (p ? p[NY * 64] : 0)) +
                           dc_bits(a.tables, 1, c[(NY + 1) * 64] - (p ? p[(NY + 1) * 64] : 0)));
@@ -313,7 +333,7 @@ __global__ __launch_bounds__(256) void jpeg_stats_kernel(EncodeArgs a, u64* freq
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (long long m = a.m0 + (long long)blockIdx.x * kWaves + w; m < a.m1; m += (long long)gridDim.x * kWaves) {
         const int16_t* c = a.coefs + m * (L::NB * 64);
-        const int16_t* p = m ? c - L::NB * 64 : nullptr;
+        const int16_t* p = prev_mcu(a, m, c, L::NB * 64);
         for (int k = 0; k < L::NB; ++k) {
             const int t = k < L::NY ? 0 : 1;
             const int v = c[k * 64 + lane];
@@ -350,7 +370,7 @@ __global__ __launch_bounds__(256) void jpeg_bits_kernel(EncodeArgs a) {
     const long long m = a.m0 + (long long)blockIdx.x * kWaves + w;
     if (m >= a.m1) return;
     const int16_t* c = a.coefs + m * (L::NB * 64);
-    const int16_t* p = m ? c - L::NB * 64 : nullptr;
+    const int16_t* p = prev_mcu(a, m, c, L::NB * 64);
     int bits = 0;
     for (int k = 0; k < L::NB; ++k) {
         const int t = k < L::NY ? 0 : 1;
@@ -410,6 +430,53 @@ void scan_u64(u64* data, long long n, u64* partial, hipStream_t s, const u64* ba
     launch_k(scan_add_kernel, dim3((unsigned)nb), dim3(256), 0, s, data, n, (const u64*)partial);
 }
 
+// ----------------------------------------------------------------------------------------------- 3b. restart intervals
+// The launch's MCUs [m0, m1) fall into the intervals j = m / restart - m0 / restart (the first may have begun in a launch before,
+// the last may go on in the next).  offsets[m0 .. m1] hold the plain scan from 0.  intervals[j] = the bits interval j adds to the
+// scan: its MCUs', then, if it ends in this launch, the padding to a whole byte -- counted from `*carry`, the position the launch
+// starts at, for the first one, which alone may start inside a byte -- and the 16 bits of its marker unless it ends the frame.
+__global__ __launch_bounds__(256) void restart_length_kernel(EncodeArgs a, long long n_int, const u64* carry) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_int) return;
+    const long long k = a.m0 / a.restart + j;
+    const long long first = max(k * a.restart, a.m0), end = min((k + 1) * (long long)a.restart, a.m1);
+    u64 len = a.offsets[end] - a.offsets[first];
+    if (end % a.restart == 0 || end == a.n_mcus) {
+        const u64 at = (j == 0 && carry ? *carry : 0) + len;
+        len += (0 - at) & 7;
+        if (end != a.n_mcus) len += 16;
+    }
+    a.intervals[j] = len;
+}
+
+// intervals[] scanned (from the carried position): intervals[j] = where interval j's MCUs of this launch start.  Each becomes
+// the shift of its MCUs' offsets, start - offsets[its first MCU]; intervals[n_int], the position after the launch, stays.
+__global__ __launch_bounds__(256) void restart_shift_kernel(EncodeArgs a, long long n_int) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_int) return;
+    a.intervals[j] -= a.offsets[max((a.m0 / a.restart + j) * a.restart, a.m0)];
+}
+
+// offsets[m] += its interval's shift; offsets[m1] = the position after the launch.  (In place: every thread touches its own
+// element, the shifts were taken from the unshifted offsets by the kernel before.)
+__global__ __launch_bounds__(256) void restart_place_kernel(EncodeArgs a, long long n_int) {
+    const long long m = a.m0 + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m < a.m1) a.offsets[m] += a.intervals[m / a.restart - a.m0 / a.restart];
+    if (m == a.m1) a.offsets[m] = a.intervals[n_int];
+}
+
+// The restart-aware scan of a launch's bits per MCU: offsets[m0 .. m1] as positions in the padded scan.  Everything stays on the
+// stream; the intervals take the same recursive scan as the MCUs, so their number is not bounded by one scan block.
+void restart_scan(const EncodeArgs& a, u64* partial, hipStream_t s, const u64* carry) {
+    const long long n = a.m1 - a.m0, n_int = (a.m1 - 1) / a.restart - a.m0 / a.restart + 1;
+    scan_u64(a.offsets + a.m0, n, partial, s);
+    const dim3 gi((unsigned)((n_int + 255) / 256)), b(256);
+    launch_k(restart_length_kernel, gi, b, 0, s, a, n_int, carry);
+    scan_u64(a.intervals, n_int, partial, s, carry);
+    launch_k(restart_shift_kernel, gi, b, 0, s, a, n_int);
+    launch_k(restart_place_kernel, dim3((unsigned)((n + 1 + 255) / 256)), b, 0, s, a, n_int);
+}
+
 // --------------------------------------------------------------------------------------------------------------- 4. pack
 // Words [ceil(begin / 32), ceil(end / 32)) of the packed scan cleared (what pack ORs into must start at zero; the word holding bit
 // `begin`, if it is not the first of its word, holds the bits of the launch before).
@@ -445,7 +512,7 @@ __global__ __launch_bounds__(256) void jpeg_pack_kernel(EncodeArgs a) {
     const int nw = live ? (int)(((start & 31) + (end - start) + 31) >> 5) : 0;
     if (live && nw <= kPackWords) {
         const int16_t* c = a.coefs + m * (L::NB * 64);
-        const int16_t* p = m ? c - L::NB * 64 : nullptr;
+        const int16_t* p = prev_mcu(a, m, c, L::NB * 64);
         int pos = (int)(start & 31);  // bit position in the wave's words
         for (int k = 0; k < L::NB; ++k) {
             const int t = k < L::NY ? 0 : 1;
@@ -480,6 +547,13 @@ __global__ __launch_bounds__(256) void jpeg_pack_kernel(EncodeArgs a) {
             if (lane == last && last < 63) put_bits(lds, at, ac[0x00] >> 8, sym_len(ac[0x00]));
             pos += __shfl(inc, 63, 64);
         }
+        // the end of a restart interval: 1-bits up to the byte boundary (jchuff.c flush_bits), then RSTn unless the frame ends
+        // (both inside [start, end): restart_scan counted them to this MCU, and kPackWords has room for their 23 bits)
+        if (a.restart && lane == 0 && ends_interval(a, m)) {
+            const int pad = -pos & 7;
+            if (pad) put_bits(lds, pos, 0xFFu, pad);
+            if (m + 1 != a.n_mcus) put_bits(lds, pos + pad, 0xFFD0u | (uint32_t)((m / a.restart) & 7), 16);
+        }
     }
     __syncthreads();
     if (!live || nw > kPackWords) return;
@@ -510,6 +584,28 @@ __device__ inline void stuff_range(const EncodeArgs& a, u64& lo, u64& hi, u64& t
     hi = total > a.bound_bits ? lo : a.last ? (total + 7) / 8 : total / 8;
 }
 
+// Whether the 0xFF at scan byte i is the first byte of a restart marker, not data: the marker before interval k ends where the
+// interval starts, at bit offsets[k restart], so byte i is one iff 8 (i + 2) is such a start.  Only a 0xFF followed by D0 .. D7
+// is looked up (a binary search over the interval starts laid out so far, k <= m1 / restart; a marker's second byte lies in the
+// same launch's bytes as its first).  Interval starts increase strictly: every MCU has bits.
+__device__ inline bool is_marker(const EncodeArgs& a, u64 i, u64 total) {
+    if (!a.restart || i + 1 >= (total + 7) / 8) return false;
+    if ((scan_byte(a.words, i + 1, total) & 0xF8) != 0xD0) return false;
+    const u64 want = 8 * (i + 2);
+    long long lo = 1, hi = min((a.n_mcus - 1) / a.restart, a.m1 / a.restart);  // interval starts k in [lo, hi]
+    while (lo < hi) {
+        const long long mid = (lo + hi) / 2;
+        if (a.offsets[mid * a.restart] < want)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo == hi && a.offsets[lo * a.restart] == want;
+}
+
+// Whether scan byte i gets a 0x00 behind it.
+__device__ inline bool stuffed(const EncodeArgs& a, uint32_t byte, u64 i, u64 total) { return byte == 0xFF && !is_marker(a, i, total); }
+
 // 0xFF bytes of each kStuffChunk bytes of the range (one chunk per workgroup, 16 bytes per thread); chunks past it count 0.
 __global__ __launch_bounds__(256) void jpeg_ff_count_kernel(EncodeArgs a) {
     __shared__ int wave_tot[4];
@@ -518,7 +614,7 @@ __global__ __launch_bounds__(256) void jpeg_ff_count_kernel(EncodeArgs a) {
     const u64 b0 = lo + (u64)blockIdx.x * jpeg::kStuffChunk + threadIdx.x * 16;
     int cnt = 0;
     for (int j = 0; j < 16; ++j)
-        if (b0 + j < hi) cnt += scan_byte(a.words, b0 + j, total) == 0xFF;
+        if (b0 + j < hi) cnt += stuffed(a, scan_byte(a.words, b0 + j, total), b0 + j, total);
     for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
     if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = cnt;
     __syncthreads();
@@ -532,11 +628,11 @@ __global__ __launch_bounds__(256) void jpeg_scatter_kernel(EncodeArgs a) {
     stuff_range(a, lo, hi, total);
     const u64 b0 = lo + (u64)blockIdx.x * jpeg::kStuffChunk + threadIdx.x * 16;
     if (lo + (u64)blockIdx.x * jpeg::kStuffChunk >= hi) return;  // (the whole workgroup: no barrier is skipped by part of it)
-    uint32_t bytes[16];
+    uint32_t bytes[16], stuff = 0;  // (stuff: bit j = a 0x00 follows byte j)
     int cnt = 0;
     for (int j = 0; j < 16; ++j) {
         bytes[j] = b0 + j < hi ? scan_byte(a.words, b0 + j, total) : 0;
-        cnt += b0 + j < hi && bytes[j] == 0xFF;
+        if (b0 + j < hi && stuffed(a, bytes[j], b0 + j, total)) stuff |= 1u << j, ++cnt;
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int inc = wave_inclusive<int>(cnt, lane);
@@ -549,7 +645,7 @@ __global__ __launch_bounds__(256) void jpeg_scatter_kernel(EncodeArgs a) {
         if (b0 + j >= hi) break;
         const u64 o = b0 + j + ff;
         out[o] = (uint8_t)bytes[j];
-        if (bytes[j] == 0xFF) {
+        if (stuff >> j & 1) {
             out[o + 1] = 0;
             ++ff;
         }
@@ -622,9 +718,11 @@ EncodeArgs encode_args(const JpegEncodeArgs& e, const jpeg::Scratch& L) {
     a.words = reinterpret_cast<uint32_t*>(base + L.words);
     a.chunks = reinterpret_cast<u64*>(base + L.chunks);
     a.n_chunks = (long long)L.stuff_chunks;
-    a.bound_bits = jpeg::scan_bound_bits(e.H, e.W, e.sampling);
+    a.bound_bits = jpeg::scan_bound_bits(e.H, e.W, e.sampling, e.restart);
     a.out = e.out, a.out_len = e.out_len;
     a.hdr_len = e.header_len;
+    a.restart = e.restart;
+    a.intervals = reinterpret_cast<u64*>(base + L.intervals);
     return a;
 }
 
@@ -653,7 +751,7 @@ McuKernels mcu_kernels(int sampling) {
 }  // namespace
 
 hipError_t launch_jpeg_stats(const JpegEncodeArgs& e, unsigned long long* freq, hipStream_t s) {
-    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W, e.sampling);
+    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W, e.sampling, e.restart);
     const EncodeArgs a = encode_args(e, L);
     const McuKernels K = mcu_kernels(e.sampling);
     const unsigned mcu_groups = (unsigned)((L.n_mcus + kWaves - 1) / kWaves);
@@ -669,7 +767,7 @@ hipError_t launch_jpeg_stats(const JpegEncodeArgs& e, unsigned long long* freq, 
 }
 
 hipError_t launch_jpeg_transform(const JpegEncodeArgs& e, hipStream_t s) {
-    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W, e.sampling);
+    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W, e.sampling, e.restart);
     const EncodeArgs a = encode_args(e, L);
     launch_k(jpeg_tables_kernel, dim3(1), dim3(256), 0, s, e.tables, const_cast<Tables*>(a.tables));
     launch_k(mcu_kernels(e.sampling).transform, dim3((unsigned)((L.n_mcus + kWaves - 1) / kWaves)), dim3(256), 0, s, a);
@@ -679,7 +777,7 @@ hipError_t launch_jpeg_transform(const JpegEncodeArgs& e, hipStream_t s) {
 void jpeg_scan_u64(unsigned long long* data, long long n, unsigned long long* partial, hipStream_t s) { scan_u64(data, n, partial, s); }
 
 hipError_t launch_jpeg_encode(const JpegEncodeArgs& e, hipStream_t s) {
-    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W, e.sampling);
+    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W, e.sampling, e.restart);
     const EncodeArgs a = encode_args(e, L);
     u64* partial = reinterpret_cast<u64*>(static_cast<uint8_t*>(e.scratch) + L.partial);
     const HeaderBytes h = header_bytes(e.header, e.header_len);
@@ -693,7 +791,10 @@ hipError_t launch_jpeg_encode(const JpegEncodeArgs& e, hipStream_t s) {
         launch_k(K.transform, dim3(mcu_groups), dim3(256), 0, s, a);
         launch_k(K.dc_bits, dim3((unsigned)((L.n_mcus + 255) / 256)), dim3(256), 0, s, a);
     }
-    scan_u64(a.offsets, a.n_mcus, partial, s);
+    if (a.restart)
+        restart_scan(a, partial, s, nullptr);
+    else
+        scan_u64(a.offsets, a.n_mcus, partial, s);
     const u64 max_words = (a.bound_bits + 31) / 32;
     launch_k(jpeg_zero_kernel, dim3((unsigned)std::min<u64>((max_words + 255) / 256, 4096)), dim3(256), 0, s, a);
     launch_k(K.pack, dim3(mcu_groups), dim3(256), 0, s, a);
@@ -705,7 +806,7 @@ hipError_t launch_jpeg_encode(const JpegEncodeArgs& e, hipStream_t s) {
 }
 
 hipError_t launch_jpeg_rows_begin(const JpegEncodeArgs& e, hipStream_t s) {
-    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W, e.sampling);
+    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W, e.sampling, e.restart);
     Tables* tables = reinterpret_cast<Tables*>(static_cast<uint8_t*>(e.scratch) + L.tables);
     launch_k(jpeg_tables_kernel, dim3(1), dim3(256), 0, s, e.tables, tables);
     launch_k(jpeg_rows_begin_kernel, dim3(1), dim3(256), 0, s, header_bytes(e.header, e.header_len), e.header_len, e.out, e.out_len,
@@ -714,7 +815,7 @@ hipError_t launch_jpeg_rows_begin(const JpegEncodeArgs& e, hipStream_t s) {
 }
 
 hipError_t launch_jpeg_rows(const JpegEncodeArgs& e, const jpeg::RowsGrid& g, bool last, hipStream_t s) {
-    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W, e.sampling);
+    const jpeg::Scratch L = jpeg::scratch_layout(e.H, e.W, e.sampling, e.restart);
     EncodeArgs a = encode_args(e, L);
     const McuKernels K = mcu_kernels(e.sampling);
     a.m0 = (long long)g.m0, a.m1 = (long long)g.m1, a.last = last ? 1 : 0;
@@ -726,7 +827,13 @@ hipError_t launch_jpeg_rows(const JpegEncodeArgs& e, const jpeg::RowsGrid& g, bo
     const unsigned mcu_groups = (unsigned)((n + kWaves - 1) / kWaves);
     launch_k(K.transform, dim3(mcu_groups), dim3(256), 0, s, a);
     launch_k(K.dc_bits, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
-    scan_u64(a.offsets + a.m0, n, partial, s, carry);  // offsets[m0] = the bits before, offsets[m1] = the bits after
+    // offsets[m0] = the bits before, offsets[m1] = the bits after.  With restart intervals the carry needs no new word: carry[0]
+    // is the position the next MCU starts at, the padding and marker of an interval that ended with the launch included, and
+    // which interval an MCU belongs to, whether it starts or ends one and the marker's number all follow from its global index.
+    if (a.restart)
+        restart_scan(a, partial, s, carry);
+    else
+        scan_u64(a.offsets + a.m0, n, partial, s, carry);
     launch_k(jpeg_zero_kernel, dim3((unsigned)std::min<u64>((g.zero_words + 255) / 256, 4096)), dim3(256), 0, s, a);
     launch_k(K.pack, dim3(mcu_groups), dim3(256), 0, s, a);
     launch_k(jpeg_ff_count_kernel, dim3((unsigned)g.stuff_chunks), dim3(256), 0, s, a);

@@ -23,25 +23,34 @@ int jpeg_prepare(r2f_ctx* ctx, int H, int W, int64_t row_stride, const r2f_jpeg_
     if (o->optimize != 0 && o->optimize != 1) return fail(ctx, R2F_EINVAL, "jpeg: optimize %d is not 0 or 1", o->optimize);
     if (o->progressive != 0 && o->progressive != 1)
         return fail(ctx, R2F_EINVAL, "jpeg: progressive %d is not 0 or 1", o->progressive);
+    if (!jpeg::valid_restart(o->restart_interval))
+        return fail(ctx, R2F_EINVAL, "jpeg: restart_interval %d is not in 0 .. %d", o->restart_interval, jpeg::kMaxRestart);
+    if (o->progressive && o->restart_interval)
+        return fail(ctx, R2F_EINVAL, "jpeg: progressive with a restart_interval is not supported (baseline only)");
+    if (o->x_density < 0 || o->y_density < 0 || o->x_density > jpeg::kMaxDensity || o->y_density > jpeg::kMaxDensity)
+        return fail(ctx, R2F_EINVAL, "jpeg: density %d x %d is not in 0 .. %d", o->x_density, o->y_density, jpeg::kMaxDensity);
     if (row_stride >= 0 && row_stride < 3LL * W)
         return fail(ctx, R2F_EINVAL, "jpeg: row stride %lld < 3 W = %lld", (long long)row_stride, 3LL * W);
     if ((uintptr_t)out_len % 8) return fail(ctx, R2F_EINVAL, "jpeg: out_len must be 8-byte aligned");
-    const uint64_t bound = o->progressive ? jpeg::prog_bound_bytes(H, W, o->sampling) : jpeg::bound_bytes(H, W, o->sampling);
+    const uint64_t bound =
+        o->progressive ? jpeg::prog_bound_bytes(H, W, o->sampling) : jpeg::bound_bytes(H, W, o->sampling, o->restart_interval);
     if (out_cap < bound)
         return fail(ctx, R2F_EINVAL, "jpeg: output capacity %llu < bound %llu", (unsigned long long)out_cap, (unsigned long long)bound);
-    const size_t total = o->progressive ? jpeg::prog_scratch_layout(H, W, o->sampling).total : jpeg::scratch_layout(H, W, o->sampling).total;
+    const size_t total = o->progressive ? jpeg::prog_scratch_layout(H, W, o->sampling).total : jpeg::scratch_layout(H, W, o->sampling, o->restart_interval).total;
     // (an earlier encode may still be working in the old buffer; no captured graph reads it)
     return ctx->jpeg.scratch.reserve(ctx, total, Grow::Sync);
 }
+
+jpeg::HeaderExtras header_extras(const r2f_jpeg_opts* o) { return jpeg::HeaderExtras{o->restart_interval, o->x_density, o->y_density}; }
 
 // The standard tables and header of an encode.
 int jpeg_std_setup(r2f_ctx* ctx, const r2f_jpeg_opts* o, int H, int W, JpegEncodeArgs* a, uint8_t* hdr, size_t cap) {
     jpeg::Huffman h;
     jpeg::std_huffman(&h);
     jpeg::make_tables(o->quality, h, &a->tables);
-    const int n = jpeg::header(o->quality, o->sampling, h, H, W, hdr, cap);
+    const int n = jpeg::header(o->quality, o->sampling, h, H, W, header_extras(o), hdr, cap);
     if (n < 0) return fail(ctx, R2F_EINVAL, "jpeg: header");
-    a->header = hdr, a->header_len = n, a->sampling = o->sampling;
+    a->header = hdr, a->header_len = n, a->sampling = o->sampling, a->restart = o->restart_interval;
     return R2F_OK;
 }
 
@@ -56,7 +65,7 @@ int jpeg_encode_progressive(r2f_ctx* ctx, const r2f_jpeg_opts* o, JpegEncodeArgs
                                 hipMemcpyDeviceToHost, s));
     R2F_HIP(ctx, hipStreamSynchronize(s));
     uint8_t frame[jpeg::kProgFrameHeaderBytes];
-    if (jpeg::prog_frame_header(o->quality, o->sampling, H, W, frame, sizeof frame) != jpeg::kProgFrameHeaderBytes)
+    if (jpeg::prog_frame_header(o->quality, o->sampling, H, W, frame, sizeof frame, o->x_density, o->y_density) != jpeg::kProgFrameHeaderBytes)
         return fail(ctx, R2F_EINVAL, "jpeg: progressive frame header");
     std::vector<ProgScanPlan> plans(jpeg::kProgScans);
     uint64_t file = jpeg::kProgFrameHeaderBytes + 2;
@@ -122,7 +131,7 @@ int r2f_jpeg_encode_ex(r2f_ctx* ctx, const uint8_t* image, int H, int W, int64_t
     JpegEncodeArgs a;
     a.image = image, a.row_stride = row_stride, a.H = H, a.W = W, a.scratch = ctx->jpeg.scratch.p;
     a.out = out, a.out_len = reinterpret_cast<unsigned long long*>(out_len);
-    uint8_t hdr[jpeg::kHeaderBytes];
+    uint8_t hdr[jpeg::kHeaderBytes + jpeg::kDriBytes];
     if ((rc = jpeg_std_setup(ctx, opts, H, W, &a, hdr, sizeof hdr))) return rc;
     if (opts->progressive) return jpeg_encode_progressive(ctx, opts, a, out_cap, s);
     if (opts->optimize) {
@@ -145,7 +154,7 @@ int r2f_jpeg_encode_ex(r2f_ctx* ctx, const uint8_t* image, int H, int W, int64_t
         if (jpeg::scan_bits(freq, h) > jpeg::scan_bound_bits(H, W, opts->sampling))
             return fail(ctx, R2F_ETOOLARGE, "jpeg: the optimized scan exceeds the bound");
         jpeg::make_tables(opts->quality, h, &a.tables);
-        const int n = jpeg::header(opts->quality, opts->sampling, h, H, W, hdr, sizeof hdr);
+        const int n = jpeg::header(opts->quality, opts->sampling, h, H, W, header_extras(opts), hdr, sizeof hdr);
         if (n < 0) return fail(ctx, R2F_EINVAL, "jpeg: header");
         a.header_len = n, a.recount = true;
     }
@@ -172,13 +181,14 @@ int r2f_jpeg_rows_begin_ex(r2f_ctx* ctx, int H, int W, const r2f_jpeg_opts* opts
     if ((rc = ctx->jpeg.carry.reserve(ctx, 64, Grow::Quiet))) return rc;
     JpegEncodeArgs a;
     a.image = nullptr, a.row_stride = 0, a.H = H, a.W = W, a.scratch = ctx->jpeg.scratch.p, a.carry = ctx->jpeg.carry.p;
-    uint8_t hdr[jpeg::kHeaderBytes];
+    uint8_t hdr[jpeg::kHeaderBytes + jpeg::kDriBytes];
     if ((rc = jpeg_std_setup(ctx, opts, H, W, &a, hdr, sizeof hdr))) return rc;
     a.out = out, a.out_len = reinterpret_cast<unsigned long long*>(out_len);
     R2F_HIP(ctx, launch_jpeg_rows_begin(a, static_cast<hipStream_t>(stream)));
     ctx->jpeg.rows.open = true;
     ctx->jpeg.rows.H = H, ctx->jpeg.rows.W = W, ctx->jpeg.rows.next_y = 0;
     ctx->jpeg.rows.sampling = opts->sampling, ctx->jpeg.rows.header_len = a.header_len;
+    ctx->jpeg.rows.restart = opts->restart_interval;
     ctx->jpeg.rows.out = out, ctx->jpeg.rows.out_len = out_len;
     return R2F_OK;
 }
@@ -199,12 +209,12 @@ int r2f_jpeg_rows(r2f_ctx* ctx, const uint8_t* image, int64_t row_stride, int y0
         return fail(ctx, R2F_EINVAL, "jpeg rows: row stride %lld < 3 W = %lld", (long long)row_stride, 3LL * r.W);
     if (y0 != r.next_y) return fail(ctx, R2F_EINVAL, "jpeg rows: rows from %d, but the encode is at row %d", y0, r.next_y);
     jpeg::RowsGrid g;
-    if (!jpeg::rows_grid(r.H, r.W, r.sampling, y0, y1, &g))
+    if (!jpeg::rows_grid(r.H, r.W, r.sampling, y0, y1, &g, r.restart))
         return fail(ctx, R2F_EINVAL, "jpeg rows: rows [%d, %d) of %d: the end must lie past the start and be a multiple of %d or %d",
                     y0, y1, r.H, jpeg::layout(r.sampling).mh, r.H);
     JpegEncodeArgs a;
     a.image = image, a.row_stride = row_stride, a.H = r.H, a.W = r.W, a.scratch = ctx->jpeg.scratch.p, a.carry = ctx->jpeg.carry.p;
-    a.sampling = r.sampling, a.header_len = r.header_len;
+    a.sampling = r.sampling, a.header_len = r.header_len, a.restart = r.restart;
     a.header = nullptr, a.out = r.out, a.out_len = reinterpret_cast<unsigned long long*>(r.out_len);
     const bool last = y1 == r.H;
     R2F_HIP(ctx, launch_jpeg_rows(a, g, last, static_cast<hipStream_t>(stream)));

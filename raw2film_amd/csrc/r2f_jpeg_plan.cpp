@@ -177,9 +177,25 @@ void make_tables(int quality, Tables* t) {
     make_tables(quality, h, t);
 }
 
+namespace {
+// APP0: JFIF 1.01, no thumbnail; no units and density 1 : 1, or dots per inch when both densities are given (Pillow's dpi)
+void app0(Writer& w, int xd, int yd) {
+    const bool dpi = xd > 0 && yd > 0;
+    w.marker(0xE0, 14);
+    for (int c : {0x4A, 0x46, 0x49, 0x46, 0, 1, 1}) w.u8(c);  // "JFIF\0", version
+    w.u8(dpi ? 1 : 0), w.u16(dpi ? xd : 1), w.u16(dpi ? yd : 1), w.u8(0), w.u8(0);
+}
+bool valid_density(int xd, int yd) { return xd >= 0 && yd >= 0 && xd <= kMaxDensity && yd <= kMaxDensity; }
+}  // namespace
+
 int header(int quality, int sampling, const Huffman& h, int H, int W, uint8_t* buf, size_t cap) {
+    return header(quality, sampling, h, H, W, HeaderExtras{}, buf, cap);
+}
+
+int header(int quality, int sampling, const Huffman& h, int H, int W, const HeaderExtras& x, uint8_t* buf, size_t cap) {
     if (!buf || !valid_sampling(sampling) || quality < 0 || quality > 100 || H < 1 || W < 1 || H > kMaxDim || W > kMaxDim) return -1;
-    int len = 275;  // everything but the DHT symbols
+    if (!valid_restart(x.restart) || !valid_density(x.x_density, x.y_density)) return -1;
+    int len = 275 + (x.restart ? kDriBytes : 0);  // everything but the DHT symbols
     for (int t = 0; t < 4; ++t) {
         int n = 0;
         for (int i = 0; i < 16; ++i) n += h.bits[t][i];
@@ -191,8 +207,7 @@ int header(int quality, int sampling, const Huffman& h, int H, int W, uint8_t* b
     quant_tables(quality, q);
     Writer w{buf};
     w.u8(0xFF), w.u8(0xD8);  // SOI
-    w.marker(0xE0, 14);      // JFIF 1.01, no units, density 1:1, no thumbnail
-    for (int c : {0x4A, 0x46, 0x49, 0x46, 0, 1, 1, 0, 0, 1, 0, 1, 0, 0}) w.u8(c);  // "JFIF\0" ...
+    app0(w, x.x_density, x.y_density);
     for (int t = 0; t < 2; ++t) {  // one DQT per table, 8-bit entries in zigzag order
         w.marker(0xDB, 65);
         w.u8(t);
@@ -207,6 +222,7 @@ int header(int quality, int sampling, const Huffman& h, int H, int W, uint8_t* b
         for (int i = 0; i < 16; ++i) w.u8(h.bits[t][i]);
         for (int i = 0; i < h.n[t]; ++i) w.u8(h.huffval[t][i]);
     }
+    if (x.restart) w.marker(0xDD, 2), w.u16(x.restart);  // DRI: MCUs per restart interval (jcmarker.c write_scan_header)
     w.marker(0xDA, 10);  // SOS: 3 components (DC / AC tables 0/0, 1/1, 1/1), Ss 0, Se 63, Ah Al 0
     for (int c : {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0}) w.u8(c);
     return (int)w.n;
@@ -241,13 +257,13 @@ uint64_t scan_partials(uint64_t n) {
 
 Scratch scratch_layout(int H, int W) { return scratch_layout(H, W, 2); }
 
-Scratch scratch_layout(int H, int W, int sampling) {
+Scratch scratch_layout(int H, int W, int sampling, int restart) {
     Scratch s{};
     s.n_mcus = mcus(H, W, sampling);
-    const uint64_t scan_bytes = (scan_bound_bits(H, W, sampling) + 7) / 8;
+    const uint64_t scan_bytes = (scan_bound_bits(H, W, sampling, restart) + 7) / 8;
     s.stuff_chunks = (scan_bytes + kStuffChunk - 1) / kStuffChunk;
     s.scan_words = s.stuff_chunks * (kStuffChunk / 4);  // (the 0xFF passes read whole chunks)
-    s.partial_elems = std::max(scan_partials(s.n_mcus), scan_partials(s.stuff_chunks));
+    s.partial_elems = std::max(scan_partials(s.n_mcus), scan_partials(s.stuff_chunks));  // (the intervals: no more than the MCUs)
     auto align = [](size_t v) { return (v + 15) & ~(size_t)15; };
     size_t at = 0;
     s.coefs = at, at = align(at + s.n_mcus * layout(sampling).nb * 64 * sizeof(int16_t));
@@ -256,24 +272,28 @@ Scratch scratch_layout(int H, int W, int sampling) {
     s.chunks = at, at = align(at + (s.stuff_chunks + 1) * sizeof(uint64_t));
     s.partial = at, at = align(at + s.partial_elems * sizeof(uint64_t));
     s.tables = at, at = align(at + sizeof(Tables));
+    s.intervals = at;
+    if (restart > 0) at = align(at + (restart_intervals(s.n_mcus, restart) + 2) * sizeof(uint64_t));
     s.total = at;
     return s;
 }
 
 bool rows_grid(int H, int W, int y0, int y1, RowsGrid* g) { return rows_grid(H, W, 2, y0, y1, g); }
 
-bool rows_grid(int H, int W, int sampling, int y0, int y1, RowsGrid* g) {
+bool rows_grid(int H, int W, int sampling, int y0, int y1, RowsGrid* g, int restart) {
     *g = RowsGrid{};
-    if (!valid_sampling(sampling)) return false;
+    if (!valid_sampling(sampling) || !valid_restart(restart)) return false;
     const Layout l = layout(sampling);
     if (H < 1 || W < 1 || H > kMaxDim || W > kMaxDim || y0 < 0 || y0 % l.mh || y1 <= y0 || y1 > H || (y1 % l.mh && y1 != H))
         return false;
     const uint64_t mx = (uint64_t)((W + l.mw - 1) / l.mw);
     g->m0 = (uint64_t)(y0 / l.mh) * mx;
     g->m1 = (uint64_t)((y1 + l.mh - 1) / l.mh) * mx;
-    const uint64_t bits = (g->m1 - g->m0) * l.nb * kBlockBoundBits;
+    uint64_t bits = (g->m1 - g->m0) * l.nb * kBlockBoundBits;
+    // (intervals that end in [m0, m1): one per `restart` MCUs, one more that began in a call before, and the frame's last)
+    if (restart > 0) bits += 23 * ((g->m1 - g->m0) / restart + 2);
     const uint64_t bytes = (bits + 7) / 8 + 1;  // [floor(before / 8), ceil(after / 8)): the carried partial byte, then the new ones
-    g->stuff_chunks = std::min((bytes + kStuffChunk - 1) / kStuffChunk, scratch_layout(H, W, sampling).stuff_chunks);
+    g->stuff_chunks = std::min((bytes + kStuffChunk - 1) / kStuffChunk, scratch_layout(H, W, sampling, restart).stuff_chunks);
     g->zero_words = (bits + 31) / 32;  // [ceil(before / 32), ceil(after / 32))
     return true;
 }
@@ -298,16 +318,15 @@ ProgGeom prog_geom(int H, int W, int sampling, int scan) {
     return ProgGeom{(uint64_t)bw * (uint64_t)bh, bw, bh};
 }
 
-int prog_frame_header(int quality, int sampling, int H, int W, uint8_t* buf, size_t cap) {
+int prog_frame_header(int quality, int sampling, int H, int W, uint8_t* buf, size_t cap, int x_density, int y_density) {
     if (!buf || !valid_sampling(sampling) || quality < 0 || quality > 100 || H < 1 || W < 1 || H > kMaxDim || W > kMaxDim ||
-        cap < (size_t)kProgFrameHeaderBytes)
+        cap < (size_t)kProgFrameHeaderBytes || !valid_density(x_density, y_density))
         return -1;
     uint8_t q[2][64];
     quant_tables(quality, q);
     Writer w{buf};
     w.u8(0xFF), w.u8(0xD8);
-    w.marker(0xE0, 14);
-    for (int c : {0x4A, 0x46, 0x49, 0x46, 0, 1, 1, 0, 0, 1, 0, 1, 0, 0}) w.u8(c);
+    app0(w, x_density, y_density);
     for (int t = 0; t < 2; ++t) {
         w.marker(0xDB, 65);
         w.u8(t);
@@ -432,16 +451,19 @@ int r2f_jpeg_header_ex(const r2f_jpeg_opts* o, int H, int W, uint8_t* buf, size_
     if (!o || !len || o->optimize || o->progressive) return R2F_EINVAL;  // (an optimized header needs the frame's statistics: r2f_jpeg_encode_ex)
     r2f::jpeg::Huffman h;
     r2f::jpeg::std_huffman(&h);
-    const int n = r2f::jpeg::header(o->quality, o->sampling, h, H, W, buf, cap);
+    const r2f::jpeg::HeaderExtras x{o->restart_interval, o->x_density, o->y_density};  // (header checks their ranges)
+    const int n = r2f::jpeg::header(o->quality, o->sampling, h, H, W, x, buf, cap);
     if (n < 0) return R2F_EINVAL;
     *len = (size_t)n;
     return R2F_OK;
 }
 
 uint64_t r2f_jpeg_bound_bytes_opts(const r2f_jpeg_opts* o, int H, int W) {
-    if (!o || (o->progressive != 0 && o->progressive != 1)) return 0;
-    if (!o->progressive) return r2f_jpeg_bound_bytes_ex(H, W, o->sampling);
+    if (!o || (o->progressive != 0 && o->progressive != 1) || !r2f::jpeg::valid_restart(o->restart_interval)) return 0;
+    if (o->progressive && o->restart_interval) return 0;  // (refused: r2f_jpeg_encode_ex)
+    if (!o->progressive && !o->restart_interval) return r2f_jpeg_bound_bytes_ex(H, W, o->sampling);
     if (H < 1 || W < 1 || H > r2f::jpeg::kMaxDim || W > r2f::jpeg::kMaxDim || !r2f::jpeg::valid_sampling(o->sampling)) return 0;
+    if (o->restart_interval) return r2f::jpeg::bound_bytes(H, W, o->sampling, o->restart_interval);
     return r2f::jpeg::prog_bound_bytes(H, W, o->sampling);
 }
 

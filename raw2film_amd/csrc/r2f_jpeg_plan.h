@@ -13,6 +13,9 @@ namespace jpeg {
 
 constexpr int kMaxDim = 65535;         // SOF0 stores H and W in 16 bits
 constexpr int kHeaderBytes = 623;      // SOI + APP0 + 2 DQT + SOF0 + 4 DHT + SOS: the same for every quality and size
+constexpr int kDriBytes = 6;           // the DRI segment a restart interval puts between the last DHT and SOS (FF DD 00 04 hi lo)
+constexpr int kMaxRestart = 65535;     // DRI stores the interval, in MCUs, in 16 bits
+constexpr int kMaxDensity = 65535;     // APP0 stores each density in 16 bits
 constexpr int kBlockBoundBits = 1660;  // most bits one block can take (DC: 11-bit code + 11 bits; 63 positions of <= 16 + 10 bits)
 constexpr int kStuffChunk = 4096;      // bytes of the packed scan per workgroup of the 0xFF count / scatter passes
 constexpr int kScanBlock = 1024;       // elements per workgroup of the device-side exclusive scan
@@ -57,6 +60,26 @@ inline uint64_t mcus(int H, int W, int sampling) {
 inline uint64_t scan_bound_bits(int H, int W, int sampling) { return mcus(H, W, sampling) * layout(sampling).nb * kBlockBoundBits; }
 inline uint64_t bound_bytes(int H, int W, int sampling) { return kHeaderBytes + 2 * ((scan_bound_bits(H, W, sampling) + 7) / 8) + 2; }
 
+// ---- Pillow's restart_marker_blocks / restart_marker_rows, resolved to `restart` MCUs per interval (0: none, the functions
+// above).  Every interval starts with the DC predictors at 0 and ends on a byte boundary: its last byte is padded with 1-bits,
+// and every interval but the last is followed by RSTn (FF D0 + n, n = the interval's index mod 8), which is not stuffed.
+inline bool valid_restart(int restart) { return restart >= 0 && restart <= kMaxRestart; }
+inline uint64_t restart_intervals(uint64_t n_mcus, int restart) { return restart > 0 ? (n_mcus + restart - 1) / restart : 0; }
+// Most bits of the scan with its padding and markers in place, before byte stuffing: per interval at most 7 padding bits, and
+// 16 marker bits behind all but the last.
+inline uint64_t scan_bound_bits(int H, int W, int sampling, int restart) {
+    const uint64_t k = restart_intervals(mcus(H, W, sampling), restart);
+    return scan_bound_bits(H, W, sampling) + (k ? 23 * k - 16 : 0);
+}
+// Largest file: the DRI segment, and per interval 4 bytes more than the scan's own bytes -- the marker (2), the byte its padding
+// completes (1) and the 0x00 stuffed behind that byte when it comes out as 0xFF (1).  With B = scan_bound_bits without restarts
+// and k intervals: the data bytes number at most (B + 7 k) / 8, each may be stuffed, and 2 (k - 1) marker bytes are not, so the
+// scan takes at most 2 (B + 7 k) / 8 + 2 (k - 1) <= 2 ceil(B / 8) + 4 k bytes.
+inline uint64_t bound_bytes(int H, int W, int sampling, int restart) {
+    const uint64_t k = restart_intervals(mcus(H, W, sampling), restart);
+    return bound_bytes(H, W, sampling) + (k ? kDriBytes + 4 * k : 0);
+}
+
 // Huffman tables as DHT holds them, in DHT order DC0, AC0, DC1, AC1: code counts per length 1..16, then n symbols.
 struct Huffman {
     uint8_t bits[4][16];
@@ -77,6 +100,13 @@ void make_tables(int quality, const Huffman& h, Tables* t);
 // The header with the sampling's SOF0 and DHT from `h`; returns its length (<= kHeaderBytes: an optimized table holds at most
 // 12 DC or 162 AC symbols), or -1 for bad arguments or a cap below the length.
 int header(int quality, int sampling, const Huffman& h, int H, int W, uint8_t* buf, size_t cap);
+// The same with a restart interval (> 0: the DRI segment, kDriBytes more) and the JFIF density (both > 0: units 1, dots per
+// inch; else no units, 1 : 1 as above).
+struct HeaderExtras {
+    int restart = 0;
+    int x_density = 0, y_density = 0;
+};
+int header(int quality, int sampling, const Huffman& h, int H, int W, const HeaderExtras& x, uint8_t* buf, size_t cap);
 // The scan's exact bit count (before padding) for symbol counts freq[DC0, AC0, DC1, AC1][256] coded with `h`; UINT64_MAX when a
 // counted symbol has no code.
 uint64_t scan_bits(const uint64_t freq[4][256], const Huffman& h);
@@ -89,11 +119,14 @@ struct Scratch {
     size_t chunks;   // uint64 [stuff_chunks + 1]: 0xFF bytes per kStuffChunk, then their exclusive scan
     size_t partial;  // uint64 [scan block sums of both scans]
     size_t tables;   // Tables
+    size_t intervals;  // uint64 [restart intervals + 2]: each interval's bits, padding and marker included, then their scan (restart > 0)
     size_t total;
     uint64_t n_mcus, scan_words, stuff_chunks, partial_elems;
 };
 Scratch scratch_layout(int H, int W);
-Scratch scratch_layout(int H, int W, int sampling);  // (coefs: int16 [mcus][nb][64])
+// (coefs: int16 [mcus][nb][64]; restart > 0: the scan's words and chunks are sized for its padding and markers too, and
+// `intervals` follows the other regions; restart = 0 gives the layout it always gave)
+Scratch scratch_layout(int H, int W, int sampling, int restart = 0);
 // Workgroup sums the scan of n elements needs (recursively, every level).
 uint64_t scan_partials(uint64_t n);
 
@@ -108,7 +141,8 @@ struct RowsGrid {
 // y0 a multiple of 16, y0 < y1 <= H, y1 a multiple of 16 or H; returns false (grid zeroed) otherwise.
 bool rows_grid(int H, int W, int y0, int y1, RowsGrid* g);
 // The same for a sampling: y0 a multiple of the MCU height (16 or 8), y1 one too or H.
-bool rows_grid(int H, int W, int sampling, int y0, int y1, RowsGrid* g);
+// restart > 0: the padding and markers of the intervals that end in the call counted in.
+bool rows_grid(int H, int W, int sampling, int y0, int y1, RowsGrid* g, int restart = 0);
 
 // ---- Pillow's progressive=True (libjpeg-turbo jcphuff.c over jpeg_simple_progression's ten scans; optimize_coding forced, so
 // every scan but the DC refinement carries its own optimized tables).  The DC scans walk the MCU grid's blocks, dummies included;
@@ -152,8 +186,8 @@ struct ProgTables {
     uint8_t huffval[2][256];
     int n[2];
 };
-// SOI .. SOF2; returns its length (kProgFrameHeaderBytes) or -1 for bad arguments or a cap below it.
-int prog_frame_header(int quality, int sampling, int H, int W, uint8_t* buf, size_t cap);
+// SOI .. SOF2 (densities as in HeaderExtras); returns its length (kProgFrameHeaderBytes) or -1 for bad arguments or a cap below it.
+int prog_frame_header(int quality, int sampling, int H, int W, uint8_t* buf, size_t cap, int x_density = 0, int y_density = 0);
 // The scan's DHT segments (none for the DC refinement) and SOS; returns the length or -1.
 int prog_scan_header(int scan, const ProgTables& t, uint8_t* buf, size_t cap);
 // The scan's exact bits before padding: freq[slot][256] coded with `t`, plus the raw bits no symbol implies (`extra`: the

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import inspect
 import math
+import operator
 import random
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -30,7 +31,7 @@ import numpy as np
 from . import _lib, filmstock, geometry, stencils
 from .context import LOG_EPS, LUT3D_SCALE, HipContext
 from . import tiff
-from .jpeg_stream import JpegBandSink, JpegStaging, app1_segment, deliver
+from .jpeg_stream import ICC_OVERHEAD, MARKER_MAX, XMP_NAMESPACE, JpegBandSink, JpegStaging, deliver, metadata_segments
 from .results import ResultBuffers
 
 REC709_TO_XYZ = np.array(  # data.py:128-135
@@ -731,17 +732,24 @@ class HipProcessor:
         return None if out is None else self._download(out)  # DEVICE -> HOST, the reference's read_texture/map_sync
 
     # ------------------------------------------------------------------ JPEG export (gui.py:2338-2341)
-    def encode_jpeg(self, image, quality=100, *, subsampling=-1, optimize=False, exif=b"", progressive=False) -> bytes:
-        """`Image.fromarray(image).save(f, "JPEG", quality=quality, subsampling=subsampling, optimize=optimize, exif=exif)` on the
-        device: the same bytes Pillow writes (JFIF, standard or optimized Huffman tables, no ICC).  image: uint8 (H, W, 3), a NumPy
+    def encode_jpeg(self, image, quality=100, *, subsampling=-1, optimize=False, exif=b"", progressive=False, icc_profile=b"",
+                    xmp=b"", comment=b"", dpi=(0, 0), restart_marker_blocks=0, restart_marker_rows=0) -> bytes:
+        """`Image.fromarray(image).save(f, "JPEG", quality=quality, subsampling=subsampling, optimize=optimize, exif=exif, ...)`
+        on the device: the same bytes Pillow writes (JFIF, standard or optimized Huffman tables).  image: uint8 (H, W, 3), a NumPy
         array or a torch tensor (a CUDA tensor may be a row-strided view); quality: an int 0 .. 100 like the reference's slider
         (gui.py:2532-2588).  subsampling: -1 (libjpeg's default, 4:2:0), 0 / "4:4:4", 1 / "4:2:2", 2 / "4:2:0".  optimize: truthy
         for per-image Huffman tables (the call then waits once for the frame's symbol counts).  exif: bytes or a PIL.Image.Exif,
         written as an APP1 segment after the JFIF one (empty: none).  progressive: True for Pillow's progressive=True (SOF2, libjpeg's
-        ten scans, each with its own optimized tables, so optimize makes no difference); False, 0 or 1 -- anything else raises."""
+        ten scans, each with its own optimized tables, so optimize makes no difference); False, 0 or 1 -- anything else raises.
+        icc_profile, xmp (bytes), comment (bytes, or str written as UTF-8): the APP2 chunks, the APP1 XMP segment and the COM
+        segment Pillow writes for them, in its order behind the EXIF.  dpi: (x, y), rounded like Pillow's into APP0's density in
+        dots per inch when both are positive.  restart_marker_blocks: MCUs per restart interval, 0 .. 65535;
+        restart_marker_rows: MCU rows per interval (it wins over blocks; the interval is clamped to 65535 MCUs).  A restart
+        interval with progressive=True raises ValueError: baseline only."""
         q = _jpeg_quality(quality)
         opts = _jpeg_options(subsampling, optimize, exif)
         prog = _jpeg_progressive(progressive)
+        extras = _jpeg_extras(icc_profile, xmp, comment, dpi, restart_marker_blocks, restart_marker_rows, prog)
         torch = self._torch
         if isinstance(image, np.ndarray):
             _check_jpeg_image(image.dtype == np.uint8, image.shape, image.dtype)
@@ -752,10 +760,11 @@ class HipProcessor:
                 image = image.to(self.device)
         else:
             raise ValueError(f"encode_jpeg: expected a uint8 (H, W, 3) NumPy array or torch tensor, got {type(image).__name__}")
-        return self._encode_device(image, q, *opts, progressive=prog)
+        return self._encode_device(image, q, *opts, progressive=prog, extras=extras)
 
     def process_jpeg(self, src, negative_film, grain_size, grain_sigma, quality=100, stream=False, file=None, *, subsampling=-1,
-                     optimize=False, exif=b"", progressive=False, **settings):
+                     optimize=False, exif=b"", progressive=False, icc_profile=b"", xmp=b"", comment=b"", dpi=(0, 0),
+                     restart_marker_blocks=0, restart_marker_rows=0, **settings):
         """The export of one frame (gui.py:2338-2341): process()'s render with the same keywords -- the pixels process() returns
         for them -- encoded on the device as encode_jpeg does; only the file comes back to the host.  The frame a preview keeps on
         the device (cache=True) is left alone: the next preview re-render uploads nothing.  The export always extracts and uploads
@@ -769,40 +778,45 @@ class HipProcessor:
         their count.  Without it the call returns the bytes.
         subsampling, optimize, exif: Pillow's, as in encode_jpeg.  optimize=True needs the whole frame's symbol counts before the
         first scan byte: with stream=True it takes the one-piece path, and `stream_rejected` says so.  progressive (as in
-        encode_jpeg) needs the whole frame for every scan: the same."""
+        encode_jpeg) needs the whole frame for every scan: the same.  icc_profile, xmp, comment, dpi, restart_marker_blocks,
+        restart_marker_rows: as in encode_jpeg; they stream (the segments are written ahead of the first scan byte, and a
+        restart interval may straddle bands)."""
         q = _jpeg_quality(quality)
         opts = _jpeg_options(subsampling, optimize, exif)
         prog = _jpeg_progressive(progressive)
+        extras = _jpeg_extras(icc_profile, xmp, comment, dpi, restart_marker_blocks, restart_marker_rows, prog)
         exposure_on_device(settings.get("exposure"))
         self.exposure_rejected = None
         settings, _, payload = self._export_frame("process_jpeg", src, negative_film, grain_size, grain_sigma, settings, stream,
                                                   (_PROGRESSIVE_REJECTED if prog else None, _OPTIMIZE_REJECTED if opts[1] else None))
         if stream and self.stream_rejected is None:
-            res = self._stream_jpeg(payload, negative_film, grain_size, grain_sigma, "cpu", q, file, settings, opts)
+            res = self._stream_jpeg(payload, negative_film, grain_size, grain_sigma, "cpu", q, file, settings, opts, extras)
             if res is not None:
                 return res
         out_u8 = self._render_export(payload, negative_film, grain_size, grain_sigma, "cpu", settings)
-        return deliver(self._encode_device(out_u8, q, *opts, progressive=prog), file)
+        return deliver(self._encode_device(out_u8, q, *opts, progressive=prog, extras=extras), file)
 
     def process_preloaded_jpeg(self, cpu_payload, negative_film, grain_size, grain_sigma, quality=100, final_scaling="gpu",
                                stream=False, file=None, *, subsampling=-1, optimize=False, exif=b"", progressive=False,
+                               icc_profile=b"", xmp=b"", comment=b"", dpi=(0, 0), restart_marker_blocks=0, restart_marker_rows=0,
                                **settings):
         """The batch export on the two-phase API: process_preloaded's render of a phase-1 payload, encoded on the device like
         process_jpeg.  The processor's device frame (prepare_gpu_textures') is left alone.  stream=True: the file is Pillow's of
         process_preloaded(cpu_payload, final_scaling=..., ...)'s pixels, and a payload process_preloaded streams in row bands is
         encoded band by band as in process_jpeg (else `stream_rejected` says why not).  file, subsampling, optimize, exif,
-        progressive: see process_jpeg."""
+        progressive, icc_profile, xmp, comment, dpi, restart_marker_blocks, restart_marker_rows: see process_jpeg."""
         q = _jpeg_quality(quality)
         opts = _jpeg_options(subsampling, optimize, exif)
         prog = _jpeg_progressive(progressive)
+        extras = _jpeg_extras(icc_profile, xmp, comment, dpi, restart_marker_blocks, restart_marker_rows, prog)
         self.exposure_rejected = None
         if self._export_preloaded("process_preloaded_jpeg", settings, stream,
                                   (_PROGRESSIVE_REJECTED if prog else None, _OPTIMIZE_REJECTED if opts[1] else None)):
-            res = self._stream_jpeg(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, q, file, settings, opts)
+            res = self._stream_jpeg(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, q, file, settings, opts, extras)
             if res is not None:
                 return res
         out_u8 = self._render_export(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, settings)
-        return deliver(self._encode_device(out_u8, q, *opts, progressive=prog), file)
+        return deliver(self._encode_device(out_u8, q, *opts, progressive=prog, extras=extras), file)
 
     def _export_frame(self, what, src, negative_film, grain_size, grain_sigma, settings, stream, early=()):
         """The prologue of an export of `src` (process_jpeg, process_tiff; `what` names it in messages): no textures, then
@@ -896,14 +910,17 @@ class HipProcessor:
 
         return self._stream(payload, negative_film, grain_size, grain_sigma, final_scaling, settings, make_sink)
 
-    def _encode_device(self, image_u8, quality, subsampling=2, optimize=False, exif=b"", progressive=False):
+    def _encode_device(self, image_u8, quality, subsampling=2, optimize=False, exif=b"", progressive=False, extras=None):
         """A uint8 (H, W, 3) device frame -> the JPEG file's bytes.  The encoder runs on the current stream; reading its 8-byte
         length back is the one synchronisation (optimize and progressive add one for the symbol counts), then only the file crosses PCIe, into a
         pinned buffer this processor keeps (grown to the largest file so far; a pageable download of a 47 MB file cost up to 34 ms)
-        and from there into the bytes object -- with the EXIF APP1 spliced in on the way, in the same single copy."""
+        and from there into the bytes object -- with the EXIF APP1 and the other segments of `extras` (_jpeg_extras) spliced in
+        on the way, in the same single copy."""
         if image_u8.stride(2) != 1 or image_u8.stride(1) != 3 or image_u8.stride(0) < 3 * image_u8.shape[1]:
             image_u8 = image_u8.contiguous()  # (a row-strided view is encoded in place)
-        out, length = self.ctx.jpeg_encode(image_u8, quality, subsampling, optimize, progressive)
+        extras = extras or _NO_EXTRAS
+        out, length = self.ctx.jpeg_encode(image_u8, quality, subsampling, optimize, progressive,
+                                           extras.restart(int(image_u8.shape[1]), subsampling), extras.density)
         n = int(length.item())
         if n <= 0:
             raise RuntimeError("r2f_jpeg_encode reported an empty file")
@@ -911,9 +928,10 @@ class HipProcessor:
         if host is None or host.numel() < n:
             host = self._jpeg_host = self._torch.empty(max(n, 1 << 20), dtype=self._torch.uint8, pin_memory=True)
         host[:n].copy_(out[:n])  # (synchronous: the bytes are there when it returns)
-        if exif:
+        segments = extras.segments(exif)
+        if segments:
             data = host[:n].numpy().data
-            return b"".join((data[:20], app1_segment(exif), data[20:]))
+            return b"".join((data[:20], segments, data[20:]))
         return host[:n].numpy().tobytes()
 
     def _process_streamed(self, src, negative_film, grain_size, grain_sigma, load, settings):
@@ -1000,7 +1018,8 @@ class HipProcessor:
         self.ctx.write_frame_params(p)     # (and the exposure-range record starts empty)
         return host, p, bounds, bufs, ha, ma
 
-    def _stream_jpeg(self, payload, negative_film, grain_size, grain_sigma, final_scaling, quality, file, settings, opts=(2, False, b"")):
+    def _stream_jpeg(self, payload, negative_film, grain_size, grain_sigma, final_scaling, quality, file, settings, opts=(2, False, b""),
+                     extras=None):
         """_stream_payload with a JPEG sink: the same bands and stage calls, no pixels downloaded; each band's finished MCU rows
         are encoded behind its tail and the file's final bytes go down while later bands arrive (jpeg_stream.py).  Returns the
         file's bytes (file=None) or their count, or None (with `stream_rejected` saying why) when the payload does not qualify."""
@@ -1010,7 +1029,9 @@ class HipProcessor:
                 staging = self._jpeg_staging = JpegStaging(self._torch, self.device)
             _, down = self._copy_streams()
             subsampling, _, exif = opts  # (optimize never streams)
-            sink = JpegBandSink(staging, self.ctx, out_u8, quality, bounds, down, file, subsampling, exif)
+            x = extras or _NO_EXTRAS
+            sink = JpegBandSink(staging, self.ctx, out_u8, quality, bounds, down, file, subsampling, segments=x.segments(exif),
+                                restart=x.restart(int(out_u8.shape[1]), subsampling), density=x.density)
             return sink, sink.band
 
         # (a JPEG is 8 bits per sample whatever `output_bits` the caller's settings carry)
@@ -1470,7 +1491,7 @@ def _jpeg_quality(quality) -> int:
 
 
 _SUBSAMPLINGS = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}
-_EXIF_MAX = 65533  # a marker segment's payload (Pillow's MAX_BYTES_IN_MARKER)
+_EXIF_MAX = MARKER_MAX  # a marker segment's payload (Pillow's MAX_BYTES_IN_MARKER)
 _OPTIMIZE_REJECTED = "optimize=True: its Huffman tables need the whole frame's statistics before the first scan byte"
 _PROGRESSIVE_REJECTED = "progressive=True: every one of its scans spans the whole frame"
 
@@ -1504,6 +1525,77 @@ def _jpeg_exif(exif) -> bytes:
 def _jpeg_options(subsampling, optimize, exif):
     """(sampling 0 / 1 / 2, optimize, exif bytes) of an export's options, checked before any work starts."""
     return _jpeg_subsampling(subsampling), bool(optimize), _jpeg_exif(exif)
+
+
+class _JpegExtras(NamedTuple):
+    """The checked options of an export that need no table or kernel of their own (_jpeg_extras)."""
+    icc_profile: bytes = b""
+    xmp: bytes = b""
+    comment: bytes = b""
+    density: tuple = (0, 0)  # APP0's (x, y) in dots per inch; (0, 0): no units
+    blocks: int = 0          # restart_marker_blocks
+    rows: int = 0            # restart_marker_rows
+
+    def restart(self, W: int, sampling: int) -> int:
+        """MCUs per restart interval for a frame W pixels wide (0: none): `rows` MCU rows, clamped to 65535 as libjpeg does,
+        else `blocks`."""
+        if self.rows > 0:
+            return min(self.rows * -(-W // (8 if sampling == 0 else 16)), 65535)
+        return self.blocks
+
+    def segments(self, exif: bytes) -> bytes:
+        return metadata_segments(exif, self.xmp, self.icc_profile, self.comment)
+
+
+_NO_EXTRAS = _JpegExtras()
+
+
+def _jpeg_bytes(name, value, limit, what) -> bytes:
+    if not isinstance(value, (bytes, bytearray, memoryview)):
+        raise ValueError(f"JPEG {name} must be bytes, got {type(value).__name__}")
+    data = bytes(value)
+    if len(data) > limit:
+        raise ValueError(f"JPEG {name} is too long: {len(data)} bytes ({what} at most {limit})")
+    return data
+
+
+def _jpeg_restart(name, value, limit) -> int:
+    try:
+        n = operator.index(value)
+    except TypeError:
+        raise ValueError(f"JPEG {name} must be an integer, got {value!r}") from None
+    if n < 0 or (limit is not None and n > limit):
+        raise ValueError(f"JPEG {name} must be {'in 0 .. ' + str(limit) if limit is not None else 'at least 0'}, got {n}")
+    return n
+
+
+def _jpeg_extras(icc_profile, xmp, comment, dpi, restart_marker_blocks, restart_marker_rows, progressive=False) -> _JpegExtras:
+    """Pillow's icc_profile, xmp, comment, dpi, restart_marker_blocks and restart_marker_rows options, checked before any work
+    starts.  Where Pillow wraps (blocks modulo 65536, a density modulo 65536), ignores (negative rows or dpi) or fails late (a
+    segment too long for its marker), this raises ValueError naming the option."""
+    icc = _jpeg_bytes("icc_profile", icc_profile, 255 * (MARKER_MAX - ICC_OVERHEAD), "255 APP2 chunks hold")
+    x = _jpeg_bytes("xmp", xmp, MARKER_MAX - len(XMP_NAMESPACE), "its APP1 segment holds")
+    if isinstance(comment, str):
+        comment = comment.encode("utf-8")  # (as Pillow writes a str)
+    elif not isinstance(comment, bytes):
+        raise ValueError(f"JPEG comment must be bytes or str, got {type(comment).__name__}")
+    if len(comment) > MARKER_MAX:
+        raise ValueError(f"JPEG comment is too long: {len(comment)} bytes (a JPEG marker holds at most {MARKER_MAX})")
+    try:
+        density = tuple(int(round(v)) for v in dpi)
+        ok = len(density) == 2 and all(0 <= v <= 65535 for v in density)
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"JPEG dpi must be two numbers that round to 0 .. 65535, got {dpi!r}")
+    if not all(density):
+        density = (0, 0)  # (Pillow sets the units only when both are positive)
+    blocks = _jpeg_restart("restart_marker_blocks", restart_marker_blocks, 65535)
+    rows = _jpeg_restart("restart_marker_rows", restart_marker_rows, None)
+    if progressive and (blocks or rows):
+        raise ValueError("JPEG progressive=True with restart_marker_blocks / restart_marker_rows is not supported: restart "
+                         "intervals are written in baseline files only")
+    return _JpegExtras(icc, x, comment, density, blocks, rows)
 
 
 def _jpeg_progressive(progressive) -> bool:

@@ -66,6 +66,31 @@ def app1_segment(exif: bytes) -> bytes:
     return b"\xff\xe1" + (len(exif) + 2).to_bytes(2, "big") + exif if exif else b""
 
 
+MARKER_MAX = 65533  # a marker segment's payload (Pillow's MAX_BYTES_IN_MARKER)
+XMP_NAMESPACE = b"http://ns.adobe.com/xap/1.0/\x00"
+ICC_OVERHEAD = 14   # b"ICC_PROFILE\0", the chunk's number from 1, the chunk count
+
+
+def _segment(marker: int, payload: bytes) -> bytes:
+    return bytes((0xFF, marker)) + (len(payload) + 2).to_bytes(2, "big") + payload
+
+
+def metadata_segments(exif: bytes = b"", xmp: bytes = b"", icc_profile: bytes = b"", comment: bytes = b"") -> bytes:
+    """Every variable-length segment of an export in the order Pillow writes them, to go right after the file's first 20 bytes
+    (SOI + APP0): APP1 Exif, APP1 XMP (its namespace first), the profile in APP2 chunks of at most 65533 - 14 bytes, COM.  Each
+    empty one is left out; the lengths were checked with the options (hip_processor._jpeg_metadata)."""
+    out = [app1_segment(exif)]
+    if xmp:
+        out.append(_segment(0xE1, XMP_NAMESPACE + xmp))
+    step = MARKER_MAX - ICC_OVERHEAD
+    chunks = [icc_profile[i:i + step] for i in range(0, len(icc_profile), step)]
+    for i, chunk in enumerate(chunks):
+        out.append(_segment(0xE2, b"ICC_PROFILE\0" + bytes((i + 1, len(chunks))) + chunk))
+    if comment:
+        out.append(_segment(0xFE, comment))
+    return b"".join(out)
+
+
 def open_output(file):
     """(binary file object, whether this call opened it) for a path or a file object; (BytesIO, False) for None."""
     if file is None:
@@ -80,14 +105,17 @@ def open_output(file):
 class JpegBandSink:
     """One streamed export: band(b) after band b's tail (on the launching thread), then finish() -> the file's bytes (file=None)
     or its length, or abandon() on an error with the device drained.  subsampling: 0 4:4:4, 1 4:2:2, 2 4:2:0; exif: the bytes of
-    an APP1 segment the writer puts after the file's first 20 bytes (b"": none)."""
+    an APP1 segment the writer puts after the file's first 20 bytes (b"": none), or with `segments` every such segment ready
+    made (metadata_segments); restart, density: r2f_jpeg_opts' restart_interval and (x_density, y_density)."""
 
-    def __init__(self, staging, ctx, image_u8, quality, bounds, down, file=None, subsampling=2, exif=b""):
+    def __init__(self, staging, ctx, image_u8, quality, bounds, down, file=None, subsampling=2, exif=b"", *, segments=None,
+                 restart=0, density=(0, 0)):
         torch = ctx._torch
         H, W = int(image_u8.shape[0]), int(image_u8.shape[1])
         self._torch, self._st, self._image, self._down = torch, staging, image_u8, down
         self.steps = jpeg_row_steps(bounds, H, 16 if subsampling == 2 else 8)
-        self._app1 = app1_segment(exif)  # (written by the first write: every first chunk holds the whole header)
+        # (written by the first write, ahead of every scan byte: every first chunk holds the whole header)
+        self._app1 = app1_segment(exif) if segments is None else segments
         self._app1_pending = bool(self._app1)
         self._lens = staging.lengths(len(self.steps))
         self._lens_np = self._lens.numpy()
@@ -99,7 +127,7 @@ class JpegBandSink:
         self._compute = torch.cuda.current_stream(ctx.device)
         self._snap = torch.empty(len(self.steps), dtype=torch.int64, device=ctx.device)  # the word after each band's encode
         try:
-            self.enc = ctx.jpeg_rows(H, W, quality, subsampling)  # (header and carry written on the launching stream)
+            self.enc = ctx.jpeg_rows(H, W, quality, subsampling, restart, density)  # (header and carry written on the launching stream)
         except BaseException:
             self._close_file()
             raise
