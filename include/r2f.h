@@ -306,6 +306,83 @@ R2F_API int r2f_resize_area(r2f_ctx* ctx, const void* in, int in_layout, int H, 
 R2F_API int r2f_warp_affine(r2f_ctx* ctx, const void* in, int in_layout, int H, int W, const double* m_dst_to_src, const r2f_planes* dst,
                     int out_h, int out_w, int oy, int ox, void* stream);
 
+/* Pre-path lens correction from numbers the caller supplies: what effects.lens_correction (effects.py:22-43) does with the values
+ * lensfun looked up -- a radial coordinate map (Modifier.apply_geometry_distortion), an 8 x 8 LANCZOS4 gather through it
+ * (lensfunpy.util.remap -> cv2.remap(..., INTER_LANCZOS4), constant border 0), a clamp at 0 and a radial vignetting gain
+ * (apply_color_modification).  The database lookup itself, TCA and an adapter from lensfunpy objects are not here.
+ *
+ * The definition.  Take output pixel (X, Y) of the corrected full frame.
+ *   - The host rounds these constants from double: cx, cy, q = 1/(norm_radius_px*scale), inv_scale = 1/scale, c0,
+ *     qv = 1/norm_radius_px.
+ *   - dx = X - cx, dy = Y - cy.
+ *   - u = dx*q, v = dy*q.
+ *   - r2 = u*u + v*v.
+ *   - The model factor f:
+ *       poly3:  f = c0 + k1*r2, with c0 = 1 - k1.
+ *       poly5:  f = 1 + r2*(k1 + k2*r2).
+ *       ptlens: r = sqrt(r2), f = c0 + r*(c + r*(b + r*a)), with c0 = 1 - a - b - c.
+ *       none:   f = 1.
+ *   - g = f*inv_scale.
+ *   - sx = cx + dx*g, sy = cy + dy*g.
+ * Every operation is one correctly rounded fp32 operation, with no contraction.
+ * Sampling restates cv2.remap(..., INTER_LANCZOS4) with constant border 0 (OpenCV's imgwarp.cpp, INTER_BITS = 5):
+ *   - qx = rint(sx*32), ix = qx >> 5, fx = qx & 31.  The same for y.
+ *   - Taps are rows iy-3 .. iy+4 and columns ix-3 .. ix+4.
+ *   - Tap weight is fl(wy[fy][k] * wx[fx][j]).  The table is 32 x 8 float: interpolateLanczos4(p/32) (r2f_lens_phase_table).
+ *   - A tap outside the frame contributes 0 (its product with the sample 0.0f is added like any other).
+ *   - The sum runs per row left to right, and rows top to bottom, each starting from the first product.
+ *   - Then o = max(sum, 0), evaluated as (sum < 0 ? 0 : sum).
+ * With vignetting:
+ *   - rv2 = (dx*qv)^2 + (dy*qv)^2.
+ *   - o = o / (1 + rv2*(v1 + rv2*(v2 + rv2*v3))), an IEEE division.
+ * Edge cases:
+ *   - A coordinate that is NaN, infinite, or beyond the frame by more than the tap reach yields 0 without indexing anything; that
+ *     decision is made in floats (on rint(sx*32), rint(sy*32)), before any conversion to int.
+ *   - One coordinate serves all three channels (upstream never calls the TCA path).
+ *   - A fourth input channel is ignored.
+ * cx = (W - 1)/2 + center_x*norm_radius_px, cy = (H - 1)/2 + center_y*norm_radius_px.
+ * Parity with real OpenCV / lensfun is UNPINNED: neither is installed on any machine this project sees; what the tests pin is this
+ * definition (tests/lens_model.py restates it in NumPy). */
+enum { R2F_LENS_NONE = 0, R2F_LENS_POLY3 = 1, R2F_LENS_POLY5 = 2, R2F_LENS_PTLENS = 3 };
+/* What the caller knows of a lens (raw2film_amd.lens.LensProfile): n_coef coefficients of `model` (0; k1; k1, k2; a, b, c), lensfun's
+ * "pa" vignetting terms when has_vignetting, the optical centre's offset in units of r, a scale > 0 (or auto_scale != 0), and the
+ * pixel distance at which r = 1 (0: half the diagonal, hypot(W - 1, H - 1)/2; 1 for a 1 x 1 frame). */
+typedef struct r2f_lens_profile {
+    int32_t model, n_coef;
+    double coef[3];
+    int32_t has_vignetting, auto_scale;
+    double vignetting[3];
+    double center[2];
+    double scale;
+    double norm_radius_px;
+} r2f_lens_profile;
+/* The fp32 constants of the definition above for one frame size; `scale` is the scale they were made for (the resolved one with
+ * auto_scale), in double. */
+typedef struct r2f_lens_params {
+    int32_t model, vignetting;
+    float cx, cy, q, inv_scale, c0;
+    float k[3];  /* poly3: k1; poly5: k1, k2; ptlens: a, b, c */
+    float qv;
+    float v[3];
+    double scale;
+} r2f_lens_params;
+/* Host planner (raw2film_amd/csrc/r2f_lens_plan.cpp; no GPU, no context): profile + (H, W) -> params.  R2F_EINVAL for an unknown
+ * model, a coefficient count that is not the model's, a non-finite number, scale <= 0, a negative norm_radius_px, a frame size
+ * below 1 x 1, or constants that do not fit a finite float.  auto_scale: the scale at which the furthest-reaching of eight probes
+ * -- the four corners and the four edge midpoints of the output frame -- lands exactly on the frame boundary [0, W - 1] x
+ * [0, H - 1], found by bisection in double over [1/16, 16] and rounded to the side on which every probe is inside; R2F_EINVAL when
+ * that range holds no such scale.  A frame none of whose probes can leave (1 x 1) takes scale 1. */
+R2F_API int r2f_lens_plan(const r2f_lens_profile* profile, int H, int W, r2f_lens_params* out);
+/* The 32 x 8 phase table of the sampling: row p = interpolateLanczos4(p/32).  No GPU, no context. */
+R2F_API int r2f_lens_phase_table(float* table_32x8);
+/* The correction itself.  `in` is the whole H x W frame (any in_layout); `dst` receives the window [oy, oy + out_h) x
+ * [ox, ox + out_w) of the corrected frame as out_h x out_w planes -- the shape of r2f_warp_affine.  The window may reach past the
+ * frame: out there the map is evaluated like anywhere else.  Lanes along x, one per output pixel of a row; the phase table sits in
+ * LDS, and so does the box of source texels a block's taps touch when it fits (a block whose box does not fit gathers from global
+ * memory, with the same sums in the same order: results do not depend on it). */
+R2F_API int r2f_lens_correct(r2f_ctx* ctx, const void* in, int in_layout, int H, int W, const r2f_lens_params* params,
+                     const r2f_planes* dst, int out_h, int out_w, int oy, int ox, void* stream);
+
 /* Post-path up-scale of the rendered uint8 frame: utils.resolution_scaling's cv.resize(image, dsize,
  * interpolation=cv.INTER_LANCZOS4) branch (utils.py:237-242), the way back from the `max_scale` pipeline resolution to the
  * requested one (cpu_processor.py:128-134, 411-412).  src/dst: uint8 (H, W, 3) / (out_h, out_w, 3) on the device.

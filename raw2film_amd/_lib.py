@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libr2f_hip.so")
 
 # enums of include/r2f.h
 LAYOUT_HWC3, LAYOUT_HWC4, LAYOUT_CHW = 0, 1, 2
+LENS_NONE, LENS_POLY3, LENS_POLY5, LENS_PTLENS = 0, 1, 2, 3
 KERNEL_HALATION, KERNEL_MTF, KERNEL_GRAIN = 0, 1, 2
 F_MATRIX, F_HALATION, F_MTF, F_GRAIN, F_GRAIN_MONO, F_BURN, F_IDENTITY_DONE, F_FRAME_RESIDENT = 1, 2, 4, 8, 16, 32, 64, 128
 F_TRACK_RANGE, F_RANGE_VALID = 256, 512
@@ -65,6 +66,18 @@ class JpegOpts(C.Structure):  # r2f_jpeg_opts (sampling: 0 4:4:4, 1 4:2:2, 2 4:2
 class TiffPlan(C.Structure):  # r2f_tiff_plan
     _fields_ = [("header_bytes", C.c_uint64), ("file_bytes", C.c_uint64), ("row_bytes", C.c_uint64), ("rows_per_strip", C.c_uint32),
                 ("strips", C.c_uint32)]
+
+
+class LensProfile(C.Structure):  # r2f_lens_profile (raw2film_amd.lens.LensProfile fills it)
+    _fields_ = [("model", C.c_int32), ("n_coef", C.c_int32), ("coef", C.c_double * 3), ("has_vignetting", C.c_int32),
+                ("auto_scale", C.c_int32), ("vignetting", C.c_double * 3), ("center", C.c_double * 2), ("scale", C.c_double),
+                ("norm_radius_px", C.c_double)]
+
+
+class LensParams(C.Structure):  # r2f_lens_params: the fp32 constants of one frame size
+    _fields_ = [("model", C.c_int32), ("vignetting", C.c_int32), ("cx", C.c_float), ("cy", C.c_float), ("q", C.c_float),
+                ("inv_scale", C.c_float), ("c0", C.c_float), ("k", C.c_float * 3), ("qv", C.c_float), ("v", C.c_float * 3),
+                ("scale", C.c_double)]
 
 
 _P = C.POINTER
@@ -140,6 +153,12 @@ _SIGNATURES = {
     "r2f_warp_affine": (
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, _P(Planes), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    ),
+    "r2f_lens_plan": (C.c_int, [_P(LensProfile), C.c_int, C.c_int, _P(LensParams)]),
+    "r2f_lens_phase_table": (C.c_int, [C.c_void_p]),
+    "r2f_lens_correct": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(LensParams), _P(Planes), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
     ),
     "r2f_resize_lanczos4_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "r2f_lanczos4_table": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -541,6 +541,23 @@ class HipContext:
                                               self._stream()))
         return out
 
+    def lens_correct(self, image, profile_or_params, window=None, layout=None):
+        """The lens correction of include/r2f.h (r2f_lens_correct: radial map, 8 x 8 LANCZOS4 gather, clamp at 0, vignetting gain)
+        of a whole frame, restricted to `window` = (row0, col0, rows, cols) of the corrected frame -> (3, rows, cols) planes.
+        profile_or_params: a raw2film_amd.lens.LensProfile (planned for this frame's size) or the r2f_lens_params of that size."""
+        torch = self._torch
+        self._check_image(image)
+        layout, H, W = self.layout_of(image, layout)
+        params = profile_or_params if isinstance(profile_or_params, _lib.LensParams) else profile_or_params.plan(H, W)
+        r0, c0, nr, nc = (0, 0, H, W) if window is None else [int(v) for v in window]
+        out = torch.empty((3, nr, nc), dtype=torch.float32, device=self.device)
+        if nr == 0 or nc == 0:
+            return out
+        pd = self.planes(out, 0)
+        self._check(self._lib.r2f_lens_correct(self._h, image.data_ptr(), layout, H, W, C.byref(params), C.byref(pd), nr, nc, r0, c0,
+                                               self._stream()))
+        return out
+
     def decode_u16(self, image_u16, factor: float, divisor: float = 65535.0, out=None):
         """raw_to_linear's last two lines (raw_conversion.py:50-52) on the device: float32(u) / divisor * float32(factor) for a
         uint16 (H, W, 3 | 4) CUDA tensor (LibRaw's 16-bit output; int16 tensors are read as the same bits) -> float32 (H, W, 3).

@@ -181,6 +181,7 @@ struct r2f_ctx {
     bool capturing = false;        // r2f_render is capturing render_launches: the frame-block write stays outside the graph
     // one per entry point: the float32 up-scale before the path and the final resize of one process() call differ in geometry
     r2f::LanczosTables lanczos_u8, lanczos_u16, lanczos_f32;
+    r2f::DeviceBuf lens_table;  // r2f_lens_correct's 32 x 8 phase table (r2f_lens_phase_table), uploaded on first use
     // the grain stencil as weight pairs for grain_stencil_fixed (small square symmetric kernels), built on first use
     r2f::DeviceBuf grain_fixed_w;
     bool grain_fixed_valid = false;

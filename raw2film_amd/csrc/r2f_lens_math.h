@@ -1,0 +1,137 @@
+// r2f_lens_math.h -- the arithmetic of the lens correction (include/r2f.h, r2f_lens_correct), as text the device kernel
+// (r2f_resample.hip) and a CPU program (tests/lens_check.cpp, g++ -ffp-contract=off) both compile: the coordinate map, the 1/32
+// phase split with its inside / outside decision, the 64-tap sample over a pixel-fetch functor and the vignetting gain.  Every
+// operation is one correctly rounded fp32 operation; contraction is off for each function (a fused multiply-add would round once
+// where the definition rounds twice).  No HIP types, no includes beyond <math.h>.
+#pragma once
+
+#include <math.h>
+
+#include "../../include/r2f.h"
+
+#if defined(__HIPCC__)
+#define R2F_HD __host__ __device__ __forceinline__
+#else
+#define R2F_HD inline
+#endif
+#if defined(__clang__)
+#define R2F_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define R2F_NO_CONTRACT  // (g++: the translation unit is compiled with -ffp-contract=off)
+#endif
+
+namespace r2f {
+namespace lens {
+
+constexpr int kPhases = 32;  // INTER_TAB_SIZE = 1 << INTER_BITS
+constexpr int kTaps = 8;
+
+// Source coordinate (sx, sy) of output pixel (X, Y); dx, dy are handed on to the vignetting gain.
+R2F_HD void source_coord(const r2f_lens_params& p, int X, int Y, float& sx, float& sy, float& dx, float& dy) {
+    R2F_NO_CONTRACT
+    dx = (float)X - p.cx;
+    dy = (float)Y - p.cy;
+    const float u = dx * p.q, v = dy * p.q;
+    const float uu = u * u, vv = v * v;
+    const float r2 = uu + vv;
+    float f = 1.f;
+    if (p.model == R2F_LENS_POLY3) {
+        const float t = p.k[0] * r2;
+        f = p.c0 + t;
+    } else if (p.model == R2F_LENS_POLY5) {
+        const float t0 = p.k[1] * r2;
+        const float t1 = p.k[0] + t0;
+        const float t2 = r2 * t1;
+        f = 1.f + t2;
+    } else if (p.model == R2F_LENS_PTLENS) {
+        const float r = sqrtf(r2);
+        const float t0 = r * p.k[0];
+        const float t1 = p.k[1] + t0;
+        const float t2 = r * t1;
+        const float t3 = p.k[2] + t2;
+        const float t4 = r * t3;
+        f = p.c0 + t4;
+    }
+    const float g = f * p.inv_scale;
+    const float ox = dx * g, oy = dy * g;
+    sx = p.cx + ox;
+    sy = p.cy + oy;
+}
+
+// One axis of the 1/32 phase split: s -> (i, phase), or false when no tap of i-3 .. i+4 can lie inside [0, n).  Decided on the
+// float rint(s*32) -- a NaN fails both comparisons, an infinity or 1e30 one of them -- so the int conversion only ever sees values
+// of at most (n + 3)*32 in magnitude.
+R2F_HD bool split_phase(float s, int n, int& i, int& phase) {
+    R2F_NO_CONTRACT
+    const float t = s * 32.f;
+    const float qf = rintf(t);
+    if (!(qf >= -128.f && qf < (float)(n + 3) * 32.f)) return false;  // i >= -4 and i <= n + 2
+    const int q = (int)qf;
+    i = q >> 5;
+    phase = q & 31;
+    return true;
+}
+
+// The 64 taps around (ix, iy) with the rows wy, wx of the phase table.  fetch(y, x, v) is called for taps inside the frame only and
+// fills the three channels; a tap outside reads 0.  Sum order: a row left to right, rows top to bottom, each from its first product.
+template <typename Fetch>
+R2F_HD void sample64(const Fetch& fetch, int H, int W, int ix, int iy, const float* wx, const float* wy, float (&acc)[3]) {
+    R2F_NO_CONTRACT
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int k = 0; k < kTaps; ++k) {
+        const int yy = iy - 3 + k;
+        const bool row_in = yy >= 0 && yy < H;
+        float h[3] = {0.f, 0.f, 0.f};
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int j = 0; j < kTaps; ++j) {
+            const int xx = ix - 3 + j;
+            float v[3] = {0.f, 0.f, 0.f};
+            if (row_in && xx >= 0 && xx < W) fetch(yy, xx, v);
+            const float w = wy[k] * wx[j];
+            for (int c = 0; c < 3; ++c) {
+                const float prod = w * v[c];
+                h[c] = j == 0 ? prod : h[c] + prod;
+            }
+        }
+        for (int c = 0; c < 3; ++c) acc[c] = k == 0 ? h[c] : acc[c] + h[c];
+    }
+}
+
+// max(sum, 0), then the vignetting gain of (dx, dy).
+R2F_HD float finish(const r2f_lens_params& p, float sum, float dx, float dy) {
+    R2F_NO_CONTRACT
+    float o = sum < 0.f ? 0.f : sum;
+    if (p.vignetting) {
+        const float a = dx * p.qv, b = dy * p.qv;
+        const float aa = a * a, bb = b * b;
+        const float rv2 = aa + bb;
+        const float t0 = rv2 * p.v[2];
+        const float t1 = p.v[1] + t0;
+        const float t2 = rv2 * t1;
+        const float t3 = p.v[0] + t2;
+        const float t4 = rv2 * t3;
+        const float d = 1.f + t4;
+        o = o / d;
+    }
+    return o;
+}
+
+// One output pixel, start to end: what the kernel's lane and the CPU program's loop body both run.  `table`: 32 x 8 floats.
+template <typename Fetch>
+R2F_HD void correct_pixel(const r2f_lens_params& p, const Fetch& fetch, int H, int W, const float* table, int X, int Y, float (&out)[3]) {
+    float sx, sy, dx, dy;
+    source_coord(p, X, Y, sx, sy, dx, dy);
+    int ix, iy, fx, fy;
+    out[0] = out[1] = out[2] = 0.f;
+    if (!split_phase(sx, W, ix, fx) || !split_phase(sy, H, iy, fy)) return;  // outside: 0, nothing indexed, no gain applied
+    float acc[3];
+    sample64(fetch, H, W, ix, iy, table + fx * kTaps, table + fy * kTaps, acc);
+    for (int c = 0; c < 3; ++c) out[c] = finish(p, acc[c], dx, dy);
+}
+
+}  // namespace lens
+}  // namespace r2f

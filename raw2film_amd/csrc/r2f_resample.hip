@@ -3,13 +3,16 @@
 //   resize_area_u8 / _u16  cpu_processor.py:411-412 -> utils.resolution_scaling -> cv.resize(canvas, INTER_AREA): the final shrink of
 //                          the rendered (and canvas-framed) uint8 / uint16 frame to the requested resolution
 //   warp_affine            pre-path free rotation (cv.warpAffine, INTER_LINEAR, zero border)
+//   lens_correct           pre-path lens correction: radial map, cv2.remap(INTER_LANCZOS4, zero border), clamp, vignetting gain
 //   lanczos4_u8            post-path up-scale of the uint8 result (cv.resize INTER_LANCZOS4): the way back from max_scale
 //   lanczos4_f32 / _u16    the float-weight LANCZOS4: the float frame before the path, the uint16 result after it
 // None of this runs inside r2f_render or a timed step; the kernels are one lane per output pixel (launch_64x4).
+#include <climits>
 #include <cstring>
 #include <vector>
 
 #include "r2f_ctx.h"
+#include "r2f_lens_math.h"
 
 using namespace r2f;
 
@@ -241,6 +244,122 @@ __global__ __launch_bounds__(256) void warp_affine_kernel(const WarpArgs a) {
     p0[2 * a.dst.plane_stride] = v[2];
 }
 
+// ------------------------------------------------------------------------------ lens correction (pre-path)
+// effects.lens_correction (effects.py:22-43) from caller-supplied numbers; the definition is in include/r2f.h and its arithmetic in
+// r2f_lens_math.h (the text tests/lens_check.cpp compiles for the CPU).  Lanes along x, four output rows per lane; the 32 x 8 phase
+// table sits in LDS (1 KiB, one float per thread to fill).
+struct LensArgs {
+    const void* in;
+    int in_layout, H, W;
+    DevPlanes dst;
+    int out_h, out_w, oy, ox;
+    r2f_lens_params p;
+    const float* table;  // 32 x 8, device
+};
+
+struct LensFetch {
+    const float* src;
+    int in_layout, H, W;
+    __device__ __forceinline__ void operator()(int y, int x, float (&v)[3]) const {
+        if (in_layout == R2F_LAYOUT_CHW) {
+            const long long plane = (long long)H * W, o = (long long)y * W + x;
+            v[0] = src[o], v[1] = src[plane + o], v[2] = src[2 * plane + o];
+        } else {
+            const float* px = src + ((long long)y * W + x) * (in_layout == R2F_LAYOUT_HWC4 ? 4 : 3);
+            v[0] = px[0], v[1] = px[1], v[2] = px[2];
+        }
+    }
+};
+
+// A block of 256 threads makes a 64 x 16 tile (four rows per lane), finds the box of source texels its taps touch,
+// and -- when the box fits kLensBoxTexels -- copies it into LDS once (a texel outside the frame as 0, which is what such a tap
+// reads), so that a texel crosses the memory system once per block instead of once per tap.  The sums are sample64's over another
+// fetch functor: the same samples in the same order, so the result does not depend on whether a block staged.  A block whose box
+// does not fit (a strong magnification: scale well below 1) gathers its taps from global memory.  Against one lane per pixel
+// gathering every tap from global memory: 5.0 instead of 7.7 ms at 100 MP; two or eight rows per lane and an interleaved float4
+// box were slower (profiles/r15_lens_correct.txt).
+constexpr int kLensRows = 4;            // rows per lane
+constexpr int kLensBoxTexels = 3072;    // 36 KiB of LDS for three planes: 71 x 23 texels for an undistorted tile
+
+struct LensLdsFetch {
+    const float* box;  // [3][kLensBoxTexels], rows bw apart
+    int x0, y0, bw;
+    __device__ __forceinline__ void operator()(int y, int x, float (&v)[3]) const {
+        const int o = (y - y0) * bw + (x - x0);
+        v[0] = box[o], v[1] = box[kLensBoxTexels + o], v[2] = box[2 * kLensBoxTexels + o];
+    }
+};
+
+__global__ __launch_bounds__(256) void lens_correct_kernel(const LensArgs a) {
+    __shared__ float table[lens::kPhases * lens::kTaps];
+    __shared__ float box[3 * kLensBoxTexels];
+    __shared__ int ext[4];  // min ix, max ix, min iy, max iy over the block's inside pixels
+    const int tid = threadIdx.y * 64 + threadIdx.x;
+    table[tid] = a.table[tid];
+    if (tid < 4) ext[tid] = (tid & 1) ? INT_MIN : INT_MAX;
+    __syncthreads();
+    const int dx = blockIdx.x * 64 + threadIdx.x, dy0 = blockIdx.y * (4 * kLensRows) + threadIdx.y;
+    const LensFetch global{static_cast<const float*>(a.in), a.in_layout, a.H, a.W};
+    int ix[kLensRows], iy[kLensRows], ph[kLensRows];  // ph: fx | fy << 8, or -1 for a pixel that samples nothing
+    float ddx[kLensRows], ddy[kLensRows];
+    int lo_x = INT_MAX, hi_x = INT_MIN, lo_y = INT_MAX, hi_y = INT_MIN;
+#pragma unroll
+    for (int r = 0; r < kLensRows; ++r) {
+        const int dy = dy0 + 4 * r;
+        ph[r] = -1;
+        ix[r] = iy[r] = 0;
+        ddx[r] = ddy[r] = 0.f;
+        if (dx >= a.out_w || dy >= a.out_h) continue;
+        float sx, sy;
+        lens::source_coord(a.p, dx + a.ox, dy + a.oy, sx, sy, ddx[r], ddy[r]);
+        int fx, fy;
+        if (!lens::split_phase(sx, a.W, ix[r], fx) || !lens::split_phase(sy, a.H, iy[r], fy)) continue;
+        ph[r] = fx | (fy << 8);
+        lo_x = min(lo_x, ix[r]), hi_x = max(hi_x, ix[r]), lo_y = min(lo_y, iy[r]), hi_y = max(hi_y, iy[r]);
+    }
+    if (lo_x <= hi_x) {
+        atomicMin(&ext[0], lo_x), atomicMax(&ext[1], hi_x);
+        atomicMin(&ext[2], lo_y), atomicMax(&ext[3], hi_y);
+    }
+    __syncthreads();
+    // (block-uniform from here: every thread reads the same four words)
+    const int x0 = ext[0] - 3, y0 = ext[2] - 3;
+    const bool any = ext[0] <= ext[1];
+    // ix, iy lie in [-4, n + 2] (split_phase), so the extents are small ints and their products cannot overflow
+    const int bw = any ? ext[1] + 4 - x0 + 1 : 0, bh = any ? ext[3] + 4 - y0 + 1 : 0;
+    const bool staged = any && (long long)bw * bh <= kLensBoxTexels;
+    if (staged) {
+        for (int i = tid; i < bw * bh; i += 256) {
+            const int y = y0 + i / bw, x = x0 + i % bw;
+            float v[3] = {0.f, 0.f, 0.f};
+            if (y >= 0 && y < a.H && x >= 0 && x < a.W) global(y, x, v);
+            box[i] = v[0], box[kLensBoxTexels + i] = v[1], box[2 * kLensBoxTexels + i] = v[2];
+        }
+    }
+    __syncthreads();
+    const LensLdsFetch lds{box, x0, y0, bw};
+#pragma unroll
+    for (int r = 0; r < kLensRows; ++r) {
+        const int dy = dy0 + 4 * r;
+        if (dx >= a.out_w || dy >= a.out_h) continue;
+        float v[3] = {0.f, 0.f, 0.f};
+        if (ph[r] >= 0) {
+            float acc[3];
+            const float *wx = table + (ph[r] & 31) * lens::kTaps, *wy = table + (ph[r] >> 8) * lens::kTaps;
+            if (staged)
+                lens::sample64(lds, a.H, a.W, ix[r], iy[r], wx, wy, acc);
+            else
+                lens::sample64(global, a.H, a.W, ix[r], iy[r], wx, wy, acc);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = lens::finish(a.p, acc[c], ddx[r], ddy[r]);
+        }
+        float* p0 = a.dst.data + (long long)(dy - a.dst.gy0) * a.out_w + dx;
+        p0[0] = v[0];
+        p0[a.dst.plane_stride] = v[1];
+        p0[2 * a.dst.plane_stride] = v[2];
+    }
+}
+
 // ------------------------------------------------------------------------------ LANCZOS4, uint8 (post-path)
 struct LanczosArgs {
     const uint8_t* src;  // (H, W, 3)
@@ -435,6 +554,32 @@ int r2f_warp_affine(r2f_ctx* ctx, const void* in, int in_layout, int H, int W, c
     WarpArgs a{in, in_layout, H, W, to_dev(dst), out_h, out_w, oy, ox, {}};
     for (int i = 0; i < 6; ++i) a.m[i] = (float)m_dst_to_src[i];
     R2F_HIP(ctx, launch_64x4(warp_affine_kernel, out_w, out_h, static_cast<hipStream_t>(stream), a));
+    return R2F_OK;
+}
+
+int r2f_lens_correct(r2f_ctx* ctx, const void* in, int in_layout, int H, int W, const r2f_lens_params* params, const r2f_planes* dst,
+                     int out_h, int out_w, int oy, int ox, void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    // (the phase split adds 3 to a frame side and multiplies by 32 in float; the window's coordinates go through int sums)
+    constexpr int kMaxSide = 1 << 24;
+    if (!in || !params || in_layout < 0 || in_layout > 2 || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0 || H > kMaxSide || W > kMaxSide ||
+        out_h > kMaxSide || out_w > kMaxSide || oy < -kMaxSide || oy > kMaxSide || ox < -kMaxSide || ox > kMaxSide)
+        return fail(ctx, R2F_EINVAL, "lens_correct: bad arguments");
+    if (params->model < R2F_LENS_NONE || params->model > R2F_LENS_PTLENS)
+        return fail(ctx, R2F_EINVAL, "lens_correct: unknown distortion model %d", params->model);
+    int rc = check_rows(ctx, "lens dst", dst, 0, out_h);
+    if (rc) return rc;
+    if (!ctx->lens_table.p) {
+        float host[lens::kPhases * lens::kTaps];
+        r2f_lens_phase_table(host);
+        rc = upload(ctx, ctx->lens_table, host, sizeof host);  // (once per context)
+        if (rc) return rc;
+    }
+    const LensArgs a{in, in_layout, H, W, to_dev(dst), out_h, out_w, oy, ox, *params, static_cast<const float*>(ctx->lens_table.p)};
+    launch_k(lens_correct_kernel, dim3((out_w + 63) / 64, (out_h + 4 * kLensRows - 1) / (4 * kLensRows)), dim3(64, 4), 0,
+             static_cast<hipStream_t>(stream), a);
+    R2F_HIP(ctx, take_launch_status());
     return R2F_OK;
 }
 

@@ -7,10 +7,11 @@ re-uploaded only when their parameter dict changes (cpu_processor.py:104-105,157
 
 Scope: the post-decode per-pixel path plus what sits either side of it: aspect crop, zoom,
 quarter turns, free rotation, the preview / `max_scale` down-scale and the pre-path chroma NR before; the highlight
-burn (S7) inside; uint8, the LANCZOS4 way back from `max_scale`, canvas and histogram after.  RAW decoding and lens
-correction (lensfun) are out of scope: a call that would need them -- `lens_correction=True` WITH a camera and a lens, the
-only case in which the reference corrects anything (effects.py:22-30) -- raises NotImplementedError instead of silently
-rendering something else.
+burn (S7) inside; uint8, the LANCZOS4 way back from `max_scale`, canvas and histogram after.  Lens correction runs on the
+device from numbers the caller supplies (`lens_profile=`, raw2film_amd.lens.LensProfile: the first device pre-path step).  RAW
+decoding and the lensfun database lookup are out of scope: a call that would need the lookup -- `lens_correction=True` WITH a
+camera and a lens, the only case in which the reference corrects anything (effects.py:22-30) -- raises NotImplementedError
+instead of silently rendering something else.
 
 `src` is therefore a decoded frame: a float32 (H, W, 3|4) array / CUDA tensor in linear CIE XYZ
 (what `raw_to_linear` returns, raw_conversion.py:33-53), or the path of a `.npy` file holding one.
@@ -30,6 +31,7 @@ import numpy as np
 
 from . import _lib, filmstock, geometry, stencils
 from .context import LOG_EPS, LUT3D_SCALE, HipContext
+from .lens import LensProfile
 from . import tiff
 from .jpeg_stream import ICC_OVERHEAD, MARKER_MAX, XMP_NAMESPACE, JpegBandSink, JpegStaging, deliver, metadata_segments
 from .results import ResultBuffers
@@ -44,6 +46,8 @@ def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canv
     """Why a phase-1 payload cannot stream through the pipeline in row bands, or None (its render's stages have the last word:
     plan_bands).  `shape`, `dtype`: of its frame as a tensor (_payload_tensor: "torch.float32", or "torch.int16" for uint16)."""
     is_u16 = dtype == "torch.int16"  # LibRaw's 16-bit output: converted band by band on the device (raw_conversion.py:50-52)
+    if payload.get("lens"):
+        return _LENS_REJECTED
     if (payload.get("warp") or payload.get("resize_to") or payload.get("upscale_to") or payload.get("chroma_nr")
             or payload.get("canvas_resolution") or canvas_mode != "No" or on_device or len(shape) != 3
             or int(shape[2]) not in (3, 4) or math.prod(shape) < (1 << 24) or dtype not in ("torch.float32", "torch.int16")
@@ -57,11 +61,13 @@ def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canv
     return None
 
 
-def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="No", highlight_burn=0.0):
+def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="No", highlight_burn=0.0, lens=False):
     """Why process(src, cache=False) renders a frame in one piece before it extracts its payload (stream_rejection and plan_bands
-    come after that), or None."""
+    come after that), or None.  lens: the call corrects the lens (lens_correction with a lens_profile)."""
     if stream_bands <= 1:
         return f"stream_bands = {stream_bands}"
+    if lens:
+        return _LENS_REJECTED
     if not isinstance(src, np.ndarray):
         return f"the source is a {type(src).__name__}, not a host array"
     if src.size < (1 << 24):
@@ -70,6 +76,9 @@ def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="
         return (f"a device pre-path, a canvas or a highlight burn: rotation = {rotation!r}, chroma_nr = {chroma_nr!r}, "
                 f"canvas_mode = {canvas_mode!r}, highlight_burn = {highlight_burn!r}")
     return None
+
+
+_LENS_REJECTED = "the lens step (lens_profile): its gather reads the whole frame, which a row band does not hold"
 
 
 def plan_bands(H, flags, ha, ma, bands, taper):
@@ -366,24 +375,34 @@ class HipProcessor:
     def extract_image_data_cpu(self, src, cam=None, lens=None, lens_correction=True, frame_width=36, frame_height=24,
                                rotation=0.0, zoom=1.0, rotate_times=0, flip=False, resolution=None, half_size=True,
                                cache=True, chroma_nr=0, max_scale=400.0, canvas_mode="No", canvas_scale=1.0,
-                               canvas_ratio=1.0, exposure=None, metadata=None, **kwargs):
+                               canvas_ratio=1.0, exposure=None, metadata=None, lens_profile=None, **kwargs):
         """PHASE 1 of the two-phase batch API (gpu_processor.py:715-783): pure host work, touches
         no instance state.  Returns the same payload dict; `image_array` is (H, W, 4) float32 ((H, W, 3) with payload_alpha=False).
         exposure="device" (a uint16 frame): no pass over the frame here.  `image_array` is then the WHOLE decoded frame -- the caller's
         array itself when that is contiguous --, `u16_window` the (row0, col0, rows, cols) the aspect and zoom crops keep of it,
         `exposure_root` calc_exposure's exponent and `u16_factor` the marker "device": phase 2 measures the exposure on the uploaded
         frame and decodes the window with it.  A frame that is turned or rotated is measured here as with exposure=None, and the
-        payload's `exposure_rejected` says why."""
+        payload's `exposure_rejected` says why.
+        lens_profile (a raw2film_amd.lens.LensProfile) with lens_correction=True: the lens correction moves to the device.  Upstream
+        corrects before any crop, so `image_array` stays the WHOLE frame and the payload gains `lens`: the r2f_lens_params of the
+        frame's size, the `window` (row0, col0, rows, cols) of the corrected frame the aspect crop keeps (with the zoom crop when
+        there is no rotation) and the quarter turns still to be applied to it; every crop-derived value (`pipeline_resolution`
+        ...) is that of the same call without a profile.  lens_correction=False ignores the profile."""
         on_device = exposure_on_device(exposure)
+        if lens_profile is not None and not isinstance(lens_profile, LensProfile):
+            raise ValueError(f"lens_profile must be a raw2film_amd.lens.LensProfile, got {type(lens_profile).__name__}")
         if lens_correction and cam is not None and lens is not None:
-            # the reference corrects only when both are given (cpu_processor.py:107-108, effects.py:22-30); lensfun is not
-            # part of the accelerated path, and rendering an uncorrected frame in its place would be a silent difference
+            # the reference corrects only when both are given (cpu_processor.py:107-108, effects.py:22-30); the lensfun lookup is
+            # not part of the accelerated path, and rendering an uncorrected frame in its place would be a silent difference
             raise NotImplementedError("lens correction (lensfunpy, effects.py:22-43) is outside the accelerated path: "
-                                      "pass lens_correction=False or no cam / lens")
+                                      "pass lens_correction=False or no cam / lens (the calibration's numbers go in lens_profile)")
+        lens_step = None  # the payload's `lens`, filled in once the frame's size is known
         # _internal (load_image_texture: the payload never leaves this object): no alpha plane, and the clamp of
         # gpu_processor.py:275 runs on the device after the upload instead of as a 12 B/px pass over host memory
         internal = bool(kwargs.get("_internal"))
         image = self._load_decoded(src, clip=not internal)
+        if lens_correction and lens_profile is not None:
+            lens_step = {"params": lens_profile.plan(image.shape[0], image.shape[1]), "window": None, "rotate_times": 0}
         u16_factor = u16_window = exposure_root = exposure_rejected = None
         if image.dtype == np.uint16 and on_device and (rotation or int(rotate_times) % 4):
             exposure_rejected = (f"rotation = {rotation!r}, rotate_times = {rotate_times!r}: a turned or rotated frame is measured on "
@@ -397,6 +416,8 @@ class HipProcessor:
             r0, c0, nr, nc = geometry.crop_box(image.shape[0], image.shape[1], 1, frame_width / frame_height, flip)
             zr0, zc0, znr, znc = geometry.crop_box(nr, nc, zoom, frame_width / frame_height, False)
             u16_window = (r0 + zr0, c0 + zc0, znr, znc)
+            if lens_step is not None:  # the frame is decoded whole: the lens step reads all of it and cuts this window itself
+                lens_step["window"], u16_window = u16_window, (0, 0, image.shape[0], image.shape[1])
             u16_factor, exposure_root = DEVICE_EXPOSURE, float(decode.exposure_root(metadata))
         elif image.dtype == np.uint16:
             # raw_to_linear's tail (raw_conversion.py:50-52) moves to the device: the auto exposure is measured here, on the
@@ -412,7 +433,10 @@ class HipProcessor:
             # aspect crop here (a view), then phase 2 warps straight into the window that effects.rotate's centred crop
             # and the zoom crop keep, and applies the quarter turns
             r0, c0, nr, nc = geometry.crop_box(image.shape[0], image.shape[1], 1, aspect, flip)
-            image = image[r0:r0 + nr, c0:c0 + nc]
+            if lens_step is not None:
+                lens_step["window"] = (r0, c0, nr, nc)  # (the warp then reads the corrected aspect crop)
+            else:
+                image = image[r0:r0 + nr, c0:c0 + nc]
             m_inv, (wr0, wc0, wnr, wnc) = geometry.rotation_plan(nr, nc, rotation)
             zr0, zc0, znr, znc = geometry.crop_box(wnr, wnc, zoom, aspect, False)
             if znr <= 0 or znc <= 0:
@@ -420,7 +444,14 @@ class HipProcessor:
             warp = {"m_dst_to_src": m_inv, "window": (wr0 + zr0, wc0 + zc0, znr, znc), "rotate_times": int(rotate_times) % 4}
             h, w = (znc, znr) if warp["rotate_times"] % 2 else (znr, znc)
         elif u16_window is not None:
-            h, w = u16_window[2:]  # (the frame stays whole: the window is cut on the device)
+            # (the frame stays whole: the window is cut on the device)
+            h, w = (lens_step["window"] if lens_step is not None else u16_window)[2:]
+        elif lens_step is not None:
+            # crop_to_frame's boxes as a window of the corrected frame; its quarter turns follow the lens step on the device
+            r0, c0, nr, nc = geometry.crop_box(image.shape[0], image.shape[1], 1, aspect, flip)
+            zr0, zc0, znr, znc = geometry.crop_box(nr, nc, zoom, aspect, False)
+            lens_step["window"], lens_step["rotate_times"] = (r0 + zr0, c0 + zc0, znr, znc), int(rotate_times) % 4
+            h, w = (znc, znr) if lens_step["rotate_times"] % 2 else (znr, znc)
         else:
             # aspect crop / zoom / quarter turns: index arithmetic of raw_conversion.crop_rotate_zoom (raw_conversion.py:56-72)
             image = geometry.crop_to_frame(image, frame_width, frame_height, zoom, rotate_times, flip)
@@ -485,6 +516,7 @@ class HipProcessor:
             "resize_to": resize_to,  # (rows, cols) of the INTER_AREA down-scale still to be applied, or None
             "warp": warp,  # free rotation still to be applied (first of the device pre-path steps), or None
             "upscale_to": upscale_to,  # (rows, cols) the rendered uint8 frame is LANCZOS4-scaled back into, or None
+            **({"lens": lens_step} if lens_step is not None else {}),  # the lens step (first of the device pre-path steps)
         }
 
     @staticmethod
@@ -517,7 +549,7 @@ class HipProcessor:
                 canvas_ratio=1.0, halation_intensity=1.0, halation=True, halation_size=1.0, halation_green_factor=0.4,
                 sharpness=True, sharpening_strength=0.0, sharpening_sigma=1.0, chroma_nr=0, grain=2,
                 highlight_burn=0.0, burn_scale=50.0, half_size=True, cache=True, color_masking=None, max_scale=400.0,
-                seed=None, exposure=None, metadata=None, src_version=None, output_bits=8, **_):
+                seed=None, exposure=None, metadata=None, src_version=None, output_bits=8, lens_profile=None, **_):
         """Load (decoded) frame and render it: np.uint8 (H, W, 3), like cpu_processor.py:414 -- including the CPU processor's
         last step, resolution_scaling of the finished (canvas-framed) frame to the requested resolution (cpu_processor.py:411-412).
         With `dst_texture` (a uint8 (h, w, 4) CUDA tensor standing in for the preview widget's wgpu texture) the call behaves
@@ -534,7 +566,9 @@ class HipProcessor:
         output_bits=16: np.uint16 (H, W, 3) instead -- clip(x * 65535, 0, 65535) truncated, cpu_processor.py:407's rule with
         2 ** 16 - 1 -- with the whole post-path at 16 bits: the canvas colour c * 257, the LANCZOS4 way back from `max_scale` and
         the final INTER_AREA as cv.resize applies them to uint16, the result lent from a pinned pool of its own and a large
-        cache=False frame streamed in row bands exactly where an 8-bit one is.  Not with dst_texture (RGBA8)."""
+        cache=False frame streamed in row bands exactly where an 8-bit one is.  Not with dst_texture (RGBA8).
+        lens_profile (raw2film_amd.lens.LensProfile) with lens_correction=True: the whole frame is uploaded and corrected on the
+        device before any crop (extract_image_data_cpu); such a frame never streams in row bands."""
         settings = dict(locals())  # every keyword of the signature (the unknown ones in `_` aside), named nowhere else
         exposure_on_device(exposure)  # (any string but "device" raises before any work starts)
         settings["output_bits"] = check_output_bits(output_bits, dst_texture)
@@ -556,7 +590,8 @@ class HipProcessor:
             self._torch.cuda.synchronize(self.device)
             t_start = time.perf_counter()
         elif (not cache and dst_texture is None
-              and host_stream_gate(src, self.stream_bands, rotation, chroma_nr, canvas_mode, highlight_burn) is None):
+              and host_stream_gate(src, self.stream_bands, rotation, chroma_nr, canvas_mode, highlight_burn,
+                                   bool(lens_correction) and lens_profile is not None) is None):
             # a large host frame that is uploaded for this one render: streamed through the pipeline in row bands while it arrives
             res = self._process_streamed(src, negative_film, grain_size, grain_sigma, load, settings)
             if res is not None:
@@ -585,7 +620,7 @@ class HipProcessor:
     def load_image_texture(self, src, cam=None, lens=None, lens_correction=True, frame_width=36, frame_height=24, rotation=0.0,
                            zoom=1.0, rotate_times=0, flip=False, resolution=None, half_size=True, cache=True, chroma_nr=0,
                            max_scale=400.0, canvas_mode="No", canvas_scale=1.0, canvas_ratio=1.0, exposure=None, metadata=None,
-                           src_version=None):
+                           src_version=None, lens_profile=None):
         """GpuProcessor.load_image_texture (gpu_processor.py:655-719): prepare and upload the frame unless the load parameters
         are those of the frame that is already on the device.  A path compares by value like upstream's `src`.  An array
         compares by identity AND by a fingerprint of its content (shape, dtype, address, a checksum of up to 32 evenly spaced
@@ -610,7 +645,7 @@ class HipProcessor:
             "frame_width": frame_width, "frame_height": frame_height, "rotation": rotation, "zoom": zoom,
             "rotate_times": rotate_times, "flip": flip, "resolution": resolution, "half_size": half_size, "chroma_nr": chroma_nr,
             "max_scale": max_scale, "canvas_mode": canvas_mode, "canvas_scale": canvas_scale, "canvas_ratio": canvas_ratio,
-            "exposure": exposure, "metadata": metadata,
+            "exposure": exposure, "metadata": metadata, "lens_profile": lens_profile,
         }
         held = getattr(self, "_texture_src", None)
         same_src = isinstance(src, str) or (held is not None and held() is src)
@@ -627,7 +662,7 @@ class HipProcessor:
             cpu_payload = self.extract_image_data_cpu(
                 src, cam, lens, lens_correction, frame_width, frame_height, rotation, zoom, rotate_times, flip, resolution,
                 half_size, cache, chroma_nr, max_scale, canvas_mode, canvas_scale, canvas_ratio, exposure=exposure, metadata=metadata,
-                _internal=True,
+                lens_profile=lens_profile, _internal=True,
             )
         if prof:
             t1 = time.perf_counter()
@@ -833,7 +868,8 @@ class HipProcessor:
             self.stream_rejected = (next((why for why in early if why), None) or
                                     ("profile_stages is on" if getattr(self, "profile_stages", False) else
                                      host_stream_gate(src, self.stream_bands, settings["rotation"], settings["chroma_nr"],
-                                                      settings["canvas_mode"], settings["highlight_burn"])))
+                                                      settings["canvas_mode"], settings["highlight_burn"],
+                                                      bool(settings["lens_correction"]) and settings["lens_profile"] is not None)))
         return settings, load, self.extract_image_data_cpu(src, **load, _internal=True)
 
     def _export_preloaded(self, what, settings, stream, early=()) -> bool:
@@ -1278,9 +1314,15 @@ class HipProcessor:
         elif cpu_payload.get("clip_on_device"):
             image = image.clamp_(0.0, 65504.0)  # np.clip(image, 0, 65504) of gpu_processor.py:275, on the uploaded copy
         layout = None  # the payload is (H, W, C) like the reference's; the device pre-path hands on (3, H, W) planes
+        lens_step = cpu_payload.get("lens")
+        if lens_step:  # lens correction (effects.lens_correction) of the whole frame, into the window the crops keep
+            image = self.ctx.lens_correct(image.contiguous(), lens_step["params"], lens_step["window"])
+            if lens_step.get("rotate_times"):
+                image = torch.rot90(image, lens_step["rotate_times"], dims=(1, 2)).contiguous()
+            layout = "chw"
         warp = cpu_payload.get("warp")
         if warp:  # free rotation (effects.rotate) + the crops behind it + quarter turns (np.rot90 on the planes)
-            image = self.ctx.warp_affine(image.contiguous(), warp["m_dst_to_src"], warp["window"])
+            image = self.ctx.warp_affine(image.contiguous(), warp["m_dst_to_src"], warp["window"], layout=layout)
             if warp["rotate_times"]:
                 image = torch.rot90(image, warp["rotate_times"], dims=(1, 2)).contiguous()
             layout = "chw"
