@@ -420,6 +420,73 @@ R2F_API int r2f_resize_area_u8(r2f_ctx* ctx, const uint8_t* src_hwc, int H, int 
 R2F_API int r2f_resize_lanczos4_u16(r2f_ctx* ctx, const uint16_t* src_hwc, int H, int W, uint16_t* dst_hwc, int out_h, int out_w, void* stream);
 R2F_API int r2f_resize_area_u16(r2f_ctx* ctx, const uint16_t* src_hwc, int H, int W, uint16_t* dst_hwc, int out_h, int out_w, void* stream);
 
+/* Demosaic of a Bayer frame on the device from numbers the caller supplies: what raw_to_linear (raw_conversion.py:33-53) has LibRaw
+ * do behind the file parser -- black / scale, demosaic (PPG, or none with half_size), camera matrix, 16-bit clip -- so that a frame
+ * crosses PCIe as the sensor's 2 bytes per pixel.  The parser stays outside; its result is an r2f_raw_profile.
+ * Parity with LibRaw's bytes is UNPINNED: rawpy is on no machine this project sees.  The arithmetic follows dcraw / LibRaw's
+ * published scale_colors, border_interpolate(3), ppg_interpolate, the half-size green mix and convert_to_rgb; what the tests pin is
+ * THIS definition (tests/demosaic_model.py restates it in NumPy).
+ *
+ * Inputs.  The mosaic is uint16 (H, W), H, W >= 2.  The 2 x 2 pattern gives each site its colour col(y, x) in {R, G, B} = {0, 1, 2}.
+ * black[4] (int32) and mul[4] (float) are per site, indexed by k = (y & 1) * 2 + (x & 1).  M is a float 3 x 3 matrix.
+ * A. Scale.  t = (int)raw - black[k]; S = clamp(trunc(fl((float)t * mul[k])), 0, 65535): one fp32 multiply, truncation toward zero.
+ * B. Full size.  S is the scaled mosaic; G, R, B are the planes being filled; a site's native plane is S and is never rewritten.
+ *    floor(a / 2^n) is an arithmetic shift of a signed int.
+ *    B0, border ring: every pixel with y < 3, y >= H - 3, x < 3 or x >= W - 3.  Each non-native colour c is floor(sum / count) of S
+ *        over the sites of colour c in the 3 x 3 neighbourhood clipped to the frame; 0 when count is 0.
+ *    B1, green at the non-green sites with 3 <= y < H - 3 and 3 <= x < W - 3.  Directions h = (0, 1), v = (1, 0); P(k) is the site
+ *        displaced by k steps; every G here is a native green sample.
+ *          guess = 2 (G(-1) + S(0) + G(1)) - S(-2) - S(2)
+ *          diff  = 3 (|S(-2) - S(0)| + |S(2) - S(0)| + |G(-1) - G(1)|) + 2 (|G(3) - G(1)| + |G(-3) - G(-1)|)
+ *        v iff diff_h > diff_v, otherwise h; G = clamp(floor(guess / 4), min(G(-1), G(1)), max(G(-1), G(1))) along that direction.
+ *    B2, red and blue at the green sites with 1 <= y < H - 1 and 1 <= x < W - 1, for h and for v; c is the colour of the two
+ *        neighbours along the direction: C = clamp(floor((S(-1) + S(1) + 2 G(0) - G(-1) - G(1)) / 2), 0, 65535); G(+-1) from B0 or B1.
+ *    B3, the opposite colour at the red and blue sites of the same range; diagonals d1 = (1, 1), d2 = (1, -1):
+ *          diff_i  = |S(-d) - S(d)| + |G(-d) - G(0)| + |G(d) - G(0)|
+ *          guess_i = S(-d) + S(d) + 2 G(0) - G(-d) - G(d)
+ *        diff_1 != diff_2: clamp(floor(guess of the smaller diff / 2), 0, 65535); else clamp(floor((guess_1 + guess_2) / 4), 0, 65535).
+ *    B2 and B3 overwrite B0's red and blue in rings 1 and 2; ring 0 keeps B0; green in rings 0 .. 2 stays B0's.  No pass reads what
+ *    the same pass writes, so every output pixel is a function of S within 4 samples of it.
+ * B'. Half size (upstream's default half_size=True): H and W even, output (H / 2, W / 2); pixel (y, x) comes from the quad at
+ *    (2 y, 2 x): R and B are S at their sites, G = (S(g1) + S(g2)) >> 1.
+ * C. Colour.  Output channel k: acc = fl(r M[k][0]); acc = fl(acc + fl(g M[k][1])); acc = fl(acc + fl(b M[k][2])): every operation
+ *    one correctly rounded fp32 operation, no contraction; out = clamp(trunc(acc), 0, 65535).
+ * The destination is uint16 (H_out, W_out, 3), contiguous: r2f_decode_u16's channels = 3 input. */
+enum { R2F_CFA_RGGB = 0, R2F_CFA_BGGR = 1, R2F_CFA_GRBG = 2, R2F_CFA_GBRG = 3 };
+/* What the caller knows of a RAW frame (raw2film_amd.raw.RawProfile): the pattern, black level and multiplier per site of the
+ * 2 x 2 quad (k = (y & 1) * 2 + (x & 1)), the camera matrix row-major, and whether to take the half-size form. */
+typedef struct r2f_raw_profile {
+    int32_t pattern, half_size;
+    double black[4];
+    double mul[4];
+    double matrix[9];
+} r2f_raw_profile;
+/* The constants of the definition above for one frame size: cfa[k] the colour id of site k, and the output's size. */
+typedef struct r2f_demosaic_params {
+    int32_t cfa[4];
+    int32_t black[4];
+    float mul[4];
+    float M[9];
+    int32_t half_size, out_h, out_w;
+} r2f_demosaic_params;
+/* Host planner (raw2film_amd/csrc/r2f_demosaic_plan.cpp; no GPU, no context): profile + (H, W) -> params.  R2F_EINVAL for an unknown
+ * pattern, H or W below 2, an odd H or W with half_size, a non-finite number, a black level outside [0, 65535] or not integral, a
+ * multiplier outside (0, 1024] (as a float too) and |M| above 64.  The last two bounds keep every trunc inside int32: step A's
+ * product is at most 65535 * 1024 < 2^27 in magnitude, step C's sum at most 3 * 64 * 65535 < 2^24. */
+R2F_API int r2f_demosaic_plan(const r2f_raw_profile* profile, int H, int W, r2f_demosaic_params* out);
+/* The demosaic itself.  src_rows: uint16 mosaic rows [src_gy0, src_gy0 + src_nrows) of the H x W frame on the device, src_pitch
+ * samples apart (>= W).  Writes output rows [y0, y1) of dst (uint16 (out_h, out_w, 3), row 0 at dst) and nothing else.  Full size
+ * reads mosaic rows [y0 - 4, y1 + 4) clipped to [0, H), half size [2 y0, 2 y1); those rows must lie inside the source window, else
+ * R2F_EINVAL before any launch.  A band's bytes are those of the same rows of a whole-frame call, whatever the cut, the pitch or
+ * the source's alignment (which only select between 32-bit and 16-bit loads of the same samples).
+ * Full size is one launch: a block stages its 64 x 32 tile of scaled samples with a 4-sample apron in LDS (step A once per
+ * sample), derives the green plane of the tile plus a 1-sample apron there, then B2 / B3 / C per output pixel; a wave's 64 pixels
+ * of a row leave through an LDS transpose as one contiguous 384-byte segment.  Half size is a lane per output pixel. */
+R2F_API int r2f_demosaic_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
+                     const r2f_demosaic_params* params, uint16_t* dst_u16_hwc3, int y0, int y1, void* stream);
+/* r2f_demosaic_u16's tile (test shapes are derived from it). */
+enum { R2F_DEMOSAIC_TILE_W = 64, R2F_DEMOSAIC_TILE_H = 32 };
+
 /* The hand-off from RAW decoding: the last two lines of raw_to_linear (raw_conversion.py:50-52) applied to LibRaw's 16-bit
  * output on the device, so that a decoded frame crosses PCIe as uint16 (6 bytes per pixel) instead of float32 (12 or 16):
  * dst = float(src) / divisor (65535, one correctly rounded fp32 division) * factor (the float32 of 2 ** calc_exposure(...),

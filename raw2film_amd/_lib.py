@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(PKG_DIR, "libr2f_hip.so")
 # enums of include/r2f.h
 LAYOUT_HWC3, LAYOUT_HWC4, LAYOUT_CHW = 0, 1, 2
 LENS_NONE, LENS_POLY3, LENS_POLY5, LENS_PTLENS = 0, 1, 2, 3
+CFA_RGGB, CFA_BGGR, CFA_GRBG, CFA_GBRG = 0, 1, 2, 3
+DEMOSAIC_TILE_W, DEMOSAIC_TILE_H = 64, 32  # R2F_DEMOSAIC_TILE_*
 KERNEL_HALATION, KERNEL_MTF, KERNEL_GRAIN = 0, 1, 2
 F_MATRIX, F_HALATION, F_MTF, F_GRAIN, F_GRAIN_MONO, F_BURN, F_IDENTITY_DONE, F_FRAME_RESIDENT = 1, 2, 4, 8, 16, 32, 64, 128
 F_TRACK_RANGE, F_RANGE_VALID = 256, 512
@@ -78,6 +80,16 @@ class LensParams(C.Structure):  # r2f_lens_params: the fp32 constants of one fra
     _fields_ = [("model", C.c_int32), ("vignetting", C.c_int32), ("cx", C.c_float), ("cy", C.c_float), ("q", C.c_float),
                 ("inv_scale", C.c_float), ("c0", C.c_float), ("k", C.c_float * 3), ("qv", C.c_float), ("v", C.c_float * 3),
                 ("scale", C.c_double)]
+
+
+class RawProfile(C.Structure):  # r2f_raw_profile (raw2film_amd.raw.RawProfile fills it)
+    _fields_ = [("pattern", C.c_int32), ("half_size", C.c_int32), ("black", C.c_double * 4), ("mul", C.c_double * 4),
+                ("matrix", C.c_double * 9)]
+
+
+class DemosaicParams(C.Structure):  # r2f_demosaic_params: the constants of one frame size
+    _fields_ = [("cfa", C.c_int32 * 4), ("black", C.c_int32 * 4), ("mul", C.c_float * 4), ("M", C.c_float * 9),
+                ("half_size", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32)]
 
 
 _P = C.POINTER
@@ -159,6 +171,11 @@ _SIGNATURES = {
     "r2f_lens_correct": (
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(LensParams), _P(Planes), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    ),
+    "r2f_demosaic_plan": (C.c_int, [_P(RawProfile), C.c_int, C.c_int, _P(DemosaicParams)]),
+    "r2f_demosaic_u16": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(DemosaicParams), C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     ),
     "r2f_resize_lanczos4_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "r2f_lanczos4_table": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

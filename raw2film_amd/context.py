@@ -558,6 +558,33 @@ class HipContext:
                                                self._stream()))
         return out
 
+    def demosaic_u16(self, mosaic, params, out=None, rows=None):
+        """The Bayer demosaic of include/r2f.h (r2f_demosaic_u16: black / scale, PPG or the half-size form, camera matrix, clip)
+        of a uint16 (H, W) CUDA mosaic (int16 tensors are read as the same bits; rows may be pitched: stride(0) >= W, stride(1)
+        = 1) -> uint16 (out_h, out_w, 3), the frame decode_u16 / decode_u16_auto / exposure_rows take.
+        params: a raw2film_amd.raw.RawProfile (planned full size for this mosaic) or the r2f_demosaic_params of its size.
+        rows = (y0, y1): only those output rows of `out` are written (default: all)."""
+        torch = self._torch
+        if not (isinstance(mosaic, torch.Tensor) and mosaic.is_cuda and mosaic.dtype in (torch.uint16, torch.int16) and mosaic.dim() == 2
+                and mosaic.shape[0] >= 2 and mosaic.shape[1] >= 2 and mosaic.stride(1) == 1 and mosaic.stride(0) >= mosaic.shape[1]):
+            raise ValueError("demosaic_u16 needs a uint16 (H, W) CUDA mosaic of at least 2 x 2 samples with contiguous rows")
+        self._same_device(mosaic, "mosaic")
+        H, W = int(mosaic.shape[0]), int(mosaic.shape[1])
+        if not isinstance(params, _lib.DemosaicParams):
+            params = params.plan(H, W)
+        shape = (int(params.out_h), int(params.out_w), 3)
+        if out is None:
+            out = torch.empty(shape, dtype=mosaic.dtype, device=self.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype in (torch.uint16, torch.int16) and out.is_contiguous()
+                  and tuple(out.shape) == shape):
+            raise ValueError(f"demosaic_u16: out must be a contiguous uint16 CUDA tensor of shape {shape}")
+        else:
+            self._same_device(out, "out")
+        y0, y1 = (0, shape[0]) if rows is None else (int(rows[0]), int(rows[1]))
+        self._check(self._lib.r2f_demosaic_u16(self._h, mosaic.data_ptr(), 0, H, int(mosaic.stride(0)), H, W, C.byref(params),
+                                               out.data_ptr(), y0, y1, self._stream()))
+        return out
+
     def decode_u16(self, image_u16, factor: float, divisor: float = 65535.0, out=None):
         """raw_to_linear's last two lines (raw_conversion.py:50-52) on the device: float32(u) / divisor * float32(factor) for a
         uint16 (H, W, 3 | 4) CUDA tensor (LibRaw's 16-bit output; int16 tensors are read as the same bits) -> float32 (H, W, 3).

@@ -8,13 +8,16 @@ re-uploaded only when their parameter dict changes (cpu_processor.py:104-105,157
 Scope: the post-decode per-pixel path plus what sits either side of it: aspect crop, zoom,
 quarter turns, free rotation, the preview / `max_scale` down-scale and the pre-path chroma NR before; the highlight
 burn (S7) inside; uint8, the LANCZOS4 way back from `max_scale`, canvas and histogram after.  Lens correction runs on the
-device from numbers the caller supplies (`lens_profile=`, raw2film_amd.lens.LensProfile: the first device pre-path step).  RAW
-decoding and the lensfun database lookup are out of scope: a call that would need the lookup -- `lens_correction=True` WITH a
+device from numbers the caller supplies (`lens_profile=`, raw2film_amd.lens.LensProfile: the first device pre-path step), and so
+does what LibRaw does behind its file parser (`raw_profile=`, raw2film_amd.raw.RawProfile, with a uint16 (H, W) Bayer mosaic as
+`src`: black / scale, demosaic, camera matrix on the device, ahead of everything else).  Parsing RAW files
+and the lensfun database lookup are out of scope: a call that would need the lookup -- `lens_correction=True` WITH a
 camera and a lens, the only case in which the reference corrects anything (effects.py:22-30) -- raises NotImplementedError
 instead of silently rendering something else.
 
 `src` is therefore a decoded frame: a float32 (H, W, 3|4) array / CUDA tensor in linear CIE XYZ
-(what `raw_to_linear` returns, raw_conversion.py:33-53), or the path of a `.npy` file holding one.
+(what `raw_to_linear` returns, raw_conversion.py:33-53), LibRaw's uint16 output of the same shape, or -- with a `raw_profile` --
+the uint16 (H, W) Bayer mosaic itself; or the path of a `.npy` file holding one of these.
 """
 
 from __future__ import annotations
@@ -32,6 +35,7 @@ import numpy as np
 from . import _lib, filmstock, geometry, stencils
 from .context import LOG_EPS, LUT3D_SCALE, HipContext
 from .lens import LensProfile
+from .raw import RawProfile
 from . import tiff
 from .jpeg_stream import ICC_OVERHEAD, MARKER_MAX, XMP_NAMESPACE, JpegBandSink, JpegStaging, deliver, metadata_segments
 from .results import ResultBuffers
@@ -46,6 +50,8 @@ def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canv
     """Why a phase-1 payload cannot stream through the pipeline in row bands, or None (its render's stages have the last word:
     plan_bands).  `shape`, `dtype`: of its frame as a tensor (_payload_tensor: "torch.float32", or "torch.int16" for uint16)."""
     is_u16 = dtype == "torch.int16"  # LibRaw's 16-bit output: converted band by band on the device (raw_conversion.py:50-52)
+    if payload.get("demosaic"):
+        return _DEMOSAIC_REJECTED
     if payload.get("lens"):
         return _LENS_REJECTED
     if (payload.get("warp") or payload.get("resize_to") or payload.get("upscale_to") or payload.get("chroma_nr")
@@ -61,11 +67,14 @@ def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canv
     return None
 
 
-def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="No", highlight_burn=0.0, lens=False):
+def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="No", highlight_burn=0.0, lens=False, demosaic=False):
     """Why process(src, cache=False) renders a frame in one piece before it extracts its payload (stream_rejection and plan_bands
-    come after that), or None.  lens: the call corrects the lens (lens_correction with a lens_profile)."""
+    come after that), or None.  lens: the call corrects the lens (lens_correction with a lens_profile); demosaic: its source is a
+    Bayer mosaic (raw_profile)."""
     if stream_bands <= 1:
         return f"stream_bands = {stream_bands}"
+    if demosaic:
+        return _DEMOSAIC_REJECTED
     if lens:
         return _LENS_REJECTED
     if not isinstance(src, np.ndarray):
@@ -78,6 +87,8 @@ def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="
     return None
 
 
+_DEMOSAIC_REJECTED = ("the demosaic step (raw_profile): the mosaic is demosaiced whole on the device before the pipeline; its row "
+                      "contract (r2f_demosaic_u16) is not streamed yet")
 _LENS_REJECTED = "the lens step (lens_profile): its gather reads the whole frame, which a row band does not hold"
 
 
@@ -375,7 +386,7 @@ class HipProcessor:
     def extract_image_data_cpu(self, src, cam=None, lens=None, lens_correction=True, frame_width=36, frame_height=24,
                                rotation=0.0, zoom=1.0, rotate_times=0, flip=False, resolution=None, half_size=True,
                                cache=True, chroma_nr=0, max_scale=400.0, canvas_mode="No", canvas_scale=1.0,
-                               canvas_ratio=1.0, exposure=None, metadata=None, lens_profile=None, **kwargs):
+                               canvas_ratio=1.0, exposure=None, metadata=None, lens_profile=None, raw_profile=None, **kwargs):
         """PHASE 1 of the two-phase batch API (gpu_processor.py:715-783): pure host work, touches
         no instance state.  Returns the same payload dict; `image_array` is (H, W, 4) float32 ((H, W, 3) with payload_alpha=False).
         exposure="device" (a uint16 frame): no pass over the frame here.  `image_array` is then the WHOLE decoded frame -- the caller's
@@ -387,8 +398,16 @@ class HipProcessor:
         corrects before any crop, so `image_array` stays the WHOLE frame and the payload gains `lens`: the r2f_lens_params of the
         frame's size, the `window` (row0, col0, rows, cols) of the corrected frame the aspect crop keeps (with the zoom crop when
         there is no rotation) and the quarter turns still to be applied to it; every crop-derived value (`pipeline_resolution`
-        ...) is that of the same call without a profile.  lens_correction=False ignores the profile."""
+        ...) is that of the same call without a profile.  lens_correction=False ignores the profile.
+        raw_profile (a raw2film_amd.raw.RawProfile): `src` is a Bayer mosaic, uint16 (H, W), demosaiced on the device (include/r2f.h,
+        r2f_demosaic_u16; `half_size` selects the half-size form) into the uint16 frame every other word of this text is about.
+        `image_array` is the mosaic and the payload gains `demosaic`: the r2f_demosaic_params, and the `window` (row0, col0, rows,
+        cols) and quarter turns that the host applies to a decoded frame's array here and the device applies to the demosaiced one.
+        No RGB frame exists on the host, so exposure=None is measured on the device like exposure="device"; where that is refused (a
+        turned or rotated frame) the call needs explicit stops."""
         on_device = exposure_on_device(exposure)
+        if raw_profile is not None and not isinstance(raw_profile, RawProfile):
+            raise ValueError(f"raw_profile must be a raw2film_amd.raw.RawProfile, got {type(raw_profile).__name__}")
         if lens_profile is not None and not isinstance(lens_profile, LensProfile):
             raise ValueError(f"lens_profile must be a raw2film_amd.lens.LensProfile, got {type(lens_profile).__name__}")
         if lens_correction and cam is not None and lens is not None:
@@ -400,7 +419,18 @@ class HipProcessor:
         # _internal (load_image_texture: the payload never leaves this object): no alpha plane, and the clamp of
         # gpu_processor.py:275 runs on the device after the upload instead of as a 12 B/px pass over host memory
         internal = bool(kwargs.get("_internal"))
-        image = self._load_decoded(src, clip=not internal)
+        image = self._load_decoded(src, clip=not internal, mosaic=raw_profile is not None)
+        mosaic = demosaic_step = None
+        if raw_profile is not None:
+            mosaic = image
+            demosaic_step = {"params": raw_profile.plan(mosaic.shape[0], mosaic.shape[1], half_size), "window": None, "rotate_times": 0}
+            # what follows plans the crops of the demosaiced frame: an array of its shape and type stands in for it (no memory)
+            image = np.broadcast_to(np.uint16(0), (demosaic_step["params"].out_h, demosaic_step["params"].out_w, 3))
+            if exposure is None or on_device:
+                if rotation or int(rotate_times) % 4:
+                    raise ValueError(f"rotation = {rotation!r}, rotate_times = {rotate_times!r}: a turned or rotated frame is measured on "
+                                     "the host, and a mosaic (raw_profile) has no RGB frame there: pass the exposure in stops")
+                on_device = True
         if lens_correction and lens_profile is not None:
             lens_step = {"params": lens_profile.plan(image.shape[0], image.shape[1]), "window": None, "rotate_times": 0}
         u16_factor = u16_window = exposure_root = exposure_rejected = None
@@ -437,6 +467,8 @@ class HipProcessor:
                 lens_step["window"] = (r0, c0, nr, nc)  # (the warp then reads the corrected aspect crop)
             else:
                 image = image[r0:r0 + nr, c0:c0 + nc]
+                if demosaic_step is not None:
+                    demosaic_step["window"] = (r0, c0, nr, nc)
             m_inv, (wr0, wc0, wnr, wnc) = geometry.rotation_plan(nr, nc, rotation)
             zr0, zc0, znr, znc = geometry.crop_box(wnr, wnc, zoom, aspect, False)
             if znr <= 0 or znc <= 0:
@@ -452,6 +484,12 @@ class HipProcessor:
             zr0, zc0, znr, znc = geometry.crop_box(nr, nc, zoom, aspect, False)
             lens_step["window"], lens_step["rotate_times"] = (r0 + zr0, c0 + zc0, znr, znc), int(rotate_times) % 4
             h, w = (znc, znr) if lens_step["rotate_times"] % 2 else (znr, znc)
+        elif demosaic_step is not None:
+            # crop_to_frame's boxes and quarter turns, applied to the demosaiced frame on the device
+            r0, c0, nr, nc = geometry.crop_box(image.shape[0], image.shape[1], 1, aspect, flip)
+            zr0, zc0, znr, znc = geometry.crop_box(nr, nc, zoom, aspect, False)
+            demosaic_step["window"], demosaic_step["rotate_times"] = (r0 + zr0, c0 + zc0, znr, znc), int(rotate_times) % 4
+            h, w = (znc, znr) if demosaic_step["rotate_times"] % 2 else (znr, znc)
         else:
             # aspect crop / zoom / quarter turns: index arithmetic of raw_conversion.crop_rotate_zoom (raw_conversion.py:56-72)
             image = geometry.crop_to_frame(image, frame_width, frame_height, zoom, rotate_times, flip)
@@ -488,7 +526,9 @@ class HipProcessor:
             res, _, _ = geometry.canvas_layout((out_h, out_w), canvas_mode, canvas_scale, canvas_ratio)
             canvas_res = (res[1], res[0])
         alpha = getattr(self, "payload_alpha", True) and not internal
-        if u16_window is not None:
+        if demosaic_step is not None:
+            image = np.ascontiguousarray(mosaic)  # (the array itself when it is contiguous)
+        elif u16_window is not None:
             image = np.ascontiguousarray(image)  # (the array itself when it is contiguous; a fourth channel is dropped on the device)
         elif u16_factor is not None:
             image = np.ascontiguousarray(image[..., :3])
@@ -517,10 +557,11 @@ class HipProcessor:
             "warp": warp,  # free rotation still to be applied (first of the device pre-path steps), or None
             "upscale_to": upscale_to,  # (rows, cols) the rendered uint8 frame is LANCZOS4-scaled back into, or None
             **({"lens": lens_step} if lens_step is not None else {}),  # the lens step (first of the device pre-path steps)
+            **({"demosaic": demosaic_step} if demosaic_step is not None else {}),  # `image_array` is a Bayer mosaic (ahead of all)
         }
 
     @staticmethod
-    def _load_decoded(src, clip=True):
+    def _load_decoded(src, clip=True, mosaic=False):
         if isinstance(src, np.ndarray):
             image = src
         elif isinstance(src, str) and src.lower().endswith(".npy"):
@@ -532,8 +573,13 @@ class HipProcessor:
             )
         else:
             raise TypeError(f"unsupported src type {type(src)!r}")
+        if mosaic:
+            if image.ndim != 2 or image.dtype != np.uint16:
+                raise ValueError(f"with a raw_profile the source is a Bayer mosaic, uint16 (H, W); got {image.dtype} {image.shape}")
+            return image
         if image.ndim != 3 or image.shape[2] not in (3, 4):
-            raise ValueError(f"decoded frame must be (H, W, 3|4), got {image.shape}")
+            raise ValueError(f"decoded frame must be (H, W, 3|4), got {image.shape}" +
+                             (" (a Bayer mosaic needs its raw_profile)" if image.ndim == 2 else ""))
         if image.dtype == np.uint16:  # LibRaw's 16-bit output: converted on the device (decode.py, r2f_decode_u16)
             return image
         image = np.asarray(image, dtype=np.float32)
@@ -549,7 +595,8 @@ class HipProcessor:
                 canvas_ratio=1.0, halation_intensity=1.0, halation=True, halation_size=1.0, halation_green_factor=0.4,
                 sharpness=True, sharpening_strength=0.0, sharpening_sigma=1.0, chroma_nr=0, grain=2,
                 highlight_burn=0.0, burn_scale=50.0, half_size=True, cache=True, color_masking=None, max_scale=400.0,
-                seed=None, exposure=None, metadata=None, src_version=None, output_bits=8, lens_profile=None, **_):
+                seed=None, exposure=None, metadata=None, src_version=None, output_bits=8, lens_profile=None, raw_profile=None,
+                **_):
         """Load (decoded) frame and render it: np.uint8 (H, W, 3), like cpu_processor.py:414 -- including the CPU processor's
         last step, resolution_scaling of the finished (canvas-framed) frame to the requested resolution (cpu_processor.py:411-412).
         With `dst_texture` (a uint8 (h, w, 4) CUDA tensor standing in for the preview widget's wgpu texture) the call behaves
@@ -568,7 +615,10 @@ class HipProcessor:
         the final INTER_AREA as cv.resize applies them to uint16, the result lent from a pinned pool of its own and a large
         cache=False frame streamed in row bands exactly where an 8-bit one is.  Not with dst_texture (RGBA8).
         lens_profile (raw2film_amd.lens.LensProfile) with lens_correction=True: the whole frame is uploaded and corrected on the
-        device before any crop (extract_image_data_cpu); such a frame never streams in row bands."""
+        device before any crop (extract_image_data_cpu); such a frame never streams in row bands.
+        raw_profile (raw2film_amd.raw.RawProfile): `src` is a Bayer mosaic, uint16 (H, W) -- 2 bytes per pixel across PCIe --,
+        demosaiced on the device (`half_size` selects the form) into the uint16 frame the rest of the call reads; it does not
+        stream in row bands either.  exposure=None is then measured on the device (extract_image_data_cpu)."""
         settings = dict(locals())  # every keyword of the signature (the unknown ones in `_` aside), named nowhere else
         exposure_on_device(exposure)  # (any string but "device" raises before any work starts)
         settings["output_bits"] = check_output_bits(output_bits, dst_texture)
@@ -591,7 +641,7 @@ class HipProcessor:
             t_start = time.perf_counter()
         elif (not cache and dst_texture is None
               and host_stream_gate(src, self.stream_bands, rotation, chroma_nr, canvas_mode, highlight_burn,
-                                   bool(lens_correction) and lens_profile is not None) is None):
+                                   bool(lens_correction) and lens_profile is not None, raw_profile is not None) is None):
             # a large host frame that is uploaded for this one render: streamed through the pipeline in row bands while it arrives
             res = self._process_streamed(src, negative_film, grain_size, grain_sigma, load, settings)
             if res is not None:
@@ -620,7 +670,7 @@ class HipProcessor:
     def load_image_texture(self, src, cam=None, lens=None, lens_correction=True, frame_width=36, frame_height=24, rotation=0.0,
                            zoom=1.0, rotate_times=0, flip=False, resolution=None, half_size=True, cache=True, chroma_nr=0,
                            max_scale=400.0, canvas_mode="No", canvas_scale=1.0, canvas_ratio=1.0, exposure=None, metadata=None,
-                           src_version=None, lens_profile=None):
+                           src_version=None, lens_profile=None, raw_profile=None):
         """GpuProcessor.load_image_texture (gpu_processor.py:655-719): prepare and upload the frame unless the load parameters
         are those of the frame that is already on the device.  A path compares by value like upstream's `src`.  An array
         compares by identity AND by a fingerprint of its content (shape, dtype, address, a checksum of up to 32 evenly spaced
@@ -645,7 +695,7 @@ class HipProcessor:
             "frame_width": frame_width, "frame_height": frame_height, "rotation": rotation, "zoom": zoom,
             "rotate_times": rotate_times, "flip": flip, "resolution": resolution, "half_size": half_size, "chroma_nr": chroma_nr,
             "max_scale": max_scale, "canvas_mode": canvas_mode, "canvas_scale": canvas_scale, "canvas_ratio": canvas_ratio,
-            "exposure": exposure, "metadata": metadata, "lens_profile": lens_profile,
+            "exposure": exposure, "metadata": metadata, "lens_profile": lens_profile, "raw_profile": raw_profile,
         }
         held = getattr(self, "_texture_src", None)
         same_src = isinstance(src, str) or (held is not None and held() is src)
@@ -662,7 +712,7 @@ class HipProcessor:
             cpu_payload = self.extract_image_data_cpu(
                 src, cam, lens, lens_correction, frame_width, frame_height, rotation, zoom, rotate_times, flip, resolution,
                 half_size, cache, chroma_nr, max_scale, canvas_mode, canvas_scale, canvas_ratio, exposure=exposure, metadata=metadata,
-                lens_profile=lens_profile, _internal=True,
+                lens_profile=lens_profile, raw_profile=raw_profile, _internal=True,
             )
         if prof:
             t1 = time.perf_counter()
@@ -869,7 +919,8 @@ class HipProcessor:
                                     ("profile_stages is on" if getattr(self, "profile_stages", False) else
                                      host_stream_gate(src, self.stream_bands, settings["rotation"], settings["chroma_nr"],
                                                       settings["canvas_mode"], settings["highlight_burn"],
-                                                      bool(settings["lens_correction"]) and settings["lens_profile"] is not None)))
+                                                      bool(settings["lens_correction"]) and settings["lens_profile"] is not None,
+                                                      settings["raw_profile"] is not None)))
         return settings, load, self.extract_image_data_cpu(src, **load, _internal=True)
 
     def _export_preloaded(self, what, settings, stream, early=()) -> bool:
@@ -1297,6 +1348,14 @@ class HipProcessor:
     def _prepare_device_frame(self, image, cpu_payload):
         """The device pre-path on an uploaded payload frame -> (frame, layout) as the pipeline reads it."""
         torch = self._torch
+        demosaic_step = cpu_payload.get("demosaic")
+        if demosaic_step:  # a Bayer mosaic: LibRaw's share of raw_to_linear on the device -> the uint16 frame of the lines below
+            image = self.ctx.demosaic_u16(image.contiguous(), demosaic_step["params"])
+            if demosaic_step["window"] is not None:
+                r0, c0, nr, nc = demosaic_step["window"]
+                image = image[r0:r0 + nr, c0:c0 + nc]
+            if demosaic_step["rotate_times"]:
+                image = torch.rot90(image, demosaic_step["rotate_times"], dims=(0, 1))
         if image.dtype in (torch.int16, torch.uint16):  # a decoded 16-bit frame: raw_conversion.py:50-52 on the device
             if cpu_payload.get("u16_factor") is None:
                 raise ValueError("a uint16 payload needs its exposure factor (`u16_factor`, extract_image_data_cpu sets it)")

@@ -1,0 +1,87 @@
+"""RawProfile: what a RAW file's parser knows of a Bayer frame, for the demosaic on the device.
+
+Upstream has LibRaw do everything behind the file parser (raw_conversion.raw_to_linear, raw_conversion.py:33-53): black / scale,
+demosaic, camera matrix, 16-bit clip.  The parser is third-party input; this module takes its RESULT -- the CFA pattern, the black
+levels, the multipliers, the camera matrix -- and `plan()` turns it into the constants of one frame size (r2f_demosaic_plan).  The
+mosaic itself is the `src` of the call.  The definition of the arithmetic is in include/r2f.h (r2f_demosaic_u16).
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+import math
+import numbers
+from dataclasses import dataclass
+
+from . import _lib
+
+_PATTERNS = {"RGGB": _lib.CFA_RGGB, "BGGR": _lib.CFA_BGGR, "GRBG": _lib.CFA_GRBG, "GBRG": _lib.CFA_GBRG}
+
+
+def _floats(name, values, counts):
+    try:
+        out = tuple(float(v) for v in values)
+    except TypeError:
+        raise ValueError(f"RawProfile.{name} must be {' or '.join(str(n) for n in counts)} numbers, got {values!r}") from None
+    if len(out) not in counts:
+        raise ValueError(f"RawProfile.{name} must be {' or '.join(str(n) for n in counts)} numbers, got {len(out)}")
+    if not all(math.isfinite(v) for v in out):
+        raise ValueError(f"RawProfile.{name} must be finite, got {values!r}")
+    return out
+
+
+@dataclass(frozen=True)
+class RawProfile:
+    """A frozen, hashable record (part of the image cache key, like LensProfile).
+
+    pattern: "RGGB" | "BGGR" | "GRBG" | "GBRG", the colours of the quad at (0, 0) in reading order.
+    black: one level for every site, or 4 per site of the quad (k = (y & 1) * 2 + (x & 1)); integers in [0, 65535].
+    multipliers: (r, g, b), or 4 per site; each in (0, 1024].  They hold the white balance AND the scale to 16 bits.
+    matrix: 3 x 3, rows are the output channels; |entries| <= 64."""
+    pattern: str = "RGGB"
+    black: tuple | float = 0
+    multipliers: tuple = (1.0, 1.0, 1.0)
+    matrix: tuple = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
+
+    def __post_init__(self):
+        if not isinstance(self.pattern, str) or self.pattern not in _PATTERNS:
+            raise ValueError(f"RawProfile.pattern must be one of {sorted(_PATTERNS)}, got {self.pattern!r}")
+        set_ = lambda k, v: object.__setattr__(self, k, v)  # noqa: E731 -- (frozen: normalised to tuples of floats once)
+        black = self.black
+        if isinstance(black, numbers.Real) and not isinstance(black, bool):
+            black = (black,) * 4
+        black = _floats("black", black, (4,))
+        if any(b < 0 or b > 65535 or b != math.floor(b) for b in black):
+            raise ValueError(f"RawProfile.black must be integers in [0, 65535], got {self.black!r}")
+        set_("black", black)
+        mul = _floats("multipliers", self.multipliers, (3, 4))
+        if len(mul) == 3:
+            mul = tuple(mul["RGB".index(c)] for c in self.pattern)
+        if any(not 0 < m <= 1024 for m in mul):
+            raise ValueError(f"RawProfile.multipliers must lie in (0, 1024], got {self.multipliers!r}")
+        set_("multipliers", mul)
+        try:
+            rows = tuple(_floats("matrix", row, (3,)) for row in self.matrix)
+        except TypeError:
+            raise ValueError(f"RawProfile.matrix must be 3 x 3, got {self.matrix!r}") from None
+        if len(rows) != 3:
+            raise ValueError(f"RawProfile.matrix must be 3 x 3, got {len(rows)} rows")
+        if any(abs(v) > 64 for row in rows for v in row):
+            raise ValueError(f"RawProfile.matrix entries must lie in [-64, 64], got {self.matrix!r}")
+        set_("matrix", rows)
+
+    def to_c(self, half_size: bool = False) -> _lib.RawProfile:
+        p = _lib.RawProfile(pattern=_PATTERNS[self.pattern], half_size=int(bool(half_size)))
+        p.black[:] = self.black
+        p.mul[:] = self.multipliers
+        p.matrix[:] = [v for row in self.matrix for v in row]
+        return p
+
+    def plan(self, H: int, W: int, half_size: bool = False) -> _lib.DemosaicParams:
+        """The r2f_demosaic_params of an H x W mosaic (no GPU); ValueError for what the planner refuses (a frame below 2 x 2, an
+        odd side with half_size, a multiplier that rounds to 0 as a float)."""
+        out = _lib.DemosaicParams()
+        profile = self.to_c(half_size)
+        if _lib.load().r2f_demosaic_plan(C.byref(profile), int(H), int(W), C.byref(out)) != _lib.OK:
+            raise ValueError(f"r2f_demosaic_plan refused {self!r} for a {H} x {W} mosaic (half_size={bool(half_size)})")
+        return out
