@@ -24,72 +24,23 @@ from __future__ import annotations
 
 import inspect
 import math
-import operator
 import random
-import sys
 from concurrent.futures import ThreadPoolExecutor
 from typing import Callable, NamedTuple
 
 import numpy as np
 
-from . import _lib, filmstock, geometry, stencils
+from . import _lib, filmstock, geometry, payload as phase1, stencils, tiff
 from .context import LOG_EPS, LUT3D_SCALE, HipContext
-from .lens import LensProfile
-from .raw import RawProfile
-from . import tiff
-from .jpeg_stream import ICC_OVERHEAD, MARKER_MAX, XMP_NAMESPACE, JpegBandSink, JpegStaging, deliver, metadata_segments
+from .jpeg_options import _check_jpeg_image, checked_options
+from .jpeg_stream import JpegBandSink, JpegStaging, deliver
+from .payload import host_stream_gate, stream_rejection
 from .results import ResultBuffers
 
 REC709_TO_XYZ = np.array(  # data.py:128-135
     [[0.4124564, 0.3575761, 0.1804375], [0.2126729, 0.7151522, 0.0721750], [0.0193339, 0.1191920, 0.9503041]],
     dtype=np.float32,
 )
-
-
-def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canvas_mode="No"):
-    """Why a phase-1 payload cannot stream through the pipeline in row bands, or None (its render's stages have the last word:
-    plan_bands).  `shape`, `dtype`: of its frame as a tensor (_payload_tensor: "torch.float32", or "torch.int16" for uint16)."""
-    is_u16 = dtype == "torch.int16"  # LibRaw's 16-bit output: converted band by band on the device (raw_conversion.py:50-52)
-    if payload.get("demosaic"):
-        return _DEMOSAIC_REJECTED
-    if payload.get("lens"):
-        return _LENS_REJECTED
-    if (payload.get("warp") or payload.get("resize_to") or payload.get("upscale_to") or payload.get("chroma_nr")
-            or payload.get("canvas_resolution") or canvas_mode != "No" or on_device or len(shape) != 3
-            or int(shape[2]) not in (3, 4) or math.prod(shape) < (1 << 24) or dtype not in ("torch.float32", "torch.int16")
-            or (payload.get("u16_factor") is None) == is_u16):  # (a uint16 frame comes with its exposure factor, a float one without)
-        return ("a device pre-path, a canvas, or a frame below 16.7 M samples: " + ", ".join(
-            f"{k} = {payload.get(k)!r}" for k in ("warp", "resize_to", "upscale_to", "chroma_nr", "canvas_resolution", "u16_factor",
-                                                  "clip_on_device")) + f", frame {tuple(shape)} {dtype}")
-    fr = payload.get("final_resolution") if final_scaling == "cpu" else None  # (cpu_processor.py:411-412: the final scaling)
-    if fr is not None and (int(fr[0]), int(fr[1])) != (int(shape[0]), int(shape[1])):
-        return f"the finished frame is scaled to {fr}"
-    return None
-
-
-def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="No", highlight_burn=0.0, lens=False, demosaic=False):
-    """Why process(src, cache=False) renders a frame in one piece before it extracts its payload (stream_rejection and plan_bands
-    come after that), or None.  lens: the call corrects the lens (lens_correction with a lens_profile); demosaic: its source is a
-    Bayer mosaic (raw_profile)."""
-    if stream_bands <= 1:
-        return f"stream_bands = {stream_bands}"
-    if demosaic:
-        return _DEMOSAIC_REJECTED
-    if lens:
-        return _LENS_REJECTED
-    if not isinstance(src, np.ndarray):
-        return f"the source is a {type(src).__name__}, not a host array"
-    if src.size < (1 << 24):
-        return f"a frame of {src.size} samples, below 16.7 M"
-    if rotation or chroma_nr or canvas_mode != "No" or highlight_burn:
-        return (f"a device pre-path, a canvas or a highlight burn: rotation = {rotation!r}, chroma_nr = {chroma_nr!r}, "
-                f"canvas_mode = {canvas_mode!r}, highlight_burn = {highlight_burn!r}")
-    return None
-
-
-_DEMOSAIC_REJECTED = ("the demosaic step (raw_profile): the mosaic is demosaiced whole on the device before the pipeline; its row "
-                      "contract (r2f_demosaic_u16) is not streamed yet")
-_LENS_REJECTED = "the lens step (lens_profile): its gather reads the whole frame, which a row band does not hold"
 
 
 def plan_bands(H, flags, ha, ma, bands, taper):
@@ -406,184 +357,64 @@ class HipProcessor:
         No RGB frame exists on the host, so exposure=None is measured on the device like exposure="device"; where that is refused (a
         turned or rotated frame) the call needs explicit stops."""
         on_device = exposure_on_device(exposure)
-        if raw_profile is not None and not isinstance(raw_profile, RawProfile):
-            raise ValueError(f"raw_profile must be a raw2film_amd.raw.RawProfile, got {type(raw_profile).__name__}")
-        if lens_profile is not None and not isinstance(lens_profile, LensProfile):
-            raise ValueError(f"lens_profile must be a raw2film_amd.lens.LensProfile, got {type(lens_profile).__name__}")
-        if lens_correction and cam is not None and lens is not None:
-            # the reference corrects only when both are given (cpu_processor.py:107-108, effects.py:22-30); the lensfun lookup is
-            # not part of the accelerated path, and rendering an uncorrected frame in its place would be a silent difference
-            raise NotImplementedError("lens correction (lensfunpy, effects.py:22-43) is outside the accelerated path: "
-                                      "pass lens_correction=False or no cam / lens (the calibration's numbers go in lens_profile)")
-        lens_step = None  # the payload's `lens`, filled in once the frame's size is known
+        phase1.check_profiles(raw_profile, lens_profile, lens_correction, cam, lens)
         # _internal (load_image_texture: the payload never leaves this object): no alpha plane, and the clamp of
         # gpu_processor.py:275 runs on the device after the upload instead of as a 12 B/px pass over host memory
         internal = bool(kwargs.get("_internal"))
-        image = self._load_decoded(src, clip=not internal, mosaic=raw_profile is not None)
-        mosaic = demosaic_step = None
-        if raw_profile is not None:
-            mosaic = image
-            demosaic_step = {"params": raw_profile.plan(mosaic.shape[0], mosaic.shape[1], half_size), "window": None, "rotate_times": 0}
-            # what follows plans the crops of the demosaiced frame: an array of its shape and type stands in for it (no memory)
-            image = np.broadcast_to(np.uint16(0), (demosaic_step["params"].out_h, demosaic_step["params"].out_w, 3))
-            if exposure is None or on_device:
-                if rotation or int(rotate_times) % 4:
-                    raise ValueError(f"rotation = {rotation!r}, rotate_times = {rotate_times!r}: a turned or rotated frame is measured on "
-                                     "the host, and a mosaic (raw_profile) has no RGB frame there: pass the exposure in stops")
-                on_device = True
+        image = phase1.load_decoded(src, clip=not internal, mosaic=raw_profile is not None)
+        rows, cols, is_u16 = image.shape[0], image.shape[1], image.dtype == np.uint16
+        demosaic_params = lens_params = None
+        if raw_profile is not None:  # the crops are those of the demosaiced frame, which is uint16
+            demosaic_params = raw_profile.plan(rows, cols, half_size)
+            rows, cols = demosaic_params.out_h, demosaic_params.out_w
+        on_device, exposure, exposure_rejected = phase1.exposure_mode(exposure, on_device, is_u16, raw_profile is not None, rotation,
+                                                                      rotate_times)
         if lens_correction and lens_profile is not None:
-            lens_step = {"params": lens_profile.plan(image.shape[0], image.shape[1]), "window": None, "rotate_times": 0}
-        u16_factor = u16_window = exposure_root = exposure_rejected = None
-        if image.dtype == np.uint16 and on_device and (rotation or int(rotate_times) % 4):
-            exposure_rejected = (f"rotation = {rotation!r}, rotate_times = {rotate_times!r}: a turned or rotated frame is measured on "
-                                 "the host")
-            on_device, exposure = False, None
-        if image.dtype == np.uint16 and on_device:
+            lens_params = lens_profile.plan(rows, cols)
+        u16_factor = exposure_root = None
+        if is_u16:
             from . import decode
 
-            # the statistic is the whole frame's (upstream measures before any crop), so the whole frame goes up; the crops become
-            # a window the device decodes (raw_conversion.crop_rotate_zoom's index arithmetic, raw_conversion.py:56-72)
-            r0, c0, nr, nc = geometry.crop_box(image.shape[0], image.shape[1], 1, frame_width / frame_height, flip)
-            zr0, zc0, znr, znc = geometry.crop_box(nr, nc, zoom, frame_width / frame_height, False)
-            u16_window = (r0 + zr0, c0 + zc0, znr, znc)
-            if lens_step is not None:  # the frame is decoded whole: the lens step reads all of it and cuts this window itself
-                lens_step["window"], u16_window = u16_window, (0, 0, image.shape[0], image.shape[1])
-            u16_factor, exposure_root = DEVICE_EXPOSURE, float(decode.exposure_root(metadata))
-        elif image.dtype == np.uint16:
-            # raw_to_linear's tail (raw_conversion.py:50-52) moves to the device: the auto exposure is measured here, on the
-            # whole decoded frame like upstream (before any crop), unless the caller brings the stops along
-            from . import decode
-
-            stops = decode.auto_exposure(image, metadata=metadata) if exposure is None else float(exposure)
-            u16_factor = float(decode.exposure_factor(stops))
-        aspect = frame_width / frame_height
-        warp = None
-        if rotation:
-            # raw_conversion.crop_rotate_zoom (raw_conversion.py:56-72) with the interpolating part deferred to the device:
-            # aspect crop here (a view), then phase 2 warps straight into the window that effects.rotate's centred crop
-            # and the zoom crop keep, and applies the quarter turns
-            r0, c0, nr, nc = geometry.crop_box(image.shape[0], image.shape[1], 1, aspect, flip)
-            if lens_step is not None:
-                lens_step["window"] = (r0, c0, nr, nc)  # (the warp then reads the corrected aspect crop)
+            if on_device:
+                # the statistic is the whole frame's (upstream measures before any crop), so the whole frame goes up and the crops
+                # become a window the device decodes
+                u16_factor, exposure_root = DEVICE_EXPOSURE, float(decode.exposure_root(metadata))
             else:
-                image = image[r0:r0 + nr, c0:c0 + nc]
-                if demosaic_step is not None:
-                    demosaic_step["window"] = (r0, c0, nr, nc)
-            m_inv, (wr0, wc0, wnr, wnc) = geometry.rotation_plan(nr, nc, rotation)
-            zr0, zc0, znr, znc = geometry.crop_box(wnr, wnc, zoom, aspect, False)
-            if znr <= 0 or znc <= 0:
-                raise ValueError(f"rotation {rotation} / zoom {zoom} leave an empty frame")
-            warp = {"m_dst_to_src": m_inv, "window": (wr0 + zr0, wc0 + zc0, znr, znc), "rotate_times": int(rotate_times) % 4}
-            h, w = (znc, znr) if warp["rotate_times"] % 2 else (znr, znc)
-        elif u16_window is not None:
-            # (the frame stays whole: the window is cut on the device)
-            h, w = (lens_step["window"] if lens_step is not None else u16_window)[2:]
-        elif lens_step is not None:
-            # crop_to_frame's boxes as a window of the corrected frame; its quarter turns follow the lens step on the device
-            r0, c0, nr, nc = geometry.crop_box(image.shape[0], image.shape[1], 1, aspect, flip)
-            zr0, zc0, znr, znc = geometry.crop_box(nr, nc, zoom, aspect, False)
-            lens_step["window"], lens_step["rotate_times"] = (r0 + zr0, c0 + zc0, znr, znc), int(rotate_times) % 4
-            h, w = (znc, znr) if lens_step["rotate_times"] % 2 else (znr, znc)
-        elif demosaic_step is not None:
-            # crop_to_frame's boxes and quarter turns, applied to the demosaiced frame on the device
-            r0, c0, nr, nc = geometry.crop_box(image.shape[0], image.shape[1], 1, aspect, flip)
-            zr0, zc0, znr, znc = geometry.crop_box(nr, nc, zoom, aspect, False)
-            demosaic_step["window"], demosaic_step["rotate_times"] = (r0 + zr0, c0 + zc0, znr, znc), int(rotate_times) % 4
-            h, w = (znc, znr) if demosaic_step["rotate_times"] % 2 else (znr, znc)
-        else:
-            # aspect crop / zoom / quarter turns: index arithmetic of raw_conversion.crop_rotate_zoom (raw_conversion.py:56-72)
-            image = geometry.crop_to_frame(image, frame_width, frame_height, zoom, rotate_times, flip)
-            h, w = image.shape[:2]
-        # cpu_processor.py:119-134: without a preview resolution the frame's own size is the target; a target finer than
-        # `max_scale` px/mm is rendered at max_scale and scaled back up at the very end (cpu_processor.py:411-412)
-        if resolution is None and max_scale is not None:
-            resolution = (h, w)
-        resize_to, upscale_to = None, None
-        # what CpuProcessor.load_image returns as `orig_resolution` (cpu_processor.py:122) and process() hands to the final
-        # resolution_scaling (cpu_processor.py:411-412)
-        final_resolution = (int(resolution[0]), int(resolution[1])) if resolution is not None else None
-        scale_factor = 1.0
-        if resolution is not None:
-            resolution = (int(resolution[0]), int(resolution[1]))
-            scale = max(resolution) / max(frame_width, frame_height)
-            if max_scale is not None and scale > max_scale:
-                scale_factor = max_scale / scale
-                upscale_to = resolution
-                resolution = tuple(round(x * scale_factor) for x in resolution)
-            # utils.resolution_scaling (utils.py:226-244), applied on the device in phase 2
-            factor = min(resolution[0] / h, resolution[1] / w)
-            if factor != 1:
-                # cv.resize(dsize=(round(w f), round(h f))): INTER_AREA down, INTER_LANCZOS4 up (a preview larger than the frame)
-                resize_to = (round(h * factor), round(w * factor))
-                h, w = resize_to
-        # gpu_processor.py:764: the size the frame has once it is back from the max_scale pipeline -- the UN-shrunk output size,
-        # which is also what the canvas is laid out for (:767-771), not the pipeline's
-        out_h, out_w = (round(x / scale_factor) for x in (h, w))
-        if upscale_to is not None and min(upscale_to[0] / h, upscale_to[1] / w) <= 1:
-            upscale_to = None  # (the uint8 result goes back up with LANCZOS4 only when that enlarges it)
-        canvas_res = None
-        if canvas_mode != "No":  # gpu_processor.py:767-771
-            res, _, _ = geometry.canvas_layout((out_h, out_w), canvas_mode, canvas_scale, canvas_ratio)
-            canvas_res = (res[1], res[0])
-        alpha = getattr(self, "payload_alpha", True) and not internal
-        if demosaic_step is not None:
-            image = np.ascontiguousarray(mosaic)  # (the array itself when it is contiguous)
-        elif u16_window is not None:
-            image = np.ascontiguousarray(image)  # (the array itself when it is contiguous; a fourth channel is dropped on the device)
-        elif u16_factor is not None:
-            image = np.ascontiguousarray(image[..., :3])
-        elif image.shape[2] == 3 and alpha:
-            image = np.concatenate([image, np.ones_like(image[..., :1])], axis=-1)  # gpu_processor.py:765
-        elif image.shape[2] == 4 and not alpha:
-            image = image[..., :3]
-        if u16_factor is None:
-            image = np.ascontiguousarray(image, dtype=np.float32)
+                # raw_to_linear's tail (raw_conversion.py:50-52) moves to the device: the auto exposure is measured here, on the
+                # whole decoded frame like upstream (before any crop), unless the caller brings the stops along
+                stops = decode.auto_exposure(image, metadata=metadata) if exposure is None else float(exposure)
+                u16_factor = float(decode.exposure_factor(stops))
+        crops = phase1.plan_crops(rows, cols, is_u16, frame_width / frame_height, flip, zoom, rotation, rotate_times, on_device,
+                                  lens_params is not None, demosaic_params is not None)
+        if crops.host is not None:
+            image = phase1.cut_and_turn(image, **crops.host)
+        res = phase1.plan_resolution(*crops.size, frame_width, frame_height, resolution, max_scale, canvas_mode, canvas_scale,
+                                     canvas_ratio)
+        image = phase1.pack_image(image, demosaic_params is not None or crops.u16_window is not None, is_u16,
+                                  getattr(self, "payload_alpha", True) and not internal)
         return {
             "image_array": image,
             # float32 exposure factor of a uint16 payload (converted on the device), else None; "device": measured there too, on the
             # whole frame `image_array` then is, of which the pipeline takes `u16_window` (calc_exposure's exponent: `exposure_root`)
             "u16_factor": u16_factor,
-            "u16_window": u16_window,
+            "u16_window": crops.u16_window,
             "exposure_root": exposure_root,
             "exposure_rejected": exposure_rejected,  # why exposure="device" was measured on the host after all, or None
             "clip_on_device": internal and u16_factor is None,  # the float frame still has to be clamped to [0, 65504]
-            "final_resolution": final_resolution,
-            "output_resolution": (out_w, out_h),
-            "canvas_resolution": canvas_res,
-            "pipeline_resolution": (w, h),
+            "final_resolution": res.final_resolution,
+            "output_resolution": res.output_resolution,
+            "canvas_resolution": res.canvas_resolution,
+            "pipeline_resolution": res.pipeline_resolution,
             # upstream filters on the host here (gpu_processor.py:750-751); this backend filters on the device in phase 2
             "chroma_nr": int(chroma_nr),
-            "resize_to": resize_to,  # (rows, cols) of the INTER_AREA down-scale still to be applied, or None
-            "warp": warp,  # free rotation still to be applied (first of the device pre-path steps), or None
-            "upscale_to": upscale_to,  # (rows, cols) the rendered uint8 frame is LANCZOS4-scaled back into, or None
-            **({"lens": lens_step} if lens_step is not None else {}),  # the lens step (first of the device pre-path steps)
-            **({"demosaic": demosaic_step} if demosaic_step is not None else {}),  # `image_array` is a Bayer mosaic (ahead of all)
+            "resize_to": res.resize_to,  # (rows, cols) of the INTER_AREA down-scale still to be applied, or None
+            "warp": crops.warp,  # free rotation still to be applied (first of the device pre-path steps), or None
+            "upscale_to": res.upscale_to,  # (rows, cols) the rendered uint8 frame is LANCZOS4-scaled back into, or None
+            # the lens step (first of the device pre-path steps)
+            **({"lens": {"params": lens_params, **crops.lens}} if lens_params is not None else {}),
+            # `image_array` is a Bayer mosaic (ahead of all)
+            **({"demosaic": {"params": demosaic_params, **crops.demosaic}} if demosaic_params is not None else {}),
         }
-
-    @staticmethod
-    def _load_decoded(src, clip=True, mosaic=False):
-        if isinstance(src, np.ndarray):
-            image = src
-        elif isinstance(src, str) and src.lower().endswith(".npy"):
-            image = np.load(src)
-        elif isinstance(src, str):
-            raise NotImplementedError(
-                f"{src!r}: RAW decoding (LibRaw/rawpy, raw_conversion.py:33-53) is outside the accelerated path; "
-                "pass the decoded linear-XYZ frame (array or .npy)"
-            )
-        else:
-            raise TypeError(f"unsupported src type {type(src)!r}")
-        if mosaic:
-            if image.ndim != 2 or image.dtype != np.uint16:
-                raise ValueError(f"with a raw_profile the source is a Bayer mosaic, uint16 (H, W); got {image.dtype} {image.shape}")
-            return image
-        if image.ndim != 3 or image.shape[2] not in (3, 4):
-            raise ValueError(f"decoded frame must be (H, W, 3|4), got {image.shape}" +
-                             (" (a Bayer mosaic needs its raw_profile)" if image.ndim == 2 else ""))
-        if image.dtype == np.uint16:  # LibRaw's 16-bit output: converted on the device (decode.py, r2f_decode_u16)
-            return image
-        image = np.asarray(image, dtype=np.float32)
-        return np.clip(image, 0, 65504) if clip else image  # gpu_processor.py:275 (clip=False: clamped after the upload)
 
     # ------------------------------------------------------------------ the operator surface
     def process(self, src, negative_film, grain_size, grain_sigma, dst_texture=None, histogram_texture=None,
@@ -639,9 +470,7 @@ class HipProcessor:
 
             self._torch.cuda.synchronize(self.device)
             t_start = time.perf_counter()
-        elif (not cache and dst_texture is None
-              and host_stream_gate(src, self.stream_bands, rotation, chroma_nr, canvas_mode, highlight_burn,
-                                   bool(lens_correction) and lens_profile is not None, raw_profile is not None) is None):
+        elif not cache and dst_texture is None and self._host_stream_gate(src, settings) is None:
             # a large host frame that is uploaded for this one render: streamed through the pipeline in row bands while it arrives
             res = self._process_streamed(src, negative_film, grain_size, grain_sigma, load, settings)
             if res is not None:
@@ -678,6 +507,7 @@ class HipProcessor:
         rows is not seen.  `src_version` (any hashable token that the caller changes with the content) replaces the
         checksum and saves its ~5 MB pass per call; `cache=False` always uploads.  The processor holds the array by weak reference
         only (upstream's cache never sees arrays: this is this backend's own rule, kept conservative)."""
+        load = {k: v for k, v in locals().items() if k in _LOAD_KEYWORDS}  # every keyword of the signature, named nowhere else
         if isinstance(src, str):
             src_key = src
         elif src_version is not None:
@@ -689,14 +519,8 @@ class HipProcessor:
             src_key = None
         else:
             src_key = self._array_fingerprint(src)
-        new_param_dict = {
-            "src": src_key, "cam": cam, "lens": lens,
-            "lens_correction": lens_correction,
-            "frame_width": frame_width, "frame_height": frame_height, "rotation": rotation, "zoom": zoom,
-            "rotate_times": rotate_times, "flip": flip, "resolution": resolution, "half_size": half_size, "chroma_nr": chroma_nr,
-            "max_scale": max_scale, "canvas_mode": canvas_mode, "canvas_scale": canvas_scale, "canvas_ratio": canvas_ratio,
-            "exposure": exposure, "metadata": metadata, "lens_profile": lens_profile, "raw_profile": raw_profile,
-        }
+        # (`cache` and `src_version` decide how the frame is compared, above; they are not part of what it is compared by)
+        new_param_dict = {"src": src_key, **{k: v for k, v in load.items() if k not in ("cache", "src_version")}}
         held = getattr(self, "_texture_src", None)
         same_src = isinstance(src, str) or (held is not None and held() is src)
         if cache and same_src and getattr(self, "_texture", None) is not None and new_param_dict == getattr(self, "image_param_dict", None):
@@ -709,11 +533,7 @@ class HipProcessor:
         cpu_payload = getattr(self, "_stash_payload", None)  # (made a moment ago by _process_streamed for a frame that did not qualify)
         self._stash_payload = None
         if cpu_payload is None:
-            cpu_payload = self.extract_image_data_cpu(
-                src, cam, lens, lens_correction, frame_width, frame_height, rotation, zoom, rotate_times, flip, resolution,
-                half_size, cache, chroma_nr, max_scale, canvas_mode, canvas_scale, canvas_ratio, exposure=exposure, metadata=metadata,
-                lens_profile=lens_profile, raw_profile=raw_profile, _internal=True,
-            )
+            cpu_payload = self.extract_image_data_cpu(src, **load, _internal=True)
         if prof:
             t1 = time.perf_counter()
         self.prepare_gpu_textures(cpu_payload)
@@ -831,10 +651,8 @@ class HipProcessor:
         dots per inch when both are positive.  restart_marker_blocks: MCUs per restart interval, 0 .. 65535;
         restart_marker_rows: MCU rows per interval (it wins over blocks; the interval is clamped to 65535 MCUs).  A restart
         interval with progressive=True raises ValueError: baseline only."""
-        q = _jpeg_quality(quality)
-        opts = _jpeg_options(subsampling, optimize, exif)
-        prog = _jpeg_progressive(progressive)
-        extras = _jpeg_extras(icc_profile, xmp, comment, dpi, restart_marker_blocks, restart_marker_rows, prog)
+        o = checked_options(quality, subsampling, optimize, exif, progressive, icc_profile, xmp, comment, dpi, restart_marker_blocks,
+                            restart_marker_rows)
         torch = self._torch
         if isinstance(image, np.ndarray):
             _check_jpeg_image(image.dtype == np.uint8, image.shape, image.dtype)
@@ -845,7 +663,7 @@ class HipProcessor:
                 image = image.to(self.device)
         else:
             raise ValueError(f"encode_jpeg: expected a uint8 (H, W, 3) NumPy array or torch tensor, got {type(image).__name__}")
-        return self._encode_device(image, q, *opts, progressive=prog, extras=extras)
+        return self._encode_device(image, o)
 
     def process_jpeg(self, src, negative_film, grain_size, grain_sigma, quality=100, stream=False, file=None, *, subsampling=-1,
                      optimize=False, exif=b"", progressive=False, icc_profile=b"", xmp=b"", comment=b"", dpi=(0, 0),
@@ -866,20 +684,17 @@ class HipProcessor:
         encode_jpeg) needs the whole frame for every scan: the same.  icc_profile, xmp, comment, dpi, restart_marker_blocks,
         restart_marker_rows: as in encode_jpeg; they stream (the segments are written ahead of the first scan byte, and a
         restart interval may straddle bands)."""
-        q = _jpeg_quality(quality)
-        opts = _jpeg_options(subsampling, optimize, exif)
-        prog = _jpeg_progressive(progressive)
-        extras = _jpeg_extras(icc_profile, xmp, comment, dpi, restart_marker_blocks, restart_marker_rows, prog)
+        o = checked_options(quality, subsampling, optimize, exif, progressive, icc_profile, xmp, comment, dpi, restart_marker_blocks,
+                            restart_marker_rows)
         exposure_on_device(settings.get("exposure"))
         self.exposure_rejected = None
-        settings, _, payload = self._export_frame("process_jpeg", src, negative_film, grain_size, grain_sigma, settings, stream,
-                                                  (_PROGRESSIVE_REJECTED if prog else None, _OPTIMIZE_REJECTED if opts[1] else None))
+        settings, _, payload = self._export_frame("process_jpeg", src, negative_film, grain_size, grain_sigma, settings, stream, o.early)
         if stream and self.stream_rejected is None:
-            res = self._stream_jpeg(payload, negative_film, grain_size, grain_sigma, "cpu", q, file, settings, opts, extras)
+            res = self._stream_jpeg(payload, negative_film, grain_size, grain_sigma, "cpu", file, settings, o)
             if res is not None:
                 return res
         out_u8 = self._render_export(payload, negative_film, grain_size, grain_sigma, "cpu", settings)
-        return deliver(self._encode_device(out_u8, q, *opts, progressive=prog, extras=extras), file)
+        return deliver(self._encode_device(out_u8, o), file)
 
     def process_preloaded_jpeg(self, cpu_payload, negative_film, grain_size, grain_sigma, quality=100, final_scaling="gpu",
                                stream=False, file=None, *, subsampling=-1, optimize=False, exif=b"", progressive=False,
@@ -890,18 +705,15 @@ class HipProcessor:
         process_preloaded(cpu_payload, final_scaling=..., ...)'s pixels, and a payload process_preloaded streams in row bands is
         encoded band by band as in process_jpeg (else `stream_rejected` says why not).  file, subsampling, optimize, exif,
         progressive, icc_profile, xmp, comment, dpi, restart_marker_blocks, restart_marker_rows: see process_jpeg."""
-        q = _jpeg_quality(quality)
-        opts = _jpeg_options(subsampling, optimize, exif)
-        prog = _jpeg_progressive(progressive)
-        extras = _jpeg_extras(icc_profile, xmp, comment, dpi, restart_marker_blocks, restart_marker_rows, prog)
+        o = checked_options(quality, subsampling, optimize, exif, progressive, icc_profile, xmp, comment, dpi, restart_marker_blocks,
+                            restart_marker_rows)
         self.exposure_rejected = None
-        if self._export_preloaded("process_preloaded_jpeg", settings, stream,
-                                  (_PROGRESSIVE_REJECTED if prog else None, _OPTIMIZE_REJECTED if opts[1] else None)):
-            res = self._stream_jpeg(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, q, file, settings, opts, extras)
+        if self._export_preloaded("process_preloaded_jpeg", settings, stream, o.early):
+            res = self._stream_jpeg(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, file, settings, o)
             if res is not None:
                 return res
         out_u8 = self._render_export(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, settings)
-        return deliver(self._encode_device(out_u8, q, *opts, progressive=prog, extras=extras), file)
+        return deliver(self._encode_device(out_u8, o), file)
 
     def _export_frame(self, what, src, negative_film, grain_size, grain_sigma, settings, stream, early=()):
         """The prologue of an export of `src` (process_jpeg, process_tiff; `what` names it in messages): no textures, then
@@ -917,11 +729,14 @@ class HipProcessor:
         if stream:
             self.stream_rejected = (next((why for why in early if why), None) or
                                     ("profile_stages is on" if getattr(self, "profile_stages", False) else
-                                     host_stream_gate(src, self.stream_bands, settings["rotation"], settings["chroma_nr"],
-                                                      settings["canvas_mode"], settings["highlight_burn"],
-                                                      bool(settings["lens_correction"]) and settings["lens_profile"] is not None,
-                                                      settings["raw_profile"] is not None)))
+                                     self._host_stream_gate(src, settings)))
         return settings, load, self.extract_image_data_cpu(src, **load, _internal=True)
+
+    def _host_stream_gate(self, src, settings):
+        """payload.host_stream_gate of a call's `settings` (process()'s keywords): why its frame is rendered in one piece, or None."""
+        return host_stream_gate(src, self.stream_bands, settings["rotation"], settings["chroma_nr"], settings["canvas_mode"],
+                                settings["highlight_burn"], bool(settings["lens_correction"]) and settings["lens_profile"] is not None,
+                                settings["raw_profile"] is not None)
 
     def _export_preloaded(self, what, settings, stream, early=()) -> bool:
         """The prologue of an export of a phase-1 payload: no textures, then with stream=True `stream_rejected` from the export's
@@ -997,17 +812,17 @@ class HipProcessor:
 
         return self._stream(payload, negative_film, grain_size, grain_sigma, final_scaling, settings, make_sink)
 
-    def _encode_device(self, image_u8, quality, subsampling=2, optimize=False, exif=b"", progressive=False, extras=None):
-        """A uint8 (H, W, 3) device frame -> the JPEG file's bytes.  The encoder runs on the current stream; reading its 8-byte
+    def _encode_device(self, image_u8, o):
+        """A uint8 (H, W, 3) device frame -> the JPEG file's bytes, with the checked options `o` (jpeg_options.checked_options).
+        The encoder runs on the current stream; reading its 8-byte
         length back is the one synchronisation (optimize and progressive add one for the symbol counts), then only the file crosses PCIe, into a
         pinned buffer this processor keeps (grown to the largest file so far; a pageable download of a 47 MB file cost up to 34 ms)
-        and from there into the bytes object -- with the EXIF APP1 and the other segments of `extras` (_jpeg_extras) spliced in
+        and from there into the bytes object -- with the EXIF APP1 and the other segments of `o.extras` spliced in
         on the way, in the same single copy."""
         if image_u8.stride(2) != 1 or image_u8.stride(1) != 3 or image_u8.stride(0) < 3 * image_u8.shape[1]:
             image_u8 = image_u8.contiguous()  # (a row-strided view is encoded in place)
-        extras = extras or _NO_EXTRAS
-        out, length = self.ctx.jpeg_encode(image_u8, quality, subsampling, optimize, progressive,
-                                           extras.restart(int(image_u8.shape[1]), subsampling), extras.density)
+        out, length = self.ctx.jpeg_encode(image_u8, o.quality, o.subsampling, o.optimize, o.progressive,
+                                           o.extras.restart(int(image_u8.shape[1]), o.subsampling), o.extras.density)
         n = int(length.item())
         if n <= 0:
             raise RuntimeError("r2f_jpeg_encode reported an empty file")
@@ -1015,7 +830,7 @@ class HipProcessor:
         if host is None or host.numel() < n:
             host = self._jpeg_host = self._torch.empty(max(n, 1 << 20), dtype=self._torch.uint8, pin_memory=True)
         host[:n].copy_(out[:n])  # (synchronous: the bytes are there when it returns)
-        segments = extras.segments(exif)
+        segments = o.extras.segments(o.exif)
         if segments:
             data = host[:n].numpy().data
             return b"".join((data[:20], segments, data[20:]))
@@ -1105,9 +920,9 @@ class HipProcessor:
         self.ctx.write_frame_params(p)     # (and the exposure-range record starts empty)
         return host, p, bounds, bufs, ha, ma
 
-    def _stream_jpeg(self, payload, negative_film, grain_size, grain_sigma, final_scaling, quality, file, settings, opts=(2, False, b""),
-                     extras=None):
-        """_stream_payload with a JPEG sink: the same bands and stage calls, no pixels downloaded; each band's finished MCU rows
+    def _stream_jpeg(self, payload, negative_film, grain_size, grain_sigma, final_scaling, file, settings, o):
+        """_stream_payload with a JPEG sink (`o`: the export's checked options; optimize and progressive never stream):
+        the same bands and stage calls, no pixels downloaded; each band's finished MCU rows
         are encoded behind its tail and the file's final bytes go down while later bands arrive (jpeg_stream.py).  Returns the
         file's bytes (file=None) or their count, or None (with `stream_rejected` saying why) when the payload does not qualify."""
         def make_sink(depth, out_u8, bounds):
@@ -1115,10 +930,9 @@ class HipProcessor:
             if staging is None:
                 staging = self._jpeg_staging = JpegStaging(self._torch, self.device)
             _, down = self._copy_streams()
-            subsampling, _, exif = opts  # (optimize never streams)
-            x = extras or _NO_EXTRAS
-            sink = JpegBandSink(staging, self.ctx, out_u8, quality, bounds, down, file, subsampling, segments=x.segments(exif),
-                                restart=x.restart(int(out_u8.shape[1]), subsampling), density=x.density)
+            x = o.extras
+            sink = JpegBandSink(staging, self.ctx, out_u8, o.quality, bounds, down, file, o.subsampling, segments=x.segments(o.exif),
+                                restart=x.restart(int(out_u8.shape[1]), o.subsampling), density=x.density)
             return sink, sink.band
 
         # (a JPEG is 8 bits per sample whatever `output_bits` the caller's settings carry)
@@ -1348,14 +1162,18 @@ class HipProcessor:
     def _prepare_device_frame(self, image, cpu_payload):
         """The device pre-path on an uploaded payload frame -> (frame, layout) as the pipeline reads it."""
         torch = self._torch
+
+        def cut_and_turn(image, window, k, dims=(1, 2)):
+            """How a whole-frame step ends: the window it did not cut itself (None: it did), then k quarter turns (np.rot90's)."""
+            if window is not None:
+                r0, c0, nr, nc = window
+                image = image[r0:r0 + nr, c0:c0 + nc]
+            return torch.rot90(image, k, dims) if k else image
+
         demosaic_step = cpu_payload.get("demosaic")
         if demosaic_step:  # a Bayer mosaic: LibRaw's share of raw_to_linear on the device -> the uint16 frame of the lines below
-            image = self.ctx.demosaic_u16(image.contiguous(), demosaic_step["params"])
-            if demosaic_step["window"] is not None:
-                r0, c0, nr, nc = demosaic_step["window"]
-                image = image[r0:r0 + nr, c0:c0 + nc]
-            if demosaic_step["rotate_times"]:
-                image = torch.rot90(image, demosaic_step["rotate_times"], dims=(0, 1))
+            image = cut_and_turn(self.ctx.demosaic_u16(image.contiguous(), demosaic_step["params"]), demosaic_step["window"],
+                                 demosaic_step["rotate_times"], dims=(0, 1))
         if image.dtype in (torch.int16, torch.uint16):  # a decoded 16-bit frame: raw_conversion.py:50-52 on the device
             if cpu_payload.get("u16_factor") is None:
                 raise ValueError("a uint16 payload needs its exposure factor (`u16_factor`, extract_image_data_cpu sets it)")
@@ -1375,15 +1193,13 @@ class HipProcessor:
         layout = None  # the payload is (H, W, C) like the reference's; the device pre-path hands on (3, H, W) planes
         lens_step = cpu_payload.get("lens")
         if lens_step:  # lens correction (effects.lens_correction) of the whole frame, into the window the crops keep
-            image = self.ctx.lens_correct(image.contiguous(), lens_step["params"], lens_step["window"])
-            if lens_step.get("rotate_times"):
-                image = torch.rot90(image, lens_step["rotate_times"], dims=(1, 2)).contiguous()
+            image = cut_and_turn(self.ctx.lens_correct(image.contiguous(), lens_step["params"], lens_step["window"]), None,
+                                 lens_step.get("rotate_times")).contiguous()  # (the planes themselves unless they were turned)
             layout = "chw"
         warp = cpu_payload.get("warp")
         if warp:  # free rotation (effects.rotate) + the crops behind it + quarter turns (np.rot90 on the planes)
-            image = self.ctx.warp_affine(image.contiguous(), warp["m_dst_to_src"], warp["window"], layout=layout)
-            if warp["rotate_times"]:
-                image = torch.rot90(image, warp["rotate_times"], dims=(1, 2)).contiguous()
+            image = cut_and_turn(self.ctx.warp_affine(image.contiguous(), warp["m_dst_to_src"], warp["window"], layout=layout), None,
+                                 warp["rotate_times"]).contiguous()
             layout = "chw"
         if cpu_payload.get("chroma_nr"):  # pre-path chroma NR (effects.py:547-561): XYZ planes out, CHW into the pipeline
             image, layout = self.ctx.chroma_nr(image.contiguous(), cpu_payload["chroma_nr"], layout=layout), "chw"
@@ -1580,138 +1396,3 @@ def torch_div257(torch, image16):
 
 
 _LOAD_KEYWORDS = tuple(inspect.signature(HipProcessor.load_image_texture).parameters)[2:]  # (self, src, then these)
-
-
-def _jpeg_quality(quality) -> int:
-    """The reference's quality slider: an int 0 .. 100 (0 writes what 1 writes, as in Pillow)."""
-    if isinstance(quality, (bool, np.bool_)) or not isinstance(quality, (int, np.integer)):
-        raise ValueError(f"JPEG quality must be an int in 0 .. 100, got {quality!r}")
-    if not 0 <= int(quality) <= 100:
-        raise ValueError(f"JPEG quality must be in 0 .. 100, got {int(quality)}")
-    return int(quality)
-
-
-_SUBSAMPLINGS = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}
-_EXIF_MAX = MARKER_MAX  # a marker segment's payload (Pillow's MAX_BYTES_IN_MARKER)
-_OPTIMIZE_REJECTED = "optimize=True: its Huffman tables need the whole frame's statistics before the first scan byte"
-_PROGRESSIVE_REJECTED = "progressive=True: every one of its scans spans the whole frame"
-
-
-def _jpeg_subsampling(subsampling) -> int:
-    """Pillow's subsampling option -> 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0): -1 (libjpeg's default, 4:2:0), 0 / "4:4:4",
-    1 / "4:2:2", 2 / "4:2:0".  "keep" (it needs a JPEG source), "4:1:1" (which Pillow maps with a warning) and anything else raise
-    ValueError."""
-    if isinstance(subsampling, str):
-        if subsampling in _SUBSAMPLINGS:
-            return _SUBSAMPLINGS[subsampling]
-    elif not isinstance(subsampling, (bool, np.bool_)) and isinstance(subsampling, (int, np.integer)) and -1 <= int(subsampling) <= 2:
-        return 2 if int(subsampling) == -1 else int(subsampling)
-    raise ValueError(f"JPEG subsampling must be -1, 0 / '4:4:4', 1 / '4:2:2' or 2 / '4:2:0', got {subsampling!r}")
-
-
-def _jpeg_exif(exif) -> bytes:
-    """Pillow's exif option -> the APP1 payload: bytes-like, or a PIL.Image.Exif (its .tobytes()); b"" for none."""
-    if isinstance(exif, (bytes, bytearray, memoryview)):
-        data = bytes(exif)
-    else:
-        Exif = getattr(sys.modules.get("PIL.Image"), "Exif", None)  # (an Exif instance means Pillow is imported already)
-        if Exif is None or not isinstance(exif, Exif):
-            raise ValueError(f"JPEG exif must be bytes or a PIL.Image.Exif, got {type(exif).__name__}")
-        data = exif.tobytes()
-    if len(data) > _EXIF_MAX:
-        raise ValueError(f"EXIF data is too long: {len(data)} bytes (a JPEG marker holds at most {_EXIF_MAX})")
-    return data
-
-
-def _jpeg_options(subsampling, optimize, exif):
-    """(sampling 0 / 1 / 2, optimize, exif bytes) of an export's options, checked before any work starts."""
-    return _jpeg_subsampling(subsampling), bool(optimize), _jpeg_exif(exif)
-
-
-class _JpegExtras(NamedTuple):
-    """The checked options of an export that need no table or kernel of their own (_jpeg_extras)."""
-    icc_profile: bytes = b""
-    xmp: bytes = b""
-    comment: bytes = b""
-    density: tuple = (0, 0)  # APP0's (x, y) in dots per inch; (0, 0): no units
-    blocks: int = 0          # restart_marker_blocks
-    rows: int = 0            # restart_marker_rows
-
-    def restart(self, W: int, sampling: int) -> int:
-        """MCUs per restart interval for a frame W pixels wide (0: none): `rows` MCU rows, clamped to 65535 as libjpeg does,
-        else `blocks`."""
-        if self.rows > 0:
-            return min(self.rows * -(-W // (8 if sampling == 0 else 16)), 65535)
-        return self.blocks
-
-    def segments(self, exif: bytes) -> bytes:
-        return metadata_segments(exif, self.xmp, self.icc_profile, self.comment)
-
-
-_NO_EXTRAS = _JpegExtras()
-
-
-def _jpeg_bytes(name, value, limit, what) -> bytes:
-    if not isinstance(value, (bytes, bytearray, memoryview)):
-        raise ValueError(f"JPEG {name} must be bytes, got {type(value).__name__}")
-    data = bytes(value)
-    if len(data) > limit:
-        raise ValueError(f"JPEG {name} is too long: {len(data)} bytes ({what} at most {limit})")
-    return data
-
-
-def _jpeg_restart(name, value, limit) -> int:
-    try:
-        n = operator.index(value)
-    except TypeError:
-        raise ValueError(f"JPEG {name} must be an integer, got {value!r}") from None
-    if n < 0 or (limit is not None and n > limit):
-        raise ValueError(f"JPEG {name} must be {'in 0 .. ' + str(limit) if limit is not None else 'at least 0'}, got {n}")
-    return n
-
-
-def _jpeg_extras(icc_profile, xmp, comment, dpi, restart_marker_blocks, restart_marker_rows, progressive=False) -> _JpegExtras:
-    """Pillow's icc_profile, xmp, comment, dpi, restart_marker_blocks and restart_marker_rows options, checked before any work
-    starts.  Where Pillow wraps (blocks modulo 65536, a density modulo 65536), ignores (negative rows or dpi) or fails late (a
-    segment too long for its marker), this raises ValueError naming the option."""
-    icc = _jpeg_bytes("icc_profile", icc_profile, 255 * (MARKER_MAX - ICC_OVERHEAD), "255 APP2 chunks hold")
-    x = _jpeg_bytes("xmp", xmp, MARKER_MAX - len(XMP_NAMESPACE), "its APP1 segment holds")
-    if isinstance(comment, str):
-        comment = comment.encode("utf-8")  # (as Pillow writes a str)
-    elif not isinstance(comment, bytes):
-        raise ValueError(f"JPEG comment must be bytes or str, got {type(comment).__name__}")
-    if len(comment) > MARKER_MAX:
-        raise ValueError(f"JPEG comment is too long: {len(comment)} bytes (a JPEG marker holds at most {MARKER_MAX})")
-    try:
-        density = tuple(int(round(v)) for v in dpi)
-        ok = len(density) == 2 and all(0 <= v <= 65535 for v in density)
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok:
-        raise ValueError(f"JPEG dpi must be two numbers that round to 0 .. 65535, got {dpi!r}")
-    if not all(density):
-        density = (0, 0)  # (Pillow sets the units only when both are positive)
-    blocks = _jpeg_restart("restart_marker_blocks", restart_marker_blocks, 65535)
-    rows = _jpeg_restart("restart_marker_rows", restart_marker_rows, None)
-    if progressive and (blocks or rows):
-        raise ValueError("JPEG progressive=True with restart_marker_blocks / restart_marker_rows is not supported: restart "
-                         "intervals are written in baseline files only")
-    return _JpegExtras(icc, x, comment, density, blocks, rows)
-
-
-def _jpeg_progressive(progressive) -> bool:
-    """Pillow's progressive option: True / False, or 0 / 1 (NumPy's included); anything else raises ValueError."""
-    if isinstance(progressive, (bool, np.bool_)):
-        return bool(progressive)
-    if isinstance(progressive, (int, np.integer)) and int(progressive) in (0, 1):
-        return bool(int(progressive))
-    raise ValueError(f"JPEG progressive must be True / False (or 0 / 1), got {progressive!r}")
-
-
-def _check_jpeg_image(is_uint8, shape, dtype):
-    if not is_uint8:
-        raise ValueError(f"encode_jpeg: the image must be uint8, got {dtype}")
-    if len(shape) != 3 or shape[2] != 3:
-        raise ValueError(f"encode_jpeg: the image must be (H, W, 3) RGB, got shape {tuple(shape)}")
-    if not (1 <= shape[0] <= 65535 and 1 <= shape[1] <= 65535):
-        raise ValueError(f"encode_jpeg: a JPEG holds 1 .. 65535 pixels per side, got {shape[0]} x {shape[1]}")

@@ -78,7 +78,7 @@ def _segment(marker: int, payload: bytes) -> bytes:
 def metadata_segments(exif: bytes = b"", xmp: bytes = b"", icc_profile: bytes = b"", comment: bytes = b"") -> bytes:
     """Every variable-length segment of an export in the order Pillow writes them, to go right after the file's first 20 bytes
     (SOI + APP0): APP1 Exif, APP1 XMP (its namespace first), the profile in APP2 chunks of at most 65533 - 14 bytes, COM.  Each
-    empty one is left out; the lengths were checked with the options (hip_processor._jpeg_metadata)."""
+    empty one is left out; the lengths were checked with the options (jpeg_options._jpeg_extras)."""
     out = [app1_segment(exif)]
     if xmp:
         out.append(_segment(0xE1, XMP_NAMESPACE + xmp))

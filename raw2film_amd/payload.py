@@ -1,0 +1,225 @@
+"""Phase 1 of the two-phase API as plain functions: what HipProcessor.extract_image_data_cpu derives from a decoded frame and the
+load settings before anything is uploaded, and why a payload does not stream in row bands.  Pure host work: no torch, no
+processor state.
+
+The crop rule (plan_crops states it once).  There is one aspect box `a` of the frame -- for a mosaic, of the demosaiced frame.
+Without a free rotation there is one full window, `a` composed with the zoom box, and k = rotate_times % 4 quarter turns; with
+one, the warp owns its own window (rotation_plan composed with the zoom box) and k, and what is left to cut ahead of it is `a`.
+Either way the cut (and the turns that go with it) is applied once, by the last step that still sees the whole frame:
+the lens step; else the device decode of an exposure="device" frame (`u16_window`; never turned or rotated: exposure_mode);
+else the demosaic step; else the host, as a view of the frame plus np.rot90."""
+
+from __future__ import annotations
+
+import math
+from collections import namedtuple
+from typing import NamedTuple
+
+import numpy as np
+
+from . import geometry
+from .lens import LensProfile
+from .raw import RawProfile
+
+_DEMOSAIC_REJECTED = ("the demosaic step (raw_profile): the mosaic is demosaiced whole on the device before the pipeline; its row "
+                      "contract (r2f_demosaic_u16) is not streamed yet")
+_LENS_REJECTED = "the lens step (lens_profile): its gather reads the whole frame, which a row band does not hold"
+
+
+def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canvas_mode="No"):
+    """Why a phase-1 payload cannot stream through the pipeline in row bands, or None (its render's stages have the last word:
+    plan_bands).  `shape`, `dtype`: of its frame as a tensor (_payload_tensor: "torch.float32", or "torch.int16" for uint16)."""
+    is_u16 = dtype == "torch.int16"  # LibRaw's 16-bit output: converted band by band on the device (raw_conversion.py:50-52)
+    if payload.get("demosaic"):
+        return _DEMOSAIC_REJECTED
+    if payload.get("lens"):
+        return _LENS_REJECTED
+    if (payload.get("warp") or payload.get("resize_to") or payload.get("upscale_to") or payload.get("chroma_nr")
+            or payload.get("canvas_resolution") or canvas_mode != "No" or on_device or len(shape) != 3
+            or int(shape[2]) not in (3, 4) or math.prod(shape) < (1 << 24) or dtype not in ("torch.float32", "torch.int16")
+            or (payload.get("u16_factor") is None) == is_u16):  # (a uint16 frame comes with its exposure factor, a float one without)
+        return ("a device pre-path, a canvas, or a frame below 16.7 M samples: " + ", ".join(
+            f"{k} = {payload.get(k)!r}" for k in ("warp", "resize_to", "upscale_to", "chroma_nr", "canvas_resolution", "u16_factor",
+                                                  "clip_on_device")) + f", frame {tuple(shape)} {dtype}")
+    fr = payload.get("final_resolution") if final_scaling == "cpu" else None  # (cpu_processor.py:411-412: the final scaling)
+    if fr is not None and (int(fr[0]), int(fr[1])) != (int(shape[0]), int(shape[1])):
+        return f"the finished frame is scaled to {fr}"
+    return None
+
+
+def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="No", highlight_burn=0.0, lens=False, demosaic=False):
+    """Why process(src, cache=False) renders a frame in one piece before it extracts its payload (stream_rejection and plan_bands
+    come after that), or None.  lens: the call corrects the lens (lens_correction with a lens_profile); demosaic: its source is a
+    Bayer mosaic (raw_profile)."""
+    if stream_bands <= 1:
+        return f"stream_bands = {stream_bands}"
+    if demosaic:
+        return _DEMOSAIC_REJECTED
+    if lens:
+        return _LENS_REJECTED
+    if not isinstance(src, np.ndarray):
+        return f"the source is a {type(src).__name__}, not a host array"
+    if src.size < (1 << 24):
+        return f"a frame of {src.size} samples, below 16.7 M"
+    if rotation or chroma_nr or canvas_mode != "No" or highlight_burn:
+        return (f"a device pre-path, a canvas or a highlight burn: rotation = {rotation!r}, chroma_nr = {chroma_nr!r}, "
+                f"canvas_mode = {canvas_mode!r}, highlight_burn = {highlight_burn!r}")
+    return None
+
+
+def check_profiles(raw_profile, lens_profile, lens_correction, cam, lens):
+    """The caller's profiles are of their types, and the call needs no lensfun lookup."""
+    if raw_profile is not None and not isinstance(raw_profile, RawProfile):
+        raise ValueError(f"raw_profile must be a raw2film_amd.raw.RawProfile, got {type(raw_profile).__name__}")
+    if lens_profile is not None and not isinstance(lens_profile, LensProfile):
+        raise ValueError(f"lens_profile must be a raw2film_amd.lens.LensProfile, got {type(lens_profile).__name__}")
+    if lens_correction and cam is not None and lens is not None:
+        # the reference corrects only when both are given (cpu_processor.py:107-108, effects.py:22-30); the lensfun lookup is
+        # not part of the accelerated path, and rendering an uncorrected frame in its place would be a silent difference
+        raise NotImplementedError("lens correction (lensfunpy, effects.py:22-43) is outside the accelerated path: "
+                                  "pass lens_correction=False or no cam / lens (the calibration's numbers go in lens_profile)")
+
+
+def load_decoded(src, clip=True, mosaic=False):
+    """The decoded frame behind `src` (an array, or the path of a .npy file): float32 (H, W, 3|4), clamped like
+    gpu_processor.py:275 unless clip=False; LibRaw's uint16 output as it is; with mosaic=True the uint16 (H, W) Bayer mosaic."""
+    if isinstance(src, np.ndarray):
+        image = src
+    elif isinstance(src, str) and src.lower().endswith(".npy"):
+        image = np.load(src)
+    elif isinstance(src, str):
+        raise NotImplementedError(
+            f"{src!r}: RAW decoding (LibRaw/rawpy, raw_conversion.py:33-53) is outside the accelerated path; "
+            "pass the decoded linear-XYZ frame (array or .npy)"
+        )
+    else:
+        raise TypeError(f"unsupported src type {type(src)!r}")
+    if mosaic:
+        if image.ndim != 2 or image.dtype != np.uint16:
+            raise ValueError(f"with a raw_profile the source is a Bayer mosaic, uint16 (H, W); got {image.dtype} {image.shape}")
+        return image
+    if image.ndim != 3 or image.shape[2] not in (3, 4):
+        raise ValueError(f"decoded frame must be (H, W, 3|4), got {image.shape}" +
+                         (" (a Bayer mosaic needs its raw_profile)" if image.ndim == 2 else ""))
+    if image.dtype == np.uint16:  # LibRaw's 16-bit output: converted on the device (decode.py, r2f_decode_u16)
+        return image
+    image = np.asarray(image, dtype=np.float32)
+    return np.clip(image, 0, 65504) if clip else image  # gpu_processor.py:275 (clip=False: clamped after the upload)
+
+
+def exposure_mode(exposure, on_device, is_u16, mosaic, rotation, rotate_times):
+    """Where the auto exposure of a uint16 frame is measured -> (on the device?, `exposure`, `exposure_rejected`).  The device
+    measures the whole frame as it was uploaded, so a turned or rotated frame is measured on the host as with exposure=None, and
+    `exposure_rejected` says why.  A mosaic (raw_profile) has no RGB frame on the host: without stops it is measured on the device
+    like exposure="device", and where that is refused the call needs explicit stops."""
+    if mosaic and (exposure is None or on_device):
+        if rotation or int(rotate_times) % 4:
+            raise ValueError(f"rotation = {rotation!r}, rotate_times = {rotate_times!r}: a turned or rotated frame is measured on "
+                             "the host, and a mosaic (raw_profile) has no RGB frame there: pass the exposure in stops")
+        on_device = True
+    if is_u16 and on_device and (rotation or int(rotate_times) % 4):
+        return False, None, (f"rotation = {rotation!r}, rotate_times = {rotate_times!r}: a turned or rotated frame is measured on "
+                             "the host")
+    return on_device, exposure, None
+
+
+class CropPlan(NamedTuple):
+    """plan_crops' answer.  A step's share is {"window": (row0, col0, rows, cols) or None, "rotate_times": k}: the payload's
+    fields of that step, next to its `params`; None without the step."""
+    size: tuple  # (h, w) of the frame the crops, the rotation and the quarter turns leave
+    u16_window: tuple | None  # what the device decode of an exposure="device" frame keeps of the uploaded frame
+    warp: dict | None  # the payload's `warp`
+    lens: dict | None
+    demosaic: dict | None
+    host: dict | None  # the host's share: cut_and_turn's arguments
+
+
+def plan_crops(rows, cols, is_u16, aspect, flip, zoom, rotation, rotate_times, on_device, lens, demosaic) -> CropPlan:
+    """The crops of a rows x cols frame (raw_conversion.crop_rotate_zoom's index arithmetic, raw_conversion.py:56-72, with the
+    interpolating part of a free rotation deferred to the device) and who applies them: see the module's text.  is_u16, on_device:
+    the frame is uint16 / measured on the device (exposure_mode's answer: then neither turned nor rotated); lens, demosaic: the
+    step exists."""
+    k = int(rotate_times) % 4
+    device_decode = is_u16 and on_device
+    r0, c0, nr, nc = aspect_box = geometry.crop_box(rows, cols, 1, aspect, flip)
+    if rotation:  # the zoom box lies in the window effects.rotate's centred crop keeps of the rotated aspect crop
+        m_inv, (r0, c0, nr, nc) = geometry.rotation_plan(nr, nc, rotation)
+    zr0, zc0, znr, znc = geometry.crop_box(nr, nc, zoom, aspect, False)
+    window = (r0 + zr0, c0 + zc0, znr, znc)
+    if rotation:
+        if znr <= 0 or znc <= 0:
+            raise ValueError(f"rotation {rotation} / zoom {zoom} leave an empty frame")
+        warp = {"m_dst_to_src": m_inv, "window": window, "rotate_times": k}
+        share = {"window": aspect_box, "rotate_times": 0}  # ahead of the warp: the aspect crop alone
+    else:
+        warp, share = None, {"window": window, "rotate_times": k}
+    idle = {"window": None, "rotate_times": 0}
+    u16_window = None
+    if device_decode:  # (with a lens step the frame is decoded whole: the step reads all of it)
+        u16_window = (0, 0, rows, cols) if lens else window
+    return CropPlan(
+        size=(znc, znr) if k % 2 else (znr, znc), u16_window=u16_window, warp=warp,
+        lens=share if lens else None,
+        demosaic=None if not demosaic else idle if lens or device_decode else share,
+        host=None if lens or device_decode or demosaic else share)
+
+
+def cut_and_turn(image, window, rotate_times):
+    """The host's share of a CropPlan: a view of the frame, turned with np.rot90 (raw_conversion.py:66-70)."""
+    r0, c0, nr, nc = window
+    view = image[r0:r0 + nr, c0:c0 + nc]
+    return np.rot90(view, k=rotate_times) if rotate_times else view
+
+
+Resolutions = namedtuple("Resolutions", "final_resolution resize_to upscale_to output_resolution canvas_resolution pipeline_resolution")
+
+
+def plan_resolution(h, w, frame_width, frame_height, resolution, max_scale, canvas_mode, canvas_scale, canvas_ratio) -> Resolutions:
+    """The payload's fields of these names for a cropped h x w frame.  cpu_processor.py:119-134: without a preview resolution the
+    frame's own size is the target; a target finer than `max_scale` px/mm is rendered at max_scale and scaled back up at the very
+    end (cpu_processor.py:411-412)."""
+    if resolution is None and max_scale is not None:
+        resolution = (h, w)
+    resize_to, upscale_to = None, None
+    # what CpuProcessor.load_image returns as `orig_resolution` (cpu_processor.py:122) and process() hands to the final
+    # resolution_scaling (cpu_processor.py:411-412)
+    final_resolution = (int(resolution[0]), int(resolution[1])) if resolution is not None else None
+    scale_factor = 1.0
+    if resolution is not None:
+        resolution = (int(resolution[0]), int(resolution[1]))
+        scale = max(resolution) / max(frame_width, frame_height)
+        if max_scale is not None and scale > max_scale:
+            scale_factor = max_scale / scale
+            upscale_to = resolution
+            resolution = tuple(round(x * scale_factor) for x in resolution)
+        # utils.resolution_scaling (utils.py:226-244), applied on the device in phase 2
+        factor = min(resolution[0] / h, resolution[1] / w)
+        if factor != 1:
+            # cv.resize(dsize=(round(w f), round(h f))): INTER_AREA down, INTER_LANCZOS4 up (a preview larger than the frame)
+            resize_to = (round(h * factor), round(w * factor))
+            h, w = resize_to
+    # gpu_processor.py:764: the size the frame has once it is back from the max_scale pipeline -- the UN-shrunk output size,
+    # which is also what the canvas is laid out for (:767-771), not the pipeline's
+    out_h, out_w = (round(x / scale_factor) for x in (h, w))
+    if upscale_to is not None and min(upscale_to[0] / h, upscale_to[1] / w) <= 1:
+        upscale_to = None  # (the uint8 result goes back up with LANCZOS4 only when that enlarges it)
+    canvas_res = None
+    if canvas_mode != "No":  # gpu_processor.py:767-771
+        res, _, _ = geometry.canvas_layout((out_h, out_w), canvas_mode, canvas_scale, canvas_ratio)
+        canvas_res = (res[1], res[0])
+    return Resolutions(final_resolution, resize_to, upscale_to, (out_w, out_h), canvas_res, (w, h))
+
+
+def pack_image(image, whole, is_u16, alpha):
+    """The payload's `image_array`.  whole: a mosaic, or the uint16 frame the device measures -- the array itself when it is
+    contiguous (a fourth channel is dropped on the device).  Another uint16 frame: its three channels.  A float frame: float32,
+    with the constant alpha plane of gpu_processor.py:765 when `alpha`, else without a fourth channel."""
+    if whole:
+        return np.ascontiguousarray(image)
+    if is_u16:
+        return np.ascontiguousarray(image[..., :3])
+    if image.shape[2] == 3 and alpha:
+        image = np.concatenate([image, np.ones_like(image[..., :1])], axis=-1)  # gpu_processor.py:765
+    elif image.shape[2] == 4 and not alpha:
+        image = image[..., :3]
+    return np.ascontiguousarray(image, dtype=np.float32)

@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 from raw2film_amd import decode, geometry
-from raw2film_amd.hip_processor import DEVICE_EXPOSURE, HipProcessor, exposure_on_device, stream_rejection
+from raw2film_amd.hip_processor import DEVICE_EXPOSURE, HipProcessor, exposure_on_device
+from raw2film_amd.payload import stream_rejection
 
 import exposure_model
 

@@ -16,7 +16,8 @@ import pytest
 
 import demosaic_model as dm
 from raw2film_amd import _lib
-from raw2film_amd.hip_processor import HipProcessor, host_stream_gate, stream_rejection
+from raw2film_amd.hip_processor import HipProcessor
+from raw2film_amd.payload import host_stream_gate, stream_rejection
 from raw2film_amd.raw import RawProfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

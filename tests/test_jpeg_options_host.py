@@ -210,7 +210,7 @@ def test_library_bound_ex_holds_for_the_worst_case():
 
 # ---- the option parser and the streamed export's row steps
 def test_subsampling_parser():
-    from raw2film_amd.hip_processor import _jpeg_exif, _jpeg_options, _jpeg_subsampling
+    from raw2film_amd.jpeg_options import _jpeg_exif, _jpeg_options, _jpeg_subsampling
 
     for v, want in ((-1, 2), (0, 0), (1, 1), (2, 2), ("4:4:4", 0), ("4:2:2", 1), ("4:2:0", 2), (np.int64(1), 1)):
         assert _jpeg_subsampling(v) == want

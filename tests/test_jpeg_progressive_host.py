@@ -146,7 +146,7 @@ def test_header_ex_refuses_progressive():
 
 
 def test_progressive_parser():
-    from raw2film_amd.hip_processor import _jpeg_progressive
+    from raw2film_amd.jpeg_options import _jpeg_progressive
 
     for v, want in ((True, True), (False, False), (0, False), (1, True), (np.bool_(True), True), (np.int64(1), True)):
         assert _jpeg_progressive(v) is want

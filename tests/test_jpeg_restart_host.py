@@ -188,7 +188,7 @@ def test_library_header_and_bound_are_pillows_with_density_and_dri():
 
 # ---- the option parsers
 def test_restart_and_metadata_parsers():
-    from raw2film_amd.hip_processor import _jpeg_extras
+    from raw2film_amd.jpeg_options import _jpeg_extras
 
     def parse(**kw):
         args = dict(icc_profile=b"", xmp=b"", comment=b"", dpi=(0, 0), restart_marker_blocks=0, restart_marker_rows=0)

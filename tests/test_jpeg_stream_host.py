@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 from raw2film_amd import _lib
-from raw2film_amd.hip_processor import host_stream_gate, plan_bands
+from raw2film_amd.hip_processor import plan_bands
+from raw2film_amd.payload import host_stream_gate
 from raw2film_amd.jpeg_stream import deliver, jpeg_row_steps
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

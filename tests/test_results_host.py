@@ -1,5 +1,5 @@
 """Host logic of the streamed path and of the result buffers, no GPU needed: the band planner and the qualification of a payload
-(hip_processor.plan_bands / stream_rejection), the fresh-array sink under a late page touch, the lease pool under concurrency."""
+(hip_processor.plan_bands / payload.stream_rejection), the fresh-array sink under a late page touch, the lease pool under concurrency."""
 
 import gc
 import threading
@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 from raw2film_amd import _lib
-from raw2film_amd.hip_processor import plan_bands, stream_rejection
+from raw2film_amd.hip_processor import plan_bands
+from raw2film_amd.payload import stream_rejection
 from raw2film_amd.results import LEASES, ResultBuffers, ResultSink, touch_pages
 
 torch = pytest.importorskip("torch")

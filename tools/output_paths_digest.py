@@ -1,12 +1,15 @@
 """One SHA-256 per output path of HipProcessor, at 8 and at 16 bits: the bit-equality check of a change to the Python output side.
 
-    python tools/output_paths_digest.py [--times FILE] > digest.txt
+    python tools/output_paths_digest.py [--times FILE] [--group prepath] > digest.txt
 
 Every case renders a seeded synthetic frame through the public API only and prints `<case> <dtype> <shape> <sha256>` -- for a file
 its length in place of dtype and shape.  Run it on two commits, each in a process of its own, and compare the outputs line for
 line.  Non-streamed cases use 96 x 160 and 70 x 257 frames (the odd width takes the 2- and 4-byte edge stores of the uint16
 output); streamed cases use 2368 x 2368 x 3, just above the 2 ** 24 samples the gate admits, in four bands, so that the taper and
 the stencil lag are exercised.  A streamed case whose frame did not stream prints `stream_rejected` in place of a digest.
+The `prepath` group renders the small frames through what runs ahead of the pipeline: the crops and quarter turns, the free
+rotation, exposure="device", a LensProfile, a RawProfile mosaic at full and half size, both together, the two-phase API and the
+exports of such frames, and one encode_jpeg call with every JPEG keyword set.
 --times FILE: wall clock of every case in ms (its first call, tables and allocations included, and a second one), kept out of
 the digest."""
 
@@ -94,6 +97,64 @@ def small_cases(proc, torch, neg, prt):
         case("process_preloaded_jpeg", lambda: proc.process_preloaded_jpeg(payload, neg, 6, 0.4, 90, final_scaling="cpu", optimize=True, **kw))
 
 
+def prepath_cases(proc, torch, neg, prt):
+    from raw2film_amd.lens import LensProfile
+    from raw2film_amd.raw import RawProfile
+    from raw2film_amd.synthetic import synthetic_frame
+
+    lens = LensProfile("ptlens", (0.02, -0.06, 0.01), vignetting=(-0.3, 0.1, -0.02), center=(0.01, -0.006))
+    raw = RawProfile("GRBG", black=(64, 60, 66, 64), multipliers=(2.1, 1.0, 1.6),
+                     matrix=((1.62, -0.41, -0.19), (-0.28, 1.52, -0.22), (0.04, -0.52, 1.49)))
+    film = dict(print_film=prt, seed=20260630, exp_kelvin=6000, color_masking=1.0, halation_green_factor=0.3)
+    shapes = {"plain": {}, "zoomed_turned": dict(zoom=1.3, rotate_times=3), "rotated": dict(rotation=3.5, zoom=1.3, rotate_times=1)}
+    for H, W in SMALL:
+        tag = f"{H}x{W}"
+        case = lambda name, fn: digest(f"prepath_{name} {tag}", timed(f"prepath_{name} {tag}", fn, repeat=True))  # noqa: E731
+        frame = synthetic_frame(H, W, seed=H + W)
+        u16 = np.ascontiguousarray((np.clip(frame, 0.0, 1.0) * 40000.0).astype(np.uint16))
+        # a frame wider than the film format, so that the aspect crop cuts columns (and rows when flipped)
+        kw = dict(film, frame_width=36.0 * W / 6000.0, frame_height=36.0 * W / 6000.0 * H / W * 1.1)
+        for name, src, extra in (("f32", frame, {}), ("u16", u16, dict(exposure=0.5))):
+            for shape, g in shapes.items():
+                case(f"{name}_{shape}", lambda: proc.process(src, neg, 6, 0.4, cache=False, **g, **extra, **kw))
+            case(f"{name}_flip", lambda: proc.process(src, neg, 6, 0.4, cache=False, flip=True, **extra, **kw))
+        case("u16_device_exposure", lambda: proc.process(u16, neg, 6, 0.4, cache=False, exposure="device", zoom=1.3, **kw))
+        print(f"prepath_u16_device_exposure_stops {tag} {proc.last_auto_exposure!r}", flush=True)
+        case("u16_device_exposure_turned", lambda: proc.process(u16, neg, 6, 0.4, cache=False, exposure="device", rotate_times=1, **kw))
+        print(f"prepath_u16_device_exposure_turned_rejected {tag} {proc.exposure_rejected!r}", flush=True)
+        rng = np.random.default_rng(H * 1000 + W)
+        mosaics = {"mosaic_full": (rng.integers(0, 40000, (H, W), dtype=np.uint16), False),
+                   "mosaic_half": (rng.integers(0, 40000, (2 * H, 2 * W), dtype=np.uint16), True)}
+        steps = [("lens", frame, dict(lens_profile=lens)), ("lens_u16", u16, dict(lens_profile=lens, exposure=0.5))]
+        for name, (mosaic, half) in mosaics.items():
+            steps.append((name, mosaic, dict(raw_profile=raw, half_size=half, exposure=0.5)))
+            steps.append((name + "_lens", mosaic, dict(raw_profile=raw, half_size=half, exposure=0.5, lens_profile=lens)))
+        for name, src, extra in steps:
+            for shape, g in shapes.items():
+                case(f"{name}_{shape}", lambda: proc.process(src, neg, 6, 0.4, cache=False, **g, **extra, **kw))
+            load = {k: v for k, v in dict(kw, **extra, zoom=1.3, rotate_times=3).items() if k not in film}
+            payload = proc.extract_image_data_cpu(src, **load)
+            for fs in ("gpu", "cpu"):
+                case(f"{name}_preloaded_{fs}", lambda: proc.process_preloaded(payload, neg, 6, 0.4, final_scaling=fs, **film, **load))
+        case("lens_u16_device_exposure", lambda: proc.process(u16, neg, 6, 0.4, cache=False, exposure="device", zoom=1.3, lens_profile=lens, **kw))
+        for name, (mosaic, half) in mosaics.items():  # (a mosaic without stops is measured on the device)
+            case(f"{name}_device_exposure", lambda: proc.process(mosaic, neg, 6, 0.4, cache=False, raw_profile=raw, half_size=half, zoom=1.3, **kw))
+        case("lens_cached_rerender", lambda: (proc.process(frame, neg, 6, 0.4, lens_profile=lens, zoom=1.3, **kw),
+                                              proc.process(frame, neg, 6, 0.4, lens_profile=lens, zoom=1.3, exp_comp=0.5, **kw))[1])
+        case("lens_chroma_nr_preview", lambda: proc.process(frame, neg, 6, 0.4, cache=False, lens_profile=lens, rotation=3.5, chroma_nr=3,
+                                                            resolution=(H // 2, W // 2), **kw))
+        case("lens_process_jpeg", lambda: proc.process_jpeg(frame, neg, 6, 0.4, 90, lens_profile=lens, zoom=1.3, rotate_times=3, **kw))
+        for bits in (8, 16):
+            case(f"lens_process_tiff_{bits}", lambda: proc.process_tiff(frame, neg, 6, 0.4, output_bits=bits, lens_profile=lens,
+                                                                         rotation=3.5, zoom=1.3, rotate_times=1, **kw))
+        image = proc.process(frame, neg, 6, 0.4, **kw)
+        case("encode_jpeg_every_keyword", lambda: proc.encode_jpeg(
+            image, 83, subsampling="4:2:2", optimize=True, exif=b"Exif\x00\x00II*\x00\x08\x00\x00\x00\x00\x00\x00\x00\x00\x00", progressive=False,
+            icc_profile=b"an odd profile.", xmp=b"<x:xmpmeta/>", comment="a comment", dpi=(300, 299.6), restart_marker_blocks=7,
+            restart_marker_rows=1))
+        case("encode_jpeg_progressive", lambda: proc.encode_jpeg(image, 83, subsampling=0, progressive=True, icc_profile=b"icc", dpi=(72, 72)))
+
+
 def streamed_cases(proc, torch, neg, prt):
     from raw2film_amd.synthetic import synthetic_frame
 
@@ -151,6 +212,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--times", help="write every case's wall clock (first call, second call; ms) into this file")
     ap.add_argument("--skip-streamed", action="store_true", help="the small frames only")
+    ap.add_argument("--group", default="all", choices=["all", "small", "prepath"], help="one group of cases only")
     args = ap.parse_args()
     import torch
 
@@ -159,8 +221,11 @@ def main():
     stocks = filmstock.builtin_stocks()
     neg, prt = stocks["Kodak Portra 400"], stocks["Kodak 2383"]
     proc = HipProcessor(device=0)
-    small_cases(proc, torch, neg, prt)
-    if not args.skip_streamed:
+    if args.group in ("all", "small"):
+        small_cases(proc, torch, neg, prt)
+    if args.group in ("all", "prepath"):
+        prepath_cases(proc, torch, neg, prt)
+    if args.group == "all" and not args.skip_streamed:
         streamed_cases(proc, torch, neg, prt)
     proc.close()
     if args.times:
