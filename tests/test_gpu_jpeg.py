@@ -6,6 +6,7 @@ import io
 import numpy as np
 import pytest
 
+import jpeg_extremes as jx
 from helpers import SEED, stocks, synthetic_frame
 from test_jpeg_host import QUALITIES, SIZES, contents, pillow_jpeg
 
@@ -34,6 +35,14 @@ def smooth(H, W):
 def test_encode_jpeg_writes_pillows_bytes(proc, H, W):
     for name, a in contents(H, W).items():
         for q in QUALITIES:
+            assert proc.encode_jpeg(a, q) == pillow_jpeg(a, q), (name, q)
+
+
+@pytest.mark.parametrize("H,W", jx.SIZES)
+def test_encode_jpeg_extreme_coefficients(proc, H, W):
+    """Category-11 DC differences in all three components and category-10 AC coefficients (tests/jpeg_extremes.py)."""
+    for name, a in jx.frames(H, W).items():
+        for q in jx.QUALITIES:
             assert proc.encode_jpeg(a, q) == pillow_jpeg(a, q), (name, q)
 
 

@@ -6,6 +6,7 @@ import gc
 import numpy as np
 import pytest
 
+import jpeg_extremes as jx
 from helpers import SEED, stocks, synthetic_frame
 from test_gpu_jpeg import smooth
 from test_gpu_jpeg_stream import MARK, render_kw, streamed
@@ -35,6 +36,16 @@ def test_encode_jpeg_options_write_pillows_bytes(proc, H, W):
                 e = EXIF if (q + s) % 2 else b""
                 got = proc.encode_jpeg(a, q, subsampling=s, optimize=o, exif=e)
                 assert got == pillow_jpeg(a, q, s, o, e), (name, q, s, o)
+
+
+@pytest.mark.parametrize("H,W", jx.SIZES)
+def test_encode_jpeg_options_extreme_coefficients(proc, H, W):
+    """tests/jpeg_extremes.py through every sampling, with the standard and the optimized tables: in 4:4:4 and 4:2:2 the 8 x 8
+    colour checker keeps its chroma swing, and optimize has to build codes for the categories no other frame uses."""
+    for name, a in jx.frames(H, W).items():
+        for q in jx.QUALITIES:
+            for s, o in OPTIONS:
+                assert proc.encode_jpeg(a, q, subsampling=s, optimize=o) == pillow_jpeg(a, q, s, o), (name, q, s, o)
 
 
 @pytest.mark.parametrize("H,W", ((4000, 6000), (12288, 8192)))

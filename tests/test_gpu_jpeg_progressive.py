@@ -4,6 +4,7 @@ progressive=True write the bytes Pillow's `save(f, "JPEG", quality=q, subsamplin
 import numpy as np
 import pytest
 
+import jpeg_extremes as jx
 from helpers import SEED, stocks, synthetic_frame
 from test_gpu_jpeg import smooth
 from test_gpu_jpeg_stream import MARK, render_kw
@@ -32,6 +33,15 @@ def test_encode_jpeg_progressive_writes_pillows_bytes(proc, H, W):
                 e = EXIF if (q + s) % 2 else b""
                 got = proc.encode_jpeg(a, q, subsampling=s, progressive=True, exif=e)
                 assert got == pillow_progressive(a, q, s, e), (name, q, s)
+
+
+@pytest.mark.parametrize("H,W", jx.SIZES)
+def test_encode_jpeg_progressive_extreme_coefficients(proc, H, W):
+    """tests/jpeg_extremes.py: the DC scans with category-11 differences, the AC scans with 10-bit magnitudes to refine."""
+    for name, a in jx.frames(H, W).items():
+        for q in jx.QUALITIES:
+            for s in (0, 1, 2):
+                assert proc.encode_jpeg(a, q, subsampling=s, progressive=True) == pillow_progressive(a, q, s), (name, q, s)
 
 
 def test_run_flushes_on_both_caps(proc):

@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import jpeg_extremes as jx
 from arena import Arena
 from helpers import SEED, stocks, synthetic_frame
 from test_gpu_jpeg_options import STREAM_CASES
@@ -51,6 +52,18 @@ def test_encode_jpeg_restart_intervals_write_pillows_bytes(proc, H, W):
                         got = proc.encode_jpeg(dev, q, subsampling=s, optimize=o, restart_marker_blocks=blocks, restart_marker_rows=rows)
                         want = pillow_save(a, q, s, o, restart_marker_blocks=blocks, restart_marker_rows=rows)
                         assert got == want, (s, o, blocks, rows)
+
+
+@pytest.mark.parametrize("H,W", jx.SIZES)
+def test_encode_jpeg_restart_extreme_coefficients(proc, H, W):
+    """tests/jpeg_extremes.py with an interval of three MCUs: category-11 DC differences inside an interval, and the predictor
+    reset right behind a DC at the end of its range."""
+    for name, a in jx.frames(H, W).items():
+        for q in jx.QUALITIES:
+            for s in (0, 1, 2):
+                for o in (False, True):
+                    got = proc.encode_jpeg(a, q, subsampling=s, optimize=o, restart_marker_blocks=3)
+                    assert got == pillow_save(a, q, s, o, restart_marker_blocks=3), (name, q, s, o)
 
 
 def test_one_mcu_gets_a_dri_and_no_marker(proc):

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import jpeg_extremes as jx
 import jpeg_model as jm
 
 Image = pytest.importorskip("PIL.Image")
@@ -65,6 +66,27 @@ def test_bound_holds_for_the_worst_case():
         scan_bits = 8 * (len(out) - len(jm.header(100, H, W)) - 2 - out.count(b"\xff\x00"))
         assert scan_bits <= jm.mcus(H, W) * 6 * jm.block_bound_bits()
     assert jm.block_bound_bits() == 1660
+
+
+# ---- coefficients at the ends of their ranges (tests/jpeg_extremes.py)
+@pytest.mark.parametrize("H,W", jx.SIZES)
+def test_model_writes_pillows_bytes_for_extreme_coefficients(H, W):
+    for name, a in jx.frames(H, W).items():
+        for q in jx.QUALITIES:
+            assert jm.encode(a, q) == pillow_jpeg(a, q), (name, q)
+
+
+def test_extreme_frames_are_not_vacuous():
+    """What the frames are for, counted on the coefficients the 4:2:0 baseline scan codes at quality 100: the widest DC difference
+    (category 11) in every component and the longest AC symbol (category 10); contents() stops at AC category 9 and, in luma and
+    Cb, at DC category 10."""
+    cat = {name: jx.categories(a) for name, a in jx.frames(64, 96).items()}
+    assert cat["block_checker"]["y_dc"] == 11 and cat["blue_yellow"]["y_dc"] == 11
+    assert cat["blue_yellow"]["cb_dc"] == 11
+    assert cat["red_cyan16"]["cr_dc"] == 11
+    assert cat["pixel_checker"]["ac"] == 10 and cat["lines"]["ac"] == 10
+    usual = [jx.categories(a, q) for a in contents(64, 96).values() for q in (100, 75)]
+    assert max(c["ac"] for c in usual) <= 9 and max(max(c["y_dc"], c["cb_dc"]) for c in usual) <= 10
 
 
 # ---- the library's plan-only exports (no GPU, no context)
