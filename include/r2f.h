@@ -486,6 +486,24 @@ R2F_API int r2f_demosaic_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0
                      const r2f_demosaic_params* params, uint16_t* dst_u16_hwc3, int y0, int y1, void* stream);
 /* r2f_demosaic_u16's tile (test shapes are derived from it). */
 enum { R2F_DEMOSAIC_TILE_W = 64, R2F_DEMOSAIC_TILE_H = 32 };
+/* The demosaic fused with the hand-off below, for a mosaic that streams in row bands: with D the uint16 (out_h, out_w, 3) frame of
+ * r2f_demosaic_u16's definition (full or half size) and (row0, col0, rows, cols) a non-empty window inside D,
+ *   dst[y, x, c] = fminf((float)D[row0 + y, col0 + x, c] / divisor * factor, 65504.0f)
+ * -- r2f_decode_u16's expression, the same two correctly rounded fp32 operations: bit-identical to r2f_decode_u16 of that window of
+ * r2f_demosaic_u16's frame, without the uint16 frame in between (12 bytes per pixel of traffic and one launch less).  dst: float32
+ * (rows, cols, 3), contiguous.  Writes window rows [y0, y1) of dst and nothing else.  Full size reads mosaic rows
+ * [row0 + y0 - 4, row0 + y1 + 4) clipped to [0, H), half size [2 (row0 + y0), 2 (row0 + y1)); those rows must lie inside the source
+ * window, else R2F_EINVAL before any launch.  The bytes depend on neither the cut, the pitch, the source's alignment nor the window's
+ * origin.  Refused: everything r2f_demosaic_u16 refuses, a window that is empty or not inside D, y0 > y1, y0 < 0, y1 > rows,
+ * divisor <= 0.  The kernels are r2f_demosaic_u16's with a second epilogue: the full-size tile grid stays anchored to the frame's
+ * columns (an odd col0 masks lanes, it does not move the tiles), and a wave's row segment leaves as contiguous float32 (768 bytes for
+ * a full tile) in 16-byte stores behind the floats that lead to a 16-byte boundary.
+ * What streams with it (raw2film_amd: HipProcessor): a mosaic whose exposure is given in stops, without quarter turns, a lens step
+ * or a device pre-path; exposure measured on the device (the statistic is the whole demosaiced frame's), turns and the lens step
+ * keep the one-piece path r2f_demosaic_u16 -> r2f_decode_u16. */
+R2F_API int r2f_demosaic_f32(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
+                     const r2f_demosaic_params* params, int row0, int col0, int rows, int cols, float divisor, float factor,
+                     float* dst_f32_hwc3, int y0, int y1, void* stream);
 
 /* The hand-off from RAW decoding: the last two lines of raw_to_linear (raw_conversion.py:50-52) applied to LibRaw's 16-bit
  * output on the device, so that a decoded frame crosses PCIe as uint16 (6 bytes per pixel) instead of float32 (12 or 16):

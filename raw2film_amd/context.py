@@ -558,6 +558,16 @@ class HipContext:
                                                self._stream()))
         return out
 
+    def _check_mosaic(self, mosaic, params, what):
+        """demosaic_u16's and demosaic_f32's view of their source -> (H, W, the r2f_demosaic_params)."""
+        torch = self._torch
+        if not (isinstance(mosaic, torch.Tensor) and mosaic.is_cuda and mosaic.dtype in (torch.uint16, torch.int16) and mosaic.dim() == 2
+                and mosaic.shape[0] >= 2 and mosaic.shape[1] >= 2 and mosaic.stride(1) == 1 and mosaic.stride(0) >= mosaic.shape[1]):
+            raise ValueError(f"{what} needs a uint16 (H, W) CUDA mosaic of at least 2 x 2 samples with contiguous rows")
+        self._same_device(mosaic, "mosaic")
+        H, W = int(mosaic.shape[0]), int(mosaic.shape[1])
+        return H, W, params if isinstance(params, _lib.DemosaicParams) else params.plan(H, W)
+
     def demosaic_u16(self, mosaic, params, out=None, rows=None):
         """The Bayer demosaic of include/r2f.h (r2f_demosaic_u16: black / scale, PPG or the half-size form, camera matrix, clip)
         of a uint16 (H, W) CUDA mosaic (int16 tensors are read as the same bits; rows may be pitched: stride(0) >= W, stride(1)
@@ -565,13 +575,7 @@ class HipContext:
         params: a raw2film_amd.raw.RawProfile (planned full size for this mosaic) or the r2f_demosaic_params of its size.
         rows = (y0, y1): only those output rows of `out` are written (default: all)."""
         torch = self._torch
-        if not (isinstance(mosaic, torch.Tensor) and mosaic.is_cuda and mosaic.dtype in (torch.uint16, torch.int16) and mosaic.dim() == 2
-                and mosaic.shape[0] >= 2 and mosaic.shape[1] >= 2 and mosaic.stride(1) == 1 and mosaic.stride(0) >= mosaic.shape[1]):
-            raise ValueError("demosaic_u16 needs a uint16 (H, W) CUDA mosaic of at least 2 x 2 samples with contiguous rows")
-        self._same_device(mosaic, "mosaic")
-        H, W = int(mosaic.shape[0]), int(mosaic.shape[1])
-        if not isinstance(params, _lib.DemosaicParams):
-            params = params.plan(H, W)
+        H, W, params = self._check_mosaic(mosaic, params, "demosaic_u16")
         shape = (int(params.out_h), int(params.out_w), 3)
         if out is None:
             out = torch.empty(shape, dtype=mosaic.dtype, device=self.device)
@@ -583,6 +587,30 @@ class HipContext:
         y0, y1 = (0, shape[0]) if rows is None else (int(rows[0]), int(rows[1]))
         self._check(self._lib.r2f_demosaic_u16(self._h, mosaic.data_ptr(), 0, H, int(mosaic.stride(0)), H, W, C.byref(params),
                                                out.data_ptr(), y0, y1, self._stream()))
+        return out
+
+    def demosaic_f32(self, mosaic, params, factor: float, divisor: float = 65535.0, window=None, out=None, rows=None):
+        """demosaic_u16 and decode_u16 in one kernel (r2f_demosaic_f32): window = (row0, col0, rows, cols) of the demosaiced frame
+        (default: all of it) -> float32 (rows, cols, 3), bit-identical to decode_u16(demosaic_u16(mosaic)[window], factor, divisor).
+        mosaic, params: demosaic_u16's; the mosaic may be the whole landing buffer of which only some rows have arrived -- a call
+        reads the rows its contract names and no others.  rows = (y0, y1): only those rows of the window are written."""
+        torch = self._torch
+        H, W, params = self._check_mosaic(mosaic, params, "demosaic_f32")
+        r0, c0, nr, nc = (0, 0, int(params.out_h), int(params.out_w)) if window is None else (int(v) for v in window)
+        if not (0 <= r0 and 0 <= c0 and nr > 0 and nc > 0 and r0 + nr <= params.out_h and c0 + nc <= params.out_w):
+            raise ValueError(f"demosaic_f32: window {(r0, c0, nr, nc)} is not inside the {params.out_h} x {params.out_w} frame")
+        shape = (nr, nc, 3)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                  and tuple(out.shape) == shape):
+            raise ValueError(f"demosaic_f32: out must be a contiguous float32 CUDA tensor of shape {shape}")
+        else:
+            self._same_device(out, "out")
+        y0, y1 = (0, nr) if rows is None else (int(rows[0]), int(rows[1]))
+        self._check(self._lib.r2f_demosaic_f32(self._h, mosaic.data_ptr(), 0, H, int(mosaic.stride(0)), H, W, C.byref(params), r0, c0, nr,
+                                               nc, float(np.float32(divisor)), float(np.float32(factor)), out.data_ptr(), y0, y1,
+                                               self._stream()))
         return out
 
     def decode_u16(self, image_u16, factor: float, divisor: float = 65535.0, out=None):

@@ -143,6 +143,13 @@ __device__ __forceinline__ int reflect101(int i, int n) {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// The uint16 hand-off's sample (include/r2f.h, r2f_decode_u16: raw_conversion.py:50-52 and the upload clamp of gpu_processor.py:275):
+// one correctly rounded fp32 division, one multiply, the clamp.  The one text of it: the decode kernels (r2f_post.hip) and the
+// demosaic's float epilogue (r2f_demosaic.hip) give the same bits for the same sample.
+__device__ __forceinline__ float decode_sample(unsigned u, float divisor, float factor) {
+    return fminf((float)u / divisor * factor, 65504.0f);
+}
+
 // ---------------------------------------------------------------------------- plane and input accesses
 // Four consecutive pixels of global row `gy` starting at column x, of three planes.
 // NT: non-temporal loads (ld4_stream) -- for planes that are read exactly once and written by another kernel (the tail's densities:

@@ -302,8 +302,8 @@ __device__ __forceinline__ void decode_quad(const uint16_t* src, float* dst, lon
         float f[12];
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
-            f[2 * i] = fminf((float)(w[i] & 0xffffu) / divisor * factor, 65504.0f);
-            f[2 * i + 1] = fminf((float)(w[i] >> 16) / divisor * factor, 65504.0f);
+            f[2 * i] = decode_sample(w[i] & 0xffffu, divisor, factor);
+            f[2 * i + 1] = decode_sample(w[i] >> 16, divisor, factor);
         }
         float4* d4 = reinterpret_cast<float4*>(dst + p0 * 3);
         d4[0] = make_float4(f[0], f[1], f[2], f[3]);
@@ -312,7 +312,7 @@ __device__ __forceinline__ void decode_quad(const uint16_t* src, float* dst, lon
         return;
     }
     for (long long p = p0; p < min(p0 + 4, n); ++p)
-        for (int c = 0; c < 3; ++c) dst[p * 3 + c] = fminf((float)src[p * ch + c] / divisor * factor, 65504.0f);
+        for (int c = 0; c < 3; ++c) dst[p * 3 + c] = decode_sample(src[p * ch + c], divisor, factor);
 }
 
 __global__ __launch_bounds__(256) void decode_u16_kernel(const DecodeU16Args a) {

@@ -355,7 +355,9 @@ class HipProcessor:
         `image_array` is the mosaic and the payload gains `demosaic`: the r2f_demosaic_params, and the `window` (row0, col0, rows,
         cols) and quarter turns that the host applies to a decoded frame's array here and the device applies to the demosaiced one.
         No RGB frame exists on the host, so exposure=None is measured on the device like exposure="device"; where that is refused (a
-        turned or rotated frame) the call needs explicit stops."""
+        turned or rotated frame) the call needs explicit stops.  With the stops given, no quarter turn and no lens step, the payload
+        of a large mosaic streams in row bands (payload.stream_rejection): band k travels as the mosaic rows its demosaic reads
+        (payload.mosaic_upload_bounds) and is demosaiced straight into the float frame (r2f_demosaic_f32)."""
         on_device = exposure_on_device(exposure)
         phase1.check_profiles(raw_profile, lens_profile, lens_correction, cam, lens)
         # _internal (load_image_texture: the payload never leaves this object): no alpha plane, and the clamp of
@@ -448,8 +450,12 @@ class HipProcessor:
         lens_profile (raw2film_amd.lens.LensProfile) with lens_correction=True: the whole frame is uploaded and corrected on the
         device before any crop (extract_image_data_cpu); such a frame never streams in row bands.
         raw_profile (raw2film_amd.raw.RawProfile): `src` is a Bayer mosaic, uint16 (H, W) -- 2 bytes per pixel across PCIe --,
-        demosaiced on the device (`half_size` selects the form) into the uint16 frame the rest of the call reads; it does not
-        stream in row bands either.  exposure=None is then measured on the device (extract_image_data_cpu)."""
+        demosaiced on the device (`half_size` selects the form) into the uint16 frame the rest of the call reads.  exposure=None is
+        then measured on the device (extract_image_data_cpu).  A large cache=False mosaic streams in row bands like a decoded frame
+        when its exposure is given in stops, rotate_times is a multiple of 4 and no lens step follows: each band is demosaiced
+        into the float frame as its mosaic rows arrive (r2f_demosaic_f32), with the bytes of the one-piece call.  Without stops
+        (the device's statistic is the whole demosaiced frame's), turned, or with a lens_profile it is demosaiced whole, and
+        `stream_rejected` of an export names the demosaic step and the reason."""
         settings = dict(locals())  # every keyword of the signature (the unknown ones in `_` aside), named nowhere else
         exposure_on_device(exposure)  # (any string but "device" raises before any work starts)
         settings["output_bits"] = check_output_bits(output_bits, dst_texture)
@@ -734,9 +740,15 @@ class HipProcessor:
 
     def _host_stream_gate(self, src, settings):
         """payload.host_stream_gate of a call's `settings` (process()'s keywords): why its frame is rendered in one piece, or None."""
+        mosaic = settings["raw_profile"] is not None
+        exposure = settings["exposure"]
         return host_stream_gate(src, self.stream_bands, settings["rotation"], settings["chroma_nr"], settings["canvas_mode"],
                                 settings["highlight_burn"], bool(settings["lens_correction"]) and settings["lens_profile"] is not None,
-                                settings["raw_profile"] is not None)
+                                mosaic, stops=exposure is not None and not isinstance(exposure, str),
+                                rotate_times=settings["rotate_times"],
+                                frame_samples=phase1.mosaic_frame_samples(src, settings["half_size"],
+                                                                          settings["frame_width"] / settings["frame_height"],
+                                                                          settings["flip"], settings["zoom"]) if mosaic else None)
 
     def _export_preloaded(self, what, settings, stream, early=()) -> bool:
         """The prologue of an export of a phase-1 payload: no textures, then with stream=True `stream_rejected` from the export's
@@ -848,6 +860,8 @@ class HipProcessor:
         The FFT stencils' windows are anchored at a call's first row, so a band's outputs agree with the whole-frame render's to the
         FFT form's rounding (an fp32 ulp on a handful of samples, like a row shard's); pointwise configurations agree bit for bit.
         A uint16 frame (LibRaw's 16-bit output: half the upload) is converted band by band on the device as it arrives.
+        A Bayer mosaic (a sixth of the upload) is demosaiced band by band into the float frame: its bands reach 4 mosaic rows into
+        their neighbours, which travel with the band that needs them first (payload.mosaic_upload_bounds).
         Returns None when the frame does not qualify (the caller then takes the one-after-the-other path): a device pre-path
         (rotation, chroma NR, scaling), a canvas, a highlight burn (a function of the whole grained frame), a small frame.
         The two-phase API's device phase (process_preloaded, submit_preloaded: batch export) streams its payload the same way."""
@@ -901,6 +915,9 @@ class HipProcessor:
         shape = tuple(host.shape)
         if payload.get("u16_window") is not None and len(shape) == 3:  # (the pipeline's frame is the window of the uploaded one)
             shape = tuple(int(v) for v in payload["u16_window"][2:]) + shape[2:]
+        step = payload.get("demosaic")
+        if step and step.get("window") is not None:  # (a mosaic: the window of the demosaiced frame)
+            shape = tuple(int(v) for v in step["window"][2:]) + (3,)
         self.stream_rejected = stream_rejection(payload, shape, str(host.dtype), host.is_cuda, final_scaling,
                                                 settings.get("canvas_mode", "No"))
         if self.stream_rejected is not None:
@@ -914,7 +931,7 @@ class HipProcessor:
         bounds, self.stream_rejected = plan_bands(H, int(params.flags), ha, ma, self.stream_bands, self.stream_taper)
         if bounds is None:
             return None
-        bufs = self._stream_buffers(host, mtf, H, W, settings.get("output_bits", 8))
+        bufs = self._stream_buffers(host, mtf, H, W, settings.get("output_bits", 8), mosaic=bool(step))
         p = _lib.Params.from_buffer_copy(params)
         p.flags |= _lib.F_FRAME_RESIDENT  # the seed is written once, here; the stage calls read it from the frame block
         self.ctx.write_frame_params(p)     # (and the exposure-range record starts empty)
@@ -938,9 +955,10 @@ class HipProcessor:
         # (a JPEG is 8 bits per sample whatever `output_bits` the caller's settings carry)
         return self._stream(payload, negative_film, grain_size, grain_sigma, final_scaling, dict(settings, output_bits=8), make_sink)
 
-    def _stream_buffers(self, host, mtf, H, W, bits=8):
+    def _stream_buffers(self, host, mtf, H, W, bits=8, mosaic=False):
         """The device buffers a streamed H x W frame works in (kept for the next frame of the same kind): `host` is its payload tensor
-        (the frame itself, or the whole uint16 frame the pipeline takes a window of)."""
+        (the frame itself, the whole uint16 frame the pipeline takes a window of, or -- `mosaic` -- the Bayer mosaic, which lands in a
+        buffer of its own shape and is demosaiced straight into the float frame: no uint16 (H, W, 3) frame exists)."""
         torch = self._torch
         chans = 3 if host.dtype == torch.int16 else int(host.shape[2])  # (a payload with upstream's alpha plane, gpu_processor.py:765: 4)
         bufs = getattr(self, "_stream_bufs", None)
@@ -949,8 +967,9 @@ class HipProcessor:
                                         "image": torch.empty((H, W, chans), dtype=torch.float32, device=self.device)}
             for k in ("E", "D", "D2") if mtf else ("E", "D"):
                 bufs[k] = torch.empty((3, H, W), dtype=torch.float32, device=self.device)
-        if host.dtype == torch.int16 and (bufs.get("u16") is None or tuple(bufs["u16"].shape) != tuple(host.shape)):
-            bufs["u16"] = torch.empty(tuple(host.shape), dtype=torch.int16, device=self.device)
+        landing = "mosaic" if mosaic else "u16"
+        if host.dtype == torch.int16 and (bufs.get(landing) is None or tuple(bufs[landing].shape) != tuple(host.shape)):
+            bufs[landing] = torch.empty(tuple(host.shape), dtype=torch.int16, device=self.device)
         self._stream_result(bufs, self._depths[bits])
         return bufs
 
@@ -973,12 +992,15 @@ class HipProcessor:
         pointwise = not (hal or mtf or grain)
         is_u16 = host.dtype == torch.int16
         image, E, D = bufs["image"], bufs["E"], bufs["D"]
-        landing = bufs["u16"] if is_u16 else image
+        step = payload.get("demosaic")  # a Bayer mosaic: bands of its window, demosaiced into `image` as their rows arrive
+        landing = bufs["mosaic"] if step else bufs["u16"] if is_u16 else image
         # exposure="device": the whole uint16 frame goes up (the statistic is the whole frame's), the bands are rows of its window --
         # band k travels as the frame rows `ub[k]:ub[k + 1]`, the first and the last taking the rows above and below the window along
         auto = is_u16 and payload.get("u16_factor") == DEVICE_EXPOSURE
         r0, c0, _, nc = payload["u16_window"] if auto else (0, 0, 0, 0)
         ub = [0] + [b + r0 for b in bounds[1:-1]] + [int(host.shape[0])] if auto else bounds
+        if step:  # band k travels with the mosaic rows its demosaic reads beyond those of the bands before it
+            ub = phase1.mosaic_upload_bounds(bounds, step["window"], int(host.shape[0]), bool(step["params"].half_size))
         up, down = self._copy_streams()
         compute = torch.cuda.current_stream(self.device)
         up.wait_stream(compute)  # (the buffers may still be read by the previous frame's launches)
@@ -1007,6 +1029,16 @@ class HipProcessor:
         uploader = None if host.is_pinned() else ThreadPoolExecutor(max_workers=1, thread_name_prefix="r2f-upload",
                                                                      initializer=torch.cuda.set_device, initargs=(self.device,))
         arrivals = None if uploader is None else [uploader.submit(send_up, k) for k in range(n)]
+        # A pinned mosaic: every upload is queued now.  Its bytes are a third of the RGB frame's, so the render, not the upload, sets
+        # the pace; with upload k queued only when band k's turn came the call was no faster than in one piece (100 MP: 15.9 against
+        # 15.8 ms, profiles/r17_mosaic_stream_probe.txt).
+        queued = [send_up(k) for k in range(n)] if step and uploader is None else None
+
+        def arrival(k):
+            if queued is not None:
+                return queued[k]
+            return send_up(k) if arrivals is None else arrivals[k].result()
+
         dens = sharp = tail = ident = 0  # bands through the halation, the MTF, the tail; the last front call's identity flag
         try:
             if auto:
@@ -1014,16 +1046,18 @@ class HipProcessor:
                 # first decode reads it, and the host never learns it in between (the render starts behind the upload in this mode)
                 Hf, Wf, root = int(host.shape[0]), int(host.shape[1]), payload["exposure_root"]
                 for k in range(n):
-                    compute.wait_event(send_up(k) if arrivals is None else arrivals[k].result())
+                    compute.wait_event(arrival(k))
                     ctx.exposure_rows(landing[ub[k]:ub[k + 1]], root, H=Hf, gy0=ub[k])
                 ctx.exposure_finish(Hf, Wf, root)
                 self._auto_exposure_pending = True
             for k in range(n):
                 a0, a1 = bounds[k], bounds[k + 1]
                 if not auto:
-                    compute.wait_event(send_up(k) if arrivals is None else arrivals[k].result())
+                    compute.wait_event(arrival(k))
                 rows = image[a0:a1]
-                if auto:
+                if step:
+                    ctx.demosaic_f32(landing, step["params"], payload["u16_factor"], window=step["window"], out=image, rows=(a0, a1))
+                elif auto:
                     ctx.decode_u16_auto(landing[r0 + a0:r0 + a1], (0, c0, a1 - a0, nc), out=rows)
                 elif is_u16:
                     ctx.decode_u16(landing[a0:a1], payload["u16_factor"], out=rows)

@@ -21,22 +21,61 @@ from . import geometry
 from .lens import LensProfile
 from .raw import RawProfile
 
-_DEMOSAIC_REJECTED = ("the demosaic step (raw_profile): the mosaic is demosaiced whole on the device before the pipeline; its row "
-                      "contract (r2f_demosaic_u16) is not streamed yet")
+_DEMOSAIC_REJECTED = "the demosaic step (raw_profile): "  # every refusal of a mosaic begins with it, then says why
 _LENS_REJECTED = "the lens step (lens_profile): its gather reads the whole frame, which a row band does not hold"
+STREAM_MIN_SAMPLES = 1 << 24  # samples of the pipeline's frame from which a frame streams (16.7 M)
+DEMOSAIC_REACH = 4  # mosaic rows above and below an output row that the full-size demosaic reads (r2f_demosaic_f32)
+
+
+def mosaic_rejection(stops, rotate_times, lens, samples):
+    """Why a Bayer mosaic is demosaiced whole instead of band by band (r2f_demosaic_f32), or None.  stops: the exposure is given in
+    stops; samples: rows x cols x 3 of the window of the demosaiced frame that the pipeline takes, or None when nobody cut one."""
+    if not stops:
+        return _DEMOSAIC_REJECTED + ("the exposure is not given in stops: measured on the device, its statistic is the whole demosaiced "
+                                     "frame's, which is demosaiced in one piece for it")
+    if int(rotate_times) % 4:
+        return _DEMOSAIC_REJECTED + f"rotate_times = {rotate_times!r}: the quarter turns are applied to the whole demosaiced frame"
+    if lens:
+        return _DEMOSAIC_REJECTED + "the lens step (lens_profile) behind it reads the whole demosaiced frame"
+    if samples is None:
+        return _DEMOSAIC_REJECTED + "no window of the demosaiced frame is known for it"
+    if samples < STREAM_MIN_SAMPLES:
+        return _DEMOSAIC_REJECTED + f"its window of the demosaiced frame has {samples} samples, below 16.7 M"
+    return None
+
+
+def mosaic_upload_bounds(bounds, window, Hm, half_size) -> list:
+    """The mosaic rows that travel with each band of a streamed mosaic: upload k is rows [ub[k], ub[k + 1]), and band k's demosaic
+    (r2f_demosaic_f32 of the window's rows [bounds[k], bounds[k + 1])) reads nothing outside [ub[0], ub[k + 1]).  bounds: plan_bands'
+    of the window's rows; window: (row0, col0, rows, cols) of the demosaiced frame; Hm: the mosaic's rows.  Full size reaches
+    DEMOSAIC_REACH rows past a band's ends, half size reads the two mosaic rows of each output row; rows outside [ub[0], ub[-1])
+    are never uploaded."""
+    row0, rows = int(window[0]), int(window[2])
+    assert bounds[0] == 0 and bounds[-1] == rows
+    if half_size:
+        return [2 * (row0 + int(b)) for b in bounds]
+    r = DEMOSAIC_REACH
+    return ([max(row0 - r, 0)] + [min(row0 + int(b) + r, Hm) for b in bounds[1:-1]] + [min(row0 + rows + r, Hm)])
 
 
 def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canvas_mode="No"):
     """Why a phase-1 payload cannot stream through the pipeline in row bands, or None (its render's stages have the last word:
-    plan_bands).  `shape`, `dtype`: of its frame as a tensor (_payload_tensor: "torch.float32", or "torch.int16" for uint16)."""
+    plan_bands).  `shape`, `dtype`: of its frame as a tensor (_payload_tensor: "torch.float32", or "torch.int16" for uint16).  The
+    frame of a mosaic (`demosaic`) is the window of the demosaiced frame, whatever `shape` says of the mosaic."""
     is_u16 = dtype == "torch.int16"  # LibRaw's 16-bit output: converted band by band on the device (raw_conversion.py:50-52)
-    if payload.get("demosaic"):
-        return _DEMOSAIC_REJECTED
+    step = payload.get("demosaic")
+    if step:
+        window = step.get("window")
+        why = mosaic_rejection(isinstance(payload.get("u16_factor"), float), step.get("rotate_times") or 0, payload.get("lens"),
+                               None if window is None else int(window[2]) * int(window[3]) * 3)
+        if why is not None:
+            return why
+        shape = (int(window[2]), int(window[3]), 3)
     if payload.get("lens"):
         return _LENS_REJECTED
     if (payload.get("warp") or payload.get("resize_to") or payload.get("upscale_to") or payload.get("chroma_nr")
             or payload.get("canvas_resolution") or canvas_mode != "No" or on_device or len(shape) != 3
-            or int(shape[2]) not in (3, 4) or math.prod(shape) < (1 << 24) or dtype not in ("torch.float32", "torch.int16")
+            or int(shape[2]) not in (3, 4) or math.prod(shape) < STREAM_MIN_SAMPLES or dtype not in ("torch.float32", "torch.int16")
             or (payload.get("u16_factor") is None) == is_u16):  # (a uint16 frame comes with its exposure factor, a float one without)
         return ("a device pre-path, a canvas, or a frame below 16.7 M samples: " + ", ".join(
             f"{k} = {payload.get(k)!r}" for k in ("warp", "resize_to", "upscale_to", "chroma_nr", "canvas_resolution", "u16_factor",
@@ -47,24 +86,40 @@ def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canv
     return None
 
 
-def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="No", highlight_burn=0.0, lens=False, demosaic=False):
+def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="No", highlight_burn=0.0, lens=False, demosaic=False, *,
+                     stops=False, rotate_times=0, frame_samples=None):
     """Why process(src, cache=False) renders a frame in one piece before it extracts its payload (stream_rejection and plan_bands
     come after that), or None.  lens: the call corrects the lens (lens_correction with a lens_profile); demosaic: its source is a
-    Bayer mosaic (raw_profile)."""
+    Bayer mosaic (raw_profile), for which stops says that the exposure is given in stops, rotate_times is the call's, and
+    frame_samples the samples of the window of the demosaiced frame that the pipeline takes (mosaic_frame_samples)."""
     if stream_bands <= 1:
         return f"stream_bands = {stream_bands}"
     if demosaic:
-        return _DEMOSAIC_REJECTED
+        why = mosaic_rejection(stops, rotate_times, lens, frame_samples)
+        if why is not None:
+            return why
     if lens:
         return _LENS_REJECTED
     if not isinstance(src, np.ndarray):
         return f"the source is a {type(src).__name__}, not a host array"
-    if src.size < (1 << 24):
+    if not demosaic and src.size < STREAM_MIN_SAMPLES:
         return f"a frame of {src.size} samples, below 16.7 M"
     if rotation or chroma_nr or canvas_mode != "No" or highlight_burn:
         return (f"a device pre-path, a canvas or a highlight burn: rotation = {rotation!r}, chroma_nr = {chroma_nr!r}, "
                 f"canvas_mode = {canvas_mode!r}, highlight_burn = {highlight_burn!r}")
     return None
+
+
+def mosaic_frame_samples(src, half_size, aspect, flip, zoom):
+    """host_stream_gate's frame_samples for a mosaic `src`: rows x cols x 3 of the window that the aspect and zoom crops keep of
+    its demosaiced frame (plan_crops without a rotation, which the gate refuses by itself), or None when `src` is no 2-D array."""
+    if not isinstance(src, np.ndarray) or src.ndim != 2:
+        return None
+    rows, cols = (src.shape[0] // 2, src.shape[1] // 2) if half_size else src.shape
+    if rows < 1 or cols < 1:
+        return None
+    window = plan_crops(rows, cols, True, aspect, flip, zoom, 0.0, 0, False, False, True).demosaic["window"]
+    return max(int(window[2]), 0) * max(int(window[3]), 0) * 3
 
 
 def check_profiles(raw_profile, lens_profile, lens_correction, cam, lens):

@@ -17,6 +17,14 @@ the same range -- the calls' times do not depend on the picture, and a 100 MP Nu
 Kernels, in this process (device events, median of round medians): r2f_demosaic_u16 full and half size at both sensor sizes, beside
 r2f_stream_copy over the same byte count (8 B per mosaic sample at full size: 2 read, 6 written; 3.5 B per sample at half size) in the
 same run.
+
+    python tools/demosaic_probe.py --stream [--out FILE] [--repeats N] [--rounds R]
+
+The streamed mosaic (profiles/r17_mosaic_stream_probe.txt), all in this process.  Kernels: r2f_demosaic_f32 against r2f_demosaic_u16
+followed by r2f_decode_u16 on the same frame, with the bytes each moves.  Calls: process(mosaic, exposure=stops, cache=False) with
+stream_bands = 16 (the mosaic in row bands), with stream_bands = 0 (one piece: what the call did before a mosaic streamed, the
+baseline) and process(uint16 RGB) streamed, each from pageable and from pinned memory; the legs take turns call by call, R rounds of N
+calls after a warm-up each; a leg's spread over all its calls is the run-to-run spread the comparison is read against.
 Needs a GPU: there is no CPU path.
 """
 
@@ -170,9 +178,103 @@ def kernels(rounds, iters, emit):
     emit()
 
 
+def stream_kernels(rounds, iters, emit):
+    import torch
+
+    from raw2film_amd.context import HipContext
+
+    ctx = HipContext(0)
+    prof = raw_profile()
+    factor = float(np.float32(2.0 ** STOPS))
+    emit(f"(a) kernels ({torch.cuda.get_device_name(0)}): device events, {iters} launches per round median, {rounds} interleaved rounds;")
+    emit("    bytes are algorithmic (every sample read once, every output written once): fused = 2 B per mosaic sample + 12 B per pixel;")
+    emit("    two kernels = 2 B per sample + 6 B per pixel written, then 6 B read + 12 B written")
+    for label, H, W in SIZES:
+        mosaic = torch.randint(0, 16384, (H, W), dtype=torch.int16, device="cuda")
+        for half in (False, True):
+            params = prof.plan(H, W, half)
+            px = params.out_h * params.out_w
+            u16 = torch.empty((params.out_h, params.out_w, 3), dtype=torch.int16, device="cuda")
+            f32 = torch.empty((params.out_h, params.out_w, 3), dtype=torch.float32, device="cuda")
+
+            def fused():
+                ctx.demosaic_f32(mosaic, params, factor, out=f32)
+
+            def two():
+                ctx.demosaic_u16(mosaic, params, out=u16)
+                ctx.decode_u16(u16, factor, out=f32)
+
+            for _ in range(3):
+                fused(), two()
+            a, b = [], []
+            for _ in range(rounds):
+                a.append(timed(torch, fused, iters))
+                b.append(timed(torch, two, iters))
+            am, bm = float(np.median(a)), float(np.median(b))
+            fused_bytes, two_bytes = 2 * H * W + 12 * px, 2 * H * W + 24 * px
+            emit(f"  {label} sensor, {'half' if half else 'full'} size: r2f_demosaic_f32 {am:.3f} ms (range {min(a):.3f} .. {max(a):.3f}), "
+                 f"{fused_bytes / 1e6:.0f} MB = {fused_bytes / am / 1e6:.0f} GB/s; r2f_demosaic_u16 + r2f_decode_u16 {bm:.3f} ms (range "
+                 f"{min(b):.3f} .. {max(b):.3f}), {two_bytes / 1e6:.0f} MB = {two_bytes / bm / 1e6:.0f} GB/s; fused / two = {am / bm:.2f}")
+            del u16, f32
+        del mosaic
+        torch.cuda.empty_cache()
+    ctx.close()
+    emit()
+
+
+def stream_calls(rounds, repeats, emit):
+    import torch
+
+    from raw2film_amd import HipProcessor, filmstock
+
+    stocks = filmstock.builtin_stocks()
+    neg, prt = stocks["Kodak Portra 400"], stocks["Kodak 2383"]
+    proc = HipProcessor(device=0, result_buffers=2)
+    emit(f"(b) calls: process(..., exposure={STOPS}, cache=False), full render (halation, MTF, grain, print film), result_buffers=2, one "
+         f"process; the legs take turns call by call, {rounds} rounds of {repeats} calls after a warm-up; wall clock with a device "
+         "synchronisation on either side")
+    legs = (("mosaic, stream_bands = 16", "mosaic", 16), ("mosaic, stream_bands = 0 (baseline)", "mosaic", 0), ("uint16 RGB, streamed", "rgb", 16))
+    for label, H, W in SIZES:
+        for half in (False, True):
+            h, w = (H // 2, W // 2) if half else (H, W)
+            rng = np.random.default_rng(H + half)
+            src = {"mosaic": rng.integers(0, 16384, (H, W), dtype=np.uint16), "rgb": rng.integers(0, 40000, (h, w, 3), dtype=np.uint16)}
+            pinned = {k: torch.from_numpy(v.view(np.int16)).pin_memory().numpy().view(np.uint16) for k, v in src.items()}
+            extra = {"mosaic": dict(raw_profile=raw_profile(), half_size=half), "rgb": {}}
+            kw = render_kw(prt, h, w)
+            times, streamed = {}, {}
+            for _ in range(rounds):
+                for r in range(repeats + 1):
+                    for memory, frames in (("pageable", src), ("pinned", pinned)):
+                        for name, kind, bands in legs:
+                            proc.stream_bands, proc.stream_rejected = bands, "not asked"
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                            res = proc.process(frames[kind], neg, 6, 0.4, **kw, **extra[kind])
+                            torch.cuda.synchronize()
+                            dt = (time.perf_counter() - t0) * 1e3
+                            assert res.shape == (h, w, 3)
+                            del res
+                            streamed[name] = proc.stream_rejected is None
+                            if r:
+                                times.setdefault((memory, name), []).append(dt)
+            proc.stream_bands = 16
+            emit(f"  {label}, {'half' if half else 'full'} size ({2 * H * W / 1e6:.0f} MB of mosaic, {6 * h * w / 1e6:.0f} MB of uint16 RGB)")
+            for memory in ("pageable", "pinned"):
+                for name, _, bands in legs:
+                    assert streamed[name] == (bands > 1), (name, proc.stream_rejected)
+                    emit(f"    {memory:<9s} {name:<36s} {spread(times[(memory, name)])}")
+                s, o, g = (statistics.median(times[(memory, name)]) for name, _, _ in legs)
+                emit(f"    {memory:<9s} streamed / one piece = {s / o:.2f}; streamed mosaic / streamed RGB = {s / g:.2f}")
+            del src, pinned
+    proc.close()
+    emit()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r16_demosaic_probe.txt"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--stream", action="store_true", help="the streamed mosaic's probe (profiles/r17_mosaic_stream_probe.txt)")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
@@ -191,10 +293,18 @@ def main():
         print(s, flush=True)
         lines.append(s)
 
-    emit("Bayer mosaic against LibRaw's uint16 RGB frame (tools/demosaic_probe.py)")
-    emit()
-    kernels(args.rounds, args.iters, emit)
-    end_to_end(args.parent, args.rounds, args.repeats, emit)
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "r17_mosaic_stream_probe.txt" if args.stream else "r16_demosaic_probe.txt")
+    if args.stream:
+        emit("A Bayer mosaic streamed in row bands against the same call in one piece (tools/demosaic_probe.py --stream)")
+        emit()
+        stream_kernels(args.rounds, args.iters, emit)
+        stream_calls(args.rounds, args.repeats, emit)
+    else:
+        emit("Bayer mosaic against LibRaw's uint16 RGB frame (tools/demosaic_probe.py)")
+        emit()
+        kernels(args.rounds, args.iters, emit)
+        end_to_end(args.parent, args.rounds, args.repeats, emit)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
