@@ -31,34 +31,17 @@ from typing import Callable, NamedTuple
 import numpy as np
 
 from . import _lib, filmstock, geometry, payload as phase1, stencils, tiff
+from .bands import band_source, plan_bands, stage_schedule
 from .context import LOG_EPS, LUT3D_SCALE, HipContext
 from .jpeg_options import _check_jpeg_image, checked_options
 from .jpeg_stream import JpegBandSink, JpegStaging, deliver
-from .payload import host_stream_gate, stream_rejection
+from .payload import DEVICE_EXPOSURE, host_stream_gate, stream_rejection
 from .results import ResultBuffers
 
 REC709_TO_XYZ = np.array(  # data.py:128-135
     [[0.4124564, 0.3575761, 0.1804375], [0.2126729, 0.7151522, 0.0721750], [0.0193339, 0.1191920, 0.9503041]],
     dtype=np.float32,
 )
-
-
-def plan_bands(H, flags, ha, ma, bands, taper):
-    """(row bounds, None) of the bands a frame of H rows streams in, or (None, why it cannot).  `flags`: prepare()'s; `ha`, `ma`:
-    (rows above, rows below) the halation / MTF stencils read, (0, 0) for a stage that does not run."""
-    if flags & _lib.F_BURN:
-        return None, "highlight burn (a function of the whole grained frame)"
-    floor_rows = max(2 * max(ha + ma) + 2, 64)  # a band holds its neighbours' halo (and is worth a launch)
-    n = min(int(bands), max(H // 512, 2))
-    while n > 1 and H // n < floor_rows:
-        n -= 1
-    if n < 2:
-        return None, f"{n} band(s) of {H} rows above the stencils' reach {ha} + {ma}"
-    bounds = [H * i // n for i in range(n + 1)]
-    # the last bands are the ones nothing hides (their stencil stages, tail and download run behind the last byte of the upload):
-    # the final `taper` of them are halved while they stay above the stencils' reach (100 MP: 23.26 -> 22.73 ms with 2)
-    cut = [(bounds[i] + bounds[i + 1]) // 2 for i in range(max(n - int(taper), 0), n) if bounds[i + 1] - bounds[i] >= 2 * floor_rows]
-    return sorted(set(bounds + cut)), None
 
 
 def check_output_bits(output_bits, dst_texture=None) -> int:
@@ -112,10 +95,6 @@ def output_depths(torch, ctx) -> dict:
 def _host16(arr):
     """The host array of a result: the uint16 view of a 16-bit frame (carried as int16, the same bits), else the array itself."""
     return arr.view(np.uint16) if arr.dtype == np.int16 else arr
-
-
-DEVICE_EXPOSURE = "device"  # exposure="device": the auto exposure of a uint16 frame is measured on the device; also the marker a
-                            # payload carries in place of its float `u16_factor`
 
 
 def exposure_on_device(exposure) -> bool:
@@ -862,6 +841,8 @@ class HipProcessor:
         A uint16 frame (LibRaw's 16-bit output: half the upload) is converted band by band on the device as it arrives.
         A Bayer mosaic (a sixth of the upload) is demosaiced band by band into the float frame: its bands reach 4 mosaic rows into
         their neighbours, which travel with the band that needs them first (payload.mosaic_upload_bounds).
+        bands.py holds the host-side plan: the bands (plan_bands), the order in which the stages take them (stage_schedule) and
+        what each kind of payload does to get its rows into the float frame (band_source); _run_bands holds the mechanics.
         Returns None when the frame does not qualify (the caller then takes the one-after-the-other path): a device pre-path
         (rotation, chroma NR, scaling), a canvas, a highlight burn (a function of the whole grained frame), a small frame.
         The two-phase API's device phase (process_preloaded, submit_preloaded: batch export) streams its payload the same way."""
@@ -889,12 +870,12 @@ class HipProcessor:
         plan = self._stream_plan(payload, negative_film, grain_size, grain_sigma, final_scaling, settings)
         if plan is None:
             return None
-        host, p, bounds, bufs, ha, ma = plan
+        host, source, p, bounds, bufs, ha, ma = plan
         depth = self._depths[settings.get("output_bits", 8)]
         out = self._stream_result(bufs, depth)
         sink, band_done = make_sink(depth, out, bounds)
         try:
-            self._run_bands(host, payload, p, bounds, bufs, ha, ma, sink, out, depth, band_done)
+            self._run_bands(host, source, p, bounds, bufs, ha, ma, sink, out, depth, band_done)
             self._collect_auto_exposure()
             res = sink.finish()
         except BaseException:
@@ -909,21 +890,16 @@ class HipProcessor:
         return res
 
     def _stream_plan(self, payload, negative_film, grain_size, grain_sigma, final_scaling, settings):
-        """Qualify a payload for the row-band path and set its frame up: (host tensor, frame params, band bounds, device buffers,
-        halation reach, MTF reach), or None with `stream_rejected` saying why it does not stream."""
+        """Qualify a payload for the row-band path and set its frame up: (host tensor, its bands.BandSource, frame params, band
+        bounds, device buffers, halation reach, MTF reach), or None with `stream_rejected` saying why it does not stream."""
         host = self._payload_tensor(payload)
-        shape = tuple(host.shape)
-        if payload.get("u16_window") is not None and len(shape) == 3:  # (the pipeline's frame is the window of the uploaded one)
-            shape = tuple(int(v) for v in payload["u16_window"][2:]) + shape[2:]
-        step = payload.get("demosaic")
-        if step and step.get("window") is not None:  # (a mosaic: the window of the demosaiced frame)
-            shape = tuple(int(v) for v in step["window"][2:]) + (3,)
-        self.stream_rejected = stream_rejection(payload, shape, str(host.dtype), host.is_cuda, final_scaling,
+        self.stream_rejected = stream_rejection(payload, tuple(host.shape), str(host.dtype), host.is_cuda, final_scaling,
                                                 settings.get("canvas_mode", "No"))
         if self.stream_rejected is not None:
             return None
         self.exposure_rejected = payload.get("exposure_rejected")
-        H, W = int(shape[0]), int(shape[1])
+        source = band_source(payload, tuple(host.shape), str(host.dtype))
+        H, W = source.frame[:2]
         params = self.prepare(negative_film, grain_size, grain_sigma, (W, H), **settings)
         hal, mtf = bool(params.flags & _lib.F_HALATION), bool(params.flags & _lib.F_MTF)
         ha = self._halation_reach if hal else (0, 0)
@@ -931,11 +907,11 @@ class HipProcessor:
         bounds, self.stream_rejected = plan_bands(H, int(params.flags), ha, ma, self.stream_bands, self.stream_taper)
         if bounds is None:
             return None
-        bufs = self._stream_buffers(host, mtf, H, W, settings.get("output_bits", 8), mosaic=bool(step))
+        bufs = self._stream_buffers(source, mtf, settings.get("output_bits", 8))
         p = _lib.Params.from_buffer_copy(params)
         p.flags |= _lib.F_FRAME_RESIDENT  # the seed is written once, here; the stage calls read it from the frame block
         self.ctx.write_frame_params(p)     # (and the exposure-range record starts empty)
-        return host, p, bounds, bufs, ha, ma
+        return host, source, p, bounds, bufs, ha, ma
 
     def _stream_jpeg(self, payload, negative_film, grain_size, grain_sigma, final_scaling, file, settings, o):
         """_stream_payload with a JPEG sink (`o`: the export's checked options; optimize and progressive never stream):
@@ -955,21 +931,19 @@ class HipProcessor:
         # (a JPEG is 8 bits per sample whatever `output_bits` the caller's settings carry)
         return self._stream(payload, negative_film, grain_size, grain_sigma, final_scaling, dict(settings, output_bits=8), make_sink)
 
-    def _stream_buffers(self, host, mtf, H, W, bits=8, mosaic=False):
-        """The device buffers a streamed H x W frame works in (kept for the next frame of the same kind): `host` is its payload tensor
-        (the frame itself, the whole uint16 frame the pipeline takes a window of, or -- `mosaic` -- the Bayer mosaic, which lands in a
-        buffer of its own shape and is demosaiced straight into the float frame: no uint16 (H, W, 3) frame exists)."""
+    def _stream_buffers(self, source, mtf, bits=8):
+        """The device buffers the streamed frame of `source` (a bands.BandSource) works in, kept for the next frame of the same kind:
+        the float frame, the stages' planes, the result, and the int16 buffer a uint16 frame or a Bayer mosaic lands in, which has
+        the payload tensor's shape (a mosaic is demosaiced straight into the float frame: no uint16 (H, W, 3) frame exists)."""
         torch = self._torch
-        chans = 3 if host.dtype == torch.int16 else int(host.shape[2])  # (a payload with upstream's alpha plane, gpu_processor.py:765: 4)
+        H, W, _ = shape = source.frame  # (a float payload with upstream's alpha plane, gpu_processor.py:765: 4 channels)
         bufs = getattr(self, "_stream_bufs", None)
-        if bufs is None or bufs["shape"] != (H, W, chans) or bufs["mtf"] != mtf:
-            bufs = self._stream_bufs = {"shape": (H, W, chans), "mtf": mtf,
-                                        "image": torch.empty((H, W, chans), dtype=torch.float32, device=self.device)}
+        if bufs is None or bufs["shape"] != shape or bufs["mtf"] != mtf:
+            bufs = self._stream_bufs = {"shape": shape, "mtf": mtf, "image": torch.empty(shape, dtype=torch.float32, device=self.device)}
             for k in ("E", "D", "D2") if mtf else ("E", "D"):
                 bufs[k] = torch.empty((3, H, W), dtype=torch.float32, device=self.device)
-        landing = "mosaic" if mosaic else "u16"
-        if host.dtype == torch.int16 and (bufs.get(landing) is None or tuple(bufs[landing].shape) != tuple(host.shape)):
-            bufs[landing] = torch.empty(tuple(host.shape), dtype=torch.int16, device=self.device)
+        if bufs.get(source.landing) is None or tuple(bufs[source.landing].shape) != source.landing_shape:  # (never the float frame)
+            bufs[source.landing] = torch.empty(source.landing_shape, dtype=torch.int16, device=self.device)
         self._stream_result(bufs, self._depths[bits])
         return bufs
 
@@ -981,26 +955,17 @@ class HipProcessor:
             bufs[key] = self._torch.empty(bufs["shape"][:2] + (3,), dtype=depth.torch_dtype, device=self.device)
         return bufs[key]
 
-    def _run_bands(self, host, payload, p, bounds, bufs, ha, ma, sink, out, depth, band_done=None):
-        """_stream's band loop (see _process_streamed): every stage runs a band as soon as the rows it reads exist (a stencil
-        stage reads into the band after its own), and the tail's rows -- written into `out`, the result at `depth` -- go back into
-        `sink` -- or, with `band_done`, band_done(b) is called instead once band b's tail is queued (on the launching stream; the
-        JPEG export's sink)."""
+    def _run_bands(self, host, source, p, bounds, bufs, ha, ma, sink, out, depth, band_done=None):
+        """_stream's band loop (see _process_streamed): the copies, their events and the one context call that each pair of
+        bands.stage_schedule stands for; `source` (bands.band_source) knows how the rows of `host` reach the float frame.  The
+        tail's rows -- written into `out`, the result at `depth` -- go back into `sink` -- or, with `band_done`, band_done(b) is
+        called instead once band b's tail is queued (on the launching stream; the JPEG export's sink)."""
         torch, ctx = self._torch, self.ctx
         H, n = int(bounds[-1]), len(bounds) - 1
         hal, mtf, grain = (bool(p.flags & f) for f in (_lib.F_HALATION, _lib.F_MTF, _lib.F_GRAIN))
         pointwise = not (hal or mtf or grain)
-        is_u16 = host.dtype == torch.int16
         image, E, D = bufs["image"], bufs["E"], bufs["D"]
-        step = payload.get("demosaic")  # a Bayer mosaic: bands of its window, demosaiced into `image` as their rows arrive
-        landing = bufs["mosaic"] if step else bufs["u16"] if is_u16 else image
-        # exposure="device": the whole uint16 frame goes up (the statistic is the whole frame's), the bands are rows of its window --
-        # band k travels as the frame rows `ub[k]:ub[k + 1]`, the first and the last taking the rows above and below the window along
-        auto = is_u16 and payload.get("u16_factor") == DEVICE_EXPOSURE
-        r0, c0, _, nc = payload["u16_window"] if auto else (0, 0, 0, 0)
-        ub = [0] + [b + r0 for b in bounds[1:-1]] + [int(host.shape[0])] if auto else bounds
-        if step:  # band k travels with the mosaic rows its demosaic reads beyond those of the bands before it
-            ub = phase1.mosaic_upload_bounds(bounds, step["window"], int(host.shape[0]), bool(step["params"].half_size))
+        landing, ub = bufs[source.landing], source.upload_bounds(bounds)
         up, down = self._copy_streams()
         compute = torch.cuda.current_stream(self.device)
         up.wait_stream(compute)  # (the buffers may still be read by the previous frame's launches)
@@ -1029,69 +994,48 @@ class HipProcessor:
         uploader = None if host.is_pinned() else ThreadPoolExecutor(max_workers=1, thread_name_prefix="r2f-upload",
                                                                      initializer=torch.cuda.set_device, initargs=(self.device,))
         arrivals = None if uploader is None else [uploader.submit(send_up, k) for k in range(n)]
-        # A pinned mosaic: every upload is queued now.  Its bytes are a third of the RGB frame's, so the render, not the upload, sets
-        # the pace; with upload k queued only when band k's turn came the call was no faster than in one piece (100 MP: 15.9 against
-        # 15.8 ms, profiles/r17_mosaic_stream_probe.txt).
-        queued = [send_up(k) for k in range(n)] if step and uploader is None else None
+        queued = [send_up(k) for k in range(n)] if source.queue_all and uploader is None else None
 
         def arrival(k):
             if queued is not None:
                 return queued[k]
             return send_up(k) if arrivals is None else arrivals[k].result()
 
-        dens = sharp = tail = ident = 0  # bands through the halation, the MTF, the tail; the last front call's identity flag
+        awaited = set()
+
+        def wait(k):  # the launching stream awaits upload k: once, ahead of whatever reads it first
+            if k not in awaited:
+                awaited.add(k)
+                compute.wait_event(arrival(k))
+
+        ident = 0  # the last front call's identity flag
         try:
-            if auto:
-                # every band's row statistic behind its arrival, then the finish: the factor is in the device-side record before the
-                # first decode reads it, and the host never learns it in between (the render starts behind the upload in this mode)
-                Hf, Wf, root = int(host.shape[0]), int(host.shape[1]), payload["exposure_root"]
-                for k in range(n):
-                    compute.wait_event(arrival(k))
-                    ctx.exposure_rows(landing[ub[k]:ub[k + 1]], root, H=Hf, gy0=ub[k])
-                ctx.exposure_finish(Hf, Wf, root)
+            if source.measure is not None:
+                source.measure(ctx, landing, ub, wait)
                 self._auto_exposure_pending = True
-            for k in range(n):
-                a0, a1 = bounds[k], bounds[k + 1]
-                if not auto:
-                    compute.wait_event(arrival(k))
-                rows = image[a0:a1]
-                if step:
-                    ctx.demosaic_f32(landing, step["params"], payload["u16_factor"], window=step["window"], out=image, rows=(a0, a1))
-                elif auto:
-                    ctx.decode_u16_auto(landing[r0 + a0:r0 + a1], (0, c0, a1 - a0, nc), out=rows)
-                elif is_u16:
-                    ctx.decode_u16(landing[a0:a1], payload["u16_factor"], out=rows)
-                elif payload.get("clip_on_device"):
-                    rows.clamp_(0.0, 65504.0)  # np.clip(image, 0, 65504) of gpu_processor.py:275, band by band
-                if pointwise:  # LUTs only: one fused pass per band, straight to the result
-                    depth.front(rows, p, out, in_gy0=a0, out_gy0=0, y0=a0, y1=a1, H_global=H)
-                    send_back(k)
-                    continue
-                if hal:
-                    ident = ctx.stage_front_split(rows, p, E, D, in_gy0=a0, y0=a0, y1=a1, H_global=H, track_range=True)
-                else:
-                    ctx.stage_front(rows, p, 1, in_gy0=a0, dst=D, dst_gy0=0, y0=a0, y1=a1, H_global=H)
-                moved = True
-                while moved:
-                    moved = False
-                    if not hal:
-                        dens = k + 1
-                    elif dens < n and k + 1 > min(dens + 1, n - 1):
-                        y0, y1 = bounds[dens], bounds[dens + 1]
-                        lo, hi = max(y0 - ha[0], 0), min(y1 + ha[1], H)
-                        ctx.stage_halation(E[:, lo:hi], D, p, src_gy0=lo, dst_gy0=0, y0=y0, y1=y1, H_global=H, identity_done=ident,
-                                           range_valid=True)
-                        dens, moved = dens + 1, True
-                    if mtf and sharp < n and dens > min(sharp + 1, n - 1):
-                        y0, y1 = bounds[sharp], bounds[sharp + 1]
-                        lo, hi = max(y0 - ma[0], 0), min(y1 + ma[1], H)
-                        ctx.stage_mtf(D[:, lo:hi], bufs["D2"], p, src_gy0=lo, dst_gy0=0, y0=y0, y1=y1, H_global=H)
-                        sharp, moved = sharp + 1, True
-                    if tail < (sharp if mtf else dens):
-                        y0, y1 = bounds[tail], bounds[tail + 1]
+            for stage, b in stage_schedule(n, hal, mtf, pointwise):
+                y0, y1 = bounds[b], bounds[b + 1]
+                if stage == "front":
+                    wait(b)
+                    source.decode(ctx, landing, image, y0, y1)
+                    rows = image[y0:y1]
+                    if pointwise:  # LUTs only: one fused pass per band, straight to the result
+                        depth.front(rows, p, out, in_gy0=y0, out_gy0=0, y0=y0, y1=y1, H_global=H)
+                    elif hal:
+                        ident = ctx.stage_front_split(rows, p, E, D, in_gy0=y0, y0=y0, y1=y1, H_global=H, track_range=True)
+                    else:
+                        ctx.stage_front(rows, p, 1, in_gy0=y0, dst=D, dst_gy0=0, y0=y0, y1=y1, H_global=H)
+                elif stage == "halation":
+                    lo, hi = max(y0 - ha[0], 0), min(y1 + ha[1], H)
+                    ctx.stage_halation(E[:, lo:hi], D, p, src_gy0=lo, dst_gy0=0, y0=y0, y1=y1, H_global=H, identity_done=ident,
+                                       range_valid=True)
+                elif stage == "mtf":
+                    lo, hi = max(y0 - ma[0], 0), min(y1 + ma[1], H)
+                    ctx.stage_mtf(D[:, lo:hi], bufs["D2"], p, src_gy0=lo, dst_gy0=0, y0=y0, y1=y1, H_global=H)
+                else:  # "tail": a pointwise band is finished already
+                    if not pointwise:
                         depth.tail(bufs["D2"] if mtf else D, p, out, src_gy0=0, out_gy0=0, y0=y0, y1=y1, H_global=H)
-                        send_back(tail)
-                        tail, moved = tail + 1, True
+                    send_back(b)
         finally:
             if uploader is not None:
                 uploader.shutdown(cancel_futures=True)

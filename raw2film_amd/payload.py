@@ -25,6 +25,8 @@ _DEMOSAIC_REJECTED = "the demosaic step (raw_profile): "  # every refusal of a m
 _LENS_REJECTED = "the lens step (lens_profile): its gather reads the whole frame, which a row band does not hold"
 STREAM_MIN_SAMPLES = 1 << 24  # samples of the pipeline's frame from which a frame streams (16.7 M)
 DEMOSAIC_REACH = 4  # mosaic rows above and below an output row that the full-size demosaic reads (r2f_demosaic_f32)
+DEVICE_EXPOSURE = "device"  # exposure="device": the auto exposure of a uint16 frame is measured on the device; also the marker a
+                            # payload carries in place of its float `u16_factor`
 
 
 def mosaic_rejection(stops, rotate_times, lens, samples):
@@ -58,10 +60,22 @@ def mosaic_upload_bounds(bounds, window, Hm, half_size) -> list:
     return ([max(row0 - r, 0)] + [min(row0 + int(b) + r, Hm) for b in bounds[1:-1]] + [min(row0 + rows + r, Hm)])
 
 
+def frame_shape(payload, shape) -> tuple:
+    """The shape of the frame the pipeline renders of a payload whose tensor has `shape`: the window of the uploaded uint16 frame
+    (`u16_window`), or of the demosaiced frame (a mosaic's `demosaic` step, where it names one), else the tensor's own shape."""
+    step = payload.get("demosaic")
+    if step:
+        window = step.get("window")
+        return tuple(shape) if window is None else (int(window[2]), int(window[3]), 3)
+    if payload.get("u16_window") is not None and len(shape) == 3:
+        return tuple(int(v) for v in payload["u16_window"][2:]) + tuple(shape[2:])
+    return tuple(shape)
+
+
 def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canvas_mode="No"):
     """Why a phase-1 payload cannot stream through the pipeline in row bands, or None (its render's stages have the last word:
-    plan_bands).  `shape`, `dtype`: of its frame as a tensor (_payload_tensor: "torch.float32", or "torch.int16" for uint16).  The
-    frame of a mosaic (`demosaic`) is the window of the demosaiced frame, whatever `shape` says of the mosaic."""
+    plan_bands).  `shape`, `dtype`: of its tensor (_payload_tensor: "torch.float32", or "torch.int16" for uint16); the frame that
+    is judged is frame_shape's."""
     is_u16 = dtype == "torch.int16"  # LibRaw's 16-bit output: converted band by band on the device (raw_conversion.py:50-52)
     step = payload.get("demosaic")
     if step:
@@ -70,9 +84,9 @@ def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canv
                                None if window is None else int(window[2]) * int(window[3]) * 3)
         if why is not None:
             return why
-        shape = (int(window[2]), int(window[3]), 3)
     if payload.get("lens"):
         return _LENS_REJECTED
+    shape = frame_shape(payload, shape)
     if (payload.get("warp") or payload.get("resize_to") or payload.get("upscale_to") or payload.get("chroma_nr")
             or payload.get("canvas_resolution") or canvas_mode != "No" or on_device or len(shape) != 3
             or int(shape[2]) not in (3, 4) or math.prod(shape) < STREAM_MIN_SAMPLES or dtype not in ("torch.float32", "torch.int16")

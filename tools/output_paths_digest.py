@@ -6,7 +6,9 @@ Every case renders a seeded synthetic frame through the public API only and prin
 its length in place of dtype and shape.  Run it on two commits, each in a process of its own, and compare the outputs line for
 line.  Non-streamed cases use 96 x 160 and 70 x 257 frames (the odd width takes the 2- and 4-byte edge stores of the uint16
 output); streamed cases use 2368 x 2368 x 3, just above the 2 ** 24 samples the gate admits, in four bands, so that the taper and
-the stencil lag are exercised.  A streamed case whose frame did not stream prints `stream_rejected` in place of a digest.
+the stencil lag are exercised; the streamed Bayer mosaics (raw_profile=, stops given) are 2400 x 2368 at full size and 4800 x 4736 at
+half size, of which the square format keeps that window.  A streamed case whose frame did not stream prints `stream_rejected` in
+place of a digest.
 The `prepath` group renders the small frames through what runs ahead of the pipeline: the crops and quarter turns, the free
 rotation, exposure="device", a LensProfile, a RawProfile mosaic at full and half size, both together, the two-phase API and the
 exports of such frames, and one encode_jpeg call with every JPEG keyword set.
@@ -156,6 +158,7 @@ def prepath_cases(proc, torch, neg, prt):
 
 
 def streamed_cases(proc, torch, neg, prt):
+    from raw2film_amd.raw import RawProfile
     from raw2film_amd.synthetic import synthetic_frame
 
     small = synthetic_frame(BIG // 8, BIG // 8, seed=8)
@@ -168,6 +171,11 @@ def streamed_cases(proc, torch, neg, prt):
     film = dict(print_film=prt, seed=20260630, exp_kelvin=6000, color_masking=1.0, halation_green_factor=0.3)
     stencils_on = dict(geom, **film)  # halation, MTF and grain: the stencil lag of the band loop
     pointwise = dict(stencils_on, grain=0, halation=False, sharpness=False)  # LUTs only: the front kernel writes the result
+    raw = RawProfile("GRBG", black=(64, 60, 66, 64), multipliers=(2.1, 1.0, 1.6),
+                     matrix=((1.62, -0.41, -0.19), (-0.28, 1.52, -0.22), (0.04, -0.52, 1.49)))
+    rng = np.random.default_rng(BIG)
+    mosaics = {"mosaic_full": (rng.integers(0, 40000, (BIG + 32, BIG), dtype=np.uint16), False),
+               "mosaic_half": (rng.integers(0, 40000, (2 * BIG + 64, 2 * BIG), dtype=np.uint16), True)}
     proc.stream_bands = 4
 
     def streamed(name, fn, repeat=True):
@@ -193,6 +201,10 @@ def streamed_cases(proc, torch, neg, prt):
             in_flight, neg, 6, 0.4, **stencils_on, **b).result()))
         streamed(f"streamed_u16_source {bits}", lambda: proc.process(u16, neg, 6, 0.4, cache=False, exposure=0.5, **stencils_on, **b))
         streamed(f"streamed_u16_device_exposure {bits}", lambda: proc.process(u16, neg, 6, 0.4, cache=False, exposure="device", **pointwise, **b))
+        for name, (mosaic, half) in mosaics.items():
+            for what, kw in (("stencils", stencils_on), ("pointwise", pointwise)):
+                streamed(f"streamed_{name} {what}/{bits}", lambda: proc.process(mosaic, neg, 6, 0.4, cache=False, raw_profile=raw,
+                                                                                 half_size=half, exposure=0.5, **kw, **b))
         streamed(f"streamed_process_tiff {bits}", lambda: proc.process_tiff(pageable, neg, 6, 0.4, stream=True, icc_profile=b"icc", **stencils_on, **b))
         streamed(f"streamed_process_preloaded_tiff {bits}", lambda: proc.process_preloaded_tiff(payload, neg, 6, 0.4, stream=True, **pointwise, **b))
     proc.stream_bands = 0  # one piece: the frame comes down into a lent pinned buffer of its depth's pool

@@ -1,7 +1,9 @@
 """process(host array, cache=False, result_buffers=2) at cfg 4 against the number of row bands the frame streams through the pipeline in
 (HipProcessor.stream_bands; 0 = upload, render, download one after the other; "16:2" = 16 bands with the last two halved,
 HipProcessor.stream_taper).    python tools/stream_bands_probe.py [bands[:taper] ...]
-R2F_PROBE_SOURCES="pinned f32,pageable f32,pinned u16,pageable u16": which source arrays (default: the pinned float frame)."""
+R2F_PROBE_SOURCES="pinned f32,pageable f32,pinned u16,pageable u16": which source arrays (default: the pinned float frame).
+R2F_PROBE_SIZE="4000x6000": rows x columns of the frame (default: cfg 4's 8192x12288).  R2F_PROBE_PKG=DIR: import raw2film_amd from
+DIR (a built checkout of another commit) instead of this tree."""
 import os
 import sys
 import time
@@ -10,12 +12,12 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.environ.get("R2F_PROBE_PKG", ROOT))
 from raw2film_amd import HipProcessor, filmstock  # noqa: E402
 from raw2film_amd.hip_processor import REC709_TO_XYZ  # noqa: E402
 from raw2film_amd.synthetic import synthetic_frame_device  # noqa: E402
 
-H, W = 8192, 12288
+H, W = (int(v) for v in os.environ.get("R2F_PROBE_SIZE", "8192x12288").split("x"))
 stocks = filmstock.builtin_stocks()
 neg, prt = stocks["Kodak Portra 400"], stocks["Kodak 2383"]
 proc = HipProcessor(device=0, result_buffers=2)
