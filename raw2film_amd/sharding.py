@@ -30,40 +30,20 @@ BatchSharder -- MANY frames (batch export, gui.py:2393-2514): frame i -> rank i 
 
 The compute itself is behind a small backend protocol so that the exchange logic can be tested
 on CPU tensors (tests/test_sharding_cpu.py); `HipStageBackend` is the product backend.
+
+Where things are: shard_plan.py holds the integer side of the row shards without torch (`plan_shard`: rows, plane extents, halos, split,
+candidate schedules; `schedule_of`; `ScheduleTuner`); here, `GraphCache` keeps the books of the captured graphs and `RowShardedRenderer`
+the planes, the exchange and ONE description of a frame -- a list of steps (`_build_steps`) that the eager launches, the capture and
+the replay all walk.  tools/shard_walk_digest.py logs what that walk asks of a backend, case by case, without a GPU.
 """
 
 from __future__ import annotations
 
 import queue
 import threading
-from dataclasses import dataclass
+from typing import NamedTuple
 
-
-def shard_rows(H: int, world: int) -> list[tuple[int, int]]:
-    """Contiguous row ranges [(r0, r1)] per rank, sizes differing by at most one row."""
-    base, extra = divmod(H, world)
-    out, r = [], 0
-    for k in range(world):
-        n = base + (1 if k < extra else 0)
-        out.append((r, r + n))
-        r += n
-    return out
-
-
-@dataclass
-class ShardPlan:
-    H: int
-    W: int
-    rank: int
-    world: int
-    r0: int
-    r1: int
-    halo_e: tuple[int, int]  # (above, below) exposure halo rows needed by the halation stencil
-    halo_d: tuple[int, int]  # (above, below) density halo rows needed by the MTF stencil
-
-    @property
-    def rows(self) -> int:
-        return self.r1 - self.r0
+from .shard_plan import ScheduleTuner, ShardPlan, plan_shard, schedule_of, shard_rows  # noqa: F401 -- (ShardPlan, shard_rows: re-exported)
 
 
 class HipStageBackend:
@@ -204,6 +184,67 @@ class HipStageBackend:
                              y0=y0, y1=y1, H_global=H)
 
 
+class GraphCache:
+    """The bookkeeping of a renderer's captured graphs -- plain Python, the graphs themselves are opaque to it.
+    key -> [frames seen with this key, its graphs or None], most recently used last, at most `LIMIT` keys: callers that hand in
+    fresh buffers every frame pile up neither graphs nor counters.
+    A capture freezes every by-value launch argument (seed, flags, curve constants, tap weights) and every device pointer into the
+    context's tables and scratch.  `state` is what the graphs were captured from: the context's change counter (table / stencil /
+    option uploads and re-allocations of its internal buffers) and the parameter block.  When it moves, every graph is dropped and
+    the frame at hand runs eagerly, like a first frame."""
+
+    LIMIT = 8
+
+    def __init__(self):
+        self._slots = {}
+        self.state = None
+
+    def slot(self, key, state) -> list:
+        """This frame's [frames seen, graphs or None], counted in.  1: a first frame with these buffers runs eagerly (tables,
+        scratch and spectra get built there); with None from 2 on: capture."""
+        if state != self.state:
+            self._slots.clear()
+            self.state = state
+        slot = self._slots.pop(key, None) or [0, None]
+        self._slots[key] = slot  # most recently used last
+        while len(self._slots) > self.LIMIT:
+            del self._slots[next(iter(self._slots))]
+        slot[0] += 1
+        return slot
+
+    def after_eager(self, key, slot, state):
+        """state: what the eager first frame left -- what it built lazily is the state the next one is captured from.  Where that
+        frame moved the context (a lazy table upload, a re-allocated scratch), graphs captured for OTHER buffer keys froze the old
+        pointers: they go, only this key's counter stays."""
+        if state != self.state:
+            self._slots = {key: slot}
+        self.state = state
+
+    def drop(self):
+        self._slots.clear()
+
+    def counts(self) -> list:
+        """Per key, least recently used first: the number of captured graphs, None where nothing is captured yet."""
+        return [None if graphs is None else len(graphs) for _, graphs in self._slots.values()]
+
+
+class Step(NamedTuple):
+    """One step of a frame (RowShardedRenderer._build_steps)."""
+    name: str  # the trace word of a host step, and of the graph that ends with this step ("replay:<name>")
+    run: object  # run(frame)
+    capture: bool  # may be part of a captured graph
+    host: bool = False  # runs on the host on every frame, noted in the trace -- also where a graph's run includes it
+
+
+class _Frame:
+    """What the steps of one frame share."""
+    __slots__ = ("image_rows", "out_f32", "out_u8", "field_ready", "pending")
+
+    def __init__(self, image_rows, out_f32, out_u8, field_ready=None):
+        self.image_rows, self.out_f32, self.out_u8, self.field_ready = image_rows, out_f32, out_u8, field_ready
+        self.pending = None  # the exposure exchange in flight
+
+
 class RowShardedRenderer:
     """Render one H x W frame whose rows are sharded over the ranks of a process group.
 
@@ -212,6 +253,10 @@ class RowShardedRenderer:
     dyn_scratch: with a backend that keeps the exposure-range record (HipStageBackend.tracks_range) the halation's FFT passes
                choose their scratch element on the device, per frame and per window pair, like a whole-frame r2f_render's (default); False: complex128
                whatever the rows hold (bit-for-bit comparisons with a render under stencil_fft_scratch96_auto = 0, A/B)
+    frame_timer(candidate, render) -> ms: how a measuring frame is timed; default: two events on the launch stream around the
+               frame (device backends only).  Tests of the tuning protocol itself inject a clock of their own (CPU backends, gloo).
+
+    The geometry, the candidate schedules and the tuner's protocol are shard_plan.py's; the order of a frame is `_build_steps`.
     """
 
     def __init__(self, backend, H: int, W: int, *, halation: bool, mtf: bool, grain: bool = True, burn: bool = False,
@@ -221,183 +266,116 @@ class RowShardedRenderer:
         import torch.distributed as dist
 
         self.torch, self.dist = torch, dist
-        self.backend = backend
-        self.group = group
+        self.backend, self.group = backend, group
+        live = dist.is_available() and dist.is_initialized()
         if rank is None:
-            rank = dist.get_rank(group) if dist.is_available() and dist.is_initialized() else 0
+            rank = dist.get_rank(group) if live else 0
         if world is None:
-            world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
-        r0, r1 = shard_rows(H, world)[rank]
-        ha, hb = backend.halation_taps if halation else (0, 0)
-        ma, mb = backend.mtf_taps if mtf else (0, 0)
+            world = dist.get_world_size(group) if live else 1
         self.halation, self.mtf, self.grain, self.burn = halation, mtf, grain, burn
         # The halation's FFT passes choose their scratch element on the device, per frame and window pair, exactly like a whole-frame r2f_render
         # (VERDICT r5, next 3): this rank's front calls record the range of the exposure rows they write, a small kernel adds the
         # halo rows the neighbours sent, and the halation calls vouch for the record.  A rank-local record is sufficient -- the
         # choice is per window pair (tiles indexed by GLOBAL rows), and every window of this rank reads rows of this rank's buffer only.
         self._dyn = bool(dyn_scratch and halation and getattr(backend, "tracks_range", False))
-        # With both stencils on there are two ways to feed the MTF's halo rows:
-        #   ONE exchange: the exposure halo is widened by the MTF reach and every rank also computes the halation for the density
-        #     rows its own MTF stencil will read (2 x 17 rows of redundant halation per shard at 100 MP) -- the same bytes on the
-        #     wire as two exchanges, one latency instead of two;
-        #   TWO exchanges: exposure halo for the halation only, the halation covers exactly the own rows, then r_m rows of DENSITY
-        #     travel.  A second latency -- but the halation's FFT form works in window rows (172 rows at 100 MP), and a 1/8 shard's
-        #     1 024 own rows are 5.95 of them where 1 058 rows are 6.15, i.e. seven: one window row in seven saved.
-        # Buffers are laid out for the wider (single-exchange) halo; which schedule runs is decided below (`exchanges`).
-        both = halation and mtf
-        self.single_exchange = both
-        ea, eb = (ha + ma, hb + mb) if both else (ha, hb)
-        self.plan = ShardPlan(H, W, rank, world, r0, r1, (ea, eb), (ma, mb))
-        # Per plane: a channel whose halation stencil is a single tap (blue on a colour stock) needs exposure halo rows only for
-        # the MTF reach, not for the halation's -- 17 instead of 59 rows at 100 MP, 6.7 instead of 8.7 MB per direction.
-        per = getattr(backend, "halation_taps_per_channel", None) if halation else None
-        if per:
-            self._halo_e_single = [((a + ma, b + mb) if both else (a, b)) for a, b in per]
-            self._halo_e_two = [(a, b) for a, b in per]
-        else:
-            self._halo_e_single = [(ea, eb)] * 3
-            self._halo_e_two = [(ha, hb)] * 3
-        self.halo_e_ch = self._halo_e_single
-        smallest = min(b - a for a, b in shard_rows(H, world))
-        need = max(ea, eb, ma, mb)
-        if world > 1 and smallest < need:
-            raise ValueError(
-                f"row shards of {smallest} rows are shorter than the {need}-row stencil halo; use fewer ranks for this frame"
-            )
-        p = self.plan
-        # extended planes: own rows plus the halo rows that exist inside the frame
-        self.e_lo, self.e_hi = max(p.r0 - ea, 0), min(p.r1 + eb, H)
-        self.d_lo, self.d_hi = max(p.r0 - ma, 0), min(p.r1 + mb, H)
-        self.E = backend.empty(self.e_hi - self.e_lo, W) if halation else None
-        self.D = backend.empty(self.d_hi - self.d_lo, W) if (halation or mtf) else None
-        self.D2 = backend.empty(p.rows, W) if mtf else None
-        self.Dplain = backend.empty(p.rows, W) if not (halation or mtf) else None
-        self.G = backend.empty(p.rows, W) if (burn and grain) else None  # grained density, needed whole before S7
-        # The grain field does not depend on the image: with a device backend it is made on a side stream while the
-        # (memory-bound) stencils run, and the tail shrinks to a pointwise pass.
-        self.side_grain = bool(side_grain and grain and not burn and (halation or mtf) and hasattr(backend, "grain_field")
-                               and getattr(backend, "device", None) is not None and torch.cuda.is_available())
-        self.F = backend.empty(p.rows, W) if self.side_grain else None
-        self.side_stream = torch.cuda.Stream(device=backend.device) if self.side_grain else None
+        lay = self._layout = plan_shard(
+            H, W, rank, world, halation=halation, mtf=mtf, halation_taps=backend.halation_taps if halation else (0, 0),
+            mtf_taps=backend.mtf_taps if mtf else (0, 0), halation_taps_per_channel=getattr(backend, "halation_taps_per_channel", None),
+            band_rows=getattr(backend, "halation_band_rows", lambda W, rows: 0), exchanges=exchanges, split_halation=split_halation)
+        self.plan, self._candidates = lay.plan, lay.candidates
+        self.e_lo, self.e_hi, self.d_lo, self.d_hi = lay.e_lo, lay.e_hi, lay.d_lo, lay.d_hi
+        on_device = getattr(backend, "device", None) is not None and torch.cuda.is_available()
+        self._allocate(bool(side_grain and on_device))
         # graph = True (device backends): everything after the halo exchange -- the ~130 launches of the FFT stencils and the
         # tail, on this renderer's own persistent planes -- is captured into a HIP graph the second time a frame arrives with
         # the same output buffers, and replayed from then on: one graph launch (10-16 us of host time) instead of one launch
         # per kernel, which is what a 1/8 row shard (~1 ms of device work) needs to stay device-bound.  With world == 1 there
         # is no exchange and the front kernel is part of the graph.  Results are the eager path's, bit for bit.
-        self.graph = bool(graph and not burn and not self.side_grain and getattr(backend, "device", None) is not None
-                          and torch.cuda.is_available() and (halation or mtf or grain))
-        # The halation in three calls: the interior rows -- whose stencil reads own exposure rows only -- are launched BEFORE the
-        # halo exchange is waited for (they run while the halos travel), a band at each inner boundary after it.  A band is one
-        # window row of the FFT form high (172 rows at 100 MP) where that is known, so the three calls together cover the same
-        # number of window rows as one call would.
-        # Worth it only where the exchange would otherwise be exposed: three calls cost ~0.05 ms more device time than one (the
-        # bands are small launches: measured on one GPU, tools/shard_model.py) and the interior front kernel already covers
-        # part of the transfer -- so this is one of the candidate schedules the first frames MEASURE (below);
-        # split_halation = True / False fixes it either way.
-        self._graphs = {}   # key -> [calls seen, captured graphs or None], most recently used last
-        self._graphs_state = None  # _graph_state() the graphs were captured from
+        self.graph = bool(graph and not burn and not self.side_grain and on_device and (halation or mtf or grain))
+        self._cache = GraphCache()
         self._identity_done = 0  # channel mask front_split finished (world == 1 only)
-        self.split = None
-        self._split_plan = None
-        band_of = getattr(backend, "halation_band_rows", lambda W, rows: 0)
-        if halation and both and world > 1:
-            need_t, need_b = (ha + ma, hb + mb)
-            band = band_of(W, self.d_hi - self.d_lo)
-            top = max(need_t, band) if rank > 0 else 0
-            bot = max(need_b, band) if rank < world - 1 else 0
-            lo, hi = self.d_lo + top, self.d_hi - bot
-            if hi - lo >= max(need_t, need_b, 1):
-                self._split_plan = (lo, hi)
-        # The schedules a rank can run: (exchanges, split).  Which one is fastest depends on what nobody can know ahead of the first
-        # frames -- how long the exchange takes on this node's links and how much of it the interior front kernel already covers
-        # (round 4 decided from a MODELLED 30 us + bytes / 55 GB/s) -- so "auto" MEASURES: after the first
-        # frame (which builds tables) every candidate renders `tune_frames` frames between two events on the launch stream, the
-        # ranks agree on the schedule whose slowest rank is fastest (one all-reduce of a few floats; the two-exchange form needs
-        # both neighbours to send density rows, so the choice must be the same everywhere), and graphs are captured for that one.
-        # Every candidate renders the frame correctly (results agree to the FFT form's rounding noise), so tuning costs no frame.
-        # Two exchanges are a candidate only where they save a halation window row on this rank's shard.
-        # (the candidate list must be the same on every rank -- they walk it in lockstep and reduce one time per candidate -- so it
-        # is derived from the geometry of a MIDDLE rank's shard, not from this rank's own; a rank without room for the split runs
-        # that candidate unsplit)
-        saves_row = False
-        if both and world > 1:
-            base = H // world
-            vy = band_of(W, base)
-            if vy > 0:
-                saves_row = -(-base // vy) < -(-(base + ma + mb) // vy)
-        cands = []
-        if both and world > 1:
-            ex_opts = [1, 2] if exchanges == "auto" else [int(exchanges)]
-            if exchanges == "auto" and not saves_row:
-                ex_opts = [1]
-            for ex in ex_opts:
-                if ex == 1:
-                    cands += [(1, sp) for sp in ([False, True] if split_halation == "auto" else [bool(split_halation)])]
-                else:
-                    cands.append((2, False))
-        self._candidates = cands
-        self._tune = None  # tuning state: {"i": candidate index, "n": frames timed, "ms": [[...], ...]} while measuring
-        self.tune_frames = int(tune_frames)
+        self.trace = None  # a list here collects (event name) in issue order: tests look at the overlap structure
         self.schedule = None
         self.tuned_ms = None  # per candidate: the measured frame time (max over ranks) the choice was made from
-        # frame_timer(candidate, render) -> ms: how a measuring frame is timed; default: two events on the launch stream around
-        # render() (device backends only).  Tests of the tuning protocol itself inject a clock of their own (CPU backends, gloo).
         self._frame_timer = frame_timer
-        can_measure = frame_timer is not None or (getattr(backend, "device", None) is not None and torch.cuda.is_available())
-        if self.tune_frames < 0:
-            raise ValueError("tune_frames must be >= 0 (0: no measuring, the first candidate runs)")
-        # The ranks walk the candidate list in lockstep (one all-reduce per decision, and the two-exchange form needs both
-        # neighbours to play along): a list that differs between ranks would deadlock in a collective much later -- compare a hash
-        # of it once, here, and fail on every rank at once
-        if cands and world > 1 and dist.is_available() and dist.is_initialized() and type(self)._exchange is RowShardedRenderer._exchange:
-            import hashlib
+        # nothing to choose from, tune_frames = 0 or a backend without a device to time (the CPU backends of the test-suite): the
+        # first candidate -- one exchange, no split -- unless the caller fixed the schedule
+        self._tuner = ScheduleTuner(lay.candidates, tune_frames, can_measure=frame_timer is not None or on_device)
+        self.tune_frames = self._tuner.tune_frames
+        self._check_candidates()
+        self._set_schedule(self._tuner.current)
 
-            h = float(int.from_bytes(hashlib.sha256(repr((cands, H, W, world)).encode()).digest()[:6], "big"))  # 48 bits: exact in fp64
-            dev = backend.device if (getattr(backend, "device", None) is not None and dist.get_backend(group) != "gloo") else "cpu"
-            both_ends = torch.tensor([h, -h], dtype=torch.float64, device=dev)
-            dist.all_reduce(both_ends, op=dist.ReduceOp.MAX, group=group)
-            if float(both_ends[0]) != -float(both_ends[1]):
-                raise RuntimeError(f"rank {rank}: the ranks derived different candidate schedules {cands} for this frame "
-                                   "(different stencils, options or library builds across the ranks?)")
-        if len(cands) > 1 and can_measure and self.tune_frames > 0:
-            self._tune = {"i": 0, "n": -1, "ms": [[] for _ in cands]}
-            self._set_schedule(cands[0])
-        elif cands:
-            # nothing to choose from, or a backend without a device to time (the CPU backends of the test-suite): the first
-            # candidate -- one exchange, no split -- unless the caller fixed the schedule
-            self._set_schedule(cands[0])
-        self.trace = None   # a list here collects (event name) in issue order: tests look at the overlap structure
+    def _allocate(self, side_grain: bool):
+        """The planes of this rank, from the backend at hand (plain attributes, read at render time: callers may share them)."""
+        p, be, W = self.plan, self.backend, self.plan.W
+        halation, mtf = self.halation, self.mtf
+        self.E = be.empty(self.e_hi - self.e_lo, W) if halation else None
+        self.D = be.empty(self.d_hi - self.d_lo, W) if (halation or mtf) else None
+        self.D2 = be.empty(p.rows, W) if mtf else None
+        self.Dplain = be.empty(p.rows, W) if not (halation or mtf) else None
+        self.G = be.empty(p.rows, W) if (self.burn and self.grain) else None  # grained density, needed whole before S7
+        # The grain field does not depend on the image: with a device backend it is made on a side stream while the
+        # (memory-bound) stencils run, and the tail shrinks to a pointwise pass.
+        self.side_grain = bool(side_grain and self.grain and not self.burn and (halation or mtf) and hasattr(be, "grain_field"))
+        self.F = be.empty(p.rows, W) if self.side_grain else None
+        self.side_stream = self.torch.cuda.Stream(device=be.device) if self.side_grain else None
+
+    # ------------------------------------------------------------------ host-side agreement
+    def _can_agree(self) -> bool:
+        """Is there a real process group to agree with?  (A subclass that replaces the transport has no peers to ask.)"""
+        dist = self.dist
+        return (self.plan.world > 1 and dist.is_available() and dist.is_initialized()
+                and type(self)._exchange is RowShardedRenderer._exchange)
+
+    def _agree_max(self, values) -> list[float]:
+        """The element-wise MAX over the ranks of a short vector of floats: one all-reduce of float64, in host memory for gloo,
+        on the backend's device otherwise."""
+        torch, dist = self.torch, self.dist
+        dev = getattr(self.backend, "device", None)
+        if dev is None or dist.get_backend(self.group) == "gloo":
+            dev = "cpu"
+        buf = torch.tensor(list(values), dtype=torch.float64, device=dev)
+        dist.all_reduce(buf, op=dist.ReduceOp.MAX, group=self.group)
+        return buf.cpu().tolist()
+
+    def _check_candidates(self):
+        """The ranks walk the candidate list in lockstep (one all-reduce per decision, and the two-exchange form needs both
+        neighbours to play along): a list that differs between ranks would deadlock in a collective much later -- compare a hash
+        of it once, at construction, and fail on every rank at once."""
+        cands, p = self._candidates, self.plan
+        if not (cands and self._can_agree()):
+            return
+        import hashlib
+
+        digest = hashlib.sha256(repr((cands, p.H, p.W, p.world)).encode()).digest()
+        h = float(int.from_bytes(digest[:6], "big"))  # 48 bits: exact in fp64
+        hi, neg_lo = self._agree_max([h, -h])
+        if hi != -neg_lo:
+            raise RuntimeError(f"rank {p.rank}: the ranks derived different candidate schedules {cands} for this frame "
+                               "(different stencils, options or library builds across the ranks?)")
 
     # ------------------------------------------------------------------ schedule
     @property
     def tuning(self) -> bool:
         """True while the first frames are still measuring the candidate schedules (they render correctly, kernel by kernel)."""
-        return self._tune is not None
+        return self._tuner.measuring
 
     def _set_schedule(self, sched):
-        """sched = (exchanges, split): 1 exchange (exposure halo widened by the MTF reach) with the halation in one call or as
-        interior + bands, or 2 exchanges (exposure halo for the halation, then density halo for the MTF)."""
-        ex, sp = sched
-        both = self.halation and self.mtf
-        self.single_exchange = both and ex == 1
-        self.halo_e_ch = self._halo_e_single if (self.single_exchange or not both) else self._halo_e_two
-        self.split = self._split_plan if (self.single_exchange and sp) else None
-        self.schedule = (ex, bool(self.split))
+        """sched = (exchanges, split) or None (shard_plan.schedule_of): the halos, the split and the frame's steps follow it."""
+        self.single_exchange, self.halo_e_ch, self.split, self.schedule = schedule_of(self._layout, sched)
+        self._build_steps()
         self.reset_graphs()
 
     def _tune_frame(self, image_rows, out_f32, out_u8):
         """One frame of the measuring phase: rendered kernel by kernel under the current candidate, timed between two events on the
         launch stream (exchange included); moves on to the next candidate / to the decision when this one has its frames."""
-        torch, t = self.torch, self._tune
-        if t["n"] < 0:
-            # the first frame of EVERY candidate is not timed: the very first builds tables, spectra and scratch, and a later
-            # candidate's first frame may still meet a window shape of its own (a spectrum upload, a larger scratch -- both
-            # synchronise), which would bias the choice towards candidate 0 whenever tune_frames is 1 (ADVICE r5)
-            t["n"] = 0
+        torch, t = self.torch, self._tuner
+        if not t.next_is_timed:
+            t.frame_done()
             return self._render_eager(image_rows, out_f32, out_u8)
         if self._frame_timer is not None:
             box = []
-            ms = self._frame_timer(self._candidates[t["i"]], lambda: box.append(self._render_eager(image_rows, out_f32, out_u8)))
+            ms = self._frame_timer(t.current, lambda: box.append(self._render_eager(image_rows, out_f32, out_u8)))
             res = box[0]
         else:
             # on the stream the launches go to: the backend's device's current stream (torch's current DEVICE may be another one)
@@ -408,12 +386,9 @@ class RowShardedRenderer:
             b.record(stream)
             b.synchronize()
             ms = a.elapsed_time(b)
-        t["ms"][t["i"]].append(float(ms))
-        t["n"] += 1
-        if t["n"] >= self.tune_frames:
-            t["i"], t["n"] = t["i"] + 1, -1
-            if t["i"] < len(self._candidates):
-                self._set_schedule(self._candidates[t["i"]])
+        if t.frame_done(ms):
+            if t.current is not None:
+                self._set_schedule(t.current)
             else:
                 self._decide()
         return res
@@ -421,16 +396,11 @@ class RowShardedRenderer:
     def _decide(self):
         """The schedule whose slowest rank was fastest (best frame of each candidate; MAX over the ranks, so every rank picks the
         same one -- the two-exchange form needs its neighbours to play along)."""
-        torch, dist = self.torch, self.dist
-        ms = torch.tensor([min(m) for m in self._tune["ms"]], dtype=torch.float64)
-        if self.plan.world > 1 and dist.is_available() and dist.is_initialized() and type(self)._exchange is RowShardedRenderer._exchange:
-            dev = self.backend.device if dist.get_backend(self.group) != "gloo" else "cpu"
-            buf = ms.to(dev)
-            dist.all_reduce(buf, op=dist.ReduceOp.MAX, group=self.group)
-            ms = buf.cpu()
-        self.tuned_ms = [float(x) for x in ms]
-        self._tune = None
-        self._set_schedule(self._candidates[int(torch.argmin(ms))])
+        ms = self._tuner.best()
+        if self._can_agree():
+            ms = self._agree_max(ms)
+        sched, self.tuned_ms = self._tuner.choose(ms)
+        self._set_schedule(sched)
 
     # ------------------------------------------------------------------ neighbour exchange
     def _exchange(self, buf, buf_gy0: int, above, below, wait: bool = True):
@@ -501,114 +471,107 @@ class RowShardedRenderer:
         return self.dist.get_global_rank(self.group, group_rank)
 
     # ------------------------------------------------------------------ one frame
+    def _build_steps(self):
+        """THE order of a frame under the current schedule; the eager launches, the capture and the replay all walk this list.
+        A step that may be captured becomes part of a graph, and a graph is a maximal run of such steps, named after its last one:
+          world > 1: the front kernels and the exchange(s) are issued every frame.  One exchange: [`halation_interior`, replayed
+            while the halos travel,] then `after_exchange`, everything downstream of the exchange.  Two exchanges (or the MTF
+            alone): `density` (the halation of the own rows), then -- after the density halo exchange, issued every frame like
+            the first one -- `finish`, the MTF and the tail.
+          world == 1: nothing travels and every step may be captured: one graph (`after_exchange`), front included (then the
+            input buffer is part of the graph's key).  The wait stays a host step all the same: it has nothing to wait for.
+        The list follows the schedule, not the frame: `_set_schedule` rebuilds it (and drops the graphs)."""
+        whole = self.plan.world == 1
+        travels = self.mtf and not self.single_exchange  # density halo rows between the halation and the MTF
+        steps = [Step("front", self._step_front, whole)]
+        if self.split:
+            steps.append(Step("halation_interior", lambda f: self._halation_interior(), True))
+        steps.append(Step("exchange_finish", lambda f: self._exchange_finish(f.pending), whole, host=True))
+        if self.halation:
+            steps.append(Step("density", lambda f: self._density(), True))
+        if travels:
+            steps.append(Step("exchange_density", lambda f: self._exchange_density(), whole))
+        steps.append(Step("finish" if travels and not whole else "after_exchange",
+                          lambda f: self._finish(f.out_f32, f.out_u8, f.field_ready), True))
+        self._steps = steps
+        self._head = 0 if whole else 1  # the front step is launched ahead of the captures of a frame, unless it is captured itself
+
+    def _walk(self, f, start=0, graphs=None):
+        """The steps of frame `f` from `start` on.  graphs = None: every step is launched here, kernel by kernel.  Otherwise
+        {index of a run's last step: its captured graph}: a captured step is left to its graph, replayed where the run ends."""
+        steps = self._steps
+        for i in range(start, len(steps)):
+            step = steps[i]
+            if graphs is None or step.host or not step.capture:
+                if step.host:
+                    self._note(step.name)
+                step.run(f)
+            if graphs is not None and i in graphs:
+                self._note("replay:" + step.name)
+                graphs[i].replay()
+        return f.out_f32, f.out_u8
+
+    def _capture(self, f, start):
+        """One graph per maximal run of capturable steps from `start` on: {index of the run's last step: graph}."""
+        torch, steps = self.torch, self._steps
+        graphs, run = {}, []
+        for i in range(start, len(steps) + 1):
+            if i < len(steps) and steps[i].capture:
+                run.append(steps[i])
+            elif run:
+                g = torch.cuda.CUDAGraph()
+                # thread_local: other threads (RCCL's watchdog polls events) may keep calling into HIP during the capture
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    for step in run:
+                        step.run(f)
+                graphs[i - 1], run = g, []
+        return graphs
+
     def render(self, image_rows, out_f32=None, out_u8=None, seed=None):
         """image_rows: this rank's own rows of the decoded frame ((rows, W, 3|4) or (3, rows, W)).
         out_*: this rank's own rows of the result, (rows, W, 3).  seed: the grain seed of this frame (every rank the same);
         None keeps the backend's.  A new seed does not cost a captured graph: it lives in a device-side block."""
         if hasattr(self.backend, "begin_frame"):
             self.backend.begin_frame(seed)
-        if self._tune is not None:
+        if self._tuner.measuring:
             return self._tune_frame(image_rows, out_f32, out_u8)
         if not self.graph:
             return self._render_eager(image_rows, out_f32, out_u8)
-        torch, p = self.torch, self.plan
-        whole = p.world == 1  # no exchange: the front kernel is captured too (then the input buffer is part of the key)
-        key = (image_rows.data_ptr() if whole else 0, tuple(image_rows.shape),
+        # world == 1: the front kernel is captured too, so the input buffer is part of the key
+        key = (image_rows.data_ptr() if self.plan.world == 1 else 0, tuple(image_rows.shape),
                out_f32.data_ptr() if out_f32 is not None else 0, out_u8.data_ptr() if out_u8 is not None else 0)
-        # A capture freezes every by-value launch argument (seed, flags, curve constants, tap weights) and every device pointer
-        # into the context's tables and scratch.  `state` is what they were captured from: the context's change counter (table /
-        # stencil / option uploads and re-allocations of its internal buffers) and the parameter block.  When either moves, every
-        # graph of this renderer is dropped and the frame at hand runs eagerly, like a first frame (ADVICE r2).
         state = self._graph_state()
-        if state != self._graphs_state:
-            self._graphs.clear()
-            self._graphs_state = state
-        slot = self._graphs.pop(key, None) or [0, None]
-        self._graphs[key] = slot  # most recently used last
-        while len(self._graphs) > 8:  # callers that hand in fresh buffers every frame: neither graphs nor counters pile up
-            del self._graphs[next(iter(self._graphs))]
-        slot[0] += 1
-        if slot[0] == 1:  # first frame with these buffers: eager (tables, scratch and spectra get built here)
+        slot = self._cache.slot(key, state)
+        if slot[0] == 1:
             res = self._render_eager(image_rows, out_f32, out_u8)
-            new_state = self._graph_state()  # what that frame built lazily is the state the next one is captured from
-            if new_state != state:
-                # the eager frame moved the context (a lazy table upload, a re-allocated scratch): graphs captured for OTHER
-                # buffer keys froze the old pointers -- drop them, keep only this key's counter (ADVICE r3)
-                self._graphs = {key: slot}
-            self._graphs_state = new_state
+            self._cache.after_eager(key, slot, self._graph_state())
             return res
-        # world > 1: the front kernels and the exchange(s) are issued every frame.  What is captured: world == 1: one graph, front
-        # included.  world > 1, one exchange: [the interior halation, replayed while the halos travel,] then everything downstream
-        # of the exchange.  Two exchanges (or the MTF alone): the density (halation of the own rows), then -- after the density halo
-        # exchange, which is issued every frame like the first one -- the MTF and the tail.
-        pending = None
-        if not whole:
-            pending = self._front_and_start_exchange(image_rows)
-        mid_exchange = (not whole) and self.mtf and not self.single_exchange
+        f, head = _Frame(image_rows, out_f32, out_u8), self._head
+        for i in range(head):
+            self._steps[i].run(f)
         if slot[1] is None:
-            graphs = {"pre": None, "a": None, "b": None}
+            slot[1] = self._try_capture(f, head, state)
+            if slot[1] is None:  # the rest of a frame whose capture did not work out, launched kernel by kernel
+                return self._walk(f, head)
+        return self._walk(f, head, slot[1])
 
-            def capture(fn):
-                g = torch.cuda.CUDAGraph()
-                # thread_local: other threads (RCCL's watchdog polls events) may keep calling into HIP during the capture
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    fn()
-                return g
-
-            try:
-                if not whole and self.split:
-                    graphs["pre"] = capture(self._halation_interior)
-                if whole:
-                    def everything():
-                        self._exchange_finish(self._front_and_start_exchange(image_rows))
-                        self._halation_interior()
-                        self._after_exchange(out_f32, out_u8, None)
-                    graphs["a"] = capture(everything)
-                elif mid_exchange:
-                    if self.halation:
-                        graphs["a"] = capture(self._density)
-                    graphs["b"] = capture(lambda: self._finish(out_f32, out_u8, None))
-                else:
-                    graphs["a"] = capture(lambda: self._after_exchange(out_f32, out_u8, None))
-            except Exception:  # noqa: BLE001 -- a failed capture must not cost the frame: eager launches from here on
-                self.graph = False
-                self._graphs.clear()
-                torch.cuda.synchronize()
-                return self._finish_eager(image_rows, pending, out_f32, out_u8, whole)
+    def _try_capture(self, f, head, state):
+        """The graphs of frame `f`'s steps from `head` on, or None where they cannot be had on this frame."""
+        try:
+            graphs = self._capture(f, head)
+        except Exception:  # noqa: BLE001 -- a failed capture must not cost the frame: eager launches from here on
+            self.graph = False
+            graphs = None
+        else:
             if self._graph_state() != state:
                 # the capture itself changed the context (a table built lazily on this frame: its upload synchronises and does
                 # not belong in a graph) -- keep this frame's eager result semantics simple: run it again eagerly, capture later
-                self._graphs.clear()
-                self._graphs_state = self._graph_state()
-                torch.cuda.synchronize()
-                return self._finish_eager(image_rows, pending, out_f32, out_u8, whole)
-            slot[1] = graphs
-        graphs = slot[1]
-        if graphs["pre"] is not None:
-            self._note("replay:halation_interior")
-            graphs["pre"].replay()
-        self._note("exchange_finish")
-        self._exchange_finish(pending)
-        if mid_exchange:
-            if graphs["a"] is not None:
-                self._note("replay:density")
-                graphs["a"].replay()
-            self._note("exchange_density")
-            self._exchange(self.D, self.d_lo, *p.halo_d)
-            self._note("replay:finish")
-            graphs["b"].replay()
-        else:
-            self._note("replay:after_exchange")
-            graphs["a"].replay()
-        return out_f32, out_u8
-
-    def _finish_eager(self, image_rows, pending, out_f32, out_u8, whole):
-        """The rest of a frame whose capture did not work out, launched kernel by kernel (`pending`: its exchange in flight)."""
-        if whole:
-            pending = self._front_and_start_exchange(image_rows)
-        self._halation_interior()
-        self._exchange_finish(pending)
-        return self._after_exchange(out_f32, out_u8, None)
+                self._cache.state = self._graph_state()
+                graphs = None
+        if graphs is None:
+            self._cache.drop()
+            self.torch.cuda.synchronize()
+        return graphs
 
     def _note(self, what):
         if self.trace is not None:
@@ -627,8 +590,12 @@ class RowShardedRenderer:
 
     def reset_graphs(self):
         """Drop every captured graph (they are re-captured on the frames that follow)."""
-        self._graphs.clear()
-        self._graphs_state = None
+        self._cache.drop()
+        self._cache.state = None
+
+    def graph_slots(self) -> list:
+        """Per graph key, least recently used first: how many graphs it holds, None where nothing is captured yet."""
+        return self._cache.counts()
 
     def _render_eager(self, image_rows, out_f32=None, out_u8=None):
         p, be = self.plan, self.backend
@@ -644,11 +611,10 @@ class RowShardedRenderer:
         if not (self.halation or self.mtf or self.grain or self.burn):  # LUTs only: one fused pointwise pass
             be.front_to_output(image_rows, p.r0, out_f32, out_u8, p.r0, p.r0, p.r1, H)
             return out_f32, out_u8
-        pending = self._front_and_start_exchange(image_rows)
-        self._halation_interior()
-        self._note("exchange_finish")
-        self._exchange_finish(pending)
-        return self._after_exchange(out_f32, out_u8, field_ready)
+        return self._walk(_Frame(image_rows, out_f32, out_u8, field_ready))
+
+    def _step_front(self, f):
+        f.pending = self._front_and_start_exchange(f.image_rows)
 
     def _front_and_start_exchange(self, image_rows):
         """S0 + S1 (+ S3 + S4 without halation) on this rank's rows; the exposure halo exchange is STARTED (the rows the neighbours
@@ -662,11 +628,11 @@ class RowShardedRenderer:
             be.front(image_rows, p.r0, 1, self.Dplain, p.r0, p.r0, p.r1, H)
         elif self.halation:
             above, below = [a for a, _ in self.halo_e_ch], [b for _, b in self.halo_e_ch]
+            tk = {"track": True} if self._dyn else {}  # the rows this rank writes go into the exposure-range record's tiles
             if p.world > 1 and (max(above) or max(below)) and p.rows >= max(above) + max(below):
                 # the rows the neighbours wait for first, then the interior while the halos travel
                 lo_band = p.r0 + (max(below) if p.rank > 0 else 0)
                 hi_band = p.r1 - (max(above) if p.rank < p.world - 1 else 0)
-                tk = {"track": True} if self._dyn else {}  # the rows this rank writes go into the exposure-range record's tiles
                 if lo_band > p.r0:
                     be.front(image_rows, p.r0, 0, self.E, self.e_lo, p.r0, lo_band, H, **tk)
                 if hi_band < p.r1:
@@ -676,10 +642,8 @@ class RowShardedRenderer:
                 be.front(image_rows, p.r0, 0, self.E, self.e_lo, lo_band, hi_band, H, **tk)
             elif p.world == 1 and hasattr(be, "front_split"):
                 # no neighbours to feed: the halation's identity channels (blue on a colour stock) skip their exposure plane
-                tk = {"track": True} if self._dyn else {}
                 self._identity_done = be.front_split(image_rows, p.r0, self.E, self.e_lo, self.D, self.d_lo, p.r0, p.r1, H, **tk)
             else:
-                tk = {"track": True} if self._dyn else {}
                 be.front(image_rows, p.r0, 0, self.E, self.e_lo, p.r0, p.r1, H, **tk)
                 self._note("exchange_start")
                 pending = self._exchange(self.E, self.e_lo, above, below, wait=False)
@@ -724,13 +688,10 @@ class RowShardedRenderer:
         # rows are still travelling)
         be.halation(self.E, self.e_lo, self.D, self.d_lo, lo, hi, p.H)
 
-    def _after_exchange(self, out_f32, out_u8, field_ready):
-        """Everything downstream of the exposure planes: S2 .. S8 on this renderer's own buffers."""
-        self._density()
-        if self.mtf and not self.single_exchange:
-            self._note("exchange_density")
-            self._exchange(self.D, self.d_lo, *self.plan.halo_d)
-        return self._finish(out_f32, out_u8, field_ready)
+    def _exchange_density(self):
+        """The second exchange of the two-exchange schedule: the MTF's halo rows of the density planes."""
+        self._note("exchange_density")
+        self._exchange(self.D, self.d_lo, *self.plan.halo_d)
 
     def _density(self):
         """S2 + S3 + S4: the halation of the rows this schedule wants density for (nothing without halation: the front kernel

@@ -112,7 +112,7 @@ def _worker_graph(rank, world, port, H, W, fw, path):
                 assert graphed.trace == ["exchange_start", "replay:halation_interior", "exchange_finish", "replay:after_exchange"] or \
                     graphed.trace[:1] == ["exchange_start"] and graphed.trace[-3:] == ["replay:halation_interior", "exchange_finish", "replay:after_exchange"], graphed.trace
             frames.append(out_g.cpu().numpy().copy())
-        assert [sum(g is not None for g in v[1].values()) for v in graphed._graphs.values() if v[1] is not None] == [2]
+        assert [n for n in graphed.graph_slots() if n is not None] == [2]
         assert not np.array_equal(frames[0], frames[1])  # the seed reaches the grain
         np.save(f"{path}.{rank}.npy", frames[1])
         proc.close()
@@ -202,7 +202,7 @@ def _worker_schedules(rank, world, port, H, W, fw, path):
         assert all(int(b) == int(chosen) or int(b) // 2 == int(chosen) // 2 for b in both)  # (the split itself is rank-local)
         for seed in (1, 2, 3):
             auto.render(img, out_f32=out_g, seed=seed)
-        assert any(v[1] is not None for v in auto._graphs.values())
+        assert any(n is not None for n in auto.graph_slots())
         proc.close()
     finally:
         dist.destroy_process_group()
@@ -512,7 +512,7 @@ def test_graph_replay_of_a_frame_is_bit_identical_to_eager_launches():
         out_g.zero_()
         graphed.render(img, out_f32=out_g, out_u8=u8_g)
         assert torch.equal(out_g, out_e), k
-    assert [v[1] is not None for v in graphed._graphs.values()] == [True]
+    assert [n is not None for n in graphed.graph_slots()] == [True]
     img.copy_(torch.from_numpy(synthetic_frame(H, W, seed=6)).cuda())  # new content, same buffers: the graph reads it
     eager.render(img, out_f32=out_e)
     graphed.render(img, out_f32=out_g, out_u8=u8_g)
@@ -521,7 +521,62 @@ def test_graph_replay_of_a_frame_is_bit_identical_to_eager_launches():
     for _ in range(3):
         graphed.render(img, out_f32=other)
         assert torch.equal(other, out_e)
-    assert len(graphed._graphs) == 2
+    assert len(graphed.graph_slots()) == 2
+    proc.close()
+
+
+def test_a_backend_assigned_after_construction_carries_the_eager_and_the_capture_frame_and_no_replayed_one():
+    """`renderer.backend = wrapper` after construction (what bench.py does with its TimedBackend): every stage call of the frames
+    that follow goes through the wrapper -- the eager first frame and the capture frame with the same argument lists, the replayed
+    frames with none (one graph launch each) -- and every frame equals an eager renderer's bit for bit."""
+    from raw2film_amd import HipProcessor, stencils
+    from raw2film_amd.hip_processor import REC709_TO_XYZ
+    from raw2film_amd.sharding import HipStageBackend, RowShardedRenderer
+    from raw2film_amd.tracing import STAGES
+
+    class Recording:
+        def __init__(self, inner):
+            self._inner, self.calls = inner, []
+
+        def __getattr__(self, name):
+            attr = getattr(self._inner, name)
+            if name not in STAGES + ("exposure_range",) or not callable(attr):
+                return attr
+
+            def recorded(*args, **kwargs):
+                seen = [(a.data_ptr(), tuple(a.shape)) if isinstance(a, torch.Tensor) else a for a in args]
+                self.calls.append((name, seen, sorted(kwargs.items())))
+                return attr(*args, **kwargs)
+
+            return recorded
+
+    neg, prt, _ = stocks()
+    H, W, fw = 300, 640, 2.0  # 320 px/mm: 81-tap halation and 33-tap MTF, both by FFT
+    proc = HipProcessor(device=0)
+    params = proc.prepare(neg, 6, 0.4, (W, H), seed=SEED, matrix=REC709_TO_XYZ, print_film=prt, frame_width=fw,
+                          frame_height=fw * H / W, halation_green_factor=0.3, exp_kelvin=6000, color_masking=1.0)
+    scale = max(H, W) / fw
+    hal, mtf = stencils.halation_stencil(scale, 1.0, halation_green_factor=0.3), stencils.mtf_stencil(neg, scale, 0.0, 1.0)
+    be = HipStageBackend.for_stencils(proc.ctx, params, hal, mtf)
+    eager = RowShardedRenderer(be, H, W, halation=True, mtf=True, grain=True, rank=0, world=1)
+    graphed = RowShardedRenderer(be, H, W, halation=True, mtf=True, grain=True, rank=0, world=1, graph=True)
+    wrapper = Recording(be)
+    graphed.backend = wrapper
+    assert graphed.graph
+    img = torch.from_numpy(synthetic_frame(H, W, seed=5)).cuda()
+    out_e = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+    out_g = torch.zeros_like(out_e)
+    per_frame = []
+    for k, seed in enumerate((SEED, 7, 0xFFFFFFFF, 12345)):  # eager, capture + replay, replay, replay
+        eager.render(img, out_f32=out_e, seed=seed)
+        out_g.zero_()
+        before = len(wrapper.calls)
+        graphed.render(img, out_f32=out_g, seed=seed)
+        per_frame.append(wrapper.calls[before:])
+        assert torch.equal(out_g, out_e), k
+    assert [c[0] for c in per_frame[0]] == ["front_split", "halation", "mtf", "tail"]
+    assert per_frame[1] == per_frame[0] and per_frame[2] == [] and per_frame[3] == []
+    assert graphed.graph_slots() == [1]
     proc.close()
 
 
@@ -556,7 +611,7 @@ def test_graph_replay_follows_parameter_table_and_buffer_changes():
             assert torch.equal(out_g, out_e), (what, k)
 
     check("first")
-    assert any(v[1] is not None for v in graphed._graphs.values())
+    assert any(n is not None for n in graphed.graph_slots())
     before = out_e.clone()
     be.params.seed = SEED + 1  # by-value kernel argument
     check("seed")
@@ -580,7 +635,7 @@ def test_graph_replay_follows_parameter_table_and_buffer_changes():
     # fresh output buffers every frame: the bookkeeping stays bounded
     for _ in range(20):
         graphed.render(img, out_f32=torch.empty_like(out_g))
-    assert len(graphed._graphs) <= 8
+    assert len(graphed.graph_slots()) <= 8
     proc.close()
 
 
