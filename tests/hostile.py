@@ -47,11 +47,30 @@ def lut2d(rng, n: int, rough: float = 1.0, base=None, black_texel: bool = True) 
     return np.maximum(out, 1e-6).astype(F32)
 
 
+def jittered_axis(rng, m: int, x_lo: float, x_hi: float, jitter: float) -> np.ndarray:
+    """m float32 abscissae (returned as float64) on [x_lo, x_hi]: a uniform grid whose inner breakpoints are each moved by
+    jitter x U(-1, 1) of a step, end points fixed.  jitter < 0.5 keeps the order by construction (neighbours stay more than
+    (1 - 2 jitter) of a step apart) -- the NEAR-uniform axis: the device's arithmetic guess of the cell (r2f_device.h, DevCurve::near)
+    is then never more than one cell off, and is one cell off for about jitter / 2 of all arguments, so the one corrective
+    gather of every look-up site is actually taken."""
+    assert 0.0 <= jitter < 0.5, jitter
+    xp = np.linspace(x_lo, x_hi, m)
+    if m > 2:
+        xp[1:-1] += jitter * rng.uniform(-1.0, 1.0, m - 2) * ((x_hi - x_lo) / (m - 1))
+    xp = xp.astype(F32).astype(np.float64)
+    assert (np.diff(xp) > 0).all(), "jittered axis is not strictly increasing in float32"
+    return xp
+
+
 def curve(rng, m: int, x_lo: float = -4.0, x_hi: float = 1.5, v_lo: float = 0.05, v_hi: float = 3.5, max_slope: float = 3.0,
-          uniform: bool = False, monotone: bool = False) -> np.ndarray:
+          uniform: bool = False, monotone: bool = False, axis: str | None = None, jitter: float = 0.45) -> np.ndarray:
     """(4, m) table, row 0 = abscissae (NON-uniform unless asked: random steps between 0.05x and 4x the mean, so the device's
-    uniform-axis guess is off by many cells), rows 1..3 = a bounded random walk whose slope stays under max_slope."""
-    if uniform:
+    uniform-axis guess is off by many cells; axis="jitter": near-uniform, see jittered_axis), rows 1..3 = a bounded random walk
+    whose slope stays under max_slope."""
+    assert axis in (None, "jitter"), axis
+    if axis == "jitter":
+        xp = jittered_axis(rng, m, x_lo, x_hi, jitter)
+    elif uniform:
         xp = np.linspace(x_lo, x_hi, m)
     else:
         steps = rng.uniform(0.05, 4.0, m - 1) ** 2
@@ -68,12 +87,18 @@ def curve(rng, m: int, x_lo: float = -4.0, x_hi: float = 1.5, v_lo: float = 0.05
     return np.stack(rows).astype(F32)
 
 
-def grain_lut(rng, m: int, steps: int = 6, amp: float = 0.06) -> np.ndarray:
+def grain_lut(rng, m: int, steps: int | None = 6, amp: float = 0.06, axis: str | None = None, jitter: float = 0.45) -> np.ndarray:
     """(4, m) grain LUT on a uniform density axis [0, 4]: piecewise constant amplitudes with `steps` jumps per channel (each jump
-    happens across ONE cell, grain.wgsl:78-89 interpolates linearly inside it)."""
-    xp = np.linspace(0.0, 4.0, m)
+    happens across ONE cell, grain.wgsl:78-89 interpolates linearly inside it).  axis="jitter": the near-uniform axis of
+    jittered_axis.  steps=None: an independent amplitude uniform(0.01, amp) at every breakpoint instead of constant runs (inside a
+    constant run a look-up that lands in the wrong cell returns the right value)."""
+    assert axis in (None, "jitter"), axis
+    xp = jittered_axis(rng, m, 0.0, 4.0, jitter) if axis == "jitter" else np.linspace(0.0, 4.0, m)
     rows = [xp]
     for c in range(3):
+        if steps is None:
+            rows.append(rng.uniform(0.01, amp, m))
+            continue
         levels = rng.uniform(0.15, 1.0, steps + 1) * amp
         edges = np.sort(rng.choice(np.arange(1, m - 1), steps, replace=False))
         rows.append(levels[np.searchsorted(edges, np.arange(m), side="right")])
