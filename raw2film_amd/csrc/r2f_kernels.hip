@@ -293,10 +293,15 @@ __global__ __launch_bounds__(256) void lut3d_kernel(const Lut3dArgs a) {
         load_planes4(a.gfield, gy, x, a.W, nv, a.vec != 0, gr, gg, gb);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            // product and sum rounded separately, like NumPy's image + grain * factor (and like the fused tail kernel)
-            r[q] = fmaxf(__fadd_rn(r[q], __fmul_rn(gr[q], curve_eval(a.grain_lut, 0, r[q]))), 0.f);
-            g[q] = fmaxf(__fadd_rn(g[q], __fmul_rn(gg[q], curve_eval(a.grain_lut, 1, g[q]))), 0.f);
-            b[q] = fmaxf(__fadd_rn(b[q], __fmul_rn(gb[q], curve_eval(a.grain_lut, 2, b[q]))), 0.f);
+            const float ar = curve_eval(a.grain_lut, 0, r[q]), ag = curve_eval(a.grain_lut, 1, g[q]), ab = curve_eval(a.grain_lut, 2, b[q]);
+            {
+                // product and sum rounded separately, like NumPy's image + grain * factor (and like the fused tail kernel): plain
+                // operators with contraction off for this block alone (the pragma is lexical: curve_eval keeps its fmaf)
+#pragma clang fp contract(off)
+                r[q] = fmaxf(r[q] + gr[q] * ar, 0.f);
+                g[q] = fmaxf(g[q] + gg[q] * ag, 0.f);
+                b[q] = fmaxf(b[q] + gb[q] * ab, 0.f);
+            }
         }
     }
 #pragma unroll
@@ -692,9 +697,14 @@ __global__ __launch_bounds__(kTailBX* kTailBY) void tail_kernel(const TailArgs a
                 ag = curve_eval(a.grain_lut, 1, g[p]);
                 ab = curve_eval(a.grain_lut, 2, b[p]);
             }
-            r[p] = fmaxf(__fadd_rn(r[p], __fmul_rn(G[0][q / 2][p][q & 1], ar)), 0.f);
-            g[p] = fmaxf(__fadd_rn(g[p], __fmul_rn(G[1][q / 2][p][q & 1], ag)), 0.f);
-            b[p] = fmaxf(__fadd_rn(b[p], __fmul_rn(G[2][q / 2][p][q & 1], ab)), 0.f);
+            {
+                // product and sum rounded separately, like NumPy's image + grain * factor: plain operators with contraction off
+                // for this block alone
+#pragma clang fp contract(off)
+                r[p] = fmaxf(r[p] + G[0][q / 2][p][q & 1] * ar, 0.f);
+                g[p] = fmaxf(g[p] + G[1][q / 2][p][q & 1] * ag, 0.f);
+                b[p] = fmaxf(b[p] + G[2][q / 2][p][q & 1] * ab, 0.f);
+            }
             if (!a.to_planes && !(R2F_TAIL_EXP & 4)) {
                 if (!tetra_nonneg)
                     apply_lut3d(a.lut3d, a.lut3d_scale, a.lut3d_mode, r[p], g[p], b[p]);

@@ -212,8 +212,14 @@ __global__ __launch_bounds__(256) void warp_affine_kernel(const WarpArgs a) {
     const int dx = blockIdx.x * 64 + threadIdx.x, dy = blockIdx.y * 4 + threadIdx.y;
     if (dx >= a.out_w || dy >= a.out_h) return;
     const float xf = (float)(dx + a.ox), yf = (float)(dy + a.oy);
-    const float sx = __fadd_rn(__fadd_rn(__fmul_rn(xf, a.m[0]), __fmul_rn(yf, a.m[1])), a.m[2]);
-    const float sy = __fadd_rn(__fadd_rn(__fmul_rn(xf, a.m[3]), __fmul_rn(yf, a.m[4])), a.m[5]);
+    float sx, sy;
+    {
+        // every product and sum its own rounding, like the float32 array arithmetic this restates: plain operators with
+        // contraction off (the pragma is what keeps them apart, see area_tab)
+#pragma clang fp contract(off)
+        sx = (xf * a.m[0] + yf * a.m[1]) + a.m[2];
+        sy = (xf * a.m[3] + yf * a.m[4]) + a.m[5];
+    }
     const float fx0 = floorf(sx), fy0 = floorf(sy);
     const float ax = sx - fx0, ay = sy - fy0;
     float v[3] = {0.f, 0.f, 0.f};
@@ -233,9 +239,11 @@ __global__ __launch_bounds__(256) void warp_affine_kernel(const WarpArgs a) {
             }
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const float top = __fadd_rn(t[0][0][c], __fmul_rn(ax, __fsub_rn(t[0][1][c], t[0][0][c])));
-            const float bot = __fadd_rn(t[1][0][c], __fmul_rn(ax, __fsub_rn(t[1][1][c], t[1][0][c])));
-            v[c] = __fadd_rn(top, __fmul_rn(ay, __fsub_rn(bot, top)));
+            // the two-step lerp: difference, product and sum each rounded on its own (contraction off, as above)
+#pragma clang fp contract(off)
+            const float top = t[0][0][c] + ax * (t[0][1][c] - t[0][0][c]);
+            const float bot = t[1][0][c] + ax * (t[1][1][c] - t[1][0][c]);
+            v[c] = top + ay * (bot - top);
         }
     }
     float* p0 = a.dst.data + (long long)(dy - a.dst.gy0) * a.out_w + dx;

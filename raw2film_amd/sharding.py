@@ -39,6 +39,7 @@ the replay all walk.  tools/shard_walk_digest.py logs what that walk asks of a b
 
 from __future__ import annotations
 
+import gc
 import queue
 import threading
 from typing import NamedTuple
@@ -515,16 +516,27 @@ class RowShardedRenderer:
         """One graph per maximal run of capturable steps from `start` on: {index of the run's last step: graph}."""
         torch, steps = self.torch, self._steps
         graphs, run = {}, []
-        for i in range(start, len(steps) + 1):
-            if i < len(steps) and steps[i].capture:
-                run.append(steps[i])
-            elif run:
-                g = torch.cuda.CUDAGraph()
-                # thread_local: other threads (RCCL's watchdog polls events) may keep calling into HIP during the capture
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    for step in run:
-                        step.run(f)
-                graphs[i - 1], run = g, []
+        # No cycle collection while a capture is open: the steps run Python, so the collector can start in the middle of one, and a
+        # dead cycle's finalizer may destroy a captured graph with its memory pool, a stream or a context (an earlier renderer is
+        # such a cycle: its step closures refer to it) -- calls a capturing thread must not make; the runtime aborts the process.
+        # torch.cuda.graph no longer collects before it begins, so this is done here, once per capture, outside of it.
+        gc_was_on = gc.isenabled()
+        gc.collect()
+        gc.disable()
+        try:
+            for i in range(start, len(steps) + 1):
+                if i < len(steps) and steps[i].capture:
+                    run.append(steps[i])
+                elif run:
+                    g = torch.cuda.CUDAGraph()
+                    # thread_local: other threads (RCCL's watchdog polls events) may keep calling into HIP during the capture
+                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                        for step in run:
+                            step.run(f)
+                    graphs[i - 1], run = g, []
+        finally:
+            if gc_was_on:
+                gc.enable()
         return graphs
 
     def render(self, image_rows, out_f32=None, out_u8=None, seed=None):

@@ -580,6 +580,81 @@ def test_a_backend_assigned_after_construction_carries_the_eager_and_the_capture
     proc.close()
 
 
+def test_no_dead_cycle_is_finalized_inside_a_stream_capture():
+    """The steps of a captured frame run Python, so the cycle collector can start in the middle of a capture; a finalizer that then
+    destroys a graph, a stream or a context makes calls a capturing thread must not make (dead renderers are such cycles).  Here every
+    stage call leaves a dead cycle behind and the collector's threshold is 1, so it runs at almost every allocation; the cycles'
+    finalizers touch nothing on the device, they only note whether the current stream was capturing.  Every one of them runs, and none may say yes."""
+    import gc
+
+    from raw2film_amd import HipProcessor, stencils
+    from raw2film_amd.hip_processor import REC709_TO_XYZ
+    from raw2film_amd.sharding import HipStageBackend, RowShardedRenderer
+    from raw2film_amd.tracing import STAGES
+
+    seen = []
+
+    class Cycle:
+        def __init__(self):
+            self.me = self
+
+        def __del__(self):
+            seen.append(bool(torch.cuda.is_current_stream_capturing()))
+
+    class Littering:
+        def __init__(self, inner):
+            self._inner, self.made, self.made_capturing = inner, 0, 0
+
+        def __getattr__(self, name):
+            attr = getattr(self._inner, name)
+            if name not in STAGES + ("exposure_range",) or not callable(attr):
+                return attr
+
+            def littered(*args, **kwargs):
+                Cycle()
+                self.made += 1
+                self.made_capturing += bool(torch.cuda.is_current_stream_capturing())
+                return attr(*args, **kwargs)
+
+            return littered
+
+    neg, prt, _ = stocks()
+    H, W, fw = 300, 640, 2.0
+    proc = HipProcessor(device=0)
+    params = proc.prepare(neg, 6, 0.4, (W, H), seed=SEED, matrix=REC709_TO_XYZ, print_film=prt, frame_width=fw,
+                          frame_height=fw * H / W, halation_green_factor=0.3, exp_kelvin=6000, color_masking=1.0)
+    scale = max(H, W) / fw
+    hal, mtf = stencils.halation_stencil(scale, 1.0, halation_green_factor=0.3), stencils.mtf_stencil(neg, scale, 0.0, 1.0)
+    be = HipStageBackend.for_stencils(proc.ctx, params, hal, mtf)
+    eager = RowShardedRenderer(be, H, W, halation=True, mtf=True, grain=True, rank=0, world=1)
+    graphed = RowShardedRenderer(be, H, W, halation=True, mtf=True, grain=True, rank=0, world=1, graph=True)
+    wrapper = Littering(be)
+    graphed.backend = wrapper
+    img = torch.from_numpy(synthetic_frame(H, W, seed=5)).cuda()
+    out_e = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+    out_g = torch.zeros_like(out_e)
+    eager.render(img, out_f32=out_e)
+    gc.collect()
+    threshold, was_on = gc.get_threshold(), gc.isenabled()
+    gc.enable()
+    gc.set_threshold(1, 10, 10)  # (the dead cycles are young: a collection of the youngest generation finds them)
+    try:
+        for k in range(3):  # eager, capture + replay, replay
+            out_g.zero_()
+            graphed.render(img, out_f32=out_g)
+            assert gc.isenabled(), k  # the capture put the collector back as it found it
+            assert torch.equal(out_g, out_e), k
+    finally:
+        gc.set_threshold(*threshold)
+        if not was_on:
+            gc.disable()
+    gc.collect()
+    assert graphed.graph_slots() == [1]
+    assert wrapper.made_capturing >= 4 and len(seen) == wrapper.made  # the capture frame's stage calls littered too
+    assert not any(seen), f"{sum(seen)} of {len(seen)} dead cycles were finalized while the stream was capturing"
+    proc.close()
+
+
 def test_graph_replay_follows_parameter_table_and_buffer_changes():
     """A captured graph freezes by-value launch arguments and device pointers into the context's tables.  The renderer keys its
     graphs on the context's change counter (r2f_generation) and the parameter block: a new seed, a new output LUT, a new stencil
