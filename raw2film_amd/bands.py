@@ -69,6 +69,17 @@ class BandSource(NamedTuple):
     decode: Callable  # (ctx, landing, image, a0, a1): the rows a0:a1 of the float frame from what has landed
 
 
+class StreamedFrame(NamedTuple):
+    """A frame set up for the band loop (HipProcessor._stream_plan makes one, _run_bands takes it)."""
+    host: object  # the payload's tensor on the host
+    source: BandSource
+    params: object  # the frame's r2f_params, already written to the device-side frame block
+    bounds: list  # plan_bands' row bounds
+    bufs: dict  # the device buffers the frame works in
+    halation_reach: tuple  # (rows above, rows below) the stencil reads; (0, 0) for a stage that does not run
+    mtf_reach: tuple
+
+
 def band_source(payload, shape, dtype) -> BandSource:
     """The BandSource of a payload that stream_rejection has passed.  `shape`, `dtype`: of its tensor, as stream_rejection takes them."""
     shape = tuple(int(v) for v in shape)

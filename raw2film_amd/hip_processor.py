@@ -31,10 +31,10 @@ from typing import Callable, NamedTuple
 import numpy as np
 
 from . import _lib, filmstock, geometry, payload as phase1, stencils, tiff
-from .bands import band_source, plan_bands, stage_schedule
+from .bands import StreamedFrame, band_source, plan_bands, stage_schedule
 from .context import LOG_EPS, LUT3D_SCALE, HipContext
 from .jpeg_options import _check_jpeg_image, checked_options
-from .jpeg_stream import JpegBandSink, JpegStaging, deliver
+from .exports import JpegExport, TiffExport
 from .payload import DEVICE_EXPOSURE, host_stream_gate, stream_rejection
 from .results import ResultBuffers
 
@@ -131,6 +131,11 @@ class PendingFrame:
 class HipProcessor:
     """Drop-in for the hot path of CpuProcessor / GpuProcessor (gui.py:1584-1585)."""
 
+    # class-level defaults: what the host-only entry points (extract_image_data_cpu, the early refusals) read without a constructed processor
+    payload_alpha = True
+    profile_stages = False  # settable: process() then times its stages into `last_stage_ms` (see there)
+    _texture = _texture_src = image_param_dict = None  # the frame cache, empty
+
     def __init__(self, cameras=None, lenses=None, device: int = 0, payload_alpha: bool = True, result_buffers: int = 0,
                  lib_path: str | None = None):
         """payload_alpha: extract_image_data_cpu appends the constant alpha plane like upstream (gpu_processor.py:765: its wgpu
@@ -141,8 +146,7 @@ class HipProcessor:
         import torch
 
         self._torch = torch
-        self.cameras = cameras
-        self.lenses = lenses
+        self.cameras, self.lenses = cameras, lenses
         self.payload_alpha = bool(payload_alpha)
         self.result_buffers = int(result_buffers)  # 0: process() returns a fresh array; n: views of n pinned buffers in turn (_download)
         # process(host array, cache=False) with pinned result buffers streams a large frame through the pipeline in row bands while it
@@ -154,14 +158,8 @@ class HipProcessor:
         self._depths = output_depths(torch, self.ctx)  # output_bits -> what differs between an 8- and a 16-bit result
         self.device = self.ctx.device  # NB: a torch device, not a wgpu device (gui.py:1652 uses bitmap mode)
         # comparison dicts, same role as cpu_processor.py:41-45 / gpu_processor.py
-        self.input_param_dict = None
-        self.curve_param_dict = None
-        self.output_param_dict = None
-        self.halation_param_dict = None
-        self.mtf_param_dict = None
-        self.grain_kernel_param_dict = None
-        self.grain_lut_param_dict = None
-        self.highlight_burn_param_dict = None
+        self.input_param_dict = self.curve_param_dict = self.output_param_dict = self.highlight_burn_param_dict = None
+        self.halation_param_dict = self.mtf_param_dict = self.grain_kernel_param_dict = self.grain_lut_param_dict = None
         self.pipeline_resolution = None  # (w, h) of the frame prepared last
         self.matrix_key = None
         self.uploads = 0  # number of table uploads, for the caching tests
@@ -174,19 +172,27 @@ class HipProcessor:
         # why the uint16 frame the last process / process_preloaded / submit_preloaded / *_jpeg call uploaded was measured on the host
         # although it asked for exposure="device"; None for every other call (one that re-rendered a cached frame included)
         self.exposure_rejected = None
+        # why the last export, or the last call that tried the row-band path, rendered its frame in one piece; None: it streamed
+        self.stream_rejected = None
+        self.last_stage_ms = None  # process()'s wall clock per stage with `profile_stages` on (bench.py's host_device_copies)
+        self._load_stage_ms = None  # ... load_image_texture's share of it, until process() folds it in
+        # the frame cache (load_image_texture): (frame, layout, payload geometry) kept on the device, a weak reference to its array, its load parameters
+        self._texture = self._texture_src = self.image_param_dict = None
+        self._halation_reach = self._mtf_reach = (0, 0)  # (rows above, rows below) of the stencils uploaded last: a band's halo
+        self._stream_bufs = None  # the device buffers of the streamed frame, kept for the next one of its kind (_stream_buffers)
+        self._jpeg_host = None  # the export buffers: the pinned buffer a one-piece JPEG comes down into (_encode_device) ...
+        self._jpeg_staging = None  # ... and the streamed JPEG export's host side (jpeg_stream.JpegStaging), made on first use
+        self._up_stream = self._down_stream = None  # the copy streams (_copy_streams), made on first use
 
     def close(self):
+        """Let go of every buffer, stream and helper thread the processor holds (a second call finds nothing left to do)."""
         for depth in self._depths.values():
             depth.pool.close()
-        self._stream_bufs = None
-        self._jpeg_host = None
-        if getattr(self, "_jpeg_staging", None) is not None:
+        if self._jpeg_staging is not None:
             self._jpeg_staging.close()
-            self._jpeg_staging = None
-        self._texture = None  # the frame kept on the device for re-renders
-        self._texture_src = None
-        self.image_param_dict = None
-        self.last_output = None
+        self._texture = self._texture_src = self.image_param_dict = self.last_output = None
+        self._stream_bufs = self._jpeg_host = self._jpeg_staging = None
+        self._up_stream = self._down_stream = None
         self.ctx.close()
 
     # ------------------------------------------------------------------ cached loaders
@@ -372,7 +378,7 @@ class HipProcessor:
         res = phase1.plan_resolution(*crops.size, frame_width, frame_height, resolution, max_scale, canvas_mode, canvas_scale,
                                      canvas_ratio)
         image = phase1.pack_image(image, demosaic_params is not None or crops.u16_window is not None, is_u16,
-                                  getattr(self, "payload_alpha", True) and not internal)
+                                  self.payload_alpha and not internal)
         return {
             "image_array": image,
             # float32 exposure factor of a uint16 payload (converted on the device), else None; "device": measured there too, on the
@@ -439,7 +445,7 @@ class HipProcessor:
         exposure_on_device(exposure)  # (any string but "device" raises before any work starts)
         settings["output_bits"] = check_output_bits(output_bits, dst_texture)
         self.exposure_rejected = None
-        for k in ("self", "src", "negative_film", "grain_size", "grain_sigma", "dst_texture", "histogram_texture", "_"):
+        for k in _PROCESS_POSITIONAL:
             del settings[k]
         # load_image_texture's share; prepare() and the render take what they need of all of them and swallow the rest
         load = {k: settings[k] for k in _LOAD_KEYWORDS}
@@ -449,20 +455,24 @@ class HipProcessor:
             self._check_texture(histogram_texture, "histogram_texture")
         # profile_stages (bench.py's host_device_copies): wall clock per stage of this call, with a device synchronisation behind
         # each -- a measuring mode (the syncs serialise what otherwise overlaps), off by default
-        prof = getattr(self, "profile_stages", False)
+        prof = self.profile_stages
         if prof:
             import time
 
             self._torch.cuda.synchronize(self.device)
             t_start = time.perf_counter()
-        elif not cache and dst_texture is None and self._host_stream_gate(src, settings) is None:
+        if not prof and not cache and dst_texture is None and self._host_stream_gate(src, settings) is None:
             # a large host frame that is uploaded for this one render: streamed through the pipeline in row bands while it arrives
-            res = self._process_streamed(src, negative_film, grain_size, grain_sigma, load, settings)
+            payload = self.extract_image_data_cpu(src, **load, _internal=True)
+            res = self._process_streamed(payload, negative_film, grain_size, grain_sigma, settings)
             if res is not None:
                 return res
-        # GpuProcessor.load_image_texture (gpu_processor.py:655-719): the pre-processed frame stays on the device while the
-        # load parameters do not change -- a re-render with other film settings neither prepares nor uploads it again
-        self.load_image_texture(src, **load)
+            # its payload did not qualify: uploaded whole like any cache=False array (nothing is recorded for the frame cache)
+            self.prepare_gpu_textures(payload)
+        else:
+            # GpuProcessor.load_image_texture (gpu_processor.py:655-719): the pre-processed frame stays on the device while the
+            # load parameters do not change -- a re-render with other film settings neither prepares nor uploads it again
+            self.load_image_texture(src, **load)
         image, layout, payload = self._texture
         if prof:
             self._torch.cuda.synchronize(self.device)
@@ -477,7 +487,7 @@ class HipProcessor:
             t_end = time.perf_counter()
             self.last_stage_ms = {"load_and_upload": (t_loaded - t_start) * 1e3, "prepare_and_render": (t_rendered - t_loaded) * 1e3,
                                   "download": (t_end - t_rendered) * 1e3, "total": (t_end - t_start) * 1e3,
-                                  **{k: v for k, v in (getattr(self, "_load_stage_ms", None) or {}).items()}}
+                                  **(self._load_stage_ms or {})}
             self._load_stage_ms = None
         return res
 
@@ -506,19 +516,16 @@ class HipProcessor:
             src_key = self._array_fingerprint(src)
         # (`cache` and `src_version` decide how the frame is compared, above; they are not part of what it is compared by)
         new_param_dict = {"src": src_key, **{k: v for k, v in load.items() if k not in ("cache", "src_version")}}
-        held = getattr(self, "_texture_src", None)
+        held = self._texture_src
         same_src = isinstance(src, str) or (held is not None and held() is src)
-        if cache and same_src and getattr(self, "_texture", None) is not None and new_param_dict == getattr(self, "image_param_dict", None):
+        if cache and same_src and self._texture is not None and new_param_dict == self.image_param_dict:
             return
-        prof = getattr(self, "profile_stages", False)
+        prof = self.profile_stages
         if prof:
             import time
 
             t0 = time.perf_counter()
-        cpu_payload = getattr(self, "_stash_payload", None)  # (made a moment ago by _process_streamed for a frame that did not qualify)
-        self._stash_payload = None
-        if cpu_payload is None:
-            cpu_payload = self.extract_image_data_cpu(src, **load, _internal=True)
+        cpu_payload = self.extract_image_data_cpu(src, **load, _internal=True)
         if prof:
             t1 = time.perf_counter()
         self.prepare_gpu_textures(cpu_payload)
@@ -672,14 +679,7 @@ class HipProcessor:
         o = checked_options(quality, subsampling, optimize, exif, progressive, icc_profile, xmp, comment, dpi, restart_marker_blocks,
                             restart_marker_rows)
         exposure_on_device(settings.get("exposure"))
-        self.exposure_rejected = None
-        settings, _, payload = self._export_frame("process_jpeg", src, negative_film, grain_size, grain_sigma, settings, stream, o.early)
-        if stream and self.stream_rejected is None:
-            res = self._stream_jpeg(payload, negative_film, grain_size, grain_sigma, "cpu", file, settings, o)
-            if res is not None:
-                return res
-        out_u8 = self._render_export(payload, negative_film, grain_size, grain_sigma, "cpu", settings)
-        return deliver(self._encode_device(out_u8, o), file)
+        return self._export(JpegExport(o), src, None, negative_film, grain_size, grain_sigma, "cpu", stream, file, settings)
 
     def process_preloaded_jpeg(self, cpu_payload, negative_film, grain_size, grain_sigma, quality=100, final_scaling="gpu",
                                stream=False, file=None, *, subsampling=-1, optimize=False, exif=b"", progressive=False,
@@ -692,30 +692,35 @@ class HipProcessor:
         progressive, icc_profile, xmp, comment, dpi, restart_marker_blocks, restart_marker_rows: see process_jpeg."""
         o = checked_options(quality, subsampling, optimize, exif, progressive, icc_profile, xmp, comment, dpi, restart_marker_blocks,
                             restart_marker_rows)
-        self.exposure_rejected = None
-        if self._export_preloaded("process_preloaded_jpeg", settings, stream, o.early):
-            res = self._stream_jpeg(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, file, settings, o)
+        return self._export(JpegExport(o), None, cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, stream, file,
+                            settings)
+
+    def _export(self, fmt, src, payload, negative_film, grain_size, grain_sigma, final_scaling, stream, file, settings):
+        """Every export behind its option checks; `fmt` (exports.py) is the file format.  Of `src` (payload None: process_jpeg,
+        process_tiff): no textures, then process()'s keywords with process()'s defaults (the unknown ones swallowed like there) and
+        the frame's payload, extracted afresh; with stream=True process(cache=False)'s gates in its order into `stream_rejected`
+        -- the format's own `early` reasons, the host gate, then the payload's (_stream_plan's).  Of a phase-1 `payload`: no
+        textures, and with stream=True the format's reasons, the processor's `stream_bands`, the payload's.  Then the row-band
+        path into fmt.sink where nothing refused it, else the one-piece render into fmt.whole."""
+        what = f"process_{fmt.name}" if payload is None else f"process_preloaded_{fmt.name}"
+        self.exposure_rejected = self.stream_rejected = None
+        self._refuse_textures(what, settings, " (use process() for the preview)" if payload is None else "")
+        early = next((why for why in fmt.early if why), None) if stream else None
+        if payload is None:
+            bound = inspect.signature(HipProcessor.process).bind(self, src, negative_film, grain_size, grain_sigma, **settings)
+            bound.apply_defaults()
+            settings = {k: v for k, v in bound.arguments.items() if k not in _PROCESS_POSITIONAL}
+            if stream:
+                self.stream_rejected = early or ("profile_stages is on" if self.profile_stages else self._host_stream_gate(src, settings))
+            payload = self.extract_image_data_cpu(src, **{k: settings[k] for k in _LOAD_KEYWORDS}, _internal=True)
+        elif stream:
+            self.stream_rejected = early or (None if self.stream_bands > 1 else f"stream_bands = {self.stream_bands}")
+        if stream and self.stream_rejected is None:
+            res = self._stream(payload, negative_film, grain_size, grain_sigma, final_scaling, dict(settings, output_bits=fmt.bits),
+                               lambda depth, out, bounds: fmt.sink(self, depth, out, bounds, file))
             if res is not None:
                 return res
-        out_u8 = self._render_export(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, settings)
-        return deliver(self._encode_device(out_u8, o), file)
-
-    def _export_frame(self, what, src, negative_film, grain_size, grain_sigma, settings, stream, early=()):
-        """The prologue of an export of `src` (process_jpeg, process_tiff; `what` names it in messages): no textures, then
-        process()'s keywords with process()'s defaults (the unknown ones swallowed like there), with stream=True process(cache=False)'s
-        gates in its order into `stream_rejected` -- the export's own `early` reasons (None where one does not apply), the early
-        ones, then the payload's (_stream_plan's) -- and the frame's payload, extracted afresh.  -> (settings, load, payload)."""
-        self._refuse_textures(what, settings, " (use process() for the preview)")
-        bound = inspect.signature(HipProcessor.process).bind(self, src, negative_film, grain_size, grain_sigma, **settings)
-        bound.apply_defaults()
-        settings = {k: v for k, v in bound.arguments.items()
-                    if k not in ("self", "src", "negative_film", "grain_size", "grain_sigma", "dst_texture", "histogram_texture", "_")}
-        load = {k: settings[k] for k in _LOAD_KEYWORDS}
-        if stream:
-            self.stream_rejected = (next((why for why in early if why), None) or
-                                    ("profile_stages is on" if getattr(self, "profile_stages", False) else
-                                     self._host_stream_gate(src, settings)))
-        return settings, load, self.extract_image_data_cpu(src, **load, _internal=True)
+        return fmt.whole(self, self._render_export(payload, negative_film, grain_size, grain_sigma, final_scaling, settings), file)
 
     def _host_stream_gate(self, src, settings):
         """payload.host_stream_gate of a call's `settings` (process()'s keywords): why its frame is rendered in one piece, or None."""
@@ -728,15 +733,6 @@ class HipProcessor:
                                 frame_samples=phase1.mosaic_frame_samples(src, settings["half_size"],
                                                                           settings["frame_width"] / settings["frame_height"],
                                                                           settings["flip"], settings["zoom"]) if mosaic else None)
-
-    def _export_preloaded(self, what, settings, stream, early=()) -> bool:
-        """The prologue of an export of a phase-1 payload: no textures, then with stream=True `stream_rejected` from the export's
-        own `early` reasons and the processor's `stream_bands`.  -> whether to try the row-band path (_stream_plan has the last word)."""
-        self._refuse_textures(what, settings)
-        if stream:
-            self.stream_rejected = (next((why for why in early if why), None) or
-                                    (None if self.stream_bands > 1 else f"stream_bands = {self.stream_bands}"))
-        return bool(stream) and self.stream_rejected is None
 
     @staticmethod
     def _refuse_textures(what, settings, hint=""):
@@ -766,42 +762,17 @@ class HipProcessor:
         bits = check_output_bits(output_bits)
         icc = tiff.check_icc(icc_profile)
         exposure_on_device(params.get("exposure"))
-        self.exposure_rejected = self.stream_rejected = None
-        settings, _, payload = self._export_frame("process_tiff", src, negative_film, grain_size, grain_sigma,
-                                                  dict(params, output_bits=bits), stream)
-        if stream and self.stream_rejected is None:
-            res = self._stream_tiff(payload, negative_film, grain_size, grain_sigma, "cpu", icc, file, settings)
-            if res is not None:
-                return res
-        out = self._render_export(payload, negative_film, grain_size, grain_sigma, "cpu", settings)
-        return tiff.deliver(self._download(out), icc, file)
+        return self._export(TiffExport(bits, icc), src, None, negative_film, grain_size, grain_sigma, "cpu", stream, file,
+                            dict(params, output_bits=bits))
 
     def process_preloaded_tiff(self, cpu_payload, negative_film, grain_size, grain_sigma, file=None, final_scaling="gpu", *,
                                output_bits=16, icc_profile=b"", stream=False, **settings):
         """The batch export on the two-phase API: process_preloaded's render of a phase-1 payload as a TIFF file like
         process_tiff's.  The processor's device frame is left alone.  stream=True: a payload process_preloaded streams in row bands
         is written band by band (else `stream_rejected` says why not)."""
-        settings["output_bits"] = check_output_bits(output_bits)
-        icc = tiff.check_icc(icc_profile)
-        self.exposure_rejected = self.stream_rejected = None
-        if self._export_preloaded("process_preloaded_tiff", settings, stream):
-            res = self._stream_tiff(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, icc, file, settings)
-            if res is not None:
-                return res
-        out = self._render_export(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, settings)
-        return tiff.deliver(self._download(out), icc, file)
-
-    def _stream_tiff(self, payload, negative_film, grain_size, grain_sigma, final_scaling, icc, file, settings):
-        """_stream_payload with a TIFF sink: the same bands and stage calls; the header first, then every band's rows into the file
-        behind their download (tiff.TiffBandSink).  Returns the file's bytes (file=None) or their count, or None (with
-        `stream_rejected` saying why) when the payload does not qualify."""
-        def make_sink(depth, out, bounds):
-            H, W = int(out.shape[0]), int(out.shape[1])
-            head, tplan = tiff.header(H, W, depth.bits, icc)  # (refuses a file past 4 GiB before any band runs)
-            target, give_back = depth.pool.borrow((H, W, 3), lease=self._lease_of(depth))
-            return tiff.TiffBandSink(target, head, tplan, file, give_back), None
-
-        return self._stream(payload, negative_film, grain_size, grain_sigma, final_scaling, settings, make_sink)
+        settings["output_bits"] = bits = check_output_bits(output_bits)
+        return self._export(TiffExport(bits, tiff.check_icc(icc_profile)), None, cpu_payload, negative_film, grain_size, grain_sigma,
+                            final_scaling, stream, file, settings)
 
     def _encode_device(self, image_u8, o):
         """A uint8 (H, W, 3) device frame -> the JPEG file's bytes, with the checked options `o` (jpeg_options.checked_options).
@@ -817,7 +788,7 @@ class HipProcessor:
         n = int(length.item())
         if n <= 0:
             raise RuntimeError("r2f_jpeg_encode reported an empty file")
-        host = getattr(self, "_jpeg_host", None)
+        host = self._jpeg_host
         if host is None or host.numel() < n:
             host = self._jpeg_host = self._torch.empty(max(n, 1 << 20), dtype=self._torch.uint8, pin_memory=True)
         host[:n].copy_(out[:n])  # (synchronous: the bytes are there when it returns)
@@ -827,7 +798,7 @@ class HipProcessor:
             return b"".join((data[:20], segments, data[20:]))
         return host[:n].numpy().tobytes()
 
-    def _process_streamed(self, src, negative_film, grain_size, grain_sigma, load, settings):
+    def _process_streamed(self, payload, negative_film, grain_size, grain_sigma, settings):
         """process() of a large host frame that is uploaded for this one render (cache=False: the GUI's export calls,
         gui.py:2374,2458,2479): the frame goes through the pipeline in `stream_bands` row bands WHILE IT ARRIVES -- band k is clamped and taken through S0 + S1
         as soon as it is on the device, the halation of band k - 1 follows (its stencil reads the first rows of band k), then the
@@ -843,39 +814,35 @@ class HipProcessor:
         their neighbours, which travel with the band that needs them first (payload.mosaic_upload_bounds).
         bands.py holds the host-side plan: the bands (plan_bands), the order in which the stages take them (stage_schedule) and
         what each kind of payload does to get its rows into the float frame (band_source); _run_bands holds the mechanics.
-        Returns None when the frame does not qualify (the caller then takes the one-after-the-other path): a device pre-path
-        (rotation, chroma NR, scaling), a canvas, a highlight burn (a function of the whole grained frame), a small frame.
+        `payload`: the frame's, as process() extracted it.  Returns None when it does not qualify (the caller then takes the
+        one-after-the-other path with the same payload): a device pre-path (rotation, chroma NR, scaling), a canvas, a highlight burn
+        (a function of the whole grained frame), a small frame.
         The two-phase API's device phase (process_preloaded, submit_preloaded: batch export) streams its payload the same way."""
-        payload = self.extract_image_data_cpu(src, **load, _internal=True)
-        res = self._stream_payload(payload, negative_film, grain_size, grain_sigma, "cpu", **settings)
-        # (should the frame not qualify, load_image_texture takes the payload from here)
-        self._stash_payload = payload if res is None else None
-        return res
+        return self._stream_payload(payload, negative_film, grain_size, grain_sigma, "cpu", **settings)
 
     def _stream_payload(self, payload, negative_film, grain_size, grain_sigma, final_scaling="cpu", **settings):
         """A phase-1 payload (extract_image_data_cpu) through the pipeline in row bands while it arrives: see _process_streamed.
         Returns the uint8 frame, or None (with `stream_rejected` saying why) when the payload does not qualify."""
         def make_sink(depth, out, bounds):
-            return depth.pool.sink(tuple(out.shape), self.result_buffers, lease=self._lease_of(depth)), None
+            return depth.pool.sink(tuple(out.shape), self.result_buffers), None
 
         res = self._stream(payload, negative_film, grain_size, grain_sigma, final_scaling, settings, make_sink)
         return None if res is None else _host16(res)
 
     def _stream(self, payload, negative_film, grain_size, grain_sigma, final_scaling, settings, make_sink):
-        """The streamed render behind _stream_payload, _stream_tiff and _stream_jpeg, which differ in where the finished rows go:
+        """The streamed render behind _stream_payload and _export, which differ in where the finished rows go:
         plan the bands, make the sink -- make_sink(depth, the frame's result buffer on the device, band bounds) -> (sink, band_done):
         a ResultSink or one with its interface and None, or a sink that downloads nothing itself and its band_done(b), called once
         band b's tail is queued --, run the bands, finish.  A finish() that raises is drained and abandoned like a band that does.
         Returns sink.finish()'s value, or None (with `stream_rejected` saying why) when the payload does not qualify."""
-        plan = self._stream_plan(payload, negative_film, grain_size, grain_sigma, final_scaling, settings)
-        if plan is None:
+        frame = self._stream_plan(payload, negative_film, grain_size, grain_sigma, final_scaling, settings)
+        if frame is None:
             return None
-        host, source, p, bounds, bufs, ha, ma = plan
         depth = self._depths[settings.get("output_bits", 8)]
-        out = self._stream_result(bufs, depth)
-        sink, band_done = make_sink(depth, out, bounds)
+        out = self._stream_result(frame.bufs, depth)
+        sink, band_done = make_sink(depth, out, frame.bounds)
         try:
-            self._run_bands(host, source, p, bounds, bufs, ha, ma, sink, out, depth, band_done)
+            self._run_bands(frame, sink, out, depth, band_done)
             self._collect_auto_exposure()
             res = sink.finish()
         except BaseException:
@@ -890,8 +857,8 @@ class HipProcessor:
         return res
 
     def _stream_plan(self, payload, negative_film, grain_size, grain_sigma, final_scaling, settings):
-        """Qualify a payload for the row-band path and set its frame up: (host tensor, its bands.BandSource, frame params, band
-        bounds, device buffers, halation reach, MTF reach), or None with `stream_rejected` saying why it does not stream."""
+        """Qualify a payload for the row-band path and set its frame up: its bands.StreamedFrame, or None with `stream_rejected`
+        saying why it does not stream."""
         host = self._payload_tensor(payload)
         self.stream_rejected = stream_rejection(payload, tuple(host.shape), str(host.dtype), host.is_cuda, final_scaling,
                                                 settings.get("canvas_mode", "No"))
@@ -911,25 +878,7 @@ class HipProcessor:
         p = _lib.Params.from_buffer_copy(params)
         p.flags |= _lib.F_FRAME_RESIDENT  # the seed is written once, here; the stage calls read it from the frame block
         self.ctx.write_frame_params(p)     # (and the exposure-range record starts empty)
-        return host, source, p, bounds, bufs, ha, ma
-
-    def _stream_jpeg(self, payload, negative_film, grain_size, grain_sigma, final_scaling, file, settings, o):
-        """_stream_payload with a JPEG sink (`o`: the export's checked options; optimize and progressive never stream):
-        the same bands and stage calls, no pixels downloaded; each band's finished MCU rows
-        are encoded behind its tail and the file's final bytes go down while later bands arrive (jpeg_stream.py).  Returns the
-        file's bytes (file=None) or their count, or None (with `stream_rejected` saying why) when the payload does not qualify."""
-        def make_sink(depth, out_u8, bounds):
-            staging = getattr(self, "_jpeg_staging", None)
-            if staging is None:
-                staging = self._jpeg_staging = JpegStaging(self._torch, self.device)
-            _, down = self._copy_streams()
-            x = o.extras
-            sink = JpegBandSink(staging, self.ctx, out_u8, o.quality, bounds, down, file, o.subsampling, segments=x.segments(o.exif),
-                                restart=x.restart(int(out_u8.shape[1]), o.subsampling), density=x.density)
-            return sink, sink.band
-
-        # (a JPEG is 8 bits per sample whatever `output_bits` the caller's settings carry)
-        return self._stream(payload, negative_film, grain_size, grain_sigma, final_scaling, dict(settings, output_bits=8), make_sink)
+        return StreamedFrame(host, source, p, bounds, bufs, ha, ma)
 
     def _stream_buffers(self, source, mtf, bits=8):
         """The device buffers the streamed frame of `source` (a bands.BandSource) works in, kept for the next frame of the same kind:
@@ -937,7 +886,7 @@ class HipProcessor:
         the payload tensor's shape (a mosaic is demosaiced straight into the float frame: no uint16 (H, W, 3) frame exists)."""
         torch = self._torch
         H, W, _ = shape = source.frame  # (a float payload with upstream's alpha plane, gpu_processor.py:765: 4 channels)
-        bufs = getattr(self, "_stream_bufs", None)
+        bufs = self._stream_bufs
         if bufs is None or bufs["shape"] != shape or bufs["mtf"] != mtf:
             bufs = self._stream_bufs = {"shape": shape, "mtf": mtf, "image": torch.empty(shape, dtype=torch.float32, device=self.device)}
             for k in ("E", "D", "D2") if mtf else ("E", "D"):
@@ -955,12 +904,13 @@ class HipProcessor:
             bufs[key] = self._torch.empty(bufs["shape"][:2] + (3,), dtype=depth.torch_dtype, device=self.device)
         return bufs[key]
 
-    def _run_bands(self, host, source, p, bounds, bufs, ha, ma, sink, out, depth, band_done=None):
-        """_stream's band loop (see _process_streamed): the copies, their events and the one context call that each pair of
-        bands.stage_schedule stands for; `source` (bands.band_source) knows how the rows of `host` reach the float frame.  The
-        tail's rows -- written into `out`, the result at `depth` -- go back into `sink` -- or, with `band_done`, band_done(b) is
-        called instead once band b's tail is queued (on the launching stream; the JPEG export's sink)."""
+    def _run_bands(self, frame, sink, out, depth, band_done=None):
+        """_stream's band loop (see _process_streamed) over `frame`, _stream_plan's StreamedFrame: the copies, their events and the
+        one context call that each pair of bands.stage_schedule stands for; frame.source (bands.band_source) knows how the rows of
+        frame.host reach the float frame.  The tail's rows -- written into `out`, the result at `depth` -- go back into `sink` -- or,
+        with `band_done`, band_done(b) is called instead once band b's tail is queued (on the launching stream; the JPEG export's sink)."""
         torch, ctx = self._torch, self.ctx
+        host, source, p, bounds, bufs, ha, ma = frame
         H, n = int(bounds[-1]), len(bounds) - 1
         hal, mtf, grain = (bool(p.flags & f) for f in (_lib.F_HALATION, _lib.F_MTF, _lib.F_GRAIN))
         pointwise = not (hal or mtf or grain)
@@ -1040,22 +990,9 @@ class HipProcessor:
             if uploader is not None:
                 uploader.shutdown(cancel_futures=True)
 
-    def _lease_result(self, shape, bits=8):
-        """A pinned buffer of `shape` to lend out as a result of that width, or None when three are out (every lease goes through
-        here; the pools are keyed by width as well as shape)."""
-        return self._depths[bits].pool.lease(shape)
-
-    def _lease_of(self, depth):
-        """`lease=` of depth.pool's sink() and borrow(): _lease_result, looked up when the lease is made, for that width.  An 8-bit
-        lease is a call with the shape alone, so a replacement of _lease_result that takes nothing else (the lease-counting test's
-        wrapper) serves 8-bit results; one that is to see 16-bit leases too takes (shape, bits=8)."""
-        if depth.bits == 8:
-            return lambda shape: self._lease_result(shape)
-        return lambda shape: self._lease_result(shape, depth.bits)
-
     def _copy_streams(self):
         """(host-to-device, device-to-host) copy streams of this processor, made on first use."""
-        if getattr(self, "_up_stream", None) is None:
+        if self._up_stream is None:
             self._up_stream = self._torch.cuda.Stream(device=self.device)
             self._down_stream = self._torch.cuda.Stream(device=self.device)
         return self._up_stream, self._down_stream
@@ -1067,7 +1004,7 @@ class HipProcessor:
         sink = None
         depth = self._depths[8 * out.element_size()]  # a 16-bit result: the same ways back, from the pool of its own width
         if self.result_buffers > 0 or out.numel() >= (3 << 20):
-            sink = depth.pool.sink(tuple(out.shape), self.result_buffers, staged=False, lease=self._lease_of(depth))
+            sink = depth.pool.sink(tuple(out.shape), self.result_buffers, staged=False)
         if sink is None:
             return _host16(out.cpu().numpy())
         sink.target.copy_(out, non_blocking=True)
@@ -1373,4 +1310,5 @@ def torch_div257(torch, image16):
     return torch.div(v, 257, rounding_mode="floor").to(torch.uint8).contiguous()
 
 
+_PROCESS_POSITIONAL = ("self", "src", "negative_film", "grain_size", "grain_sigma", "dst_texture", "histogram_texture", "_")  # no settings
 _LOAD_KEYWORDS = tuple(inspect.signature(HipProcessor.load_image_texture).parameters)[2:]  # (self, src, then these)

@@ -96,15 +96,15 @@ class ResultBuffers:
         self._made += 1
         return self._alloc(shape)
 
-    def sink(self, shape, ring=0, staged=True, lease=None):
-        """A ring buffer (ring > 0), else a lent buffer (`lease`, default self.lease), else a fresh array staged through a pinned
-        buffer -- or with staged=False None (the caller then downloads into a fresh array itself)."""
+    def sink(self, shape, ring=0, staged=True):
+        """A ring buffer (ring > 0), else a lent buffer (lease), else a fresh array staged through a pinned buffer -- or with
+        staged=False None (the caller then downloads into a fresh array itself)."""
         if ring > 0:
             if len(self._ring) != ring or tuple(self._ring[0].shape) != shape:
                 self._ring, self._turn = [self._alloc(shape) for _ in range(ring)], 0
             self._turn += 1
             return ResultSink(self._ring[(self._turn - 1) % ring])
-        leased = (lease or self.lease)(shape)
+        leased = self.lease(shape)
         if leased is not None:
             return ResultSink(leased, give_back=self._free.append)
         if not staged:
@@ -115,11 +115,11 @@ class ResultBuffers:
             self._pool = ThreadPoolExecutor(max_workers=TOUCH_PARTS, thread_name_prefix="r2f-result")
         return ResultSink(self._stage, fresh=np.empty(shape, self._dtype), pool=self._pool)
 
-    def borrow(self, shape, lease=None):
+    def borrow(self, shape):
         """(buffer, give_back) for a caller that fills a whole frame and is done with it before it returns (the TIFF export writes it
         to the file): a lent buffer and how it goes back into the pool, or -- when LEASES of them are out -- the pool's staging buffer,
         which sink() keeps for the same case, and None."""
-        leased = (lease or self.lease)(shape)
+        leased = self.lease(shape)
         if leased is not None:
             return leased, self._free.append
         if self._stage is None or tuple(self._stage.shape) != shape:

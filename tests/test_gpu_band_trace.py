@@ -63,10 +63,10 @@ def proc():
         p._depths[bits] = d._replace(front=tap("front", d.front), tail=tap("tail", d.tail))
     inner = p._run_bands
 
-    def run_bands(host, source, params, bounds, *a, **k):
-        log.update(on=True, calls=[], idents=[], bounds=list(bounds))
+    def run_bands(frame, *a, **k):
+        log.update(on=True, calls=[], idents=[], bounds=list(frame.bounds))
         try:
-            return inner(host, source, params, bounds, *a, **k)
+            return inner(frame, *a, **k)
         finally:
             log["on"] = False
 

@@ -52,9 +52,9 @@ def proc():
     p.band_plans = []
     inner = p._run_bands
 
-    def spy(host, payload, params, bounds, *a, **k):
-        p.band_plans.append(list(bounds))
-        return inner(host, payload, params, bounds, *a, **k)
+    def spy(frame, *a, **k):
+        p.band_plans.append(list(frame.bounds))
+        return inner(frame, *a, **k)
 
     p._run_bands = spy
     yield p

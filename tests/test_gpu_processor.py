@@ -658,7 +658,7 @@ def test_a_large_host_frame_streams_through_the_pipeline_in_row_bands():
 
 def test_a_lent_result_is_never_written_while_anybody_holds_it():
     """process() without result_buffers hands back the caller's own array -- since round 6 a view of one of up to three pinned
-    buffers the processor lends out and takes back when the array and every view of it are gone (hip_processor._lease_result).
+    buffers the processor lends out and takes back when the array and every view of it are gone (results.ResultBuffers.lease).
     A random walk over what a caller may do with results -- keep them, keep a slice only, drop them, keep more than three --
     while frames keep coming: whatever is still held, array or slice, keeps the content it came with."""
     import gc
@@ -674,8 +674,9 @@ def test_a_lent_result_is_never_written_while_anybody_holds_it():
     kw = dict(print_film=prt, lens_correction=False, seed=2, grain=0, halation=False, sharpness=False)
     held = []  # (what the caller kept, a private copy of what it must still hold)
     leases = []
-    inner = proc._lease_result
-    proc._lease_result = lambda shape: (leases.append(inner(shape)), leases[-1])[1]
+    pool = proc._depths[8].pool
+    inner = pool.lease
+    pool.lease = lambda shape: (leases.append(inner(shape)), leases[-1])[1]
     for i in range(60):
         out = proc.process(base * np.float32(0.2 + 0.8 * rng.random()), neg, 6, 0.4, cache=False, **kw)
         what = int(rng.integers(0, 4))
@@ -720,3 +721,57 @@ def test_pinned_result_buffers_return_views_in_turn():
     assert not np.shares_memory(fresh, plain.process(img, neg, 6, 0.4, **kw))  # the default: a new array per call
     plain.close()
     ring.close()
+
+
+def test_a_frame_the_gate_passes_and_the_payload_refuses_is_extracted_once():
+    """process(host array, cache=False) of a frame the host gate lets through (2368 x 2368 x 3: the smallest square above 2 ** 24
+    samples) whose payload then does not stream (a preview resolution: an INTER_AREA step on the device): the payload is extracted
+    once and handed to the one-piece path, which gives the result of a processor that never tries the bands and records nothing
+    for the frame cache -- a following cache=True call of the same array uploads again."""
+    from raw2film_amd import HipProcessor, filmstock
+
+    stocks = filmstock.builtin_stocks()
+    neg, prt = stocks["Kodak Portra 400"], stocks["Kodak 2383"]
+    N = 2368
+    img = np.random.default_rng(23).random((N, N, 3), dtype=np.float32)
+    kw = dict(print_film=prt, lens_correction=False, frame_width=36, frame_height=36, seed=2, grain=0, halation=False, sharpness=False,
+              resolution=(N // 2, N // 2))
+    proc = HipProcessor(device=0)
+    proc.stream_bands = 0
+    want = proc.process(img, neg, 6, 0.4, cache=False, **kw).copy()
+    proc.stream_bands = 16
+    extracts, loads = [], []
+    inner_extract, inner_load = proc.extract_image_data_cpu, proc.prepare_gpu_textures
+    proc.extract_image_data_cpu = lambda *a, **k: (extracts.append(1), inner_extract(*a, **k))[1]
+    proc.prepare_gpu_textures = lambda p: (loads.append(1), inner_load(p))[1]
+    proc.stream_rejected = None
+    got = proc.process(img, neg, 6, 0.4, cache=False, **kw)
+    assert extracts == [1] and loads == [1], (extracts, loads)
+    assert isinstance(proc.stream_rejected, str) and proc.stream_rejected
+    assert got.shape == (N // 2, N // 2, 3)
+    np.testing.assert_array_equal(got, want)
+    assert proc.image_param_dict is None
+    np.testing.assert_array_equal(proc.process(img, neg, 6, 0.4, cache=True, **kw), want)
+    assert loads == [1, 1], "a cache=False frame was taken for the cached one"
+    proc.close()
+
+
+def test_close_releases_what_the_constructor_declares_and_may_be_called_twice():
+    from raw2film_amd import HipProcessor
+
+    neg, prt, _ = stocks()
+    fresh = HipProcessor(device=0)  # (never rendered)
+    fresh.close()
+    fresh.close()
+    used = HipProcessor(device=0)
+    img = _xyz(96, 160)
+    kw = dict(print_film=prt, lens_correction=False, frame_width=1.0, frame_height=0.6, seed=SEED)
+    assert used.process(img, neg, 6, 0.4, **kw).shape == (96, 160, 3)
+    assert used.process_jpeg(img, neg, 6, 0.4, 90, stream=False, **kw)[:2] == b"\xff\xd8"
+    assert used._texture is not None and used._jpeg_host is not None and used.last_output is not None
+    used.close()
+    used.close()
+    for p in (fresh, used):
+        for name in ("_texture", "_texture_src", "image_param_dict", "last_output", "_stream_bufs", "_jpeg_host", "_jpeg_staging",
+                     "_up_stream", "_down_stream"):
+            assert getattr(p, name) is None, name

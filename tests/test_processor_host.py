@@ -314,3 +314,63 @@ def test_payload_without_the_alpha_plane():
     rgba = np.concatenate([img, np.ones_like(img[..., :1])], axis=-1)
     p4 = HipProcessor.extract_image_data_cpu(proc, rgba, lens_correction=False)
     np.testing.assert_array_equal(p4["image_array"], img)
+
+
+def test_the_processor_declares_every_attribute_it_reads():
+    """Every `self.<name>` a HipProcessor method reads is assigned in __init__ or is a class attribute or method, and no method
+    asks for an attribute of its own through getattr(self, "<name>", default): state the constructor does not know about."""
+    import ast
+
+    from raw2film_amd import hip_processor
+
+    tree = ast.parse(inspect.getsource(hip_processor))
+    cls = next(n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "HipProcessor")
+    declared = set()
+    for node in cls.body:
+        if isinstance(node, (ast.FunctionDef, ast.AsyncFunctionDef)):
+            declared.add(node.name)
+        elif isinstance(node, (ast.Assign, ast.AnnAssign)):
+            for target in (node.targets if isinstance(node, ast.Assign) else [node.target]):
+                declared.update(n.id for n in ast.walk(target) if isinstance(n, ast.Name))
+    init = next(n for n in cls.body if isinstance(n, ast.FunctionDef) and n.name == "__init__")
+
+    def own(node, ctx):
+        return (isinstance(node, ast.Attribute) and isinstance(node.ctx, ctx) and isinstance(node.value, ast.Name)
+                and node.value.id == "self")
+
+    declared.update(n.attr for n in ast.walk(init) if own(n, ast.Store))
+    assert {"_texture", "_stream_bufs", "_jpeg_host", "_jpeg_staging", "_up_stream", "stream_rejected", "last_stage_ms"} <= declared
+    read = {n.attr for n in ast.walk(cls) if own(n, ast.Load)}
+    assert read - declared == set(), sorted(read - declared)
+    probes = [n for n in ast.walk(cls) if isinstance(n, ast.Call) and isinstance(n.func, ast.Name) and n.func.id == "getattr"
+              and n.args and isinstance(n.args[0], ast.Name) and n.args[0].id == "self" and len(n.args) > 1
+              and isinstance(n.args[1], ast.Constant) and isinstance(n.args[1].value, str)]
+    assert probes == [], [ast.unparse(n) for n in probes]
+
+
+def test_every_export_resets_stream_rejected_and_refuses_textures():
+    """process_jpeg, process_preloaded_jpeg, process_tiff and process_preloaded_tiff share one prologue: `stream_rejected` and
+    `exposure_rejected` are None from the call's entry on -- whatever an earlier call left, with stream=False too, and before a
+    texture is refused --, and dst_texture / histogram_texture are refused by name."""
+    import re
+
+    p = object.__new__(HipProcessor)
+    frame = np.zeros((2, 3, 3), np.float32)
+    p.extract_image_data_cpu = lambda src, **kw: {"image_array": src}
+    p._render_export = lambda *a, **kw: "the device result"
+    p._encode_device = lambda out, o: b"\xff\xd8 jpeg"
+    p._download = lambda out: np.zeros((2, 3, 3), np.uint8)
+    for name, first, hint in (("process_jpeg", frame, " (use process() for the preview)"),
+                              ("process_preloaded_jpeg", {"image_array": frame}, ""),
+                              ("process_tiff", frame, " (use process() for the preview)"),
+                              ("process_preloaded_tiff", {"image_array": frame}, "")):
+        export = getattr(p, name)
+        p.stream_rejected = p.exposure_rejected = "left by an earlier call"
+        data = export(first, "film", 6, 0.4, stream=False)
+        assert isinstance(data, bytes) and data, name
+        assert p.stream_rejected is None and p.exposure_rejected is None, name
+        for texture in ("dst_texture", "histogram_texture"):
+            p.stream_rejected = "left by an earlier call"
+            with pytest.raises(ValueError, match=re.escape(f"{name} writes a file: {texture} is not taken{hint}") + "$"):
+                export(first, "film", 6, 0.4, stream=False, **{texture: object()})
+            assert p.stream_rejected is None, (name, texture)

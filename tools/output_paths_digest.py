@@ -8,7 +8,7 @@ line.  Non-streamed cases use 96 x 160 and 70 x 257 frames (the odd width takes 
 output); streamed cases use 2368 x 2368 x 3, just above the 2 ** 24 samples the gate admits, in four bands, so that the taper and
 the stencil lag are exercised; the streamed Bayer mosaics (raw_profile=, stops given) are 2400 x 2368 at full size and 4800 x 4736 at
 half size, of which the square format keeps that window.  A streamed case whose frame did not stream prints `stream_rejected` in
-place of a digest.
+place of a digest (one case is made for that: the host gate passes, a preview resolution then keeps the payload from streaming).
 The `prepath` group renders the small frames through what runs ahead of the pipeline: the crops and quarter turns, the free
 rotation, exposure="device", a LensProfile, a RawProfile mosaic at full and half size, both together, the two-phase API and the
 exports of such frames, and one encode_jpeg call with every JPEG keyword set.
@@ -213,6 +213,9 @@ def streamed_cases(proc, torch, neg, prt):
             pageable, neg, 6, 0.4, cache=False, output_bits=bits, **stencils_on)))
     proc.stream_bands = 4
     digest("one_piece_process_tiff_big 16", timed("one_piece_process_tiff_big 16", lambda: proc.process_tiff(pageable, neg, 6, 0.4, **stencils_on)))
+    # the host gate lets the frame through, its payload then does not stream (a preview resolution): extracted once, rendered whole
+    streamed("gate_passed_payload_refused", lambda: proc.process(pageable, neg, 6, 0.4, cache=False, resolution=(BIG // 2, BIG // 2), **pointwise))
+    digest("gate_passed_payload_refused_last_output", proc.last_output.cpu().numpy())  # (the line above holds the reason, not the pixels)
     streamed("streamed_process_jpeg", lambda: proc.process_jpeg(pageable, neg, 6, 0.4, 90, stream=True, **stencils_on))
     streamed("streamed_process_jpeg_pinned_444", lambda: proc.process_jpeg(pinned, neg, 6, 0.4, 90, stream=True, subsampling=0, **pointwise))
     streamed("streamed_process_preloaded_jpeg", lambda: proc.process_preloaded_jpeg(payload, neg, 6, 0.4, 90, stream=True, **stencils_on))
