@@ -505,6 +505,85 @@ R2F_API int r2f_demosaic_f32(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0
                      const r2f_demosaic_params* params, int row0, int col0, int rows, int cols, float divisor, float factor,
                      float* dst_f32_hwc3, int y0, int y1, void* stream);
 
+/* Demosaic of a mosaic with a 6 x 6 colour filter array (Fujifilm's X-Trans) on the device: the same share of raw_to_linear as the
+ * Bayer path above, next to it.  LibRaw switches to its own X-Trans interpolation (Markesteijn's) for these files; THIS IS NOT
+ * THAT ALGORITHM.  It is the project's own interpolation -- directional green, colour-difference red and blue -- defined here in
+ * integers, and parity with LibRaw's bytes is UNPINNED: rawpy is on no machine this project sees.  What the tests pin is THIS
+ * definition (tests/xtrans_model.py restates it in NumPy).  Nothing is special-cased to Fujifilm's layout: every admissible
+ * pattern (below) is handled, among them the canonical GBGGRG / RGRBGB / GBGGRG / GRGGBG / BGBRGR / GRGGBG and its 36 cyclic shifts.
+ *
+ * Inputs.  The mosaic is uint16 (H, W), H, W >= 6.  col(y, x) = pattern[y % 6][x % 6] in {R, G, B} = {0, 1, 2}.  black[36] (int32)
+ * is indexed by the site's phase (y % 6) * 6 + x % 6, mul[3] (float) by its colour.  M is a float 3 x 3 matrix.  floor(a / n) is
+ * the floor division of a signed int (toward minus infinity).
+ * A. Scale, as in the Bayer definition: t = (int)raw - black[phase]; S = clamp(trunc(fl((float)t * mul[col])), 0, 65535).
+ * B. Full size.
+ *    B0, border ring: every pixel with y < 3, y >= H - 3, x < 3 or x >= W - 3.  Each non-native colour c is floor(sum / count) of S
+ *        over the sites of colour c in the 3 x 3 neighbourhood clipped to the frame; 0 when count is 0.  The native colour is S.
+ *    B1, green, defined wherever B2 reads it: at the sites with 2 <= y < H - 2 and 2 <= x < W - 2.  Green at a green site is S.  At a
+ *        non-green site, for the directions h = (0, 1) and v = (1, 0): a >= 1 is the distance to the nearest green site on the
+ *        negative side, b >= 1 that on the positive side (an admissible pattern has a, b <= 2), S(-a) and S(+b) those two samples;
+ *          est  = floor((b S(-a) + a S(+b) + floor((a + b) / 2)) / (a + b))
+ *          diff = |S(-a) - S(+b)|,  span = a + b
+ *        v iff diff_h span_v > diff_v span_h, otherwise h; G is that direction's est.
+ *    B2, red and blue at the interior pixels 3 <= y < H - 3, 3 <= x < W - 3.  For each colour c that is not the site's own, Q is the
+ *        set of sites of colour c in the centred 3 x 3; w = 2 for the four edge neighbours, 1 for the four diagonal ones:
+ *          C = clamp(G(0) + floor(sum_Q w(q) (S(q) - G(q)) / sum_Q w(q)), 0, 65535),  G from B1
+ *        (for c = green at a non-green site every term is 0: the green of an interior pixel is B1's).  An admissible pattern has Q
+ *        non-empty.  No pass reads what the same pass writes: every output pixel is a function of S within 3 samples of it.
+ * B'. Reduced size (upstream's half_size=True; for a 6 x 6 array it yields A THIRD, not a half): the output is (H / 3, W / 3),
+ *    rounded down; pixel (y, x) comes from the 3 x 3 cell at (3 y, 3 x), each channel floor(sum / count) of S over the cell's sites of
+ *    that colour.  Trailing rows and columns that do not fill a cell are dropped.
+ * C. Colour: step C of the Bayer definition, unchanged.
+ * Every intermediate stays well inside int32: B1's numerator is at most 4 * 65535 + 2, B2's at most 12 * 65535 in magnitude.
+ *
+ * Admissible patterns (r2f_xtrans_plan returns R2F_EINVAL otherwise): 36 colour ids in {0, 1, 2}, each colour present; every
+ * non-green site has a green site within 2 on both sides along h and along v, the pattern taken cyclically; every centred 3 x 3,
+ * taken cyclically, holds both colours other than its centre's; for the reduced size each of the four aligned 3 x 3 cells holds all
+ * three colours (the planner checks it then, but the rule before it already says so: an aligned cell is the centred 3 x 3 of its
+ * middle site, so no pattern is admissible at full size only).  The numeric bounds are r2f_demosaic_plan's: black integral in [0, 65535], multipliers in (0, 1024]
+ * as floats too, |M| <= 64, every number finite.  H or W below 6 is refused. */
+typedef struct r2f_xtrans_profile {
+    int32_t pattern[36]; /* colour id per phase, reading order */
+    int32_t reduced;
+    double black[36];
+    double mul[3];
+    double matrix[9];
+} r2f_xtrans_profile;
+/* The constants of the definition for one frame size, and the per-phase tables with which no lane searches for a neighbour:
+ * gap[phase] = {a_h, b_h, a_v, b_v} of B1 (0 at a green site); for slot 0 = red and slot 1 = blue, taps[phase][slot] the 3 x 3 mask
+ * of Q (bit (dy + 1) * 3 + dx + 1; 0 for the site's own colour), wsum its weight sum and recip = floor(2^32 / wsum) + 1 (0 where
+ * wsum <= 1), the multiplier of the floor division (r2f_xtrans_math.h has the proof of range); cell_count[(cy, cx)][c] the sites of
+ * colour c in the aligned cell at phase (3 cy, 3 cx). */
+typedef struct r2f_xtrans_params {
+    uint8_t cfa[36];
+    uint8_t gap[36][4];
+    uint16_t taps[36][2];
+    uint8_t wsum[36][2];
+    uint8_t cell_count[4][3];
+    uint32_t recip[36][2];
+    int32_t black[36];
+    float mul[3];
+    float M[9];
+    int32_t reduced, out_h, out_w;
+} r2f_xtrans_params;
+/* Host planner (raw2film_amd/csrc/r2f_xtrans_plan.cpp; no GPU, no context): profile + (H, W) -> params, or R2F_EINVAL for what the
+ * text above refuses; a refusal leaves *out alone. */
+R2F_API int r2f_xtrans_plan(const r2f_xtrans_profile* profile, int H, int W, r2f_xtrans_params* out);
+/* The demosaic itself, with r2f_demosaic_u16's row-range contract.  src_rows: uint16 mosaic rows [src_gy0, src_gy0 + src_nrows) of
+ * the H x W frame on the device, src_pitch samples apart (>= W).  Writes output rows [y0, y1) of dst (uint16 (out_h, out_w, 3), row
+ * 0 at dst) and nothing else.  Full size reads mosaic rows [y0 - 3, y1 + 3) clipped to [0, H), reduced size [3 y0, 3 y1); those rows
+ * must lie inside the source window, else R2F_EINVAL before any launch.  A band's bytes are those of the same rows of a whole-frame
+ * call, whatever the cut (it need not be a multiple of 6 or 3), the pitch or the source's alignment.  Params whose tables are not
+ * those the planner derives from their cfa are refused.
+ * Full size is one launch shaped like the Bayer one: a block stages its 64 x 32 tile of scaled samples with a 3-sample apron in LDS
+ * (step A once per sample), derives the colour-difference plane S - G of the tile plus a 1-sample apron there (B1), then B2 / C per
+ * output pixel; rows leave as contiguous segments through an LDS transpose.  The phase is that of the frame, never of the tile.
+ * Reduced size is a lane per output pixel.  Row bands do not stream through the pipeline yet (raw2film_amd: the one-piece path). */
+R2F_API int r2f_demosaic_xtrans_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
+                     const r2f_xtrans_params* params, uint16_t* dst_u16_hwc3, int y0, int y1, void* stream);
+/* r2f_demosaic_xtrans_u16's tile (test shapes are derived from it): its sides are 4 and 2 modulo 6. */
+enum { R2F_XTRANS_TILE_W = 64, R2F_XTRANS_TILE_H = 32 };
+
 /* The hand-off from RAW decoding: the last two lines of raw_to_linear (raw_conversion.py:50-52) applied to LibRaw's 16-bit
  * output on the device, so that a decoded frame crosses PCIe as uint16 (6 bytes per pixel) instead of float32 (12 or 16):
  * dst = float(src) / divisor (65535, one correctly rounded fp32 division) * factor (the float32 of 2 ** calc_exposure(...),

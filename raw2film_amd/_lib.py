@@ -17,6 +17,7 @@ LAYOUT_HWC3, LAYOUT_HWC4, LAYOUT_CHW = 0, 1, 2
 LENS_NONE, LENS_POLY3, LENS_POLY5, LENS_PTLENS = 0, 1, 2, 3
 CFA_RGGB, CFA_BGGR, CFA_GRBG, CFA_GBRG = 0, 1, 2, 3
 DEMOSAIC_TILE_W, DEMOSAIC_TILE_H = 64, 32  # R2F_DEMOSAIC_TILE_*
+XTRANS_TILE_W, XTRANS_TILE_H = 64, 32  # R2F_XTRANS_TILE_*
 KERNEL_HALATION, KERNEL_MTF, KERNEL_GRAIN = 0, 1, 2
 F_MATRIX, F_HALATION, F_MTF, F_GRAIN, F_GRAIN_MONO, F_BURN, F_IDENTITY_DONE, F_FRAME_RESIDENT = 1, 2, 4, 8, 16, 32, 64, 128
 F_TRACK_RANGE, F_RANGE_VALID = 256, 512
@@ -90,6 +91,17 @@ class RawProfile(C.Structure):  # r2f_raw_profile (raw2film_amd.raw.RawProfile f
 class DemosaicParams(C.Structure):  # r2f_demosaic_params: the constants of one frame size
     _fields_ = [("cfa", C.c_int32 * 4), ("black", C.c_int32 * 4), ("mul", C.c_float * 4), ("M", C.c_float * 9),
                 ("half_size", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32)]
+
+
+class XTransProfile(C.Structure):  # r2f_xtrans_profile (raw2film_amd.raw.XTransProfile fills it)
+    _fields_ = [("pattern", C.c_int32 * 36), ("reduced", C.c_int32), ("black", C.c_double * 36), ("mul", C.c_double * 3),
+                ("matrix", C.c_double * 9)]
+
+
+class XTransParams(C.Structure):  # r2f_xtrans_params: the constants and per-phase tables of one frame size
+    _fields_ = [("cfa", C.c_uint8 * 36), ("gap", C.c_uint8 * 4 * 36), ("taps", C.c_uint16 * 2 * 36), ("wsum", C.c_uint8 * 2 * 36),
+                ("cell_count", C.c_uint8 * 3 * 4), ("recip", C.c_uint32 * 2 * 36), ("black", C.c_int32 * 36), ("mul", C.c_float * 3),
+                ("M", C.c_float * 9), ("reduced", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32)]
 
 
 _P = C.POINTER
@@ -181,6 +193,11 @@ _SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(DemosaicParams), C.c_int, C.c_int, C.c_int, C.c_int,
          C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    ),
+    "r2f_xtrans_plan": (C.c_int, [_P(XTransProfile), C.c_int, C.c_int, _P(XTransParams)]),
+    "r2f_demosaic_xtrans_u16": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(XTransParams), C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     ),
     "r2f_resize_lanczos4_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "r2f_lanczos4_table": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -589,6 +589,34 @@ class HipContext:
                                                out.data_ptr(), y0, y1, self._stream()))
         return out
 
+    def demosaic_xtrans(self, mosaic, params, out=None, rows=None):
+        """The X-Trans demosaic of include/r2f.h (r2f_demosaic_xtrans_u16: black / scale, the project's own directional-green /
+        colour-difference interpolation or the reduced third-size form, camera matrix, clip -- not LibRaw's algorithm) of a uint16
+        (H, W) CUDA mosaic of at least 6 x 6 samples (int16 tensors are read as the same bits; rows may be pitched) -> uint16
+        (out_h, out_w, 3), the frame decode_u16 / decode_u16_auto / exposure_rows take.
+        params: a raw2film_amd.raw.XTransProfile (planned full size for this mosaic) or the r2f_xtrans_params of its size.
+        rows = (y0, y1): only those output rows of `out` are written (default: all)."""
+        torch = self._torch
+        if not (isinstance(mosaic, torch.Tensor) and mosaic.is_cuda and mosaic.dtype in (torch.uint16, torch.int16) and mosaic.dim() == 2
+                and mosaic.shape[0] >= 6 and mosaic.shape[1] >= 6 and mosaic.stride(1) == 1 and mosaic.stride(0) >= mosaic.shape[1]):
+            raise ValueError("demosaic_xtrans needs a uint16 (H, W) CUDA mosaic of at least 6 x 6 samples with contiguous rows")
+        self._same_device(mosaic, "mosaic")
+        H, W = int(mosaic.shape[0]), int(mosaic.shape[1])
+        if not isinstance(params, _lib.XTransParams):
+            params = params.plan(H, W)
+        shape = (int(params.out_h), int(params.out_w), 3)
+        if out is None:
+            out = torch.empty(shape, dtype=mosaic.dtype, device=self.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype in (torch.uint16, torch.int16) and out.is_contiguous()
+                  and tuple(out.shape) == shape):
+            raise ValueError(f"demosaic_xtrans: out must be a contiguous uint16 CUDA tensor of shape {shape}")
+        else:
+            self._same_device(out, "out")
+        y0, y1 = (0, shape[0]) if rows is None else (int(rows[0]), int(rows[1]))
+        self._check(self._lib.r2f_demosaic_xtrans_u16(self._h, mosaic.data_ptr(), 0, H, int(mosaic.stride(0)), H, W, C.byref(params),
+                                                      out.data_ptr(), y0, y1, self._stream()))
+        return out
+
     def demosaic_f32(self, mosaic, params, factor: float, divisor: float = 65535.0, window=None, out=None, rows=None):
         """demosaic_u16 and decode_u16 in one kernel (r2f_demosaic_f32): window = (row0, col0, rows, cols) of the demosaiced frame
         (default: all of it) -> float32 (rows, cols, 3), bit-identical to decode_u16(demosaic_u16(mosaic)[window], factor, divisor).

@@ -342,7 +342,10 @@ class HipProcessor:
         No RGB frame exists on the host, so exposure=None is measured on the device like exposure="device"; where that is refused (a
         turned or rotated frame) the call needs explicit stops.  With the stops given, no quarter turn and no lens step, the payload
         of a large mosaic streams in row bands (payload.stream_rejection): band k travels as the mosaic rows its demosaic reads
-        (payload.mosaic_upload_bounds) and is demosaiced straight into the float frame (r2f_demosaic_f32)."""
+        (payload.mosaic_upload_bounds) and is demosaiced straight into the float frame (r2f_demosaic_f32).
+        A raw2film_amd.raw.XTransProfile in its place: `src` is an X-Trans mosaic (6 x 6 array, at least 6 x 6 samples), demosaiced by
+        r2f_demosaic_xtrans_u16 -- the project's own interpolation, not LibRaw's; `demosaic` holds the r2f_xtrans_params; half_size
+        yields a third of the mosaic's sides; such a payload takes the one-piece path (it does not stream yet)."""
         on_device = exposure_on_device(exposure)
         phase1.check_profiles(raw_profile, lens_profile, lens_correction, cam, lens)
         # _internal (load_image_texture: the payload never leaves this object): no alpha plane, and the clamp of
@@ -440,7 +443,9 @@ class HipProcessor:
         when its exposure is given in stops, rotate_times is a multiple of 4 and no lens step follows: each band is demosaiced
         into the float frame as its mosaic rows arrive (r2f_demosaic_f32), with the bytes of the one-piece call.  Without stops
         (the device's statistic is the whole demosaiced frame's), turned, or with a lens_profile it is demosaiced whole, and
-        `stream_rejected` of an export names the demosaic step and the reason."""
+        `stream_rejected` of an export names the demosaic step and the reason.  With a raw2film_amd.raw.XTransProfile `src` is an
+        X-Trans mosaic (r2f_demosaic_xtrans_u16: the project's own interpolation; half_size yields a third); it is always demosaiced
+        whole ("X-Trans mosaics do not stream yet")."""
         settings = dict(locals())  # every keyword of the signature (the unknown ones in `_` aside), named nowhere else
         exposure_on_device(exposure)  # (any string but "device" raises before any work starts)
         settings["output_bits"] = check_output_bits(output_bits, dst_texture)
@@ -724,7 +729,8 @@ class HipProcessor:
 
     def _host_stream_gate(self, src, settings):
         """payload.host_stream_gate of a call's `settings` (process()'s keywords): why its frame is rendered in one piece, or None."""
-        mosaic = settings["raw_profile"] is not None
+        profile = settings["raw_profile"]
+        mosaic = profile is not None
         exposure = settings["exposure"]
         return host_stream_gate(src, self.stream_bands, settings["rotation"], settings["chroma_nr"], settings["canvas_mode"],
                                 settings["highlight_burn"], bool(settings["lens_correction"]) and settings["lens_profile"] is not None,
@@ -732,7 +738,9 @@ class HipProcessor:
                                 rotate_times=settings["rotate_times"],
                                 frame_samples=phase1.mosaic_frame_samples(src, settings["half_size"],
                                                                           settings["frame_width"] / settings["frame_height"],
-                                                                          settings["flip"], settings["zoom"]) if mosaic else None)
+                                                                          settings["flip"], settings["zoom"],
+                                                                          getattr(profile, "reduction", 2)) if mosaic else None,
+                                xtrans=isinstance(profile, phase1.XTransProfile))
 
     @staticmethod
     def _refuse_textures(what, settings, hint=""):
@@ -1086,8 +1094,9 @@ class HipProcessor:
             return torch.rot90(image, k, dims) if k else image
 
         demosaic_step = cpu_payload.get("demosaic")
-        if demosaic_step:  # a Bayer mosaic: LibRaw's share of raw_to_linear on the device -> the uint16 frame of the lines below
-            image = cut_and_turn(self.ctx.demosaic_u16(image.contiguous(), demosaic_step["params"]), demosaic_step["window"],
+        if demosaic_step:  # a mosaic: LibRaw's share of raw_to_linear on the device -> the uint16 frame of the lines below
+            demosaic = self.ctx.demosaic_xtrans if phase1.is_xtrans(demosaic_step["params"]) else self.ctx.demosaic_u16
+            image = cut_and_turn(demosaic(image.contiguous(), demosaic_step["params"]), demosaic_step["window"],
                                  demosaic_step["rotate_times"], dims=(0, 1))
         if image.dtype in (torch.int16, torch.uint16):  # a decoded 16-bit frame: raw_conversion.py:50-52 on the device
             if cpu_payload.get("u16_factor") is None:

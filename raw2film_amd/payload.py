@@ -17,9 +17,9 @@ from typing import NamedTuple
 
 import numpy as np
 
-from . import geometry
+from . import _lib, geometry
 from .lens import LensProfile
-from .raw import RawProfile
+from .raw import RawProfile, XTransProfile
 
 _DEMOSAIC_REJECTED = "the demosaic step (raw_profile): "  # every refusal of a mosaic begins with it, then says why
 _LENS_REJECTED = "the lens step (lens_profile): its gather reads the whole frame, which a row band does not hold"
@@ -29,9 +29,12 @@ DEVICE_EXPOSURE = "device"  # exposure="device": the auto exposure of a uint16 f
                             # payload carries in place of its float `u16_factor`
 
 
-def mosaic_rejection(stops, rotate_times, lens, samples):
-    """Why a Bayer mosaic is demosaiced whole instead of band by band (r2f_demosaic_f32), or None.  stops: the exposure is given in
-    stops; samples: rows x cols x 3 of the window of the demosaiced frame that the pipeline takes, or None when nobody cut one."""
+def mosaic_rejection(stops, rotate_times, lens, samples, xtrans=False):
+    """Why a mosaic is demosaiced whole instead of band by band (r2f_demosaic_f32), or None.  stops: the exposure is given in
+    stops; samples: rows x cols x 3 of the window of the demosaiced frame that the pipeline takes, or None when nobody cut one;
+    xtrans: the mosaic is an X-Trans one (r2f_demosaic_xtrans_u16 has the row-range contract, the band loop does not use it yet)."""
+    if xtrans:
+        return _DEMOSAIC_REJECTED + "X-Trans mosaics do not stream yet"
     if not stops:
         return _DEMOSAIC_REJECTED + ("the exposure is not given in stops: measured on the device, its statistic is the whole demosaiced "
                                      "frame's, which is demosaiced in one piece for it")
@@ -81,7 +84,7 @@ def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canv
     if step:
         window = step.get("window")
         why = mosaic_rejection(isinstance(payload.get("u16_factor"), float), step.get("rotate_times") or 0, payload.get("lens"),
-                               None if window is None else int(window[2]) * int(window[3]) * 3)
+                               None if window is None else int(window[2]) * int(window[3]) * 3, is_xtrans(step.get("params")))
         if why is not None:
             return why
     if payload.get("lens"):
@@ -100,16 +103,22 @@ def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canv
     return None
 
 
+def is_xtrans(params) -> bool:
+    """A demosaic step's `params` are those of an X-Trans mosaic (r2f_xtrans_params), not of a Bayer one."""
+    return isinstance(params, _lib.XTransParams)
+
+
 def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="No", highlight_burn=0.0, lens=False, demosaic=False, *,
-                     stops=False, rotate_times=0, frame_samples=None):
+                     stops=False, rotate_times=0, frame_samples=None, xtrans=False):
     """Why process(src, cache=False) renders a frame in one piece before it extracts its payload (stream_rejection and plan_bands
     come after that), or None.  lens: the call corrects the lens (lens_correction with a lens_profile); demosaic: its source is a
-    Bayer mosaic (raw_profile), for which stops says that the exposure is given in stops, rotate_times is the call's, and
-    frame_samples the samples of the window of the demosaiced frame that the pipeline takes (mosaic_frame_samples)."""
+    mosaic (raw_profile), for which stops says that the exposure is given in stops, rotate_times is the call's, frame_samples the
+    samples of the window of the demosaiced frame that the pipeline takes (mosaic_frame_samples), and xtrans that the profile is an
+    XTransProfile (which does not stream yet)."""
     if stream_bands <= 1:
         return f"stream_bands = {stream_bands}"
     if demosaic:
-        why = mosaic_rejection(stops, rotate_times, lens, frame_samples)
+        why = mosaic_rejection(stops, rotate_times, lens, frame_samples, xtrans)
         if why is not None:
             return why
     if lens:
@@ -124,12 +133,13 @@ def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="
     return None
 
 
-def mosaic_frame_samples(src, half_size, aspect, flip, zoom):
+def mosaic_frame_samples(src, half_size, aspect, flip, zoom, reduction=2):
     """host_stream_gate's frame_samples for a mosaic `src`: rows x cols x 3 of the window that the aspect and zoom crops keep of
-    its demosaiced frame (plan_crops without a rotation, which the gate refuses by itself), or None when `src` is no 2-D array."""
+    its demosaiced frame (plan_crops without a rotation, which the gate refuses by itself), or None when `src` is no 2-D array.
+    reduction: what half_size divides the mosaic's sides by, as its profile states it (2 for a Bayer quad, 3 for X-Trans cells)."""
     if not isinstance(src, np.ndarray) or src.ndim != 2:
         return None
-    rows, cols = (src.shape[0] // 2, src.shape[1] // 2) if half_size else src.shape
+    rows, cols = (src.shape[0] // reduction, src.shape[1] // reduction) if half_size else src.shape
     if rows < 1 or cols < 1:
         return None
     window = plan_crops(rows, cols, True, aspect, flip, zoom, 0.0, 0, False, False, True).demosaic["window"]
@@ -138,8 +148,8 @@ def mosaic_frame_samples(src, half_size, aspect, flip, zoom):
 
 def check_profiles(raw_profile, lens_profile, lens_correction, cam, lens):
     """The caller's profiles are of their types, and the call needs no lensfun lookup."""
-    if raw_profile is not None and not isinstance(raw_profile, RawProfile):
-        raise ValueError(f"raw_profile must be a raw2film_amd.raw.RawProfile, got {type(raw_profile).__name__}")
+    if raw_profile is not None and not isinstance(raw_profile, (RawProfile, XTransProfile)):
+        raise ValueError(f"raw_profile must be a raw2film_amd.raw.RawProfile or XTransProfile, got {type(raw_profile).__name__}")
     if lens_profile is not None and not isinstance(lens_profile, LensProfile):
         raise ValueError(f"lens_profile must be a raw2film_amd.lens.LensProfile, got {type(lens_profile).__name__}")
     if lens_correction and cam is not None and lens is not None:

@@ -4,6 +4,9 @@ Upstream has LibRaw do everything behind the file parser (raw_conversion.raw_to_
 demosaic, camera matrix, 16-bit clip.  The parser is third-party input; this module takes its RESULT -- the CFA pattern, the black
 levels, the multipliers, the camera matrix -- and `plan()` turns it into the constants of one frame size (r2f_demosaic_plan).  The
 mosaic itself is the `src` of the call.  The definition of the arithmetic is in include/r2f.h (r2f_demosaic_u16).
+
+XTransProfile is the same record for a 6 x 6 array (r2f_xtrans_plan, r2f_demosaic_xtrans_u16).  Each profile states its own
+`reduction`: what half_size=True divides a mosaic's sides by.
 """
 
 from __future__ import annotations
@@ -18,16 +21,28 @@ from . import _lib
 _PATTERNS = {"RGGB": _lib.CFA_RGGB, "BGGR": _lib.CFA_BGGR, "GRBG": _lib.CFA_GRBG, "GBRG": _lib.CFA_GBRG}
 
 
-def _floats(name, values, counts):
+def _floats(name, values, counts, who="RawProfile"):
     try:
         out = tuple(float(v) for v in values)
     except TypeError:
-        raise ValueError(f"RawProfile.{name} must be {' or '.join(str(n) for n in counts)} numbers, got {values!r}") from None
+        raise ValueError(f"{who}.{name} must be {' or '.join(str(n) for n in counts)} numbers, got {values!r}") from None
     if len(out) not in counts:
-        raise ValueError(f"RawProfile.{name} must be {' or '.join(str(n) for n in counts)} numbers, got {len(out)}")
+        raise ValueError(f"{who}.{name} must be {' or '.join(str(n) for n in counts)} numbers, got {len(out)}")
     if not all(math.isfinite(v) for v in out):
-        raise ValueError(f"RawProfile.{name} must be finite, got {values!r}")
+        raise ValueError(f"{who}.{name} must be finite, got {values!r}")
     return out
+
+
+def _matrix(matrix, who):
+    try:
+        rows = tuple(_floats("matrix", row, (3,), who) for row in matrix)
+    except TypeError:
+        raise ValueError(f"{who}.matrix must be 3 x 3, got {matrix!r}") from None
+    if len(rows) != 3:
+        raise ValueError(f"{who}.matrix must be 3 x 3, got {len(rows)} rows")
+    if any(abs(v) > 64 for row in rows for v in row):
+        raise ValueError(f"{who}.matrix entries must lie in [-64, 64], got {matrix!r}")
+    return rows
 
 
 @dataclass(frozen=True)
@@ -42,6 +57,8 @@ class RawProfile:
     black: tuple | float = 0
     multipliers: tuple = (1.0, 1.0, 1.0)
     matrix: tuple = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
+
+    reduction = 2  # what half_size=True divides a mosaic's sides by (no dataclass field: not part of equality, hash or repr)
 
     def __post_init__(self):
         if not isinstance(self.pattern, str) or self.pattern not in _PATTERNS:
@@ -60,15 +77,7 @@ class RawProfile:
         if any(not 0 < m <= 1024 for m in mul):
             raise ValueError(f"RawProfile.multipliers must lie in (0, 1024], got {self.multipliers!r}")
         set_("multipliers", mul)
-        try:
-            rows = tuple(_floats("matrix", row, (3,)) for row in self.matrix)
-        except TypeError:
-            raise ValueError(f"RawProfile.matrix must be 3 x 3, got {self.matrix!r}") from None
-        if len(rows) != 3:
-            raise ValueError(f"RawProfile.matrix must be 3 x 3, got {len(rows)} rows")
-        if any(abs(v) > 64 for row in rows for v in row):
-            raise ValueError(f"RawProfile.matrix entries must lie in [-64, 64], got {self.matrix!r}")
-        set_("matrix", rows)
+        set_("matrix", _matrix(self.matrix, "RawProfile"))
 
     def to_c(self, half_size: bool = False) -> _lib.RawProfile:
         p = _lib.RawProfile(pattern=_PATTERNS[self.pattern], half_size=int(bool(half_size)))
@@ -84,4 +93,72 @@ class RawProfile:
         profile = self.to_c(half_size)
         if _lib.load().r2f_demosaic_plan(C.byref(profile), int(H), int(W), C.byref(out)) != _lib.OK:
             raise ValueError(f"r2f_demosaic_plan refused {self!r} for a {H} x {W} mosaic (half_size={bool(half_size)})")
+        return out
+
+
+XTRANS = ("GBGGRG", "RGRBGB", "GBGGRG", "GRGGBG", "BGBRGR", "GRGGBG")  # the canonical layout; a camera's is one of its 36 cyclic shifts
+
+
+@dataclass(frozen=True)
+class XTransProfile:
+    """What a RAW file's parser knows of a frame with a 6 x 6 colour filter array (Fujifilm's X-Trans), for the demosaic on the
+    device: r2f_demosaic_xtrans_u16 of include/r2f.h -- the project's own interpolation, not LibRaw's (Markesteijn's); parity with
+    LibRaw's bytes is unpinned.  A frozen, hashable record (part of the image cache key, like RawProfile).
+
+    pattern: six strings of six letters from "RGB" (the rows of the array at (0, 0)), or one string of 36.  Which patterns are
+        admissible is the planner's to say (`plan`): green within 2 samples on both sides of every other site along rows and
+        columns, both other colours in every centred 3 x 3.
+    black: one level for every site, or 36 per phase ((y % 6) * 6 + x % 6); integers in [0, 65535].
+    multipliers: (r, g, b); each in (0, 1024].  They hold the white balance AND the scale to 16 bits.
+    matrix: 3 x 3, rows are the output channels; |entries| <= 64.
+    half_size=True yields A THIRD of the mosaic's sides (the 3 x 3 cells of the array), not a half: `reduction`."""
+    pattern: tuple | str = XTRANS
+    black: tuple | float = 0
+    multipliers: tuple = (1.0, 1.0, 1.0)
+    matrix: tuple = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
+
+    reduction = 3
+
+    def __post_init__(self):
+        set_ = lambda k, v: object.__setattr__(self, k, v)  # noqa: E731 -- (frozen: normalised to tuples once)
+        pattern = self.pattern
+        if isinstance(pattern, str):
+            pattern = tuple(pattern[i:i + 6] for i in range(0, 36, 6)) if len(pattern) == 36 else (pattern,)
+        try:
+            pattern = tuple(pattern)
+        except TypeError:
+            pattern = ()
+        if len(pattern) != 6 or not all(isinstance(r, str) and len(r) == 6 and set(r) <= set("RGB") for r in pattern):
+            raise ValueError(f"XTransProfile.pattern must be six strings of six letters from 'RGB' (or one of 36), got {self.pattern!r}")
+        if set("".join(pattern)) != set("RGB"):
+            raise ValueError(f"XTransProfile.pattern must hold each of R, G and B, got {self.pattern!r}")
+        set_("pattern", pattern)
+        black = self.black
+        if isinstance(black, numbers.Real) and not isinstance(black, bool):
+            black = (black,) * 36
+        black = _floats("black", black, (36,), "XTransProfile")
+        if any(b < 0 or b > 65535 or b != math.floor(b) for b in black):
+            raise ValueError(f"XTransProfile.black must be integers in [0, 65535], got {self.black!r}")
+        set_("black", black)
+        mul = _floats("multipliers", self.multipliers, (3,), "XTransProfile")
+        if any(not 0 < m <= 1024 for m in mul):
+            raise ValueError(f"XTransProfile.multipliers must lie in (0, 1024], got {self.multipliers!r}")
+        set_("multipliers", mul)
+        set_("matrix", _matrix(self.matrix, "XTransProfile"))
+
+    def to_c(self, half_size: bool = False) -> _lib.XTransProfile:
+        p = _lib.XTransProfile(reduced=int(bool(half_size)))
+        p.pattern[:] = ["RGB".index(c) for row in self.pattern for c in row]
+        p.black[:] = self.black
+        p.mul[:] = self.multipliers
+        p.matrix[:] = [v for row in self.matrix for v in row]
+        return p
+
+    def plan(self, H: int, W: int, half_size: bool = False) -> _lib.XTransParams:
+        """The r2f_xtrans_params of an H x W mosaic (no GPU); ValueError for what the planner refuses (a frame below 6 x 6, a
+        pattern that is not admissible -- for the reduced size, with half_size --, a multiplier that rounds to 0 as a float)."""
+        out = _lib.XTransParams()
+        profile = self.to_c(half_size)
+        if _lib.load().r2f_xtrans_plan(C.byref(profile), int(H), int(W), C.byref(out)) != _lib.OK:
+            raise ValueError(f"r2f_xtrans_plan refused {self!r} for a {H} x {W} mosaic (half_size={bool(half_size)})")
         return out
