@@ -567,7 +567,7 @@ __device__ __forceinline__ void fft_cols_body(const FftConvArgs& a, const int mo
             for (int q = 0; q < 16; ++q) kr[q] = (R2F_FFT_EXP2 & 4) ? 0.5 + 0.25 * q : rat(kf, sidx(l + 16 * q, k, NBX));
         }
 #pragma unroll
-        for (int q = 0; q < 16; ++q) v[q] = make_double2(v[q].x * kr[q], v[q].y * kr[q]);
+        for (int q = 0; q < 16; ++q) v[q] = cscale(v[q], kr[q]);
     } else {
 #pragma unroll
         for (int q = 0; q < 16; ++q) v[q] = cmul(v[q], (R2F_FFT_EXP2 & 4) ? make_double2(0.5, 0.25 * q) : at(kf, sidx(l + 16 * q, k, NBX)));
@@ -617,7 +617,7 @@ __device__ __forceinline__ void fft_cols_y512_body(const FftConvArgs& a, const i
 #pragma unroll
         for (int q = 0; q < 16; ++q) kr[q] = rat(kf, sidx(f0 + 16 * q, k, NBX));
 #pragma unroll
-        for (int q = 0; q < 16; ++q) v[q] = make_double2(v[q].x * kr[q], v[q].y * kr[q]);
+        for (int q = 0; q < 16; ++q) v[q] = cscale(v[q], kr[q]);
     } else {
 #pragma unroll
         for (int q = 0; q < 16; ++q) v[q] = cmul(v[q], at(kf, sidx(f0 + 16 * q, k, NBX)));
@@ -696,7 +696,7 @@ __device__ __forceinline__ void fft_cols_walk_body(const FftConvArgs& a, double*
         }
         fft256<false>(v, w, tbuf, lane);
 #pragma unroll
-        for (int q = 0; q < 16; ++q) v[q] = make_double2(v[q].x * kr[q], v[q].y * kr[q]);
+        for (int q = 0; q < 16; ++q) v[q] = cscale(v[q], kr[q]);
         asm volatile("" : "+v"(w.x), "+v"(w.y));
         fft256<true>(v, w, tbuf, lane);
         if (ST == 3) {

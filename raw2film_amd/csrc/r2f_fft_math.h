@@ -10,9 +10,22 @@ typedef double2 cplx;
 
 __device__ __forceinline__ cplx cadd(cplx a, cplx b) { return make_double2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ cplx csub(cplx a, cplx b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ cplx cmul(cplx a, cplx b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+// The complex products state their own fusion: one rounded product and one fma per component, and nothing left for the compiler to
+// contract.  Left free, it fused the same source differently from kernel to kernel (the one-shot column pass and the column walk
+// came out with five fusions apart), and their results then differed in the last bits of a double -- visible in the float32 output
+// wherever the exact result is 0 (taps of both signs on integer samples: tests/test_gpu_exact_taps.py).
+__device__ __forceinline__ cplx cmul(cplx a, cplx b) {
+#pragma clang fp contract(off)
+    return make_double2(__builtin_fma(a.x, b.x, -(a.y * b.y)), __builtin_fma(a.x, b.y, a.y * b.x));
+}
 __device__ __forceinline__ cplx cmulc(cplx a, cplx b) {  // a * conj(b)
-    return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y);
+#pragma clang fp contract(off)
+    return make_double2(__builtin_fma(a.x, b.x, a.y * b.y), __builtin_fma(a.y, b.x, -(a.x * b.y)));
+}
+// A spectrum element times a real value (the real kernel spectrum of centred symmetric taps), each product rounded on its own.
+__device__ __forceinline__ cplx cscale(cplx a, double k) {
+#pragma clang fp contract(off)
+    return make_double2(a.x * k, a.y * k);
 }
 template <bool INV>
 __device__ __forceinline__ cplx ctw(cplx a, cplx w) {  // a * w (forward) or a * conj(w) (inverse)

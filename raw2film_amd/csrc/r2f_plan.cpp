@@ -241,14 +241,28 @@ bool separable_taps(const Taps& t, int R, float u[3][19], float v[3][10]) {
 }
 
 void stencil_source_rows(int y0, int y1, int above, int below, int H, int* lo_out, int* hi_out) {
-    int lo = y0 - above, hi = y1 - 1 + below;  // inclusive
-    int need_lo = std::max(lo, 0), need_hi = std::min(hi, H - 1);
-    if (H > 1) {
-        if (lo < 0) need_hi = std::max(need_hi, std::min(-lo, H - 1));
-        if (hi > H - 1) need_lo = std::min(need_lo, std::max(2 * (H - 1) - hi, 0));
+    // The rows y + d, y in [y0, y1), d in [-above, below], are the interval [lo, hi] (above + below = taps - 1 >= 0).  A tap box
+    // that does not hold the anchor row makes `above` or `below` negative: the interval then lies beside the output rows, or
+    // wholly outside the frame, and comes back reflected.  reflect-101 has period 2 (H - 1), is 0 at its multiples and H - 1 half
+    // a period further, and is monotone in between: the interval's image is [0 or the smaller end, H - 1 or the larger end].
+    if (H <= 1) {
+        *lo_out = 0, *hi_out = 1;
+        return;
     }
-    *lo_out = need_lo;
-    *hi_out = need_hi + 1;
+    const long long P = 2LL * (H - 1), lo = (long long)y0 - above, hi = (long long)y1 - 1 + below;
+    auto reflect = [&](long long i) {
+        i %= P;
+        if (i < 0) i += P;
+        return (int)(i < H ? i : P - i);
+    };
+    auto next_at = [&](long long from, long long phase) {  // the smallest phase + k P >= from
+        long long k = (from - phase) / P;
+        if (phase + k * P < from) ++k;
+        return phase + k * P;
+    };
+    const int a = reflect(lo), b = reflect(hi);
+    *lo_out = next_at(lo, 0) <= hi ? 0 : std::min(a, b);
+    *hi_out = (next_at(lo, H - 1) <= hi ? H - 1 : std::max(a, b)) + 1;
 }
 
 // ------------------------------------------------------------------------------------------------ FFT form
@@ -581,7 +595,9 @@ bool store_option(Options* o, const OptionRow& row, int value) {
 namespace {
 
 // Does the entry list reproduce the taps it was built from?  Every non-zero tap of the cropped box exactly once per output row of
-// a lane (the centre column of a mirrored list at half weight), every LDS offset inside its phase's rows.
+// a lane (the centre column of a mirrored list at half weight), every LDS offset inside its phase's rows, and the live-column
+// masks of every row step's first and last entry (the mirrored form skips the tap columns whose bit is clear) recomputed from
+// the taps, with their unions.
 #ifdef R2F_PLAN_DEBUG
 static bool fail_at(int n) { fprintf(stderr, "stream_consistent: check %d failed\n", n); return false; }
 #else
@@ -598,6 +614,15 @@ bool stream_consistent(const r2f::plan::Taps& t, int c, const int box[4], const 
     // (a tap K[i][j] is used once per output row q of a lane: in row step m = i + q)
     std::vector<float> seen((size_t)g.kh * g.kw * Q, 0.f);
     std::vector<char> hit((size_t)g.kh * g.kw * Q, 0);
+    // the weight the list must hold for tap (i, j) of the virtual (padded) stencil
+    auto want_at = [&](int i, int j) -> float {
+        const int bj = j - pad;
+        if (i < 0 || i >= g.kh || j < 0 || j >= g.kw) return 0.f;
+        const float v = (bj >= 0 && bj < bw) ? t.at(box[0] + i, box[2] + bj, c) : 0.f;
+        if (!g.sym) return v;
+        return j > r ? 0.f : (j == r ? 0.5f * v : v);
+    };
+    int first_or = 0, last_or = 0;
     if ((int)sh.phases.size() != 4 * (sh.n_phases + 1) || (int)sh.rowinfo.size() != 4 * (sh.n_rowsteps + 2)) return fail_at(2);
     if ((int)sh.w.size() != 4 * Q * (sh.n_entries + 2)) return fail_at(3);
     int entry = 0, rowstep = 0;
@@ -619,6 +644,18 @@ bool stream_consistent(const r2f::plan::Taps& t, int c, const int box[4], const 
             if (4 * (c_lo + n) > (g.sym ? (r + 1 + 3) / 4 * 4 : g.kw_pad)) return fail_at(9);
             // the mirrored 8-float block of entry e starts at 2 r - 4 (c_lo + e) - 4 >= 0
             if (g.sym && (offr != mrel * g.RS + 2 * r - 4 * c_lo - 4 || 2 * r - 4 * (c_lo + n - 1) - 4 < 0)) return fail_at(10);
+            // live tap columns of the first and of the last entry: bit t set when some row m - q has a non-zero tap in column 4 c + t
+            auto live = [&](int chunk) {
+                int bits = 0;
+                for (int tt = 0; tt < 4; ++tt)
+                    for (int q = 0; q < Q; ++q)
+                        if (want_at(m - q, 4 * chunk + tt) != 0.f) bits |= 1 << tt;
+                return bits;
+            };
+            const int first = live(c_lo), last = live(c_lo + n - 1);
+            if (first == 0 || last == 0) return fail_at(15);  // a row step begins and ends on a chunk that holds a tap
+            if (sh.rowinfo[4 * rowstep + 3] != (first | last << 4)) return fail_at(16);
+            first_or |= first, last_or |= last;
             for (int e = 0; e < n; ++e, ++entry)
                 for (int tt = 0; tt < 4; ++tt)
                     for (int q = 0; q < Q; ++q) {
@@ -633,11 +670,10 @@ bool stream_consistent(const r2f::plan::Taps& t, int c, const int box[4], const 
         }
     }
     if (entry != sh.n_entries || rowstep != sh.n_rowsteps) return fail_at(13);
+    if (first_or != sh.mask_first_or || last_or != sh.mask_last_or || first_or != g.mask_first_or || last_or != g.mask_last_or) return fail_at(17);
     for (int i = 0; i < g.kh; ++i)
         for (int j = 0; j < g.kw; ++j) {
-            const int bj = j - pad;
-            float want = (bj >= 0 && bj < bw) ? t.at(box[0] + i, box[2] + bj, c) : 0.f;
-            if (g.sym) want = j > r ? 0.f : (j == r ? 0.5f * want : want);
+            const float want = want_at(i, j);
             for (int q = 0; q < Q; ++q) {
                 const float got = seen[((size_t)i * g.kw + j) * Q + q];
                 if (memcmp(&want, &got, sizeof want) && !(want == 0.f && got == 0.f)) return fail_at(14);

@@ -54,7 +54,8 @@ std::vector<float> fixed_stencil_weights(const Taps& t, int R, int Q, bool* same
 // Is every channel's (2 R + 1)^2 box K = u v^T to 6e-7 of its largest tap?  Fills u[c][0 .. 2 R], v[c][0 .. R] (left half).
 bool separable_taps(const Taps& t, int R, float u[3][19], float v[3][10]);
 
-// Source rows [lo, hi) a stencil reaching `above` / `below` rows needs for outputs [y0, y1) of an H-row frame (reflect-101).
+// Source rows [lo, hi) a stencil reaching `above` / `below` rows needs for outputs [y0, y1) of an H-row frame (reflect-101): exactly
+// the hull of the rows read.  above + below >= 0; either may be negative (a tap box that does not hold the anchor row).
 void stencil_source_rows(int y0, int y1, int above, int below, int H, int* lo, int* hi);
 
 // ------------------------------------------------------------------------------------------------ FFT form

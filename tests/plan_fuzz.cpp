@@ -1,9 +1,14 @@
 // plan_fuzz.cpp -- fuzz harness for the host-side planners of libr2f_hip.so (raw2film_amd/csrc/r2f_plan.cpp), built by
 // tests/test_plan_sanitizers.py with `g++ -fsanitize=address,undefined -fno-sanitize-recover=all` and run as a child process:
 // the sanitizers abort on the first out-of-bounds access, overflow or invalid cast; the checks below abort on a plan that breaks
-// its own contract.  Test infrastructure: nothing in the product links this file.
+// its own contract (for an entry list: stream_consistent in r2f_plan.cpp -- every tap once per output row, the LDS offsets, and the
+// live-column masks of every row step's first and last entry recomputed from the taps).  The random stencils include the sparsity
+// of tests/exact_taps.py's families (ragged rows, runs of zero rows and columns, isolated taps, tap boxes beside the anchor), and
+// stencil_source_rows is held to the brute-force hull of the rows read, with a negative reach above or below.
+// Test infrastructure: nothing in the product links this file.
 //
 //   plan_fuzz <seed> <cases>
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -89,6 +94,33 @@ static void fuzz_fft() {
     if (bw > 200) CHECK(p.nx >= 512, "wide box in %d columns", p.nx);
 }
 
+// stencil_source_rows against brute force.  `above` / `below` as run_stencil derives them from a tap box and the anchor: they sum
+// to the box's height - 1 >= 0, and one of them is negative when the box does not hold the anchor row (a pure translation).  The
+// rows reflect-101 visits must lie inside [lo, hi) and touch both ends: a row more would refuse a caller's exact window.
+static int reflect101_host(long long i, int n) {
+    if (n == 1) return 0;
+    const long long p = 2LL * n - 2;
+    i %= p;
+    if (i < 0) i += p;
+    return (int)(i < n ? i : p - i);
+}
+static void check_source_rows() {
+    const int H = rnd() % 3 ? rint_in(1, 40) : frame_dim(), y0 = rint_in(0, H - 1), y1 = rnd() % 4 ? std::min(H, y0 + rint_in(1, 70)) : rint_in(y0 + 1, H);
+    const int taps = rnd() % 3 ? rint_in(1, 90) : rint_in(1, 400);
+    const int above = rnd() % 2 ? rint_in(0, taps - 1) : rint_in(-250, 250), below = taps - 1 - above;
+    int lo = -1, hi = -1;
+    stencil_source_rows(y0, y1, above, below, H, &lo, &hi);
+    CHECK(lo >= 0 && hi <= H && lo < hi, "source rows [%d, %d) for [%d, %d) of %d, above %d below %d", lo, hi, y0, y1, H, above, below);
+    if (above >= 0 && below >= 0) CHECK(lo <= y0 && hi >= y1, "source rows [%d, %d) do not hold [%d, %d)", lo, hi, y0, y1);
+    int seen_lo = H, seen_hi = -1;
+    for (long long i = (long long)y0 - above; i <= (long long)y1 - 1 + below; ++i) {
+        const int s = reflect101_host(i, H);
+        seen_lo = std::min(seen_lo, s), seen_hi = std::max(seen_hi, s);
+    }
+    CHECK(seen_lo == lo && seen_hi + 1 == hi, "source rows [%d, %d), visited [%d, %d]: outputs [%d, %d) of %d, above %d below %d", lo, hi, seen_lo,
+          seen_hi, y0, y1, H, above, below);
+}
+
 static void fuzz_stencil() {
     // a random stencil: dense, sparse, disc-like, mirror symmetric or not, with zero borders (cropping) and zero planes
     int kh = rnd() % 4 ? rint_in(1, 40) : tap_dim(), kw = rnd() % 4 ? rint_in(1, 40) : tap_dim();
@@ -108,6 +140,42 @@ static void fuzz_stencil() {
                 }
                 k[((size_t)i * kw + j) * kc + c] = v;
             }
+    // the sparsity no dense box or disc has (tests/exact_taps.py's families): every row with a first and last column of its own, runs
+    // of 1 .. 5 all-zero rows and all-zero columns inside the box, a few isolated taps in an empty box, a tap box beside the anchor
+    const int sparse = rnd() % 8;
+    for (int c = 0; c < kc && sparse < 4; ++c) {
+        auto at = [&](int i, int j) -> float& { return k[((size_t)i * kw + j) * kc + c]; };
+        if (sparse == 0) {  // ragged rows; some collapse to one chunk or one tap
+            for (int i = 0; i < kh; ++i) {
+                int f = rint_in(0, kw - 1), l = rint_in(0, kw - 1);
+                if (f > l) std::swap(f, l);
+                if (rnd() % 6 == 0) l = std::min(l, f + (int)(rnd() % 4));
+                for (int j = 0; j < kw; ++j)
+                    if (j < f || j > l) at(i, j) = 0.f;
+                if (rnd() % 2) at(i, f) = at(i, l) = 0.25f;
+            }
+        } else if (sparse == 1) {  // zero rows in runs, zero columns
+            for (int i = rint_in(0, 3), run = 1; i < kh; i += run + rint_in(1, 3), run = run % 5 + 1)
+                for (int z = i; z < std::min(kh, i + run); ++z)
+                    for (int j = 0; j < kw; ++j) at(z, j) = 0.f;
+            for (int j = rint_in(0, 4); j < kw; j += rint_in(1, 9)) {
+                const int run = rnd() % 3 ? 1 : 4;
+                for (int z = j; z < std::min(kw, j + run); ++z)
+                    for (int i = 0; i < kh; ++i) at(i, z) = 0.f;
+            }
+        } else {  // isolated taps: the corners and the centre of a box (2), or a small cluster anywhere -- beside the anchor as a rule (3)
+            for (int i = 0; i < kh; ++i)
+                for (int j = 0; j < kw; ++j) at(i, j) = 0.f;
+            if (sparse == 2) {
+                at(0, 0) = at(0, kw - 1) = at(kh - 1, 0) = at(kh - 1, kw - 1) = 0.125f, at(kh / 2, kw / 2) = 0.5f;
+                for (int n = 0; n < 10; ++n) at(rint_in(0, kh - 1), rint_in(0, kw - 1)) = rfloat() - 0.5f;
+            } else {
+                const int i0 = rint_in(0, kh - 1), j0 = rint_in(0, kw - 1), ch = rint_in(1, 3), cw = rint_in(1, 5);
+                for (int i = i0; i < std::min(kh, i0 + ch); ++i)
+                    for (int j = j0; j < std::min(kw, j0 + cw); ++j) at(i, j) = 0.5f - rfloat();
+            }
+        }
+    }
     if (mode != 3 && rnd() % 2)  // mirror the left half onto the right one, bit for bit
         for (int c = 0; c < kc; ++c)
             for (int i = 0; i < kh; ++i)
@@ -155,10 +223,7 @@ static void fuzz_stencil() {
         float u[3][19], v[3][10];
         if (R <= 9) (void)separable_taps(t, R, u, v);
     }
-    int lo, hi;
-    const int H = frame_dim(), y0 = rint_in(0, H - 1), y1 = rint_in(y0 + 1, H);
-    stencil_source_rows(y0, y1, rint_in(0, 250), rint_in(0, 250), H, &lo, &hi);
-    CHECK(lo >= 0 && hi <= H && lo < hi && lo <= y0 && hi >= y1, "source rows [%d, %d) for [%d, %d) of %d", lo, hi, y0, y1, H);
+    check_source_rows();
 }
 
 static void fuzz_tables() {

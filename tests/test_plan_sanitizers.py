@@ -7,7 +7,9 @@ library that can run under one: the same translation unit the library links is c
 of the FFT options, and checks each plan against its own contract (windows cover the rows and columns, batches cover the pairs,
 an entry list reproduces the taps it was built from -- every tap once per output row -- inside the LDS rows of its phase, a
 tile order is a permutation ...).  Round 4: 229 000 cases over 13 seeds, nothing found (the round-2 division by zero in the
-window choice is the kind of bug this is for)."""
+window choice is the kind of bug this is for).  The entry-list check covers the live-column masks of each row step's first and last
+entry, the stencils include ragged, gapped, isolated and shifted taps (tests/exact_taps.py's kind), and the source-row rule is held to
+the brute-force hull for tap boxes that do not hold the anchor row (a negative reach): there it used to name rows nobody reads."""
 
 import ctypes
 import os
