@@ -14,6 +14,9 @@ import numpy as np
 from . import _lib
 
 LOG_EPS = 1e-6  # lut_1d.wgsl:24
+# params type -> (the HipContext method that demosaics a mosaic of it to the uint16 frame, the smallest side of such a mosaic): the one
+# place that says which demosaic a params type selects
+MOSAIC_KINDS = {_lib.DemosaicParams: ("demosaic_u16", 2), _lib.XTransParams: ("demosaic_xtrans", 6)}
 LUT3D_SCALE = 0.25  # cpu_processor.py:405
 
 
@@ -558,15 +561,38 @@ class HipContext:
                                                self._stream()))
         return out
 
-    def _check_mosaic(self, mosaic, params, what):
-        """demosaic_u16's and demosaic_f32's view of their source -> (H, W, the r2f_demosaic_params)."""
+    def _check_mosaic(self, mosaic, params, what, params_type):
+        """A demosaic's view of its source -> (H, W, the params of `params_type`, planned from a profile where it was given one)."""
         torch = self._torch
+        m = MOSAIC_KINDS[params_type][1]
         if not (isinstance(mosaic, torch.Tensor) and mosaic.is_cuda and mosaic.dtype in (torch.uint16, torch.int16) and mosaic.dim() == 2
-                and mosaic.shape[0] >= 2 and mosaic.shape[1] >= 2 and mosaic.stride(1) == 1 and mosaic.stride(0) >= mosaic.shape[1]):
-            raise ValueError(f"{what} needs a uint16 (H, W) CUDA mosaic of at least 2 x 2 samples with contiguous rows")
+                and mosaic.shape[0] >= m and mosaic.shape[1] >= m and mosaic.stride(1) == 1 and mosaic.stride(0) >= mosaic.shape[1]):
+            raise ValueError(f"{what} needs a uint16 (H, W) CUDA mosaic of at least {m} x {m} samples with contiguous rows")
         self._same_device(mosaic, "mosaic")
         H, W = int(mosaic.shape[0]), int(mosaic.shape[1])
-        return H, W, params if isinstance(params, _lib.DemosaicParams) else params.plan(H, W)
+        return H, W, params if isinstance(params, params_type) else params.plan(H, W)
+
+    def _demosaic(self, what, fn, params_type, mosaic, params, out, rows, window=None, decode=None):
+        """The three demosaic methods: the mosaic check, the planning of a profile, the window, the `out` check, `rows`, the call.
+        fn: the C entry point; decode = (divisor, factor): the float32 epilogue, which also takes a window (default: the frame)."""
+        torch = self._torch
+        H, W, params = self._check_mosaic(mosaic, params, what, params_type)
+        r0, c0, nr, nc = (0, 0, int(params.out_h), int(params.out_w)) if window is None else (int(v) for v in window)
+        if not (0 <= r0 and 0 <= c0 and nr > 0 and nc > 0 and r0 + nr <= params.out_h and c0 + nc <= params.out_w):
+            raise ValueError(f"{what}: window {(r0, c0, nr, nc)} is not inside the {params.out_h} x {params.out_w} frame")
+        shape = (nr, nc, 3)
+        dtypes, name = ((torch.float32,), "float32") if decode else ((torch.uint16, torch.int16), "uint16")
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32 if decode else mosaic.dtype, device=self.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype in dtypes and out.is_contiguous() and tuple(out.shape) == shape):
+            raise ValueError(f"{what}: out must be a contiguous {name} CUDA tensor of shape {shape}")
+        else:
+            self._same_device(out, "out")
+        y0, y1 = (0, nr) if rows is None else (int(rows[0]), int(rows[1]))
+        epilogue = (r0, c0, nr, nc, *decode) if decode else ()
+        self._check(fn(self._h, mosaic.data_ptr(), 0, H, int(mosaic.stride(0)), H, W, C.byref(params), *epilogue, out.data_ptr(), y0, y1,
+                       self._stream()))
+        return out
 
     def demosaic_u16(self, mosaic, params, out=None, rows=None):
         """The Bayer demosaic of include/r2f.h (r2f_demosaic_u16: black / scale, PPG or the half-size form, camera matrix, clip)
@@ -574,20 +600,7 @@ class HipContext:
         = 1) -> uint16 (out_h, out_w, 3), the frame decode_u16 / decode_u16_auto / exposure_rows take.
         params: a raw2film_amd.raw.RawProfile (planned full size for this mosaic) or the r2f_demosaic_params of its size.
         rows = (y0, y1): only those output rows of `out` are written (default: all)."""
-        torch = self._torch
-        H, W, params = self._check_mosaic(mosaic, params, "demosaic_u16")
-        shape = (int(params.out_h), int(params.out_w), 3)
-        if out is None:
-            out = torch.empty(shape, dtype=mosaic.dtype, device=self.device)
-        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype in (torch.uint16, torch.int16) and out.is_contiguous()
-                  and tuple(out.shape) == shape):
-            raise ValueError(f"demosaic_u16: out must be a contiguous uint16 CUDA tensor of shape {shape}")
-        else:
-            self._same_device(out, "out")
-        y0, y1 = (0, shape[0]) if rows is None else (int(rows[0]), int(rows[1]))
-        self._check(self._lib.r2f_demosaic_u16(self._h, mosaic.data_ptr(), 0, H, int(mosaic.stride(0)), H, W, C.byref(params),
-                                               out.data_ptr(), y0, y1, self._stream()))
-        return out
+        return self._demosaic("demosaic_u16", self._lib.r2f_demosaic_u16, _lib.DemosaicParams, mosaic, params, out, rows)
 
     def demosaic_xtrans(self, mosaic, params, out=None, rows=None):
         """The X-Trans demosaic of include/r2f.h (r2f_demosaic_xtrans_u16: black / scale, the project's own directional-green /
@@ -596,50 +609,15 @@ class HipContext:
         (out_h, out_w, 3), the frame decode_u16 / decode_u16_auto / exposure_rows take.
         params: a raw2film_amd.raw.XTransProfile (planned full size for this mosaic) or the r2f_xtrans_params of its size.
         rows = (y0, y1): only those output rows of `out` are written (default: all)."""
-        torch = self._torch
-        if not (isinstance(mosaic, torch.Tensor) and mosaic.is_cuda and mosaic.dtype in (torch.uint16, torch.int16) and mosaic.dim() == 2
-                and mosaic.shape[0] >= 6 and mosaic.shape[1] >= 6 and mosaic.stride(1) == 1 and mosaic.stride(0) >= mosaic.shape[1]):
-            raise ValueError("demosaic_xtrans needs a uint16 (H, W) CUDA mosaic of at least 6 x 6 samples with contiguous rows")
-        self._same_device(mosaic, "mosaic")
-        H, W = int(mosaic.shape[0]), int(mosaic.shape[1])
-        if not isinstance(params, _lib.XTransParams):
-            params = params.plan(H, W)
-        shape = (int(params.out_h), int(params.out_w), 3)
-        if out is None:
-            out = torch.empty(shape, dtype=mosaic.dtype, device=self.device)
-        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype in (torch.uint16, torch.int16) and out.is_contiguous()
-                  and tuple(out.shape) == shape):
-            raise ValueError(f"demosaic_xtrans: out must be a contiguous uint16 CUDA tensor of shape {shape}")
-        else:
-            self._same_device(out, "out")
-        y0, y1 = (0, shape[0]) if rows is None else (int(rows[0]), int(rows[1]))
-        self._check(self._lib.r2f_demosaic_xtrans_u16(self._h, mosaic.data_ptr(), 0, H, int(mosaic.stride(0)), H, W, C.byref(params),
-                                                      out.data_ptr(), y0, y1, self._stream()))
-        return out
+        return self._demosaic("demosaic_xtrans", self._lib.r2f_demosaic_xtrans_u16, _lib.XTransParams, mosaic, params, out, rows)
 
     def demosaic_f32(self, mosaic, params, factor: float, divisor: float = 65535.0, window=None, out=None, rows=None):
         """demosaic_u16 and decode_u16 in one kernel (r2f_demosaic_f32): window = (row0, col0, rows, cols) of the demosaiced frame
         (default: all of it) -> float32 (rows, cols, 3), bit-identical to decode_u16(demosaic_u16(mosaic)[window], factor, divisor).
         mosaic, params: demosaic_u16's; the mosaic may be the whole landing buffer of which only some rows have arrived -- a call
         reads the rows its contract names and no others.  rows = (y0, y1): only those rows of the window are written."""
-        torch = self._torch
-        H, W, params = self._check_mosaic(mosaic, params, "demosaic_f32")
-        r0, c0, nr, nc = (0, 0, int(params.out_h), int(params.out_w)) if window is None else (int(v) for v in window)
-        if not (0 <= r0 and 0 <= c0 and nr > 0 and nc > 0 and r0 + nr <= params.out_h and c0 + nc <= params.out_w):
-            raise ValueError(f"demosaic_f32: window {(r0, c0, nr, nc)} is not inside the {params.out_h} x {params.out_w} frame")
-        shape = (nr, nc, 3)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
-                  and tuple(out.shape) == shape):
-            raise ValueError(f"demosaic_f32: out must be a contiguous float32 CUDA tensor of shape {shape}")
-        else:
-            self._same_device(out, "out")
-        y0, y1 = (0, nr) if rows is None else (int(rows[0]), int(rows[1]))
-        self._check(self._lib.r2f_demosaic_f32(self._h, mosaic.data_ptr(), 0, H, int(mosaic.stride(0)), H, W, C.byref(params), r0, c0, nr,
-                                               nc, float(np.float32(divisor)), float(np.float32(factor)), out.data_ptr(), y0, y1,
-                                               self._stream()))
-        return out
+        return self._demosaic("demosaic_f32", self._lib.r2f_demosaic_f32, _lib.DemosaicParams, mosaic, params, out, rows, window,
+                              (float(np.float32(divisor)), float(np.float32(factor))))
 
     def decode_u16(self, image_u16, factor: float, divisor: float = 65535.0, out=None):
         """raw_to_linear's last two lines (raw_conversion.py:50-52) on the device: float32(u) / divisor * float32(factor) for a

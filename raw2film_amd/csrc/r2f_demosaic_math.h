@@ -1,41 +1,24 @@
 // r2f_demosaic_math.h -- the per-pixel arithmetic of the Bayer demosaic (include/r2f.h, r2f_demosaic_u16), as text the device
 // kernels (r2f_demosaic.hip) and a CPU program (tests/demosaic_check.cpp, g++ -ffp-contract=off) both compile: step A (black /
-// scale), B0 (border ring), B1 (green), B2 / B3 (red and blue), B' (half size) and C (colour matrix, clip).  Everything is integer
-// arithmetic except the one fp32 multiply of step A and the five fp32 operations per channel of step C, for which contraction is
-// off.  Samples come through accessors: `S(y, x)` the scaled mosaic, `G(y, x)` the finished green plane, both at frame coordinates
-// inside the frame.  No HIP types, no includes beyond <math.h>.
+// scale), B0 (border ring), B1 (green), B2 / B3 (red and blue) and B' (half size); step C (colour matrix, clip) is r2f_mosaic_math.h's,
+// shared with the X-Trans pattern.  Everything is integer arithmetic except the one fp32 multiply of step A (and the five fp32
+// operations per channel of step C), for which contraction is off.  Samples come through accessors: `S(y, x)` the scaled mosaic,
+// `G(y, x)` the finished green plane, both at frame coordinates inside the frame.  No HIP types.
 #pragma once
 
-#include <math.h>
-
 #include "../../include/r2f.h"
-
-#if defined(__HIPCC__)
-#define R2F_HD __host__ __device__ __forceinline__
-#else
-#define R2F_HD inline
-#endif
-#if defined(__clang__)
-#define R2F_NO_CONTRACT _Pragma("clang fp contract(off)")
-#define R2F_UNROLL _Pragma("unroll")  // (a loop over a small register array: unrolled, its indices are constants)
-#else
-#define R2F_NO_CONTRACT  // (g++: the translation unit is compiled with -ffp-contract=off)
-#define R2F_UNROLL _Pragma("GCC unroll 4")
-#endif
+#include "r2f_mosaic_math.h"
 
 namespace r2f {
 namespace demosaic {
 
-constexpr int kRed = 0, kGreen = 1, kBlue = 2;
+using namespace mosaic;  // the macro set, kRed / kGreen / kBlue, clip16, iabs, in_ring and step C (colour)
 
-R2F_HD int clip16(int v) { return v < 0 ? 0 : (v > 65535 ? 65535 : v); }
-R2F_HD int iabs(int v) { return v < 0 ? -v : v; }
 R2F_HD int site(int y, int x) { return (y & 1) * 2 + (x & 1); }
 // (selects, not an indexed load: the params sit in registers on the device, and a register array indexed by a variable goes to scratch)
 template <typename T>
 R2F_HD T pick4(const T (&v)[4], int k) { return k == 0 ? v[0] : (k == 1 ? v[1] : (k == 2 ? v[2] : v[3])); }
 R2F_HD int colour_of(const r2f_demosaic_params& p, int y, int x) { return pick4(p.cfa, site(y, x)); }
-R2F_HD bool in_ring(int H, int W, int y, int x, int width) { return y < width || y >= H - width || x < width || x >= W - width; }
 
 // A: one raw sample of site k.  |t * mul| <= 65535 * 1024: the truncation stays inside int.
 R2F_HD int scale_sample(const r2f_demosaic_params& p, int raw, int k) {
@@ -124,20 +107,8 @@ R2F_HD void half_rgb(const r2f_demosaic_params& p, const int (&q)[4], int (&rgb)
     rgb[kRed] = r, rgb[kGreen] = g >> 1, rgb[kBlue] = b;
 }
 
-// C: the matrix and the clip.  |acc| <= 3 * 64 * 65535: the truncation stays inside int.
-R2F_HD void colour(const r2f_demosaic_params& p, const int (&rgb)[3], uint16_t (&out)[3]) {
-    R2F_NO_CONTRACT
-    const float r = (float)rgb[0], g = (float)rgb[1], b = (float)rgb[2];
-    R2F_UNROLL
-    for (int k = 0; k < 3; ++k) {
-        float acc = r * p.M[3 * k];
-        const float t1 = g * p.M[3 * k + 1];
-        acc = acc + t1;
-        const float t2 = b * p.M[3 * k + 2];
-        acc = acc + t2;
-        out[k] = (uint16_t)clip16((int)acc);
-    }
-}
+// C with the pattern's params: mosaic::colour (r2f_mosaic_math.h) on their matrix.
+R2F_HD void colour(const r2f_demosaic_params& p, const int (&rgb)[3], uint16_t (&out)[3]) { mosaic::colour(p.M, rgb, out); }
 
 }  // namespace demosaic
 }  // namespace r2f

@@ -1,8 +1,7 @@
 // r2f_demosaic_plan.cpp -- host planner of the Bayer demosaic (include/r2f.h: r2f_demosaic_plan).  No HIP in this file: hipcc
 // compiles it into the library, g++ -fsanitize=address,undefined,float-cast-overflow into tests/demosaic_check.cpp's program.
-#include <cmath>
-
 #include "../../include/r2f.h"
+#include "r2f_mosaic_plan.h"
 
 namespace {
 
@@ -24,22 +23,10 @@ int r2f_demosaic_plan(const r2f_raw_profile* p, int H, int W, r2f_demosaic_param
     const bool half = p->half_size != 0;
     if (half && ((H | W) & 1)) return R2F_EINVAL;
     r2f_demosaic_params r{};
-    for (int k = 0; k < 4; ++k) {
-        const double b = p->black[k], m = p->mul[k];
-        // (the comparisons are written so that a NaN fails them)
-        if (!(b >= 0.0 && b <= 65535.0) || b != std::floor(b)) return R2F_EINVAL;
-        if (!(m > 0.0 && m <= 1024.0)) return R2F_EINVAL;
-        const float mf = (float)m;
-        if (!(mf > 0.f && mf <= 1024.f)) return R2F_EINVAL;  // (a double below the smallest float rounds to 0)
-        r.cfa[k] = kCfa[p->pattern][k];
-        r.black[k] = (int32_t)b;
-        r.mul[k] = mf;
-    }
-    for (int i = 0; i < 9; ++i) {
-        const double v = p->matrix[i];
-        if (!(std::fabs(v) <= 64.0)) return R2F_EINVAL;
-        r.M[i] = (float)v;
-    }
+    if (!r2f::mosaic_plan::black_levels(p->black, r.black) || !r2f::mosaic_plan::multipliers(p->mul, r.mul) ||
+        !r2f::mosaic_plan::matrix(p->matrix, r.M))
+        return R2F_EINVAL;
+    for (int k = 0; k < 4; ++k) r.cfa[k] = kCfa[p->pattern][k];
     r.half_size = half ? 1 : 0;
     r.out_h = half ? H / 2 : H;
     r.out_w = half ? W / 2 : W;

@@ -1,0 +1,282 @@
+// r2f_mosaic_stage.h -- the staging of the two demosaics (r2f_demosaic.hip the Bayer pattern's, r2f_xtrans.hip the X-Trans one's):
+// which samples a block holds in LDS, how they are loaded and how the finished pixels leave; and the entry points' checks.  Device
+// text, included by those two files.  The arithmetic is not here: it is the pattern's (r2f_demosaic_math.h, r2f_xtrans_math.h) and
+// r2f_mosaic_math.h's.
+//   mosaic_full_kernel     one launch: scaled tile + apron in LDS (step A once per sample), the pattern's auxiliary plane of the tile +
+//                          1-sample apron in LDS, then the pattern's pixel_rgb and step C per output pixel; a wave's row leaves
+//                          through an LDS transpose as one contiguous segment
+//   mosaic_reduced_kernel  one lane per output pixel of the reduced form (a half or a third of the mosaic's sides)
+//   mosaic_rows            the checks every entry point makes, then one launch
+// Each is a template over a Pattern and over the epilogue: the uint16 frame, or a window of it decoded to the float frame the front
+// stage reads (decode_sample of r2f_device.h on each finished sample).  A Pattern states what differs and nothing else:
+//   Params, Aux                   its r2f_*_params and the auxiliary plane's element type (uint16_t green / int colour difference)
+//   kMinSide, kReduction          the smallest mosaic side, what the reduced form divides the sides by
+//   kReachY, kApronX              mosaic rows a full-size output row reads above and below it; staged columns each side of a tile
+//   kParamsInLds                  whether lanes index the params' tables (then a block keeps them in LDS, else they stay arguments)
+//   kPlanner                      the planner's name, for messages
+//   reduced(p)                    whether p asks for the reduced form
+//   check_params(ctx, what, p, H, W)     R2F_OK, or the refusal of params no planner made
+//   scale_pair(p, y, x, r0, r1, v0, v1)  step A of the raw samples (y, x) and (y, x + 1), x even, with the pattern's phase rule
+//   kAuxRing, aux_at(p, S, H, W, y, x)   the auxiliary plane at a frame site at least kAuxRing samples from every edge (0 is staged
+//                                 outside: nothing reads it there)
+//   pixel_rgb(p, S, A, H, W, y, x, rgb)  the three planes of an output pixel, before the matrix
+//   reduced_rgb(a, p, y, x, rgb)  those of a pixel of the reduced form, from the cell it loads itself
+// Nothing here runs inside r2f_render or a timed step.  The kernels have static LDS: they need no dynamic-LDS attribute and so no row
+// in r2f_kernels.hip's instantiation tables.
+#pragma once
+
+#include <cstdint>
+#include <type_traits>
+
+#include "r2f_ctx.h"
+#include "r2f_mosaic_math.h"
+
+namespace r2f {
+namespace {
+
+constexpr int kTW = 64, kTH = 32;  // the tile; lanes along x: a wave is one row of it
+constexpr int kRowsPerLane = kTH / 4;
+static_assert(R2F_DEMOSAIC_TILE_W == kTW && R2F_DEMOSAIC_TILE_H == kTH && R2F_XTRANS_TILE_W == kTW && R2F_XTRANS_TILE_H == kTH,
+              "include/r2f.h states the tile of either pattern");
+static_assert(kTW == 64 && kTH % 4 == 0, "a wave per tile row, workgroups of (64, 4)");
+
+template <typename Params>
+struct MosaicArgs {
+    const uint16_t* src;  // row src_gy0 of the mosaic
+    int src_gy0;
+    long long pitch;  // samples
+    int H, W;
+    Params p;
+    void* dst;   // row dst_y0, column x0 of the demosaiced frame D: rows of x1 - x0 pixels, uint16 or float
+    int y0, y1;  // the rows of D this call writes
+    int wide;    // 1: src is 4-byte aligned and the pitch even -> a pair of samples at an even x is one 32-bit load
+    int dst_y0, x0, x1;     // the window of D that dst holds (the uint16 entry points: all of it)
+    float divisor, factor;  // the float epilogue's
+};
+
+// The extents of what a block stages: the scaled samples, and the auxiliary plane with its 1-sample apron.
+template <typename Pattern>
+struct Staged {
+    static constexpr int kSW = kTW + 2 * Pattern::kApronX, kSH = kTH + 2 * Pattern::kReachY;
+    static constexpr int kAW = kTW + 2, kAH = kTH + 2;
+    // The tile origin is a multiple of 64 and the apron even, so load_pair's x is even.  For an even x, x + 1 >= 0 exactly when
+    // x >= 0: load_pair's `in1 = in0 && x + 1 < W` and the symmetric `x + 1 >= 0 && x + 1 < W` are the same predicate.
+    static_assert(kTW % 2 == 0 && Pattern::kApronX % 2 == 0 && kSW % 2 == 0, "the samples are loaded in pairs at even columns");
+    static_assert(Pattern::kApronX >= Pattern::kReachY, "the staged columns cover the reach");
+};
+
+// A pattern's params where its lanes read them: the kernel's arguments, or a block's copy of them in LDS.
+template <typename Pattern>
+__device__ __forceinline__ const typename Pattern::Params& params_of(const MosaicArgs<typename Pattern::Params>& a,
+                                                                     const typename Pattern::Params& s_p) {
+    if constexpr (Pattern::kParamsInLds)
+        return s_p;
+    else
+        return a.p;
+}
+template <typename Params>
+__device__ __forceinline__ void stage_params(const MosaicArgs<Params>& a, Params& s_p, int tid) {
+    static_assert(sizeof(Params) % 4 == 0 && alignof(Params) == 4, "copied to LDS in 32-bit words");
+    const uint32_t* from = reinterpret_cast<const uint32_t*>(&a.p);
+    uint32_t* to = reinterpret_cast<uint32_t*>(&s_p);
+    for (int i = tid; i < (int)(sizeof(Params) / 4); i += 256) to[i] = from[i];
+}
+
+// The samples (y, x) and (y, x + 1), x even, scaled (step A); 0 for one outside the frame's columns.  One 32-bit load where that is
+// allowed and both are inside, else one 16-bit load each: the same samples either way.  y is inside the frame.
+template <typename Pattern>
+__device__ __forceinline__ void load_pair(const MosaicArgs<typename Pattern::Params>& a, const typename Pattern::Params& p, int y, int x,
+                                          int& s0, int& s1) {
+    const bool in0 = x >= 0 && x < a.W, in1 = in0 && x + 1 < a.W;
+    unsigned r0 = 0, r1 = 0;
+    if (in0) {
+        const uint16_t* row = a.src + (long long)(y - a.src_gy0) * a.pitch;
+        if (in1 && a.wide) {
+            const uint32_t v = *reinterpret_cast<const uint32_t*>(row + x);
+            r0 = v & 0xFFFFu, r1 = v >> 16;
+        } else {
+            r0 = row[x];
+            if (in1) r1 = row[x + 1];
+        }
+    }
+    int v0, v1;
+    Pattern::scale_pair(p, y, x, (int)r0, (int)r1, v0, v1);
+    s0 = in0 ? v0 : 0, s1 = in1 ? v1 : 0;
+}
+
+template <typename T, int Pitch>
+struct Tile {  // a plane a block holds in LDS, at frame coordinates
+    const T* s;
+    int y_org, x_org;  // frame coordinates of s[0]
+    __device__ __forceinline__ int operator()(int y, int x) const { return s[(y - y_org) * Pitch + (x - x_org)]; }
+};
+
+// What leaves: the finished uint16 sample, or its decode to the float frame.
+template <bool F32>
+using OutT = std::conditional_t<F32, float, uint16_t>;
+template <bool F32, typename Params>
+__device__ __forceinline__ OutT<F32> finish_sample(const MosaicArgs<Params>& a, uint16_t v) {
+    if constexpr (F32)
+        return decode_sample(v, a.divisor, a.factor);
+    else
+        return v;
+}
+
+// n contiguous elements from LDS to `seg`, by the wave's 64 lanes, in stores as wide as seg's alignment allows: uint16 as 32-bit
+// words where the segment starts on one; float as 16-byte stores behind the up to three floats that lead to a 16-byte boundary.
+__device__ __forceinline__ void store_segment(uint16_t* seg, const uint16_t* s, int n, int tx) {
+    if ((reinterpret_cast<uintptr_t>(seg) & 3u) == 0) {
+        uint32_t* seg32 = reinterpret_cast<uint32_t*>(seg);
+        const uint32_t* out32 = reinterpret_cast<const uint32_t*>(s);
+        for (int j = tx; j < n / 2; j += 64) seg32[j] = out32[j];
+        if ((n & 1) && tx == 0) seg[n - 1] = s[n - 1];
+    } else {
+        for (int j = tx; j < n; j += 64) seg[j] = s[j];
+    }
+}
+__device__ __forceinline__ void store_segment(float* seg, const float* s, int n, int tx) {
+    int head = (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(seg) & 15u)) & 15u) >> 2;  // (seg is 4-byte aligned)
+    head = head < n ? head : n;
+    const int quads = (n - head) / 4;
+    if (tx < head) seg[tx] = s[tx];
+    float4* seg4 = reinterpret_cast<float4*>(seg + head);
+    for (int j = tx; j < quads; j += 64) {
+        const float* q = s + head + 4 * j;
+        seg4[j] = make_float4(q[0], q[1], q[2], q[3]);
+    }
+    for (int j = head + 4 * quads + tx; j < n; j += 64) seg[j] = s[j];
+}
+
+// The tile grid is anchored to the frame's columns (tile origins at multiples of 64, so that load_pair's x stays even whatever the
+// window's col0) and to the call's first row; lanes outside the window's columns compute nothing and store nothing.  Every phase is
+// taken from frame coordinates, never from the tile's.
+template <typename Pattern, bool F32>
+__global__ __launch_bounds__(256) void mosaic_full_kernel(const MosaicArgs<typename Pattern::Params> a) {
+    using St = Staged<Pattern>;
+    using Aux = typename Pattern::Aux;
+    constexpr int kReachY = Pattern::kReachY, kApronX = Pattern::kApronX, kSW = St::kSW, kSH = St::kSH, kAW = St::kAW, kAH = St::kAH;
+    __shared__ typename Pattern::Params s_p;  // (no use of it, and so no LDS, unless the pattern keeps its params there)
+    __shared__ __align__(16) uint16_t s_s[kSH * kSW];
+    __shared__ __align__(16) Aux s_a[kAH * kAW];
+    __shared__ __align__(16) OutT<F32> s_out[4][3 * kTW];
+    const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * 64 + tx;
+    const int tx0 = (a.x0 / kTW + (int)blockIdx.x) * kTW, ty0 = a.y0 + blockIdx.y * kTH;
+    if constexpr (Pattern::kParamsInLds) {
+        stage_params(a, s_p, tid);
+        __syncthreads();
+    }
+    const typename Pattern::Params& p = params_of<Pattern>(a, s_p);
+    // the rows this call may read (the entry point has checked that the source window holds them)
+    const int ry0 = a.y0 - kReachY > 0 ? a.y0 - kReachY : 0, ry1 = a.y1 + kReachY < a.H ? a.y1 + kReachY : a.H;
+
+    for (int i = tid; i < kSH * (kSW / 2); i += 256) {
+        const int r = i / (kSW / 2), c = 2 * (i % (kSW / 2));
+        const int y = ty0 - kReachY + r, x = tx0 - kApronX + c;  // (x is even: Staged)
+        int s0 = 0, s1 = 0;
+        if (y >= ry0 && y < ry1) load_pair<Pattern>(a, p, y, x, s0, s1);
+        s_s[r * kSW + c] = (uint16_t)s0, s_s[r * kSW + c + 1] = (uint16_t)s1;
+    }
+    __syncthreads();
+
+    const Tile<uint16_t, kSW> S{s_s, ty0 - kReachY, tx0 - kApronX};
+    // the auxiliary plane where this call's rows read it: rows [y0 - 1, y1 + 1) of the frame, inside the pattern's ring
+    constexpr int kRing = Pattern::kAuxRing;
+    const int ay0 = a.y0 - 1 > kRing ? a.y0 - 1 : kRing, ay1 = a.y1 + 1 < a.H - kRing ? a.y1 + 1 : a.H - kRing;
+    for (int i = tid; i < kAH * kAW; i += 256) {
+        const int r = i / kAW, c = i % kAW;
+        const int y = ty0 - 1 + r, x = tx0 - 1 + c;
+        int v = 0;
+        if (y >= ay0 && y < ay1 && x >= kRing && x < a.W - kRing) v = Pattern::aux_at(p, S, a.H, a.W, y, x);
+        s_a[i] = (Aux)v;
+    }
+    __syncthreads();
+
+    const Tile<Aux, kAW> A{s_a, ty0 - 1, tx0 - 1};
+    const int x = tx0 + tx;
+    // this tile's share of a row of the window: columns [xa, xb), n elements
+    const int xa = tx0 > a.x0 ? tx0 : a.x0, xb = tx0 + kTW < a.x1 ? tx0 + kTW : a.x1, n = 3 * (xb - xa);
+    // the wave's row segment, n contiguous elements of dst: that of its first row, then four rows on per step (one 64-bit product
+    // here, none per row)
+    const long long row_elems = 3LL * (a.x1 - a.x0);
+    OutT<F32>* seg = static_cast<OutT<F32>*>(a.dst) + (ty0 + ty - a.dst_y0) * row_elems + 3 * (xa - a.x0);
+    for (int q = 0; q < kRowsPerLane; ++q, seg += 4 * row_elems) {
+        const int y = ty0 + ty + 4 * q;  // (the same for all 64 lanes of a wave)
+        if (y < a.y1 && x >= xa && x < xb) {
+            int rgb[3];
+            uint16_t out[3];
+            Pattern::pixel_rgb(p, S, A, a.H, a.W, y, x, rgb);
+            mosaic::colour(p.M, rgb, out);
+            OutT<F32>* o = s_out[ty] + 3 * (x - xa);
+            o[0] = finish_sample<F32>(a, out[0]), o[1] = finish_sample<F32>(a, out[1]), o[2] = finish_sample<F32>(a, out[2]);
+        }
+        __syncthreads();
+        if (y < a.y1) store_segment(seg, s_out[ty], n, tx);
+        __syncthreads();
+    }
+}
+
+template <typename Pattern, bool F32>
+__global__ __launch_bounds__(256) void mosaic_reduced_kernel(const MosaicArgs<typename Pattern::Params> a) {
+    __shared__ typename Pattern::Params s_p;  // (as above)
+    if constexpr (Pattern::kParamsInLds) {
+        stage_params(a, s_p, threadIdx.y * 64 + threadIdx.x);
+        __syncthreads();
+    }
+    const typename Pattern::Params& p = params_of<Pattern>(a, s_p);
+    const int x = a.x0 + blockIdx.x * 64 + threadIdx.x, y = a.y0 + blockIdx.y * 4 + threadIdx.y;
+    if (x >= a.x1 || y >= a.y1) return;
+    int rgb[3];
+    uint16_t out[3];
+    Pattern::reduced_rgb(a, p, y, x, rgb);
+    mosaic::colour(p.M, rgb, out);
+    OutT<F32>* d = static_cast<OutT<F32>*>(a.dst) + ((long long)(y - a.dst_y0) * (a.x1 - a.x0) + (x - a.x0)) * 3;
+    d[0] = finish_sample<F32>(a, out[0]), d[1] = finish_sample<F32>(a, out[1]), d[2] = finish_sample<F32>(a, out[2]);
+}
+
+// An entry point: the checks, then one launch.  The window (row0, col0, rows, cols) of the demosaiced frame is what dst holds (none:
+// all of it); [y0, y1) are rows of the window.  `what` names the entry point in messages.
+template <typename Pattern, bool F32>
+int mosaic_rows(r2f_ctx* ctx, const char* what, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
+                const typename Pattern::Params* params, const int* window, float divisor, float factor, void* dst, int y0, int y1,
+                void* stream) {
+    constexpr int kMaxSide = 1 << 17;  // (the reduced grid has a block per four rows; indices go through long long)
+    constexpr int kMin = Pattern::kMinSide, kReduction = Pattern::kReduction, kReachY = Pattern::kReachY;
+    if (!src_rows || !params || !dst || H < kMin || W < kMin || H > kMaxSide || W > kMaxSide || src_pitch < W || src_gy0 < 0 || src_nrows < 0)
+        return fail(ctx, R2F_EINVAL, "%s: a mosaic of at least %d x %d samples, a pitch of at least W and a source window are required", what,
+                    kMin, kMin);
+    const typename Pattern::Params& p = *params;
+    if (const int rc = Pattern::check_params(ctx, what, p, H, W)) return rc;
+    const bool reduced = Pattern::reduced(p);
+    if (p.out_h != (reduced ? H / kReduction : H) || p.out_w != (reduced ? W / kReduction : W))
+        return fail(ctx, R2F_EINVAL, "%s: the params are those of another frame size (%s)", what, Pattern::kPlanner);
+    const int row0 = window ? window[0] : 0, col0 = window ? window[1] : 0, rows = window ? window[2] : p.out_h,
+              cols = window ? window[3] : p.out_w;
+    if (row0 < 0 || col0 < 0 || rows <= 0 || cols <= 0 || rows > p.out_h - row0 || cols > p.out_w - col0)
+        return fail(ctx, R2F_EINVAL, "%s: the window (%d, %d, %d, %d) is empty or not inside the %d x %d frame", what, row0, col0, rows, cols,
+                    p.out_h, p.out_w);
+    if (y0 < 0 || y1 > rows || y0 > y1) return fail(ctx, R2F_EINVAL, "%s: rows [%d, %d) not inside the output's [0, %d)", what, y0, y1, rows);
+    if (F32 && (!(divisor > 0.f) || (reinterpret_cast<uintptr_t>(dst) & 3u)))
+        return fail(ctx, R2F_EINVAL, "%s: a positive divisor and a 4-byte aligned destination are required", what);
+    if (y0 == y1) return R2F_OK;
+    const int fy0 = row0 + y0, fy1 = row0 + y1;  // the rows of the demosaiced frame
+    const int lo = reduced ? kReduction * fy0 : (fy0 - kReachY > 0 ? fy0 - kReachY : 0),
+              hi = reduced ? kReduction * fy1 : (fy1 + kReachY < H ? fy1 + kReachY : H);
+    if (lo < src_gy0 || (long long)hi > (long long)src_gy0 + src_nrows)
+        return fail(ctx, R2F_EINVAL, "%s: rows [%d, %d) read mosaic rows [%d, %d), the source window holds [%d, %lld)", what, y0, y1, lo, hi,
+                    src_gy0, (long long)src_gy0 + src_nrows);
+    const int wide = ((reinterpret_cast<uintptr_t>(src_rows) & 3u) == 0 && src_pitch % 2 == 0) ? 1 : 0;
+    const MosaicArgs<typename Pattern::Params> a{
+        src_rows, src_gy0, (long long)src_pitch, H, W, p, dst, fy0, fy1, wide, row0, col0, col0 + cols, divisor, factor};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (reduced) {
+        launch_k(mosaic_reduced_kernel<Pattern, F32>, dim3((cols + 63) / 64, (y1 - y0 + 3) / 4), dim3(64, 4), 0, s, a);
+    } else {
+        const int tiles_x = (col0 + cols - 1) / kTW - col0 / kTW + 1;  // (the whole frame: ceil(W / 64), tiles from column 0)
+        launch_k(mosaic_full_kernel<Pattern, F32>, dim3(tiles_x, (y1 - y0 + kTH - 1) / kTH), dim3(64, 4), 0, s, a);
+    }
+    R2F_HIP(ctx, take_launch_status());
+    return R2F_OK;
+}
+
+}  // namespace
+}  // namespace r2f

@@ -1,10 +1,11 @@
 // r2f_xtrans_math.h -- the per-pixel arithmetic of the X-Trans demosaic (include/r2f.h, r2f_demosaic_xtrans_u16), as text the
 // device kernels (r2f_xtrans.hip) and a CPU program (tests/xtrans_check.cpp, g++ -ffp-contract=off) both compile: step A (black /
-// scale), B0 (border ring), B1 (green), B2 (red and blue), B' (reduced size) and C (colour matrix, clip).  Everything is integer
-// arithmetic except the one fp32 multiply of step A and the five fp32 operations per channel of step C, for which contraction is
-// off.  Samples come through accessors at frame coordinates inside the frame: `S(y, x)` the scaled mosaic, `D(y, x)` the
-// colour-difference plane S - G (diff_at), which the kernel keeps instead of G: B2 reads nothing else of its neighbours.  The
-// per-phase tables are the planner's (r2f_xtrans_params): no function here searches for a neighbour.
+// scale), B0 (border ring), B1 (green), B2 (red and blue) and B' (reduced size); step C (colour matrix, clip) is r2f_mosaic_math.h's,
+// shared with the Bayer pattern.  Everything is integer arithmetic except the one fp32 multiply of step A (and the five fp32
+// operations per channel of step C), for which contraction is off.  Samples come through accessors at frame coordinates inside the
+// frame: `S(y, x)` the scaled mosaic, `D(y, x)` the colour-difference plane S - G (diff_at), which the kernel keeps instead of G: B2
+// reads nothing else of its neighbours.  The per-phase tables are the planner's (r2f_xtrans_params): no function here searches for
+// a neighbour.
 //
 // The floor divisions, each exact for the numerators the definition allows:
 //   by 2 (B1's rounding term floor((a + b) / 2)): a + b >= 2, a shift of a non-negative int.
@@ -19,23 +20,8 @@
 //   by count in 1 .. 9 (B0, B'): sums of non-negative samples, the integer divide of the language (truncation is the floor).
 #pragma once
 
-#include <math.h>
-#include <stdint.h>
-
 #include "../../include/r2f.h"
-
-#if defined(__HIPCC__)
-#define R2F_XT_HD __host__ __device__ __forceinline__
-#else
-#define R2F_XT_HD inline
-#endif
-#if defined(__clang__)
-#define R2F_XT_NO_CONTRACT _Pragma("clang fp contract(off)")
-#define R2F_XT_UNROLL _Pragma("unroll")
-#else
-#define R2F_XT_NO_CONTRACT  // (g++: the translation unit is compiled with -ffp-contract=off)
-#define R2F_XT_UNROLL _Pragma("GCC unroll 9")
-#endif
+#include "r2f_mosaic_math.h"
 
 namespace r2f {
 
@@ -45,15 +31,13 @@ bool xtrans_tables(const uint8_t (&cfa)[36], bool reduced, r2f_xtrans_params* ou
 
 namespace xtrans {
 
-constexpr int kRed = 0, kGreen = 1, kBlue = 2;
+using namespace mosaic;  // the macro set, kRed / kGreen / kBlue, clip16, iabs, in_ring and step C (colour)
+
 constexpr int kDivBias = 1 << 20;  // floor_div's: above 12 * 65535
 
-R2F_XT_HD int clip16(int v) { return v < 0 ? 0 : (v > 65535 ? 65535 : v); }
-R2F_XT_HD int iabs(int v) { return v < 0 ? -v : v; }
-R2F_XT_HD int wrap6(int v) { return v < 0 ? v + 6 : (v >= 6 ? v - 6 : v); }  // v in [-6, 12)
-R2F_XT_HD int phase(int y, int x) { return (y % 6) * 6 + x % 6; }            // y, x >= 0
-R2F_XT_HD bool in_ring(int H, int W, int y, int x, int width) { return y < width || y >= H - width || x < width || x >= W - width; }
-R2F_XT_HD uint32_t mul_hi(uint32_t a, uint32_t b) {
+R2F_HD int wrap6(int v) { return v < 0 ? v + 6 : (v >= 6 ? v - 6 : v); }  // v in [-6, 12)
+R2F_HD int phase(int y, int x) { return (y % 6) * 6 + x % 6; }            // y, x >= 0
+R2F_HD uint32_t mul_hi(uint32_t a, uint32_t b) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __umulhi(a, b);
 #else
@@ -61,15 +45,15 @@ R2F_XT_HD uint32_t mul_hi(uint32_t a, uint32_t b) {
 #endif
 }
 // floor(n / d) for 1 <= d <= 12 and |n| <= 12 * 65535, m = floor(2^32 / d) + 1 (anything for d = 1): see the head of the file.
-R2F_XT_HD int floor_div(int n, int d, uint32_t m) {
+R2F_HD int floor_div(int n, int d, uint32_t m) {
     const uint32_t u = (uint32_t)(n + d * kDivBias);
     return (int)(d <= 1 ? u : mul_hi(u, m)) - kDivBias;
 }
-R2F_XT_HD uint32_t recip_of_span(int span) { return span == 2 ? 0x80000001u : (span == 3 ? 0x55555556u : 0x40000001u); }  // 2, 3, 4
+R2F_HD uint32_t recip_of_span(int span) { return span == 2 ? 0x80000001u : (span == 3 ? 0x55555556u : 0x40000001u); }  // 2, 3, 4
 
 // A: one raw sample at phase ph.  |t * mul| <= 65535 * 1024: the truncation stays inside int.
-R2F_XT_HD int scale_sample(const r2f_xtrans_params& p, int raw, int ph) {
-    R2F_XT_NO_CONTRACT
+R2F_HD int scale_sample(const r2f_xtrans_params& p, int raw, int ph) {
+    R2F_NO_CONTRACT
     const int c = p.cfa[ph];
     const float m = c == 0 ? p.mul[0] : (c == 1 ? p.mul[1] : p.mul[2]);
     const float f = (float)(raw - p.black[ph]) * m;
@@ -78,7 +62,7 @@ R2F_XT_HD int scale_sample(const r2f_xtrans_params& p, int raw, int ph) {
 
 // B1: green at the non-green site (y, x) of phase ph, 2 <= y < H - 2, 2 <= x < W - 2.
 template <typename SFn>
-R2F_XT_HD int green_est(const r2f_xtrans_params& p, const SFn& S, int y, int x, int ph) {
+R2F_HD int green_est(const r2f_xtrans_params& p, const SFn& S, int y, int x, int ph) {
     const int ah = p.gap[ph][0], bh = p.gap[ph][1], av = p.gap[ph][2], bv = p.gap[ph][3];
     const int hm = S(y, x - ah), hp = S(y, x + bh), vm = S(y - av, x), vp = S(y + bv, x);
     const int span_h = ah + bh, span_v = av + bv;
@@ -89,14 +73,14 @@ R2F_XT_HD int green_est(const r2f_xtrans_params& p, const SFn& S, int y, int x, 
 
 // S - G at (y, x), 2 <= y < H - 2, 2 <= x < W - 2: 0 at a green site.
 template <typename SFn>
-R2F_XT_HD int diff_at(const r2f_xtrans_params& p, const SFn& S, int y, int x) {
+R2F_HD int diff_at(const r2f_xtrans_params& p, const SFn& S, int y, int x) {
     const int ph = phase(y, x);
     return p.cfa[ph] == kGreen ? 0 : S(y, x) - green_est(p, S, y, x, ph);
 }
 
 // B0: the three planes of a ring pixel, the means over the 3 x 3 neighbourhood clipped to the frame.
 template <typename SFn>
-R2F_XT_HD void border_rgb(const r2f_xtrans_params& p, const SFn& S, int H, int W, int y, int x, int (&rgb)[3]) {
+R2F_HD void border_rgb(const r2f_xtrans_params& p, const SFn& S, int H, int W, int y, int x, int (&rgb)[3]) {
     int sum[3] = {0, 0, 0}, count[3] = {0, 0, 0};
     const int py = y % 6, px = x % 6;
     for (int dy = -1; dy <= 1; ++dy)
@@ -104,22 +88,22 @@ R2F_XT_HD void border_rgb(const r2f_xtrans_params& p, const SFn& S, int H, int W
             const int yy = y + dy, xx = x + dx;
             if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
             const int c = p.cfa[wrap6(py + dy) * 6 + wrap6(px + dx)], s = S(yy, xx);
-            R2F_XT_UNROLL
+            R2F_UNROLL
             for (int k = 0; k < 3; ++k) sum[k] += c == k ? s : 0, count[k] += c == k ? 1 : 0;
         }
     const int c0 = p.cfa[py * 6 + px], own = S(y, x);
-    R2F_XT_UNROLL
+    R2F_UNROLL
     for (int k = 0; k < 3; ++k) rgb[k] = k == c0 ? own : (count[k] ? sum[k] / count[k] : 0);  // (sum >= 0: the division is the floor)
 }
 
 // B2: the three planes of an interior pixel from its sample and the colour differences of its centred 3 x 3.
 template <typename SFn, typename DFn>
-R2F_XT_HD void interior_rgb(const r2f_xtrans_params& p, const SFn& S, const DFn& D, int y, int x, int (&rgb)[3]) {
+R2F_HD void interior_rgb(const r2f_xtrans_params& p, const SFn& S, const DFn& D, int y, int x, int (&rgb)[3]) {
     const int ph = phase(y, x), c0 = p.cfa[ph];
     const int g0 = S(y, x) - D(y, x);
     const unsigned mr = p.taps[ph][0], mb = p.taps[ph][1];
     int sr = 0, sb = 0;
-    R2F_XT_UNROLL
+    R2F_UNROLL
     for (int k = 0; k < 9; ++k) {
         if (k == 4) continue;
         const int dy = k / 3 - 1, dx = k % 3 - 1;
@@ -132,7 +116,7 @@ R2F_XT_HD void interior_rgb(const r2f_xtrans_params& p, const SFn& S, const DFn&
 }
 
 template <typename SFn, typename DFn>
-R2F_XT_HD void pixel_rgb(const r2f_xtrans_params& p, const SFn& S, const DFn& D, int H, int W, int y, int x, int (&rgb)[3]) {
+R2F_HD void pixel_rgb(const r2f_xtrans_params& p, const SFn& S, const DFn& D, int H, int W, int y, int x, int (&rgb)[3]) {
     if (in_ring(H, W, y, x, 3))
         border_rgb(p, S, H, W, y, x, rgb);
     else
@@ -140,32 +124,20 @@ R2F_XT_HD void pixel_rgb(const r2f_xtrans_params& p, const SFn& S, const DFn& D,
 }
 
 // B': output pixel (y, x) of the reduced size from the cell at (3 y, 3 x); q[3 j + i] the scaled sample of the cell's (j, i).
-R2F_XT_HD void reduced_rgb(const r2f_xtrans_params& p, const int (&q)[9], int y, int x, int (&rgb)[3]) {
+R2F_HD void reduced_rgb(const r2f_xtrans_params& p, const int (&q)[9], int y, int x, int (&rgb)[3]) {
     const int cy = y & 1, cx = x & 1;  // (3 y % 6 is 0 or 3)
     int sum[3] = {0, 0, 0};
-    R2F_XT_UNROLL
+    R2F_UNROLL
     for (int k = 0; k < 9; ++k) {
         const int c = p.cfa[(3 * cy + k / 3) * 6 + 3 * cx + k % 3];
         sum[0] += c == 0 ? q[k] : 0, sum[1] += c == 1 ? q[k] : 0, sum[2] += c == 2 ? q[k] : 0;
     }
-    R2F_XT_UNROLL
+    R2F_UNROLL
     for (int c = 0; c < 3; ++c) rgb[c] = sum[c] / p.cell_count[cy * 2 + cx][c];  // (a planned reduced pattern: every count >= 1)
 }
 
-// C: the matrix and the clip.  |acc| <= 3 * 64 * 65535: the truncation stays inside int.
-R2F_XT_HD void colour(const r2f_xtrans_params& p, const int (&rgb)[3], uint16_t (&out)[3]) {
-    R2F_XT_NO_CONTRACT
-    const float r = (float)rgb[0], g = (float)rgb[1], b = (float)rgb[2];
-    R2F_XT_UNROLL
-    for (int k = 0; k < 3; ++k) {
-        float acc = r * p.M[3 * k];
-        const float t1 = g * p.M[3 * k + 1];
-        acc = acc + t1;
-        const float t2 = b * p.M[3 * k + 2];
-        acc = acc + t2;
-        out[k] = (uint16_t)clip16((int)acc);
-    }
-}
+// C with the pattern's params: mosaic::colour (r2f_mosaic_math.h) on their matrix.
+R2F_HD void colour(const r2f_xtrans_params& p, const int (&rgb)[3], uint16_t (&out)[3]) { mosaic::colour(p.M, rgb, out); }
 
 }  // namespace xtrans
 }  // namespace r2f

@@ -1,9 +1,9 @@
 // r2f_xtrans_plan.cpp -- host planner of the X-Trans demosaic (include/r2f.h: r2f_xtrans_plan).  No HIP in this file: hipcc
 // compiles it into the library, g++ -fsanitize=address,undefined,float-cast-overflow into tests/xtrans_check.cpp's program.
-#include <cmath>
 #include <cstring>
 
 #include "../../include/r2f.h"
+#include "r2f_mosaic_plan.h"
 
 namespace r2f {
 
@@ -72,25 +72,11 @@ int r2f_xtrans_plan(const r2f_xtrans_profile* p, int H, int W, r2f_xtrans_params
     for (int i = 0; i < 36; ++i) {
         if (p->pattern[i] < 0 || p->pattern[i] > 2) return R2F_EINVAL;
         r.cfa[i] = (uint8_t)p->pattern[i];
-        const double b = p->black[i];
-        // (the comparisons are written so that a NaN fails them)
-        if (!(b >= 0.0 && b <= 65535.0) || b != std::floor(b)) return R2F_EINVAL;
-        r.black[i] = (int32_t)b;
     }
     const bool reduced = p->reduced != 0;
-    if (!r2f::xtrans_tables(r.cfa, reduced, &r)) return R2F_EINVAL;
-    for (int k = 0; k < 3; ++k) {
-        const double m = p->mul[k];
-        if (!(m > 0.0 && m <= 1024.0)) return R2F_EINVAL;
-        const float mf = (float)m;
-        if (!(mf > 0.f && mf <= 1024.f)) return R2F_EINVAL;  // (a double below the smallest float rounds to 0)
-        r.mul[k] = mf;
-    }
-    for (int i = 0; i < 9; ++i) {
-        const double v = p->matrix[i];
-        if (!(std::fabs(v) <= 64.0)) return R2F_EINVAL;
-        r.M[i] = (float)v;
-    }
+    if (!r2f::mosaic_plan::black_levels(p->black, r.black) || !r2f::xtrans_tables(r.cfa, reduced, &r) ||
+        !r2f::mosaic_plan::multipliers(p->mul, r.mul) || !r2f::mosaic_plan::matrix(p->matrix, r.M))
+        return R2F_EINVAL;
     r.reduced = reduced ? 1 : 0;
     r.out_h = reduced ? H / 3 : H;
     r.out_w = reduced ? W / 3 : W;

@@ -32,7 +32,7 @@ import numpy as np
 
 from . import _lib, filmstock, geometry, payload as phase1, stencils, tiff
 from .bands import StreamedFrame, band_source, plan_bands, stage_schedule
-from .context import LOG_EPS, LUT3D_SCALE, HipContext
+from .context import LOG_EPS, LUT3D_SCALE, MOSAIC_KINDS, HipContext
 from .jpeg_options import _check_jpeg_image, checked_options
 from .exports import JpegExport, TiffExport
 from .payload import DEVICE_EXPOSURE, host_stream_gate, stream_rejection
@@ -1095,7 +1095,7 @@ class HipProcessor:
 
         demosaic_step = cpu_payload.get("demosaic")
         if demosaic_step:  # a mosaic: LibRaw's share of raw_to_linear on the device -> the uint16 frame of the lines below
-            demosaic = self.ctx.demosaic_xtrans if phase1.is_xtrans(demosaic_step["params"]) else self.ctx.demosaic_u16
+            demosaic = getattr(self.ctx, MOSAIC_KINDS[type(demosaic_step["params"])][0])
             image = cut_and_turn(demosaic(image.contiguous(), demosaic_step["params"]), demosaic_step["window"],
                                  demosaic_step["rotate_times"], dims=(0, 1))
         if image.dtype in (torch.int16, torch.uint16):  # a decoded 16-bit frame: raw_conversion.py:50-52 on the device

@@ -24,7 +24,8 @@ from .raw import RawProfile, XTransProfile
 _DEMOSAIC_REJECTED = "the demosaic step (raw_profile): "  # every refusal of a mosaic begins with it, then says why
 _LENS_REJECTED = "the lens step (lens_profile): its gather reads the whole frame, which a row band does not hold"
 STREAM_MIN_SAMPLES = 1 << 24  # samples of the pipeline's frame from which a frame streams (16.7 M)
-DEMOSAIC_REACH = 4  # mosaic rows above and below an output row that the full-size demosaic reads (r2f_demosaic_f32)
+DEMOSAIC_REACH = 4  # mosaic rows above and below an output row that the full-size demosaic reads (r2f_demosaic_f32): the Python
+                    # statement of BayerPattern::kReachY in csrc/r2f_demosaic.hip, which the entry point checks a call against
 DEVICE_EXPOSURE = "device"  # exposure="device": the auto exposure of a uint16 frame is measured on the device; also the marker a
                             # payload carries in place of its float `u16_factor`
 

@@ -21,7 +21,7 @@ from . import _lib
 _PATTERNS = {"RGGB": _lib.CFA_RGGB, "BGGR": _lib.CFA_BGGR, "GRBG": _lib.CFA_GRBG, "GBRG": _lib.CFA_GBRG}
 
 
-def _floats(name, values, counts, who="RawProfile"):
+def _floats(name, values, counts, who):
     try:
         out = tuple(float(v) for v in values)
     except TypeError:
@@ -45,8 +45,39 @@ def _matrix(matrix, who):
     return rows
 
 
+class _MosaicProfile:
+    """What the two profiles share: the normalisation of black, multipliers and matrix, and `plan()`.  A profile class states
+    `_sites` (black levels per period of its array), `_multiplier_counts`, its params type, its planner's name and `to_c` (the C
+    profile)."""
+
+    def _normalise(self):
+        """black, multipliers and matrix as tuples of floats, checked (frozen: set once, from __post_init__)."""
+        who = type(self).__name__
+        black = self.black
+        if isinstance(black, numbers.Real) and not isinstance(black, bool):
+            black = (black,) * self._sites
+        black = _floats("black", black, (self._sites,), who)
+        if any(b < 0 or b > 65535 or b != math.floor(b) for b in black):
+            raise ValueError(f"{who}.black must be integers in [0, 65535], got {self.black!r}")
+        mul = _floats("multipliers", self.multipliers, self._multiplier_counts, who)
+        if any(not 0 < m <= 1024 for m in mul):
+            raise ValueError(f"{who}.multipliers must lie in (0, 1024], got {self.multipliers!r}")
+        for name, value in (("black", black), ("multipliers", mul), ("matrix", _matrix(self.matrix, who))):
+            object.__setattr__(self, name, value)
+
+    def plan(self, H: int, W: int, half_size: bool = False):
+        """The params of an H x W mosaic (no GPU: r2f_demosaic_params / r2f_xtrans_params); ValueError for what the planner refuses
+        (a frame below the array's 2 x 2 / 6 x 6, an odd side with half_size of a Bayer frame, an X-Trans pattern that is not
+        admissible -- for the reduced size, with half_size --, a multiplier that rounds to 0 as a float)."""
+        out = self._c_params()
+        profile = self.to_c(half_size)
+        if getattr(_lib.load(), self._planner)(C.byref(profile), int(H), int(W), C.byref(out)) != _lib.OK:
+            raise ValueError(f"{self._planner} refused {self!r} for a {H} x {W} mosaic (half_size={bool(half_size)})")
+        return out
+
+
 @dataclass(frozen=True)
-class RawProfile:
+class RawProfile(_MosaicProfile):
     """A frozen, hashable record (part of the image cache key, like LensProfile).
 
     pattern: "RGGB" | "BGGR" | "GRBG" | "GBRG", the colours of the quad at (0, 0) in reading order.
@@ -59,25 +90,15 @@ class RawProfile:
     matrix: tuple = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
 
     reduction = 2  # what half_size=True divides a mosaic's sides by (no dataclass field: not part of equality, hash or repr)
+    _sites, _multiplier_counts = 4, (3, 4)
+    _c_params, _planner = _lib.DemosaicParams, "r2f_demosaic_plan"
 
     def __post_init__(self):
         if not isinstance(self.pattern, str) or self.pattern not in _PATTERNS:
             raise ValueError(f"RawProfile.pattern must be one of {sorted(_PATTERNS)}, got {self.pattern!r}")
-        set_ = lambda k, v: object.__setattr__(self, k, v)  # noqa: E731 -- (frozen: normalised to tuples of floats once)
-        black = self.black
-        if isinstance(black, numbers.Real) and not isinstance(black, bool):
-            black = (black,) * 4
-        black = _floats("black", black, (4,))
-        if any(b < 0 or b > 65535 or b != math.floor(b) for b in black):
-            raise ValueError(f"RawProfile.black must be integers in [0, 65535], got {self.black!r}")
-        set_("black", black)
-        mul = _floats("multipliers", self.multipliers, (3, 4))
-        if len(mul) == 3:
-            mul = tuple(mul["RGB".index(c)] for c in self.pattern)
-        if any(not 0 < m <= 1024 for m in mul):
-            raise ValueError(f"RawProfile.multipliers must lie in (0, 1024], got {self.multipliers!r}")
-        set_("multipliers", mul)
-        set_("matrix", _matrix(self.matrix, "RawProfile"))
+        self._normalise()
+        if len(self.multipliers) == 3:  # (r, g, b) -> per site of the quad
+            object.__setattr__(self, "multipliers", tuple(self.multipliers["RGB".index(c)] for c in self.pattern))
 
     def to_c(self, half_size: bool = False) -> _lib.RawProfile:
         p = _lib.RawProfile(pattern=_PATTERNS[self.pattern], half_size=int(bool(half_size)))
@@ -86,21 +107,12 @@ class RawProfile:
         p.matrix[:] = [v for row in self.matrix for v in row]
         return p
 
-    def plan(self, H: int, W: int, half_size: bool = False) -> _lib.DemosaicParams:
-        """The r2f_demosaic_params of an H x W mosaic (no GPU); ValueError for what the planner refuses (a frame below 2 x 2, an
-        odd side with half_size, a multiplier that rounds to 0 as a float)."""
-        out = _lib.DemosaicParams()
-        profile = self.to_c(half_size)
-        if _lib.load().r2f_demosaic_plan(C.byref(profile), int(H), int(W), C.byref(out)) != _lib.OK:
-            raise ValueError(f"r2f_demosaic_plan refused {self!r} for a {H} x {W} mosaic (half_size={bool(half_size)})")
-        return out
-
 
 XTRANS = ("GBGGRG", "RGRBGB", "GBGGRG", "GRGGBG", "BGBRGR", "GRGGBG")  # the canonical layout; a camera's is one of its 36 cyclic shifts
 
 
 @dataclass(frozen=True)
-class XTransProfile:
+class XTransProfile(_MosaicProfile):
     """What a RAW file's parser knows of a frame with a 6 x 6 colour filter array (Fujifilm's X-Trans), for the demosaic on the
     device: r2f_demosaic_xtrans_u16 of include/r2f.h -- the project's own interpolation, not LibRaw's (Markesteijn's); parity with
     LibRaw's bytes is unpinned.  A frozen, hashable record (part of the image cache key, like RawProfile).
@@ -118,9 +130,10 @@ class XTransProfile:
     matrix: tuple = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
 
     reduction = 3
+    _sites, _multiplier_counts = 36, (3,)
+    _c_params, _planner = _lib.XTransParams, "r2f_xtrans_plan"
 
     def __post_init__(self):
-        set_ = lambda k, v: object.__setattr__(self, k, v)  # noqa: E731 -- (frozen: normalised to tuples once)
         pattern = self.pattern
         if isinstance(pattern, str):
             pattern = tuple(pattern[i:i + 6] for i in range(0, 36, 6)) if len(pattern) == 36 else (pattern,)
@@ -132,19 +145,8 @@ class XTransProfile:
             raise ValueError(f"XTransProfile.pattern must be six strings of six letters from 'RGB' (or one of 36), got {self.pattern!r}")
         if set("".join(pattern)) != set("RGB"):
             raise ValueError(f"XTransProfile.pattern must hold each of R, G and B, got {self.pattern!r}")
-        set_("pattern", pattern)
-        black = self.black
-        if isinstance(black, numbers.Real) and not isinstance(black, bool):
-            black = (black,) * 36
-        black = _floats("black", black, (36,), "XTransProfile")
-        if any(b < 0 or b > 65535 or b != math.floor(b) for b in black):
-            raise ValueError(f"XTransProfile.black must be integers in [0, 65535], got {self.black!r}")
-        set_("black", black)
-        mul = _floats("multipliers", self.multipliers, (3,), "XTransProfile")
-        if any(not 0 < m <= 1024 for m in mul):
-            raise ValueError(f"XTransProfile.multipliers must lie in (0, 1024], got {self.multipliers!r}")
-        set_("multipliers", mul)
-        set_("matrix", _matrix(self.matrix, "XTransProfile"))
+        object.__setattr__(self, "pattern", pattern)
+        self._normalise()
 
     def to_c(self, half_size: bool = False) -> _lib.XTransProfile:
         p = _lib.XTransProfile(reduced=int(bool(half_size)))
@@ -153,12 +155,3 @@ class XTransProfile:
         p.mul[:] = self.multipliers
         p.matrix[:] = [v for row in self.matrix for v in row]
         return p
-
-    def plan(self, H: int, W: int, half_size: bool = False) -> _lib.XTransParams:
-        """The r2f_xtrans_params of an H x W mosaic (no GPU); ValueError for what the planner refuses (a frame below 6 x 6, a
-        pattern that is not admissible -- for the reduced size, with half_size --, a multiplier that rounds to 0 as a float)."""
-        out = _lib.XTransParams()
-        profile = self.to_c(half_size)
-        if _lib.load().r2f_xtrans_plan(C.byref(profile), int(H), int(W), C.byref(out)) != _lib.OK:
-            raise ValueError(f"r2f_xtrans_plan refused {self!r} for a {H} x {W} mosaic (half_size={bool(half_size)})")
-        return out
