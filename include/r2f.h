@@ -584,6 +584,36 @@ R2F_API int r2f_demosaic_xtrans_u16(r2f_ctx* ctx, const uint16_t* src_rows, int 
 /* r2f_demosaic_xtrans_u16's tile (test shapes are derived from it): its sides are 4 and 2 modulo 6. */
 enum { R2F_XTRANS_TILE_W = 64, R2F_XTRANS_TILE_H = 32 };
 
+/* The sensor's orientation in the demosaic.  LibRaw rotates its output by the orientation the camera recorded (sizes.flip, with
+ * user_flip left alone as raw_to_linear leaves it); the two entry points below write the demosaiced frame that way round, out of the
+ * LDS in which the kernels hold every finished pixel, without a second frame.  Parity with LibRaw's bytes is UNPINNED like the rest
+ * of the demosaic, and so is the reading of sizes.flip: rawpy is on no machine this project sees.
+ * Let D be the uint16 (out_h, out_w, 3) frame of r2f_demosaic_u16 or r2f_demosaic_xtrans_u16 (full or reduced size).  orientation
+ * is an integer 0 .. 7 with LibRaw's sizes.flip bits: 4 swaps the axes, 2 mirrors rows, 1 mirrors columns -- 0 is upright, 3 is 180
+ * degrees, 5 is 90 degrees counter-clockwise and 6 is 90 degrees clockwise.  The oriented frame O has shape (out_h, out_w, 3) without
+ * bit 4 and (out_w, out_h, 3) with it, and O[r, c] = D[r', c'] with
+ *   (a, b) = (c, r) if orientation & 4, else (r, c);  r' = out_h - 1 - a if orientation & 2, else a;  c' = out_w - 1 - b if
+ *   orientation & 1, else b.
+ * In NumPy: E = D; if o & 2: E = E[::-1]; if o & 1: E = E[:, ::-1]; if o & 4: E = E.transpose(1, 0, 2).
+ * [y0, y1) are rows of O: the call writes those rows of dst (O, contiguous, row 0 at dst) and nothing else.  Without bit 4 they are
+ * D's rows [y0, y1), or [out_h - y1, out_h - y0) with bit 2, and the call reads the mosaic rows the upright contract names for those
+ * rows of D (full size: 4 rows either side for a Bayer mosaic, 3 for an X-Trans one, clipped to [0, H); reduced size: 2 or 3 mosaic
+ * rows per row); those must lie in the source window, else R2F_EINVAL before any launch.  With bit 4 they are D's columns [y0, y1),
+ * or [out_w - y1, out_w - y0) with bit 1: the call reads every mosaic row, and the source window must hold [0, H).  Refused:
+ * everything the upright entry point refuses, and an orientation outside 0 .. 7.  orientation = 0 writes the bytes of the upright
+ * entry point (and launches its kernel).  A band's bytes are those of the same rows of a whole-frame call, whatever the cut, the
+ * pitch or the source's alignment.  Every phase is still taken from frame coordinates of D.
+ * The kernels are the upright ones with another epilogue (a compile-time class; raw2film_amd/csrc/r2f_mosaic_math.h has the index
+ * map).  Mirrored (bits 1 and 2 only): a wave's row of the tile is still one contiguous segment of dst; with bit 1 the lanes write
+ * their pixel to the mirrored slot of the row buffer, with bit 2 the segment walks upward.  Turned (bit 4): a row of D is a column
+ * of O, so the block collects its 64 x 32 tile in LDS in O's layout -- 64 rows of O, an odd number of 32-bit words apart so that a
+ * wave's 64 lanes write 64 rows without a bank conflict -- and each leaves as one contiguous run of up to 192 bytes.  The reduced
+ * sizes stay a lane per output pixel, stored where the map puts it. */
+R2F_API int r2f_demosaic_oriented_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
+                     const r2f_demosaic_params* params, int orientation, uint16_t* dst_u16_hwc3, int y0, int y1, void* stream);
+R2F_API int r2f_demosaic_xtrans_oriented_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H,
+                     int W, const r2f_xtrans_params* params, int orientation, uint16_t* dst_u16_hwc3, int y0, int y1, void* stream);
+
 /* The hand-off from RAW decoding: the last two lines of raw_to_linear (raw_conversion.py:50-52) applied to LibRaw's 16-bit
  * output on the device, so that a decoded frame crosses PCIe as uint16 (6 bytes per pixel) instead of float32 (12 or 16):
  * dst = float(src) / divisor (65535, one correctly rounded fp32 division) * factor (the float32 of 2 ** calc_exposure(...),

@@ -199,6 +199,16 @@ _SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(XTransParams), C.c_void_p, C.c_int, C.c_int, C.c_void_p],
     ),
+    "r2f_demosaic_oriented_u16": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(DemosaicParams), C.c_int, C.c_void_p, C.c_int, C.c_int,
+         C.c_void_p],
+    ),
+    "r2f_demosaic_xtrans_oriented_u16": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(XTransParams), C.c_int, C.c_void_p, C.c_int, C.c_int,
+         C.c_void_p],
+    ),
     "r2f_resize_lanczos4_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "r2f_lanczos4_table": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "r2f_kernel_timing": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_double), _P(C.c_int), _P(C.c_double)]),

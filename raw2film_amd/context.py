@@ -8,6 +8,7 @@ torch is used for memory and streams only; every computation is a HIP kernel of 
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 
 import numpy as np
 
@@ -572,14 +573,19 @@ class HipContext:
         H, W = int(mosaic.shape[0]), int(mosaic.shape[1])
         return H, W, params if isinstance(params, params_type) else params.plan(H, W)
 
-    def _demosaic(self, what, fn, params_type, mosaic, params, out, rows, window=None, decode=None):
+    def _demosaic(self, what, fn, params_type, mosaic, params, out, rows, window=None, decode=None, orientation=0):
         """The three demosaic methods: the mosaic check, the planning of a profile, the window, the `out` check, `rows`, the call.
-        fn: the C entry point; decode = (divisor, factor): the float32 epilogue, which also takes a window (default: the frame)."""
+        fn: the C entry point; decode = (divisor, factor): the float32 epilogue, which also takes a window (default: the frame);
+        orientation: not 0 with the oriented form of `fn` (r2f_demosaic_oriented_u16: `out` and `rows` are then those of O)."""
         torch = self._torch
         H, W, params = self._check_mosaic(mosaic, params, what, params_type)
+        if isinstance(orientation, bool) or not isinstance(orientation, numbers.Integral) or not 0 <= orientation <= 7:
+            raise ValueError(f"{what}: orientation must be an integer 0 .. 7 (LibRaw's sizes.flip bits), got {orientation!r}")
         r0, c0, nr, nc = (0, 0, int(params.out_h), int(params.out_w)) if window is None else (int(v) for v in window)
         if not (0 <= r0 and 0 <= c0 and nr > 0 and nc > 0 and r0 + nr <= params.out_h and c0 + nc <= params.out_w):
             raise ValueError(f"{what}: window {(r0, c0, nr, nc)} is not inside the {params.out_h} x {params.out_w} frame")
+        if orientation & 4:  # (no window with an orientation: the oriented frame's sides)
+            nr, nc = nc, nr
         shape = (nr, nc, 3)
         dtypes, name = ((torch.float32,), "float32") if decode else ((torch.uint16, torch.int16), "uint16")
         if out is None:
@@ -589,27 +595,32 @@ class HipContext:
         else:
             self._same_device(out, "out")
         y0, y1 = (0, nr) if rows is None else (int(rows[0]), int(rows[1]))
-        epilogue = (r0, c0, nr, nc, *decode) if decode else ()
+        epilogue = (r0, c0, nr, nc, *decode) if decode else (int(orientation),) if orientation else ()
         self._check(fn(self._h, mosaic.data_ptr(), 0, H, int(mosaic.stride(0)), H, W, C.byref(params), *epilogue, out.data_ptr(), y0, y1,
                        self._stream()))
         return out
 
-    def demosaic_u16(self, mosaic, params, out=None, rows=None):
+    def demosaic_u16(self, mosaic, params, out=None, rows=None, orientation=0):
         """The Bayer demosaic of include/r2f.h (r2f_demosaic_u16: black / scale, PPG or the half-size form, camera matrix, clip)
         of a uint16 (H, W) CUDA mosaic (int16 tensors are read as the same bits; rows may be pitched: stride(0) >= W, stride(1)
         = 1) -> uint16 (out_h, out_w, 3), the frame decode_u16 / decode_u16_auto / exposure_rows take.
         params: a raw2film_amd.raw.RawProfile (planned full size for this mosaic) or the r2f_demosaic_params of its size.
-        rows = (y0, y1): only those output rows of `out` are written (default: all)."""
-        return self._demosaic("demosaic_u16", self._lib.r2f_demosaic_u16, _lib.DemosaicParams, mosaic, params, out, rows)
+        rows = (y0, y1): only those output rows of `out` are written (default: all).
+        orientation (0 .. 7, LibRaw's sizes.flip bits; not taken from a profile: name it): not 0 writes the oriented frame O of
+        include/r2f.h (r2f_demosaic_oriented_u16) -- (out_w, out_h, 3) with bit 4 --, and `out` and `rows` are O's."""
+        fn = self._lib.r2f_demosaic_oriented_u16 if orientation else self._lib.r2f_demosaic_u16
+        return self._demosaic("demosaic_u16", fn, _lib.DemosaicParams, mosaic, params, out, rows, orientation=orientation)
 
-    def demosaic_xtrans(self, mosaic, params, out=None, rows=None):
+    def demosaic_xtrans(self, mosaic, params, out=None, rows=None, orientation=0):
         """The X-Trans demosaic of include/r2f.h (r2f_demosaic_xtrans_u16: black / scale, the project's own directional-green /
         colour-difference interpolation or the reduced third-size form, camera matrix, clip -- not LibRaw's algorithm) of a uint16
         (H, W) CUDA mosaic of at least 6 x 6 samples (int16 tensors are read as the same bits; rows may be pitched) -> uint16
         (out_h, out_w, 3), the frame decode_u16 / decode_u16_auto / exposure_rows take.
         params: a raw2film_amd.raw.XTransProfile (planned full size for this mosaic) or the r2f_xtrans_params of its size.
-        rows = (y0, y1): only those output rows of `out` are written (default: all)."""
-        return self._demosaic("demosaic_xtrans", self._lib.r2f_demosaic_xtrans_u16, _lib.XTransParams, mosaic, params, out, rows)
+        rows = (y0, y1): only those output rows of `out` are written (default: all).
+        orientation: demosaic_u16's (r2f_demosaic_xtrans_oriented_u16)."""
+        fn = self._lib.r2f_demosaic_xtrans_oriented_u16 if orientation else self._lib.r2f_demosaic_xtrans_u16
+        return self._demosaic("demosaic_xtrans", fn, _lib.XTransParams, mosaic, params, out, rows, orientation=orientation)
 
     def demosaic_f32(self, mosaic, params, factor: float, divisor: float = 65535.0, window=None, out=None, rows=None):
         """demosaic_u16 and decode_u16 in one kernel (r2f_demosaic_f32): window = (row0, col0, rows, cols) of the demosaiced frame

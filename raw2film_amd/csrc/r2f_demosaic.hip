@@ -1,9 +1,12 @@
 // r2f_demosaic.hip -- the Bayer demosaic ahead of the uint16 hand-off (include/r2f.h: r2f_demosaic_u16, r2f_demosaic_f32): what the
 // Bayer pattern supplies to the staging of r2f_mosaic_stage.h (kernels, LDS tiles, loads, stores and the entry points' checks), and
-// its entry points.  The arithmetic is r2f_demosaic_math.h's (the text tests/demosaic_check.cpp compiles for the CPU).  Four
-// kernels: the full and the half size, each with the uint16 and with the float epilogue.
+// its entry points.  The arithmetic is r2f_demosaic_math.h's (the text tests/demosaic_check.cpp compiles for the CPU).  Seven
+// kernels: the full and the half size, each with the uint16 and with the float epilogue; and for r2f_demosaic_oriented_u16 the
+// mirrored and the turned full size and the oriented half size (uint16).
 // LDS per block of the full size: 5760 (72 x 40 samples) + 4488 (the green plane, 66 x 34) and the row buffer of the epilogue, 1536
-// (uint16) or 3072 (float) -- 11.5 or 13 KB: a dozen blocks fit a CU's 160 KB either way, so the wave slots are the limit, not LDS
+// (uint16, upright or mirrored) or 3072 (float) -- 11.5 or 13 KB: a dozen blocks fit a CU's 160 KB either way, so the wave slots are
+// the limit, not LDS.  The turned class holds the whole tile in O's layout instead, 64 rows of 196 bytes = 12544: 22.3 KB, seven
+// blocks a CU -- 28 waves of its 32 (the upright kernels keep their 11.5 KB: the class is a template parameter)
 #include "r2f_mosaic_stage.h"  // (first: the HIP runtime, whose qualifiers the math headers use)
 
 #include "r2f_demosaic_math.h"
@@ -73,6 +76,14 @@ int r2f_demosaic_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int sr
     R2F_GUARD(ctx);
     return mosaic_rows<BayerPattern, false>(ctx, "demosaic_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, params, nullptr, 1.f, 1.f,
                                             dst_u16_hwc3, y0, y1, stream);
+}
+
+int r2f_demosaic_oriented_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
+                              const r2f_demosaic_params* params, int orientation, uint16_t* dst_u16_hwc3, int y0, int y1, void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    return mosaic_rows<BayerPattern, false>(ctx, "demosaic_oriented_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, params, nullptr, 1.f,
+                                            1.f, dst_u16_hwc3, y0, y1, stream, orientation);
 }
 
 int r2f_demosaic_f32(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,

@@ -1,7 +1,8 @@
 // r2f_mosaic_math.h -- what the per-pixel arithmetic of the two demosaics has in common (r2f_demosaic_math.h the Bayer pattern's,
-// r2f_xtrans_math.h the X-Trans one's): the host/device macro set, the integer helpers and step C (colour matrix, clip).  Like the
-// two pattern headers this is text that hipcc compiles for the device and g++ -ffp-contract=off for the CPU programs
-// (tests/demosaic_check.cpp, tests/xtrans_check.cpp).  No HIP types, no includes beyond <math.h> and <stdint.h>.
+// r2f_xtrans_math.h the X-Trans one's): the host/device macro set, the integer helpers, step C (colour matrix, clip), the row-range
+// contract and the index map of the oriented entry points (namespace orient).  Like the two pattern headers this is text that hipcc
+// compiles for the device and g++ -ffp-contract=off for the CPU programs (tests/demosaic_check.cpp, tests/xtrans_check.cpp,
+// tests/orient_check.cpp).  No HIP types, no includes beyond <math.h> and <stdint.h>.
 #pragma once
 
 #include <math.h>
@@ -45,5 +46,54 @@ R2F_HD void colour(const float (&M)[9], const int (&rgb)[3], uint16_t (&out)[3])
     }
 }
 
+// The mosaic rows [lo, hi) that rows [fy0, fy1) of the demosaiced frame D read (the row-range contract of include/r2f.h): full size
+// `reach` rows either side, clipped to the H rows of the mosaic; the reduced form (reduction = 2 or 3, else 0) the rows of its cells.
+R2F_HD void source_rows(int fy0, int fy1, int H, int reach, int reduction, int& lo, int& hi) {
+    lo = reduction ? reduction * fy0 : (fy0 - reach > 0 ? fy0 - reach : 0);
+    hi = reduction ? reduction * fy1 : (fy1 + reach < H ? fy1 + reach : H);
+}
+
 }  // namespace mosaic
+
+// The sensor's orientation (include/r2f.h, r2f_demosaic_oriented_u16): LibRaw's sizes.flip bits.  D is the demosaiced frame,
+// out_h x out_w; O the oriented one, rows(o) x cols(o), with O[r, c] = D[to_frame(r, c)].  One text for the entry points' checks, the
+// kernels and tests/orient_check.cpp.
+namespace orient {
+
+constexpr int kCols = 1, kRows = 2, kSwap = 4;  // mirror the columns, mirror the rows, swap the axes
+
+R2F_HD bool valid(int o) { return o >= 0 && o <= 7; }
+R2F_HD int rows(int o, int out_h, int out_w) { return o & kSwap ? out_w : out_h; }
+R2F_HD int cols(int o, int out_h, int out_w) { return o & kSwap ? out_h : out_w; }
+
+// the pixel of D that O[r, c] holds
+R2F_HD void to_frame(int o, int out_h, int out_w, int r, int c, int& dy, int& dx) {
+    const int a = o & kSwap ? c : r, b = o & kSwap ? r : c;
+    dy = o & kRows ? out_h - 1 - a : a;
+    dx = o & kCols ? out_w - 1 - b : b;
+}
+// ... and its inverse: where D[dy, dx] goes (both mirrors are involutions, the swap comes last)
+R2F_HD void from_frame(int o, int out_h, int out_w, int dy, int dx, int& r, int& c) {
+    const int a = o & kRows ? out_h - 1 - dy : dy, b = o & kCols ? out_w - 1 - dx : dx;
+    r = o & kSwap ? b : a;
+    c = o & kSwap ? a : b;
+}
+
+struct Rect {
+    int y0, y1, x0, x1;  // rows [y0, y1) and columns [x0, x1) of D
+};
+// The pixels of D that rows [y0, y1) of O hold, 0 <= y0 <= y1 <= rows(o): whole rows of D, or with the axes swapped whole columns.
+R2F_HD Rect rect_of(int o, int out_h, int out_w, int y0, int y1) {
+    if (o & kSwap) return o & kCols ? Rect{0, out_h, out_w - y1, out_w - y0} : Rect{0, out_h, y0, y1};
+    return o & kRows ? Rect{out_h - y1, out_h - y0, 0, out_w} : Rect{y0, y1, 0, out_w};
+}
+// The mosaic rows [lo, hi) a call for that rectangle reads: those of its rows of D; with the axes swapped every row of the mosaic.
+R2F_HD void source_rows(int o, const Rect& d, int H, int reach, int reduction, int& lo, int& hi) {
+    if (o & kSwap)
+        lo = 0, hi = H;
+    else
+        mosaic::source_rows(d.y0, d.y1, H, reach, reduction, lo, hi);
+}
+
+}  // namespace orient
 }  // namespace r2f

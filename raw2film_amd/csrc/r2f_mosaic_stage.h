@@ -8,7 +8,9 @@
 //   mosaic_reduced_kernel  one lane per output pixel of the reduced form (a half or a third of the mosaic's sides)
 //   mosaic_rows            the checks every entry point makes, then one launch
 // Each is a template over a Pattern and over the epilogue: the uint16 frame, or a window of it decoded to the float frame the front
-// stage reads (decode_sample of r2f_device.h on each finished sample).  A Pattern states what differs and nothing else:
+// stage reads (decode_sample of r2f_device.h on each finished sample); and, for the uint16 frame written the way round the sensor
+// was held (the oriented entry points; the index map is r2f_mosaic_math.h's orient), over an OrientClass: mirrored rows leave from
+// the row buffer, quarter turns through the whole tile transposed in LDS.  A Pattern states what differs and nothing else:
 //   Params, Aux                   its r2f_*_params and the auxiliary plane's element type (uint16_t green / int colour difference)
 //   kMinSide, kReduction          the smallest mosaic side, what the reduced form divides the sides by
 //   kReachY, kApronX              mosaic rows a full-size output row reads above and below it; staged columns each side of a tile
@@ -52,7 +54,19 @@ struct MosaicArgs {
     int wide;    // 1: src is 4-byte aligned and the pitch even -> a pair of samples at an even x is one 32-bit load
     int dst_y0, x0, x1;     // the window of D that dst holds (the uint16 entry points: all of it)
     float divisor, factor;  // the float epilogue's
+    int orientation;        // the oriented entry points': dst is then row 0 of O, and [y0, y1) x [x0, x1) the rectangle of D it takes
 };
+
+// How the finished pixels of the full size leave: as rows of D; as rows of O that are rows of D mirrored (bits 1 and 2 of the
+// orientation); or as rows of O that are columns of D (bit 4).  A compile-time class: each has its own epilogue and LDS.
+enum OrientClass { kUpright = 0, kMirrored = 1, kTurned = 2 };
+// The turned class collects a tile's finished pixels in LDS in O's layout: kTW rows of O (a column of D each) of up to kTH pixels.
+// A wave's 64 lanes hold one row of D: each writes its pixel into a different row of that buffer, at the same offset in it.  Every
+// ds_write goes to bank (byte address / 4) % 32, lanes conflict within a 32-lane half; with a pitch of P dwords lane l's bank is
+// (l * P + const) % 32, and for an odd P the 32 lanes of a half hit 32 different banks.  A row holds 3 * kTH uint16 = 48 dwords; 49
+// is the next odd number: 98 uint16.  (A pitch of 48 would put lanes l and l + 2 on one bank: 16 ways.)
+constexpr int kTurnPitch = 3 * kTH + 2;  // uint16
+static_assert(kTurnPitch % 2 == 0 && (kTurnPitch / 2) % 2 == 1, "whole dwords per row (store_segment reads them), an odd number of them");
 
 // The extents of what a block stages: the scaled samples, and the auxiliary plane with its 1-sample apron.
 template <typename Pattern>
@@ -150,15 +164,17 @@ __device__ __forceinline__ void store_segment(float* seg, const float* s, int n,
 // The tile grid is anchored to the frame's columns (tile origins at multiples of 64, so that load_pair's x stays even whatever the
 // window's col0) and to the call's first row; lanes outside the window's columns compute nothing and store nothing.  Every phase is
 // taken from frame coordinates, never from the tile's.
-template <typename Pattern, bool F32>
+template <typename Pattern, bool F32, int Cls = kUpright>
 __global__ __launch_bounds__(256) void mosaic_full_kernel(const MosaicArgs<typename Pattern::Params> a) {
+    static_assert(Cls == kUpright || !F32, "the float epilogue is upright");
     using St = Staged<Pattern>;
     using Aux = typename Pattern::Aux;
     constexpr int kReachY = Pattern::kReachY, kApronX = Pattern::kApronX, kSW = St::kSW, kSH = St::kSH, kAW = St::kAW, kAH = St::kAH;
     __shared__ typename Pattern::Params s_p;  // (no use of it, and so no LDS, unless the pattern keeps its params there)
     __shared__ __align__(16) uint16_t s_s[kSH * kSW];
     __shared__ __align__(16) Aux s_a[kAH * kAW];
-    __shared__ __align__(16) OutT<F32> s_out[4][3 * kTW];
+    using OutBuffer = std::conditional_t<Cls == kTurned, uint16_t[kTW * kTurnPitch], OutT<F32>[4][3 * kTW]>;  // the tile, or a row per wave
+    __shared__ __align__(16) OutBuffer s_out;
     const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * 64 + tx;
     const int tx0 = (a.x0 / kTW + (int)blockIdx.x) * kTW, ty0 = a.y0 + blockIdx.y * kTH;
     if constexpr (Pattern::kParamsInLds) {
@@ -195,27 +211,78 @@ __global__ __launch_bounds__(256) void mosaic_full_kernel(const MosaicArgs<typen
     const int x = tx0 + tx;
     // this tile's share of a row of the window: columns [xa, xb), n elements
     const int xa = tx0 > a.x0 ? tx0 : a.x0, xb = tx0 + kTW < a.x1 ? tx0 + kTW : a.x1, n = 3 * (xb - xa);
-    // the wave's row segment, n contiguous elements of dst: that of its first row, then four rows on per step (one 64-bit product
-    // here, none per row)
-    const long long row_elems = 3LL * (a.x1 - a.x0);
-    OutT<F32>* seg = static_cast<OutT<F32>*>(a.dst) + (ty0 + ty - a.dst_y0) * row_elems + 3 * (xa - a.x0);
-    for (int q = 0; q < kRowsPerLane; ++q, seg += 4 * row_elems) {
-        const int y = ty0 + ty + 4 * q;  // (the same for all 64 lanes of a wave)
-        if (y < a.y1 && x >= xa && x < xb) {
-            int rgb[3];
-            uint16_t out[3];
-            Pattern::pixel_rgb(p, S, A, a.H, a.W, y, x, rgb);
-            mosaic::colour(p.M, rgb, out);
-            OutT<F32>* o = s_out[ty] + 3 * (x - xa);
-            o[0] = finish_sample<F32>(a, out[0]), o[1] = finish_sample<F32>(a, out[1]), o[2] = finish_sample<F32>(a, out[2]);
+    if constexpr (Cls == kTurned) {
+        // The tile's rows of D, [ty0, ye), are columns [c0, c0 + ye - ty0) of O, backwards with the rows mirrored; its column x of D is
+        // row x of O, or out_w - 1 - x with the columns mirrored.  All pixels into the buffer first, then a wave takes every fourth
+        // row of it to dst as one contiguous run.
+        const bool flip_rows = a.orientation & orient::kRows, flip_cols = a.orientation & orient::kCols;
+        const int ye = ty0 + kTH < a.y1 ? ty0 + kTH : a.y1, c0 = flip_rows ? a.p.out_h - ye : ty0;
+        for (int q = 0; q < kRowsPerLane; ++q) {
+            const int y = ty0 + ty + 4 * q;
+            if (y < ye && x >= xa && x < xb) {
+                int rgb[3];
+                uint16_t out[3];
+                Pattern::pixel_rgb(p, S, A, a.H, a.W, y, x, rgb);
+                mosaic::colour(p.M, rgb, out);
+                uint16_t* o = s_out + tx * kTurnPitch + 3 * (flip_rows ? ye - 1 - y : y - ty0);
+                o[0] = out[0], o[1] = out[1], o[2] = out[2];
+            }
         }
         __syncthreads();
-        if (y < a.y1) store_segment(seg, s_out[ty], n, tx);
-        __syncthreads();
+        uint16_t* dst = static_cast<uint16_t*>(a.dst);
+        for (int j = ty; j < kTW; j += 4) {  // (the same for all 64 lanes of a wave)
+            const int xj = tx0 + j;
+            if (xj < xa || xj >= xb) continue;
+            const int r = flip_cols ? a.p.out_w - 1 - xj : xj;
+            store_segment(dst + ((long long)r * a.p.out_h + c0) * 3, s_out + j * kTurnPitch, 3 * (ye - ty0), tx);
+        }
+    } else if constexpr (Cls == kMirrored) {
+        // The upright walk below with two changes (the window is the frame: x0 = 0, x1 = out_w, dst_y0 = 0).  Row y of D is row
+        // out_h - 1 - y of O with bit 2: the segment pointer walks upward.  With bit 1 the tile's columns [xa, xb) are O's
+        // [out_w - xb, out_w - xa), and a lane writes its pixel to the mirrored slot of the row buffer.
+        const bool flip_rows = a.orientation & orient::kRows, flip_cols = a.orientation & orient::kCols;
+        const long long row_elems = 3LL * a.p.out_w, step = flip_rows ? -4 * row_elems : 4 * row_elems;
+        const int slot = flip_cols ? xb - 1 - x : x - xa;
+        uint16_t* seg = static_cast<uint16_t*>(a.dst) + (flip_rows ? a.p.out_h - 1 - (ty0 + ty) : ty0 + ty) * row_elems +
+                        3 * (flip_cols ? a.p.out_w - xb : xa);
+        for (int q = 0; q < kRowsPerLane; ++q, seg += step) {
+            const int y = ty0 + ty + 4 * q;  // (the same for all 64 lanes of a wave)
+            if (y < a.y1 && x >= xa && x < xb) {
+                int rgb[3];
+                uint16_t out[3];
+                Pattern::pixel_rgb(p, S, A, a.H, a.W, y, x, rgb);
+                mosaic::colour(p.M, rgb, out);
+                uint16_t* o = s_out[ty] + 3 * slot;
+                o[0] = out[0], o[1] = out[1], o[2] = out[2];
+            }
+            __syncthreads();
+            if (y < a.y1) store_segment(seg, s_out[ty], n, tx);
+            __syncthreads();
+        }
+    } else {
+        // the wave's row segment, n contiguous elements of dst: that of its first row, then four rows on per step (one 64-bit product
+        // here, none per row)
+        const long long row_elems = 3LL * (a.x1 - a.x0);
+        OutT<F32>* seg = static_cast<OutT<F32>*>(a.dst) + (ty0 + ty - a.dst_y0) * row_elems + 3 * (xa - a.x0);
+        for (int q = 0; q < kRowsPerLane; ++q, seg += 4 * row_elems) {
+            const int y = ty0 + ty + 4 * q;  // (the same for all 64 lanes of a wave)
+            if (y < a.y1 && x >= xa && x < xb) {
+                int rgb[3];
+                uint16_t out[3];
+                Pattern::pixel_rgb(p, S, A, a.H, a.W, y, x, rgb);
+                mosaic::colour(p.M, rgb, out);
+                OutT<F32>* o = s_out[ty] + 3 * (x - xa);
+                o[0] = finish_sample<F32>(a, out[0]), o[1] = finish_sample<F32>(a, out[1]), o[2] = finish_sample<F32>(a, out[2]);
+            }
+            __syncthreads();
+            if (y < a.y1) store_segment(seg, s_out[ty], n, tx);
+            __syncthreads();
+        }
     }
 }
 
-template <typename Pattern, bool F32>
+// Oriented: the lane stores its pixel where orient::from_frame puts it in O (a quarter or a ninth of the samples: no transpose buffer).
+template <typename Pattern, bool F32, bool Oriented = false>
 __global__ __launch_bounds__(256) void mosaic_reduced_kernel(const MosaicArgs<typename Pattern::Params> a) {
     __shared__ typename Pattern::Params s_p;  // (as above)
     if constexpr (Pattern::kParamsInLds) {
@@ -229,16 +296,25 @@ __global__ __launch_bounds__(256) void mosaic_reduced_kernel(const MosaicArgs<ty
     uint16_t out[3];
     Pattern::reduced_rgb(a, p, y, x, rgb);
     mosaic::colour(p.M, rgb, out);
-    OutT<F32>* d = static_cast<OutT<F32>*>(a.dst) + ((long long)(y - a.dst_y0) * (a.x1 - a.x0) + (x - a.x0)) * 3;
+    OutT<F32>* d;
+    if constexpr (Oriented) {
+        static_assert(!F32, "the float epilogue is upright");
+        int r, c;
+        orient::from_frame(a.orientation, a.p.out_h, a.p.out_w, y, x, r, c);
+        d = static_cast<OutT<F32>*>(a.dst) + ((long long)r * orient::cols(a.orientation, a.p.out_h, a.p.out_w) + c) * 3;
+    } else {
+        d = static_cast<OutT<F32>*>(a.dst) + ((long long)(y - a.dst_y0) * (a.x1 - a.x0) + (x - a.x0)) * 3;
+    }
     d[0] = finish_sample<F32>(a, out[0]), d[1] = finish_sample<F32>(a, out[1]), d[2] = finish_sample<F32>(a, out[2]);
 }
 
 // An entry point: the checks, then one launch.  The window (row0, col0, rows, cols) of the demosaiced frame is what dst holds (none:
-// all of it); [y0, y1) are rows of the window.  `what` names the entry point in messages.
+// all of it); [y0, y1) are rows of the window.  `what` names the entry point in messages.  The oriented entry points (uint16, no
+// window) pass their orientation: [y0, y1) are then rows of O, dst is O, and the launch walks orient::rect_of's rectangle of D.
 template <typename Pattern, bool F32>
 int mosaic_rows(r2f_ctx* ctx, const char* what, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
                 const typename Pattern::Params* params, const int* window, float divisor, float factor, void* dst, int y0, int y1,
-                void* stream) {
+                void* stream, int orientation = 0) {
     constexpr int kMaxSide = 1 << 17;  // (the reduced grid has a block per four rows; indices go through long long)
     constexpr int kMin = Pattern::kMinSide, kReduction = Pattern::kReduction, kReachY = Pattern::kReachY;
     if (!src_rows || !params || !dst || H < kMin || W < kMin || H > kMaxSide || W > kMaxSide || src_pitch < W || src_gy0 < 0 || src_nrows < 0)
@@ -249,31 +325,48 @@ int mosaic_rows(r2f_ctx* ctx, const char* what, const uint16_t* src_rows, int sr
     const bool reduced = Pattern::reduced(p);
     if (p.out_h != (reduced ? H / kReduction : H) || p.out_w != (reduced ? W / kReduction : W))
         return fail(ctx, R2F_EINVAL, "%s: the params are those of another frame size (%s)", what, Pattern::kPlanner);
-    const int row0 = window ? window[0] : 0, col0 = window ? window[1] : 0, rows = window ? window[2] : p.out_h,
+    if (!orient::valid(orientation) || (orientation && (F32 || window)))
+        return fail(ctx, R2F_EINVAL, "%s: orientation %d is not one of 0 .. 7 (LibRaw's sizes.flip bits)", what, orientation);
+    const int frame_rows = orient::rows(orientation, p.out_h, p.out_w);  // (an oriented call has no window: dst is all of O)
+    const int row0 = window ? window[0] : 0, col0 = window ? window[1] : 0, rows = window ? window[2] : frame_rows,
               cols = window ? window[3] : p.out_w;
-    if (row0 < 0 || col0 < 0 || rows <= 0 || cols <= 0 || rows > p.out_h - row0 || cols > p.out_w - col0)
+    if (row0 < 0 || col0 < 0 || rows <= 0 || cols <= 0 || rows > frame_rows - row0 || cols > p.out_w - col0)
         return fail(ctx, R2F_EINVAL, "%s: the window (%d, %d, %d, %d) is empty or not inside the %d x %d frame", what, row0, col0, rows, cols,
                     p.out_h, p.out_w);
     if (y0 < 0 || y1 > rows || y0 > y1) return fail(ctx, R2F_EINVAL, "%s: rows [%d, %d) not inside the output's [0, %d)", what, y0, y1, rows);
     if (F32 && (!(divisor > 0.f) || (reinterpret_cast<uintptr_t>(dst) & 3u)))
         return fail(ctx, R2F_EINVAL, "%s: a positive divisor and a 4-byte aligned destination are required", what);
     if (y0 == y1) return R2F_OK;
-    const int fy0 = row0 + y0, fy1 = row0 + y1;  // the rows of the demosaiced frame
-    const int lo = reduced ? kReduction * fy0 : (fy0 - kReachY > 0 ? fy0 - kReachY : 0),
-              hi = reduced ? kReduction * fy1 : (fy1 + kReachY < H ? fy1 + kReachY : H);
+    // the rectangle of the demosaiced frame this call takes: the window's rows [y0, y1) over its columns, or what O's rows hold
+    const orient::Rect d = orientation ? orient::rect_of(orientation, p.out_h, p.out_w, y0, y1) : orient::Rect{row0 + y0, row0 + y1, col0, col0 + cols};
+    int lo, hi;
+    orient::source_rows(orientation, d, H, kReachY, reduced ? kReduction : 0, lo, hi);
     if (lo < src_gy0 || (long long)hi > (long long)src_gy0 + src_nrows)
         return fail(ctx, R2F_EINVAL, "%s: rows [%d, %d) read mosaic rows [%d, %d), the source window holds [%d, %lld)", what, y0, y1, lo, hi,
                     src_gy0, (long long)src_gy0 + src_nrows);
     const int wide = ((reinterpret_cast<uintptr_t>(src_rows) & 3u) == 0 && src_pitch % 2 == 0) ? 1 : 0;
     const MosaicArgs<typename Pattern::Params> a{
-        src_rows, src_gy0, (long long)src_pitch, H, W, p, dst, fy0, fy1, wide, row0, col0, col0 + cols, divisor, factor};
+        src_rows, src_gy0, (long long)src_pitch, H, W, p, dst, d.y0, d.y1, wide, orientation ? 0 : row0, d.x0, d.x1, divisor, factor, orientation};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (reduced) {
-        launch_k(mosaic_reduced_kernel<Pattern, F32>, dim3((cols + 63) / 64, (y1 - y0 + 3) / 4), dim3(64, 4), 0, s, a);
-    } else {
-        const int tiles_x = (col0 + cols - 1) / kTW - col0 / kTW + 1;  // (the whole frame: ceil(W / 64), tiles from column 0)
-        launch_k(mosaic_full_kernel<Pattern, F32>, dim3(tiles_x, (y1 - y0 + kTH - 1) / kTH), dim3(64, 4), 0, s, a);
+    const dim3 reduced_grid((d.x1 - d.x0 + 63) / 64, (d.y1 - d.y0 + 3) / 4);
+    // (the whole frame: ceil(W / 64) tiles from column 0)
+    const dim3 full_grid((d.x1 - 1) / kTW - d.x0 / kTW + 1, (d.y1 - d.y0 + kTH - 1) / kTH);
+    if constexpr (!F32) {
+        if (orientation) {
+            if (reduced)
+                launch_k(mosaic_reduced_kernel<Pattern, false, true>, reduced_grid, dim3(64, 4), 0, s, a);
+            else if (orientation & orient::kSwap)
+                launch_k(mosaic_full_kernel<Pattern, false, kTurned>, full_grid, dim3(64, 4), 0, s, a);
+            else
+                launch_k(mosaic_full_kernel<Pattern, false, kMirrored>, full_grid, dim3(64, 4), 0, s, a);
+            R2F_HIP(ctx, take_launch_status());
+            return R2F_OK;
+        }
     }
+    if (reduced)
+        launch_k(mosaic_reduced_kernel<Pattern, F32>, reduced_grid, dim3(64, 4), 0, s, a);
+    else
+        launch_k(mosaic_full_kernel<Pattern, F32>, full_grid, dim3(64, 4), 0, s, a);
     R2F_HIP(ctx, take_launch_status());
     return R2F_OK;
 }

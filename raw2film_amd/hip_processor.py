@@ -345,7 +345,10 @@ class HipProcessor:
         (payload.mosaic_upload_bounds) and is demosaiced straight into the float frame (r2f_demosaic_f32).
         A raw2film_amd.raw.XTransProfile in its place: `src` is an X-Trans mosaic (6 x 6 array, at least 6 x 6 samples), demosaiced by
         r2f_demosaic_xtrans_u16 -- the project's own interpolation, not LibRaw's; `demosaic` holds the r2f_xtrans_params; half_size
-        yields a third of the mosaic's sides; such a payload takes the one-piece path (it does not stream yet)."""
+        yields a third of the mosaic's sides; such a payload takes the one-piece path (it does not stream yet).
+        A profile with an `orientation` (LibRaw's sizes.flip): the demosaic writes the frame that way round (r2f_demosaic_oriented_u16),
+        so every crop-derived number is that of the oriented frame, as upstream's is; the `demosaic` step then carries
+        `orientation` (an upright payload has no such key), and the payload takes the one-piece path."""
         on_device = exposure_on_device(exposure)
         phase1.check_profiles(raw_profile, lens_profile, lens_correction, cam, lens)
         # _internal (load_image_texture: the payload never leaves this object): no alpha plane, and the clamp of
@@ -356,7 +359,7 @@ class HipProcessor:
         demosaic_params = lens_params = None
         if raw_profile is not None:  # the crops are those of the demosaiced frame, which is uint16
             demosaic_params = raw_profile.plan(rows, cols, half_size)
-            rows, cols = demosaic_params.out_h, demosaic_params.out_w
+            rows, cols = raw_profile.oriented_shape(rows, cols, half_size)  # (the params' out_h, out_w, the way round the sensor was held)
         on_device, exposure, exposure_rejected = phase1.exposure_mode(exposure, on_device, is_u16, raw_profile is not None, rotation,
                                                                       rotate_times)
         if lens_correction and lens_profile is not None:
@@ -403,7 +406,9 @@ class HipProcessor:
             # the lens step (first of the device pre-path steps)
             **({"lens": {"params": lens_params, **crops.lens}} if lens_params is not None else {}),
             # `image_array` is a Bayer mosaic (ahead of all)
-            **({"demosaic": {"params": demosaic_params, **crops.demosaic}} if demosaic_params is not None else {}),
+            **({"demosaic": {"params": demosaic_params, **crops.demosaic,
+                             **({"orientation": raw_profile.orientation} if raw_profile.orientation else {})}}
+               if demosaic_params is not None else {}),
         }
 
     # ------------------------------------------------------------------ the operator surface
@@ -445,7 +450,8 @@ class HipProcessor:
         (the device's statistic is the whole demosaiced frame's), turned, or with a lens_profile it is demosaiced whole, and
         `stream_rejected` of an export names the demosaic step and the reason.  With a raw2film_amd.raw.XTransProfile `src` is an
         X-Trans mosaic (r2f_demosaic_xtrans_u16: the project's own interpolation; half_size yields a third); it is always demosaiced
-        whole ("X-Trans mosaics do not stream yet")."""
+        whole ("X-Trans mosaics do not stream yet").  A profile's `orientation` turns the demosaiced frame the way the sensor was
+        held before anything else sees it (crops, exposure statistic, lens step, rotate_times); such a mosaic is demosaiced whole."""
         settings = dict(locals())  # every keyword of the signature (the unknown ones in `_` aside), named nowhere else
         exposure_on_device(exposure)  # (any string but "device" raises before any work starts)
         settings["output_bits"] = check_output_bits(output_bits, dst_texture)
@@ -739,8 +745,9 @@ class HipProcessor:
                                 frame_samples=phase1.mosaic_frame_samples(src, settings["half_size"],
                                                                           settings["frame_width"] / settings["frame_height"],
                                                                           settings["flip"], settings["zoom"],
-                                                                          getattr(profile, "reduction", 2)) if mosaic else None,
-                                xtrans=isinstance(profile, phase1.XTransProfile))
+                                                                          getattr(profile, "reduction", 2),
+                                                                          getattr(profile, "orientation", 0)) if mosaic else None,
+                                xtrans=isinstance(profile, phase1.XTransProfile), orientation=getattr(profile, "orientation", 0))
 
     @staticmethod
     def _refuse_textures(what, settings, hint=""):
@@ -1096,8 +1103,8 @@ class HipProcessor:
         demosaic_step = cpu_payload.get("demosaic")
         if demosaic_step:  # a mosaic: LibRaw's share of raw_to_linear on the device -> the uint16 frame of the lines below
             demosaic = getattr(self.ctx, MOSAIC_KINDS[type(demosaic_step["params"])][0])
-            image = cut_and_turn(demosaic(image.contiguous(), demosaic_step["params"]), demosaic_step["window"],
-                                 demosaic_step["rotate_times"], dims=(0, 1))
+            image = cut_and_turn(demosaic(image.contiguous(), demosaic_step["params"], orientation=demosaic_step.get("orientation", 0)),
+                                 demosaic_step["window"], demosaic_step["rotate_times"], dims=(0, 1))
         if image.dtype in (torch.int16, torch.uint16):  # a decoded 16-bit frame: raw_conversion.py:50-52 on the device
             if cpu_payload.get("u16_factor") is None:
                 raise ValueError("a uint16 payload needs its exposure factor (`u16_factor`, extract_image_data_cpu sets it)")

@@ -2,7 +2,8 @@
 load settings before anything is uploaded, and why a payload does not stream in row bands.  Pure host work: no torch, no
 processor state.
 
-The crop rule (plan_crops states it once).  There is one aspect box `a` of the frame -- for a mosaic, of the demosaiced frame.
+The crop rule (plan_crops states it once).  There is one aspect box `a` of the frame -- for a mosaic, of the demosaiced frame, the
+way round its profile's orientation puts it.
 Without a free rotation there is one full window, `a` composed with the zoom box, and k = rotate_times % 4 quarter turns; with
 one, the warp owns its own window (rotation_plan composed with the zoom box) and k, and what is left to cut ahead of it is `a`.
 Either way the cut (and the turns that go with it) is applied once, by the last step that still sees the whole frame:
@@ -30,10 +31,14 @@ DEVICE_EXPOSURE = "device"  # exposure="device": the auto exposure of a uint16 f
                             # payload carries in place of its float `u16_factor`
 
 
-def mosaic_rejection(stops, rotate_times, lens, samples, xtrans=False):
+def mosaic_rejection(stops, rotate_times, lens, samples, xtrans=False, orientation=0):
     """Why a mosaic is demosaiced whole instead of band by band (r2f_demosaic_f32), or None.  stops: the exposure is given in
     stops; samples: rows x cols x 3 of the window of the demosaiced frame that the pipeline takes, or None when nobody cut one;
-    xtrans: the mosaic is an X-Trans one (r2f_demosaic_xtrans_u16 has the row-range contract, the band loop does not use it yet)."""
+    xtrans: the mosaic is an X-Trans one (r2f_demosaic_xtrans_u16 has the row-range contract, the band loop does not use it yet);
+    orientation: the profile's (the fused demosaic-to-float of the band loop is upright; a turned band reads every mosaic row)."""
+    if orientation:
+        return _DEMOSAIC_REJECTED + (f"orientation = {orientation!r}: an oriented mosaic is demosaiced in one piece "
+                                     "(r2f_demosaic_oriented_u16), the band loop's demosaic is upright")
     if xtrans:
         return _DEMOSAIC_REJECTED + "X-Trans mosaics do not stream yet"
     if not stops:
@@ -85,7 +90,8 @@ def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canv
     if step:
         window = step.get("window")
         why = mosaic_rejection(isinstance(payload.get("u16_factor"), float), step.get("rotate_times") or 0, payload.get("lens"),
-                               None if window is None else int(window[2]) * int(window[3]) * 3, is_xtrans(step.get("params")))
+                               None if window is None else int(window[2]) * int(window[3]) * 3, is_xtrans(step.get("params")),
+                               step.get("orientation", 0))
         if why is not None:
             return why
     if payload.get("lens"):
@@ -110,16 +116,16 @@ def is_xtrans(params) -> bool:
 
 
 def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="No", highlight_burn=0.0, lens=False, demosaic=False, *,
-                     stops=False, rotate_times=0, frame_samples=None, xtrans=False):
+                     stops=False, rotate_times=0, frame_samples=None, xtrans=False, orientation=0):
     """Why process(src, cache=False) renders a frame in one piece before it extracts its payload (stream_rejection and plan_bands
     come after that), or None.  lens: the call corrects the lens (lens_correction with a lens_profile); demosaic: its source is a
     mosaic (raw_profile), for which stops says that the exposure is given in stops, rotate_times is the call's, frame_samples the
-    samples of the window of the demosaiced frame that the pipeline takes (mosaic_frame_samples), and xtrans that the profile is an
-    XTransProfile (which does not stream yet)."""
+    samples of the window of the demosaiced frame that the pipeline takes (mosaic_frame_samples), xtrans that the profile is an
+    XTransProfile (which does not stream yet), and orientation the profile's (not 0: the one-piece path)."""
     if stream_bands <= 1:
         return f"stream_bands = {stream_bands}"
     if demosaic:
-        why = mosaic_rejection(stops, rotate_times, lens, frame_samples, xtrans)
+        why = mosaic_rejection(stops, rotate_times, lens, frame_samples, xtrans, orientation)
         if why is not None:
             return why
     if lens:
@@ -134,13 +140,16 @@ def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="
     return None
 
 
-def mosaic_frame_samples(src, half_size, aspect, flip, zoom, reduction=2):
+def mosaic_frame_samples(src, half_size, aspect, flip, zoom, reduction=2, orientation=0):
     """host_stream_gate's frame_samples for a mosaic `src`: rows x cols x 3 of the window that the aspect and zoom crops keep of
     its demosaiced frame (plan_crops without a rotation, which the gate refuses by itself), or None when `src` is no 2-D array.
-    reduction: what half_size divides the mosaic's sides by, as its profile states it (2 for a Bayer quad, 3 for X-Trans cells)."""
+    reduction: what half_size divides the mosaic's sides by, as its profile states it (2 for a Bayer quad, 3 for X-Trans cells);
+    orientation: the profile's -- with bit 4 the crops see the frame with its sides swapped."""
     if not isinstance(src, np.ndarray) or src.ndim != 2:
         return None
     rows, cols = (src.shape[0] // reduction, src.shape[1] // reduction) if half_size else src.shape
+    if int(orientation) & 4:
+        rows, cols = cols, rows
     if rows < 1 or cols < 1:
         return None
     window = plan_crops(rows, cols, True, aspect, flip, zoom, 0.0, 0, False, False, True).demosaic["window"]

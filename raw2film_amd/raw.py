@@ -46,12 +46,13 @@ def _matrix(matrix, who):
 
 
 class _MosaicProfile:
-    """What the two profiles share: the normalisation of black, multipliers and matrix, and `plan()`.  A profile class states
+    """What the two profiles share: the normalisation of black, multipliers, matrix and orientation, `oriented_shape()` and `plan()`.  A profile class states
     `_sites` (black levels per period of its array), `_multiplier_counts`, its params type, its planner's name and `to_c` (the C
     profile)."""
 
     def _normalise(self):
-        """black, multipliers and matrix as tuples of floats, checked (frozen: set once, from __post_init__)."""
+        """black, multipliers and matrix as tuples of floats and the orientation as an int, checked (frozen: set once, from
+        __post_init__)."""
         who = type(self).__name__
         black = self.black
         if isinstance(black, numbers.Real) and not isinstance(black, bool):
@@ -64,6 +65,16 @@ class _MosaicProfile:
             raise ValueError(f"{who}.multipliers must lie in (0, 1024], got {self.multipliers!r}")
         for name, value in (("black", black), ("multipliers", mul), ("matrix", _matrix(self.matrix, who))):
             object.__setattr__(self, name, value)
+        o = self.orientation
+        if isinstance(o, bool) or not isinstance(o, numbers.Integral) or not 0 <= o <= 7:
+            raise ValueError(f"{who}.orientation must be an integer 0 .. 7 (LibRaw's sizes.flip bits), got {o!r}")
+        object.__setattr__(self, "orientation", int(o))
+
+    def oriented_shape(self, H: int, W: int, half_size: bool = False) -> tuple:
+        """(rows, cols) of the frame the demosaic of an H x W mosaic yields with this profile's orientation: the demosaiced frame's
+        sides (the mosaic's, divided by `reduction` and rounded down with half_size), swapped where bit 4 is set."""
+        rows, cols = (int(H) // self.reduction, int(W) // self.reduction) if half_size else (int(H), int(W))
+        return (cols, rows) if self.orientation & 4 else (rows, cols)
 
     def plan(self, H: int, W: int, half_size: bool = False):
         """The params of an H x W mosaic (no GPU: r2f_demosaic_params / r2f_xtrans_params); ValueError for what the planner refuses
@@ -83,11 +94,16 @@ class RawProfile(_MosaicProfile):
     pattern: "RGGB" | "BGGR" | "GRBG" | "GBRG", the colours of the quad at (0, 0) in reading order.
     black: one level for every site, or 4 per site of the quad (k = (y & 1) * 2 + (x & 1)); integers in [0, 65535].
     multipliers: (r, g, b), or 4 per site; each in (0, 1024].  They hold the white balance AND the scale to 16 bits.
-    matrix: 3 x 3, rows are the output channels; |entries| <= 64."""
+    matrix: 3 x 3, rows are the output channels; |entries| <= 64.
+    orientation: 0 .. 7, how the sensor was held, as LibRaw's sizes.flip bits (4 swaps the axes, 2 mirrors rows, 1 mirrors
+        columns: 0 upright, 3 180 degrees, 5 90 degrees counter-clockwise, 6 90 degrees clockwise).  The demosaic writes the frame
+        that way round (r2f_demosaic_oriented_u16), and everything behind it -- crops, statistic, lens step, turns -- sees that
+        frame, as upstream's does.  (Not `flip`: process(flip=) is the aspect's.)"""
     pattern: str = "RGGB"
     black: tuple | float = 0
     multipliers: tuple = (1.0, 1.0, 1.0)
     matrix: tuple = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
+    orientation: int = 0
 
     reduction = 2  # what half_size=True divides a mosaic's sides by (no dataclass field: not part of equality, hash or repr)
     _sites, _multiplier_counts = 4, (3, 4)
@@ -123,11 +139,13 @@ class XTransProfile(_MosaicProfile):
     black: one level for every site, or 36 per phase ((y % 6) * 6 + x % 6); integers in [0, 65535].
     multipliers: (r, g, b); each in (0, 1024].  They hold the white balance AND the scale to 16 bits.
     matrix: 3 x 3, rows are the output channels; |entries| <= 64.
+    orientation: 0 .. 7, LibRaw's sizes.flip bits, as RawProfile's (r2f_demosaic_xtrans_oriented_u16).
     half_size=True yields A THIRD of the mosaic's sides (the 3 x 3 cells of the array), not a half: `reduction`."""
     pattern: tuple | str = XTRANS
     black: tuple | float = 0
     multipliers: tuple = (1.0, 1.0, 1.0)
     matrix: tuple = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
+    orientation: int = 0
 
     reduction = 3
     _sites, _multiplier_counts = 36, (3,)
