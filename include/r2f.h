@@ -614,6 +614,65 @@ R2F_API int r2f_demosaic_oriented_u16(r2f_ctx* ctx, const uint16_t* src_rows, in
 R2F_API int r2f_demosaic_xtrans_oriented_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H,
                      int W, const r2f_xtrans_params* params, int orientation, uint16_t* dst_u16_hwc3, int y0, int y1, void* stream);
 
+/* The scale of a mosaic from the sensor's levels and the frame's measured maximum, on the device.  raw_to_linear's raw.postprocess
+ * (raw_conversion.py:38-48) leaves LibRaw's adjust_maximum_thr at its default of 0.75: LibRaw then scales a frame to its largest
+ * black-subtracted sample (its data_maximum) in place of the nominal white level whenever that sample lies between 75 % and 100 % of
+ * the nominal one.  A profile's multipliers hold the white balance AND the scale to 16 bits, so a caller who wants that scale would
+ * have to pass over the whole mosaic on the host; this is that pass on the device, and the multipliers derived from it.
+ * Parity with LibRaw's bytes is UNPINNED like the rest of the demosaic: rawpy is on no machine this project sees.  The arithmetic
+ * follows LibRaw's published raw2image_ex, adjust_maximum and scale_colors; what the tests pin is THIS definition
+ * (tests/levels_model.py restates it in NumPy).
+ *
+ * Data maximum.  The mosaic is uint16 (H, W); P is the array's period, 2 or 6; black[P * P] (int32, each in [0, 65535]) is indexed by
+ * the site's phase (y % P) * P + x % P, as in both definitions above.
+ *   d = max over all sites of max((int)raw(y, x) - black[phase], 0):
+ * an integer in [0, 65535], taken over the WHOLE mosaic, whatever window of the demosaiced frame the pipeline keeps.
+ * Scale.  Inputs: the white balance wb[3] (doubles, finite, > 0), white_level (an integer in [1, 65535]), thr (a double in [0, 1]),
+ * the black table and d.
+ *   m = white_level - min(black); refused when m < 1.
+ *   The threshold follows LibRaw's rule: thr < 0.00001 means no adjustment; thr > 0.99999 means 0.75; otherwise it is thr itself.
+ *   With t = (float)threshold the frame is adjusted if and only if d > 0, d < m and (float)d > fl((float)m * t): one fp32 multiply
+ *   and one fp32 comparison, as in LibRaw's expression.
+ *   m_eff = d when adjusted, else m.
+ *   mul[c] = wb[c] / min(wb) * 65535.0 / m_eff, evaluated in double, left to right.
+ * The planners above round mul[c] to float once and refuse anything outside (0, 1024]; a Bayer profile spreads the three multipliers
+ * over its quad by the pattern. */
+typedef struct r2f_raw_levels {
+    double white_balance[3];
+    int32_t white_level;
+    double adjust_maximum_thr;
+} r2f_raw_levels;
+/* What the Scale steps yield: the multipliers, m_eff, and whether the frame was adjusted (1) or keeps the nominal scale (0). */
+typedef struct r2f_raw_scale {
+    double mul[3];
+    int32_t maximum_used;
+    int32_t adjusted;
+} r2f_raw_scale;
+/* Host planner (raw2film_amd/csrc/r2f_levels_plan.cpp; no GPU, no context): the Scale steps.  black: n_black = 4 or 36 levels as a
+ * profile states them (doubles, integral, in [0, 65535]); data_maximum: d (0 plans the nominal scale).  R2F_EINVAL for a null
+ * pointer, another n_black, a black level, white balance, white level or threshold outside its range (a NaN is outside every range),
+ * data_maximum above 65535 and m < 1; a refusal leaves *out alone. */
+R2F_API int r2f_raw_scale_plan(const r2f_raw_levels* levels, const double* black, int n_black, uint32_t data_maximum, r2f_raw_scale* out);
+/* The data maximum of mosaic rows [y0, y1), folded into a device word: *dst_max = max(*dst_max, d of those rows).  The caller zeroes
+ * the word before the first call; bands in any order and any cut then compose to the whole frame's value, and since an integer
+ * maximum does not depend on order the result is exact and the same on every run.  src_rows: uint16 mosaic rows [src_gy0, src_gy0 +
+ * src_nrows) of the H x W frame on the device, src_pitch samples apart (>= W); black: period * period levels ON THE HOST.  Reads
+ * mosaic rows [y0, y1) and no others; those rows must lie inside the source window, else R2F_EINVAL before any launch.  Writes the 4
+ * bytes of *dst_max and nothing else; y0 == y1 is R2F_OK with no launch.  Refused: a period other than 2 or 6, H or W below the
+ * period, y0 > y1, y0 < 0 or y1 > H, src_pitch < W, a black level outside [0, 65535], null pointers.  The phase is that of the frame
+ * (src_gy0, y0), never that of the buffer or the block; the source's alignment and pitch only select between wider and narrower loads
+ * of the same samples (r2f_demosaic_u16's rule).
+ * One launch of a resident grid: a block walks groups of R2F_MOSAIC_MAX_ROWS rows, a wave per row; a lane loads R2F_MOSAIC_MAX_VEC
+ * samples at a time (16 bytes) behind the up to 7 samples that lead to a 16-byte boundary and ahead of the up to 7 that trail, and
+ * subtracts and folds them as packed 16-bit pairs (subtract with clamp at 0, then max).  A 2 x 2 table is widened to 6 x 6 on the
+ * host, so the kernel knows one period; a block keeps it in LDS and a lane fetches its row's six levels once per row: along a row
+ * the pairs of a lane's vectors cycle through three registers.  The lanes' maxima meet across the wave, then across the block's
+ * waves in LDS, and leave through one atomicMax per block; a block without rows does not touch the word. */
+R2F_API int r2f_mosaic_maximum(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
+                     int period, const int32_t* black, int y0, int y1, uint32_t* dst_max, void* stream);
+/* r2f_mosaic_maximum's widest load in samples and the rows a block walks per step (test shapes are derived from them). */
+enum { R2F_MOSAIC_MAX_VEC = 8, R2F_MOSAIC_MAX_ROWS = 4 };
+
 /* The hand-off from RAW decoding: the last two lines of raw_to_linear (raw_conversion.py:50-52) applied to LibRaw's 16-bit
  * output on the device, so that a decoded frame crosses PCIe as uint16 (6 bytes per pixel) instead of float32 (12 or 16):
  * dst = float(src) / divisor (65535, one correctly rounded fp32 division) * factor (the float32 of 2 ** calc_exposure(...),

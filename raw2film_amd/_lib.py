@@ -18,6 +18,7 @@ LENS_NONE, LENS_POLY3, LENS_POLY5, LENS_PTLENS = 0, 1, 2, 3
 CFA_RGGB, CFA_BGGR, CFA_GRBG, CFA_GBRG = 0, 1, 2, 3
 DEMOSAIC_TILE_W, DEMOSAIC_TILE_H = 64, 32  # R2F_DEMOSAIC_TILE_*
 XTRANS_TILE_W, XTRANS_TILE_H = 64, 32  # R2F_XTRANS_TILE_*
+MOSAIC_MAX_VEC, MOSAIC_MAX_ROWS = 8, 4  # R2F_MOSAIC_MAX_*
 KERNEL_HALATION, KERNEL_MTF, KERNEL_GRAIN = 0, 1, 2
 F_MATRIX, F_HALATION, F_MTF, F_GRAIN, F_GRAIN_MONO, F_BURN, F_IDENTITY_DONE, F_FRAME_RESIDENT = 1, 2, 4, 8, 16, 32, 64, 128
 F_TRACK_RANGE, F_RANGE_VALID = 256, 512
@@ -102,6 +103,14 @@ class XTransParams(C.Structure):  # r2f_xtrans_params: the constants and per-pha
     _fields_ = [("cfa", C.c_uint8 * 36), ("gap", C.c_uint8 * 4 * 36), ("taps", C.c_uint16 * 2 * 36), ("wsum", C.c_uint8 * 2 * 36),
                 ("cell_count", C.c_uint8 * 3 * 4), ("recip", C.c_uint32 * 2 * 36), ("black", C.c_int32 * 36), ("mul", C.c_float * 3),
                 ("M", C.c_float * 9), ("reduced", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32)]
+
+
+class RawLevels(C.Structure):  # r2f_raw_levels (raw2film_amd.raw.RawLevels fills it)
+    _fields_ = [("white_balance", C.c_double * 3), ("white_level", C.c_int32), ("adjust_maximum_thr", C.c_double)]
+
+
+class RawScale(C.Structure):  # r2f_raw_scale: the multipliers of one frame, the maximum they scale to and whether it was the measured one
+    _fields_ = [("mul", C.c_double * 3), ("maximum_used", C.c_int32), ("adjusted", C.c_int32)]
 
 
 _P = C.POINTER
@@ -207,6 +216,12 @@ _SIGNATURES = {
     "r2f_demosaic_xtrans_oriented_u16": (
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(XTransParams), C.c_int, C.c_void_p, C.c_int, C.c_int,
+         C.c_void_p],
+    ),
+    "r2f_raw_scale_plan": (C.c_int, [_P(RawLevels), _P(C.c_double), C.c_int, C.c_uint32, _P(RawScale)]),
+    "r2f_mosaic_maximum": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P(C.c_int32), C.c_int, C.c_int, C.c_void_p,
          C.c_void_p],
     ),
     "r2f_resize_lanczos4_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

@@ -562,15 +562,18 @@ class HipContext:
                                                self._stream()))
         return out
 
-    def _check_mosaic(self, mosaic, params, what, params_type):
-        """A demosaic's view of its source -> (H, W, the params of `params_type`, planned from a profile where it was given one)."""
+    def _mosaic_size(self, mosaic, what, m):
+        """A mosaic as the entry points take it: uint16 or int16 bits, (H, W) of at least m x m samples, pitched rows allowed -> (H, W)."""
         torch = self._torch
-        m = MOSAIC_KINDS[params_type][1]
         if not (isinstance(mosaic, torch.Tensor) and mosaic.is_cuda and mosaic.dtype in (torch.uint16, torch.int16) and mosaic.dim() == 2
                 and mosaic.shape[0] >= m and mosaic.shape[1] >= m and mosaic.stride(1) == 1 and mosaic.stride(0) >= mosaic.shape[1]):
             raise ValueError(f"{what} needs a uint16 (H, W) CUDA mosaic of at least {m} x {m} samples with contiguous rows")
         self._same_device(mosaic, "mosaic")
-        H, W = int(mosaic.shape[0]), int(mosaic.shape[1])
+        return int(mosaic.shape[0]), int(mosaic.shape[1])
+
+    def _check_mosaic(self, mosaic, params, what, params_type):
+        """A demosaic's view of its source -> (H, W, the params of `params_type`, planned from a profile where it was given one)."""
+        H, W = self._mosaic_size(mosaic, what, MOSAIC_KINDS[params_type][1])
         return H, W, params if isinstance(params, params_type) else params.plan(H, W)
 
     def _demosaic(self, what, fn, params_type, mosaic, params, out, rows, window=None, decode=None, orientation=0):
@@ -629,6 +632,39 @@ class HipContext:
         reads the rows its contract names and no others.  rows = (y0, y1): only those rows of the window are written."""
         return self._demosaic("demosaic_f32", self._lib.r2f_demosaic_f32, _lib.DemosaicParams, mosaic, params, out, rows, window,
                               (float(np.float32(divisor)), float(np.float32(factor))))
+
+    def mosaic_maximum(self, mosaic, profile_or_black, period=None, rows=None, out=None):
+        """The data maximum of include/r2f.h (r2f_mosaic_maximum): the largest black-subtracted sample, clamped at 0, of a uint16
+        (H, W) CUDA mosaic (int16 tensors are read as the same bits; rows may be pitched) -> int, read back from the device (4
+        bytes, one synchronisation of the stream).  What a deferred profile's `resolve` takes.
+        profile_or_black: a RawProfile or XTransProfile (its black table and its array's period), or period * period black levels
+        in [0, 65535] with `period` 2 or 6 (default: 2 for 4 levels, 6 for 36).
+        rows = (y0, y1): only those mosaic rows are read (default: all).
+        out: a one-element int32 or uint32 CUDA tensor the maximum is folded into -- out = max(out, d of the rows) -- in place of
+        a word of this call's own that starts at 0; `out` is then returned, and nothing is read back or waited for: bands in any
+        order and any cut compose to the whole frame's value."""
+        torch = self._torch
+        black = getattr(profile_or_black, "black", profile_or_black)
+        try:
+            black = [int(b) for b in black]
+        except (TypeError, ValueError):
+            raise ValueError(f"mosaic_maximum: a profile or a sequence of black levels is required, got {profile_or_black!r}") from None
+        if period is None:
+            period = {4: 2, 36: 6}.get(len(black))
+        if period not in (2, 6) or len(black) != period * period:
+            raise ValueError(f"mosaic_maximum: {len(black)} black levels with period {period!r}; 4 go with period 2 and 36 with period 6")
+        H, W = self._mosaic_size(mosaic, "mosaic_maximum", period)
+        word = out
+        if word is None:
+            word = torch.zeros(1, dtype=torch.int32, device=self.device)
+        elif not (isinstance(word, torch.Tensor) and word.is_cuda and word.dtype in (torch.int32, torch.uint32) and word.numel() == 1):
+            raise ValueError("mosaic_maximum: out must be a one-element int32 or uint32 CUDA tensor")
+        else:
+            self._same_device(word, "out")
+        y0, y1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
+        self._check(self._lib.r2f_mosaic_maximum(self._h, mosaic.data_ptr(), 0, H, int(mosaic.stride(0)), H, W, period,
+                                                 (C.c_int32 * len(black))(*black), y0, y1, word.data_ptr(), self._stream()))
+        return int(word.item()) if out is None else out
 
     def decode_u16(self, image_u16, factor: float, divisor: float = 65535.0, out=None):
         """raw_to_linear's last two lines (raw_conversion.py:50-52) on the device: float32(u) / divisor * float32(factor) for a

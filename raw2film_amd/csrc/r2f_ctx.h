@@ -242,6 +242,18 @@ int fail(r2f_ctx* ctx, int code, const char* fmt, ...);
         if (e_ != hipSuccess) return fail(ctx, R2F_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// The multiprocessors of the context's device, asked for once: what the resident grids (the FFT's column walk, r2f_mosaic_maximum)
+// are sized by.
+inline int device_cu_count(r2f_ctx* ctx, int* out) {
+    if (!ctx->fft.cu_count) {
+        int n = 0;
+        R2F_HIP(ctx, hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, ctx->device));
+        ctx->fft.cu_count = n > 0 ? n : 256;
+    }
+    *out = ctx->fft.cu_count;
+    return R2F_OK;
+}
+
 // Every entry point that touches HIP binds the context's device for the duration of the call and puts the caller's
 // current device back on return: two contexts on two GPUs can be driven from one thread (and torch's notion of the current
 // device is left alone).

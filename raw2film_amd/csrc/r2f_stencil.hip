@@ -208,13 +208,10 @@ static int run_stencil_fft(r2f_ctx* ctx, int which, const int* chans, int nch, c
     a.kreal = kreal ? 1 : 0;
     a.oy = kreal ? a.ay : 0;
     a.ox = kreal ? a.ax : 0;
-    if (!ctx->fft.cu_count) {
-        int n = 0;
-        R2F_HIP(ctx, hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, ctx->device));
-        ctx->fft.cu_count = n > 0 ? n : 256;
-    }
+    int cus = 0;
+    if (const int rc = device_cu_count(ctx, &cus)) return rc;
     a.cols_walk = ctx->opt.fft_cols_walk;
-    a.cols_slots = 2 * ctx->fft.cu_count;
+    a.cols_slots = 2 * cus;
     int rc = ctx->fft.s1.reserve(ctx, img * sizeof(double2), Grow::SyncGeneration);
     if (rc) return rc;
     for (int i = 0; i < nch; ++i) {

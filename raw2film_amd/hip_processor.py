@@ -174,6 +174,10 @@ class HipProcessor:
         self.exposure_rejected = None
         # why the last export, or the last call that tried the row-band path, rendered its frame in one piece; None: it streamed
         self.stream_rejected = None
+        # a deferred profile's resolved scale ({"data_maximum", "maximum_used", "adjusted"}) of the frame the last process /
+        # process_preloaded / submit_preloaded / export call rendered -- a cached frame's is kept with the frame, which is not measured
+        # again --; None when that frame's profile was numeric (streamed or in one piece), or it was no mosaic
+        self.last_raw_scale = None
         self.last_stage_ms = None  # process()'s wall clock per stage with `profile_stages` on (bench.py's host_device_copies)
         self._load_stage_ms = None  # ... load_image_texture's share of it, until process() folds it in
         # the frame cache (load_image_texture): (frame, layout, payload geometry) kept on the device, a weak reference to its array, its load parameters
@@ -348,7 +352,11 @@ class HipProcessor:
         yields a third of the mosaic's sides; such a payload takes the one-piece path (it does not stream yet).
         A profile with an `orientation` (LibRaw's sizes.flip): the demosaic writes the frame that way round (r2f_demosaic_oriented_u16),
         so every crop-derived number is that of the oriented frame, as upstream's is; the `demosaic` step then carries
-        `orientation` (an upright payload has no such key), and the payload takes the one-piece path."""
+        `orientation` (an upright payload has no such key), and the payload takes the one-piece path.
+        A deferred profile (its multipliers are a raw2film_amd.raw.RawLevels): `params` are provisional, those of the nominal
+        scale, and the `demosaic` step carries the profile under `levels` (a numeric profile's step has no such key).  Phase 2
+        measures the uploaded mosaic's data maximum (r2f_mosaic_maximum), resolves the profile with it and plans the params the
+        demosaic runs with; `last_raw_scale` then holds the numbers.  Such a payload takes the one-piece path."""
         on_device = exposure_on_device(exposure)
         phase1.check_profiles(raw_profile, lens_profile, lens_correction, cam, lens)
         # _internal (load_image_texture: the payload never leaves this object): no alpha plane, and the clamp of
@@ -407,7 +415,8 @@ class HipProcessor:
             **({"lens": {"params": lens_params, **crops.lens}} if lens_params is not None else {}),
             # `image_array` is a Bayer mosaic (ahead of all)
             **({"demosaic": {"params": demosaic_params, **crops.demosaic,
-                             **({"orientation": raw_profile.orientation} if raw_profile.orientation else {})}}
+                             **({"orientation": raw_profile.orientation} if raw_profile.orientation else {}),
+                             **({"levels": raw_profile} if raw_profile.deferred else {})}}
                if demosaic_params is not None else {}),
         }
 
@@ -451,11 +460,14 @@ class HipProcessor:
         `stream_rejected` of an export names the demosaic step and the reason.  With a raw2film_amd.raw.XTransProfile `src` is an
         X-Trans mosaic (r2f_demosaic_xtrans_u16: the project's own interpolation; half_size yields a third); it is always demosaiced
         whole ("X-Trans mosaics do not stream yet").  A profile's `orientation` turns the demosaiced frame the way the sensor was
-        held before anything else sees it (crops, exposure statistic, lens step, rotate_times); such a mosaic is demosaiced whole."""
+        held before anything else sees it (crops, exposure statistic, lens step, rotate_times); such a mosaic is demosaiced whole.
+        A profile whose multipliers are a raw2film_amd.raw.RawLevels is deferred: the uploaded mosaic's data maximum is measured on
+        the device (r2f_mosaic_maximum) and the profile resolved with it ahead of the demosaic -- LibRaw's adjust_maximum rule,
+        parity unpinned; `last_raw_scale` holds the numbers, a cached frame keeps them.  Such a mosaic is demosaiced whole too."""
         settings = dict(locals())  # every keyword of the signature (the unknown ones in `_` aside), named nowhere else
         exposure_on_device(exposure)  # (any string but "device" raises before any work starts)
         settings["output_bits"] = check_output_bits(output_bits, dst_texture)
-        self.exposure_rejected = None
+        self.exposure_rejected = self.last_raw_scale = None
         for k in _PROCESS_POSITIONAL:
             del settings[k]
         # load_image_texture's share; prepare() and the render take what they need of all of them and swallow the rest
@@ -485,6 +497,7 @@ class HipProcessor:
             # load parameters do not change -- a re-render with other film settings neither prepares nor uploads it again
             self.load_image_texture(src, **load)
         image, layout, payload = self._texture
+        self.last_raw_scale = payload.get("raw_scale")  # (the frame's own: a cached frame was not measured again)
         if prof:
             self._torch.cuda.synchronize(self.device)
             t_loaded = time.perf_counter()
@@ -577,10 +590,11 @@ class HipProcessor:
     def prepare_gpu_textures(self, cpu_payload):
         """PHASE 2's stateful half (gpu_processor.py:785-790): upload the payload's frame and run the device pre-path on it
         (uint16 conversion, free rotation, chroma NR, preview scaling); the result is the frame the pipeline reads."""
+        self.last_raw_scale = None
         image, layout = self._upload_payload(cpu_payload)
         # (what is kept next to the device frame is the payload's geometry, not its host frame: the processor must not keep a
-        # 1.2 GB decode buffer alive)
-        self._texture = (image, layout, {k: v for k, v in cpu_payload.items() if k != "image_array"})
+        # 1.2 GB decode buffer alive; and the scale a deferred profile resolved to, which belongs to this frame: `raw_scale`)
+        self._texture = (image, layout, {**{k: v for k, v in cpu_payload.items() if k != "image_array"}, "raw_scale": self.last_raw_scale})
         self.image_param_dict = None  # (a payload from outside: no load parameters to compare the next process() with)
         self._texture_src = None
 
@@ -628,7 +642,7 @@ class HipProcessor:
         "cpu" -- like CpuProcessor.process (cpu_processor.py:411-412), the finished frame, canvas included, is scaled to the
         requested resolution (INTER_AREA down, LANCZOS4 up).  dst_texture / histogram_texture, output_bits: see process()."""
         check_output_bits(settings.get("output_bits", 8), dst_texture)
-        self.exposure_rejected = None
+        self.exposure_rejected = self.last_raw_scale = None
         if dst_texture is None and histogram_texture is None and self.stream_bands > 1:
             res = self._stream_payload(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, **settings)
             if res is not None:  # a large frame without a device pre-path: through the pipeline in row bands while it arrives
@@ -714,7 +728,7 @@ class HipProcessor:
         textures, and with stream=True the format's reasons, the processor's `stream_bands`, the payload's.  Then the row-band
         path into fmt.sink where nothing refused it, else the one-piece render into fmt.whole."""
         what = f"process_{fmt.name}" if payload is None else f"process_preloaded_{fmt.name}"
-        self.exposure_rejected = self.stream_rejected = None
+        self.exposure_rejected = self.stream_rejected = self.last_raw_scale = None
         self._refuse_textures(what, settings, " (use process() for the preview)" if payload is None else "")
         early = next((why for why in fmt.early if why), None) if stream else None
         if payload is None:
@@ -747,7 +761,8 @@ class HipProcessor:
                                                                           settings["flip"], settings["zoom"],
                                                                           getattr(profile, "reduction", 2),
                                                                           getattr(profile, "orientation", 0)) if mosaic else None,
-                                xtrans=isinstance(profile, phase1.XTransProfile), orientation=getattr(profile, "orientation", 0))
+                                xtrans=isinstance(profile, phase1.XTransProfile), orientation=getattr(profile, "orientation", 0),
+                                levels=bool(getattr(profile, "deferred", False)))
 
     @staticmethod
     def _refuse_textures(what, settings, hint=""):
@@ -1044,7 +1059,7 @@ class HipProcessor:
         reference's queue.write_texture / read_texture pair serialises."""
         check_output_bits(settings.get("output_bits", 8))
         torch = self._torch
-        self.exposure_rejected = None
+        self.exposure_rejected = self.last_raw_scale = None
         src = cpu_payload.get("image_array")
         if self.stream_bands > 1 and not (isinstance(src, torch.Tensor) and (src.is_cuda or src.is_pinned())):
             # a large frame in ordinary (pageable) host memory: its copy blocks this thread, so nothing of the next frame's host work
@@ -1102,8 +1117,19 @@ class HipProcessor:
 
         demosaic_step = cpu_payload.get("demosaic")
         if demosaic_step:  # a mosaic: LibRaw's share of raw_to_linear on the device -> the uint16 frame of the lines below
-            demosaic = getattr(self.ctx, MOSAIC_KINDS[type(demosaic_step["params"])][0])
-            image = cut_and_turn(demosaic(image.contiguous(), demosaic_step["params"], orientation=demosaic_step.get("orientation", 0)),
+            params = demosaic_step["params"]
+            demosaic = getattr(self.ctx, MOSAIC_KINDS[type(params)][0])
+            image = image.contiguous()
+            deferred = demosaic_step.get("levels")
+            if deferred is not None:
+                # the scale is the frame's own: the whole uploaded mosaic's data maximum (one read of it, 4 bytes back, the one
+                # synchronisation of this path), LibRaw's rule on it, and the params planned again with the resolved numbers
+                d = self.ctx.mosaic_maximum(image, deferred)
+                resolved, scale = deferred.resolve_scale(d)
+                self.last_raw_scale = {"data_maximum": d, "maximum_used": int(scale.maximum_used), "adjusted": bool(scale.adjusted)}
+                reduced = bool(params.reduced if phase1.is_xtrans(params) else params.half_size)
+                params = resolved.plan(int(image.shape[0]), int(image.shape[1]), reduced)
+            image = cut_and_turn(demosaic(image, params, orientation=demosaic_step.get("orientation", 0)),
                                  demosaic_step["window"], demosaic_step["rotate_times"], dims=(0, 1))
         if image.dtype in (torch.int16, torch.uint16):  # a decoded 16-bit frame: raw_conversion.py:50-52 on the device
             if cpu_payload.get("u16_factor") is None:

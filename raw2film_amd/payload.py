@@ -31,11 +31,17 @@ DEVICE_EXPOSURE = "device"  # exposure="device": the auto exposure of a uint16 f
                             # payload carries in place of its float `u16_factor`
 
 
-def mosaic_rejection(stops, rotate_times, lens, samples, xtrans=False, orientation=0):
+_LEVELS_REJECTED = _DEMOSAIC_REJECTED + ("its multipliers are a RawLevels: the scale follows the mosaic's data maximum, which is known "
+                                         "only after the last mosaic row has arrived")
+
+
+def mosaic_rejection(stops, rotate_times, lens, samples, xtrans=False, orientation=0, *, levels=False):
     """Why a mosaic is demosaiced whole instead of band by band (r2f_demosaic_f32), or None.  stops: the exposure is given in
     stops; samples: rows x cols x 3 of the window of the demosaiced frame that the pipeline takes, or None when nobody cut one;
     xtrans: the mosaic is an X-Trans one (r2f_demosaic_xtrans_u16 has the row-range contract, the band loop does not use it yet);
-    orientation: the profile's (the fused demosaic-to-float of the band loop is upright; a turned band reads every mosaic row)."""
+    orientation: the profile's (the fused demosaic-to-float of the band loop is upright; a turned band reads every mosaic row);
+    levels: the profile is deferred (its multipliers are a RawLevels: r2f_mosaic_maximum of the whole mosaic comes first) -- the
+    last reason asked for."""
     if orientation:
         return _DEMOSAIC_REJECTED + (f"orientation = {orientation!r}: an oriented mosaic is demosaiced in one piece "
                                      "(r2f_demosaic_oriented_u16), the band loop's demosaic is upright")
@@ -52,6 +58,8 @@ def mosaic_rejection(stops, rotate_times, lens, samples, xtrans=False, orientati
         return _DEMOSAIC_REJECTED + "no window of the demosaiced frame is known for it"
     if samples < STREAM_MIN_SAMPLES:
         return _DEMOSAIC_REJECTED + f"its window of the demosaiced frame has {samples} samples, below 16.7 M"
+    if levels:
+        return _LEVELS_REJECTED
     return None
 
 
@@ -91,7 +99,7 @@ def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canv
         window = step.get("window")
         why = mosaic_rejection(isinstance(payload.get("u16_factor"), float), step.get("rotate_times") or 0, payload.get("lens"),
                                None if window is None else int(window[2]) * int(window[3]) * 3, is_xtrans(step.get("params")),
-                               step.get("orientation", 0))
+                               step.get("orientation", 0), levels=step.get("levels") is not None)
         if why is not None:
             return why
     if payload.get("lens"):
@@ -116,12 +124,13 @@ def is_xtrans(params) -> bool:
 
 
 def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="No", highlight_burn=0.0, lens=False, demosaic=False, *,
-                     stops=False, rotate_times=0, frame_samples=None, xtrans=False, orientation=0):
+                     stops=False, rotate_times=0, frame_samples=None, xtrans=False, orientation=0, levels=False):
     """Why process(src, cache=False) renders a frame in one piece before it extracts its payload (stream_rejection and plan_bands
     come after that), or None.  lens: the call corrects the lens (lens_correction with a lens_profile); demosaic: its source is a
     mosaic (raw_profile), for which stops says that the exposure is given in stops, rotate_times is the call's, frame_samples the
     samples of the window of the demosaiced frame that the pipeline takes (mosaic_frame_samples), xtrans that the profile is an
-    XTransProfile (which does not stream yet), and orientation the profile's (not 0: the one-piece path)."""
+    XTransProfile (which does not stream yet), orientation the profile's (not 0: the one-piece path), and levels that the profile
+    is deferred (RawLevels: the one-piece path, the last reason asked for)."""
     if stream_bands <= 1:
         return f"stream_bands = {stream_bands}"
     if demosaic:
@@ -137,6 +146,8 @@ def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="
     if rotation or chroma_nr or canvas_mode != "No" or highlight_burn:
         return (f"a device pre-path, a canvas or a highlight burn: rotation = {rotation!r}, chroma_nr = {chroma_nr!r}, "
                 f"canvas_mode = {canvas_mode!r}, highlight_burn = {highlight_burn!r}")
+    if demosaic and levels:
+        return _LEVELS_REJECTED
     return None
 
 

@@ -7,6 +7,10 @@ mosaic itself is the `src` of the call.  The definition of the arithmetic is in 
 
 XTransProfile is the same record for a 6 x 6 array (r2f_xtrans_plan, r2f_demosaic_xtrans_u16).  Each profile states its own
 `reduction`: what half_size=True divides a mosaic's sides by.
+
+RawLevels states the sensor's levels instead of finished multipliers: a profile that holds one as its `multipliers` is DEFERRED --
+its scale follows LibRaw's adjust_maximum rule from the frame's data maximum, which the device measures (r2f_mosaic_maximum,
+r2f_raw_scale_plan; include/r2f.h has the definition, and its parity with LibRaw's bytes is unpinned like the demosaic's).
 """
 
 from __future__ import annotations
@@ -14,7 +18,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import numbers
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 from . import _lib
 
@@ -45,10 +49,56 @@ def _matrix(matrix, who):
     return rows
 
 
+@dataclass(frozen=True)
+class RawLevels:
+    """The sensor's levels, in place of a profile's numeric `multipliers`: a frozen, hashable record.
+
+    white_balance: (r, g, b), finite and > 0 (only their ratios count: the smallest becomes 1).
+    white_level: the nominal white level, an integer in [1, 65535], before the black level is subtracted.
+    adjust_maximum_thr: LibRaw's parameter of the same name, in [0, 1]; 0.75 is its default, which upstream's raw.postprocess call
+        leaves alone; 0 never adjusts.
+    A profile holding one scales a frame by 65535 / (white_level - min(black)), or by 65535 / d when the frame's largest
+    black-subtracted sample d lies between the threshold's share and the whole of that maximum (include/r2f.h: the Scale steps)."""
+    white_balance: tuple
+    white_level: int
+    adjust_maximum_thr: float = 0.75
+
+    def __post_init__(self):
+        wb = _floats("white_balance", self.white_balance, (3,), "RawLevels")
+        if any(not v > 0 for v in wb):
+            raise ValueError(f"RawLevels.white_balance must be three positive numbers, got {self.white_balance!r}")
+        level = self.white_level
+        if isinstance(level, bool) or not isinstance(level, numbers.Integral) or not 1 <= level <= 65535:
+            raise ValueError(f"RawLevels.white_level must be an integer in [1, 65535], got {level!r}")
+        thr = self.adjust_maximum_thr
+        if isinstance(thr, bool) or not isinstance(thr, numbers.Real) or not 0 <= thr <= 1:  # (a NaN fails the comparison)
+            raise ValueError(f"RawLevels.adjust_maximum_thr must be a number in [0, 1], got {thr!r}")
+        for name, value in (("white_balance", wb), ("white_level", int(level)), ("adjust_maximum_thr", float(thr))):
+            object.__setattr__(self, name, value)
+
+    def to_c(self) -> _lib.RawLevels:
+        c = _lib.RawLevels(white_level=self.white_level, adjust_maximum_thr=self.adjust_maximum_thr)
+        c.white_balance[:] = self.white_balance
+        return c
+
+    def scale(self, black, data_maximum: int = 0) -> _lib.RawScale:
+        """r2f_raw_scale_plan of these levels, a profile's black table (4 or 36 levels) and a data maximum (0: the nominal scale);
+        ValueError for what the planner refuses (a white level that is not above the smallest black level, a maximum above 65535)."""
+        d = data_maximum
+        if isinstance(d, bool) or not isinstance(d, numbers.Integral) or not 0 <= d <= 65535:
+            raise ValueError(f"the data maximum must be an integer in [0, 65535], got {data_maximum!r}")
+        out = _lib.RawScale()
+        table = (C.c_double * len(black))(*black)
+        if _lib.load().r2f_raw_scale_plan(C.byref(self.to_c()), table, len(black), int(d), C.byref(out)) != _lib.OK:
+            raise ValueError(f"r2f_raw_scale_plan refused {self!r} with black levels {tuple(black)!r} and a data maximum of {d}")
+        return out
+
+
 class _MosaicProfile:
     """What the two profiles share: the normalisation of black, multipliers, matrix and orientation, `oriented_shape()` and `plan()`.  A profile class states
     `_sites` (black levels per period of its array), `_multiplier_counts`, its params type, its planner's name and `to_c` (the C
-    profile)."""
+    profile).
+    With a RawLevels as its `multipliers` a profile is deferred (`deferred`): the numbers come from the frame (`resolve`)."""
 
     def _normalise(self):
         """black, multipliers and matrix as tuples of floats and the orientation as an int, checked (frozen: set once, from
@@ -60,9 +110,11 @@ class _MosaicProfile:
         black = _floats("black", black, (self._sites,), who)
         if any(b < 0 or b > 65535 or b != math.floor(b) for b in black):
             raise ValueError(f"{who}.black must be integers in [0, 65535], got {self.black!r}")
-        mul = _floats("multipliers", self.multipliers, self._multiplier_counts, who)
-        if any(not 0 < m <= 1024 for m in mul):
-            raise ValueError(f"{who}.multipliers must lie in (0, 1024], got {self.multipliers!r}")
+        mul = self.multipliers
+        if not isinstance(mul, RawLevels):  # (a deferred profile keeps the record: part of equality and hash like the numbers)
+            mul = _floats("multipliers", mul, self._multiplier_counts, who)
+            if any(not 0 < m <= 1024 for m in mul):
+                raise ValueError(f"{who}.multipliers must lie in (0, 1024], got {self.multipliers!r}")
         for name, value in (("black", black), ("multipliers", mul), ("matrix", _matrix(self.matrix, who))):
             object.__setattr__(self, name, value)
         o = self.orientation
@@ -76,10 +128,42 @@ class _MosaicProfile:
         rows, cols = (int(H) // self.reduction, int(W) // self.reduction) if half_size else (int(H), int(W))
         return (cols, rows) if self.orientation & 4 else (rows, cols)
 
+    @property
+    def deferred(self) -> bool:
+        """The multipliers are a RawLevels: the scale is derived from the frame's data maximum (`resolve`)."""
+        return isinstance(self.multipliers, RawLevels)
+
+    def resolve(self, data_maximum: int):
+        """This profile with numeric multipliers: r2f_raw_scale_plan of its levels, its black table and the frame's data maximum
+        (HipContext.mosaic_maximum measures it; 0 is the nominal scale).  A numeric profile is returned as it is.  ValueError for
+        what the planner refuses, and for a scale outside (0, 1024]."""
+        return self.resolve_scale(data_maximum)[0]
+
+    def resolve_scale(self, data_maximum: int) -> tuple:
+        """(resolve(data_maximum), the r2f_raw_scale it was resolved with: mul, maximum_used, adjusted) from one run of the planner;
+        (the profile itself, None) for a numeric profile."""
+        if not self.deferred:
+            return self, None
+        scale = self.multipliers.scale(self.black, data_maximum)
+        return replace(self, multipliers=tuple(scale.mul)), scale
+
+    def _c_multipliers(self) -> tuple:
+        """The multipliers `to_c` states, per site or colour as the profile keeps them: a deferred profile's are those of the
+        NOMINAL scale (resolve(0)'s, unchecked: the planner refuses what is out of range)."""
+        if not self.deferred:
+            return self.multipliers
+        mul = tuple(self.multipliers.scale(self.black, 0).mul)
+        return self._spread(mul)
+
+    def _spread(self, mul):  # (r, g, b) as the profile keeps its multipliers
+        return mul
+
     def plan(self, H: int, W: int, half_size: bool = False):
         """The params of an H x W mosaic (no GPU: r2f_demosaic_params / r2f_xtrans_params); ValueError for what the planner refuses
         (a frame below the array's 2 x 2 / 6 x 6, an odd side with half_size of a Bayer frame, an X-Trans pattern that is not
-        admissible -- for the reduced size, with half_size --, a multiplier that rounds to 0 as a float)."""
+        admissible -- for the reduced size, with half_size --, a multiplier that rounds to 0 as a float).
+        A deferred profile (`to_c` as well) plans its NOMINAL scale, resolve(0)'s: phase 1 needs out_h / out_w and the tables
+        without a GPU, and the frame's own scale is planned once the device has measured its maximum (`resolve`)."""
         out = self._c_params()
         profile = self.to_c(half_size)
         if getattr(_lib.load(), self._planner)(C.byref(profile), int(H), int(W), C.byref(out)) != _lib.OK:
@@ -93,7 +177,8 @@ class RawProfile(_MosaicProfile):
 
     pattern: "RGGB" | "BGGR" | "GRBG" | "GBRG", the colours of the quad at (0, 0) in reading order.
     black: one level for every site, or 4 per site of the quad (k = (y & 1) * 2 + (x & 1)); integers in [0, 65535].
-    multipliers: (r, g, b), or 4 per site; each in (0, 1024].  They hold the white balance AND the scale to 16 bits.
+    multipliers: (r, g, b), or 4 per site; each in (0, 1024].  They hold the white balance AND the scale to 16 bits.  Or a
+        RawLevels: the profile is then deferred, and its (r, g, b) are derived from each frame's data maximum (`resolve`).
     matrix: 3 x 3, rows are the output channels; |entries| <= 64.
     orientation: 0 .. 7, how the sensor was held, as LibRaw's sizes.flip bits (4 swaps the axes, 2 mirrors rows, 1 mirrors
         columns: 0 upright, 3 180 degrees, 5 90 degrees counter-clockwise, 6 90 degrees clockwise).  The demosaic writes the frame
@@ -101,7 +186,7 @@ class RawProfile(_MosaicProfile):
         frame, as upstream's does.  (Not `flip`: process(flip=) is the aspect's.)"""
     pattern: str = "RGGB"
     black: tuple | float = 0
-    multipliers: tuple = (1.0, 1.0, 1.0)
+    multipliers: tuple | RawLevels = (1.0, 1.0, 1.0)
     matrix: tuple = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
     orientation: int = 0
 
@@ -113,13 +198,16 @@ class RawProfile(_MosaicProfile):
         if not isinstance(self.pattern, str) or self.pattern not in _PATTERNS:
             raise ValueError(f"RawProfile.pattern must be one of {sorted(_PATTERNS)}, got {self.pattern!r}")
         self._normalise()
-        if len(self.multipliers) == 3:  # (r, g, b) -> per site of the quad
-            object.__setattr__(self, "multipliers", tuple(self.multipliers["RGB".index(c)] for c in self.pattern))
+        if not self.deferred and len(self.multipliers) == 3:
+            object.__setattr__(self, "multipliers", self._spread(self.multipliers))
+
+    def _spread(self, mul):  # (r, g, b) -> per site of the quad
+        return tuple(mul["RGB".index(c)] for c in self.pattern)
 
     def to_c(self, half_size: bool = False) -> _lib.RawProfile:
         p = _lib.RawProfile(pattern=_PATTERNS[self.pattern], half_size=int(bool(half_size)))
         p.black[:] = self.black
-        p.mul[:] = self.multipliers
+        p.mul[:] = self._c_multipliers()
         p.matrix[:] = [v for row in self.matrix for v in row]
         return p
 
@@ -137,13 +225,14 @@ class XTransProfile(_MosaicProfile):
         admissible is the planner's to say (`plan`): green within 2 samples on both sides of every other site along rows and
         columns, both other colours in every centred 3 x 3.
     black: one level for every site, or 36 per phase ((y % 6) * 6 + x % 6); integers in [0, 65535].
-    multipliers: (r, g, b); each in (0, 1024].  They hold the white balance AND the scale to 16 bits.
+    multipliers: (r, g, b); each in (0, 1024].  They hold the white balance AND the scale to 16 bits.  Or a RawLevels, as
+        RawProfile's (a deferred profile).
     matrix: 3 x 3, rows are the output channels; |entries| <= 64.
     orientation: 0 .. 7, LibRaw's sizes.flip bits, as RawProfile's (r2f_demosaic_xtrans_oriented_u16).
     half_size=True yields A THIRD of the mosaic's sides (the 3 x 3 cells of the array), not a half: `reduction`."""
     pattern: tuple | str = XTRANS
     black: tuple | float = 0
-    multipliers: tuple = (1.0, 1.0, 1.0)
+    multipliers: tuple | RawLevels = (1.0, 1.0, 1.0)
     matrix: tuple = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
     orientation: int = 0
 
@@ -170,6 +259,6 @@ class XTransProfile(_MosaicProfile):
         p = _lib.XTransProfile(reduced=int(bool(half_size)))
         p.pattern[:] = ["RGB".index(c) for row in self.pattern for c in row]
         p.black[:] = self.black
-        p.mul[:] = self.multipliers
+        p.mul[:] = self._c_multipliers()
         p.matrix[:] = [v for row in self.matrix for v in row]
         return p
