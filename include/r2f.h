@@ -309,7 +309,8 @@ R2F_API int r2f_warp_affine(r2f_ctx* ctx, const void* in, int in_layout, int H, 
 /* Pre-path lens correction from numbers the caller supplies: what effects.lens_correction (effects.py:22-43) does with the values
  * lensfun looked up -- a radial coordinate map (Modifier.apply_geometry_distortion), an 8 x 8 LANCZOS4 gather through it
  * (lensfunpy.util.remap -> cv2.remap(..., INTER_LANCZOS4), constant border 0), a clamp at 0 and a radial vignetting gain
- * (apply_color_modification).  The database lookup itself, TCA and an adapter from lensfunpy objects are not here.
+ * (apply_color_modification).  Transverse chromatic aberration is an entry point of its own, r2f_lens_correct_tca below.  The
+ * database lookup itself and an adapter from lensfunpy objects are not here.
  *
  * The definition.  Take output pixel (X, Y) of the corrected full frame.
  *   - The host rounds these constants from double: cx, cy, q = 1/(norm_radius_px*scale), inv_scale = 1/scale, c0,
@@ -338,7 +339,7 @@ R2F_API int r2f_warp_affine(r2f_ctx* ctx, const void* in, int in_layout, int H, 
  * Edge cases:
  *   - A coordinate that is NaN, infinite, or beyond the frame by more than the tap reach yields 0 without indexing anything; that
  *     decision is made in floats (on rint(sx*32), rint(sy*32)), before any conversion to int.
- *   - One coordinate serves all three channels (upstream never calls the TCA path).
+ *   - One coordinate serves all three channels here; r2f_lens_correct_tca gives red and blue coordinates of their own.
  *   - A fourth input channel is ignored.
  * cx = (W - 1)/2 + center_x*norm_radius_px, cy = (H - 1)/2 + center_y*norm_radius_px.
  * Parity with real OpenCV / lensfun is UNPINNED: neither is installed on any machine this project sees; what the tests pin is this
@@ -382,6 +383,54 @@ R2F_API int r2f_lens_phase_table(float* table_32x8);
  * memory, with the same sums in the same order: results do not depend on it). */
 R2F_API int r2f_lens_correct(r2f_ctx* ctx, const void* in, int in_layout, int H, int W, const r2f_lens_params* params,
                      const r2f_planes* dst, int out_h, int out_w, int oy, int ox, void* stream);
+
+/* The lens correction with transverse chromatic aberration (TCA): red and blue sample at coordinates of their own.  This follows
+ * lensfun's order: the sub-pixel callbacks (apply_subpixel_distortion) act on the coordinates the geometry callbacks produced.
+ *
+ * The definition.  Everything of r2f_lens_correct's up to g = f*inv_scale is unchanged.  Then:
+ *   - ox = dx*g, oy = dy*g.
+ *   - Green: sx = cx + ox, sy = cy + oy -- r2f_lens_correct's values, bit for bit.
+ *   - Red and blue each have three constants (v, c, b) and a factor t:
+ *       linear: t = v (lensfun's kr / kb).
+ *       poly3:  a = ox*qv, e = oy*qv, r2 = a*a + e*e, r = sqrt(r2); t0 = r*b, t1 = c + t0, t2 = r*t1, t = v + t2
+ *               (lensfun's Rd = Ru (b Ru^2 + c Ru + v)).
+ *     sx_c = cx + ox*t, sy_c = cy + oy*t.
+ *   - qv = 1/norm_radius_px is the one r2f_lens_params carries, filled whether or not vignetting is on.
+ * Every operation is one correctly rounded fp32 operation, with no contraction.
+ * Each channel runs the phase split on its own coordinate and its own 64-tap sum over its own plane only: weights fl(wy*wx) from
+ * its own phases, in the same sum order.  Then the clamp at 0 and the vignetting gain of the output pixel's (dx, dy), the same
+ * for all three channels.  A channel whose coordinate is outside yields 0 for that channel alone.
+ * Two consequences hold bit for bit:
+ *   - the green plane equals r2f_lens_correct's green plane for the same r2f_lens_params;
+ *   - a record whose factors are exactly 1 -- linear (1, 1), or poly3 with v = 1, c = b = 0 -- gives r2f_lens_correct's result on
+ *     all three planes.
+ * Parity with lensfun is UNPINNED, like the rest of this section (tests/lens_tca_model.py restates the definition in NumPy).
+ * Lensfun's other TCA variants are not here. */
+enum { R2F_TCA_NONE = 0, R2F_TCA_LINEAR = 1, R2F_TCA_POLY3 = 2 };
+/* What the caller knows of a lens's TCA: n_coef constants per channel of `model` -- 1 for linear (v), 3 for poly3 (v, c, b) --
+ * for red and for blue.  Constants past n_coef are not read. */
+typedef struct r2f_lens_tca {
+    int32_t model, n_coef;
+    double red[3], blue[3]; /* (v, c, b) */
+} r2f_lens_tca;
+/* The fp32 constants of the TCA step: the doubles rounded to float; c = b = 0 for linear. */
+typedef struct r2f_lens_tca_params {
+    int32_t model;
+    float red[3], blue[3]; /* (v, c, b) */
+} r2f_lens_tca_params;
+/* r2f_lens_plan for a profile with a TCA record: r2f_lens_plan's checks, and R2F_EINVAL for an unknown TCA model (R2F_TCA_NONE
+ * included: such a profile is r2f_lens_plan's), a count that is not the model's, a non-finite constant or one that does not fit a
+ * float.  auto_scale: the eight probes are evaluated for all three channels -- the map in double with the TCA factor in double
+ * on top -- and the furthest reach of any channel decides, so that no channel shows a border; a record whose factors are exactly 1
+ * resolves to r2f_lens_plan's scale to the last bit.  Without auto_scale *out is r2f_lens_plan's, byte for byte. */
+R2F_API int r2f_lens_plan_tca(const r2f_lens_profile* profile, const r2f_lens_tca* tca, int H, int W, r2f_lens_params* out,
+                      r2f_lens_tca_params* out_tca);
+/* The correction with TCA: r2f_lens_correct's contract for the window, the layouts and the rows of `dst`.  tca_params->model
+ * R2F_TCA_NONE is refused with R2F_EINVAL (that case is r2f_lens_correct's), and so is an unknown one.  The box a block stages in
+ * LDS is the union of its three channels' tap extents; results do not depend on whether a block staged. */
+R2F_API int r2f_lens_correct_tca(r2f_ctx* ctx, const void* in, int in_layout, int H, int W, const r2f_lens_params* params,
+                         const r2f_lens_tca_params* tca_params, const r2f_planes* dst, int out_h, int out_w, int oy, int ox,
+                         void* stream);
 
 /* Post-path up-scale of the rendered uint8 frame: utils.resolution_scaling's cv.resize(image, dsize,
  * interpolation=cv.INTER_LANCZOS4) branch (utils.py:237-242), the way back from the `max_scale` pipeline resolution to the

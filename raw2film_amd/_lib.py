@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libr2f_hip.so")
 # enums of include/r2f.h
 LAYOUT_HWC3, LAYOUT_HWC4, LAYOUT_CHW = 0, 1, 2
 LENS_NONE, LENS_POLY3, LENS_POLY5, LENS_PTLENS = 0, 1, 2, 3
+TCA_NONE, TCA_LINEAR, TCA_POLY3 = 0, 1, 2
 CFA_RGGB, CFA_BGGR, CFA_GRBG, CFA_GBRG = 0, 1, 2, 3
 DEMOSAIC_TILE_W, DEMOSAIC_TILE_H = 64, 32  # R2F_DEMOSAIC_TILE_*
 XTRANS_TILE_W, XTRANS_TILE_H = 64, 32  # R2F_XTRANS_TILE_*
@@ -82,6 +83,14 @@ class LensParams(C.Structure):  # r2f_lens_params: the fp32 constants of one fra
     _fields_ = [("model", C.c_int32), ("vignetting", C.c_int32), ("cx", C.c_float), ("cy", C.c_float), ("q", C.c_float),
                 ("inv_scale", C.c_float), ("c0", C.c_float), ("k", C.c_float * 3), ("qv", C.c_float), ("v", C.c_float * 3),
                 ("scale", C.c_double)]
+
+
+class LensTca(C.Structure):  # r2f_lens_tca: (v, c, b) of red and of blue (raw2film_amd.lens.LensProfile.to_c_tca fills it)
+    _fields_ = [("model", C.c_int32), ("n_coef", C.c_int32), ("red", C.c_double * 3), ("blue", C.c_double * 3)]
+
+
+class LensTcaParams(C.Structure):  # r2f_lens_tca_params: the same constants in fp32
+    _fields_ = [("model", C.c_int32), ("red", C.c_float * 3), ("blue", C.c_float * 3)]
 
 
 class RawProfile(C.Structure):  # r2f_raw_profile (raw2film_amd.raw.RawProfile fills it)
@@ -192,6 +201,12 @@ _SIGNATURES = {
     "r2f_lens_correct": (
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(LensParams), _P(Planes), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    ),
+    "r2f_lens_plan_tca": (C.c_int, [_P(LensProfile), _P(LensTca), C.c_int, C.c_int, _P(LensParams), _P(LensTcaParams)]),
+    "r2f_lens_correct_tca": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(LensParams), _P(LensTcaParams), _P(Planes), C.c_int, C.c_int, C.c_int,
+         C.c_int, C.c_void_p],
     ),
     "r2f_demosaic_plan": (C.c_int, [_P(RawProfile), C.c_int, C.c_int, _P(DemosaicParams)]),
     "r2f_demosaic_u16": (

@@ -1,6 +1,7 @@
-// r2f_lens_math.h -- the arithmetic of the lens correction (include/r2f.h, r2f_lens_correct), as text the device kernel
-// (r2f_resample.hip) and a CPU program (tests/lens_check.cpp, g++ -ffp-contract=off) both compile: the coordinate map, the 1/32
-// phase split with its inside / outside decision, the 64-tap sample over a pixel-fetch functor and the vignetting gain.  Every
+// r2f_lens_math.h -- the arithmetic of the lens correction (include/r2f.h, r2f_lens_correct and r2f_lens_correct_tca), as text the
+// device kernels (r2f_resample.hip) and CPU programs (tests/lens_check.cpp, tests/lens_tca_check.cpp, g++ -ffp-contract=off) both
+// compile: the coordinate map, red's and blue's TCA step on it, the 1/32 phase split with its inside / outside decision, the 64-tap
+// sample over a pixel-fetch functor (three channels at one coordinate, or one channel at its own) and the vignetting gain.  Every
 // operation is one correctly rounded fp32 operation; contraction is off for each function (a fused multiply-add would round once
 // where the definition rounds twice).  No HIP types, no includes beyond <math.h>.
 #pragma once
@@ -26,8 +27,9 @@ namespace lens {
 constexpr int kPhases = 32;  // INTER_TAB_SIZE = 1 << INTER_BITS
 constexpr int kTaps = 8;
 
-// Source coordinate (sx, sy) of output pixel (X, Y); dx, dy are handed on to the vignetting gain.
-R2F_HD void source_coord(const r2f_lens_params& p, int X, int Y, float& sx, float& sy, float& dx, float& dy) {
+// The offset (ox, oy) = (dx*g, dy*g) of output pixel (X, Y)'s source coordinate from the optical centre: the map up to the point at
+// which the channels part (r2f_lens_correct_tca).  dx, dy are handed on to the vignetting gain.
+R2F_HD void source_offset(const r2f_lens_params& p, int X, int Y, float& ox, float& oy, float& dx, float& dy) {
     R2F_NO_CONTRACT
     dx = (float)X - p.cx;
     dy = (float)Y - p.cy;
@@ -53,7 +55,38 @@ R2F_HD void source_coord(const r2f_lens_params& p, int X, int Y, float& sx, floa
         f = p.c0 + t4;
     }
     const float g = f * p.inv_scale;
-    const float ox = dx * g, oy = dy * g;
+    ox = dx * g, oy = dy * g;
+}
+
+// Source coordinate (sx, sy) of output pixel (X, Y); dx, dy are handed on to the vignetting gain.
+R2F_HD void source_coord(const r2f_lens_params& p, int X, int Y, float& sx, float& sy, float& dx, float& dy) {
+    R2F_NO_CONTRACT
+    float ox, oy;
+    source_offset(p, X, Y, ox, oy, dx, dy);
+    sx = p.cx + ox;
+    sy = p.cy + oy;
+}
+
+// The coordinate at which channel ch (0 red, 1 green, 2 blue) samples: green at the centre plus the offset, red and blue at the
+// centre plus the offset times their TCA factor t (linear: v; poly3: v + r*(c + r*b), r the offset's length in units of the
+// normalisation radius).
+R2F_HD void channel_coord(const r2f_lens_params& p, const r2f_lens_tca_params& tca, int ch, float ox, float oy, float& sx, float& sy) {
+    R2F_NO_CONTRACT
+    if (ch != 1) {
+        const float* k = ch == 0 ? tca.red : tca.blue;
+        float t = k[0];
+        if (tca.model == R2F_TCA_POLY3) {
+            const float a = ox * p.qv, e = oy * p.qv;
+            const float aa = a * a, ee = e * e;
+            const float r2 = aa + ee;
+            const float r = sqrtf(r2);
+            const float t0 = r * k[2];
+            const float t1 = k[1] + t0;
+            const float t2 = r * t1;
+            t = k[0] + t2;
+        }
+        ox = ox * t, oy = oy * t;
+    }
     sx = p.cx + ox;
     sy = p.cy + oy;
 }
@@ -101,6 +134,34 @@ R2F_HD void sample64(const Fetch& fetch, int H, int W, int ix, int iy, const flo
     }
 }
 
+// sample64 for one channel: fetch(ch, y, x) returns that channel's sample of a texel inside the frame.  The same weights, products
+// and sum order as sample64's for that channel.
+template <typename Fetch>
+R2F_HD float sample64_channel(const Fetch& fetch, int ch, int H, int W, int ix, int iy, const float* wx, const float* wy) {
+    R2F_NO_CONTRACT
+    float acc = 0.f;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int k = 0; k < kTaps; ++k) {
+        const int yy = iy - 3 + k;
+        const bool row_in = yy >= 0 && yy < H;
+        float h = 0.f;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int j = 0; j < kTaps; ++j) {
+            const int xx = ix - 3 + j;
+            const float v = row_in && xx >= 0 && xx < W ? fetch(ch, yy, xx) : 0.f;
+            const float w = wy[k] * wx[j];
+            const float prod = w * v;
+            h = j == 0 ? prod : h + prod;
+        }
+        acc = k == 0 ? h : acc + h;
+    }
+    return acc;
+}
+
 // max(sum, 0), then the vignetting gain of (dx, dy).
 R2F_HD float finish(const r2f_lens_params& p, float sum, float dx, float dy) {
     R2F_NO_CONTRACT
@@ -131,6 +192,22 @@ R2F_HD void correct_pixel(const r2f_lens_params& p, const Fetch& fetch, int H, i
     float acc[3];
     sample64(fetch, H, W, ix, iy, table + fx * kTaps, table + fy * kTaps, acc);
     for (int c = 0; c < 3; ++c) out[c] = finish(p, acc[c], dx, dy);
+}
+
+// One output pixel of r2f_lens_correct_tca, start to end: each channel with its own coordinate, decision, phases and sum.
+template <typename Fetch>
+R2F_HD void correct_pixel_tca(const r2f_lens_params& p, const r2f_lens_tca_params& tca, const Fetch& fetch, int H, int W, const float* table,
+                              int X, int Y, float (&out)[3]) {
+    float ox, oy, dx, dy;
+    source_offset(p, X, Y, ox, oy, dx, dy);
+    for (int ch = 0; ch < 3; ++ch) {
+        float sx, sy;
+        channel_coord(p, tca, ch, ox, oy, sx, sy);
+        int ix, iy, fx, fy;
+        out[ch] = 0.f;
+        if (!split_phase(sx, W, ix, fx) || !split_phase(sy, H, iy, fy)) continue;  // outside: 0 for this channel alone
+        out[ch] = finish(p, sample64_channel(fetch, ch, H, W, ix, iy, table + fx * kTaps, table + fy * kTaps), dx, dy);
+    }
 }
 
 }  // namespace lens

@@ -1,5 +1,6 @@
-// r2f_lens_plan.cpp -- host planner of the lens correction (include/r2f.h: r2f_lens_plan, r2f_lens_phase_table).  No HIP in this
-// file: hipcc compiles it into the library, g++ -fsanitize=address,undefined,float-cast-overflow into tests/lens_check.cpp's program.
+// r2f_lens_plan.cpp -- host planner of the lens correction (include/r2f.h: r2f_lens_plan, r2f_lens_plan_tca, r2f_lens_phase_table).
+// No HIP in this file: hipcc compiles it into the library, g++ -fsanitize=address,undefined,float-cast-overflow into the programs of
+// tests/lens_check.cpp and tests/lens_tca_check.cpp.
 #include <cmath>
 
 #include "../../include/r2f.h"
@@ -22,9 +23,15 @@ double model_factor(const r2f_lens_profile& p, double r2) {
     }
 }
 
+// The TCA factor t of one channel's constants (v, c, b) in double, at an offset of length r in units of the normalisation radius.
+double tca_factor(const r2f_lens_tca& tca, const double* k, double r) {
+    return tca.model == R2F_TCA_POLY3 ? k[0] + r * (k[1] + r * k[2]) : k[0];
+}
+
 // How far the furthest-reaching of the eight probes lands outside [0, W - 1] x [0, H - 1], in pixels (<= 0: every probe is inside;
-// 0: one lies exactly on the boundary).  NaN when the map is not finite at a probe.
-double outside(const r2f_lens_profile& p, int H, int W, double cx, double cy, double norm, double scale) {
+// 0: one lies exactly on the boundary).  NaN when the map is not finite at a probe.  With a TCA record each probe is evaluated for
+// green, red and blue, and the furthest reach of any channel counts.
+double outside(const r2f_lens_profile& p, const r2f_lens_tca* tca, int H, int W, double cx, double cy, double norm, double scale) {
     const double xs[3] = {0.0, (W - 1) / 2.0, (double)(W - 1)}, ys[3] = {0.0, (H - 1) / 2.0, (double)(H - 1)};
     double worst = -INFINITY;
     for (int j = 0; j < 3; ++j)
@@ -33,20 +40,25 @@ double outside(const r2f_lens_profile& p, int H, int W, double cx, double cy, do
             const double dx = xs[i] - cx, dy = ys[j] - cy;
             const double q = 1.0 / (norm * scale), u = dx * q, v = dy * q;
             const double g = model_factor(p, u * u + v * v) / scale;
-            const double sx = cx + dx * g, sy = cy + dy * g;
-            if (!std::isfinite(sx) || !std::isfinite(sy)) return NAN;
-            worst = std::fmax(worst, std::fmax(std::fmax(-sx, sx - (W - 1)), std::fmax(-sy, sy - (H - 1))));
+            const double ox = dx * g, oy = dy * g;
+            for (int ch = 0; ch < (tca ? 3 : 1); ++ch) {  // green first: the only one without a record
+                double t = 1.0;
+                if (ch) {
+                    const double a = ox / norm, e = oy / norm;
+                    t = tca_factor(*tca, ch == 1 ? tca->red : tca->blue, std::sqrt(a * a + e * e));
+                }
+                const double sx = cx + ox * t, sy = cy + oy * t;
+                if (!std::isfinite(sx) || !std::isfinite(sy)) return NAN;
+                worst = std::fmax(worst, std::fmax(std::fmax(-sx, sx - (W - 1)), std::fmax(-sy, sy - (H - 1))));
+            }
         }
     return worst;
 }
 
 bool fits_float(double v) { return std::isfinite(v) && std::fabs(v) <= 3.0e38; }
 
-}  // namespace
-
-extern "C" {
-
-int r2f_lens_plan(const r2f_lens_profile* p, int H, int W, r2f_lens_params* out) {
+// r2f_lens_plan, with the probes of the auto scale going through `tca` too when there is one.
+int plan(const r2f_lens_profile* p, const r2f_lens_tca* tca, int H, int W, r2f_lens_params* out) {
     if (!p || !out || H < 1 || W < 1) return R2F_EINVAL;
     if (p->model < R2F_LENS_NONE || p->model > R2F_LENS_PTLENS || p->n_coef != kCoefCount[p->model]) return R2F_EINVAL;
     for (int i = 0; i < p->n_coef; ++i)
@@ -71,11 +83,11 @@ int r2f_lens_plan(const r2f_lens_profile* p, int H, int W, r2f_lens_params* out)
         } else {
             // at `lo` a probe is outside (or the map is not finite there: NaN), at `hi` all are inside; keep that while halving
             double lo = 1.0 / 16, hi = 16.0;
-            if (!(outside(*p, H, W, cx, cy, norm, hi) <= 0) || outside(*p, H, W, cx, cy, norm, lo) <= 0) return R2F_EINVAL;
+            if (!(outside(*p, tca, H, W, cx, cy, norm, hi) <= 0) || outside(*p, tca, H, W, cx, cy, norm, lo) <= 0) return R2F_EINVAL;
             for (int it = 0; it < 200; ++it) {
                 const double mid = lo + (hi - lo) / 2;
                 if (mid <= lo || mid >= hi) break;
-                if (outside(*p, H, W, cx, cy, norm, mid) <= 0)
+                if (outside(*p, tca, H, W, cx, cy, norm, mid) <= 0)
                     hi = mid;
                 else
                     lo = mid;
@@ -105,6 +117,29 @@ int r2f_lens_plan(const r2f_lens_profile* p, int H, int W, r2f_lens_params* out)
     }
     r.scale = scale;
     *out = r;
+    return R2F_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int r2f_lens_plan(const r2f_lens_profile* p, int H, int W, r2f_lens_params* out) { return plan(p, nullptr, H, W, out); }
+
+int r2f_lens_plan_tca(const r2f_lens_profile* p, const r2f_lens_tca* tca, int H, int W, r2f_lens_params* out, r2f_lens_tca_params* out_tca) {
+    if (!tca || !out || !out_tca) return R2F_EINVAL;
+    if (tca->model != R2F_TCA_LINEAR && tca->model != R2F_TCA_POLY3) return R2F_EINVAL;
+    if (tca->n_coef != (tca->model == R2F_TCA_LINEAR ? 1 : 3)) return R2F_EINVAL;
+    r2f_lens_tca_params t{};
+    t.model = tca->model;
+    for (int i = 0; i < tca->n_coef; ++i) {
+        if (!fits_float(tca->red[i]) || !fits_float(tca->blue[i])) return R2F_EINVAL;
+        t.red[i] = (float)tca->red[i], t.blue[i] = (float)tca->blue[i];
+    }
+    r2f_lens_params r;
+    const int rc = plan(p, tca, H, W, &r);
+    if (rc != R2F_OK) return rc;
+    *out = r, *out_tca = t;
     return R2F_OK;
 }
 

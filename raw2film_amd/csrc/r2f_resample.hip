@@ -368,6 +368,111 @@ __global__ __launch_bounds__(256) void lens_correct_kernel(const LensArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------ lens correction with TCA (pre-path)
+// r2f_lens_correct_tca: red and blue sample at coordinates of their own (lens::channel_coord).  The shape is lens_correct_kernel's
+// -- a 64 x 16 tile, four rows per lane, the phase table and one planar box of kLensBoxTexels in LDS -- with these differences:
+//   - the box is the union of the three channels' tap extents (a texel is staged once for all of its channels, so an interleaved
+//     source is still read in whole pixels), and the staged / unstaged decision is made on that union;
+//   - a lane keeps nothing per row between the extent pass and the sampling pass: it evaluates the map again (some 40 operations
+//     beside 3 x 64 taps), so that beyond the map's result only one channel's indices, phases and accumulator are live at a time;
+//   - rows and channels are loops, not unrolled copies: one staged and one unstaged 64-tap body in the program.
+// The sums are lens::sample64_channel's over either fetch functor: results do not depend on whether a block staged.
+// The compiler reports (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage) 145 VGPRs, no VGPR spills, no scratch, 21 SGPRs
+// spilled into VGPR lanes, 37,904 B of LDS and 3 waves per SIMD, against lens_correct_kernel's 253 VGPRs and 2 waves.  Beside that
+// kernel in one process: 1.08 x its time with factors of 1, 1.15 x / 1.23 x at 24 / 100 MP with a poly3 record that parts red and
+// blue by up to 12 px at 100 MP, where a tenth of the blocks' unions no longer fit the box (profiles/r25_lens_tca_probe.txt).
+struct LensTcaArgs {
+    LensArgs lens;
+    r2f_lens_tca_params tca;
+};
+
+struct LensChannelFetch {
+    const float* src;
+    int in_layout, H, W;
+    __device__ __forceinline__ float operator()(int ch, int y, int x) const {
+        if (in_layout == R2F_LAYOUT_CHW) return src[(long long)ch * H * W + (long long)y * W + x];
+        return src[((long long)y * W + x) * (in_layout == R2F_LAYOUT_HWC4 ? 4 : 3) + ch];
+    }
+};
+
+struct LensLdsChannelFetch {
+    const float* box;  // [3][kLensBoxTexels], rows bw apart
+    int x0, y0, bw;
+    __device__ __forceinline__ float operator()(int ch, int y, int x) const { return box[ch * kLensBoxTexels + (y - y0) * bw + (x - x0)]; }
+};
+
+__global__ __launch_bounds__(256) void lens_correct_tca_kernel(const LensTcaArgs t) {
+    const LensArgs& a = t.lens;
+    __shared__ float table[lens::kPhases * lens::kTaps];
+    __shared__ float box[3 * kLensBoxTexels];
+    __shared__ int ext[4];  // min ix, max ix, min iy, max iy over the block's inside pixels, all channels
+    const int tid = threadIdx.y * 64 + threadIdx.x;
+    table[tid] = a.table[tid];
+    if (tid < 4) ext[tid] = (tid & 1) ? INT_MIN : INT_MAX;
+    __syncthreads();
+    const int dx = blockIdx.x * 64 + threadIdx.x, dy0 = blockIdx.y * (4 * kLensRows) + threadIdx.y;
+    int lo_x = INT_MAX, hi_x = INT_MIN, lo_y = INT_MAX, hi_y = INT_MIN;
+    if (dx < a.out_w) {
+#pragma unroll 1
+        for (int dy = dy0; dy < min(a.out_h, dy0 + 4 * kLensRows); dy += 4) {
+            float ox, oy, ddx, ddy;
+            lens::source_offset(a.p, dx + a.ox, dy + a.oy, ox, oy, ddx, ddy);
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                float sx, sy;
+                lens::channel_coord(a.p, t.tca, ch, ox, oy, sx, sy);
+                int ix, iy, fx, fy;
+                if (!lens::split_phase(sx, a.W, ix, fx) || !lens::split_phase(sy, a.H, iy, fy)) continue;
+                lo_x = min(lo_x, ix), hi_x = max(hi_x, ix), lo_y = min(lo_y, iy), hi_y = max(hi_y, iy);
+            }
+        }
+    }
+    if (lo_x <= hi_x) {
+        atomicMin(&ext[0], lo_x), atomicMax(&ext[1], hi_x);
+        atomicMin(&ext[2], lo_y), atomicMax(&ext[3], hi_y);
+    }
+    __syncthreads();
+    // (block-uniform from here: every thread reads the same four words)
+    const int x0 = ext[0] - 3, y0 = ext[2] - 3;
+    const bool any = ext[0] <= ext[1];
+    // ix, iy lie in [-4, n + 2] (split_phase), so the extents are small ints and their products cannot overflow
+    const int bw = any ? ext[1] + 4 - x0 + 1 : 0, bh = any ? ext[3] + 4 - y0 + 1 : 0;
+    const bool staged = any && (long long)bw * bh <= kLensBoxTexels;
+    if (staged) {
+        const LensFetch global{static_cast<const float*>(a.in), a.in_layout, a.H, a.W};
+        for (int i = tid; i < bw * bh; i += 256) {
+            const int y = y0 + i / bw, x = x0 + i % bw;
+            float v[3] = {0.f, 0.f, 0.f};
+            if (y >= 0 && y < a.H && x >= 0 && x < a.W) global(y, x, v);
+            box[i] = v[0], box[kLensBoxTexels + i] = v[1], box[2 * kLensBoxTexels + i] = v[2];
+        }
+    }
+    __syncthreads();
+    if (dx >= a.out_w) return;  // (no barrier below)
+    const LensLdsChannelFetch lds{box, x0, y0, bw};
+    const LensChannelFetch global{static_cast<const float*>(a.in), a.in_layout, a.H, a.W};
+#pragma unroll 1
+    for (int dy = dy0; dy < min(a.out_h, dy0 + 4 * kLensRows); dy += 4) {
+        float ox, oy, ddx, ddy;
+        lens::source_offset(a.p, dx + a.ox, dy + a.oy, ox, oy, ddx, ddy);
+        float* p0 = a.dst.data + (long long)(dy - a.dst.gy0) * a.out_w + dx;
+#pragma unroll 1
+        for (int ch = 0; ch < 3; ++ch) {
+            float sx, sy;
+            lens::channel_coord(a.p, t.tca, ch, ox, oy, sx, sy);
+            int ix, iy, fx, fy;
+            float v = 0.f;
+            if (lens::split_phase(sx, a.W, ix, fx) && lens::split_phase(sy, a.H, iy, fy)) {
+                const float *wx = table + fx * lens::kTaps, *wy = table + fy * lens::kTaps;
+                const float acc = staged ? lens::sample64_channel(lds, ch, a.H, a.W, ix, iy, wx, wy)
+                                         : lens::sample64_channel(global, ch, a.H, a.W, ix, iy, wx, wy);
+                v = lens::finish(a.p, acc, ddx, ddy);
+            }
+            p0[ch * a.dst.plane_stride] = v;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------ LANCZOS4, uint8 (post-path)
 struct LanczosArgs {
     const uint8_t* src;  // (H, W, 3)
@@ -565,17 +670,16 @@ int r2f_warp_affine(r2f_ctx* ctx, const void* in, int in_layout, int H, int W, c
     return R2F_OK;
 }
 
-int r2f_lens_correct(r2f_ctx* ctx, const void* in, int in_layout, int H, int W, const r2f_lens_params* params, const r2f_planes* dst,
-                     int out_h, int out_w, int oy, int ox, void* stream) {
-    if (!ctx) return R2F_EINVAL;
-    R2F_GUARD(ctx);
+// What both lens entry points check and set up: the arguments, the rows of `dst`, the phase table on the device -> the kernel's args.
+static int lens_args(r2f_ctx* ctx, const char* what, const void* in, int in_layout, int H, int W, const r2f_lens_params* params,
+                     const r2f_planes* dst, int out_h, int out_w, int oy, int ox, LensArgs* a) {
     // (the phase split adds 3 to a frame side and multiplies by 32 in float; the window's coordinates go through int sums)
     constexpr int kMaxSide = 1 << 24;
     if (!in || !params || in_layout < 0 || in_layout > 2 || H <= 0 || W <= 0 || out_h <= 0 || out_w <= 0 || H > kMaxSide || W > kMaxSide ||
         out_h > kMaxSide || out_w > kMaxSide || oy < -kMaxSide || oy > kMaxSide || ox < -kMaxSide || ox > kMaxSide)
-        return fail(ctx, R2F_EINVAL, "lens_correct: bad arguments");
+        return fail(ctx, R2F_EINVAL, "%s: bad arguments", what);
     if (params->model < R2F_LENS_NONE || params->model > R2F_LENS_PTLENS)
-        return fail(ctx, R2F_EINVAL, "lens_correct: unknown distortion model %d", params->model);
+        return fail(ctx, R2F_EINVAL, "%s: unknown distortion model %d", what, params->model);
     int rc = check_rows(ctx, "lens dst", dst, 0, out_h);
     if (rc) return rc;
     if (!ctx->lens_table.p) {
@@ -584,9 +688,36 @@ int r2f_lens_correct(r2f_ctx* ctx, const void* in, int in_layout, int H, int W, 
         rc = upload(ctx, ctx->lens_table, host, sizeof host);  // (once per context)
         if (rc) return rc;
     }
-    const LensArgs a{in, in_layout, H, W, to_dev(dst), out_h, out_w, oy, ox, *params, static_cast<const float*>(ctx->lens_table.p)};
-    launch_k(lens_correct_kernel, dim3((out_w + 63) / 64, (out_h + 4 * kLensRows - 1) / (4 * kLensRows)), dim3(64, 4), 0,
-             static_cast<hipStream_t>(stream), a);
+    *a = LensArgs{in, in_layout, H, W, to_dev(dst), out_h, out_w, oy, ox, *params, static_cast<const float*>(ctx->lens_table.p)};
+    return R2F_OK;
+}
+
+static dim3 lens_grid(int out_h, int out_w) { return dim3((out_w + 63) / 64, (out_h + 4 * kLensRows - 1) / (4 * kLensRows)); }
+
+int r2f_lens_correct(r2f_ctx* ctx, const void* in, int in_layout, int H, int W, const r2f_lens_params* params, const r2f_planes* dst,
+                     int out_h, int out_w, int oy, int ox, void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    LensArgs a;
+    const int rc = lens_args(ctx, "lens_correct", in, in_layout, H, W, params, dst, out_h, out_w, oy, ox, &a);
+    if (rc) return rc;
+    launch_k(lens_correct_kernel, lens_grid(out_h, out_w), dim3(64, 4), 0, static_cast<hipStream_t>(stream), a);
+    R2F_HIP(ctx, take_launch_status());
+    return R2F_OK;
+}
+
+int r2f_lens_correct_tca(r2f_ctx* ctx, const void* in, int in_layout, int H, int W, const r2f_lens_params* params,
+                         const r2f_lens_tca_params* tca_params, const r2f_planes* dst, int out_h, int out_w, int oy, int ox, void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    if (!tca_params) return fail(ctx, R2F_EINVAL, "lens_correct_tca: bad arguments");
+    if (tca_params->model != R2F_TCA_LINEAR && tca_params->model != R2F_TCA_POLY3)
+        return fail(ctx, R2F_EINVAL, "lens_correct_tca: TCA model %d (without TCA the call is r2f_lens_correct)", tca_params->model);
+    LensTcaArgs a;
+    const int rc = lens_args(ctx, "lens_correct_tca", in, in_layout, H, W, params, dst, out_h, out_w, oy, ox, &a.lens);
+    if (rc) return rc;
+    a.tca = *tca_params;
+    launch_k(lens_correct_tca_kernel, lens_grid(out_h, out_w), dim3(64, 4), 0, static_cast<hipStream_t>(stream), a);
     R2F_HIP(ctx, take_launch_status());
     return R2F_OK;
 }

@@ -2,8 +2,9 @@
 
 Upstream corrects through lensfunpy (effects.py:22-43): it looks the camera and the lens up in lensfun's database and applies what
 it finds.  The lookup is third-party input; this module takes its RESULT -- a distortion model with its coefficients, a vignetting
-model, the optical centre, a scale -- and `plan()` turns it into the fp32 constants of one frame size (r2f_lens_plan, which also
-resolves scale="auto").  The definition of the correction is in include/r2f.h (r2f_lens_correct).
+model, the optical centre, a scale, TCA constants -- and `plan()` / `plan_tca()` turn it into the fp32 constants of one frame size
+(r2f_lens_plan, r2f_lens_plan_tca, which also resolve scale="auto").  The definition of the correction is in include/r2f.h
+(r2f_lens_correct, r2f_lens_correct_tca).
 """
 
 from __future__ import annotations
@@ -15,6 +16,7 @@ from dataclasses import dataclass
 from . import _lib
 
 _MODELS = {"none": (_lib.LENS_NONE, 0), "poly3": (_lib.LENS_POLY3, 1), "poly5": (_lib.LENS_POLY5, 2), "ptlens": (_lib.LENS_PTLENS, 3)}
+_TCA_MODELS = {"linear": (_lib.TCA_LINEAR, 1), "poly3": (_lib.TCA_POLY3, 3)}  # (enum, constants per channel)
 
 
 def _floats(name, values, n):
@@ -38,13 +40,17 @@ class LensProfile:
     vignetting: None or (k1, k2, k3), lensfun's "pa" model: the frame is divided by 1 + k1 r^2 + k2 r^4 + k3 r^6.
     center: (dx, dy) offset of the optical centre from the frame's, in units of r.
     scale: a positive float, or "auto" (the largest view that shows no border: r2f_lens_plan).
-    norm_radius_px: the pixel distance at which r = 1; None: half the diagonal, hypot(W - 1, H - 1) / 2."""
+    norm_radius_px: the pixel distance at which r = 1; None: half the diagonal, hypot(W - 1, H - 1) / 2.
+    tca: None, ("linear", (kr, kb)) or ("poly3", (vr, vb, cr, cb, br, bb)) -- transverse chromatic aberration, in the order of
+    lensfun's XML attributes: red and blue sample at the corrected coordinate's offset from the centre times kr / kb, or times
+    b Ru^2 + c Ru + v of their own constants (r2f_lens_correct_tca)."""
     distortion: str = "none"
     coefficients: tuple = ()
     vignetting: tuple | None = None
     center: tuple = (0.0, 0.0)
     scale: float | str = 1.0
     norm_radius_px: float | None = None
+    tca: tuple | None = None
 
     def __post_init__(self):
         if not isinstance(self.distortion, str) or self.distortion not in _MODELS:
@@ -67,6 +73,14 @@ class LensProfile:
             if norm <= 0:
                 raise ValueError(f"LensProfile.norm_radius_px must be positive, got {self.norm_radius_px!r}")
             set_("norm_radius_px", norm)
+        if self.tca is not None:
+            try:
+                model, values = self.tca
+            except (TypeError, ValueError):
+                raise ValueError(f"LensProfile.tca must be (model, numbers), got {self.tca!r}") from None
+            if not isinstance(model, str) or model not in _TCA_MODELS:
+                raise ValueError(f"LensProfile.tca's model must be one of {sorted(_TCA_MODELS)}, got {model!r}")
+            set_("tca", (model, _floats("tca", values, 2 * _TCA_MODELS[model][1])))
 
     def to_c(self) -> _lib.LensProfile:
         model, n = _MODELS[self.distortion]
@@ -87,3 +101,25 @@ class LensProfile:
         if _lib.load().r2f_lens_plan(C.byref(profile), int(H), int(W), C.byref(out)) != _lib.OK:
             raise ValueError(f"r2f_lens_plan refused {self!r} for a {H} x {W} frame")
         return out
+
+    def to_c_tca(self) -> _lib.LensTca | None:
+        """The r2f_lens_tca of `tca` -- (v, c, b) of red and of blue -- or None without one."""
+        if self.tca is None:
+            return None
+        model, values = self.tca
+        code, n = _TCA_MODELS[model]
+        t = _lib.LensTca(model=code, n_coef=n)
+        t.red[:n], t.blue[:n] = values[0::2], values[1::2]
+        return t
+
+    def plan_tca(self, H: int, W: int) -> tuple:
+        """(r2f_lens_params, r2f_lens_tca_params) of an H x W frame (no GPU; r2f_lens_plan_tca: with scale="auto" no channel may
+        show a border); (plan(H, W), None) for a profile without `tca`.  ValueError for what the planner refuses."""
+        tca = self.to_c_tca()
+        if tca is None:
+            return self.plan(H, W), None
+        out, out_tca = _lib.LensParams(), _lib.LensTcaParams()
+        profile = self.to_c()
+        if _lib.load().r2f_lens_plan_tca(C.byref(profile), C.byref(tca), int(H), int(W), C.byref(out), C.byref(out_tca)) != _lib.OK:
+            raise ValueError(f"r2f_lens_plan_tca refused {self!r} for a {H} x {W} frame")
+        return out, out_tca
