@@ -150,9 +150,7 @@ int r2f_create(int device, r2f_ctx** out) {
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return R2F_EHIP;
     DeviceGuard guard(device);  // the caller's current device is restored on return
     if (guard.status != hipSuccess) return R2F_EHIP;
-    if (init_kernel_attributes() != hipSuccess || fft_init_attributes() != hipSuccess ||
-        front_fast_init_attributes() != hipSuccess)
-        return R2F_EHIP;
+    if (init_kernel_attributes() != hipSuccess || front_fast_init_attributes() != hipSuccess) return R2F_EHIP;
     r2f_ctx* ctx = new r2f_ctx();
     ctx->device = device;
     if (ctx->frame_buf.reserve(ctx, sizeof(FrameParams), Grow::Quiet) != R2F_OK || hipMemset(ctx->frame_buf.p, 0, sizeof(FrameParams)) != hipSuccess ||
@@ -272,11 +270,7 @@ int r2f_set_kernel(r2f_ctx* ctx, int which, const float* k, int kh, int kw, int 
     }
     ++ctx->generation;
     s.built_q = 0;
-    for (int c = 0; c < 3; ++c) {
-        ctx->fft.kf_dims[which][c] = 0;
-        ctx->fft.last_real[which][c] = 0;
-        for (bool& v : ctx->fft.kf_valid[which][c]) v = false;
-    }
+    for (int c = 0; c < 3; ++c) ctx->fft.forget(which, c);
     if (which == R2F_KERNEL_GRAIN) ctx->grain_fixed_valid = false;
     ctx->stencil_fixed_valid[which] = false;
     return R2F_OK;
@@ -496,7 +490,7 @@ int r2f_stencil_stats(r2f_ctx* ctx, int which, int* out) {
         const int sep = which == R2F_KERNEL_GRAIN && fr && ctx->grain_fixed_valid && ctx->grain_sep && ctx->opt.grain_sep;
         o[0] = d.n_entries, o[1] = d.n_rowsteps, o[2] = d.n_phases, o[3] = d.sym | (fr << 1) | (sep << 8);
         o[4] = d.kh, o[5] = d.kw, o[6] = set.built_q;
-        o[7] = fft_eligible(ctx, set, c) ? 1 | (ctx->fft.kf_dims[which][c] << 1) | (ctx->fft.last_real[which][c] << 30) : 0;
+        o[7] = fft_eligible(ctx, set, c) ? 1 | (ctx->fft.last[which][c].dims << 1) | (ctx->fft.last[which][c].real << 30) : 0;
     }
     return R2F_OK;
 }

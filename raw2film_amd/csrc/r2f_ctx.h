@@ -161,18 +161,25 @@ struct r2f_ctx {
     struct Fft {
         static constexpr int kShapes = 6;  // {256, 512} rows x {256, 512, 1024} columns
         static int shape_index(int ny, int nx) { return (ny == 512 ? 3 : 0) + (nx == 256 ? 0 : (nx == 512 ? 1 : 2)); }
-        r2f::DeviceBuf tw, kf[3][3][kShapes], s1, kimg;
-        bool kf_valid[3][3][kShapes] = {};
-        bool kf_real[3][3][kShapes] = {};  // what the cached spectrum of (stencil, channel, shape) holds
-        int kf_dims[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};  // window shape (ny * 4096 + nx) of the channel's last launch
-        int last_real[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};  // ... and whether that launch multiplied by a real spectrum
+        r2f::DeviceBuf tw, s1, kimg;
+        struct Spectrum {  // of one (stencil, channel, window shape)
+            r2f::DeviceBuf buf;
+            bool valid = false, real = false;  // built for the stencil's current taps; laid out for a real spectrum
+        } spectrum[3][3][kShapes];
+        struct Last {  // one (stencil, channel)'s last launch, for r2f_stencil_stats: its window (ny * 4096 + nx), a real spectrum?
+            int dims = 0, real = 0;
+        } last[3][3];
+        void forget(int which, int c) {  // the stencil's taps changed (r2f_set_kernel)
+            last[which][c] = Last();
+            for (Spectrum& sp : spectrum[which][c]) sp.valid = false;
+        }
         // two internal streams take alternate batches (each with its own half of the scratch), so the tail of one launch
         // overlaps the head of the other stream's; fenced against the caller's stream with events
         hipStream_t stream[4] = {nullptr, nullptr, nullptr, nullptr};
         hipEvent_t ev_in = nullptr, ev_out[4] = {nullptr, nullptr, nullptr, nullptr};
-        int cu_count = 0;  // multiprocessors of the context's device (grid size of the resident pass 2)
         ~Fft();
     } fft;
+    int cu_count = 0;  // multiprocessors of the context's device, asked for once (device_cu_count)
     // kernel_timing: the event pairs of the timed launches, [pass + 3 * (complex64 scratch ? 1 : 0)], until r2f_kernel_timing reads them
     std::vector<std::pair<hipEvent_t, hipEvent_t>> timing_ev[6];
     double timing_bytes[6] = {0, 0, 0, 0, 0, 0};
@@ -245,12 +252,12 @@ int fail(r2f_ctx* ctx, int code, const char* fmt, ...);
 // The multiprocessors of the context's device, asked for once: what the resident grids (the FFT's column walk, r2f_mosaic_maximum)
 // are sized by.
 inline int device_cu_count(r2f_ctx* ctx, int* out) {
-    if (!ctx->fft.cu_count) {
+    if (!ctx->cu_count) {
         int n = 0;
         R2F_HIP(ctx, hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, ctx->device));
-        ctx->fft.cu_count = n > 0 ? n : 256;
+        ctx->cu_count = n > 0 ? n : 256;
     }
-    *out = ctx->fft.cu_count;
+    *out = ctx->cu_count;
     return R2F_OK;
 }
 

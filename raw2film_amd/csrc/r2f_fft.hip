@@ -855,88 +855,36 @@ __global__ __launch_bounds__(kFftThreads) __attribute__((amdgpu_waves_per_eu(EPI
 // ---------------------------------------------------------------------------------------------------- launchers
 static size_t fft_lds_bytes() { return (size_t)(kFftThreads / 64) * 4 * kTLine * sizeof(double); }
 
-
-template <int XL>
-static void launch_rows_fwd(const FftConvArgs& a, hipStream_t s) {
-    const dim3 block(kFftThreads), grid(a.ny / RowGeom<XL>::ROWS, a.npairs);
-    if (a.s32 == 1)
-        launch_k((fft_rows_fwd_kernel<XL, 1>), grid, block, fft_lds_bytes(), s, a);
-    else if (a.s32 == 3)
-        launch_k((fft_rows_fwd_kernel<XL, 3>), grid, block, fft_lds_bytes(), s, a);
-    else if (a.s32 == 2)
-        launch_k((fft_rows_fwd_kernel<XL, 2>), grid, block, fft_lds_bytes(), s, a);
+// The two run-time values every launcher turns into template arguments, each in one place.  f is called with a
+// std::integral_constant, so its body names the kernel with `decltype(v)::value`.
+template <int V>
+using Const = std::integral_constant<int, V>;
+// a.s32 -> the kernel's scratch element ST: the one of `Admitted...` it names, complex128 (0) otherwise.
+template <int... Admitted, typename F>
+static void with_element(int s32, F&& f) {
+    if (!((s32 == Admitted && (f(Const<Admitted>{}), true)) || ...)) f(Const<0>{});
+}
+// a.nx -> the column class XL: 0 / 1 / 2 = 256 / 512 / 1024 columns (16 << XL column blocks of 16 for the column passes).
+template <typename F>
+static void with_columns(int nx, F&& f) {
+    if (nx == 1024)
+        f(Const<2>{});
+    else if (nx == 512)
+        f(Const<1>{});
     else
-        launch_k((fft_rows_fwd_kernel<XL, 0>), grid, block, fft_lds_bytes(), s, a);
+        f(Const<0>{});
 }
 
 hipError_t launch_fft_rows_fwd(const FftConvArgs& a, hipStream_t s) {
-    if (a.nx == 1024)
-        launch_rows_fwd<2>(a, s);
-    else if (a.nx == 512)
-        launch_rows_fwd<1>(a, s);
-    else
-        launch_rows_fwd<0>(a, s);
+    with_columns(a.nx, [&](auto xl) {
+        constexpr int XL = decltype(xl)::value;
+        const dim3 grid(a.ny / RowGeom<XL>::ROWS, a.npairs);
+        with_element<1, 2, 3>(a.s32, [&](auto st) {
+            launch_k((fft_rows_fwd_kernel<XL, decltype(st)::value>), grid, dim3(kFftThreads), fft_lds_bytes(), s, a);
+        });
+    });
     return take_launch_status();
 }
-
-template <int NBX, bool Y512, bool KR>
-static void launch_cols_kr(const FftConvArgs& a, int mode, hipStream_t s) {
-    const dim3 block(kFftThreads), grid(a.nx / (Y512 ? 8 : 16), a.npairs);
-    if (a.s32 == 1)
-        launch_k((fft_cols_kernel<NBX, Y512, 1, KR>), grid, block, fft_lds_bytes(), s, a, mode);
-    else if (a.s32 == 2)
-        launch_k((fft_cols_kernel<NBX, Y512, 2, KR>), grid, block, fft_lds_bytes(), s, a, mode);
-    else
-        launch_k((fft_cols_kernel<NBX, Y512, 0, KR>), grid, block, fft_lds_bytes(), s, a, mode);
-}
-
-template <int NBX, bool Y512>
-static void launch_cols(const FftConvArgs& a, int mode, hipStream_t s) {
-    if (a.kreal)
-        launch_cols_kr<NBX, Y512, true>(a, mode, s);
-    else
-        launch_cols_kr<NBX, Y512, false>(a, mode, s);
-}
-
-template <bool Y512>
-static void launch_cols_nx(const FftConvArgs& a, int mode, hipStream_t s) {
-    if (a.nx == 1024)
-        launch_cols<64, Y512>(a, mode, s);
-    else if (a.nx == 512)
-        launch_cols<32, Y512>(a, mode, s);
-    else
-        launch_cols<16, Y512>(a, mode, s);
-}
-
-// The walk applies to 256-row windows with a real spectrum in convolution mode.
-static bool cols_walk_applies(const FftConvArgs& a, int mode) { return a.cols_walk && mode == 0 && a.ny == 256 && a.kreal; }
-
-template <int NBX>
-static void launch_cols_walk_st(const FftConvArgs& a, dim3 grid, hipStream_t s) {
-    const dim3 block(kFftThreads);
-    if (a.s32 == 1)
-        launch_k((fft_cols_walk_kernel<NBX, 1>), grid, block, fft_lds_bytes(), s, a);
-    else if (a.s32 == 3)
-        launch_k((fft_cols_walk_kernel<NBX, 3>), grid, block, fft_lds_bytes(), s, a);
-    else if (a.s32 == 2)
-        launch_k((fft_cols_walk_kernel<NBX, 2>), grid, block, fft_lds_bytes(), s, a);
-    else
-        launch_k((fft_cols_walk_kernel<NBX, 0>), grid, block, fft_lds_bytes(), s, a);
-}
-
-static void launch_cols_walk(const FftConvArgs& a, hipStream_t s) {
-    // as many workgroups as fit the GPU at two per CU (cols_slots), every one walking the same number of pairs when that divides
-    const int cb = a.nx / 16, per = std::max(1, a.cols_slots / cb), iters = (a.npairs + per - 1) / per, G = (a.npairs + iters - 1) / iters;
-    const dim3 grid(cb, G);
-    if (a.nx == 1024)
-        launch_cols_walk_st<64>(a, grid, s);
-    else if (a.nx == 512)
-        launch_cols_walk_st<32>(a, grid, s);
-    else
-        launch_cols_walk_st<16>(a, grid, s);
-}
-
-hipError_t fft_init_attributes() { return hipSuccess; }
 
 hipError_t launch_fft_decide(const FftConvArgs& a, const RangeRecord& rec, float bound, float floor_, int* flags, hipStream_t s) {
     if (a.ppc <= 0) return hipSuccess;
@@ -944,61 +892,72 @@ hipError_t launch_fft_decide(const FftConvArgs& a, const RangeRecord& rec, float
     return take_launch_status();
 }
 
+// One workgroup per column block and pair.  (No per-pair element here: a call that chooses on the device takes the walk below, and
+// spectrum builds are complex128.)
+template <bool Y512, bool KR>
+static void launch_cols(const FftConvArgs& a, int mode, hipStream_t s) {
+    const dim3 grid(a.nx / (Y512 ? 8 : 16), a.npairs);
+    with_columns(a.nx, [&](auto xl) {
+        constexpr int NBX = 16 << decltype(xl)::value;
+        with_element<1, 2>(a.s32, [&](auto st) {
+            launch_k((fft_cols_kernel<NBX, Y512, decltype(st)::value, KR>), grid, dim3(kFftThreads), fft_lds_bytes(), s, a, mode);
+        });
+    });
+}
+
+// The walk applies to 256-row windows with a real spectrum in convolution mode.
+static bool cols_walk_applies(const FftConvArgs& a, int mode) { return a.cols_walk && mode == 0 && a.ny == 256 && a.kreal; }
+
+static void launch_cols_walk(const FftConvArgs& a, hipStream_t s) {
+    // as many workgroups as fit the GPU at two per CU (cols_slots), every one walking the same number of pairs when that divides
+    const int cb = a.nx / 16, per = std::max(1, a.cols_slots / cb), iters = (a.npairs + per - 1) / per, G = (a.npairs + iters - 1) / iters;
+    const dim3 grid(cb, G);
+    with_columns(a.nx, [&](auto xl) {
+        constexpr int NBX = 16 << decltype(xl)::value;
+        with_element<1, 2, 3>(a.s32, [&](auto st) {
+            launch_k((fft_cols_walk_kernel<NBX, decltype(st)::value>), grid, dim3(kFftThreads), fft_lds_bytes(), s, a);
+        });
+    });
+}
+
 hipError_t launch_fft_cols(const FftConvArgs& a, int mode, hipStream_t s) {
-    if (cols_walk_applies(a, mode)) {
+    if (cols_walk_applies(a, mode))
         launch_cols_walk(a, s);
-        return take_launch_status();
-    }
-    if (a.ny == 512)
-        launch_cols_nx<true>(a, mode, s);
+    else if (a.ny == 512)
+        a.kreal ? launch_cols<true, true>(a, mode, s) : launch_cols<true, false>(a, mode, s);
     else
-        launch_cols_nx<false>(a, mode, s);
+        a.kreal ? launch_cols<false, true>(a, mode, s) : launch_cols<false, false>(a, mode, s);
     return take_launch_status();
 }
 
-template <int XL, int EPI>
+template <int EPI>
 static void launch_rows_inv(const FftConvArgs& a0, hipStream_t s) {
-    const int rows = RowGeom<XL>::ROWS;
-    const dim3 grid(((a0.oy & (rows - 1)) + a0.vy + rows - 1) / rows, a0.npairs);  // rows without valid outputs are never stored
     FftConvArgs a = a0;
     size_t lds = fft_lds_bytes();
     a.epi_lds_off = 0;
-    // the epilogue's curve cells behind the transpose buffers, while three workgroups still fit a CU (the kernel's registers allow
-    // three waves per SIMD): up to 1 152 cells (18 KB) -- a 1 024-point curve; longer curves gather from global memory
-    if (EPI == 2) {
+    if (EPI == 2) {  // the curve cells behind the transpose buffers
         a.epi_lds_off = (int)(lds / sizeof(double));
         lds += (size_t)(a.curve.m - 1) * sizeof(float4);
     }
-    if (a.s32 == 1)
-        launch_k((fft_rows_inv_kernel<XL, EPI, 1>), grid, dim3(kFftThreads), lds, s, a);
-    else if (a.s32 == 3)
-        launch_k((fft_rows_inv_kernel<XL, EPI, 3>), grid, dim3(kFftThreads), lds, s, a);
-    else if (a.s32 == 2)
-        launch_k((fft_rows_inv_kernel<XL, EPI, 2>), grid, dim3(kFftThreads), lds, s, a);
-    else
-        launch_k((fft_rows_inv_kernel<XL, EPI, 0>), grid, dim3(kFftThreads), lds, s, a);
+    with_columns(a.nx, [&](auto xl) {
+        constexpr int XL = decltype(xl)::value, rows = RowGeom<XL>::ROWS;
+        const dim3 grid(((a.oy & (rows - 1)) + a.vy + rows - 1) / rows, a.npairs);  // rows without valid outputs are never stored
+        with_element<1, 2, 3>(a.s32, [&](auto st) {
+            launch_k((fft_rows_inv_kernel<XL, EPI, decltype(st)::value>), grid, dim3(kFftThreads), lds, s, a);
+        });
+    });
 }
 
-template <int XL>
-static void launch_rows_inv_epi(const FftConvArgs& a, hipStream_t s) {
+hipError_t launch_fft_rows_inv(const FftConvArgs& a, hipStream_t s) {
     // the epilogue's curve cells behind the transpose buffers while three workgroups still fit a CU (the kernel's registers allow
     // three waves per SIMD): up to 1 152 cells (18 KB) -- a 1 024-point curve -- of a curve whose first guess is never more than
     // a cell off (DevCurve::near: any near-uniform axis); anything else gathers from global memory through the generic walk
     if (a.epilogue == 1 && a.epi_lds && a.curve.near && (size_t)(a.curve.m - 1) * sizeof(float4) + fft_lds_bytes() <= 53 * 1024)
-        launch_rows_inv<XL, 2>(a, s);
+        launch_rows_inv<2>(a, s);
     else if (a.epilogue == 1)
-        launch_rows_inv<XL, 1>(a, s);
+        launch_rows_inv<1>(a, s);
     else
-        launch_rows_inv<XL, 0>(a, s);
-}
-
-hipError_t launch_fft_rows_inv(const FftConvArgs& a, hipStream_t s) {
-    if (a.nx == 1024)
-        launch_rows_inv_epi<2>(a, s);
-    else if (a.nx == 512)
-        launch_rows_inv_epi<1>(a, s);
-    else
-        launch_rows_inv_epi<0>(a, s);
+        launch_rows_inv<0>(a, s);
     return take_launch_status();
 }
 

@@ -211,7 +211,6 @@ struct FftConvArgs {
     int epi_lds;              // pass 3 with the epilogue: 1 = the channel's curve cells may be copied to LDS (A/B knob)
     int epi_lds_off;          // set by the launcher: offset (in doubles) of those cells in the dynamic LDS, 0 = gather from global memory
 };
-hipError_t fft_init_attributes();
 hipError_t launch_fft_rows_fwd(const FftConvArgs& a, hipStream_t s);
 hipError_t launch_fft_cols(const FftConvArgs& a, int mode, hipStream_t s);
 hipError_t launch_fft_rows_inv(const FftConvArgs& a, hipStream_t s);

@@ -281,7 +281,8 @@ bool fft_window(const FftOptions& o, int bh, int bw, int W, int H, bool s32, int
         for (int x = 256; x <= 1024; x *= 2) {
             if (x > window_max && x != o.window) continue;
             if (bw > 200 ? (x < 512 || (o.window >= 512 && x != o.window)) : (o.window && x != o.window)) continue;
-            const int vy = y - bh + 1, vx = (x - bw + 1) & ~3;
+            int vy, vx;
+            fft_valid(y, x, bh, bw, &vy, &vx);
             if (vy < 1 || vx < 4) continue;  // the window has to keep outputs (and vx, vy divide below)
             const double n = (double)y * x, part = n * vy / y;
             // per window: pass 1 (floats in, image out), pass 2 (image in, valid rows out), pass 3 (valid rows in, floats out);
@@ -299,8 +300,7 @@ bool fft_window(const FftOptions& o, int bh, int bw, int W, int H, bool s32, int
 FftBatches fft_batches(const FftOptions& o, int ny, int nx, int bh, int bw, int W, int y0, int y1, int nch, int elem_bytes) {
     FftBatches b;
     b.ny = ny, b.nx = nx;
-    b.vy = ny - bh + 1;
-    b.vx = (nx - bw + 1) & ~3;  // a multiple of 4: window origins stay 16-byte aligned for the float4 stores of pass 3
+    fft_valid(ny, nx, bh, bw, &b.vy, &b.vx);
     if (b.vy < 1 || b.vx < 4 || nch < 1 || y1 <= y0 || W < 1) return b;
     b.gx = (W + b.vx - 1) / b.vx;
     b.ntiles = b.gx * ((y1 - y0 + b.vy - 1) / b.vy);
@@ -322,6 +322,47 @@ FftBatches fft_batches(const FftOptions& o, int ny, int nx, int bh, int bw, int 
     b.launches = (b.pairs + b.batch - 1) / b.batch;
     b.scratch_bytes = (size_t)b.batch * b.nstreams * b.img_bytes;
     return b;
+}
+
+void FftCallIn::take_options(const Options& o) {
+    fo.window = o.fft_window, fo.window_max = o.fft_window_max, fo.window_rows = o.fft_window_rows;
+    fo.batch_mib = o.fft_batch, fo.streams = o.fft_streams, fo.even = o.fft_even;
+    fft_s32 = o.fft_s32, fft_s96 = o.fft_s96, fft_s96_auto = o.fft_s96_auto;
+    fft_real = o.fft_real, fft_mixed_sign = o.fft_mixed_sign, fft_cols_walk = o.fft_cols_walk;
+}
+
+FftCall fft_call(const FftCallIn& in) {
+    FftCall c;
+    // A channel with cancelling taps keeps complex128 scratch whatever the masks say: no float32 (or 48-bit) rounding between the
+    // passes either (fft_eligible).
+    const bool cancelling = in.any_mixed_sign && in.fft_mixed_sign;
+    const bool complex64 = ((in.fft_s32 >> in.which) & 1) && !cancelling;
+    // The window is chosen for the rows of THIS call, not of the global frame (a row shard's 1 058-row call is 6.15 window rows of
+    // 172 and should not be planned as if the seventh were free; a whole-frame call sees the frame), and priced with complex64 or
+    // complex128 scratch only: the 12-byte element is an A/B of the same windows.
+    int ny = 0, nx = 0;
+    if (!fft_window(in.fo, in.bh, in.bw, in.W, in.y1 - in.y0, complex64, &ny, &nx)) return c;
+    c.ok = true;
+    // Real spectra: every channel of the group centrally symmetric around an anchor at the centre of its (odd x odd) box
+    c.kreal = in.fft_real && in.symmetric ? 1 : 0;
+    c.oy = c.kreal ? in.ay : 0;
+    c.ox = c.kreal ? in.ax : 0;
+    c.element = cancelling ? 0 : (((in.fft_s96 >> in.which) & 1) ? 2 : (complex64 ? 1 : 0));
+    // The halation of a whole-frame render whose front kernel recorded the range of the exposure planes: element chosen on the
+    // device.  The guard compares a window's SAMPLES; it speaks for the outputs only under a stencil of unit gain (the reference's
+    // halation kernels are normalised and non-negative, effects.py:200-217): taps that cancel or sum to 0.01 make outputs far below
+    // the samples.  (The per-pair choice is read by the column walk of 256-row windows with a real spectrum.)
+    if (c.element == 0 && in.which == R2F_KERNEL_HALATION && in.epilogue == 1 && in.dyn && in.fft_s96_auto && c.kreal && in.all_unit_gain && ny == 256 &&
+        in.fft_cols_walk && in.curve_set)
+        c.element = 3;
+    c.elem_bytes = c.element == 1 ? 8 : (c.element == 2 ? 12 : 16);
+    c.timing_offset = c.element == 1 ? 3 : 0;
+    c.b = fft_batches(in.fo, ny, nx, in.bh, in.bw, in.W, in.y0, in.y1, in.nch, c.elem_bytes);
+    const double img = (double)((size_t)ny * nx), full = (double)c.b.img_bytes, part = full * c.b.vy / ny;
+    c.pass_bytes[0] = 2.0 * img * sizeof(float) + full;
+    c.pass_bytes[1] = full + part;
+    c.pass_bytes[2] = part + 2.0 * c.b.vy * c.b.vx * sizeof(float);
+    return c;
 }
 
 // ------------------------------------------------------------------------------------------------ tables
@@ -694,11 +735,14 @@ int r2f_plan_fft(int bh, int bw, int W, int rows, int nch, int scratch_elem_byte
     if ((window != 0 && window != 256 && window != 512 && window != 1024) || (window_rows != 0 && window_rows != 256 && window_rows != 512) ||
         (window_max != 256 && window_max != 512 && window_max != 1024) || batch_mib < 1 || streams < 1 || streams > 4)
         return R2F_EINVAL;
-    FftOptions o;
-    o.window = window, o.window_rows = window_rows, o.window_max = window_max, o.batch_mib = batch_mib, o.streams = streams;
-    int ny = 0, nx = 0;
-    if (!fft_window(o, bh, bw, W, rows, scratch_elem_bytes == 8, &ny, &nx)) return R2F_EINVAL;
-    const FftBatches b = fft_batches(o, ny, nx, bh, bw, W, 0, rows, nch, scratch_elem_bytes);
+    // (the elements as the option masks of a halation call ask for them: the device call's own path through fft_call)
+    FftCallIn in;
+    in.bh = bh, in.bw = bw, in.nch = nch, in.W = W, in.y1 = rows;
+    in.fo.window = window, in.fo.window_rows = window_rows, in.fo.window_max = window_max, in.fo.batch_mib = batch_mib, in.fo.streams = streams;
+    in.fft_s32 = scratch_elem_bytes == 8, in.fft_s96 = scratch_elem_bytes == 12;
+    const FftCall call = fft_call(in);
+    if (!call.ok) return R2F_EINVAL;
+    const FftBatches& b = call.b;
     out->ny = b.ny, out->nx = b.nx, out->vy = b.vy, out->vx = b.vx, out->gx = b.gx, out->ntiles = b.ntiles;
     out->pairs_per_channel = b.ppc, out->pairs = b.pairs, out->streams = b.nstreams, out->batch = b.batch, out->launches = b.launches;
     out->scratch_bytes = b.scratch_bytes;

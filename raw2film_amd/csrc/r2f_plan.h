@@ -1,5 +1,5 @@
 // r2f_plan.h -- the host-side planners of libr2f_hip.so, free of HIP: everything the host units (r2f_api.hip, r2f_stencil.hip)
-// decide on the CPU before they upload a table or launch a kernel (the option table, tap boxes and their device entry lists, FFT window shapes and batch sizes, tile orders,
+// decide on the CPU before they upload a table or launch a kernel (the option table, tap boxes and their device entry lists, every decision of a call of the FFT form (fft_call: window, scratch element, batches and their walk), tile orders,
 // LANCZOS4 / Gaussian tables, curve cells, workspace sizes).  Plain C++ so that the same translation unit also builds with
 // `g++ -fsanitize=address,undefined` into the fuzz harness of tests/test_plan_sanitizers.py (GPU-side sanitizers are not available on
 // this pool; this is the part of the library that can run under one).  Nothing here touches the device.
@@ -76,8 +76,53 @@ struct FftBatches {
     int nstreams = 1, batch = 0, launches = 0;
     size_t img_bytes = 0, scratch_bytes = 0;
 };
+// Outputs a window keeps of a bh x bw tap box (the one statement of the rule: fft_window prices with it, fft_batches tiles with it).
+inline void fft_valid(int ny, int nx, int bh, int bw, int* vy, int* vx) {
+    *vy = ny - bh + 1;
+    *vx = (nx - bw + 1) & ~3;  // a multiple of 4: window origins stay 16-byte aligned for the float4 stores of pass 3
+}
 // Tiling of output rows [y0, y1) x W columns into window pairs and their batches; elem_bytes: 16 (complex128), 8 or 12.
 FftBatches fft_batches(const FftOptions& o, int ny, int nx, int bh, int bw, int W, int y0, int y1, int nch, int elem_bytes);
+
+struct Options;
+// Every host decision of ONE call of the FFT form (run_stencil_fft), from plain facts: what the device call launches and what
+// r2f_plan_fft reports are both read off the FftCall this returns.
+struct FftCallIn {
+    int bh = 0, bw = 0;  // the group's tap box
+    int ay = 0, ax = 0;  // the anchor inside it (kh / 2 - box[0], kw / 2 - box[2]: cv.filter2D's default anchor)
+    int nch = 1, which = 0, W = 0, y0 = 0, y1 = 0;
+    // the group's channels: any with taps of both signs?  all of unit gain?  all centrally symmetric (centrally_symmetric)?
+    bool any_mixed_sign = false, all_unit_gain = false, symmetric = false;
+    // the caller: its epilogue, whether it vouches for the exposure-range record (run_stencil's dyn), whether a density curve is set
+    int epilogue = 0;
+    bool dyn = false, curve_set = false;
+    FftOptions fo;
+    int fft_s32 = 0, fft_s96 = 0, fft_s96_auto = 0, fft_real = 0, fft_mixed_sign = 0, fft_cols_walk = 0;  // as in Options
+    void take_options(const Options& o);
+};
+struct FftBatch {
+    int pair0, npairs, lane;
+    size_t scratch_offset;  // bytes into the call's scratch: a lane's batches share one slice of it
+};
+struct FftCall {
+    bool ok = false;  // false: no window shape fits the box under the window options (nothing else is filled in)
+    int kreal = 0, oy = 0, ox = 0;  // real spectrum (the box laid out with its anchor on the window origin), and that origin shift
+    // scratch element (FftConvArgs::s32): 0 complex128, 1 complex64, 2 the 12-byte element, 3 complex128 or 12 bytes per window
+    // pair, chosen on the device (batches are sized for complex128)
+    int element = 0;
+    int elem_bytes = 16;   // what the batches are sized by
+    int timing_offset = 0;  // added to a pass's timing class (kernel_timing: complex64 launches are classes 3-5)
+    FftBatches b;           // window, valid outputs, tiling, batches (ny, nx, vy, vx, gx, ntiles, ppc, pairs, nstreams, batch, ...)
+    // algorithmic bytes of the three passes PER PAIR: window floats in (2 per pair) + scratch image out; scratch in + valid rows
+    // out; valid rows in + valid outputs out.  (The kernel spectrum, 1 MB, stays in L2.)
+    double pass_bytes[3] = {0, 0, 0};
+    // batch i of b.launches: `batch` pairs from pair i * batch on, dealt to the lanes in turn
+    FftBatch batch(int i) const {
+        const int p0 = i * b.batch, lane = i % b.nstreams;
+        return {p0, b.pairs - p0 < b.batch ? b.pairs - p0 : b.batch, lane, (size_t)lane * b.batch * b.img_bytes};
+    }
+};
+FftCall fft_call(const FftCallIn& in);
 
 // Is every channel of `chans` centrally symmetric bit for bit (k[i][j] == k[bh-1-i][bw-1-j]) inside `box`, an odd x odd box whose
 // centre is the anchor (kh / 2, kw / 2)?  Such a box, laid out with its anchor on the window origin, has a real spectrum.

@@ -1,5 +1,6 @@
 // r2f_stencil.hip -- the stencil stages' dispatch: a stencil's device forms (entry lists, tile orders, the unrolled fixed form, FFT
-// spectra) built on demand, and the choice between them per channel (run_stencil).
+// spectra) built on demand, and the choice between them per channel (run_stencil).  The FFT form's call (run_stencil_fft) is a
+// sequence of named steps around plan::fft_call: see the section "FFT form" below.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -145,196 +146,202 @@ void dyn_rule(const r2f_ctx* ctx, float* bound, float* floor) {
     *floor = (float)std::pow(10.0, (double)ctx->curve.x0);
 }
 
-static plan::FftOptions fft_options(const r2f_ctx* ctx) {
-    plan::FftOptions o;
-    o.window = ctx->opt.fft_window;
-    o.window_max = ctx->opt.fft_window_max;
-    o.window_rows = ctx->opt.fft_window_rows;
-    o.batch_mib = ctx->opt.fft_batch;
-    o.streams = ctx->opt.fft_streams;
-    o.even = ctx->opt.fft_even;
-    return o;
+// ------------------------------------------------------------------------------------------------ FFT form
+// One call = the channels `chans` of a stencil (all with the same tap box) as fp64 overlap-save FFT correlations (r2f_fft.hip); their
+// window pairs share the launches.  Everything the host decides about the call is plan::fft_call's (window, real spectrum, scratch
+// element, batches, timing classes and bytes: r2f_plan.cpp, pinned on the CPU by tests/test_fft_call_host.py); what follows owns
+// the device side of it -- the twiddle table, the spectrum cache, the lanes, the timing bracket -- and run_stencil_fft strings them.
+
+// The facts fft_call plans from: the group's tap box and anchor, what r2f_set_kernel noted of its channels, the caller, the options.
+static plan::FftCallIn fft_call_facts(const r2f_ctx* ctx, int which, const int* chans, int nch, const int box[4], int y0, int y1, int W,
+                                      int epilogue, bool dyn) {
+    const StencilSet& set = ctx->stencil[which];
+    plan::FftCallIn in;
+    in.bh = box[1] - box[0] + 1, in.bw = box[3] - box[2] + 1;
+    in.ay = set.kh / 2 - box[0], in.ax = set.kw / 2 - box[2];
+    in.nch = nch, in.which = which, in.W = W, in.y0 = y0, in.y1 = y1;
+    in.all_unit_gain = true;
+    for (int i = 0; i < nch; ++i) {
+        in.any_mixed_sign = in.any_mixed_sign || set.mixed_sign[chans[i]];
+        in.all_unit_gain = in.all_unit_gain && set.unit_gain[chans[i]];
+    }
+    in.symmetric = plan::centrally_symmetric(set.taps(), chans, nch, box);
+    in.epilogue = epilogue, in.dyn = dyn, in.curve_set = ctx->curve.cells != nullptr;
+    in.take_options(ctx->opt);
+    return in;
 }
 
-// The channels `chans` of a stencil (all with the same tap box) as fp64 overlap-save FFT correlations (r2f_fft.hip);
-// their window pairs share the launches.
-// dyn: the caller vouches that the context's exposure-range record (its tiles) was kept for the samples `src` holds this frame: the
-// passes may then choose their scratch element on the device, per window pair (FftConvArgs::dyn_flags, fft_decide_kernel).
-static int run_stencil_fft(r2f_ctx* ctx, int which, const int* chans, int nch, const r2f_planes* src, const r2f_planes* dst, int y0,
-                           int y1, int W, int H, int epilogue, float log_eps, hipStream_t s, bool dyn) {
-    StencilSet& set = ctx->stencil[which];
-    int b[4];
-    plan::tap_box(set.taps(), chans[0], b);
-    const int bh = b[1] - b[0] + 1, bw = b[3] - b[2] + 1;
-    int ny = 256, nx = 256;
-    // (the rows of THIS call, not of the global frame: a row shard's 1 058-row call is 6.15 window rows of 172 and should not be
-    // planned as if the seventh were free -- VERDICT r3, next 4; a whole-frame call sees the frame as before)
-    const plan::FftOptions fo = fft_options(ctx);
-    // scratch element of THIS launch: complex64 only where the stencil's bit says so and no channel of the group has cancelling taps
-    // (those keep complex128: no float32 rounding between the passes either) -- the window choice is priced with it
-    bool s32_eff = (ctx->opt.fft_s32 >> which) & 1;
-    for (int i = 0; i < nch; ++i)
-        if (set.mixed_sign[chans[i]] && ctx->opt.fft_mixed_sign) s32_eff = false;
-    if (!plan::fft_window(fo, bh, bw, W, y1 - y0, s32_eff, &ny, &nx))
-        return fail(ctx, R2F_EINVAL, "stencil %d: no FFT window shape fits a %d x %d tap box under the current stencil_fft_window* options",
-                    which, bh, bw);
-    const size_t img = (size_t)ny * nx;
-    const int shape = r2f_ctx::Fft::shape_index(ny, nx);
-    if (!ctx->fft.tw.p) {
-        // W_256^k, k < 256, then W_512^k, k < 256, then W_1024^k, k < 64
-        std::vector<double> tw(4 * kFftN + 2 * 64);
-        const double pi = 3.14159265358979323846264338327950288;
-        for (int k = 0; k < kFftN; ++k) {
-            tw[2 * k] = std::cos(-2.0 * pi * k / kFftN), tw[2 * k + 1] = std::sin(-2.0 * pi * k / kFftN);
-            tw[2 * (kFftN + k)] = std::cos(-pi * k / kFftN), tw[2 * (kFftN + k) + 1] = std::sin(-pi * k / kFftN);
-        }
-        for (int k = 0; k < 64; ++k)
-            tw[2 * (2 * kFftN + k)] = std::cos(-2.0 * pi * k / 1024.0), tw[2 * (2 * kFftN + k) + 1] = std::sin(-2.0 * pi * k / 1024.0);
-        int rc = upload(ctx, ctx->fft.tw, tw.data(), tw.size() * sizeof(double));
-        if (rc) return rc;
+// W_256^k, k < 256, then W_512^k, k < 256, then W_1024^k, k < 64: built and uploaded once per context.
+static int ensure_twiddles(r2f_ctx* ctx) {
+    if (ctx->fft.tw.p) return R2F_OK;
+    std::vector<double> tw(4 * kFftN + 2 * 64);
+    const double pi = 3.14159265358979323846264338327950288;
+    for (int k = 0; k < kFftN; ++k) {
+        tw[2 * k] = std::cos(-2.0 * pi * k / kFftN), tw[2 * k + 1] = std::sin(-2.0 * pi * k / kFftN);
+        tw[2 * (kFftN + k)] = std::cos(-pi * k / kFftN), tw[2 * (kFftN + k) + 1] = std::sin(-pi * k / kFftN);
     }
+    for (int k = 0; k < 64; ++k)
+        tw[2 * (2 * kFftN + k)] = std::cos(-2.0 * pi * k / 1024.0), tw[2 * (2 * kFftN + k) + 1] = std::sin(-2.0 * pi * k / 1024.0);
+    return upload(ctx, ctx->fft.tw, tw.data(), tw.size() * sizeof(double));
+}
+
+// What every launch of the call -- a spectrum build or a batch -- is told of its windows.
+static FftConvArgs fft_window_args(const r2f_ctx* ctx, const plan::FftCallIn& in, const plan::FftCall& call, int cus) {
     FftConvArgs a;
     memset(&a, 0, sizeof a);
     a.tw = static_cast<const double2*>(ctx->fft.tw.p);
     a.tw512 = a.tw + kFftN;
     a.tw1024 = a.tw + 2 * kFftN;
-    a.ny = ny, a.nx = nx;
-    a.ay = set.kh / 2 - b[0];  // anchor (kh/2, kw/2): cv.filter2D's default
-    a.ax = set.kw / 2 - b[2];
-    a.vy = ny - bh + 1;
-    a.vx = (nx - bw + 1) & ~3;  // a multiple of 4: window origins stay 16-byte aligned for the float4 stores of pass 3
-    // Real spectra: every channel of the group centrally symmetric around an anchor at the centre of its (odd x odd) box
-    const bool kreal = ctx->opt.fft_real && plan::centrally_symmetric(set.taps(), chans, nch, b);
-    a.kreal = kreal ? 1 : 0;
-    a.oy = kreal ? a.ay : 0;
-    a.ox = kreal ? a.ax : 0;
-    int cus = 0;
-    if (const int rc = device_cu_count(ctx, &cus)) return rc;
+    a.ny = call.b.ny, a.nx = call.b.nx;
+    a.ay = in.ay, a.ax = in.ax;
+    a.vy = call.b.vy, a.vx = call.b.vx;
+    a.kreal = call.kreal, a.oy = call.oy, a.ox = call.ox;
     a.cols_walk = ctx->opt.fft_cols_walk;
     a.cols_slots = 2 * cus;
-    int rc = ctx->fft.s1.reserve(ctx, img * sizeof(double2), Grow::SyncGeneration);
-    if (rc) return rc;
-    for (int i = 0; i < nch; ++i) {
-        const int c = chans[i];
-        ctx->fft.kf_dims[which][c] = ny * 4096 + nx;
-        ctx->fft.last_real[which][c] = kreal ? 1 : 0;
-        if (ctx->fft.kf_valid[which][c][shape] && ctx->fft.kf_real[which][c][shape] == kreal) continue;
-        // the kernel's spectrum: the same two forward passes on its zero-padded image -- the box in the window's top left corner
-        // (outputs from row / column 0 on), or, for a real spectrum, wrapped around the window with its anchor on the origin
-        const std::vector<float> kimg = plan::fft_kernel_image(set.taps(), c, b, ny, nx, kreal);
-        rc = upload(ctx, ctx->fft.kimg, kimg.data(), img * sizeof(float));
+    return a;
+}
+
+// The spectrum of channel c's tap box for the call's window, from the cache; a missing or stale one (r2f_set_kernel, another
+// stencil_fft_real) is built by the same two forward passes on the zero-padded kernel image -- the box in the window's top left
+// corner (outputs from row / column 0 on), or, for a real spectrum, wrapped around the window with its anchor on the origin.
+// `wa`: fft_window_args of the call; the passes use the start of the scratch (one complex128 image, reserved by the caller).
+static int ensure_spectrum(r2f_ctx* ctx, int which, int c, const int box[4], const FftConvArgs& wa, hipStream_t s, const double2** out) {
+    const size_t img = (size_t)wa.ny * wa.nx;
+    ctx->fft.last[which][c] = {wa.ny * 4096 + wa.nx, wa.kreal};
+    r2f_ctx::Fft::Spectrum& sp = ctx->fft.spectrum[which][c][r2f_ctx::Fft::shape_index(wa.ny, wa.nx)];
+    if (!(sp.valid && sp.real == (wa.kreal != 0))) {
+        const std::vector<float> kimg = plan::fft_kernel_image(ctx->stencil[which].taps(), c, box, wa.ny, wa.nx, wa.kreal != 0);
+        int rc = upload(ctx, ctx->fft.kimg, kimg.data(), img * sizeof(float));
         if (rc) return rc;
-        rc = ctx->fft.kf[which][c][shape].reserve(ctx, img * sizeof(double2), Grow::SyncGeneration);
+        rc = sp.buf.reserve(ctx, img * sizeof(double2), Grow::SyncGeneration);
         if (rc) return rc;
-        ctx->fft.kf_real[which][c][shape] = kreal;
-        FftConvArgs k = a;
+        sp.real = wa.kreal != 0;
+        FftConvArgs k = wa;
         k.src.data = static_cast<float*>(ctx->fft.kimg.p);
         k.raw = 1;
         k.s32 = 0;  // spectra are always built and kept in complex128
         k.nch = 1, k.chan[0] = 0, k.ppc = 1;
         k.ntiles = 1, k.gx = 1, k.npairs = 1, k.pair0 = 0;
         k.s1 = static_cast<double2*>(ctx->fft.s1.p);
-        k.kf_out = static_cast<double2*>(ctx->fft.kf[which][c][shape].p);
+        k.kf_out = static_cast<double2*>(sp.buf.p);
         R2F_HIP(ctx, launch_fft_rows_fwd(k, s));
         R2F_HIP(ctx, launch_fft_cols(k, 1, s));
-        ctx->fft.kf_valid[which][c][shape] = true;
+        sp.valid = true;
     }
-    a.src = to_dev(src);
-    a.dst = to_dev(dst);
-    a.nch = nch;
-    for (int i = 0; i < nch; ++i) {
-        a.chan[i] = chans[i];
-        a.kfs[i] = static_cast<const double2*>(ctx->fft.kf[which][chans[i]][shape].p);
-    }
-    a.y0 = y0, a.y1 = y1, a.W = W, a.H_global = H;
-    a.s32 = ((ctx->opt.fft_s96 >> which) & 1) ? 2 : (s32_eff ? 1 : 0);
-    for (int i = 0; i < nch; ++i)
-        if (set.mixed_sign[chans[i]] && ctx->opt.fft_mixed_sign) a.s32 = 0;  // (the 12-byte element neither)
-    // the halation of a whole-frame render whose front kernel recorded the range of the exposure planes: element chosen on the device.
-    // The guard compares a window's SAMPLES; it speaks for the outputs only under a stencil of unit gain (the reference's halation
-    // kernels are normalised and non-negative, effects.py:200-217): taps that cancel or sum to 0.01 make outputs far below the samples
-    bool unit_gain = true;
-    for (int i = 0; i < nch; ++i) unit_gain = unit_gain && set.unit_gain[chans[i]];
-    if (a.s32 == 0 && which == R2F_KERNEL_HALATION && epilogue == 1 && dyn && ctx->opt.fft_s96_auto && a.kreal && unit_gain &&
-        ny == 256 && ctx->opt.fft_cols_walk && ctx->curve.cells) {
-        a.s32 = 3;  // (the flags are worked out below, once the call's tiling is known)
-        ctx->frame_dyn_armed = true;
-    }
-    const plan::FftBatches fb = plan::fft_batches(fo, ny, nx, bh, bw, W, y0, y1, nch, a.s32 == 1 ? 8 : (a.s32 == 2 ? 12 : 16));  // (3: sized for 16)
-    a.gx = fb.gx;
-    a.ntiles = fb.ntiles;
-    a.ppc = fb.ppc;
-    a.epilogue = epilogue;
-    a.epi_lds = ctx->opt.fft_epi_lds;
-    a.curve = ctx->curve;
-    a.log_eps = log_eps;
-    a.vec4 = planes_vec_ok(dst, W) ? 1 : 0;
-    const size_t img_bytes = fb.img_bytes;
-    const int pairs = fb.pairs, nstreams = fb.nstreams, batch = fb.batch;
-    rc = ctx->fft.s1.reserve(ctx, fb.scratch_bytes, Grow::SyncGeneration);
-    if (rc) return rc;
-    if (a.s32 == 3) {
-        // the element of every window pair of this call, from the exposure-range tiles its caller vouches for: one small launch on the
-        // caller's stream ahead of the passes (they fan out to the internal streams behind it)
-        rc = ensure_range_tiles(ctx, H, W);
-        if (rc) return rc;
-        rc = ctx->dyn_flags.reserve(ctx, (size_t)std::max(fb.ppc, 1) * sizeof(int), Grow::SyncGeneration);
-        if (rc) return rc;
-        float bound, floor_;
-        dyn_rule(ctx, &bound, &floor_);
-        a.dyn_flags = static_cast<const int*>(ctx->dyn_flags.p);
-        ctx->dyn_flags_ppc = fb.ppc;
-        R2F_HIP(ctx, launch_fft_decide(a, record_of(ctx), bound, floor_, static_cast<int*>(ctx->dyn_flags.p), s));
-    }
-    hipStream_t lanes[4] = {s, s, s, s};
-    if (nstreams > 1) {
-        for (int i = 0; i < nstreams; ++i) {
-            if (!ctx->fft.stream[i]) R2F_HIP(ctx, hipStreamCreateWithFlags(&ctx->fft.stream[i], hipStreamNonBlocking));
-            if (!ctx->fft.ev_out[i]) R2F_HIP(ctx, hipEventCreateWithFlags(&ctx->fft.ev_out[i], hipEventDisableTiming));
-            lanes[i] = ctx->fft.stream[i];
-        }
-        if (!ctx->fft.ev_in) R2F_HIP(ctx, hipEventCreateWithFlags(&ctx->fft.ev_in, hipEventDisableTiming));
-        R2F_HIP(ctx, hipEventRecord(ctx->fft.ev_in, s));  // everything queued on the caller's stream so far (src, spectra)
-        for (int i = 0; i < nstreams; ++i) R2F_HIP(ctx, hipStreamWaitEvent(lanes[i], ctx->fft.ev_in, 0));
-    }
-    auto timed = [&](int cls, double bytes, hipStream_t st, auto&& launch) -> int {
-        if (!(ctx->opt.timing & (1 << cls))) {
-            R2F_HIP(ctx, launch());
-            return R2F_OK;
-        }
-        hipEvent_t e0, e1;
-        R2F_HIP(ctx, hipEventCreate(&e0));
-        R2F_HIP(ctx, hipEventCreate(&e1));
-        R2F_HIP(ctx, hipEventRecord(e0, st));
-        R2F_HIP(ctx, launch());
-        R2F_HIP(ctx, hipEventRecord(e1, st));
-        ctx->timing_ev[cls + 3 * (a.s32 == 1)].push_back({e0, e1});
-        ctx->timing_bytes[cls + 3 * (a.s32 == 1)] += bytes;
-        return R2F_OK;
-    };
-    int turn = 0;
-    for (int p0 = 0; p0 < pairs; p0 += batch, turn = (turn + 1) % nstreams) {
-        const int li = turn;
-        hipStream_t st = lanes[li];
-        a.pair0 = p0;
-        a.npairs = std::min(batch, pairs - p0);
-        a.s1 = reinterpret_cast<double2*>(static_cast<char*>(ctx->fft.s1.p) + (size_t)li * batch * img_bytes);
-        // algorithmic bytes of the passes: window floats in (2 per pair) + scratch image out; scratch in + valid rows out;
-        // valid rows in + valid outputs out.  The kernel spectrum (1 MB) stays in L2.
-        const double np = a.npairs, full = (double)img_bytes, part = full * a.vy / ny;
-        rc = timed(0, np * (2.0 * img * sizeof(float) + full), st, [&] { return launch_fft_rows_fwd(a, st); });
-        if (rc) return rc;
-        rc = timed(1, np * (full + part), st, [&] { return launch_fft_cols(a, 0, st); });
-        if (rc) return rc;
-        rc = timed(2, np * (part + 2.0 * a.vy * a.vx * sizeof(float)), st, [&] { return launch_fft_rows_inv(a, st); });
-        if (rc) return rc;
-    }
-    if (nstreams > 1)
-        for (int i = 0; i < nstreams; ++i) {
-            R2F_HIP(ctx, hipEventRecord(ctx->fft.ev_out[i], lanes[i]));
-            R2F_HIP(ctx, hipStreamWaitEvent(s, ctx->fft.ev_out[i], 0));
-        }
+    *out = static_cast<const double2*>(sp.buf.p);
     return R2F_OK;
+}
+
+// The per-pair element of a call whose passes choose it on the device (element 3), from the exposure-range tiles its caller vouches
+// for: one small launch on the caller's stream ahead of the passes (they fan out to the internal streams behind it).
+static int queue_pair_flags(r2f_ctx* ctx, FftConvArgs* a, int W, hipStream_t s) {
+    int rc = ensure_range_tiles(ctx, a->H_global, W);
+    if (rc) return rc;
+    rc = ctx->dyn_flags.reserve(ctx, (size_t)std::max(a->ppc, 1) * sizeof(int), Grow::SyncGeneration);
+    if (rc) return rc;
+    float bound, floor_;
+    dyn_rule(ctx, &bound, &floor_);
+    a->dyn_flags = static_cast<const int*>(ctx->dyn_flags.p);
+    ctx->dyn_flags_ppc = a->ppc;
+    R2F_HIP(ctx, launch_fft_decide(*a, record_of(ctx), bound, floor_, static_cast<int*>(ctx->dyn_flags.p), s));
+    return R2F_OK;
+}
+
+// The lanes of a call: the caller's stream alone, or n internal streams (created on first use) that start behind everything queued
+// on the caller's stream so far (src, spectra, flags) ...
+static int fork_lanes(r2f_ctx* ctx, hipStream_t s, int n, hipStream_t lane[4]) {
+    r2f_ctx::Fft& f = ctx->fft;
+    for (int i = 0; i < 4; ++i) lane[i] = s;
+    if (n <= 1) return R2F_OK;
+    for (int i = 0; i < n; ++i) {
+        if (!f.stream[i]) R2F_HIP(ctx, hipStreamCreateWithFlags(&f.stream[i], hipStreamNonBlocking));
+        if (!f.ev_out[i]) R2F_HIP(ctx, hipEventCreateWithFlags(&f.ev_out[i], hipEventDisableTiming));
+        lane[i] = f.stream[i];
+    }
+    if (!f.ev_in) R2F_HIP(ctx, hipEventCreateWithFlags(&f.ev_in, hipEventDisableTiming));
+    R2F_HIP(ctx, hipEventRecord(f.ev_in, s));
+    for (int i = 0; i < n; ++i) R2F_HIP(ctx, hipStreamWaitEvent(lane[i], f.ev_in, 0));
+    return R2F_OK;
+}
+// ... and that the caller's stream waits for at the end.
+static int join_lanes(r2f_ctx* ctx, hipStream_t s, int n, const hipStream_t lane[4]) {
+    for (int i = 0; i < n && n > 1; ++i) {
+        R2F_HIP(ctx, hipEventRecord(ctx->fft.ev_out[i], lane[i]));
+        R2F_HIP(ctx, hipStreamWaitEvent(s, ctx->fft.ev_out[i], 0));
+    }
+    return R2F_OK;
+}
+
+// One launch, bracketed by timing events on its stream when kernel_timing asks for its class (r2f_kernel_timing reads them).
+template <typename Launch>
+static int timed_launch(r2f_ctx* ctx, int pass, int cls, double bytes, hipStream_t st, Launch&& launch) {
+    if (!(ctx->opt.timing & (1 << pass))) {
+        R2F_HIP(ctx, launch());
+        return R2F_OK;
+    }
+    hipEvent_t e0, e1;
+    R2F_HIP(ctx, hipEventCreate(&e0));
+    R2F_HIP(ctx, hipEventCreate(&e1));
+    R2F_HIP(ctx, hipEventRecord(e0, st));
+    R2F_HIP(ctx, launch());
+    R2F_HIP(ctx, hipEventRecord(e1, st));
+    ctx->timing_ev[cls].push_back({e0, e1});
+    ctx->timing_bytes[cls] += bytes;
+    return R2F_OK;
+}
+
+// The launch arguments of the call, from its plan: fft_window_args `wa` plus what the call reads and writes.  (Per channel the
+// spectrum, per batch pair0 / npairs / s1 and, when the element is chosen per pair, the flags are filled in where they are made.)
+static FftConvArgs fft_call_args(const r2f_ctx* ctx, const FftConvArgs& wa, const plan::FftCall& call, const int* chans, int nch,
+                                 const r2f_planes* src, const r2f_planes* dst, int y0, int y1, int W, int H, int epilogue, float log_eps) {
+    FftConvArgs a = wa;
+    a.src = to_dev(src), a.dst = to_dev(dst);
+    a.nch = nch;
+    for (int i = 0; i < nch; ++i) a.chan[i] = chans[i];
+    a.y0 = y0, a.y1 = y1, a.W = W, a.H_global = H;
+    a.s32 = call.element;
+    a.gx = call.b.gx, a.ntiles = call.b.ntiles, a.ppc = call.b.ppc;
+    a.epilogue = epilogue, a.epi_lds = ctx->opt.fft_epi_lds, a.curve = ctx->curve, a.log_eps = log_eps;
+    a.vec4 = planes_vec_ok(dst, W) ? 1 : 0;
+    return a;
+}
+
+// dyn: the caller vouches that the context's exposure-range record (its tiles) was kept for the samples `src` holds this frame: the
+// passes may then choose their scratch element on the device, per window pair (FftConvArgs::dyn_flags, fft_decide_kernel).
+static int run_stencil_fft(r2f_ctx* ctx, int which, const int* chans, int nch, const r2f_planes* src, const r2f_planes* dst, int y0,
+                           int y1, int W, int H, int epilogue, float log_eps, hipStream_t s, bool dyn) {
+    int box[4];
+    plan::tap_box(ctx->stencil[which].taps(), chans[0], box);
+    const plan::FftCallIn in = fft_call_facts(ctx, which, chans, nch, box, y0, y1, W, epilogue, dyn);
+    const plan::FftCall call = plan::fft_call(in);
+    if (!call.ok)
+        return fail(ctx, R2F_EINVAL, "stencil %d: no FFT window shape fits a %d x %d tap box under the current stencil_fft_window* options",
+                    which, in.bh, in.bw);
+    const plan::FftBatches& fb = call.b;
+    int rc = ensure_twiddles(ctx), cus = 0;
+    if (rc || (rc = device_cu_count(ctx, &cus))) return rc;
+    const FftConvArgs wa = fft_window_args(ctx, in, call, cus);
+    FftConvArgs a = fft_call_args(ctx, wa, call, chans, nch, src, dst, y0, y1, W, H, epilogue, log_eps);
+    rc = ctx->fft.s1.reserve(ctx, (size_t)fb.ny * fb.nx * sizeof(double2), Grow::SyncGeneration);  // (a spectrum build's image)
+    for (int i = 0; i < nch && !rc; ++i) rc = ensure_spectrum(ctx, which, chans[i], box, wa, s, &a.kfs[i]);
+    if (rc) return rc;
+    if (call.element == 3) ctx->frame_dyn_armed = true;
+    rc = ctx->fft.s1.reserve(ctx, fb.scratch_bytes, Grow::SyncGeneration);
+    if (!rc && call.element == 3) rc = queue_pair_flags(ctx, &a, W, s);
+    if (rc) return rc;
+    hipStream_t lane[4];
+    if ((rc = fork_lanes(ctx, s, fb.nstreams, lane))) return rc;
+    for (int i = 0; i < fb.launches; ++i) {
+        const plan::FftBatch bt = call.batch(i);
+        hipStream_t st = lane[bt.lane];
+        a.pair0 = bt.pair0, a.npairs = bt.npairs;
+        a.s1 = reinterpret_cast<double2*>(static_cast<char*>(ctx->fft.s1.p) + bt.scratch_offset);
+        const int cls = call.timing_offset;
+        if ((rc = timed_launch(ctx, 0, cls + 0, bt.npairs * call.pass_bytes[0], st, [&] { return launch_fft_rows_fwd(a, st); }))) return rc;
+        if ((rc = timed_launch(ctx, 1, cls + 1, bt.npairs * call.pass_bytes[1], st, [&] { return launch_fft_cols(a, 0, st); }))) return rc;
+        if ((rc = timed_launch(ctx, 2, cls + 2, bt.npairs * call.pass_bytes[2], st, [&] { return launch_fft_rows_inv(a, st); }))) return rc;
+    }
+    return join_lanes(ctx, s, fb.nstreams, lane);
 }
 
 int run_stencil(r2f_ctx* ctx, int which, const r2f_planes* src, const r2f_planes* dst, int y0, int y1, int W, int H, int epilogue,
@@ -448,7 +455,7 @@ int run_stencil(r2f_ctx* ctx, int which, const r2f_planes* src, const r2f_planes
 
 }  // namespace r2f
 
-// The internal streams and their fences (created by run_stencil_fft on first use); the buffers free themselves.
+// The internal streams and their fences (created by fork_lanes on first use); the buffers free themselves.
 r2f_ctx::Fft::~Fft() {
     for (int i = 0; i < 4; ++i) {
         if (stream[i]) (void)hipStreamDestroy(stream[i]);

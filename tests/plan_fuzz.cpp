@@ -92,6 +92,36 @@ static void fuzz_fft() {
     if (window && bw <= 200) CHECK(p.nx == window, "columns forced %d got %d", window, p.nx);
     if (bh > 200) CHECK(p.ny == 512, "tall box in %d rows", p.ny);
     if (bw > 200) CHECK(p.nx >= 512, "wide box in %d columns", p.nx);
+    // The batch walk of the device call (plan::fft_call, the rows [y0, y1) this time): the batches cover the pairs once and in order,
+    // on lanes that exist, inside the scratch; only the batches of one lane share scratch.  (A wrong offset stops here, not on a GPU.)
+    FftCallIn in;
+    in.bh = bh, in.bw = bw, in.nch = nch, in.W = W, in.y0 = y0, in.y1 = y1;
+    in.fo.window = window, in.fo.window_rows = window_rows, in.fo.window_max = window_max, in.fo.batch_mib = batch, in.fo.streams = streams;
+    in.fo.even = (int)(rnd() % 2);
+    in.which = rint_in(0, 1);
+    in.fft_s32 = (elem == 8 ? 1 : 0) << in.which, in.fft_s96 = (elem == 12 ? 1 : 0) << in.which;
+    const FftCall c = fft_call(in);
+    CHECK(c.ok && c.elem_bytes == elem, "element %d sized by %d, wanted %d", c.element, c.elem_bytes, elem);
+    const FftBatches& b = c.b;
+    CHECK(b.ny == p.ny && b.nx == p.nx && b.vy == p.vy && b.vx == p.vx && b.img_bytes == (size_t)p.ny * p.nx * elem, "call window %d x %d", b.ny, b.nx);
+    CHECK(b.pairs == p.pairs && b.nstreams >= 1 && b.nstreams <= streams && b.launches >= 1, "call pairs %d streams %d", b.pairs, b.nstreams);
+    if (in.fo.even) CHECK(b.batch == p.batch && b.launches == p.launches && b.scratch_bytes == p.scratch_bytes, "call batch %d", b.batch);
+    int next = 0;
+    size_t lane_lo[4] = {0, 0, 0, 0}, lane_hi[4] = {0, 0, 0, 0};
+    for (int i = 0; i < b.launches; ++i) {
+        const FftBatch t = c.batch(i);
+        CHECK(t.pair0 == next && t.npairs >= 1, "batch %d starts at pair %d, not %d", i, t.pair0, next);
+        next += t.npairs;
+        CHECK(t.lane >= 0 && t.lane < b.nstreams, "batch %d on lane %d of %d", i, t.lane, b.nstreams);
+        const size_t lo = t.scratch_offset, hi = lo + (size_t)t.npairs * b.img_bytes;
+        CHECK(hi <= b.scratch_bytes, "batch %d: scratch [%zu, %zu) of %zu", i, lo, hi, b.scratch_bytes);
+        if (lane_hi[t.lane]) CHECK(lo == lane_lo[t.lane], "batch %d: lane %d moved its scratch", i, t.lane);
+        lane_lo[t.lane] = lo, lane_hi[t.lane] = std::max(lane_hi[t.lane], hi);
+    }
+    CHECK(next == b.pairs, "batches cover %d of %d pairs", next, b.pairs);
+    for (int l = 0; l < b.nstreams; ++l)
+        for (int m = l + 1; m < b.nstreams; ++m)
+            if (lane_hi[l] && lane_hi[m]) CHECK(lane_hi[l] <= lane_lo[m] || lane_hi[m] <= lane_lo[l], "lanes %d and %d share scratch", l, m);
 }
 
 // stencil_source_rows against brute force.  `above` / `below` as run_stencil derives them from a tap box and the anchor: they sum

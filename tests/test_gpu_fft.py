@@ -911,3 +911,49 @@ def test_pass2_walk_over_the_pairs_is_bit_identical_to_one_workgroup_per_pair(ct
             assert_close(walk, ref, 1e-6, 1e-3, f"walk, scratch32={s32}, batch={batch}")
     ctx.set_option("stencil_fft_batch", 192)
     ctx.set_option("stencil_fft_scratch32", 2)
+
+
+@pytest.mark.parametrize("case", ["halation_six_batches_two_lanes", "halation_rows_40_200", "mtf_complex64", "halation_twelve_byte"])
+def test_the_device_call_runs_the_plan_the_cpu_tests_pin(ctx, case):
+    """plan::fft_call is held to its rules without a GPU (tests/test_fft_call_host.py, the fuzz of tests/test_plan_sanitizers.py);
+    this ties that plan to what the device ran: per timing class as many timed launches as r2f_plan_fft's `launches` for the same
+    inputs (complex64 scratch: classes 3-5, otherwise 0-2), the planned window in stencil_stats, and -- the batches of one pair on
+    two lanes against one launch of all pairs -- the same output bit for bit.  31 x 31 = 961 taps: above stencil_fft_min_taps and
+    above the unrolled form's 23 x 23; 300 x 520 in 256 x 256 windows is 2 x 3 windows, three pairs per channel."""
+    import ctypes
+
+    from raw2film_amd import _lib
+
+    which, rows, elem, extra = {"halation_six_batches_two_lanes": (0, None, 16, {}), "halation_rows_40_200": (0, (40, 200), 16, {}),
+                                "mtf_complex64": (1, None, 8, {}), "halation_twelve_byte": (0, None, 12, {"stencil_fft_scratch96": 1})}[case]
+    H, W = 300, 520
+    rng = np.random.default_rng(26)
+    img = rng.uniform(0.05, 2.0, (H, W, 3)).astype(np.float32)
+    y, x = np.mgrid[-15:16, -15:16]
+    disc = np.exp(-(y * y + x * x) / 60.0)
+    k = np.zeros((31, 31, 3), dtype=np.float32)  # like a halation kernel: two channels share the launches, blue is the identity
+    k[..., 0] = k[..., 1] = (disc / disc.sum()).astype(np.float32)
+    k[15, 15, 2] = 1.0
+    assert np.array_equal(k, k[::-1, ::-1])
+    y0, y1 = rows or (0, H)
+    p = _lib.FftPlan()
+    assert _lib.load().r2f_plan_fft(31, 31, W, y1 - y0, 2, elem, 0, 0, 512, 1, 2, ctypes.byref(p)) == 0
+    if case == "halation_six_batches_two_lanes":
+        assert (p.ny, p.nx, p.pairs, p.batch, p.launches, p.streams) == (256, 256, 6, 1, 6, 2)
+    assert p.launches > 1 and p.streams == 2
+    try:
+        for cls in range(6):
+            ctx.kernel_timing(cls)
+        got = run(ctx, which, img, k, 1, rows=rows, stencil_fft_batch=1, kernel_timing=7, **extra)
+        counts = [ctx.kernel_timing(cls)[1] for cls in range(6)]
+        stats = ctx.stencil_stats(which)
+        ctx.set_option("kernel_timing", 0)
+        one_launch = run(ctx, which, img, k, 1, rows=rows, stencil_fft_batch=192, **extra)
+    finally:
+        ctx.set_option("kernel_timing", 0)
+        ctx.set_option("stencil_fft_batch", 192)
+        ctx.set_option("stencil_fft_scratch96", 0)
+    print(case, "plan", (p.ny, p.nx), p.launches, "timed launches per class", counts)
+    assert counts == ([0, 0, 0] + [p.launches] * 3 if elem == 8 else [p.launches] * 3 + [0, 0, 0])
+    assert [c["fft"] for c in stats] == [1, 1, 0] and [c["window"] for c in stats] == [(p.ny, p.nx)] * 2 + [None]
+    np.testing.assert_array_equal(got, one_launch)
