@@ -432,6 +432,80 @@ R2F_API int r2f_lens_correct_tca(r2f_ctx* ctx, const void* in, int in_layout, in
                          const r2f_lens_tca_params* tca_params, const r2f_planes* dst, int out_h, int out_w, int oy, int ox,
                          void* stream);
 
+/* The lens correction of a lens whose own projection is not rectilinear: a fisheye frame is straightened.  This is lensfun's
+ * geometry conversion from the target projection (rectilinear, the only target here) to the lens's, the step
+ * Modifier.apply_geometry_distortion runs between the scale and the distortion polynomial.
+ *
+ * The definition.  Everything of r2f_lens_correct's up to r2 = u*u + v*v is unchanged.  Then:
+ *   - r = sqrt(r2), t = r*inv_focal.  inv_focal is the float rounded from 1/focal; focal is the lens's focal length in units of
+ *     the normalisation radius (of r = 1).  t is the tangent of the angle theta between the ray and the axis.
+ *   - The projection factor P(t): the lens's image radius over the rectilinear radius tan(theta).  With tt = t*t, s1 = 1 + tt,
+ *     s = sqrt(s1):
+ *       orthographic:  P = 1/s                                      (sin(theta)/t)
+ *       stereographic: d = 1 + s, P = 2/d                           (2 tan(theta/2)/t)
+ *       equisolid:     n = s + 1, m = 2*s, h = n/m, e = sqrt(h), b = s*e, P = 1/b     (2 sin(theta/2)/t)
+ *       fisheye (equidistant): P = atan(t)/t, evaluated without a library call from the odd polynomial atan(x) ~ x*p(x*x):
+ *         t <= 1:  P = p(tt)
+ *         t >  1:  w = 1/t, ww = w*w, a = w*p(ww), b = pi_2 - a, P = b*w     (atan(t) = pi/2 - atan(1/t))
+ *         pi_2 = 0x1.921fb6p+0f.  p(x) = c0 + x*(c1 + x*(c2 + ... + x*c9)) by Horner from c9 down -- acc = c9; then for k = 8 .. 0:
+ *         acc = acc*x, acc = c_k + acc -- with
+ *           c0 = 0x1p+0f          c1 = -0x1.55554p-2f   c2 = 0x1.999278p-3f   c3 = -0x1.242702p-3f  c4 = 0x1.c0d2e2p-4f
+ *           c5 = -0x1.58dd68p-4f  c6 = 0x1.dd11b4p-5f   c7 = -0x1.01b21p-5f   c8 = 0x1.6a946ap-7f   c9 = -0x1.df068p-10f
+ *         Measured against atan in double over every float32 t (tests/lens_projection_check.cpp, mode `atan`), in units of the
+ *         last place of the exact atan(t)/t:
+ *           largest error of P for t in [2^-13, 1]: 1.16 ulp
+ *           largest error of P for t in (1, 64]: 2.65 ulp
+ *         (below 2^-13 p(tt) is exactly 1, within half a unit of atan(t)/t.)
+ *   - u' = u*P, v' = v*P, r2' = u'*u' + v'*v'.  The model factor f comes from r2' exactly as r2f_lens_correct's does from r2
+ *     (ptlens takes sqrt(r2')).
+ *   - g0 = f*P, g = g0*inv_scale, ox = dx*g, oy = dy*g.
+ *   - From there on nothing changes: sx = cx + ox, sy = cy + oy -- or, with a TCA record, r2f_lens_correct_tca's step on
+ *     (ox, oy) -- the phase split, the 64-tap sums, the clamp, and the vignetting gain of the output pixel's (dx, dy).
+ * Every operation is one correctly rounded fp32 operation (the divisions and square roots included), with no contraction.
+ * One consequence holds bit for bit: when focal is so large that 1 + tt rounds to 1 everywhere in the window (and, for fisheye,
+ * p(tt) to 1: tt below 2^-25 does both), P is exactly 1, and the result equals r2f_lens_correct's on all three planes -- with a
+ * TCA record r2f_lens_correct_tca's.
+ * Not here: lensfun's thoby, panoramic and equirectangular lens types, and any target projection other than rectilinear.
+ * Parity with lensfun is UNPINNED, like the rest of this section (tests/lens_projection_model.py restates the definition). */
+enum {
+    R2F_PROJ_NONE = 0,
+    R2F_PROJ_FISHEYE = 1,
+    R2F_PROJ_STEREOGRAPHIC = 2,
+    R2F_PROJ_EQUISOLID = 3,
+    R2F_PROJ_ORTHOGRAPHIC = 4
+};
+/* What the caller knows of the lens's projection: its type and its focal length in units of the normalisation radius. */
+typedef struct r2f_lens_projection {
+    int32_t type;
+    double focal;
+} r2f_lens_projection;
+/* The fp32 constant of the projection step. */
+typedef struct r2f_lens_projection_params {
+    int32_t type;
+    float inv_focal;
+} r2f_lens_projection_params;
+/* r2f_lens_plan (with tca == NULL and out_tca == NULL) or r2f_lens_plan_tca (with both) for a profile with a projection: their
+ * checks, and R2F_EINVAL for an unknown type, R2F_PROJ_NONE (that case is the other planners'), a focal that is not finite and
+ * positive, or one whose reciprocal does not fit a finite float.  Without auto_scale *out is r2f_lens_plan's, byte for byte.
+ * auto_scale: the same eight probes and the same bisection over [1/16, 16]; each probe goes through the projected map in double
+ * (P from std::sqrt / std::atan, then rounded to float: the precision at which the kernel applies it, so that a projection the
+ * kernel cannot resolve leaves the scale r2f_lens_plan's to the last bit), with the TCA factor on top when there is a record.
+ * R2F_EINVAL when the range holds no fitting scale -- a circular fisheye whose whole image circle lies inside the frame never
+ * puts a probe on the boundary. */
+R2F_API int r2f_lens_plan_projected(const r2f_lens_profile* profile, const r2f_lens_projection* projection, const r2f_lens_tca* tca,
+                                    int H, int W, r2f_lens_params* out, r2f_lens_projection_params* out_projection,
+                                    r2f_lens_tca_params* out_tca);
+/* The projected correction: r2f_lens_correct's contract for the window, the layouts and the rows of `dst`.  tca_params may be
+ * NULL; a record whose model is R2F_TCA_NONE or unknown is refused with R2F_EINVAL, and so is a projection of type
+ * R2F_PROJ_NONE (that case is r2f_lens_correct's or r2f_lens_correct_tca's) or of an unknown type.  A block makes a 64 x 16 tile
+ * and stages the box of source texels its taps touch in LDS; where a magnifying scale makes that box too large it works in two
+ * halves of 64 x 8 with a box each, and only a half whose box does not fit either gathers from global memory.  The sums are the
+ * same over either source in the same order: results do not depend on the route a block took. */
+R2F_API int r2f_lens_correct_projected(r2f_ctx* ctx, const void* in, int in_layout, int H, int W, const r2f_lens_params* params,
+                                       const r2f_lens_projection_params* projection_params,
+                                       const r2f_lens_tca_params* tca_params, const r2f_planes* dst, int out_h, int out_w, int oy,
+                                       int ox, void* stream);
+
 /* Post-path up-scale of the rendered uint8 frame: utils.resolution_scaling's cv.resize(image, dsize,
  * interpolation=cv.INTER_LANCZOS4) branch (utils.py:237-242), the way back from the `max_scale` pipeline resolution to the
  * requested one (cpu_processor.py:128-134, 411-412).  src/dst: uint8 (H, W, 3) / (out_h, out_w, 3) on the device.

@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libr2f_hip.so")
 LAYOUT_HWC3, LAYOUT_HWC4, LAYOUT_CHW = 0, 1, 2
 LENS_NONE, LENS_POLY3, LENS_POLY5, LENS_PTLENS = 0, 1, 2, 3
 TCA_NONE, TCA_LINEAR, TCA_POLY3 = 0, 1, 2
+PROJ_NONE, PROJ_FISHEYE, PROJ_STEREOGRAPHIC, PROJ_EQUISOLID, PROJ_ORTHOGRAPHIC = 0, 1, 2, 3, 4
 CFA_RGGB, CFA_BGGR, CFA_GRBG, CFA_GBRG = 0, 1, 2, 3
 DEMOSAIC_TILE_W, DEMOSAIC_TILE_H = 64, 32  # R2F_DEMOSAIC_TILE_*
 XTRANS_TILE_W, XTRANS_TILE_H = 64, 32  # R2F_XTRANS_TILE_*
@@ -91,6 +92,14 @@ class LensTca(C.Structure):  # r2f_lens_tca: (v, c, b) of red and of blue (raw2f
 
 class LensTcaParams(C.Structure):  # r2f_lens_tca_params: the same constants in fp32
     _fields_ = [("model", C.c_int32), ("red", C.c_float * 3), ("blue", C.c_float * 3)]
+
+
+class LensProjection(C.Structure):  # r2f_lens_projection (raw2film_amd.lens.LensProfile.to_c_projection fills it)
+    _fields_ = [("type", C.c_int32), ("focal", C.c_double)]
+
+
+class LensProjectionParams(C.Structure):  # r2f_lens_projection_params: the projection step's constant in fp32
+    _fields_ = [("type", C.c_int32), ("inv_focal", C.c_float)]
 
 
 class RawProfile(C.Structure):  # r2f_raw_profile (raw2film_amd.raw.RawProfile fills it)
@@ -207,6 +216,15 @@ _SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(LensParams), _P(LensTcaParams), _P(Planes), C.c_int, C.c_int, C.c_int,
          C.c_int, C.c_void_p],
+    ),
+    "r2f_lens_plan_projected": (
+        C.c_int,
+        [_P(LensProfile), _P(LensProjection), _P(LensTca), C.c_int, C.c_int, _P(LensParams), _P(LensProjectionParams), _P(LensTcaParams)],
+    ),
+    "r2f_lens_correct_projected": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _P(LensParams), _P(LensProjectionParams), _P(LensTcaParams), _P(Planes),
+         C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
     ),
     "r2f_demosaic_plan": (C.c_int, [_P(RawProfile), C.c_int, C.c_int, _P(DemosaicParams)]),
     "r2f_demosaic_u16": (

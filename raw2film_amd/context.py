@@ -545,27 +545,34 @@ class HipContext:
                                               self._stream()))
         return out
 
-    def lens_correct(self, image, profile_or_params, window=None, layout=None, tca=None):
+    def lens_correct(self, image, profile_or_params, window=None, layout=None, tca=None, projection=None):
         """The lens correction of include/r2f.h (r2f_lens_correct: radial map, 8 x 8 LANCZOS4 gather, clamp at 0, vignetting gain)
         of a whole frame, restricted to `window` = (row0, col0, rows, cols) of the corrected frame -> (3, rows, cols) planes.
-        profile_or_params: a raw2film_amd.lens.LensProfile (planned for this frame's size, its `tca` included) or the
-        r2f_lens_params of that size.  tca: the r2f_lens_tca_params that go with such params; with them the call is
-        r2f_lens_correct_tca (red and blue sample at coordinates of their own)."""
+        profile_or_params: a raw2film_amd.lens.LensProfile (planned for this frame's size, its `tca` and `projection` included) or
+        the r2f_lens_params of that size.  tca: the r2f_lens_tca_params that go with such params; with them the call is
+        r2f_lens_correct_tca (red and blue sample at coordinates of their own).  projection: the r2f_lens_projection_params that go
+        with such params; with them the call is r2f_lens_correct_projected (a fisheye frame is straightened), with or without `tca`."""
         torch = self._torch
         self._check_image(image)
         layout, H, W = self.layout_of(image, layout)
         if isinstance(profile_or_params, _lib.LensParams):
             params = profile_or_params
-        elif tca is None:
-            params, tca = profile_or_params.plan_tca(H, W)
-        else:
+        elif tca is not None:
             raise ValueError("lens_correct: `tca` goes with r2f_lens_params; a LensProfile carries its own")
+        elif projection is not None:
+            raise ValueError("lens_correct: `projection` goes with r2f_lens_params; a LensProfile carries its own")
+        else:
+            params, projection, tca = profile_or_params.plan_projected(H, W)
         r0, c0, nr, nc = (0, 0, H, W) if window is None else [int(v) for v in window]
         out = torch.empty((3, nr, nc), dtype=torch.float32, device=self.device)
         if nr == 0 or nc == 0:
             return out
         pd = self.planes(out, 0)
-        if tca is None:
+        if projection is not None:
+            self._check(self._lib.r2f_lens_correct_projected(self._h, image.data_ptr(), layout, H, W, C.byref(params), C.byref(projection),
+                                                             None if tca is None else C.byref(tca), C.byref(pd), nr, nc, r0, c0,
+                                                             self._stream()))
+        elif tca is None:
             self._check(self._lib.r2f_lens_correct(self._h, image.data_ptr(), layout, H, W, C.byref(params), C.byref(pd), nr, nc, r0, c0,
                                                    self._stream()))
         else:

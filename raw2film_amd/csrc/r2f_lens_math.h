@@ -1,6 +1,7 @@
-// r2f_lens_math.h -- the arithmetic of the lens correction (include/r2f.h, r2f_lens_correct and r2f_lens_correct_tca), as text the
-// device kernels (r2f_resample.hip) and CPU programs (tests/lens_check.cpp, tests/lens_tca_check.cpp, g++ -ffp-contract=off) both
-// compile: the coordinate map, red's and blue's TCA step on it, the 1/32 phase split with its inside / outside decision, the 64-tap
+// r2f_lens_math.h -- the arithmetic of the lens correction (include/r2f.h, r2f_lens_correct, r2f_lens_correct_tca and
+// r2f_lens_correct_projected), as text the device kernels (r2f_resample.hip) and CPU programs (tests/lens_check.cpp,
+// tests/lens_tca_check.cpp, tests/lens_projection_check.cpp, g++ -ffp-contract=off) both compile: the coordinate map, the projection
+// factor in front of its distortion model, red's and blue's TCA step on it, the 1/32 phase split with its inside / outside decision, the 64-tap
 // sample over a pixel-fetch functor (three channels at one coordinate, or one channel at its own) and the vignetting gain.  Every
 // operation is one correctly rounded fp32 operation; contraction is off for each function (a fused multiply-add would round once
 // where the definition rounds twice).  No HIP types, no includes beyond <math.h>.
@@ -27,15 +28,9 @@ namespace lens {
 constexpr int kPhases = 32;  // INTER_TAB_SIZE = 1 << INTER_BITS
 constexpr int kTaps = 8;
 
-// The offset (ox, oy) = (dx*g, dy*g) of output pixel (X, Y)'s source coordinate from the optical centre: the map up to the point at
-// which the channels part (r2f_lens_correct_tca).  dx, dy are handed on to the vignetting gain.
-R2F_HD void source_offset(const r2f_lens_params& p, int X, int Y, float& ox, float& oy, float& dx, float& dy) {
+// The model factor f of r2 (ptlens: of r = sqrt(r2)).
+R2F_HD float model_factor(const r2f_lens_params& p, float r2) {
     R2F_NO_CONTRACT
-    dx = (float)X - p.cx;
-    dy = (float)Y - p.cy;
-    const float u = dx * p.q, v = dy * p.q;
-    const float uu = u * u, vv = v * v;
-    const float r2 = uu + vv;
     float f = 1.f;
     if (p.model == R2F_LENS_POLY3) {
         const float t = p.k[0] * r2;
@@ -54,7 +49,88 @@ R2F_HD void source_offset(const r2f_lens_params& p, int X, int Y, float& ox, flo
         const float t4 = r * t3;
         f = p.c0 + t4;
     }
+    return f;
+}
+
+// The offset (ox, oy) = (dx*g, dy*g) of output pixel (X, Y)'s source coordinate from the optical centre: the map up to the point at
+// which the channels part (r2f_lens_correct_tca).  dx, dy are handed on to the vignetting gain.
+R2F_HD void source_offset(const r2f_lens_params& p, int X, int Y, float& ox, float& oy, float& dx, float& dy) {
+    R2F_NO_CONTRACT
+    dx = (float)X - p.cx;
+    dy = (float)Y - p.cy;
+    const float u = dx * p.q, v = dy * p.q;
+    const float uu = u * u, vv = v * v;
+    const float r2 = uu + vv;
+    const float f = model_factor(p, r2);
     const float g = f * p.inv_scale;
+    ox = dx * g, oy = dy * g;
+}
+
+// p(x) of include/r2f.h's fisheye factor: atan(t) ~ t*p(t*t) on [0, 1], Horner from c9 down, each product and sum rounded on its own.
+R2F_HD float atan_poly(float x) {
+    R2F_NO_CONTRACT
+    const float c[10] = {0x1p+0f,         -0x1.55554p-2f, 0x1.999278p-3f, -0x1.242702p-3f, 0x1.c0d2e2p-4f,
+                         -0x1.58dd68p-4f, 0x1.dd11b4p-5f, -0x1.01b21p-5f, 0x1.6a946ap-7f,  -0x1.df068p-10f};
+    float acc = c[9];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int k = 8; k >= 0; --k) {
+        acc = acc * x;
+        acc = c[k] + acc;
+    }
+    return acc;
+}
+
+// The projection factor P(t) of r2f_lens_correct_projected: the lens's image radius over the rectilinear one, t = tan(theta).
+// An unknown type (the entry point refuses it) gives 1.
+R2F_HD float projection_factor(int type, float t) {
+    R2F_NO_CONTRACT
+    const float tt = t * t;
+    if (type == R2F_PROJ_FISHEYE) {
+        if (t <= 1.f) return atan_poly(tt);
+        const float w = 1.f / t;
+        const float ww = w * w;
+        const float a = w * atan_poly(ww);
+        const float b = 0x1.921fb6p+0f - a;
+        return b * w;
+    }
+    const float s1 = 1.f + tt;
+    const float s = sqrtf(s1);
+    if (type == R2F_PROJ_ORTHOGRAPHIC) return 1.f / s;
+    if (type == R2F_PROJ_STEREOGRAPHIC) {
+        const float d = 1.f + s;
+        return 2.f / d;
+    }
+    if (type == R2F_PROJ_EQUISOLID) {
+        const float n = s + 1.f, m = 2.f * s;
+        const float h = n / m;
+        const float e = sqrtf(h);
+        const float b = s * e;
+        return 1.f / b;
+    }
+    return 1.f;
+}
+
+// source_offset through the projection step (r2f_lens_correct_projected): the output pixel's rectilinear radius goes to the lens's
+// own projection before the distortion model sees it.  With P == 1 every value below is source_offset's.
+R2F_HD void source_offset(const r2f_lens_params& p, const r2f_lens_projection_params& pp, int X, int Y, float& ox, float& oy, float& dx,
+                          float& dy) {
+    R2F_NO_CONTRACT
+    dx = (float)X - p.cx;
+    dy = (float)Y - p.cy;
+    const float u = dx * p.q, v = dy * p.q;
+    const float uu = u * u, vv = v * v;
+    const float r2 = uu + vv;
+    const float r = sqrtf(r2);
+    const float t = r * pp.inv_focal;
+    const float P = projection_factor(pp.type, t);
+    const float up = u * P, vp = v * P;
+    const float upp = up * up, vpp = vp * vp;
+    const float r2p = upp + vpp;
+    const float f = model_factor(p, r2p);
+    const float g0 = f * P;
+    const float g = g0 * p.inv_scale;
     ox = dx * g, oy = dy * g;
 }
 
@@ -63,6 +139,13 @@ R2F_HD void source_coord(const r2f_lens_params& p, int X, int Y, float& sx, floa
     R2F_NO_CONTRACT
     float ox, oy;
     source_offset(p, X, Y, ox, oy, dx, dy);
+    sx = p.cx + ox;
+    sy = p.cy + oy;
+}
+
+// The centre plus an offset: the coordinate all three channels share without a TCA record, and green's with one.
+R2F_HD void centre_coord(const r2f_lens_params& p, float ox, float oy, float& sx, float& sy) {
+    R2F_NO_CONTRACT
     sx = p.cx + ox;
     sy = p.cy + oy;
 }
@@ -206,6 +289,39 @@ R2F_HD void correct_pixel_tca(const r2f_lens_params& p, const r2f_lens_tca_param
         int ix, iy, fx, fy;
         out[ch] = 0.f;
         if (!split_phase(sx, W, ix, fx) || !split_phase(sy, H, iy, fy)) continue;  // outside: 0 for this channel alone
+        out[ch] = finish(p, sample64_channel(fetch, ch, H, W, ix, iy, table + fx * kTaps, table + fy * kTaps), dx, dy);
+    }
+}
+
+// correct_pixel through the projection step.
+template <typename Fetch>
+R2F_HD void correct_pixel(const r2f_lens_params& p, const r2f_lens_projection_params& pp, const Fetch& fetch, int H, int W, const float* table,
+                          int X, int Y, float (&out)[3]) {
+    R2F_NO_CONTRACT
+    float ox, oy, dx, dy;
+    source_offset(p, pp, X, Y, ox, oy, dx, dy);
+    float sx, sy;
+    centre_coord(p, ox, oy, sx, sy);
+    int ix, iy, fx, fy;
+    out[0] = out[1] = out[2] = 0.f;
+    if (!split_phase(sx, W, ix, fx) || !split_phase(sy, H, iy, fy)) return;
+    float acc[3];
+    sample64(fetch, H, W, ix, iy, table + fx * kTaps, table + fy * kTaps, acc);
+    for (int c = 0; c < 3; ++c) out[c] = finish(p, acc[c], dx, dy);
+}
+
+// correct_pixel_tca through the projection step.
+template <typename Fetch>
+R2F_HD void correct_pixel_tca(const r2f_lens_params& p, const r2f_lens_projection_params& pp, const r2f_lens_tca_params& tca, const Fetch& fetch,
+                              int H, int W, const float* table, int X, int Y, float (&out)[3]) {
+    float ox, oy, dx, dy;
+    source_offset(p, pp, X, Y, ox, oy, dx, dy);
+    for (int ch = 0; ch < 3; ++ch) {
+        float sx, sy;
+        channel_coord(p, tca, ch, ox, oy, sx, sy);
+        int ix, iy, fx, fy;
+        out[ch] = 0.f;
+        if (!split_phase(sx, W, ix, fx) || !split_phase(sy, H, iy, fy)) continue;
         out[ch] = finish(p, sample64_channel(fetch, ch, H, W, ix, iy, table + fx * kTaps, table + fy * kTaps), dx, dy);
     }
 }

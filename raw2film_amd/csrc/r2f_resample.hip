@@ -473,6 +473,159 @@ __global__ __launch_bounds__(256) void lens_correct_tca_kernel(const LensTcaArgs
     }
 }
 
+// ------------------------------------------------------------------------------ lens correction of a projected lens (pre-path)
+// r2f_lens_correct_projected: the fisheye-to-rectilinear step in front of the distortion model (lens::source_offset with the
+// projection params), without a TCA record (kTca false: one coordinate, lens::sample64 over three channels) or with one (kTca true:
+// lens::channel_coord and lens::sample64_channel per channel).  The shape is lens_correct_tca_kernel's -- a 64 x 16 tile, four rows
+// per lane, the map evaluated again in the sampling pass so that nothing per row stays live -- with another staging rule.  A fisheye
+// frame at its auto scale is magnified in the middle (scale 0.70 for a 180-degree diagonal on 3:2: a centre tile's taps span some
+// 99 x 31 texels and more with a TCA record, at or past the 3072 a box holds) and shrunk towards the corners, so the tiles that cover
+// most of the picture would be the ones to lose their box.  Three routes, decided per block from the tap extents of its two halves
+// (tile rows 0 .. 7 and 8 .. 15):
+//   whole   the union of the halves' extents fits the box: one staging, one sampling pass over all four rows per lane;
+//   halves  it does not: each half is a pass of its own with its own box (some 99 x 20 texels at scale 0.70), staged when it fits;
+//   gather  a half whose box does not fit either takes its taps from global memory.
+// The sums are lens::sample64's / sample64_channel's over either fetch functor in the same order: the result does not depend on the
+// route.  The compiler reports (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage) for <false> / <true>: 253 / 153 VGPRs,
+// 2 / 3 waves per SIMD, no VGPR spills, no scratch, 0 / 7 SGPRs spilled into VGPR lanes, 37,920 B of LDS; lens_correct_kernel and
+// lens_correct_tca_kernel keep their 253 VGPRs / 2 waves and 145 VGPRs / 3 waves / 37,904 B.
+// Measured beside the unprojected kernels in one process (profiles/r26_lens_projection_probe.txt), 24 / 100 MP:
+//   - identity record (P exactly 1, the same texels, bit-identical output): <false> 1.39 x / 1.40 x lens_correct_kernel -- the price
+//     of evaluating the map twice and of rows as a loop where that kernel keeps four unrolled rows' indices in registers; a form
+//     of <false> with lens_correct_kernel's unrolled rows inside the pass loop spilled (9.5 KB of scratch per lane) and was
+//     dropped; <true> 1.20 x / 1.18 x lens_correct_tca_kernel;
+//   - fisheye record (focal 2/pi) at its auto scale (0.76 on these 2:3 frames): every block whole without a record; with the poly3
+//     record 5 % / 26 % of the blocks work in halves and 0 / 5 % gather.  <false> 1.97 x / 2.05 x lens_correct_kernel at the same
+//     scale, <true> 1.20 x / 1.00 x lens_correct_tca_kernel;
+//   - equisolid record (0.55) at its auto scale (0.60): 12 % of the blocks in halves without a record; with it 18 % / 15 % in halves
+//     and 5 % / 22 % gathering.  <false> 2.34 x / 2.34 x, <true> 1.71 x / 1.96 x their unprojected kernels at the same scale.
+// The unprojected kernels get FASTER as the scale falls (lens_correct_kernel 1.24 -> 0.82 ms at 24 MP from scale 1.02 to 0.60, its
+// gathering blocks included: a magnified frame reads fewer texels and its gathers hit in cache), while the projected ones stay at
+// 19 - 21 x the copy: at these scales the two-halves route saves less than the estimate that motivated it, and the projected
+// kernels are bound by their per-pixel arithmetic (the map twice, one division and a 19-operation polynomial or two square roots
+// and up to three divisions for P), not by staging.
+struct LensProjectedArgs {
+    LensArgs lens;
+    r2f_lens_projection_params proj;
+    r2f_lens_tca_params tca;  // read by the kernel with a TCA record only
+};
+
+template <bool kTca>
+__global__ __launch_bounds__(256) void lens_correct_projected_kernel(const LensProjectedArgs t) {
+    const LensArgs& a = t.lens;
+    __shared__ float table[lens::kPhases * lens::kTaps];
+    __shared__ float box[3 * kLensBoxTexels];
+    __shared__ int ext[2][4];  // per half: min ix, max ix, min iy, max iy over its inside pixels, all channels
+    const int tid = threadIdx.y * 64 + threadIdx.x;
+    table[tid] = a.table[tid];
+    if (tid < 8) ext[tid >> 2][tid & 3] = (tid & 1) ? INT_MIN : INT_MAX;
+    __syncthreads();
+    const int dx = blockIdx.x * 64 + threadIdx.x, dy0 = blockIdx.y * (4 * kLensRows) + threadIdx.y;
+    const bool col_in = dx < a.out_w;
+    constexpr int kHalfRows = kLensRows / 2;  // rows per lane in a half
+    if (col_in) {
+#pragma unroll 1
+        for (int half = 0; half < 2; ++half) {
+            int lo_x = INT_MAX, hi_x = INT_MIN, lo_y = INT_MAX, hi_y = INT_MIN;
+#pragma unroll 1
+            for (int r = half * kHalfRows; r < (half + 1) * kHalfRows; ++r) {
+                const int dy = dy0 + 4 * r;
+                if (dy >= a.out_h) break;
+                float ox, oy, ddx, ddy;
+                lens::source_offset(a.p, t.proj, dx + a.ox, dy + a.oy, ox, oy, ddx, ddy);
+#pragma unroll
+                for (int ch = kTca ? 0 : 1; ch < (kTca ? 3 : 2); ++ch) {  // (without a record every channel is green's)
+                    float sx, sy;
+                    if constexpr (kTca)
+                        lens::channel_coord(a.p, t.tca, ch, ox, oy, sx, sy);
+                    else
+                        lens::centre_coord(a.p, ox, oy, sx, sy);
+                    int ix, iy, fx, fy;
+                    if (!lens::split_phase(sx, a.W, ix, fx) || !lens::split_phase(sy, a.H, iy, fy)) continue;
+                    lo_x = min(lo_x, ix), hi_x = max(hi_x, ix), lo_y = min(lo_y, iy), hi_y = max(hi_y, iy);
+                }
+            }
+            if (lo_x <= hi_x) {
+                atomicMin(&ext[half][0], lo_x), atomicMax(&ext[half][1], hi_x);
+                atomicMin(&ext[half][2], lo_y), atomicMax(&ext[half][3], hi_y);
+            }
+        }
+    }
+    __syncthreads();
+    // (block-uniform from here: every thread reads the same eight words; ix, iy lie in [-4, n + 2] (split_phase), so the extents
+    // are small ints and their products cannot overflow)
+    const int un_lo_x = min(ext[0][0], ext[1][0]), un_hi_x = max(ext[0][1], ext[1][1]);
+    const int un_lo_y = min(ext[0][2], ext[1][2]), un_hi_y = max(ext[0][3], ext[1][3]);
+    const bool whole = un_lo_x > un_hi_x || (long long)(un_hi_x - un_lo_x + 8) * (un_hi_y - un_lo_y + 8) <= kLensBoxTexels;
+    const LensFetch global3{static_cast<const float*>(a.in), a.in_layout, a.H, a.W};
+    const LensChannelFetch global1{static_cast<const float*>(a.in), a.in_layout, a.H, a.W};
+#pragma unroll 1
+    for (int pass = 0; pass < (whole ? 1 : 2); ++pass) {
+        const int lo_x = whole ? un_lo_x : ext[pass][0], hi_x = whole ? un_hi_x : ext[pass][1];
+        const int lo_y = whole ? un_lo_y : ext[pass][2], hi_y = whole ? un_hi_y : ext[pass][3];
+        const int r_begin = whole ? 0 : pass * kHalfRows, r_end = whole ? kLensRows : (pass + 1) * kHalfRows;
+        const bool any = lo_x <= hi_x;
+        const int x0 = lo_x - 3, y0 = lo_y - 3;
+        const int bw = any ? hi_x + 4 - x0 + 1 : 0, bh = any ? hi_y + 4 - y0 + 1 : 0;
+        const bool staged = any && (long long)bw * bh <= kLensBoxTexels;
+        if (pass) __syncthreads();  // (the first half's lanes are done with the box)
+        if (staged) {
+            for (int i = tid; i < bw * bh; i += 256) {
+                const int y = y0 + i / bw, x = x0 + i % bw;
+                float v[3] = {0.f, 0.f, 0.f};
+                if (y >= 0 && y < a.H && x >= 0 && x < a.W) global3(y, x, v);
+                box[i] = v[0], box[kLensBoxTexels + i] = v[1], box[2 * kLensBoxTexels + i] = v[2];
+            }
+        }
+        __syncthreads();
+        if (!col_in) continue;  // (block-uniform trip count: such a lane still meets every barrier)
+        const LensLdsFetch lds3{box, x0, y0, bw};
+        const LensLdsChannelFetch lds1{box, x0, y0, bw};
+#pragma unroll 1
+        for (int r = r_begin; r < r_end; ++r) {
+            const int dy = dy0 + 4 * r;
+            if (dy >= a.out_h) break;
+            float ox, oy, ddx, ddy;
+            lens::source_offset(a.p, t.proj, dx + a.ox, dy + a.oy, ox, oy, ddx, ddy);
+            float* p0 = a.dst.data + (long long)(dy - a.dst.gy0) * a.out_w + dx;
+            if constexpr (kTca) {
+#pragma unroll 1
+                for (int ch = 0; ch < 3; ++ch) {
+                    float sx, sy;
+                    lens::channel_coord(a.p, t.tca, ch, ox, oy, sx, sy);
+                    int ix, iy, fx, fy;
+                    float v = 0.f;
+                    if (lens::split_phase(sx, a.W, ix, fx) && lens::split_phase(sy, a.H, iy, fy)) {
+                        const float *wx = table + fx * lens::kTaps, *wy = table + fy * lens::kTaps;
+                        const float acc = staged ? lens::sample64_channel(lds1, ch, a.H, a.W, ix, iy, wx, wy)
+                                                 : lens::sample64_channel(global1, ch, a.H, a.W, ix, iy, wx, wy);
+                        v = lens::finish(a.p, acc, ddx, ddy);
+                    }
+                    p0[ch * a.dst.plane_stride] = v;
+                }
+            } else {
+                float sx, sy;
+                lens::centre_coord(a.p, ox, oy, sx, sy);
+                int ix, iy, fx, fy;
+                float v[3] = {0.f, 0.f, 0.f};
+                if (lens::split_phase(sx, a.W, ix, fx) && lens::split_phase(sy, a.H, iy, fy)) {
+                    const float *wx = table + fx * lens::kTaps, *wy = table + fy * lens::kTaps;
+                    float acc[3];
+                    if (staged)
+                        lens::sample64(lds3, a.H, a.W, ix, iy, wx, wy, acc);
+                    else
+                        lens::sample64(global3, a.H, a.W, ix, iy, wx, wy, acc);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) v[c] = lens::finish(a.p, acc[c], ddx, ddy);
+                }
+                p0[0] = v[0];
+                p0[a.dst.plane_stride] = v[1];
+                p0[2 * a.dst.plane_stride] = v[2];
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------ LANCZOS4, uint8 (post-path)
 struct LanczosArgs {
     const uint8_t* src;  // (H, W, 3)
@@ -718,6 +871,29 @@ int r2f_lens_correct_tca(r2f_ctx* ctx, const void* in, int in_layout, int H, int
     if (rc) return rc;
     a.tca = *tca_params;
     launch_k(lens_correct_tca_kernel, lens_grid(out_h, out_w), dim3(64, 4), 0, static_cast<hipStream_t>(stream), a);
+    R2F_HIP(ctx, take_launch_status());
+    return R2F_OK;
+}
+
+int r2f_lens_correct_projected(r2f_ctx* ctx, const void* in, int in_layout, int H, int W, const r2f_lens_params* params,
+                               const r2f_lens_projection_params* projection_params, const r2f_lens_tca_params* tca_params,
+                               const r2f_planes* dst, int out_h, int out_w, int oy, int ox, void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    if (!projection_params) return fail(ctx, R2F_EINVAL, "lens_correct_projected: bad arguments");
+    if (projection_params->type < R2F_PROJ_FISHEYE || projection_params->type > R2F_PROJ_ORTHOGRAPHIC)
+        return fail(ctx, R2F_EINVAL, "lens_correct_projected: projection type %d (without a projection the call is r2f_lens_correct or r2f_lens_correct_tca)",
+                    projection_params->type);
+    if (tca_params && tca_params->model != R2F_TCA_LINEAR && tca_params->model != R2F_TCA_POLY3)
+        return fail(ctx, R2F_EINVAL, "lens_correct_projected: TCA model %d (without TCA pass no record)", tca_params->model);
+    LensProjectedArgs a{};
+    const int rc = lens_args(ctx, "lens_correct_projected", in, in_layout, H, W, params, dst, out_h, out_w, oy, ox, &a.lens);
+    if (rc) return rc;
+    a.proj = *projection_params;
+    if (tca_params) a.tca = *tca_params;
+    // the two forms of the projected kernel, by whether there is a TCA record
+    static constexpr void (*kProjected[2])(LensProjectedArgs) = {lens_correct_projected_kernel<false>, lens_correct_projected_kernel<true>};
+    launch_k(kProjected[tca_params ? 1 : 0], lens_grid(out_h, out_w), dim3(64, 4), 0, static_cast<hipStream_t>(stream), a);
     R2F_HIP(ctx, take_launch_status());
     return R2F_OK;
 }

@@ -339,7 +339,9 @@ class HipProcessor:
         frame's size, the `window` (row0, col0, rows, cols) of the corrected frame the aspect crop keeps (with the zoom crop when
         there is no rotation) and the quarter turns still to be applied to it; every crop-derived value (`pipeline_resolution`
         ...) is that of the same call without a profile.  A profile with `tca` adds the r2f_lens_tca_params under `tca`, and the
-        step is r2f_lens_correct_tca; without one the step has no such key.  lens_correction=False ignores the profile.
+        step is r2f_lens_correct_tca; without one the step has no such key.  A profile with `projection` adds the
+        r2f_lens_projection_params under `projection` in the same way, and the step is r2f_lens_correct_projected.
+        lens_correction=False ignores the profile.
         raw_profile (a raw2film_amd.raw.RawProfile): `src` is a Bayer mosaic, uint16 (H, W), demosaiced on the device (include/r2f.h,
         r2f_demosaic_u16; `half_size` selects the half-size form) into the uint16 frame every other word of this text is about.
         `image_array` is the mosaic and the payload gains `demosaic`: the r2f_demosaic_params, and the `window` (row0, col0, rows,
@@ -365,14 +367,14 @@ class HipProcessor:
         internal = bool(kwargs.get("_internal"))
         image = phase1.load_decoded(src, clip=not internal, mosaic=raw_profile is not None)
         rows, cols, is_u16 = image.shape[0], image.shape[1], image.dtype == np.uint16
-        demosaic_params = lens_params = lens_tca = None
+        demosaic_params = lens_params = lens_projection = lens_tca = None
         if raw_profile is not None:  # the crops are those of the demosaiced frame, which is uint16
             demosaic_params = raw_profile.plan(rows, cols, half_size)
             rows, cols = raw_profile.oriented_shape(rows, cols, half_size)  # (the params' out_h, out_w, the way round the sensor was held)
         on_device, exposure, exposure_rejected = phase1.exposure_mode(exposure, on_device, is_u16, raw_profile is not None, rotation,
                                                                       rotate_times)
         if lens_correction and lens_profile is not None:
-            lens_params, lens_tca = lens_profile.plan_tca(rows, cols)
+            lens_params, lens_projection, lens_tca = lens_profile.plan_projected(rows, cols)
         u16_factor = exposure_root = None
         if is_u16:
             from . import decode
@@ -413,8 +415,10 @@ class HipProcessor:
             "warp": crops.warp,  # free rotation still to be applied (first of the device pre-path steps), or None
             "upscale_to": res.upscale_to,  # (rows, cols) the rendered uint8 frame is LANCZOS4-scaled back into, or None
             # the lens step (first of the device pre-path steps)
-            # (with `tca`, the r2f_lens_tca_params, only for a profile that has TCA)
-            **({"lens": {"params": lens_params, **crops.lens, **({"tca": lens_tca} if lens_tca is not None else {})}}
+            # (with `tca`, the r2f_lens_tca_params, only for a profile that has TCA; with `projection`, the
+            # r2f_lens_projection_params, only for one that has a projection)
+            **({"lens": {"params": lens_params, **crops.lens, **({"tca": lens_tca} if lens_tca is not None else {}),
+                         **({"projection": lens_projection} if lens_projection is not None else {})}}
                if lens_params is not None else {}),
             # `image_array` is a Bayer mosaic (ahead of all)
             **({"demosaic": {"params": demosaic_params, **crops.demosaic,
@@ -1153,7 +1157,8 @@ class HipProcessor:
         layout = None  # the payload is (H, W, C) like the reference's; the device pre-path hands on (3, H, W) planes
         lens_step = cpu_payload.get("lens")
         if lens_step:  # lens correction (effects.lens_correction) of the whole frame, into the window the crops keep
-            corrected = self.ctx.lens_correct(image.contiguous(), lens_step["params"], lens_step["window"], tca=lens_step.get("tca"))
+            corrected = self.ctx.lens_correct(image.contiguous(), lens_step["params"], lens_step["window"], tca=lens_step.get("tca"),
+                                              projection=lens_step.get("projection"))
             image = cut_and_turn(corrected, None, lens_step.get("rotate_times")).contiguous()  # (the planes themselves unless they were turned)
             layout = "chw"
         warp = cpu_payload.get("warp")

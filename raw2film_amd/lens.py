@@ -2,21 +2,24 @@
 
 Upstream corrects through lensfunpy (effects.py:22-43): it looks the camera and the lens up in lensfun's database and applies what
 it finds.  The lookup is third-party input; this module takes its RESULT -- a distortion model with its coefficients, a vignetting
-model, the optical centre, a scale, TCA constants -- and `plan()` / `plan_tca()` turn it into the fp32 constants of one frame size
-(r2f_lens_plan, r2f_lens_plan_tca, which also resolve scale="auto").  The definition of the correction is in include/r2f.h
-(r2f_lens_correct, r2f_lens_correct_tca).
+model, the optical centre, a scale, TCA constants, the lens's projection -- and `plan()` / `plan_tca()` / `plan_projected()` turn it
+into the fp32 constants of one frame size (r2f_lens_plan, r2f_lens_plan_tca, r2f_lens_plan_projected, which also resolve
+scale="auto").  The definition of the correction is in include/r2f.h (r2f_lens_correct, r2f_lens_correct_tca,
+r2f_lens_correct_projected).
 """
 
 from __future__ import annotations
 
 import ctypes as C
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 from . import _lib
 
 _MODELS = {"none": (_lib.LENS_NONE, 0), "poly3": (_lib.LENS_POLY3, 1), "poly5": (_lib.LENS_POLY5, 2), "ptlens": (_lib.LENS_PTLENS, 3)}
 _TCA_MODELS = {"linear": (_lib.TCA_LINEAR, 1), "poly3": (_lib.TCA_POLY3, 3)}  # (enum, constants per channel)
+_PROJECTIONS = {"fisheye": _lib.PROJ_FISHEYE, "stereographic": _lib.PROJ_STEREOGRAPHIC, "equisolid": _lib.PROJ_EQUISOLID,
+                "orthographic": _lib.PROJ_ORTHOGRAPHIC}
 
 
 def _floats(name, values, n):
@@ -43,13 +46,17 @@ class LensProfile:
     norm_radius_px: the pixel distance at which r = 1; None: half the diagonal, hypot(W - 1, H - 1) / 2.
     tca: None, ("linear", (kr, kb)) or ("poly3", (vr, vb, cr, cb, br, bb)) -- transverse chromatic aberration, in the order of
     lensfun's XML attributes: red and blue sample at the corrected coordinate's offset from the centre times kr / kb, or times
-    b Ru^2 + c Ru + v of their own constants (r2f_lens_correct_tca)."""
+    b Ru^2 + c Ru + v of their own constants (r2f_lens_correct_tca).
+    projection: None, or (type, focal) with type "fisheye" | "stereographic" | "equisolid" | "orthographic" -- lensfun's lens types
+    that are not rectilinear -- and focal the focal length in units of r: the frame is taken to the rectilinear projection in front
+    of the distortion model (r2f_lens_correct_projected).  It is the last parameter of the constructor and goes by keyword."""
     distortion: str = "none"
     coefficients: tuple = ()
     vignetting: tuple | None = None
     center: tuple = (0.0, 0.0)
     scale: float | str = 1.0
     norm_radius_px: float | None = None
+    projection: tuple | None = field(default=None, kw_only=True)  # (a keyword-only field comes last in the constructor)
     tca: tuple | None = None
 
     def __post_init__(self):
@@ -81,6 +88,17 @@ class LensProfile:
             if not isinstance(model, str) or model not in _TCA_MODELS:
                 raise ValueError(f"LensProfile.tca's model must be one of {sorted(_TCA_MODELS)}, got {model!r}")
             set_("tca", (model, _floats("tca", values, 2 * _TCA_MODELS[model][1])))
+        if self.projection is not None:
+            try:
+                kind, focal = self.projection
+            except (TypeError, ValueError):
+                raise ValueError(f"LensProfile.projection must be (type, focal), got {self.projection!r}") from None
+            if not isinstance(kind, str) or kind not in _PROJECTIONS:
+                raise ValueError(f"LensProfile.projection's type must be one of {sorted(_PROJECTIONS)}, got {kind!r}")
+            (focal,) = _floats("projection", (focal,), 1)
+            if focal <= 0:
+                raise ValueError(f"LensProfile.projection's focal length must be positive, got {self.projection!r}")
+            set_("projection", (kind, focal))
 
     def to_c(self) -> _lib.LensProfile:
         model, n = _MODELS[self.distortion]
@@ -123,3 +141,29 @@ class LensProfile:
         if _lib.load().r2f_lens_plan_tca(C.byref(profile), C.byref(tca), int(H), int(W), C.byref(out), C.byref(out_tca)) != _lib.OK:
             raise ValueError(f"r2f_lens_plan_tca refused {self!r} for a {H} x {W} frame")
         return out, out_tca
+
+    def to_c_projection(self) -> _lib.LensProjection | None:
+        """The r2f_lens_projection of `projection`, or None without one."""
+        if self.projection is None:
+            return None
+        kind, focal = self.projection
+        return _lib.LensProjection(type=_PROJECTIONS[kind], focal=focal)
+
+    def plan_projected(self, H: int, W: int) -> tuple:
+        """(r2f_lens_params, r2f_lens_projection_params, r2f_lens_tca_params or None) of an H x W frame (no GPU;
+        r2f_lens_plan_projected: with scale="auto" the probes go through the projection, and through `tca` when there is one);
+        (plan_tca(H, W)[0], None, plan_tca(H, W)[1]) for a profile without `projection`.  ValueError for what the planner refuses:
+        with scale="auto" also a circular fisheye, whose image circle never reaches the frame's boundary."""
+        projection = self.to_c_projection()
+        if projection is None:
+            params, tca_params = self.plan_tca(H, W)
+            return params, None, tca_params
+        tca = self.to_c_tca()
+        out, out_projection = _lib.LensParams(), _lib.LensProjectionParams()
+        out_tca = None if tca is None else _lib.LensTcaParams()
+        profile = self.to_c()
+        rc = _lib.load().r2f_lens_plan_projected(C.byref(profile), C.byref(projection), None if tca is None else C.byref(tca), int(H), int(W),
+                                                 C.byref(out), C.byref(out_projection), None if tca is None else C.byref(out_tca))
+        if rc != _lib.OK:
+            raise ValueError(f"r2f_lens_plan_projected refused {self!r} for a {H} x {W} frame")
+        return out, out_projection, out_tca
