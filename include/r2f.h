@@ -776,6 +776,80 @@ typedef struct r2f_raw_scale {
  * pointer, another n_black, a black level, white balance, white level or threshold outside its range (a NaN is outside every range),
  * data_maximum above 65535 and m < 1; a refusal leaves *out alone. */
 R2F_API int r2f_raw_scale_plan(const r2f_raw_levels* levels, const double* black, int n_black, uint32_t data_maximum, r2f_raw_scale* out);
+
+/* LibRaw's highlight modes 1 (unclip) and 2 (blend) -- rawpy's highlight_mode= of the same postprocess call.  The Scale steps above
+ * are mode 0 (clip): the smallest white-balance factor becomes 1 and step A clamps at 65535, so a channel with a larger factor loses
+ * the top 1 - min(wb) / wb[c] of the sensor's range.  Modes 3 .. 9 (rebuild) are a sequential spreading over a down-sampled map and
+ * are NOT built: they are refused by name.  Parity with LibRaw's bytes is UNPINNED like the rest of the demosaic; the arithmetic
+ * follows dcraw / LibRaw's published scale_colors and blend_highlights, and what the tests pin is THIS definition
+ * (tests/highlight_model.py restates it in NumPy).
+ *
+ * Scale with a highlight mode.  Inputs: those of the Scale steps, and mode in {0, 1, 2}.  m, the threshold rule, d and m_eff are
+ * unchanged.
+ *   Mode 0: exactly the Scale steps' result.
+ *   Modes 1 and 2: mul[c] = wb[c] / max(wb) * 65535.0 / m_eff, evaluated in double, left to right: the largest factor becomes 1 and
+ *   nothing is cut below the sensor's own saturation.
+ *   Mode 2 also yields the clip level: p[c] = (float)(wb[c] / max(wb)); clip = min over c of trunc(fl(65535.0f * p[c])) -- one fp32
+ *   multiply per channel; refused when clip < 1.  As in LibRaw an adjusted maximum changes mul and does not change clip.
+ *
+ * Blend sits between the interpolation and step C of either demosaic: it acts on the pixel's three integers (v0, v1, v2) in
+ * [0, 65535] as B / B' leave them, at full and at reduced size and for either pattern.  Its one parameter is clip in [1, 65535].
+ * Every operation below is one correctly rounded fp32 operation, no contraction; trunc is toward zero.
+ *   If no v[c] > clip the pixel is unchanged (a pixel exactly at clip is unchanged).  Otherwise
+ *     cam0[c] = (float)v[c];  cam1[c] = min(cam0[c], (float)clip)
+ *     for i in {0, 1}:  lab[i][k] = fl(fl(fl(T[k][0] cam_i[0]) + fl(T[k][1] cam_i[1])) + fl(T[k][2] cam_i[2])),  k = 0, 1, 2
+ *       T = {{1, 1, 1}, {0x1.bb67aep+0f, -0x1.bb67aep+0f, 0}, {-1, -1, 2}}                       (0x1.bb67aep+0f = 1.7320508f)
+ *     sum[i] = fl(fl(lab[i][1]^2) + fl(lab[i][2]^2))
+ *     chratio = sqrtf(fl(sum[1] / sum[0])), correctly rounded; 1 when sum[0] == 0.  (dcraw divides 0 by 0 there: three equal
+ *       channels above clip have no chroma to scale, cam1's sum is 0 as well, and the NaN of 0 / 0 would reach the integer
+ *       conversion.  With chratio = 1 the pixel leaves as it came, up to the rounding of the two transforms.)
+ *     lab[0][1] = fl(lab[0][1] chratio);  lab[0][2] = fl(lab[0][2] chratio)
+ *     out[c] = clamp(trunc(fl(fl(fl(fl(I[c][0] lab[0][0]) + fl(I[c][1] lab[0][1])) + fl(I[c][2] lab[0][2])) / 3.0f)), 0, 65535)
+ *       I = {{1, 0x1.bb67aep-1f, -0x1p-1f}, {1, -0x1.bb67aep-1f, -0x1p-1f}, {1, 0, 1}}            (0x1.bb67aep-1f = 0.8660254f)
+ *   Step C then runs on out.  All magnitudes stay below 2^20 ahead of the squares and below 2^41 behind them: nothing overflows, no
+ *   NaN arises (sum[0] > 0 where it divides), and the truncation stays inside int. */
+enum { R2F_HIGHLIGHT_CLIP = 0, R2F_HIGHLIGHT_UNCLIP = 1, R2F_HIGHLIGHT_BLEND = 2 };
+/* What the Scale steps yield beside the r2f_raw_scale: the mode, and mode 2's clip level (0 for modes 0 and 1). */
+typedef struct r2f_highlight {
+    int32_t mode, clip;
+} r2f_highlight;
+/* Host planner (raw2film_amd/csrc/r2f_levels_plan.cpp; no GPU, no context): Scale with a highlight mode.  Mode 0 yields
+ * r2f_raw_scale_plan's result bit for bit and *hl = {0, 0}.  R2F_EINVAL for everything r2f_raw_scale_plan refuses, a null hl, a mode
+ * outside {0, 1, 2} -- LibRaw's rebuild modes 3 .. 9 among them -- and clip < 1; a refusal leaves *out and *hl alone. */
+R2F_API int r2f_raw_scale_plan_highlight(const r2f_raw_levels* levels, const double* black, int n_black, uint32_t data_maximum, int mode,
+                     r2f_raw_scale* out, r2f_highlight* hl);
+/* The demosaics with Blend.  Each is the entry point it is named after with one more argument, clip, and the same kernels compiled
+ * with Blend between the interpolation and step C; nothing new is staged in LDS, and the branch diverges inside a wave only where
+ * a tile crosses a blown area.  clip outside [1, 65535] is refused before any launch; clip = 65535 writes the bytes of the plain
+ * entry point (no integer in [0, 65535] exceeds it).
+ * r2f_demosaic_blend_u16 carries r2f_demosaic_oriented_u16's contract.  src_rows: uint16 mosaic rows [src_gy0, src_gy0 +
+ * src_nrows) of the H x W frame on the device, src_pitch samples apart (>= W).  orientation = 0 is upright: writes output rows
+ * [y0, y1) of dst (uint16 (out_h, out_w, 3), row 0 at dst) and nothing else; full size reads mosaic rows [y0 - 4, y1 + 4) clipped to
+ * [0, H), half size [2 y0, 2 y1); those rows must lie inside the source window, else R2F_EINVAL before any launch.  With an
+ * orientation [y0, y1) are rows of O: the call writes those rows of dst (O, contiguous, row 0 at dst) and nothing else.  Without
+ * bit 4 they are D's rows [y0, y1), or [out_h - y1, out_h - y0) with bit 2, and the call reads the mosaic rows the upright contract
+ * names for those rows of D; those must lie in the source window, else R2F_EINVAL before any launch.  With bit 4 they are D's columns
+ * [y0, y1), or [out_w - y1, out_w - y0) with bit 1: the call reads every mosaic row, and the source window must hold [0, H).
+ * Refused: everything the upright entry point refuses, and an orientation outside 0 .. 7.  A band's bytes are those of the same
+ * rows of a whole-frame call, whatever the cut, the pitch or the source's alignment (which only select between 32-bit and 16-bit
+ * loads of the same samples).  Every phase is still taken from frame coordinates of D.
+ * r2f_demosaic_blend_f32 carries r2f_demosaic_f32's contract.  With D the uint16 frame above (upright, with Blend) and (row0,
+ * col0, rows, cols) a non-empty window inside D, dst[y, x, c] = fminf((float)D[row0 + y, col0 + x, c] / divisor * factor, 65504.0f).
+ * dst: float32 (rows, cols, 3), contiguous, 4-byte aligned.  Writes window rows [y0, y1) of dst and nothing else.  Full size reads
+ * mosaic rows [row0 + y0 - 4, row0 + y1 + 4) clipped to [0, H), half size [2 (row0 + y0), 2 (row0 + y1)); those rows must lie inside
+ * the source window, else R2F_EINVAL before any launch.  The bytes depend on neither the cut, the pitch, the source's alignment nor
+ * the window's origin.  Refused: everything r2f_demosaic_u16 refuses, a window that is empty or not inside D, y0 > y1, y0 < 0, y1 >
+ * rows, divisor <= 0.
+ * r2f_demosaic_xtrans_blend_u16 carries r2f_demosaic_xtrans_oriented_u16's contract: the first paragraph above with full size
+ * reading mosaic rows [y0 - 3, y1 + 3) clipped to [0, H) and reduced size [3 y0, 3 y1) (the cut need not be a multiple of 6 or 3);
+ * params whose tables are not those the planner derives from their cfa are refused. */
+R2F_API int r2f_demosaic_blend_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
+                     const r2f_demosaic_params* params, int orientation, int clip, uint16_t* dst_u16_hwc3, int y0, int y1, void* stream);
+R2F_API int r2f_demosaic_blend_f32(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
+                     const r2f_demosaic_params* params, int clip, int row0, int col0, int rows, int cols, float divisor, float factor,
+                     float* dst_f32_hwc3, int y0, int y1, void* stream);
+R2F_API int r2f_demosaic_xtrans_blend_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H,
+                     int W, const r2f_xtrans_params* params, int orientation, int clip, uint16_t* dst_u16_hwc3, int y0, int y1, void* stream);
 /* The data maximum of mosaic rows [y0, y1), folded into a device word: *dst_max = max(*dst_max, d of those rows).  The caller zeroes
  * the word before the first call; bands in any order and any cut then compose to the whole frame's value, and since an integer
  * maximum does not depend on order the result is exact and the same on every run.  src_rows: uint16 mosaic rows [src_gy0, src_gy0 +

@@ -131,6 +131,12 @@ class RawScale(C.Structure):  # r2f_raw_scale: the multipliers of one frame, the
     _fields_ = [("mul", C.c_double * 3), ("maximum_used", C.c_int32), ("adjusted", C.c_int32)]
 
 
+class Highlight(C.Structure):  # r2f_highlight: the highlight mode a scale was planned with, and mode 2's clip level
+    _fields_ = [("mode", C.c_int32), ("clip", C.c_int32)]
+
+
+HIGHLIGHT_CLIP, HIGHLIGHT_UNCLIP, HIGHLIGHT_BLEND = 0, 1, 2  # R2F_HIGHLIGHT_*: LibRaw's highlight modes 0, 1 and 2
+
 _P = C.POINTER
 _fp = C.c_void_p  # float* (host numpy or device) passed as an address
 _SIGNATURES = {
@@ -252,6 +258,23 @@ _SIGNATURES = {
          C.c_void_p],
     ),
     "r2f_raw_scale_plan": (C.c_int, [_P(RawLevels), _P(C.c_double), C.c_int, C.c_uint32, _P(RawScale)]),
+    "r2f_raw_scale_plan_highlight": (
+        C.c_int, [_P(RawLevels), _P(C.c_double), C.c_int, C.c_uint32, C.c_int, _P(RawScale), _P(Highlight)]),
+    "r2f_demosaic_blend_u16": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(DemosaicParams), C.c_int, C.c_int, C.c_void_p, C.c_int,
+         C.c_int, C.c_void_p],
+    ),
+    "r2f_demosaic_blend_f32": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(DemosaicParams), C.c_int, C.c_int, C.c_int, C.c_int,
+         C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    ),
+    "r2f_demosaic_xtrans_blend_u16": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(XTransParams), C.c_int, C.c_int, C.c_void_p, C.c_int,
+         C.c_int, C.c_void_p],
+    ),
     "r2f_mosaic_maximum": (
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P(C.c_int32), C.c_int, C.c_int, C.c_void_p,

@@ -93,10 +93,13 @@ def band_source(payload, shape, dtype) -> BandSource:
     frame, factor = frame[:2] + (3,), payload.get("u16_factor")
     step = payload.get("demosaic")
     if step:  # a Bayer mosaic: band k travels with the mosaic rows its demosaic reads beyond those of the bands before it
-        window, params = step["window"], step["params"]
+        window, params, clip = step["window"], step["params"], step.get("clip")
 
         def demosaic(ctx, landing, image, a0, a1):
-            ctx.demosaic_f32(landing, params, factor, window=window, out=image, rows=(a0, a1))
+            if clip is None:
+                ctx.demosaic_f32(landing, params, factor, window=window, out=image, rows=(a0, a1))
+            else:  # a ("blend", clip) profile: the same kernel with Blend ahead of the matrix
+                ctx.demosaic_blend_f32(landing, params, clip, factor, window=window, out=image, rows=(a0, a1))
 
         # A pinned mosaic queues every upload at once.  Its bytes are a third of the RGB frame's, so the render, not the upload, sets
         # the pace; with upload k queued only when band k's turn came the call was no faster than in one piece (100 MP: 15.9 against

@@ -18,6 +18,8 @@ LOG_EPS = 1e-6  # lut_1d.wgsl:24
 # params type -> (the HipContext method that demosaics a mosaic of it to the uint16 frame, the smallest side of such a mosaic): the one
 # place that says which demosaic a params type selects
 MOSAIC_KINDS = {_lib.DemosaicParams: ("demosaic_u16", 2), _lib.XTransParams: ("demosaic_xtrans", 6)}
+# ... and the method that does so with Blend (LibRaw's highlight mode 2), which takes the clip level behind the params
+MOSAIC_BLEND_KINDS = {_lib.DemosaicParams: "demosaic_blend_u16", _lib.XTransParams: "demosaic_xtrans_blend"}
 LUT3D_SCALE = 0.25  # cpu_processor.py:405
 
 
@@ -594,10 +596,11 @@ class HipContext:
         H, W = self._mosaic_size(mosaic, what, MOSAIC_KINDS[params_type][1])
         return H, W, params if isinstance(params, params_type) else params.plan(H, W)
 
-    def _demosaic(self, what, fn, params_type, mosaic, params, out, rows, window=None, decode=None, orientation=0):
-        """The three demosaic methods: the mosaic check, the planning of a profile, the window, the `out` check, `rows`, the call.
+    def _demosaic(self, what, fn, params_type, mosaic, params, out, rows, window=None, decode=None, orientation=0, clip=None):
+        """The demosaic methods: the mosaic check, the planning of a profile, the window, the `out` check, `rows`, the call.
         fn: the C entry point; decode = (divisor, factor): the float32 epilogue, which also takes a window (default: the frame);
-        orientation: not 0 with the oriented form of `fn` (r2f_demosaic_oriented_u16: `out` and `rows` are then those of O)."""
+        orientation: not 0 with the oriented form of `fn` (r2f_demosaic_oriented_u16: `out` and `rows` are then those of O);
+        clip: the blend form of `fn` (r2f_demosaic_blend_u16, which always takes an orientation, 0 included)."""
         torch = self._torch
         H, W, params = self._check_mosaic(mosaic, params, what, params_type)
         if isinstance(orientation, bool) or not isinstance(orientation, numbers.Integral) or not 0 <= orientation <= 7:
@@ -616,7 +619,9 @@ class HipContext:
         else:
             self._same_device(out, "out")
         y0, y1 = (0, nr) if rows is None else (int(rows[0]), int(rows[1]))
-        epilogue = (r0, c0, nr, nc, *decode) if decode else (int(orientation),) if orientation else ()
+        epilogue = (r0, c0, nr, nc, *decode) if decode else (int(orientation),) if orientation or clip is not None else ()
+        if clip is not None:
+            epilogue = (clip, *epilogue) if decode else (*epilogue, clip)
         self._check(fn(self._h, mosaic.data_ptr(), 0, H, int(mosaic.stride(0)), H, W, C.byref(params), *epilogue, out.data_ptr(), y0, y1,
                        self._stream()))
         return out
@@ -650,6 +655,30 @@ class HipContext:
         reads the rows its contract names and no others.  rows = (y0, y1): only those rows of the window are written."""
         return self._demosaic("demosaic_f32", self._lib.r2f_demosaic_f32, _lib.DemosaicParams, mosaic, params, out, rows, window,
                               (float(np.float32(divisor)), float(np.float32(factor))))
+
+    @staticmethod
+    def _blend_clip(what, clip) -> int:
+        if isinstance(clip, bool) or not isinstance(clip, numbers.Integral) or not 1 <= clip <= 65535:
+            raise ValueError(f"{what}: clip must be an integer in [1, 65535], got {clip!r}")
+        return int(clip)
+
+    def demosaic_blend_u16(self, mosaic, params, clip, out=None, rows=None, orientation=0):
+        """demosaic_u16 with Blend (r2f_demosaic_blend_u16; include/r2f.h, LibRaw's highlight mode 2): a pixel with a channel above
+        `clip` (an integer in [1, 65535]; a resolved "blend" profile's `blend_clip`) takes the chroma of its clipped version ahead of
+        the camera matrix.  Everything else is demosaic_u16's, `orientation` included; clip = 65535 yields its bytes."""
+        return self._demosaic("demosaic_blend_u16", self._lib.r2f_demosaic_blend_u16, _lib.DemosaicParams, mosaic, params, out, rows,
+                              orientation=orientation, clip=self._blend_clip("demosaic_blend_u16", clip))
+
+    def demosaic_xtrans_blend(self, mosaic, params, clip, out=None, rows=None, orientation=0):
+        """demosaic_xtrans with Blend (r2f_demosaic_xtrans_blend_u16): demosaic_blend_u16's `clip` for an X-Trans mosaic."""
+        return self._demosaic("demosaic_xtrans_blend", self._lib.r2f_demosaic_xtrans_blend_u16, _lib.XTransParams, mosaic, params, out, rows,
+                              orientation=orientation, clip=self._blend_clip("demosaic_xtrans_blend", clip))
+
+    def demosaic_blend_f32(self, mosaic, params, clip, factor: float, divisor: float = 65535.0, window=None, out=None, rows=None):
+        """demosaic_f32 with Blend (r2f_demosaic_blend_f32): bit-identical to decode_u16(demosaic_blend_u16(mosaic, params,
+        clip)[window], factor, divisor)."""
+        return self._demosaic("demosaic_blend_f32", self._lib.r2f_demosaic_blend_f32, _lib.DemosaicParams, mosaic, params, out, rows, window,
+                              (float(np.float32(divisor)), float(np.float32(factor))), clip=self._blend_clip("demosaic_blend_f32", clip))
 
     def mosaic_maximum(self, mosaic, profile_or_black, period=None, rows=None, out=None):
         """The data maximum of include/r2f.h (r2f_mosaic_maximum): the largest black-subtracted sample, clamped at 0, of a uint16

@@ -41,4 +41,33 @@ int r2f_raw_scale_plan(const r2f_raw_levels* levels, const double* black, int n_
     return R2F_OK;
 }
 
+// Mode 0 is the call above; modes 1 and 2 take its m_eff and normalise by the largest factor.  Both outputs are written together, and
+// only once nothing is left to refuse.
+int r2f_raw_scale_plan_highlight(const r2f_raw_levels* levels, const double* black, int n_black, uint32_t data_maximum, int mode,
+                                 r2f_raw_scale* out, r2f_highlight* hl) {
+    if (!out || !hl || mode < R2F_HIGHLIGHT_CLIP || mode > R2F_HIGHLIGHT_BLEND) return R2F_EINVAL;  // (3 .. 9: LibRaw's rebuild modes)
+    r2f_raw_scale r{};
+    if (const int rc = r2f_raw_scale_plan(levels, black, n_black, data_maximum, &r)) return rc;
+    r2f_highlight h{mode, 0};
+    if (mode != R2F_HIGHLIGHT_CLIP) {
+        const double* wb = levels->white_balance;  // (finite and > 0: the call above has passed them)
+        double wb_max = wb[0];
+        for (int c = 0; c < 3; ++c) wb_max = wb[c] > wb_max ? wb[c] : wb_max;
+        for (int c = 0; c < 3; ++c) r.mul[c] = wb[c] / wb_max * 65535.0 / (double)r.maximum_used;
+        if (mode == R2F_HIGHLIGHT_BLEND) {
+            int clip = 65535;
+            for (int c = 0; c < 3; ++c) {
+                const float p = (float)(wb[c] / wb_max);  // in [0, 1]
+                const float level = 65535.0f * p;         // one fp32 multiply, in [0, 65535]: the truncation stays inside int
+                clip = (int)level < clip ? (int)level : clip;
+            }
+            if (clip < 1) return R2F_EINVAL;
+            h.clip = clip;
+        }
+    }
+    *out = r;
+    *hl = h;
+    return R2F_OK;
+}
+
 }  // extern "C"

@@ -46,6 +46,47 @@ R2F_HD void colour(const float (&M)[9], const int (&rgb)[3], uint16_t (&out)[3])
     }
 }
 
+// Blend (include/r2f.h, LibRaw's highlight mode 2): a pixel with a channel above `clip` keeps its lightness and takes the chroma
+// magnitude of its clipped version; every other pixel is left alone.  Between the interpolation and step C, on the three integers in
+// [0, 65535]; clip in [1, 65535].  Each line is one fp32 operation, in the header's order.  |lab| < 2^19, the squares' sum < 2^41,
+// sum0 > 0 where it divides and |acc / 3| < 2^20: no NaN, and the truncation stays inside int.
+R2F_HD void blend_pixel(int (&v)[3], int clip) {
+    R2F_NO_CONTRACT
+    if (v[0] <= clip && v[1] <= clip && v[2] <= clip) return;
+    constexpr float kSqrt3 = 0x1.bb67aep+0f, kHalfSqrt3 = 0x1.bb67aep-1f;
+    const float fclip = (float)clip;
+    float lab[2][3];
+    float sum[2];
+    R2F_UNROLL
+    for (int i = 0; i < 2; ++i) {
+        float cam[3];
+        R2F_UNROLL
+        for (int c = 0; c < 3; ++c) {
+            const float f = (float)v[c];
+            cam[c] = i && f > fclip ? fclip : f;
+        }
+        // T = {{1, 1, 1}, {sqrt3, -sqrt3, 0}, {-1, -1, 2}}: a product with 1, -1 or 0 is exact, and x + 0 = x (no -0 arises here
+        // that a later step could tell from +0), so only the four roundings that can differ from the plain sum are spelled out
+        lab[i][0] = (cam[0] + cam[1]) + cam[2];
+        const float a = kSqrt3 * cam[0], b = -kSqrt3 * cam[1];
+        lab[i][1] = a + b;
+        const float t = 2.f * cam[2];
+        lab[i][2] = (-cam[0] + -cam[1]) + t;
+        const float s1 = lab[i][1] * lab[i][1], s2 = lab[i][2] * lab[i][2];
+        sum[i] = s1 + s2;
+    }
+    float chratio = 1.f;
+    if (sum[0] != 0.f) {
+        const float q = sum[1] / sum[0];
+        chratio = sqrtf(q);
+    }
+    const float l0 = lab[0][0], l1 = lab[0][1] * chratio, l2 = lab[0][2] * chratio;
+    // I = {{1, h, -1/2}, {1, -h, -1/2}, {1, 0, 1}}, h = sqrt3 / 2
+    const float h1 = kHalfSqrt3 * l1, n1 = -kHalfSqrt3 * l1, m2 = -0.5f * l2;
+    const float o0 = (l0 + h1) + m2, o1 = (l0 + n1) + m2, o2 = l0 + l2;
+    v[0] = clip16((int)(o0 / 3.0f)), v[1] = clip16((int)(o1 / 3.0f)), v[2] = clip16((int)(o2 / 3.0f));
+}
+
 // The mosaic rows [lo, hi) that rows [fy0, fy1) of the demosaiced frame D read (the row-range contract of include/r2f.h): full size
 // `reach` rows either side, clipped to the H rows of the mosaic; the reduced form (reduction = 2 or 3, else 0) the rows of its cells.
 R2F_HD void source_rows(int fy0, int fy1, int H, int reach, int reduction, int& lo, int& hi) {

@@ -10,7 +10,10 @@
 // Each is a template over a Pattern and over the epilogue: the uint16 frame, or a window of it decoded to the float frame the front
 // stage reads (decode_sample of r2f_device.h on each finished sample); and, for the uint16 frame written the way round the sensor
 // was held (the oriented entry points; the index map is r2f_mosaic_math.h's orient), over an OrientClass: mirrored rows leave from
-// the row buffer, quarter turns through the whole tile transposed in LDS.  A Pattern states what differs and nothing else:
+// the row buffer, quarter turns through the whole tile transposed in LDS; and over a Blend flag (the blend entry points: LibRaw's
+// highlight mode 2), which runs mosaic::blend_pixel on the pixel's three integers between pixel_rgb / reduced_rgb and step C -- in
+// registers: it stages nothing, and a wave diverges on it only where its row crosses a blown area.  The instantiations without the
+// flag are the kernels of before it.  A Pattern states what differs and nothing else:
 //   Params, Aux                   its r2f_*_params and the auxiliary plane's element type (uint16_t green / int colour difference)
 //   kMinSide, kReduction          the smallest mosaic side, what the reduced form divides the sides by
 //   kReachY, kApronX              mosaic rows a full-size output row reads above and below it; staged columns each side of a tile
@@ -55,6 +58,7 @@ struct MosaicArgs {
     int dst_y0, x0, x1;     // the window of D that dst holds (the uint16 entry points: all of it)
     float divisor, factor;  // the float epilogue's
     int orientation;        // the oriented entry points': dst is then row 0 of O, and [y0, y1) x [x0, x1) the rectangle of D it takes
+    int clip;               // the blend entry points': mosaic::blend_pixel's level (read by the Blend instantiations only)
 };
 
 // How the finished pixels of the full size leave: as rows of D; as rows of O that are rows of D mirrored (bits 1 and 2 of the
@@ -164,7 +168,7 @@ __device__ __forceinline__ void store_segment(float* seg, const float* s, int n,
 // The tile grid is anchored to the frame's columns (tile origins at multiples of 64, so that load_pair's x stays even whatever the
 // window's col0) and to the call's first row; lanes outside the window's columns compute nothing and store nothing.  Every phase is
 // taken from frame coordinates, never from the tile's.
-template <typename Pattern, bool F32, int Cls = kUpright>
+template <typename Pattern, bool F32, int Cls = kUpright, bool Blend = false>
 __global__ __launch_bounds__(256) void mosaic_full_kernel(const MosaicArgs<typename Pattern::Params> a) {
     static_assert(Cls == kUpright || !F32, "the float epilogue is upright");
     using St = Staged<Pattern>;
@@ -223,6 +227,7 @@ __global__ __launch_bounds__(256) void mosaic_full_kernel(const MosaicArgs<typen
                 int rgb[3];
                 uint16_t out[3];
                 Pattern::pixel_rgb(p, S, A, a.H, a.W, y, x, rgb);
+                if constexpr (Blend) mosaic::blend_pixel(rgb, a.clip);
                 mosaic::colour(p.M, rgb, out);
                 uint16_t* o = s_out + tx * kTurnPitch + 3 * (flip_rows ? ye - 1 - y : y - ty0);
                 o[0] = out[0], o[1] = out[1], o[2] = out[2];
@@ -251,6 +256,7 @@ __global__ __launch_bounds__(256) void mosaic_full_kernel(const MosaicArgs<typen
                 int rgb[3];
                 uint16_t out[3];
                 Pattern::pixel_rgb(p, S, A, a.H, a.W, y, x, rgb);
+                if constexpr (Blend) mosaic::blend_pixel(rgb, a.clip);
                 mosaic::colour(p.M, rgb, out);
                 uint16_t* o = s_out[ty] + 3 * slot;
                 o[0] = out[0], o[1] = out[1], o[2] = out[2];
@@ -270,6 +276,7 @@ __global__ __launch_bounds__(256) void mosaic_full_kernel(const MosaicArgs<typen
                 int rgb[3];
                 uint16_t out[3];
                 Pattern::pixel_rgb(p, S, A, a.H, a.W, y, x, rgb);
+                if constexpr (Blend) mosaic::blend_pixel(rgb, a.clip);
                 mosaic::colour(p.M, rgb, out);
                 OutT<F32>* o = s_out[ty] + 3 * (x - xa);
                 o[0] = finish_sample<F32>(a, out[0]), o[1] = finish_sample<F32>(a, out[1]), o[2] = finish_sample<F32>(a, out[2]);
@@ -282,7 +289,7 @@ __global__ __launch_bounds__(256) void mosaic_full_kernel(const MosaicArgs<typen
 }
 
 // Oriented: the lane stores its pixel where orient::from_frame puts it in O (a quarter or a ninth of the samples: no transpose buffer).
-template <typename Pattern, bool F32, bool Oriented = false>
+template <typename Pattern, bool F32, bool Oriented = false, bool Blend = false>
 __global__ __launch_bounds__(256) void mosaic_reduced_kernel(const MosaicArgs<typename Pattern::Params> a) {
     __shared__ typename Pattern::Params s_p;  // (as above)
     if constexpr (Pattern::kParamsInLds) {
@@ -295,6 +302,7 @@ __global__ __launch_bounds__(256) void mosaic_reduced_kernel(const MosaicArgs<ty
     int rgb[3];
     uint16_t out[3];
     Pattern::reduced_rgb(a, p, y, x, rgb);
+    if constexpr (Blend) mosaic::blend_pixel(rgb, a.clip);
     mosaic::colour(p.M, rgb, out);
     OutT<F32>* d;
     if constexpr (Oriented) {
@@ -311,10 +319,10 @@ __global__ __launch_bounds__(256) void mosaic_reduced_kernel(const MosaicArgs<ty
 // An entry point: the checks, then one launch.  The window (row0, col0, rows, cols) of the demosaiced frame is what dst holds (none:
 // all of it); [y0, y1) are rows of the window.  `what` names the entry point in messages.  The oriented entry points (uint16, no
 // window) pass their orientation: [y0, y1) are then rows of O, dst is O, and the launch walks orient::rect_of's rectangle of D.
-template <typename Pattern, bool F32>
+template <typename Pattern, bool F32, bool Blend = false>
 int mosaic_rows(r2f_ctx* ctx, const char* what, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
                 const typename Pattern::Params* params, const int* window, float divisor, float factor, void* dst, int y0, int y1,
-                void* stream, int orientation = 0) {
+                void* stream, int orientation = 0, int clip = 0) {
     constexpr int kMaxSide = 1 << 17;  // (the reduced grid has a block per four rows; indices go through long long)
     constexpr int kMin = Pattern::kMinSide, kReduction = Pattern::kReduction, kReachY = Pattern::kReachY;
     if (!src_rows || !params || !dst || H < kMin || W < kMin || H > kMaxSide || W > kMaxSide || src_pitch < W || src_gy0 < 0 || src_nrows < 0)
@@ -327,6 +335,7 @@ int mosaic_rows(r2f_ctx* ctx, const char* what, const uint16_t* src_rows, int sr
         return fail(ctx, R2F_EINVAL, "%s: the params are those of another frame size (%s)", what, Pattern::kPlanner);
     if (!orient::valid(orientation) || (orientation && (F32 || window)))
         return fail(ctx, R2F_EINVAL, "%s: orientation %d is not one of 0 .. 7 (LibRaw's sizes.flip bits)", what, orientation);
+    if (Blend && (clip < 1 || clip > 65535)) return fail(ctx, R2F_EINVAL, "%s: clip %d is not inside [1, 65535]", what, clip);
     const int frame_rows = orient::rows(orientation, p.out_h, p.out_w);  // (an oriented call has no window: dst is all of O)
     const int row0 = window ? window[0] : 0, col0 = window ? window[1] : 0, rows = window ? window[2] : frame_rows,
               cols = window ? window[3] : p.out_w;
@@ -346,7 +355,7 @@ int mosaic_rows(r2f_ctx* ctx, const char* what, const uint16_t* src_rows, int sr
                     src_gy0, (long long)src_gy0 + src_nrows);
     const int wide = ((reinterpret_cast<uintptr_t>(src_rows) & 3u) == 0 && src_pitch % 2 == 0) ? 1 : 0;
     const MosaicArgs<typename Pattern::Params> a{
-        src_rows, src_gy0, (long long)src_pitch, H, W, p, dst, d.y0, d.y1, wide, orientation ? 0 : row0, d.x0, d.x1, divisor, factor, orientation};
+        src_rows, src_gy0, (long long)src_pitch, H, W, p, dst, d.y0, d.y1, wide, orientation ? 0 : row0, d.x0, d.x1, divisor, factor, orientation, clip};
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 reduced_grid((d.x1 - d.x0 + 63) / 64, (d.y1 - d.y0 + 3) / 4);
     // (the whole frame: ceil(W / 64) tiles from column 0)
@@ -354,19 +363,19 @@ int mosaic_rows(r2f_ctx* ctx, const char* what, const uint16_t* src_rows, int sr
     if constexpr (!F32) {
         if (orientation) {
             if (reduced)
-                launch_k(mosaic_reduced_kernel<Pattern, false, true>, reduced_grid, dim3(64, 4), 0, s, a);
+                launch_k(mosaic_reduced_kernel<Pattern, false, true, Blend>, reduced_grid, dim3(64, 4), 0, s, a);
             else if (orientation & orient::kSwap)
-                launch_k(mosaic_full_kernel<Pattern, false, kTurned>, full_grid, dim3(64, 4), 0, s, a);
+                launch_k(mosaic_full_kernel<Pattern, false, kTurned, Blend>, full_grid, dim3(64, 4), 0, s, a);
             else
-                launch_k(mosaic_full_kernel<Pattern, false, kMirrored>, full_grid, dim3(64, 4), 0, s, a);
+                launch_k(mosaic_full_kernel<Pattern, false, kMirrored, Blend>, full_grid, dim3(64, 4), 0, s, a);
             R2F_HIP(ctx, take_launch_status());
             return R2F_OK;
         }
     }
     if (reduced)
-        launch_k(mosaic_reduced_kernel<Pattern, F32>, reduced_grid, dim3(64, 4), 0, s, a);
+        launch_k(mosaic_reduced_kernel<Pattern, F32, false, Blend>, reduced_grid, dim3(64, 4), 0, s, a);
     else
-        launch_k(mosaic_full_kernel<Pattern, F32>, full_grid, dim3(64, 4), 0, s, a);
+        launch_k(mosaic_full_kernel<Pattern, F32, kUpright, Blend>, full_grid, dim3(64, 4), 0, s, a);
     R2F_HIP(ctx, take_launch_status());
     return R2F_OK;
 }

@@ -22,6 +22,7 @@ the uint16 (H, W) Bayer mosaic itself; or the path of a `.npy` file holding one 
 
 from __future__ import annotations
 
+import functools
 import inspect
 import math
 import random
@@ -32,7 +33,7 @@ import numpy as np
 
 from . import _lib, filmstock, geometry, payload as phase1, stencils, tiff
 from .bands import StreamedFrame, band_source, plan_bands, stage_schedule
-from .context import LOG_EPS, LUT3D_SCALE, MOSAIC_KINDS, HipContext
+from .context import LOG_EPS, LUT3D_SCALE, MOSAIC_BLEND_KINDS, MOSAIC_KINDS, HipContext
 from .jpeg_options import _check_jpeg_image, checked_options
 from .exports import JpegExport, TiffExport
 from .payload import DEVICE_EXPOSURE, host_stream_gate, stream_rejection
@@ -357,7 +358,9 @@ class HipProcessor:
         so every crop-derived number is that of the oriented frame, as upstream's is; the `demosaic` step then carries
         `orientation` (an upright payload has no such key), and the payload takes the one-piece path.
         A deferred profile (its multipliers are a raw2film_amd.raw.RawLevels): `params` are provisional, those of the nominal
-        scale, and the `demosaic` step carries the profile under `levels` (a numeric profile's step has no such key).  Phase 2
+        scale, and the `demosaic` step carries the profile under `levels` (a numeric profile's step has no such key).  A numeric
+        profile with highlight=("blend", clip) adds `clip` to the step (r2f_demosaic_blend_u16 / _f32 take the place of the plain
+        entry points; it streams where a plain numeric profile does); a deferred one's highlight mode is resolved with its scale.  Phase 2
         measures the uploaded mosaic's data maximum (r2f_mosaic_maximum), resolves the profile with it and plans the params the
         demosaic runs with; `last_raw_scale` then holds the numbers.  Such a payload takes the one-piece path."""
         on_device = exposure_on_device(exposure)
@@ -423,7 +426,8 @@ class HipProcessor:
             # `image_array` is a Bayer mosaic (ahead of all)
             **({"demosaic": {"params": demosaic_params, **crops.demosaic,
                              **({"orientation": raw_profile.orientation} if raw_profile.orientation else {}),
-                             **({"levels": raw_profile} if raw_profile.deferred else {})}}
+                             **({"levels": raw_profile} if raw_profile.deferred else {}),
+                             **({"clip": raw_profile.blend_clip} if raw_profile.blend_clip is not None else {})}}
                if demosaic_params is not None else {}),
         }
 
@@ -1125,9 +1129,8 @@ class HipProcessor:
         demosaic_step = cpu_payload.get("demosaic")
         if demosaic_step:  # a mosaic: LibRaw's share of raw_to_linear on the device -> the uint16 frame of the lines below
             params = demosaic_step["params"]
-            demosaic = getattr(self.ctx, MOSAIC_KINDS[type(params)][0])
             image = image.contiguous()
-            deferred = demosaic_step.get("levels")
+            deferred, clip = demosaic_step.get("levels"), demosaic_step.get("clip")
             if deferred is not None:
                 # the scale is the frame's own: the whole uploaded mosaic's data maximum (one read of it, 4 bytes back, the one
                 # synchronisation of this path), LibRaw's rule on it, and the params planned again with the resolved numbers
@@ -1135,7 +1138,11 @@ class HipProcessor:
                 resolved, scale = deferred.resolve_scale(d)
                 self.last_raw_scale = {"data_maximum": d, "maximum_used": int(scale.maximum_used), "adjusted": bool(scale.adjusted)}
                 reduced = bool(params.reduced if phase1.is_xtrans(params) else params.half_size)
-                params = resolved.plan(int(image.shape[0]), int(image.shape[1]), reduced)
+                params, clip = resolved.plan(int(image.shape[0]), int(image.shape[1]), reduced), resolved.blend_clip
+            if clip is None:
+                demosaic = getattr(self.ctx, MOSAIC_KINDS[type(params)][0])
+            else:  # highlight mode 2: the blend entry point of the same demosaic
+                demosaic = functools.partial(getattr(self.ctx, MOSAIC_BLEND_KINDS[type(params)]), clip=clip)
             image = cut_and_turn(demosaic(image, params, orientation=demosaic_step.get("orientation", 0)),
                                  demosaic_step["window"], demosaic_step["rotate_times"], dims=(0, 1))
         if image.dtype in (torch.int16, torch.uint16):  # a decoded 16-bit frame: raw_conversion.py:50-52 on the device

@@ -11,6 +11,11 @@ XTransProfile is the same record for a 6 x 6 array (r2f_xtrans_plan, r2f_demosai
 RawLevels states the sensor's levels instead of finished multipliers: a profile that holds one as its `multipliers` is DEFERRED --
 its scale follows LibRaw's adjust_maximum rule from the frame's data maximum, which the device measures (r2f_mosaic_maximum,
 r2f_raw_scale_plan; include/r2f.h has the definition, and its parity with LibRaw's bytes is unpinned like the demosaic's).
+
+`highlight` is LibRaw's highlight mode (rawpy's highlight_mode=): "clip" (0, the default), and on a deferred profile "unclip" (1)
+and "blend" (2), which normalise by the largest white-balance factor (r2f_raw_scale_plan_highlight); a profile resolved from
+"blend" carries ("blend", clip), the level above which the demosaic blends a pixel's chroma (r2f_demosaic_blend_u16).  The rebuild
+modes 3 .. 9 are not built.
 """
 
 from __future__ import annotations
@@ -18,10 +23,11 @@ from __future__ import annotations
 import ctypes as C
 import math
 import numbers
-from dataclasses import dataclass, replace
+from dataclasses import dataclass, field, replace
 
 from . import _lib
 
+_HIGHLIGHT_MODES = {"clip": _lib.HIGHLIGHT_CLIP, "unclip": _lib.HIGHLIGHT_UNCLIP, "blend": _lib.HIGHLIGHT_BLEND}
 _PATTERNS = {"RGGB": _lib.CFA_RGGB, "BGGR": _lib.CFA_BGGR, "GRBG": _lib.CFA_GRBG, "GBRG": _lib.CFA_GBRG}
 
 
@@ -93,6 +99,25 @@ class RawLevels:
             raise ValueError(f"r2f_raw_scale_plan refused {self!r} with black levels {tuple(black)!r} and a data maximum of {d}")
         return out
 
+    def scale_highlight(self, black, data_maximum: int = 0, highlight: str = "clip") -> tuple:
+        """r2f_raw_scale_plan_highlight: `scale` with LibRaw's highlight mode "clip", "unclip" or "blend" -> (the r2f_raw_scale, the
+        r2f_highlight: mode and, for "blend", the clip level).  "clip" is `scale` itself.  ValueError for what `scale` refuses, and
+        for a "blend" whose clip level would fall below 1."""
+        if highlight not in _HIGHLIGHT_MODES:
+            raise ValueError(f"the highlight mode must be one of {sorted(_HIGHLIGHT_MODES)}, got {highlight!r}")
+        if highlight == "clip":
+            return self.scale(black, data_maximum), _lib.Highlight()
+        d = data_maximum
+        if isinstance(d, bool) or not isinstance(d, numbers.Integral) or not 0 <= d <= 65535:
+            raise ValueError(f"the data maximum must be an integer in [0, 65535], got {data_maximum!r}")
+        out, hl = _lib.RawScale(), _lib.Highlight()
+        table = (C.c_double * len(black))(*black)
+        if _lib.load().r2f_raw_scale_plan_highlight(C.byref(self.to_c()), table, len(black), int(d), _HIGHLIGHT_MODES[highlight],
+                                                    C.byref(out), C.byref(hl)) != _lib.OK:
+            raise ValueError(f"r2f_raw_scale_plan_highlight refused {self!r} with black levels {tuple(black)!r}, a data maximum of {d} "
+                             f"and highlight = {highlight!r}")
+        return out, hl
+
 
 class _MosaicProfile:
     """What the two profiles share: the normalisation of black, multipliers, matrix and orientation, `oriented_shape()` and `plan()`.  A profile class states
@@ -121,6 +146,35 @@ class _MosaicProfile:
         if isinstance(o, bool) or not isinstance(o, numbers.Integral) or not 0 <= o <= 7:
             raise ValueError(f"{who}.orientation must be an integer 0 .. 7 (LibRaw's sizes.flip bits), got {o!r}")
         object.__setattr__(self, "orientation", int(o))
+        object.__setattr__(self, "highlight", self._highlight(who, isinstance(mul, RawLevels)))
+
+    def _highlight(self, who, deferred):
+        """The `highlight` field, checked: a mode's name on a deferred profile; "clip" or ("blend", clip) on a numeric one."""
+        h = self.highlight
+        if isinstance(h, list):
+            h = tuple(h)
+        rebuild = isinstance(h, numbers.Integral) and not isinstance(h, bool) and 3 <= h <= 9
+        if rebuild or h == "rebuild" or (isinstance(h, tuple) and h[:1] == ("rebuild",)):
+            raise ValueError(f"{who}.highlight = {self.highlight!r}: LibRaw's rebuild modes (3 .. 9) are not built; "
+                             "\"clip\", \"unclip\" and \"blend\" are")
+        if deferred:
+            if not isinstance(h, str) or h not in _HIGHLIGHT_MODES:
+                raise ValueError(f"{who}.highlight of a profile with RawLevels must be \"clip\", \"unclip\" or \"blend\", got {self.highlight!r}")
+            return h
+        if isinstance(h, str) and h in ("unclip", "blend"):
+            raise ValueError(f"{who}.highlight = {h!r} needs the sensor's levels: numeric multipliers already fix the normalisation; "
+                             "give a RawLevels as `multipliers` (or (\"blend\", clip) with the level a resolved profile carries)")
+        if isinstance(h, str) and h == "clip":
+            return h
+        if (isinstance(h, tuple) and len(h) == 2 and h[0] == "blend" and isinstance(h[1], numbers.Integral)
+                and not isinstance(h[1], bool) and 1 <= h[1] <= 65535):
+            return ("blend", int(h[1]))
+        raise ValueError(f"{who}.highlight must be \"clip\" or (\"blend\", clip) with clip an integer in [1, 65535], got {self.highlight!r}")
+
+    @property
+    def blend_clip(self):
+        """The clip level of a numeric ("blend", clip) profile, which the demosaic blends above (r2f_demosaic_blend_u16); else None."""
+        return self.highlight[1] if isinstance(self.highlight, tuple) else None
 
     def oriented_shape(self, H: int, W: int, half_size: bool = False) -> tuple:
         """(rows, cols) of the frame the demosaic of an H x W mosaic yields with this profile's orientation: the demosaiced frame's
@@ -136,7 +190,9 @@ class _MosaicProfile:
     def resolve(self, data_maximum: int):
         """This profile with numeric multipliers: r2f_raw_scale_plan of its levels, its black table and the frame's data maximum
         (HipContext.mosaic_maximum measures it; 0 is the nominal scale).  A numeric profile is returned as it is.  ValueError for
-        what the planner refuses, and for a scale outside (0, 1024]."""
+        what the planner refuses, and for a scale outside (0, 1024].  The highlight mode goes into the numbers
+        (r2f_raw_scale_plan_highlight): "unclip" resolves to a profile with highlight="clip" -- its multipliers are normalised by the
+        largest white-balance factor, and nothing else differs --, "blend" to one with ("blend", clip)."""
         return self.resolve_scale(data_maximum)[0]
 
     def resolve_scale(self, data_maximum: int) -> tuple:
@@ -144,15 +200,16 @@ class _MosaicProfile:
         (the profile itself, None) for a numeric profile."""
         if not self.deferred:
             return self, None
-        scale = self.multipliers.scale(self.black, data_maximum)
-        return replace(self, multipliers=tuple(scale.mul)), scale
+        scale, hl = self.multipliers.scale_highlight(self.black, data_maximum, self.highlight)
+        highlight = ("blend", int(hl.clip)) if hl.mode == _lib.HIGHLIGHT_BLEND else "clip"
+        return replace(self, multipliers=tuple(scale.mul), highlight=highlight), scale
 
     def _c_multipliers(self) -> tuple:
         """The multipliers `to_c` states, per site or colour as the profile keeps them: a deferred profile's are those of the
         NOMINAL scale (resolve(0)'s, unchecked: the planner refuses what is out of range)."""
         if not self.deferred:
             return self.multipliers
-        mul = tuple(self.multipliers.scale(self.black, 0).mul)
+        mul = tuple(self.multipliers.scale_highlight(self.black, 0, self.highlight)[0].mul)
         return self._spread(mul)
 
     def _spread(self, mul):  # (r, g, b) as the profile keeps its multipliers
@@ -183,11 +240,17 @@ class RawProfile(_MosaicProfile):
     orientation: 0 .. 7, how the sensor was held, as LibRaw's sizes.flip bits (4 swaps the axes, 2 mirrors rows, 1 mirrors
         columns: 0 upright, 3 180 degrees, 5 90 degrees counter-clockwise, 6 90 degrees clockwise).  The demosaic writes the frame
         that way round (r2f_demosaic_oriented_u16), and everything behind it -- crops, statistic, lens step, turns -- sees that
-        frame, as upstream's does.  (Not `flip`: process(flip=) is the aspect's.)"""
+        frame, as upstream's does.  (Not `flip`: process(flip=) is the aspect's.)
+    highlight: LibRaw's highlight mode (rawpy's highlight_mode=).  With a RawLevels: "clip" (0), "unclip" (1: normalised by the
+        largest white-balance factor, so nothing is cut below the sensor's saturation) or "blend" (2: unclip, and pixels with a
+        channel above the clip level take the chroma of their clipped version).  With numeric multipliers: "clip", or ("blend",
+        clip) as `resolve` of a "blend" profile yields it (`blend_clip`).  The rebuild modes 3 .. 9 are not built."""
     pattern: str = "RGGB"
     black: tuple | float = 0
     multipliers: tuple | RawLevels = (1.0, 1.0, 1.0)
     matrix: tuple = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
+    # keyword-only, and stated ahead of `orientation`: the positional order (..., matrix, orientation) and the last field stay as they were
+    highlight: str | tuple = field(default="clip", kw_only=True)
     orientation: int = 0
 
     reduction = 2  # what half_size=True divides a mosaic's sides by (no dataclass field: not part of equality, hash or repr)
@@ -229,11 +292,14 @@ class XTransProfile(_MosaicProfile):
         RawProfile's (a deferred profile).
     matrix: 3 x 3, rows are the output channels; |entries| <= 64.
     orientation: 0 .. 7, LibRaw's sizes.flip bits, as RawProfile's (r2f_demosaic_xtrans_oriented_u16).
+    highlight: LibRaw's highlight mode, as RawProfile's (r2f_demosaic_xtrans_blend_u16).
     half_size=True yields A THIRD of the mosaic's sides (the 3 x 3 cells of the array), not a half: `reduction`."""
     pattern: tuple | str = XTRANS
     black: tuple | float = 0
     multipliers: tuple | RawLevels = (1.0, 1.0, 1.0)
     matrix: tuple = ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
+    # keyword-only, and stated ahead of `orientation`: the positional order (..., matrix, orientation) and the last field stay as they were
+    highlight: str | tuple = field(default="clip", kw_only=True)
     orientation: int = 0
 
     reduction = 3
