@@ -870,6 +870,75 @@ R2F_API int r2f_mosaic_maximum(r2f_ctx* ctx, const uint16_t* src_rows, int src_g
 /* r2f_mosaic_maximum's widest load in samples and the rows a block walks per step (test shapes are derived from them). */
 enum { R2F_MOSAIC_MAX_VEC = 8, R2F_MOSAIC_MAX_ROWS = 4 };
 
+/* The wavelet denoise of a Bayer mosaic on the device: rawpy's noise_thr=, dcraw's -n, the first half of wavelet_denoise() inside
+ * LibRaw's scale_colors.  It runs where LibRaw runs it: behind the black subtraction and adjust_maximum, ahead of the scale, so it
+ * sits in front of either Bayer demosaic above.  Parity with LibRaw's bytes is UNPINNED like the rest of the demosaic: rawpy is on
+ * no machine this project sees.  The arithmetic follows dcraw / LibRaw's published wavelet_denoise and hat_transform; what the
+ * tests pin is THIS definition (tests/denoise_model.py restates it in NumPy).
+ * NOT built: the second half of dcraw's function, which pulls the two greens of a quad together; anything for X-Trans mosaics;
+ * streaming in row bands (the five levels reach 31 plane rows either side, and every level is a whole-frame pass).
+ *
+ * Inputs.  The mosaic, uint16 (H, W), H and W even and at least 64; black[4] (int32, each in [0, 65535]) per site k = (y & 1) * 2 +
+ * (x & 1); a maximum M, an integer in [1, 65535] -- the white level less the black level the frame is scaled by, maximum_used of
+ * r2f_raw_scale --; a threshold T, a float in (0, 1e6].  The step knows nothing of colours: the four sites of the quad are four
+ * planes, whatever the pattern.  Every operation below is one correctly rounded fp32 operation; trunc is toward zero.
+ *   1. s is the largest integer >= 0 with (M << s) < 65536: 0 for M >= 32768, 15 for M = 1.
+ *   2. Plane k has n_r = H / 2 rows and n_c = W / 2 columns.  With (yy, xx) = (k >> 1, k & 1):
+ *        t[y, x] = max((int)raw[2 y + yy, 2 x + xx] - black[k], 0)
+ *        F[y, x] = fl(256 * sqrtf((float)(t << s)))            (the shift product is below 2^31 and exact as a float)
+ *   3. For lev = 0 .. 4 with c = 1 << lev; In = F at level 0, else L of the level before:
+ *        hat(b, i, n) = fl(fl(2 b[i] + b[m]) + b[p]),   m = i - c if i >= c, else c - i;   p = i + c if i + c < n, else 2 n - 2 - (i + c)
+ *        R[y, x] = 0.25 * hat(In[y, .], x, n_c);   L[y, x] = 0.25 * hat(R[., x], y, n_r)    (rows first, then columns; both
+ *          quarterings are exact)
+ *        theta = fl(T * noise[lev]),   noise = {0.8002f, 0.2735f, 0.1202f, 0.0585f, 0.0291f}
+ *        d = fl(In - L);   d' = fl(d + theta) if d < -theta;  fl(d - theta) if d > theta;  0 otherwise
+ *        D = d' at level 0, D = fl(D + d') afterwards
+ *   4. out = clamp(trunc(fl(fl(D + L)^2) / 65536), 0, 65535) with L that of level 4, written at the sample's own site.
+ * Side bound: n >= 32 keeps every m and p inside [0, n) at c = 16 (dcraw indexes outside the row below that size), which is why
+ * sides below 64 are refused rather than defined.
+ * Output and plug-in.  The output mosaic is black-free and in units of t << s: the demosaic that follows runs with black = 0 and
+ * every multiplier times 2^-s (exact); all else in the profile is unchanged, and a blend clip level, which lives behind the scale,
+ * does not move. */
+typedef struct r2f_denoise_params {
+    int32_t black[4];
+    int32_t shift;    /* s */
+    float threshold;  /* T */
+} r2f_denoise_params;
+/* The tile of one plane a workgroup of the denoise owns, in plane samples (test shapes are derived from them). */
+enum { R2F_DENOISE_TILE_W = 64, R2F_DENOISE_TILE_H = 32 };
+/* Host planner (raw2film_amd/csrc/r2f_denoise_plan.cpp; no GPU, no context): step 1 and the checks.  black: 4 levels as a profile
+ * states them (doubles, integral, in [0, 65535]).  R2F_EINVAL for a null pointer, a threshold outside (0, 1e6] or one that rounds to
+ * 0 as a float, a maximum outside [1, 65535], a black level outside its range (a NaN is outside every range), an odd side or a side
+ * below 64; a refusal leaves *out alone. */
+R2F_API int r2f_mosaic_denoise_plan(double threshold, int maximum, const double* black, int H, int W, r2f_denoise_params* out);
+/* The bytes of workspace r2f_mosaic_denoise needs for an H x W mosaic: 12 per sample (D and two L buffers as planar floats); 0 for
+ * sides the planner refuses.  No GPU, no context. */
+R2F_API size_t r2f_mosaic_denoise_workspace_bytes(int H, int W);
+/* Steps 2 to 4 of an H x W mosaic on the device.  src: uint16, rows src_pitch samples apart (>= W); dst: the same with dst_pitch;
+ * dst == src is allowed (the last launch alone writes dst, the first alone reads src).  workspace: device memory, 16-byte aligned,
+ * workspace_bytes >= r2f_mosaic_denoise_workspace_bytes(H, W), overlapping neither src nor dst.  Reads the H x W samples of src;
+ * writes the H x W samples of dst and bytes inside the stated workspace, and nothing else.  Refused before any launch: null
+ * pointers, sides the planner refuses, a pitch below W, a workspace that is too small, misaligned or overlaps a frame, and params
+ * the planner would not have produced (a black level outside [0, 65535], a shift outside [0, 15], a threshold outside (0, 1e6]).
+ * The alignment and pitch of src and dst only select between 32-bit and 16-bit accesses of the same samples.
+ * Five launches, one per level; row pass, column pass, threshold and accumulation are fused in each.  A workgroup stages its
+ * R2F_DENOISE_TILE_W x R2F_DENOISE_TILE_H tile of In with an apron of c samples on all four sides in LDS, runs the row pass over
+ * the tile's rows and apron rows into a second LDS array, then the column pass and the rest per output sample.  Reflection is taken
+ * in PLANE coordinates: the reflected sample of a border tile lies inside the tile's own clipped box.  Level 0 reads the uint16
+ * source itself (step 2 on the fly, apron included) and writes D and L; levels 1 to 3 read one L buffer, write the other and update
+ * D at their own samples; level 4 stores no L, finishes step 4 and writes the uint16 result.  No workgroup reads a plane another
+ * workgroup of the same launch writes.  At levels 0 and 4 a workgroup owns the same tile of all four planes, so mosaic rows enter
+ * and leave as contiguous segments; in between the planes are planar floats. */
+R2F_API int r2f_mosaic_denoise(r2f_ctx* ctx, const uint16_t* src, int64_t src_pitch, int H, int W, const r2f_denoise_params* params,
+                     uint16_t* dst, int64_t dst_pitch, void* workspace, size_t workspace_bytes, void* stream);
+/* Measurement aid (tools/denoise_probe.py): the launch of ONE level, 0 .. 4, of r2f_mosaic_denoise with that call's arguments, checks and
+ * buffers -- level 0 reads src, level 4 writes dst, every level reads and writes the workspace where the whole chain keeps D and L, so
+ * the five calls in order are the chain.  A level other than 0 on a workspace the levels before it have not filled computes on
+ * whatever the workspace holds; it reads and writes the same bytes either way.  R2F_EINVAL for a level outside 0 .. 4. */
+R2F_API int r2f_mosaic_denoise_level(r2f_ctx* ctx, int level, const uint16_t* src, int64_t src_pitch, int H, int W,
+                     const r2f_denoise_params* params, uint16_t* dst, int64_t dst_pitch, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 /* The hand-off from RAW decoding: the last two lines of raw_to_linear (raw_conversion.py:50-52) applied to LibRaw's 16-bit
  * output on the device, so that a decoded frame crosses PCIe as uint16 (6 bytes per pixel) instead of float32 (12 or 16):
  * dst = float(src) / divisor (65535, one correctly rounded fp32 division) * factor (the float32 of 2 ** calc_exposure(...),

@@ -48,6 +48,7 @@ class HipContext:
             raise R2FError(f"r2f_create(device={device}) failed with code {rc}")
         self._h = handle
         self._workspace = None
+        self._denoise_workspace = None  # mosaic_denoise's, apart from the render's: growing it moves no buffer a captured frame holds
 
     # ------------------------------------------------------------------ plumbing
     def close(self):
@@ -712,6 +713,35 @@ class HipContext:
         self._check(self._lib.r2f_mosaic_maximum(self._h, mosaic.data_ptr(), 0, H, int(mosaic.stride(0)), H, W, period,
                                                  (C.c_int32 * len(black))(*black), y0, y1, word.data_ptr(), self._stream()))
         return int(word.item()) if out is None else out
+
+    def mosaic_denoise(self, mosaic, params, out=None):
+        """The wavelet denoise of include/r2f.h (r2f_mosaic_denoise: rawpy's noise_thr=, ahead of the demosaic) of a uint16 (H, W)
+        CUDA Bayer mosaic with even sides of at least 64 samples (int16 tensors are read as the same bits; rows may be pitched) ->
+        the denoised mosaic, black-free and in units of t << shift, of the mosaic's dtype.
+        params: the r2f_denoise_params of raw2film_amd.raw.WaveletDenoise.plan.
+        out: a uint16 or int16 (H, W) CUDA tensor with contiguous samples along a row to write into (rows may be pitched); the
+        mosaic itself is allowed.  The 12 bytes per sample of workspace are a buffer the context keeps and reuses."""
+        torch = self._torch
+        if not isinstance(params, _lib.DenoiseParams):
+            raise ValueError(f"mosaic_denoise: params must be the r2f_denoise_params of WaveletDenoise.plan, got {type(params).__name__}")
+        H, W = self._mosaic_size(mosaic, "mosaic_denoise", 64)
+        if out is None:
+            out = torch.empty((H, W), dtype=mosaic.dtype, device=self.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype in (torch.uint16, torch.int16) and tuple(out.shape) == (H, W)
+                  and out.stride(1) == 1 and out.stride(0) >= W):
+            raise ValueError(f"mosaic_denoise: out must be a uint16 CUDA tensor of shape {(H, W)} with contiguous rows")
+        else:
+            self._same_device(out, "out")
+        nbytes = int(self._lib.r2f_mosaic_denoise_workspace_bytes(H, W))
+        if nbytes == 0:
+            raise ValueError(f"mosaic_denoise: a {H} x {W} mosaic; both sides must be even and at least 64")
+        ws = self._denoise_workspace
+        if ws is None or ws.numel() < nbytes:
+            self._denoise_workspace = None
+            ws = self._denoise_workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._check(self._lib.r2f_mosaic_denoise(self._h, mosaic.data_ptr(), int(mosaic.stride(0)), H, W, C.byref(params), out.data_ptr(),
+                                                 int(out.stride(0)), ws.data_ptr(), int(ws.numel()), self._stream()))
+        return out
 
     def decode_u16(self, image_u16, factor: float, divisor: float = 65535.0, out=None):
         """raw_to_linear's last two lines (raw_conversion.py:50-52) on the device: float32(u) / divisor * float32(factor) for a

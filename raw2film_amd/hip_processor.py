@@ -179,6 +179,9 @@ class HipProcessor:
         # process_preloaded / submit_preloaded / export call rendered -- a cached frame's is kept with the frame, which is not measured
         # again --; None when that frame's profile was numeric (streamed or in one piece), or it was no mosaic
         self.last_raw_scale = None
+        # what the wavelet denoise of that frame's mosaic ran with ({"threshold", "maximum", "shift"}: raw_denoise), kept with a cached
+        # frame like the scale; None when the call had no raw_denoise
+        self.last_raw_denoise = None
         self.last_stage_ms = None  # process()'s wall clock per stage with `profile_stages` on (bench.py's host_device_copies)
         self._load_stage_ms = None  # ... load_image_texture's share of it, until process() folds it in
         # the frame cache (load_image_texture): (frame, layout, payload geometry) kept on the device, a weak reference to its array, its load parameters
@@ -327,7 +330,8 @@ class HipProcessor:
     def extract_image_data_cpu(self, src, cam=None, lens=None, lens_correction=True, frame_width=36, frame_height=24,
                                rotation=0.0, zoom=1.0, rotate_times=0, flip=False, resolution=None, half_size=True,
                                cache=True, chroma_nr=0, max_scale=400.0, canvas_mode="No", canvas_scale=1.0,
-                               canvas_ratio=1.0, exposure=None, metadata=None, lens_profile=None, raw_profile=None, **kwargs):
+                               canvas_ratio=1.0, exposure=None, metadata=None, lens_profile=None, raw_profile=None, raw_denoise=None,
+                               **kwargs):
         """PHASE 1 of the two-phase batch API (gpu_processor.py:715-783): pure host work, touches
         no instance state.  Returns the same payload dict; `image_array` is (H, W, 4) float32 ((H, W, 3) with payload_alpha=False).
         exposure="device" (a uint16 frame): no pass over the frame here.  `image_array` is then the WHOLE decoded frame -- the caller's
@@ -362,7 +366,14 @@ class HipProcessor:
         profile with highlight=("blend", clip) adds `clip` to the step (r2f_demosaic_blend_u16 / _f32 take the place of the plain
         entry points; it streams where a plain numeric profile does); a deferred one's highlight mode is resolved with its scale.  Phase 2
         measures the uploaded mosaic's data maximum (r2f_mosaic_maximum), resolves the profile with it and plans the params the
-        demosaic runs with; `last_raw_scale` then holds the numbers.  Such a payload takes the one-piece path."""
+        demosaic runs with; `last_raw_scale` then holds the numbers.  Such a payload takes the one-piece path.
+        raw_denoise (a raw2film_amd.raw.WaveletDenoise; rawpy's noise_thr=): the Bayer mosaic is denoised on the device ahead of its
+        demosaic (include/r2f.h, r2f_mosaic_denoise; parity with LibRaw's bytes is unpinned, the pull of the two greens, X-Trans
+        mosaics and streaming are not built).  The `demosaic` step carries the record under `denoise` (a step without one has no such
+        key).  Phase 2 measures and resolves a deferred profile on the UNdenoised mosaic first, denoises with the record's maximum
+        (None: the resolved scale's `maximum_used`), then demosaics with black 0 and the multipliers times 2^-shift;
+        `last_raw_denoise` holds {"threshold", "maximum", "shift"}.  ValueError without a raw_profile, with an XTransProfile, with
+        maximum=None on a numeric profile, and for a mosaic with an odd side or a side below 64.  The one-piece path."""
         on_device = exposure_on_device(exposure)
         phase1.check_profiles(raw_profile, lens_profile, lens_correction, cam, lens)
         # _internal (load_image_texture: the payload never leaves this object): no alpha plane, and the clamp of
@@ -371,6 +382,7 @@ class HipProcessor:
         image = phase1.load_decoded(src, clip=not internal, mosaic=raw_profile is not None)
         rows, cols, is_u16 = image.shape[0], image.shape[1], image.dtype == np.uint16
         demosaic_params = lens_params = lens_projection = lens_tca = None
+        phase1.check_denoise(raw_denoise, raw_profile, rows, cols)
         if raw_profile is not None:  # the crops are those of the demosaiced frame, which is uint16
             demosaic_params = raw_profile.plan(rows, cols, half_size)
             rows, cols = raw_profile.oriented_shape(rows, cols, half_size)  # (the params' out_h, out_w, the way round the sensor was held)
@@ -427,6 +439,7 @@ class HipProcessor:
             **({"demosaic": {"params": demosaic_params, **crops.demosaic,
                              **({"orientation": raw_profile.orientation} if raw_profile.orientation else {}),
                              **({"levels": raw_profile} if raw_profile.deferred else {}),
+                             **({"denoise": raw_denoise, "profile": raw_profile} if raw_denoise is not None else {}),
                              **({"clip": raw_profile.blend_clip} if raw_profile.blend_clip is not None else {})}}
                if demosaic_params is not None else {}),
         }
@@ -442,7 +455,7 @@ class HipProcessor:
                 sharpness=True, sharpening_strength=0.0, sharpening_sigma=1.0, chroma_nr=0, grain=2,
                 highlight_burn=0.0, burn_scale=50.0, half_size=True, cache=True, color_masking=None, max_scale=400.0,
                 seed=None, exposure=None, metadata=None, src_version=None, output_bits=8, lens_profile=None, raw_profile=None,
-                **_):
+                raw_denoise=None, **_):
         """Load (decoded) frame and render it: np.uint8 (H, W, 3), like cpu_processor.py:414 -- including the CPU processor's
         last step, resolution_scaling of the finished (canvas-framed) frame to the requested resolution (cpu_processor.py:411-412).
         With `dst_texture` (a uint8 (h, w, 4) CUDA tensor standing in for the preview widget's wgpu texture) the call behaves
@@ -474,11 +487,14 @@ class HipProcessor:
         held before anything else sees it (crops, exposure statistic, lens step, rotate_times); such a mosaic is demosaiced whole.
         A profile whose multipliers are a raw2film_amd.raw.RawLevels is deferred: the uploaded mosaic's data maximum is measured on
         the device (r2f_mosaic_maximum) and the profile resolved with it ahead of the demosaic -- LibRaw's adjust_maximum rule,
-        parity unpinned; `last_raw_scale` holds the numbers, a cached frame keeps them.  Such a mosaic is demosaiced whole too."""
+        parity unpinned; `last_raw_scale` holds the numbers, a cached frame keeps them.  Such a mosaic is demosaiced whole too.
+        raw_denoise (raw2film_amd.raw.WaveletDenoise; rawpy's noise_thr=): the Bayer mosaic is denoised on the device ahead of the
+        demosaic (extract_image_data_cpu; r2f_mosaic_denoise), in one piece; `last_raw_denoise` holds the threshold, the maximum
+        and the shift it ran with, and a cached frame keeps them."""
         settings = dict(locals())  # every keyword of the signature (the unknown ones in `_` aside), named nowhere else
         exposure_on_device(exposure)  # (any string but "device" raises before any work starts)
         settings["output_bits"] = check_output_bits(output_bits, dst_texture)
-        self.exposure_rejected = self.last_raw_scale = None
+        self.exposure_rejected = self.last_raw_scale = self.last_raw_denoise = None
         for k in _PROCESS_POSITIONAL:
             del settings[k]
         # load_image_texture's share; prepare() and the render take what they need of all of them and swallow the rest
@@ -509,6 +525,7 @@ class HipProcessor:
             self.load_image_texture(src, **load)
         image, layout, payload = self._texture
         self.last_raw_scale = payload.get("raw_scale")  # (the frame's own: a cached frame was not measured again)
+        self.last_raw_denoise = payload.get("raw_denoise")
         if prof:
             self._torch.cuda.synchronize(self.device)
             t_loaded = time.perf_counter()
@@ -529,7 +546,7 @@ class HipProcessor:
     def load_image_texture(self, src, cam=None, lens=None, lens_correction=True, frame_width=36, frame_height=24, rotation=0.0,
                            zoom=1.0, rotate_times=0, flip=False, resolution=None, half_size=True, cache=True, chroma_nr=0,
                            max_scale=400.0, canvas_mode="No", canvas_scale=1.0, canvas_ratio=1.0, exposure=None, metadata=None,
-                           src_version=None, lens_profile=None, raw_profile=None):
+                           src_version=None, lens_profile=None, raw_profile=None, raw_denoise=None):
         """GpuProcessor.load_image_texture (gpu_processor.py:655-719): prepare and upload the frame unless the load parameters
         are those of the frame that is already on the device.  A path compares by value like upstream's `src`.  An array
         compares by identity AND by a fingerprint of its content (shape, dtype, address, a checksum of up to 32 evenly spaced
@@ -601,11 +618,12 @@ class HipProcessor:
     def prepare_gpu_textures(self, cpu_payload):
         """PHASE 2's stateful half (gpu_processor.py:785-790): upload the payload's frame and run the device pre-path on it
         (uint16 conversion, free rotation, chroma NR, preview scaling); the result is the frame the pipeline reads."""
-        self.last_raw_scale = None
+        self.last_raw_scale = self.last_raw_denoise = None
         image, layout = self._upload_payload(cpu_payload)
         # (what is kept next to the device frame is the payload's geometry, not its host frame: the processor must not keep a
         # 1.2 GB decode buffer alive; and the scale a deferred profile resolved to, which belongs to this frame: `raw_scale`)
-        self._texture = (image, layout, {**{k: v for k, v in cpu_payload.items() if k != "image_array"}, "raw_scale": self.last_raw_scale})
+        self._texture = (image, layout, {**{k: v for k, v in cpu_payload.items() if k != "image_array"}, "raw_scale": self.last_raw_scale,
+                                         "raw_denoise": self.last_raw_denoise})
         self.image_param_dict = None  # (a payload from outside: no load parameters to compare the next process() with)
         self._texture_src = None
 
@@ -653,7 +671,7 @@ class HipProcessor:
         "cpu" -- like CpuProcessor.process (cpu_processor.py:411-412), the finished frame, canvas included, is scaled to the
         requested resolution (INTER_AREA down, LANCZOS4 up).  dst_texture / histogram_texture, output_bits: see process()."""
         check_output_bits(settings.get("output_bits", 8), dst_texture)
-        self.exposure_rejected = self.last_raw_scale = None
+        self.exposure_rejected = self.last_raw_scale = self.last_raw_denoise = None
         if dst_texture is None and histogram_texture is None and self.stream_bands > 1:
             res = self._stream_payload(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, **settings)
             if res is not None:  # a large frame without a device pre-path: through the pipeline in row bands while it arrives
@@ -739,7 +757,7 @@ class HipProcessor:
         textures, and with stream=True the format's reasons, the processor's `stream_bands`, the payload's.  Then the row-band
         path into fmt.sink where nothing refused it, else the one-piece render into fmt.whole."""
         what = f"process_{fmt.name}" if payload is None else f"process_preloaded_{fmt.name}"
-        self.exposure_rejected = self.stream_rejected = self.last_raw_scale = None
+        self.exposure_rejected = self.stream_rejected = self.last_raw_scale = self.last_raw_denoise = None
         self._refuse_textures(what, settings, " (use process() for the preview)" if payload is None else "")
         early = next((why for why in fmt.early if why), None) if stream else None
         if payload is None:
@@ -773,7 +791,7 @@ class HipProcessor:
                                                                           getattr(profile, "reduction", 2),
                                                                           getattr(profile, "orientation", 0)) if mosaic else None,
                                 xtrans=isinstance(profile, phase1.XTransProfile), orientation=getattr(profile, "orientation", 0),
-                                levels=bool(getattr(profile, "deferred", False)))
+                                levels=bool(getattr(profile, "deferred", False)), denoise=settings.get("raw_denoise") is not None)
 
     @staticmethod
     def _refuse_textures(what, settings, hint=""):
@@ -1070,7 +1088,7 @@ class HipProcessor:
         reference's queue.write_texture / read_texture pair serialises."""
         check_output_bits(settings.get("output_bits", 8))
         torch = self._torch
-        self.exposure_rejected = self.last_raw_scale = None
+        self.exposure_rejected = self.last_raw_scale = self.last_raw_denoise = None
         src = cpu_payload.get("image_array")
         if self.stream_bands > 1 and not (isinstance(src, torch.Tensor) and (src.is_cuda or src.is_pinned())):
             # a large frame in ordinary (pageable) host memory: its copy blocks this thread, so nothing of the next frame's host work
@@ -1139,6 +1157,17 @@ class HipProcessor:
                 self.last_raw_scale = {"data_maximum": d, "maximum_used": int(scale.maximum_used), "adjusted": bool(scale.adjusted)}
                 reduced = bool(params.reduced if phase1.is_xtrans(params) else params.half_size)
                 params, clip = resolved.plan(int(image.shape[0]), int(image.shape[1]), reduced), resolved.blend_clip
+            denoise = demosaic_step.get("denoise")
+            if denoise is not None:
+                # behind the measurement and the resolve, which see the UNdenoised mosaic as LibRaw's adjust_maximum does; the
+                # denoised mosaic is black-free and in units of t << shift, and the demosaic is planned again for that
+                H, W = int(image.shape[0]), int(image.shape[1])
+                profile = resolved if deferred is not None else demosaic_step["profile"]
+                maximum = denoise.maximum if denoise.maximum is not None else int(scale.maximum_used)
+                dn = denoise.plan(profile.black, H, W, maximum)
+                self.last_raw_denoise = {"threshold": denoise.threshold, "maximum": int(maximum), "shift": int(dn.shift)}
+                image = self.ctx.mosaic_denoise(image, dn)
+                params = denoise.shifted(profile, dn.shift).plan(H, W, bool(params.half_size))
             if clip is None:
                 demosaic = getattr(self.ctx, MOSAIC_KINDS[type(params)][0])
             else:  # highlight mode 2: the blend entry point of the same demosaic

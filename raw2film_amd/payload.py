@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib, geometry
 from .lens import LensProfile
-from .raw import RawProfile, XTransProfile
+from .raw import RawProfile, WaveletDenoise, XTransProfile
 
 _DEMOSAIC_REJECTED = "the demosaic step (raw_profile): "  # every refusal of a mosaic begins with it, then says why
 _LENS_REJECTED = "the lens step (lens_profile): its gather reads the whole frame, which a row band does not hold"
@@ -33,15 +33,18 @@ DEVICE_EXPOSURE = "device"  # exposure="device": the auto exposure of a uint16 f
 
 _LEVELS_REJECTED = _DEMOSAIC_REJECTED + ("its multipliers are a RawLevels: the scale follows the mosaic's data maximum, which is known "
                                          "only after the last mosaic row has arrived")
+_DENOISE_REJECTED = _DEMOSAIC_REJECTED + ("raw_denoise: the wavelet denoise ahead of it is five whole-frame passes that reach 31 plane rows "
+                                          "either side; a row band does not hold them")
 
 
-def mosaic_rejection(stops, rotate_times, lens, samples, xtrans=False, orientation=0, *, levels=False):
+def mosaic_rejection(stops, rotate_times, lens, samples, xtrans=False, orientation=0, *, levels=False, denoise=False):
     """Why a mosaic is demosaiced whole instead of band by band (r2f_demosaic_f32), or None.  stops: the exposure is given in
     stops; samples: rows x cols x 3 of the window of the demosaiced frame that the pipeline takes, or None when nobody cut one;
     xtrans: the mosaic is an X-Trans one (r2f_demosaic_xtrans_u16 has the row-range contract, the band loop does not use it yet);
     orientation: the profile's (the fused demosaic-to-float of the band loop is upright; a turned band reads every mosaic row);
     levels: the profile is deferred (its multipliers are a RawLevels: r2f_mosaic_maximum of the whole mosaic comes first) -- the
-    last reason asked for."""
+    last reason asked for but one; denoise: the call denoises the mosaic (raw_denoise: r2f_mosaic_denoise of the whole mosaic comes
+    first) -- the last."""
     if orientation:
         return _DEMOSAIC_REJECTED + (f"orientation = {orientation!r}: an oriented mosaic is demosaiced in one piece "
                                      "(r2f_demosaic_oriented_u16), the band loop's demosaic is upright")
@@ -60,6 +63,8 @@ def mosaic_rejection(stops, rotate_times, lens, samples, xtrans=False, orientati
         return _DEMOSAIC_REJECTED + f"its window of the demosaiced frame has {samples} samples, below 16.7 M"
     if levels:
         return _LEVELS_REJECTED
+    if denoise:
+        return _DENOISE_REJECTED
     return None
 
 
@@ -99,7 +104,8 @@ def stream_rejection(payload, shape, dtype, on_device, final_scaling="cpu", canv
         window = step.get("window")
         why = mosaic_rejection(isinstance(payload.get("u16_factor"), float), step.get("rotate_times") or 0, payload.get("lens"),
                                None if window is None else int(window[2]) * int(window[3]) * 3, is_xtrans(step.get("params")),
-                               step.get("orientation", 0), levels=step.get("levels") is not None)
+                               step.get("orientation", 0), levels=step.get("levels") is not None,
+                               denoise=step.get("denoise") is not None)
         if why is not None:
             return why
     if payload.get("lens"):
@@ -124,13 +130,14 @@ def is_xtrans(params) -> bool:
 
 
 def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="No", highlight_burn=0.0, lens=False, demosaic=False, *,
-                     stops=False, rotate_times=0, frame_samples=None, xtrans=False, orientation=0, levels=False):
+                     stops=False, rotate_times=0, frame_samples=None, xtrans=False, orientation=0, levels=False, denoise=False):
     """Why process(src, cache=False) renders a frame in one piece before it extracts its payload (stream_rejection and plan_bands
     come after that), or None.  lens: the call corrects the lens (lens_correction with a lens_profile); demosaic: its source is a
     mosaic (raw_profile), for which stops says that the exposure is given in stops, rotate_times is the call's, frame_samples the
     samples of the window of the demosaiced frame that the pipeline takes (mosaic_frame_samples), xtrans that the profile is an
     XTransProfile (which does not stream yet), orientation the profile's (not 0: the one-piece path), and levels that the profile
-    is deferred (RawLevels: the one-piece path, the last reason asked for)."""
+    is deferred (RawLevels: the one-piece path, the last reason asked for but one); denoise: the call has a raw_denoise (the
+    one-piece path, the last reason asked for)."""
     if stream_bands <= 1:
         return f"stream_bands = {stream_bands}"
     if demosaic:
@@ -148,6 +155,8 @@ def host_stream_gate(src, stream_bands, rotation=0.0, chroma_nr=0, canvas_mode="
                 f"canvas_mode = {canvas_mode!r}, highlight_burn = {highlight_burn!r}")
     if demosaic and levels:
         return _LEVELS_REJECTED
+    if demosaic and denoise:
+        return _DENOISE_REJECTED
     return None
 
 
@@ -178,6 +187,24 @@ def check_profiles(raw_profile, lens_profile, lens_correction, cam, lens):
         # not part of the accelerated path, and rendering an uncorrected frame in its place would be a silent difference
         raise NotImplementedError("lens correction (lensfunpy, effects.py:22-43) is outside the accelerated path: "
                                   "pass lens_correction=False or no cam / lens (the calibration's numbers go in lens_profile)")
+
+
+def check_denoise(raw_denoise, raw_profile, rows, cols):
+    """The caller's raw_denoise is a WaveletDenoise that this profile and this rows x cols mosaic can run (None passes)."""
+    if raw_denoise is None:
+        return
+    if not isinstance(raw_denoise, WaveletDenoise):
+        raise ValueError(f"raw_denoise must be a raw2film_amd.raw.WaveletDenoise, got {type(raw_denoise).__name__}")
+    if raw_profile is None:
+        raise ValueError("raw_denoise needs a raw_profile: the wavelet denoise runs on a Bayer mosaic, ahead of its demosaic")
+    if isinstance(raw_profile, XTransProfile):
+        raise ValueError("raw_denoise with an XTransProfile: the wavelet denoise is not built for X-Trans mosaics")
+    if raw_denoise.maximum is None and not raw_profile.deferred:
+        raise ValueError("raw_denoise has maximum=None and the raw_profile's multipliers are numbers: no scale is resolved whose "
+                         "maximum it could take; give WaveletDenoise(threshold, maximum) or a RawLevels as the profile's multipliers")
+    if rows % 2 or cols % 2 or rows < 64 or cols < 64:
+        raise ValueError(f"raw_denoise on a {rows} x {cols} mosaic: both sides must be even and at least 64 (the five levels reflect "
+                         "inside a plane of at least 32 samples a side)")
 
 
 def load_decoded(src, clip=True, mosaic=False):

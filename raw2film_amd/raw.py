@@ -16,6 +16,9 @@ r2f_raw_scale_plan; include/r2f.h has the definition, and its parity with LibRaw
 and "blend" (2), which normalise by the largest white-balance factor (r2f_raw_scale_plan_highlight); a profile resolved from
 "blend" carries ("blend", clip), the level above which the demosaic blends a pixel's chroma (r2f_demosaic_blend_u16).  The rebuild
 modes 3 .. 9 are not built.
+
+WaveletDenoise is no part of a profile: it is the record of process(raw_denoise=), LibRaw's wavelet denoise of the Bayer mosaic ahead
+of its demosaic (rawpy's noise_thr=; r2f_mosaic_denoise_plan, r2f_mosaic_denoise).
 """
 
 from __future__ import annotations
@@ -117,6 +120,58 @@ class RawLevels:
             raise ValueError(f"r2f_raw_scale_plan_highlight refused {self!r} with black levels {tuple(black)!r}, a data maximum of {d} "
                              f"and highlight = {highlight!r}")
         return out, hl
+
+
+@dataclass(frozen=True)
+class WaveletDenoise:
+    """The wavelet denoise of a Bayer mosaic ahead of its demosaic (process(raw_denoise=); rawpy's noise_thr=, dcraw's -n): a frozen,
+    hashable record (part of the image cache key).  include/r2f.h has the definition (r2f_mosaic_denoise); parity with LibRaw's
+    bytes is unpinned.  Not built: the pull of a quad's two greens toward each other (the second half of dcraw's function),
+    anything for X-Trans mosaics, streaming in row bands.
+
+    threshold: rawpy's noise_thr, a number in (0, 1e6].
+    maximum: the white level less the black level the frame is scaled by, an integer in [1, 65535]; None takes the resolved
+        scale's `maximum_used` of a profile with RawLevels (a numeric profile needs the number)."""
+    threshold: float
+    maximum: int | None = None
+
+    def __post_init__(self):
+        t = self.threshold
+        if isinstance(t, bool) or not isinstance(t, numbers.Real) or not 0 < t <= 1e6:  # (a NaN fails the comparison)
+            raise ValueError(f"WaveletDenoise.threshold must be a number in (0, 1e6], got {t!r}")
+        object.__setattr__(self, "threshold", float(t))
+        if self.maximum is not None:
+            object.__setattr__(self, "maximum", self._maximum(self.maximum))
+
+    @staticmethod
+    def _maximum(m) -> int:
+        if isinstance(m, bool) or not isinstance(m, numbers.Integral) or not 1 <= m <= 65535:
+            raise ValueError(f"WaveletDenoise.maximum must be an integer in [1, 65535], got {m!r}")
+        return int(m)
+
+    def plan(self, black, H: int, W: int, maximum=None) -> _lib.DenoiseParams:
+        """The r2f_denoise_params of an H x W mosaic (no GPU: r2f_mosaic_denoise_plan).  black: the four levels per site of the
+        quad; maximum: in place of the record's own (one of them is required).  ValueError for what the planner refuses (an odd
+        side or a side below 64, a black level outside [0, 65535], a threshold that rounds to 0 as a float)."""
+        m = self._maximum(self.maximum if maximum is None else maximum) if (maximum is not None or self.maximum is not None) else None
+        if m is None:
+            raise ValueError(f"{self!r} has no maximum and none was given: a numeric profile needs WaveletDenoise(threshold, maximum)")
+        black = _floats("black", black, (4,), "WaveletDenoise.plan")
+        out = _lib.DenoiseParams()
+        if _lib.load().r2f_mosaic_denoise_plan(self.threshold, m, (C.c_double * 4)(*black), int(H), int(W), C.byref(out)) != _lib.OK:
+            raise ValueError(f"r2f_mosaic_denoise_plan refused {self!r} with black levels {black!r} and a maximum of {m} for a {H} x {W} "
+                             "mosaic (both sides must be even and at least 64)")
+        return out
+
+    def shift(self, maximum=None) -> int:
+        """s of include/r2f.h: the largest shift with (maximum << s) < 65536.  The denoised mosaic is in units of t << s."""
+        return int(self.plan((0, 0, 0, 0), 64, 64, maximum).shift)
+
+    @staticmethod
+    def shifted(profile, shift: int):
+        """The numeric RawProfile the demosaic behind the denoise runs with: black 0 and every multiplier times 2^-shift (exact);
+        all else is the profile's, a blend clip level included."""
+        return replace(profile, black=(0.0,) * 4, multipliers=tuple(m * 2.0 ** -int(shift) for m in profile.multipliers))
 
 
 class _MosaicProfile:
