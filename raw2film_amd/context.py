@@ -571,16 +571,14 @@ class HipContext:
         if nr == 0 or nc == 0:
             return out
         pd = self.planes(out, 0)
+        # which entry point, and the records it takes between the params and the planes
         if projection is not None:
-            self._check(self._lib.r2f_lens_correct_projected(self._h, image.data_ptr(), layout, H, W, C.byref(params), C.byref(projection),
-                                                             None if tca is None else C.byref(tca), C.byref(pd), nr, nc, r0, c0,
-                                                             self._stream()))
-        elif tca is None:
-            self._check(self._lib.r2f_lens_correct(self._h, image.data_ptr(), layout, H, W, C.byref(params), C.byref(pd), nr, nc, r0, c0,
-                                                   self._stream()))
+            fn, records = self._lib.r2f_lens_correct_projected, (C.byref(projection), None if tca is None else C.byref(tca))
+        elif tca is not None:
+            fn, records = self._lib.r2f_lens_correct_tca, (C.byref(tca),)
         else:
-            self._check(self._lib.r2f_lens_correct_tca(self._h, image.data_ptr(), layout, H, W, C.byref(params), C.byref(tca), C.byref(pd),
-                                                       nr, nc, r0, c0, self._stream()))
+            fn, records = self._lib.r2f_lens_correct, ()
+        self._check(fn(self._h, image.data_ptr(), layout, H, W, C.byref(params), *records, C.byref(pd), nr, nc, r0, c0, self._stream()))
         return out
 
     def _mosaic_size(self, mosaic, what, m):

@@ -1,6 +1,6 @@
 // r2f_api.hip -- C ABI (include/r2f.h) over the gfx950 kernels: context, options, table and stencil upload and the stage entry
 // points of the render path.  The stencil dispatch (r2f_stencil.hip), the whole-frame render with its graph cache (r2f_graph.hip),
-// the JPEG entries (r2f_jpeg_api.hip) and the stages off the path with their entries (r2f_resample.hip, r2f_post.hip) are units of
+// the JPEG entries (r2f_jpeg_api.hip) and the stages off the path with their entries (r2f_resample.hip, r2f_lens.hip, r2f_post.hip) are units of
 // their own; r2f_ctx.h is what they share.
 #include <algorithm>
 #include <cmath>

@@ -1,5 +1,5 @@
 // r2f_ctx.h -- what the host units of the library share (r2f_api.hip, r2f_stencil.hip, r2f_graph.hip, r2f_jpeg_api.hip and the
-// entries of r2f_resample.hip and r2f_post.hip): the
+// entries of r2f_resample.hip, r2f_lens.hip and r2f_post.hip): the
 // context, its owned device buffers, the error and device-binding macros, and the functions one unit calls in another.
 #pragma once
 

@@ -1,5 +1,5 @@
 // r2f_kernels.hip -- gfx950 kernels of the film-emulation render path and their launchers; nothing here runs off the path (the
-// resamplers are in r2f_resample.hip, the hand-off, chroma NR, blit and histograms in r2f_post.hip).
+// resamplers are in r2f_resample.hip, the lens step in r2f_lens.hip, the hand-off, chroma NR, blit and histograms in r2f_post.hip).
 //
 // Kernel inventory (pass graph mirrors gpu_processor.py:1763-1862, fused where it is free):
 //   front_kernel      S0 3x3 + S1 2-D LUT [+ S3 log + S4 curve [+ S8 3-D LUT + S9 u8]]        HBM-bound

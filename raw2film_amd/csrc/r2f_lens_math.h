@@ -1,5 +1,5 @@
 // r2f_lens_math.h -- the arithmetic of the lens correction (include/r2f.h, r2f_lens_correct, r2f_lens_correct_tca and
-// r2f_lens_correct_projected), as text the device kernels (r2f_resample.hip) and CPU programs (tests/lens_check.cpp,
+// r2f_lens_correct_projected), as text the device kernels (r2f_lens.hip) and CPU programs (tests/lens_check.cpp,
 // tests/lens_tca_check.cpp, tests/lens_projection_check.cpp, g++ -ffp-contract=off) both compile: the coordinate map, the projection
 // factor in front of its distortion model, red's and blue's TCA step on it, the 1/32 phase split with its inside / outside decision, the 64-tap
 // sample over a pixel-fetch functor (three channels at one coordinate, or one channel at its own) and the vignetting gain.  Every

@@ -1,4 +1,4 @@
-// r2f_post.hip -- everything off the render path that is not a resampler (those: r2f_resample.hip), each stage's entry point
+// r2f_post.hip -- everything off the render path that is not a resampler (those: r2f_resample.hip) or the lens step (r2f_lens.hip), each stage's entry point
 // (include/r2f.h) next to its kernel.  Before the path:
 //   decode_u16 / exposure_rows, _finish / decode_u16_auto   the hand-off from RAW decoding: uint16 -> float frame, with the exposure
 //                      factor given or measured on the device (calc_exposure)

@@ -246,7 +246,7 @@ ROUTES = ("whole", "halves", "gather")
 
 
 def tile_routes(c, rec, tca, H, W, window=None):
-    """Per tile of the window (default: the whole frame) the route of r2f_resample.hip's projected kernel: "whole" (the union of the
+    """Per tile of the window (default: the whole frame) the route of r2f_lens.hip's projected kernel: "whole" (the union of the
     two halves' tap extents fits BOX_TEXELS), else per half "halves" (its own box fits) or "gather" (it does not); -> a list of
     (tile row, tile column, routes of its passes).  Extents are over the inside pixels of all sampled channels."""
     r0, c0, nr, nc = (0, 0, H, W) if window is None else window

@@ -77,9 +77,9 @@ def table():
         rows = sorted(r for part in pool.map(lambda s: digest_source(s, tmp), hips) for r in part)
     print("# tools/codeobj_digest.py: hipcc --offload-arch=gfx950, the product's flags; hash = sha256[:16] of the kernel's instructions")
     print("# (comments and directives dropped, local labels renumbered); LDS = static only; waves/SIMD = register-limited occupancy")
-    print(f"{'kernel':<60}{'file':<20}{'hash':<18}{'insts':>6}{'VGPR':>5}{'AGPR':>5}{'SGPR':>5}{'spilled':>8}{'scratch B':>10}{'waves/SIMD':>11}{'LDS':>7}")
+    print(f"{'kernel':<60}{'file':<24}{'hash':<18}{'insts':>6}{'VGPR':>5}{'AGPR':>5}{'SGPR':>5}{'spilled':>8}{'scratch B':>10}{'waves/SIMD':>11}{'LDS':>7}")
     for r in rows:
-        print(f"{r[0]:<60}{r[1]:<20}{r[2]:<18}{r[3]:>6}{r[4]:>5}{r[5]:>5}{r[6]:>5}{r[7]:>8}{r[8]:>10}{r[9]:>11}{r[10]:>7}")
+        print(f"{r[0]:<60}{r[1]:<24}{r[2]:<18}{r[3]:>6}{r[4]:>5}{r[5]:>5}{r[6]:>5}{r[7]:>8}{r[8]:>10}{r[9]:>11}{r[10]:>7}")
     bad = [r for r in rows if r[7] > 0 or r[8] > 0]
     print(f"# {len(rows)} kernels; with spilled registers or scratch: {len(bad)}" + "".join(f"\n#   {r[0]}" for r in bad))
 
@@ -87,12 +87,13 @@ def table():
 def diff(path_a, path_b):
     def load(p):
         with open(p) as f:
-            rows = [ln.split() for ln in f if ln.strip() and not ln.startswith("#") and not ln.startswith("kernel ")]
-        # a name with template arguments holds blanks: the file column is the first one that ends in .hip
+            rows = [ln for ln in f if ln.strip() and not ln.startswith("#") and not ln.startswith("kernel ")]
+        # a name with template arguments holds blanks, and a file name as wide as its column runs into the hash: the file column is
+        # the first word that ends in .hip
         out = {}
-        for t in rows:
-            i = next(k for k, v in enumerate(t) if v.endswith(".hip"))
-            out[" ".join(t[:i])] = t[i:]
+        for ln in rows:
+            m = re.match(r"(.+?)\s+(\w+\.hip)\s*(.*)", ln)
+            out[" ".join(m.group(1).split())] = [m.group(2)] + m.group(3).split()
         return out
 
     a, b = load(path_a), load(path_b)

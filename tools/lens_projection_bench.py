@@ -9,9 +9,14 @@ with the tests' `poly3` record:
 The share of blocks on each staging route comes from the host restatement of the kernel's rule (tests/lens_projection_model.py's,
 evaluated here strip by strip).
 
-    python tools/lens_projection_bench.py [--rounds 6] [--iters 10]
+    python tools/lens_projection_bench.py [--rounds 6] [--iters 10] [--lib path/to/other/libr2f_hip.so]
 
 The yardsticks are the unprojected kernels and the copy in the same run, not an absolute time.
+
+--lib binds ANOTHER build of the library beside the in-tree one (the parent commit's, to see whether a kernel moved): every case is
+also launched through it, taking turns with the in-tree one inside every round, its output is compared bit for bit (the last line counts the cases that differ, and any makes the exit status 1), and per case the
+ratio in-tree / --lib of every round's median is printed.  The spread of those ratios with --lib pointing at a copy of the in-tree
+library itself is the noise of the method.  The route shares, which do not depend on the build, are left out of such a run.
 """
 import argparse
 import math
@@ -33,6 +38,7 @@ from raw2film_amd.lens import LensProfile  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=6)
 ap.add_argument("--iters", type=int, default=10)
+ap.add_argument("--lib", default=None)
 args = ap.parse_args()
 SHAPES = {"24 MP": (4000, 6000), "100 MP": (8192, 12288)}
 BASE = dict(distortion="ptlens", coefficients=(0.02, -0.06, 0.01), vignetting=(-0.3, 0.1, -0.02))
@@ -40,6 +46,8 @@ POLY3 = tm.TCA_SPECS["poly3"]
 RECORDS = {"fisheye": ("fisheye", 2.0 / math.pi), "equisolid": ("equisolid", 0.55)}
 F = np.float32
 ctx = HipContext(0)
+other_ctx = HipContext(0, lib_path=args.lib) if args.lib else None
+differing = []  # the cases whose output through --lib is not the in-tree library's
 
 
 def timed(fn, iters):
@@ -101,11 +109,13 @@ for label, (H, W) in SHAPES.items():
     print(f"{label} ({H} x {W}): copy {copy_ms:.3f} ms = {2 * img.numel() * 4 / copy_ms / 1e6:.0f} GB/s", flush=True)
     del other
     for tca_name, tca in (("no TCA", None), ("poly3 TCA", POLY3)):
-        calls, yardstick = {}, {}
+        calls, other_calls, yardstick = {}, {}, {}
 
         def add(name, prof, base=None):
             params, proj, tca_params = prof.plan_projected(H, W)
             calls[name] = lambda p=params, j=proj, t=tca_params: ctx.lens_correct(img, p, tca=t, projection=j)
+            if other_ctx:
+                other_calls[name] = lambda p=params, j=proj, t=tca_params: other_ctx.lens_correct(img, p, tca=t, projection=j)
             yardstick[name] = base
             return params.scale
 
@@ -114,9 +124,10 @@ for label, (H, W) in SHAPES.items():
         for rname, record in RECORDS.items():
             auto = LensProfile(**BASE, scale="auto", tca=tca, projection=record)
             scale = auto.plan_projected(H, W)[0].scale
-            shares = route_shares(LensProfile(**BASE, scale=scale, tca=tca, projection=record), H, W, scale)
-            print(f"  [{tca_name}] {rname} auto scale {scale:.4f}: blocks whole {shares['whole']:.3f}, in two staged halves {shares['halves']:.3f}, "
-                  f"with a gathering half {shares['gather']:.3f}", flush=True)
+            if not other_ctx:
+                shares = route_shares(LensProfile(**BASE, scale=scale, tca=tca, projection=record), H, W, scale)
+                print(f"  [{tca_name}] {rname} auto scale {scale:.4f}: blocks whole {shares['whole']:.3f}, in two staged halves {shares['halves']:.3f}, "
+                      f"with a gathering half {shares['gather']:.3f}", flush=True)
             add(f"unprojected, scale {scale:.3f}", LensProfile(**BASE, scale=scale, tca=tca))
             add(f"projected {rname}, scale {scale:.3f}", LensProfile(**BASE, scale=scale, tca=tca, projection=record), f"unprojected, scale {scale:.3f}")
         outs = {}
@@ -125,15 +136,32 @@ for label, (H, W) in SHAPES.items():
                 outs[name] = fn()
         same = torch.equal(outs["projected identity, scale 1.02"].view(torch.int32), outs["unprojected, scale 1.02"].view(torch.int32))
         print(f"  [{tca_name}] identity bit-identical to the unprojected kernel: {same}", flush=True)
+        for name, fn in other_calls.items():
+            for _ in range(3):
+                out = fn()
+            same = torch.equal(out.view(torch.int32), outs[name].view(torch.int32))
+            print(f"  [{tca_name}] {name}: bit-identical to {os.path.basename(args.lib)}'s: {same}", flush=True)
+            if not same:
+                differing.append(f"{label} [{tca_name}] {name}")
+            del out
         del outs
-        rounds = {name: [] for name in calls}
+        rounds, other_rounds = {name: [] for name in calls}, {name: [] for name in other_calls}
         for _ in range(args.rounds):
             for name, fn in calls.items():  # interleaved: every kernel takes its turn in every round
                 rounds[name].append(timed(fn, args.iters))
+                if other_ctx:
+                    other_rounds[name].append(timed(other_calls[name], args.iters))
         med = {name: float(np.median(r)) for name, r in rounds.items()}
         for name, r in rounds.items():
             against = f" = {med[name] / med[yardstick[name]]:.2f} x {yardstick[name]}" if yardstick[name] else ""
             print(f"  [{tca_name}] {name}: median of {args.rounds} round medians {med[name]:.3f} ms (range {min(r):.3f} .. {max(r):.3f}) = "
                   f"{med[name] / copy_ms:.2f} x the copy{against}", flush=True)
+            if other_ctx:
+                ratios = [t / o for t, o in zip(r, other_rounds[name])]
+                print(f"      in-tree / {os.path.basename(args.lib)} per round: {' '.join(f'{q:.4f}' for q in ratios)}  "
+                      f"(min {min(ratios):.4f}, max {max(ratios):.4f})", flush=True)
     del img
     torch.cuda.empty_cache()
+if other_ctx:
+    print(f"outputs that differ from {os.path.basename(args.lib)}'s: {len(differing)}" + "".join(f"\n  {d}" for d in differing), flush=True)
+    sys.exit(1 if differing else 0)
