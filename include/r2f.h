@@ -850,6 +850,41 @@ R2F_API int r2f_demosaic_blend_f32(r2f_ctx* ctx, const uint16_t* src_rows, int s
                      float* dst_f32_hwc3, int y0, int y1, void* stream);
 R2F_API int r2f_demosaic_xtrans_blend_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H,
                      int W, const r2f_xtrans_params* params, int orientation, int clip, uint16_t* dst_u16_hwc3, int y0, int y1, void* stream);
+/* Step M: the median filter of the colour differences (LibRaw's median_filter(): its med_passes, rawpy's median_filter_passes=,
+ * dcraw's -m n).  Parity with LibRaw's bytes is UNPINNED, like every step around it.  M sits between B / B' and Blend of either
+ * demosaic, for both patterns, at full and at reduced size.
+ *   Let I_0 = (R, G, B) be the three integer planes in [0, 65535] that B (full size) or B' (reduced size) leaves.  They cover the
+ *   WHOLE demosaiced frame D of out_h x out_w pixels, whatever window or row range a call takes.  For pass k = 1 .. n and for c in
+ *   {R, B} independently:
+ *     at an interior pixel (1 <= y < out_h - 1 and 1 <= x < out_w - 1)
+ *       I_k[c](y, x) = clamp(median{ I_{k-1}[c](y + j, x + i) - G(y + j, x + i) : i, j in {-1, 0, 1} } + G(y, x), 0, 65535)
+ *     at a border pixel  I_k[c] = I_{k-1}[c].
+ *   G never changes.  Every pass reads only the pass before it (dcraw copies the channel aside before it writes).  The median of
+ *   nine integers is unique; dcraw's 19-exchange network is one way to find it, not part of the definition.  Blend (if any) and
+ *   step C then run on I_n.  A frame with a side below 3 has no interior: its result is the plain entry point's.
+ *   n is in 1 .. R2F_MEDIAN_MAX_PASSES; the cap is what the kernels' LDS apron is sized for, and more passes are refused by name.
+ * Reach.  Full size: an output row reads the mosaic rows within 4 + n (Bayer) or 3 + n (X-Trans) of it, clipped to the frame.
+ * Reduced size: output rows [y0, y1) read the reduced rows [y0 - n, y1 + n) clipped to the frame, that is mosaic rows 2 (or 3) times
+ * that range.  A window edge or a band edge that is not a frame edge is NOT a border: the median there reads pixels outside the
+ * window and outside the band.
+ * Each entry point below is the Blend entry point it is named after -- r2f_demosaic_blend_u16, r2f_demosaic_blend_f32,
+ * r2f_demosaic_xtrans_blend_u16: their arguments, contracts and refusals -- with one more argument, passes, and two changes: clip =
+ * 0 means no Blend (else [1, 65535]; Blend is a uniform branch of the same kernel and gives the Blend entry point's bytes), and the
+ * mosaic rows a call reads are those of the reach above, which must lie inside the source window, else R2F_EINVAL before any launch
+ * with the rows named.  passes outside [1, R2F_MEDIAN_MAX_PASSES] is refused before any launch.  A band's bytes are those of the
+ * same rows of a whole-frame call.  One launch per call: a block stages its tile's samples n rows and columns further, evaluates
+ * B once per pixel of the tile plus an n-pixel ring into LDS planes ((64 + 2n)(32 + 2n) / 2048 of the plain kernel's
+ * interpolation), runs the passes there and leaves through the plain kernels' epilogues. */
+#define R2F_MEDIAN_MAX_PASSES 4
+R2F_API int r2f_demosaic_median_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
+                     const r2f_demosaic_params* params, int orientation, int clip, int passes, uint16_t* dst_u16_hwc3, int y0, int y1,
+                     void* stream);
+R2F_API int r2f_demosaic_median_f32(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
+                     const r2f_demosaic_params* params, int clip, int passes, int row0, int col0, int rows, int cols, float divisor,
+                     float factor, float* dst_f32_hwc3, int y0, int y1, void* stream);
+R2F_API int r2f_demosaic_xtrans_median_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H,
+                     int W, const r2f_xtrans_params* params, int orientation, int clip, int passes, uint16_t* dst_u16_hwc3, int y0, int y1,
+                     void* stream);
 /* The data maximum of mosaic rows [y0, y1), folded into a device word: *dst_max = max(*dst_max, d of those rows).  The caller zeroes
  * the word before the first call; bands in any order and any cut then compose to the whole frame's value, and since an integer
  * maximum does not depend on order the result is exact and the same on every run.  src_rows: uint16 mosaic rows [src_gy0, src_gy0 +

@@ -141,6 +141,7 @@ class DenoiseParams(C.Structure):  # r2f_denoise_params (raw2film_amd.raw.Wavele
 
 
 HIGHLIGHT_CLIP, HIGHLIGHT_UNCLIP, HIGHLIGHT_BLEND = 0, 1, 2  # R2F_HIGHLIGHT_*: LibRaw's highlight modes 0, 1 and 2
+MEDIAN_MAX_PASSES = 4  # R2F_MEDIAN_MAX_PASSES: the most passes of step M (LibRaw's med_passes) the median kernels' LDS holds
 
 _P = C.POINTER
 _fp = C.c_void_p  # float* (host numpy or device) passed as an address
@@ -279,6 +280,21 @@ _SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(XTransParams), C.c_int, C.c_int, C.c_void_p, C.c_int,
          C.c_int, C.c_void_p],
+    ),
+    "r2f_demosaic_median_u16": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(DemosaicParams), C.c_int, C.c_int, C.c_int, C.c_void_p,
+         C.c_int, C.c_int, C.c_void_p],
+    ),
+    "r2f_demosaic_median_f32": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(DemosaicParams), C.c_int, C.c_int, C.c_int, C.c_int,
+         C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
+    ),
+    "r2f_demosaic_xtrans_median_u16": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(XTransParams), C.c_int, C.c_int, C.c_int, C.c_void_p,
+         C.c_int, C.c_int, C.c_void_p],
     ),
     "r2f_mosaic_maximum": (
         C.c_int,

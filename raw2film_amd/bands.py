@@ -93,10 +93,12 @@ def band_source(payload, shape, dtype) -> BandSource:
     frame, factor = frame[:2] + (3,), payload.get("u16_factor")
     step = payload.get("demosaic")
     if step:  # a Bayer mosaic: band k travels with the mosaic rows its demosaic reads beyond those of the bands before it
-        window, params, clip = step["window"], step["params"], step.get("clip")
+        window, params, clip, median = step["window"], step["params"], step.get("clip"), step.get("median", 0)
 
         def demosaic(ctx, landing, image, a0, a1):
-            if clip is None:
+            if median:  # a profile with median_passes: step M reads `median` output rows past the band's ends
+                ctx.demosaic_median_f32(landing, params, median, factor, clip=clip, window=window, out=image, rows=(a0, a1))
+            elif clip is None:
                 ctx.demosaic_f32(landing, params, factor, window=window, out=image, rows=(a0, a1))
             else:  # a ("blend", clip) profile: the same kernel with Blend ahead of the matrix
                 ctx.demosaic_blend_f32(landing, params, clip, factor, window=window, out=image, rows=(a0, a1))
@@ -105,7 +107,7 @@ def band_source(payload, shape, dtype) -> BandSource:
         # the pace; with upload k queued only when band k's turn came the call was no faster than in one piece (100 MP: 15.9 against
         # 15.8 ms, profiles/r17_mosaic_stream_probe.txt).
         return BandSource(frame, landing="mosaic", landing_shape=shape, queue_all=True, measure=None, decode=demosaic,
-                          upload_bounds=lambda bounds: mosaic_upload_bounds(bounds, window, shape[0], bool(params.half_size)))
+                          upload_bounds=lambda bounds: mosaic_upload_bounds(bounds, window, shape[0], bool(params.half_size), median))
     if factor == DEVICE_EXPOSURE:
         # the whole uint16 frame goes up (the statistic is the whole frame's), the bands are rows of its window: band k travels as the
         # frame rows ub[k]:ub[k + 1], the first and the last taking the rows above and below the window along

@@ -20,6 +20,8 @@ LOG_EPS = 1e-6  # lut_1d.wgsl:24
 MOSAIC_KINDS = {_lib.DemosaicParams: ("demosaic_u16", 2), _lib.XTransParams: ("demosaic_xtrans", 6)}
 # ... and the method that does so with Blend (LibRaw's highlight mode 2), which takes the clip level behind the params
 MOSAIC_BLEND_KINDS = {_lib.DemosaicParams: "demosaic_blend_u16", _lib.XTransParams: "demosaic_xtrans_blend"}
+# ... and with step M (median_passes; `clip` is then an argument of the same method, None for no Blend)
+MOSAIC_MEDIAN_KINDS = {_lib.DemosaicParams: "demosaic_median_u16", _lib.XTransParams: "demosaic_xtrans_median"}
 LUT3D_SCALE = 0.25  # cpu_processor.py:405
 
 
@@ -595,11 +597,13 @@ class HipContext:
         H, W = self._mosaic_size(mosaic, what, MOSAIC_KINDS[params_type][1])
         return H, W, params if isinstance(params, params_type) else params.plan(H, W)
 
-    def _demosaic(self, what, fn, params_type, mosaic, params, out, rows, window=None, decode=None, orientation=0, clip=None):
+    def _demosaic(self, what, fn, params_type, mosaic, params, out, rows, window=None, decode=None, orientation=0, clip=None,
+                  passes=None):
         """The demosaic methods: the mosaic check, the planning of a profile, the window, the `out` check, `rows`, the call.
         fn: the C entry point; decode = (divisor, factor): the float32 epilogue, which also takes a window (default: the frame);
         orientation: not 0 with the oriented form of `fn` (r2f_demosaic_oriented_u16: `out` and `rows` are then those of O);
-        clip: the blend form of `fn` (r2f_demosaic_blend_u16, which always takes an orientation, 0 included)."""
+        clip: the blend form of `fn` (r2f_demosaic_blend_u16, which always takes an orientation, 0 included);
+        passes: the median form of `fn` (r2f_demosaic_median_u16: `passes` follows `clip`, which is 0 for no Blend)."""
         torch = self._torch
         H, W, params = self._check_mosaic(mosaic, params, what, params_type)
         if isinstance(orientation, bool) or not isinstance(orientation, numbers.Integral) or not 0 <= orientation <= 7:
@@ -620,7 +624,8 @@ class HipContext:
         y0, y1 = (0, nr) if rows is None else (int(rows[0]), int(rows[1]))
         epilogue = (r0, c0, nr, nc, *decode) if decode else (int(orientation),) if orientation or clip is not None else ()
         if clip is not None:
-            epilogue = (clip, *epilogue) if decode else (*epilogue, clip)
+            blend = (clip,) if passes is None else (clip, passes)
+            epilogue = (*blend, *epilogue) if decode else (*epilogue, *blend)
         self._check(fn(self._h, mosaic.data_ptr(), 0, H, int(mosaic.stride(0)), H, W, C.byref(params), *epilogue, out.data_ptr(), y0, y1,
                        self._stream()))
         return out
@@ -678,6 +683,40 @@ class HipContext:
         clip)[window], factor, divisor)."""
         return self._demosaic("demosaic_blend_f32", self._lib.r2f_demosaic_blend_f32, _lib.DemosaicParams, mosaic, params, out, rows, window,
                               (float(np.float32(divisor)), float(np.float32(factor))), clip=self._blend_clip("demosaic_blend_f32", clip))
+
+    @staticmethod
+    def _median_passes(what, passes) -> int:
+        n = _lib.MEDIAN_MAX_PASSES
+        if isinstance(passes, bool) or not isinstance(passes, numbers.Integral) or not 1 <= passes <= n:
+            raise ValueError(f"{what}: passes must be an integer in [1, {n}] (LibRaw's med_passes; R2F_MEDIAN_MAX_PASSES), got {passes!r}")
+        return int(passes)
+
+    def demosaic_median_u16(self, mosaic, params, passes, clip=None, out=None, rows=None, orientation=0):
+        """demosaic_u16 with step M (r2f_demosaic_median_u16; include/r2f.h, LibRaw's med_passes): `passes` (1 .. 4) passes of the
+        3 x 3 median of R - G and B - G of the whole demosaiced frame between the interpolation and Blend.  clip: None for no
+        Blend, else demosaic_blend_u16's.  Everything else is demosaic_u16's, `orientation` included; rows = (y0, y1) read the
+        mosaic rows of `passes` more output rows either side."""
+        what = "demosaic_median_u16"
+        return self._demosaic(what, self._lib.r2f_demosaic_median_u16, _lib.DemosaicParams, mosaic, params, out, rows, orientation=orientation,
+                              clip=0 if clip is None else self._blend_clip(what, clip), passes=self._median_passes(what, passes))
+
+    def demosaic_xtrans_median(self, mosaic, params, passes, clip=None, out=None, rows=None, orientation=0):
+        """demosaic_xtrans with step M (r2f_demosaic_xtrans_median_u16): demosaic_median_u16's `passes` and `clip` for an X-Trans
+        mosaic."""
+        what = "demosaic_xtrans_median"
+        return self._demosaic(what, self._lib.r2f_demosaic_xtrans_median_u16, _lib.XTransParams, mosaic, params, out, rows,
+                              orientation=orientation, clip=0 if clip is None else self._blend_clip(what, clip),
+                              passes=self._median_passes(what, passes))
+
+    def demosaic_median_f32(self, mosaic, params, passes, factor: float, divisor: float = 65535.0, clip=None, window=None, out=None,
+                            rows=None):
+        """demosaic_f32 with step M (r2f_demosaic_median_f32): bit-identical to decode_u16(demosaic_median_u16(mosaic, params,
+        passes, clip)[window], factor, divisor).  The median at a window or row-range edge that is no frame edge reads the frame
+        beyond it: a call reads the mosaic rows of `passes` more output rows either side."""
+        what = "demosaic_median_f32"
+        return self._demosaic(what, self._lib.r2f_demosaic_median_f32, _lib.DemosaicParams, mosaic, params, out, rows, window,
+                              (float(np.float32(divisor)), float(np.float32(factor))),
+                              clip=0 if clip is None else self._blend_clip(what, clip), passes=self._median_passes(what, passes))
 
     def mosaic_maximum(self, mosaic, profile_or_black, period=None, rows=None, out=None):
         """The data maximum of include/r2f.h (r2f_mosaic_maximum): the largest black-subtracted sample, clamped at 0, of a uint16

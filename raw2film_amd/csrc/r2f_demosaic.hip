@@ -3,7 +3,8 @@
 // its entry points.  The arithmetic is r2f_demosaic_math.h's (the text tests/demosaic_check.cpp compiles for the CPU).  Seven
 // kernels: the full and the half size, each with the uint16 and with the float epilogue; and for r2f_demosaic_oriented_u16 the
 // mirrored and the turned full size and the oriented half size (uint16).  Seven more with Blend for r2f_demosaic_blend_u16 /
-// r2f_demosaic_blend_f32: the same staging and LDS, mosaic::blend_pixel ahead of the matrix (2 more VGPRs at full size).
+// r2f_demosaic_blend_f32: the same staging and LDS, mosaic::blend_pixel ahead of the matrix (2 more VGPRs at full size).  And seven
+// median kernels for r2f_demosaic_median_u16 / r2f_demosaic_median_f32 (step M; r2f_mosaic_stage.h has them and their LDS).
 // LDS per block of the full size: 5760 (72 x 40 samples) + 4488 (the green plane, 66 x 34) and the row buffer of the epilogue, 1536
 // (uint16, upright or mirrored) or 3072 (float) -- 11.5 or 13 KB: a dozen blocks fit a CU's 160 KB either way, so the wave slots are
 // the limit, not LDS.  The turned class holds the whole tile in O's layout instead, 64 rows of 196 bytes = 12544: 22.3 KB, seven
@@ -115,6 +116,26 @@ int r2f_demosaic_blend_f32(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, 
     const int window[4] = {row0, col0, rows, cols};
     return mosaic_rows<BayerPattern, true, true>(ctx, "demosaic_blend_f32", src_rows, src_gy0, src_nrows, src_pitch, H, W, params, window,
                                                  divisor, factor, dst_f32_hwc3, y0, y1, stream, 0, clip);
+}
+
+// Step M between the interpolation and Blend (clip 0: no Blend): the median kernels of r2f_mosaic_stage.h
+int r2f_demosaic_median_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
+                            const r2f_demosaic_params* params, int orientation, int clip, int passes, uint16_t* dst_u16_hwc3, int y0, int y1,
+                            void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    return mosaic_rows<BayerPattern, false, false, true>(ctx, "demosaic_median_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, params,
+                                                         nullptr, 1.f, 1.f, dst_u16_hwc3, y0, y1, stream, orientation, clip, passes);
+}
+
+int r2f_demosaic_median_f32(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
+                            const r2f_demosaic_params* params, int clip, int passes, int row0, int col0, int rows, int cols, float divisor,
+                            float factor, float* dst_f32_hwc3, int y0, int y1, void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    const int window[4] = {row0, col0, rows, cols};
+    return mosaic_rows<BayerPattern, true, false, true>(ctx, "demosaic_median_f32", src_rows, src_gy0, src_nrows, src_pitch, H, W, params,
+                                                        window, divisor, factor, dst_f32_hwc3, y0, y1, stream, 0, clip, passes);
 }
 
 }  // extern "C"

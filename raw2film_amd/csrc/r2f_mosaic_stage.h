@@ -6,6 +6,9 @@
 //                          1-sample apron in LDS, then the pattern's pixel_rgb and step C per output pixel; a wave's row leaves
 //                          through an LDS transpose as one contiguous segment
 //   mosaic_reduced_kernel  one lane per output pixel of the reduced form (a half or a third of the mosaic's sides)
+//   mosaic_median_full_kernel, mosaic_median_reduced_kernel   the same two with step M (LibRaw's med_passes) behind the interpolation:
+//                          the tile's three planes plus an n-pixel ring in LDS, n passes of the 3 x 3 median of R - G and B - G there
+//                          (median_passes; the arithmetic is r2f_median_math.h's), then the epilogues above (leave_tile)
 //   mosaic_rows            the checks every entry point makes, then one launch
 // Each is a template over a Pattern and over the epilogue: the uint16 frame, or a window of it decoded to the float frame the front
 // stage reads (decode_sample of r2f_device.h on each finished sample); and, for the uint16 frame written the way round the sensor
@@ -34,6 +37,7 @@
 #include <type_traits>
 
 #include "r2f_ctx.h"
+#include "r2f_median_math.h"
 #include "r2f_mosaic_math.h"
 
 namespace r2f {
@@ -316,13 +320,283 @@ __global__ __launch_bounds__(256) void mosaic_reduced_kernel(const MosaicArgs<ty
     d[0] = finish_sample<F32>(a, out[0]), d[1] = finish_sample<F32>(a, out[1]), d[2] = finish_sample<F32>(a, out[2]);
 }
 
+// ------------------------------------------------------------------------------------------------------------------------ step M
+// The median kernels (include/r2f.h, step M: LibRaw's med_passes): the two kernels above with n passes of the 3 x 3 median of R - G
+// and B - G between the interpolation and Blend / step C.  A block holds the three planes of its tile plus an n-pixel ring in LDS
+// (sized for the cap: the kernels keep static LDS), filled once from pixel_rgb / reduced_rgb; the passes run in LDS, ping-pong for
+// red and blue, and the region that is still exact shrinks by one ring per pass down to the tile.  The ring is the frame's, not
+// the call's: a window or row-range edge that is no frame edge reads beyond it, so the staged samples reach n further
+// (kReachY + n rows; the entry point has checked the source window for them).  Blend is a uniform run-time branch on `clip` here
+// (0: none), not a template flag: half the instantiations, the same bytes.  The argument record is the kernels' own: MosaicArgs and
+// the kernels above are what they were.
+constexpr int kMedN = R2F_MEDIAN_MAX_PASSES;
+constexpr int kMedW = kTW + 2 * kMedN, kMedH = kTH + 2 * kMedN;  // the region of the cap: 72 x 40 pixels
+static_assert(kMedN % 2 == 0, "the staged samples start at an even column");
+
+template <typename Params>
+struct MedianArgs {
+    MosaicArgs<Params> m;  // (clip: 0 for no Blend)
+    int passes;            // n, 1 .. kMedN
+};
+
+// A block's planes: green, and red / blue twice: I_k is in r0, b0 for an even k, in r1, b1 for an odd one.  (Selects, not a pointer
+// array: a register array indexed by a variable goes to scratch.)
+struct MedianPlanes {
+    uint16_t *g, *r0, *b0, *r1, *b1;
+    __device__ __forceinline__ uint16_t* r(int odd) const { return odd ? r1 : r0; }
+    __device__ __forceinline__ uint16_t* b(int odd) const { return odd ? b1 : b0; }
+};
+
+// The n passes.  The planes hold kMedH x kMedW pixels from frame position (y_org, x_org); on entry g, r0, b0 are I_0 on the
+// block's rectangle [ya, yb) x [xa, xb) of D grown by n rings and clipped to the frame (written by these lanes: the barrier is
+// here).  Pass k writes that rectangle grown by n - k rings: an interior pixel of the frame by median::pass_pixel, a border pixel
+// carried over.  I_n on the rectangle itself is then in r(n & 1), b(n & 1), which is returned; a barrier stands behind the last pass.
+__device__ __forceinline__ int median_passes(const MedianPlanes& pl, int y_org, int x_org, int ya, int yb, int xa, int xb, int n, int out_h,
+                                             int out_w, int tid) {
+    __syncthreads();
+    const Tile<uint16_t, kMedW> G{pl.g, y_org, x_org};
+    for (int k = 1; k <= n; ++k) {
+        const int m = n - k, from = (k - 1) & 1;
+        const int py0 = ya - m > 0 ? ya - m : 0, py1 = yb + m < out_h ? yb + m : out_h;
+        const int px0 = xa - m > 0 ? xa - m : 0, px1 = xb + m < out_w ? xb + m : out_w;
+        const Tile<uint16_t, kMedW> R{pl.r(from), y_org, x_org}, B{pl.b(from), y_org, x_org};
+        uint16_t *to_r = pl.r(from ^ 1), *to_b = pl.b(from ^ 1);
+        for (int i = tid; i < kMedH * kMedW; i += 256) {
+            const int y = y_org + i / kMedW, x = x_org + i % kMedW;
+            if (y < py0 || y >= py1 || x < px0 || x >= px1) continue;
+            int r, b;
+            if (mosaic::in_ring(out_h, out_w, y, x, 1))
+                r = R(y, x), b = B(y, x);
+            else
+                median::pass_pixel(R, B, G, y, x, r, b);
+            to_r[i] = (uint16_t)r, to_b[i] = (uint16_t)b;
+        }
+        __syncthreads();
+    }
+    return n & 1;
+}
+
+// How a tile's finished pixels leave, by OrientClass: mosaic_full_kernel's three epilogues from the point where they call pixel_rgb,
+// as a function.  `rgb_of(y, x, rgb)` yields the three planes of pixel (y, x) of D ahead of the matrix M (step C), s_out is the
+// block's row buffers (the turned class: the whole tile).  Called by all 256 lanes of a (64, 4) block whose tile has its origin at
+// (ty0, tx0).  (mosaic_full_kernel keeps its own text: calling this function from it left its registers and LDS alone but reordered
+// its instructions, and it ran 1 - 3 % slower beside the build of before in one process.  The comments on the index arithmetic are
+// there.)
+template <bool F32, int Cls, typename Params, typename OutBuffer, typename RgbFn>
+__device__ __forceinline__ void leave_tile(const MosaicArgs<Params>& a, const float (&M)[9], OutBuffer& s_out, int tx0, int ty0,
+                                           const RgbFn& rgb_of) {
+    const int tx = threadIdx.x, ty = threadIdx.y;
+    const int x = tx0 + tx;
+    // this tile's share of a row of the window: columns [xa, xb), n elements
+    const int xa = tx0 > a.x0 ? tx0 : a.x0, xb = tx0 + kTW < a.x1 ? tx0 + kTW : a.x1, n = 3 * (xb - xa);
+    if constexpr (Cls == kTurned) {
+        // The tile's rows of D, [ty0, ye), are columns [c0, c0 + ye - ty0) of O, backwards with the rows mirrored; its column x of D is
+        // row x of O, or out_w - 1 - x with the columns mirrored.  All pixels into the buffer first, then a wave takes every fourth
+        // row of it to dst as one contiguous run.
+        const bool flip_rows = a.orientation & orient::kRows, flip_cols = a.orientation & orient::kCols;
+        const int ye = ty0 + kTH < a.y1 ? ty0 + kTH : a.y1, c0 = flip_rows ? a.p.out_h - ye : ty0;
+        for (int q = 0; q < kRowsPerLane; ++q) {
+            const int y = ty0 + ty + 4 * q;
+            if (y < ye && x >= xa && x < xb) {
+                int rgb[3];
+                uint16_t out[3];
+                rgb_of(y, x, rgb);
+                mosaic::colour(M, rgb, out);
+                uint16_t* o = s_out + tx * kTurnPitch + 3 * (flip_rows ? ye - 1 - y : y - ty0);
+                o[0] = out[0], o[1] = out[1], o[2] = out[2];
+            }
+        }
+        __syncthreads();
+        uint16_t* dst = static_cast<uint16_t*>(a.dst);
+        for (int j = ty; j < kTW; j += 4) {  // (the same for all 64 lanes of a wave)
+            const int xj = tx0 + j;
+            if (xj < xa || xj >= xb) continue;
+            const int r = flip_cols ? a.p.out_w - 1 - xj : xj;
+            store_segment(dst + ((long long)r * a.p.out_h + c0) * 3, s_out + j * kTurnPitch, 3 * (ye - ty0), tx);
+        }
+    } else if constexpr (Cls == kMirrored) {
+        // The upright walk below with two changes (the window is the frame: x0 = 0, x1 = out_w, dst_y0 = 0).  Row y of D is row
+        // out_h - 1 - y of O with bit 2: the segment pointer walks upward.  With bit 1 the tile's columns [xa, xb) are O's
+        // [out_w - xb, out_w - xa), and a lane writes its pixel to the mirrored slot of the row buffer.
+        const bool flip_rows = a.orientation & orient::kRows, flip_cols = a.orientation & orient::kCols;
+        const long long row_elems = 3LL * a.p.out_w, step = flip_rows ? -4 * row_elems : 4 * row_elems;
+        const int slot = flip_cols ? xb - 1 - x : x - xa;
+        uint16_t* seg = static_cast<uint16_t*>(a.dst) + (flip_rows ? a.p.out_h - 1 - (ty0 + ty) : ty0 + ty) * row_elems +
+                        3 * (flip_cols ? a.p.out_w - xb : xa);
+        for (int q = 0; q < kRowsPerLane; ++q, seg += step) {
+            const int y = ty0 + ty + 4 * q;  // (the same for all 64 lanes of a wave)
+            if (y < a.y1 && x >= xa && x < xb) {
+                int rgb[3];
+                uint16_t out[3];
+                rgb_of(y, x, rgb);
+                mosaic::colour(M, rgb, out);
+                uint16_t* o = s_out[ty] + 3 * slot;
+                o[0] = out[0], o[1] = out[1], o[2] = out[2];
+            }
+            __syncthreads();
+            if (y < a.y1) store_segment(seg, s_out[ty], n, tx);
+            __syncthreads();
+        }
+    } else {
+        // the wave's row segment, n contiguous elements of dst: that of its first row, then four rows on per step (one 64-bit product
+        // here, none per row)
+        const long long row_elems = 3LL * (a.x1 - a.x0);
+        OutT<F32>* seg = static_cast<OutT<F32>*>(a.dst) + (ty0 + ty - a.dst_y0) * row_elems + 3 * (xa - a.x0);
+        for (int q = 0; q < kRowsPerLane; ++q, seg += 4 * row_elems) {
+            const int y = ty0 + ty + 4 * q;  // (the same for all 64 lanes of a wave)
+            if (y < a.y1 && x >= xa && x < xb) {
+                int rgb[3];
+                uint16_t out[3];
+                rgb_of(y, x, rgb);
+                mosaic::colour(M, rgb, out);
+                OutT<F32>* o = s_out[ty] + 3 * (x - xa);
+                o[0] = finish_sample<F32>(a, out[0]), o[1] = finish_sample<F32>(a, out[1]), o[2] = finish_sample<F32>(a, out[2]);
+            }
+            __syncthreads();
+            if (y < a.y1) store_segment(seg, s_out[ty], n, tx);
+            __syncthreads();
+        }
+    }
+}
+
+// The full size.  LDS: the three planes of I_0, and behind them one range that first holds the staged samples and the auxiliary
+// plane (dead once the planes exist) and then the second red and blue planes and the epilogue's buffer.
+template <typename Pattern, bool F32, int Cls = kUpright>
+__global__ __launch_bounds__(256) void mosaic_median_full_kernel(const MedianArgs<typename Pattern::Params> ma) {
+    static_assert(Cls == kUpright || !F32, "the float epilogue is upright");
+    using Aux = typename Pattern::Aux;
+    constexpr int kReachY = Pattern::kReachY + kMedN, kApronX = Pattern::kApronX + kMedN;  // of the cap; a call loads what its n reaches
+    constexpr int kSW = kTW + 2 * kApronX, kSH = kTH + 2 * kReachY, kAW = kMedW + 2, kAH = kMedH + 2, kPlane = kMedH * kMedW;
+    using OutBuffer = std::conditional_t<Cls == kTurned, uint16_t[kTW * kTurnPitch], OutT<F32>[4][3 * kTW]>;
+    constexpr int kSamplesBytes = (kSH * kSW * 2 + 15) / 16 * 16, kStageBytes = kSamplesBytes + kAH * kAW * (int)sizeof(Aux);
+    constexpr int kLateBytes = 2 * kPlane * 2 + (int)sizeof(OutBuffer);
+    static_assert(kSW % 2 == 0 && (kPlane * 2) % 16 == 0, "pairs at even columns; 16-byte aligned planes and buffer");
+    __shared__ typename Pattern::Params s_p;  // (no use of it, and so no LDS, unless the pattern keeps its params there)
+    __shared__ __align__(16) uint16_t s_i0[3 * kPlane];
+    __shared__ __align__(16) unsigned char s_u[kStageBytes > kLateBytes ? kStageBytes : kLateBytes];
+    uint16_t* s_s = reinterpret_cast<uint16_t*>(s_u);
+    Aux* s_a = reinterpret_cast<Aux*>(s_u + kSamplesBytes);
+    uint16_t* s_i1 = reinterpret_cast<uint16_t*>(s_u);
+    OutBuffer& s_out = *reinterpret_cast<OutBuffer*>(s_u + 2 * kPlane * 2);
+    const MedianPlanes pl{s_i0, s_i0 + kPlane, s_i0 + 2 * kPlane, s_i1, s_i1 + kPlane};
+
+    const MosaicArgs<typename Pattern::Params>& a = ma.m;
+    const int n = ma.passes;
+    const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * 64 + tx;
+    const int tx0 = (a.x0 / kTW + (int)blockIdx.x) * kTW, ty0 = a.y0 + blockIdx.y * kTH;
+    if constexpr (Pattern::kParamsInLds) {
+        stage_params(a, s_p, tid);
+        __syncthreads();
+    }
+    const typename Pattern::Params& p = params_of<Pattern>(a, s_p);
+    // the block's rectangle of D, and the rows and columns of I_0 it needs: n rings more, inside the frame
+    const int ya = ty0, yb = ty0 + kTH < a.y1 ? ty0 + kTH : a.y1;
+    const int xa = tx0 > a.x0 ? tx0 : a.x0, xb = tx0 + kTW < a.x1 ? tx0 + kTW : a.x1;
+    const int iy0 = ya - n > 0 ? ya - n : 0, iy1 = yb + n < a.H ? yb + n : a.H, ix0 = xa - n > 0 ? xa - n : 0, ix1 = xb + n < a.W ? xb + n : a.W;
+    // the samples those pixels read (the entry point has checked that the source window holds the rows)
+    const int ry0 = iy0 - Pattern::kReachY > 0 ? iy0 - Pattern::kReachY : 0, ry1 = iy1 + Pattern::kReachY < a.H ? iy1 + Pattern::kReachY : a.H;
+
+    for (int i = tid; i < kSH * (kSW / 2); i += 256) {
+        const int r = i / (kSW / 2), c = 2 * (i % (kSW / 2));
+        const int y = ty0 - kReachY + r, x = tx0 - kApronX + c;  // (x is even: the tile origin, the apron and the cap are)
+        int s0 = 0, s1 = 0;
+        if (y >= ry0 && y < ry1) load_pair<Pattern>(a, p, y, x, s0, s1);
+        s_s[r * kSW + c] = (uint16_t)s0, s_s[r * kSW + c + 1] = (uint16_t)s1;
+    }
+    __syncthreads();
+
+    const Tile<uint16_t, kSW> S{s_s, ty0 - kReachY, tx0 - kApronX};
+    // the auxiliary plane where those pixels read it: one sample around them, inside the pattern's ring
+    constexpr int kRing = Pattern::kAuxRing;
+    const int ay0 = iy0 - 1 > kRing ? iy0 - 1 : kRing, ay1 = iy1 + 1 < a.H - kRing ? iy1 + 1 : a.H - kRing;
+    const int ax0 = ix0 - 1 > kRing ? ix0 - 1 : kRing, ax1 = ix1 + 1 < a.W - kRing ? ix1 + 1 : a.W - kRing;
+    for (int i = tid; i < kAH * kAW; i += 256) {
+        const int r = i / kAW, c = i % kAW;
+        const int y = ty0 - kMedN - 1 + r, x = tx0 - kMedN - 1 + c;
+        int v = 0;
+        if (y >= ay0 && y < ay1 && x >= ax0 && x < ax1) v = Pattern::aux_at(p, S, a.H, a.W, y, x);
+        s_a[i] = (Aux)v;
+    }
+    __syncthreads();
+
+    const Tile<Aux, kAW> A{s_a, ty0 - kMedN - 1, tx0 - kMedN - 1};
+    const int y_org = ty0 - kMedN, x_org = tx0 - kMedN;
+    for (int i = tid; i < kPlane; i += 256) {  // I_0: pixel_rgb once per pixel of the region
+        const int y = y_org + i / kMedW, x = x_org + i % kMedW;
+        if (y < iy0 || y >= iy1 || x < ix0 || x >= ix1) continue;
+        int rgb[3];
+        Pattern::pixel_rgb(p, S, A, a.H, a.W, y, x, rgb);
+        pl.r0[i] = (uint16_t)rgb[0], pl.g[i] = (uint16_t)rgb[1], pl.b0[i] = (uint16_t)rgb[2];
+    }
+    const int last = median_passes(pl, y_org, x_org, ya, yb, xa, xb, n, a.H, a.W, tid);  // (full size: D has the mosaic's sides)
+
+    const Tile<uint16_t, kMedW> R{pl.r(last), y_org, x_org}, G{pl.g, y_org, x_org}, B{pl.b(last), y_org, x_org};
+    leave_tile<F32, Cls>(a, p.M, s_out, tx0, ty0, [&](int y, int x, int (&rgb)[3]) {
+        rgb[0] = R(y, x), rgb[1] = G(y, x), rgb[2] = B(y, x);
+        if (a.clip) mosaic::blend_pixel(rgb, a.clip);
+    });
+}
+
+// The reduced form: the same region from reduced_rgb (each lane loads its cells itself), the same passes; a lane then stores its
+// pixels as mosaic_reduced_kernel does.  Tiles are anchored to the call's rectangle.
+template <typename Pattern, bool F32, bool Oriented = false>
+__global__ __launch_bounds__(256) void mosaic_median_reduced_kernel(const MedianArgs<typename Pattern::Params> ma) {
+    constexpr int kPlane = kMedH * kMedW;
+    __shared__ typename Pattern::Params s_p;  // (as above)
+    __shared__ __align__(16) uint16_t s_i[5 * kPlane];
+    const MedianPlanes pl{s_i, s_i + kPlane, s_i + 2 * kPlane, s_i + 3 * kPlane, s_i + 4 * kPlane};
+    const MosaicArgs<typename Pattern::Params>& a = ma.m;
+    const int n = ma.passes;
+    const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * 64 + tx;
+    if constexpr (Pattern::kParamsInLds) {
+        stage_params(a, s_p, tid);
+        __syncthreads();
+    }
+    const typename Pattern::Params& p = params_of<Pattern>(a, s_p);
+    const int out_h = a.p.out_h, out_w = a.p.out_w;
+    const int xa = a.x0 + blockIdx.x * kTW, ya = a.y0 + blockIdx.y * kTH;
+    const int xb = xa + kTW < a.x1 ? xa + kTW : a.x1, yb = ya + kTH < a.y1 ? ya + kTH : a.y1;
+    const int iy0 = ya - n > 0 ? ya - n : 0, iy1 = yb + n < out_h ? yb + n : out_h, ix0 = xa - n > 0 ? xa - n : 0, ix1 = xb + n < out_w ? xb + n : out_w;
+    const int y_org = ya - kMedN, x_org = xa - kMedN;
+    for (int i = tid; i < kPlane; i += 256) {
+        const int y = y_org + i / kMedW, x = x_org + i % kMedW;
+        if (y < iy0 || y >= iy1 || x < ix0 || x >= ix1) continue;
+        int rgb[3];
+        Pattern::reduced_rgb(a, p, y, x, rgb);
+        pl.r0[i] = (uint16_t)rgb[0], pl.g[i] = (uint16_t)rgb[1], pl.b0[i] = (uint16_t)rgb[2];
+    }
+    const int last = median_passes(pl, y_org, x_org, ya, yb, xa, xb, n, out_h, out_w, tid);
+
+    const Tile<uint16_t, kMedW> R{pl.r(last), y_org, x_org}, G{pl.g, y_org, x_org}, B{pl.b(last), y_org, x_org};
+    const int x = xa + tx;
+    if (x >= xb) return;  // (no barrier below)
+    for (int y = ya + ty; y < yb; y += 4) {
+        int rgb[3] = {R(y, x), G(y, x), B(y, x)};
+        uint16_t out[3];
+        if (a.clip) mosaic::blend_pixel(rgb, a.clip);
+        mosaic::colour(p.M, rgb, out);
+        OutT<F32>* d;
+        if constexpr (Oriented) {
+            static_assert(!F32, "the float epilogue is upright");
+            int r, c;
+            orient::from_frame(a.orientation, out_h, out_w, y, x, r, c);
+            d = static_cast<OutT<F32>*>(a.dst) + ((long long)r * orient::cols(a.orientation, out_h, out_w) + c) * 3;
+        } else {
+            d = static_cast<OutT<F32>*>(a.dst) + ((long long)(y - a.dst_y0) * (a.x1 - a.x0) + (x - a.x0)) * 3;
+        }
+        d[0] = finish_sample<F32>(a, out[0]), d[1] = finish_sample<F32>(a, out[1]), d[2] = finish_sample<F32>(a, out[2]);
+    }
+}
+
 // An entry point: the checks, then one launch.  The window (row0, col0, rows, cols) of the demosaiced frame is what dst holds (none:
 // all of it); [y0, y1) are rows of the window.  `what` names the entry point in messages.  The oriented entry points (uint16, no
 // window) pass their orientation: [y0, y1) are then rows of O, dst is O, and the launch walks orient::rect_of's rectangle of D.
-template <typename Pattern, bool F32, bool Blend = false>
+// The median entry points (Median) pass their passes n and a clip that may be 0 (no Blend); their rows of D read I_0 n rows further.
+template <typename Pattern, bool F32, bool Blend = false, bool Median = false>
 int mosaic_rows(r2f_ctx* ctx, const char* what, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
                 const typename Pattern::Params* params, const int* window, float divisor, float factor, void* dst, int y0, int y1,
-                void* stream, int orientation = 0, int clip = 0) {
+                void* stream, int orientation = 0, int clip = 0, int passes = 0) {
+    static_assert(!(Blend && Median), "the median kernels branch on clip");
     constexpr int kMaxSide = 1 << 17;  // (the reduced grid has a block per four rows; indices go through long long)
     constexpr int kMin = Pattern::kMinSide, kReduction = Pattern::kReduction, kReachY = Pattern::kReachY;
     if (!src_rows || !params || !dst || H < kMin || W < kMin || H > kMaxSide || W > kMaxSide || src_pitch < W || src_gy0 < 0 || src_nrows < 0)
@@ -336,6 +610,10 @@ int mosaic_rows(r2f_ctx* ctx, const char* what, const uint16_t* src_rows, int sr
     if (!orient::valid(orientation) || (orientation && (F32 || window)))
         return fail(ctx, R2F_EINVAL, "%s: orientation %d is not one of 0 .. 7 (LibRaw's sizes.flip bits)", what, orientation);
     if (Blend && (clip < 1 || clip > 65535)) return fail(ctx, R2F_EINVAL, "%s: clip %d is not inside [1, 65535]", what, clip);
+    if (Median && (clip < 0 || clip > 65535)) return fail(ctx, R2F_EINVAL, "%s: clip %d is neither 0 (no Blend) nor inside [1, 65535]", what, clip);
+    if (Median && (passes < 1 || passes > R2F_MEDIAN_MAX_PASSES))
+        return fail(ctx, R2F_EINVAL, "%s: passes %d is not inside [1, R2F_MEDIAN_MAX_PASSES = %d] (LibRaw's med_passes)", what, passes,
+                    R2F_MEDIAN_MAX_PASSES);
     const int frame_rows = orient::rows(orientation, p.out_h, p.out_w);  // (an oriented call has no window: dst is all of O)
     const int row0 = window ? window[0] : 0, col0 = window ? window[1] : 0, rows = window ? window[2] : frame_rows,
               cols = window ? window[3] : p.out_w;
@@ -348,8 +626,10 @@ int mosaic_rows(r2f_ctx* ctx, const char* what, const uint16_t* src_rows, int sr
     if (y0 == y1) return R2F_OK;
     // the rectangle of the demosaiced frame this call takes: the window's rows [y0, y1) over its columns, or what O's rows hold
     const orient::Rect d = orientation ? orient::rect_of(orientation, p.out_h, p.out_w, y0, y1) : orient::Rect{row0 + y0, row0 + y1, col0, col0 + cols};
+    // the rows of D whose I_0 it reads: its own, and with step M `passes` more either side, inside the frame
+    const orient::Rect read{d.y0 - passes > 0 ? d.y0 - passes : 0, d.y1 + passes < p.out_h ? d.y1 + passes : p.out_h, d.x0, d.x1};
     int lo, hi;
-    orient::source_rows(orientation, d, H, kReachY, reduced ? kReduction : 0, lo, hi);
+    orient::source_rows(orientation, read, H, kReachY, reduced ? kReduction : 0, lo, hi);
     if (lo < src_gy0 || (long long)hi > (long long)src_gy0 + src_nrows)
         return fail(ctx, R2F_EINVAL, "%s: rows [%d, %d) read mosaic rows [%d, %d), the source window holds [%d, %lld)", what, y0, y1, lo, hi,
                     src_gy0, (long long)src_gy0 + src_nrows);
@@ -360,6 +640,28 @@ int mosaic_rows(r2f_ctx* ctx, const char* what, const uint16_t* src_rows, int sr
     const dim3 reduced_grid((d.x1 - d.x0 + 63) / 64, (d.y1 - d.y0 + 3) / 4);
     // (the whole frame: ceil(W / 64) tiles from column 0)
     const dim3 full_grid((d.x1 - 1) / kTW - d.x0 / kTW + 1, (d.y1 - d.y0 + kTH - 1) / kTH);
+    if constexpr (Median) {
+        const MedianArgs<typename Pattern::Params> ma{a, passes};
+        const dim3 tiles((d.x1 - d.x0 + kTW - 1) / kTW, full_grid.y);  // (the reduced form's: anchored to the rectangle)
+        if constexpr (!F32) {
+            if (orientation) {
+                if (reduced)
+                    launch_k(mosaic_median_reduced_kernel<Pattern, false, true>, tiles, dim3(64, 4), 0, s, ma);
+                else if (orientation & orient::kSwap)
+                    launch_k(mosaic_median_full_kernel<Pattern, false, kTurned>, full_grid, dim3(64, 4), 0, s, ma);
+                else
+                    launch_k(mosaic_median_full_kernel<Pattern, false, kMirrored>, full_grid, dim3(64, 4), 0, s, ma);
+                R2F_HIP(ctx, take_launch_status());
+                return R2F_OK;
+            }
+        }
+        if (reduced)
+            launch_k(mosaic_median_reduced_kernel<Pattern, F32, false>, tiles, dim3(64, 4), 0, s, ma);
+        else
+            launch_k(mosaic_median_full_kernel<Pattern, F32, kUpright>, full_grid, dim3(64, 4), 0, s, ma);
+        R2F_HIP(ctx, take_launch_status());
+        return R2F_OK;
+    }
     if constexpr (!F32) {
         if (orientation) {
             if (reduced)

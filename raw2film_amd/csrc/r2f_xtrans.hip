@@ -3,7 +3,8 @@
 // entry points.  The arithmetic is r2f_xtrans_math.h's (the text tests/xtrans_check.cpp compiles for the CPU).  Five kernels: the
 // full and the reduced (third) size with the uint16 epilogue, and for r2f_demosaic_xtrans_oriented_u16 the mirrored and the turned
 // full size and the oriented reduced size; the float epilogue and the window exist in the staging and are not instantiated for this
-// pattern.  Five more with Blend for r2f_demosaic_xtrans_blend_u16: the same staging and LDS.
+// pattern.  Five more with Blend for r2f_demosaic_xtrans_blend_u16: the same staging and LDS.  And five median kernels for
+// r2f_demosaic_xtrans_median_u16 (step M; r2f_mosaic_stage.h has them and their LDS).
 // LDS per block of the full size: 900 (tables) + 5472 (72 x 38 samples) + 8976 (differences, 66 x 34 int32: 17 bits) + 1536 (row
 // buffers, upright or mirrored) = 16.9 KB: nine blocks fit a CU's 160 KB, more than its wave slots take at 256 threads.  The turned
 // class holds the whole tile in O's layout in place of the row buffers, 64 rows of 196 bytes = 12544: 27.9 KB, five blocks a CU --
@@ -98,6 +99,16 @@ int r2f_demosaic_xtrans_blend_u16(r2f_ctx* ctx, const uint16_t* src_rows, int sr
     R2F_GUARD(ctx);
     return mosaic_rows<XTransPattern, false, true>(ctx, "demosaic_xtrans_blend_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, params,
                                                    nullptr, 1.f, 1.f, dst_u16_hwc3, y0, y1, stream, orientation, clip);
+}
+
+// Step M between the interpolation and Blend (clip 0: no Blend): the median kernels of r2f_mosaic_stage.h
+int r2f_demosaic_xtrans_median_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
+                                   const r2f_xtrans_params* params, int orientation, int clip, int passes, uint16_t* dst_u16_hwc3, int y0,
+                                   int y1, void* stream) {
+    if (!ctx) return R2F_EINVAL;
+    R2F_GUARD(ctx);
+    return mosaic_rows<XTransPattern, false, false, true>(ctx, "demosaic_xtrans_median_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W,
+                                                          params, nullptr, 1.f, 1.f, dst_u16_hwc3, y0, y1, stream, orientation, clip, passes);
 }
 
 }  // extern "C"

@@ -33,7 +33,7 @@ import numpy as np
 
 from . import _lib, filmstock, geometry, payload as phase1, stencils, tiff
 from .bands import StreamedFrame, band_source, plan_bands, stage_schedule
-from .context import LOG_EPS, LUT3D_SCALE, MOSAIC_BLEND_KINDS, MOSAIC_KINDS, HipContext
+from .context import LOG_EPS, LUT3D_SCALE, MOSAIC_BLEND_KINDS, MOSAIC_KINDS, MOSAIC_MEDIAN_KINDS, HipContext
 from .jpeg_options import _check_jpeg_image, checked_options
 from .exports import JpegExport, TiffExport
 from .payload import DEVICE_EXPOSURE, host_stream_gate, stream_rejection
@@ -367,6 +367,9 @@ class HipProcessor:
         entry points; it streams where a plain numeric profile does); a deferred one's highlight mode is resolved with its scale.  Phase 2
         measures the uploaded mosaic's data maximum (r2f_mosaic_maximum), resolves the profile with it and plans the params the
         demosaic runs with; `last_raw_scale` then holds the numbers.  Such a payload takes the one-piece path.
+        A profile with median_passes=n > 0 (LibRaw's med_passes) adds `median` to the step (a step without passes has no such key):
+        n passes of the 3 x 3 median of the colour differences between the interpolation and the highlight blend
+        (r2f_demosaic_median_u16 / _f32, r2f_demosaic_xtrans_median_u16); a Bayer mosaic streams with it where it streams without.
         raw_denoise (a raw2film_amd.raw.WaveletDenoise; rawpy's noise_thr=): the Bayer mosaic is denoised on the device ahead of its
         demosaic (include/r2f.h, r2f_mosaic_denoise; parity with LibRaw's bytes is unpinned, the pull of the two greens, X-Trans
         mosaics and streaming are not built).  The `demosaic` step carries the record under `denoise` (a step without one has no such
@@ -440,7 +443,8 @@ class HipProcessor:
                              **({"orientation": raw_profile.orientation} if raw_profile.orientation else {}),
                              **({"levels": raw_profile} if raw_profile.deferred else {}),
                              **({"denoise": raw_denoise, "profile": raw_profile} if raw_denoise is not None else {}),
-                             **({"clip": raw_profile.blend_clip} if raw_profile.blend_clip is not None else {})}}
+                             **({"clip": raw_profile.blend_clip} if raw_profile.blend_clip is not None else {}),
+                             **({"median": raw_profile.median_passes} if raw_profile.median_passes else {})}}
                if demosaic_params is not None else {}),
         }
 
@@ -1168,7 +1172,10 @@ class HipProcessor:
                 self.last_raw_denoise = {"threshold": denoise.threshold, "maximum": int(maximum), "shift": int(dn.shift)}
                 image = self.ctx.mosaic_denoise(image, dn)
                 params = denoise.shifted(profile, dn.shift).plan(H, W, bool(params.half_size))
-            if clip is None:
+            median = demosaic_step.get("median", 0)
+            if median:  # LibRaw's med_passes: the median entry point of the same demosaic (its clip may be None)
+                demosaic = functools.partial(getattr(self.ctx, MOSAIC_MEDIAN_KINDS[type(params)]), passes=median, clip=clip)
+            elif clip is None:
                 demosaic = getattr(self.ctx, MOSAIC_KINDS[type(params)][0])
             else:  # highlight mode 2: the blend entry point of the same demosaic
                 demosaic = functools.partial(getattr(self.ctx, MOSAIC_BLEND_KINDS[type(params)]), clip=clip)

@@ -68,17 +68,19 @@ def mosaic_rejection(stops, rotate_times, lens, samples, xtrans=False, orientati
     return None
 
 
-def mosaic_upload_bounds(bounds, window, Hm, half_size) -> list:
+def mosaic_upload_bounds(bounds, window, Hm, half_size, median=0) -> list:
     """The mosaic rows that travel with each band of a streamed mosaic: upload k is rows [ub[k], ub[k + 1]), and band k's demosaic
     (r2f_demosaic_f32 of the window's rows [bounds[k], bounds[k + 1])) reads nothing outside [ub[0], ub[k + 1]).  bounds: plan_bands'
     of the window's rows; window: (row0, col0, rows, cols) of the demosaiced frame; Hm: the mosaic's rows.  Full size reaches
     DEMOSAIC_REACH rows past a band's ends, half size reads the two mosaic rows of each output row; rows outside [ub[0], ub[-1])
-    are never uploaded."""
-    row0, rows = int(window[0]), int(window[2])
-    assert bounds[0] == 0 and bounds[-1] == rows
+    are never uploaded.  median: the profile's median_passes n (r2f_demosaic_median_f32: a band edge is no border of step M) --
+    a band then reads the frame n output rows further either side, clipped to the frame: full size DEMOSAIC_REACH + n mosaic rows
+    past its ends, half size the mosaic rows of n more output rows (2 n)."""
+    row0, rows, n = int(window[0]), int(window[2]), int(median)
+    assert bounds[0] == 0 and bounds[-1] == rows and n >= 0
     if half_size:
-        return [2 * (row0 + int(b)) for b in bounds]
-    r = DEMOSAIC_REACH
+        return [2 * max(row0 - n, 0)] + [2 * min(row0 + int(b) + n, Hm // 2) for b in bounds[1:]]
+    r = DEMOSAIC_REACH + n
     return ([max(row0 - r, 0)] + [min(row0 + int(b) + r, Hm) for b in bounds[1:-1]] + [min(row0 + rows + r, Hm)])
 
 

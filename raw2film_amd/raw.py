@@ -17,6 +17,10 @@ and "blend" (2), which normalise by the largest white-balance factor (r2f_raw_sc
 "blend" carries ("blend", clip), the level above which the demosaic blends a pixel's chroma (r2f_demosaic_blend_u16).  The rebuild
 modes 3 .. 9 are not built.
 
+`median_passes` is LibRaw's med_passes (rawpy's median_filter_passes=, dcraw's -m n): 0 .. 4 passes of the 3 x 3 median of the
+colour differences between the interpolation and the highlight blend (include/r2f.h, step M; r2f_demosaic_median_u16).  A keyword
+of both profiles, 0 by default; it is part of equality, hash and repr but no dataclass field (`_median_keyword`).
+
 WaveletDenoise is no part of a profile: it is the record of process(raw_denoise=), LibRaw's wavelet denoise of the Bayer mosaic ahead
 of its demosaic (rawpy's noise_thr=; r2f_mosaic_denoise_plan, r2f_mosaic_denoise).
 """
@@ -56,6 +60,40 @@ def _matrix(matrix, who):
     if any(abs(v) > 64 for row in rows for v in row):
         raise ValueError(f"{who}.matrix entries must lie in [-64, 64], got {matrix!r}")
     return rows
+
+
+def _median_passes(who, n) -> int:
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or not 0 <= n <= _lib.MEDIAN_MAX_PASSES:
+        raise ValueError(f"{who}.median_passes must be an integer in [0, {_lib.MEDIAN_MAX_PASSES}] (LibRaw's med_passes), got {n!r}")
+    return int(n)
+
+
+def _median_keyword(cls):
+    """Give a profile dataclass its `median_passes`: a keyword of the constructor (default 0), validated, part of equality, hash
+    and repr (a profile with 0 passes has the hash and the repr of before), and carried by
+    dataclasses.replace(profile, ..., median_passes=n) -- but NOT a dataclass field: the six fields, their
+    positional order and `orientation` as the last of them are what callers and the cache keys of stored frames were built on, and
+    stay.  So plain dataclasses.replace(profile, ...) drops it like any non-field; `_MosaicProfile._replace` carries it."""
+    init, eq, hash_, repr_ = cls.__init__, cls.__eq__, cls.__hash__, cls.__repr__
+
+    def __init__(self, *args, median_passes=0, **kwargs):
+        object.__setattr__(self, "median_passes", _median_passes(cls.__name__, median_passes))
+        init(self, *args, **kwargs)
+
+    def __eq__(self, other):
+        same = eq(self, other)
+        return same if same is NotImplemented or not same else self.median_passes == other.median_passes
+
+    def __hash__(self):
+        return hash((hash_(self), self.median_passes)) if self.median_passes else hash_(self)
+
+    def __repr__(self):
+        return f"{repr_(self)[:-1]}, median_passes={self.median_passes})" if self.median_passes else repr_(self)
+
+    for fn in (__init__, __eq__, __hash__, __repr__):
+        fn.__qualname__ = f"{cls.__qualname__}.{fn.__name__}"
+        setattr(cls, fn.__name__, fn)
+    return cls
 
 
 @dataclass(frozen=True)
@@ -171,7 +209,7 @@ class WaveletDenoise:
     def shifted(profile, shift: int):
         """The numeric RawProfile the demosaic behind the denoise runs with: black 0 and every multiplier times 2^-shift (exact);
         all else is the profile's, a blend clip level included."""
-        return replace(profile, black=(0.0,) * 4, multipliers=tuple(m * 2.0 ** -int(shift) for m in profile.multipliers))
+        return profile._replace(black=(0.0,) * 4, multipliers=tuple(m * 2.0 ** -int(shift) for m in profile.multipliers))
 
 
 class _MosaicProfile:
@@ -226,6 +264,10 @@ class _MosaicProfile:
             return ("blend", int(h[1]))
         raise ValueError(f"{who}.highlight must be \"clip\" or (\"blend\", clip) with clip an integer in [1, 65535], got {self.highlight!r}")
 
+    def _replace(self, **changes):
+        """dataclasses.replace that carries `median_passes`, which is no field (`_median_keyword`)."""
+        return replace(self, **{"median_passes": self.median_passes, **changes})
+
     @property
     def blend_clip(self):
         """The clip level of a numeric ("blend", clip) profile, which the demosaic blends above (r2f_demosaic_blend_u16); else None."""
@@ -257,7 +299,7 @@ class _MosaicProfile:
             return self, None
         scale, hl = self.multipliers.scale_highlight(self.black, data_maximum, self.highlight)
         highlight = ("blend", int(hl.clip)) if hl.mode == _lib.HIGHLIGHT_BLEND else "clip"
-        return replace(self, multipliers=tuple(scale.mul), highlight=highlight), scale
+        return self._replace(multipliers=tuple(scale.mul), highlight=highlight), scale
 
     def _c_multipliers(self) -> tuple:
         """The multipliers `to_c` states, per site or colour as the profile keeps them: a deferred profile's are those of the
@@ -283,6 +325,7 @@ class _MosaicProfile:
         return out
 
 
+@_median_keyword
 @dataclass(frozen=True)
 class RawProfile(_MosaicProfile):
     """A frozen, hashable record (part of the image cache key, like LensProfile).
@@ -299,7 +342,9 @@ class RawProfile(_MosaicProfile):
     highlight: LibRaw's highlight mode (rawpy's highlight_mode=).  With a RawLevels: "clip" (0), "unclip" (1: normalised by the
         largest white-balance factor, so nothing is cut below the sensor's saturation) or "blend" (2: unclip, and pixels with a
         channel above the clip level take the chroma of their clipped version).  With numeric multipliers: "clip", or ("blend",
-        clip) as `resolve` of a "blend" profile yields it (`blend_clip`).  The rebuild modes 3 .. 9 are not built."""
+        clip) as `resolve` of a "blend" profile yields it (`blend_clip`).  The rebuild modes 3 .. 9 are not built.
+    median_passes (keyword): LibRaw's med_passes, an int in 0 .. 4 (0: none): that many passes of the 3 x 3 median of R - G and
+        B - G over the demosaiced frame, between the interpolation and the highlight blend (r2f_demosaic_median_u16)."""
     pattern: str = "RGGB"
     black: tuple | float = 0
     multipliers: tuple | RawLevels = (1.0, 1.0, 1.0)
@@ -333,6 +378,7 @@ class RawProfile(_MosaicProfile):
 XTRANS = ("GBGGRG", "RGRBGB", "GBGGRG", "GRGGBG", "BGBRGR", "GRGGBG")  # the canonical layout; a camera's is one of its 36 cyclic shifts
 
 
+@_median_keyword
 @dataclass(frozen=True)
 class XTransProfile(_MosaicProfile):
     """What a RAW file's parser knows of a frame with a 6 x 6 colour filter array (Fujifilm's X-Trans), for the demosaic on the
@@ -348,6 +394,7 @@ class XTransProfile(_MosaicProfile):
     matrix: 3 x 3, rows are the output channels; |entries| <= 64.
     orientation: 0 .. 7, LibRaw's sizes.flip bits, as RawProfile's (r2f_demosaic_xtrans_oriented_u16).
     highlight: LibRaw's highlight mode, as RawProfile's (r2f_demosaic_xtrans_blend_u16).
+    median_passes (keyword): LibRaw's med_passes, as RawProfile's (r2f_demosaic_xtrans_median_u16).
     half_size=True yields A THIRD of the mosaic's sides (the 3 x 3 cells of the array), not a half: `reduction`."""
     pattern: tuple | str = XTRANS
     black: tuple | float = 0
