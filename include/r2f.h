@@ -974,6 +974,69 @@ R2F_API int r2f_mosaic_denoise_level(r2f_ctx* ctx, int level, const uint16_t* sr
                      const r2f_denoise_params* params, uint16_t* dst, int64_t dst_pitch, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* The repair of hot pixels of a mosaic on the device, ahead of everything else that reads it (the data maximum, the denoise, either
+ * demosaic).  This is the project's OWN rule, as the X-Trans interpolation is: it is NOT LibRaw's bad_pixels, which takes a caller's
+ * coordinate list and works sequentially and in place (not built; nor are a repair fused into the demosaic's staging, streaming for
+ * the profiles that do not stream, and dark-frame subtraction).  tests/repair_model.py restates it in NumPy.
+ *
+ * Inputs.  The mosaic, uint16 (H, W), H and W at least 6; P its period, 2 for a Bayer array and 6 for an X-Trans array; phase(y, x) =
+ * (y % P) * P + x % P; black[P * P] (int32, each in [0, 65535]), the profile's table; a threshold in [0, 65535], in black-subtracted
+ * raw units; q in [1, 255], a ratio in 1/256ths; min_neighbours, 3 or 4.
+ *   N. Every sample has four neighbours, each of its own colour.
+ *        Bayer: (dy, dx) = (-2, 0), (0, 2), (2, 0), (0, -2): the same site of the quad, so the same black level, and the same green of
+ *        the two.
+ *        X-Trans: one per quadrant d = up, right, down, left.  The candidates of ring r = 1, 2 are (-r, a), (a, r), (r, -a), (-a, -r)
+ *        for the four quadrants, with the lateral offset a in the order 0, 1, -1, 2 over -r < a <= r: the eight sites of ring 1 and the
+ *        sixteen of ring 2 belong to exactly one quadrant each.  The neighbour is the first candidate of the sample's colour, ring 1
+ *        before ring 2, with the pattern taken cyclically.  The planner tables them per phase and refuses a pattern that has a phase
+ *        and quadrant without one inside ring 2 (Fujifilm's canonical pattern and its 36 cyclic shifts have four distinct neighbours
+ *        at every phase).
+ *   T. t(y, x) = max((int)raw(y, x) - black[phase(y, x)], 0).
+ *   H. A neighbour k is BELOW its centre when q * t_centre > 256 * t_k (both products stay under 2^24).  The centre is hot when
+ *      t_centre > threshold and at least min_neighbours of its four neighbours are below it; then
+ *        out = clamp(max{t_k : k below} + black[phase of the centre], 0, 65535),
+ *      and out = raw, untouched bit for bit, for every other sample.  A sample with any neighbour outside the frame is never hot (for
+ *      Bayer that is the 2-sample ring).
+ * Every output is a function of raw within 2 samples of it, and no pass reads what it writes.
+ * The params hold one period, 6: a 2 x 2 table is widened by the planner (6 is a multiple of 2, every site keeps its level and its
+ * neighbours). */
+typedef struct r2f_repair_params {
+    int32_t period;            /* 2 or 6, as the caller stated it */
+    int32_t black[36];         /* per phase (y % 6) * 6 + x % 6 */
+    int8_t offset[36][4][2];   /* per phase and quadrant (up, right, down, left): (dy, dx), each within 2 samples */
+    int32_t threshold, q, min_neighbours;
+} r2f_repair_params;
+/* Host planner (raw2film_amd/csrc/r2f_repair_plan.cpp; no GPU, no context).  cfa: 36 colour ids of the 6 x 6 pattern for period 6
+ * (ignored, and may be null, for period 2); black: period * period levels as a profile states them (doubles, integral, in [0, 65535]).
+ * R2F_EINVAL for a null pointer, a period other than 2 or 6, a black level outside its range (a NaN is outside every range), a
+ * threshold outside [0, 65535], q outside [1, 255], min_neighbours other than 3 or 4, H or W below 6, a colour id outside {0, 1, 2}
+ * and a pattern with a phase and quadrant that has no neighbour inside ring 2; a refusal leaves *out alone. */
+R2F_API int r2f_mosaic_repair_plan(int period, const int32_t* cfa, const double* black, int threshold, int q, int min_neighbours, int H,
+                     int W, r2f_repair_params* out);
+/* Steps N, T and H of mosaic rows [y0, y1) on the device, with the mosaic entry points' row-range contract.  src_rows: uint16 mosaic
+ * rows [src_gy0, src_gy0 + src_nrows) of the H x W frame, src_pitch samples apart (>= W); dst: an H-row mosaic, row 0 at dst, rows
+ * dst_pitch samples apart (>= W).  Writes the W samples of rows [y0, y1) of dst and nothing else; reads rows [y0 - 2, y1 + 2) clipped
+ * to the frame, which must lie inside the source window, else R2F_EINVAL before any launch.  The bytes of a band are those of the same
+ * rows of a whole-frame call, whatever the cut, the pitches and the source's alignment; y0 == y1 is R2F_OK with no launch.
+ * count: null, or a device uint32 to which the call ADDS the number of samples it replaced in [y0, y1), with one atomic per block at
+ * most (a block that replaced none does not touch it).
+ * Refused: null pointers (count aside), H or W below 6, pitches below W, y0 > y1, y0 < 0, y1 > H, the rows read or the rows written of
+ * src and dst sharing bytes, and params the planner would not have produced.
+ * One launch of a resident grid shaped like r2f_mosaic_maximum's: a block walks groups of R2F_MOSAIC_REPAIR_ROWS rows, a wave per
+ * row; a lane loads and stores R2F_MOSAIC_REPAIR_VEC samples at a time (16 bytes) behind the up to 7 samples that lead to a 16-byte
+ * boundary of the SOURCE row and ahead of the up to 7 that trail (a destination row that is not aligned the same way takes narrower
+ * stores of the same samples).  Step T and the threshold test run on packed 16-bit pairs; only a sample whose t exceeds the
+ * threshold fetches its four neighbours, as 16-bit loads that the cache serves: the rows above and below are rows that the waves
+ * next to this one stream through the same L2 at the same time, so a launch moves 2 bytes in and 2 bytes out per sample across the
+ * memory bus by design, and the gathers add 8 bytes of cache traffic per candidate.  No LDS staging of rows: the candidates are
+ * sparse wherever the step is of use (a threshold below the signal makes every sample a candidate, and the kernel then runs at the
+ * cache's rate; the result is the same).  Two instances: period 2 with its offsets as compile-time constants, period 6 with the
+ * offset table in LDS; both keep the 36 levels in LDS. */
+R2F_API int r2f_mosaic_repair(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
+                     const r2f_repair_params* params, uint16_t* dst, int64_t dst_pitch, int y0, int y1, uint32_t* count, void* stream);
+/* r2f_mosaic_repair's widest access in samples and the rows a block walks per step (test shapes are derived from them). */
+enum { R2F_MOSAIC_REPAIR_VEC = 8, R2F_MOSAIC_REPAIR_ROWS = 4 };
+
 /* The hand-off from RAW decoding: the last two lines of raw_to_linear (raw_conversion.py:50-52) applied to LibRaw's 16-bit
  * output on the device, so that a decoded frame crosses PCIe as uint16 (6 bytes per pixel) instead of float32 (12 or 16):
  * dst = float(src) / divisor (65535, one correctly rounded fp32 division) * factor (the float32 of 2 ** calc_exposure(...),

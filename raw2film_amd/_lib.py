@@ -21,6 +21,7 @@ CFA_RGGB, CFA_BGGR, CFA_GRBG, CFA_GBRG = 0, 1, 2, 3
 DEMOSAIC_TILE_W, DEMOSAIC_TILE_H = 64, 32  # R2F_DEMOSAIC_TILE_*
 XTRANS_TILE_W, XTRANS_TILE_H = 64, 32  # R2F_XTRANS_TILE_*
 MOSAIC_MAX_VEC, MOSAIC_MAX_ROWS = 8, 4  # R2F_MOSAIC_MAX_*
+MOSAIC_REPAIR_VEC, MOSAIC_REPAIR_ROWS = 8, 4  # R2F_MOSAIC_REPAIR_*
 DENOISE_TILE_W, DENOISE_TILE_H = 64, 32  # R2F_DENOISE_TILE_*
 KERNEL_HALATION, KERNEL_MTF, KERNEL_GRAIN = 0, 1, 2
 F_MATRIX, F_HALATION, F_MTF, F_GRAIN, F_GRAIN_MONO, F_BURN, F_IDENTITY_DONE, F_FRAME_RESIDENT = 1, 2, 4, 8, 16, 32, 64, 128
@@ -138,6 +139,11 @@ class Highlight(C.Structure):  # r2f_highlight: the highlight mode a scale was p
 
 class DenoiseParams(C.Structure):  # r2f_denoise_params (raw2film_amd.raw.WaveletDenoise.plan fills it)
     _fields_ = [("black", C.c_int32 * 4), ("shift", C.c_int32), ("threshold", C.c_float)]
+
+
+class RepairParams(C.Structure):  # r2f_repair_params (raw2film_amd.raw.HotPixels.plan fills it)
+    _fields_ = [("period", C.c_int32), ("black", C.c_int32 * 36), ("offset", C.c_int8 * 2 * 4 * 36), ("threshold", C.c_int32),
+                ("q", C.c_int32), ("min_neighbours", C.c_int32)]
 
 
 HIGHLIGHT_CLIP, HIGHLIGHT_UNCLIP, HIGHLIGHT_BLEND = 0, 1, 2  # R2F_HIGHLIGHT_*: LibRaw's highlight modes 0, 1 and 2
@@ -311,6 +317,15 @@ _SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, _P(DenoiseParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t,
          C.c_void_p],
+    ),
+    "r2f_mosaic_repair_plan": (
+        C.c_int,
+        [C.c_int, _P(C.c_int32), _P(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(RepairParams)],
+    ),
+    "r2f_mosaic_repair": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(RepairParams), C.c_void_p, C.c_int64, C.c_int, C.c_int,
+         C.c_void_p, C.c_void_p],
     ),
     "r2f_resize_lanczos4_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "r2f_lanczos4_table": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

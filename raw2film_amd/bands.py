@@ -10,7 +10,7 @@ from __future__ import annotations
 from typing import Callable, NamedTuple
 
 from . import _lib
-from .payload import DEVICE_EXPOSURE, frame_shape, mosaic_upload_bounds
+from .payload import DEVICE_EXPOSURE, REPAIR_REACH, frame_shape, mosaic_upload_bounds
 
 
 def plan_bands(H, flags, ha, ma, bands, taper):
@@ -80,8 +80,9 @@ class StreamedFrame(NamedTuple):
     mtf_reach: tuple
 
 
-def band_source(payload, shape, dtype) -> BandSource:
-    """The BandSource of a payload that stream_rejection has passed.  `shape`, `dtype`: of its tensor, as stream_rejection takes them."""
+def band_source(payload, shape, dtype, repair_count=None) -> BandSource:
+    """The BandSource of a payload that stream_rejection has passed.  `shape`, `dtype`: of its tensor, as stream_rejection takes them.
+    repair_count: for a mosaic with a `repair` step, the device word its bands add their repaired samples to (None: not counted)."""
     shape = tuple(int(v) for v in shape)
     frame = frame_shape(payload, shape)
     if dtype != "torch.int16":  # a float frame lands where the pipeline reads it
@@ -95,7 +96,23 @@ def band_source(payload, shape, dtype) -> BandSource:
     if step:  # a Bayer mosaic: band k travels with the mosaic rows its demosaic reads beyond those of the bands before it
         window, params, clip, median = step["window"], step["params"], step.get("clip"), step.get("median", 0)
 
+        repair, half, rows = step.get("repair"), bool(params.half_size), int(window[2])
+        if repair is not None:
+            repair_params = repair.plan(step["profile"], shape[0], shape[1])
+            repaired_to = []  # [the mosaic row up to which the bands so far have repaired] (they come in order)
+
+        def repaired(ctx, landing, a1):
+            """The context's second mosaic, repaired as far as the demosaic of the window's rows [0, a1) reads: this band adds the
+            mosaic rows that no band before it repaired, so every row is repaired exactly once (upload k brought REPAIR_REACH more
+            rows than the demosaic reads: what the repair of its last rows reads)."""
+            lo, hi = mosaic_upload_bounds([0, a1] if a1 == rows else [0, a1, rows], window, shape[0], half, median)[:2]
+            done = repaired_to.pop() if repaired_to else lo
+            repaired_to.append(max(hi, done))
+            return ctx.mosaic_repair(landing, repair_params, rows=(done, repaired_to[0]), count=repair_count)
+
         def demosaic(ctx, landing, image, a0, a1):
+            if repair is not None:
+                landing = repaired(ctx, landing, a1)
             if median:  # a profile with median_passes: step M reads `median` output rows past the band's ends
                 ctx.demosaic_median_f32(landing, params, median, factor, clip=clip, window=window, out=image, rows=(a0, a1))
             elif clip is None:
@@ -107,7 +124,8 @@ def band_source(payload, shape, dtype) -> BandSource:
         # the pace; with upload k queued only when band k's turn came the call was no faster than in one piece (100 MP: 15.9 against
         # 15.8 ms, profiles/r17_mosaic_stream_probe.txt).
         return BandSource(frame, landing="mosaic", landing_shape=shape, queue_all=True, measure=None, decode=demosaic,
-                          upload_bounds=lambda bounds: mosaic_upload_bounds(bounds, window, shape[0], bool(params.half_size), median))
+                          upload_bounds=lambda bounds: mosaic_upload_bounds(bounds, window, shape[0], half, median,
+                                                                            REPAIR_REACH if repair is not None else 0))
     if factor == DEVICE_EXPOSURE:
         # the whole uint16 frame goes up (the statistic is the whole frame's), the bands are rows of its window: band k travels as the
         # frame rows ub[k]:ub[k + 1], the first and the last taking the rows above and below the window along

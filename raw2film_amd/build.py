@@ -15,8 +15,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libr2f_hip.so")
 SOURCES = ["r2f_kernels.hip", "r2f_fft.hip", "r2f_front.hip", "r2f_post.hip", "r2f_resample.hip", "r2f_lens.hip", "r2f_api.hip", "r2f_stencil.hip", "r2f_graph.hip", "r2f_jpeg_api.hip", "r2f_plan.cpp", "r2f_jpeg.hip", "r2f_jpeg_prog.hip", "r2f_jpeg_plan.cpp", "r2f_tiff_plan.cpp", "r2f_lens_plan.cpp", "r2f_demosaic.hip", "r2f_demosaic_plan.cpp", "r2f_xtrans.hip", "r2f_xtrans_plan.cpp", "r2f_mosaic_stats.hip", "r2f_levels_plan.cpp", "r2f_mosaic_denoise.hip",
-           "r2f_denoise_plan.cpp"]
-HEADERS = ["r2f_device.h", "r2f_launch.h", "r2f_fft_math.h", "r2f_ctx.h", "r2f_plan.h", "r2f_jpeg.h", "r2f_jpeg_plan.h", "r2f_lens_math.h", "r2f_demosaic_math.h", "r2f_xtrans_math.h", "r2f_mosaic_math.h", "r2f_median_math.h", "r2f_mosaic_plan.h", "r2f_mosaic_stage.h", "r2f_denoise_math.h", os.path.join("..", "..", "include", "r2f.h")]
+           "r2f_denoise_plan.cpp", "r2f_mosaic_repair.hip", "r2f_repair_plan.cpp"]
+HEADERS = ["r2f_device.h", "r2f_launch.h", "r2f_fft_math.h", "r2f_ctx.h", "r2f_plan.h", "r2f_jpeg.h", "r2f_jpeg_plan.h", "r2f_lens_math.h", "r2f_demosaic_math.h", "r2f_xtrans_math.h", "r2f_mosaic_math.h", "r2f_median_math.h", "r2f_mosaic_plan.h", "r2f_mosaic_stage.h", "r2f_denoise_math.h", "r2f_repair_math.h", os.path.join("..", "..", "include", "r2f.h")]
 ARCH = "gfx950"
 EXPORTS_MAP = os.path.join(CSRC, "r2f_exports.map")  # only the r2f_* entry points of include/r2f.h stay dynamic
 

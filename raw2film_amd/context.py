@@ -51,6 +51,7 @@ class HipContext:
         self._h = handle
         self._workspace = None
         self._denoise_workspace = None  # mosaic_denoise's, apart from the render's: growing it moves no buffer a captured frame holds
+        self._repair_mosaic = None  # mosaic_repair's second mosaic, kept for the next mosaic of its size
 
     # ------------------------------------------------------------------ plumbing
     def close(self):
@@ -778,6 +779,42 @@ class HipContext:
             ws = self._denoise_workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self._check(self._lib.r2f_mosaic_denoise(self._h, mosaic.data_ptr(), int(mosaic.stride(0)), H, W, C.byref(params), out.data_ptr(),
                                                  int(out.stride(0)), ws.data_ptr(), int(ws.numel()), self._stream()))
+        return out
+
+    def mosaic_repair(self, mosaic, params, rows=None, count=None, out=None):
+        """The hot-pixel repair of include/r2f.h (r2f_mosaic_repair: the project's own rule, ahead of everything else that reads the
+        mosaic) of a uint16 (H, W) CUDA mosaic of at least 6 x 6 samples (int16 tensors are read as the same bits; rows may be
+        pitched) -> the repaired mosaic, of the mosaic's dtype.
+        params: the r2f_repair_params of raw2film_amd.raw.HotPixels.plan.
+        rows = (y0, y1): only those mosaic rows are written (default: all); the call reads rows [y0 - 2, y1 + 2) of `mosaic`, clipped
+        to the frame.
+        count: a one-element int32 or uint32 CUDA tensor to which the call ADDS the number of samples it replaced in its rows (the
+        caller zeroes it; nothing is read back or waited for); None: not counted.
+        out: a uint16 or int16 (H, W) CUDA tensor with contiguous samples along a row to write into (rows may be pitched), which
+        must not share bytes with the mosaic; None: the second mosaic is a buffer the context keeps and reuses for mosaics of this
+        size -- the next call with out=None overwrites it, and row-range calls fill it band by band."""
+        torch = self._torch
+        if not isinstance(params, _lib.RepairParams):
+            raise ValueError(f"mosaic_repair: params must be the r2f_repair_params of HotPixels.plan, got {type(params).__name__}")
+        H, W = self._mosaic_size(mosaic, "mosaic_repair", 6)
+        if out is None:
+            out = self._repair_mosaic
+            if out is None or tuple(out.shape) != (H, W) or out.dtype != mosaic.dtype:
+                self._repair_mosaic = None
+                out = self._repair_mosaic = torch.empty((H, W), dtype=mosaic.dtype, device=self.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype in (torch.uint16, torch.int16) and tuple(out.shape) == (H, W)
+                  and out.stride(1) == 1 and out.stride(0) >= W):
+            raise ValueError(f"mosaic_repair: out must be a uint16 CUDA tensor of shape {(H, W)} with contiguous rows")
+        else:
+            self._same_device(out, "out")
+        if count is not None:
+            if not (isinstance(count, torch.Tensor) and count.is_cuda and count.dtype in (torch.int32, torch.uint32) and count.numel() == 1):
+                raise ValueError("mosaic_repair: count must be a one-element int32 or uint32 CUDA tensor")
+            self._same_device(count, "count")
+        y0, y1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
+        self._check(self._lib.r2f_mosaic_repair(self._h, mosaic.data_ptr(), 0, H, int(mosaic.stride(0)), H, W, C.byref(params),
+                                                out.data_ptr(), int(out.stride(0)), y0, y1,
+                                                None if count is None else count.data_ptr(), self._stream()))
         return out
 
     def decode_u16(self, image_u16, factor: float, divisor: float = 65535.0, out=None):

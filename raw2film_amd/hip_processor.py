@@ -136,6 +136,7 @@ class HipProcessor:
     payload_alpha = True
     profile_stages = False  # settable: process() then times its stages into `last_stage_ms` (see there)
     _texture = _texture_src = image_param_dict = None  # the frame cache, empty
+    _raw_repair = None
 
     def __init__(self, cameras=None, lenses=None, device: int = 0, payload_alpha: bool = True, result_buffers: int = 0,
                  lib_path: str | None = None):
@@ -182,6 +183,9 @@ class HipProcessor:
         # what the wavelet denoise of that frame's mosaic ran with ({"threshold", "maximum", "shift"}: raw_denoise), kept with a cached
         # frame like the scale; None when the call had no raw_denoise
         self.last_raw_denoise = None
+        # what the hot-pixel repair of that frame's mosaic ran with and did ({"threshold", "q", "min_neighbours", "repaired"}:
+        # raw_repair; the property `last_raw_repair`), kept with a cached frame like the scale; None when the call had no raw_repair
+        self._raw_repair = None
         self.last_stage_ms = None  # process()'s wall clock per stage with `profile_stages` on (bench.py's host_device_copies)
         self._load_stage_ms = None  # ... load_image_texture's share of it, until process() folds it in
         # the frame cache (load_image_texture): (frame, layout, payload geometry) kept on the device, a weak reference to its array, its load parameters
@@ -331,7 +335,7 @@ class HipProcessor:
                                rotation=0.0, zoom=1.0, rotate_times=0, flip=False, resolution=None, half_size=True,
                                cache=True, chroma_nr=0, max_scale=400.0, canvas_mode="No", canvas_scale=1.0,
                                canvas_ratio=1.0, exposure=None, metadata=None, lens_profile=None, raw_profile=None, raw_denoise=None,
-                               **kwargs):
+                               raw_repair=None, **kwargs):
         """PHASE 1 of the two-phase batch API (gpu_processor.py:715-783): pure host work, touches
         no instance state.  Returns the same payload dict; `image_array` is (H, W, 4) float32 ((H, W, 3) with payload_alpha=False).
         exposure="device" (a uint16 frame): no pass over the frame here.  `image_array` is then the WHOLE decoded frame -- the caller's
@@ -376,7 +380,12 @@ class HipProcessor:
         key).  Phase 2 measures and resolves a deferred profile on the UNdenoised mosaic first, denoises with the record's maximum
         (None: the resolved scale's `maximum_used`), then demosaics with black 0 and the multipliers times 2^-shift;
         `last_raw_denoise` holds {"threshold", "maximum", "shift"}.  ValueError without a raw_profile, with an XTransProfile, with
-        maximum=None on a numeric profile, and for a mosaic with an odd side or a side below 64.  The one-piece path."""
+        maximum=None on a numeric profile, and for a mosaic with an odd side or a side below 64.  The one-piece path.
+        raw_repair (a raw2film_amd.raw.HotPixels): hot pixels of the mosaic, Bayer or X-Trans, are repaired on the device ahead of
+        everything else that reads it -- the data maximum of a deferred profile, the denoise, the demosaic -- by the project's own
+        rule (include/r2f.h, r2f_mosaic_repair; not LibRaw's bad_pixels).  The `demosaic` step carries the record under `repair` (a
+        step without one has no such key).  It changes no gate: a mosaic that streams streams with it, each band travelling with 2
+        more mosaic rows (payload.mosaic_upload_bounds(repair=2)).  ValueError without a raw_profile and for a mosaic below 6 x 6."""
         on_device = exposure_on_device(exposure)
         phase1.check_profiles(raw_profile, lens_profile, lens_correction, cam, lens)
         # _internal (load_image_texture: the payload never leaves this object): no alpha plane, and the clamp of
@@ -386,6 +395,7 @@ class HipProcessor:
         rows, cols, is_u16 = image.shape[0], image.shape[1], image.dtype == np.uint16
         demosaic_params = lens_params = lens_projection = lens_tca = None
         phase1.check_denoise(raw_denoise, raw_profile, rows, cols)
+        phase1.check_repair(raw_repair, raw_profile, rows, cols)
         if raw_profile is not None:  # the crops are those of the demosaiced frame, which is uint16
             demosaic_params = raw_profile.plan(rows, cols, half_size)
             rows, cols = raw_profile.oriented_shape(rows, cols, half_size)  # (the params' out_h, out_w, the way round the sensor was held)
@@ -443,6 +453,7 @@ class HipProcessor:
                              **({"orientation": raw_profile.orientation} if raw_profile.orientation else {}),
                              **({"levels": raw_profile} if raw_profile.deferred else {}),
                              **({"denoise": raw_denoise, "profile": raw_profile} if raw_denoise is not None else {}),
+                             **({"repair": raw_repair, "profile": raw_profile} if raw_repair is not None else {}),
                              **({"clip": raw_profile.blend_clip} if raw_profile.blend_clip is not None else {}),
                              **({"median": raw_profile.median_passes} if raw_profile.median_passes else {})}}
                if demosaic_params is not None else {}),
@@ -459,7 +470,7 @@ class HipProcessor:
                 sharpness=True, sharpening_strength=0.0, sharpening_sigma=1.0, chroma_nr=0, grain=2,
                 highlight_burn=0.0, burn_scale=50.0, half_size=True, cache=True, color_masking=None, max_scale=400.0,
                 seed=None, exposure=None, metadata=None, src_version=None, output_bits=8, lens_profile=None, raw_profile=None,
-                raw_denoise=None, **_):
+                raw_denoise=None, raw_repair=None, **_):
         """Load (decoded) frame and render it: np.uint8 (H, W, 3), like cpu_processor.py:414 -- including the CPU processor's
         last step, resolution_scaling of the finished (canvas-framed) frame to the requested resolution (cpu_processor.py:411-412).
         With `dst_texture` (a uint8 (h, w, 4) CUDA tensor standing in for the preview widget's wgpu texture) the call behaves
@@ -494,11 +505,16 @@ class HipProcessor:
         parity unpinned; `last_raw_scale` holds the numbers, a cached frame keeps them.  Such a mosaic is demosaiced whole too.
         raw_denoise (raw2film_amd.raw.WaveletDenoise; rawpy's noise_thr=): the Bayer mosaic is denoised on the device ahead of the
         demosaic (extract_image_data_cpu; r2f_mosaic_denoise), in one piece; `last_raw_denoise` holds the threshold, the maximum
-        and the shift it ran with, and a cached frame keeps them."""
+        and the shift it ran with, and a cached frame keeps them.
+        raw_repair (raw2film_amd.raw.HotPixels): hot pixels of the mosaic are repaired on the device first of all, ahead of the data
+        maximum, the denoise and the demosaic, which then run unchanged on the repaired mosaic (extract_image_data_cpu;
+        r2f_mosaic_repair: the project's own rule, not LibRaw's bad_pixels).  It needs a raw_profile, of either kind, and changes no
+        gate: a mosaic that streams streams with it.  `last_raw_repair` holds the threshold, q, min_neighbours and the number of
+        samples repaired (read back from the device when the attribute is read); a cached frame keeps them."""
         settings = dict(locals())  # every keyword of the signature (the unknown ones in `_` aside), named nowhere else
         exposure_on_device(exposure)  # (any string but "device" raises before any work starts)
         settings["output_bits"] = check_output_bits(output_bits, dst_texture)
-        self.exposure_rejected = self.last_raw_scale = self.last_raw_denoise = None
+        self.exposure_rejected = self.last_raw_scale = self.last_raw_denoise = self.last_raw_repair = None
         for k in _PROCESS_POSITIONAL:
             del settings[k]
         # load_image_texture's share; prepare() and the render take what they need of all of them and swallow the rest
@@ -530,6 +546,7 @@ class HipProcessor:
         image, layout, payload = self._texture
         self.last_raw_scale = payload.get("raw_scale")  # (the frame's own: a cached frame was not measured again)
         self.last_raw_denoise = payload.get("raw_denoise")
+        self.last_raw_repair = payload.get("raw_repair")
         if prof:
             self._torch.cuda.synchronize(self.device)
             t_loaded = time.perf_counter()
@@ -550,7 +567,7 @@ class HipProcessor:
     def load_image_texture(self, src, cam=None, lens=None, lens_correction=True, frame_width=36, frame_height=24, rotation=0.0,
                            zoom=1.0, rotate_times=0, flip=False, resolution=None, half_size=True, cache=True, chroma_nr=0,
                            max_scale=400.0, canvas_mode="No", canvas_scale=1.0, canvas_ratio=1.0, exposure=None, metadata=None,
-                           src_version=None, lens_profile=None, raw_profile=None, raw_denoise=None):
+                           src_version=None, lens_profile=None, raw_profile=None, raw_denoise=None, raw_repair=None):
         """GpuProcessor.load_image_texture (gpu_processor.py:655-719): prepare and upload the frame unless the load parameters
         are those of the frame that is already on the device.  A path compares by value like upstream's `src`.  An array
         compares by identity AND by a fingerprint of its content (shape, dtype, address, a checksum of up to 32 evenly spaced
@@ -622,12 +639,12 @@ class HipProcessor:
     def prepare_gpu_textures(self, cpu_payload):
         """PHASE 2's stateful half (gpu_processor.py:785-790): upload the payload's frame and run the device pre-path on it
         (uint16 conversion, free rotation, chroma NR, preview scaling); the result is the frame the pipeline reads."""
-        self.last_raw_scale = self.last_raw_denoise = None
+        self.last_raw_scale = self.last_raw_denoise = self.last_raw_repair = None
         image, layout = self._upload_payload(cpu_payload)
         # (what is kept next to the device frame is the payload's geometry, not its host frame: the processor must not keep a
         # 1.2 GB decode buffer alive; and the scale a deferred profile resolved to, which belongs to this frame: `raw_scale`)
         self._texture = (image, layout, {**{k: v for k, v in cpu_payload.items() if k != "image_array"}, "raw_scale": self.last_raw_scale,
-                                         "raw_denoise": self.last_raw_denoise})
+                                         "raw_denoise": self.last_raw_denoise, "raw_repair": self._raw_repair})
         self.image_param_dict = None  # (a payload from outside: no load parameters to compare the next process() with)
         self._texture_src = None
 
@@ -675,7 +692,7 @@ class HipProcessor:
         "cpu" -- like CpuProcessor.process (cpu_processor.py:411-412), the finished frame, canvas included, is scaled to the
         requested resolution (INTER_AREA down, LANCZOS4 up).  dst_texture / histogram_texture, output_bits: see process()."""
         check_output_bits(settings.get("output_bits", 8), dst_texture)
-        self.exposure_rejected = self.last_raw_scale = self.last_raw_denoise = None
+        self.exposure_rejected = self.last_raw_scale = self.last_raw_denoise = self.last_raw_repair = None
         if dst_texture is None and histogram_texture is None and self.stream_bands > 1:
             res = self._stream_payload(cpu_payload, negative_film, grain_size, grain_sigma, final_scaling, **settings)
             if res is not None:  # a large frame without a device pre-path: through the pipeline in row bands while it arrives
@@ -761,7 +778,7 @@ class HipProcessor:
         textures, and with stream=True the format's reasons, the processor's `stream_bands`, the payload's.  Then the row-band
         path into fmt.sink where nothing refused it, else the one-piece render into fmt.whole."""
         what = f"process_{fmt.name}" if payload is None else f"process_preloaded_{fmt.name}"
-        self.exposure_rejected = self.stream_rejected = self.last_raw_scale = self.last_raw_denoise = None
+        self.exposure_rejected = self.stream_rejected = self.last_raw_scale = self.last_raw_denoise = self.last_raw_repair = None
         self._refuse_textures(what, settings, " (use process() for the preview)" if payload is None else "")
         early = next((why for why in fmt.early if why), None) if stream else None
         if payload is None:
@@ -928,7 +945,8 @@ class HipProcessor:
         if self.stream_rejected is not None:
             return None
         self.exposure_rejected = payload.get("exposure_rejected")
-        source = band_source(payload, tuple(host.shape), str(host.dtype))
+        repair = (payload.get("demosaic") or {}).get("repair")  # (every band's repair adds to the frame's count word: bands.band_source)
+        source = band_source(payload, tuple(host.shape), str(host.dtype), None if repair is None else self._begin_repair_record(repair))
         H, W = source.frame[:2]
         params = self.prepare(negative_film, grain_size, grain_sigma, (W, H), **settings)
         hal, mtf = bool(params.flags & _lib.F_HALATION), bool(params.flags & _lib.F_MTF)
@@ -1092,7 +1110,7 @@ class HipProcessor:
         reference's queue.write_texture / read_texture pair serialises."""
         check_output_bits(settings.get("output_bits", 8))
         torch = self._torch
-        self.exposure_rejected = self.last_raw_scale = self.last_raw_denoise = None
+        self.exposure_rejected = self.last_raw_scale = self.last_raw_denoise = self.last_raw_repair = None
         src = cpu_payload.get("image_array")
         if self.stream_bands > 1 and not (isinstance(src, torch.Tensor) and (src.is_cuda or src.is_pinned())):
             # a large frame in ordinary (pageable) host memory: its copy blocks this thread, so nothing of the next frame's host work
@@ -1153,6 +1171,11 @@ class HipProcessor:
             params = demosaic_step["params"]
             image = image.contiguous()
             deferred, clip = demosaic_step.get("levels"), demosaic_step.get("clip")
+            repair = demosaic_step.get("repair")
+            if repair is not None:
+                # ahead of everything else that reads the mosaic: the measurement, the denoise and the demosaic below run unchanged,
+                # on the second mosaic the context keeps
+                image = self._repair_mosaic(image, repair, demosaic_step["profile"])
             if deferred is not None:
                 # the scale is the frame's own: the whole uploaded mosaic's data maximum (one read of it, 4 bytes back, the one
                 # synchronisation of this path), LibRaw's rule on it, and the params planned again with the resolved numbers
@@ -1268,6 +1291,33 @@ class HipProcessor:
                 out = depth.resize_area(out.contiguous(), *size)
         self.last_output = out
         return out
+
+    def _begin_repair_record(self, repair):
+        """Begin the frame's `last_raw_repair` -> the device word, at 0, to which its repair adds the samples it replaces."""
+        count = self._torch.zeros(1, dtype=self._torch.int32, device=self.device)
+        self._raw_repair = {"threshold": repair.threshold, "q": repair.q, "min_neighbours": repair.min_neighbours, "repaired": count}
+        return count
+
+    def _repair_mosaic(self, mosaic, repair, profile):
+        """process(raw_repair=)'s device step in one piece: r2f_mosaic_repair of `mosaic` into the context's second mosaic, which is
+        returned."""
+        params = repair.plan(profile, int(mosaic.shape[0]), int(mosaic.shape[1]))
+        return self.ctx.mosaic_repair(mosaic, params, count=self._begin_repair_record(repair))
+
+    @property
+    def last_raw_repair(self):
+        """What the hot-pixel repair of the frame rendered last ran with and did: {"threshold", "q", "min_neighbours", "repaired"},
+        or None when the call had no raw_repair.  `repaired`, the number of samples replaced, is counted on the device and read back
+        by the first look at this attribute (4 bytes; it waits for the repair, not for the render): nothing on the render path
+        waits for it.  A cached frame keeps its record."""
+        record = self._raw_repair
+        if record is not None and not isinstance(record["repaired"], int):
+            record["repaired"] = int(record["repaired"].item())
+        return record
+
+    @last_raw_repair.setter
+    def last_raw_repair(self, record):
+        self._raw_repair = record
 
     def _collect_auto_exposure(self, now=False):
         """exposure="device": once the frame is queued, the stops the device measured come back into `last_auto_exposure` (the wait

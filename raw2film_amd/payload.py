@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib, geometry
 from .lens import LensProfile
-from .raw import RawProfile, WaveletDenoise, XTransProfile
+from .raw import HotPixels, RawProfile, WaveletDenoise, XTransProfile
 
 _DEMOSAIC_REJECTED = "the demosaic step (raw_profile): "  # every refusal of a mosaic begins with it, then says why
 _LENS_REJECTED = "the lens step (lens_profile): its gather reads the whole frame, which a row band does not hold"
@@ -68,20 +68,27 @@ def mosaic_rejection(stops, rotate_times, lens, samples, xtrans=False, orientati
     return None
 
 
-def mosaic_upload_bounds(bounds, window, Hm, half_size, median=0) -> list:
+REPAIR_REACH = 2  # mosaic rows above and below a row that its repair reads (r2f_mosaic_repair; kReach of csrc/r2f_repair_math.h)
+
+
+def mosaic_upload_bounds(bounds, window, Hm, half_size, median=0, repair=0) -> list:
     """The mosaic rows that travel with each band of a streamed mosaic: upload k is rows [ub[k], ub[k + 1]), and band k's demosaic
     (r2f_demosaic_f32 of the window's rows [bounds[k], bounds[k + 1])) reads nothing outside [ub[0], ub[k + 1]).  bounds: plan_bands'
     of the window's rows; window: (row0, col0, rows, cols) of the demosaiced frame; Hm: the mosaic's rows.  Full size reaches
     DEMOSAIC_REACH rows past a band's ends, half size reads the two mosaic rows of each output row; rows outside [ub[0], ub[-1])
     are never uploaded.  median: the profile's median_passes n (r2f_demosaic_median_f32: a band edge is no border of step M) --
     a band then reads the frame n output rows further either side, clipped to the frame: full size DEMOSAIC_REACH + n mosaic rows
-    past its ends, half size the mosaic rows of n more output rows (2 n)."""
-    row0, rows, n = int(window[0]), int(window[2]), int(median)
-    assert bounds[0] == 0 and bounds[-1] == rows and n >= 0
+    past its ends, half size the mosaic rows of n more output rows (2 n).  repair: REPAIR_REACH for a call with a raw_repair (band
+    k then repairs the rows [rb[k], rb[k + 1]) of the answer for repair=0 before it demosaics from them, and the repair of a row
+    reads `repair` rows either side of it): that many more mosaic rows travel with each band, clipped to the frame."""
+    row0, rows, n, e = int(window[0]), int(window[2]), int(median), int(repair)
+    assert bounds[0] == 0 and bounds[-1] == rows and n >= 0 and e >= 0
     if half_size:
-        return [2 * max(row0 - n, 0)] + [2 * min(row0 + int(b) + n, Hm // 2) for b in bounds[1:]]
-    r = DEMOSAIC_REACH + n
-    return ([max(row0 - r, 0)] + [min(row0 + int(b) + r, Hm) for b in bounds[1:-1]] + [min(row0 + rows + r, Hm)])
+        ub = [2 * max(row0 - n, 0)] + [2 * min(row0 + int(b) + n, Hm // 2) for b in bounds[1:]]
+    else:
+        r = DEMOSAIC_REACH + n
+        ub = [max(row0 - r, 0)] + [min(row0 + int(b) + r, Hm) for b in bounds[1:-1]] + [min(row0 + rows + r, Hm)]
+    return [max(ub[0] - e, 0)] + [min(b + e, Hm) for b in ub[1:]]
 
 
 def frame_shape(payload, shape) -> tuple:
@@ -207,6 +214,18 @@ def check_denoise(raw_denoise, raw_profile, rows, cols):
     if rows % 2 or cols % 2 or rows < 64 or cols < 64:
         raise ValueError(f"raw_denoise on a {rows} x {cols} mosaic: both sides must be even and at least 64 (the five levels reflect "
                          "inside a plane of at least 32 samples a side)")
+
+
+def check_repair(raw_repair, raw_profile, rows, cols):
+    """The caller's raw_repair is a HotPixels that this rows x cols mosaic can run, and comes with a profile (None passes)."""
+    if raw_repair is None:
+        return
+    if not isinstance(raw_repair, HotPixels):
+        raise ValueError(f"raw_repair must be a raw2film_amd.raw.HotPixels, got {type(raw_repair).__name__}")
+    if raw_profile is None:
+        raise ValueError("raw_repair needs a raw_profile: the repair runs on a mosaic, ahead of its demosaic")
+    if rows < 6 or cols < 6:
+        raise ValueError(f"raw_repair on a {rows} x {cols} mosaic: both sides must be at least 6")
 
 
 def load_decoded(src, clip=True, mosaic=False):

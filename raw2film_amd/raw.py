@@ -23,6 +23,9 @@ of both profiles, 0 by default; it is part of equality, hash and repr but no dat
 
 WaveletDenoise is no part of a profile: it is the record of process(raw_denoise=), LibRaw's wavelet denoise of the Bayer mosaic ahead
 of its demosaic (rawpy's noise_thr=; r2f_mosaic_denoise_plan, r2f_mosaic_denoise).
+
+HotPixels is the record of process(raw_repair=): the repair of hot pixels of a mosaic, Bayer or X-Trans, ahead of everything else that
+reads it -- the project's own rule, not LibRaw's bad_pixels (r2f_mosaic_repair_plan, r2f_mosaic_repair).
 """
 
 from __future__ import annotations
@@ -210,6 +213,58 @@ class WaveletDenoise:
         """The numeric RawProfile the demosaic behind the denoise runs with: black 0 and every multiplier times 2^-shift (exact);
         all else is the profile's, a blend clip level included."""
         return profile._replace(black=(0.0,) * 4, multipliers=tuple(m * 2.0 ** -int(shift) for m in profile.multipliers))
+
+
+@dataclass(frozen=True)
+class HotPixels:
+    """The repair of hot pixels of a mosaic ahead of everything else that reads it (process(raw_repair=)): a frozen, hashable record
+    (part of the image cache key).  include/r2f.h has the definition (r2f_mosaic_repair): the project's own rule, NOT LibRaw's
+    bad_pixels (a caller's coordinate list, sequential and in place: not built).  A sample is hot when it stands more than
+    `threshold` above its black level and at least `min_neighbours` of its four neighbours of the same colour lie below `ratio`
+    times it; it takes the largest of those neighbours.  For a Bayer or an X-Trans mosaic.
+
+    threshold: an integer in [0, 65535], in black-subtracted raw units.
+    ratio: a number whose q = round(ratio * 256) lies in [1, 255]; 0.125 (q = 32) by default.
+    min_neighbours: 3 or 4."""
+    threshold: int
+    ratio: float = 0.125
+    min_neighbours: int = 4
+
+    def __post_init__(self):
+        t = self.threshold
+        if isinstance(t, bool) or not isinstance(t, numbers.Integral) or not 0 <= t <= 65535:
+            raise ValueError(f"HotPixels.threshold must be an integer in [0, 65535], got {t!r}")
+        r = self.ratio
+        if isinstance(r, bool) or not isinstance(r, numbers.Real) or not math.isfinite(r) or not 1 <= round(r * 256) <= 255:
+            raise ValueError(f"HotPixels.ratio must be a number whose round(ratio * 256) lies in [1, 255], got {r!r}")
+        n = self.min_neighbours
+        if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n not in (3, 4):
+            raise ValueError(f"HotPixels.min_neighbours must be 3 or 4, got {n!r}")
+        for name, value in (("threshold", int(t)), ("ratio", float(r)), ("min_neighbours", int(n))):
+            object.__setattr__(self, name, value)
+
+    @property
+    def q(self) -> int:
+        """The ratio in 1/256ths, as the device compares with it: q * t_centre > 256 * t_neighbour."""
+        return int(round(self.ratio * 256))
+
+    def plan(self, profile, H: int, W: int) -> _lib.RepairParams:
+        """The r2f_repair_params of an H x W mosaic of `profile` (a RawProfile or an XTransProfile; no GPU: r2f_mosaic_repair_plan).
+        ValueError for another kind of profile and for what the planner refuses (a side below 6, an X-Trans pattern with a phase
+        and quadrant that has no neighbour of its colour inside ring 2)."""
+        if isinstance(profile, RawProfile):
+            period, cfa = 2, None
+        elif isinstance(profile, XTransProfile):
+            period, cfa = 6, (C.c_int32 * 36)(*["RGB".index(c) for row in profile.pattern for c in row])
+        else:
+            raise ValueError(f"HotPixels.plan needs a RawProfile or an XTransProfile, got {type(profile).__name__}")
+        out = _lib.RepairParams()
+        black = (C.c_double * len(profile.black))(*profile.black)
+        if _lib.load().r2f_mosaic_repair_plan(period, cfa, black, self.threshold, self.q, self.min_neighbours, int(H), int(W),
+                                              C.byref(out)) != _lib.OK:
+            raise ValueError(f"r2f_mosaic_repair_plan refused {self!r} with {profile!r} for a {H} x {W} mosaic (both sides must be at "
+                             "least 6)")
+        return out
 
 
 class _MosaicProfile:
