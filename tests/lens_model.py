@@ -35,7 +35,10 @@ cx = (W - 1)/2 + center_x*norm_radius_px, cy = (H - 1)/2 + center_y*norm_radius_
 UNPINNED against real OpenCV / lensfun: neither cv2 nor lensfunpy is installed on any machine this project sees, so this model is
 a restatement of their sources (imgwarp.cpp's remapLanczos4 with a zero border, lensfun's poly3 / poly5 / ptlens / "pa" formulas)
 that no test has compared with the libraries themselves.  What IS pinned: the device kernel and the shared arithmetic against this
-model, bit for bit.
+model, bit for bit; and the model's CONVENTIONS -- the direction of the polynomial, which TCA constant is red's, that vignetting
+divides, the sign of `center`, the direction of the projection -- against a simulated lens that owes nothing to this file
+(tests/camera_sim.py; tests/test_camera_sim_host.py runs it on this model, tests/test_gpu_camera_sim.py on the device).  The
+libraries' bytes stay unpinned.
 
 Besides the float32 model: `evaluate64`, the same definition in float64 with unrounded constants (what upstream's float64 frame
 would see, the table's float weights aside), and per pixel the running error bound gamma_66 * sum |w v| of the float32 sum (64
