@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libr2f_hip.so")
@@ -151,6 +152,64 @@ MEDIAN_MAX_PASSES = 4  # R2F_MEDIAN_MAX_PASSES: the most passes of step M (LibRa
 
 _P = C.POINTER
 _fp = C.c_void_p  # float* (host numpy or device) passed as an address
+
+# The demosaic entry points of include/r2f.h.  All share the head (ctx, src_rows, src_gy0, src_nrows, src_pitch, H, W, params) and the
+# tail (dst, y0, y1, stream); this table is the one place that says what each takes in between, in the header's order, and which
+# options select it (demosaic_entry).  DEMOSAIC_ARGS: an argument's name here -> the C parameters it stands for.
+DEMOSAIC_ARGS = {"orientation": (("orientation", C.c_int),), "clip": (("clip", C.c_int),), "passes": (("passes", C.c_int),),
+                 "window": (("row0", C.c_int), ("col0", C.c_int), ("rows", C.c_int), ("cols", C.c_int)),
+                 "decode": (("divisor", C.c_float), ("factor", C.c_float))}
+
+
+class MosaicKind(NamedTuple):
+    """A kind of mosaic, by its params struct (MOSAIC_KINDS)."""
+    min_side: int  # the smallest side of such a mosaic
+    reduced_field: str  # the params field that says "reduced"
+    entries: dict  # (float epilogue, form) -> (entry point, the arguments between `params` and `dst`)
+
+    def reduced(self, params) -> bool:
+        return bool(getattr(params, self.reduced_field))
+
+
+MOSAIC_KINDS = {
+    DemosaicParams: MosaicKind(2, "half_size", {
+        (False, "plain"): ("r2f_demosaic_u16", ()),
+        (False, "oriented"): ("r2f_demosaic_oriented_u16", ("orientation",)),
+        (False, "blend"): ("r2f_demosaic_blend_u16", ("orientation", "clip")),
+        (False, "median"): ("r2f_demosaic_median_u16", ("orientation", "clip", "passes")),
+        (True, "plain"): ("r2f_demosaic_f32", ("window", "decode")),
+        (True, "blend"): ("r2f_demosaic_blend_f32", ("clip", "window", "decode")),
+        (True, "median"): ("r2f_demosaic_median_f32", ("clip", "passes", "window", "decode")),
+    }),
+    XTransParams: MosaicKind(6, "reduced", {
+        (False, "plain"): ("r2f_demosaic_xtrans_u16", ()),
+        (False, "oriented"): ("r2f_demosaic_xtrans_oriented_u16", ("orientation",)),
+        (False, "blend"): ("r2f_demosaic_xtrans_blend_u16", ("orientation", "clip")),
+        (False, "median"): ("r2f_demosaic_xtrans_median_u16", ("orientation", "clip", "passes")),
+    }),
+}
+
+
+def demosaic_entry(params_type, f32, orientation=0, clip=None, passes=0):
+    """Which entry point a demosaic's options select -> (its name, the arguments it takes between `params` and `dst`).  passes > 0:
+    the median form (a `clip` of None goes as 0); else a clip: the blend form (an orientation of 0 is passed along); else an
+    orientation with the uint16 result: the oriented form; else the plain one.  ValueError for what has no entry point."""
+    if f32 and orientation:
+        raise ValueError(f"the float epilogue writes the upright frame: orientation {orientation!r} has no entry point")
+    form = "median" if passes else "blend" if clip is not None else "oriented" if orientation else "plain"
+    try:
+        return MOSAIC_KINDS[params_type].entries[bool(f32), form]
+    except KeyError:
+        raise ValueError(f"no demosaic entry point takes {params_type.__name__} with the {'float' if f32 else 'uint16'} epilogue") from None
+
+
+def _demosaic_signatures():
+    head = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int]
+    tail = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    return {name: (C.c_int, head + [_P(params_type)] + [t for a in args for _, t in DEMOSAIC_ARGS[a]] + tail)
+            for params_type, kind in MOSAIC_KINDS.items() for name, args in kind.entries.values()}
+
+
 _SIGNATURES = {
     "r2f_version": (C.c_char_p, []),
     "r2f_create": (C.c_int, [C.c_int, _P(C.c_void_p)]),
@@ -245,63 +304,11 @@ _SIGNATURES = {
          C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p],
     ),
     "r2f_demosaic_plan": (C.c_int, [_P(RawProfile), C.c_int, C.c_int, _P(DemosaicParams)]),
-    "r2f_demosaic_u16": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(DemosaicParams), C.c_void_p, C.c_int, C.c_int, C.c_void_p],
-    ),
-    "r2f_demosaic_f32": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(DemosaicParams), C.c_int, C.c_int, C.c_int, C.c_int,
-         C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
-    ),
+    **_demosaic_signatures(),
     "r2f_xtrans_plan": (C.c_int, [_P(XTransProfile), C.c_int, C.c_int, _P(XTransParams)]),
-    "r2f_demosaic_xtrans_u16": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(XTransParams), C.c_void_p, C.c_int, C.c_int, C.c_void_p],
-    ),
-    "r2f_demosaic_oriented_u16": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(DemosaicParams), C.c_int, C.c_void_p, C.c_int, C.c_int,
-         C.c_void_p],
-    ),
-    "r2f_demosaic_xtrans_oriented_u16": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(XTransParams), C.c_int, C.c_void_p, C.c_int, C.c_int,
-         C.c_void_p],
-    ),
     "r2f_raw_scale_plan": (C.c_int, [_P(RawLevels), _P(C.c_double), C.c_int, C.c_uint32, _P(RawScale)]),
     "r2f_raw_scale_plan_highlight": (
         C.c_int, [_P(RawLevels), _P(C.c_double), C.c_int, C.c_uint32, C.c_int, _P(RawScale), _P(Highlight)]),
-    "r2f_demosaic_blend_u16": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(DemosaicParams), C.c_int, C.c_int, C.c_void_p, C.c_int,
-         C.c_int, C.c_void_p],
-    ),
-    "r2f_demosaic_blend_f32": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(DemosaicParams), C.c_int, C.c_int, C.c_int, C.c_int,
-         C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
-    ),
-    "r2f_demosaic_xtrans_blend_u16": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(XTransParams), C.c_int, C.c_int, C.c_void_p, C.c_int,
-         C.c_int, C.c_void_p],
-    ),
-    "r2f_demosaic_median_u16": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(DemosaicParams), C.c_int, C.c_int, C.c_int, C.c_void_p,
-         C.c_int, C.c_int, C.c_void_p],
-    ),
-    "r2f_demosaic_median_f32": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(DemosaicParams), C.c_int, C.c_int, C.c_int, C.c_int,
-         C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p],
-    ),
-    "r2f_demosaic_xtrans_median_u16": (
-        C.c_int,
-        [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P(XTransParams), C.c_int, C.c_int, C.c_int, C.c_void_p,
-         C.c_int, C.c_int, C.c_void_p],
-    ),
     "r2f_mosaic_maximum": (
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _P(C.c_int32), C.c_int, C.c_int, C.c_void_p,

@@ -96,7 +96,8 @@ def band_source(payload, shape, dtype, repair_count=None) -> BandSource:
     if step:  # a Bayer mosaic: band k travels with the mosaic rows its demosaic reads beyond those of the bands before it
         window, params, clip, median = step["window"], step["params"], step.get("clip"), step.get("median", 0)
 
-        repair, half, rows = step.get("repair"), bool(params.half_size), int(window[2])
+        # (only a Bayer mosaic streams: stream_rejection has refused the other kind)
+        repair, half, rows = step.get("repair"), _lib.MOSAIC_KINDS[_lib.DemosaicParams].reduced(params), int(window[2])
         if repair is not None:
             repair_params = repair.plan(step["profile"], shape[0], shape[1])
             repaired_to = []  # [the mosaic row up to which the bands so far have repaired] (they come in order)
@@ -113,12 +114,9 @@ def band_source(payload, shape, dtype, repair_count=None) -> BandSource:
         def demosaic(ctx, landing, image, a0, a1):
             if repair is not None:
                 landing = repaired(ctx, landing, a1)
-            if median:  # a profile with median_passes: step M reads `median` output rows past the band's ends
-                ctx.demosaic_median_f32(landing, params, median, factor, clip=clip, window=window, out=image, rows=(a0, a1))
-            elif clip is None:
-                ctx.demosaic_f32(landing, params, factor, window=window, out=image, rows=(a0, a1))
-            else:  # a ("blend", clip) profile: the same kernel with Blend ahead of the matrix
-                ctx.demosaic_blend_f32(landing, params, clip, factor, window=window, out=image, rows=(a0, a1))
+            # (clip: a ("blend", clip) profile's level or None; median: a profile's median_passes or 0, step M then reads `median`
+            # output rows past the band's ends)
+            ctx.demosaic(landing, params, factor, clip=clip, passes=median, window=window, out=image, rows=(a0, a1))
 
         # A pinned mosaic queues every upload at once.  Its bytes are a third of the RGB frame's, so the render, not the upload, sets
         # the pace; with upload k queued only when band k's turn came the call was no faster than in one piece (100 MP: 15.9 against

@@ -15,13 +15,6 @@ import numpy as np
 from . import _lib
 
 LOG_EPS = 1e-6  # lut_1d.wgsl:24
-# params type -> (the HipContext method that demosaics a mosaic of it to the uint16 frame, the smallest side of such a mosaic): the one
-# place that says which demosaic a params type selects
-MOSAIC_KINDS = {_lib.DemosaicParams: ("demosaic_u16", 2), _lib.XTransParams: ("demosaic_xtrans", 6)}
-# ... and the method that does so with Blend (LibRaw's highlight mode 2), which takes the clip level behind the params
-MOSAIC_BLEND_KINDS = {_lib.DemosaicParams: "demosaic_blend_u16", _lib.XTransParams: "demosaic_xtrans_blend"}
-# ... and with step M (median_passes; `clip` is then an argument of the same method, None for no Blend)
-MOSAIC_MEDIAN_KINDS = {_lib.DemosaicParams: "demosaic_median_u16", _lib.XTransParams: "demosaic_xtrans_median"}
 LUT3D_SCALE = 0.25  # cpu_processor.py:405
 
 
@@ -593,42 +586,62 @@ class HipContext:
         self._same_device(mosaic, "mosaic")
         return int(mosaic.shape[0]), int(mosaic.shape[1])
 
-    def _check_mosaic(self, mosaic, params, what, params_type):
-        """A demosaic's view of its source -> (H, W, the params of `params_type`, planned from a profile where it was given one)."""
-        H, W = self._mosaic_size(mosaic, what, MOSAIC_KINDS[params_type][1])
-        return H, W, params if isinstance(params, params_type) else params.plan(H, W)
+    @staticmethod
+    def _blend_clip(clip) -> int:
+        if isinstance(clip, bool) or not isinstance(clip, numbers.Integral) or not 1 <= clip <= 65535:
+            raise ValueError(f"demosaic: clip must be an integer in [1, 65535], got {clip!r}")
+        return int(clip)
 
-    def _demosaic(self, what, fn, params_type, mosaic, params, out, rows, window=None, decode=None, orientation=0, clip=None,
-                  passes=None):
-        """The demosaic methods: the mosaic check, the planning of a profile, the window, the `out` check, `rows`, the call.
-        fn: the C entry point; decode = (divisor, factor): the float32 epilogue, which also takes a window (default: the frame);
-        orientation: not 0 with the oriented form of `fn` (r2f_demosaic_oriented_u16: `out` and `rows` are then those of O);
-        clip: the blend form of `fn` (r2f_demosaic_blend_u16, which always takes an orientation, 0 included);
-        passes: the median form of `fn` (r2f_demosaic_median_u16: `passes` follows `clip`, which is 0 for no Blend)."""
+    @staticmethod
+    def _median_passes(passes) -> int:
+        n = _lib.MEDIAN_MAX_PASSES
+        if isinstance(passes, bool) or not isinstance(passes, numbers.Integral) or not 1 <= passes <= n:
+            raise ValueError(f"demosaic: passes must be an integer in [1, {n}] (LibRaw's med_passes; R2F_MEDIAN_MAX_PASSES), got {passes!r}")
+        return int(passes)
+
+    def demosaic(self, mosaic, params, factor=None, divisor=65535.0, *, clip=None, passes=0, orientation=0, window=None, out=None,
+                 rows=None):
+        """Every demosaic of include/r2f.h through one call: the kind of mosaic is the params' (a RawProfile or r2f_demosaic_params:
+        Bayer; an XTransProfile or r2f_xtrans_params: X-Trans), the entry point is the one the options select (_lib.demosaic_entry).
+        factor: None yields the uint16 (out_h, out_w, 3) frame; a factor yields the float32 frame decode_u16(that frame, factor,
+        divisor) would, of `window` = (row0, col0, rows, cols) of it (default: all of it; Bayer only).
+        clip: None, or Blend's level, an integer in [1, 65535] (LibRaw's highlight mode 2).  passes: 0, or step M's count, 1 ..
+        MEDIAN_MAX_PASSES (LibRaw's med_passes).  orientation: 0 .. 7 (LibRaw's sizes.flip bits), not 0 with the uint16 frame only:
+        `out` and `rows` are then those of the oriented frame O.  out: the tensor to write (default: a new one).  rows = (y0, y1):
+        only those rows of `out` are written (default: all).  The methods below say what each form computes."""
         torch = self._torch
-        H, W, params = self._check_mosaic(mosaic, params, what, params_type)
+        what = "demosaic"
+        if clip is not None:
+            clip = self._blend_clip(clip)
+        if passes != 0 or isinstance(passes, bool):
+            passes = self._median_passes(passes)
+        params_type = type(params) if type(params) in _lib.MOSAIC_KINDS else params._c_params
+        H, W = self._mosaic_size(mosaic, what, _lib.MOSAIC_KINDS[params_type].min_side)
+        if not isinstance(params, params_type):
+            params = params.plan(H, W)
         if isinstance(orientation, bool) or not isinstance(orientation, numbers.Integral) or not 0 <= orientation <= 7:
             raise ValueError(f"{what}: orientation must be an integer 0 .. 7 (LibRaw's sizes.flip bits), got {orientation!r}")
+        f32 = factor is not None
+        if window is not None and not f32:
+            raise ValueError(f"{what}: a window goes with the float epilogue (a factor); the uint16 frame is written whole")
+        name, between = _lib.demosaic_entry(params_type, f32, orientation, clip, passes)
         r0, c0, nr, nc = (0, 0, int(params.out_h), int(params.out_w)) if window is None else (int(v) for v in window)
         if not (0 <= r0 and 0 <= c0 and nr > 0 and nc > 0 and r0 + nr <= params.out_h and c0 + nc <= params.out_w):
             raise ValueError(f"{what}: window {(r0, c0, nr, nc)} is not inside the {params.out_h} x {params.out_w} frame")
-        if orientation & 4:  # (no window with an orientation: the oriented frame's sides)
-            nr, nc = nc, nr
-        shape = (nr, nc, 3)
-        dtypes, name = ((torch.float32,), "float32") if decode else ((torch.uint16, torch.int16), "uint16")
+        given = {"orientation": (int(orientation),), "clip": (clip or 0,), "passes": (passes,), "window": (r0, c0, nr, nc)}
+        if f32:
+            given["decode"] = (float(np.float32(divisor)), float(np.float32(factor)))
+        shape = (nc, nr, 3) if orientation & 4 else (nr, nc, 3)  # (no window with an orientation: the oriented frame's sides)
+        dtypes, dtype_name = ((torch.float32,), "float32") if f32 else ((torch.uint16, torch.int16), "uint16")
         if out is None:
-            out = torch.empty(shape, dtype=torch.float32 if decode else mosaic.dtype, device=self.device)
+            out = torch.empty(shape, dtype=torch.float32 if f32 else mosaic.dtype, device=self.device)
         elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype in dtypes and out.is_contiguous() and tuple(out.shape) == shape):
-            raise ValueError(f"{what}: out must be a contiguous {name} CUDA tensor of shape {shape}")
+            raise ValueError(f"{what}: out must be a contiguous {dtype_name} CUDA tensor of shape {shape}")
         else:
             self._same_device(out, "out")
-        y0, y1 = (0, nr) if rows is None else (int(rows[0]), int(rows[1]))
-        epilogue = (r0, c0, nr, nc, *decode) if decode else (int(orientation),) if orientation or clip is not None else ()
-        if clip is not None:
-            blend = (clip,) if passes is None else (clip, passes)
-            epilogue = (*blend, *epilogue) if decode else (*epilogue, *blend)
-        self._check(fn(self._h, mosaic.data_ptr(), 0, H, int(mosaic.stride(0)), H, W, C.byref(params), *epilogue, out.data_ptr(), y0, y1,
-                       self._stream()))
+        y0, y1 = (0, shape[0]) if rows is None else (int(rows[0]), int(rows[1]))
+        self._check(getattr(self._lib, name)(self._h, mosaic.data_ptr(), 0, H, int(mosaic.stride(0)), H, W, C.byref(params),
+                                             *(v for arg in between for v in given[arg]), out.data_ptr(), y0, y1, self._stream()))
         return out
 
     def demosaic_u16(self, mosaic, params, out=None, rows=None, orientation=0):
@@ -639,8 +652,7 @@ class HipContext:
         rows = (y0, y1): only those output rows of `out` are written (default: all).
         orientation (0 .. 7, LibRaw's sizes.flip bits; not taken from a profile: name it): not 0 writes the oriented frame O of
         include/r2f.h (r2f_demosaic_oriented_u16) -- (out_w, out_h, 3) with bit 4 --, and `out` and `rows` are O's."""
-        fn = self._lib.r2f_demosaic_oriented_u16 if orientation else self._lib.r2f_demosaic_u16
-        return self._demosaic("demosaic_u16", fn, _lib.DemosaicParams, mosaic, params, out, rows, orientation=orientation)
+        return self.demosaic(mosaic, params, out=out, rows=rows, orientation=orientation)
 
     def demosaic_xtrans(self, mosaic, params, out=None, rows=None, orientation=0):
         """The X-Trans demosaic of include/r2f.h (r2f_demosaic_xtrans_u16: black / scale, the project's own directional-green /
@@ -650,74 +662,48 @@ class HipContext:
         params: a raw2film_amd.raw.XTransProfile (planned full size for this mosaic) or the r2f_xtrans_params of its size.
         rows = (y0, y1): only those output rows of `out` are written (default: all).
         orientation: demosaic_u16's (r2f_demosaic_xtrans_oriented_u16)."""
-        fn = self._lib.r2f_demosaic_xtrans_oriented_u16 if orientation else self._lib.r2f_demosaic_xtrans_u16
-        return self._demosaic("demosaic_xtrans", fn, _lib.XTransParams, mosaic, params, out, rows, orientation=orientation)
+        return self.demosaic(mosaic, params, out=out, rows=rows, orientation=orientation)
 
     def demosaic_f32(self, mosaic, params, factor: float, divisor: float = 65535.0, window=None, out=None, rows=None):
         """demosaic_u16 and decode_u16 in one kernel (r2f_demosaic_f32): window = (row0, col0, rows, cols) of the demosaiced frame
         (default: all of it) -> float32 (rows, cols, 3), bit-identical to decode_u16(demosaic_u16(mosaic)[window], factor, divisor).
         mosaic, params: demosaic_u16's; the mosaic may be the whole landing buffer of which only some rows have arrived -- a call
         reads the rows its contract names and no others.  rows = (y0, y1): only those rows of the window are written."""
-        return self._demosaic("demosaic_f32", self._lib.r2f_demosaic_f32, _lib.DemosaicParams, mosaic, params, out, rows, window,
-                              (float(np.float32(divisor)), float(np.float32(factor))))
-
-    @staticmethod
-    def _blend_clip(what, clip) -> int:
-        if isinstance(clip, bool) or not isinstance(clip, numbers.Integral) or not 1 <= clip <= 65535:
-            raise ValueError(f"{what}: clip must be an integer in [1, 65535], got {clip!r}")
-        return int(clip)
+        return self.demosaic(mosaic, params, factor, divisor, window=window, out=out, rows=rows)
 
     def demosaic_blend_u16(self, mosaic, params, clip, out=None, rows=None, orientation=0):
         """demosaic_u16 with Blend (r2f_demosaic_blend_u16; include/r2f.h, LibRaw's highlight mode 2): a pixel with a channel above
         `clip` (an integer in [1, 65535]; a resolved "blend" profile's `blend_clip`) takes the chroma of its clipped version ahead of
         the camera matrix.  Everything else is demosaic_u16's, `orientation` included; clip = 65535 yields its bytes."""
-        return self._demosaic("demosaic_blend_u16", self._lib.r2f_demosaic_blend_u16, _lib.DemosaicParams, mosaic, params, out, rows,
-                              orientation=orientation, clip=self._blend_clip("demosaic_blend_u16", clip))
+        return self.demosaic(mosaic, params, clip=self._blend_clip(clip), out=out, rows=rows, orientation=orientation)
 
     def demosaic_xtrans_blend(self, mosaic, params, clip, out=None, rows=None, orientation=0):
         """demosaic_xtrans with Blend (r2f_demosaic_xtrans_blend_u16): demosaic_blend_u16's `clip` for an X-Trans mosaic."""
-        return self._demosaic("demosaic_xtrans_blend", self._lib.r2f_demosaic_xtrans_blend_u16, _lib.XTransParams, mosaic, params, out, rows,
-                              orientation=orientation, clip=self._blend_clip("demosaic_xtrans_blend", clip))
+        return self.demosaic(mosaic, params, clip=self._blend_clip(clip), out=out, rows=rows, orientation=orientation)
 
     def demosaic_blend_f32(self, mosaic, params, clip, factor: float, divisor: float = 65535.0, window=None, out=None, rows=None):
         """demosaic_f32 with Blend (r2f_demosaic_blend_f32): bit-identical to decode_u16(demosaic_blend_u16(mosaic, params,
         clip)[window], factor, divisor)."""
-        return self._demosaic("demosaic_blend_f32", self._lib.r2f_demosaic_blend_f32, _lib.DemosaicParams, mosaic, params, out, rows, window,
-                              (float(np.float32(divisor)), float(np.float32(factor))), clip=self._blend_clip("demosaic_blend_f32", clip))
-
-    @staticmethod
-    def _median_passes(what, passes) -> int:
-        n = _lib.MEDIAN_MAX_PASSES
-        if isinstance(passes, bool) or not isinstance(passes, numbers.Integral) or not 1 <= passes <= n:
-            raise ValueError(f"{what}: passes must be an integer in [1, {n}] (LibRaw's med_passes; R2F_MEDIAN_MAX_PASSES), got {passes!r}")
-        return int(passes)
+        return self.demosaic(mosaic, params, factor, divisor, clip=self._blend_clip(clip), window=window, out=out, rows=rows)
 
     def demosaic_median_u16(self, mosaic, params, passes, clip=None, out=None, rows=None, orientation=0):
         """demosaic_u16 with step M (r2f_demosaic_median_u16; include/r2f.h, LibRaw's med_passes): `passes` (1 .. 4) passes of the
         3 x 3 median of R - G and B - G of the whole demosaiced frame between the interpolation and Blend.  clip: None for no
         Blend, else demosaic_blend_u16's.  Everything else is demosaic_u16's, `orientation` included; rows = (y0, y1) read the
         mosaic rows of `passes` more output rows either side."""
-        what = "demosaic_median_u16"
-        return self._demosaic(what, self._lib.r2f_demosaic_median_u16, _lib.DemosaicParams, mosaic, params, out, rows, orientation=orientation,
-                              clip=0 if clip is None else self._blend_clip(what, clip), passes=self._median_passes(what, passes))
+        return self.demosaic(mosaic, params, clip=clip, passes=self._median_passes(passes), out=out, rows=rows, orientation=orientation)
 
     def demosaic_xtrans_median(self, mosaic, params, passes, clip=None, out=None, rows=None, orientation=0):
         """demosaic_xtrans with step M (r2f_demosaic_xtrans_median_u16): demosaic_median_u16's `passes` and `clip` for an X-Trans
         mosaic."""
-        what = "demosaic_xtrans_median"
-        return self._demosaic(what, self._lib.r2f_demosaic_xtrans_median_u16, _lib.XTransParams, mosaic, params, out, rows,
-                              orientation=orientation, clip=0 if clip is None else self._blend_clip(what, clip),
-                              passes=self._median_passes(what, passes))
+        return self.demosaic(mosaic, params, clip=clip, passes=self._median_passes(passes), out=out, rows=rows, orientation=orientation)
 
     def demosaic_median_f32(self, mosaic, params, passes, factor: float, divisor: float = 65535.0, clip=None, window=None, out=None,
                             rows=None):
         """demosaic_f32 with step M (r2f_demosaic_median_f32): bit-identical to decode_u16(demosaic_median_u16(mosaic, params,
         passes, clip)[window], factor, divisor).  The median at a window or row-range edge that is no frame edge reads the frame
         beyond it: a call reads the mosaic rows of `passes` more output rows either side."""
-        what = "demosaic_median_f32"
-        return self._demosaic(what, self._lib.r2f_demosaic_median_f32, _lib.DemosaicParams, mosaic, params, out, rows, window,
-                              (float(np.float32(divisor)), float(np.float32(factor))),
-                              clip=0 if clip is None else self._blend_clip(what, clip), passes=self._median_passes(what, passes))
+        return self.demosaic(mosaic, params, factor, divisor, clip=clip, passes=self._median_passes(passes), window=window, out=out, rows=rows)
 
     def mosaic_maximum(self, mosaic, profile_or_black, period=None, rows=None, out=None):
         """The data maximum of include/r2f.h (r2f_mosaic_maximum): the largest black-subtracted sample, clamped at 0, of a uint16

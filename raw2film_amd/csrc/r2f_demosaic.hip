@@ -1,6 +1,6 @@
 // r2f_demosaic.hip -- the Bayer demosaic ahead of the uint16 hand-off (include/r2f.h: r2f_demosaic_u16, r2f_demosaic_f32): what the
 // Bayer pattern supplies to the staging of r2f_mosaic_stage.h (kernels, LDS tiles, loads, stores and the entry points' checks), and
-// its entry points.  The arithmetic is r2f_demosaic_math.h's (the text tests/demosaic_check.cpp compiles for the CPU).  Seven
+// its seven entry points, each of which names what it passes in a MosaicCall and hands it to mosaic_rows.  The arithmetic is r2f_demosaic_math.h's (the text tests/demosaic_check.cpp compiles for the CPU).  Seven
 // kernels: the full and the half size, each with the uint16 and with the float epilogue; and for r2f_demosaic_oriented_u16 the
 // mirrored and the turned full size and the oriented half size (uint16).  Seven more with Blend for r2f_demosaic_blend_u16 /
 // r2f_demosaic_blend_f32: the same staging and LDS, mosaic::blend_pixel ahead of the matrix (2 more VGPRs at full size).  And seven
@@ -70,22 +70,24 @@ struct BayerPattern {
 }  // namespace r2f
 
 // =============================================================================== C ABI
+// Each entry point fills a MosaicCall: the head and the tail all share, then what it alone takes, by name.
 extern "C" {
 
 int r2f_demosaic_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
                      const r2f_demosaic_params* params, uint16_t* dst_u16_hwc3, int y0, int y1, void* stream) {
     if (!ctx) return R2F_EINVAL;
     R2F_GUARD(ctx);
-    return mosaic_rows<BayerPattern, false>(ctx, "demosaic_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, params, nullptr, 1.f, 1.f,
-                                            dst_u16_hwc3, y0, y1, stream);
+    return mosaic_rows<BayerPattern, false>(ctx, params,
+                                            {"demosaic_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, dst_u16_hwc3, y0, y1, stream});
 }
 
 int r2f_demosaic_oriented_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
                               const r2f_demosaic_params* params, int orientation, uint16_t* dst_u16_hwc3, int y0, int y1, void* stream) {
     if (!ctx) return R2F_EINVAL;
     R2F_GUARD(ctx);
-    return mosaic_rows<BayerPattern, false>(ctx, "demosaic_oriented_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, params, nullptr, 1.f,
-                                            1.f, dst_u16_hwc3, y0, y1, stream, orientation);
+    MosaicCall c{"demosaic_oriented_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, dst_u16_hwc3, y0, y1, stream};
+    c.orientation = orientation;
+    return mosaic_rows<BayerPattern, false>(ctx, params, c);
 }
 
 int r2f_demosaic_f32(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
@@ -94,8 +96,9 @@ int r2f_demosaic_f32(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int sr
     if (!ctx) return R2F_EINVAL;
     R2F_GUARD(ctx);
     const int window[4] = {row0, col0, rows, cols};
-    return mosaic_rows<BayerPattern, true>(ctx, "demosaic_f32", src_rows, src_gy0, src_nrows, src_pitch, H, W, params, window, divisor, factor,
-                                           dst_f32_hwc3, y0, y1, stream);
+    MosaicCall c{"demosaic_f32", src_rows, src_gy0, src_nrows, src_pitch, H, W, dst_f32_hwc3, y0, y1, stream};
+    c.window = window, c.divisor = divisor, c.factor = factor;
+    return mosaic_rows<BayerPattern, true>(ctx, params, c);
 }
 
 // The same kernels with Blend between the interpolation and step C (seven more: every epilogue and class above)
@@ -104,8 +107,9 @@ int r2f_demosaic_blend_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, 
                            void* stream) {
     if (!ctx) return R2F_EINVAL;
     R2F_GUARD(ctx);
-    return mosaic_rows<BayerPattern, false, true>(ctx, "demosaic_blend_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, params, nullptr,
-                                                  1.f, 1.f, dst_u16_hwc3, y0, y1, stream, orientation, clip);
+    MosaicCall c{"demosaic_blend_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, dst_u16_hwc3, y0, y1, stream};
+    c.form = MosaicForm::kBlend, c.orientation = orientation, c.clip = clip;
+    return mosaic_rows<BayerPattern, false>(ctx, params, c);
 }
 
 int r2f_demosaic_blend_f32(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
@@ -114,8 +118,9 @@ int r2f_demosaic_blend_f32(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, 
     if (!ctx) return R2F_EINVAL;
     R2F_GUARD(ctx);
     const int window[4] = {row0, col0, rows, cols};
-    return mosaic_rows<BayerPattern, true, true>(ctx, "demosaic_blend_f32", src_rows, src_gy0, src_nrows, src_pitch, H, W, params, window,
-                                                 divisor, factor, dst_f32_hwc3, y0, y1, stream, 0, clip);
+    MosaicCall c{"demosaic_blend_f32", src_rows, src_gy0, src_nrows, src_pitch, H, W, dst_f32_hwc3, y0, y1, stream};
+    c.form = MosaicForm::kBlend, c.clip = clip, c.window = window, c.divisor = divisor, c.factor = factor;
+    return mosaic_rows<BayerPattern, true>(ctx, params, c);
 }
 
 // Step M between the interpolation and Blend (clip 0: no Blend): the median kernels of r2f_mosaic_stage.h
@@ -124,8 +129,9 @@ int r2f_demosaic_median_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0,
                             void* stream) {
     if (!ctx) return R2F_EINVAL;
     R2F_GUARD(ctx);
-    return mosaic_rows<BayerPattern, false, false, true>(ctx, "demosaic_median_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, params,
-                                                         nullptr, 1.f, 1.f, dst_u16_hwc3, y0, y1, stream, orientation, clip, passes);
+    MosaicCall c{"demosaic_median_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, dst_u16_hwc3, y0, y1, stream};
+    c.form = MosaicForm::kMedian, c.orientation = orientation, c.clip = clip, c.passes = passes;
+    return mosaic_rows<BayerPattern, false>(ctx, params, c);
 }
 
 int r2f_demosaic_median_f32(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
@@ -134,8 +140,9 @@ int r2f_demosaic_median_f32(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0,
     if (!ctx) return R2F_EINVAL;
     R2F_GUARD(ctx);
     const int window[4] = {row0, col0, rows, cols};
-    return mosaic_rows<BayerPattern, true, false, true>(ctx, "demosaic_median_f32", src_rows, src_gy0, src_nrows, src_pitch, H, W, params,
-                                                        window, divisor, factor, dst_f32_hwc3, y0, y1, stream, 0, clip, passes);
+    MosaicCall c{"demosaic_median_f32", src_rows, src_gy0, src_nrows, src_pitch, H, W, dst_f32_hwc3, y0, y1, stream};
+    c.form = MosaicForm::kMedian, c.clip = clip, c.passes = passes, c.window = window, c.divisor = divisor, c.factor = factor;
+    return mosaic_rows<BayerPattern, true>(ctx, params, c);
 }
 
 }  // extern "C"

@@ -9,7 +9,8 @@
 //   mosaic_median_full_kernel, mosaic_median_reduced_kernel   the same two with step M (LibRaw's med_passes) behind the interpolation:
 //                          the tile's three planes plus an n-pixel ring in LDS, n passes of the 3 x 3 median of R - G and B - G there
 //                          (median_passes; the arithmetic is r2f_median_math.h's), then the epilogues above (leave_tile)
-//   mosaic_rows            the checks every entry point makes, then one launch
+//   MosaicCall, mosaic_rows  what an entry point passes (its form -- plain, blend or median -- among it); the checks every entry point
+//                          makes, then one launch: the choice among reduced, turned, mirrored and upright is written once for all forms
 // Each is a template over a Pattern and over the epilogue: the uint16 frame, or a window of it decoded to the float frame the front
 // stage reads (decode_sample of r2f_device.h on each finished sample); and, for the uint16 frame written the way round the sensor
 // was held (the oriented entry points; the index map is r2f_mosaic_math.h's orient), over an OrientClass: mirrored rows leave from
@@ -588,18 +589,37 @@ __global__ __launch_bounds__(256) void mosaic_median_reduced_kernel(const Median
     }
 }
 
-// An entry point: the checks, then one launch.  The window (row0, col0, rows, cols) of the demosaiced frame is what dst holds (none:
-// all of it); [y0, y1) are rows of the window.  `what` names the entry point in messages.  The oriented entry points (uint16, no
-// window) pass their orientation: [y0, y1) are then rows of O, dst is O, and the launch walks orient::rect_of's rectangle of D.
-// The median entry points (Median) pass their passes n and a clip that may be 0 (no Blend); their rows of D read I_0 n rows further.
-template <typename Pattern, bool F32, bool Blend = false, bool Median = false>
-int mosaic_rows(r2f_ctx* ctx, const char* what, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
-                const typename Pattern::Params* params, const int* window, float divisor, float factor, void* dst, int y0, int y1,
-                void* stream, int orientation = 0, int clip = 0, int passes = 0) {
-    static_assert(!(Blend && Median), "the median kernels branch on clip");
+// What an entry point passes to mosaic_rows: the head and the tail all eleven share, in the header's order, then by name what it alone
+// takes.  The form says which of clip and passes it has: the blend form a clip inside [1, 65535]; the median form its passes n and a
+// clip that may be 0 (no Blend), and its rows of D read I_0 n rows further.
+enum class MosaicForm { kPlain, kBlend, kMedian };
+struct MosaicCall {
+    const char* what;  // names the entry point in messages
+    const uint16_t* src_rows;  // the source window: mosaic rows [src_gy0, src_gy0 + src_nrows), src_pitch samples apart
+    int src_gy0, src_nrows;
+    int64_t src_pitch;
+    int H, W;
+    void* dst;
+    int y0, y1;  // rows of the window, [y0, y1)
+    void* stream;
+    MosaicForm form = MosaicForm::kPlain;
+    int orientation = 0;  // not 0 (uint16, no window): [y0, y1) are rows of O, dst is O, the launch walks orient::rect_of's rectangle of D
+    int clip = 0, passes = 0;  // (0 where the form has none)
+    const int* window = nullptr;  // (row0, col0, rows, cols) of the demosaiced frame: what dst holds (none: all of it)
+    float divisor = 1.f, factor = 1.f;  // the float epilogue's
+};
+
+// An entry point: the checks, then one launch.
+template <typename Pattern, bool F32>
+int mosaic_rows(r2f_ctx* ctx, const typename Pattern::Params* params, const MosaicCall& c) {
     constexpr int kMaxSide = 1 << 17;  // (the reduced grid has a block per four rows; indices go through long long)
     constexpr int kMin = Pattern::kMinSide, kReduction = Pattern::kReduction, kReachY = Pattern::kReachY;
-    if (!src_rows || !params || !dst || H < kMin || W < kMin || H > kMaxSide || W > kMaxSide || src_pitch < W || src_gy0 < 0 || src_nrows < 0)
+    const char* what = c.what;
+    const int H = c.H, W = c.W, y0 = c.y0, y1 = c.y1, orientation = c.orientation, clip = c.clip, passes = c.passes;
+    const int* window = c.window;
+    const bool blend = c.form == MosaicForm::kBlend, median = c.form == MosaicForm::kMedian;
+    if (!c.src_rows || !params || !c.dst || H < kMin || W < kMin || H > kMaxSide || W > kMaxSide || c.src_pitch < W || c.src_gy0 < 0 ||
+        c.src_nrows < 0)
         return fail(ctx, R2F_EINVAL, "%s: a mosaic of at least %d x %d samples, a pitch of at least W and a source window are required", what,
                     kMin, kMin);
     const typename Pattern::Params& p = *params;
@@ -609,9 +629,9 @@ int mosaic_rows(r2f_ctx* ctx, const char* what, const uint16_t* src_rows, int sr
         return fail(ctx, R2F_EINVAL, "%s: the params are those of another frame size (%s)", what, Pattern::kPlanner);
     if (!orient::valid(orientation) || (orientation && (F32 || window)))
         return fail(ctx, R2F_EINVAL, "%s: orientation %d is not one of 0 .. 7 (LibRaw's sizes.flip bits)", what, orientation);
-    if (Blend && (clip < 1 || clip > 65535)) return fail(ctx, R2F_EINVAL, "%s: clip %d is not inside [1, 65535]", what, clip);
-    if (Median && (clip < 0 || clip > 65535)) return fail(ctx, R2F_EINVAL, "%s: clip %d is neither 0 (no Blend) nor inside [1, 65535]", what, clip);
-    if (Median && (passes < 1 || passes > R2F_MEDIAN_MAX_PASSES))
+    if (blend && (clip < 1 || clip > 65535)) return fail(ctx, R2F_EINVAL, "%s: clip %d is not inside [1, 65535]", what, clip);
+    if (median && (clip < 0 || clip > 65535)) return fail(ctx, R2F_EINVAL, "%s: clip %d is neither 0 (no Blend) nor inside [1, 65535]", what, clip);
+    if (median && (passes < 1 || passes > R2F_MEDIAN_MAX_PASSES))
         return fail(ctx, R2F_EINVAL, "%s: passes %d is not inside [1, R2F_MEDIAN_MAX_PASSES = %d] (LibRaw's med_passes)", what, passes,
                     R2F_MEDIAN_MAX_PASSES);
     const int frame_rows = orient::rows(orientation, p.out_h, p.out_w);  // (an oriented call has no window: dst is all of O)
@@ -621,7 +641,7 @@ int mosaic_rows(r2f_ctx* ctx, const char* what, const uint16_t* src_rows, int sr
         return fail(ctx, R2F_EINVAL, "%s: the window (%d, %d, %d, %d) is empty or not inside the %d x %d frame", what, row0, col0, rows, cols,
                     p.out_h, p.out_w);
     if (y0 < 0 || y1 > rows || y0 > y1) return fail(ctx, R2F_EINVAL, "%s: rows [%d, %d) not inside the output's [0, %d)", what, y0, y1, rows);
-    if (F32 && (!(divisor > 0.f) || (reinterpret_cast<uintptr_t>(dst) & 3u)))
+    if (F32 && (!(c.divisor > 0.f) || (reinterpret_cast<uintptr_t>(c.dst) & 3u)))
         return fail(ctx, R2F_EINVAL, "%s: a positive divisor and a 4-byte aligned destination are required", what);
     if (y0 == y1) return R2F_OK;
     // the rectangle of the demosaiced frame this call takes: the window's rows [y0, y1) over its columns, or what O's rows hold
@@ -630,54 +650,39 @@ int mosaic_rows(r2f_ctx* ctx, const char* what, const uint16_t* src_rows, int sr
     const orient::Rect read{d.y0 - passes > 0 ? d.y0 - passes : 0, d.y1 + passes < p.out_h ? d.y1 + passes : p.out_h, d.x0, d.x1};
     int lo, hi;
     orient::source_rows(orientation, read, H, kReachY, reduced ? kReduction : 0, lo, hi);
-    if (lo < src_gy0 || (long long)hi > (long long)src_gy0 + src_nrows)
+    if (lo < c.src_gy0 || (long long)hi > (long long)c.src_gy0 + c.src_nrows)
         return fail(ctx, R2F_EINVAL, "%s: rows [%d, %d) read mosaic rows [%d, %d), the source window holds [%d, %lld)", what, y0, y1, lo, hi,
-                    src_gy0, (long long)src_gy0 + src_nrows);
-    const int wide = ((reinterpret_cast<uintptr_t>(src_rows) & 3u) == 0 && src_pitch % 2 == 0) ? 1 : 0;
-    const MosaicArgs<typename Pattern::Params> a{
-        src_rows, src_gy0, (long long)src_pitch, H, W, p, dst, d.y0, d.y1, wide, orientation ? 0 : row0, d.x0, d.x1, divisor, factor, orientation, clip};
-    hipStream_t s = static_cast<hipStream_t>(stream);
+                    c.src_gy0, (long long)c.src_gy0 + c.src_nrows);
+    const int wide = ((reinterpret_cast<uintptr_t>(c.src_rows) & 3u) == 0 && c.src_pitch % 2 == 0) ? 1 : 0;
+    const MosaicArgs<typename Pattern::Params> a{c.src_rows, c.src_gy0, (long long)c.src_pitch, H, W, p, c.dst, d.y0, d.y1, wide,
+                                                 orientation ? 0 : row0, d.x0, d.x1, c.divisor, c.factor, orientation, clip};
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
     const dim3 reduced_grid((d.x1 - d.x0 + 63) / 64, (d.y1 - d.y0 + 3) / 4);
     // (the whole frame: ceil(W / 64) tiles from column 0)
     const dim3 full_grid((d.x1 - 1) / kTW - d.x0 / kTW + 1, (d.y1 - d.y0 + kTH - 1) / kTH);
-    if constexpr (Median) {
-        const MedianArgs<typename Pattern::Params> ma{a, passes};
-        const dim3 tiles((d.x1 - d.x0 + kTW - 1) / kTW, full_grid.y);  // (the reduced form's: anchored to the rectangle)
-        if constexpr (!F32) {
-            if (orientation) {
-                if (reduced)
-                    launch_k(mosaic_median_reduced_kernel<Pattern, false, true>, tiles, dim3(64, 4), 0, s, ma);
-                else if (orientation & orient::kSwap)
-                    launch_k(mosaic_median_full_kernel<Pattern, false, kTurned>, full_grid, dim3(64, 4), 0, s, ma);
-                else
-                    launch_k(mosaic_median_full_kernel<Pattern, false, kMirrored>, full_grid, dim3(64, 4), 0, s, ma);
-                R2F_HIP(ctx, take_launch_status());
-                return R2F_OK;
-            }
-        }
-        if (reduced)
-            launch_k(mosaic_median_reduced_kernel<Pattern, F32, false>, tiles, dim3(64, 4), 0, s, ma);
+    const dim3 tiles((d.x1 - d.x0 + kTW - 1) / kTW, full_grid.y), block(64, 4);  // (the median reduced form's: anchored to the rectangle)
+    // The choice among reduced, turned, mirrored and upright, once for the three forms (the reduced kernels know oriented or not).
+    auto launch = [&](auto cls) {
+        constexpr int Cls = decltype(cls)::value;
+        constexpr bool Oriented = Cls != kUpright;
+        if (median)
+            launch_k(reduced ? mosaic_median_reduced_kernel<Pattern, F32, Oriented> : mosaic_median_full_kernel<Pattern, F32, Cls>,
+                     reduced ? tiles : full_grid, block, 0, s, MedianArgs<typename Pattern::Params>{a, passes});
+        else if (blend)
+            launch_k(reduced ? mosaic_reduced_kernel<Pattern, F32, Oriented, true> : mosaic_full_kernel<Pattern, F32, Cls, true>,
+                     reduced ? reduced_grid : full_grid, block, 0, s, a);
         else
-            launch_k(mosaic_median_full_kernel<Pattern, F32, kUpright>, full_grid, dim3(64, 4), 0, s, ma);
-        R2F_HIP(ctx, take_launch_status());
-        return R2F_OK;
-    }
-    if constexpr (!F32) {
-        if (orientation) {
-            if (reduced)
-                launch_k(mosaic_reduced_kernel<Pattern, false, true, Blend>, reduced_grid, dim3(64, 4), 0, s, a);
-            else if (orientation & orient::kSwap)
-                launch_k(mosaic_full_kernel<Pattern, false, kTurned, Blend>, full_grid, dim3(64, 4), 0, s, a);
-            else
-                launch_k(mosaic_full_kernel<Pattern, false, kMirrored, Blend>, full_grid, dim3(64, 4), 0, s, a);
-            R2F_HIP(ctx, take_launch_status());
-            return R2F_OK;
-        }
-    }
-    if (reduced)
-        launch_k(mosaic_reduced_kernel<Pattern, F32, false, Blend>, reduced_grid, dim3(64, 4), 0, s, a);
+            launch_k(reduced ? mosaic_reduced_kernel<Pattern, F32, Oriented, false> : mosaic_full_kernel<Pattern, F32, Cls, false>,
+                     reduced ? reduced_grid : full_grid, block, 0, s, a);
+    };
+    if constexpr (F32)  // (upright: the float epilogue has no oriented kernels, and the checks have refused an orientation)
+        launch(std::integral_constant<int, kUpright>{});
+    else if (orientation & orient::kSwap)
+        launch(std::integral_constant<int, kTurned>{});
+    else if (orientation)
+        launch(std::integral_constant<int, kMirrored>{});
     else
-        launch_k(mosaic_full_kernel<Pattern, F32, kUpright, Blend>, full_grid, dim3(64, 4), 0, s, a);
+        launch(std::integral_constant<int, kUpright>{});
     R2F_HIP(ctx, take_launch_status());
     return R2F_OK;
 }

@@ -1,6 +1,7 @@
 // r2f_xtrans.hip -- the X-Trans demosaic ahead of the uint16 hand-off (include/r2f.h: r2f_demosaic_xtrans_u16): what the X-Trans
 // pattern supplies to the staging of r2f_mosaic_stage.h (kernels, LDS tiles, loads, stores and the entry point's checks), and its
-// entry points.  The arithmetic is r2f_xtrans_math.h's (the text tests/xtrans_check.cpp compiles for the CPU).  Five kernels: the
+// four entry points, each of which names what it passes in a MosaicCall and hands it to mosaic_rows.  The arithmetic is
+// r2f_xtrans_math.h's (the text tests/xtrans_check.cpp compiles for the CPU).  Five kernels: the
 // full and the reduced (third) size with the uint16 epilogue, and for r2f_demosaic_xtrans_oriented_u16 the mirrored and the turned
 // full size and the oriented reduced size; the float epilogue and the window exist in the staging and are not instantiated for this
 // pattern.  Five more with Blend for r2f_demosaic_xtrans_blend_u16: the same staging and LDS.  And five median kernels for
@@ -72,14 +73,15 @@ struct XTransPattern {
 }  // namespace r2f
 
 // =============================================================================== C ABI
+// Each entry point fills a MosaicCall: the head and the tail all share, then what it alone takes, by name.
 extern "C" {
 
 int r2f_demosaic_xtrans_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
                             const r2f_xtrans_params* params, uint16_t* dst_u16_hwc3, int y0, int y1, void* stream) {
     if (!ctx) return R2F_EINVAL;
     R2F_GUARD(ctx);
-    return mosaic_rows<XTransPattern, false>(ctx, "demosaic_xtrans_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, params, nullptr, 1.f,
-                                             1.f, dst_u16_hwc3, y0, y1, stream);
+    return mosaic_rows<XTransPattern, false>(ctx, params,
+                                             {"demosaic_xtrans_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, dst_u16_hwc3, y0, y1, stream});
 }
 
 int r2f_demosaic_xtrans_oriented_u16(r2f_ctx* ctx, const uint16_t* src_rows, int src_gy0, int src_nrows, int64_t src_pitch, int H, int W,
@@ -87,8 +89,9 @@ int r2f_demosaic_xtrans_oriented_u16(r2f_ctx* ctx, const uint16_t* src_rows, int
                                      void* stream) {
     if (!ctx) return R2F_EINVAL;
     R2F_GUARD(ctx);
-    return mosaic_rows<XTransPattern, false>(ctx, "demosaic_xtrans_oriented_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, params,
-                                             nullptr, 1.f, 1.f, dst_u16_hwc3, y0, y1, stream, orientation);
+    MosaicCall c{"demosaic_xtrans_oriented_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, dst_u16_hwc3, y0, y1, stream};
+    c.orientation = orientation;
+    return mosaic_rows<XTransPattern, false>(ctx, params, c);
 }
 
 // The same kernels with Blend between the interpolation and step C (five more)
@@ -97,8 +100,9 @@ int r2f_demosaic_xtrans_blend_u16(r2f_ctx* ctx, const uint16_t* src_rows, int sr
                                   void* stream) {
     if (!ctx) return R2F_EINVAL;
     R2F_GUARD(ctx);
-    return mosaic_rows<XTransPattern, false, true>(ctx, "demosaic_xtrans_blend_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, params,
-                                                   nullptr, 1.f, 1.f, dst_u16_hwc3, y0, y1, stream, orientation, clip);
+    MosaicCall c{"demosaic_xtrans_blend_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, dst_u16_hwc3, y0, y1, stream};
+    c.form = MosaicForm::kBlend, c.orientation = orientation, c.clip = clip;
+    return mosaic_rows<XTransPattern, false>(ctx, params, c);
 }
 
 // Step M between the interpolation and Blend (clip 0: no Blend): the median kernels of r2f_mosaic_stage.h
@@ -107,8 +111,9 @@ int r2f_demosaic_xtrans_median_u16(r2f_ctx* ctx, const uint16_t* src_rows, int s
                                    int y1, void* stream) {
     if (!ctx) return R2F_EINVAL;
     R2F_GUARD(ctx);
-    return mosaic_rows<XTransPattern, false, false, true>(ctx, "demosaic_xtrans_median_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W,
-                                                          params, nullptr, 1.f, 1.f, dst_u16_hwc3, y0, y1, stream, orientation, clip, passes);
+    MosaicCall c{"demosaic_xtrans_median_u16", src_rows, src_gy0, src_nrows, src_pitch, H, W, dst_u16_hwc3, y0, y1, stream};
+    c.form = MosaicForm::kMedian, c.orientation = orientation, c.clip = clip, c.passes = passes;
+    return mosaic_rows<XTransPattern, false>(ctx, params, c);
 }
 
 }  // extern "C"

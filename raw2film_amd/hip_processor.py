@@ -22,7 +22,6 @@ the uint16 (H, W) Bayer mosaic itself; or the path of a `.npy` file holding one 
 
 from __future__ import annotations
 
-import functools
 import inspect
 import math
 import random
@@ -33,7 +32,7 @@ import numpy as np
 
 from . import _lib, filmstock, geometry, payload as phase1, stencils, tiff
 from .bands import StreamedFrame, band_source, plan_bands, stage_schedule
-from .context import LOG_EPS, LUT3D_SCALE, MOSAIC_BLEND_KINDS, MOSAIC_KINDS, MOSAIC_MEDIAN_KINDS, HipContext
+from .context import LOG_EPS, LUT3D_SCALE, HipContext
 from .jpeg_options import _check_jpeg_image, checked_options
 from .exports import JpegExport, TiffExport
 from .payload import DEVICE_EXPOSURE, host_stream_gate, stream_rejection
@@ -1157,53 +1156,10 @@ class HipProcessor:
 
     def _prepare_device_frame(self, image, cpu_payload):
         """The device pre-path on an uploaded payload frame -> (frame, layout) as the pipeline reads it."""
-        torch = self._torch
-
-        def cut_and_turn(image, window, k, dims=(1, 2)):
-            """How a whole-frame step ends: the window it did not cut itself (None: it did), then k quarter turns (np.rot90's)."""
-            if window is not None:
-                r0, c0, nr, nc = window
-                image = image[r0:r0 + nr, c0:c0 + nc]
-            return torch.rot90(image, k, dims) if k else image
-
+        torch, cut_and_turn = self._torch, self._cut_and_turn
         demosaic_step = cpu_payload.get("demosaic")
         if demosaic_step:  # a mosaic: LibRaw's share of raw_to_linear on the device -> the uint16 frame of the lines below
-            params = demosaic_step["params"]
-            image = image.contiguous()
-            deferred, clip = demosaic_step.get("levels"), demosaic_step.get("clip")
-            repair = demosaic_step.get("repair")
-            if repair is not None:
-                # ahead of everything else that reads the mosaic: the measurement, the denoise and the demosaic below run unchanged,
-                # on the second mosaic the context keeps
-                image = self._repair_mosaic(image, repair, demosaic_step["profile"])
-            if deferred is not None:
-                # the scale is the frame's own: the whole uploaded mosaic's data maximum (one read of it, 4 bytes back, the one
-                # synchronisation of this path), LibRaw's rule on it, and the params planned again with the resolved numbers
-                d = self.ctx.mosaic_maximum(image, deferred)
-                resolved, scale = deferred.resolve_scale(d)
-                self.last_raw_scale = {"data_maximum": d, "maximum_used": int(scale.maximum_used), "adjusted": bool(scale.adjusted)}
-                reduced = bool(params.reduced if phase1.is_xtrans(params) else params.half_size)
-                params, clip = resolved.plan(int(image.shape[0]), int(image.shape[1]), reduced), resolved.blend_clip
-            denoise = demosaic_step.get("denoise")
-            if denoise is not None:
-                # behind the measurement and the resolve, which see the UNdenoised mosaic as LibRaw's adjust_maximum does; the
-                # denoised mosaic is black-free and in units of t << shift, and the demosaic is planned again for that
-                H, W = int(image.shape[0]), int(image.shape[1])
-                profile = resolved if deferred is not None else demosaic_step["profile"]
-                maximum = denoise.maximum if denoise.maximum is not None else int(scale.maximum_used)
-                dn = denoise.plan(profile.black, H, W, maximum)
-                self.last_raw_denoise = {"threshold": denoise.threshold, "maximum": int(maximum), "shift": int(dn.shift)}
-                image = self.ctx.mosaic_denoise(image, dn)
-                params = denoise.shifted(profile, dn.shift).plan(H, W, bool(params.half_size))
-            median = demosaic_step.get("median", 0)
-            if median:  # LibRaw's med_passes: the median entry point of the same demosaic (its clip may be None)
-                demosaic = functools.partial(getattr(self.ctx, MOSAIC_MEDIAN_KINDS[type(params)]), passes=median, clip=clip)
-            elif clip is None:
-                demosaic = getattr(self.ctx, MOSAIC_KINDS[type(params)][0])
-            else:  # highlight mode 2: the blend entry point of the same demosaic
-                demosaic = functools.partial(getattr(self.ctx, MOSAIC_BLEND_KINDS[type(params)]), clip=clip)
-            image = cut_and_turn(demosaic(image, params, orientation=demosaic_step.get("orientation", 0)),
-                                 demosaic_step["window"], demosaic_step["rotate_times"], dims=(0, 1))
+            image = self._demosaic_mosaic(image.contiguous(), demosaic_step)
         if image.dtype in (torch.int16, torch.uint16):  # a decoded 16-bit frame: raw_conversion.py:50-52 on the device
             if cpu_payload.get("u16_factor") is None:
                 raise ValueError("a uint16 payload needs its exposure factor (`u16_factor`, extract_image_data_cpu sets it)")
@@ -1303,6 +1259,45 @@ class HipProcessor:
         returned."""
         params = repair.plan(profile, int(mosaic.shape[0]), int(mosaic.shape[1]))
         return self.ctx.mosaic_repair(mosaic, params, count=self._begin_repair_record(repair))
+
+    def _cut_and_turn(self, image, window, k, dims=(1, 2)):
+        """How a whole-frame step ends: the window it did not cut itself (None: it did), then k quarter turns (np.rot90's)."""
+        if window is not None:
+            r0, c0, nr, nc = window
+            image = image[r0:r0 + nr, c0:c0 + nc]
+        return self._torch.rot90(image, k, dims) if k else image
+
+    def _demosaic_mosaic(self, image, step):
+        """The payload's `demosaic` step on an uploaded mosaic in one piece: repair, measure and resolve, denoise, demosaic, cut and
+        turn -> the uint16 frame the hand-off decodes."""
+        params, kind = step["params"], _lib.MOSAIC_KINDS[type(step["params"])]
+        deferred, clip = step.get("levels"), step.get("clip")
+        repair = step.get("repair")
+        if repair is not None:
+            # ahead of everything else that reads the mosaic: the measurement, the denoise and the demosaic below run unchanged,
+            # on the second mosaic the context keeps
+            image = self._repair_mosaic(image, repair, step["profile"])
+        H, W = int(image.shape[0]), int(image.shape[1])
+        if deferred is not None:
+            # the scale is the frame's own: the whole uploaded mosaic's data maximum (one read of it, 4 bytes back, the one
+            # synchronisation of this path), LibRaw's rule on it, and the params planned again with the resolved numbers
+            d = self.ctx.mosaic_maximum(image, deferred)
+            resolved, scale = deferred.resolve_scale(d)
+            self.last_raw_scale = {"data_maximum": d, "maximum_used": int(scale.maximum_used), "adjusted": bool(scale.adjusted)}
+            params, clip = resolved.plan(H, W, kind.reduced(params)), resolved.blend_clip
+        denoise = step.get("denoise")
+        if denoise is not None:
+            # behind the measurement and the resolve, which see the UNdenoised mosaic as LibRaw's adjust_maximum does; the
+            # denoised mosaic is black-free and in units of t << shift, and the demosaic is planned again for that
+            profile = resolved if deferred is not None else step["profile"]
+            maximum = denoise.maximum if denoise.maximum is not None else int(scale.maximum_used)
+            dn = denoise.plan(profile.black, H, W, maximum)
+            self.last_raw_denoise = {"threshold": denoise.threshold, "maximum": int(maximum), "shift": int(dn.shift)}
+            image = self.ctx.mosaic_denoise(image, dn)
+            params = denoise.shifted(profile, dn.shift).plan(H, W, kind.reduced(params))
+        # (clip: highlight mode 2's level or None; median: LibRaw's med_passes or 0 -- the options pick the entry point)
+        frame = self.ctx.demosaic(image, params, clip=clip, passes=step.get("median", 0), orientation=step.get("orientation", 0))
+        return self._cut_and_turn(frame, step["window"], step["rotate_times"], dims=(0, 1))
 
     @property
     def last_raw_repair(self):

@@ -173,8 +173,9 @@ def test_a_mosaic_travels_with_its_demosaics_reach_and_lands_in_the_float_frame(
         src.decode(ctx, landing, image, a0, a1)
     assert len(ctx.calls) == bands
     for (name, args, kw), a0, a1 in zip(ctx.calls, bounds, bounds[1:]):
-        assert name == "demosaic_f32" and args[0] is landing and args[1] is params and args[2:] == (1.5,)
-        assert set(kw) == {"window", "out", "rows"} and kw["window"] == window and kw["out"] is image and kw["rows"] == (a0, a1)
+        assert name == "demosaic" and args[0] is landing and args[1] is params and args[2:] == (1.5,)
+        assert set(kw) == {"clip", "passes", "window", "out", "rows"} and kw["window"] == window and kw["out"] is image and kw["rows"] == (a0, a1)
+        assert kw["clip"] is None and kw["passes"] == 0  # a plain profile: neither Blend nor step M went along
     # only a mosaic has all its uploads queued ahead of the first band
     others = (band_source(dict(u16_factor=None, clip_on_device=True), (H, W, 3), "torch.float32"),
               band_source(dict(u16_factor=1.0), (H, W, 3), "torch.int16"),

@@ -22,8 +22,8 @@ N = 2368
 POINTWISE = dict(halation=False, sharpness=False, grain=0, exp_kelvin=6000, color_masking=1.0, frame_width=36, frame_height=36,
                  max_scale=None, lens_correction=False, seed=3)
 STENCILS = dict(POINTWISE, halation=True, sharpness=True, grain=2, frame_width=360, frame_height=360, halation_green_factor=0.3)
-ROW_KEYS = ("y0", "y1", "src_gy0", "in_gy0", "dst_gy0", "rows", "gy0", "H", "window", "identity_done")
-CTX_CALLS = ("stage_front", "stage_front_split", "stage_halation", "stage_mtf", "decode_u16", "decode_u16_auto", "demosaic_f32",
+ROW_KEYS = ("y0", "y1", "src_gy0", "in_gy0", "dst_gy0", "rows", "gy0", "H", "window", "identity_done", "clip", "passes")
+CTX_CALLS = ("stage_front", "stage_front_split", "stage_halation", "stage_mtf", "decode_u16", "decode_u16_auto", "demosaic",
              "exposure_rows", "exposure_finish")
 STOPS = 0.5
 
@@ -122,7 +122,8 @@ def expected_trace(proc, kind, src, extra, bounds, settings, idents):
             elif kind == "device":
                 trace.append(("decode_u16_auto", (y1 - y0, Wf, 3), ((0, c0, y1 - y0, nc),), {}))
             elif kind == "mosaic":
-                trace.append(("demosaic_f32", tuple(src.shape), (factor,), dict(rows=(y0, y1), window=window)))
+                # (a plain profile: neither Blend nor step M goes along)
+                trace.append(("demosaic", tuple(src.shape), (factor,), dict(rows=(y0, y1), window=window, clip=None, passes=0)))
             band = (y1 - y0, W, 3)
             if pointwise:
                 trace.append(("front", band, (), dict(y0=y0, y1=y1, in_gy0=y0)))

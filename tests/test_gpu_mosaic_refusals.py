@@ -1,8 +1,11 @@
-"""What the three demosaic entry points refuse, and in which words: r2f_demosaic_u16, r2f_demosaic_f32 and r2f_demosaic_xtrans_u16
-on an 8 x 8 Bayer and a 12 x 12 X-Trans mosaic.  Every call below is refused before it launches anything (or, for an empty row
-range, returns before it does), so the test runs no kernel; it pins, for each refused call, the code, the exact r2f_last_error text,
-which message wins when a call breaks two rules at once (the checks run in a stated order), and that the canary-filled destination
-and the source are untouched after all of them.  The texts are the entry points' own, copied from their source."""
+"""What the eleven demosaic entry points refuse, and in which words: every r2f_demosaic_* of include/r2f.h on an 8 x 8 Bayer and a
+12 x 12 X-Trans mosaic (and one 16 x 16 Bayer mosaic, where step M's extra reach shows).  Every call below is refused before it
+launches anything (or, for an empty row range, returns before it does), so the test runs no kernel; it pins, for each refused call,
+the code, the exact r2f_last_error text, which message wins when a call breaks two rules at once (the checks run in a stated order:
+the mosaic, the params, the frame size, the orientation, the clip, the passes, the window, the rows, the divisor, the source
+window), and that the canary-filled destination and the source are untouched after all of them.  The texts are the entry points'
+own, copied from their source.  A row whose text differs for the median entry points (their rows of the frame read one more row
+either side per pass, and a good call here has one pass) carries that text as a fourth item."""
 
 import ctypes as C
 
@@ -83,16 +86,20 @@ BAYER = [
      "{what}: rows [0, 5) not inside the output's [0, 4)"),
     # the full size reads 4 mosaic rows past its own on either side, clipped to the frame
     ("a source window that ends a row early", dict(y0=1, y1=2, nrows=5),
-     "{what}: rows [1, 2) read mosaic rows [0, 6), the source window holds [0, 5)"),
+     "{what}: rows [1, 2) read mosaic rows [0, 6), the source window holds [0, 5)",
+     "{what}: rows [1, 2) read mosaic rows [0, 7), the source window holds [0, 5)"),
     ("a source window that begins a row late", dict(y0=5, y1=6, gy0=2, nrows=6),
-     "{what}: rows [5, 6) read mosaic rows [1, 8), the source window holds [2, 8)"),
+     "{what}: rows [5, 6) read mosaic rows [1, 8), the source window holds [2, 8)",
+     "{what}: rows [5, 6) read mosaic rows [0, 8), the source window holds [2, 8)"),
     ("a source window a row short of the frame's last", dict(y0=0, y1=8, nrows=7),
      "{what}: rows [0, 8) read mosaic rows [0, 8), the source window holds [0, 7)"),
     # the half size reads the two mosaic rows of each of its own
     ("half size, a source window that ends a row early", dict(params=lambda: bayer(half=True), y0=1, y1=3, gy0=2, nrows=3),
-     "{what}: rows [1, 3) read mosaic rows [2, 6), the source window holds [2, 5)"),
+     "{what}: rows [1, 3) read mosaic rows [2, 6), the source window holds [2, 5)",
+     "{what}: rows [1, 3) read mosaic rows [0, 8), the source window holds [2, 5)"),
     ("half size, a source window that begins a row late", dict(params=lambda: bayer(half=True), y0=1, y1=3, gy0=3, nrows=3),
-     "{what}: rows [1, 3) read mosaic rows [2, 6), the source window holds [3, 6)"),
+     "{what}: rows [1, 3) read mosaic rows [2, 6), the source window holds [3, 6)",
+     "{what}: rows [1, 3) read mosaic rows [0, 8), the source window holds [3, 6)"),
     # two rules at once: the earlier check speaks
     ("a pitch below W and no Bayer pattern", dict(pitch=7, params=lambda: bayer(cfa=(0, 0, 1, 2))), B_FIRST),
     ("a bad colour id and no Bayer pattern", dict(params=lambda: bayer(cfa=(1, 1, 1, 5))), "{what}: colour id 5 at site 3"),
@@ -118,9 +125,11 @@ F32_ONLY = [
     ("a destination no float can start at", dict(dst_offset=2), F_DIVISOR),
     # rows [3, 4) of a window that begins at row 2 are the frame's row 5
     ("a window's source rows that begin a row late", dict(window=(2, 0, 4, 8), y0=3, y1=4, gy0=2, nrows=6),
-     "{what}: rows [3, 4) read mosaic rows [1, 8), the source window holds [2, 8)"),
+     "{what}: rows [3, 4) read mosaic rows [1, 8), the source window holds [2, 8)",
+     "{what}: rows [3, 4) read mosaic rows [0, 8), the source window holds [2, 8)"),
     ("a window's source rows that end a row early", dict(window=(1, 0, 4, 8), y0=0, y1=1, nrows=5),
-     "{what}: rows [0, 1) read mosaic rows [0, 6), the source window holds [0, 5)"),
+     "{what}: rows [0, 1) read mosaic rows [0, 6), the source window holds [0, 5)",
+     "{what}: rows [0, 1) read mosaic rows [0, 7), the source window holds [0, 5)"),
     ("another frame size and a bad window", dict(params=lambda: bayer(10, 8), window=(2, 3, 0, 4)), B_ANOTHER),
     ("a bad window and rows outside", dict(window=(2, 3, 0, 4), y0=-1, y1=4), "{what}: the window (2, 3, 0, 4) is empty or not inside the 8 x 8 frame"),
     ("rows outside and a bad divisor", dict(y0=-1, y1=4, divisor=0.0), "{what}: rows [-1, 4) not inside the output's [0, 8)"),
@@ -157,18 +166,23 @@ XTRANS = [
      "{what}: rows [0, 5) not inside the output's [0, 4)"),
     # the full size reads 3 mosaic rows past its own on either side, clipped to the frame
     ("a source window that begins a row late", dict(y0=5, y1=6, gy0=3, nrows=9),
-     "{what}: rows [5, 6) read mosaic rows [2, 9), the source window holds [3, 12)"),
+     "{what}: rows [5, 6) read mosaic rows [2, 9), the source window holds [3, 12)",
+     "{what}: rows [5, 6) read mosaic rows [1, 10), the source window holds [3, 12)"),
     ("a source window that ends a row early", dict(y0=5, y1=6, gy0=2, nrows=6),
-     "{what}: rows [5, 6) read mosaic rows [2, 9), the source window holds [2, 8)"),
+     "{what}: rows [5, 6) read mosaic rows [2, 9), the source window holds [2, 8)",
+     "{what}: rows [5, 6) read mosaic rows [1, 10), the source window holds [2, 8)"),
     ("a source window a row short at the frame's top", dict(y0=0, y1=2, nrows=4),
-     "{what}: rows [0, 2) read mosaic rows [0, 5), the source window holds [0, 4)"),
+     "{what}: rows [0, 2) read mosaic rows [0, 5), the source window holds [0, 4)",
+     "{what}: rows [0, 2) read mosaic rows [0, 6), the source window holds [0, 4)"),
     ("a source window a row short of the frame's last", dict(y0=0, y1=12, nrows=11),
      "{what}: rows [0, 12) read mosaic rows [0, 12), the source window holds [0, 11)"),
     # the reduced size reads the three mosaic rows of each of its own
     ("reduced size, a source window that begins a row late", dict(params=lambda: xtrans(reduced=True), y0=1, y1=3, gy0=4, nrows=5),
-     "{what}: rows [1, 3) read mosaic rows [3, 9), the source window holds [4, 9)"),
+     "{what}: rows [1, 3) read mosaic rows [3, 9), the source window holds [4, 9)",
+     "{what}: rows [1, 3) read mosaic rows [0, 12), the source window holds [4, 9)"),
     ("reduced size, a source window that ends a row early", dict(params=lambda: xtrans(reduced=True), y0=1, y1=3, gy0=3, nrows=5),
-     "{what}: rows [1, 3) read mosaic rows [3, 9), the source window holds [3, 8)"),
+     "{what}: rows [1, 3) read mosaic rows [3, 9), the source window holds [3, 8)",
+     "{what}: rows [1, 3) read mosaic rows [0, 12), the source window holds [3, 8)"),
     # two rules at once: the earlier check speaks
     ("a pitch below W and tampered tables", dict(pitch=11, params=lambda: xtrans(tamper="gap")), X_FIRST),
     ("tampered tables and another frame size", dict(params=lambda: xtrans(15, 12, tamper="cfa")), X_TABLES),
@@ -177,44 +191,104 @@ XTRANS = [
     ("rows outside and a short source window", dict(y0=-1, y1=4, nrows=0), "{what}: rows [-1, 4) not inside the output's [0, 12)"),
 ]
 
-# entry point -> (its name in messages, the side of the mosaic, the destination's element type, how its params are planned, its table)
+# ------------------------------------------------------------------------------- the arguments between the params and the destination
+# (either pattern: none of these texts names one.  A bad window below is F32_ONLY's empty one.)
+ORIENTATION = "{what}: orientation %d is not one of 0 .. 7 (LibRaw's sizes.flip bits)"
+BLEND_CLIP = "{what}: clip %d is not inside [1, 65535]"
+MEDIAN_CLIP = "{what}: clip %d is neither 0 (no Blend) nor inside [1, 65535]"
+PASSES = "{what}: passes %d is not inside [1, R2F_MEDIAN_MAX_PASSES = 4] (LibRaw's med_passes)"
+
+ORIENTED = [  # every entry point that takes an orientation
+    ("an orientation of -1", dict(orientation=-1), ORIENTATION % -1),
+    ("an orientation of 8", dict(orientation=8), ORIENTATION % 8),
+    ("a bad orientation and rows outside", dict(orientation=8, y0=-1, y1=4), ORIENTATION % 8),
+    ("a bad orientation and a short source window", dict(orientation=-1, nrows=0), ORIENTATION % -1),
+]
+BLEND = [  # the blend entry points' clip
+    ("a clip of 0", dict(clip=0), BLEND_CLIP % 0),
+    ("a clip of 65536", dict(clip=65536), BLEND_CLIP % 65536),
+    ("a bad clip and rows outside", dict(clip=0, y0=-1, y1=4), BLEND_CLIP % 0),
+]
+BLEND_ORIENTED = [("a bad orientation and a bad clip", dict(orientation=8, clip=65536), ORIENTATION % 8)]
+BLEND_F32 = [("a bad clip and a bad window", dict(clip=65536, window=(2, 3, 0, 4)), BLEND_CLIP % 65536)]
+MEDIAN = [  # the median entry points' clip (0: no Blend) and passes
+    ("a clip of -1", dict(clip=-1), MEDIAN_CLIP % -1),
+    ("a clip of 65536", dict(clip=65536), MEDIAN_CLIP % 65536),
+    ("no pass", dict(passes=0), PASSES % 0),
+    ("a pass more than the cap", dict(passes=5), PASSES % 5),
+    ("a bad clip and bad passes", dict(clip=-1, passes=0), MEDIAN_CLIP % -1),
+    ("bad passes and rows outside", dict(passes=5, y0=-1, y1=4), PASSES % 5),
+]
+MEDIAN_ORIENTED = [("a bad orientation and a bad clip", dict(orientation=8, clip=65536), ORIENTATION % 8),
+                   ("a bad orientation and bad passes", dict(orientation=-1, passes=0), ORIENTATION % -1)]
+MEDIAN_F32 = [("a bad clip and a bad window", dict(clip=65536, window=(2, 3, 0, 4)), MEDIAN_CLIP % 65536),
+              ("bad passes and a bad window", dict(passes=0, window=(2, 3, 0, 4)), PASSES % 0)]
+# step M's reach on a 16 x 16 Bayer mosaic: row 7 with two passes reads rows [5, 10) of the frame, and those read 4 mosaic rows more
+MEDIAN_REACH = [("two passes, a source window that begins a row late", dict(side=16, y0=7, y1=8, passes=2, gy0=2, nrows=14),
+                 "{what}: rows [7, 8) read mosaic rows [1, 14), the source window holds [2, 16)")]
+
+# entry point -> (its name in messages, the destination's element type, how its params are planned (which says the mosaic's side),
+# the arguments it takes between the params and the destination, its table)
+SIDES = {bayer: 8, xtrans: 12}
+BAYER_F32 = BAYER + F32_ONLY
 ENTRIES = {
-    "r2f_demosaic_u16": ("demosaic_u16", 8, torch.int16, bayer, BAYER),
-    "r2f_demosaic_f32": ("demosaic_f32", 8, torch.float32, bayer, BAYER + F32_ONLY),
-    "r2f_demosaic_xtrans_u16": ("demosaic_xtrans_u16", 12, torch.int16, xtrans, XTRANS),
+    "r2f_demosaic_u16": ("demosaic_u16", torch.int16, bayer, (), BAYER),
+    "r2f_demosaic_oriented_u16": ("demosaic_oriented_u16", torch.int16, bayer, ("orientation",), BAYER + ORIENTED),
+    "r2f_demosaic_blend_u16": ("demosaic_blend_u16", torch.int16, bayer, ("orientation", "clip"), BAYER + ORIENTED + BLEND + BLEND_ORIENTED),
+    "r2f_demosaic_median_u16": ("demosaic_median_u16", torch.int16, bayer, ("orientation", "clip", "passes"),
+                                BAYER + ORIENTED + MEDIAN + MEDIAN_ORIENTED + MEDIAN_REACH),
+    "r2f_demosaic_f32": ("demosaic_f32", torch.float32, bayer, ("window", "decode"), BAYER_F32),
+    "r2f_demosaic_blend_f32": ("demosaic_blend_f32", torch.float32, bayer, ("clip", "window", "decode"), BAYER_F32 + BLEND + BLEND_F32),
+    "r2f_demosaic_median_f32": ("demosaic_median_f32", torch.float32, bayer, ("clip", "passes", "window", "decode"),
+                                BAYER_F32 + MEDIAN + MEDIAN_F32 + MEDIAN_REACH),
+    "r2f_demosaic_xtrans_u16": ("demosaic_xtrans_u16", torch.int16, xtrans, (), XTRANS),
+    "r2f_demosaic_xtrans_oriented_u16": ("demosaic_xtrans_oriented_u16", torch.int16, xtrans, ("orientation",), XTRANS + ORIENTED),
+    "r2f_demosaic_xtrans_blend_u16": ("demosaic_xtrans_blend_u16", torch.int16, xtrans, ("orientation", "clip"),
+                                      XTRANS + ORIENTED + BLEND + BLEND_ORIENTED),
+    "r2f_demosaic_xtrans_median_u16": ("demosaic_xtrans_median_u16", torch.int16, xtrans, ("orientation", "clip", "passes"),
+                                       XTRANS + ORIENTED + MEDIAN + MEDIAN_ORIENTED),
 }
 
 
 @pytest.mark.parametrize("entry", sorted(ENTRIES))
 def test_refused_calls_say_why_and_write_nothing(ctx, entry):
-    what, side, dtype, plan, table = ENTRIES[entry]
-    src = Arena.holding(torch.arange(side * side, dtype=torch.int16).reshape(side, side).cuda())
-    dst = Arena.hwc(side, side, dtype, device="cuda")
-    good = plan()
+    what, dtype, plan, between, table = ENTRIES[entry]
+    side, median = SIDES[plan], "passes" in between
+    sides = {side} | {args.get("side", side) for _, args, *_ in table}
+    sources = {s: Arena.holding(torch.arange(s * s, dtype=torch.int16).reshape(s, s).cuda()) for s in sides}
+    dst = Arena.hwc(16, 16, dtype, device="cuda")
+    planned = {s: plan(s, s) for s in sources}
 
-    good_call = dict(src=src.view.data_ptr(), gy0=0, nrows=side, pitch=side, H=side, W=side, params=lambda: good, dst=dst.view.data_ptr(),
-                     dst_offset=0, y0=0, y1=4, window=None, divisor=65535.0)
+    def good_call(s):  # (a good call of a mosaic of s x s samples: one pass, a clip inside both ranges, upright)
+        return dict(src=sources[s].view.data_ptr(), gy0=0, nrows=s, pitch=s, H=s, W=s, params=lambda: planned[s], dst=dst.view.data_ptr(),
+                    dst_offset=0, y0=0, y1=4, window=None, divisor=65535.0, orientation=0, clip=1000, passes=1)
 
-    def call(**args):
-        a = {**good_call, **args}
+    def call(side=side, **args):
+        a = {**good_call(side), **args}
         p = a["params"]() if a["params"] is not None else None
         ref = C.byref(p) if p is not None else None
         d = a["dst"] + a["dst_offset"] if a["dst"] is not None else None
-        head = (ctx._h, a["src"], a["gy0"], a["nrows"], a["pitch"], a["H"], a["W"], ref)
-        if entry == "r2f_demosaic_f32":
-            win = a["window"] or (0, 0, p.out_h if p is not None else side, p.out_w if p is not None else side)
-            rc = ctx._lib.r2f_demosaic_f32(*head, *win, a["divisor"], 1.0, d, a["y0"], a["y1"], ctx._stream())
-        else:
-            rc = getattr(ctx._lib, entry)(*head, d, a["y0"], a["y1"], ctx._stream())
+        a["window"] = a["window"] or (0, 0, p.out_h if p is not None else side, p.out_w if p is not None else side)
+        a["decode"] = (a["divisor"], 1.0)
+        middle = [v for name in between for v in (a[name] if name in ("window", "decode") else (a[name],))]
+        rc = getattr(ctx._lib, entry)(ctx._h, a["src"], a["gy0"], a["nrows"], a["pitch"], a["H"], a["W"], ref, *middle, d, a["y0"], a["y1"],
+                                      ctx._stream())
         return rc, ctx._lib.r2f_last_error(ctx._h).decode()
 
     seen = set()
-    for wrong, args, message in table:
+    for wrong, args, message, *median_message in table:
         assert wrong not in seen, f"two cases named {wrong!r}"
         seen.add(wrong)
+        if median and median_message:
+            message = median_message[0]
         assert call(**args) == (EINVAL, message.format(what=what)), f"{entry}: {wrong}"
-    # an empty row range is no refusal, reads nothing (so it needs no source rows) and launches nothing either
+    # an empty row range is no refusal, reads nothing (so it needs no source rows) and launches nothing either; nor does an
+    # orientation with nothing else wrong change that
     assert call(y0=2, y1=2, nrows=0)[0] == 0, f"{entry}: an empty row range"
+    if "orientation" in between:
+        assert call(orientation=5, y0=2, y1=2, nrows=0)[0] == 0, f"{entry}: an empty row range of the oriented frame"
     torch.cuda.synchronize()
     dst.check(None, what=f"refused {entry}")
-    src.unchanged(f"refused {entry}")
+    for s in sources.values():
+        s.unchanged(f"refused {entry}")
+

@@ -25,6 +25,14 @@ followed by r2f_decode_u16 on the same frame, with the bytes each moves.  Calls:
 stream_bands = 16 (the mosaic in row bands), with stream_bands = 0 (one piece: what the call did before a mosaic streamed, the
 baseline) and process(uint16 RGB) streamed, each from pageable and from pinned memory; the legs take turns call by call, R rounds of N
 calls after a warm-up each; a leg's spread over all its calls is the run-to-run spread the comparison is read against.
+
+    python tools/demosaic_probe.py --calls [--out FILE] [--repeats N] [--rounds R] [--parent DIR]
+
+The host cost of a call (profiles/r31_demosaic_call_cost.txt): HipContext.demosaic_u16, demosaic_median_u16 (one pass) and demosaic_f32
+on a 64 x 64 mosaic, one tile, which is launch-bound: what the Python method and the C++ entry point spend between the caller and the
+launch shows.  Wall clock around a tight loop of N calls (default 2000) with a device synchronisation on either side, after a warm-up
+of a tenth as many; this tree and the parent's checkout (--parent DIR) in child processes of their own that take turns, R rounds.  A
+leg's range over its rounds is the round-to-round spread the two medians are read against.
 Needs a GPU: there is no CPU path.
 """
 
@@ -102,6 +110,60 @@ def child(mode, repeats):
             del pageable, pinned
     proc.close()
     print(json.dumps(out))
+
+
+def calls_child(calls):
+    """One turn of one leg of --calls -> JSON {method: microseconds per call} on stdout."""
+    import torch
+
+    from raw2film_amd.context import HipContext
+
+    ctx = HipContext(0)
+    m = torch.from_numpy(np.random.default_rng(31).integers(0, 16384, (64, 64), dtype=np.uint16).view(np.int16)).cuda()
+    params = raw_profile().plan(64, 64)
+    u16, f32 = torch.empty((64, 64, 3), dtype=torch.int16, device="cuda"), torch.empty((64, 64, 3), dtype=torch.float32, device="cuda")
+    legs = {"demosaic_u16": lambda: ctx.demosaic_u16(m, params, out=u16),
+            "demosaic_median_u16": lambda: ctx.demosaic_median_u16(m, params, 1, out=u16),
+            "demosaic_f32": lambda: ctx.demosaic_f32(m, params, 1.5, out=f32)}
+    out = {}
+    for name, fn in legs.items():
+        for _ in range(max(calls // 10, 1)):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            fn()
+        torch.cuda.synchronize()
+        out[name] = (time.perf_counter() - t0) * 1e6 / calls
+    ctx.close()
+    print(json.dumps(out))
+
+
+def call_cost(parent, rounds, calls, emit):
+    legs = [("this tree", ROOT)] + ([("parent", os.path.abspath(parent))] if parent else [])
+    res = {}
+    for r in range(rounds):
+        for name, pkg in (legs if r % 2 == 0 else legs[::-1]):  # (in turn, the other one first in every other round)
+            run = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "calls", "--repeats", str(calls)],
+                                 env=dict(os.environ, R2F_PROBE_PKG=pkg), capture_output=True, text=True, timeout=300)
+            if run.returncode != 0:
+                raise RuntimeError(f"{name}: exit {run.returncode}: {run.stderr[-2000:]}")
+            for method, us in json.loads(run.stdout.strip().splitlines()[-1]).items():
+                res.setdefault(method, {}).setdefault(name, []).append(us)
+    emit(f"host cost of a call: a 64 x 64 Bayer mosaic (one tile), `out` given; microseconds per call, wall clock around {calls} calls in a "
+         f"tight loop with a device synchronisation on either side; each leg in child processes of its own, {rounds} rounds in turn")
+    if not parent:
+        emit("  (no --parent checkout given: only this tree was run)")
+    for method, by_leg in res.items():
+        emit(f"  {method}")
+        for name, _ in legs:
+            xs = by_leg[name]
+            emit(f"    {name:<10s} {min(xs):7.2f} .. {max(xs):7.2f} us (median {statistics.median(xs):7.2f}, n = {len(xs)})")
+        if parent:
+            t, xs = statistics.median(by_leg["this tree"]), by_leg["parent"]
+            emit(f"    this tree's median / the parent's = {t / statistics.median(xs):.3f}; "
+                 f"{'inside' if min(xs) <= t <= max(xs) else 'OUTSIDE'} the parent's range over its rounds")
+    emit()
 
 
 def end_to_end(parent, rounds, repeats, emit):
@@ -275,14 +337,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--stream", action="store_true", help="the streamed mosaic's probe (profiles/r17_mosaic_stream_probe.txt)")
-    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--calls", action="store_true", help="the host cost of a call (profiles/r31_demosaic_call_cost.txt)")
+    ap.add_argument("--repeats", type=int, default=None, help="calls per case and round (default 5; --calls: 2000 per loop)")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit for leg (a)")
-    ap.add_argument("--child", default=None, choices=("rgb", "mosaic"))
+    ap.add_argument("--child", default=None, choices=("rgb", "mosaic", "calls"))
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 2000 if args.calls else 5
     if args.child:
-        return child(args.child, args.repeats)
+        return calls_child(args.repeats) if args.child == "calls" else child(args.child, args.repeats)
     import torch
 
     if not torch.cuda.is_available():
@@ -294,8 +359,13 @@ def main():
         lines.append(s)
 
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "r17_mosaic_stream_probe.txt" if args.stream else "r16_demosaic_probe.txt")
-    if args.stream:
+        name = "r31_demosaic_call_cost.txt" if args.calls else "r17_mosaic_stream_probe.txt" if args.stream else "r16_demosaic_probe.txt"
+        args.out = os.path.join(ROOT, "profiles", name)
+    if args.calls:
+        emit("What a demosaic call costs on the host, this tree against the parent commit (tools/demosaic_probe.py --calls)")
+        emit()
+        call_cost(args.parent, args.rounds, args.repeats, emit)
+    elif args.stream:
         emit("A Bayer mosaic streamed in row bands against the same call in one piece (tools/demosaic_probe.py --stream)")
         emit()
         stream_kernels(args.rounds, args.iters, emit)
