@@ -935,6 +935,7 @@ class HipContext:
             word = out[8 * c + 7]
             d["unrolled"] = (d["sym"] >> 1) & 0x7F  # R of the fully unrolled (2 R + 1)^2 direct form, 0: the entry list
             d["separable"] = (d["sym"] >> 8) & 1  # grain stencil only: two 1-D passes of 2 R + 1 taps
+            d["xpass_registers"] = (d["sym"] >> 9) & 1  # ... the one along x in registers as the noise is hashed (R <= 4)
             d["sym"] &= 1
             d["fft"] = word & 1
             dims = (word >> 1) & 0x1FFFFFFF

@@ -488,7 +488,9 @@ int r2f_stencil_stats(r2f_ctx* ctx, int which, int* out) {
                                                         : 0);
         // bit 8: the grain stencil runs as two 1-D passes (known once a tail launch has looked at the taps)
         const int sep = which == R2F_KERNEL_GRAIN && fr && ctx->grain_fixed_valid && ctx->grain_sep && ctx->opt.grain_sep;
-        o[0] = d.n_entries, o[1] = d.n_rowsteps, o[2] = d.n_phases, o[3] = d.sym | (fr << 1) | (sep << 8);
+        // bit 9: ... with the pass along x in registers (launch_tail: R <= kTailXRegMaxR unless grain_xpass_lds)
+        const int xreg = sep && fr <= kTailXRegMaxR && !ctx->opt.grain_xpass_lds;
+        o[0] = d.n_entries, o[1] = d.n_rowsteps, o[2] = d.n_phases, o[3] = d.sym | (fr << 1) | (sep << 8) | (xreg << 9);
         o[4] = d.kh, o[5] = d.kw, o[6] = set.built_q;
         o[7] = fft_eligible(ctx, set, c) ? 1 | (ctx->fft.last[which][c].dims << 1) | (ctx->fft.last[which][c].real << 30) : 0;
     }
@@ -608,6 +610,7 @@ static int run_tail(r2f_ctx* ctx, const r2f_params* p, const r2f_planes* density
         a.fixed_w = static_cast<const float*>(ctx->grain_fixed_w.p);
         // (monochrome noise with per-channel taps: the one noise plane cannot be filtered in place three ways -> 2-D form)
         a.sep = (a.fixed_r && ctx->opt.grain_sep && ctx->grain_sep && (!a.mono || ctx->grain_fixed_same)) ? 1 : 0;
+        a.xpass_lds = ctx->opt.grain_xpass_lds ? 1 : 0;
         memcpy(a.sep_u, ctx->grain_sep_u, sizeof a.sep_u);
         memcpy(a.sep_v, ctx->grain_sep_v, sizeof a.sep_v);
         if (tail_lds_bytes(a.gk, a.mono) > kMaxLds)

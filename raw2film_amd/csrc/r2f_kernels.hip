@@ -485,17 +485,34 @@ __global__ __launch_bounds__(256) void single_tap_kernel(const TapArgs a) {
 // FR = 0: the generic entry list, every tap column of every entry (run-time masks, i.e. branches, cost more than the
 // padding columns they skip in a stencil of two entries per row step).
 // SEP (with FR = R > 0): every channel's grain stencil is separable, K = u v^T to fp32 rounding (checked on the host; any
-// Gaussian-like kernel is): the noise planes are filtered along x IN PLACE (every thread first reads the inputs of its row
-// segments, barrier, then stores), then along y out of LDS -- 2 (2 R + 1) taps per pixel instead of (2 R + 1)^2.
-template <int FR, bool SEP = false>
+// Gaussian-like kernel is): the noise is filtered along x, then along y out of LDS -- 2 (2 R + 1) taps per pixel instead of
+// (2 R + 1)^2.  The pass along x takes one of two forms, which sum the same taps in the same order and so give the same bits:
+//   in registers (XREG; R <= kTailXRegMaxR): a lane hashes the four samples of one 4-column segment, takes the R samples on
+//     either side from the lanes next to it (DPP wave shifts, no LDS) and stores the FILTERED segment: planes of TH + 2 R rows x TW
+//     columns, one barrier;
+//   in LDS, in place (R > kTailXRegMaxR, or the option grain_xpass_lds): every thread hashes single samples into planes of
+//     pitch RS, barrier, reads the inputs of its row segments, barrier, stores, barrier.
+static_assert(kTailXRegMaxR <= 4, "a segment's taps must reach no further than the segment on either side");
+
+// neighbouring lanes' values inside a wave: lane l takes lane l - 1's (from_left) or lane l + 1's; lanes 0 / 63 get 0
+__device__ __forceinline__ float wave_from_left(float v) {
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x138 /* wave_shr:1 */, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float wave_from_right(float v) {
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x130 /* wave_shl:1 */, 0xf, 0xf, true));
+}
+
+template <int FR, bool SEP = false, bool XREG = false>
 __global__ __launch_bounds__(kTailBX* kTailBY) void tail_kernel(const TailArgs a) {
+    static_assert(!XREG || (SEP && FR >= 1 && FR <= kTailXRegMaxR), "the pass along x in registers: separable stencils of R <= 4");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NT = kTailBX * kTailBY, TW = 4 * kTailBX, TH = kTailQ * kTailBY, Q = kTailQ;
     const int tile_x0 = blockIdx.x * TW, tile_y0 = a.y0 + blockIdx.y * TH;
     const DevStencil g0 = a.gk[0];
-    const int RS = g0.RS;
+    const int RS = XREG ? TW : g0.RS;  // (TW: a lane's two rows of the pass along y then start 2 x 64 banks apart, conflict free)
     const int rows = TH + g0.kh - 1;
-    const int plane_sz = rows * RS + 16;  // + slack: the prefetch of the dummy entry reads past the last row
+    // + slack: the prefetch of the dummy entry reads past the last row (the register form holds output columns only, and no slack)
+    const int plane_sz = XREG ? (TH + 2 * FR) * TW : rows * RS + 16;
     const int cols_valid = TW + g0.kw - 1;
     const bool mono = a.mono != 0;
     const uint32_t seed = a.frame->seed;  // wave-uniform: one scalar load
@@ -523,9 +540,56 @@ __global__ __launch_bounds__(kTailBX* kTailBY) void tail_kernel(const TailArgs a
     // (row, column) of element idx advance with it: one division per thread, not one per element
     // Only the cols_valid columns that taps can reach are hashed (the padding columns up to RS are zeroed below): every lane
     // of a wave then does a hash, instead of the lanes that fall on padding idling through it.
+    if constexpr (XREG) {
+        // S6a + the pass along x in one.  The 4-column segments of the tile and its halo, s = -1 .. TW / 4 of rows 0 .. TH + 2 R - 1, are
+        // numbered row by row; a wave step takes 64 consecutive ones, so that segment e's neighbours e -+ 1 sit in lanes -+ 1.  Lanes 0
+        // and 63 have only one neighbour: they hash (for the lane beside them) and store nothing, and the next step starts on lane
+        // 63's segment again -- 62 segments of a step are new, about 4 % more hashes than samples.  Every lane of a wave runs every
+        // hash and every shift (a DPP read of an idle lane returns nothing): numbers past the ends are clamped, never branched on.
+        constexpr int R = FR > 0 ? FR : 1, SEGS = TW / 4 + 2, TOTAL = (TH + 2 * R) * SEGS, OWN = 62;
+        constexpr int STEPS = (TOTAL + OWN - 1) / OWN, NWAVES = NT / 64, MAXI = (STEPS + NWAVES - 1) / NWAVES;
+        static_assert(NT % 64 == 0 && TW % 4 == 0, "whole waves, whole segments");
+        const int lane = (int)threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+#pragma unroll
+        for (int i = 0; i < ((R2F_TAIL_EXP & 1) ? 0 : MAXI); ++i) {
+            const int k = wave + NWAVES * i;  // wave-uniform
+            if (k >= STEPS) break;
+            const int e_raw = OWN * k + lane - 1, e = clampi(e_raw, 0, TOTAL - 1);
+            const int rr = e / SEGS, s = e - rr * SEGS - 1;
+            const int sy = clampi(tile_y0 - g0.ay + rr, 0, a.H_global - 1);
+            float n[3][4];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const int sx = clampi(tile_x0 + 4 * s + p, 0, a.W - 1);
+                gaussian_noise((uint32_t)sx, (uint32_t)sy, seed, mono, n[0][p], n[1][p], n[2][p]);
+            }
+            const bool owner = lane >= 1 && lane <= OWN && e_raw < TOTAL && s >= 0 && s < TW / 4;
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) {
+                if (pl > 0 && mono) break;
+                const float* wv = a.sep_v[pl];  // compile-time plane index: the taps stay in SGPRs
+                float x[12];  // columns 4 s - 4 .. 4 s + 7; only 4 - R .. 7 + R are used
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    x[j] = j >= 4 - R ? wave_from_left(n[pl][j]) : 0.f;
+                    x[4 + j] = n[pl][j];
+                    x[8 + j] = j < R ? wave_from_right(n[pl][j]) : 0.f;
+                }
+                float o[4];
+#pragma unroll
+                for (int pp = 0; pp < 4; ++pp) {  // mirrored taps summed first (v is symmetric), outer taps to the centre
+                    float acc = wv[0] * (x[4 - R + pp] + x[4 - R + pp + 2 * R]);
+#pragma unroll
+                    for (int j = 1; j < R; ++j) acc = fmaf(wv[j], x[4 - R + pp + j] + x[4 - R + pp + 2 * R - j], acc);
+                    o[pp] = fmaf(wv[R], x[4 + pp], acc);
+                }
+                if (owner) *reinterpret_cast<float4v*>(smem + pl * plane_sz + rr * TW + 4 * s) = (float4v){o[0], o[1], o[2], o[3]};
+            }
+        }
+    }
     const int step_r = NT / cols_valid, step_c = NT - step_r * cols_valid;
     int r = (int)threadIdx.x / cols_valid, c = (int)threadIdx.x - r * cols_valid;
-    for (int idx = threadIdx.x; idx < ((R2F_TAIL_EXP & 1) ? 0 : rows * cols_valid); idx += NT, r += step_r, c += step_c) {
+    for (int idx = threadIdx.x; idx < ((XREG || (R2F_TAIL_EXP & 1)) ? 0 : rows * cols_valid); idx += NT, r += step_r, c += step_c) {
         if (c >= cols_valid) c -= cols_valid, ++r;
         float nr, ng, nb;
         const int sx = clampi(tile_x0 - g0.ax + c, 0, a.W - 1);
@@ -538,7 +602,7 @@ __global__ __launch_bounds__(kTailBX* kTailBY) void tail_kernel(const TailArgs a
             smem[2 * plane_sz + at] = nb;
         }
     }
-    {
+    if constexpr (!XREG) {  // (the register form stores every float of its planes, and nothing reads past them)
         const int padc = RS - cols_valid;  // < 16
         for (int idx = threadIdx.x; idx < rows * padc; idx += NT) {
             const int rr = idx / padc, at = rr * RS + cols_valid + (idx - rr * padc);
@@ -564,50 +628,52 @@ __global__ __launch_bounds__(kTailBX* kTailBY) void tail_kernel(const TailArgs a
         // 4 s .. 4 s + 3 of one row of one plane; its result goes to columns 4 s .. of that row (16-byte aligned).
         constexpr int R = FR > 0 ? FR : 1, AX = fixed_stencil_ax(R), O = AX - R, NB = (O + 2 * R + 4 + 3) / 4;
         constexpr int SEGS = TW / 4, PER = (TH + 2 * R) * SEGS, MAXI = (PER + NT - 1) / NT;
-        float4v held[3][MAXI];
+        if constexpr (!XREG) {  // (the register form stored filtered rows)
+            float4v held[3][MAXI];
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-            if (pl > 0 && mono) break;
-            const float* wv = a.sep_v[pl];  // compile-time plane index: the taps stay in SGPRs
+            for (int pl = 0; pl < 3; ++pl) {
+                if (pl > 0 && mono) break;
+                const float* wv = a.sep_v[pl];  // compile-time plane index: the taps stay in SGPRs
 #pragma unroll
-            for (int i = 0; i < MAXI; ++i) {
-                const int rem = (int)threadIdx.x + NT * i;
-                held[pl][i] = (float4v){0.f, 0.f, 0.f, 0.f};
-                if (rem < PER) {
-                    const int rr = rem / SEGS, sg = rem - rr * SEGS;
-                    const float* src = smem + pl * plane_sz + rr * RS + 4 * sg;
-                    float x[4 * NB];
+                for (int i = 0; i < MAXI; ++i) {
+                    const int rem = (int)threadIdx.x + NT * i;
+                    held[pl][i] = (float4v){0.f, 0.f, 0.f, 0.f};
+                    if (rem < PER) {
+                        const int rr = rem / SEGS, sg = rem - rr * SEGS;
+                        const float* src = smem + pl * plane_sz + rr * RS + 4 * sg;
+                        float x[4 * NB];
 #pragma unroll
-                    for (int b = 0; b < NB; ++b) {
-                        const float4v v = *reinterpret_cast<const float4v*>(src + 4 * b);
-                        x[4 * b] = v.x, x[4 * b + 1] = v.y, x[4 * b + 2] = v.z, x[4 * b + 3] = v.w;
+                        for (int b = 0; b < NB; ++b) {
+                            const float4v v = *reinterpret_cast<const float4v*>(src + 4 * b);
+                            x[4 * b] = v.x, x[4 * b + 1] = v.y, x[4 * b + 2] = v.z, x[4 * b + 3] = v.w;
+                        }
+                        float o[4];
+#pragma unroll
+                        for (int pp = 0; pp < 4; ++pp) {  // mirrored taps summed first (v is symmetric), outer taps to the centre
+                            float acc = wv[0] * (x[O + pp] + x[O + pp + 2 * R]);
+#pragma unroll
+                            for (int j = 1; j < R; ++j) acc = fmaf(wv[j], x[O + pp + j] + x[O + pp + 2 * R - j], acc);
+                            o[pp] = fmaf(wv[R], x[O + pp + R], acc);
+                        }
+                        held[pl][i] = (float4v){o[0], o[1], o[2], o[3]};
                     }
-                    float o[4];
-#pragma unroll
-                    for (int pp = 0; pp < 4; ++pp) {  // mirrored taps summed first (v is symmetric), outer taps to the centre
-                        float acc = wv[0] * (x[O + pp] + x[O + pp + 2 * R]);
-#pragma unroll
-                        for (int j = 1; j < R; ++j) acc = fmaf(wv[j], x[O + pp + j] + x[O + pp + 2 * R - j], acc);
-                        o[pp] = fmaf(wv[R], x[O + pp + R], acc);
-                    }
-                    held[pl][i] = (float4v){o[0], o[1], o[2], o[3]};
                 }
             }
-        }
-        __syncthreads();
+            __syncthreads();
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-            if (pl > 0 && mono) break;
+            for (int pl = 0; pl < 3; ++pl) {
+                if (pl > 0 && mono) break;
 #pragma unroll
-            for (int i = 0; i < MAXI; ++i) {
-                const int rem = (int)threadIdx.x + NT * i;
-                if (rem < PER) {
-                    const int rr = rem / SEGS, sg = rem - rr * SEGS;
-                    *reinterpret_cast<float4v*>(smem + pl * plane_sz + rr * RS + 4 * sg) = held[pl][i];
+                for (int i = 0; i < MAXI; ++i) {
+                    const int rem = (int)threadIdx.x + NT * i;
+                    if (rem < PER) {
+                        const int rr = rem / SEGS, sg = rem - rr * SEGS;
+                        *reinterpret_cast<float4v*>(smem + pl * plane_sz + rr * RS + 4 * sg) = held[pl][i];
+                    }
                 }
             }
+            __syncthreads();
         }
-        __syncthreads();
         // ---- pass along y: output row y of the tile reads rows y .. y + 2 R of the filtered plane
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -824,12 +890,13 @@ size_t stencil_lds_bytes(const StencilVariant& v, const DevStencil* st, int ncha
 }
 
 // noise planes, then (when they fit next to them in half a CU's LDS) the grain LUT's cells
-size_t tail_plane_floats(const DevStencil* gk, int mono) {
-    const size_t plane = (size_t)gk[0].RS * (size_t)gk[0].max_lds_rows + 16;
+// (xreg_r = R: the separable form with the pass along x in registers, whose planes hold the tile's columns only and no slack)
+size_t tail_plane_floats(const DevStencil* gk, int mono, int xreg_r) {
+    const size_t plane = xreg_r ? (size_t)(kTailQ * kTailBY + 2 * xreg_r) * (size_t)(4 * kTailBX) : (size_t)gk[0].RS * (size_t)gk[0].max_lds_rows + 16;
     return (plane * (mono ? 1 : 3) + 3) / 4 * 4;
 }
-size_t tail_lds_bytes(const DevStencil* gk, int mono, int cells_in_lds, int grain_m) {
-    return tail_plane_floats(gk, mono) * sizeof(float) + (cells_in_lds ? (size_t)3 * (grain_m - 1) * sizeof(float4) : 0);
+size_t tail_lds_bytes(const DevStencil* gk, int mono, int cells_in_lds, int grain_m, int xreg_r) {
+    return tail_plane_floats(gk, mono, xreg_r) * sizeof(float) + (cells_in_lds ? (size_t)3 * (grain_m - 1) * sizeof(float4) : 0);
 }
 
 // Every instantiation of the two templated kernel families, listed ONCE: init_kernel_attributes raises the dynamic-LDS limit of every
@@ -850,6 +917,10 @@ template <bool SEP, int... R>
 constexpr std::array<TailFn, sizeof...(R)> tail_row(std::integer_sequence<int, R...>) {
     return {{tail_kernel<R, SEP && (R > 0)>...}};  // (R = 0 has no separable form: the entry list either way)
 }
+template <int... R>
+constexpr std::array<TailFn, sizeof...(R)> tail_xreg_row(std::integer_sequence<int, R...>) {
+    return {{tail_kernel<R + 1, true, true>...}};  // R = 1 .. kTailXRegMaxR
+}
 template <int N>
 using UpTo = std::make_integer_sequence<int, N>;
 // [EPI][R]: variant 0's tile; R = 0 is its entry-list form
@@ -860,6 +931,8 @@ constexpr std::array<std::array<StencilFn, kNumStencilVariants>, 2> kStencilGene
     {stencil_generic_row<0>(UpTo<kNumStencilVariants>{}), stencil_generic_row<1>(UpTo<kNumStencilVariants>{})}};
 // [SEP][R]
 constexpr std::array<std::array<TailFn, kTailFixedN>, 2> kTail = {{tail_row<false>(UpTo<kTailFixedN>{}), tail_row<true>(UpTo<kTailFixedN>{})}};
+// [R - 1]: the separable form of R <= kTailXRegMaxR with the pass along x in registers (kTail[1][R] has it in LDS)
+constexpr std::array<std::array<TailFn, kTailXRegMaxR>, 1> kTailXReg = {{tail_xreg_row(UpTo<kTailXRegMaxR>{})}};
 
 hipError_t init_kernel_attributes() {
     auto raise = [](const void* k) { return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds); };
@@ -874,6 +947,7 @@ hipError_t init_kernel_attributes() {
     hipError_t e = raise_all(kStencilFixed);
     if (e == hipSuccess) e = raise_all(kStencilGeneric);
     if (e == hipSuccess) e = raise_all(kTail);
+    if (e == hipSuccess) e = raise_all(kTailXReg);
     if (e == hipSuccess) e = raise(reinterpret_cast<const void*>(front_kernel<true>));
     return e;
 }
@@ -934,12 +1008,14 @@ hipError_t launch_tail(const TailArgs& a, hipStream_t s) {
     const int TW = 4 * kTailBX, TH = kTailQ * kTailBY;
     dim3 block(kTailBX * kTailBY), grid((a.W + TW - 1) / TW, (a.y1 - a.y0 + TH - 1) / TH);
     TailArgs b = a;
-    b.cells_off = (int)tail_plane_floats(a.gk, a.mono);
-    b.cells_in_lds = tail_lds_bytes(a.gk, a.mono, 1, a.grain_lut.m) <= 80 * 1024 ? 1 : 0;  // keep two workgroups per CU
-    const size_t lds = tail_lds_bytes(a.gk, a.mono, b.cells_in_lds, a.grain_lut.m);
     // small square mirror-symmetric stencils take the unrolled form, separable ones two 1-D passes
     const int r = a.fixed_r > 0 && a.fixed_r < kTailFixedN ? a.fixed_r : 0;
-    launch_k(kTail[a.sep ? 1 : 0][r], grid, block, lds, s, b);
+    const bool x_in_reach = a.sep && r >= 1 && r <= kTailXRegMaxR;  // the pass along x can run in registers
+    const int xreg_r = x_in_reach && !a.xpass_lds ? r : 0;
+    b.cells_off = (int)tail_plane_floats(a.gk, a.mono, xreg_r);
+    b.cells_in_lds = tail_lds_bytes(a.gk, a.mono, 1, a.grain_lut.m, xreg_r) <= 80 * 1024 ? 1 : 0;  // keep two workgroups per CU
+    const size_t lds = tail_lds_bytes(a.gk, a.mono, b.cells_in_lds, a.grain_lut.m, xreg_r);
+    launch_k(xreg_r ? kTailXReg[0][r - 1] : kTail[a.sep ? 1 : 0][r], grid, block, lds, s, b);
     return take_launch_status();
 }
 

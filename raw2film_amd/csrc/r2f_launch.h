@@ -156,7 +156,8 @@ struct TailArgs {
     const float* fixed_w;
     // sep = 1 (with fixed_r = R): every channel's stencil is u v^T to fp32 rounding, v mirror symmetric: two 1-D passes.
     // sep_u[c][i], i <= 2 R: taps along y; sep_v[c][j], j <= R: the left half of the taps along x
-    int sep;
+    // xpass_lds = 1: the pass along x stays in LDS where R would allow it in registers (the option grain_xpass_lds)
+    int sep, xpass_lds;
     float sep_u[3][19], sep_v[3][10];
 };
 
@@ -242,11 +243,12 @@ extern const StencilVariant kStencilVariants[kNumStencilVariants];
 #ifndef R2F_TAIL_Q
 #define R2F_TAIL_Q 2
 #endif
+constexpr int kTailXRegMaxR = 4;  // separable grain stencils up to this radius run their pass along x in registers (tail_kernel)
 constexpr int kTailBX = R2F_TAIL_BX, kTailBY = R2F_TAIL_BY, kTailQ = R2F_TAIL_Q;  // grain/tail tile 64 x 64, 512 threads
 constexpr size_t kMaxLds = 160 * 1024;
 
 size_t stencil_lds_bytes(const StencilVariant& v, const DevStencil* st, int nchan);
-size_t tail_lds_bytes(const DevStencil* gk, int mono, int cells_in_lds = 0, int grain_m = 2);
+size_t tail_lds_bytes(const DevStencil* gk, int mono, int cells_in_lds = 0, int grain_m = 2, int xreg_r = 0);
 
 hipError_t init_kernel_attributes();
 hipError_t launch_front(const FrontArgs& a, hipStream_t s);

@@ -590,6 +590,7 @@ const OptionRow kOptions[] = {
     {"grain_fixed", &Options::grain_fixed, K::Switch, 0, 0, {}, nullptr},
     {"front_fast", &Options::front_fast, K::Switch, 0, 0, {}, nullptr},
     {"grain_separable", &Options::grain_sep, K::Switch, 0, 0, {}, nullptr},
+    {"grain_xpass_lds", &Options::grain_xpass_lds, K::Switch, 0, 0, {}, nullptr},
     {"front_blocks_per_cu", &Options::front_blocks, K::Range, 1, 64, {}, "front_blocks_per_cu must be in [1, 64]"},
     {"stencil_fft_window_rows", &Options::fft_window_rows, K::OneOf, 3, 0, {0, 256, 512}, "stencil_fft_window_rows must be 0, 256 or 512"},
     {"stencil_fft_min_taps", &Options::fft_min_taps, K::Raw, 0, 0, {}, nullptr},

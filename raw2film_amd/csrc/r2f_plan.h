@@ -173,6 +173,7 @@ struct Options {
     int sym = 1;      // use the mirror-symmetric entry form when a channel's taps allow it
     int grain_fixed = 1;  // 0: always the generic entry list (A/B)
     int grain_sep = 1;    // 0: never take the separable form (A/B)
+    int grain_xpass_lds = 0;  // 1: the separable form's pass along x through LDS at every R (A/B; 0: in registers up to R = 4)
     int stencil_fixed = 1;
     int front_fast = 1;    // the fused LUT-only pass may take the specialised kernel (r2f_front.hip); 0 = always the generic one (A/B)
     int front_blocks = 6;  // front kernel with the curve in LDS: workgroups per CU in its grid (3 are resident at 48 KB each)
